@@ -1,7 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- Mrays/s of the eye pass on BASELINE.json's configurations.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5] [--scaling weak|strong]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5] [--scaling weak|strong] [--full]
+                  [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps, writes the outputs if --dump-outputs is given and prints the JSON line
+(headline value, ms_per_step and the roofline figures of the timed launches).  --full adds everything that takes runs of
+its own: the CPU baselines (cpu_baseline, cpu_baseline_all_cores, gpu_over_cpu) and, for c2 at N = 1, the secondary
+full-size frames of the other configurations (other_configs).
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned, as .npy files:
+  frame.npy           float32 [rows, W, 3]: the framebuffer (N > 1: the gathered frame).  Where the whole buffer exceeds
+                      48 MB, a fixed sample of its rows (seed 12345, sorted) is written instead, and
+  frame_rows.npy      float64 [rows]: the buffer rows frame.npy holds (written in both cases).
+  counts_per_step.npy float64 [2]: rays and hitpoints of one timed step (counter totals of the timed steps / K).
+The inputs (scene, camera, seed) are fixed, so two builds run with the same arguments can be compared file by file.
 
 N > 1 needs one process per GPU.  Either an external launcher starts them (the driver's
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`: WORLD_SIZE/RANK/LOCAL_RANK are then set), or
@@ -35,10 +47,11 @@ The JSON line carries, besides the contract's fields:
                  stated result.  `traffic` is null in the live line: PMC counters cannot be read from
                  inside the process; `traffic_from_profile` / `valu_from_profile` REPLAY the committed rocprofv3 --pmc
                  passes of this same command (profiles/) and say so.
-  cpu_baseline : the compiled REFERENCE (oracle/_ref, unmodified main.cpp trace(); `kind` "reference") when its prebuilt
+  cpu_baseline : --full only.  The compiled REFERENCE (oracle/_ref, unmodified main.cpp trace(); `kind` "reference") when its prebuilt
                  library travelled with the repo -- it is git-ignored and only exists where __graft_entry__.build() ran
                  with /root/reference present -- else our CPU oracle ("port"); `ref_library_found` records which.
                  1 thread like the reference's serial HitPointPass, on a bounded sample of the same workload.
+  other_configs: --full only (c2, N = 1).  Single frames of configs[2..4] at full size and the reference's main() end to end.
   --rehearse   : no GPU: the kernel launch is replaced by a closed-form row pattern so that launcher, rendezvous, stripe
                  mapping, gather and the JSON line can be exercised on CPU with gloo (tests/test_bench_launch.py).
 """
@@ -361,12 +374,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--config", choices=["c2", "c4", "c5"], default="c2")
     ap.add_argument("--scaling", choices=["weak", "strong"], default=None, help="c2 only (c4 is strong, c5 weak by definition)")
-    ap.add_argument("--cpu-spp", type=int, default=None, help="spp of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--cpu-spp", type=int, default=None, help="--full: spp of the CPU baseline sample (0 = skip)")
     ap.add_argument("--stripe-rows", type=int, default=None)
     ap.add_argument("--spp", type=int, default=None, help="override the configuration's spp (marks the line as NOT the named config)")
     ap.add_argument("--check", action="store_true", help="verify a crop of the frame against the oracle (c2, N = 1)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the secondary single-frame measurements")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the secondary single-frame measurements")
     ap.add_argument("--rehearse", action="store_true", help="no GPU: pattern instead of the kernel, gloo (control path only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baselines and (c2, N = 1) the secondary single-frame measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's framebuffer and counts as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -495,6 +512,10 @@ def main():
     kern_ms = sum(a.elapsed_time(b) for a, b in kernel_events) / max(1, len(kernel_events)) if kernel_events else None
 
     if rank == 0:
+        if args.dump_outputs:
+            if frame is None:  # --steps 0: no timed step computed anything
+                raise SystemExit("--dump-outputs needs at least one timed step")
+            dump_outputs(args.dump_outputs, frame, cnt, steps)
         rays_per_step = total_rays / max(1, steps)
         value = total_rays / dt / 1e6
         line = {
@@ -550,7 +571,7 @@ def main():
                                     "source": valu_prof["source"] + "; time = this run's HIP events"}
             line["roofline_valu"] = rv
             cpu_spp = args.cpu_spp
-            if cpu_spp is None or cpu_spp > 0:
+            if args.full and (cpu_spp is None or cpu_spp > 0):
                 with stdout_to_stderr():
                     base = cpu_baseline(cfg, cpu_spp)
                 line["cpu_baseline"] = base
@@ -561,7 +582,7 @@ def main():
                             line["cpu_baseline_all_cores"] = cpu_baseline(cfg, cpu_spp, threads=os.cpu_count() or 1)
                     except Exception as e:  # pragma: no cover
                         line["cpu_baseline_all_cores"] = {"error": str(e)}
-            if n == 1 and cfg["name"] == "c2" and not args.no_other_configs:
+            if args.full and n == 1 and cfg["name"] == "c2" and not args.no_other_configs:
                 try:
                     with stdout_to_stderr():
                         line["other_configs"] = other_configs(dev_index)
@@ -581,6 +602,27 @@ def main():
     if n > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_FRAME_BYTES = 48 << 20  # frame.npy's share of the 64 MB --dump-outputs budget
+
+
+def dump_outputs(path, frame, cnt, steps):
+    """--dump-outputs: the last timed step's framebuffer (a fixed, seeded sample of its rows where it is larger than
+    DUMP_FRAME_BYTES) and the rays / hitpoints of one step, as float32 / float64 .npy files under `path`."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    rows, W = frame.shape[0], frame.shape[1]
+    if frame.numel() * 4 <= DUMP_FRAME_BYTES:
+        idx = np.arange(rows)
+    else:
+        k = DUMP_FRAME_BYTES // (W * 3 * 4)
+        idx = np.sort(np.random.default_rng(SEED).choice(rows, size=k, replace=False))
+        frame = frame.index_select(0, torch.as_tensor(idx, device=frame.device))
+    np.save(os.path.join(path, "frame.npy"), frame.float().cpu().numpy())
+    np.save(os.path.join(path, "frame_rows.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "counts_per_step.npy"), cnt[:2].cpu().numpy().astype(np.float64) / max(1, steps))
 
 
 def _rehearsal_frame_ok(frame, cfg, n):

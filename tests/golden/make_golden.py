@@ -5,6 +5,7 @@ HIP path) to the reference everywhere else.
 
     python tests/golden/make_golden.py            # everything
     python tests/golden/make_golden.py loader t1  # (internal) one reference file-load per process, quirk Q9
+    python tests/golden/make_golden.py oracle_vs_ref  # only oracle_vs_ref.npz (tests/test_oracle_vs_ref.py)
 
 Contents of each trace fixture: acc_sum [H,W,3] f64 (sum of hp.f per pixel, emission order), nhit [H,W],
 nrays, and the emission-ordered hitpoint stream hp [n,9] = f, pos, normal with hp_pix / hp_smp.
@@ -83,6 +84,67 @@ def tonemap_input():
                            np.full((1, 31, 3), 50.0), np.linspace(0, 8, 3 * 31 * 60).reshape(60, 31, 3)])
 
 
+def random_sphere_scene(seed):
+    """tests/test_oracle_vs_ref.py: the walls plus five random spheres (diffuse, mirror or glass); 80x60, spp 3, depth 5."""
+    rng = np.random.default_rng(seed)
+    objs = scenes.wall_spheres()
+    for _ in range(5):
+        c = (rng.uniform(-15, 15), rng.uniform(-18, 10), rng.uniform(20, 38))
+        kind = rng.integers(0, 3)
+        refl, transp = [(0, 0), (0.8, 0), (0.8, 0.5)][kind]
+        objs.append(scenes.Sphere(c, rng.uniform(2, 6), tuple(rng.uniform(0.2, 1, 3)), refl, transp))
+    return objs
+
+
+def procedural_glass_mesh_scene():
+    """tests/test_oracle_vs_ref.py: a procedural glass mesh over the chessboard planes; 64x64, spp 2, depth 5."""
+    tris = scenes.procedural_mesh(24, 12, (0, -8, 30), 7.0)
+    m = TriangleMesh.from_triangles(tris, (1, 1, 1), 0.8, 0.5)
+    return scenes.planes(scenes.chessboard_texture(False)) + [m]
+
+
+def lens_probe():
+    """tests/test_oracle_vs_ref.py: (seed, pix, smp, radius) of the lens sampler comparison."""
+    return 99, np.arange(1000, dtype=np.int64) * 7919, (np.arange(1000) % 64).astype(np.int32), 1.5
+
+
+def bezier_probe():
+    """tests/test_oracle_vs_ref.py: 600 keyed rays at the vase (org, dir, keys)."""
+    rng = np.random.default_rng(77)
+    n = 600
+    org = np.tile(np.array([0, 0, -10.0]), (n, 1)) + rng.normal(size=(n, 3))
+    tgt = np.array([15, -10.1, 35.0]) + (rng.random((n, 3)) - 0.5) * np.array([10, 22, 10])
+    d = tgt - org
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    keys = rng.integers(0, 2 ** 63, n, dtype=np.uint64)
+    return org, d, keys
+
+
+def array_digest(a):
+    """sha256 of a float64 array's shape and values: equal digests <=> np.array_equal, with -0.0 counted as 0.0 (`+ 0.0`
+    makes it +0.0) and NaN, which array_equal never matches, refused."""
+    a = np.ascontiguousarray(a, np.float64) + 0.0
+    assert not np.isnan(a).any()
+    return hashlib.sha256(repr(a.shape).encode() + a.tobytes()).hexdigest()
+
+
+def write_oracle_vs_ref(ref):
+    """oracle_vs_ref.npz: the reference's answers to the cases of tests/test_oracle_vs_ref.py.  The frame sums and hitpoint
+    streams (about 1 MB each, incompressible) are stored as their length and array_digest(); the rest in full."""
+    g = {}
+    for seed in (1, 2, 3):
+        r = BackendScene(ref, random_sphere_scene(seed)).trace_grid(scenes.cam_dof(), 80, 60, 3, 5, seed=seed, capture=True)
+        g.update({"spheres%d_nrays" % seed: np.int64(r["nrays"]), "spheres%d_nhp" % seed: np.int64(len(r["hp"])),
+                  "spheres%d_acc_sum_sha256" % seed: np.str_(array_digest(r["acc_sum"])),
+                  "spheres%d_hp_sha256" % seed: np.str_(array_digest(r["hp"]))})
+    r = BackendScene(ref, procedural_glass_mesh_scene()).trace_grid(scenes.cam_dof(), 64, 64, 2, 5, capture=True)
+    g.update(mesh_nrays=np.int64(r["nrays"]), mesh_nhp=np.int64(len(r["hp"])), mesh_hp_sha256=np.str_(array_digest(r["hp"])))
+    g["lens_out"] = lens_samples(ref, *lens_probe())
+    h, l, n = BackendScene(ref, [scenes.vase_bezier()]).intersect_batch(0, *bezier_probe())
+    g.update(bez_hit=h, bez_len=l, bez_n=n)
+    np.savez_compressed(os.path.join(HERE, "oracle_vs_ref.npz"), **g)
+
+
 def fingerprint(nodes, leaf):
     sizes = nodes[:, 2]
     leaves = sizes[sizes < 10]
@@ -153,6 +215,8 @@ def main():
     if len(sys.argv) > 2 and sys.argv[1] == "loader":
         return loader_child(sys.argv[2])
     ref = Backend("ref")
+    if len(sys.argv) > 1 and sys.argv[1] == "oracle_vs_ref":
+        return write_oracle_vs_ref(ref)
     meta = {}
     # `only NAME...`: (re)generate just these trace fixtures and merge their entries into trace_meta.json
     only = set(sys.argv[2:]) if len(sys.argv) > 2 and sys.argv[1] == "only" else None
@@ -259,6 +323,7 @@ def main():
     # ---- tone map + flip (row f2): the reference's own gammaCorr and PNG pixel loop ----
     timg = tonemap_input()
     np.savez_compressed(os.path.join(HERE, "tonemap.npz"), image=timg, rgb8=ref.tonemap(timg))
+    write_oracle_vs_ref(ref)
     # ---- loaders: one process per file ----
     write_test_meshes()
     for name in LOADER_CASES:

@@ -42,6 +42,28 @@ def test_self_launch_rehearsal(args, n, W, H, rows, scaling):
         assert k in line
 
 
+@pytest.mark.parametrize("config,rows,sampled", [("c2", 1080, False), ("c4", 4096, True)])
+def test_dump_outputs_rehearsal(tmp_path, config, rows, sampled):
+    """--dump-outputs writes the last timed step's frame (a fixed sample of its rows where it exceeds 48 MB), the rows it holds
+    and the counts of one step; the rehearsal frame carries each row's index, so a mis-sampled row shows."""
+    import numpy as np
+    dirs = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        _run(["--rehearse", "--config", config, "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)])
+        dirs.append(d)
+    got = {f: np.load(dirs[0] / f) for f in ("frame.npy", "frame_rows.npy", "counts_per_step.npy")}
+    assert got["frame.npy"].dtype == np.float32 and got["frame_rows.npy"].dtype == np.float64
+    assert got["counts_per_step.npy"].dtype == np.float64 and got["counts_per_step.npy"].shape == (2,)
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    idx = got["frame_rows.npy"]
+    assert (len(idx) < rows) == sampled and np.all(np.diff(idx) > 0) and idx[-1] < rows
+    assert np.array_equal(got["frame.npy"][:, 0, 0], idx) and np.array_equal(got["frame.npy"][:, -1, 2], idx)
+    assert got["counts_per_step.npy"][0] == rows * got["frame.npy"].shape[1]
+    for f, a in got.items():  # same arguments, same outputs
+        assert np.array_equal(np.load(dirs[1] / f), a)
+
+
 def test_weak_dims_keep_view_and_work():
     sys.path.insert(0, ROOT)
     import bench

@@ -5,9 +5,9 @@ set -x
 O=gpurun_out/r03
 mkdir -p $O
 export TMPDIR=/tmp
-python bench.py > $O/bench.json 2> $O/bench.err
-python bench.py --config c4 > $O/bench_c4.json 2>> $O/bench.err
-python bench.py --config c5 > $O/bench_c5.json 2>> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
+python bench.py --full --config c4 > $O/bench_c4.json 2>> $O/bench.err
+python bench.py --full --config c5 > $O/bench_c5.json 2>> $O/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c2 -o s -- python3 bench.py --no-other-configs --cpu-spp 0 > $O/bench_under_rocprof.json 2> $O/stats_c2.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c3 -o s -- python3 tools/one_frame.py c3 64 > $O/stats_c3.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c4 -o s -- python3 tools/one_frame.py c4 256 > $O/stats_c4.log 2>&1
