@@ -20,6 +20,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <map>
+#include <mutex>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -625,15 +627,105 @@ int cgrt_scene_tree_dump(const cgrt_scene *s, int t, int32_t *node_lr_size, int3
     return CGRT_OK;
 }
 
-// A launch whose dynamic LDS exceeds the default allowance asks for it first (a CU has 160 KiB; scenes with hundreds of
-// top-level objects).  The attribute is per kernel; setting it again is harmless.
-#define BIG_LDS(kernel, bytes)                                                                                                 \
+// ---- LDS of a launch ----
+// A workgroup may use at most a CU's LDS (MI355X: 160 KiB): the kernel's static __shared__ bytes plus the dynamic bytes of
+// the launch.  Each launch family sizes its dynamic bytes in one place below and passes them through BIG_LDS, which refuses
+// a launch that would not fit (CGRT_ERR_LIMIT, naming the launch and the bytes) and asks for more than the default 64 KiB
+// where needed.  The static bytes are the compiler's (hipFuncGetAttributes); the static_asserts use kStaticLdsAllowance.
+static constexpr size_t kStaticLdsAllowance = 512;  // the eye kernels have 336 B (ROCm 7.2): wg_cnt, tile_entry, tl_rays, ...
+static constexpr size_t kWideStackLds = (size_t)kThreads * kWideLdsDepth * sizeof(uint2);
+static constexpr size_t kNodeCacheLds = (size_t)kNodeCache * sizeof(NodeRec);
+// LDS of the most general variant (Hitpoint capture, the eye pass's SPILL_GEN) besides its object list: pending-ray levels,
+// one BezLds per wave, the cached tree
+static size_t general_other_lds(const DeviceScene &d) {
+    return kStackBytes + (kThreads / 64) * sizeof(BezLds) + (d.cached_tree >= 0 ? (size_t)d.cached_nodes * sizeof(NodeRec) : 0);
+}
+// Every launch that stages kLdsObjsMax objects fits beside its other LDS (the general variant lowers its count instead):
+// the eye pass without SPILL (glass: pending-ray levels; else the wide walk's stack; and the node cache), ...
+static_assert(kLdsObjsMax * sizeof(ObjRec) + std::max(kStackBytes, kWideStackLds) + kNodeCacheLds + kStaticLdsAllowance <= kLdsBytes,
+              "eye pass, 256-thread variants");
+// ... the one-wave Bezier variants, the sphere-only SPILL variant, the light variants, ...
+static_assert(kLdsObjsMax * sizeof(ObjRec) + TileGeom<64>::stack_bytes + sizeof(BezLds) + kNodeCacheLds + kStaticLdsAllowance <= kLdsBytes,
+              "eye pass, one-wave Bezier variants");
+static_assert((kLdsObjsMax + kThreads / 64) * sizeof(ObjRec) + kStackBytes + kStaticLdsAllowance <= kLdsBytes, "eye pass, SPILL_SPH");
+static_assert(kLdsObjsMax * sizeof(ObjRec) + kNodeCacheLds + kWideStackLds + kStaticLdsAllowance <= kLdsBytes, "light variants");
+// ... primary_walk_kernel (all objects staged when it finishes units; it runs only when none is spilled), the photon launches
+static_assert(kLdsObjsMax * sizeof(ObjRec) + kWideStackLds + kStaticLdsAllowance <= kLdsBytes, "primary_walk_kernel");
+static_assert((kLdsObjsMax + kThreads / 64) * sizeof(ObjRec) + (kThreads / 64) * sizeof(BezLds) + kStaticLdsAllowance <= kLdsBytes,
+              "photon_trace_kernel");
+// The general variant keeps at least 600 objects resident whatever the scene.
+static_assert((kLdsBytes - kStackBytes - (kThreads / 64) * sizeof(BezLds) - kNodeCacheLds - kStaticLdsAllowance) / sizeof(ObjRec) -
+                      kThreads / 64 >= 600,
+              "general variant: resident objects");
+
+static size_t device_lds_bytes(int device) {
+    static std::mutex mu;
+    static std::map<int, size_t> known;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = known.find(device);
+    if (it != known.end()) return it->second;
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess || v <= 0) {
+        (void)hipGetLastError();
+        v = (int)kLdsBytes;
+    }
+    return known[device] = (size_t)v;
+}
+static size_t kernel_static_lds(const void *fn) {
+    static std::mutex mu;
+    static std::map<const void *, size_t> known;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = known.find(fn);
+    if (it != known.end()) return it->second;
+    hipFuncAttributes a{};
+    size_t b = kStaticLdsAllowance;
+    if (hipFuncGetAttributes(&a, fn) == hipSuccess) b = a.sharedSizeBytes;
+    else (void)hipGetLastError();
+    return known[fn] = b;
+}
+// Objects a launch may keep resident beside `other` bytes of LDS in a kernel with `static_bytes` of its own: the scene's
+// n_lds when the whole launch fits, else as many as fit beside one staging record per wave (the SPILL variant then reads
+// the rest from `objs`).
+static int resident_objs(const DeviceScene &d, size_t other, size_t static_bytes, size_t limit, int waves) {
+    if (obj_list_lds(d, waves) + other + static_bytes <= limit) return d.n_lds;
+    const long long room = (long long)limit - (long long)(other + static_bytes);
+    const long long r = room / (long long)sizeof(ObjRec) - waves;
+    return (int)std::max(0ll, std::min(r, (long long)d.n_lds));
+}
+// The launch's copy of the scene with `resident` objects in LDS.  A run of planes tested as a group (plane_run) is read from
+// the LDS list, so it ends inside it: a shorter run is the same test over fewer planes.
+static DeviceScene with_resident(const DeviceScene &d, int resident) {
+    DeviceScene c = d;
+    c.n_lds = resident;
+    if (c.prun_end > resident) c.prun_end = resident;
+    if (c.prun_end - c.prun_begin < 3) c.prun_begin = c.prun_end = 0;
+    return c;
+}
+static int lds_check(const void *fn, size_t dyn, int device, const char *what) {
+    const size_t st = kernel_static_lds(fn), lim = device_lds_bytes(device);
+    if (st + dyn > lim)
+        return fail(CGRT_ERR_LIMIT, std::string(what) + ": needs " + std::to_string(dyn) + " B of dynamic LDS + " + std::to_string(st) +
+                                        " B static, more than the " + std::to_string(lim) + " B a workgroup may use");
+    if (dyn > ((size_t)64 << 10) &&
+        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess)
+        (void)hipGetLastError();  // not needed / not supported by this runtime: the launch itself will tell
+    return CGRT_OK;
+}
+// Checks a launch's LDS (returns from the enclosing function if it does not fit) and asks for more than 64 KiB where needed.
+// The attribute is per kernel; setting it again is harmless.
+#define BIG_LDS(kernel, bytes, what)                                                                                          \
     do {                                                                                                                      \
-        if ((bytes) > ((size_t)64 << 10)) {                                                                                    \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(&kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)) != hipSuccess) \
-                (void)hipGetLastError(); /* not needed / not supported by this runtime: the launch itself will tell */          \
-        }                                                                                                                     \
+        if (const int lds_rc_ = lds_check(reinterpret_cast<const void *>(&kernel), (bytes), s->device, (what))) return lds_rc_; \
     } while (0)
+
+// Objects the most general variant keeps resident for this scene: the Hitpoint capture (hps) or the eye pass's SPILL_GEN.
+// Below the scene's n_lds when the list would not fit beside the variant's other LDS; the launch then runs the SPILL form.
+static int general_resident(const cgrt_scene *s, bool dof, bool hps) {
+#define GENERAL(D, H) reinterpret_cast<const void *>(&trace_grid_kernel<true, true, D, true, false, false, H, 256, true>)
+    const void *k = hps ? (dof ? GENERAL(true, true) : GENERAL(false, true)) : (dof ? GENERAL(true, false) : GENERAL(false, false));
+#undef GENERAL
+    return resident_objs(s->dev, general_other_lds(s->dev), kernel_static_lds(k), device_lds_bytes(s->device), kThreads / 64);
+}
 
 // Which instantiation of trace_grid_kernel a launch uses (chosen from the scene's materials and the camera).
 struct GridVariant {
@@ -679,6 +771,13 @@ int cgrt_trace_grid_variant(const cgrt_scene *s, const cgrt_camera *cam, const c
     if (rc) return rc;
     if (!name || cap == 0) return fail(CGRT_ERR_INVALID, "null name buffer");
     const GridVariant v = grid_variant(s, cam, grid);
+    if (grid->flags & CGRT_GRID_HITPOINTS) {  // the Hitpoint capture's launch
+        ON_DEVICE(s->device);
+        const bool spill = s->dev.n_objs > general_resident(s, v.dof, true);
+        std::snprintf(name, cap, "trace_grid_kernel<TREES=1,BEZ=1,DOF=%d,GLASS=1,SPH=0,STATS=0,HPS=1,NT=256%s>", (int)v.dof,
+                      spill ? ",SPILL=1" : "");
+        return CGRT_OK;
+    }
     if (s->dev.n_objs > s->dev.n_lds) {
         if (s->dev.all_spheres)
             std::snprintf(name, cap, "trace_grid_kernel<TREES=0,BEZ=0,DOF=%d,GLASS=%d,SPH=1,STATS=0,HPS=0,NT=256,SPILL=1>", (int)v.dof, (int)v.glass);
@@ -863,12 +962,12 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     if (trees && !glass && !bez && s->dev.has_wide) lds += (size_t)kThreads * kWideLdsDepth * sizeof(uint2);  // wide walk's stack
     static const int env_lds_pad = [] { const char *e = std::getenv("CGRT_LDS_PAD"); return e ? std::atoi(e) : 0; }();
     lds += (size_t)env_lds_pad;
-    auto launch_mode = [&](auto sched_tag, const GridParams &gp, dim3 gd, float *rgb_, uint32_t *nhit_, unsigned long long *cnt_) {
+    auto launch_mode = [&](auto sched_tag, const GridParams &gp, dim3 gd, float *rgb_, uint32_t *nhit_, unsigned long long *cnt_) -> int {
         constexpr bool SCHED = decltype(sched_tag)::value;
 #define LAUNCH(T, B, D, G, P, S)                                                                                              \
     do {                                                                                                                      \
-        if (SCHED) { BIG_LDS((trace_grid_sched_kernel<T, B, D, G, P, S, 256>), lds); hipLaunchKernelGGL((trace_grid_sched_kernel<T, B, D, G, P, S, 256>), gd, block, lds, st, s->dev, gp, rgb_, nhit_, cnt_); } \
-        else { BIG_LDS((trace_grid_kernel<T, B, D, G, P, S>), lds); hipLaunchKernelGGL((trace_grid_kernel<T, B, D, G, P, S>), gd, block, lds, st, s->dev, gp, rgb_, nhit_, cnt_); }     \
+        if (SCHED) { BIG_LDS((trace_grid_sched_kernel<T, B, D, G, P, S, 256>), lds, "eye pass"); hipLaunchKernelGGL((trace_grid_sched_kernel<T, B, D, G, P, S, 256>), gd, block, lds, st, s->dev, gp, rgb_, nhit_, cnt_); } \
+        else { BIG_LDS((trace_grid_kernel<T, B, D, G, P, S>), lds, "eye pass"); hipLaunchKernelGGL((trace_grid_kernel<T, B, D, G, P, S>), gd, block, lds, st, s->dev, gp, rgb_, nhit_, cnt_); }     \
     } while (0)
 #define LAUNCH_DG(T, B, P, S)                                      \
     do {                                                           \
@@ -878,8 +977,8 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
         if (bez) {  // Bezier scenes share the tree-capable variants (the tree code is skipped when there is no tree)
 #define LAUNCH1(D, G)                                                                                                          \
     do {                                                                                                                       \
-        if (SCHED) { BIG_LDS((trace_grid_sched_kernel<true, true, D, G, false, false, 64>), lds); hipLaunchKernelGGL((trace_grid_sched_kernel<true, true, D, G, false, false, 64>), gd, block, lds, st, s->dev, gp, rgb_, nhit_, cnt_); } \
-        else { BIG_LDS((trace_grid_kernel<true, true, D, G, false, false, false, 64>), lds); hipLaunchKernelGGL((trace_grid_kernel<true, true, D, G, false, false, false, 64>), gd, block, lds, st, s->dev, gp, rgb_, nhit_, cnt_); }    \
+        if (SCHED) { BIG_LDS((trace_grid_sched_kernel<true, true, D, G, false, false, 64>), lds, "eye pass (Bezier)"); hipLaunchKernelGGL((trace_grid_sched_kernel<true, true, D, G, false, false, 64>), gd, block, lds, st, s->dev, gp, rgb_, nhit_, cnt_); } \
+        else { BIG_LDS((trace_grid_kernel<true, true, D, G, false, false, false, 64>), lds, "eye pass (Bezier)"); hipLaunchKernelGGL((trace_grid_kernel<true, true, D, G, false, false, false, 64>), gd, block, lds, st, s->dev, gp, rgb_, nhit_, cnt_); }    \
     } while (0)
             if (dof) { if (glass) LAUNCH1(true, true); else LAUNCH1(true, false); }
             else     { if (glass) LAUNCH1(false, true); else LAUNCH1(false, false); }
@@ -893,9 +992,10 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
         }
 #undef LAUNCH_DG
 #undef LAUNCH
+        return CGRT_OK;
     };
     auto launch = [&](const GridParams &gp, dim3 gd, float *rgb_, uint32_t *nhit_, unsigned long long *cnt_) {
-        launch_mode(std::false_type{}, gp, gd, rgb_, nhit_, cnt_);
+        return launch_mode(std::false_type{}, gp, gd, rgb_, nhit_, cnt_);
     };
     if (spill) {
         // More top-level objects than the LDS list holds (kLdsObjsMax): the SPILL variants, which read the others from the
@@ -908,19 +1008,20 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
             const size_t l = obj_list_lds(s->dev, kThreads / 64) + (glass ? kStackBytes : 0);
 #define SPILL_SPH(D, G)                                                                                                       \
     do {                                                                                                                      \
-        BIG_LDS((trace_grid_kernel<false, false, D, G, true, false, false, 256, true>), l);                                    \
+        BIG_LDS((trace_grid_kernel<false, false, D, G, true, false, false, 256, true>), l, "eye pass, SPILL (spheres)");       \
         hipLaunchKernelGGL((trace_grid_kernel<false, false, D, G, true, false, false, 256, true>), gd, blk, l, st, s->dev, gs, rgb, nhit, cnt); \
     } while (0)
             if (dof) { if (glass) SPILL_SPH(true, true); else SPILL_SPH(true, false); }
             else     { if (glass) SPILL_SPH(false, true); else SPILL_SPH(false, false); }
 #undef SPILL_SPH
         } else {
-            const size_t l = obj_list_lds(s->dev, kThreads / 64) + kStackBytes + (kThreads / 64) * sizeof(BezLds) +
-                             (s->dev.cached_tree >= 0 ? (size_t)s->dev.cached_nodes * sizeof(NodeRec) : 0);
+            // the general variant keeps as many objects resident as fit beside its other LDS (general_resident)
+            const DeviceScene dl = with_resident(s->dev, general_resident(s, dof, false));
+            const size_t l = obj_list_lds(dl, kThreads / 64) + general_other_lds(dl);
 #define SPILL_GEN(D)                                                                                                          \
     do {                                                                                                                      \
-        BIG_LDS((trace_grid_kernel<true, true, D, true, false, false, false, 256, true>), l);                                  \
-        hipLaunchKernelGGL((trace_grid_kernel<true, true, D, true, false, false, false, 256, true>), gd, blk, l, st, s->dev, gs, rgb, nhit, cnt); \
+        BIG_LDS((trace_grid_kernel<true, true, D, true, false, false, false, 256, true>), l, "eye pass, SPILL (general)");     \
+        hipLaunchKernelGGL((trace_grid_kernel<true, true, D, true, false, false, false, 256, true>), gd, blk, l, st, dl, gs, rgb, nhit, cnt); \
     } while (0)
             if (dof) SPILL_GEN(true); else SPILL_GEN(false);
 #undef SPILL_GEN
@@ -956,7 +1057,7 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
             gp.light = light;
             gp.light_mode = 0;
         }
-        launch(gp, dim3((unsigned)tile_blocks), nullptr, nullptr, nullptr);
+        if ((rc = launch(gp, dim3((unsigned)tile_blocks), nullptr, nullptr, nullptr))) return rc;
         if (split_light) {
             // The light tiles: the variant without tree / Bezier / pending-ray code on the second stream, beside everything that
             // follows here.  It needs nothing but the classification and starts as soon as the probe is through, beside the
@@ -976,13 +1077,13 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
             gl.xcd_tiles = 0;
 #define LIGHT(T, D)                                                                                                           \
     do {                                                                                                                      \
-        BIG_LDS((trace_grid_kernel<T, false, D, false, false, false>), lds_light);                                             \
+        BIG_LDS((trace_grid_kernel<T, false, D, false, false, false>), lds_light, "eye pass, light tiles");                                             \
         hipLaunchKernelGGL((trace_grid_kernel<T, false, D, false, false, false>), gd_light, dim3(kThreads), lds_light, s->aux_stream, \
                            s->dev, gl, rgb, nhit, cnt);                                                                       \
     } while (0)
 #define LIGHT_HF(D)                                                                                                           \
     do {                                                                                                                      \
-        BIG_LDS((trace_grid_kernel<true, false, D, false, false, false, false, 256, false, true>), lds_hf);                    \
+        BIG_LDS((trace_grid_kernel<true, false, D, false, false, false, false, 256, false, true>), lds_hf, "eye pass, light tiles (HFONLY)");                    \
         hipLaunchKernelGGL((trace_grid_kernel<true, false, D, false, false, false, false, 256, false, true>), gd_light, dim3(kThreads), lds_hf, \
                            s->aux_stream, s->dev, gl, rgb, nhit, cnt);                                                         \
     } while (0)
@@ -1057,12 +1158,17 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
             pw.pad_ = 0;
             pw.counters = cnt;
             const size_t lds_pw = (size_t)(pw.finish ? s->dev.n_objs : pw.obj + 1) * sizeof(ObjRec) + (size_t)kThreads * kWideLdsDepth * sizeof(uint2);
-            if (dof) hipLaunchKernelGGL(primary_walk_kernel<true>, dim3((unsigned)n_cu2 * 4), dim3(kThreads), lds_pw, st, s->dev, g, pw);
-            else hipLaunchKernelGGL(primary_walk_kernel<false>, dim3((unsigned)n_cu2 * 4), dim3(kThreads), lds_pw, st, s->dev, g, pw);
+            if (dof) {
+                BIG_LDS(primary_walk_kernel<true>, lds_pw, "primary_walk_kernel");
+                hipLaunchKernelGGL(primary_walk_kernel<true>, dim3((unsigned)n_cu2 * 4), dim3(kThreads), lds_pw, st, s->dev, g, pw);
+            } else {
+                BIG_LDS(primary_walk_kernel<false>, lds_pw, "primary_walk_kernel");
+                hipLaunchKernelGGL(primary_walk_kernel<false>, dim3((unsigned)n_cu2 * 4), dim3(kThreads), lds_pw, st, s->dev, g, pw);
+            }
         }
-        launch_mode(std::true_type{}, g, dim3((unsigned)g.heavy_blocks + grid_dim.x), rgb, nhit, cnt);
+        if ((rc = launch_mode(std::true_type{}, g, dim3((unsigned)g.heavy_blocks + grid_dim.x), rgb, nhit, cnt))) return rc;
     } else {
-        launch(g, grid_dim, rgb, nhit, cnt);
+        if ((rc = launch(g, grid_dim, rgb, nhit, cnt))) return rc;
     }
     if (g.chunks > 1)
         hipLaunchKernelGGL(finalize_chunks_kernel, dim3((unsigned)((npx_all + 255) / 256)), dim3(256), 0, st, g, rgb, nhit);
@@ -1137,17 +1243,18 @@ static int hitpoints_device(const cgrt_scene *s, const cgrt_camera *cam, const c
     HIP_TRY(hipMemset(d_cnt, 0, sizeof(unsigned long long)));
     g.xcd_tiles = (s->dev.has_mesh && !s->dev.has_bezier) ? 1 : 0;
     const dim3 grid_dim((unsigned)tile_grid_blocks(g.W, g.rows, g.xcd_tiles != 0)), block(kThreads);
-    const size_t lds = obj_list_lds(s->dev, kThreads / 64) + kStackBytes + (kThreads / 64) * sizeof(BezLds) +
-                       (s->dev.cached_tree >= 0 ? (size_t)s->dev.cached_nodes * sizeof(NodeRec) : 0);
+    // the general variant, with as many objects resident as fit beside its other LDS (general_resident)
+    const DeviceScene dl = with_resident(s->dev, general_resident(s, cam->lens_radius > 0, true));
+    const size_t lds = obj_list_lds(dl, kThreads / 64) + general_other_lds(dl);
     HitpointSink sink{d_rec, d_cnt, (unsigned long long)cap};
     // the most general variant serves every scene; capture is a verification / hand-off path, not the hot path
 #define CAPTURE(D, SP)                                                                                                         \
     do {                                                                                                                      \
-        BIG_LDS((trace_grid_kernel<true, true, D, true, false, false, true, 256, SP>), lds);                                   \
-        hipLaunchKernelGGL((trace_grid_kernel<true, true, D, true, false, false, true, 256, SP>), grid_dim, block, lds, 0, s->dev, g, d_rgb, \
+        BIG_LDS((trace_grid_kernel<true, true, D, true, false, false, true, 256, SP>), lds, "Hitpoint capture");               \
+        hipLaunchKernelGGL((trace_grid_kernel<true, true, D, true, false, false, true, 256, SP>), grid_dim, block, lds, 0, dl, g, d_rgb, \
                            (uint32_t *)nullptr, (unsigned long long *)nullptr, sink);                                          \
     } while (0)
-    const bool spill = s->dev.n_objs > s->dev.n_lds;
+    const bool spill = dl.n_objs > dl.n_lds;
     if (cam->lens_radius > 0) { if (spill) CAPTURE(true, true); else CAPTURE(true, false); }
     else                      { if (spill) CAPTURE(false, true); else CAPTURE(false, false); }
 #undef CAPTURE

@@ -494,26 +494,30 @@ int sort_pairs(SortTemp &tmp, unsigned long long *kin, unsigned long long *kout,
     return CGRT_OK;
 }
 
-void launch_photon_trace(const cgrt_scene *s, const PhotonArgs &pa, double *events, unsigned char *valid, hipStream_t st = 0) {
+int launch_photon_trace(const cgrt_scene *s, const PhotonArgs &pa, double *events, unsigned char *valid, hipStream_t st = 0) {
     const dim3 grid((pa.count + kThreads - 1) / kThreads), block(kThreads);
     const size_t lds = obj_list_lds(s->dev, kThreads / 64);
     if (s->dev.n_objs > s->dev.n_lds) {  // more objects than the LDS list holds: the variants that read the rest from the uploaded array
         const size_t l2 = lds + (s->dev.has_bezier ? (kThreads / 64) * sizeof(BezLds) : 0);
         if (s->dev.has_bezier) {
-            BIG_LDS((photon_trace_kernel<true, true>), l2);
+            BIG_LDS((photon_trace_kernel<true, true>), l2, "photon_trace_kernel, SPILL");
             hipLaunchKernelGGL((photon_trace_kernel<true, true>), grid, block, l2, st, s->dev, pa, events, valid);
         } else {
-            BIG_LDS((photon_trace_kernel<false, true>), l2);
+            BIG_LDS((photon_trace_kernel<false, true>), l2, "photon_trace_kernel, SPILL");
             hipLaunchKernelGGL((photon_trace_kernel<false, true>), grid, block, l2, st, s->dev, pa, events, valid);
         }
-        return;
+        return CGRT_OK;
     }
-    if (s->dev.has_bezier)
-        hipLaunchKernelGGL(photon_trace_kernel<true>, grid, block, lds + (kThreads / 64) * sizeof(BezLds), st, s->dev, pa, events,
-                           valid);
-    else
-        hipLaunchKernelGGL(photon_trace_kernel<false>, grid, block,
-                           lds + (photon_lds_stack(s->dev) ? (size_t)kThreads * kWideLdsDepth * sizeof(uint2) : 0), st, s->dev, pa, events, valid);
+    if (s->dev.has_bezier) {
+        const size_t l = lds + (kThreads / 64) * sizeof(BezLds);
+        BIG_LDS(photon_trace_kernel<true>, l, "photon_trace_kernel");
+        hipLaunchKernelGGL(photon_trace_kernel<true>, grid, block, l, st, s->dev, pa, events, valid);
+    } else {
+        const size_t l = lds + (photon_lds_stack(s->dev) ? (size_t)kThreads * kWideLdsDepth * sizeof(uint2) : 0);
+        BIG_LDS(photon_trace_kernel<false>, l, "photon_trace_kernel");
+        hipLaunchKernelGGL(photon_trace_kernel<false>, grid, block, l, st, s->dev, pa, events, valid);
+    }
+    return CGRT_OK;
 }
 
 int sort_pairs32(SortTemp &tmp, unsigned int *kin, unsigned int *kout, unsigned int *vin, unsigned int *vout, size_t n,
@@ -570,7 +574,7 @@ int PhotonProducer::produce(const cgrt_scene *s, const PhotonArgs &pa, const Has
     const int nslots = pa.count * kSegStride;
     if (used[b]) HIP_TRY(hipStreamWaitEvent(st, consumed[b], 0));
     HIP_TRY(hipMemsetAsync(valid[b].p, 0, (size_t)nslots, st));
-    launch_photon_trace(s, pa, ev[b].as<double>(), valid[b].as<unsigned char>(), st);
+    if (const int rc = launch_photon_trace(s, pa, ev[b].as<double>(), valid[b].as<unsigned char>(), st)) return rc;
     hipLaunchKernelGGL(event_keys_kernel, dim3((nslots + T - 1) / T), dim3(T), 0, st, ev[b].as<double>(), valid[b].as<unsigned char>(),
                        nslots, ha, ek0[b].as<unsigned int>(), eo0[b].as<unsigned int>());
     const int rc = sort_pairs32(tmp, ek0[b].as<unsigned int>(), ek1[b].as<unsigned int>(), eo0[b].as<unsigned int>(),
@@ -601,7 +605,7 @@ extern "C" int cgrt_photon_events(const cgrt_scene *s, const cgrt_photons *ph, i
     for (int k = 0; k < 3; k++) pa.light[k] = ph->light[k];
     pa.jitter = ph->jitter; pa.power = ph->power; pa.alpha = ph->alpha;
     pa.first = first; pa.count = count; pa.max_depth = max_depth; pa.seed = ph->seed;
-    launch_photon_trace(s, pa, ev.as<double>(), va.as<unsigned char>());
+    if (const int rc = launch_photon_trace(s, pa, ev.as<double>(), va.as<unsigned char>())) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(events9, ev.p, nslots * 9 * sizeof(double), hipMemcpyDeviceToHost));

@@ -2,6 +2,7 @@
 // Everything the kernels read lives in these structs; the flattened scene is uploaded once at commit.
 #ifndef CGRT_TYPES_H
 #define CGRT_TYPES_H
+#include <stddef.h>
 #include <stdint.h>
 
 namespace cgrt {
@@ -151,11 +152,16 @@ struct BezSlabRec {
 };
 static constexpr int kBezSlabs = 64;
 
-// Top-level objects kept in LDS per workgroup: 768 x 128 B = 96 KiB, which leaves every kernel variant's other LDS (pending-ray
-// levels 38 KiB, node cache 8 KiB, wide-walk stack 32 KiB, Bezier scratch) inside a CU's 160 KiB.  `vector<Object*> objs`
-// (main.cpp:277) has no bound: objects beyond that are read from HBM / L2 -- through the scalar cache in the sphere loop, through a
-// per-wave LDS staging record in the general loop.
+// Top-level objects kept in LDS per workgroup: at most 768 x 128 B = 96 KiB.  Beside the other LDS of the eye-pass, light,
+// primary-walk and photon launches (pending-ray levels 38 KiB, node cache 8 KiB, wide-walk stack 32 KiB, Bezier scratch) that fits
+// a CU's 160 KiB (static_asserts in cgrt_hip.hip).  The most general variant (Hitpoint capture, and the eye pass of a scene
+// beyond the list that is not all spheres) carries the pending-ray levels, four waves' Bezier scratch and the node cache at once:
+// its launches stage only as many objects as fit beside those (n_lds lowered in the launch's copy of DeviceScene: 723, or 659
+// beside a 256-node cached tree) and run the SPILL variant for the rest.  `vector<Object*> objs` (main.cpp:277) has no bound: objects
+// beyond the LDS list are read from HBM / L2 -- through the scalar cache in the sphere loop, through a per-wave LDS staging
+// record in the general loop.
 static constexpr int kLdsObjsMax = 768;
+static constexpr size_t kLdsBytes = (size_t)160 << 10;  // LDS of a CU (MI355X): the most one workgroup may use, static + dynamic
 static constexpr int kMaxObjs = 1 << 20;  // sanity limit of cgrt_scene_add_* (CGRT_ERR_LIMIT beyond it)
 
 // Kernel argument block.

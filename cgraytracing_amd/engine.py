@@ -262,9 +262,12 @@ class Scene:
         check(self._L.cgrt_surface_colors(self._h, self.obj_index[obj], pts.ctypes.data, len(pts), out.ctypes.data))
         return out
 
-    def kernel_variant(self, width, height, spp=1, camera=None, max_depth=5, rows=None, stripe=None, flags=0):
-        """Name of the trace_grid_kernel instantiation this grid launches (what a rocprofv3 kernel trace shows)."""
+    def kernel_variant(self, width, height, spp=1, camera=None, max_depth=5, rows=None, stripe=None, flags=0,
+                       hitpoints=False):
+        """Name of the trace_grid_kernel instantiation this grid launches (what a rocprofv3 kernel trace shows).
+        hitpoints: the one the Hitpoint capture launches (trace_grid_hitpoints, the eye pass of ppm_render)."""
         rows = height if rows is None else rows
+        flags |= 32 if hitpoints else 0  # CGRT_GRID_HITPOINTS
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, 0, 0, stripe, 0, None, flags)
         buf = C.create_string_buffer(160)
         check(self._L.cgrt_trace_grid_variant(self._h, C.byref(cc), C.byref(g), buf, len(buf)))

@@ -86,6 +86,9 @@ enum {
                                  and to test both paths.  Device memory: up to 12 GiB (at most 1/8 of the device) of parked
                                  values per scene handle, sized by the largest launch (CGRT_DEFER_BYTES overrides)    */
     CGRT_GRID_FORCE_REORDER = 16, /* cost-schedule sphere-only scenes too (off by default: measured no gain on them)    */
+    CGRT_GRID_HITPOINTS = 32, /* cgrt_trace_grid_variant only: name the launch of the Hitpoint capture
+                                 (cgrt_trace_grid_hitpoints, the eye pass of cgrt_ppm_render) instead of cgrt_trace_grid's;
+                                 ignored by the other calls                                                            */
     CGRT_GRID_SPLIT_SAMPLES = 4 /* let several workgroups share a tile's samples: each sums a contiguous chunk of the
                                  samples in fp64 and the chunk sums are added in chunk order by a second kernel.
                                  Reproducible, but the fp64 summation ORDER differs from the sample-by-sample sum
@@ -311,7 +314,8 @@ int cgrt_intersect_rays(const cgrt_scene *s, int obj, const double *org3, const 
 int cgrt_surface_colors(const cgrt_scene *s, int obj, const double *points3, int n, double *colors3);
 
 /* Name of the trace_grid_kernel instantiation cgrt_trace_grid would launch for (scene, cam, grid) -- the kernel name a
- * rocprofv3 kernel trace shows; written NUL-terminated into name[cap]. */
+ * rocprofv3 kernel trace shows; written NUL-terminated into name[cap].  With CGRT_GRID_HITPOINTS in grid->flags: the
+ * instantiation the Hitpoint capture launches (",SPILL=1" when objects beyond the ones it keeps in LDS are read from HBM). */
 int cgrt_trace_grid_variant(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, char *name, size_t cap);
 
 /* Host evaluation of the lens stream (cgrt_rng.hpp, the same inline code the kernel runs): writes

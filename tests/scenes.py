@@ -205,3 +205,43 @@ def scene_dragon():
     """The committed main() scene minus the bump floor: planes + diffuse dragon (main.cpp:292,348-353)."""
     m = TriangleMesh.from_triangles(dragon_tris(), (0.25, 0.25, 0.5), 0.0, 0.0, 1)
     return planes() + [m]
+
+
+def many_spheres(n, seed, head=None, dup_pairs=()):
+    """Scenes of many top-level objects: `head` (default: the five wall spheres) and then seeded spheres of all three
+    materials (half diffuse, a quarter mirror, a quarter glass) up to exactly n objects, about one in twenty followed by an
+    exact duplicate.  dup_pairs: (a, b) with a < b -- object b is an exact duplicate (magenta, diffuse) of sphere a, both placed
+    in plain view near the front of the room, so that the earlier object visibly has to win the tie (main.cpp:57) whatever
+    separates a from b (an LDS boundary)."""
+    rng = np.random.default_rng(seed)
+    objs = list(wall_spheres() if head is None else head)
+    pairs = {a: b for a, b in dup_pairs if b < n}
+    dups = {}
+    while len(objs) < n:
+        i = len(objs)
+        if i in dups:
+            objs.append(dups.pop(i))
+            continue
+        if i in pairs:
+            k = sorted(pairs).index(i)
+            c = (-12.0 + 6.0 * (k % 5), -8.0 + 8.0 * ((k // 5) % 3), 14.0)
+            s = Sphere(c, 1.5, (0.2, 0.9, 0.4), *[(0, 0), (0.8, 0), (0.8, 0.5)][k % 3])
+            objs.append(s)
+            dups[pairs[i]] = Sphere(c, s.radius, (1.0, 0.0, 1.0), 0, 0)
+            continue
+        c = (rng.uniform(-17, 17), rng.uniform(-18, 17), rng.uniform(12, 38))
+        refl, transp = [(0, 0), (0, 0), (0.8, 0), (0.8, 0.5)][rng.integers(0, 4)]
+        s = Sphere(c, rng.uniform(0.3, 1.6), tuple(rng.uniform(0.2, 1, 3)), refl, transp)
+        objs.append(s)
+        if len(objs) < n and len(objs) not in dups and len(objs) not in pairs and rng.random() < 0.05:
+            objs.append(Sphere(c, s.radius, (1.0, 0.0, 1.0), 0, 0))  # an exact duplicate later in the list
+    return objs
+
+
+def room_with_objects(n, seed, mesh=None, floor_tex=None, extra=(), dup_pairs=()):
+    """A room of five planes (`planes(floor_tex)`: they lead the list, so the plane-run test stays in play), then `mesh` and
+    `extra` objects if given, then spheres up to exactly n top-level objects (many_spheres, with its duplicates)."""
+    head = planes(floor_tex) + ([mesh] if mesh is not None else []) + list(extra)
+    objs = many_spheres(n, seed, head=head, dup_pairs=dup_pairs)
+    assert len(objs) == n
+    return objs
