@@ -22,6 +22,9 @@
 // its final gather (main.cpp:252-258); the image is summed per pixel in that order.
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include <climits>
+#include <memory>
+
 namespace {
 
 constexpr int kSegStride = 8;          // event slots per photon (MAX_DEPTH = 5 segments)
@@ -436,27 +439,52 @@ __global__ void photon_apply_kernel(const unsigned long long *__restrict__ keys,
     hps[8 * i + 3] = r2;  // the next batch's search radius
 }
 
-// final gather, main.cpp:252-258: per pixel, in table order
-__global__ void photon_image_kernel(const unsigned long long *__restrict__ keys, const unsigned int *__restrict__ vals,
-                                    long long nhp, const double *__restrict__ hp, double norm, long long npix,
-                                    double *__restrict__ image) {
+// ---- the per-pixel index (CSR) the final gather walks.  A hitpoint's pixel and table position never change after the
+// table is built, so the index is built once: image_keys_kernel keys every hitpoint by (pixel, table position), a radix
+// sort orders them, the sorted values are `order` and pix_start[px] .. pix_start[px+1] is pixel px's range of it.
+// pix_start[px] = first position of the sorted keys whose pixel is >= px, px in [0, npix]
+__global__ void pix_start_kernel(const unsigned long long *__restrict__ keys, long long nhp, long long npix,
+                                 unsigned int *__restrict__ pix_start) {
     const long long px = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (px >= npix) return;
+    if (px > npix) return;
     const unsigned long long klo = (unsigned long long)px << 32;
     long long lo = 0, hi = nhp;
     while (lo < hi) {
         const long long mid = (lo + hi) >> 1;
         if (keys[mid] < klo) lo = mid + 1; else hi = mid;
     }
+    pix_start[px] = (unsigned int)lo;
+}
+// gammaCorr, util.h:45-47: one byte of main.cpp:403-412
+__device__ __forceinline__ unsigned char tonemap_byte(double x) {
+    const double v = pow(1 - exp(-x), 1 / 2.2) * 255 + .5;
+    return (v >= 0) ? (unsigned char)(int)(v < 255.0 ? v : 255.0) : 0;  // NaN -> 0
+}
+// final gather, main.cpp:252-258: one lane per pixel sums flux / (PI * r2 * N * spp) over the pixel's hitpoints in table
+// order.  image and rgb8 may each be null; rgb8 receives the tone-mapped byte of tonemap_kernel at the flipped row (row 0 =
+// top), so a checkpoint needs no second pass over the image.
+__global__ void ppm_gather_kernel(const unsigned int *__restrict__ pix_start, const unsigned int *__restrict__ order,
+                                  const double *__restrict__ hp, double norm, long long npix, int W, int rows,
+                                  double *__restrict__ image, unsigned char *__restrict__ rgb8) {
+    const long long px = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (px >= npix) return;
+    const unsigned int k1 = pix_start[px + 1];
     double r = 0, g = 0, b = 0;
-    for (long long k = lo; k < nhp && (keys[k] >> 32) == (unsigned long long)px; k++) {
-        const double *h = hp + 16 * (size_t)vals[k];
+    for (unsigned int k = pix_start[px]; k < k1; k++) {
+        const double *h = hp + 16 * (size_t)order[k];
         const double sc = 1.0 / (kPiRef * h[14] * norm);  // 1/(PI*r2*N*spp), main.cpp:256
         r += h[11] * sc;
         g += h[12] * sc;
         b += h[13] * sc;
     }
-    image[3 * px] = r; image[3 * px + 1] = g; image[3 * px + 2] = b;
+    if (image) {
+        image[3 * px] = r; image[3 * px + 1] = g; image[3 * px + 2] = b;
+    }
+    if (rgb8) {
+        const long long row = px / W, col = px % W;
+        unsigned char *o = rgb8 + ((long long)(rows - 1 - row) * W + col) * 3;
+        o[0] = tonemap_byte(r); o[1] = tonemap_byte(g); o[2] = tonemap_byte(b);
+    }
 }
 __global__ void image_keys_kernel(const double *__restrict__ hp, long long nhp, int spp, unsigned long long *__restrict__ keys,
                                   unsigned int *__restrict__ vals) {
@@ -619,9 +647,7 @@ __global__ void tonemap_kernel(const double *__restrict__ image, int W, int H, u
     const long long n = (long long)W * H * 3;
     if (i >= n) return;
     const long long row = i / ((long long)W * 3), rest = i % ((long long)W * 3);
-    const double x = image[(long long)(H - 1 - row) * W * 3 + rest];
-    const double v = pow(1 - exp(-x), 1 / 2.2) * 255 + .5;
-    rgb8[i] = (v >= 0) ? (unsigned char)(int)(v < 255.0 ? v : 255.0) : 0;  // NaN -> 0
+    rgb8[i] = tonemap_byte(image[(long long)(H - 1 - row) * W * 3 + rest]);
 }
 
 namespace {
@@ -655,116 +681,179 @@ extern "C" int cgrt_tonemap_rgb8(int device, const double *image, int width, int
     return CGRT_OK;
 }
 
-extern "C" int cgrt_ppm_render(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid,
-                               const cgrt_photons *ph, cgrt_ppm_result *out) {
-    int rc = check_grid(s, cam, grid);
-    if (rc) return rc;
-    if (!ph || !out) return fail(CGRT_ERR_INVALID, "null argument");
-    if (ph->nphotons < 0 || ph->hashsize < 1 || ph->hashsize > (1 << 20) || ph->batch < 0 || !(ph->initial_radius >= 0) ||
-        ph->pair_cap < 0)
-        return fail(CGRT_ERR_INVALID, "bad photon parameters");
-    if (grid->stripe_nranks > 1 && out->rgb8)
-        return fail(CGRT_ERR_UNSUPPORTED, "photon pass: rgb8 needs contiguous rows; tone-map the assembled frame (cgrt_tonemap_rgb8)");
-    ON_DEVICE(s->device);
+// ---- the stages of render() main.cpp:169-258, shared by cgrt_ppm_render (one call) and a live cgrt_ppm_session ----------
+// table(): eye pass, the reference's table order, the per-pixel index.  photon_setup() + photons(last): photons
+// [done, last) in batches.  gather(): the image at the current photon count.  Photon i always draws from the keyed stream
+// (seed, i) and a hitpoint replays its events in photon order, so the state after photons [0, a) then [a, b) is the state
+// after [0, b): how the photons are split into calls and batches never shows in the result.
+struct cgrt_ppm_session {
+    const cgrt_scene *s = nullptr;
+    cgrt_camera cam{};
+    cgrt_grid grid{};
+    cgrt_photons ph{};
+    bool lookahead = false;  // session: trace the next batch on the producer stream when a call ends
+    size_t n = 0;            // hitpoints
+    long long npix = 0;
+    HashArgs ha{};
+    int64_t dev_bytes = 0;  // what this state allocated itself (sort scratch and producer buffers are added by bytes())
+    DevBuf hp, hps, bstart, pix_start, order;  // table state and per-pixel index
+    DevBuf pk0, pk1, pv0, pv1, npairs;          // (hitpoint, event) pairs of one batch
+    DevBuf img, rgb8;                           // session: device image of cgrt_ppm_session_image (host outputs)
+    SortTemp main_tmp;
+    PhotonProducer pp;  // declared last of the buffers: its destructor waits for its stream before they are freed
+    int64_t pp_bytes = 0;
+    bool overlap = false;
+    int batch = 0, batch_max = 0, pair_key_bits = 25;
+    unsigned long long pair_cap = 0;
+    long long done = 0;       // photons [0, done) are applied
+    long long ahead_first = -1;  // the batch already enqueued on the producer: its range and buffer
+    int ahead_count = 0, ahead_buf = 0, cur = 0;
+    uint64_t n_events = 0, n_pairs = 0, n_halvings = 0;
+    double ms_eye = 0, ms_table = 0, ms_photons = 0, ms_last_add = 0;
+    mutable double ms_last_image = 0;
+    mutable hipEvent_t img_a = nullptr, img_b = nullptr;  // session: brackets the last gather (on the stream it ran on)
+    mutable bool img_pending = false;                     // img_b recorded, ms_last_image not yet read from it
+
+    ~cgrt_ppm_session() {
+        if (img_b) (void)hipEventSynchronize(img_b);
+        if (img_a) (void)hipEventDestroy(img_a);
+        if (img_b) (void)hipEventDestroy(img_b);
+    }
+    hipError_t take(DevBuf &b, size_t bytes) {
+        dev_bytes += (int64_t)bytes;
+        return b.alloc(bytes);
+    }
+    int64_t bytes() const { return dev_bytes + pp_bytes + (int64_t)main_tmp.cap + (int64_t)pp.tmp.cap; }
+    int table(const cgrt_scene *s_, const cgrt_camera *cam_, const cgrt_grid *grid_, const cgrt_photons *ph_);
+    int photon_setup(bool session);
+    int photons(long long last, bool keep_ahead);
+    int gather(double *d_img, unsigned char *d_rgb8, hipStream_t st) const;
+};
+
+int cgrt_ppm_session::table(const cgrt_scene *s_, const cgrt_camera *cam_, const cgrt_grid *grid_, const cgrt_photons *ph_) {
+    s = s_; cam = *cam_; grid = *grid_; ph = *ph_;
     Timer tm;
     // ---- eye pass: hitpoint records, device resident (count first, then capture) ----
     tm.start();
     uint64_t nhp = 0;
-    rc = hitpoints_device(s, cam, grid, 0, nullptr, &nhp);
+    int rc = hitpoints_device(s, &cam, &grid, 0, nullptr, &nhp);
     if (rc) return rc;
-    const long long npix = (long long)grid->rows * grid->width;
-    const size_t n = (size_t)nhp;
+    npix = (long long)grid.rows * grid.width;
+    n = (size_t)nhp;
     if (n >= (1ull << 31)) return fail(CGRT_ERR_LIMIT, "photon pass: more than 2^31 hitpoints");
-    DevBuf rec, hp, hps, bucket_of, bstart, k0, k1, v0, v1, img;
-    SortTemp main_tmp;
+    DevBuf rec, bucket_of, k0, k1, v0, v1;
     if (n) {
         double *d_rec = nullptr;
-        rc = hitpoints_device(s, cam, grid, nhp, &d_rec, &nhp);
+        rc = hitpoints_device(s, &cam, &grid, nhp, &d_rec, &nhp);
         rec.p = d_rec;
         if (rc) return rc;
     }
-    out->ms_eye = tm.stop();
-    // ---- the reference's table order: (bucket, insertion order) ----
+    ms_eye = tm.stop();
+    // ---- the reference's table order: (bucket, insertion order); then the per-pixel index ----
     tm.start();
-    HIP_TRY(hp.alloc(n * 16 * sizeof(double)));
-    HIP_TRY(hps.alloc(n * 8 * sizeof(double)));
+    HIP_TRY(take(hp, n * 16 * sizeof(double)));
+    HIP_TRY(take(hps, n * 8 * sizeof(double)));
+    HIP_TRY(take(bstart, ((size_t)ph.hashsize + 2) * sizeof(int)));
+    HIP_TRY(take(pix_start, ((size_t)npix + 1) * sizeof(unsigned int)));
     HIP_TRY(bucket_of.alloc(n * sizeof(int)));
-    HIP_TRY(bstart.alloc(((size_t)ph->hashsize + 2) * sizeof(int)));
     HIP_TRY(k0.alloc(n * 8)); HIP_TRY(k1.alloc(n * 8)); HIP_TRY(v0.alloc(n * 4)); HIP_TRY(v1.alloc(n * 4));
-    HashArgs ha;
-    ha.hashsize = ph->hashsize;
+    ha.hashsize = ph.hashsize;
     // main.cpp:84,183: r = 200.0 / height with the reference's COMPILE-TIME height (768) whatever frame is rendered;
     // a host that mirrors a reference built for another height passes that build's 200/height here
-    const double r0 = ph->initial_radius > 0 ? ph->initial_radius : 200.0 / 768;
+    const double r0 = ph.initial_radius > 0 ? ph.initial_radius : 200.0 / 768;
     ha.celllength = 70.0 / std::ceil(70.0 / r0);  // hash.h:25-26
     const int T = 256;
     const unsigned nb = (unsigned)((n + T - 1) / T);
     if (n) {
-        hipLaunchKernelGGL(hp_keys_kernel, dim3(nb), dim3(T), 0, 0, rec.as<double>(), (long long)n, ha, (int)npix, grid->spp,
+        hipLaunchKernelGGL(hp_keys_kernel, dim3(nb), dim3(T), 0, 0, rec.as<double>(), (long long)n, ha, (int)npix, grid.spp,
                            k0.as<unsigned long long>(), v0.as<unsigned int>());
         rc = sort_pairs(main_tmp, k0.as<unsigned long long>(), k1.as<unsigned long long>(), v0.as<unsigned int>(), v1.as<unsigned int>(), n);
         if (rc) return rc;
         hipLaunchKernelGGL(hp_gather_kernel, dim3(nb), dim3(T), 0, 0, rec.as<double>(), k1.as<unsigned long long>(),
                            v1.as<unsigned int>(), (long long)n, r0 * r0, hp.as<double>(), hps.as<double>(), bucket_of.as<int>());
-    }
-    hipLaunchKernelGGL(bucket_start_kernel, dim3((ph->hashsize + 1 + T - 1) / T), dim3(T), 0, 0, bucket_of.as<int>(),
-                       (long long)n, ph->hashsize, bstart.as<int>());
-    HIP_TRY(hipGetLastError());
-    out->ms_table = tm.stop();
-    // ---- photons, in batches ----
-    tm.start();
-    int batch = ph->batch > 0 ? (ph->batch < (1 << 20) ? ph->batch : (1 << 20)) : (1 << 20);
-    const int batch_max = batch;
-    const int nslots_max = batch * kSegStride;
-    DevBuf pk0, pk1, pv0, pv1, npairs;
-    // pairs per batch: room for 128 per hitpoint, between 4 M and 128 M (3 GiB of keys and values); a batch that overflows is halved
-    const unsigned long long want_cap = (unsigned long long)n * 128ull;
-    unsigned long long pair_cap = want_cap < (1ull << 22) ? (1ull << 22) : (want_cap > (1ull << 27) ? (1ull << 27) : want_cap);
-    if (ph->pair_cap > 0) pair_cap = (unsigned long long)ph->pair_cap < (1ull << 27) ? (unsigned long long)ph->pair_cap : (1ull << 27);
-    // Two event buffers: while batch k's pairs are sorted and replayed (null stream), batch k+1 is traced and its events are
-    // put in hash-cell order on the producer's stream.  CGRT_PHOTON_OVERLAP=0: one buffer, everything on the null stream.
-    const char *ov = std::getenv("CGRT_PHOTON_OVERLAP");
-    const bool overlap = !(ov && ov[0] == '0') && ph->nphotons > batch;
-    PhotonProducer pp;
-    if (n > 0 && ph->nphotons > 0) {
-        rc = pp.init(overlap ? 2 : 1, (size_t)nslots_max, overlap);
+        hipLaunchKernelGGL(image_keys_kernel, dim3(nb), dim3(T), 0, 0, hp.as<double>(), (long long)n, grid.spp,
+                           k0.as<unsigned long long>(), v0.as<unsigned int>());
+        rc = sort_pairs(main_tmp, k0.as<unsigned long long>(), k1.as<unsigned long long>(), v0.as<unsigned int>(), v1.as<unsigned int>(), n);
         if (rc) return rc;
     }
-    HIP_TRY(pk0.alloc((size_t)pair_cap * 8)); HIP_TRY(pk1.alloc((size_t)pair_cap * 8));
-    HIP_TRY(pv0.alloc((size_t)pair_cap * 4)); HIP_TRY(pv1.alloc((size_t)pair_cap * 4));
-    HIP_TRY(npairs.alloc(16));
-    out->n_events = 0;
-    out->n_pairs = 0;
-    out->n_batch_halvings = 0;
-    int pair_key_bits = 25;  // key = hitpoint << 24 | slot
+    hipLaunchKernelGGL(bucket_start_kernel, dim3((ph.hashsize + 1 + T - 1) / T), dim3(T), 0, 0, bucket_of.as<int>(),
+                       (long long)n, ph.hashsize, bstart.as<int>());
+    hipLaunchKernelGGL(pix_start_kernel, dim3((unsigned)((npix + 1 + T - 1) / T)), dim3(T), 0, 0, k1.as<unsigned long long>(),
+                       (long long)n, npix, pix_start.as<unsigned int>());
+    HIP_TRY(hipGetLastError());
+    order.p = v1.release();  // hitpoint indices by pixel, then table order
+    dev_bytes += (int64_t)(n ? n * 4 : 16);
+    ms_table = tm.stop();
+    return CGRT_OK;
+}
+
+// Batch size, pair buffers and the producer.  One call traces on a second stream only when it has more photons than one
+// batch; a session always does (its calls are not known in advance).  CGRT_PHOTON_OVERLAP=0: one buffer, null stream.
+int cgrt_ppm_session::photon_setup(bool session) {
+    batch = ph.batch > 0 ? (ph.batch < (1 << 20) ? ph.batch : (1 << 20)) : (1 << 20);
+    batch_max = batch;
+    const int nslots_max = batch * kSegStride;
+    // pairs per batch: room for 128 per hitpoint, between 4 M and 128 M (3 GiB of keys and values); a batch that overflows is halved
+    const unsigned long long want_cap = (unsigned long long)n * 128ull;
+    pair_cap = want_cap < (1ull << 22) ? (1ull << 22) : (want_cap > (1ull << 27) ? (1ull << 27) : want_cap);
+    if (ph.pair_cap > 0) pair_cap = (unsigned long long)ph.pair_cap < (1ull << 27) ? (unsigned long long)ph.pair_cap : (1ull << 27);
+    // Two event buffers: while batch k's pairs are sorted and replayed (null stream), batch k+1 is traced and its events are
+    // put in hash-cell order on the producer's stream.
+    const char *ov = std::getenv("CGRT_PHOTON_OVERLAP");
+    overlap = !(ov && ov[0] == '0') && (session || ph.nphotons > batch);
+    if (n > 0 && (session || ph.nphotons > 0)) {
+        const int nbuf = overlap ? 2 : 1;
+        const int rc = pp.init(nbuf, (size_t)nslots_max, overlap);
+        if (rc) return rc;
+        pp_bytes = (int64_t)nbuf * nslots_max * (9 * sizeof(double) + 1 + 4 * 4);
+    }
+    HIP_TRY(take(pk0, (size_t)pair_cap * 8)); HIP_TRY(take(pk1, (size_t)pair_cap * 8));
+    HIP_TRY(take(pv0, (size_t)pair_cap * 4)); HIP_TRY(take(pv1, (size_t)pair_cap * 4));
+    HIP_TRY(take(npairs, 16));
+    pair_key_bits = 25;  // key = hitpoint << 24 | slot
     while (pair_key_bits < 64 && (n >> (pair_key_bits - 24)) != 0) pair_key_bits++;
-    auto batch_args = [&](long long first, int batch_now) {
+    return CGRT_OK;
+}
+
+// Photons [done, last), applied on the null stream.  A batch is applied whole or not at all: `done` only moves past a batch
+// once its pairs fit, so a failure leaves the state of the first `done` photons.  keep_ahead: when the range is done, the
+// next batch from `done` is enqueued on the producer stream for the next call (which uses it if it starts with exactly
+// that batch; it is sized for a call as long as this one); otherwise nothing is traced beyond `last` and the producer stream
+// is drained.
+int cgrt_ppm_session::photons(long long last, bool keep_ahead) {
+    if (n == 0) {  // no hitpoint can change: nothing to trace
+        done = last > done ? last : done;
+        return CGRT_OK;
+    }
+    const int T = 256;
+    const unsigned nb = (unsigned)((n + T - 1) / T);
+    auto batch_args = [&](long long first, int batch_now, long long end) {
         PhotonArgs pa;
-        for (int k = 0; k < 3; k++) pa.light[k] = ph->light[k];
-        pa.jitter = ph->jitter; pa.power = ph->power; pa.alpha = ph->alpha;
+        for (int k = 0; k < 3; k++) pa.light[k] = ph.light[k];
+        pa.jitter = ph.jitter; pa.power = ph.power; pa.alpha = ph.alpha;
         pa.first = first;
-        pa.count = (int)((ph->nphotons - first < batch_now) ? (ph->nphotons - first) : batch_now);
-        pa.max_depth = grid->max_depth;
-        pa.seed = ph->seed;
+        pa.count = (int)((end - first < batch_now) ? (end - first) : batch_now);
+        pa.max_depth = grid.max_depth;
+        pa.seed = ph.seed;
         return pa;
     };
-    long long ahead_first = -1;  // the batch already enqueued on the producer: its range and buffer
-    int ahead_count = 0, ahead_buf = 0, cur = 0;
-    for (long long first = 0; first < ph->nphotons && n > 0;) {
-        const PhotonArgs pa = batch_args(first, batch);
+    int rc = CGRT_OK;
+    const long long call = last - done;
+    while (done < last) {
+        const PhotonArgs pa = batch_args(done, batch, last);
         const int nslots = pa.count * kSegStride;
         if (ahead_first == pa.first && ahead_count == pa.count) {
             cur = ahead_buf;
-        } else {  // first batch, or the plan changed (a halving): produce it now
+        } else {  // first batch, the plan changed (a halving), or a lookahead that does not fit this call: produce it now
             rc = pp.produce(s, pa, ha, cur);
             if (rc) return rc;
         }
         ahead_first = -1;
-        if (overlap && first + pa.count < ph->nphotons) {
+        if (overlap && done + pa.count < last) {
             // Enqueue the NEXT batch now, so that it is traced under this batch's search, sort and replay.  Its range assumes
             // this batch neither overflows the pair buffer nor changes the batch size; if it does, the range will not match
             // at the top of the loop and the batch is produced again (results do not depend on the batching).
-            const PhotonArgs nx = batch_args(first + pa.count, batch);
+            const PhotonArgs nx = batch_args(done + pa.count, batch, last);
             rc = pp.produce(s, nx, ha, 1 - cur);
             if (rc) return rc;
             ahead_first = nx.first; ahead_count = nx.count; ahead_buf = 1 - cur;
@@ -778,59 +867,227 @@ extern "C" int cgrt_ppm_render(const cgrt_scene *s, const cgrt_camera *cam, cons
         unsigned long long np2[2] = {0, 0};  // pairs (the full 64-bit count, stored or not), events
         HIP_TRY(hipMemcpy(np2, npairs.p, 16, hipMemcpyDeviceToHost));
         if (np2[0] > pair_cap) {  // nothing has been applied yet: redo this range in smaller batches (same result)
-            if (pa.count <= 1) return fail(CGRT_ERR_LIMIT, "photon pass: one photon's pairs exceed the pair buffer");
-            batch = (pa.count < batch ? pa.count : batch) / 2;
-            out->n_batch_halvings++;
             rc = pp.release(cur);
             if (rc) return rc;
+            if (pa.count <= 1) return fail(CGRT_ERR_LIMIT, "photon pass: one photon's pairs exceed the pair buffer");
+            batch = (pa.count < batch ? pa.count : batch) / 2;
+            n_halvings++;
             continue;
         }
         const unsigned int np = (unsigned int)np2[0];  // <= pair_cap <= 2^27
-        first += pa.count;
-        out->n_events += np2[1];
-        if (batch < batch_max && np < pair_cap / 4) batch *= 2;  // radii shrink as photons arrive: later batches hold fewer pairs
+        done += pa.count;
+        n_events += np2[1];
+        // radii shrink as photons arrive: later batches hold fewer pairs.  Never beyond batch_max, the event buffers' size (a
+        // batch halved from a size that is not batch_max / 2^k would otherwise double past it)
+        if (batch < batch_max && np < pair_cap / 4) batch = batch < batch_max / 2 ? batch * 2 : batch_max;
         if (np != 0) {
-            out->n_pairs += np;
+            n_pairs += np;
             rc = sort_pairs(main_tmp, pk0.as<unsigned long long>(), pk1.as<unsigned long long>(), pv0.as<unsigned int>(),
                             pv1.as<unsigned int>(), np, pair_key_bits);
             if (rc) return rc;
             hipLaunchKernelGGL(photon_apply_kernel, dim3(nb), dim3(T), 0, 0, pk1.as<unsigned long long>(), pv1.as<unsigned int>(), np,
-                               pp.ev[cur].as<double>(), ph->alpha, hp.as<double>(), hps.as<double>(), (long long)n);
+                               pp.ev[cur].as<double>(), ph.alpha, hp.as<double>(), hps.as<double>(), (long long)n);
             HIP_TRY(hipGetLastError());
         }
         rc = pp.release(cur);
         if (rc) return rc;
     }
-    if (pp.st) HIP_TRY(hipStreamSynchronize(pp.st));
+    if (keep_ahead && overlap) {
+        // the lookahead: the first batch of a next call of as many photons as this one (a run of equal calls is the interactive
+        // pattern), traced while the caller looks at the image.  Buffer 1 - cur: the replay of cur may still be running.
+        const long long span = call > 0 ? call : (ahead_first == done ? ahead_count : batch);  // an empty call keeps it
+        if (ahead_first != done || ahead_count != (span < batch ? span : batch)) {
+            const PhotonArgs nx = batch_args(done, batch, done + span);
+            rc = pp.produce(s, nx, ha, 1 - cur);
+            if (rc) return rc;
+            ahead_first = nx.first; ahead_count = nx.count; ahead_buf = 1 - cur;
+        }
+    } else if (pp.st) {
+        ahead_first = -1;
+        HIP_TRY(hipStreamSynchronize(pp.st));
+    }
+    return CGRT_OK;
+}
+
+// The image at `done` photons into device buffers (either may be null), enqueued on `st`.
+int cgrt_ppm_session::gather(double *d_img, unsigned char *d_rgb8, hipStream_t st) const {
+    const int T = 256;
+    hipLaunchKernelGGL(ppm_gather_kernel, dim3((unsigned)((npix + T - 1) / T)), dim3(T), 0, st, static_cast<const unsigned int *>(pix_start.p),
+                       static_cast<const unsigned int *>(order.p), static_cast<const double *>(hp.p), (double)done * grid.spp, npix, grid.width, grid.rows,
+                       d_img, d_rgb8);
+    HIP_TRY(hipGetLastError());
+    return CGRT_OK;
+}
+
+static int check_photons(const cgrt_photons *ph) {
+    if (ph->nphotons < 0 || ph->hashsize < 1 || ph->hashsize > (1 << 20) || ph->batch < 0 || !(ph->initial_radius >= 0) ||
+        ph->pair_cap < 0)
+        return fail(CGRT_ERR_INVALID, "bad photon parameters");
+    return CGRT_OK;
+}
+
+extern "C" int cgrt_ppm_render(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid,
+                               const cgrt_photons *ph, cgrt_ppm_result *out) {
+    int rc = check_grid(s, cam, grid);
+    if (rc) return rc;
+    if (!ph || !out) return fail(CGRT_ERR_INVALID, "null argument");
+    if ((rc = check_photons(ph))) return rc;
+    if (grid->stripe_nranks > 1 && out->rgb8)
+        return fail(CGRT_ERR_UNSUPPORTED, "photon pass: rgb8 needs contiguous rows; tone-map the assembled frame (cgrt_tonemap_rgb8)");
+    ON_DEVICE(s->device);
+    cgrt_ppm_session run;
+    rc = run.table(s, cam, grid, ph);
+    out->ms_eye = run.ms_eye;
+    out->ms_table = run.ms_table;
+    if (rc) return rc;
+    // ---- photons, in batches ----
+    Timer tm;
+    tm.start();
+    rc = run.photon_setup(false);
+    if (rc == CGRT_OK) rc = run.photons(ph->nphotons, false);
+    out->n_events = run.n_events;
+    out->n_pairs = run.n_pairs;
+    out->n_batch_halvings = run.n_halvings;
+    if (rc) return rc;
     out->ms_photons = tm.stop();
     // ---- final gather + tone map ----
     tm.start();
+    const long long npix = run.npix;
+    DevBuf img, rgb8;
     HIP_TRY(img.alloc((size_t)npix * 3 * sizeof(double)));
-    HIP_TRY(hipMemset(img.p, 0, (size_t)npix * 3 * sizeof(double)));
-    if (n) {
-        hipLaunchKernelGGL(image_keys_kernel, dim3(nb), dim3(T), 0, 0, hp.as<double>(), (long long)n, grid->spp,
-                           k0.as<unsigned long long>(), v0.as<unsigned int>());
-        rc = sort_pairs(main_tmp, k0.as<unsigned long long>(), k1.as<unsigned long long>(), v0.as<unsigned int>(), v1.as<unsigned int>(), n);
-        if (rc) return rc;
-        hipLaunchKernelGGL(photon_image_kernel, dim3((unsigned)((npix + T - 1) / T)), dim3(T), 0, 0, k1.as<unsigned long long>(),
-                           v1.as<unsigned int>(), (long long)n, hp.as<double>(), (double)ph->nphotons * grid->spp, npix,
-                           img.as<double>());
-    }
-    DevBuf rgb8;
-    if (out->rgb8) {
-        HIP_TRY(rgb8.alloc((size_t)npix * 3));
-        hipLaunchKernelGGL(tonemap_kernel, dim3((unsigned)((npix * 3 + T - 1) / T)), dim3(T), 0, 0, img.as<double>(), grid->width,
-                           grid->rows, rgb8.as<unsigned char>());
-    }
-    HIP_TRY(hipGetLastError());
+    if (out->rgb8) HIP_TRY(rgb8.alloc((size_t)npix * 3));
+    rc = run.gather(img.as<double>(), out->rgb8 ? rgb8.as<unsigned char>() : nullptr, 0);
+    if (rc) return rc;
     out->ms_gather = tm.stop();
     if (out->image) HIP_TRY(hipMemcpy(out->image, img.p, (size_t)npix * 3 * sizeof(double), hipMemcpyDeviceToHost));
     if (out->rgb8) HIP_TRY(hipMemcpy(out->rgb8, rgb8.p, (size_t)npix * 3, hipMemcpyDeviceToHost));
-    out->hp_count = nhp;
+    out->hp_count = run.n;
     if (out->hp16 && out->hp_cap) {
-        const size_t m = n < out->hp_cap ? n : (size_t)out->hp_cap;
-        HIP_TRY(hipMemcpy(out->hp16, hp.p, m * 16 * sizeof(double), hipMemcpyDeviceToHost));
+        const size_t m = run.n < out->hp_cap ? run.n : (size_t)out->hp_cap;
+        HIP_TRY(hipMemcpy(out->hp16, run.hp.p, m * 16 * sizeof(double), hipMemcpyDeviceToHost));
     }
+    return CGRT_OK;
+}
+
+// ---- resumable photon mapping: the state above, kept between calls -------------------------------------------------
+extern "C" int cgrt_ppm_session_create(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid,
+                                       const cgrt_photons *ph, int flags, cgrt_ppm_session **out) {
+    if (!out) return fail(CGRT_ERR_INVALID, "null argument");
+    *out = nullptr;
+    int rc = check_grid(s, cam, grid);
+    if (rc) return rc;
+    if (!ph) return fail(CGRT_ERR_INVALID, "null argument");
+    if ((rc = check_photons(ph))) return rc;
+    if (flags & ~CGRT_PPM_SESSION_NO_LOOKAHEAD) return fail(CGRT_ERR_INVALID, "unknown session flags");
+    ON_DEVICE(s->device);
+    std::unique_ptr<cgrt_ppm_session> p(new (std::nothrow) cgrt_ppm_session());
+    if (!p) return fail(CGRT_ERR_LIMIT, "out of host memory");
+    p->lookahead = !(flags & CGRT_PPM_SESSION_NO_LOOKAHEAD);
+    HIP_TRY(hipEventCreate(&p->img_a));
+    HIP_TRY(hipEventCreate(&p->img_b));
+    if ((rc = p->table(s, cam, grid, ph))) return rc;
+    Timer tm;
+    tm.start();
+    rc = p->photon_setup(true);
+    if (rc == CGRT_OK) rc = p->photons(ph->nphotons, p->lookahead);
+    p->ms_last_add = tm.stop();
+    p->ms_photons = p->ms_last_add;
+    if (rc) return rc;
+    *out = p.release();
+    return CGRT_OK;
+}
+
+extern "C" void cgrt_ppm_session_destroy(cgrt_ppm_session *p) {
+    if (!p) return;
+    DeviceGuard g(p->s->device);
+    if (g.err == hipSuccess) (void)hipStreamSynchronize(0);
+    delete p;  // waits for the last gather and the producer stream (lookahead) before freeing
+}
+
+extern "C" int cgrt_ppm_session_add_photons(cgrt_ppm_session *p, int64_t count) {
+    if (!p || count < 0 || count > LLONG_MAX - p->done) return fail(CGRT_ERR_INVALID, "bad argument");
+    ON_DEVICE(p->s->device);
+    if (p->img_pending) HIP_TRY(hipStreamWaitEvent(0, p->img_b, 0));  // a gather on a caller's stream reads hp
+    Timer tm;
+    tm.start();
+    const int rc = p->photons(p->done + count, p->lookahead);
+    p->ms_last_add = tm.stop();  // also when a batch failed: what was applied before it has finished
+    p->ms_photons += p->ms_last_add;
+    return rc;
+}
+
+static int session_image_args(const cgrt_ppm_session *p, const uint8_t *rgb8) {
+    if (!p) return fail(CGRT_ERR_INVALID, "null session");
+    if (p->done == 0) return fail(CGRT_ERR_INVALID, "photon session: no photon yet (the image would be flux / (PI r2 0))");
+    if (rgb8 && p->grid.stripe_nranks > 1)
+        return fail(CGRT_ERR_UNSUPPORTED, "photon session: rgb8 needs contiguous rows; tone-map the assembled frame (cgrt_tonemap_rgb8)");
+    return CGRT_OK;
+}
+
+extern "C" int cgrt_ppm_session_image(const cgrt_ppm_session *cp, double *image, uint8_t *rgb8) {
+    int rc = session_image_args(cp, rgb8);
+    if (rc) return rc;
+    cgrt_ppm_session *p = const_cast<cgrt_ppm_session *>(cp);  // the image buffers are scratch, not state
+    ON_DEVICE(p->s->device);
+    const size_t npix = (size_t)p->npix;
+    if (image && !p->img.p) HIP_TRY(p->take(p->img, npix * 3 * sizeof(double)));
+    if (rgb8 && !p->rgb8.p) HIP_TRY(p->take(p->rgb8, npix * 3));
+    HIP_TRY(hipEventRecord(p->img_a, 0));
+    rc = p->gather(image ? p->img.as<double>() : nullptr, rgb8 ? p->rgb8.as<unsigned char>() : nullptr, 0);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(p->img_b, 0));
+    HIP_TRY(hipEventSynchronize(p->img_b));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, p->img_a, p->img_b));
+    p->ms_last_image = ms;
+    p->img_pending = false;
+    if (image) HIP_TRY(hipMemcpy(image, p->img.p, npix * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (rgb8) HIP_TRY(hipMemcpy(rgb8, p->rgb8.p, npix * 3, hipMemcpyDeviceToHost));
+    return CGRT_OK;
+}
+
+extern "C" int cgrt_ppm_session_image_device(const cgrt_ppm_session *p, double *image, uint8_t *rgb8, void *stream) {
+    int rc = session_image_args(p, rgb8);
+    if (rc) return rc;
+    ON_DEVICE(p->s->device);
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipEventRecord(p->img_a, st));
+    if ((rc = p->gather(image, rgb8, st))) return rc;
+    HIP_TRY(hipEventRecord(p->img_b, st));
+    p->img_pending = true;  // the next add_photons waits for it; get_info reads its time
+    return CGRT_OK;
+}
+
+extern "C" int cgrt_ppm_session_hitpoints(const cgrt_ppm_session *p, double *hp16, uint64_t cap, uint64_t *count) {
+    if (!p || !count || (cap > 0 && !hp16)) return fail(CGRT_ERR_INVALID, "bad argument");
+    ON_DEVICE(p->s->device);
+    *count = p->n;
+    const size_t m = p->n < cap ? p->n : (size_t)cap;
+    if (m) HIP_TRY(hipMemcpy(hp16, p->hp.p, m * 16 * sizeof(double), hipMemcpyDeviceToHost));
+    return CGRT_OK;
+}
+
+extern "C" int cgrt_ppm_session_get_info(const cgrt_ppm_session *p, cgrt_ppm_session_info *out) {
+    if (!p || !out) return fail(CGRT_ERR_INVALID, "null argument");
+    if (p->img_pending) {
+        ON_DEVICE(p->s->device);
+        HIP_TRY(hipEventSynchronize(p->img_b));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, p->img_a, p->img_b));
+        p->ms_last_image = ms;
+        p->img_pending = false;
+    }
+    out->photons_done = p->done;
+    out->hp_count = p->n;
+    out->n_events = p->n_events;
+    out->n_pairs = p->n_pairs;
+    out->n_batch_halvings = p->n_halvings;
+    out->device_bytes = p->bytes();
+    out->ms_eye = p->ms_eye;
+    out->ms_table = p->ms_table;
+    out->ms_photons = p->ms_photons;
+    out->ms_last_add = p->ms_last_add;
+    out->ms_last_image = p->ms_last_image;
     return CGRT_OK;
 }
 

@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -33,6 +34,7 @@ class Scene:
         self._h = h
         self._L = L
         self.device = int(device)
+        self._sessions = weakref.WeakSet()  # live PpmSessions: closed before the scene handle goes
         self.obj_index = []
         tex_ids = {}
         try:
@@ -73,6 +75,8 @@ class Scene:
             raise
 
     def close(self):
+        for ses in list(getattr(self, "_sessions", ())):
+            ses.close()
         if getattr(self, "_h", None):
             self._L.cgrt_scene_destroy(self._h)
             self._h = None
@@ -244,6 +248,23 @@ class Scene:
             out["rgb8"] = rgb8
         return out
 
+    def ppm_session(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, nphotons=0, photon_seed=777,
+                    hashsize=1000001, light=(0.0, 19.999, 20.0), jitter=2.0, power=700.0, alpha=0.7, batch=0, rows=None,
+                    row_offset=0, stripe=None, initial_radius=0.0, pair_cap=0, lookahead=True):
+        """A live photon-mapping render (cgrt_ppm_session): eye pass and table now, then `nphotons` photons (0 allowed);
+        PpmSession.add_photons(n) traces more.  Same keywords as ppm_render; after photons totalling k the image, rgb8 and
+        hitpoints are ppm_render(nphotons=k)'s bit for bit.  lookahead=False: CGRT_PPM_SESSION_NO_LOOKAHEAD (no batch is
+        traced ahead for the next call)."""
+        rows = height if rows is None else rows
+        cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, 0, None, 0)
+        ph = _capi.Photons(_d3(light), jitter, power, alpha, nphotons, hashsize, batch, photon_seed, initial_radius, pair_cap)
+        h = C.c_void_p()
+        check(self._L.cgrt_ppm_session_create(self._h, C.byref(cc), C.byref(g), C.byref(ph),
+                                              0 if lookahead else _capi.PPM_SESSION_NO_LOOKAHEAD, C.byref(h)))
+        ses = PpmSession(self, h, width, rows, spp)
+        self._sessions.add(ses)
+        return ses
+
     def photon_events(self, first, count, max_depth=5, photon_seed=777, light=(0.0, 19.999, 20.0), jitter=2.0,
                       power=700.0):
         """Verification probe: diffuse hits of photons [first, first+count): [n,10] = photon, P, n, flux in serial
@@ -287,6 +308,86 @@ class Scene:
         check(self._L.cgrt_intersect_rays(self._h, self.obj_index[obj], org.ctypes.data, dirs.ctypes.data, kp, n,
                                           hit.ctypes.data, ln.ctypes.data, nv.ctypes.data))
         return hit, ln, nv
+
+
+class PpmSession:
+    """Owns a cgrt_ppm_session (Scene.ppm_session).  Holds a reference to its Scene, which therefore outlives it; closing the
+    Scene closes its sessions first."""
+
+    def __init__(self, scene, h, width, rows, spp):
+        self._scene = scene
+        self._L = scene._L
+        self._h = h
+        self.width, self.rows, self.spp = width, rows, spp
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.cgrt_ppm_session_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def add_photons(self, n):
+        """Traces photons [photons_done, photons_done + n) and applies them; returns when they are applied."""
+        check(self._L.cgrt_ppm_session_add_photons(self._h, int(n)))
+        return self
+
+    def info(self):
+        inf = _capi.PpmSessionInfo()
+        check(self._L.cgrt_ppm_session_get_info(self._h, C.byref(inf)))
+        return {f: getattr(inf, f) for f, _ in inf._fields_}
+
+    @property
+    def photons_done(self):
+        return self.info()["photons_done"]
+
+    def image(self):
+        """[rows, W, 3] float64, row 0 = bottom: ppm_render(nphotons=photons_done)["image"]."""
+        img = np.zeros((self.rows, self.width, 3), np.float64)
+        check(self._L.cgrt_ppm_session_image(self._h, img.ctypes.data, None))
+        return img
+
+    def rgb8(self):
+        """[rows, W, 3] uint8, top row first (contiguous rows only): ppm_render(..., want_rgb8=True)["rgb8"]."""
+        out = np.zeros((self.rows, self.width, 3), np.uint8)
+        check(self._L.cgrt_ppm_session_image(self._h, None, out.ctypes.data))
+        return out
+
+    def image_tensor(self, out=None, rgb8_out=None, stream=None):
+        """The image as a float64 [rows, W, 3] torch tensor on the scene's device, gathered on torch's current stream (or
+        `stream`) without a host copy.  rgb8_out (uint8 [rows, W, 3], optional) receives the tone-mapped bytes in the same
+        pass.  Returns `out`."""
+        import torch
+
+        dev = torch.device("cuda", self._scene.device)
+        if out is None:
+            out = torch.empty((self.rows, self.width, 3), dtype=torch.float64, device=dev)
+        assert out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (self.rows, self.width, 3)
+        if rgb8_out is not None:
+            assert rgb8_out.is_contiguous() and rgb8_out.dtype == torch.uint8 and rgb8_out.numel() == self.rows * self.width * 3
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(self._L.cgrt_ppm_session_image_device(self._h, out.data_ptr(),
+                                                    rgb8_out.data_ptr() if rgb8_out is not None else None, C.c_void_p(st)))
+        return out
+
+    def hitpoints(self):
+        """[n, 16] of the current state: ppm_render(want_hitpoints=True)["hp"] at photons_done photons."""
+        n = self.info()["hp_count"]
+        hp = np.zeros((max(n, 1), 16), np.float64)
+        cnt = C.c_uint64(0)
+        check(self._L.cgrt_ppm_session_hitpoints(self._h, hp.ctypes.data, n, C.byref(cnt)))
+        return hp[:n]
 
 
 def render(objs, width=1024, height=768, num_of_samples=1, camera=None, max_depth=5, seed=12345, device=0):

@@ -288,6 +288,52 @@ typedef struct cgrt_ppm_result {
 int cgrt_ppm_render(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, const cgrt_photons *ph,
                     cgrt_ppm_result *out);
 
+/* ---- resumable photon mapping: a live render() that photons are added to --------------------------------------
+ * A session keeps what cgrt_ppm_render frees when it returns: the hitpoint table, the pair buffers, the photon producer and
+ * a per-pixel index of the hitpoints.  Photon i draws from the keyed stream (seed, i) and a hitpoint replays its events in
+ * photon order, so after add_photons calls totalling k photons the image, rgb8 and hitpoints are those of cgrt_ppm_render
+ * with nphotons = k and the same other fields, bit for bit, whatever the chunk sizes, batch, pair_cap or halvings.
+ * A batch is applied whole or not at all: a failing add_photons (CGRT_ERR_LIMIT when one photon's pairs exceed the pair
+ * buffer, say) leaves the state of the first photons_done photons and the session usable.
+ * Lifetime and ordering: the scene must outlive its sessions; calls on a session, and on the sessions of one scene, are
+ * ordered by the caller like launches on one scene handle (see Threading above).  add_photons and image run on the null
+ * stream and synchronise, like cgrt_ppm_render; image_device runs on the caller's stream and the next add_photons waits for it.
+ * Device memory: up to ~3 GiB of pair buffers plus two event buffers of batch * 8 * 89 bytes stay allocated while the
+ * session lives (cgrt_ppm_session_info.device_bytes). */
+typedef struct cgrt_ppm_session cgrt_ppm_session; /* opaque */
+enum {
+    CGRT_PPM_SESSION_NO_LOOKAHEAD = 1 /* by default, when add_photons (or create) ends, the trace of the next batch from
+                                         `done` is enqueued on the session's producer stream, sized as the first batch of a call
+                                         of as many photons as the one that just ended ([done, done + batch) after create); a
+                                         next call that starts with exactly that batch uses it, any other drops it.  This flag
+                                         turns that off. */
+};
+/* Eye pass + table for grid (same rows / stripes rules as cgrt_ppm_render), then ph->nphotons photons (0 allowed).  ph's
+ * other fields (light, jitter, power, alpha, hashsize, seed, initial_radius, batch, pair_cap) are fixed for the session's
+ * life.  A grid without hitpoints is valid (its image is zero). */
+int cgrt_ppm_session_create(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, const cgrt_photons *ph,
+                            int flags, cgrt_ppm_session **out);
+/* Waits for anything in flight, then frees the session.  NULL is ignored. */
+void cgrt_ppm_session_destroy(cgrt_ppm_session *p);
+/* Traces photons [done, done + count) and applies them; returns when they are applied.  count >= 0. */
+int cgrt_ppm_session_add_photons(cgrt_ppm_session *p, int64_t count);
+/* Final gather at the current photon count (main.cpp:252-258), as cgrt_ppm_result.image / .rgb8.  HOST buffers; either may be
+ * NULL.  CGRT_ERR_INVALID before the first photon (the reference's flux / (PI r2 0)); rgb8 with stripes: CGRT_ERR_UNSUPPORTED. */
+int cgrt_ppm_session_image(const cgrt_ppm_session *p, double *image, uint8_t *rgb8);
+/* Same into DEVICE buffers on the session's device, enqueued on `stream` (a hipStream_t as void*, NULL = null stream). */
+int cgrt_ppm_session_image_device(const cgrt_ppm_session *p, double *image, uint8_t *rgb8, void *stream);
+/* Up to cap hp16 records (layout and table order of cgrt_ppm_result.hp16) of the current state; *count = hitpoints. */
+int cgrt_ppm_session_hitpoints(const cgrt_ppm_session *p, double *hp16, uint64_t cap, uint64_t *count);
+typedef struct cgrt_ppm_session_info {
+    int64_t photons_done;                                   /* photons applied                                       */
+    uint64_t hp_count, n_events, n_pairs, n_batch_halvings; /* as cgrt_ppm_result; sums over all photons so far       */
+    int64_t device_bytes;                                   /* device memory the session holds                        */
+    double ms_eye, ms_table;                                /* device time of the eye pass and table (at create)      */
+    double ms_photons;                                      /* photon stage, summed over create and every add_photons */
+    double ms_last_add, ms_last_image;                      /* the last add_photons (or create), the last gather     */
+} cgrt_ppm_session_info;
+int cgrt_ppm_session_get_info(const cgrt_ppm_session *p, cgrt_ppm_session_info *out);
+
 /* ---- row f2 of SURVEY.md section 8: tone map, flip, PNG (util.h:45-47, main.cpp:403-412) ----------------------
  * rgb8[(height-1-h)*width + w][c] = int(pow(1 - exp(-image[h][w][c]), 1/2.2) * 255 + .5) computed on `device`;
  * HOST buffers.  NaN and negative inputs give 0 (the reference's int(NaN) is undefined). */

@@ -389,6 +389,65 @@ inline void render_ppm(const std::vector<Object *> &objs, const RenderParams &rp
     }
 }
 
+// render() as a live, resumable render: the eye pass and hash table once, then photons added in as many steps as wanted
+// (cgrt_ppm_session).  After add_photons calls totalling k, image() equals render_ppm with k photons bit for bit.
+// pp.num_photon / pp.num_threads are not used here: no photon is traced until add_photons.
+class PpmSession {
+  public:
+    PpmSession(const std::vector<Object *> &objs, const RenderParams &rp, const PhotonParams &pp, bool lookahead = true)
+        : width_(rp.width), height_(rp.height), session_(nullptr) {
+        for (const Object *o : objs) o->add_to(sb_);
+        check(cgrt_scene_commit(sb_.scene, rp.device));
+        cgrt_camera cam;
+        rp.camorg.get(cam.cam);
+        cam.half_width = 10.0;
+        cam.focus_plane = rp.focus_plane;
+        cam.lens_radius = rp.depth_of_field ? rp.radius : 0.0;
+        cgrt_grid g{};
+        g.width = rp.width;
+        g.height = rp.height;
+        g.rows = rp.height;
+        g.stripe_nranks = 1;
+        g.spp = rp.num_of_samples;
+        g.spp_total = rp.num_of_samples;
+        g.max_depth = rp.max_depth;
+        g.seed = rp.seed;
+        cgrt_photons ph{};
+        pp.lightorg.get(ph.light);
+        ph.jitter = pp.jitter;
+        ph.power = pp.power;
+        ph.alpha = pp.alpha;
+        ph.nphotons = 0;
+        ph.hashsize = pp.hashsize;
+        ph.seed = pp.seed;
+        ph.initial_radius = pp.initial_radius;
+        check(cgrt_ppm_session_create(sb_.scene, &cam, &g, &ph, lookahead ? 0 : CGRT_PPM_SESSION_NO_LOOKAHEAD, &session_));
+    }
+    ~PpmSession() { cgrt_ppm_session_destroy(session_); }  // before sb_ destroys the scene
+    PpmSession(const PpmSession &) = delete;
+    PpmSession &operator=(const PpmSession &) = delete;
+
+    // traces photons [photons_done(), photons_done() + n) and applies them
+    void add_photons(long long n) { check(cgrt_ppm_session_add_photons(session_, n)); }
+    long long photons_done() const { return (long long)info().photons_done; }
+    // the gathered image (doubles, row 0 = bottom) and the bytes main.cpp:403-411 hands to stbi_write_png
+    void image(std::vector<double> &image, std::vector<unsigned char> &image_data) const {
+        image.assign((size_t)width_ * height_ * 3, 0.0);
+        image_data.assign((size_t)width_ * height_ * 3, 0);
+        check(cgrt_ppm_session_image(session_, image.data(), image_data.data()));
+    }
+    cgrt_ppm_session_info info() const {
+        cgrt_ppm_session_info inf{};
+        check(cgrt_ppm_session_get_info(session_, &inf));
+        return inf;
+    }
+
+  private:
+    int width_, height_;
+    SceneBuilder sb_;
+    cgrt_ppm_session *session_;
+};
+
 // stbi_write_png("test.png", width, height, 3, image_data, width * 3), main.cpp:412
 inline void write_png(const char *path, int width, int height, const std::vector<unsigned char> &image_data) {
     check(cgrt_write_png(path, width, height, image_data.data()));
