@@ -627,36 +627,75 @@ int cgrt_scene_tree_dump(const cgrt_scene *s, int t, int32_t *node_lr_size, int3
     return CGRT_OK;
 }
 
+}  // extern "C"
+
 // ---- LDS of a launch ----
 // A workgroup may use at most a CU's LDS (MI355X: 160 KiB): the kernel's static __shared__ bytes plus the dynamic bytes of
-// the launch.  Each launch family sizes its dynamic bytes in one place below and passes them through BIG_LDS, which refuses
-// a launch that would not fit (CGRT_ERR_LIMIT, naming the launch and the bytes) and asks for more than the default 64 KiB
-// where needed.  The static bytes are the compiler's (hipFuncGetAttributes); the static_asserts use kStaticLdsAllowance.
+// the launch.  Each launch family's dynamic bytes come from one function below, and every launch goes through
+// launch_checked, which refuses a launch that would not fit (CGRT_ERR_LIMIT, naming the launch and the bytes) and asks for
+// more than the default 64 KiB where needed.  The static bytes are the compiler's (hipFuncGetAttributes); the static_asserts
+// use kStaticLdsAllowance.
 static constexpr size_t kStaticLdsAllowance = 512;  // the eye kernels have 336 B (ROCm 7.2): wg_cnt, tile_entry, tl_rays, ...
 static constexpr size_t kWideStackLds = (size_t)kThreads * kWideLdsDepth * sizeof(uint2);
-static constexpr size_t kNodeCacheLds = (size_t)kNodeCache * sizeof(NodeRec);
-// LDS of the most general variant (Hitpoint capture, the eye pass's SPILL_GEN) besides its object list: pending-ray levels,
-// one BezLds per wave, the cached tree
-static size_t general_other_lds(const DeviceScene &d) {
-    return kStackBytes + (kThreads / 64) * sizeof(BezLds) + (d.cached_tree >= 0 ? (size_t)d.cached_nodes * sizeof(NodeRec) : 0);
+
+// The template flags of a trace_grid_kernel / trace_grid_sched_kernel instantiation
+struct EyeFlags {
+    bool trees, bez, dof, glass, sph, stats, hps, spill, hfonly;
+    int nt;  // threads per workgroup: 256 (32x8-pixel tiles) or 64 (Bezier scenes: one-wave workgroups on 16x4 tiles)
+    constexpr int id() const {
+        return (int)trees | (int)bez << 1 | (int)dof << 2 | (int)glass << 3 | (int)sph << 4 | (int)stats << 5 | (int)hps << 6 |
+               (int)spill << 7 | (int)hfonly << 8 | (nt == 64 ? 1 << 9 : 0);
+    }
+};
+// image order, the probe and the scheduled form: Bezier scenes share the tree-capable variants (one-wave workgroups)
+static constexpr EyeFlags image_flags(bool trees, bool bez, bool dof, bool glass, bool sph, bool stats) {
+    return {trees, bez, dof, glass, sph, stats, false, false, false, bez ? 64 : kThreads};
 }
+// the sphere loop reading the objects beyond the LDS list from `objs`
+static constexpr EyeFlags spill_sph_flags(bool dof, bool glass) { return {false, false, dof, glass, true, false, false, true, false, kThreads}; }
+// the most general body (trees, Bezier, pending rays): the Hitpoint capture (hps) and the eye pass's SPILL form
+static constexpr EyeFlags general_flags(bool dof, bool hps, bool spill) { return {true, true, dof, true, false, false, hps, spill, false, kThreads}; }
+// the light tiles: no Bezier or pending-ray code; with trees beside bump-mapped planes, or only their height-field walk (hfonly)
+static constexpr EyeFlags light_flags(bool trees, bool dof, bool hfonly) { return {trees, false, dof, false, false, false, false, false, hfonly, kThreads}; }
+
+// Dynamic LDS of an eye-pass launch, in the order of trace_grid_body's carve-up (cgrt_eye.hpp): pending-ray levels (GLASS) |
+// `resident` objects | one staging record per wave (SPILL) | one BezLds per wave (BEZ) | the cached tree's `cached_nodes`
+// (TREES) | the first entries of the wide walk's stack (TREES without GLASS or BEZ, when the scene has a wide tree).  The
+// HFONLY variant walks height fields only and gets neither of the last two.
+static constexpr size_t eye_lds(const EyeFlags &f, size_t resident, size_t cached_nodes, bool wide) {
+    const size_t waves = (size_t)f.nt / 64;
+    const bool walk = f.trees && !f.hfonly;
+    return (f.glass ? (f.nt == 64 ? TileGeom<64>::stack_bytes : TileGeom<kThreads>::stack_bytes) : 0) +
+           (resident + (f.spill ? waves : 0)) * sizeof(ObjRec) + (f.bez ? waves * sizeof(BezLds) : 0) +
+           (walk ? cached_nodes * sizeof(NodeRec) : 0) + (walk && !f.glass && !f.bez && wide ? kWideStackLds : 0);
+}
+static size_t eye_lds(const EyeFlags &f, const DeviceScene &d) {
+    return eye_lds(f, (size_t)d.n_lds, d.cached_tree >= 0 ? (size_t)d.cached_nodes : 0, d.has_wide != 0);
+}
+// primary_walk_kernel (cgrt_primwalk.hpp): `staged` objects | the wide walk's stack entries
+static constexpr size_t primary_walk_lds(size_t staged) { return staged * sizeof(ObjRec) + kWideStackLds; }
+// photon_trace_kernel (cgrt_photon.hpp): `resident` objects | one staging record per wave (SPILL) | one BezLds per wave (BEZ),
+// or else, without SPILL, the first entries of the wide walk's stack where photon_lds_stack asks for them
+static constexpr size_t photon_lds(size_t resident, bool spill, bool bez, bool wide_stack) {
+    return (resident + (spill ? kThreads / 64 : 0)) * sizeof(ObjRec) + (bez ? (kThreads / 64) * sizeof(BezLds) : 0) +
+           (!bez && !spill && wide_stack ? kWideStackLds : 0);
+}
+
+static constexpr bool fits_lds(size_t dyn) { return dyn + kStaticLdsAllowance <= kLdsBytes; }
 // Every launch that stages kLdsObjsMax objects fits beside its other LDS (the general variant lowers its count instead):
-// the eye pass without SPILL (glass: pending-ray levels; else the wide walk's stack; and the node cache), ...
-static_assert(kLdsObjsMax * sizeof(ObjRec) + std::max(kStackBytes, kWideStackLds) + kNodeCacheLds + kStaticLdsAllowance <= kLdsBytes,
-              "eye pass, 256-thread variants");
-// ... the one-wave Bezier variants, the sphere-only SPILL variant, the light variants, ...
-static_assert(kLdsObjsMax * sizeof(ObjRec) + TileGeom<64>::stack_bytes + sizeof(BezLds) + kNodeCacheLds + kStaticLdsAllowance <= kLdsBytes,
+// the eye pass without SPILL, with and without glass (the light variants are the latter), ...
+static_assert(fits_lds(eye_lds(image_flags(true, false, false, true, false, false), kLdsObjsMax, kNodeCache, true)) &&
+                  fits_lds(eye_lds(image_flags(true, false, false, false, false, false), kLdsObjsMax, kNodeCache, true)),
+              "eye pass, 256-thread and light variants");
+// ... the one-wave Bezier variants, the sphere-only SPILL variant, ...
+static_assert(fits_lds(eye_lds(image_flags(true, true, false, true, false, false), kLdsObjsMax, kNodeCache, true)),
               "eye pass, one-wave Bezier variants");
-static_assert((kLdsObjsMax + kThreads / 64) * sizeof(ObjRec) + kStackBytes + kStaticLdsAllowance <= kLdsBytes, "eye pass, SPILL_SPH");
-static_assert(kLdsObjsMax * sizeof(ObjRec) + kNodeCacheLds + kWideStackLds + kStaticLdsAllowance <= kLdsBytes, "light variants");
+static_assert(fits_lds(eye_lds(spill_sph_flags(false, true), kLdsObjsMax, 0, false)), "eye pass, SPILL_SPH");
 // ... primary_walk_kernel (all objects staged when it finishes units; it runs only when none is spilled), the photon launches
-static_assert(kLdsObjsMax * sizeof(ObjRec) + kWideStackLds + kStaticLdsAllowance <= kLdsBytes, "primary_walk_kernel");
-static_assert((kLdsObjsMax + kThreads / 64) * sizeof(ObjRec) + (kThreads / 64) * sizeof(BezLds) + kStaticLdsAllowance <= kLdsBytes,
-              "photon_trace_kernel");
+static_assert(fits_lds(primary_walk_lds(kLdsObjsMax)), "primary_walk_kernel");
+static_assert(fits_lds(photon_lds(kLdsObjsMax, true, true, false)), "photon_trace_kernel");
 // The general variant keeps at least 600 objects resident whatever the scene.
-static_assert((kLdsBytes - kStackBytes - (kThreads / 64) * sizeof(BezLds) - kNodeCacheLds - kStaticLdsAllowance) / sizeof(ObjRec) -
-                      kThreads / 64 >= 600,
-              "general variant: resident objects");
+static_assert(fits_lds(eye_lds(general_flags(false, false, true), 600, kNodeCache, false)), "general variant: resident objects");
 
 static size_t device_lds_bytes(int device) {
     static std::mutex mu;
@@ -683,24 +722,6 @@ static size_t kernel_static_lds(const void *fn) {
     else (void)hipGetLastError();
     return known[fn] = b;
 }
-// Objects a launch may keep resident beside `other` bytes of LDS in a kernel with `static_bytes` of its own: the scene's
-// n_lds when the whole launch fits, else as many as fit beside one staging record per wave (the SPILL variant then reads
-// the rest from `objs`).
-static int resident_objs(const DeviceScene &d, size_t other, size_t static_bytes, size_t limit, int waves) {
-    if (obj_list_lds(d, waves) + other + static_bytes <= limit) return d.n_lds;
-    const long long room = (long long)limit - (long long)(other + static_bytes);
-    const long long r = room / (long long)sizeof(ObjRec) - waves;
-    return (int)std::max(0ll, std::min(r, (long long)d.n_lds));
-}
-// The launch's copy of the scene with `resident` objects in LDS.  A run of planes tested as a group (plane_run) is read from
-// the LDS list, so it ends inside it: a shorter run is the same test over fewer planes.
-static DeviceScene with_resident(const DeviceScene &d, int resident) {
-    DeviceScene c = d;
-    c.n_lds = resident;
-    if (c.prun_end > resident) c.prun_end = resident;
-    if (c.prun_end - c.prun_begin < 3) c.prun_begin = c.prun_end = 0;
-    return c;
-}
 static int lds_check(const void *fn, size_t dyn, int device, const char *what) {
     const size_t st = kernel_static_lds(fn), lim = device_lds_bytes(device);
     if (st + dyn > lim)
@@ -711,43 +732,235 @@ static int lds_check(const void *fn, size_t dyn, int device, const char *what) {
         (void)hipGetLastError();  // not needed / not supported by this runtime: the launch itself will tell
     return CGRT_OK;
 }
-// Checks a launch's LDS (returns from the enclosing function if it does not fit) and asks for more than 64 KiB where needed.
-// The attribute is per kernel; setting it again is harmless.
-#define BIG_LDS(kernel, bytes, what)                                                                                          \
-    do {                                                                                                                      \
-        if (const int lds_rc_ = lds_check(reinterpret_cast<const void *>(&kernel), (bytes), s->device, (what))) return lds_rc_; \
-    } while (0)
-
-// Objects the most general variant keeps resident for this scene: the Hitpoint capture (hps) or the eye pass's SPILL_GEN.
-// Below the scene's n_lds when the list would not fit beside the variant's other LDS; the launch then runs the SPILL form.
-static int general_resident(const cgrt_scene *s, bool dof, bool hps) {
-#define GENERAL(D, H) reinterpret_cast<const void *>(&trace_grid_kernel<true, true, D, true, false, false, H, 256, true>)
-    const void *k = hps ? (dof ? GENERAL(true, true) : GENERAL(false, true)) : (dof ? GENERAL(true, false) : GENERAL(false, false));
-#undef GENERAL
-    return resident_objs(s->dev, general_other_lds(s->dev), kernel_static_lds(k), device_lds_bytes(s->device), kThreads / 64);
+template <class T> struct same_type { using type = T; };
+// Launches `fn` with `lds` bytes of dynamic LDS once lds_check has passed it (returns its error otherwise).  The attribute is
+// per kernel; setting it again is harmless.  A failed launch shows in hipGetLastError, as with <<<...>>>.
+template <class... P>
+static int launch_checked(void (*fn)(P...), const char *what, int device, dim3 grid, dim3 block, size_t lds, hipStream_t st,
+                          typename same_type<P>::type... args) {
+    const void *k = reinterpret_cast<const void *>(fn);
+    if (const int rc = lds_check(k, lds, device, what)) return rc;
+    void *argv[] = {&args...};
+    (void)hipLaunchKernel(k, grid, block, argv, lds, st);
+    return CGRT_OK;
 }
 
-// Which instantiation of trace_grid_kernel a launch uses (chosen from the scene's materials and the camera).
-struct GridVariant {
-    bool trees, bez, dof, glass, sph, stats;
-    bool sched;  // the scheduled form (trace_grid_sched_kernel): heavy-tile unit queue in front of the tile workgroups
-    int nt;  // threads per workgroup: 256 (32x8-pixel tiles) or 64 (Bezier scenes: one-wave workgroups on 16x4 tiles)
+// The instantiations of the eye kernels that are launched -- only these are compiled (every combination of the flags would
+// multiply the library's build time and size).
+using GridKernel = void (*)(DeviceScene, GridParams, float *, uint32_t *, unsigned long long *, HitpointSink);
+using SchedKernel = void (*)(DeviceScene, GridParams, float *, uint32_t *, unsigned long long *);
+struct EyeKernels {
+    int id;             // EyeFlags::id()
+    GridKernel grid;    // trace_grid_kernel
+    SchedKernel sched;  // trace_grid_sched_kernel where the scheduled form runs these flags, else nullptr
 };
-static GridVariant grid_variant(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid) {
-    GridVariant v;
-    v.bez = s->dev.has_bezier != 0;
-    v.trees = s->dev.has_mesh != 0 || v.bez;  // Bezier scenes share the tree-capable variants
-    v.dof = cam->lens_radius > 0;
-    v.glass = s->dev.has_glass != 0 && grid->max_depth > 1;
-    v.sph = !v.trees && s->dev.all_spheres != 0;
-    v.stats = (grid->flags & CGRT_GRID_STATS) != 0 && s->dev.has_mesh != 0 && !v.bez;
-    v.nt = v.bez ? 64 : kThreads;
-    v.sched = grid->spp >= 4 && !(grid->flags & CGRT_GRID_NO_REORDER) && (!((s->dev.has_mesh == 0 && s->dev.has_bezier == 0) || s->dev.single_ray != 0) || (grid->flags & CGRT_GRID_FORCE_REORDER)) &&  // (CGRT_FORCE_REORDER, a measurement aid, is not reflected here)
-              ((size_t)((grid->width + kWaveTileW - 1) / kWaveTileW) * ((grid->rows + kWaveTileH - 1) / kWaveTileH)) > 1;
-    return v;
+template <int T, int B, int D, int G, int P, int S, int H = 0, int NT = kThreads, int SP = 0, int HF = 0>
+static constexpr EyeKernels gk() {  // trace_grid_kernel only
+    return {EyeFlags{T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, SP != 0, HF != 0, NT}.id(),
+            &trace_grid_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, NT, SP != 0, HF != 0>, nullptr};
+}
+template <int T, int B, int D, int G, int P, int S, int NT = kThreads>
+static constexpr EyeKernels gsk() {  // both forms
+    EyeKernels e = gk<T, B, D, G, P, S, 0, NT>();
+    e.sched = &trace_grid_sched_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, NT>;
+    return e;
+}
+//                        TREES BEZ DOF GLASS SPH STATS [HPS NT SPILL HFONLY]
+static const EyeKernels kEyeKernels[] = {
+    // image order, the probe and the scheduled form (the light variants are the tree and plain ones without GLASS or STATS)
+    gsk<1, 1, 0, 0, 0, 0, 64>(), gsk<1, 1, 0, 1, 0, 0, 64>(), gsk<1, 1, 1, 0, 0, 0, 64>(), gsk<1, 1, 1, 1, 0, 0, 64>(),
+    gsk<1, 0, 0, 0, 0, 0>(), gsk<1, 0, 0, 1, 0, 0>(), gsk<1, 0, 1, 0, 0, 0>(), gsk<1, 0, 1, 1, 0, 0>(),
+    gsk<1, 0, 0, 0, 0, 1>(), gsk<1, 0, 0, 1, 0, 1>(), gsk<1, 0, 1, 0, 0, 1>(), gsk<1, 0, 1, 1, 0, 1>(),
+    gsk<0, 0, 0, 0, 1, 0>(), gsk<0, 0, 0, 1, 1, 0>(), gsk<0, 0, 1, 0, 1, 0>(), gsk<0, 0, 1, 1, 1, 0>(),
+    gsk<0, 0, 0, 0, 0, 0>(), gsk<0, 0, 0, 1, 0, 0>(), gsk<0, 0, 1, 0, 0, 0>(), gsk<0, 0, 1, 1, 0, 0>(),
+    // SPILL: spheres, and the general body; the Hitpoint capture (general, HPS) with and without SPILL
+    gk<0, 0, 0, 0, 1, 0, 0, 256, 1>(), gk<0, 0, 0, 1, 1, 0, 0, 256, 1>(), gk<0, 0, 1, 0, 1, 0, 0, 256, 1>(), gk<0, 0, 1, 1, 1, 0, 0, 256, 1>(),
+    gk<1, 1, 0, 1, 0, 0, 0, 256, 1>(), gk<1, 1, 1, 1, 0, 0, 0, 256, 1>(),
+    gk<1, 1, 0, 1, 0, 0, 1, 256, 0>(), gk<1, 1, 1, 1, 0, 0, 1, 256, 0>(), gk<1, 1, 0, 1, 0, 0, 1, 256, 1>(), gk<1, 1, 1, 1, 0, 0, 1, 256, 1>(),
+    // light tiles beside bump-mapped planes that need only the height-field walk
+    gk<1, 0, 0, 0, 0, 0, 0, 256, 0, 1>(), gk<1, 0, 1, 0, 0, 0, 0, 256, 0, 1>(),
+};
+static const EyeKernels *eye_kernels(const EyeFlags &f) {
+    for (const EyeKernels &e : kEyeKernels)
+        if (e.id == f.id()) return &e;
+    return nullptr;
 }
 
-static bool glass_possible(const cgrt_scene *s, const cgrt_grid *grid) { return s->dev.has_glass != 0 && grid->max_depth > 1; }
+// The launch's copy of the scene with `resident` objects in LDS.  A run of planes tested as a group (plane_run) is read from
+// the LDS list, so it ends inside it: a shorter run is the same test over fewer planes.
+static DeviceScene with_resident(const DeviceScene &d, int resident) {
+    DeviceScene c = d;
+    c.n_lds = resident;
+    if (c.prun_end > resident) c.prun_end = resident;
+    if (c.prun_end - c.prun_begin < 3) c.prun_begin = c.prun_end = 0;
+    return c;
+}
+// Objects the most general variant (the Hitpoint capture, or the eye pass's SPILL form) keeps resident: the scene's n_lds when
+// its list fits beside the variant's other LDS, else as many as fit beside one staging record per wave (the SPILL variant
+// then reads the rest from `objs`).
+static int general_resident(const cgrt_scene *s, bool dof, bool hps) {
+    const DeviceScene &d = s->dev;
+    const size_t st = kernel_static_lds(reinterpret_cast<const void *>(eye_kernels(general_flags(dof, hps, true))->grid));
+    const size_t lim = device_lds_bytes(s->device);
+    if (eye_lds(general_flags(dof, hps, d.n_objs > d.n_lds), d) + st <= lim) return d.n_lds;
+    const long long room = (long long)lim - (long long)(st + eye_lds(general_flags(dof, hps, true), with_resident(d, 0)));
+    return (int)std::max(0ll, std::min(room / (long long)sizeof(ObjRec), (long long)d.n_lds));
+}
+
+// ---- the eye pass's environment switches (measurement and development aids) ----
+// Read once per process, at the first launch, except CGRT_TIMELINE_FILE, which every launch reads.
+static const char *env_str(const char *name) { const char *e = std::getenv(name); return e ? e : ""; }
+static bool env_on(const char *name) { const char *e = env_str(name); return *e && *e != '0'; }
+static int positive_or(int v, int def) { return v > 0 ? v : def; }
+struct EyeKnobs {
+    bool force_reorder = env_on("CGRT_FORCE_REORDER");  // schedule sphere-only scenes too
+    long long defer_bytes = std::atoll(env_str("CGRT_DEFER_BYTES"));  // <= 0: the default
+    int heavy_div = positive_or(std::atoi(env_str("CGRT_HEAVY_DIV")), 32);
+    int units_per_item = (positive_or(std::atoi(env_str("CGRT_UNITS_PER_ITEM")), 256) + 63) / 64 * 64;  // whole waves
+    bool no_primwalk = env_on("CGRT_NO_PRIMWALK");
+    bool pw_no_finish = env_on("CGRT_PW_NO_FINISH");
+    int pw_refill = positive_or(std::atoi(env_str("CGRT_PW_REFILL")), 16);
+    int pw_rounds = positive_or(std::atoi(env_str("CGRT_PW_ROUNDS")), 8);
+    int lds_pad = std::atoi(env_str("CGRT_LDS_PAD"));  // extra dynamic LDS bytes of the main launch
+    bool no_hfonly = env_on("CGRT_NO_HFONLY");
+    bool no_tile_queue = env_on("CGRT_NO_TILE_QUEUE");
+    bool plan_dump = env_on("CGRT_PLAN_DUMP");
+    const char *timeline_file = nullptr;  // CGRT_TIMELINE_FILE (nullptr: off)
+};
+static EyeKnobs eye_knobs() {
+    static const EyeKnobs once;
+    EyeKnobs k = once;
+    const char *tf = env_str("CGRT_TIMELINE_FILE");
+    k.timeline_file = *tf ? tf : nullptr;
+    return k;
+}
+
+// ---- the eye pass's launch plan ----
+enum class EyeForm { Image, Sched, SpillSph, SpillGen, Capture, Light, LightHF };
+// One launch of the eye pass: which kernel (form and template flags), the scene as it sees it and its dynamic LDS
+struct EyeLaunch {
+    EyeForm form;
+    EyeFlags k;       // k.nt is the block size
+    DeviceScene dev;  // the general variant's copy holds its resident objects (with_resident)
+    size_t lds;       // dynamic LDS bytes
+    const char *what() const {  // the launch's name in a refusal
+        static const char *const names[] = {"eye pass", "eye pass", "eye pass, SPILL (spheres)", "eye pass, SPILL (general)",
+                                            "Hitpoint capture", "eye pass, light tiles", "eye pass, light tiles (HFONLY)"};
+        return form <= EyeForm::Sched && k.bez ? "eye pass (Bezier)" : names[(int)form];
+    }
+};
+
+// The eye pass's main launch for (scene, camera, grid): the Hitpoint capture (capture), else cgrt_trace_grid's.
+static EyeLaunch eye_launch(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, const EyeKnobs &kn, bool capture) {
+    const DeviceScene &d = s->dev;
+    const bool dof = cam->lens_radius > 0, glass = d.has_glass != 0 && grid->max_depth > 1;
+    const bool spill = d.n_objs > d.n_lds;  // more top-level objects than the LDS list holds (kLdsObjsMax)
+    EyeLaunch L;
+    L.dev = d;
+    if (capture || (spill && !d.all_spheres)) {
+        // the most general variant serves every scene, with as many objects resident as fit beside its other LDS; the
+        // capture is a verification / hand-off path, not the hot path
+        L.form = capture ? EyeForm::Capture : EyeForm::SpillGen;
+        L.dev = with_resident(d, general_resident(s, dof, capture));
+        L.k = general_flags(dof, capture, L.dev.n_objs > L.dev.n_lds);
+    } else if (spill) {
+        L.form = EyeForm::SpillSph;
+        L.k = spill_sph_flags(dof, glass);
+    } else {
+        const bool bez = d.has_bezier != 0, trees = d.has_mesh != 0 || bez;
+        L.k = image_flags(trees, bez, dof, glass, !trees && d.all_spheres != 0,
+                          (grid->flags & CGRT_GRID_STATS) != 0 && d.has_mesh != 0 && !bez);
+        // Scenes of spheres and plain planes are left in image order: without a tree or a Newton solve behind a ray, a tile's
+        // cost varies only with the size of its ray trees (<= 31 rays per sample), the per-lane sample loop already keeps 97 %
+        // of the lanes busy, and measured on C2 the unit queue costs 13 % more VALU instructions (at 93 % VALU busy) and 0.9 GB
+        // of deferred values per frame for a gain within the noise (4.0-4.2 ms either way); a room of five planes, 4096x4096
+        // spp 4: 2.2 ms scheduled (probe and plan for nothing), 1.0 ms in image order.
+        // The same holds when every ray tree is a single ray (diffuse planes, bump-mapped or not, and diffuse spheres): a room
+        // with the stone floor, 8192 x 512 rows at spp 16: floor band 7.7 ms scheduled (every tile of a uniform frame counts as
+        // heavy), 5.4 ms in image order; wall band 4.0 and 1.7 ms.
+        const bool plain_scene = (d.has_mesh == 0 && d.has_bezier == 0) || d.single_ray != 0;  // has_mesh: any tree, a bump floor's included
+        const size_t n_wt = (size_t)((grid->width + kWaveTileW - 1) / kWaveTileW) * ((grid->rows + kWaveTileH - 1) / kWaveTileH);
+        const bool reorder = grid->spp >= 4 && !(grid->flags & CGRT_GRID_NO_REORDER) && n_wt > 1 && n_wt < (1u << 30) &&
+                             (!plain_scene || (grid->flags & CGRT_GRID_FORCE_REORDER) || kn.force_reorder);
+        L.form = reorder ? EyeForm::Sched : EyeForm::Image;
+    }
+    L.lds = eye_lds(L.k, L.dev) + (L.form == EyeForm::Image || L.form == EyeForm::Sched ? (size_t)kn.lds_pad : 0);
+    return L;
+}
+// The light tiles' launch beside the scheduled form (classify_kernel): bump-mapped planes take the tree-capable variant (the
+// same LDS carve-up as the main launch's), or only its height-field walk where that is all they need.
+static EyeLaunch light_launch(const DeviceScene &d, bool dof, const EyeKnobs &kn) {
+    const bool trees = d.light_trees != 0, hf = trees && d.light_hf_only && !kn.no_hfonly;
+    EyeLaunch L;
+    L.form = hf ? EyeForm::LightHF : EyeForm::Light;
+    L.k = light_flags(trees, dof, hf);
+    L.dev = d;
+    L.lds = eye_lds(L.k, d);
+    return L;
+}
+// Launches the plan's kernel: trace_grid_sched_kernel when `sched`, else trace_grid_kernel
+static int launch_eye(const EyeLaunch &L, bool sched, int device, const GridParams &g, dim3 gd, hipStream_t st, float *rgb,
+                      uint32_t *nhit, unsigned long long *cnt, HitpointSink sink = HitpointSink{nullptr, nullptr, 0}) {
+    const dim3 block((unsigned)L.k.nt);
+    const EyeKernels *e = eye_kernels(L.k);
+    if (e && sched && e->sched) return launch_checked(e->sched, L.what(), device, gd, block, L.lds, st, L.dev, g, rgb, nhit, cnt);
+    if (e && !sched) return launch_checked(e->grid, L.what(), device, gd, block, L.lds, st, L.dev, g, rgb, nhit, cnt, sink);
+    return fail(CGRT_ERR_UNSUPPORTED, std::string(L.what()) + ": no kernel built for this variant");
+}
+
+// The GridParams of a launch over `grid` seen from `cam`, every scheduling, chunk and primary-walk field at its default:
+// row-major tiles, one workgroup per tile with all its samples, no probe, no light split, nothing deferred or walked ahead
+// (fields not named here are 0 / nullptr).
+static GridParams grid_params(const cgrt_camera *cam, const cgrt_grid *grid) {
+    GridParams g{};
+    g.W = grid->width;
+    g.H = grid->height;
+    g.rows = grid->rows;
+    g.row_offset = grid->row_offset;
+    g.stripe_rows = grid->stripe_rows;
+    g.stripe_rank = grid->stripe_rank;
+    g.stripe_nranks = grid->stripe_nranks;
+    g.spp = grid->spp;
+    g.sample_offset = grid->sample_offset;
+    g.max_depth = grid->max_depth;
+    g.accumulate = (grid->flags & CGRT_GRID_ACCUMULATE) ? 1 : 0;
+    g.inv_spp_total = 1.0 / (double)grid->spp_total;
+    g.seed = grid->seed;
+    for (int k = 0; k < 3; k++) g.cam[k] = cam->cam[k];
+    g.half_width = cam->half_width;
+    g.focus_plane = cam->focus_plane;
+    g.lens_radius = cam->lens_radius;
+    g.chunks = 1;
+    g.chunk_spp = grid->spp;
+    g.items_per_tile = 1;
+    g.units_per_item = 256;
+    g.maxhp = 16;
+    g.prim_obj = -1;
+    g.pw_refill = 16;
+    g.pw_rounds = 8;
+    return g;
+}
+
+// The scheduler's deferred buffer: per heavy tile, its Hitpoint values [spp][maxhp][64 px][3], their counts [spp][64 px]
+// (padded to 8 bytes), the pixel constants [7][64] and, with the primary walk, its distances and triangles [spp][64].  Each
+// array holds kmax heavy tiles, one array after another.
+struct DeferLayout {
+    size_t vals, cnt, pconst, prim_len, prim_tri;  // bytes per heavy tile
+    DeferLayout(int spp, int maxhp, bool prim)
+        : vals((size_t)spp * 64 * (size_t)maxhp * 3 * sizeof(double)), cnt(((size_t)spp * 64 + 7) & ~(size_t)7),
+          pconst(7 * 64 * sizeof(double)), prim_len(prim ? (size_t)spp * 64 * sizeof(double) : 0),
+          prim_tri(prim ? (size_t)spp * 64 * sizeof(int32_t) : 0) {}
+    size_t per_tile() const { return vals + cnt + pconst + prim_len + prim_tri; }
+    void place(GridParams &g, unsigned char *base, size_t kmax) const {
+        g.dvals = reinterpret_cast<double *>(base);
+        g.dcnt = base + kmax * vals;
+        g.pconst = reinterpret_cast<double *>(base + kmax * (vals + cnt));
+        if (prim_len) {
+            g.prim_len = reinterpret_cast<const double *>(base + kmax * (vals + cnt + pconst));
+            g.prim_tri = reinterpret_cast<const int32_t *>(base + kmax * (vals + cnt + pconst + prim_len));
+        }
+    }
+};
 
 static int check_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *g) {
     if (!s || !cam || !g) return fail(CGRT_ERR_INVALID, "null argument");
@@ -766,28 +979,20 @@ static int check_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_gr
     return CGRT_OK;
 }
 
+extern "C" {
+
 int cgrt_trace_grid_variant(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, char *name, size_t cap) {
     int rc = check_grid(s, cam, grid);
     if (rc) return rc;
     if (!name || cap == 0) return fail(CGRT_ERR_INVALID, "null name buffer");
-    const GridVariant v = grid_variant(s, cam, grid);
-    if (grid->flags & CGRT_GRID_HITPOINTS) {  // the Hitpoint capture's launch
-        ON_DEVICE(s->device);
-        const bool spill = s->dev.n_objs > general_resident(s, v.dof, true);
-        std::snprintf(name, cap, "trace_grid_kernel<TREES=1,BEZ=1,DOF=%d,GLASS=1,SPH=0,STATS=0,HPS=1,NT=256%s>", (int)v.dof,
-                      spill ? ",SPILL=1" : "");
-        return CGRT_OK;
-    }
-    if (s->dev.n_objs > s->dev.n_lds) {
-        if (s->dev.all_spheres)
-            std::snprintf(name, cap, "trace_grid_kernel<TREES=0,BEZ=0,DOF=%d,GLASS=%d,SPH=1,STATS=0,HPS=0,NT=256,SPILL=1>", (int)v.dof, (int)v.glass);
-        else
-            std::snprintf(name, cap, "trace_grid_kernel<TREES=1,BEZ=1,DOF=%d,GLASS=1,SPH=0,STATS=0,HPS=0,NT=256,SPILL=1>", (int)v.dof);
-        return CGRT_OK;
-    }
-    std::snprintf(name, cap, "trace_grid_%skernel<TREES=%d,BEZ=%d,DOF=%d,GLASS=%d,SPH=%d,STATS=%d,%sNT=%d>",
-                  v.sched ? "sched_" : "", (int)v.trees, (int)v.bez, (int)v.dof, (int)v.glass, (int)v.sph, (int)v.stats,
-                  v.sched ? "" : "HPS=0,", v.nt);
+    ON_DEVICE(s->device);
+    // CGRT_GRID_HITPOINTS: the Hitpoint capture's launch
+    const EyeLaunch L = eye_launch(s, cam, grid, eye_knobs(), (grid->flags & CGRT_GRID_HITPOINTS) != 0);
+    const EyeFlags &k = L.k;
+    const bool sched = L.form == EyeForm::Sched;
+    std::snprintf(name, cap, "trace_grid_%skernel<TREES=%d,BEZ=%d,DOF=%d,GLASS=%d,SPH=%d,STATS=%d,%sNT=%d%s>", sched ? "sched_" : "",
+                  (int)k.trees, (int)k.bez, (int)k.dof, (int)k.glass, (int)k.sph, (int)k.stats,
+                  sched ? "" : (k.hps ? "HPS=1," : "HPS=0,"), k.nt, k.spill ? ",SPILL=1" : "");
     return CGRT_OK;
 }
 
@@ -796,36 +1001,22 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     int rc = check_grid(s, cam, grid);
     if (rc) return rc;
     if (!rgb) return fail(CGRT_ERR_INVALID, "null rgb");
-    GridParams g;
-    g.W = grid->width;
-    g.H = grid->height;
-    g.rows = grid->rows;
-    g.row_offset = grid->row_offset;
-    g.stripe_rows = grid->stripe_rows;
-    g.stripe_rank = grid->stripe_rank;
-    g.stripe_nranks = grid->stripe_nranks;
-    g.spp = grid->spp;
-    g.sample_offset = grid->sample_offset;
-    g.max_depth = grid->max_depth;
-    g.accumulate = (grid->flags & CGRT_GRID_ACCUMULATE) ? 1 : 0;
-    g.inv_spp_total = 1.0 / (double)grid->spp_total;
-    g.seed = grid->seed;
-    for (int k = 0; k < 3; k++) g.cam[k] = cam->cam[k];
-    g.half_width = cam->half_width;
-    g.focus_plane = cam->focus_plane;
-    g.lens_radius = cam->lens_radius;
-
-    g.xcd_tiles = (s->dev.has_mesh && !s->dev.has_bezier) ? 1 : 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    auto *cnt = reinterpret_cast<unsigned long long *>(counters);
+    // launch on the scene's device whatever the caller's current device is (one host thread may drive several GPUs)
+    ON_DEVICE(s->device);
+    const EyeKnobs kn = eye_knobs();
+    const EyeLaunch L = eye_launch(s, cam, grid, kn, false);
+    GridParams g = grid_params(cam, grid);
+    g.xcd_tiles = (!L.k.spill && s->dev.has_mesh && !s->dev.has_bezier) ? 1 : 0;
+    g.units_per_item = kn.units_per_item;
+    g.maxhp = L.k.glass ? 16 : 1;  // Hitpoints per sample: a mirror chain ends in one, a glass tree of depth 5 in <= 16
+    g.pw_refill = kn.pw_refill;
+    g.pw_rounds = kn.pw_rounds;
     // Split a tile's samples over several workgroups (CGRT_GRID_SPLIT_SAMPLES, opt-in for every scene since the cost
     // scheduler balances Bezier scenes too): chunks of >= 16 samples, at most 16 chunks, at most 4 GiB of chunk sums.
-    g.chunks = 1;
-    g.chunk_spp = grid->spp;
-    g.partial = nullptr;
-    g.partial_nhit = nullptr;
-    g.timeline = nullptr;
     const size_t npx_all = (size_t)grid->rows * grid->width;
-    const bool spill = s->dev.n_objs > s->dev.n_lds;  // image order, whole tiles (see the SPILL launch below)
-    if ((grid->flags & CGRT_GRID_SPLIT_SAMPLES) && grid->spp >= 32 && !spill) {
+    if ((grid->flags & CGRT_GRID_SPLIT_SAMPLES) && grid->spp >= 32 && !L.k.spill) {
         int chunks = grid->spp / 16;
         if (chunks > 16) chunks = 16;
         while (chunks > 1 && (size_t)chunks * npx_all * 28 > ((size_t)4 << 30)) chunks--;
@@ -835,18 +1026,19 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
         }
     }
     // Bezier scenes run one-wave workgroups on 16x4 tiles (TileGeom<64>): waves over the vase outlast their neighbours ~100x
-    const bool one_wave = s->dev.has_bezier != 0;
-    const int waves_per_block = one_wave ? 1 : kThreads / 64;
+    const bool one_wave = L.k.nt == 64;
+    const int waves_per_block = L.k.nt / 64;
     const int tile_blocks = one_wave ? tile_grid_blocks(g.W, g.rows, false, TileGeom<64>::W, TileGeom<64>::H)
                                      : tile_grid_blocks(g.W, g.rows, g.xcd_tiles != 0);
-    const dim3 natural_dim((unsigned)(tile_blocks * g.chunks)), block(one_wave ? 64 : kThreads);
-    size_t lds = obj_list_lds(s->dev, waves_per_block);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    auto *cnt = reinterpret_cast<unsigned long long *>(counters);
-    // launch on the scene's device whatever the caller's current device is (one host thread may drive several GPUs)
-    ON_DEVICE(s->device);
-    const GridVariant gv = grid_variant(s, cam, grid);
-    const bool trees = s->dev.has_mesh != 0, dof = gv.dof, bez = gv.bez, glass = gv.glass, stats = gv.stats;
+    dim3 grid_dim((unsigned)(tile_blocks * g.chunks));
+    if (L.k.spill) {
+        // More top-level objects than the LDS list holds: the SPILL variants, in image order, whole tiles.  Such scenes are
+        // bound by their object loop, not by tile imbalance.
+        if ((rc = launch_eye(L, false, s->device, g, grid_dim, st, rgb, nhit, cnt))) return rc;
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(CGRT_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
+        return CGRT_OK;
+    }
     // Cost-aware scheduling ("classify -> probe -> plan -> render -> ordered sum"; DESIGN.md sections 4.6-4.7).  A frame's cost
     // is concentrated in a few tiles (a glass mesh: one 32x8 tile ran 38 of the frame's 46 ms while four of the eight XCDs
     // were idle after 6 ms), the hardware hands out workgroups in block-index order, and a tile is bound to one wave per
@@ -860,58 +1052,37 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     // adds the heavy tiles' Hitpoint values in the reference's order.  The image does not depend on any of this -- every
     // Hitpoint value is added to its pixel in sample order, emission order within a sample --: identical bits and counters;
     // the probe costs 1/spp of the frame and the whole scheme is skipped below 4 samples per pixel or on request
-    // (CGRT_GRID_NO_REORDER).
+    // (CGRT_GRID_NO_REORDER); eye_launch decides it.
     const int wtiles_x = (g.W + kWaveTileW - 1) / kWaveTileW, wtiles_y = (g.rows + kWaveTileH - 1) / kWaveTileH;
     const size_t n_wt = (size_t)wtiles_x * wtiles_y;
-    static const bool env_force_reorder = [] { const char *e = std::getenv("CGRT_FORCE_REORDER"); return e && *e && *e != '0'; }();
-    // Scenes of spheres and plain planes are left in image order: without a tree or a Newton solve behind a ray, a tile's cost
-    // varies only with the size of its ray trees (<= 31 rays per sample), the per-lane sample loop already keeps 97 % of the
-    // lanes busy, and measured on C2 the unit queue costs 13 % more VALU instructions (at 93 % VALU busy) and 0.9 GB of deferred
-    // values per frame for a gain within the noise (4.0-4.2 ms either way); a room of five planes, 4096x4096 spp 4: 2.2 ms
-    // scheduled (probe and plan for nothing), 1.0 ms in image order.
-    // The same holds when every ray tree is a single ray (diffuse planes, bump-mapped or not, and diffuse spheres): a room with the
-    // stone floor, 8192 x 512 rows at spp 16: floor band 7.7 ms scheduled (every tile of a uniform frame counts as heavy), 5.4 ms
-    // in image order; wall band 4.0 and 1.7 ms.
-    const bool plain_scene = (s->dev.has_mesh == 0 && s->dev.has_bezier == 0) || s->dev.single_ray != 0;  // has_mesh: any tree, a bump floor's included
-    const bool reorder = !spill && grid->spp >= 4 && !(grid->flags & CGRT_GRID_NO_REORDER) && n_wt > 1 && n_wt < (1u << 30) &&
-                         (!plain_scene || (grid->flags & CGRT_GRID_FORCE_REORDER) || env_force_reorder);
-    static const long long env_defer_bytes = [] { const char *e = std::getenv("CGRT_DEFER_BYTES"); return e ? std::atoll(e) : 0ll; }();
-    static const int env_heavy_div = [] { const char *e = std::getenv("CGRT_HEAVY_DIV"); return e ? std::atoi(e) : 0; }();
-    static const int env_units = [] { const char *e = std::getenv("CGRT_UNITS_PER_ITEM"); return e ? std::atoi(e) : 0; }();
-    // deferred Hitpoint values: up to 12 GiB, at most an eighth of THIS scene's device (MI355X: 288 GB; read at commit -- a
-    // process may drive devices of different sizes); allocated once per scene handle, as large as the biggest launch needed it
-    const size_t defer_budget = env_defer_bytes > 0 ? (size_t)env_defer_bytes : std::min((size_t)12 << 30, s->mem_total / 8);
-    const int heavy_div = env_heavy_div > 0 ? env_heavy_div : 32;
-    const int units_per_item = env_units > 0 ? ((env_units + 63) / 64) * 64 : 256;
-    const int maxhp = glass_possible(s, grid) ? 16 : 1;  // Hitpoints per sample: a mirror chain ends in one, a glass tree of depth 5 in <= 16
-    const size_t tile_vals = (size_t)grid->spp * 64 * (size_t)maxhp * 3 * sizeof(double), tile_cnt = (size_t)grid->spp * 64;
-    const size_t tile_pconst = 7 * 64 * sizeof(double);
+    const bool reorder = L.form == EyeForm::Sched;
     // primary-ray mesh hits of the heavy tiles' units (cgrt_primwalk.hpp): a double and an int per unit
-    static const bool env_no_primwalk = [] { const char *e = std::getenv("CGRT_NO_PRIMWALK"); return e && *e && *e != '0'; }();
-    const bool use_prim = s->dev.prim_obj >= 0 && !env_no_primwalk && !(grid->flags & CGRT_GRID_STATS);
-    const size_t tile_prim = use_prim ? (size_t)grid->spp * 64 * (sizeof(double) + sizeof(int32_t)) : 0;
+    const bool use_prim = s->dev.prim_obj >= 0 && !kn.no_primwalk && !(grid->flags & CGRT_GRID_STATS);
+    const DeferLayout defer(grid->spp, g.maxhp, use_prim);
     size_t kmax = 0;
     const size_t sched_pad = 8;
     size_t sched_bytes = 0, defer_bytes = 0;
     if (reorder) {
+        // deferred Hitpoint values: up to 12 GiB, at most an eighth of THIS scene's device (MI355X: 288 GB; read at commit -- a
+        // process may drive devices of different sizes); allocated once per scene handle, as large as the biggest launch needed it
+        const size_t defer_budget = kn.defer_bytes > 0 ? (size_t)kn.defer_bytes : std::min((size_t)12 << 30, s->mem_total / 8);
         sched_bytes = (4 * (n_wt + sched_pad) + 64) * sizeof(uint32_t) + ((n_wt + 255) & ~(size_t)255);  // cost, order, hidx, border, plan, light
         sched_bytes = (sched_bytes + 255) & ~(size_t)255;
-        kmax = defer_budget / (tile_vals + ((tile_cnt + 7) & ~(size_t)7) + tile_pconst + tile_prim);
-        if (kmax > n_wt) kmax = n_wt;
-        defer_bytes = kmax * (tile_vals + ((tile_cnt + 7) & ~(size_t)7) + tile_pconst + tile_prim) + 256;
+        kmax = std::min(defer_budget / defer.per_tile(), n_wt);
+        defer_bytes = kmax * defer.per_tile() + 256;
     }
     size_t chunk_bytes = 0;
     if (g.chunks > 1) chunk_bytes = (size_t)g.chunks * npx_all * (3 * sizeof(double) + sizeof(uint32_t));
     const size_t chunk_bytes_al = (chunk_bytes + 255) & ~(size_t)255;
-    const size_t per_tile = tile_vals + ((tile_cnt + 7) & ~(size_t)7) + tile_pconst + tile_prim;
     size_t scratch_need = chunk_bytes_al + sched_bytes + defer_bytes;
-    // A size this device has refused before is not asked for again (every attempt is a synchronous hipFree plus failing
-    // hipMallocs): the deferred buffer shrinks -- fewer heavy tiles, same image -- until the need lies below it.
-    while (s->scratch_refused && scratch_need >= s->scratch_refused && kmax > 0) {
+    const auto halve_defer = [&] {  // fewer heavy tiles, same image
         kmax /= 2;
-        defer_bytes = kmax ? kmax * per_tile + 256 : 0;
+        defer_bytes = kmax ? kmax * defer.per_tile() + 256 : 0;
         scratch_need = chunk_bytes_al + sched_bytes + defer_bytes;
-    }
+    };
+    // A size this device has refused before is not asked for again (every attempt is a synchronous hipFree plus failing
+    // hipMallocs): the deferred buffer shrinks until the need lies below it.
+    while (s->scratch_refused && scratch_need >= s->scratch_refused && kmax > 0) halve_defer();
     if (scratch_need > 0 && s->scratch_bytes < scratch_need) {
         if (s->scratch) (void)hipFree(s->scratch);
         s->scratch = nullptr;
@@ -922,9 +1093,7 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
             s->scratch = nullptr;
             if (!s->scratch_refused || scratch_need < s->scratch_refused) s->scratch_refused = scratch_need;
             if (kmax == 0) return fail(CGRT_ERR_DEVICE, "cannot allocate launch scratch (chunk sums / schedule / deferred Hitpoint values)");
-            kmax /= 2;
-            defer_bytes = kmax ? kmax * per_tile + 256 : 0;
-            scratch_need = chunk_bytes_al + sched_bytes + defer_bytes;
+            halve_defer();
         }
         s->scratch_bytes = scratch_need;
     }
@@ -932,105 +1101,6 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
         g.partial = reinterpret_cast<double *>(s->scratch);
         g.partial_nhit = nhit ? reinterpret_cast<uint32_t *>(g.partial + (size_t)g.chunks * npx_all * 3) : nullptr;
     }
-    g.light = nullptr;
-    g.light_mode = 0;
-    g.pad_light_ = 0;
-    g.order = nullptr;
-    g.border = nullptr;
-    g.cost = nullptr;
-    g.hidx = nullptr;
-    g.plan = nullptr;
-    g.dvals = nullptr;
-    g.dcnt = nullptr;
-    g.pconst = nullptr;
-    g.probe = 0;
-    g.heavy_blocks = 0;
-    g.items_per_tile = 1;
-    g.units_per_item = units_per_item;
-    g.maxhp = maxhp;
-    g.prim_len = nullptr;
-    g.prim_tri = nullptr;
-    g.prim_obj = -1;
-    g.prim_done = 0;
-    static const int env_pw_refill = [] { const char *e = std::getenv("CGRT_PW_REFILL"); return e ? std::atoi(e) : 0; }();
-    static const int env_pw_rounds = [] { const char *e = std::getenv("CGRT_PW_ROUNDS"); return e ? std::atoi(e) : 0; }();
-    g.pw_refill = env_pw_refill > 0 ? env_pw_refill : 16;
-    g.pw_rounds = env_pw_rounds > 0 ? env_pw_rounds : 8;
-    if (one_wave) lds += (glass ? TileGeom<64>::stack_bytes : 0) + sizeof(BezLds);
-    else lds += glass ? kStackBytes : 0;
-    if (trees && s->dev.cached_tree >= 0) lds += (size_t)s->dev.cached_nodes * sizeof(NodeRec);
-    if (trees && !glass && !bez && s->dev.has_wide) lds += (size_t)kThreads * kWideLdsDepth * sizeof(uint2);  // wide walk's stack
-    static const int env_lds_pad = [] { const char *e = std::getenv("CGRT_LDS_PAD"); return e ? std::atoi(e) : 0; }();
-    lds += (size_t)env_lds_pad;
-    auto launch_mode = [&](auto sched_tag, const GridParams &gp, dim3 gd, float *rgb_, uint32_t *nhit_, unsigned long long *cnt_) -> int {
-        constexpr bool SCHED = decltype(sched_tag)::value;
-#define LAUNCH(T, B, D, G, P, S)                                                                                              \
-    do {                                                                                                                      \
-        if (SCHED) { BIG_LDS((trace_grid_sched_kernel<T, B, D, G, P, S, 256>), lds, "eye pass"); hipLaunchKernelGGL((trace_grid_sched_kernel<T, B, D, G, P, S, 256>), gd, block, lds, st, s->dev, gp, rgb_, nhit_, cnt_); } \
-        else { BIG_LDS((trace_grid_kernel<T, B, D, G, P, S>), lds, "eye pass"); hipLaunchKernelGGL((trace_grid_kernel<T, B, D, G, P, S>), gd, block, lds, st, s->dev, gp, rgb_, nhit_, cnt_); }     \
-    } while (0)
-#define LAUNCH_DG(T, B, P, S)                                      \
-    do {                                                           \
-        if (dof) { if (glass) LAUNCH(T, B, true, true, P, S); else LAUNCH(T, B, true, false, P, S); }   \
-        else     { if (glass) LAUNCH(T, B, false, true, P, S); else LAUNCH(T, B, false, false, P, S); } \
-    } while (0)
-        if (bez) {  // Bezier scenes share the tree-capable variants (the tree code is skipped when there is no tree)
-#define LAUNCH1(D, G)                                                                                                          \
-    do {                                                                                                                       \
-        if (SCHED) { BIG_LDS((trace_grid_sched_kernel<true, true, D, G, false, false, 64>), lds, "eye pass (Bezier)"); hipLaunchKernelGGL((trace_grid_sched_kernel<true, true, D, G, false, false, 64>), gd, block, lds, st, s->dev, gp, rgb_, nhit_, cnt_); } \
-        else { BIG_LDS((trace_grid_kernel<true, true, D, G, false, false, false, 64>), lds, "eye pass (Bezier)"); hipLaunchKernelGGL((trace_grid_kernel<true, true, D, G, false, false, false, 64>), gd, block, lds, st, s->dev, gp, rgb_, nhit_, cnt_); }    \
-    } while (0)
-            if (dof) { if (glass) LAUNCH1(true, true); else LAUNCH1(true, false); }
-            else     { if (glass) LAUNCH1(false, true); else LAUNCH1(false, false); }
-#undef LAUNCH1
-        } else if (trees) {
-            if (stats) LAUNCH_DG(true, false, false, true); else LAUNCH_DG(true, false, false, false);
-        } else if (s->dev.all_spheres) {
-            LAUNCH_DG(false, false, true, false);
-        } else {
-            LAUNCH_DG(false, false, false, false);
-        }
-#undef LAUNCH_DG
-#undef LAUNCH
-        return CGRT_OK;
-    };
-    auto launch = [&](const GridParams &gp, dim3 gd, float *rgb_, uint32_t *nhit_, unsigned long long *cnt_) {
-        return launch_mode(std::false_type{}, gp, gd, rgb_, nhit_, cnt_);
-    };
-    if (spill) {
-        // More top-level objects than the LDS list holds (kLdsObjsMax): the SPILL variants, which read the others from the
-        // uploaded array, in image order -- the sphere loop for sphere-only scenes, else the most general body (trees, Bezier,
-        // pending rays), as the Hitpoint capture does.  Such scenes are bound by their object loop, not by tile imbalance.
-        const dim3 gd((unsigned)tile_grid_blocks(g.W, g.rows, false)), blk(kThreads);
-        GridParams gs = g;
-        gs.xcd_tiles = 0;
-        if (s->dev.all_spheres) {
-            const size_t l = obj_list_lds(s->dev, kThreads / 64) + (glass ? kStackBytes : 0);
-#define SPILL_SPH(D, G)                                                                                                       \
-    do {                                                                                                                      \
-        BIG_LDS((trace_grid_kernel<false, false, D, G, true, false, false, 256, true>), l, "eye pass, SPILL (spheres)");       \
-        hipLaunchKernelGGL((trace_grid_kernel<false, false, D, G, true, false, false, 256, true>), gd, blk, l, st, s->dev, gs, rgb, nhit, cnt); \
-    } while (0)
-            if (dof) { if (glass) SPILL_SPH(true, true); else SPILL_SPH(true, false); }
-            else     { if (glass) SPILL_SPH(false, true); else SPILL_SPH(false, false); }
-#undef SPILL_SPH
-        } else {
-            // the general variant keeps as many objects resident as fit beside its other LDS (general_resident)
-            const DeviceScene dl = with_resident(s->dev, general_resident(s, dof, false));
-            const size_t l = obj_list_lds(dl, kThreads / 64) + general_other_lds(dl);
-#define SPILL_GEN(D)                                                                                                          \
-    do {                                                                                                                      \
-        BIG_LDS((trace_grid_kernel<true, true, D, true, false, false, false, 256, true>), l, "eye pass, SPILL (general)");     \
-        hipLaunchKernelGGL((trace_grid_kernel<true, true, D, true, false, false, false, 256, true>), gd, blk, l, st, dl, gs, rgb, nhit, cnt); \
-    } while (0)
-            if (dof) SPILL_GEN(true); else SPILL_GEN(false);
-#undef SPILL_GEN
-        }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(CGRT_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-        return CGRT_OK;
-    }
-    dim3 grid_dim = natural_dim;
     if (reorder && kmax > 0) {
         unsigned char *base = reinterpret_cast<unsigned char *>(s->scratch) + chunk_bytes_al;
         uint32_t *sb = reinterpret_cast<uint32_t *>(base);
@@ -1040,8 +1110,7 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
         uint32_t *border = sb + 3 * np;
         uint32_t *plan = sb + 4 * np;
         unsigned char *light = reinterpret_cast<unsigned char *>(sb + 4 * np + 64);
-        unsigned char *dbase = base + sched_bytes;
-        const bool split_light = s->dev.light_ok != 0 && g.chunks == 1 && !stats;
+        const bool split_light = s->dev.light_ok != 0 && g.chunks == 1 && !L.k.stats;
         if (split_light)
             hipLaunchKernelGGL(classify_kernel, dim3((unsigned)((n_wt + 255) / 256)), dim3(256), 0, st, s->dev, g, light, (int)n_wt);
         GridParams gp = g;  // the probe: this launch's first sample, natural order, one workgroup per tile, nothing stored
@@ -1057,7 +1126,7 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
             gp.light = light;
             gp.light_mode = 0;
         }
-        if ((rc = launch(gp, dim3((unsigned)tile_blocks), nullptr, nullptr, nullptr))) return rc;
+        if ((rc = launch_eye(L, false, s->device, gp, dim3((unsigned)tile_blocks), st, nullptr, nullptr, nullptr))) return rc;
         if (split_light) {
             // The light tiles: the variant without tree / Bezier / pending-ray code on the second stream, beside everything that
             // follows here.  It needs nothing but the classification and starts as soon as the probe is through, beside the
@@ -1067,63 +1136,35 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
             gl.light = light;
             gl.light_mode = 1;
             gl.timeline = nullptr;
+            gl.xcd_tiles = 0;
             HIP_TRY(hipEventRecord(s->ev_fork, st));
             HIP_TRY(hipStreamWaitEvent(s->aux_stream, s->ev_fork, 0));
-            size_t lds_light = obj_list_lds(s->dev, kThreads / 64);
-            const bool ltrees = s->dev.light_trees != 0;  // bump-mapped planes: the tree-capable variant (same LDS carve-up as the main launch's)
-            if (ltrees && s->dev.cached_tree >= 0) lds_light += (size_t)s->dev.cached_nodes * sizeof(NodeRec);
-            if (ltrees && s->dev.has_wide) lds_light += (size_t)kThreads * kWideLdsDepth * sizeof(uint2);
-            const dim3 gd_light((unsigned)tile_grid_blocks(g.W, g.rows, false));
-            gl.xcd_tiles = 0;
-#define LIGHT(T, D)                                                                                                           \
-    do {                                                                                                                      \
-        BIG_LDS((trace_grid_kernel<T, false, D, false, false, false>), lds_light, "eye pass, light tiles");                                             \
-        hipLaunchKernelGGL((trace_grid_kernel<T, false, D, false, false, false>), gd_light, dim3(kThreads), lds_light, s->aux_stream, \
-                           s->dev, gl, rgb, nhit, cnt);                                                                       \
-    } while (0)
-#define LIGHT_HF(D)                                                                                                           \
-    do {                                                                                                                      \
-        BIG_LDS((trace_grid_kernel<true, false, D, false, false, false, false, 256, false, true>), lds_hf, "eye pass, light tiles (HFONLY)");                    \
-        hipLaunchKernelGGL((trace_grid_kernel<true, false, D, false, false, false, false, 256, false, true>), gd_light, dim3(kThreads), lds_hf, \
-                           s->aux_stream, s->dev, gl, rgb, nhit, cnt);                                                         \
-    } while (0)
-            const size_t lds_hf = obj_list_lds(s->dev, kThreads / 64);  // no node cache, no walk stack
-            static const bool env_no_hfonly = [] { const char *e = std::getenv("CGRT_NO_HFONLY"); return e && *e && *e != '0'; }();
-            if (ltrees && s->dev.light_hf_only && !env_no_hfonly) { if (dof) LIGHT_HF(true); else LIGHT_HF(false); }
-            else if (ltrees) { if (dof) LIGHT(true, true); else LIGHT(true, false); }
-            else        { if (dof) LIGHT(false, true); else LIGHT(false, false); }
-#undef LIGHT_HF
-#undef LIGHT
+            if ((rc = launch_eye(light_launch(s->dev, L.k.dof, kn), false, s->device, gl,
+                                 dim3((unsigned)tile_grid_blocks(g.W, g.rows, false)), s->aux_stream, rgb, nhit, cnt)))
+                return rc;
             HIP_TRY(hipEventRecord(s->ev_join, s->aux_stream));
         }
         // heavy: cost x spp > (total cost x spp / wave slots) / heavy_div
         int n_cu = 256;
         (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, s->device);
-        const int wave_slots = n_cu * 4 * (one_wave ? kBezWaves : (trees ? kSchedTreeWaves : 4));
+        const int wave_slots = n_cu * 4 * (one_wave ? kBezWaves : (L.k.trees ? kSchedTreeWaves : 4));
         // tiles through a queue too (GridParams::border) unless their samples are split over workgroups or the workgroups are
         // single waves (trace_grid_sched_kernel)
-        static const bool env_no_tile_queue = [] { const char *e = std::getenv("CGRT_NO_TILE_QUEUE"); return e && *e && *e != '0'; }();
-        const bool tile_queue = g.chunks == 1 && !one_wave && !env_no_tile_queue;
+        const bool tile_queue = g.chunks == 1 && !one_wave && !kn.no_tile_queue;
         hipLaunchKernelGGL(plan_kernel, dim3(1), dim3(1024), 0, st, cost, split_light ? light : nullptr, (int)n_wt, (unsigned)kmax,
-                           (unsigned long long)wave_slots * (unsigned long long)heavy_div, plan, order, hidx,
+                           (unsigned long long)wave_slots * (unsigned long long)kn.heavy_div, plan, order, hidx,
                            tile_queue ? border : nullptr, wtiles_x, wtiles_y, one_wave ? 1 : kTileW / kWaveTileW,
                            one_wave ? 1 : kTileH / kWaveTileH);
         if (split_light) g.light = light;
         g.order = order;
         g.hidx = hidx;
         g.plan = plan;
-        g.dvals = reinterpret_cast<double *>(dbase);
-        g.dcnt = dbase + kmax * tile_vals;
-        g.pconst = reinterpret_cast<double *>(dbase + kmax * (tile_vals + ((tile_cnt + 7) & ~(size_t)7)));
+        defer.place(g, base + sched_bytes, kmax);
         if (use_prim) {
-            unsigned char *pb = dbase + kmax * (tile_vals + ((tile_cnt + 7) & ~(size_t)7) + tile_pconst);
-            g.prim_len = reinterpret_cast<const double *>(pb);
-            g.prim_tri = reinterpret_cast<const int32_t *>(pb + kmax * (size_t)grid->spp * 64 * sizeof(double));
             g.prim_obj = s->dev.prim_obj;
-            static const bool env_no_finish = [] { const char *e = std::getenv("CGRT_PW_NO_FINISH"); return e && *e && *e != '0'; }();
-            g.prim_done = (s->dev.prim_finish && !env_no_finish) ? 1 : 0;
+            g.prim_done = (s->dev.prim_finish && !kn.pw_no_finish) ? 1 : 0;
         }
-        g.items_per_tile = (int)(((size_t)grid->spp * 64 + units_per_item - 1) / units_per_item);
+        g.items_per_tile = (int)(((size_t)grid->spp * 64 + g.units_per_item - 1) / g.units_per_item);
         // enough heavy workgroups to fill the chip once: they loop over the item queue until it is empty
         size_t hb = (kmax * (size_t)g.items_per_tile + waves_per_block - 1) / waves_per_block;
         const size_t fill = (size_t)wave_slots / waves_per_block;
@@ -1136,8 +1177,7 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     }
     // development aid: CGRT_TIMELINE_FILE=path makes this launch synchronous and dumps, per workgroup, when and where it ran
     DevBuf timeline;
-    const char *timeline_file = std::getenv("CGRT_TIMELINE_FILE");
-    if (timeline_file && *timeline_file) {
+    if (kn.timeline_file) {
         HIP_TRY(timeline.alloc(((size_t)grid_dim.x + g.heavy_blocks) * 32));
         HIP_TRY(hipMemsetAsync(timeline.p, 0, ((size_t)grid_dim.x + g.heavy_blocks) * 32, st));
         g.timeline = timeline.as<unsigned long long>();
@@ -1157,18 +1197,14 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
             pw.finish = g.prim_done;
             pw.pad_ = 0;
             pw.counters = cnt;
-            const size_t lds_pw = (size_t)(pw.finish ? s->dev.n_objs : pw.obj + 1) * sizeof(ObjRec) + (size_t)kThreads * kWideLdsDepth * sizeof(uint2);
-            if (dof) {
-                BIG_LDS(primary_walk_kernel<true>, lds_pw, "primary_walk_kernel");
-                hipLaunchKernelGGL(primary_walk_kernel<true>, dim3((unsigned)n_cu2 * 4), dim3(kThreads), lds_pw, st, s->dev, g, pw);
-            } else {
-                BIG_LDS(primary_walk_kernel<false>, lds_pw, "primary_walk_kernel");
-                hipLaunchKernelGGL(primary_walk_kernel<false>, dim3((unsigned)n_cu2 * 4), dim3(kThreads), lds_pw, st, s->dev, g, pw);
-            }
+            const size_t staged = (size_t)(pw.finish ? s->dev.n_objs : pw.obj + 1);  // all objects when it finishes units
+            if ((rc = launch_checked(L.k.dof ? &primary_walk_kernel<true> : &primary_walk_kernel<false>, "primary_walk_kernel",
+                                     s->device, dim3((unsigned)n_cu2 * 4), dim3(kThreads), primary_walk_lds(staged), st, s->dev, g, pw)))
+                return rc;
         }
-        if ((rc = launch_mode(std::true_type{}, g, dim3((unsigned)g.heavy_blocks + grid_dim.x), rgb, nhit, cnt))) return rc;
+        if ((rc = launch_eye(L, true, s->device, g, dim3((unsigned)g.heavy_blocks + grid_dim.x), st, rgb, nhit, cnt))) return rc;
     } else {
-        if ((rc = launch(g, grid_dim, rgb, nhit, cnt))) return rc;
+        if ((rc = launch_eye(L, false, s->device, g, grid_dim, st, rgb, nhit, cnt))) return rc;
     }
     if (g.chunks > 1)
         hipLaunchKernelGGL(finalize_chunks_kernel, dim3((unsigned)((npx_all + 255) / 256)), dim3(256), 0, st, g, rgb, nhit);
@@ -1179,8 +1215,8 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
         std::vector<unsigned long long> tl(((size_t)grid_dim.x + g.heavy_blocks) * 4);
         HIP_TRY(hipStreamSynchronize(st));
         HIP_TRY(hipMemcpy(tl.data(), timeline.p, tl.size() * 8, hipMemcpyDeviceToHost));
-        if (FILE *f = std::fopen(timeline_file, "wb")) {
-            const unsigned long long head[4] = {(unsigned long long)grid_dim.x + g.heavy_blocks, block.x, (unsigned long long)g.chunks, (unsigned long long)g.xcd_tiles};
+        if (FILE *f = std::fopen(kn.timeline_file, "wb")) {
+            const unsigned long long head[4] = {(unsigned long long)grid_dim.x + g.heavy_blocks, (unsigned long long)L.k.nt, (unsigned long long)g.chunks, (unsigned long long)g.xcd_tiles};
             std::fwrite(head, 8, 4, f);
             std::fwrite(tl.data(), 8, tl.size(), f);
             std::fclose(f);
@@ -1188,8 +1224,7 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     }
     if (launch_err != hipSuccess) return fail(CGRT_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(launch_err));
     // development aid: CGRT_PLAN_DUMP=1 makes the launch synchronous and prints what the planner decided
-    static const bool env_plan_dump = [] { const char *e = std::getenv("CGRT_PLAN_DUMP"); return e && *e && *e != '0'; }();
-    if (env_plan_dump && g.plan) {
+    if (kn.plan_dump && g.plan) {
         uint32_t pl[8] = {0};
         HIP_TRY(hipStreamSynchronize(st));
         HIP_TRY(hipMemcpy(pl, g.plan, sizeof(pl), hipMemcpyDeviceToHost));
@@ -1218,20 +1253,9 @@ __global__ void unpermute_stripes_kernel(const float *__restrict__ shares, int n
 // *d_rec_out is hipMalloc'ed here (caller frees) unless cap == 0.
 static int hitpoints_device(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, uint64_t cap,
                             double **d_rec_out, uint64_t *count) {
-    GridParams g;
-    g.W = grid->width; g.H = grid->height; g.rows = grid->rows; g.row_offset = grid->row_offset;
-    g.stripe_rows = grid->stripe_rows; g.stripe_rank = grid->stripe_rank; g.stripe_nranks = grid->stripe_nranks;
-    g.spp = grid->spp; g.sample_offset = grid->sample_offset; g.max_depth = grid->max_depth;
+    GridParams g = grid_params(cam, grid);  // capture keeps one workgroup per tile
     g.accumulate = 0;
-    g.inv_spp_total = 1.0 / (double)grid->spp_total;
-    g.seed = grid->seed;
-    for (int k = 0; k < 3; k++) g.cam[k] = cam->cam[k];
-    g.half_width = cam->half_width; g.focus_plane = cam->focus_plane; g.lens_radius = cam->lens_radius;
-    g.chunks = 1; g.chunk_spp = grid->spp; g.partial = nullptr; g.partial_nhit = nullptr;  // capture keeps one workgroup per tile
-    g.timeline = nullptr;
-    g.light = nullptr; g.light_mode = 0; g.pad_light_ = 0; g.order = nullptr; g.border = nullptr; g.cost = nullptr; g.hidx = nullptr; g.plan = nullptr; g.dvals = nullptr; g.dcnt = nullptr; g.pconst = nullptr;
-    g.probe = 0; g.heavy_blocks = 0; g.items_per_tile = 1; g.units_per_item = 256; g.maxhp = 16;
-    g.prim_len = nullptr; g.prim_tri = nullptr; g.prim_obj = -1; g.prim_done = 0; g.pw_refill = 16; g.pw_rounds = 8;
+    g.xcd_tiles = (s->dev.has_mesh && !s->dev.has_bezier) ? 1 : 0;
     const size_t npx = (size_t)grid->rows * grid->width;
     DevBuf b_rgb, b_rec, b_cnt;
     HIP_TRY(b_rgb.alloc(npx * 3 * sizeof(float)));
@@ -1241,24 +1265,10 @@ static int hitpoints_device(const cgrt_scene *s, const cgrt_camera *cam, const c
     double *d_rec = b_rec.as<double>();
     unsigned long long *d_cnt = b_cnt.as<unsigned long long>();
     HIP_TRY(hipMemset(d_cnt, 0, sizeof(unsigned long long)));
-    g.xcd_tiles = (s->dev.has_mesh && !s->dev.has_bezier) ? 1 : 0;
-    const dim3 grid_dim((unsigned)tile_grid_blocks(g.W, g.rows, g.xcd_tiles != 0)), block(kThreads);
-    // the general variant, with as many objects resident as fit beside its other LDS (general_resident)
-    const DeviceScene dl = with_resident(s->dev, general_resident(s, cam->lens_radius > 0, true));
-    const size_t lds = obj_list_lds(dl, kThreads / 64) + general_other_lds(dl);
-    HitpointSink sink{d_rec, d_cnt, (unsigned long long)cap};
-    // the most general variant serves every scene; capture is a verification / hand-off path, not the hot path
-#define CAPTURE(D, SP)                                                                                                         \
-    do {                                                                                                                      \
-        BIG_LDS((trace_grid_kernel<true, true, D, true, false, false, true, 256, SP>), lds, "Hitpoint capture");               \
-        hipLaunchKernelGGL((trace_grid_kernel<true, true, D, true, false, false, true, 256, SP>), grid_dim, block, lds, 0, dl, g, d_rgb, \
-                           (uint32_t *)nullptr, (unsigned long long *)nullptr, sink);                                          \
-    } while (0)
-    const bool spill = dl.n_objs > dl.n_lds;
-    if (cam->lens_radius > 0) { if (spill) CAPTURE(true, true); else CAPTURE(true, false); }
-    else                      { if (spill) CAPTURE(false, true); else CAPTURE(false, false); }
-#undef CAPTURE
-    int rc = CGRT_OK;
+    const EyeLaunch L = eye_launch(s, cam, grid, eye_knobs(), true);
+    int rc = launch_eye(L, false, s->device, g, dim3((unsigned)tile_grid_blocks(g.W, g.rows, g.xcd_tiles != 0)), 0, d_rgb, nullptr,
+                        nullptr, HitpointSink{d_rec, d_cnt, (unsigned long long)cap});
+    if (rc) return rc;
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) rc = fail(CGRT_ERR_DEVICE, std::string("hitpoint kernel: ") + hipGetErrorString(e));

@@ -523,29 +523,14 @@ int sort_pairs(SortTemp &tmp, unsigned long long *kin, unsigned long long *kout,
 }
 
 int launch_photon_trace(const cgrt_scene *s, const PhotonArgs &pa, double *events, unsigned char *valid, hipStream_t st = 0) {
-    const dim3 grid((pa.count + kThreads - 1) / kThreads), block(kThreads);
-    const size_t lds = obj_list_lds(s->dev, kThreads / 64);
-    if (s->dev.n_objs > s->dev.n_lds) {  // more objects than the LDS list holds: the variants that read the rest from the uploaded array
-        const size_t l2 = lds + (s->dev.has_bezier ? (kThreads / 64) * sizeof(BezLds) : 0);
-        if (s->dev.has_bezier) {
-            BIG_LDS((photon_trace_kernel<true, true>), l2, "photon_trace_kernel, SPILL");
-            hipLaunchKernelGGL((photon_trace_kernel<true, true>), grid, block, l2, st, s->dev, pa, events, valid);
-        } else {
-            BIG_LDS((photon_trace_kernel<false, true>), l2, "photon_trace_kernel, SPILL");
-            hipLaunchKernelGGL((photon_trace_kernel<false, true>), grid, block, l2, st, s->dev, pa, events, valid);
-        }
-        return CGRT_OK;
-    }
-    if (s->dev.has_bezier) {
-        const size_t l = lds + (kThreads / 64) * sizeof(BezLds);
-        BIG_LDS(photon_trace_kernel<true>, l, "photon_trace_kernel");
-        hipLaunchKernelGGL(photon_trace_kernel<true>, grid, block, l, st, s->dev, pa, events, valid);
-    } else {
-        const size_t l = lds + (photon_lds_stack(s->dev) ? (size_t)kThreads * kWideLdsDepth * sizeof(uint2) : 0);
-        BIG_LDS(photon_trace_kernel<false>, l, "photon_trace_kernel");
-        hipLaunchKernelGGL(photon_trace_kernel<false>, grid, block, l, st, s->dev, pa, events, valid);
-    }
-    return CGRT_OK;
+    const DeviceScene &d = s->dev;
+    // more objects than the LDS list holds: the variants that read the rest from the uploaded array
+    const bool spill = d.n_objs > d.n_lds, bez = d.has_bezier != 0;
+    const auto fn = spill ? (bez ? &photon_trace_kernel<true, true> : &photon_trace_kernel<false, true>)
+                          : (bez ? &photon_trace_kernel<true> : &photon_trace_kernel<false>);
+    return launch_checked(fn, spill ? "photon_trace_kernel, SPILL" : "photon_trace_kernel", s->device,
+                          dim3((pa.count + kThreads - 1) / kThreads), dim3(kThreads),
+                          photon_lds((size_t)d.n_lds, spill, bez, photon_lds_stack(d)), st, d, pa, events, valid);
 }
 
 int sort_pairs32(SortTemp &tmp, unsigned int *kin, unsigned int *kout, unsigned int *vin, unsigned int *vout, size_t n,
