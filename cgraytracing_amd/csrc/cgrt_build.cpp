@@ -905,4 +905,188 @@ int HostScene::add_bezier(const double *cp3, int ncp, const double pos[3], const
     return (int)objs.size() - 1;
 }
 
+// ---- commit: layout and traits ----------------------------------------------------------------------------------------
+
+CommitKnobs commit_knobs() {
+    auto flag = [](const char *name) { const char *e = std::getenv(name); return e && *e && *e != '0'; };
+    CommitKnobs k;
+    const char *tree = std::getenv("CGRT_TREE");
+    k.ref_tree = tree && std::strcmp(tree, "ref") == 0;
+    if (const char *e = std::getenv("CGRT_LDS_OBJS")) k.lds_objs = std::atoi(e);
+    k.no_plane_run = flag("CGRT_NO_PLANE_RUN");
+    k.no_bezier_cull = flag("CGRT_NO_BEZIER_CULL");
+    const char *prio = std::getenv("CGRT_AUX_PRIORITY");
+    if (prio && std::strcmp(prio, "same") == 0) k.aux_priority = AUX_SAME;
+    if (prio && std::strcmp(prio, "high") == 0) k.aux_priority = AUX_HIGH;
+    return k;
+}
+
+// bound on |coordinate| of every box face (the fp32 box test's error term, cgrt_traverse.hpp Ray32): the vertices' largest
+// magnitude, the growth of the boxes and a little more
+float tree_bmax(double max_abs) { return (float)((max_abs + 2 * kBoxPad) * (1 + 1e-6)) * (1.f + 1e-6f); }
+
+namespace {
+
+// a host-built tree: its records are appended to the layout's arrays
+TreeRec place_host_tree(const HostTree &t, bool ref_tree, SceneLayout &L) {
+    TreeRec tr{};
+    tr.node_begin = (int64_t)L.nodes.size();
+    tr.tri_begin = (int64_t)L.tris.size();
+    tr.otri_begin = (int64_t)L.otris.size();
+    tr.tbox_begin = (int64_t)L.tboxes.size();
+    tr.wnode_begin = (int64_t)L.wnodes.size();
+    tr.ntris = (int32_t)t.tris.size();
+    tr.tri_level = (!ref_tree && t.tri_level) ? 1 : 0;
+    tr.nwide = tr.tri_level ? (int32_t)t.wide.size() : 0;
+    double m = 0;
+    for (double v : t.tri9) m = std::max(m, std::fabs(v));
+    tr.bmax = tree_bmax(m);
+    tr.hfield = -1;
+    if (t.is_hfield) {
+        HFieldRec hf = t.hfield;
+        hf.cell_begin = (int64_t)L.hcells.size();
+        tr.hfield = (int32_t)L.hfields.size();
+        L.hfields.push_back(hf);
+        L.hcells.insert(L.hcells.end(), t.hcells.begin(), t.hcells.end());
+        L.hcell_y.insert(L.hcell_y.end(), t.hcell_y.begin(), t.hcell_y.end());
+    }
+    if (tr.tri_level) L.otris.insert(L.otris.end(), t.otris.begin(), t.otris.end());
+    if (tr.nwide > 0) {  // the device walks the wide form: the one-box-per-node copies stay on the host (cgrt_scene_bvh_dump)
+        tr.noct = 1;
+        L.wnodes.insert(L.wnodes.end(), t.wide.begin(), t.wide.end());
+    } else {  // CGRT_TREE=ref: the reference's own inner nodes instead of the SAH hierarchy's eight octant copies
+        const std::vector<NodeRec> &nodes = ref_tree ? t.nodes : t.bvh;
+        tr.nnodes = ref_tree ? (int32_t)t.nodes.size() : t.bvh_nodes;
+        tr.noct = ref_tree ? 1 : 8;
+        L.nodes.insert(L.nodes.end(), nodes.begin(), nodes.end());
+    }
+    L.tboxes.insert(L.tboxes.end(), t.tboxes.begin(), t.tboxes.end());
+    L.tris.insert(L.tris.end(), t.tris.begin(), t.tris.end());
+    return tr;
+}
+
+// a device-built tree: room behind the host-built records (nwide, bmax and the floor's height range come from the build)
+TreeRec place_device_tree(const HostTree &t, SceneLayout &L) {
+    TreeRec tr{};
+    tr.node_begin = (int64_t)L.nodes.size();
+    tr.tbox_begin = (int64_t)L.tboxes.size();
+    tr.tri_begin = (int64_t)(L.tris.size() + L.room_tris);
+    tr.otri_begin = (int64_t)(L.otris.size() + L.room_otris);
+    tr.wnode_begin = (int64_t)(L.wnodes.size() + L.room_wnodes);
+    tr.ntris = (int32_t)t.dev_ntri;
+    tr.noct = 1;
+    tr.hfield = -1;
+    L.room_tris += (size_t)t.dev_ntri;
+    if (t.dev_kind == 1) {  // opaque mesh: triangle-level hierarchy, 4-wide
+        tr.tri_level = 1;
+        L.room_otris += (size_t)t.dev_ntri;
+        L.room_wnodes += (size_t)t.dev_ntri;
+    } else {  // bump floor: grid cells
+        HFieldRec hf = t.hfield;
+        hf.cell_begin = (int64_t)(L.hcells.size() + L.room_hcells);
+        L.room_hcells += (size_t)hf.nx * (size_t)hf.nz;
+        tr.hfield = (int32_t)L.hfields.size();
+        L.hfields.push_back(hf);
+    }
+    return tr;
+}
+
+}  // namespace
+
+SceneLayout scene_layout(const HostScene &H, const CommitKnobs &k) {
+    SceneLayout L;
+    L.trees.resize(H.trees.size());
+    for (size_t i = 0; i < H.trees.size(); i++)
+        if (!H.trees[i].dev_kind) L.trees[i] = place_host_tree(H.trees[i], k.ref_tree, L);
+    for (size_t i = 0; i < H.trees.size(); i++)  // behind every host-built record, so after all of them
+        if (H.trees[i].dev_kind) {
+            L.trees[i] = place_device_tree(H.trees[i], L);
+            L.n_dev_trees++;
+        }
+    for (const HostTexture &t : H.textures) {
+        TexRec tr{};
+        tr.texel_begin = (int64_t)L.texels.size();
+        tr.rows = t.rows;
+        tr.cols = t.cols;
+        for (int c = 0; c < 3; c++) {
+            tr.n[c] = t.n[c];
+            tr.p[c] = t.p[c];
+        }
+        tr.lenx = t.lenx;
+        tr.leny = t.leny;
+        tr.isbump = t.isbump ? 1 : 0;
+        L.texels.insert(L.texels.end(), t.rgb.begin(), t.rgb.end());
+        L.texs.push_back(tr);
+    }
+    return L;
+}
+
+void scene_traits(const HostScene &H, const std::vector<TreeRec> &trees, const CommitKnobs &k, DeviceScene &d) {
+    const std::vector<ObjRec> &objs = H.objs;
+    d.n_objs = (int32_t)objs.size();
+    d.n_lds = std::max(0, std::min({d.n_objs, kLdsObjsMax, k.lds_objs}));  // objects resident in LDS
+    d.n_trees = (int32_t)trees.size();
+    d.n_texs = (int32_t)H.textures.size();
+    d.n_beziers = (int32_t)H.beziers.size();
+    d.n_cover = (int32_t)(H.cover.size() / 4);
+    d.has_wide = 0;
+    for (const TreeRec &tr : trees)
+        if (tr.nwide > 0) d.has_wide = 1;
+    d.has_mesh = trees.empty() ? 0 : 1;
+    d.has_bezier = H.beziers.empty() ? 0 : 1;
+    d.cached_tree = -1;
+    d.cached_nodes = 0;
+    for (size_t t = 0; t < trees.size(); t++)
+        if (trees[t].nnodes > 0 && trees[t].nnodes <= kNodeCache) {  // first tree small enough to live in LDS
+            d.cached_tree = (int32_t)t;
+            d.cached_nodes = trees[t].nnodes;
+            break;
+        }
+    d.all_spheres = 1;
+    d.has_glass = 0;
+    for (const ObjRec &o : objs) {
+        if (o.kind != KIND_SPHERE) d.all_spheres = 0;
+        if (!(o.transp < kEps)) d.has_glass = 1;  // main.cpp:129: the glass branch is `!(transparency < eps)`
+    }
+    {   // the one opaque mesh whose primary-ray walks may run as their own kernel (cgrt_primwalk.hpp): no other mesh, no Bezier object
+        int n_mesh = 0, at = -1;
+        for (size_t i = 0; i < objs.size(); i++)
+            if (objs[i].kind == KIND_MESH) { n_mesh++; at = (int)i; }
+        d.prim_obj = -1;
+        if (n_mesh == 1 && H.beziers.empty() && objs[(size_t)at].transp < kEps && objs[(size_t)at].tree >= 0 &&
+            trees[(size_t)objs[(size_t)at].tree].nwide > 0 && at < d.n_lds)
+            d.prim_obj = at;
+        d.prim_finish = d.prim_obj >= 0 ? 1 : 0;
+        for (const ObjRec &o : objs)
+            if (o.kind == KIND_PLANE && o.tree >= 0) d.prim_finish = 0;
+    }
+    // light tiles (classify_kernel): possible when planes are plain diffuse surfaces and something else is not
+    bool planes_plain = true, special = false, plane_trees = false;
+    for (const ObjRec &o : objs) {
+        const bool diffuse = o.refl < kEps && o.transp < kEps;
+        if (o.kind == KIND_PLANE && !diffuse) planes_plain = false;  // a bump map is fine: a diffuse bumped floor still ends the path
+        if (o.kind == KIND_PLANE && o.tree >= 0) plane_trees = true;
+        if (o.kind == KIND_MESH || o.kind == KIND_BEZIER || (o.kind == KIND_SPHERE && !diffuse)) special = true;
+    }
+    d.light_ok = (planes_plain && special && !d.all_spheres) ? 1 : 0;
+    d.single_ray = (planes_plain && !special) ? 1 : 0;
+    d.light_trees = plane_trees ? 1 : 0;  // the light variant then needs the tree / height-field code (not Bezier, not glass)
+    d.light_hf_only = plane_trees ? 1 : 0;
+    for (const ObjRec &o : objs)
+        if (o.kind == KIND_PLANE && o.tree >= 0 && !(o.transp < kEps && trees[(size_t)o.tree].hfield >= 0)) d.light_hf_only = 0;
+    // the first run of >= 3 axis-aligned planes without a bump tree, with nothing but other planes in front of it, all in the LDS list
+    d.prun_begin = d.prun_end = 0;
+    if (!k.no_plane_run) {
+        auto eligible = [&](int j) { return objs[(size_t)j].kind == KIND_PLANE && objs[(size_t)j].axis >= 0 && objs[(size_t)j].tree < 0; };
+        int b = 0;  // planes of any sort may stand in front of the run (a bump floor), nothing else
+        while (b < d.n_lds && objs[(size_t)b].kind == KIND_PLANE && !eligible(b)) b++;
+        int j = b;
+        while (j < d.n_lds && eligible(j)) j++;
+        if (j - b >= 3) {
+            d.prun_begin = b;
+            d.prun_end = j;
+        }
+    }
+}
+
 }  // namespace cgrt

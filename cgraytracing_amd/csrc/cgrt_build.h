@@ -1,4 +1,4 @@
-// Host-side scene assembly: mesh loaders, bump-mesh construction, tree build, flattening.
+// Host-side scene assembly: mesh loaders, bump-mesh construction, tree build, flattening, scene traits.
 // These are the reference's pre-pass (objects.h:217-267,338-403,480-504; texture.h:19-38), run once per
 // scene on the CPU; the per-ray work is all in cgrt_hip.hip.
 #ifndef CGRT_BUILD_H
@@ -90,6 +90,46 @@ struct HostScene {
 // returns false and sets err on malformed input; a missing file gives an empty list and true
 bool load_mesh_file(const char *file, double a, const double b[3], int type, std::vector<double> &tri9,
                     std::string &err);
+
+// ---- the host side of cgrt_scene_commit: knobs -> layout -> (uploads, device builds) -> traits ----------------------------
+
+// The commit's switches (measurement and test aids), read from the environment once per commit.
+enum AuxPriority { AUX_LOWEST, AUX_SAME, AUX_HIGH };
+struct CommitKnobs {
+    bool ref_tree = false;        // CGRT_TREE=ref: the device walks the reference's own inner nodes instead of the SAH hierarchy
+    int lds_objs = kLdsObjsMax;   // CGRT_LDS_OBJS=n: at most n objects resident in LDS (drives the SPILL variants)
+    bool no_plane_run = false;    // CGRT_NO_PLANE_RUN=1: the leading planes are tested one by one
+    bool no_bezier_cull = false;  // CGRT_NO_BEZIER_CULL=1: every solve of every ray that enters a Bezier object's box is run
+    AuxPriority aux_priority = AUX_LOWEST;  // CGRT_AUX_PRIORITY=same|high: priority of the light launch's stream
+};
+CommitKnobs commit_knobs();
+
+// TreeRec::bmax from the largest |coordinate| of a tree's vertices: the growth of the boxes and a little more
+float tree_bmax(double max_abs);
+
+// Where every record of the device arrays goes.  Host-built records come first, in tree order.  Behind them each array keeps
+// room for what the device builds (HostTree::dev_kind) write at commit, again in tree order; that room has no host copy.
+struct SceneLayout {
+    std::vector<NodeRec> nodes;
+    std::vector<TriRec> tris;
+    std::vector<OTriRec> otris;
+    std::vector<NodeRec> tboxes;
+    std::vector<WideNodeRec> wnodes;
+    std::vector<HCellRec> hcells;
+    std::vector<HCellY> hcell_y;  // parallel to hcells
+    std::vector<uint8_t> texels;
+    std::vector<TexRec> texs;
+    std::vector<HFieldRec> hfields;
+    std::vector<TreeRec> trees;   // one per HostTree, device-built ones included (their nwide, a mesh's bmax and a floor's
+                                  // height range are filled by the build)
+    size_t room_tris = 0, room_otris = 0, room_wnodes = 0, room_hcells = 0;  // records behind the host-built ones (hcells: and hcell_y)
+    int n_dev_trees = 0;
+};
+SceneLayout scene_layout(const HostScene &H, const CommitKnobs &k);
+
+// Every scalar field of d -- the inputs of kernel-variant selection -- from the scene (objects, cover spheres), its final tree
+// records (after the device builds) and the knobs.  The pointers are left as they are.
+void scene_traits(const HostScene &H, const std::vector<TreeRec> &trees, const CommitKnobs &k, DeviceScene &d);
 
 }  // namespace cgrt
 #endif

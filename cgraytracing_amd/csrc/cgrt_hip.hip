@@ -52,7 +52,6 @@ struct cgrt_scene {
     DeviceScene dev{};
     std::vector<void *> allocs;
     int64_t device_bytes = 0;
-    std::vector<int> tree_of;  // flat tree list (object order)
     // CGRT_GRID_SPLIT_SAMPLES: chunk sums between the two kernels; grown on demand, reused by later launches on this handle
     // (launches on one handle are ordered by the caller: cgrt.h, "Threading")
     mutable void *scratch = nullptr;
@@ -231,6 +230,96 @@ int cgrt_scene_add_bezier(cgrt_scene *s, const double *cp3, int ncp, const doubl
     return added(s, s->host.add_bezier(cp3, ncp, pos, sc, refl, transp));
 }
 
+static double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// Row f3 (cgrt_devbuild.hpp): the device builds fill the room scene_layout() left behind the host-built records and finish what
+// only they know -- a floor's height range; a mesh's 4-wide node count, bmax, bounding sphere and cover spheres (appended to H.cover)
+static int device_builds(HostScene &H, SceneLayout &L, const DeviceScene &d) {
+    int rc = CGRT_OK;
+    for (size_t ti = 0; ti < H.trees.size(); ti++) {
+        HostTree &t = H.trees[ti];
+        TreeRec &tr = L.trees[ti];
+        if (t.dev_kind == 2) {
+            const HostTexture &tx = H.textures[(size_t)t.dev_tex];
+            HFieldRec &hf = L.hfields[(size_t)tr.hfield];
+            devbuild::BumpResult br;
+            if ((rc = devbuild::build_bump_floor(d.texels + L.texs[(size_t)t.dev_tex].texel_begin, tx.rows, tx.cols, tx.p, tx.lenx,
+                                                 tx.leny, t.dev_plane_y, const_cast<HCellRec *>(d.hcells) + hf.cell_begin,
+                                                 const_cast<HCellY *>(d.hcell_y) + hf.cell_begin,
+                                                 const_cast<TriRec *>(d.tris) + tr.tri_begin, br)))
+                return rc;
+            hf.ylo = br.ylo;
+            hf.yhi = br.yhi;
+            t.hfield.ylo = br.ylo;
+            t.hfield.yhi = br.yhi;
+        } else if (t.dev_kind == 1) {
+            devbuild::MeshResult mr;
+            if ((rc = devbuild::build_mesh_hierarchy(t.tri9.data(), (int)t.dev_ntri, const_cast<TriRec *>(d.tris) + tr.tri_begin,
+                                                     const_cast<OTriRec *>(d.otris) + tr.otri_begin,
+                                                     const_cast<WideNodeRec *>(d.wnodes) + tr.wnode_begin, mr)))
+                return rc;
+            tr.nwide = mr.nwide;
+            tr.bmax = tree_bmax(mr.bmax);
+            t.dev_nwide = mr.nwide;
+            t.wide_stack = mr.stack_need;
+            t.dev_balanced = mr.balanced;
+            ObjRec &ob = H.objs[(size_t)t.dev_obj];
+            for (int k = 0; k < 3; k++) ob.a[k] = mr.centre[k];
+            ob.s0 = mr.r2;
+            t.dev_cover_at = H.cover.size();
+            H.cover.insert(H.cover.end(), mr.cover.begin(), mr.cover.end());
+        }
+    }
+    return CGRT_OK;
+}
+
+// every array of the scene, device builds included; fills d's pointers
+static int upload_scene(cgrt_scene *s, SceneLayout &L, const CommitKnobs &k, DeviceScene &d, double &ms_device_build) {
+    HostScene &H = s->host;
+    int rc = CGRT_OK;
+    // the large arrays first: the device builds write into the room behind the host-built records
+    if ((rc = upload(s, L.nodes, &d.nodes))) return rc;
+    if ((rc = upload(s, L.tris, &d.tris, L.room_tris))) return rc;
+    if ((rc = upload(s, L.texels, &d.texels))) return rc;
+    if ((rc = upload(s, L.hcells, &d.hcells, L.room_hcells))) return rc;
+    if ((rc = upload(s, L.hcell_y, &d.hcell_y, L.room_hcells))) return rc;
+    if ((rc = upload(s, L.otris, &d.otris, L.room_otris))) return rc;
+    if ((rc = upload(s, L.tboxes, &d.tboxes))) return rc;
+    if ((rc = upload(s, L.wnodes, &d.wnodes, L.room_wnodes))) return rc;
+    if (L.n_dev_trees > 0) {
+        const auto t_build0 = std::chrono::steady_clock::now();
+        if ((rc = device_builds(H, L, d))) return rc;
+        ms_device_build = ms_since(t_build0);
+    }
+    // then the ones the builds finish
+    if ((rc = upload(s, H.objs, &d.objs))) return rc;
+    if ((rc = upload(s, L.trees, &d.trees))) return rc;
+    if ((rc = upload(s, L.texs, &d.texs))) return rc;
+    if ((rc = upload(s, H.beziers, &d.beziers))) return rc;
+    if ((rc = upload(s, H.bez_slabs, &d.bez_slabs))) return rc;
+    if (k.no_bezier_cull) d.bez_slabs = nullptr;
+    if ((rc = upload(s, L.hfields, &d.hfields))) return rc;
+    if ((rc = upload(s, H.cover, &d.cover))) return rc;
+    return CGRT_OK;
+}
+
+// the light-tile launch's stream and fork/join events; without them every tile is rendered by the full variant
+static void open_light_stream(cgrt_scene *s, AuxPriority priority, DeviceScene &d) {
+    if (!d.light_ok || s->aux_stream) return;
+    // the light launch yields to the scheduled one: lowest stream priority
+    int prio_least = 0, prio_greatest = 0;
+    (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
+    const int prio = priority == AUX_SAME ? 0 : priority == AUX_HIGH ? prio_greatest : prio_least;
+    if (hipStreamCreateWithPriority(&s->aux_stream, hipStreamNonBlocking, prio) != hipSuccess ||
+        hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming) != hipSuccess)
+        d.light_ok = 0;
+}
+
+// A commit that fails leaves the scene open, with no device memory and with H.cover as before (the device builds append to it):
+// a later commit starts from scratch.
 int cgrt_scene_commit(cgrt_scene *s, int device) {
     NEED_OPEN(s);
     int ndev = 0;
@@ -240,181 +329,12 @@ int cgrt_scene_commit(cgrt_scene *s, int device) {
     s->device = device;
     HostScene &H = s->host;
     const auto t_commit0 = std::chrono::steady_clock::now();
-    auto ms_since = [](std::chrono::steady_clock::time_point t0) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    };
-    // flatten trees
-    std::vector<NodeRec> nodes;
-    std::vector<TriRec> tris;
-    std::vector<TreeRec> trees;
-    std::vector<HFieldRec> hfields;
-    std::vector<HCellRec> hcells;
-    std::vector<HCellY> hcell_y;
-    std::vector<OTriRec> otris;
-    std::vector<NodeRec> tboxes;
-    std::vector<WideNodeRec> wnodes;
-    // row f3: records a device build will produce go BEHIND the host-built ones of the same array (room only, no host copy)
-    size_t dev_tris = 0, dev_otris = 0, dev_wnodes = 0, dev_hcells = 0;
-    for (auto &t : H.trees) {
-        TreeRec tr;
-        if (t.dev_kind) {  // offsets are assigned once the host parts' sizes are known (second loop below)
-            std::memset(&tr, 0, sizeof(tr));
-            trees.push_back(tr);
-            continue;
-        }
-        tr.node_begin = (int64_t)nodes.size();
-        tr.tri_begin = (int64_t)tris.size();
-        // CGRT_TREE=ref (measurement aid): traverse the reference's own inner nodes instead of the SAH hierarchy
-        const char *tree_env = std::getenv("CGRT_TREE");
-        const bool ref_order = tree_env && std::strcmp(tree_env, "ref") == 0;
-        const std::vector<NodeRec> &dev_nodes = ref_order ? t.nodes : t.bvh;
-        tr.nnodes = ref_order ? (int32_t)t.nodes.size() : t.bvh_nodes;
-        tr.noct = ref_order ? 1 : 8;
-        tr.tri_level = (!ref_order && t.tri_level) ? 1 : 0;
-        {   // bound on |coordinate| of every box face (the fp32 box test's error term, cgrt_traverse.hpp Ray32): the vertices'
-            // largest magnitude, the growth of the boxes and a little more
-            double m = 0;
-            for (double v : t.tri9) m = std::max(m, std::fabs(v));
-            tr.bmax = (float)((m + 2 * kBoxPad) * (1 + 1e-6)) * (1.f + 1e-6f);
-        }
-        tr.otri_begin = (int64_t)otris.size();
-        if (tr.tri_level) otris.insert(otris.end(), t.otris.begin(), t.otris.end());
-        tr.ntris = (int32_t)t.tris.size();
-        tr.hfield = -1;
-        if (t.is_hfield) {
-            HFieldRec hf = t.hfield;
-            hf.cell_begin = (int64_t)hcells.size();
-            tr.hfield = (int32_t)hfields.size();
-            hfields.push_back(hf);
-            hcells.insert(hcells.end(), t.hcells.begin(), t.hcells.end());
-            hcell_y.insert(hcell_y.end(), t.hcell_y.begin(), t.hcell_y.end());
-        }
-        tr.tbox_begin = (int64_t)tboxes.size();
-        tr.wnode_begin = (int64_t)wnodes.size();
-        tr.nwide = tr.tri_level ? (int32_t)t.wide.size() : 0;
-        tr.pad2 = 0;
-        if (tr.nwide > 0) wnodes.insert(wnodes.end(), t.wide.begin(), t.wide.end());
-        tboxes.insert(tboxes.end(), t.tboxes.begin(), t.tboxes.end());
-        if (tr.nwide > 0) {  // the device walks the wide form: the one-box-per-node copies stay on the host (cgrt_scene_bvh_dump)
-            tr.nnodes = 0;
-            tr.noct = 1;
-        } else {
-            nodes.insert(nodes.end(), dev_nodes.begin(), dev_nodes.end());
-        }
-        tris.insert(tris.end(), t.tris.begin(), t.tris.end());
-        trees.push_back(tr);
-    }
-    std::vector<TexRec> texs;
-    std::vector<uint8_t> texels;
-    for (auto &t : H.textures) {
-        TexRec tr;
-        std::memset(&tr, 0, sizeof(tr));
-        tr.texel_begin = (int64_t)texels.size();
-        tr.rows = t.rows;
-        tr.cols = t.cols;
-        for (int k = 0; k < 3; k++) {
-            tr.n[k] = t.n[k];
-            tr.p[k] = t.p[k];
-        }
-        tr.lenx = t.lenx;
-        tr.leny = t.leny;
-        tr.isbump = t.isbump ? 1 : 0;
-        texels.insert(texels.end(), t.rgb.begin(), t.rgb.end());
-        texs.push_back(tr);
-    }
-    // device-built trees: their place behind the host-built records
-    int n_dev_trees = 0;
-    for (size_t ti = 0; ti < H.trees.size(); ti++) {
-        const HostTree &t = H.trees[ti];
-        if (!t.dev_kind) continue;
-        n_dev_trees++;
-        TreeRec &tr = trees[ti];
-        tr.hfield = -1;
-        tr.noct = 1;
-        tr.ntris = (int32_t)t.dev_ntri;
-        tr.node_begin = (int64_t)nodes.size();
-        tr.tbox_begin = (int64_t)tboxes.size();
-        tr.tri_begin = (int64_t)(tris.size() + dev_tris);
-        tr.otri_begin = (int64_t)(otris.size() + dev_otris);
-        tr.wnode_begin = (int64_t)(wnodes.size() + dev_wnodes);
-        dev_tris += (size_t)t.dev_ntri;
-        if (t.dev_kind == 1) {  // opaque mesh: triangle-level hierarchy, 4-wide (nwide is known after the build)
-            tr.tri_level = 1;
-            dev_otris += (size_t)t.dev_ntri;
-            dev_wnodes += (size_t)t.dev_ntri;
-        } else {  // bump floor: grid cells
-            HFieldRec hf = t.hfield;
-            hf.cell_begin = (int64_t)(hcells.size() + dev_hcells);
-            dev_hcells += (size_t)hf.nx * (size_t)hf.nz;
-            tr.hfield = (int32_t)hfields.size();
-            hfields.push_back(hf);  // ylo / yhi come from the build
-        }
-    }
+    const CommitKnobs knobs = commit_knobs();
+    SceneLayout L = scene_layout(H, knobs);
     DeviceScene d{};
-    int rc = CGRT_OK;
     double ms_device_build = 0;
-    const size_t cover_host = H.cover.size();  // device builds append their cover spheres; a failed commit takes them back
-    // a commit that fails part-way leaves nothing behind: the scene stays open and a later commit starts from scratch
-    auto all_uploads = [&]() -> int {
-        // the large arrays first: the device builds write into the room behind the host-built records
-        if ((rc = upload(s, nodes, &d.nodes))) return rc;
-        if ((rc = upload(s, tris, &d.tris, dev_tris))) return rc;
-        if ((rc = upload(s, texels, &d.texels))) return rc;
-        if ((rc = upload(s, hcells, &d.hcells, dev_hcells))) return rc;
-        if ((rc = upload(s, hcell_y, &d.hcell_y, dev_hcells))) return rc;
-        if ((rc = upload(s, otris, &d.otris, dev_otris))) return rc;
-        if ((rc = upload(s, tboxes, &d.tboxes))) return rc;
-        if ((rc = upload(s, wnodes, &d.wnodes, dev_wnodes))) return rc;
-        if (n_dev_trees > 0) {
-            const auto t_build0 = std::chrono::steady_clock::now();
-            for (size_t ti = 0; ti < H.trees.size(); ti++) {
-                HostTree &t = H.trees[ti];
-                TreeRec &tr = trees[ti];
-                if (t.dev_kind == 2) {
-                    const HostTexture &tx = H.textures[(size_t)t.dev_tex];
-                    HFieldRec &hf = hfields[(size_t)tr.hfield];
-                    devbuild::BumpResult br;
-                    if ((rc = devbuild::build_bump_floor(d.texels + texs[(size_t)t.dev_tex].texel_begin, tx.rows, tx.cols, tx.p, tx.lenx,
-                                                         tx.leny, t.dev_plane_y, const_cast<HCellRec *>(d.hcells) + hf.cell_begin,
-                                                         const_cast<HCellY *>(d.hcell_y) + hf.cell_begin,
-                                                         const_cast<TriRec *>(d.tris) + tr.tri_begin, br)))
-                        return rc;
-                    hf.ylo = br.ylo;
-                    hf.yhi = br.yhi;
-                    t.hfield.ylo = br.ylo;
-                    t.hfield.yhi = br.yhi;
-                } else if (t.dev_kind == 1) {
-                    devbuild::MeshResult mr;
-                    if ((rc = devbuild::build_mesh_hierarchy(t.tri9.data(), (int)t.dev_ntri, const_cast<TriRec *>(d.tris) + tr.tri_begin,
-                                                             const_cast<OTriRec *>(d.otris) + tr.otri_begin,
-                                                             const_cast<WideNodeRec *>(d.wnodes) + tr.wnode_begin, mr)))
-                        return rc;
-                    tr.nwide = mr.nwide;
-                    tr.bmax = (float)((mr.bmax + 2 * kBoxPad) * (1 + 1e-6)) * (1.f + 1e-6f);
-                    t.dev_nwide = mr.nwide;
-                    t.wide_stack = mr.stack_need;
-                    t.dev_balanced = mr.balanced;
-                    ObjRec &ob = H.objs[(size_t)t.dev_obj];
-                    for (int k = 0; k < 3; k++) ob.a[k] = mr.centre[k];
-                    ob.s0 = mr.r2;
-                    t.dev_cover_at = H.cover.size();
-                    H.cover.insert(H.cover.end(), mr.cover.begin(), mr.cover.end());
-                }
-            }
-            ms_device_build = ms_since(t_build0);
-        }
-        if ((rc = upload(s, H.objs, &d.objs))) return rc;
-        if ((rc = upload(s, trees, &d.trees))) return rc;
-        if ((rc = upload(s, texs, &d.texs))) return rc;
-        if ((rc = upload(s, H.beziers, &d.beziers))) return rc;
-        if ((rc = upload(s, H.bez_slabs, &d.bez_slabs))) return rc;
-        // CGRT_NO_BEZIER_CULL=1 (measurement / test aid, read at every commit): run every solve of every ray that enters the box
-        if (const char *e = std::getenv("CGRT_NO_BEZIER_CULL")) if (*e && *e != '0') d.bez_slabs = nullptr;
-        if ((rc = upload(s, hfields, &d.hfields))) return rc;
-        if ((rc = upload(s, H.cover, &d.cover))) return rc;
-        return CGRT_OK;
-    };
-    if (all_uploads() != CGRT_OK) {
+    const size_t cover_host = H.cover.size();
+    if (int rc = upload_scene(s, L, knobs, d, ms_device_build)) {
         for (void *p : s->allocs) (void)hipFree(p);
         s->allocs.clear();
         s->device_bytes = 0;
@@ -422,95 +342,14 @@ int cgrt_scene_commit(cgrt_scene *s, int device) {
         H.cover.resize(cover_host);
         return rc;
     }
-    d.n_objs = (int32_t)H.objs.size();
-    // objects resident in LDS: all of them up to kLdsObjsMax (CGRT_LDS_OBJS, read at every commit, lowers that for measurements
-    // and tests of the spill path)
-    d.n_lds = std::min(d.n_objs, kLdsObjsMax);
-    if (const char *e = std::getenv("CGRT_LDS_OBJS")) d.n_lds = std::max(0, std::min(d.n_lds, std::atoi(e)));
-    d.n_trees = (int32_t)trees.size();
-    d.n_texs = (int32_t)texs.size();
-    d.n_beziers = (int32_t)H.beziers.size();
-    d.n_cover = (int32_t)(H.cover.size() / 4);
-    d.has_wide = 0;
-    for (const TreeRec &tr : trees)
-        if (tr.nwide > 0) d.has_wide = 1;
-    d.has_mesh = trees.empty() ? 0 : 1;
-    d.has_bezier = H.beziers.empty() ? 0 : 1;
-    d.cached_tree = -1;
-    d.cached_nodes = 0;
-    for (size_t t = 0; t < trees.size(); t++)
-        if (trees[t].nnodes > 0 && trees[t].nnodes <= kNodeCache) {  // first tree small enough to live in LDS
-            d.cached_tree = (int32_t)t;
-            d.cached_nodes = trees[t].nnodes;
-            break;
-        }
-    d.all_spheres = 1;
-    d.has_glass = 0;
-    for (auto &o : H.objs) {
-        if (o.kind != KIND_SPHERE) d.all_spheres = 0;
-        if (!(o.transp < kEps)) d.has_glass = 1;  // main.cpp:129: the glass branch is `!(transparency < eps)`
-    }
-    {   // the one opaque mesh whose primary-ray walks may run as their own kernel (cgrt_primwalk.hpp): no other mesh, no Bezier object
-        int n_mesh = 0, at = -1;
-        for (size_t i = 0; i < H.objs.size(); i++)
-            if (H.objs[i].kind == KIND_MESH) { n_mesh++; at = (int)i; }
-        d.prim_obj = -1;
-        if (n_mesh == 1 && H.beziers.empty() && H.objs[(size_t)at].transp < kEps && H.objs[(size_t)at].tree >= 0 &&
-            trees[(size_t)H.objs[(size_t)at].tree].nwide > 0 && at < d.n_lds)
-            d.prim_obj = at;
-        d.prim_finish = d.prim_obj >= 0 ? 1 : 0;
-        for (auto &o : H.objs)
-            if (o.kind == KIND_PLANE && o.tree >= 0) d.prim_finish = 0;
-    }
-    // light tiles (classify_kernel): possible when planes are plain diffuse surfaces and something else is not
-    {
-        bool planes_plain = true, special = false, plane_trees = false;
-        for (auto &o : H.objs) {
-            const bool diffuse = o.refl < kEps && o.transp < kEps;
-            if (o.kind == KIND_PLANE && !diffuse) planes_plain = false;  // a bump map is fine: a diffuse bumped floor still ends the path
-            if (o.kind == KIND_PLANE && o.tree >= 0) plane_trees = true;
-            if (o.kind == KIND_MESH || o.kind == KIND_BEZIER || (o.kind == KIND_SPHERE && !diffuse)) special = true;
-        }
-        d.light_ok = (planes_plain && special && !d.all_spheres) ? 1 : 0;
-        d.single_ray = (planes_plain && !special) ? 1 : 0;
-        d.light_trees = plane_trees ? 1 : 0;  // the light variant then needs the tree / height-field code (not Bezier, not glass)
-        d.light_hf_only = plane_trees ? 1 : 0;
-        // the first run of >= 3 axis-aligned planes without a bump tree, with nothing but other planes in front of it, all in the LDS list
-        d.prun_begin = d.prun_end = 0;
-        static const bool env_no_plane_run = [] { const char *e = std::getenv("CGRT_NO_PLANE_RUN"); return e && *e && *e != '0'; }();
-        if (!env_no_plane_run) {
-            auto eligible = [&](int j) { return H.objs[(size_t)j].kind == KIND_PLANE && H.objs[(size_t)j].axis >= 0 && H.objs[(size_t)j].tree < 0; };
-            int b = 0;  // planes of any sort may stand in front of the run (a bump floor), nothing else
-            while (b < d.n_lds && H.objs[(size_t)b].kind == KIND_PLANE && !eligible(b)) b++;
-            int j = b;
-            while (j < d.n_lds && eligible(j)) j++;
-            if (j - b >= 3) {
-                d.prun_begin = b;
-                d.prun_end = j;
-            }
-        }
-        for (auto &o : H.objs)
-            if (o.kind == KIND_PLANE && o.tree >= 0 && !(o.transp < kEps && trees[(size_t)o.tree].hfield >= 0)) d.light_hf_only = 0;
-        if (d.light_ok && !s->aux_stream) {
-            // the light launch yields to the scheduled one: lowest stream priority
-            int prio_least = 0, prio_greatest = 0;
-            (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-            const char *pe = std::getenv("CGRT_AUX_PRIORITY");
-            const int prio = (pe && std::strcmp(pe, "same") == 0) ? 0 : (pe && std::strcmp(pe, "high") == 0) ? prio_greatest : prio_least;
-            if (hipStreamCreateWithPriority(&s->aux_stream, hipStreamNonBlocking, prio) != hipSuccess ||
-                hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming) != hipSuccess)
-                d.light_ok = 0;  // no second stream: render everything with the full variant
-        }
-    }
+    scene_traits(H, L.trees, knobs, d);
+    open_light_stream(s, knobs.aux_priority, d);
     s->dev = d;
     s->committed = true;
-    s->tree_recs = trees;
-    {
-        size_t fr = 0, tot = 0;
-        s->mem_total = hipMemGetInfo(&fr, &tot) == hipSuccess ? tot : ((size_t)32 << 30);
-    }
-    s->build_info.n_device_trees = n_dev_trees;
+    s->tree_recs = std::move(L.trees);
+    size_t fr = 0, tot = 0;
+    s->mem_total = hipMemGetInfo(&fr, &tot) == hipSuccess ? tot : ((size_t)32 << 30);
+    s->build_info.n_device_trees = L.n_dev_trees;
     s->build_info.ms_device_build = ms_device_build;
     s->build_info.ms_commit = ms_since(t_commit0);
     return CGRT_OK;

@@ -197,10 +197,6 @@ __host__ __device__ inline size_t obj_list_lds(const DeviceScene &sc, int waves)
     return ((size_t)sc.n_lds + (sc.n_objs > sc.n_lds ? (size_t)waves : 0)) * sizeof(ObjRec);
 }
 
-// One small tree (<= kNodeCache nodes: the bunny's 255, a coarse bump floor) is staged whole in LDS by every workgroup:
-// traversal is latency-bound on dependent node fetches, and an LDS read costs ~100 cycles against ~500-800 for L1/L2.
-static constexpr int kNodeCache = 256;  // 8 KiB of 32-byte nodes
-
 // per-workgroup LDS resources handed down to the scene walk
 struct LdsAux {
     volatile BezLds *bl;    // this wave's Bezier scratch (BEZ variants) or nullptr

@@ -163,6 +163,9 @@ static constexpr int kBezSlabs = 64;
 static constexpr int kLdsObjsMax = 768;
 static constexpr size_t kLdsBytes = (size_t)160 << 10;  // LDS of a CU (MI355X): the most one workgroup may use, static + dynamic
 static constexpr int kMaxObjs = 1 << 20;  // sanity limit of cgrt_scene_add_* (CGRT_ERR_LIMIT beyond it)
+// One small tree (<= kNodeCache nodes: the bunny's 255, a coarse bump floor) is staged whole in LDS by every workgroup:
+// traversal is latency-bound on dependent node fetches, and an LDS read costs ~100 cycles against ~500-800 for L1/L2.
+static constexpr int kNodeCache = 256;  // 8 KiB of 32-byte nodes
 
 // Kernel argument block.
 struct DeviceScene {
