@@ -1,0 +1,337 @@
+// The host side of an eye-pass launch in plain C++ (no HIP): the kernel parameters, the workgroup / tile constants, the
+// environment switches and the frame plan -- sample chunks, tile counts, heavy-tile capacity, scheduling and where each
+// array lies in the handle's launch scratch.  cgrt_trace_grid (cgrt_hip.hip) launches what frame_plan decides;
+// tests/native/frame_plan.cpp checks it on the CPU.
+#ifndef CGRT_FRAME_H
+#define CGRT_FRAME_H
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <cstdlib>
+
+#include "../../include/cgrt.h"
+
+// =====================================================================================================
+// kernel parameters
+// =====================================================================================================
+struct GridParams {
+    int32_t W, H, rows, row_offset, stripe_rows, stripe_rank, stripe_nranks;
+    int32_t spp, sample_offset, max_depth;
+    int32_t accumulate;  // CGRT_GRID_ACCUMULATE: rgb += this pass (nhit is overwritten)
+    int32_t xcd_tiles;   // block -> tile mapping: 1 = XCD-aware super-tiles, 0 = row-major (see tile_of_block)
+    // CGRT_GRID_SPLIT_SAMPLES: chunks > 1 workgroups per tile, workgroup c of a tile takes samples [c*chunk_spp, ...) and
+    // leaves its raw fp64 sums in partial[c][local pixel][3] (and its hit count in partial_nhit[c][local pixel])
+    int32_t chunks, chunk_spp;
+    double *partial;
+    uint32_t *partial_nhit;
+    // Cost-aware scheduling (cgrt_hip.hip, "classify -> probe -> plan -> render -> ordered sum").  The unit of
+    // bookkeeping is a WAVE TILE of 16x4 pixels, numbered wy * ceil(W/16) + wx over the local rows.
+    //   probe != 0 : trace this launch's first sample only to measure it -- nothing is stored except cost[wave tile] =
+    //                shader-clock ticks the wave spent on it.
+    //   render     : order[0..K) = the HEAVY wave tiles (plan_kernel), plan[0] = K, hidx[wave tile] = rank among them or -1.
+    //                The first heavy_blocks workgroups of the render launch (the unit-form body; they loop until the queue
+    //                is empty) serve the heavy tiles through a queue of ITEMS (plan[2] = next item; item = heavy tile rank *
+    //                items_per_tile + part): an item is units_per_item (pixel, sample) UNITS of one heavy tile, which the
+    //                lanes of the wave take one after another as they become free, so a heavy tile is spread over many waves
+    //                on many CUs and no lane idles while units remain.  Every Hitpoint value of a unit goes to
+    //                dvals[rank][sample][emission index][pixel] (dcnt = how many), and deferred_sum_kernel adds them per
+    //                pixel in the reference's order -- sample by sample, emission order within a sample -- so the fp64 sum
+    //                is bit for bit the sequential one.  The other tiles are rendered in the tile form (waves whose tile is
+    //                heavy stand down): through the tile queue below, or one workgroup per tile.
+    // Light tiles (classify_kernel): light[wave tile] != 0 -- no primary ray of the tile can come near a mesh, a Bezier
+    // object or a mirror / glass sphere, so it is rendered by the kernel variant without tree, Bezier and pending-ray code
+    // (fewer registers, more waves per SIMD; with bump-mapped diffuse planes: the tree-capable variant without Bezier and
+    // pending-ray code), launched beside the full variant on a second stream.  light_mode: 0 = this
+    // launch leaves the light tiles alone, 1 = this launch renders only them; light == nullptr: no split.
+    const unsigned char *light;
+    int32_t light_mode, pad_light_;
+    const uint32_t *order;
+    // Tile queue of the scheduled launch (chunks == 1): border[0..plan[3]) = the tiles (ty * tiles_x + tx) with at least one
+    // wave tile that is neither heavy nor light, costliest first (plan_kernel); plan[4] = next entry.  The launch is then
+    // heavy_blocks + a chip's worth of workgroups, each serving one queue until it is empty and then the other, so neither
+    // empty tiles nor a late expensive tile cost anything at the end of the frame.  nullptr: one workgroup per tile.
+    const uint32_t *border;
+    uint32_t *cost;
+    const int32_t *hidx;
+    uint32_t *plan;
+    double *dvals;
+    unsigned char *dcnt;
+    double *pconst;  // heavy tiles: per pixel {pdir(3), pof(3), bits of k_pix}, layout [rank][7][64], filled by pixel_const_kernel
+    int32_t probe, heavy_blocks, items_per_tile, units_per_item, maxhp;
+    // Primary-ray mesh hits of the heavy tiles' units, computed by primary_walk_kernel before the render launch
+    // (cgrt_primwalk.hpp): [rank][sample][pixel] distance (kInf: none) and triangle (-1: none) in object prim_obj; nullptr: off
+    const double *prim_len;
+    const int32_t *prim_tri;
+    int32_t prim_obj;
+    int32_t prim_done;  // primary_walk_kernel also completes units (dcnt != 255: done there, the unit-queue body skips them)
+    int32_t pw_refill, pw_rounds;  // primary_walk_kernel: idle lanes that trigger a refill; inner-node rounds between leaf phases
+    // development aid (env CGRT_TIMELINE_FILE, cgrt_hip.hip): per workgroup {start, end (wall_clock64, 100 MHz), HW_ID | XCC_ID << 32,
+    // tile_x | tile_y << 16 | rays << 32}; nullptr in normal operation
+    unsigned long long *timeline;
+    double inv_spp_total;
+    uint64_t seed;
+    double cam[3], half_width, focus_plane, lens_radius;
+};
+static_assert(sizeof(GridParams) == 280, "GridParams is a kernel argument: its layout is fixed");
+
+static constexpr int kTileW = 32, kTileH = 8, kThreads = 256;
+static constexpr int kWaveTileW = 16, kWaveTileH = 4;  // one pixel per lane
+// blockIdx -> tile, XCD-aware (tile_of_block, cgrt_grid.hpp): super-tiles of kSuperW x kSuperH tiles dealt to kXcds L2 groups
+static constexpr int kXcds = 8, kSuperW = 4, kSuperH = 4, kSuperTiles = kSuperW * kSuperH;
+
+inline int tile_grid_blocks(int W, int rows, bool xcd_tiles, int tile_w = kTileW, int tile_h = kTileH) {
+    const int tiles_x = (W + tile_w - 1) / tile_w, tiles_y = (rows + tile_h - 1) / tile_h;
+    if (!xcd_tiles) return tiles_x * tiles_y;
+    const int sx = (tiles_x + kSuperW - 1) / kSuperW, sy = (tiles_y + kSuperH - 1) / kSuperH;
+    const int nsuper = sx * sy;
+    return ((nsuper + kXcds - 1) / kXcds) * kXcds * kSuperTiles;
+}
+
+// The GridParams of a launch over `grid` seen from `cam`, every scheduling, chunk and primary-walk field at its default:
+// row-major tiles, one workgroup per tile with all its samples, no probe, no light split, nothing deferred or walked ahead
+// (fields not named here are 0 / nullptr).
+inline GridParams grid_params(const cgrt_camera *cam, const cgrt_grid *grid) {
+    GridParams g{};
+    g.W = grid->width;
+    g.H = grid->height;
+    g.rows = grid->rows;
+    g.row_offset = grid->row_offset;
+    g.stripe_rows = grid->stripe_rows;
+    g.stripe_rank = grid->stripe_rank;
+    g.stripe_nranks = grid->stripe_nranks;
+    g.spp = grid->spp;
+    g.sample_offset = grid->sample_offset;
+    g.max_depth = grid->max_depth;
+    g.accumulate = (grid->flags & CGRT_GRID_ACCUMULATE) ? 1 : 0;
+    g.inv_spp_total = 1.0 / (double)grid->spp_total;
+    g.seed = grid->seed;
+    for (int k = 0; k < 3; k++) g.cam[k] = cam->cam[k];
+    g.half_width = cam->half_width;
+    g.focus_plane = cam->focus_plane;
+    g.lens_radius = cam->lens_radius;
+    g.chunks = 1;
+    g.chunk_spp = grid->spp;
+    g.items_per_tile = 1;
+    g.units_per_item = 256;
+    g.maxhp = 16;
+    g.prim_obj = -1;
+    g.pw_refill = 16;
+    g.pw_rounds = 8;
+    return g;
+}
+
+// ---- the eye pass's environment switches CGRT_* (measurement and development aids) ----
+struct EyeKnobs {
+    bool force_reorder = false;  // FORCE_REORDER: schedule sphere-only scenes too
+    long long defer_bytes = 0;   // DEFER_BYTES: <= 0: the default
+    int heavy_div = 32, units_per_item = 256;  // HEAVY_DIV, UNITS_PER_ITEM (whole waves)
+    bool no_primwalk = false, pw_no_finish = false;
+    int pw_refill = 16, pw_rounds = 8;
+    int lds_pad = 0;  // LDS_PAD: extra dynamic LDS bytes of the main launch
+    bool no_hfonly = false, no_tile_queue = false, plan_dump = false;
+    const char *timeline_file = nullptr;  // TIMELINE_FILE (nullptr: off)
+};
+inline const char *env_str(const char *name) { const char *e = std::getenv(name); return e ? e : ""; }
+inline bool env_on(const char *name) { const char *e = env_str(name); return *e && *e != '0'; }
+inline int env_positive(const char *name, int def) { const int v = std::atoi(env_str(name)); return v > 0 ? v : def; }
+// Read once per process, at the first launch, except CGRT_TIMELINE_FILE, which every launch reads.
+inline EyeKnobs eye_knobs() {
+    static const EyeKnobs once = [] {
+        EyeKnobs k;
+        k.force_reorder = env_on("CGRT_FORCE_REORDER");
+        k.defer_bytes = std::atoll(env_str("CGRT_DEFER_BYTES"));
+        k.heavy_div = env_positive("CGRT_HEAVY_DIV", 32);
+        k.units_per_item = (env_positive("CGRT_UNITS_PER_ITEM", 256) + 63) / 64 * 64;
+        k.no_primwalk = env_on("CGRT_NO_PRIMWALK");
+        k.pw_no_finish = env_on("CGRT_PW_NO_FINISH");
+        k.pw_refill = env_positive("CGRT_PW_REFILL", 16);
+        k.pw_rounds = env_positive("CGRT_PW_ROUNDS", 8);
+        k.lds_pad = std::atoi(env_str("CGRT_LDS_PAD"));
+        k.no_hfonly = env_on("CGRT_NO_HFONLY");
+        k.no_tile_queue = env_on("CGRT_NO_TILE_QUEUE");
+        k.plan_dump = env_on("CGRT_PLAN_DUMP");
+        return k;
+    }();
+    EyeKnobs k = once;
+    k.timeline_file = *env_str("CGRT_TIMELINE_FILE") ? env_str("CGRT_TIMELINE_FILE") : nullptr;
+    return k;
+}
+
+// =====================================================================================================
+// the frame plan
+// =====================================================================================================
+// What the plan needs of a launch: cgrt_trace_grid's arguments, its eye launch (EyeLaunch), the scene (DeviceScene) and
+// the device (read at commit)
+struct FrameInputs {
+    cgrt_grid grid;
+    cgrt_camera cam;
+    bool sched, spill, stats, glass;  // the eye launch: form == Sched, and its kernel's flags
+    int nt;                           // threads per workgroup: 256, or 64 (one-wave workgroups on 16x4 tiles)
+    bool has_mesh, has_bezier, prim_finish, light_ok;
+    int prim_obj;
+    EyeKnobs knobs;
+    size_t mem_total;
+    int n_cu, waves_per_simd;  // waves_per_simd: the scheduled kernel's occupancy (kBezWaves, kSchedTreeWaves or 4)
+};
+
+// A part of the launch scratch; bytes == 0: not used by this frame (its pointer is nullptr)
+struct Region {
+    size_t at, bytes;
+    template <class T> T *in(unsigned char *base) const { return bytes ? reinterpret_cast<T *>(base + at) : nullptr; }
+};
+// Where each array of a launch lies in the handle's scratch, in bytes from its start: the chunk sums, then (scheduled
+// launches) the schedule arrays and the deferred arrays of kmax heavy tiles, one array after another.
+struct ScratchLayout {
+    Region partial{}, partial_nhit{}, cost{}, order{}, hidx{}, border{}, plan{}, light{}, dvals{}, dcnt{}, pconst{}, prim_len{}, prim_tri{};
+    size_t total = 0;  // bytes to allocate
+    void place(GridParams &g, unsigned char *base, bool nhit) const {
+        g.partial = partial.in<double>(base);
+        g.partial_nhit = nhit ? partial_nhit.in<uint32_t>(base) : nullptr;
+        g.cost = cost.in<uint32_t>(base);
+        g.order = order.in<uint32_t>(base);
+        g.hidx = hidx.in<int32_t>(base);
+        g.border = border.in<uint32_t>(base);
+        g.plan = plan.in<uint32_t>(base);
+        g.light = light.in<unsigned char>(base);
+        g.dvals = dvals.in<double>(base);
+        g.dcnt = dcnt.in<unsigned char>(base);
+        g.pconst = pconst.in<double>(base);
+        g.prim_len = prim_len.in<double>(base);
+        g.prim_tri = prim_tri.in<int32_t>(base);
+    }
+};
+
+struct FramePlan {
+    int chunks = 1, chunk_spp = 0;  // CGRT_GRID_SPLIT_SAMPLES: workgroups per tile, samples per workgroup
+    bool xcd_tiles = false;         // XCD-aware super-tiles, else row-major (tile_of_block)
+    int maxhp = 1;                  // Hitpoints per sample: a mirror chain ends in one, a glass tree of depth 5 in <= 16
+    int tile_blocks = 0;            // workgroups over the tiles of one chunk
+    size_t grid_dim = 0;            // the launch's tile workgroups (behind heavy_blocks unit-form ones)
+    int wtiles_x = 0, wtiles_y = 0;
+    size_t n_wt = 0, tile_bytes = 0, kmax = 0;  // wave tiles; deferred bytes per heavy tile; heavy tiles they hold (0: image order)
+    bool use_prim = false;                      // the primary walk's distances and triangles (in tile_bytes)
+    // kmax > 0 only (off / 0 otherwise)
+    bool split_light = false, tile_queue = false, prim_done = false;
+    int wave_slots = 0, items_per_tile = 1, heavy_blocks = 0;
+    unsigned long long plan_div = 0;  // plan_kernel: heavy when cost x spp > total x spp / plan_div
+    ScratchLayout scratch;
+};
+
+static constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// The launch at capacity kmax (0 when it is not scheduled): a function of the inputs and kmax only
+inline FramePlan frame_plan(const FrameInputs &in, size_t kmax) {
+    const cgrt_grid &gr = in.grid;
+    const EyeKnobs &kn = in.knobs;
+    FramePlan p;
+    p.chunk_spp = gr.spp;
+    p.xcd_tiles = !in.spill && in.has_mesh && !in.has_bezier;
+    p.maxhp = in.glass ? 16 : 1;
+    // Split a tile's samples over several workgroups (CGRT_GRID_SPLIT_SAMPLES, opt-in for every scene since the cost
+    // scheduler balances Bezier scenes too): chunks of >= 16 samples, at most 16 chunks, at most 4 GiB of chunk sums.
+    const size_t npx = (size_t)gr.rows * gr.width;
+    if ((gr.flags & CGRT_GRID_SPLIT_SAMPLES) && gr.spp >= 32 && !in.spill) {
+        int chunks = std::min(gr.spp / 16, 16);
+        while (chunks > 1 && (size_t)chunks * npx * 28 > ((size_t)4 << 30)) chunks--;
+        if (chunks > 1) {
+            p.chunk_spp = (gr.spp + chunks - 1) / chunks;
+            p.chunks = (gr.spp + p.chunk_spp - 1) / p.chunk_spp;
+        }
+    }
+    // Bezier scenes run one-wave workgroups on 16x4 tiles (TileGeom<64>): waves over the vase outlast their neighbours ~100x
+    const bool one_wave = in.nt == 64;
+    const int waves_per_block = in.nt / 64;
+    p.tile_blocks = one_wave ? tile_grid_blocks(gr.width, gr.rows, false, kWaveTileW, kWaveTileH)
+                             : tile_grid_blocks(gr.width, gr.rows, p.xcd_tiles);
+    p.grid_dim = (size_t)p.tile_blocks * p.chunks;
+    p.wtiles_x = (gr.width + kWaveTileW - 1) / kWaveTileW;
+    p.wtiles_y = (gr.rows + kWaveTileH - 1) / kWaveTileH;
+    p.n_wt = (size_t)p.wtiles_x * p.wtiles_y;
+    // primary-ray mesh hits of the heavy tiles' units (cgrt_primwalk.hpp): a double and an int per unit
+    p.use_prim = in.sched && in.prim_obj >= 0 && !kn.no_primwalk && !(gr.flags & CGRT_GRID_STATS);
+    // per heavy tile: its Hitpoint values [spp][maxhp][64 px][3], their counts [spp][64 px] (padded to 8 bytes), the pixel
+    // constants [7][64] and, with the primary walk, its distances and triangles [spp][64]
+    const size_t units = (size_t)gr.spp * 64;
+    const size_t vals = units * (size_t)p.maxhp * 3 * sizeof(double), cnt = (units + 7) & ~(size_t)7, pconst = 7 * 64 * sizeof(double),
+                 plen = p.use_prim ? units * sizeof(double) : 0, ptri = p.use_prim ? units * sizeof(int32_t) : 0;
+    p.tile_bytes = vals + cnt + pconst + plen + ptri;
+    p.kmax = in.sched ? kmax : 0;
+
+    ScratchLayout &L = p.scratch;
+    size_t end = 0;  // the arrays one after another; used == false: room kept, nothing placed
+    const auto take = [&end](size_t bytes, bool used = true) { end += bytes; return Region{end - bytes, used ? bytes : 0}; };
+    if (p.chunks > 1) {
+        L.partial = take((size_t)p.chunks * npx * 3 * sizeof(double));
+        L.partial_nhit = take((size_t)p.chunks * npx * sizeof(uint32_t));
+    }
+    L.total = end = align256(end);
+    if (!in.sched) return p;
+    // cost, order, hidx, border (8 entries of slack each), plan[64], light: reserved even when no heavy tile fits
+    const size_t np = (p.n_wt + 8) * sizeof(uint32_t), sched_bytes = align256(4 * np + 64 * sizeof(uint32_t) + align256(p.n_wt));
+    L.total += sched_bytes + (p.kmax ? p.kmax * p.tile_bytes + 256 : 0);
+    if (p.kmax == 0) return p;
+    p.split_light = in.light_ok && p.chunks == 1 && !in.stats;
+    // tiles through a queue too (GridParams::border) unless their samples are split over workgroups or the workgroups are
+    // single waves (trace_grid_sched_kernel)
+    p.tile_queue = p.chunks == 1 && !one_wave && !kn.no_tile_queue;
+    p.prim_done = p.use_prim && in.prim_finish && !kn.pw_no_finish;
+    // heavy: cost x spp > (total cost x spp / wave slots) / heavy_div
+    p.wave_slots = in.n_cu * 4 * in.waves_per_simd;
+    p.plan_div = (unsigned long long)p.wave_slots * (unsigned long long)kn.heavy_div;
+    p.items_per_tile = (int)((units + kn.units_per_item - 1) / kn.units_per_item);
+    // enough heavy workgroups to fill the chip once: they loop over the item queue until it is empty
+    const size_t fill = (size_t)p.wave_slots / waves_per_block;
+    p.heavy_blocks = (int)std::min((p.kmax * (size_t)p.items_per_tile + waves_per_block - 1) / waves_per_block, fill);
+    if (p.tile_queue) p.grid_dim = fill;  // tile workgroups: a chip's worth, each loops over the tile queue
+    const size_t sched_at = end;
+    L.cost = take(np);
+    L.order = take(np);
+    L.hidx = take(np);
+    L.border = take(np, p.tile_queue);
+    L.plan = take(64 * sizeof(uint32_t));
+    L.light = take(p.n_wt, p.split_light);
+    end = sched_at + sched_bytes;
+    L.dvals = take(p.kmax * vals);
+    L.dcnt = take(p.kmax * cnt);
+    L.pconst = take(p.kmax * pconst);
+    L.prim_len = take(p.kmax * plen);
+    L.prim_tri = take(p.kmax * ptri);
+    return p;
+}
+
+// Heavy tiles the deferred arrays may hold before the device is asked: up to 12 GiB, at most an eighth of the scene's
+// device (MI355X: 288 GB; read at commit -- a process may drive devices of different sizes), or CGRT_DEFER_BYTES
+inline size_t max_heavy_tiles(const FrameInputs &in) {
+    if (!in.sched) return 0;
+    const FramePlan p = frame_plan(in, 0);
+    const size_t budget = in.knobs.defer_bytes > 0 ? (size_t)in.knobs.defer_bytes : std::min((size_t)12 << 30, in.mem_total / 8);
+    return std::min(budget / p.tile_bytes, p.n_wt);
+}
+
+// A size the device has refused before (refused; 0: none) is not asked for again -- every attempt is a synchronous hipFree
+// plus failing hipMallocs: the deferred arrays shrink, fewer heavy tiles and the same image, until the need lies below it
+inline size_t fit_heavy_tiles(const FrameInputs &in, size_t kmax, size_t refused) {
+    while (refused && kmax > 0 && frame_plan(in, kmax).scratch.total >= refused) kmax /= 2;
+    return kmax;
+}
+
+// The launch's GridParams, scratch not yet placed
+inline GridParams frame_params(const FrameInputs &in, const FramePlan &p) {
+    GridParams g = grid_params(&in.cam, &in.grid);
+    g.xcd_tiles = p.xcd_tiles ? 1 : 0;
+    g.chunks = p.chunks;
+    g.chunk_spp = p.chunk_spp;
+    g.maxhp = p.maxhp;
+    g.units_per_item = in.knobs.units_per_item;
+    g.pw_refill = in.knobs.pw_refill;
+    g.pw_rounds = in.knobs.pw_rounds;
+    g.items_per_tile = p.items_per_tile;
+    g.heavy_blocks = p.heavy_blocks;
+    if (p.heavy_blocks > 0 && p.use_prim) {
+        g.prim_obj = in.prim_obj;
+        g.prim_done = p.prim_done ? 1 : 0;
+    }
+    return g;
+}
+
+#endif

@@ -45,6 +45,30 @@ using namespace cgrt;
 // =====================================================================================================
 // host side: scene handle, upload, C ABI
 // =====================================================================================================
+// Grow-only device scratch, reused by later launches or batches (hipFree synchronises, so it is not freed per use): a larger
+// request frees it and allocates the new size; a failed one leaves it empty
+struct GrowBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    GrowBuf() = default;
+    GrowBuf(const GrowBuf &) = delete;
+    GrowBuf &operator=(const GrowBuf &) = delete;
+    ~GrowBuf() { release(); }
+    hipError_t need(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e == hipSuccess) cap = bytes;
+        else p = nullptr;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
 struct cgrt_scene {
     HostScene host;
     bool committed = false;
@@ -52,12 +76,12 @@ struct cgrt_scene {
     DeviceScene dev{};
     std::vector<void *> allocs;
     int64_t device_bytes = 0;
-    // CGRT_GRID_SPLIT_SAMPLES: chunk sums between the two kernels; grown on demand, reused by later launches on this handle
+    // launch scratch (chunk sums, schedule, deferred Hitpoint values: ScratchLayout); reused by later launches on this handle
     // (launches on one handle are ordered by the caller: cgrt.h, "Threading")
-    mutable void *scratch = nullptr;
-    mutable size_t scratch_bytes = 0;
+    mutable GrowBuf scratch;
     mutable size_t scratch_refused = 0;  // smallest scratch size this device has refused (0: none yet): not asked for again
     size_t mem_total = 0;                // memory of the scene's device (read at commit; bounds the deferred-value budget)
+    int n_cu = 256;                      // compute units of the scene's device (read at commit; wave slots of the scheduler)
     // second stream + fork/join events for the light-tile launch that runs beside the full one (created at commit)
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -143,11 +167,11 @@ int cgrt_scene_create(cgrt_scene **out) {
 
 void cgrt_scene_destroy(cgrt_scene *s) {
     if (!s) return;
-    if (!s->allocs.empty() || s->scratch || s->aux_stream) {
+    if (!s->allocs.empty() || s->scratch.p || s->aux_stream) {
         DeviceGuard g(s->device);
         if (g.err == hipSuccess) {
             for (void *p : s->allocs) (void)hipFree(p);
-            if (s->scratch) (void)hipFree(s->scratch);
+            s->scratch.release();
             if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
             if (s->ev_join) (void)hipEventDestroy(s->ev_join);
             if (s->aux_stream) (void)hipStreamDestroy(s->aux_stream);
@@ -349,6 +373,10 @@ int cgrt_scene_commit(cgrt_scene *s, int device) {
     s->tree_recs = std::move(L.trees);
     size_t fr = 0, tot = 0;
     s->mem_total = hipMemGetInfo(&fr, &tot) == hipSuccess ? tot : ((size_t)32 << 30);
+    if (hipDeviceGetAttribute(&s->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || s->n_cu <= 0) {
+        (void)hipGetLastError();
+        s->n_cu = 256;
+    }
     s->build_info.n_device_trees = L.n_dev_trees;
     s->build_info.ms_device_build = ms_device_build;
     s->build_info.ms_commit = ms_since(t_commit0);
@@ -381,7 +409,7 @@ int cgrt_scene_get_stats(const cgrt_scene *s, cgrt_scene_stats *out) {
     bytes += 56 * out->n_nodes + 72 * out->n_triangles;
     for (auto &t : H.textures) bytes += 3 * (int64_t)t.rows * t.cols;
     out->scene_bytes_fp64 = bytes;
-    out->device_bytes = s->device_bytes + (int64_t)s->scratch_bytes;  // uploaded scene + the handle's launch scratch
+    out->device_bytes = s->device_bytes + (int64_t)s->scratch.cap;  // uploaded scene + the handle's launch scratch
     out->committed = s->committed ? 1 : 0;
     return CGRT_OK;
 }
@@ -646,34 +674,6 @@ static int general_resident(const cgrt_scene *s, bool dof, bool hps) {
     return (int)std::max(0ll, std::min(room / (long long)sizeof(ObjRec), (long long)d.n_lds));
 }
 
-// ---- the eye pass's environment switches (measurement and development aids) ----
-// Read once per process, at the first launch, except CGRT_TIMELINE_FILE, which every launch reads.
-static const char *env_str(const char *name) { const char *e = std::getenv(name); return e ? e : ""; }
-static bool env_on(const char *name) { const char *e = env_str(name); return *e && *e != '0'; }
-static int positive_or(int v, int def) { return v > 0 ? v : def; }
-struct EyeKnobs {
-    bool force_reorder = env_on("CGRT_FORCE_REORDER");  // schedule sphere-only scenes too
-    long long defer_bytes = std::atoll(env_str("CGRT_DEFER_BYTES"));  // <= 0: the default
-    int heavy_div = positive_or(std::atoi(env_str("CGRT_HEAVY_DIV")), 32);
-    int units_per_item = (positive_or(std::atoi(env_str("CGRT_UNITS_PER_ITEM")), 256) + 63) / 64 * 64;  // whole waves
-    bool no_primwalk = env_on("CGRT_NO_PRIMWALK");
-    bool pw_no_finish = env_on("CGRT_PW_NO_FINISH");
-    int pw_refill = positive_or(std::atoi(env_str("CGRT_PW_REFILL")), 16);
-    int pw_rounds = positive_or(std::atoi(env_str("CGRT_PW_ROUNDS")), 8);
-    int lds_pad = std::atoi(env_str("CGRT_LDS_PAD"));  // extra dynamic LDS bytes of the main launch
-    bool no_hfonly = env_on("CGRT_NO_HFONLY");
-    bool no_tile_queue = env_on("CGRT_NO_TILE_QUEUE");
-    bool plan_dump = env_on("CGRT_PLAN_DUMP");
-    const char *timeline_file = nullptr;  // CGRT_TIMELINE_FILE (nullptr: off)
-};
-static EyeKnobs eye_knobs() {
-    static const EyeKnobs once;
-    EyeKnobs k = once;
-    const char *tf = env_str("CGRT_TIMELINE_FILE");
-    k.timeline_file = *tf ? tf : nullptr;
-    return k;
-}
-
 // ---- the eye pass's launch plan ----
 enum class EyeForm { Image, Sched, SpillSph, SpillGen, Capture, Light, LightHF };
 // One launch of the eye pass: which kernel (form and template flags), the scene as it sees it and its dynamic LDS
@@ -747,60 +747,6 @@ static int launch_eye(const EyeLaunch &L, bool sched, int device, const GridPara
     return fail(CGRT_ERR_UNSUPPORTED, std::string(L.what()) + ": no kernel built for this variant");
 }
 
-// The GridParams of a launch over `grid` seen from `cam`, every scheduling, chunk and primary-walk field at its default:
-// row-major tiles, one workgroup per tile with all its samples, no probe, no light split, nothing deferred or walked ahead
-// (fields not named here are 0 / nullptr).
-static GridParams grid_params(const cgrt_camera *cam, const cgrt_grid *grid) {
-    GridParams g{};
-    g.W = grid->width;
-    g.H = grid->height;
-    g.rows = grid->rows;
-    g.row_offset = grid->row_offset;
-    g.stripe_rows = grid->stripe_rows;
-    g.stripe_rank = grid->stripe_rank;
-    g.stripe_nranks = grid->stripe_nranks;
-    g.spp = grid->spp;
-    g.sample_offset = grid->sample_offset;
-    g.max_depth = grid->max_depth;
-    g.accumulate = (grid->flags & CGRT_GRID_ACCUMULATE) ? 1 : 0;
-    g.inv_spp_total = 1.0 / (double)grid->spp_total;
-    g.seed = grid->seed;
-    for (int k = 0; k < 3; k++) g.cam[k] = cam->cam[k];
-    g.half_width = cam->half_width;
-    g.focus_plane = cam->focus_plane;
-    g.lens_radius = cam->lens_radius;
-    g.chunks = 1;
-    g.chunk_spp = grid->spp;
-    g.items_per_tile = 1;
-    g.units_per_item = 256;
-    g.maxhp = 16;
-    g.prim_obj = -1;
-    g.pw_refill = 16;
-    g.pw_rounds = 8;
-    return g;
-}
-
-// The scheduler's deferred buffer: per heavy tile, its Hitpoint values [spp][maxhp][64 px][3], their counts [spp][64 px]
-// (padded to 8 bytes), the pixel constants [7][64] and, with the primary walk, its distances and triangles [spp][64].  Each
-// array holds kmax heavy tiles, one array after another.
-struct DeferLayout {
-    size_t vals, cnt, pconst, prim_len, prim_tri;  // bytes per heavy tile
-    DeferLayout(int spp, int maxhp, bool prim)
-        : vals((size_t)spp * 64 * (size_t)maxhp * 3 * sizeof(double)), cnt(((size_t)spp * 64 + 7) & ~(size_t)7),
-          pconst(7 * 64 * sizeof(double)), prim_len(prim ? (size_t)spp * 64 * sizeof(double) : 0),
-          prim_tri(prim ? (size_t)spp * 64 * sizeof(int32_t) : 0) {}
-    size_t per_tile() const { return vals + cnt + pconst + prim_len + prim_tri; }
-    void place(GridParams &g, unsigned char *base, size_t kmax) const {
-        g.dvals = reinterpret_cast<double *>(base);
-        g.dcnt = base + kmax * vals;
-        g.pconst = reinterpret_cast<double *>(base + kmax * (vals + cnt));
-        if (prim_len) {
-            g.prim_len = reinterpret_cast<const double *>(base + kmax * (vals + cnt + pconst));
-            g.prim_tri = reinterpret_cast<const int32_t *>(base + kmax * (vals + cnt + pconst + prim_len));
-        }
-    }
-};
-
 static int check_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *g) {
     if (!s || !cam || !g) return fail(CGRT_ERR_INVALID, "null argument");
     if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
@@ -815,6 +761,110 @@ static int check_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_gr
         return fail(CGRT_ERR_INVALID, "bad row_offset");
     }
     if (!(cam->lens_radius >= 0)) return fail(CGRT_ERR_INVALID, "lens_radius must be >= 0");
+    return CGRT_OK;
+}
+
+// ---- cgrt_trace_grid's stages ----
+// The plan whose scratch the handle holds.  A device short of memory gets a smaller deferred buffer (fewer heavy tiles, the
+// same image) before it gets an error; every refused size is remembered (fit_heavy_tiles).
+static int fit_scratch(const cgrt_scene *s, const FrameInputs &in, FramePlan &p) {
+    p = frame_plan(in, fit_heavy_tiles(in, max_heavy_tiles(in), s->scratch_refused));
+    while (s->scratch.need(p.scratch.total) != hipSuccess) {
+        (void)hipGetLastError();
+        if (!s->scratch_refused || p.scratch.total < s->scratch_refused) s->scratch_refused = p.scratch.total;
+        if (p.kmax == 0) return fail(CGRT_ERR_DEVICE, "cannot allocate launch scratch (chunk sums / schedule / deferred Hitpoint values)");
+        p = frame_plan(in, p.kmax / 2);
+    }
+    return CGRT_OK;
+}
+
+// Cost-aware scheduling ("classify -> probe -> plan -> render -> ordered sum"; DESIGN.md sections 4.6-4.7).  A frame's cost
+// is concentrated in a few tiles (a glass mesh: one 32x8 tile ran 38 of the frame's 46 ms while four of the eight XCDs
+// were idle after 6 ms), the hardware hands out workgroups in block-index order, and a tile is bound to one wave per
+// 64 pixels.  So: (0) classify_kernel marks the LIGHT wave tiles (no primary ray can reach a mesh, a Bezier object or a
+// reflecting / refracting sphere), which a lighter kernel variant renders on a second stream; (1) the full variant traces
+// ONE sample of every other wave tile (16x4 pixels) storing nothing but the shader-clock ticks it took; (2) plan_kernel
+// marks as HEAVY the tiles that alone would hold a wave slot for more than 1/heavy_div of the frame's ideal duration,
+// orders them heaviest first, and lists the remaining tiles with something to render, costliest first; (3) the render
+// launch serves the heavy tiles through a queue of (pixel, sample) units that any lane of any wave may take, and the
+// other tiles through a queue of tiles, with persistent workgroups serving both (GridParams); (4) deferred_sum_kernel
+// adds the heavy tiles' Hitpoint values in the reference's order.  The image does not depend on any of this -- every
+// Hitpoint value is added to its pixel in sample order, emission order within a sample --: identical bits and counters;
+// the probe costs 1/spp of the frame and the whole scheme is skipped below 4 samples per pixel or on request
+// (CGRT_GRID_NO_REORDER); eye_launch decides it.  Here (0) to (2); g: the frame's GridParams before the scratch is placed.
+static int probe_and_plan(const cgrt_scene *s, const EyeLaunch &L, const EyeKnobs &kn, const FramePlan &p, const GridParams &g,
+                          unsigned char *scratch, hipStream_t st, float *rgb, uint32_t *nhit, unsigned long long *cnt) {
+    const ScratchLayout &at = p.scratch;
+    unsigned char *light = at.light.in<unsigned char>(scratch);  // nullptr: no light split
+    if (light)
+        hipLaunchKernelGGL(classify_kernel, dim3((unsigned)((p.n_wt + 255) / 256)), dim3(256), 0, st, s->dev, g, light, (int)p.n_wt);
+    GridParams gp = g;  // the probe: this launch's first sample, natural order, one workgroup per tile, nothing stored
+    gp.spp = gp.chunks = gp.chunk_spp = 1;
+    gp.probe = 1;
+    gp.cost = at.cost.in<uint32_t>(scratch);
+    gp.light = light;  // light tiles are not probed (plan_kernel counts them as zero); their cost entries stay unwritten
+    int rc = launch_eye(L, false, s->device, gp, dim3((unsigned)p.tile_blocks), st, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    if (light) {
+        // The light tiles: the variant without tree / Bezier / pending-ray code on the second stream, beside everything that
+        // follows here.  It needs nothing but the classification and starts as soon as the probe is through, beside the
+        // plan (one workgroup, 0.1-0.3 ms).  Started before the probe it perturbs the measured costs and delays the
+        // probe's workgroups: C3 14.4 -> 14.1 ms but C4 (spp 64) 33.6 -> 35.3 ms.
+        GridParams gl = g;
+        gl.light = light;
+        gl.light_mode = 1;
+        gl.xcd_tiles = 0;
+        HIP_TRY(hipEventRecord(s->ev_fork, st));
+        HIP_TRY(hipStreamWaitEvent(s->aux_stream, s->ev_fork, 0));
+        if ((rc = launch_eye(light_launch(s->dev, L.k.dof, kn), false, s->device, gl,
+                             dim3((unsigned)tile_grid_blocks(g.W, g.rows, false)), s->aux_stream, rgb, nhit, cnt)))
+            return rc;
+        HIP_TRY(hipEventRecord(s->ev_join, s->aux_stream));
+    }
+    const int tw = L.k.nt == 64 ? 1 : kTileW / kWaveTileW, th = L.k.nt == 64 ? 1 : kTileH / kWaveTileH;  // wave tiles per tile
+    hipLaunchKernelGGL(plan_kernel, dim3(1), dim3(1024), 0, st, gp.cost, light, (int)p.n_wt, (unsigned)p.kmax, p.plan_div,
+                       at.plan.in<uint32_t>(scratch), at.order.in<uint32_t>(scratch), at.hidx.in<int32_t>(scratch),
+                       at.border.in<uint32_t>(scratch), p.wtiles_x, p.wtiles_y, tw, th);
+    return CGRT_OK;
+}
+
+// The heavy units' primary rays against the mesh, as a walk-only kernel with lane refill (cgrt_primwalk.hpp): a chip's worth
+// of persistent workgroups at 4 waves per SIMD
+static int primary_walk(const cgrt_scene *s, const EyeLaunch &L, const GridParams &g, hipStream_t st, unsigned long long *cnt) {
+    PrimWalkArgs pw;
+    pw.len = const_cast<double *>(g.prim_len);
+    pw.tri = const_cast<int32_t *>(g.prim_tri);
+    pw.obj = s->dev.prim_obj;
+    pw.tree = s->host.objs[(size_t)s->dev.prim_obj].tree;
+    pw.finish = g.prim_done;
+    pw.pad_ = 0;
+    pw.counters = cnt;
+    const size_t staged = (size_t)(pw.finish ? s->dev.n_objs : pw.obj + 1);  // all objects when it finishes units
+    return launch_checked(L.k.dof ? &primary_walk_kernel<true> : &primary_walk_kernel<false>, "primary_walk_kernel", s->device,
+                          dim3((unsigned)s->n_cu * 4), dim3(kThreads), primary_walk_lds(staged), st, s->dev, g, pw);
+}
+
+// development aid: CGRT_TIMELINE_FILE=path makes a launch synchronous and dumps, per workgroup, when and where it ran
+// (GridParams::timeline), behind a header {workgroups, threads per workgroup, chunks, xcd_tiles} (tools/timeline_probe.py)
+static int write_timeline(const char *file, const DevBuf &tl, size_t n_blocks, const FramePlan &p, int nt, hipStream_t st) {
+    std::vector<unsigned long long> rec(n_blocks * 4);
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(rec.data(), tl.p, rec.size() * 8, hipMemcpyDeviceToHost));
+    if (FILE *f = std::fopen(file, "wb")) {
+        const unsigned long long head[4] = {n_blocks, (unsigned long long)nt, (unsigned long long)p.chunks, (unsigned long long)p.xcd_tiles};
+        std::fwrite(head, 8, 4, f);
+        std::fwrite(rec.data(), 8, rec.size(), f);
+        std::fclose(f);
+    }
+    return CGRT_OK;
+}
+// development aid: CGRT_PLAN_DUMP=1 makes a scheduled launch synchronous and prints what the planner decided
+static int dump_plan(const FramePlan &p, const GridParams &g, hipStream_t st) {
+    uint32_t pl[8] = {0};
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(pl, g.plan, sizeof(pl), hipMemcpyDeviceToHost));
+    std::fprintf(stderr, "cgrt plan: wave tiles %zu, heavy %u (capacity %zu), cost threshold %u, tile-queue entries %u, items per tile %d, prim walk %s\n",
+                 p.n_wt, pl[0], p.kmax, pl[1], pl[3], g.items_per_tile, g.prim_len ? "on" : "off");
     return CGRT_OK;
 }
 
@@ -846,231 +896,38 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     ON_DEVICE(s->device);
     const EyeKnobs kn = eye_knobs();
     const EyeLaunch L = eye_launch(s, cam, grid, kn, false);
-    GridParams g = grid_params(cam, grid);
-    g.xcd_tiles = (!L.k.spill && s->dev.has_mesh && !s->dev.has_bezier) ? 1 : 0;
-    g.units_per_item = kn.units_per_item;
-    g.maxhp = L.k.glass ? 16 : 1;  // Hitpoints per sample: a mirror chain ends in one, a glass tree of depth 5 in <= 16
-    g.pw_refill = kn.pw_refill;
-    g.pw_rounds = kn.pw_rounds;
-    // Split a tile's samples over several workgroups (CGRT_GRID_SPLIT_SAMPLES, opt-in for every scene since the cost
-    // scheduler balances Bezier scenes too): chunks of >= 16 samples, at most 16 chunks, at most 4 GiB of chunk sums.
-    const size_t npx_all = (size_t)grid->rows * grid->width;
-    if ((grid->flags & CGRT_GRID_SPLIT_SAMPLES) && grid->spp >= 32 && !L.k.spill) {
-        int chunks = grid->spp / 16;
-        if (chunks > 16) chunks = 16;
-        while (chunks > 1 && (size_t)chunks * npx_all * 28 > ((size_t)4 << 30)) chunks--;
-        if (chunks > 1) {
-            g.chunk_spp = (grid->spp + chunks - 1) / chunks;
-            g.chunks = (grid->spp + g.chunk_spp - 1) / g.chunk_spp;
-        }
-    }
-    // Bezier scenes run one-wave workgroups on 16x4 tiles (TileGeom<64>): waves over the vase outlast their neighbours ~100x
-    const bool one_wave = L.k.nt == 64;
-    const int waves_per_block = L.k.nt / 64;
-    const int tile_blocks = one_wave ? tile_grid_blocks(g.W, g.rows, false, TileGeom<64>::W, TileGeom<64>::H)
-                                     : tile_grid_blocks(g.W, g.rows, g.xcd_tiles != 0);
-    dim3 grid_dim((unsigned)(tile_blocks * g.chunks));
-    if (L.k.spill) {
-        // More top-level objects than the LDS list holds: the SPILL variants, in image order, whole tiles.  Such scenes are
-        // bound by their object loop, not by tile imbalance.
-        if ((rc = launch_eye(L, false, s->device, g, grid_dim, st, rgb, nhit, cnt))) return rc;
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(CGRT_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-        return CGRT_OK;
-    }
-    // Cost-aware scheduling ("classify -> probe -> plan -> render -> ordered sum"; DESIGN.md sections 4.6-4.7).  A frame's cost
-    // is concentrated in a few tiles (a glass mesh: one 32x8 tile ran 38 of the frame's 46 ms while four of the eight XCDs
-    // were idle after 6 ms), the hardware hands out workgroups in block-index order, and a tile is bound to one wave per
-    // 64 pixels.  So: (0) classify_kernel marks the LIGHT wave tiles (no primary ray can reach a mesh, a Bezier object or a
-    // reflecting / refracting sphere), which a lighter kernel variant renders on a second stream; (1) the full variant traces
-    // ONE sample of every other wave tile (16x4 pixels) storing nothing but the shader-clock ticks it took; (2) plan_kernel
-    // marks as HEAVY the tiles that alone would hold a wave slot for more than 1/heavy_div of the frame's ideal duration,
-    // orders them heaviest first, and lists the remaining tiles with something to render, costliest first; (3) the render
-    // launch serves the heavy tiles through a queue of (pixel, sample) units that any lane of any wave may take, and the
-    // other tiles through a queue of tiles, with persistent workgroups serving both (GridParams); (4) deferred_sum_kernel
-    // adds the heavy tiles' Hitpoint values in the reference's order.  The image does not depend on any of this -- every
-    // Hitpoint value is added to its pixel in sample order, emission order within a sample --: identical bits and counters;
-    // the probe costs 1/spp of the frame and the whole scheme is skipped below 4 samples per pixel or on request
-    // (CGRT_GRID_NO_REORDER); eye_launch decides it.
-    const int wtiles_x = (g.W + kWaveTileW - 1) / kWaveTileW, wtiles_y = (g.rows + kWaveTileH - 1) / kWaveTileH;
-    const size_t n_wt = (size_t)wtiles_x * wtiles_y;
-    const bool reorder = L.form == EyeForm::Sched;
-    // primary-ray mesh hits of the heavy tiles' units (cgrt_primwalk.hpp): a double and an int per unit
-    const bool use_prim = s->dev.prim_obj >= 0 && !kn.no_primwalk && !(grid->flags & CGRT_GRID_STATS);
-    const DeferLayout defer(grid->spp, g.maxhp, use_prim);
-    size_t kmax = 0;
-    const size_t sched_pad = 8;
-    size_t sched_bytes = 0, defer_bytes = 0;
-    if (reorder) {
-        // deferred Hitpoint values: up to 12 GiB, at most an eighth of THIS scene's device (MI355X: 288 GB; read at commit -- a
-        // process may drive devices of different sizes); allocated once per scene handle, as large as the biggest launch needed it
-        const size_t defer_budget = kn.defer_bytes > 0 ? (size_t)kn.defer_bytes : std::min((size_t)12 << 30, s->mem_total / 8);
-        sched_bytes = (4 * (n_wt + sched_pad) + 64) * sizeof(uint32_t) + ((n_wt + 255) & ~(size_t)255);  // cost, order, hidx, border, plan, light
-        sched_bytes = (sched_bytes + 255) & ~(size_t)255;
-        kmax = std::min(defer_budget / defer.per_tile(), n_wt);
-        defer_bytes = kmax * defer.per_tile() + 256;
-    }
-    size_t chunk_bytes = 0;
-    if (g.chunks > 1) chunk_bytes = (size_t)g.chunks * npx_all * (3 * sizeof(double) + sizeof(uint32_t));
-    const size_t chunk_bytes_al = (chunk_bytes + 255) & ~(size_t)255;
-    size_t scratch_need = chunk_bytes_al + sched_bytes + defer_bytes;
-    const auto halve_defer = [&] {  // fewer heavy tiles, same image
-        kmax /= 2;
-        defer_bytes = kmax ? kmax * defer.per_tile() + 256 : 0;
-        scratch_need = chunk_bytes_al + sched_bytes + defer_bytes;
-    };
-    // A size this device has refused before is not asked for again (every attempt is a synchronous hipFree plus failing
-    // hipMallocs): the deferred buffer shrinks until the need lies below it.
-    while (s->scratch_refused && scratch_need >= s->scratch_refused && kmax > 0) halve_defer();
-    if (scratch_need > 0 && s->scratch_bytes < scratch_need) {
-        if (s->scratch) (void)hipFree(s->scratch);
-        s->scratch = nullptr;
-        s->scratch_bytes = 0;
-        // a device short of memory gets a smaller deferred buffer before it gets an error
-        while (hipMalloc(&s->scratch, scratch_need) != hipSuccess) {
-            (void)hipGetLastError();
-            s->scratch = nullptr;
-            if (!s->scratch_refused || scratch_need < s->scratch_refused) s->scratch_refused = scratch_need;
-            if (kmax == 0) return fail(CGRT_ERR_DEVICE, "cannot allocate launch scratch (chunk sums / schedule / deferred Hitpoint values)");
-            halve_defer();
-        }
-        s->scratch_bytes = scratch_need;
-    }
-    if (g.chunks > 1) {
-        g.partial = reinterpret_cast<double *>(s->scratch);
-        g.partial_nhit = nhit ? reinterpret_cast<uint32_t *>(g.partial + (size_t)g.chunks * npx_all * 3) : nullptr;
-    }
-    if (reorder && kmax > 0) {
-        unsigned char *base = reinterpret_cast<unsigned char *>(s->scratch) + chunk_bytes_al;
-        uint32_t *sb = reinterpret_cast<uint32_t *>(base);
-        const size_t np = n_wt + sched_pad;
-        uint32_t *cost = sb, *order = sb + np;
-        int32_t *hidx = reinterpret_cast<int32_t *>(sb + 2 * np);
-        uint32_t *border = sb + 3 * np;
-        uint32_t *plan = sb + 4 * np;
-        unsigned char *light = reinterpret_cast<unsigned char *>(sb + 4 * np + 64);
-        const bool split_light = s->dev.light_ok != 0 && g.chunks == 1 && !L.k.stats;
-        if (split_light)
-            hipLaunchKernelGGL(classify_kernel, dim3((unsigned)((n_wt + 255) / 256)), dim3(256), 0, st, s->dev, g, light, (int)n_wt);
-        GridParams gp = g;  // the probe: this launch's first sample, natural order, one workgroup per tile, nothing stored
-        gp.spp = 1;
-        gp.chunks = 1;
-        gp.chunk_spp = 1;
-        gp.partial = nullptr;
-        gp.partial_nhit = nullptr;
-        gp.probe = 1;
-        gp.cost = cost;
-        gp.timeline = nullptr;
-        if (split_light) {  // light tiles are not probed (plan_kernel counts them as zero); their cost entries stay unwritten
-            gp.light = light;
-            gp.light_mode = 0;
-        }
-        if ((rc = launch_eye(L, false, s->device, gp, dim3((unsigned)tile_blocks), st, nullptr, nullptr, nullptr))) return rc;
-        if (split_light) {
-            // The light tiles: the variant without tree / Bezier / pending-ray code on the second stream, beside everything that
-            // follows here.  It needs nothing but the classification and starts as soon as the probe is through, beside the
-            // plan (one workgroup, 0.1-0.3 ms).  Started before the probe it perturbs the measured costs and delays the
-            // probe's workgroups: C3 14.4 -> 14.1 ms but C4 (spp 64) 33.6 -> 35.3 ms.
-            GridParams gl = g;
-            gl.light = light;
-            gl.light_mode = 1;
-            gl.timeline = nullptr;
-            gl.xcd_tiles = 0;
-            HIP_TRY(hipEventRecord(s->ev_fork, st));
-            HIP_TRY(hipStreamWaitEvent(s->aux_stream, s->ev_fork, 0));
-            if ((rc = launch_eye(light_launch(s->dev, L.k.dof, kn), false, s->device, gl,
-                                 dim3((unsigned)tile_grid_blocks(g.W, g.rows, false)), s->aux_stream, rgb, nhit, cnt)))
-                return rc;
-            HIP_TRY(hipEventRecord(s->ev_join, s->aux_stream));
-        }
-        // heavy: cost x spp > (total cost x spp / wave slots) / heavy_div
-        int n_cu = 256;
-        (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, s->device);
-        const int wave_slots = n_cu * 4 * (one_wave ? kBezWaves : (L.k.trees ? kSchedTreeWaves : 4));
-        // tiles through a queue too (GridParams::border) unless their samples are split over workgroups or the workgroups are
-        // single waves (trace_grid_sched_kernel)
-        const bool tile_queue = g.chunks == 1 && !one_wave && !kn.no_tile_queue;
-        hipLaunchKernelGGL(plan_kernel, dim3(1), dim3(1024), 0, st, cost, split_light ? light : nullptr, (int)n_wt, (unsigned)kmax,
-                           (unsigned long long)wave_slots * (unsigned long long)kn.heavy_div, plan, order, hidx,
-                           tile_queue ? border : nullptr, wtiles_x, wtiles_y, one_wave ? 1 : kTileW / kWaveTileW,
-                           one_wave ? 1 : kTileH / kWaveTileH);
-        if (split_light) g.light = light;
-        g.order = order;
-        g.hidx = hidx;
-        g.plan = plan;
-        defer.place(g, base + sched_bytes, kmax);
-        if (use_prim) {
-            g.prim_obj = s->dev.prim_obj;
-            g.prim_done = (s->dev.prim_finish && !kn.pw_no_finish) ? 1 : 0;
-        }
-        g.items_per_tile = (int)(((size_t)grid->spp * 64 + g.units_per_item - 1) / g.units_per_item);
-        // enough heavy workgroups to fill the chip once: they loop over the item queue until it is empty
-        size_t hb = (kmax * (size_t)g.items_per_tile + waves_per_block - 1) / waves_per_block;
-        const size_t fill = (size_t)wave_slots / waves_per_block;
-        if (hb > fill) hb = fill;
-        g.heavy_blocks = (int)hb;
-        if (tile_queue) {
-            g.border = border;
-            grid_dim = dim3((unsigned)fill);  // tile workgroups: a chip's worth, each loops over the tile queue
-        }
-    }
-    // development aid: CGRT_TIMELINE_FILE=path makes this launch synchronous and dumps, per workgroup, when and where it ran
+    const DeviceScene &d = s->dev;
+    const FrameInputs in{*grid, *cam, L.form == EyeForm::Sched, L.k.spill, L.k.stats, L.k.glass, L.k.nt, d.has_mesh != 0,
+                         d.has_bezier != 0, d.prim_finish != 0, d.light_ok != 0, d.prim_obj, kn, s->mem_total, s->n_cu,
+                         L.k.nt == 64 ? kBezWaves : (L.k.trees ? kSchedTreeWaves : 4)};
+    FramePlan p;
+    if ((rc = fit_scratch(s, in, p))) return rc;
+    GridParams g = frame_params(in, p);
+    unsigned char *scratch = reinterpret_cast<unsigned char *>(s->scratch.p);
+    if (p.heavy_blocks > 0 && (rc = probe_and_plan(s, L, kn, p, g, scratch, st, rgb, nhit, cnt))) return rc;
+    p.scratch.place(g, scratch, nhit != nullptr);
+    const size_t n_blocks = (size_t)p.heavy_blocks + p.grid_dim;
     DevBuf timeline;
     if (kn.timeline_file) {
-        HIP_TRY(timeline.alloc(((size_t)grid_dim.x + g.heavy_blocks) * 32));
-        HIP_TRY(hipMemsetAsync(timeline.p, 0, ((size_t)grid_dim.x + g.heavy_blocks) * 32, st));
+        HIP_TRY(timeline.alloc(n_blocks * 32));
+        HIP_TRY(hipMemsetAsync(timeline.p, 0, n_blocks * 32, st));
         g.timeline = timeline.as<unsigned long long>();
     }
-    if (g.heavy_blocks > 0) {  // heavy workgroups in front, the tile workgroups behind them, one launch
-        hipLaunchKernelGGL(pixel_const_kernel, dim3((unsigned)kmax), dim3(64), 0, st, g);
-        if (g.prim_len) {
-            // the heavy units' primary rays against the mesh, as a walk-only kernel with lane refill (cgrt_primwalk.hpp): a
-            // chip's worth of persistent workgroups at 4 waves per SIMD
-            int n_cu2 = 256;
-            (void)hipDeviceGetAttribute(&n_cu2, hipDeviceAttributeMultiprocessorCount, s->device);
-            PrimWalkArgs pw;
-            pw.len = const_cast<double *>(g.prim_len);
-            pw.tri = const_cast<int32_t *>(g.prim_tri);
-            pw.obj = s->dev.prim_obj;
-            pw.tree = s->host.objs[(size_t)s->dev.prim_obj].tree;
-            pw.finish = g.prim_done;
-            pw.pad_ = 0;
-            pw.counters = cnt;
-            const size_t staged = (size_t)(pw.finish ? s->dev.n_objs : pw.obj + 1);  // all objects when it finishes units
-            if ((rc = launch_checked(L.k.dof ? &primary_walk_kernel<true> : &primary_walk_kernel<false>, "primary_walk_kernel",
-                                     s->device, dim3((unsigned)n_cu2 * 4), dim3(kThreads), primary_walk_lds(staged), st, s->dev, g, pw)))
-                return rc;
-        }
-        if ((rc = launch_eye(L, true, s->device, g, dim3((unsigned)g.heavy_blocks + grid_dim.x), st, rgb, nhit, cnt))) return rc;
-    } else {
-        if ((rc = launch_eye(L, false, s->device, g, grid_dim, st, rgb, nhit, cnt))) return rc;
+    if (p.heavy_blocks > 0) {  // (3) heavy workgroups in front, the tile workgroups behind them, one launch
+        hipLaunchKernelGGL(pixel_const_kernel, dim3((unsigned)p.kmax), dim3(64), 0, st, g);
+        if (g.prim_len && (rc = primary_walk(s, L, g, st, cnt))) return rc;
+        if ((rc = launch_eye(L, true, s->device, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) return rc;
+    } else if ((rc = launch_eye(L, false, s->device, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) {
+        return rc;
     }
-    if (g.chunks > 1)
-        hipLaunchKernelGGL(finalize_chunks_kernel, dim3((unsigned)((npx_all + 255) / 256)), dim3(256), 0, st, g, rgb, nhit);
-    if (g.heavy_blocks > 0) hipLaunchKernelGGL(deferred_sum_kernel, dim3((unsigned)kmax), dim3(64), 0, st, g, rgb, nhit);
+    if (p.chunks > 1)
+        hipLaunchKernelGGL(finalize_chunks_kernel, dim3((unsigned)(((size_t)g.rows * g.W + 255) / 256)), dim3(256), 0, st, g, rgb, nhit);
+    if (p.heavy_blocks > 0) hipLaunchKernelGGL(deferred_sum_kernel, dim3((unsigned)p.kmax), dim3(64), 0, st, g, rgb, nhit);  // (4)
     if (g.light) HIP_TRY(hipStreamWaitEvent(st, s->ev_join, 0));  // the caller's stream continues when both launches are done
     const hipError_t launch_err = hipGetLastError();
-    if (g.timeline && launch_err == hipSuccess) {
-        std::vector<unsigned long long> tl(((size_t)grid_dim.x + g.heavy_blocks) * 4);
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(tl.data(), timeline.p, tl.size() * 8, hipMemcpyDeviceToHost));
-        if (FILE *f = std::fopen(kn.timeline_file, "wb")) {
-            const unsigned long long head[4] = {(unsigned long long)grid_dim.x + g.heavy_blocks, (unsigned long long)L.k.nt, (unsigned long long)g.chunks, (unsigned long long)g.xcd_tiles};
-            std::fwrite(head, 8, 4, f);
-            std::fwrite(tl.data(), 8, tl.size(), f);
-            std::fclose(f);
-        }
-    }
+    if (g.timeline && launch_err == hipSuccess && (rc = write_timeline(kn.timeline_file, timeline, n_blocks, p, L.k.nt, st))) return rc;
     if (launch_err != hipSuccess) return fail(CGRT_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(launch_err));
-    // development aid: CGRT_PLAN_DUMP=1 makes the launch synchronous and prints what the planner decided
-    if (kn.plan_dump && g.plan) {
-        uint32_t pl[8] = {0};
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(pl, g.plan, sizeof(pl), hipMemcpyDeviceToHost));
-        std::fprintf(stderr, "cgrt plan: wave tiles %zu, heavy %u (capacity %zu), cost threshold %u, tile-queue entries %u, items per tile %d, prim walk %s\n",
-                     n_wt, pl[0], kmax, pl[1], pl[3], g.items_per_tile, g.prim_len ? "on" : "off");
-    }
-    return CGRT_OK;
+    return kn.plan_dump && g.plan ? dump_plan(p, g, st) : CGRT_OK;
 }
 
 }  // extern "C"

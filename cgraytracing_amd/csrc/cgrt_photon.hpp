@@ -495,30 +495,12 @@ __global__ void image_keys_kernel(const double *__restrict__ hp, long long nhp, 
     vals[i] = (unsigned int)i;
 }
 
-// Grow-only scratch for the radix sorts: hipMalloc / hipFree per sort would drain the device (hipFree synchronises)
-// twice per photon batch.
-struct SortTemp {
-    DevBuf buf;
-    size_t cap = 0;
-    hipError_t need(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (buf.p) {
-            (void)hipFree(buf.p);
-            buf.p = nullptr;
-            cap = 0;
-        }
-        const hipError_t e = buf.alloc(bytes);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
-};
-
-int sort_pairs(SortTemp &tmp, unsigned long long *kin, unsigned long long *kout, unsigned int *vin, unsigned int *vout, size_t n,
+int sort_pairs(GrowBuf &tmp, unsigned long long *kin, unsigned long long *kout, unsigned int *vin, unsigned int *vout, size_t n,
                int end_bit = 64, hipStream_t st = 0) {
     size_t tmp_bytes = 0;
     HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, kin, kout, vin, vout, n, 0u, (unsigned)end_bit, st));
     HIP_TRY(tmp.need(tmp_bytes));
-    HIP_TRY(rocprim::radix_sort_pairs(tmp.buf.p, tmp_bytes, kin, kout, vin, vout, n, 0u, (unsigned)end_bit, st));
+    HIP_TRY(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, kin, kout, vin, vout, n, 0u, (unsigned)end_bit, st));
     return CGRT_OK;
 }
 
@@ -533,12 +515,12 @@ int launch_photon_trace(const cgrt_scene *s, const PhotonArgs &pa, double *event
                           photon_lds((size_t)d.n_lds, spill, bez, photon_lds_stack(d)), st, d, pa, events, valid);
 }
 
-int sort_pairs32(SortTemp &tmp, unsigned int *kin, unsigned int *kout, unsigned int *vin, unsigned int *vout, size_t n,
+int sort_pairs32(GrowBuf &tmp, unsigned int *kin, unsigned int *kout, unsigned int *vin, unsigned int *vout, size_t n,
                  hipStream_t st = 0) {
     size_t tmp_bytes = 0;
     HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, kin, kout, vin, vout, n, 0u, 32u, st));
     HIP_TRY(tmp.need(tmp_bytes));
-    HIP_TRY(rocprim::radix_sort_pairs(tmp.buf.p, tmp_bytes, kin, kout, vin, vout, n, 0u, 32u, st));
+    HIP_TRY(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, kin, kout, vin, vout, n, 0u, 32u, st));
     return CGRT_OK;
 }
 
@@ -549,7 +531,7 @@ struct PhotonProducer {
     hipEvent_t produced[2] = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr};
     bool used[2] = {false, false};
     DevBuf ev[2], valid[2], ek0[2], ek1[2], eo0[2], eo1[2];
-    SortTemp tmp;
+    GrowBuf tmp;
     ~PhotonProducer() {
         if (st) {
             (void)hipStreamSynchronize(st);
@@ -684,7 +666,7 @@ struct cgrt_ppm_session {
     DevBuf hp, hps, bstart, pix_start, order;  // table state and per-pixel index
     DevBuf pk0, pk1, pv0, pv1, npairs;          // (hitpoint, event) pairs of one batch
     DevBuf img, rgb8;                           // session: device image of cgrt_ppm_session_image (host outputs)
-    SortTemp main_tmp;
+    GrowBuf main_tmp;
     PhotonProducer pp;  // declared last of the buffers: its destructor waits for its stream before they are freed
     int64_t pp_bytes = 0;
     bool overlap = false;
