@@ -79,6 +79,20 @@ class BuildInfo(C.Structure):
 
 BUILD_HOST, BUILD_DEVICE = 0, 1
 
+
+class Rays(C.Structure):
+    _fields_ = [("n", C.c_int64), ("org3", C.c_void_p), ("dir3", C.c_void_p), ("keys", C.c_void_p),
+                ("first_index", C.c_int64), ("seed", C.c_uint64), ("max_depth", C.c_int32), ("flags", C.c_int32)]
+
+
+class RayResults(C.Structure):
+    _fields_ = [("acc3", C.c_void_p), ("nhit", C.c_void_p), ("hit_obj", C.c_void_p), ("hit_t", C.c_void_p),
+                ("hit_normal3", C.c_void_p)]
+
+
+RAYS_STATS = 1
+RAYS_NO_SIGN_PASS = 2
+
 # every symbol include/cgrt.h declares, with its signature
 _DP = C.POINTER(C.c_double)
 SIGNATURES = {
@@ -130,6 +144,11 @@ SIGNATURES = {
     "cgrt_lens_samples": (C.c_int, [C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
     "cgrt_surface_colors": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "cgrt_trace_grid_variant": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Grid), C.c_char_p, C.c_size_t]),
+    "cgrt_trace_rays": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(RayResults), C.c_void_p, C.c_void_p]),
+    "cgrt_trace_rays_host": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(RayResults), C.c_void_p]),
+    "cgrt_trace_rays_variant": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(RayResults), C.c_char_p, C.c_size_t]),
+    "cgrt_camera_rays": (C.c_int, [C.POINTER(Camera), C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cgrt_camera_rays_host": (C.c_int, [C.POINTER(Camera), C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cgrt_intersect_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
 }

@@ -32,7 +32,7 @@ static constexpr int kSchedTreeWaves = CGRT_SCHED_TREE_WAVES;  // ... the tree-c
 // uniform_sampling_circle (sampling.h:35-43) on a sample's lens stream (cgrt_rng.hpp): attempt j takes the two draws of the
 // splitmix output z_j = fin64(key + (j + 1) G) -- what Stream::pair returns at position 2j, with the 64-bit multiply of the
 // counter replaced by a running addition (the same integers mod 2^64).  Shared by every kernel that starts a primary ray.
-__device__ __forceinline__ void lens_disc(uint64_t k_smp, double &sx, double &sy) {
+__host__ __device__ __forceinline__ void lens_disc(uint64_t k_smp, double &sx, double &sy) {  // (host: cgrt_camera_rays_host)
     uint64_t ctr = k_smp;
     while (true) {
         ctr += kGolden;

@@ -21,7 +21,7 @@ static constexpr size_t kStackBytes = (size_t)kLdsLevels * kLevelBytes;
 static constexpr size_t kTileBytes = (size_t)8 * 32 * 3 * sizeof(float);
 
 // local row -> global row (cgrt.h: block-cyclic stripes)
-__device__ __forceinline__ int global_row(const GridParams &g, int j) {
+__host__ __device__ __forceinline__ int global_row(const GridParams &g, int j) {
     if (g.stripe_nranks > 1) {
         int S = g.stripe_rows;
         return ((j / S) * g.stripe_nranks + g.stripe_rank) * S + (j % S);

@@ -39,6 +39,7 @@
 #include "cgrt_scene_walk.hpp"
 #include "cgrt_eye.hpp"
 #include "cgrt_primwalk.hpp"
+#include "cgrt_rays.hpp"
 
 using namespace cgrt;
 
@@ -548,6 +549,28 @@ static constexpr size_t photon_lds(size_t resident, bool spill, bool bez, bool w
            (!bez && !spill && wide_stack ? kWideStackLds : 0);
 }
 
+// The template flags of a trace_rays_kernel instantiation (cgrt_rays.hpp)
+struct RayFlags {
+    bool trees, bez, glass, sph, stats, spill, first;
+    int nt;  // threads per workgroup: 256, or 64 (Bezier scenes: one BezLds per workgroup, as the eye pass's one-wave form)
+    constexpr int id() const {
+        return (int)trees | (int)bez << 1 | (int)glass << 2 | (int)sph << 3 | (int)stats << 4 | (int)spill << 5 | (int)first << 6 |
+               (nt == 64 ? 1 << 7 : 0);
+    }
+};
+// trace_rays_kernel: the carve-up of the eye pass (eye_lds) at the kernel's workgroup size -- pending-ray levels (GLASS) |
+// `resident` objects | one staging record per wave (SPILL) | one BezLds per wave (BEZ) | the cached tree (TREES) | the first
+// entries of the wide walk's stack (TREES without GLASS or BEZ, when the scene has a wide tree)
+static constexpr size_t rays_lds(const RayFlags &f, size_t resident, size_t cached_nodes, bool wide) {
+    const size_t waves = (size_t)f.nt / 64;
+    return (f.glass ? (size_t)kLdsLevels * f.nt * (kPendDoubles * sizeof(double) + sizeof(uint32_t)) : 0) +
+           (resident + (f.spill ? waves : 0)) * sizeof(ObjRec) + (f.bez ? waves * sizeof(BezLds) : 0) +
+           (f.trees ? cached_nodes * sizeof(NodeRec) : 0) + (f.trees && !f.glass && !f.bez && wide ? kWideStackLds : 0);
+}
+static size_t rays_lds(const RayFlags &f, const DeviceScene &d) {
+    return rays_lds(f, (size_t)d.n_lds, d.cached_tree >= 0 ? (size_t)d.cached_nodes : 0, d.has_wide != 0);
+}
+
 static constexpr bool fits_lds(size_t dyn) { return dyn + kStaticLdsAllowance <= kLdsBytes; }
 // Every launch that stages kLdsObjsMax objects fits beside its other LDS (the general variant lowers its count instead):
 // the eye pass without SPILL, with and without glass (the light variants are the latter), ...
@@ -561,6 +584,14 @@ static_assert(fits_lds(eye_lds(spill_sph_flags(false, true), kLdsObjsMax, 0, fal
 // ... primary_walk_kernel (all objects staged when it finishes units; it runs only when none is spilled), the photon launches
 static_assert(fits_lds(primary_walk_lds(kLdsObjsMax)), "primary_walk_kernel");
 static_assert(fits_lds(photon_lds(kLdsObjsMax, true, true, false)), "photon_trace_kernel");
+// ... and the ray-list launches: trees with and without pending rays, the one-wave Bezier form, the sphere loop with SPILL
+static_assert(fits_lds(rays_lds(RayFlags{true, false, true, false, false, false, false, kThreads}, kLdsObjsMax, kNodeCache, true)) &&
+                  fits_lds(rays_lds(RayFlags{true, false, false, false, false, false, false, kThreads}, kLdsObjsMax, kNodeCache, true)) &&
+                  fits_lds(rays_lds(RayFlags{true, true, true, false, false, false, false, 64}, kLdsObjsMax, kNodeCache, true)) &&
+                  fits_lds(rays_lds(RayFlags{false, false, true, true, false, true, false, kThreads}, kLdsObjsMax, 0, false)),
+              "trace_rays_kernel");
+static_assert(fits_lds(rays_lds(RayFlags{true, true, true, false, false, true, false, kThreads}, 600, kNodeCache, false)),
+              "trace_rays_kernel, general variant: resident objects");
 // The general variant keeps at least 600 objects resident whatever the scene.
 static_assert(fits_lds(eye_lds(general_flags(false, false, true), 600, kNodeCache, false)), "general variant: resident objects");
 
@@ -928,6 +959,239 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     if (g.timeline && launch_err == hipSuccess && (rc = write_timeline(kn.timeline_file, timeline, n_blocks, p, L.k.nt, st))) return rc;
     if (launch_err != hipSuccess) return fail(CGRT_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(launch_err));
     return kn.plan_dump && g.plan ? dump_plan(p, g, st) : CGRT_OK;
+}
+
+}  // extern "C"
+
+
+// =====================================================================================================
+// caller-supplied rays (cgrt_rays.hpp)
+// =====================================================================================================
+// The instantiations of trace_rays_kernel that are launched (rays_launch below) -- only these are compiled.
+using RaysKernel = void (*)(DeviceScene, RayParams, unsigned long long *);
+struct RaysKernels {
+    int id;  // RayFlags::id()
+    RaysKernel fn;
+};
+template <int T, int B, int G, int P, int S, int SP, int F, int NT = kThreads>
+static constexpr RaysKernels rk() {
+    return {RayFlags{T != 0, B != 0, G != 0, P != 0, S != 0, SP != 0, F != 0, NT}.id(),
+            &trace_rays_kernel<T != 0, B != 0, G != 0, P != 0, S != 0, SP != 0, F != 0, NT>};
+}
+//                          TREES BEZ GLASS SPH STATS SPILL FIRST [NT]
+static const RaysKernels kRaysKernels[] = {
+    // the full trace: Bezier scenes (one-wave workgroups), meshes / bump floors (with and without STATS), spheres, plain scenes
+    rk<1, 1, 0, 0, 0, 0, 0, 64>(), rk<1, 1, 1, 0, 0, 0, 0, 64>(),
+    rk<1, 0, 0, 0, 0, 0, 0>(), rk<1, 0, 1, 0, 0, 0, 0>(), rk<1, 0, 0, 0, 1, 0, 0>(), rk<1, 0, 1, 0, 1, 0, 0>(),
+    rk<0, 0, 0, 1, 0, 0, 0>(), rk<0, 0, 1, 1, 0, 0, 0>(), rk<0, 0, 0, 0, 0, 0, 0>(), rk<0, 0, 1, 0, 0, 0, 0>(),
+    // SPILL: spheres, and the general body
+    rk<0, 0, 0, 1, 0, 1, 0>(), rk<0, 0, 1, 1, 0, 1, 0>(), rk<1, 1, 1, 0, 0, 1, 0>(),
+    // the nearest-hit query: no GLASS variants
+    rk<1, 1, 0, 0, 0, 0, 1, 64>(), rk<1, 0, 0, 0, 0, 0, 1>(), rk<1, 0, 0, 0, 1, 0, 1>(), rk<0, 0, 0, 1, 0, 0, 1>(),
+    rk<0, 0, 0, 0, 0, 0, 1>(), rk<0, 0, 0, 1, 0, 1, 1>(), rk<1, 1, 0, 0, 0, 1, 1>(),
+};
+static const RaysKernels *rays_kernels(const RayFlags &f) {
+    for (const RaysKernels &e : kRaysKernels)
+        if (e.id == f.id()) return &e;
+    return nullptr;
+}
+
+// One launch of trace_rays_kernel: the flags chosen from the scene's traits the way eye_launch chooses the eye pass's
+struct RaysLaunch {
+    RayFlags k;
+    DeviceScene dev;  // the general variant's copy holds its resident objects (with_resident)
+    size_t lds;
+    const char *what() const {
+        return k.spill ? (k.sph ? "ray list, SPILL (spheres)" : "ray list, SPILL (general)") : (k.bez ? "ray list (Bezier)" : "ray list");
+    }
+};
+static RaysLaunch rays_launch(const cgrt_scene *s, int max_depth, bool stats, bool first) {
+    const DeviceScene &d = s->dev;
+    const bool glass = !first && d.has_glass != 0 && max_depth > 1;
+    const bool spill = d.n_objs > d.n_lds;
+    RaysLaunch L;
+    L.dev = d;
+    if (spill && !d.all_spheres) {
+        // the most general body, with as many objects resident as fit beside its other LDS; the rest are read from `objs`
+        L.k = RayFlags{true, true, !first, false, false, true, first, kThreads};
+        const RaysKernels *e = rays_kernels(L.k);
+        const size_t st = e ? kernel_static_lds(reinterpret_cast<const void *>(e->fn)) : kStaticLdsAllowance;
+        const size_t lim = device_lds_bytes(s->device);
+        if (rays_lds(L.k, d) + st > lim) {
+            const long long room = (long long)lim - (long long)(st + rays_lds(L.k, with_resident(d, 0)));
+            L.dev = with_resident(d, (int)std::max(0ll, std::min(room / (long long)sizeof(ObjRec), (long long)d.n_lds)));
+        }
+    } else if (spill) {
+        L.k = RayFlags{false, false, glass, true, false, true, first, kThreads};
+    } else {
+        const bool bez = d.has_bezier != 0, trees = d.has_mesh != 0 || bez;
+        L.k = RayFlags{trees, bez, glass, !trees && d.all_spheres != 0, stats && d.has_mesh != 0 && !bez, false, first, bez ? 64 : kThreads};
+    }
+    L.lds = rays_lds(L.k, L.dev);
+    return L;
+}
+
+static constexpr long long kMaxRays = 1ll << 36;  // blocks of 64 rays are numbered in 32 bits with room for the waves' last draws
+
+static int check_rays(const cgrt_scene *s, const cgrt_rays *r, const cgrt_ray_results *out) {
+    if (!s || !r || !out) return fail(CGRT_ERR_INVALID, "null argument");
+    if (r->n < 0) return fail(CGRT_ERR_INVALID, "negative ray count");
+    if (r->n > 0 && (!r->org3 || !r->dir3)) return fail(CGRT_ERR_INVALID, "null org3 / dir3");
+    if ((out->acc3 || out->nhit) && (r->max_depth < 1 || r->max_depth > kMaxDepth)) return fail(CGRT_ERR_INVALID, "max_depth must be 1..5");
+    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+    if (r->n > kMaxRays) return fail(CGRT_ERR_LIMIT, "more than 2^36 rays in one call");
+    return CGRT_OK;
+}
+// The rows / stripes / samples of a grid that cgrt_camera_rays reads (max_depth, spp_total and flags are not looked at)
+static int check_camera_rays(const cgrt_camera *cam, const cgrt_grid *g) {
+    if (!cam || !g) return fail(CGRT_ERR_INVALID, "null argument");
+    if (g->width <= 0 || g->height <= 0 || g->rows <= 0) return fail(CGRT_ERR_INVALID, "empty grid");
+    if (g->spp <= 0 || g->sample_offset < 0) return fail(CGRT_ERR_INVALID, "bad sample range");
+    if (g->stripe_nranks > 1) {
+        if (g->stripe_rows <= 0 || g->stripe_rows % kTileH != 0)
+            return fail(CGRT_ERR_INVALID, "stripe_rows must be a positive multiple of 8");
+        if (g->stripe_rank < 0 || g->stripe_rank >= g->stripe_nranks) return fail(CGRT_ERR_INVALID, "bad stripe_rank");
+    } else if (g->row_offset < 0) {
+        return fail(CGRT_ERR_INVALID, "bad row_offset");
+    }
+    if (!(cam->lens_radius >= 0)) return fail(CGRT_ERR_INVALID, "lens_radius must be >= 0");
+    if ((long long)g->spp * g->rows > (1ll << 38) / g->width) return fail(CGRT_ERR_LIMIT, "more than 2^38 camera rays in one call");
+    return CGRT_OK;
+}
+
+extern "C" {
+
+int cgrt_trace_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_results *out, uint64_t *counters, void *stream) {
+    int rc = check_rays(s, rays, out);
+    if (rc) return rc;
+    if (rays->n == 0) return CGRT_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    ON_DEVICE(s->device);
+    const bool first = !out->acc3 && !out->nhit;  // nearest-hit query: one scene walk per ray
+    const RaysLaunch L = rays_launch(s, rays->max_depth, (rays->flags & CGRT_RAYS_STATS) != 0, first);
+    const RaysKernels *e = rays_kernels(L.k);
+    if (!e) return fail(CGRT_ERR_UNSUPPORTED, std::string(L.what()) + ": no kernel built for this variant");
+    // the queue's head lives in the handle's launch scratch (launches on one handle are ordered by the caller)
+    // (and, where the normals' signs are recounted below without the caller asking for hit_obj, the winners)
+    const bool sign_pass = out->hit_normal3 && L.dev.has_wide && !(rays->flags & CGRT_RAYS_NO_SIGN_PASS);
+    const size_t own_obj = sign_pass && !out->hit_obj ? (size_t)rays->n * sizeof(int32_t) : 0;
+    if (s->scratch.need(256 + own_obj) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(CGRT_ERR_DEVICE, "cannot allocate launch scratch (ray queue)");
+    }
+    HIP_TRY(hipMemsetAsync(s->scratch.p, 0, sizeof(unsigned int), st));
+    RayParams rp{};
+    rp.n = rays->n;
+    rp.org = rays->org3;
+    rp.dir = rays->dir3;
+    rp.keys = reinterpret_cast<const unsigned long long *>(rays->keys);
+    rp.first_index = rays->first_index;
+    rp.seed = rays->seed;
+    rp.max_depth = rays->max_depth;
+    rp.acc = out->acc3;
+    rp.nhit = out->nhit;
+    rp.hit_obj = own_obj ? reinterpret_cast<int32_t *>(reinterpret_cast<unsigned char *>(s->scratch.p) + 256) : out->hit_obj;
+    rp.hit_t = out->hit_t;
+    rp.hit_normal = out->hit_normal3;
+    rp.queue = reinterpret_cast<unsigned int *>(s->scratch.p);
+    // persistent workgroups: at most two chips' worth at the kernel's occupancy, fewer when the rays are few
+    const long long waves_per_wg = L.k.nt / 64, n_blocks = (rays->n + 63) / 64;
+    const long long chip = (long long)s->n_cu * 4 * (L.k.bez ? kBezWaves : (L.k.trees ? kTreeWaves : 4)) / waves_per_wg;
+    const long long wgs = std::max(1ll, std::min((n_blocks + waves_per_wg - 1) / waves_per_wg, 2 * chip));
+    if ((rc = launch_checked(e->fn, L.what(), s->device, dim3((unsigned)wgs), dim3((unsigned)L.k.nt), L.lds, st, L.dev, rp,
+                             reinterpret_cast<unsigned long long *>(counters))))
+        return rc;
+    // an opaque mesh's normal gets the reference's sign (ray_normal_sign_kernel)
+    if (sign_pass) hipLaunchKernelGGL(ray_normal_sign_kernel, dim3((unsigned)((rays->n + 255) / 256)), dim3(256), 0, st, L.dev, rp);
+    HIP_TRY(hipGetLastError());
+    return CGRT_OK;
+}
+
+int cgrt_trace_rays_variant(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_results *out, char *name, size_t cap) {
+    if (!s || !rays || !out || !name || cap == 0) return fail(CGRT_ERR_INVALID, "null argument");
+    const bool first = !out->acc3 && !out->nhit;
+    if (!first && (rays->max_depth < 1 || rays->max_depth > kMaxDepth)) return fail(CGRT_ERR_INVALID, "max_depth must be 1..5");
+    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+    ON_DEVICE(s->device);
+    const RayFlags k = rays_launch(s, rays->max_depth, (rays->flags & CGRT_RAYS_STATS) != 0, first).k;
+    std::snprintf(name, cap, "trace_rays_kernel<TREES=%d,BEZ=%d,GLASS=%d,SPH=%d,STATS=%d,SPILL=%d,FIRST=%d,NT=%d>", (int)k.trees, (int)k.bez,
+                  (int)k.glass, (int)k.sph, (int)k.stats, (int)k.spill, (int)k.first, k.nt);
+    return CGRT_OK;
+}
+
+int cgrt_trace_rays_host(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_results *out, uint64_t *counters) {
+    int rc = check_rays(s, rays, out);
+    if (rc) return rc;
+    const size_t n = (size_t)rays->n;
+    if (n == 0) {
+        if (counters) std::memset(counters, 0, CGRT_NCOUNTERS * sizeof(uint64_t));
+        return CGRT_OK;
+    }
+    ON_DEVICE(s->device);
+    DevBuf b_o, b_d, b_k, b_acc, b_nhit, b_obj, b_t, b_n, b_cnt;
+    cgrt_rays dr = *rays;
+    cgrt_ray_results dout{};
+    HIP_TRY(b_o.alloc(n * 24));
+    HIP_TRY(b_d.alloc(n * 24));
+    HIP_TRY(hipMemcpy(b_o.p, rays->org3, n * 24, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_d.p, rays->dir3, n * 24, hipMemcpyHostToDevice));
+    dr.org3 = b_o.as<double>();
+    dr.dir3 = b_d.as<double>();
+    if (rays->keys) {
+        HIP_TRY(b_k.alloc(n * 8));
+        HIP_TRY(hipMemcpy(b_k.p, rays->keys, n * 8, hipMemcpyHostToDevice));
+        dr.keys = b_k.as<uint64_t>();
+    }
+    if (out->acc3) { HIP_TRY(b_acc.alloc(n * 24)); dout.acc3 = b_acc.as<double>(); }
+    if (out->nhit) { HIP_TRY(b_nhit.alloc(n * 4)); dout.nhit = b_nhit.as<uint32_t>(); }
+    if (out->hit_obj) { HIP_TRY(b_obj.alloc(n * 4)); dout.hit_obj = b_obj.as<int32_t>(); }
+    if (out->hit_t) { HIP_TRY(b_t.alloc(n * 8)); dout.hit_t = b_t.as<double>(); }
+    if (out->hit_normal3) { HIP_TRY(b_n.alloc(n * 24)); dout.hit_normal3 = b_n.as<double>(); }
+    HIP_TRY(b_cnt.alloc(CGRT_NCOUNTERS * sizeof(uint64_t)));
+    HIP_TRY(hipMemset(b_cnt.p, 0, CGRT_NCOUNTERS * sizeof(uint64_t)));
+    rc = cgrt_trace_rays(s, &dr, &dout, b_cnt.as<uint64_t>(), nullptr);
+    if (rc == CGRT_OK) {
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess) rc = fail(CGRT_ERR_DEVICE, std::string("kernel: ") + hipGetErrorString(e));
+    }
+    if (rc == CGRT_OK) {
+        if (out->acc3) HIP_TRY(hipMemcpy(out->acc3, b_acc.p, n * 24, hipMemcpyDeviceToHost));
+        if (out->nhit) HIP_TRY(hipMemcpy(out->nhit, b_nhit.p, n * 4, hipMemcpyDeviceToHost));
+        if (out->hit_obj) HIP_TRY(hipMemcpy(out->hit_obj, b_obj.p, n * 4, hipMemcpyDeviceToHost));
+        if (out->hit_t) HIP_TRY(hipMemcpy(out->hit_t, b_t.p, n * 8, hipMemcpyDeviceToHost));
+        if (out->hit_normal3) HIP_TRY(hipMemcpy(out->hit_normal3, b_n.p, n * 24, hipMemcpyDeviceToHost));
+        if (counters) HIP_TRY(hipMemcpy(counters, b_cnt.p, CGRT_NCOUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    return rc;
+}
+
+int cgrt_camera_rays(const cgrt_camera *cam, const cgrt_grid *grid, double *org3, double *dir3, uint64_t *keys, void *stream) {
+    int rc = check_camera_rays(cam, grid);
+    if (rc) return rc;
+    const GridParams g = grid_params(cam, grid);
+    const long long total = (long long)grid->spp * grid->rows * grid->width;
+    hipLaunchKernelGGL(camera_rays_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), g,
+                       org3, dir3, reinterpret_cast<unsigned long long *>(keys), total);
+    HIP_TRY(hipGetLastError());
+    return CGRT_OK;
+}
+
+int cgrt_camera_rays_host(const cgrt_camera *cam, const cgrt_grid *grid, double *org3, double *dir3, uint64_t *keys) {
+    int rc = check_camera_rays(cam, grid);
+    if (rc) return rc;
+    const GridParams g = grid_params(cam, grid);
+    size_t i = 0;
+    for (int k = 0; k < grid->spp; k++)
+        for (int j = 0; j < grid->rows; j++)
+            for (int w = 0; w < grid->width; w++, i++) {
+                const CameraRay c = camera_ray(g, j, w, g.sample_offset + k);
+                for (int a = 0; a < 3; a++) {
+                    if (org3) org3[3 * i + a] = c.o[a];
+                    if (dir3) dir3[3 * i + a] = c.d[a];
+                }
+                if (keys) keys[i] = c.key;
+            }
+    return CGRT_OK;
 }
 
 }  // extern "C"

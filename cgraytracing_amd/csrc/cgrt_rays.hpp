@@ -1,0 +1,466 @@
+// Caller-supplied rays: trace_rays_kernel (cgrt_trace_rays) and camera_rays_kernel (cgrt_camera_rays).  Part of libcgrt.so
+// (cgrt_hip.hip).  The work items are rays from a buffer; nothing of the eye pass's tile geometry is used.
+#ifndef CGRT_RAYS_HPP
+#define CGRT_RAYS_HPP
+#include "cgrt_eye.hpp"
+
+// Kernel arguments of trace_rays_kernel (cgrt_rays / cgrt_ray_results of cgrt.h; every output pointer may be nullptr)
+struct RayParams {
+    long long n;
+    const double *org, *dir;
+    const unsigned long long *keys;  // nullptr: sample_key(pixel_key(seed, first_index + i), 0)
+    long long first_index;
+    uint64_t seed;
+    int32_t max_depth, pad_;
+    double *acc;
+    uint32_t *nhit;
+    int32_t *hit_obj;
+    double *hit_t, *hit_normal;
+    unsigned int *queue;  // head of the block queue (block = 64 consecutive rays), zeroed before the launch
+};
+
+// One step of trace() behind the scene walk (main.cpp:64-157) for a ray that hit object hit.id: the expressions of
+// trace_grid_body (cgrt_eye.hpp), in its order -- that order is the parity contract (fp64, no contraction, sqrt_cr,
+// normalized).  trace_grid_body keeps its own copy (DESIGN.md section 4.17 names the tests that pin each).
+struct RayState {
+    V3 o, d, adj;
+    int32_t depth_left;
+    uint32_t path;
+};
+enum RayStep {
+    RAY_END = 0,      // absorbed: a mirror or glass hit at the depth limit (main.cpp:46)
+    RAY_HITPOINT = 1, // diffuse: `hf` is the Hitpoint's f * adj (main.cpp:88); the ray ends
+    RAY_CONTINUE = 2, // `r` is the reflected child
+    RAY_SPLIT = 3     // `r` is the reflected child and `pe` the refracted one, to be traced after r's subtree
+};
+template <bool GLASS, bool SPILL>
+__device__ __forceinline__ RayStep shade_step(const DeviceScene &sc, const ObjRec *__restrict__ lobjs, const SceneHit &hit,
+                                              RayState &r, V3 &hf, Pending &pe) {
+    const ObjMat ob = load_mat<SPILL>(lobjs, sc.n_lds, sc.objs, hit.id);
+    const V3 o = r.o, d = r.d;
+    const V3 P = o + d * hit.t;  // main.cpp:68
+    V3 n = hit.n;
+    const V3 n_old = n;
+    bool into = true;
+    if (dot(n, d) > 0) {  // main.cpp:73-76
+        n = -n;
+        into = false;
+    }
+    V3 f = ob.col;  // getSurfaceColor
+    if (ob.kind == KIND_PLANE && ob.tex >= 0) {
+        V3 c;
+        if (texture_color(sc.texs[ob.tex], sc.texels, P, c)) f = c;  // objects.h:533-539
+    }
+    const double refl = ob.refl, transp = ob.transp;
+    if (refl < kEps && transp < kEps) {
+        hf = mulv(f, r.adj);  // main.cpp:85-100
+        return RAY_HITPOINT;
+    }
+    if (!(r.depth_left > 1)) return RAY_END;
+    if (transp < kEps) {
+        // mirror, main.cpp:129-134
+        const V3 nd = d - n * 2.0 * dot(n, d);
+        r.adj = mulv(f, r.adj) * refl;
+        r.o = P + n * kEps;
+        r.d = nd;
+        r.depth_left--;
+        r.path = r.path * 2;
+        return RAY_CONTINUE;
+    }
+    if (!GLASS) return RAY_END;  // (not instantiated for scenes with a transparent object at max_depth > 1)
+    // glass, main.cpp:135-157
+    RayStep step = RAY_CONTINUE;
+    const double nc = 1.0, nt = 1.33;
+    const double nnt = into ? nc / nt : nt / nc;
+    const double ddn = dot(d, n);
+    const V3 refl_dir = d - n_old * 2.0 * dot(n_old, d);
+    const double cos2t = 1 - nnt * nnt * (1 - ddn * ddn);
+    if (cos2t < 0) {
+        // total internal reflection keeps adj (main.cpp:144)
+        r.o = P + n * kEps;
+        r.d = refl_dir;
+    } else {
+        const V3 refr_dir = normalized(d * nnt - n_old * ((into ? 1 : -1) * (ddn * nnt + sqrt_cr(cos2t))));
+        const double a = nt - nc, b = nt + nc, R0 = a * a / (b * b);
+        const double c = 1 - (into ? -ddn : dot(refr_dir, n_old));
+        const double Re = R0 + (1 - R0) * c * c * c * c * c;
+        const V3 fa = mulv(f, r.adj);
+        pe.o = P - n * kEps;
+        pe.d = refr_dir;
+        pe.adj = fa * (1 - Re);
+        pe.depth_left = r.depth_left - 1;
+        pe.path = r.path * 2 + 1;
+        r.o = P + n * kEps;
+        r.d = refl_dir;
+        r.adj = fa * Re;
+        step = RAY_SPLIT;
+    }
+    r.depth_left--;
+    r.path = r.path * 2;
+    return step;
+}
+
+// Persistent workgroups of NT threads.  A wave draws blocks of 64 consecutive rays from one queue counter (lane 0's atomic, the
+// next block's already in flight while the current one is traced); a lane whose ray tree is finished stores that ray's results
+// and takes the next ray of the wave's block at once, and the wave moves on to its next block while other lanes still finish
+// rays of the old one: lanes idle only when the queue is empty.  A ray's Hitpoint values are added in the lane in emission
+// order (reflect subtree, then refract), so its result does not depend on which lane or wave traced it, nor on what the other
+// lanes were doing.
+// FIRST: nearest-hit query -- one scene walk per ray, no shading, no pending-ray code.
+// LDS carve-up as trace_grid_body's: [ pending-ray levels (GLASS) | objs | staging record per wave (SPILL) | BezLds per wave (BEZ)
+// | node cache (TREES) | wide-walk stack (TREES without GLASS or BEZ) ]; rays_lds() in cgrt_hip.hip is its size.
+template <bool TREES, bool BEZ, bool GLASS, bool SPH, bool STATS, bool SPILL, bool FIRST, int NT>
+__global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) void trace_rays_kernel(DeviceScene sc, RayParams rp,
+                                                                                               unsigned long long *__restrict__ counters) {
+    static_assert(NT == 256 || NT == 64, "workgroup = 4 waves or 1 wave");
+    static_assert(!(FIRST && GLASS), "a nearest-hit query has no pending rays");
+    constexpr size_t level_bytes = (size_t)NT * (kPendDoubles * sizeof(double) + sizeof(uint32_t));
+    constexpr size_t stack_bytes = (size_t)kLdsLevels * level_bytes;
+    __shared__ unsigned long long wg_cnt[CGRT_NCOUNTERS];
+    unsigned long long *wc = wg_counters_begin(wg_cnt, counters);
+
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    ObjRec *lobjs = reinterpret_cast<ObjRec *>(lds_raw + (GLASS ? stack_bytes : 0));
+    unsigned char *lrest = reinterpret_cast<unsigned char *>(lobjs + sc.n_lds);
+    LdsAux aux;
+    if (SPILL) {
+        aux.spill = reinterpret_cast<ObjRec *>(lrest) + (threadIdx.x >> 6);
+        lrest += (NT / 64) * sizeof(ObjRec);
+    }
+    aux.bl = BEZ ? reinterpret_cast<volatile BezLds *>(lrest) + (threadIdx.x >> 6) : nullptr;
+    if (BEZ) lrest += (NT / 64) * sizeof(BezLds);
+    NodeRec *lnodes = reinterpret_cast<NodeRec *>(lrest);
+    aux.lnodes = (TREES && sc.cached_tree >= 0) ? lnodes : nullptr;
+    aux.wstack = (TREES && !GLASS && !BEZ && sc.has_wide)
+                     ? reinterpret_cast<uint2 *>(lrest + ((sc.cached_tree >= 0 ? (size_t)sc.cached_nodes * sizeof(NodeRec) : 0)))
+                     : nullptr;
+    if (TREES && sc.cached_tree >= 0) {
+        const uint4 *src = reinterpret_cast<const uint4 *>(sc.nodes + sc.trees[sc.cached_tree].node_begin);
+        uint4 *dst = reinterpret_cast<uint4 *>(lnodes);
+        const int n16 = sc.cached_nodes * (int)(sizeof(NodeRec) / 16);
+        for (int k = threadIdx.x; k < n16; k += NT) dst[k] = src[k];
+    }
+    {
+        const uint4 *src = reinterpret_cast<const uint4 *>(sc.objs);
+        uint4 *dst = reinterpret_cast<uint4 *>(lobjs);
+        const int n16 = sc.n_lds * (int)(sizeof(ObjRec) / 16);
+        for (int k = threadIdx.x; k < n16; k += NT) dst[k] = src[k];
+    }
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63;
+    const unsigned long long lanes_below = (1ull << lane) - 1ull;
+    const unsigned n_blocks = (unsigned)((rp.n + 63) >> 6);
+
+    // the wave's block: rays [ray_next, ray_end) are still to be handed out (wave-uniform)
+    long long ray_next = 0, ray_end = 0;
+    bool queue_empty = false;
+    unsigned block_ahead = 0;
+    if (lane == 0) block_ahead = atomicAdd(rp.queue, 1u);
+
+    // the lane's ray tree
+    long long my_ray = 0;  // index of the ray whose tree this lane is tracing
+    bool open = false;     // its sums are still to be stored
+    bool primary = false;  // the next walk is the ray's own: it supplies hit_obj / hit_t / hit_normal
+    bool have = false;
+    uint64_t key = 0;
+    RayState r;
+    r.o = mk(0, 0, 0);
+    r.d = mk(0, 0, 1);
+    r.adj = mk(1, 1, 1);
+    r.depth_left = 0;
+    r.path = 1;
+    double acc_r = 0, acc_g = 0, acc_b = 0;
+    uint32_t ray_hits = 0;
+    uint32_t my_hits = 0, my_rays = 0, my_nodes = 0, my_tris = 0, wave_iters = 0;
+
+    Pending deep[2];  // third stack level (scratch)
+    Pending sib;      // refracted sibling of a leaf-level glass hit (registers)
+    bool sib_valid = false;
+    unsigned char *lslot = lds_raw;  // level L, field f of this thread: lslot + L*level_bytes + (f*NT + tid)*8
+    int sp = 0;
+
+    while (true) {
+        const bool want = !have;
+        const unsigned long long m = __ballot(want);
+        if (m != 0ull) {
+            if (!FIRST && want && open) {  // the finished ray's sums
+                if (rp.acc) {
+                    double *q = rp.acc + 3 * my_ray;
+                    q[0] = acc_r;
+                    q[1] = acc_g;
+                    q[2] = acc_b;
+                }
+                if (rp.nhit) rp.nhit[my_ray] = ray_hits;
+                open = false;
+            }
+            if (ray_next >= ray_end && !queue_empty) {
+                // the block fetched ahead, and the request for the one after it
+                const unsigned blk = (unsigned)__builtin_amdgcn_readfirstlane((int)block_ahead);
+                if (lane == 0) block_ahead = atomicAdd(rp.queue, 1u);
+                if (blk >= n_blocks) {
+                    queue_empty = true;
+                } else {
+                    ray_next = (long long)blk << 6;
+                    ray_end = ray_next + 64 < rp.n ? ray_next + 64 : rp.n;
+                }
+            }
+            const long long u = ray_next + (long long)__popcll(m & lanes_below);
+            ray_next += (long long)__popcll(m);  // lanes that drew beyond ray_end draw again from the next block
+            if (want && u < ray_end) {
+                r.o = ld3(rp.org + 3 * u);
+                r.d = ld3(rp.dir + 3 * u);
+                if (r.d.x == 0.0 && r.d.y == 0.0 && r.d.z == 0.0) {
+                    // not a ray (cgrt_camera_rays' padding rows): the results of a miss, nothing counted
+                    if (!FIRST && rp.acc) {
+                        double *q = rp.acc + 3 * u;
+                        q[0] = 0.0;
+                        q[1] = 0.0;
+                        q[2] = 0.0;
+                    }
+                    if (!FIRST && rp.nhit) rp.nhit[u] = 0u;
+                    if (rp.hit_obj) rp.hit_obj[u] = -1;
+                    if (rp.hit_t) rp.hit_t[u] = 0.0;
+                    if (rp.hit_normal) {
+                        double *q = rp.hit_normal + 3 * u;
+                        q[0] = 0.0;
+                        q[1] = 0.0;
+                        q[2] = 0.0;
+                    }
+                } else {
+                    my_ray = u;
+                    key = rp.keys ? (uint64_t)rp.keys[u] : sample_key(pixel_key(rp.seed, (uint64_t)(rp.first_index + u)), 0);
+                    r.adj = mk(1, 1, 1);
+                    r.depth_left = rp.max_depth;
+                    r.path = 1;
+                    acc_r = acc_g = acc_b = 0;
+                    ray_hits = 0;
+                    primary = true;
+                    open = true;
+                    have = true;
+                }
+            }
+        }
+        if (__ballot(have) == 0ull) {
+            if (queue_empty && ray_next >= ray_end) break;  // nothing left anywhere
+            continue;                                       // drew nothing traceable (block boundary, padding rays)
+        }
+        wave_iters++;
+        // All 64 lanes enter the scene walk together (lanes without a ray carry on == false)
+        RayKey rk{key, r.path, false, 0u};
+        const SceneHit hit = intersect_scene<TREES, BEZ, SPH, STATS, SPILL, /*PRE*/ false, /*HFONLY*/ false>(
+            lobjs, sc.n_lds, sc.n_objs, sc, r.o, r.d, rk, have, aux, my_nodes, my_tris);
+        if (have) {
+            my_rays++;
+            have = false;
+            if (FIRST || primary) {
+                primary = false;
+                const bool is_hit = hit.id >= 0;
+                if (rp.hit_obj) rp.hit_obj[my_ray] = is_hit ? hit.id : -1;
+                if (rp.hit_t) rp.hit_t[my_ray] = is_hit ? hit.t : 0.0;
+                if (rp.hit_normal) {
+                    double *q = rp.hit_normal + 3 * my_ray;
+                    q[0] = is_hit ? hit.n.x : 0.0;
+                    q[1] = is_hit ? hit.n.y : 0.0;
+                    q[2] = is_hit ? hit.n.z : 0.0;
+                }
+            }
+            if (!FIRST) {
+                if (hit.id >= 0) {
+                    V3 hf;
+                    Pending pe;
+                    const RayStep step = shade_step<GLASS, SPILL>(sc, lobjs, hit, r, hf, pe);
+                    if (step == RAY_HITPOINT) {
+                        acc_r += hf.x;
+                        acc_g += hf.y;
+                        acc_b += hf.z;
+                        ray_hits++;
+                        my_hits++;
+                    } else if (step != RAY_END) {
+                        have = true;
+                        if (GLASS && step == RAY_SPLIT) {
+                            if (pe.depth_left == 1) {  // the children are leaves of the recursion: consumed right after the reflected one
+                                sib = pe;
+                                sib_valid = true;
+                            } else {
+                                if (sp < kLdsLevels) {
+                                    double *q = reinterpret_cast<double *>(lslot + sp * level_bytes) + threadIdx.x;
+                                    q[0 * NT] = pe.o.x; q[1 * NT] = pe.o.y; q[2 * NT] = pe.o.z;
+                                    q[3 * NT] = pe.d.x; q[4 * NT] = pe.d.y; q[5 * NT] = pe.d.z;
+                                    q[6 * NT] = pe.adj.x; q[7 * NT] = pe.adj.y; q[8 * NT] = pe.adj.z;
+                                    // depth_left <= 4 and path < 32: one word
+                                    reinterpret_cast<uint32_t *>(lslot + sp * level_bytes + kPendDoubles * NT * sizeof(double))[threadIdx.x] =
+                                        ((uint32_t)pe.depth_left << 8) | pe.path;
+                                } else {
+                                    deep[sp - kLdsLevels] = pe;
+                                }
+                                sp++;
+                            }
+                        }
+                    }
+                }
+                if (GLASS && !have && sib_valid) {
+                    r.o = sib.o;
+                    r.d = sib.d;
+                    r.adj = sib.adj;
+                    r.depth_left = sib.depth_left;
+                    r.path = sib.path;
+                    sib_valid = false;
+                    have = true;
+                }
+                if (GLASS && !have && sp > 0) {
+                    --sp;
+                    if (sp < kLdsLevels) {
+                        const double *q = reinterpret_cast<const double *>(lslot + sp * level_bytes) + threadIdx.x;
+                        r.o = mk(q[0 * NT], q[1 * NT], q[2 * NT]);
+                        r.d = mk(q[3 * NT], q[4 * NT], q[5 * NT]);
+                        r.adj = mk(q[6 * NT], q[7 * NT], q[8 * NT]);
+                        const uint32_t meta =
+                            reinterpret_cast<const uint32_t *>(lslot + sp * level_bytes + kPendDoubles * NT * sizeof(double))[threadIdx.x];
+                        r.depth_left = (int)(meta >> 8);
+                        r.path = meta & 0xffu;
+                    } else {
+                        const Pending &pe = deep[sp - kLdsLevels];
+                        r.o = pe.o;
+                        r.d = pe.d;
+                        r.adj = pe.adj;
+                        r.depth_left = pe.depth_left;
+                        r.path = pe.path;
+                    }
+                    have = true;
+                }
+            }
+        }
+    }  // ray loop
+
+    if (wc) {
+        // wave reduction, then one LDS atomic per wave and counter; the workgroup adds its sums once (wg_counters_end)
+        unsigned long long rr = my_rays, hh = my_hits, nn = my_nodes, tt = my_tris;
+        for (int off = 32; off > 0; off >>= 1) {
+            rr += __shfl_xor(rr, off);
+            hh += __shfl_xor(hh, off);
+            if (STATS) {
+                nn += __shfl_xor(nn, off);
+                tt += __shfl_xor(tt, off);
+            }
+        }
+        if (lane == 0 && (rr | (unsigned long long)wave_iters) != 0ull) {
+            atomicAdd(&wc[CGRT_CNT_RAYS], rr);
+            atomicAdd(&wc[CGRT_CNT_HITPOINTS], hh);
+            atomicAdd(&wc[CGRT_CNT_WAVE_ITERS], (unsigned long long)wave_iters);
+            if (STATS) {
+                atomicAdd(&wc[CGRT_CNT_NODE_TESTS], nn);
+                atomicAdd(&wc[CGRT_CNT_TRI_TESTS], tt);
+            }
+        }
+    }
+    wg_counters_end(wg_cnt, counters);
+}
+
+// hit_normal3 of rays whose nearest object is an OPAQUE mesh walked in its 4-wide form: the scene walk prunes such a mesh by
+// distance and orients the normal as for an odd improvement count (tree_intersect_wide: counter = 1; nothing trace() computes
+// depends on the sign, main.cpp:73-76).  The array promises the normal intersect() returned, so this pass -- launched behind
+// trace_rays_kernel only when hit_normal3 is asked for and the scene has such a mesh -- recounts the improvements without
+// pruning (tree_count_wide) and turns the normal where the reference's count is even.  One thread per ray.
+__global__ __launch_bounds__(256) void ray_normal_sign_kernel(DeviceScene sc, RayParams rp) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rp.n) return;
+    const int id = rp.hit_obj[i];
+    if (id < 0) return;
+    const ObjRec &ob = sc.objs[id];
+    if (ob.kind != KIND_MESH || !(ob.transp < kEps) || ob.aux == 2) return;  // (objtype 2 fixes the sign itself, objects.h:434-436)
+    const TreeRec T = sc.trees[ob.tree];
+    if (!T.tri_level || T.nwide == 0) return;
+    const V3 o = ld3(rp.org + 3 * i), d = ld3(rp.dir + 3 * i);
+    const V3 inv = mk(1.0 / d.x, 1.0 / d.y, 1.0 / d.z);
+    const Ray32 r32 = make_ray32(o, inv, T.bmax);
+    const int c = tree_count_wide(sc.wnodes + T.wnode_begin, sc.otris + T.otri_begin, sc.tris + T.tri_begin, o, d, r32);
+    if (c > 0 && (c & 1) == 0) {
+        double *q = rp.hit_normal + 3 * i;
+        q[0] = -q[0];
+        q[1] = -q[1];
+        q[2] = -q[2];
+    }
+}
+
+// ---- the primary rays of the eye pass, as a ray list --------------------------------------------------------------------
+// What a (pixel, sample) of the grid starts with: set_pixel / start_sample of trace_grid_body (main.cpp:188-189,198,203-209).
+// Host and device evaluate this one function; the device's normalized() and the host's sqrt and division are correctly
+// rounded, the rest is plain IEEE arithmetic without contraction, so both give the same bits (tests/test_gpu_rays.py).
+struct CameraRay {
+    double o[3], d[3];
+    uint64_t key;
+};
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ void camera_normalize(double &x, double &y, double &z) {
+    const V3 v = normalized(mk(x, y, z));
+    x = v.x;
+    y = v.y;
+    z = v.z;
+}
+#else
+inline void camera_normalize(double &x, double &y, double &z) {  // vec3.h:36-44
+    const double len = std::sqrt(x * x + y * y + z * z);
+    if (len > 0) {
+        const double r = 1 / len;
+        x *= r;
+        y *= r;
+        z *= r;
+    }
+}
+#endif
+// local row j, column w, sample index `smp` (sample_offset included)
+__host__ __device__ __forceinline__ CameraRay camera_ray(const GridParams &g, int j, int w, int smp) {
+    CameraRay c;
+    const int h = global_row(g, j);
+    c.o[0] = g.cam[0];
+    c.o[1] = g.cam[1];
+    c.o[2] = g.cam[2];
+    c.d[0] = c.d[1] = c.d[2] = 0.0;
+    c.key = 0;
+    if (h >= g.H) return c;  // a row beyond the image (stripe padding): dir = 0, not to be traced
+    const double px = (2.0 * ((double)w / g.W) - 1) * g.half_width;
+    const double py = (2.0 * ((double)h / g.H) - 1) * g.half_width * g.H / g.W;
+    double dx = px - g.cam[0], dy = py - g.cam[1], dz = 0 - g.cam[2];
+    camera_normalize(dx, dy, dz);
+    c.key = sample_key(pixel_key(g.seed, (uint64_t)h * (uint64_t)g.W + (uint64_t)w), (uint64_t)smp);
+    if (g.lens_radius > 0) {
+        const double pf = (g.focus_plane - g.cam[2]) / dz;  // pof = pdir * pf + camorg
+        const double fx = dx * pf + g.cam[0], fy = dy * pf + g.cam[1], fz = dz * pf + g.cam[2];
+        double sx, sy;
+        lens_disc(c.key, sx, sy);
+        c.o[0] = g.cam[0] + sx * g.lens_radius;
+        c.o[1] = g.cam[1] + sy * g.lens_radius;
+        c.o[2] = g.cam[2] + 0 * g.lens_radius;
+        dx = fx - c.o[0];
+        dy = fy - c.o[1];
+        dz = fz - c.o[2];
+        camera_normalize(dx, dy, dz);
+    }
+    c.d[0] = dx;
+    c.d[1] = dy;
+    c.d[2] = dz;
+    return c;
+}
+
+// one thread per (sample, local row, column): ray index = (k * rows + j) * W + w
+__global__ __launch_bounds__(256) void camera_rays_kernel(GridParams g, double *__restrict__ org, double *__restrict__ dir,
+                                                          unsigned long long *__restrict__ keys, long long total) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int w = (int)(i % g.W), j = (int)((i / g.W) % g.rows), k = (int)(i / ((long long)g.W * g.rows));
+    const CameraRay c = camera_ray(g, j, w, g.sample_offset + k);
+    if (org) {
+        org[3 * i] = c.o[0];
+        org[3 * i + 1] = c.o[1];
+        org[3 * i + 2] = c.o[2];
+    }
+    if (dir) {
+        dir[3 * i] = c.d[0];
+        dir[3 * i + 1] = c.d[1];
+        dir[3 * i + 2] = c.d[2];
+    }
+    if (keys) keys[i] = c.key;
+}
+
+#endif

@@ -525,6 +525,77 @@ __device__ __forceinline__ TreeHit hfield_intersect(const HFieldRec &H, const HC
     return r;
 }
 
+// The improvement counter of KDTree::intersect_subtree (objects.h:276-289,314) for an opaque owner's wide hierarchy: the sum,
+// over the reference's leaves, of the times a leaf's running minimum improved while its triangles were scanned in leaf
+// order.  tree_intersect_wide prunes by distance and cannot know it; this walk prunes nothing -- it visits every triangle
+// whose boxes the ray touches (a triangle the ray hits is among them: the superset argument above) and, for every accepted
+// hit (leaf-order index k, first index `leaf` of its reference leaf), rescans that leaf's earlier triangles tris[leaf .. k)
+// with the same test: the hit improved the leaf's minimum iff none of them was hit at a distance <= its own (strict <,
+// objects.h:281).  A leaf the reference reaches without a hit adds nothing, so the inner nodes do not matter.  Used only to
+// give cgrt_trace_rays' hit_normal3 the reference's sign (ray_normal_sign_kernel, cgrt_rays.hpp).
+// tri_test restates the triangle test that tree_intersect, tree_intersect_lq, tree_intersect_wide and hfield_intersect each
+// carry inline (those walks are left as they are: their code generation is measured); the recount is only right while the
+// copies agree, which tests/test_gpu_rays.py::test_random_rays_hit_normal[dragon] checks on every hit.
+// Returns 0 (count unknown: the caller leaves the normal alone) if the stack would overflow -- cgrt_build.cpp bounds a wide
+// tree's depth so that it cannot (kWideStack), as for tree_intersect_wide, whose pushes per node these are.
+__device__ __forceinline__ bool tri_test(const TriRec &t, V3 o, V3 d, double &len) {
+    const V3 pa = ld3(t.pa), e1 = ld3(t.e1), e2 = ld3(t.e2);
+    const V3 s = pa - o;
+    const double det1 = det3(d, e1, e2);
+    const double det2 = det3(s, e1, e2);
+    const double det3_ = det3(d, s, e2);
+    const double det4 = det3(d, e1, s);
+    const double sg = det1 > 0.0 ? 1.0 : -1.0;
+    const double a1 = det1 * sg;
+    const bool ok = (det1 != 0.0) && (det2 * sg > 0.0) && (det3_ * sg >= 0.0) && (det4 * sg >= 0.0) && ((det3_ + det4) * sg <= a1);
+    if (ok) len = det2 / det1;
+    return ok;
+}
+__device__ __forceinline__ int tree_count_wide(const WideNodeRec *__restrict__ wn, const OTriRec *__restrict__ otris,
+                                               const TriRec *__restrict__ tris, V3 o, V3 d, const Ray32 &r32) {
+    int counter = 0;
+    int32_t stk[kWideStack];
+    int sp = 0;
+    int32_t nxt = ~0;  // the root
+    while (nxt != kWideNone) {
+        if (nxt < 0) {
+            const float4 *q = reinterpret_cast<const float4 *>(wn + (~nxt));
+            const float4 lox = q[0], loy = q[1], loz = q[2], hix = q[3], hiy = q[4], hiz = q[5];
+            const int4 ref = reinterpret_cast<const int4 *>(q)[6];
+            const float lx[4] = {lox.x, lox.y, lox.z, lox.w}, ly[4] = {loy.x, loy.y, loy.z, loy.w}, lz[4] = {loz.x, loz.y, loz.z, loz.w};
+            const float hx[4] = {hix.x, hix.y, hix.z, hix.w}, hy[4] = {hiy.x, hiy.y, hiy.z, hiy.w}, hz[4] = {hiz.x, hiz.y, hiz.z, hiz.w};
+            const int32_t rf[4] = {ref.x, ref.y, ref.z, ref.w};
+            nxt = kWideNone;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                float tn, tf;
+                slab32(r32, lx[k], ly[k], lz[k], hx[k], hy[k], hz[k], tn, tf);
+                if ((rf[k] != kWideNone) && (tf > 0.f) && (tn <= tf)) {
+                    if (nxt == kWideNone) nxt = rf[k];
+                    else if (sp < kWideStack) stk[sp++] = rf[k];
+                    else return 0;
+                }
+            }
+            if (nxt != kWideNone) continue;
+        } else {
+            const OTriRec *tp = otris + (nxt >> 4);
+            const int cnt = nxt & 15;
+            for (int k = 0; k < cnt; k++) {
+                double len;
+                if (!tri_test(tp[k].t, o, d, len) || !(len < kInf)) continue;  // (`len = doubleINF` at objects.h:278)
+                bool improved = true;
+                for (int j = tp[k].leaf; j < tp[k].k && improved; j++) {
+                    double lj;
+                    if (tri_test(tris[j], o, d, lj) && lj <= len) improved = false;
+                }
+                if (improved) counter++;
+            }
+        }
+        nxt = sp > 0 ? stk[--sp] : kWideNone;
+    }
+    return counter;
+}
+
 // normal of the winning triangle, oriented by the improvement-counter parity (objects.h:107,321-327)
 __device__ __forceinline__ V3 tree_normal(const TriRec *__restrict__ tris, const TreeHit &h, V3 d) {
     const V3 e1 = ld3(tris[h.tri].e1), e2 = ld3(tris[h.tri].e2);

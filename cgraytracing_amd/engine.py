@@ -184,6 +184,127 @@ class Scene:
                                       counters.data_ptr(), C.c_void_p(st)))
         return out, nhit, counters
 
+    # ---- caller-supplied rays ----
+    _WANT = ("acc", "nhit", "hit")
+
+    def camera_rays(self, width, height, spp=1, camera=None, seed=12345, rows=None, row_offset=0, stripe=None,
+                    sample_offset=0, stream=None):
+        """The primary rays trace_grid starts for samples sample_offset .. sample_offset + spp - 1 of the grid's rows
+        (cgrt_camera_rays), made on the device: (org [n,3] float64, dirs [n,3] float64, keys [n] int64 (bit pattern uint64))
+        torch tensors, n = spp * rows * width, ray index = (k * rows + local row) * width + w.  Rows beyond `height` of a
+        striped grid have dirs = 0 and are not traced by trace_rays."""
+        import torch
+
+        rows = height - row_offset if rows is None else rows
+        dev = torch.device("cuda", self.device)
+        n = spp * rows * width
+        org = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        dirs = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        keys = torch.empty((n,), dtype=torch.int64, device=dev)
+        cc, g = self._structs(camera, width, height, rows, spp, 1, seed, row_offset, stripe, sample_offset, None, 0)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            check(self._L.cgrt_camera_rays(C.byref(cc), C.byref(g), org.data_ptr(), dirs.data_ptr(), keys.data_ptr(),
+                                           C.c_void_p(st)))
+        return org, dirs, keys
+
+    def trace_rays(self, org, dirs, keys=None, max_depth=5, seed=12345, first_index=0, want=("acc", "nhit", "hit"),
+                   counters=None, stream=None, stats=False, out=None, sign_pass=True):
+        """cgrt_trace_rays on torch tensors: org, dirs float64 [n,3] contiguous on the scene's device, keys int64 [n] or None.
+        want: which results -- "acc" (float64 [n,3]: the ray tree's sum of f*adj), "nhit" (int32 [n]), "hit" (hit_obj int32
+        [n], hit_t float64 [n], hit_normal float64 [n,3]: the ray's own nearest hit).  want=("hit",) is a nearest-hit query
+        (one scene walk per ray, no shading).  out: dict of preallocated result tensors to write into.  Asynchronous on torch's
+        current stream (or `stream`); counters (int64 [8]) are ADDED to.  sign_pass=False: CGRT_RAYS_NO_SIGN_PASS (an opaque
+        mesh's hit_normal is then right up to its sign; saves an unpruned mesh walk per ray).  Returns a dict of the tensors
+        and "counters"."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        for name, t in (("org", org), ("dirs", dirs)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == 3 and
+                    t.is_contiguous() and t.device == dev):
+                raise ValueError("trace_rays: %s must be a contiguous float64 [n,3] tensor on %s" % (name, dev))
+        n = org.shape[0]
+        if dirs.shape[0] != n:
+            raise ValueError("trace_rays: org and dirs differ in length")
+        if keys is not None and not (isinstance(keys, torch.Tensor) and keys.dtype == torch.int64 and tuple(keys.shape) == (n,) and
+                                     keys.is_contiguous() and keys.device == dev):
+            raise ValueError("trace_rays: keys must be a contiguous int64 [n] tensor on %s" % (dev,))
+        want = tuple(want)
+        if not want or any(w not in self._WANT for w in want):
+            raise ValueError("trace_rays: want is a non-empty subset of %r" % (self._WANT,))
+        shapes = {}
+        if "acc" in want:
+            shapes["acc"] = ((n, 3), torch.float64)
+        if "nhit" in want:
+            shapes["nhit"] = ((n,), torch.int32)
+        if "hit" in want:
+            shapes.update(hit_obj=((n,), torch.int32), hit_t=((n,), torch.float64), hit_normal=((n, 3), torch.float64))
+        res = {}
+        for name, (shape, dtype) in shapes.items():
+            t = out.get(name) if out else None
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=dev)
+            elif not (t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev):
+                raise ValueError("trace_rays: out[%r] must be a contiguous %s %r tensor on %s" % (name, dtype, shape, dev))
+            res[name] = t
+        if counters is None:
+            counters = torch.zeros((_capi.CGRT_NCOUNTERS,), dtype=torch.int64, device=dev)
+        elif not (counters.dtype == torch.int64 and counters.numel() == _capi.CGRT_NCOUNTERS and counters.is_contiguous() and
+                  counters.device == dev):
+            raise ValueError("trace_rays: counters must be a contiguous int64 [8] tensor on %s" % (dev,))
+        res["counters"] = counters
+        if n == 0:
+            return res
+        ptr = lambda k: res[k].data_ptr() if k in res else None
+        r = _capi.Rays(n, org.data_ptr(), dirs.data_ptr(), keys.data_ptr() if keys is not None else None, first_index, seed,
+                       max_depth, (_capi.RAYS_STATS if stats else 0) | (0 if sign_pass else _capi.RAYS_NO_SIGN_PASS))
+        o = _capi.RayResults(ptr("acc"), ptr("nhit"), ptr("hit_obj"), ptr("hit_t"), ptr("hit_normal"))
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(self._L.cgrt_trace_rays(self._h, C.byref(r), C.byref(o), counters.data_ptr(), C.c_void_p(st)))
+        return res
+
+    def trace_rays_host(self, org, dirs, keys=None, max_depth=5, seed=12345, first_index=0, want=("acc", "nhit", "hit"),
+                        stats=False, sign_pass=True):
+        """Synchronous form of trace_rays on numpy arrays (no torch needed): dict(acc, nhit (uint32), hit_obj, hit_t,
+        hit_normal -- those in `want` --, counters (uint64 [8]), nrays, nhp)."""
+        org = np.ascontiguousarray(org, np.float64).reshape(-1, 3)
+        dirs = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
+        n = len(org)
+        if len(dirs) != n:
+            raise ValueError("trace_rays_host: org and dirs differ in length")
+        if keys is not None:
+            keys = np.ascontiguousarray(keys, np.uint64)
+            if keys.shape != (n,):
+                raise ValueError("trace_rays_host: keys must have one entry per ray")
+        want = tuple(want)
+        if not want or any(w not in self._WANT for w in want):
+            raise ValueError("trace_rays_host: want is a non-empty subset of %r" % (self._WANT,))
+        res = {}
+        if "acc" in want:
+            res["acc"] = np.zeros((n, 3), np.float64)
+        if "nhit" in want:
+            res["nhit"] = np.zeros(n, np.uint32)
+        if "hit" in want:
+            res.update(hit_obj=np.zeros(n, np.int32), hit_t=np.zeros(n, np.float64), hit_normal=np.zeros((n, 3), np.float64))
+        cnt = np.zeros((_capi.CGRT_NCOUNTERS,), np.uint64)
+        ptr = lambda k: res[k].ctypes.data if k in res else None
+        r = _capi.Rays(n, org.ctypes.data, dirs.ctypes.data, keys.ctypes.data if keys is not None else None, first_index, seed,
+                       max_depth, (_capi.RAYS_STATS if stats else 0) | (0 if sign_pass else _capi.RAYS_NO_SIGN_PASS))
+        o = _capi.RayResults(ptr("acc"), ptr("nhit"), ptr("hit_obj"), ptr("hit_t"), ptr("hit_normal"))
+        check(self._L.cgrt_trace_rays_host(self._h, C.byref(r), C.byref(o), cnt.ctypes.data))
+        res.update(counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]), nhp=int(cnt[_capi.CNT_HITPOINTS]))
+        return res
+
+    def rays_variant(self, max_depth=5, want=("acc", "nhit", "hit"), stats=False):
+        """Name of the trace_rays_kernel instantiation trace_rays launches for these arguments (cgrt_trace_rays_variant)."""
+        full = 1 if ("acc" in want or "nhit" in want) else None
+        r = _capi.Rays(1, None, None, None, 0, 0, max_depth, _capi.RAYS_STATS if stats else 0)
+        o = _capi.RayResults(full, None, 1 if "hit" in want else None, None, None)
+        buf = C.create_string_buffer(160)
+        check(self._L.cgrt_trace_rays_variant(self._h, C.byref(r), C.byref(o), buf, len(buf)))
+        return buf.value.decode()
+
     def trace_grid_host(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                         stripe=None, sample_offset=0, spp_total=None, stats=False, split_samples=False, reorder=True,
                         force_reorder=False):
@@ -388,6 +509,23 @@ class PpmSession:
         cnt = C.c_uint64(0)
         check(self._L.cgrt_ppm_session_hitpoints(self._h, hp.ctypes.data, n, C.byref(cnt)))
         return hp[:n]
+
+
+def camera_rays_host(width, height, spp=1, camera=None, seed=12345, rows=None, row_offset=0, stripe=None, sample_offset=0):
+    """cgrt_camera_rays_host: the primary rays of the eye pass evaluated on the host -- no GPU and no scene needed.
+    Returns (org [n,3] float64, dirs [n,3] float64, keys [n] uint64) numpy arrays, n = spp * rows * width, ray index =
+    (k * rows + local row) * width + w; the same bits Scene.camera_rays makes on the device."""
+    rows = height - row_offset if rows is None else rows
+    camera = camera or Camera()
+    cc = _CCamera(_d3(camera.cam), camera.half_width, camera.focus_plane, camera.lens_radius)
+    s_rows, s_rank, s_n = stripe if stripe else (0, 0, 1)
+    g = _CGrid(width, height, rows, row_offset, s_rows, s_rank, s_n, spp, sample_offset, spp, 1, 0, seed)
+    n = spp * rows * width
+    org = np.zeros((n, 3), np.float64)
+    dirs = np.zeros((n, 3), np.float64)
+    keys = np.zeros(n, np.uint64)
+    check(_capi.lib().cgrt_camera_rays_host(C.byref(cc), C.byref(g), org.ctypes.data, dirs.ctypes.data, keys.ctypes.data))
+    return org, dirs, keys
 
 
 def render(objs, width=1024, height=768, num_of_samples=1, camera=None, max_depth=5, seed=12345, device=0):

@@ -16,7 +16,8 @@
  * and never exits or throws; cgrt_last_error() gives the message for the calling thread.  Object handles are
  * not thread-safe; distinct scenes may be used concurrently from different host threads / devices.
  * Threading: launches on ONE scene handle must be ordered by the caller (same stream, or events between streams) --
- * a handle owns device scratch that consecutive launches reuse (CGRT_GRID_SPLIT_SAMPLES chunk sums).
+ * a handle owns device scratch that consecutive launches reuse (CGRT_GRID_SPLIT_SAMPLES chunk sums; the schedule of a
+ * cost-ordered frame; the queue counter of cgrt_trace_rays, which is one of these launches).
  * All geometry is IEEE double, like the reference (Vec3 = 3 x double, vec3.h:11-30).
  */
 #ifndef CGRT_H
@@ -31,7 +32,9 @@ extern "C" {
 
 #define CGRT_VERSION 112 /* 110: cgrt_photons.initial_radius / .pair_cap, cgrt_ppm_result.n_batch_halvings,
                             cgrt_surface_colors, cgrt_trace_grid_variant; 111: cgrt_scene_wide_dump;
-                            112: cgrt_scene_set_build, cgrt_scene_build_info (row f3: structures built on the device) */
+                            112: cgrt_scene_set_build, cgrt_scene_build_info (row f3: structures built on the device);
+                            added since without a new number, like the cgrt_ppm_session_* calls: cgrt_trace_rays,
+                            cgrt_trace_rays_host, cgrt_trace_rays_variant, cgrt_camera_rays, cgrt_camera_rays_host (caller-supplied rays) */
 
 enum {
     CGRT_OK = 0,
@@ -218,6 +221,69 @@ int cgrt_scene_wide_dump(const cgrt_scene *s, int tree, int32_t *nwide, int32_t 
  * rounding is the final store. */
 int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, float *rgb,
                     uint32_t *nhit, uint64_t *counters, void *stream);
+
+/* ---- caller-supplied rays -----------------------------------------------------------------------------------------
+ * cgrt_trace_grid traces the rays its own camera makes (image plane z = 0, view along +z).  cgrt_trace_rays runs the same
+ * trace(flag=true) recursion -- the same arithmetic in the same order -- for rays from a buffer: arbitrary cameras (make the
+ * rays yourself, or take cgrt_camera_rays' and transform them), nearest-hit queries (picking, visibility), radiance probes. */
+typedef struct cgrt_rays {
+    int64_t n;               /* rays; 0 is valid and does nothing; more than 2^36: CGRT_ERR_LIMIT                           */
+    const double *org3;      /* [n][3]                                                                                        */
+    const double *dir3;      /* [n][3] used as given: trace() never normalises its dir (main.cpp:42); unit length is the
+                                caller's contract.  A dir of exactly (0,0,0) marks a ray that is NOT traced: its results are
+                                those of a miss and it is not counted                                                        */
+    const uint64_t *keys;    /* [n] or NULL: key of ray i's Bezier draw streams (the k_smp of cgrt_rng.hpp).
+                                NULL: sample_key(pixel_key(seed, first_index + i), 0)                                        */
+    int64_t first_index;     /* only used when keys == NULL: lets a caller split a ray set over calls / GPUs                 */
+    uint64_t seed;
+    int32_t max_depth;       /* 1..5, as cgrt_grid.max_depth; not looked at by a nearest-hit query                           */
+    int32_t flags;           /* bit set of CGRT_RAYS_*                                                                       */
+} cgrt_rays;
+enum {
+    CGRT_RAYS_STATS = 1,       /* also count tree-node and triangle tests, like CGRT_GRID_STATS                              */
+    CGRT_RAYS_NO_SIGN_PASS = 2 /* hit_normal3 of an opaque mesh: skip the pass that gives it the reference's sign (below); the
+                                  vector is then right up to its sign, and the call costs one unpruned mesh walk per ray less */
+};
+
+typedef struct cgrt_ray_results {   /* every pointer may be NULL: only the arrays asked for are written */
+    double   *acc3;        /* [n][3] sum over the ray tree's Hitpoints of f*adj (main.cpp:88), fp64, added in the reference's
+                              emission order (reflect subtree, then refract); NOT divided by anything                       */
+    uint32_t *nhit;        /* [n]    Hitpoints of the ray tree                                                              */
+    int32_t  *hit_obj;     /* [n]    position in objs of the nearest object the ray itself hits (main.cpp:52-62: strict <,
+                              the first object wins), -1 for none                                                            */
+    double   *hit_t;       /* [n]    its distance; 0 when hit_obj = -1                                                       */
+    double   *hit_normal3; /* [n][3] the normal intersect() returned, before the flip of main.cpp:73-76; 0 on a miss.
+                              Spheres, planes, Bezier objects, transparent meshes and transparent bump floors: as the scene walk
+                              finds it.  OPAQUE mesh: the reference takes the sign from the parity of its walk's improvement
+                              counter (objects.h:321-327), which the pruned scene walk does not know; asking for this array on
+                              a scene with an opaque mesh walked in its 4-wide form (the default build) adds a pass that
+                              recounts it, unless CGRT_RAYS_NO_SIGN_PASS.  NOT recounted -- the vector is right, its sign is
+                              that of ONE improvement (along the ray): an opaque mesh whose hierarchy is not the 4-wide one
+                              (the CGRT_TREE=ref development build of the hierarchy) and the triangles of an opaque BUMP
+                              FLOOR (a ray reaching the height field from above hits one triangle).  trace() turns an opaque
+                              owner's normal against the ray in any case, so no radiance depends on the sign                */
+} cgrt_ray_results;
+
+/* DEVICE pointers on the scene's device; asynchronous on `stream`; counters (may be NULL) are ADDED to: CGRT_CNT_RAYS,
+ * _HITPOINTS and _WAVE_ITERS (and, with CGRT_RAYS_STATS, the two test counters) mean what they mean for cgrt_trace_grid.
+ * With acc3 and nhit both NULL the call is a NEAREST-HIT QUERY: one scene walk per ray, no shading.  Otherwise the full
+ * recursion runs per ray.  A ray's results do not depend on the other rays of the call, on their order or on how a ray set
+ * is split over calls (with keys, or first_index, kept alike).  This is a launch on the scene handle (Threading above). */
+int cgrt_trace_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_results *out, uint64_t *counters, void *stream);
+/* HOST pointers: allocates device buffers, runs, synchronises and copies back (counters are overwritten). */
+int cgrt_trace_rays_host(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_results *out, uint64_t *counters);
+/* Name of the trace_rays_kernel instantiation cgrt_trace_rays would launch for (scene, rays, out), as cgrt_trace_grid_variant
+ * names the eye pass's; only rays->n, max_depth, flags and which of out's pointers are NULL matter (no pointer is read). */
+int cgrt_trace_rays_variant(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_results *out, char *name, size_t cap);
+
+/* The primary rays cgrt_trace_grid starts for sample `sample_offset + k`, k in [0, spp), of every pixel of the grid's rows
+ * (contiguous or striped): ray index = (k * rows + local row) * width + w.  org3 / dir3 / keys as in cgrt_rays (any may be
+ * NULL); pixels of rows beyond `height` in a striped grid get org = cam, dir = 0, key = 0 and are not traced by
+ * cgrt_trace_rays.  max_depth, spp_total and flags are ignored.  More than 2^38 rays: CGRT_ERR_LIMIT.
+ * DEVICE pointers on the current device, asynchronous on `stream`. */
+int cgrt_camera_rays(const cgrt_camera *cam, const cgrt_grid *grid, double *org3, double *dir3, uint64_t *keys, void *stream);
+/* The same bits evaluated on the HOST into host buffers; needs no GPU (like cgrt_lens_samples). */
+int cgrt_camera_rays_host(const cgrt_camera *cam, const cgrt_grid *grid, double *org3, double *dir3, uint64_t *keys);
 
 /* Row e of SURVEY.md section 8: the un-permute that follows the framebuffer gather.  shares = n_present buffers
  * [rows_local][width][channels] float, share-major (share r's local row j is global row ((j / stripe_rows) * nshares + r) *

@@ -324,6 +324,50 @@ inline void render(const std::vector<Object *> &objs, const RenderParams &rp, st
     }
 }
 
+// trace() for rays of the caller's own (cgrt_trace_rays_host): acc[i] = the sum of hp.f over ray i's Hitpoints (three doubles, not
+// divided by anything), nhit[i] their number; dir is used as given (unit length is the caller's contract).  A look-at camera,
+// a fisheye or a light probe is a ray list away.
+struct RayHit {
+    std::vector<int32_t> obj;   // position in objs of the nearest object hit by the ray itself, -1 for none
+    std::vector<double> t, normal;  // its distance (0 on a miss); the normal intersect() returned (3 per ray)
+};
+inline void trace_rays(const std::vector<Object *> &objs, const std::vector<double> &org3, const std::vector<double> &dir3,
+                       std::vector<double> &acc3, std::vector<uint32_t> *nhit = nullptr, RayHit *hit = nullptr, int max_depth = 5,
+                       uint64_t seed = 12345, int device = 0, RenderStats *stats = nullptr) {
+    if (org3.size() != dir3.size() || org3.size() % 3) throw Error(CGRT_ERR_INVALID, "trace_rays: org3 / dir3 are n x 3 doubles");
+    SceneBuilder sb;
+    for (const Object *o : objs) o->add_to(sb);
+    check(cgrt_scene_commit(sb.scene, device));
+    const size_t n = org3.size() / 3;
+    cgrt_rays r{};
+    r.n = (int64_t)n;
+    r.org3 = org3.data();
+    r.dir3 = dir3.data();
+    r.seed = seed;
+    r.max_depth = max_depth;
+    acc3.assign(3 * n, 0.0);
+    cgrt_ray_results out{};
+    out.acc3 = acc3.data();
+    if (nhit) {
+        nhit->assign(n, 0u);
+        out.nhit = nhit->data();
+    }
+    if (hit) {
+        hit->obj.assign(n, -1);
+        hit->t.assign(n, 0.0);
+        hit->normal.assign(3 * n, 0.0);
+        out.hit_obj = hit->obj.data();
+        out.hit_t = hit->t.data();
+        out.hit_normal3 = hit->normal.data();
+    }
+    uint64_t cnt[CGRT_NCOUNTERS] = {0};
+    check(cgrt_trace_rays_host(sb.scene, &r, &out, cnt));
+    if (stats) {
+        stats->rays = cnt[CGRT_CNT_RAYS];
+        stats->hitpoints = cnt[CGRT_CNT_HITPOINTS];
+    }
+}
+
 // ---- the whole of render() + main()'s PNG loop: main.cpp:169-258, 403-412 ---------------------------------------
 // Photon-pass constants of the reference as runtime fields with the same defaults.
 struct PhotonParams {

@@ -32,6 +32,10 @@ def demangle_variant(name):
     if m:
         t = [int(x) for x in m.groups()]
         return "trace_grid_kernel<TREES=%d,BEZ=%d,DOF=%d,GLASS=%d,SPH=%d,STATS=%d,HPS=%d,NT=%d>" % tuple(t)
+    m = re.match(r"_Z17trace_rays_kernelIL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)ELi(\d+)EE", name)
+    if m:
+        t = [int(x) for x in m.groups()]
+        return "trace_rays_kernel<TREES=%d,BEZ=%d,GLASS=%d,SPH=%d,STATS=%d,SPILL=%d,FIRST=%d,NT=%d>" % tuple(t)
     m = re.search(r"19photon_trace_kernelILb(\d)ELb(\d)EE", name)
     if m:
         return "photon_trace_kernel<BEZ=%s,SPILL=%s>" % m.groups()
