@@ -90,8 +90,13 @@ class RayResults(C.Structure):
                 ("hit_normal3", C.c_void_p)]
 
 
+class RayPixels(C.Structure):
+    _fields_ = [("width", C.c_int32), ("rows", C.c_int32), ("spp", C.c_int32), ("pad_", C.c_int32), ("pixel", C.c_void_p)]
+
+
 RAYS_STATS = 1
 RAYS_NO_SIGN_PASS = 2
+RAYS_HITPOINTS = 4
 
 # every symbol include/cgrt.h declares, with its signature
 _DP = C.POINTER(C.c_double)
@@ -128,6 +133,8 @@ SIGNATURES = {
                                   C.POINTER(PpmResult)]),
     "cgrt_ppm_session_create": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Grid), C.POINTER(Photons), C.c_int,
                                           C.POINTER(C.c_void_p)]),
+    "cgrt_ppm_session_create_rays": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(RayPixels), C.POINTER(Photons), C.c_int,
+                                               C.POINTER(C.c_void_p)]),
     "cgrt_ppm_session_destroy": (None, [C.c_void_p]),
     "cgrt_ppm_session_add_photons": (C.c_int, [C.c_void_p, C.c_int64]),
     "cgrt_ppm_session_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -147,6 +154,7 @@ SIGNATURES = {
     "cgrt_trace_rays": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(RayResults), C.c_void_p, C.c_void_p]),
     "cgrt_trace_rays_host": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(RayResults), C.c_void_p]),
     "cgrt_trace_rays_variant": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(RayResults), C.c_char_p, C.c_size_t]),
+    "cgrt_trace_rays_hitpoints": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cgrt_camera_rays": (C.c_int, [C.POINTER(Camera), C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cgrt_camera_rays_host": (C.c_int, [C.POINTER(Camera), C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cgrt_intersect_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,

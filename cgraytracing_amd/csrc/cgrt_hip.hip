@@ -995,6 +995,31 @@ static const RaysKernels *rays_kernels(const RayFlags &f) {
         if (e.id == f.id()) return &e;
     return nullptr;
 }
+// The instantiations of capture_rays_kernel: one for every full-trace entry above without STATS (rays_launch(stats = false,
+// first = false) chooses among exactly these).
+using CaptureKernel = void (*)(DeviceScene, RayParams, RaySink);
+struct CaptureKernels {
+    int id;  // RayFlags::id() of the trace_rays_kernel it is the capture form of
+    CaptureKernel fn;
+};
+template <int T, int B, int G, int P, int SP, int NT = kThreads>
+static constexpr CaptureKernels ck() {
+    return {RayFlags{T != 0, B != 0, G != 0, P != 0, false, SP != 0, false, NT}.id(),
+            &capture_rays_kernel<T != 0, B != 0, G != 0, P != 0, SP != 0, NT>};
+}
+//                                TREES BEZ GLASS SPH SPILL [NT]
+static const CaptureKernels kCaptureKernels[] = {
+    ck<1, 1, 0, 0, 0, 64>(), ck<1, 1, 1, 0, 0, 64>(),
+    ck<1, 0, 0, 0, 0>(), ck<1, 0, 1, 0, 0>(),
+    ck<0, 0, 0, 1, 0>(), ck<0, 0, 1, 1, 0>(), ck<0, 0, 0, 0, 0>(), ck<0, 0, 1, 0, 0>(),
+    // SPILL: spheres, and the general body
+    ck<0, 0, 0, 1, 1>(), ck<0, 0, 1, 1, 1>(), ck<1, 1, 1, 0, 1>(),
+};
+static const CaptureKernels *capture_kernels(const RayFlags &f) {
+    for (const CaptureKernels &e : kCaptureKernels)
+        if (e.id == f.id()) return &e;
+    return nullptr;
+}
 
 // One launch of trace_rays_kernel: the flags chosen from the scene's traits the way eye_launch chooses the eye pass's
 struct RaysLaunch {
@@ -1038,6 +1063,16 @@ static int check_rays(const cgrt_scene *s, const cgrt_rays *r, const cgrt_ray_re
     if (r->n < 0) return fail(CGRT_ERR_INVALID, "negative ray count");
     if (r->n > 0 && (!r->org3 || !r->dir3)) return fail(CGRT_ERR_INVALID, "null org3 / dir3");
     if ((out->acc3 || out->nhit) && (r->max_depth < 1 || r->max_depth > kMaxDepth)) return fail(CGRT_ERR_INVALID, "max_depth must be 1..5");
+    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+    if (r->n > kMaxRays) return fail(CGRT_ERR_LIMIT, "more than 2^36 rays in one call");
+    return CGRT_OK;
+}
+// What the Hitpoint capture reads of a ray set: every ray is traced in full, so max_depth always counts
+static int check_capture_rays(const cgrt_scene *s, const cgrt_rays *r) {
+    if (!s || !r) return fail(CGRT_ERR_INVALID, "null argument");
+    if (r->n < 0) return fail(CGRT_ERR_INVALID, "negative ray count");
+    if (r->n > 0 && (!r->org3 || !r->dir3)) return fail(CGRT_ERR_INVALID, "null org3 / dir3");
+    if (r->max_depth < 1 || r->max_depth > kMaxDepth) return fail(CGRT_ERR_INVALID, "max_depth must be 1..5");
     if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
     if (r->n > kMaxRays) return fail(CGRT_ERR_LIMIT, "more than 2^36 rays in one call");
     return CGRT_OK;
@@ -1108,7 +1143,16 @@ int cgrt_trace_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_r
 }
 
 int cgrt_trace_rays_variant(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_results *out, char *name, size_t cap) {
-    if (!s || !rays || !out || !name || cap == 0) return fail(CGRT_ERR_INVALID, "null argument");
+    if (!s || !rays || !name || cap == 0 || (!out && !(rays->flags & CGRT_RAYS_HITPOINTS))) return fail(CGRT_ERR_INVALID, "null argument");
+    if (rays->flags & CGRT_RAYS_HITPOINTS) {  // the capture's launch: out is not looked at
+        if (rays->max_depth < 1 || rays->max_depth > kMaxDepth) return fail(CGRT_ERR_INVALID, "max_depth must be 1..5");
+        if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+        ON_DEVICE(s->device);
+        const RayFlags k = rays_launch(s, rays->max_depth, false, false).k;
+        std::snprintf(name, cap, "capture_rays_kernel<TREES=%d,BEZ=%d,GLASS=%d,SPH=%d,SPILL=%d,NT=%d>", (int)k.trees, (int)k.bez,
+                      (int)k.glass, (int)k.sph, (int)k.spill, k.nt);
+        return CGRT_OK;
+    }
     const bool first = !out->acc3 && !out->nhit;
     if (!first && (rays->max_depth < 1 || rays->max_depth > kMaxDepth)) return fail(CGRT_ERR_INVALID, "max_depth must be 1..5");
     if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
@@ -1209,6 +1253,52 @@ __global__ void unpermute_stripes_kernel(const float *__restrict__ shares, int n
     frame[(size_t)h * row_floats + x] = v;
 }
 
+// The ray-buffer form of hitpoints_device below: capture_rays_kernel over rays' DEVICE arrays (pixel: DEVICE, or nullptr)
+// into a device buffer of `cap` records; *count = Hitpoints produced.  *d_rec_out is hipMalloc'ed here (caller frees) unless
+// cap == 0.  Runs on the null stream and synchronises.
+static int ray_hitpoints_device(const cgrt_scene *s, const cgrt_rays *rays, const int64_t *pixel, uint64_t cap, double **d_rec_out,
+                                uint64_t *count) {
+    *count = 0;
+    if (rays->n == 0) return CGRT_OK;
+    const RaysLaunch L = rays_launch(s, rays->max_depth, false, false);
+    const CaptureKernels *e = capture_kernels(L.k);
+    if (!e) return fail(CGRT_ERR_UNSUPPORTED, std::string(L.what()) + ": no capture kernel built for this variant");
+    DevBuf b_rec, b_cnt;
+    HIP_TRY(b_rec.alloc((cap ? cap : 1) * 10 * sizeof(double)));
+    HIP_TRY(b_cnt.alloc(sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(b_cnt.p, 0, sizeof(unsigned long long)));
+    // the queue's head lives in the handle's launch scratch, as cgrt_trace_rays'
+    if (s->scratch.need(256) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(CGRT_ERR_DEVICE, "cannot allocate launch scratch (ray queue)");
+    }
+    HIP_TRY(hipMemsetAsync(s->scratch.p, 0, sizeof(unsigned int), 0));
+    RayParams rp{};
+    rp.n = rays->n;
+    rp.org = rays->org3;
+    rp.dir = rays->dir3;
+    rp.keys = reinterpret_cast<const unsigned long long *>(rays->keys);
+    rp.first_index = rays->first_index;
+    rp.seed = rays->seed;
+    rp.max_depth = rays->max_depth;
+    rp.queue = reinterpret_cast<unsigned int *>(s->scratch.p);
+    const RaySink sink{b_rec.as<double>(), b_cnt.as<unsigned long long>(), (unsigned long long)cap,
+                       reinterpret_cast<const long long *>(pixel)};
+    const long long waves_per_wg = L.k.nt / 64, n_blocks = (rays->n + 63) / 64;
+    const long long chip = (long long)s->n_cu * 4 * (L.k.bez ? kBezWaves : (L.k.trees ? kTreeWaves : 4)) / waves_per_wg;
+    const long long wgs = std::max(1ll, std::min((n_blocks + waves_per_wg - 1) / waves_per_wg, 2 * chip));
+    int rc = launch_checked(e->fn, L.what(), s->device, dim3((unsigned)wgs), dim3((unsigned)L.k.nt), L.lds, 0, L.dev, rp, sink);
+    if (rc) return rc;
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipDeviceSynchronize();
+    if (err != hipSuccess) return fail(CGRT_ERR_DEVICE, std::string("ray hitpoint kernel: ") + hipGetErrorString(err));
+    unsigned long long n = 0;
+    if (hipMemcpy(&n, b_cnt.p, sizeof(n), hipMemcpyDeviceToHost) != hipSuccess) return fail(CGRT_ERR_DEVICE, "hitpoint count copy");
+    *count = n;
+    if (cap && d_rec_out) *d_rec_out = reinterpret_cast<double *>(b_rec.release());
+    return CGRT_OK;
+}
+
 // Eye pass with Hitpoint capture into a device buffer of `cap` records (10 doubles each); *count = hitpoints produced.
 // *d_rec_out is hipMalloc'ed here (caller frees) unless cap == 0.
 static int hitpoints_device(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, uint64_t cap,
@@ -1251,6 +1341,24 @@ int cgrt_trace_grid_hitpoints(const cgrt_scene *s, const cgrt_camera *cam, const
     double *d_rec = nullptr;
     uint64_t n = 0;
     rc = hitpoints_device(s, cam, grid, cap, &d_rec, &n);
+    if (rc == CGRT_OK) {
+        *count = n;
+        const uint64_t m = n < cap ? n : cap;
+        if (m && hipMemcpy(hp10, d_rec, (size_t)m * 10 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(CGRT_ERR_DEVICE, "hitpoint copy");
+    }
+    if (d_rec) (void)hipFree(d_rec);
+    return rc;
+}
+
+int cgrt_trace_rays_hitpoints(const cgrt_scene *s, const cgrt_rays *rays, double *hp10, uint64_t cap, uint64_t *count) {
+    int rc = check_capture_rays(s, rays);
+    if (rc) return rc;
+    if (!count || (cap > 0 && !hp10)) return fail(CGRT_ERR_INVALID, "null output");
+    ON_DEVICE(s->device);
+    double *d_rec = nullptr;
+    uint64_t n = 0;
+    rc = ray_hitpoints_device(s, rays, nullptr, cap, &d_rec, &n);
     if (rc == CGRT_OK) {
         *count = n;
         const uint64_t m = n < cap ? n : cap;

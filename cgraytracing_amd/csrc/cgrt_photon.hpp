@@ -96,6 +96,54 @@ __global__ void hp_gather_kernel(const double *__restrict__ rec, const unsigned 
     c[7] = 0;
     bucket_of[i] = (int)(keys[i] >> 44);
 }
+// ---- the same table for Hitpoints of a ray buffer (cgrt_ppm_session_create_rays).  Order contract: inside a bucket the
+// Hitpoints stand in the insertion order of a serial loop over texels, for each texel over its rays in ray-index order, for
+// each ray in emission order.  (bucket, texel, ray, seq) does not fit one 64-bit key, and the radix sort is stable: the
+// records are sorted by their label (ray << 4 | seq) first, then by (bucket << 32 | texel).  For rays in cgrt_camera_rays'
+// order without a pixel array (ray = sample * npix + texel) this is hp_keys_kernel's order.
+__device__ __forceinline__ unsigned long long ray_texel(const long long *__restrict__ pixel, unsigned long long ray, long long npix) {
+    return pixel ? (unsigned long long)pixel[ray] : ray % (unsigned long long)npix;  // (a ray with a Hitpoint has a texel >= 0)
+}
+__global__ void hp_ray_label_keys_kernel(const double *__restrict__ rec, long long n, unsigned long long *__restrict__ keys,
+                                         unsigned int *__restrict__ vals) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    keys[i] = (unsigned long long)rec[10 * i + 9];  // < 2^40
+    vals[i] = (unsigned int)i;
+}
+// vals: record indices in label order; keys out: (bucket << 32) | texel, in that order
+__global__ void hp_ray_bucket_keys_kernel(const double *__restrict__ rec, const unsigned int *__restrict__ vals, long long n, HashArgs ha,
+                                          const long long *__restrict__ pixel, long long npix, unsigned long long *__restrict__ keys) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double *q = rec + 10 * (long long)vals[i];
+    int ix, iy, iz;
+    ref_coord(q[3], q[4], q[5], ha.celllength, ix, iy, iz);
+    const unsigned long long b = ref_hash(ix, iy, iz, ha.hashsize);
+    keys[i] = (b << 32) | ray_texel(pixel, (unsigned long long)q[9] >> 4, npix);  // bucket < 2^20, texel < 2^31
+}
+// hp_gather_kernel for that order: hp[0] = the ray index, hp[1] = the emission index
+__global__ void hp_ray_gather_kernel(const double *__restrict__ rec, const unsigned long long *__restrict__ keys,
+                                     const unsigned int *__restrict__ vals, long long n, double r2_init, double *__restrict__ hp,
+                                     double *__restrict__ hps, int *__restrict__ bucket_of) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double *q = rec + 10 * (long long)vals[i];
+    double *o = hp + 16 * i;
+    const unsigned long long lab = (unsigned long long)q[9];
+    o[0] = (double)(lab >> 4);
+    o[1] = (double)(lab & 15ull);
+    for (int k = 0; k < 9; k++) o[2 + k] = q[k];
+    o[11] = 0; o[12] = 0; o[13] = 0;
+    o[14] = r2_init;
+    o[15] = 0;
+    double *c = hps + 8 * i;
+    for (int k = 0; k < 3; k++) c[k] = q[3 + k];
+    c[3] = r2_init;
+    for (int k = 0; k < 3; k++) c[4 + k] = q[6 + k];
+    c[7] = 0;
+    bucket_of[i] = (int)(keys[i] >> 32);
+}
 __global__ void bucket_start_kernel(const int *__restrict__ bucket_of, long long n, int hashsize, int *__restrict__ bstart) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b > hashsize) return;
@@ -495,6 +543,15 @@ __global__ void image_keys_kernel(const double *__restrict__ hp, long long nhp, 
     vals[i] = (unsigned int)i;
 }
 
+// image_keys_kernel for a ray session: the texel is the ray's
+__global__ void image_ray_keys_kernel(const double *__restrict__ hp, long long nhp, const long long *__restrict__ pixel, long long npix,
+                                      unsigned long long *__restrict__ keys, unsigned int *__restrict__ vals) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nhp) return;
+    keys[i] = (ray_texel(pixel, (unsigned long long)hp[16 * i], npix) << 32) | (unsigned long long)i;
+    vals[i] = (unsigned int)i;
+}
+
 int sort_pairs(GrowBuf &tmp, unsigned long long *kin, unsigned long long *kout, unsigned int *vin, unsigned int *vout, size_t n,
                int end_bit = 64, hipStream_t st = 0) {
     size_t tmp_bytes = 0;
@@ -649,15 +706,18 @@ extern "C" int cgrt_tonemap_rgb8(int device, const double *image, int width, int
 }
 
 // ---- the stages of render() main.cpp:169-258, shared by cgrt_ppm_render (one call) and a live cgrt_ppm_session ----------
-// table(): eye pass, the reference's table order, the per-pixel index.  photon_setup() + photons(last): photons
+// eye_grid() / eye_rays(): the Hitpoint records of a grid or of a ray buffer; table(): the reference's table order and the
+// per-pixel index over them.  photon_setup() + photons(last): photons
 // [done, last) in batches.  gather(): the image at the current photon count.  Photon i always draws from the keyed stream
 // (seed, i) and a hitpoint replays its events in photon order, so the state after photons [0, a) then [a, b) is the state
 // after [0, b): how the photons are split into calls and batches never shows in the result.
 struct cgrt_ppm_session {
     const cgrt_scene *s = nullptr;
-    cgrt_camera cam{};
-    cgrt_grid grid{};
     cgrt_photons ph{};
+    // the image the session gathers into, the gather's normaliser and the photons' depth limit: a grid session's grid.width,
+    // .rows, .spp, .max_depth; a ray session's cgrt_ray_pixels and rays->max_depth
+    int width = 0, rows = 0, spp = 1, max_depth = 0;
+    bool striped = false;  // grid session over block-cyclic rows: no rgb8
     bool lookahead = false;  // session: trace the next batch on the producer stream when a call ends
     size_t n = 0;            // hitpoints
     long long npix = 0;
@@ -691,32 +751,64 @@ struct cgrt_ppm_session {
         return b.alloc(bytes);
     }
     int64_t bytes() const { return dev_bytes + pp_bytes + (int64_t)main_tmp.cap + (int64_t)pp.tmp.cap; }
-    int table(const cgrt_scene *s_, const cgrt_camera *cam_, const cgrt_grid *grid_, const cgrt_photons *ph_);
+    int eye_grid(const cgrt_scene *s_, const cgrt_camera *cam, const cgrt_grid *grid, const cgrt_photons *ph_, DevBuf &rec);
+    int eye_rays(const cgrt_scene *s_, const cgrt_rays *rays, const cgrt_ray_pixels *px, const cgrt_photons *ph_, DevBuf &rec);
+    int table(DevBuf &rec, const int64_t *ray_pixel, bool rays);
     int photon_setup(bool session);
     int photons(long long last, bool keep_ahead);
     int gather(double *d_img, unsigned char *d_rgb8, hipStream_t st) const;
 };
 
-int cgrt_ppm_session::table(const cgrt_scene *s_, const cgrt_camera *cam_, const cgrt_grid *grid_, const cgrt_photons *ph_) {
-    s = s_; cam = *cam_; grid = *grid_; ph = *ph_;
+// ---- eye pass: hitpoint records, device resident (count first, then capture) ----
+int cgrt_ppm_session::eye_grid(const cgrt_scene *s_, const cgrt_camera *cam, const cgrt_grid *grid, const cgrt_photons *ph_, DevBuf &rec) {
+    s = s_; ph = *ph_;
+    width = grid->width; rows = grid->rows; spp = grid->spp; max_depth = grid->max_depth;
+    striped = grid->stripe_nranks > 1;
     Timer tm;
-    // ---- eye pass: hitpoint records, device resident (count first, then capture) ----
     tm.start();
     uint64_t nhp = 0;
-    int rc = hitpoints_device(s, &cam, &grid, 0, nullptr, &nhp);
+    int rc = hitpoints_device(s, cam, grid, 0, nullptr, &nhp);
     if (rc) return rc;
-    npix = (long long)grid.rows * grid.width;
+    npix = (long long)rows * width;
     n = (size_t)nhp;
     if (n >= (1ull << 31)) return fail(CGRT_ERR_LIMIT, "photon pass: more than 2^31 hitpoints");
-    DevBuf rec, bucket_of, k0, k1, v0, v1;
     if (n) {
         double *d_rec = nullptr;
-        rc = hitpoints_device(s, &cam, &grid, nhp, &d_rec, &nhp);
+        rc = hitpoints_device(s, cam, grid, nhp, &d_rec, &nhp);
         rec.p = d_rec;
         if (rc) return rc;
     }
     ms_eye = tm.stop();
-    // ---- the reference's table order: (bucket, insertion order); then the per-pixel index ----
+    return CGRT_OK;
+}
+int cgrt_ppm_session::eye_rays(const cgrt_scene *s_, const cgrt_rays *rays, const cgrt_ray_pixels *px, const cgrt_photons *ph_, DevBuf &rec) {
+    s = s_; ph = *ph_;
+    width = px->width; rows = px->rows; spp = px->spp; max_depth = rays->max_depth;
+    Timer tm;
+    tm.start();
+    uint64_t nhp = 0;
+    int rc = ray_hitpoints_device(s, rays, px->pixel, 0, nullptr, &nhp);
+    if (rc) return rc;
+    npix = (long long)rows * width;
+    n = (size_t)nhp;
+    if (n >= (1ull << 31)) return fail(CGRT_ERR_LIMIT, "photon pass: more than 2^31 hitpoints");
+    if (n) {
+        double *d_rec = nullptr;
+        rc = ray_hitpoints_device(s, rays, px->pixel, nhp, &d_rec, &nhp);
+        rec.p = d_rec;
+        if (rc) return rc;
+    }
+    ms_eye = tm.stop();
+    return CGRT_OK;
+}
+
+// ---- the reference's table order: (bucket, insertion order); then the per-pixel index.  rays: the records' labels are
+// (ray << 4 | seq) and ray_pixel (DEVICE, or null) maps rays to texels ----
+int cgrt_ppm_session::table(DevBuf &rec, const int64_t *ray_pixel, bool rays) {
+    Timer tm;
+    int rc = CGRT_OK;
+    DevBuf bucket_of, k0, k1, v0, v1;
+    const long long *pixel = reinterpret_cast<const long long *>(ray_pixel);
     tm.start();
     HIP_TRY(take(hp, n * 16 * sizeof(double)));
     HIP_TRY(take(hps, n * 8 * sizeof(double)));
@@ -731,14 +823,29 @@ int cgrt_ppm_session::table(const cgrt_scene *s_, const cgrt_camera *cam_, const
     ha.celllength = 70.0 / std::ceil(70.0 / r0);  // hash.h:25-26
     const int T = 256;
     const unsigned nb = (unsigned)((n + T - 1) / T);
-    if (n) {
-        hipLaunchKernelGGL(hp_keys_kernel, dim3(nb), dim3(T), 0, 0, rec.as<double>(), (long long)n, ha, (int)npix, grid.spp,
+    if (n && rays) {
+        hipLaunchKernelGGL(hp_ray_label_keys_kernel, dim3(nb), dim3(T), 0, 0, rec.as<double>(), (long long)n, k0.as<unsigned long long>(),
+                           v0.as<unsigned int>());
+        rc = sort_pairs(main_tmp, k0.as<unsigned long long>(), k1.as<unsigned long long>(), v0.as<unsigned int>(), v1.as<unsigned int>(), n, 40);
+        if (rc) return rc;
+        hipLaunchKernelGGL(hp_ray_bucket_keys_kernel, dim3(nb), dim3(T), 0, 0, rec.as<double>(), v1.as<unsigned int>(), (long long)n, ha,
+                           pixel, npix, k0.as<unsigned long long>());
+        rc = sort_pairs(main_tmp, k0.as<unsigned long long>(), k1.as<unsigned long long>(), v1.as<unsigned int>(), v0.as<unsigned int>(), n, 52);
+        if (rc) return rc;
+        hipLaunchKernelGGL(hp_ray_gather_kernel, dim3(nb), dim3(T), 0, 0, rec.as<double>(), k1.as<unsigned long long>(),
+                           v0.as<unsigned int>(), (long long)n, r0 * r0, hp.as<double>(), hps.as<double>(), bucket_of.as<int>());
+        hipLaunchKernelGGL(image_ray_keys_kernel, dim3(nb), dim3(T), 0, 0, hp.as<double>(), (long long)n, pixel, npix,
+                           k0.as<unsigned long long>(), v0.as<unsigned int>());
+        rc = sort_pairs(main_tmp, k0.as<unsigned long long>(), k1.as<unsigned long long>(), v0.as<unsigned int>(), v1.as<unsigned int>(), n);
+        if (rc) return rc;
+    } else if (n) {
+        hipLaunchKernelGGL(hp_keys_kernel, dim3(nb), dim3(T), 0, 0, rec.as<double>(), (long long)n, ha, (int)npix, spp,
                            k0.as<unsigned long long>(), v0.as<unsigned int>());
         rc = sort_pairs(main_tmp, k0.as<unsigned long long>(), k1.as<unsigned long long>(), v0.as<unsigned int>(), v1.as<unsigned int>(), n);
         if (rc) return rc;
         hipLaunchKernelGGL(hp_gather_kernel, dim3(nb), dim3(T), 0, 0, rec.as<double>(), k1.as<unsigned long long>(),
                            v1.as<unsigned int>(), (long long)n, r0 * r0, hp.as<double>(), hps.as<double>(), bucket_of.as<int>());
-        hipLaunchKernelGGL(image_keys_kernel, dim3(nb), dim3(T), 0, 0, hp.as<double>(), (long long)n, grid.spp,
+        hipLaunchKernelGGL(image_keys_kernel, dim3(nb), dim3(T), 0, 0, hp.as<double>(), (long long)n, spp,
                            k0.as<unsigned long long>(), v0.as<unsigned int>());
         rc = sort_pairs(main_tmp, k0.as<unsigned long long>(), k1.as<unsigned long long>(), v0.as<unsigned int>(), v1.as<unsigned int>(), n);
         if (rc) return rc;
@@ -800,7 +907,7 @@ int cgrt_ppm_session::photons(long long last, bool keep_ahead) {
         pa.jitter = ph.jitter; pa.power = ph.power; pa.alpha = ph.alpha;
         pa.first = first;
         pa.count = (int)((end - first < batch_now) ? (end - first) : batch_now);
-        pa.max_depth = grid.max_depth;
+        pa.max_depth = max_depth;
         pa.seed = ph.seed;
         return pa;
     };
@@ -880,7 +987,7 @@ int cgrt_ppm_session::photons(long long last, bool keep_ahead) {
 int cgrt_ppm_session::gather(double *d_img, unsigned char *d_rgb8, hipStream_t st) const {
     const int T = 256;
     hipLaunchKernelGGL(ppm_gather_kernel, dim3((unsigned)((npix + T - 1) / T)), dim3(T), 0, st, static_cast<const unsigned int *>(pix_start.p),
-                       static_cast<const unsigned int *>(order.p), static_cast<const double *>(hp.p), (double)done * grid.spp, npix, grid.width, grid.rows,
+                       static_cast<const unsigned int *>(order.p), static_cast<const double *>(hp.p), (double)done * spp, npix, width, rows,
                        d_img, d_rgb8);
     HIP_TRY(hipGetLastError());
     return CGRT_OK;
@@ -903,10 +1010,14 @@ extern "C" int cgrt_ppm_render(const cgrt_scene *s, const cgrt_camera *cam, cons
         return fail(CGRT_ERR_UNSUPPORTED, "photon pass: rgb8 needs contiguous rows; tone-map the assembled frame (cgrt_tonemap_rgb8)");
     ON_DEVICE(s->device);
     cgrt_ppm_session run;
-    rc = run.table(s, cam, grid, ph);
-    out->ms_eye = run.ms_eye;
-    out->ms_table = run.ms_table;
-    if (rc) return rc;
+    {
+        DevBuf rec;
+        rc = run.eye_grid(s, cam, grid, ph, rec);
+        out->ms_eye = run.ms_eye;
+        if (rc == CGRT_OK) rc = run.table(rec, nullptr, false);
+        out->ms_table = run.ms_table;
+        if (rc) return rc;
+    }
     // ---- photons, in batches ----
     Timer tm;
     tm.start();
@@ -937,6 +1048,16 @@ extern "C" int cgrt_ppm_render(const cgrt_scene *s, const cgrt_camera *cam, cons
 }
 
 // ---- resumable photon mapping: the state above, kept between calls -------------------------------------------------
+// what both creators do behind the table: the photon buffers and ph.nphotons photons
+static int session_first_photons(cgrt_ppm_session &p) {
+    Timer tm;
+    tm.start();
+    int rc = p.photon_setup(true);
+    if (rc == CGRT_OK) rc = p.photons(p.ph.nphotons, p.lookahead);
+    p.ms_last_add = tm.stop();
+    p.ms_photons = p.ms_last_add;
+    return rc;
+}
 extern "C" int cgrt_ppm_session_create(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid,
                                        const cgrt_photons *ph, int flags, cgrt_ppm_session **out) {
     if (!out) return fail(CGRT_ERR_INVALID, "null argument");
@@ -952,14 +1073,40 @@ extern "C" int cgrt_ppm_session_create(const cgrt_scene *s, const cgrt_camera *c
     p->lookahead = !(flags & CGRT_PPM_SESSION_NO_LOOKAHEAD);
     HIP_TRY(hipEventCreate(&p->img_a));
     HIP_TRY(hipEventCreate(&p->img_b));
-    if ((rc = p->table(s, cam, grid, ph))) return rc;
-    Timer tm;
-    tm.start();
-    rc = p->photon_setup(true);
-    if (rc == CGRT_OK) rc = p->photons(ph->nphotons, p->lookahead);
-    p->ms_last_add = tm.stop();
-    p->ms_photons = p->ms_last_add;
+    {
+        DevBuf rec;
+        if ((rc = p->eye_grid(s, cam, grid, ph, rec))) return rc;
+        if ((rc = p->table(rec, nullptr, false))) return rc;
+    }
+    if ((rc = session_first_photons(*p))) return rc;
+    *out = p.release();
+    return CGRT_OK;
+}
+
+extern "C" int cgrt_ppm_session_create_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_pixels *px,
+                                            const cgrt_photons *ph, int flags, cgrt_ppm_session **out) {
+    if (!out) return fail(CGRT_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!s || !rays || !px || !ph) return fail(CGRT_ERR_INVALID, "null argument");
+    if (px->width <= 0 || px->rows <= 0 || px->spp <= 0) return fail(CGRT_ERR_INVALID, "ray pixels: width, rows and spp must be positive");
+    if ((long long)px->width * px->rows >= (1ll << 31)) return fail(CGRT_ERR_LIMIT, "ray pixels: 2^31 texels or more");
+    int rc = check_photons(ph);
     if (rc) return rc;
+    if (flags & ~CGRT_PPM_SESSION_NO_LOOKAHEAD) return fail(CGRT_ERR_INVALID, "unknown session flags");
+    if ((rc = check_capture_rays(s, rays))) return rc;  // (the last of the checks: it is the one that looks at the scene's state)
+    ON_DEVICE(s->device);
+    std::unique_ptr<cgrt_ppm_session> p(new (std::nothrow) cgrt_ppm_session());
+    if (!p) return fail(CGRT_ERR_LIMIT, "out of host memory");
+    p->lookahead = !(flags & CGRT_PPM_SESSION_NO_LOOKAHEAD);
+    HIP_TRY(hipEventCreate(&p->img_a));
+    HIP_TRY(hipEventCreate(&p->img_b));
+    {
+        DevBuf rec;
+        if ((rc = p->eye_rays(s, rays, px, ph, rec))) return rc;
+        if ((rc = p->table(rec, px->pixel, true))) return rc;
+        HIP_TRY(hipDeviceSynchronize());  // px->pixel and the records are read before the call returns
+    }
+    if ((rc = session_first_photons(*p))) return rc;
     *out = p.release();
     return CGRT_OK;
 }
@@ -986,7 +1133,7 @@ extern "C" int cgrt_ppm_session_add_photons(cgrt_ppm_session *p, int64_t count) 
 static int session_image_args(const cgrt_ppm_session *p, const uint8_t *rgb8) {
     if (!p) return fail(CGRT_ERR_INVALID, "null session");
     if (p->done == 0) return fail(CGRT_ERR_INVALID, "photon session: no photon yet (the image would be flux / (PI r2 0))");
-    if (rgb8 && p->grid.stripe_nranks > 1)
+    if (rgb8 && p->striped)
         return fail(CGRT_ERR_UNSUPPORTED, "photon session: rgb8 needs contiguous rows; tone-map the assembled frame (cgrt_tonemap_rgb8)");
     return CGRT_OK;
 }

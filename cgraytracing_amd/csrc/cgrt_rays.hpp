@@ -18,6 +18,15 @@ struct RayParams {
     double *hit_t, *hit_normal;
     unsigned int *queue;  // head of the block queue (block = 64 consecutive rays), zeroed before the launch
 };
+// Where capture_rays_kernel puts the Hitpoints (cgrt_trace_rays_hitpoints, the eye stage of cgrt_ppm_session_create_rays):
+// records of 10 doubles {hf, P, n, label} as HitpointSink's (cgrt_eye.hpp), label = (ray index << 4) | position of the
+// Hitpoint in the ray tree's emission order.  *count is advanced for every Hitpoint, records beyond cap are dropped.
+struct RaySink {
+    double *rec;
+    unsigned long long *count;
+    unsigned long long cap;
+    const long long *pixel;  // nullptr, or per ray: a ray whose entry is negative belongs to no texel and is not traced
+};
 
 // One step of trace() behind the scene walk (main.cpp:64-157) for a ray that hit object hit.id: the expressions of
 // trace_grid_body (cgrt_eye.hpp), in its order -- that order is the parity contract (fp64, no contraction, sqrt_cr,
@@ -33,9 +42,12 @@ enum RayStep {
     RAY_CONTINUE = 2, // `r` is the reflected child
     RAY_SPLIT = 3     // `r` is the reflected child and `pe` the refracted one, to be traced after r's subtree
 };
+struct RaySurface {  // where the step happened: what a Hitpoint stores beside its value (main.cpp:89-90)
+    V3 P, n;         // o + d * t, and the normal after the flip of main.cpp:73-76
+};
 template <bool GLASS, bool SPILL>
 __device__ __forceinline__ RayStep shade_step(const DeviceScene &sc, const ObjRec *__restrict__ lobjs, const SceneHit &hit,
-                                              RayState &r, V3 &hf, Pending &pe) {
+                                              RayState &r, V3 &hf, Pending &pe, RaySurface &at) {
     const ObjMat ob = load_mat<SPILL>(lobjs, sc.n_lds, sc.objs, hit.id);
     const V3 o = r.o, d = r.d;
     const V3 P = o + d * hit.t;  // main.cpp:68
@@ -54,6 +66,8 @@ __device__ __forceinline__ RayStep shade_step(const DeviceScene &sc, const ObjRe
     const double refl = ob.refl, transp = ob.transp;
     if (refl < kEps && transp < kEps) {
         hf = mulv(f, r.adj);  // main.cpp:85-100
+        at.P = P;
+        at.n = n;
         return RAY_HITPOINT;
     }
     if (!(r.depth_left > 1)) return RAY_END;
@@ -107,17 +121,16 @@ __device__ __forceinline__ RayStep shade_step(const DeviceScene &sc, const ObjRe
 // order (reflect subtree, then refract), so its result does not depend on which lane or wave traced it, nor on what the other
 // lanes were doing.
 // FIRST: nearest-hit query -- one scene walk per ray, no shading, no pending-ray code.
+// CAPTURE: every Hitpoint is also appended to `sink` (capture_rays_kernel below); false compiles all of that away.
 // LDS carve-up as trace_grid_body's: [ pending-ray levels (GLASS) | objs | staging record per wave (SPILL) | BezLds per wave (BEZ)
 // | node cache (TREES) | wide-walk stack (TREES without GLASS or BEZ) ]; rays_lds() in cgrt_hip.hip is its size.
-template <bool TREES, bool BEZ, bool GLASS, bool SPH, bool STATS, bool SPILL, bool FIRST, int NT>
-__global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) void trace_rays_kernel(DeviceScene sc, RayParams rp,
-                                                                                               unsigned long long *__restrict__ counters) {
+template <bool TREES, bool BEZ, bool GLASS, bool SPH, bool STATS, bool SPILL, bool FIRST, int NT, bool CAPTURE>
+__device__ __forceinline__ void trace_rays_body(const DeviceScene &sc, const RayParams &rp, unsigned long long *wc, const RaySink &sink) {
     static_assert(NT == 256 || NT == 64, "workgroup = 4 waves or 1 wave");
     static_assert(!(FIRST && GLASS), "a nearest-hit query has no pending rays");
+    static_assert(!(CAPTURE && (FIRST || STATS)), "Hitpoints come from the full trace; the capture counts nothing");
     constexpr size_t level_bytes = (size_t)NT * (kPendDoubles * sizeof(double) + sizeof(uint32_t));
     constexpr size_t stack_bytes = (size_t)kLdsLevels * level_bytes;
-    __shared__ unsigned long long wg_cnt[CGRT_NCOUNTERS];
-    unsigned long long *wc = wg_counters_begin(wg_cnt, counters);
 
     extern __shared__ __align__(16) unsigned char lds_raw[];
     ObjRec *lobjs = reinterpret_cast<ObjRec *>(lds_raw + (GLASS ? stack_bytes : 0));
@@ -210,8 +223,10 @@ __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) voi
             if (want && u < ray_end) {
                 r.o = ld3(rp.org + 3 * u);
                 r.d = ld3(rp.dir + 3 * u);
-                if (r.d.x == 0.0 && r.d.y == 0.0 && r.d.z == 0.0) {
-                    // not a ray (cgrt_camera_rays' padding rows): the results of a miss, nothing counted
+                bool skip = r.d.x == 0.0 && r.d.y == 0.0 && r.d.z == 0.0;
+                if (CAPTURE && sink.pixel) skip = skip || sink.pixel[u] < 0;
+                if (skip) {
+                    // not a ray (cgrt_camera_rays' padding rows; a ray without a texel): the results of a miss, nothing counted
                     if (!FIRST && rp.acc) {
                         double *q = rp.acc + 3 * u;
                         q[0] = 0.0;
@@ -269,8 +284,26 @@ __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) voi
                 if (hit.id >= 0) {
                     V3 hf;
                     Pending pe;
-                    const RayStep step = shade_step<GLASS, SPILL>(sc, lobjs, hit, r, hf, pe);
+                    RaySurface at;
+                    const RayStep step = shade_step<GLASS, SPILL>(sc, lobjs, hit, r, hf, pe, at);
                     if (step == RAY_HITPOINT) {
+                        if (CAPTURE) {
+                            // one atomic per wave, as trace_grid_body's capture: the lanes that are at a Hitpoint together take
+                            // consecutive places behind the count their first lane fetched
+                            const unsigned long long here = __ballot(true);
+                            const int lead = (int)__ffsll((long long)here) - 1;
+                            unsigned long long base = 0ull;
+                            if (lane == lead) base = atomicAdd(sink.count, (unsigned long long)__popcll(here));
+                            base = (unsigned long long)__shfl((long long)base, lead);
+                            const unsigned long long k = base + (unsigned long long)__popcll(here & lanes_below);
+                            if (k < sink.cap) {
+                                double *q = sink.rec + 10 * k;
+                                q[0] = hf.x; q[1] = hf.y; q[2] = hf.z;
+                                q[3] = at.P.x; q[4] = at.P.y; q[5] = at.P.z;
+                                q[6] = at.n.x; q[7] = at.n.y; q[8] = at.n.z;
+                                q[9] = (double)(((unsigned long long)my_ray << 4) | (unsigned long long)ray_hits);  // ray < 2^36
+                            }
+                        }
                         acc_r += hf.x;
                         acc_g += hf.y;
                         acc_b += hf.z;
@@ -354,7 +387,21 @@ __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) voi
             }
         }
     }
+}
+
+template <bool TREES, bool BEZ, bool GLASS, bool SPH, bool STATS, bool SPILL, bool FIRST, int NT>
+__global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) void trace_rays_kernel(DeviceScene sc, RayParams rp,
+                                                                                               unsigned long long *__restrict__ counters) {
+    __shared__ unsigned long long wg_cnt[CGRT_NCOUNTERS];
+    unsigned long long *wc = wg_counters_begin(wg_cnt, counters);
+    trace_rays_body<TREES, BEZ, GLASS, SPH, STATS, SPILL, FIRST, NT, false>(sc, rp, wc, RaySink{nullptr, nullptr, 0ull, nullptr});
     wg_counters_end(wg_cnt, counters);
+}
+// The capture form: the full trace of every ray that has a texel, its Hitpoints appended to `sink`; rp's result pointers are
+// null and nothing is counted.  Same LDS carve-up and occupancy as trace_rays_kernel<..., STATS=false, FIRST=false, NT>.
+template <bool TREES, bool BEZ, bool GLASS, bool SPH, bool SPILL, int NT>
+__global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) void capture_rays_kernel(DeviceScene sc, RayParams rp, RaySink sink) {
+    trace_rays_body<TREES, BEZ, GLASS, SPH, false, SPILL, false, NT, true>(sc, rp, nullptr, sink);
 }
 
 // hit_normal3 of rays whose nearest object is an OPAQUE mesh walked in its 4-wide form: the scene walk prunes such a mesh by

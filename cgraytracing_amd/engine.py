@@ -386,6 +386,79 @@ class Scene:
         self._sessions.add(ses)
         return ses
 
+    def _ray_tensors(self, what, org, dirs, keys, pixel=None):
+        """The argument checks of trace_rays for the ray-buffer calls; returns n."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        for name, t in (("org", org), ("dirs", dirs)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == 3 and
+                    t.is_contiguous() and t.device == dev):
+                raise ValueError("%s: %s must be a contiguous float64 [n,3] tensor on %s" % (what, name, dev))
+        n = org.shape[0]
+        if dirs.shape[0] != n:
+            raise ValueError("%s: org and dirs differ in length" % what)
+        for name, t in (("keys", keys), ("pixel", pixel)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.int64 and tuple(t.shape) == (n,) and
+                                      t.is_contiguous() and t.device == dev):
+                raise ValueError("%s: %s must be a contiguous int64 [n] tensor on %s" % (what, name, dev))
+        return n
+
+    def trace_rays_hitpoints(self, org, dirs, keys=None, max_depth=5, seed=12345, first_index=0, cap=None):
+        """cgrt_trace_rays_hitpoints: the Hitpoints of the rays' trees (torch tensors as for trace_rays), unordered:
+        dict(hp [m,9] = f, pos, normal (after the flip of main.cpp:73-76); ray [m]; seq [m] (position in the ray tree's
+        emission order); count (Hitpoints produced; m = min(count, cap))).  Synchronous."""
+        if not self.stats()["committed"]:
+            check(self._L.cgrt_trace_rays_hitpoints(self._h, C.byref(_capi.Rays(0, None, None, None, 0, 0, max_depth, 0)), None, 0,
+                                                    C.byref(C.c_uint64(0))))
+        n = self._ray_tensors("trace_rays_hitpoints", org, dirs, keys)
+        cap = int(cap if cap is not None else n * 16)
+        rec = np.zeros((max(cap, 1), 10), np.float64)
+        cnt = C.c_uint64(0)
+        r = _capi.Rays(n, org.data_ptr(), dirs.data_ptr(), keys.data_ptr() if keys is not None else None, first_index, seed,
+                       max_depth, 0)
+        check(self._L.cgrt_trace_rays_hitpoints(self._h, C.byref(r), rec.ctypes.data, cap, C.byref(cnt)))
+        m = min(int(cnt.value), cap)
+        lab = rec[:m, 9].astype(np.int64)
+        return dict(hp=rec[:m, :9].copy(), ray=lab >> 4, seq=lab & 15, count=int(cnt.value))
+
+    def ppm_session_rays(self, org, dirs, keys=None, *, width, rows, spp=1, pixel=None, max_depth=5, seed=12345, first_index=0,
+                         nphotons=0, photon_seed=777, hashsize=1000001, light=(0.0, 19.999, 20.0), jitter=2.0, power=700.0,
+                         alpha=0.7, batch=0, initial_radius=0.0, pair_cap=0, lookahead=True):
+        """A live photon-mapping render over caller-supplied rays (cgrt_ppm_session_create_rays): org, dirs, keys as for
+        trace_rays; the session gathers into a [rows, width, 3] image, ray i into texel pixel[i] (int64 [n] on the scene's
+        device; negative: the ray is not traced), or i % (width * rows) without `pixel` -- camera_rays' order.  spp is the
+        gather's normaliser (rays per texel).  Returns a PpmSession; its hitpoints()[:, 0] is the ray index.  For
+        camera_rays(width, rows, spp, ...) without `pixel` the session equals ppm_session on that grid bit for bit."""
+        if not self.stats()["committed"]:  # the library's own answer (no tensor is looked at)
+            check(self._L.cgrt_ppm_session_create_rays(self._h, C.byref(_capi.Rays(0, None, None, None, 0, 0, max_depth, 0)),
+                                                       C.byref(_capi.RayPixels(width, rows, spp, 0, None)),
+                                                       C.byref(_capi.Photons(_d3(light), jitter, power, alpha, 0, hashsize, batch,
+                                                                             photon_seed, initial_radius, pair_cap)),
+                                                       0, C.byref(C.c_void_p())))
+        n = self._ray_tensors("ppm_session_rays", org, dirs, keys, pixel)
+        r = _capi.Rays(n, org.data_ptr(), dirs.data_ptr(), keys.data_ptr() if keys is not None else None, first_index, seed,
+                       max_depth, 0)
+        px = _capi.RayPixels(width, rows, spp, 0, pixel.data_ptr() if pixel is not None else None)
+        ph = _capi.Photons(_d3(light), jitter, power, alpha, nphotons, hashsize, batch, photon_seed, initial_radius, pair_cap)
+        h = C.c_void_p()
+        import torch
+
+        torch.cuda.current_stream(org.device).synchronize()  # the session's eye stage runs on the null stream
+        check(self._L.cgrt_ppm_session_create_rays(self._h, C.byref(r), C.byref(px), C.byref(ph),
+                                                   0 if lookahead else _capi.PPM_SESSION_NO_LOOKAHEAD, C.byref(h)))
+        ses = PpmSession(self, h, width, rows, spp)
+        self._sessions.add(ses)
+        return ses
+
+    def capture_variant(self, max_depth=5):
+        """Name of the capture_rays_kernel instantiation trace_rays_hitpoints / ppm_session_rays launch (cgrt_trace_rays_variant
+        with CGRT_RAYS_HITPOINTS)."""
+        r = _capi.Rays(1, None, None, None, 0, 0, max_depth, _capi.RAYS_HITPOINTS)
+        buf = C.create_string_buffer(160)
+        check(self._L.cgrt_trace_rays_variant(self._h, C.byref(r), None, buf, len(buf)))
+        return buf.value.decode()
+
     def photon_events(self, first, count, max_depth=5, photon_seed=777, light=(0.0, 19.999, 20.0), jitter=2.0,
                       power=700.0):
         """Verification probe: diffuse hits of photons [first, first+count): [n,10] = photon, P, n, flux in serial

@@ -17,7 +17,8 @@
  * not thread-safe; distinct scenes may be used concurrently from different host threads / devices.
  * Threading: launches on ONE scene handle must be ordered by the caller (same stream, or events between streams) --
  * a handle owns device scratch that consecutive launches reuse (CGRT_GRID_SPLIT_SAMPLES chunk sums; the schedule of a
- * cost-ordered frame; the queue counter of cgrt_trace_rays, which is one of these launches).
+ * cost-ordered frame; the queue counter of cgrt_trace_rays, cgrt_trace_rays_hitpoints and cgrt_ppm_session_create_rays, which
+ * are such launches).
  * All geometry is IEEE double, like the reference (Vec3 = 3 x double, vec3.h:11-30).
  */
 #ifndef CGRT_H
@@ -34,7 +35,8 @@ extern "C" {
                             cgrt_surface_colors, cgrt_trace_grid_variant; 111: cgrt_scene_wide_dump;
                             112: cgrt_scene_set_build, cgrt_scene_build_info (row f3: structures built on the device);
                             added since without a new number, like the cgrt_ppm_session_* calls: cgrt_trace_rays,
-                            cgrt_trace_rays_host, cgrt_trace_rays_variant, cgrt_camera_rays, cgrt_camera_rays_host (caller-supplied rays) */
+                            cgrt_trace_rays_host, cgrt_trace_rays_variant, cgrt_camera_rays, cgrt_camera_rays_host (caller-supplied rays);
+                            cgrt_trace_rays_hitpoints, cgrt_ppm_session_create_rays (photon mapping of caller-supplied rays) */
 
 enum {
     CGRT_OK = 0,
@@ -241,8 +243,11 @@ typedef struct cgrt_rays {
 } cgrt_rays;
 enum {
     CGRT_RAYS_STATS = 1,       /* also count tree-node and triangle tests, like CGRT_GRID_STATS                              */
-    CGRT_RAYS_NO_SIGN_PASS = 2 /* hit_normal3 of an opaque mesh: skip the pass that gives it the reference's sign (below); the
+    CGRT_RAYS_NO_SIGN_PASS = 2,/* hit_normal3 of an opaque mesh: skip the pass that gives it the reference's sign (below); the
                                   vector is then right up to its sign, and the call costs one unpruned mesh walk per ray less */
+    CGRT_RAYS_HITPOINTS = 4    /* cgrt_trace_rays_variant only: name the launch of the Hitpoint capture (cgrt_trace_rays_hitpoints,
+                                  the eye stage of cgrt_ppm_session_create_rays) instead of cgrt_trace_rays'; `out` is then not
+                                  looked at and may be NULL.  Ignored by the other calls, as CGRT_GRID_HITPOINTS is              */
 };
 
 typedef struct cgrt_ray_results {   /* every pointer may be NULL: only the arrays asked for are written */
@@ -305,6 +310,14 @@ int cgrt_trace_grid_host(const cgrt_scene *s, const cgrt_camera *cam, const cgrt
  * would consume and what parity tests compare with the reference's own records. */
 int cgrt_trace_grid_hitpoints(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, double *hp10,
                               uint64_t cap, uint64_t *count);
+
+/* The same hand-off for caller-supplied rays: the Hitpoints of every ray tree of `rays` (DEVICE pointers, as for
+ * cgrt_trace_rays; max_depth always counts), up to `cap` records of 10 doubles {f(3), pos(3), normal(3), label} into the HOST
+ * buffer hp10, in no particular order; normal is the one AFTER the flip of main.cpp:73-76, as the grid form stores it;
+ * label = (ray index << 4) | position of the Hitpoint in the ray tree's emission order.  *count = Hitpoints produced (the
+ * excess over cap was dropped).  The sum of a ray's f in emission order is cgrt_ray_results.acc3 of that ray, bit for bit.
+ * CGRT_RAYS_STATS / CGRT_RAYS_NO_SIGN_PASS are ignored.  Runs on the null stream and synchronises; a launch on the scene handle. */
+int cgrt_trace_rays_hitpoints(const cgrt_scene *s, const cgrt_rays *rays, double *hp10, uint64_t cap, uint64_t *count);
 
 /* ---- row f1 of SURVEY.md section 8: the photon pass and final gather, render() main.cpp:223-258 ----------------
  * Constants of the reference as fields.  The reference races eight OpenMP threads over time-seeded rand(); what is
@@ -379,6 +392,27 @@ enum {
  * life.  A grid without hitpoints is valid (its image is zero). */
 int cgrt_ppm_session_create(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, const cgrt_photons *ph,
                             int flags, cgrt_ppm_session **out);
+
+/* A session whose Hitpoints come from caller-supplied rays (any camera; probe rays) instead of the grid's own.  The rays
+ * are bound to the image the session gathers into by */
+typedef struct cgrt_ray_pixels {
+    int32_t width, rows;   /* the image the session gathers into: npix = width * rows texels (< 2^31), row 0 = bottom, as
+                              cgrt_ppm_result.image; rgb8 flips rows with these                                            */
+    int32_t spp;           /* normaliser of the final gather: flux / (PI * r2 * nphotons * spp), main.cpp:256 (>= 1)         */
+    int32_t pad_;
+    const int64_t *pixel;  /* [n] DEVICE, or NULL.  Texel of ray i in [0, npix); -1 (any negative value): the ray belongs to
+                              no texel and is not traced.  NULL: ray i belongs to texel i % npix -- cgrt_camera_rays' ray order */
+} cgrt_ray_pixels;
+/* Order contract: inside a hash bucket the Hitpoints stand in the insertion order of a serial loop over texels, for each
+ * texel over its rays in ray-index order, for each ray in emission order.  For rays in cgrt_camera_rays' order with pixel ==
+ * NULL that is the reference's pixel-major, then sample, then emission order: such a session is cgrt_ppm_session_create's on
+ * the same grid bit for bit -- image, rgb8, hitpoints, table order -- except that hp16[0] of a ray session is the RAY INDEX
+ * (a grid session's is pixel*spp + sample).  The photons' depth limit is rays->max_depth.  A ray with dir = (0,0,0) or
+ * without a texel is not traced.  rays' pointers and px->pixel are DEVICE pointers on the scene's device, read before the call
+ * returns; CGRT_RAYS_STATS / CGRT_RAYS_NO_SIGN_PASS are ignored.  Every cgrt_ppm_session_* call works on the session as on a
+ * grid session's.  The eye stage is a launch on the scene handle (Threading above).  2^31 Hitpoints or more: CGRT_ERR_LIMIT. */
+int cgrt_ppm_session_create_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_pixels *px,
+                                 const cgrt_photons *ph, int flags, cgrt_ppm_session **out);
 /* Waits for anything in flight, then frees the session.  NULL is ignored. */
 void cgrt_ppm_session_destroy(cgrt_ppm_session *p);
 /* Traces photons [done, done + count) and applies them; returns when they are applied.  count >= 0. */

@@ -456,16 +456,20 @@ class PpmSession {
         g.spp_total = rp.num_of_samples;
         g.max_depth = rp.max_depth;
         g.seed = rp.seed;
-        cgrt_photons ph{};
-        pp.lightorg.get(ph.light);
-        ph.jitter = pp.jitter;
-        ph.power = pp.power;
-        ph.alpha = pp.alpha;
-        ph.nphotons = 0;
-        ph.hashsize = pp.hashsize;
-        ph.seed = pp.seed;
-        ph.initial_radius = pp.initial_radius;
+        const cgrt_photons ph = photons(pp);
         check(cgrt_ppm_session_create(sb_.scene, &cam, &g, &ph, lookahead ? 0 : CGRT_PPM_SESSION_NO_LOOKAHEAD, &session_));
+    }
+    // The same live render over caller-supplied rays (cgrt_ppm_session_create_rays): any camera, or probe rays.  rays' arrays
+    // and px.pixel are DEVICE pointers on device `device`, read before the constructor returns; px names the image that
+    // image() fills (px.width x px.rows, row 0 = bottom).  For cgrt_camera_rays' rays of a grid and px.pixel == nullptr the
+    // session is the grid constructor's, bit for bit.
+    PpmSession(const std::vector<Object *> &objs, const cgrt_rays &rays, const cgrt_ray_pixels &px, const PhotonParams &pp,
+               int device = 0, bool lookahead = true)
+        : width_(px.width), height_(px.rows), session_(nullptr) {
+        for (const Object *o : objs) o->add_to(sb_);
+        check(cgrt_scene_commit(sb_.scene, device));
+        const cgrt_photons ph = photons(pp);
+        check(cgrt_ppm_session_create_rays(sb_.scene, &rays, &px, &ph, lookahead ? 0 : CGRT_PPM_SESSION_NO_LOOKAHEAD, &session_));
     }
     ~PpmSession() { cgrt_ppm_session_destroy(session_); }  // before sb_ destroys the scene
     PpmSession(const PpmSession &) = delete;
@@ -487,6 +491,18 @@ class PpmSession {
     }
 
   private:
+    static cgrt_photons photons(const PhotonParams &pp) {  // a session starts without photons
+        cgrt_photons ph{};
+        pp.lightorg.get(ph.light);
+        ph.jitter = pp.jitter;
+        ph.power = pp.power;
+        ph.alpha = pp.alpha;
+        ph.nphotons = 0;
+        ph.hashsize = pp.hashsize;
+        ph.seed = pp.seed;
+        ph.initial_radius = pp.initial_radius;
+        return ph;
+    }
     int width_, height_;
     SceneBuilder sb_;
     cgrt_ppm_session *session_;
