@@ -576,8 +576,16 @@ __global__ __launch_bounds__(NT, BEZ ? kBezWaves : ((TREES && !HFONLY) ? kTreeWa
                                                              HitpointSink hps = HitpointSink{nullptr, nullptr, 0}) {
     __shared__ unsigned long long wg_cnt[CGRT_NCOUNTERS];
     unsigned long long *wc = wg_counters_begin(wg_cnt, counters);
-    trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY>(sc, g, rgb, nhit_out, wc, hps, (int)blockIdx.x,
-                                                                                       (int)gridDim.x);
+    // tile_order: the workgroup's tile comes from tile_order_kernel's list (the body's tile-queue entry: a literal tile number)
+    int tile_block = (int)blockIdx.x, tile_grid = (int)gridDim.x;
+    if (g.tile_order) {
+        tile_block = (int)load_uniform(g.border + blockIdx.x);
+        tile_grid = -1;
+#ifdef CGRT_TILE_ORDER_PRIO  // EXPERIMENT (make exp): issue priority for the workgroups of classes 0-2, for the whole tile
+        if (blockIdx.x < load_uniform(g.plan + 3)) __builtin_amdgcn_s_setprio(3);
+#endif
+    }
+    trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid);
     wg_counters_end(wg_cnt, counters);
 }
 // ... or the scheduled form: the first g.heavy_blocks workgroups serve the heavy tiles' unit queue, the others are the tile
@@ -675,45 +683,56 @@ __global__ void finalize_chunks_kernel(GridParams g, float *__restrict__ rgb, ui
 // deviation over its depth range.  A mesh is bounded by its cover spheres (DeviceScene::cover: up to 64 spheres over
 // median-split groups of its triangles -- a long thin mesh fills little of one sphere around all of it).  Anything doubtful
 // (object behind or around the camera, rows beyond the image) is FULL.
+// The test itself, shared by classify_kernel and tile_order_kernel.  pixel_dir: the pinhole direction of pixel (w, local row j).
+__device__ __forceinline__ V3 pixel_dir(const GridParams &g, V3 cam, int w, int j) {
+    const int h = global_row(g, j);
+    const double px = (2.0 * ((double)w / g.W) - 1) * g.half_width;
+    const double py = (2.0 * ((double)h / g.H) - 1) * g.half_width * g.H / g.W;
+    return normalized(mk(px, py, 0) - cam);
+}
+struct TileCone {  // the cone around a wave tile's pinhole directions: axis dc, half-angle alpha
+    V3 cam, dc;
+    double alpha;
+};
+__device__ __forceinline__ TileCone wave_tile_cone(const GridParams &g, int wx, int wy) {
+    TileCone tc;
+    tc.cam = mk(g.cam[0], g.cam[1], g.cam[2]);
+    const int w0 = wx * kWaveTileW, j0 = wy * kWaveTileH;
+    // corners one pixel beyond the tile on every side (pixels are sampled at their lower-left corner; the margin also covers
+    // the curvature of the angle function along the edges)
+    const V3 c00 = pixel_dir(g, tc.cam, w0 - 1, j0 - 1), c10 = pixel_dir(g, tc.cam, w0 + kWaveTileW, j0 - 1),
+             c01 = pixel_dir(g, tc.cam, w0 - 1, j0 + kWaveTileH), c11 = pixel_dir(g, tc.cam, w0 + kWaveTileW, j0 + kWaveTileH);
+    tc.dc = normalized((c00 + c10) + (c01 + c11));
+    double cmin = fmin(fmin(dot(tc.dc, c00), dot(tc.dc, c10)), fmin(dot(tc.dc, c01), dot(tc.dc, c11)));
+    cmin = fmin(1.0, fmax(-1.0, cmin));
+    tc.alpha = 1.5 * acos(cmin) + 1e-6;
+    return tc;
+}
+// the stripe mapping keeps a wave tile's four rows adjacent (stripes are multiples of 8 rows), so the corners bound it
+// false: the sphere (c, r) may be touched by a primary ray of the tile
+__device__ __forceinline__ bool cone_clear_of(const GridParams &g, const TileCone &tc, V3 c, double r) {
+    r = r * (1 + 1e-9) + 1e-6;
+    if (g.lens_radius > 0) {
+        const double f = g.focus_plane - tc.cam.z;
+        const double s_lo = (c.z - r - tc.cam.z) / f, s_hi = (c.z + r - tc.cam.z) / f;
+        if (!(f > 0) || !(s_lo > 0)) return false;  // object reaches the lens plane or behind it
+        r += g.lens_radius * fmax(fabs(1 - s_lo), fabs(1 - s_hi));
+    }
+    const V3 v = c - tc.cam;
+    const double dist = sqrt(dot(v, v));
+    if (!(dist > r)) return false;
+    double ct = dot(tc.dc, v) / dist;
+    ct = fmin(1.0, fmax(-1.0, ct));
+    return !(acos(ct) <= tc.alpha + asin(r / dist) + 1e-6);
+}
+
 __global__ void classify_kernel(DeviceScene sc, GridParams g, unsigned char *__restrict__ light, int n_wt) {
     const int wt = blockIdx.x * blockDim.x + threadIdx.x;
     if (wt >= n_wt) return;
     const int wtiles_x = (g.W + kWaveTileW - 1) / kWaveTileW;
-    const int wx = wt % wtiles_x, wy = wt / wtiles_x;
-    const V3 cam = mk(g.cam[0], g.cam[1], g.cam[2]);
-    auto dir_of = [&](int w, int j) {
-        const int h = global_row(g, j);
-        const double px = (2.0 * ((double)w / g.W) - 1) * g.half_width;
-        const double py = (2.0 * ((double)h / g.H) - 1) * g.half_width * g.H / g.W;
-        return normalized(mk(px, py, 0) - cam);
-    };
-    const int w0 = wx * kWaveTileW, j0 = wy * kWaveTileH;
-    // corners one pixel beyond the tile on every side (pixels are sampled at their lower-left corner; the margin also covers
-    // the curvature of the angle function along the edges)
-    const V3 c00 = dir_of(w0 - 1, j0 - 1), c10 = dir_of(w0 + kWaveTileW, j0 - 1), c01 = dir_of(w0 - 1, j0 + kWaveTileH),
-             c11 = dir_of(w0 + kWaveTileW, j0 + kWaveTileH);
-    const V3 dc = normalized((c00 + c10) + (c01 + c11));
-    double cmin = fmin(fmin(dot(dc, c00), dot(dc, c10)), fmin(dot(dc, c01), dot(dc, c11)));
-    cmin = fmin(1.0, fmax(-1.0, cmin));
-    const double alpha = 1.5 * acos(cmin) + 1e-6;
+    const TileCone tc = wave_tile_cone(g, wt % wtiles_x, wt / wtiles_x);
     bool is_light = true;
-    // the stripe mapping keeps a wave tile's four rows adjacent (stripes are multiples of 8 rows), so the corners bound it
-    // false: the sphere (c, r) may be touched by a primary ray of the tile
-    auto clear_of = [&](V3 c, double r) {
-        r = r * (1 + 1e-9) + 1e-6;
-        if (g.lens_radius > 0) {
-            const double f = g.focus_plane - cam.z;
-            const double s_lo = (c.z - r - cam.z) / f, s_hi = (c.z + r - cam.z) / f;
-            if (!(f > 0) || !(s_lo > 0)) return false;  // object reaches the lens plane or behind it
-            r += g.lens_radius * fmax(fabs(1 - s_lo), fabs(1 - s_hi));
-        }
-        const V3 v = c - cam;
-        const double dist = sqrt(dot(v, v));
-        if (!(dist > r)) return false;
-        double ct = dot(dc, v) / dist;
-        ct = fmin(1.0, fmax(-1.0, ct));
-        return !(acos(ct) <= alpha + asin(r / dist) + 1e-6);
-    };
+    auto clear_of = [&](V3 c, double r) { return cone_clear_of(g, tc, c, r); };
     for (int i = 0; i < sc.n_objs && is_light; i++) {
         const ObjRec &ob = sc.objs[i];
         if (ob.kind == KIND_SPHERE) {
@@ -730,6 +749,90 @@ __global__ void classify_kernel(DeviceScene sc, GridParams g, unsigned char *__r
     for (int i = 0; i < sc.n_cover && is_light; i++)
         is_light = clear_of(mk(sc.cover[4 * i], sc.cover[4 * i + 1], sc.cover[4 * i + 2]), sc.cover[4 * i + 3]);
     light[wt] = is_light ? 1 : 0;
+}
+
+// ---- tile order of image-order launches (GridParams::tile_order) ----------------------------------------------------------
+// A scene of spheres and planes is rendered in image order, one workgroup per 32x8 tile, and the hardware starts workgroups in
+// index order.  The tiles that see a refracting sphere carry ray trees of up to 31 rays per sample and run ~10x longer than a
+// wall tile: in row-major order the longest of them (C2: the glass sphere's centre) starts only when the first generation of
+// wall tiles retires, and that wait is added to the frame.  This kernel, launched in front of trace_grid_kernel on the same
+// stream, lists the tiles so that they start first.  Every tile is rendered by the same code on the same lanes: only the
+// workgroup index it gets changes, so image, hit counts and counters are bit for bit the row-major launch's.
+//   class 0: the tile's centre direction hits a refracting sphere itself     class 2: ... a sphere that only reflects
+//   class 1: some primary ray of the tile may touch a refracting sphere      class 3: everything else
+// (1 and 2 by the test above over the tile's wave tiles; a doubtful case only moves a tile forward).  One thread per wave tile
+// classes it; the last workgroup through (plan[kOrderArrived], reset for the next launch) folds the wave tiles into tiles
+// and writes list[] = a stable counting sort by class, row-major within a class, plan[c] = tiles of classes < c (c = 0..4).
+// The sorting pass reads back only class bytes its own thread wrote, so list[] is a permutation of the tiles whatever it saw
+// of the other workgroups' bytes.
+__global__ __launch_bounds__(1024) void tile_order_kernel(GridParams g, OrderSpheres sp, int tiles_x, int tiles_y, uint32_t *__restrict__ plan,
+                                                          uint32_t *__restrict__ list, unsigned char *__restrict__ tcls,
+                                                          unsigned char *__restrict__ wcls) {
+    constexpr int NT = 1024;
+    const int wtiles_x = (g.W + kWaveTileW - 1) / kWaveTileW, wtiles_y = (g.rows + kWaveTileH - 1) / kWaveTileH;
+    const int n_wt = wtiles_x * wtiles_y, n = tiles_x * tiles_y, tid = threadIdx.x;
+    for (int wt = blockIdx.x * NT + tid; wt < n_wt; wt += gridDim.x * NT) {
+        const TileCone tc = wave_tile_cone(g, wt % wtiles_x, wt / wtiles_x);
+        int c = 3;
+        for (unsigned i = 0; i < sp.n; i++)
+            if (!cone_clear_of(g, tc, mk(sp.s[i][0], sp.s[i][1], sp.s[i][2]), sp.s[i][3])) c = min(c, ((sp.transp >> i) & 1u) ? 1 : 2);
+        wcls[wt] = (unsigned char)c;
+    }
+    __shared__ unsigned last_s;
+    __shared__ uint32_t pos[kOrderClasses][NT];
+    __threadfence();
+    __syncthreads();
+    if (tid == 0) last_s = atomicAdd(&plan[kOrderArrived], 1u) == gridDim.x - 1 ? 1u : 0u;
+    __syncthreads();
+    if (!last_s) return;
+    __threadfence();
+    // thread t sorts the tiles [t0, t1): counts per class, a scan over the threads, then the tiles in order
+    const int per = (n + NT - 1) / NT, t0 = min(n, tid * per), t1 = min(n, t0 + per);
+    const V3 cam = mk(g.cam[0], g.cam[1], g.cam[2]);
+    for (int c = 0; c < kOrderClasses; c++) pos[c][tid] = 0;
+    for (int t = t0; t < t1; t++) {
+        const int tx = t % tiles_x, ty = t / tiles_x;
+        int c = 3;
+        for (int b = 0; b < kTileH / kWaveTileH; b++)
+            for (int a = 0; a < kTileW / kWaveTileW; a++) {
+                const int wx = tx * (kTileW / kWaveTileW) + a, wy = ty * (kTileH / kWaveTileH) + b;
+                if (wx < wtiles_x && wy < wtiles_y) c = min(c, (int)wcls[wy * wtiles_x + wx]);
+            }
+        c = max(c, 1);
+        if (c == 1) {
+            const V3 d = pixel_dir(g, cam, tx * kTileW + kTileW / 2, ty * kTileH + kTileH / 2);
+            for (unsigned i = 0; i < sp.n; i++) {
+                if (!((sp.transp >> i) & 1u)) continue;
+                const V3 v = mk(sp.s[i][0], sp.s[i][1], sp.s[i][2]) - cam;
+                const double along = dot(d, v);
+                if (along > 0 && along * along - dot(v, v) + sp.s[i][3] * sp.s[i][3] >= 0) c = 0;
+            }
+        }
+        tcls[t] = (unsigned char)c;
+        pos[c][tid]++;
+    }
+    uint32_t own[kOrderClasses], v[kOrderClasses];
+    for (int c = 0; c < kOrderClasses; c++) own[c] = pos[c][tid];
+    __syncthreads();
+    for (int off = 1; off < NT; off <<= 1) {  // inclusive scan over the threads, all classes at once
+        for (int c = 0; c < kOrderClasses; c++) v[c] = tid >= off ? pos[c][tid - off] : 0u;
+        __syncthreads();
+        for (int c = 0; c < kOrderClasses; c++) pos[c][tid] += v[c];
+        __syncthreads();
+    }
+    uint32_t base = 0;
+    for (int c = 0; c < kOrderClasses; c++) {
+        v[c] = base + pos[c][tid] - own[c];  // where this thread's first tile of class c goes
+        if (tid == 0) plan[c] = base;
+        base += pos[c][NT - 1];
+    }
+    __syncthreads();
+    for (int c = 0; c < kOrderClasses; c++) pos[c][tid] = v[c];
+    for (int t = t0; t < t1; t++) list[pos[tcls[t]][tid]++] = (uint32_t)t;
+    if (tid == 0) {
+        plan[kOrderClasses] = (uint32_t)n;
+        plan[kOrderArrived] = 0;
+    }
 }
 
 // ---- cost-aware scheduling: plan and ordered sum (GridParams, "Cost-aware scheduling") ------------------------------------

@@ -44,7 +44,10 @@ struct GridParams {
     // pending-ray code), launched beside the full variant on a second stream.  light_mode: 0 = this
     // launch leaves the light tiles alone, 1 = this launch renders only them; light == nullptr: no split.
     const unsigned char *light;
-    int32_t light_mode, pad_light_;
+    // tile_order != 0 (set only by the image-order launch of a sphere scene that ran tile_order_kernel, never by a probe, a
+    // light or a scheduled launch): trace_grid_kernel's workgroup b renders tile border[b] (ty * tiles_x + tx), the tiles that
+    // may see a refracting or reflecting sphere first; plan[c] = workgroups of classes < c (kOrderSpheresMax below)
+    int32_t light_mode, tile_order;
     const uint32_t *order;
     // Tile queue of the scheduled launch (chunks == 1): border[0..plan[3]) = the tiles (ty * tiles_x + tx) with at least one
     // wave tile that is neither heavy nor light, costliest first (plan_kernel); plan[4] = next entry.  The launch is then
@@ -75,6 +78,17 @@ struct GridParams {
 static_assert(sizeof(GridParams) == 280, "GridParams is a kernel argument: its layout is fixed");
 
 static constexpr int kTileW = 32, kTileH = 8, kThreads = 256;
+// Tile order of image-order launches (tile_order_kernel, cgrt_eye.hpp): the special spheres -- those that reflect or refract --
+// travel as a kernel argument; a scene with more of them than this is left in row-major order.  The handle's order buffer is
+// plan[kOrderPlanWords] | list[n_tiles] | tile class[n_tiles] (bytes) | wave-tile class[n_wt] (bytes); plan[c], c = 0..4 = tiles of
+// classes < c, plan[kOrderArrived] = the workgroups of tile_order_kernel that are through (0 between launches).
+static constexpr int kOrderSpheresMax = 16, kOrderClasses = 4, kOrderPlanWords = 8, kOrderArrived = 5;
+struct OrderSpheres {
+    double s[kOrderSpheresMax][4];  // centre, radius
+    uint32_t n, transp;             // transp: bit i set = sphere i refracts (transp >= kEps), else it only reflects
+};
+static constexpr size_t order_pad(size_t b) { return (b + 255) & ~(size_t)255; }
+inline size_t tile_order_bytes(size_t n_tiles, size_t n_wt) { return order_pad((kOrderPlanWords + n_tiles) * sizeof(uint32_t)) + order_pad(n_tiles) + order_pad(n_wt); }
 static constexpr int kWaveTileW = 16, kWaveTileH = 4;  // one pixel per lane
 // blockIdx -> tile, XCD-aware (tile_of_block, cgrt_grid.hpp): super-tiles of kSuperW x kSuperH tiles dealt to kXcds L2 groups
 static constexpr int kXcds = 8, kSuperW = 4, kSuperH = 4, kSuperTiles = kSuperW * kSuperH;

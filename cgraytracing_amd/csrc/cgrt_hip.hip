@@ -81,6 +81,13 @@ struct cgrt_scene {
     // (launches on one handle are ordered by the caller: cgrt.h, "Threading")
     mutable GrowBuf scratch;
     mutable size_t scratch_refused = 0;  // smallest scratch size this device has refused (0: none yet): not asked for again
+    // tile order of image-order launches (tile_order_kernel): the scene's reflecting / refracting spheres (read at commit;
+    // order_ok: the scene is spheres and planes with 1..kOrderSpheresMax of them), the order buffer -- launch scratch like
+    // `scratch`, kept apart so that the frame plan's layout stays what it is -- and the tiles the last launch ordered (0: none)
+    OrderSpheres order_spheres{};
+    bool order_ok = false;
+    mutable GrowBuf order_buf;
+    mutable size_t order_tiles = 0;
     size_t mem_total = 0;                // memory of the scene's device (read at commit; bounds the deferred-value budget)
     int n_cu = 256;                      // compute units of the scene's device (read at commit; wave slots of the scheduler)
     // second stream + fork/join events for the light-tile launch that runs beside the full one (created at commit)
@@ -168,11 +175,12 @@ int cgrt_scene_create(cgrt_scene **out) {
 
 void cgrt_scene_destroy(cgrt_scene *s) {
     if (!s) return;
-    if (!s->allocs.empty() || s->scratch.p || s->aux_stream) {
+    if (!s->allocs.empty() || s->scratch.p || s->order_buf.p || s->aux_stream) {
         DeviceGuard g(s->device);
         if (g.err == hipSuccess) {
             for (void *p : s->allocs) (void)hipFree(p);
             s->scratch.release();
+            s->order_buf.release();
             if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
             if (s->ev_join) (void)hipEventDestroy(s->ev_join);
             if (s->aux_stream) (void)hipStreamDestroy(s->aux_stream);
@@ -370,6 +378,22 @@ int cgrt_scene_commit(cgrt_scene *s, int device) {
     scene_traits(H, L.trees, knobs, d);
     open_light_stream(s, knobs.aux_priority, d);
     s->dev = d;
+    {   // the spheres tile_order_kernel orders an image-order launch by
+        OrderSpheres &os = s->order_spheres;
+        os = OrderSpheres{};
+        size_t special = 0;
+        for (const ObjRec &o : H.objs) {
+            if (o.kind != KIND_SPHERE || (o.refl < kEps && o.transp < kEps)) continue;
+            if (special < (size_t)kOrderSpheresMax) {
+                for (int k = 0; k < 3; k++) os.s[special][k] = o.a[k];
+                os.s[special][3] = std::sqrt(o.s0);
+                if (!(o.transp < kEps)) os.transp |= 1u << special;
+            }
+            special++;
+        }
+        os.n = (uint32_t)std::min(special, (size_t)kOrderSpheresMax);
+        s->order_ok = !d.has_mesh && !d.has_bezier && special >= 1 && special <= (size_t)kOrderSpheresMax;
+    }
     s->committed = true;
     s->tree_recs = std::move(L.trees);
     size_t fr = 0, tot = 0;
@@ -410,7 +434,7 @@ int cgrt_scene_get_stats(const cgrt_scene *s, cgrt_scene_stats *out) {
     bytes += 56 * out->n_nodes + 72 * out->n_triangles;
     for (auto &t : H.textures) bytes += 3 * (int64_t)t.rows * t.cols;
     out->scene_bytes_fp64 = bytes;
-    out->device_bytes = s->device_bytes + (int64_t)s->scratch.cap;  // uploaded scene + the handle's launch scratch
+    out->device_bytes = s->device_bytes + (int64_t)s->scratch.cap + (int64_t)s->order_buf.cap;  // uploaded scene + the handle's launch scratch
     out->committed = s->committed ? 1 : 0;
     return CGRT_OK;
 }
@@ -875,6 +899,30 @@ static int primary_walk(const cgrt_scene *s, const EyeLaunch &L, const GridParam
                           dim3((unsigned)s->n_cu * 4), dim3(kThreads), primary_walk_lds(staged), st, s->dev, g, pw);
 }
 
+// The tile order of an image-order launch over a scene with reflecting or refracting spheres (tile_order_kernel, cgrt_eye.hpp):
+// one small launch in front of the eye launch, on its stream, that lists the tiles the costly ones first; g then maps the
+// eye launch's workgroups through the list.  The buffer is launch scratch of the handle, written and read on this stream.
+static int order_tiles(const cgrt_scene *s, const FramePlan &p, GridParams &g, hipStream_t st) {
+    const int tiles_x = (g.W + kTileW - 1) / kTileW, tiles_y = (g.rows + kTileH - 1) / kTileH;
+    const size_t n = (size_t)tiles_x * tiles_y;
+    const void *before = s->order_buf.p;
+    if (s->order_buf.need(tile_order_bytes(n, p.n_wt)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(CGRT_ERR_DEVICE, "cannot allocate launch scratch (tile order)");
+    }
+    unsigned char *base = reinterpret_cast<unsigned char *>(s->order_buf.p);
+    uint32_t *plan = reinterpret_cast<uint32_t *>(base), *list = plan + kOrderPlanWords;
+    unsigned char *tcls = base + order_pad((kOrderPlanWords + n) * sizeof(uint32_t)), *wcls = tcls + order_pad(n);
+    if (s->order_buf.p != before) HIP_TRY(hipMemsetAsync(plan, 0, kOrderPlanWords * sizeof(uint32_t), st));  // plan[kOrderArrived]
+    const unsigned blocks = (unsigned)std::min((p.n_wt + 1023) / 1024, (size_t)64);
+    hipLaunchKernelGGL(tile_order_kernel, dim3(blocks), dim3(1024), 0, st, g, s->order_spheres, tiles_x, tiles_y, plan, list, tcls, wcls);
+    g.plan = plan;
+    g.border = list;
+    g.tile_order = 1;
+    s->order_tiles = n;
+    return CGRT_OK;
+}
+
 // development aid: CGRT_TIMELINE_FILE=path makes a launch synchronous and dumps, per workgroup, when and where it ran
 // (GridParams::timeline), behind a header {workgroups, threads per workgroup, chunks, xcd_tiles} (tools/timeline_probe.py)
 static int write_timeline(const char *file, const DevBuf &tl, size_t n_blocks, const FramePlan &p, int nt, hipStream_t st) {
@@ -938,6 +986,11 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     if (p.heavy_blocks > 0 && (rc = probe_and_plan(s, L, kn, p, g, scratch, st, rgb, nhit, cnt))) return rc;
     p.scratch.place(g, scratch, nhit != nullptr);
     const size_t n_blocks = (size_t)p.heavy_blocks + p.grid_dim;
+    // image order, one workgroup per tile with all its samples, row-major: the tiles that see a mirror or glass sphere first
+    s->order_tiles = 0;
+    if (L.form == EyeForm::Image && p.chunks == 1 && !p.xcd_tiles && L.k.nt == kThreads && s->order_ok &&
+        !(grid->flags & CGRT_GRID_NO_TILE_ORDER) && (rc = order_tiles(s, p, g, st)))
+        return rc;
     DevBuf timeline;
     if (kn.timeline_file) {
         HIP_TRY(timeline.alloc(n_blocks * 32));
@@ -958,7 +1011,22 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     const hipError_t launch_err = hipGetLastError();
     if (g.timeline && launch_err == hipSuccess && (rc = write_timeline(kn.timeline_file, timeline, n_blocks, p, L.k.nt, st))) return rc;
     if (launch_err != hipSuccess) return fail(CGRT_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(launch_err));
-    return kn.plan_dump && g.plan ? dump_plan(p, g, st) : CGRT_OK;
+    return kn.plan_dump && g.plan && !g.tile_order ? dump_plan(p, g, st) : CGRT_OK;
+}
+
+int cgrt_scene_last_tile_order(const cgrt_scene *s, uint32_t *plan5, uint32_t *list, uint8_t *cls, int64_t cap, int64_t *n_tiles) {
+    if (!s || !n_tiles) return fail(CGRT_ERR_INVALID, "null argument");
+    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+    ON_DEVICE(s->device);
+    const size_t n = s->order_tiles;
+    *n_tiles = (int64_t)n;
+    if (n == 0 || cap < (int64_t)n) return CGRT_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    const unsigned char *base = reinterpret_cast<const unsigned char *>(s->order_buf.p);
+    if (plan5) HIP_TRY(hipMemcpy(plan5, base, (kOrderClasses + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (list) HIP_TRY(hipMemcpy(list, base + kOrderPlanWords * sizeof(uint32_t), n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (cls) HIP_TRY(hipMemcpy(cls, base + order_pad((kOrderPlanWords + n) * sizeof(uint32_t)), n, hipMemcpyDeviceToHost));
+    return CGRT_OK;
 }
 
 }  // extern "C"

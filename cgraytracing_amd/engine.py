@@ -156,9 +156,10 @@ class Scene:
 
     def trace_grid(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                    stripe=None, sample_offset=0, spp_total=None, out=None, nhit=None, counters=None, stream=None,
-                   stats=False, accumulate=False, split_samples=False, reorder=True, force_reorder=False):
+                   stats=False, accumulate=False, split_samples=False, reorder=True, force_reorder=False, tile_order=True):
         """Asynchronous launch on torch's current stream (or `stream`).  reorder=False: CGRT_GRID_NO_REORDER (tiles in image
-        order instead of heaviest-first; same image).  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
+        order instead of heaviest-first; same image).  tile_order=False: CGRT_GRID_NO_TILE_ORDER (an image-order launch starts
+        its tiles row-major instead of mirror / glass tiles first; same image).  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
         workgroups share a tile's samples; reproducible, fp64 summation order differs from the sample-by-sample sum).  Returns (rgb, nhit, counters) torch
         tensors on the scene's device: float32 [rows,width,3], int32 [rows,width] (bit pattern uint32),
         int64 [8] (counters are ADDED to)."""
@@ -177,7 +178,7 @@ class Scene:
         assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (rows, width, 3)
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (2 if accumulate else 0) | (4 if split_samples else 0) |
-                              (0 if reorder else 8) | (16 if force_reorder else 0))
+                              (0 if reorder else 8) | (16 if force_reorder else 0) | (0 if tile_order else 64))
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         check(self._L.cgrt_trace_grid(self._h, C.byref(cc), C.byref(g), out.data_ptr(),
                                       nhit.data_ptr() if nhit is not None else None,
@@ -307,7 +308,7 @@ class Scene:
 
     def trace_grid_host(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                         stripe=None, sample_offset=0, spp_total=None, stats=False, split_samples=False, reorder=True,
-                        force_reorder=False):
+                        force_reorder=False, tile_order=True):
         """Synchronous form with numpy outputs (no torch needed): dict(rgb, nhit, counters)."""
         rows = height - row_offset if rows is None else rows
         rgb = np.zeros((rows, width, 3), np.float32)
@@ -315,11 +316,23 @@ class Scene:
         cnt = np.zeros((_capi.CGRT_NCOUNTERS,), np.uint64)
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (4 if split_samples else 0) | (0 if reorder else 8) |
-                              (16 if force_reorder else 0))
+                              (16 if force_reorder else 0) | (0 if tile_order else 64))
         check(self._L.cgrt_trace_grid_host(self._h, C.byref(cc), C.byref(g), rgb.ctypes.data, nhit.ctypes.data,
                                            cnt.ctypes.data))
         return dict(rgb=rgb, nhit=nhit, counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]),
                     nhp=int(cnt[_capi.CNT_HITPOINTS]))
+
+    def last_tile_order(self):
+        """The tile order of this scene's last trace_grid / trace_grid_host (cgrt_scene_last_tile_order; synchronises the
+        device): None when that launch ran no ordering kernel, else dict(plan [5] uint32: tiles of classes < c,
+        list [n] uint32: the tile workgroup i rendered, cls [n] uint8: class of tile t)."""
+        n = C.c_int64()
+        check(self._L.cgrt_scene_last_tile_order(self._h, None, None, None, 0, C.byref(n)))
+        if n.value == 0:
+            return None
+        plan, lst, cls = np.zeros(5, np.uint32), np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint8)
+        check(self._L.cgrt_scene_last_tile_order(self._h, plan.ctypes.data, lst.ctypes.data, cls.ctypes.data, n.value, C.byref(n)))
+        return dict(plan=plan, list=lst, cls=cls)
 
     def trace_grid_hitpoints(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None,
                              row_offset=0, cap=None):

@@ -17,7 +17,7 @@
  * not thread-safe; distinct scenes may be used concurrently from different host threads / devices.
  * Threading: launches on ONE scene handle must be ordered by the caller (same stream, or events between streams) --
  * a handle owns device scratch that consecutive launches reuse (CGRT_GRID_SPLIT_SAMPLES chunk sums; the schedule of a
- * cost-ordered frame; the queue counter of cgrt_trace_rays, cgrt_trace_rays_hitpoints and cgrt_ppm_session_create_rays, which
+ * cost-ordered frame; the tile order of an image-order one; the queue counter of cgrt_trace_rays, cgrt_trace_rays_hitpoints and cgrt_ppm_session_create_rays, which
  * are such launches).
  * All geometry is IEEE double, like the reference (Vec3 = 3 x double, vec3.h:11-30).
  */
@@ -91,6 +91,12 @@ enum {
                                  and to test both paths.  Device memory: up to 12 GiB (at most 1/8 of the device) of parked
                                  values per scene handle, sized by the largest launch (CGRT_DEFER_BYTES overrides)    */
     CGRT_GRID_FORCE_REORDER = 16, /* cost-schedule sphere-only scenes too (off by default: measured no gain on them)    */
+    CGRT_GRID_NO_TILE_ORDER = 64, /* image-order launches only: start the tiles in row-major order.  By default an image-order
+                                 launch over a scene of spheres and planes with 1..16 reflecting or refracting spheres is
+                                 preceded by one small kernel that lists the 32x8-pixel tiles whose primary rays may reach
+                                 such a sphere in front of the others (refracting first), and the tiles are started in that
+                                 order, so that the frame's longest tiles do not start late.  Every pixel is computed by
+                                 the same code either way: image, hit counts and counters are identical                */
     CGRT_GRID_HITPOINTS = 32, /* cgrt_trace_grid_variant only: name the launch of the Hitpoint capture
                                  (cgrt_trace_grid_hitpoints, the eye pass of cgrt_ppm_render) instead of cgrt_trace_grid's;
                                  ignored by the other calls                                                            */
@@ -463,6 +469,14 @@ int cgrt_surface_colors(const cgrt_scene *s, int obj, const double *points3, int
  * rocprofv3 kernel trace shows; written NUL-terminated into name[cap].  With CGRT_GRID_HITPOINTS in grid->flags: the
  * instantiation the Hitpoint capture launches (",SPILL=1" when objects beyond the ones it keeps in LDS are read from HBM). */
 int cgrt_trace_grid_variant(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, char *name, size_t cap);
+
+/* Verification / development aid: the tile order the LAST cgrt_trace_grid on this handle started its tiles in (see
+ * CGRT_GRID_NO_TILE_ORDER).  *n_tiles = the number of 32x8 tiles it ordered, 0 when that launch ran no ordering kernel (then
+ * nothing else is written).  With cap >= *n_tiles: synchronises the device and copies to HOST memory (each may be NULL)
+ * plan5[c] = tiles of classes < c (c = 0..4; classes: 0 centre on a refracting sphere, 1 may see a refracting sphere, 2 may
+ * see a reflecting sphere, 3 the rest), list[i] = the tile (ty * ceil(width / 32) + tx) workgroup i rendered, cls[t] = class
+ * of tile t. */
+int cgrt_scene_last_tile_order(const cgrt_scene *s, uint32_t *plan5, uint32_t *list, uint8_t *cls, int64_t cap, int64_t *n_tiles);
 
 /* Host evaluation of the lens stream (cgrt_rng.hpp, the same inline code the kernel runs): writes
  * uniform_sampling_circle(radius) (sampling.h:35-43) for n (pixel, sample) pairs as 3 doubles each.  Lets CPU-only

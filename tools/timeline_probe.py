@@ -44,6 +44,7 @@ def main():
     os.environ["CGRT_TIMELINE_FILE"] = tf
     r = sc.trace_grid_host(W, H, spp, cam, 5, 12345, rows=rows, row_offset=row_offset, split_samples=split, reorder=not natural)
     del os.environ["CGRT_TIMELINE_FILE"]
+    tile_order = sc.last_tile_order() if hasattr(sc, "last_tile_order") else None  # image-order launches of sphere scenes
     sc.close()
     raw = np.fromfile(tf, dtype=np.uint64)
     os.unlink(tf)
@@ -91,6 +92,17 @@ def main():
                                       "started_after_half": int((late & (a > 0.5 * span)).sum())}
     half = 0.5 * max(conc)
     doc["fraction_of_span_below_half_peak_concurrency"] = round(sum(1 for c in conc if c < half) / bins, 2)
+    if tile_order is not None and nblk == len(tile_order["list"]):
+        # workgroup i rendered tile list[i]; plan[c] = workgroups of classes < c (classes 0-2: tiles that may see a glass / mirror sphere)
+        plan = [int(x) for x in tile_order["plan"]]
+        blk = np.nonzero(ran)[0]
+        c0, c3 = blk < plan[1], blk >= plan[3]
+        doc["tile_order"] = {"class_bounds": plan,
+                             "class0_last_start_us": round(float(a[c0].max()), 1) if c0.any() else None,
+                             "class012_last_start_us": round(float(a[~c3].max()), 1) if (~c3).any() else None,
+                             "class3_first_start_us": round(float(a[c3].min()), 1) if c3.any() else None,
+                             "class3_last_end_us": round(float(b[c3].max()), 1) if c3.any() else None,
+                             "class012_last_end_us": round(float(b[~c3].max()), 1) if (~c3).any() else None}
     print(json.dumps(doc, indent=1))
     if out:
         json.dump(doc, open(out, "w"), indent=1)
