@@ -521,6 +521,9 @@ struct Sink {
     uint64_t hp_cap = 0, hp_n = 0;
     int64_t label = 0;
     uint64_t stats[2] = {0, 0};  // node tests, triangle tests
+    // shape of the current primary ray's tree (observation only; orc_trace_trees resets them per primary ray)
+    int waiting = 0, max_pending = 0;  // refracted children with depth_left >= 2 whose reflected sibling is being traced
+    uint32_t path_mask = 0;            // bit p: the ray with path label p passed the depth test
 };
 struct RayCtx {
     uint64_t seed, pixel, sample;
@@ -548,6 +551,7 @@ static void trace(const Scene &sc, const V3 &org, const V3 &dir, V3 adj, int dep
                   const RayCtx &rc, Sink &sink) {
     if (depth_left <= 0) return;  // main.cpp:46
     sink.nrays++;
+    sink.path_mask |= 1u << (path & 31u);
     real len = 0;
     int id = -1;
     V3 normalvec, temp;
@@ -603,7 +607,13 @@ static void trace(const Scene &sc, const V3 &org, const V3 &dir, V3 adj, int dep
         real a = nt - nc, b = nt + nc, R0 = a * a / (b * b), c = 1 - (into ? -ddn : dot(refr_dir, n_old));
         real Re = R0 + (1 - R0) * c * c * c * c * c;
         V3 fa = mul(f, adj);
+        // while the reflected branch runs, the refracted child waits; one that will itself look at the scene again and may
+        // split (depth_left - 1 >= 2) counts as pending
+        const int waits = depth_left - 1 >= 2 ? 1 : 0;
+        sink.waiting += waits;
+        if (sink.waiting > sink.max_pending) sink.max_pending = sink.waiting;
         trace(sc, P + normalvec * EPS, refl_dir, fa * Re, depth_left - 1, path * 2, rc, sink);
+        sink.waiting -= waits;
         trace(sc, P - normalvec * EPS, refr_dir, fa * (1 - Re), depth_left - 1, path * 2 + 1, rc, sink);
     }
 }
@@ -1045,9 +1055,10 @@ void orc_lens_samples(uint64_t seed, const int64_t *pix, const int32_t *smp, int
 
 // ---- the eye pass (main.cpp:185-219).  Same signature as ref_trace_grid; `hashsize` is ignored.
 // stats (optional, 2 x uint64): node tests, triangle tests.  Hitpoint capture forces one thread.
-double orc_trace_grid(void *sp, const orc_camera *cam, const orc_grid *g, int hashsize, double *acc, uint32_t *nhit,
-                      uint64_t *nrays, double *hp, int64_t *hp_pix, uint64_t hp_cap, uint64_t *hp_count) {
-    (void)hashsize;
+// tree_* (optional, orc_trace_trees): per primary ray, index (sample * nrows + local row) * W + w.
+static double trace_grid_impl(void *sp, const orc_camera *cam, const orc_grid *g, double *acc, uint32_t *nhit,
+                              uint64_t *nrays, double *hp, int64_t *hp_pix, uint64_t hp_cap, uint64_t *hp_count,
+                              uint8_t *tree_pending, uint32_t *tree_mask, uint32_t *tree_nhit) {
     Scene *s = (Scene *)sp;
     const int W = g->W, H = g->H;
     V3 camorg = v3(cam->cam);
@@ -1070,6 +1081,9 @@ double orc_trace_grid(void *sp, const orc_camera *cam, const orc_grid *g, int ha
             for (int j = g->sample0; j < g->sample0 + g->spp; j++) {
                 RayCtx rc{g->seed, (uint64_t)h * (uint64_t)W + (uint64_t)w, (uint64_t)j};
                 sink.label = ((int64_t)(j - g->sample0) << 32) | (int64_t)pix;
+                sink.waiting = sink.max_pending = 0;
+                sink.path_mask = 0;
+                const uint32_t nhit_before = *sink.nhit;
                 if (cam->lens_radius > 0) {
                     Rng r{cgrt_key(rc.seed, rc.pixel, rc.sample, 0), 0};
                     V3 neworg = camorg + lens_sample(r, cam->lens_radius);           // main.cpp:205
@@ -1078,6 +1092,10 @@ double orc_trace_grid(void *sp, const orc_camera *cam, const orc_grid *g, int ha
                 } else {
                     trace(*s, camorg, dir, V3(1, 1, 1), g->depth, 1, rc, sink);     // main.cpp:209
                 }
+                const size_t ray = (size_t)(j - g->sample0) * g->nrows * W + pix;
+                if (tree_pending) tree_pending[ray] = (uint8_t)sink.max_pending;
+                if (tree_mask) tree_mask[ray] = sink.path_mask;
+                if (tree_nhit) tree_nhit[ray] = *sink.nhit - nhit_before;
             }
         }
         total_rays += sink.nrays;
@@ -1087,6 +1105,18 @@ double orc_trace_grid(void *sp, const orc_camera *cam, const orc_grid *g, int ha
     if (nrays) *nrays = total_rays;
     if (hp_count) *hp_count = total_hp;
     return std::chrono::duration<double>(t1 - t0).count();
+}
+double orc_trace_grid(void *sp, const orc_camera *cam, const orc_grid *g, int hashsize, double *acc, uint32_t *nhit,
+                      uint64_t *nrays, double *hp, int64_t *hp_pix, uint64_t hp_cap, uint64_t *hp_count) {
+    (void)hashsize;
+    return trace_grid_impl(sp, cam, g, acc, nhit, nrays, hp, hp_pix, hp_cap, hp_count, nullptr, nullptr, nullptr);
+}
+
+// The shape of every primary ray's tree (cgrt_testapi.h): the eye pass of orc_trace_grid, observed.  max_pending, path_mask
+// and ray_nhit hold spp * nrows * W entries, index (sample * nrows + local row) * W + w; acc and nhit as orc_trace_grid.
+void orc_trace_trees(void *sp, const orc_camera *cam, const orc_grid *g, double *acc, uint32_t *nhit, uint64_t *nrays,
+                     uint8_t *max_pending, uint32_t *path_mask, uint32_t *ray_nhit) {
+    trace_grid_impl(sp, cam, g, acc, nhit, nrays, nullptr, nullptr, 0, nullptr, max_pending, path_mask, ray_nhit);
 }
 
 // diffuse photon hits of photons [first, first+count) in serial order: 10 doubles each (photon, P, n, flux)

@@ -30,6 +30,17 @@ typedef struct {
  *   hp_pix[cap]       int64  : (sample << 32) | local pixel index
  */
 
+/* outputs of orc_trace_trees (oracle only), one entry per primary ray = (sample, pixel), index
+ * (sample * nrows + local row) * W + w -- the shape of the ray's tree, stated on the recursion of trace() itself:
+ *   max_pending uint8  : 0..3, the largest number of refracted children (main.cpp:157) that were waiting at once for
+ *                        their reflected sibling's subtree to finish, counting those with depth_left >= 2 (they look at
+ *                        the scene again and may split); equally, the longest run of splitting ancestors, each entered by
+ *                        its reflected branch, above a ray that splits with depth_left >= 3
+ *   path_mask   uint32 : bit p set = the ray with path label p passed the depth test (main.cpp:46); the label is 1 for
+ *                        the primary ray, 2p for the reflected (or mirrored) child of p, 2p + 1 for the refracted one
+ *   ray_nhit    uint32 : Hitpoints of the ray's tree
+ */
+
 /* Photon pass (main.cpp:223-258).  Deterministic SERIAL semantics: photons are
  * traced one after another in index order on one thread, photon i drawing from the keyed stream
  * cgrt_key(seed, i, 0, CGRT_PURPOSE_PHOTON) in the reference's own call order. */

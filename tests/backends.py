@@ -105,6 +105,9 @@ class Backend:
                              C.c_uint64, C.c_void_p]
         if prefix == "orc":
             L.orc_set_threads.argtypes = [C.c_int]
+            L.orc_trace_trees.restype = None
+            L.orc_trace_trees.argtypes = [C.c_void_p, C.POINTER(OrcCamera), C.POINTER(OrcGrid), C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p]
         self.f = f
 
     def set_threads(self, n):
@@ -210,6 +213,22 @@ class BackendScene:
             out["hp_pix"] = (hp_pix[:n] & 0xFFFFFFFF).astype(np.int64)
             out["hp_smp"] = (hp_pix[:n] >> 32).astype(np.int64)
         return out
+
+    def trace_trees(self, cam, W, H, spp=1, depth=5, seed=12345):
+        """Oracle only: the eye pass with the shape of every primary ray's tree (orc_trace_trees, cgrt_testapi.h).  Returns
+        trace_grid's acc_sum, nhit and nrays, and per ray in camera_rays' order (index (sample * H + row) * W + w):
+        max_pending [n] uint8 (refracted children with depth_left >= 2 waiting at once), path_mask [n] uint32 (bit p: the ray
+        with path label p was traced), ray_nhit [n] uint32."""
+        c = OrcCamera(_d3(cam.cam), cam.half_width, cam.focus_plane, cam.lens_radius)
+        g = OrcGrid(W, H, 0, H, spp, 0, depth, 0, seed)
+        acc = np.zeros((H, W, 3), np.float64)
+        nhit = np.zeros((H, W), np.uint32)
+        nrays = C.c_uint64(0)
+        n = spp * H * W
+        pend, mask, rnhit = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        self.be.lib.orc_trace_trees(self.h, C.byref(c), C.byref(g), acc.ctypes.data, nhit.ctypes.data, C.byref(nrays),
+                                    pend.ctypes.data, mask.ctypes.data, rnhit.ctypes.data)
+        return dict(acc_sum=acc, nhit=nhit, nrays=int(nrays.value), max_pending=pend, path_mask=mask, ray_nhit=rnhit)
 
     def ppm(self, cam, W, H, spp=1, depth=5, seed=12345, nphotons=10000, photon_seed=777, hashsize=1000001,
             light=(0.0, 19.999, 20.0), jitter=2.0, power=700.0, alpha=0.7):
