@@ -94,6 +94,11 @@ class RayPixels(C.Structure):
     _fields_ = [("width", C.c_int32), ("rows", C.c_int32), ("spp", C.c_int32), ("pad_", C.c_int32), ("pixel", C.c_void_p)]
 
 
+class PhotonRays(C.Structure):
+    _fields_ = [("n", C.c_int64), ("org3", C.c_void_p), ("dir3", C.c_void_p), ("flux3", C.c_void_p), ("keys", C.c_void_p),
+                ("draws", C.c_void_p)]
+
+
 RAYS_STATS = 1
 RAYS_NO_SIGN_PASS = 2
 RAYS_HITPOINTS = 4
@@ -137,6 +142,12 @@ SIGNATURES = {
                                                C.POINTER(C.c_void_p)]),
     "cgrt_ppm_session_destroy": (None, [C.c_void_p]),
     "cgrt_ppm_session_add_photons": (C.c_int, [C.c_void_p, C.c_int64]),
+    "cgrt_ppm_session_add_photon_rays": (C.c_int, [C.c_void_p, C.POINTER(PhotonRays)]),
+    "cgrt_photon_emit": (C.c_int, [C.POINTER(Photons), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    "cgrt_photon_emit_host": (C.c_int, [C.POINTER(Photons), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "cgrt_photon_ray_events": (C.c_int, [C.c_void_p, C.POINTER(PhotonRays), C.c_uint64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "cgrt_ppm_session_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cgrt_ppm_session_image_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cgrt_ppm_session_hitpoints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),

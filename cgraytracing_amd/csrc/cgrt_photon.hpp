@@ -163,13 +163,75 @@ __device__ __forceinline__ V3 sample_sphere(Stream &rs) {
     }
 }
 
+// ---- the built-in emitter, main.cpp:240-246 --------------------------------------------------------------------------
+// What photon `index` of cgrt_photons starts with: its origin (the light, jittered in x and z), a direction uniform over the
+// sphere (sampling.h:11-20 by rejection), the flux power * 4 PI in each channel, and the stream its bounces go on drawing from
+// (rs.n = the draws the emission consumed: 2 + 3 per attempt at the direction).  ONE function is photon_trace_kernel's
+// emission, cgrt_photon_emit's kernel and cgrt_photon_emit_host's loop: the device's normalized() and the host's sqrt and
+// division are correctly rounded, the rest is plain IEEE arithmetic without contraction, so all three give the same bits
+// (as camera_ray does for cgrt_camera_rays / _host).
+struct EmitArgs {
+    double light[3], jitter, power;
+    uint64_t seed;
+};
+struct EmittedPhoton {
+    double o[3], d[3], flux[3];
+};
+__host__ __device__ __forceinline__ EmittedPhoton photon_emit(const EmitArgs &ea, Stream &rs) {
+    EmittedPhoton e;
+    const double a = rs.u01() * (2 * ea.jitter) - ea.jitter;
+    const double b = rs.u01() * (2 * ea.jitter) - ea.jitter;
+    e.o[0] = ea.light[0] + a;
+    e.o[1] = ea.light[1] + 0;
+    e.o[2] = ea.light[2] + b;
+    while (true) {
+        double x = rs.u01() * 2.0 - 1, y = rs.u01() * 2.0 - 1, z = rs.u01() * 2.0 - 1;
+        if (x * x + y * y + z * z <= 1) {
+            camera_normalize(x, y, z);  // vec3.h:36-44 (cgrt_rays.hpp: normalized() on the device)
+            e.d[0] = x; e.d[1] = y; e.d[2] = z;
+            break;
+        }
+    }
+    e.flux[0] = e.flux[1] = e.flux[2] = ea.power * (kPiRef * 4.0);
+    return e;
+}
+__host__ __device__ __forceinline__ uint64_t photon_key(uint64_t seed, uint64_t index) { return stream_key(seed, index, 0, 0x70686f74ull); }
+
+// What photon_trace_kernel<.., RAYS = true> reads instead: the caller's arrays (cgrt_photon_rays), already moved to the batch's
+// first photon; keys / draws may be null
+struct PhotonRayArgs {
+    const double *org, *dir, *flux;
+    const unsigned long long *keys;
+    const unsigned int *draws;
+};
+// Component j of lane's triple in an [n][3] array of doubles, read so that a wave reads whole lines: the wave's 64 triples are
+// 192 consecutive doubles (1536 B = twelve 128-byte lines when the array is line-aligned), fetched as three loads of 64
+// consecutive doubles -- every load instruction covers four whole lines, where a lane reading its own triple would touch all
+// twelve lines three times, a third of each -- and handed to their lanes by three cross-lane reads per component.  `a` points at
+// the wave's first triple, nd = 3 * (photons of this wave that exist); called by all 64 lanes.
+__device__ __forceinline__ V3 wave_load3(const double *__restrict__ a, int nd, int lane) {
+    double r[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) r[k] = (64 * k + lane < nd) ? a[64 * k + lane] : 0.0;
+    double c[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const int e = 3 * lane + j, src = e & 63, k = e >> 6;
+        const double v0 = __shfl(r[0], src), v1 = __shfl(r[1], src), v2 = __shfl(r[2], src);
+        c[j] = k == 0 ? v0 : (k == 1 ? v1 : v2);
+    }
+    return mk(c[0], c[1], c[2]);
+}
+
 // whether photon_trace_kernel<false> keeps the wide walk's first stack entries in LDS: 32 KiB per workgroup, taken only
 // while four workgroups (its 4 waves/SIMD) still fit a CU's 160 KiB beside the object list
 __host__ __device__ inline bool photon_lds_stack(const DeviceScene &sc) { return sc.has_wide && sc.n_objs <= 56; }
 // 1. photon paths.  events: count*kSegStride records of 9 doubles; valid: same count of bytes.
-template <bool BEZ, bool SPILL = false>
+// RAYS: the photons' starts come from the caller's arrays (cgrt_ppm_session_add_photon_rays) instead of the built-in emitter;
+// a compile-time choice, so neither form carries the other's code or a branch for it.
+template <bool BEZ, bool SPILL = false, bool RAYS = false>
 __global__ __launch_bounds__(kThreads, BEZ ? 2 : kPhotonWaves) void photon_trace_kernel(DeviceScene sc, PhotonArgs pa, double *__restrict__ events,
-                                                                   unsigned char *__restrict__ valid) {
+                                                                   unsigned char *__restrict__ valid, PhotonRayArgs ra) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     ObjRec *lobjs = reinterpret_cast<ObjRec *>(lds_raw);
     {
@@ -187,14 +249,35 @@ __global__ __launch_bounds__(kThreads, BEZ ? 2 : kPhotonWaves) void photon_trace
     if (!BEZ && !SPILL && photon_lds_stack(sc)) aux.wstack = reinterpret_cast<uint2 *>(lrest);  // (the SPILL launch reserves no room for it)
     const int p = blockIdx.x * kThreads + threadIdx.x;
     bool alive = p < pa.count;
-    Stream rs(stream_key(pa.seed, (uint64_t)(pa.first + (alive ? p : 0)), 0, 0x70686f74ull));
+    Stream rs(photon_key(pa.seed, (uint64_t)(pa.first + (alive ? p : 0))));
     V3 o = mk(0, 0, 0), d = mk(0, 0, 1), flux = mk(0, 0, 0);
-    if (alive) {  // main.cpp:240-246
-        const double a = rs.u01() * (2 * pa.jitter) - pa.jitter;
-        const double b = rs.u01() * (2 * pa.jitter) - pa.jitter;
-        o = mk(pa.light[0], pa.light[1], pa.light[2]) + mk(a, 0, b);
-        d = sample_sphere(rs);
-        flux = mk(pa.power, pa.power, pa.power) * (kPiRef * 4.0);
+    if (RAYS) {
+        // all 64 lanes take part in the loads (the cross-lane reads need them); a wave beyond the batch has nothing to read
+        const int lane = threadIdx.x & 63, wave_first = p - lane;
+        const int nd = 3 * (pa.count - wave_first < 64 ? pa.count - wave_first : 64);
+        if (nd > 0) {  // wave-uniform
+            o = wave_load3(ra.org + 3 * (size_t)wave_first, nd, lane);
+            d = wave_load3(ra.dir + 3 * (size_t)wave_first, nd, lane);
+            flux = wave_load3(ra.flux + 3 * (size_t)wave_first, nd, lane);
+        }
+        if (alive) {
+            if (ra.keys) rs.key = ra.keys[p];  // (uniform: a kernel argument)
+            if (ra.draws) rs.n = ra.draws[p];
+            alive = !(d.x == 0 && d.y == 0 && d.z == 0);  // emitted, goes nowhere: counted by the host, never traced
+        }
+        if (!alive) {  // an inactive lane rides along with what the built-in form gives it
+            o = mk(0, 0, 0);
+            d = mk(0, 0, 1);
+            flux = mk(0, 0, 0);
+        }
+    } else if (alive) {  // main.cpp:240-246
+        EmitArgs ea;
+        ea.light[0] = pa.light[0]; ea.light[1] = pa.light[1]; ea.light[2] = pa.light[2];
+        ea.jitter = pa.jitter; ea.power = pa.power; ea.seed = pa.seed;
+        const EmittedPhoton e = photon_emit(ea, rs);
+        o = mk(e.o[0], e.o[1], e.o[2]);
+        d = mk(e.d[0], e.d[1], e.d[2]);
+        flux = mk(e.flux[0], e.flux[1], e.flux[2]);
     }
     uint32_t dn = 0, dt = 0;
     for (int seg = 0; seg < pa.max_depth; seg++) {
@@ -265,6 +348,23 @@ __global__ __launch_bounds__(kThreads, BEZ ? 2 : kPhotonWaves) void photon_trace
             }
         }
     }
+}
+
+// cgrt_photon_emit: one lane per photon, no scene.  Any output may be null.
+__global__ __launch_bounds__(256) void photon_emit_kernel(EmitArgs ea, long long first, long long count, double *__restrict__ org,
+                                                          double *__restrict__ dir, double *__restrict__ flux,
+                                                          unsigned long long *__restrict__ keys, unsigned int *__restrict__ draws) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    Stream rs(photon_key(ea.seed, (uint64_t)(first + i)));
+    const EmittedPhoton e = photon_emit(ea, rs);
+    for (int k = 0; k < 3; k++) {
+        if (org) org[3 * i + k] = e.o[k];
+        if (dir) dir[3 * i + k] = e.d[k];
+        if (flux) flux[3 * i + k] = e.flux[k];
+    }
+    if (keys) keys[i] = rs.key;
+    if (draws) draws[i] = rs.n;
 }
 
 // Spatial order for the pair search: events keyed by their hash-grid cell (invalid slots last).  Lanes of a wave then
@@ -561,15 +661,20 @@ int sort_pairs(GrowBuf &tmp, unsigned long long *kin, unsigned long long *kout, 
     return CGRT_OK;
 }
 
-int launch_photon_trace(const cgrt_scene *s, const PhotonArgs &pa, double *events, unsigned char *valid, hipStream_t st = 0) {
+// ra: null for the built-in emitter, else the caller's photons of this batch (the RAYS instantiations)
+int launch_photon_trace(const cgrt_scene *s, const PhotonArgs &pa, double *events, unsigned char *valid, hipStream_t st = 0,
+                        const PhotonRayArgs *ra = nullptr) {
     const DeviceScene &d = s->dev;
     // more objects than the LDS list holds: the variants that read the rest from the uploaded array
     const bool spill = d.n_objs > d.n_lds, bez = d.has_bezier != 0;
-    const auto fn = spill ? (bez ? &photon_trace_kernel<true, true> : &photon_trace_kernel<false, true>)
-                          : (bez ? &photon_trace_kernel<true> : &photon_trace_kernel<false>);
+    const auto fn = ra ? (spill ? (bez ? &photon_trace_kernel<true, true, true> : &photon_trace_kernel<false, true, true>)
+                                : (bez ? &photon_trace_kernel<true, false, true> : &photon_trace_kernel<false, false, true>))
+                       : (spill ? (bez ? &photon_trace_kernel<true, true> : &photon_trace_kernel<false, true>)
+                                : (bez ? &photon_trace_kernel<true> : &photon_trace_kernel<false>));
     return launch_checked(fn, spill ? "photon_trace_kernel, SPILL" : "photon_trace_kernel", s->device,
                           dim3((pa.count + kThreads - 1) / kThreads), dim3(kThreads),
-                          photon_lds((size_t)d.n_lds, spill, bez, photon_lds_stack(d)), st, d, pa, events, valid);
+                          photon_lds((size_t)d.n_lds, spill, bez, photon_lds_stack(d)), st, d, pa, events, valid,
+                          ra ? *ra : PhotonRayArgs{});
 }
 
 int sort_pairs32(GrowBuf &tmp, unsigned int *kin, unsigned int *kout, unsigned int *vin, unsigned int *vout, size_t n,
@@ -611,8 +716,8 @@ struct PhotonProducer {
         }
         return CGRT_OK;
     }
-    // enqueue batch `pa` into buffer b (after the replay that last read b has finished)
-    int produce(const cgrt_scene *s, const PhotonArgs &pa, const HashArgs &ha, int b);
+    // enqueue batch `pa` into buffer b (after the replay that last read b has finished); ra: the caller's photons of the batch
+    int produce(const cgrt_scene *s, const PhotonArgs &pa, const HashArgs &ha, int b, const PhotonRayArgs *ra = nullptr);
     // null stream: the replay of buffer b is enqueued; b may be overwritten once it has run
     int release(int b) {
         HIP_TRY(hipEventRecord(consumed[b], 0));
@@ -621,12 +726,12 @@ struct PhotonProducer {
     }
 };
 
-int PhotonProducer::produce(const cgrt_scene *s, const PhotonArgs &pa, const HashArgs &ha, int b) {
+int PhotonProducer::produce(const cgrt_scene *s, const PhotonArgs &pa, const HashArgs &ha, int b, const PhotonRayArgs *ra) {
     const int T = 256;
     const int nslots = pa.count * kSegStride;
     if (used[b]) HIP_TRY(hipStreamWaitEvent(st, consumed[b], 0));
     HIP_TRY(hipMemsetAsync(valid[b].p, 0, (size_t)nslots, st));
-    if (const int rc = launch_photon_trace(s, pa, ev[b].as<double>(), valid[b].as<unsigned char>(), st)) return rc;
+    if (const int rc = launch_photon_trace(s, pa, ev[b].as<double>(), valid[b].as<unsigned char>(), st, ra)) return rc;
     hipLaunchKernelGGL(event_keys_kernel, dim3((nslots + T - 1) / T), dim3(T), 0, st, ev[b].as<double>(), valid[b].as<unsigned char>(),
                        nslots, ha, ek0[b].as<unsigned int>(), eo0[b].as<unsigned int>());
     const int rc = sort_pairs32(tmp, ek0[b].as<unsigned int>(), ek1[b].as<unsigned int>(), eo0[b].as<unsigned int>(),
@@ -658,6 +763,105 @@ extern "C" int cgrt_photon_events(const cgrt_scene *s, const cgrt_photons *ph, i
     pa.jitter = ph->jitter; pa.power = ph->power; pa.alpha = ph->alpha;
     pa.first = first; pa.count = count; pa.max_depth = max_depth; pa.seed = ph->seed;
     if (const int rc = launch_photon_trace(s, pa, ev.as<double>(), va.as<unsigned char>())) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(events9, ev.p, nslots * 9 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(valid, va.p, nslots, hipMemcpyDeviceToHost));
+    return CGRT_OK;
+}
+
+// ---- caller-supplied photons: argument checks, the built-in emitter as a producer, the probe -------------------------------
+constexpr long long kMaxPhotonRays = 1ll << 36;
+// what can be said without a device or a session (so the refusals are the same wherever the struct arrives)
+static int check_photon_rays(const cgrt_photon_rays *pr) {
+    if (!pr) return fail(CGRT_ERR_INVALID, "null cgrt_photon_rays");
+    if (pr->n < 0) return fail(CGRT_ERR_INVALID, "negative photon count");
+    if (pr->n > kMaxPhotonRays) return fail(CGRT_ERR_LIMIT, "more than 2^36 photons in one call");
+    if (pr->n > 0 && (!pr->org3 || !pr->dir3 || !pr->flux3)) return fail(CGRT_ERR_INVALID, "null org3 / dir3 / flux3");
+    return CGRT_OK;
+}
+static int check_emit(const cgrt_photons *ph, int64_t first, int64_t count) {
+    if (!ph) return fail(CGRT_ERR_INVALID, "null cgrt_photons");
+    if (first < 0 || count < 0) return fail(CGRT_ERR_INVALID, "negative photon index or count");
+    if (count > kMaxPhotonRays) return fail(CGRT_ERR_LIMIT, "more than 2^36 photons in one call");
+    if (first > LLONG_MAX - count) return fail(CGRT_ERR_INVALID, "photon index out of range");
+    return CGRT_OK;
+}
+static EmitArgs emit_args(const cgrt_photons *ph) {
+    EmitArgs ea;
+    for (int k = 0; k < 3; k++) ea.light[k] = ph->light[k];
+    ea.jitter = ph->jitter; ea.power = ph->power; ea.seed = ph->seed;
+    return ea;
+}
+
+extern "C" int cgrt_photon_emit(const cgrt_photons *ph, int64_t first, int64_t count, double *org3, double *dir3, double *flux3,
+                                uint64_t *keys, uint32_t *draws, void *stream) {
+    if (const int rc = check_emit(ph, first, count)) return rc;
+    if (count == 0) return CGRT_OK;
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const EmitArgs ea = emit_args(ph);
+    // 2^36 photons are 2^28 workgroups: launched in pieces of at most 2^30 photons (a grid's x extent is below 2^31)
+    for (long long k0 = 0; k0 < count; k0 += 1ll << 30) {
+        const long long m = count - k0 < (1ll << 30) ? count - k0 : (1ll << 30);
+        hipLaunchKernelGGL(photon_emit_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, ea, (long long)first + k0, m,
+                           org3 ? org3 + 3 * k0 : nullptr, dir3 ? dir3 + 3 * k0 : nullptr, flux3 ? flux3 + 3 * k0 : nullptr,
+                           keys ? reinterpret_cast<unsigned long long *>(keys) + k0 : nullptr, draws ? draws + k0 : nullptr);
+    }
+    HIP_TRY(hipGetLastError());
+    return CGRT_OK;
+}
+
+extern "C" int cgrt_photon_emit_host(const cgrt_photons *ph, int64_t first, int64_t count, double *org3, double *dir3,
+                                     double *flux3, uint64_t *keys, uint32_t *draws) {
+    if (const int rc = check_emit(ph, first, count)) return rc;
+    const EmitArgs ea = emit_args(ph);
+    for (int64_t i = 0; i < count; i++) {
+        Stream rs(photon_key(ea.seed, (uint64_t)(first + i)));
+        const EmittedPhoton e = photon_emit(ea, rs);
+        for (int k = 0; k < 3; k++) {
+            if (org3) org3[3 * i + k] = e.o[k];
+            if (dir3) dir3[3 * i + k] = e.d[k];
+            if (flux3) flux3[3 * i + k] = e.flux[k];
+        }
+        if (keys) keys[i] = rs.key;
+        if (draws) draws[i] = rs.n;
+    }
+    return CGRT_OK;
+}
+
+// cgrt_photon_events for caller-supplied photons (HOST arrays): uploads them, runs the RAYS instantiation, copies the slots back
+extern "C" int cgrt_photon_ray_events(const cgrt_scene *s, const cgrt_photon_rays *pr, uint64_t seed, int64_t first_index,
+                                      int max_depth, double *events9, uint8_t *valid) {
+    if (const int rc = check_photon_rays(pr)) return rc;
+    if (!s || !s->committed || !events9 || !valid || pr->n < 1 || pr->n > (1 << 20) || first_index < 0 || max_depth < 1 ||
+        max_depth > kMaxDepth)
+        return fail(CGRT_ERR_INVALID, "bad argument");
+    ON_DEVICE(s->device);
+    const size_t n = (size_t)pr->n, nslots = n * kSegStride;
+    DevBuf ev, va, b_o, b_d, b_f, b_k, b_n;
+    HIP_TRY(ev.alloc(nslots * 9 * sizeof(double)));
+    HIP_TRY(va.alloc(nslots));
+    HIP_TRY(hipMemset(ev.p, 0, nslots * 9 * sizeof(double)));
+    HIP_TRY(hipMemset(va.p, 0, nslots));
+    PhotonRayArgs ra{};
+    HIP_TRY(b_o.alloc(n * 24)); HIP_TRY(b_d.alloc(n * 24)); HIP_TRY(b_f.alloc(n * 24));
+    HIP_TRY(hipMemcpy(b_o.p, pr->org3, n * 24, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_d.p, pr->dir3, n * 24, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_f.p, pr->flux3, n * 24, hipMemcpyHostToDevice));
+    ra.org = b_o.as<double>(); ra.dir = b_d.as<double>(); ra.flux = b_f.as<double>();
+    if (pr->keys) {
+        HIP_TRY(b_k.alloc(n * 8));
+        HIP_TRY(hipMemcpy(b_k.p, pr->keys, n * 8, hipMemcpyHostToDevice));
+        ra.keys = b_k.as<unsigned long long>();
+    }
+    if (pr->draws) {
+        HIP_TRY(b_n.alloc(n * 4));
+        HIP_TRY(hipMemcpy(b_n.p, pr->draws, n * 4, hipMemcpyHostToDevice));
+        ra.draws = b_n.as<unsigned int>();
+    }
+    PhotonArgs pa{};
+    pa.first = first_index; pa.count = (int)n; pa.max_depth = max_depth; pa.seed = seed;
+    if (const int rc = launch_photon_trace(s, pa, ev.as<double>(), va.as<unsigned char>(), 0, &ra)) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(events9, ev.p, nslots * 9 * sizeof(double), hipMemcpyDeviceToHost));
@@ -755,7 +959,7 @@ struct cgrt_ppm_session {
     int eye_rays(const cgrt_scene *s_, const cgrt_rays *rays, const cgrt_ray_pixels *px, const cgrt_photons *ph_, DevBuf &rec);
     int table(DevBuf &rec, const int64_t *ray_pixel, bool rays);
     int photon_setup(bool session);
-    int photons(long long last, bool keep_ahead);
+    int photons(long long last, bool keep_ahead, const cgrt_photon_rays *pr = nullptr);
     int gather(double *d_img, unsigned char *d_rgb8, hipStream_t st) const;
 };
 
@@ -894,11 +1098,33 @@ int cgrt_ppm_session::photon_setup(bool session) {
 // next batch from `done` is enqueued on the producer stream for the next call (which uses it if it starts with exactly
 // that batch; it is sized for a call as long as this one); otherwise nothing is traced beyond `last` and the producer stream
 // is drained.
-int cgrt_ppm_session::photons(long long last, bool keep_ahead) {
+// pr: the photons [done, last) are the caller's (pr->n = last - done; DEVICE arrays) instead of the built-in emitter's.  Inside the
+// call batch k+1 is traced under batch k's replay as ever; a batch traced ahead by an earlier add_photons is not pr's and is
+// dropped, and the caller passes keep_ahead = false: the photons after `last` are not known, and the drain is what makes pr's
+// arrays read before the call returns.
+int cgrt_ppm_session::photons(long long last, bool keep_ahead, const cgrt_photon_rays *pr) {
     if (n == 0) {  // no hitpoint can change: nothing to trace
         done = last > done ? last : done;
         return CGRT_OK;
     }
+    const long long call_first = done;
+    if (pr) ahead_first = -1;
+    // the caller's arrays at photon `first` of this call (a batch's PhotonRayArgs)
+    auto ray_args = [&](long long first) {
+        const size_t k = (size_t)(first - call_first);
+        PhotonRayArgs ra;
+        ra.org = pr->org3 + 3 * k;
+        ra.dir = pr->dir3 + 3 * k;
+        ra.flux = pr->flux3 + 3 * k;
+        ra.keys = pr->keys ? reinterpret_cast<const unsigned long long *>(pr->keys) + k : nullptr;
+        ra.draws = pr->draws ? pr->draws + k : nullptr;
+        return ra;
+    };
+    auto produce = [&](const PhotonArgs &pa, int b) {
+        if (!pr) return pp.produce(s, pa, ha, b);
+        const PhotonRayArgs ra = ray_args(pa.first);
+        return pp.produce(s, pa, ha, b, &ra);
+    };
     const int T = 256;
     const unsigned nb = (unsigned)((n + T - 1) / T);
     auto batch_args = [&](long long first, int batch_now, long long end) {
@@ -919,7 +1145,7 @@ int cgrt_ppm_session::photons(long long last, bool keep_ahead) {
         if (ahead_first == pa.first && ahead_count == pa.count) {
             cur = ahead_buf;
         } else {  // first batch, the plan changed (a halving), or a lookahead that does not fit this call: produce it now
-            rc = pp.produce(s, pa, ha, cur);
+            rc = produce(pa, cur);
             if (rc) return rc;
         }
         ahead_first = -1;
@@ -928,7 +1154,7 @@ int cgrt_ppm_session::photons(long long last, bool keep_ahead) {
             // this batch neither overflows the pair buffer nor changes the batch size; if it does, the range will not match
             // at the top of the loop and the batch is produced again (results do not depend on the batching).
             const PhotonArgs nx = batch_args(done + pa.count, batch, last);
-            rc = pp.produce(s, nx, ha, 1 - cur);
+            rc = produce(nx, 1 - cur);
             if (rc) return rc;
             ahead_first = nx.first; ahead_count = nx.count; ahead_buf = 1 - cur;
         }
@@ -1126,6 +1352,28 @@ extern "C" int cgrt_ppm_session_add_photons(cgrt_ppm_session *p, int64_t count) 
     tm.start();
     const int rc = p->photons(p->done + count, p->lookahead);
     p->ms_last_add = tm.stop();  // also when a batch failed: what was applied before it has finished
+    p->ms_photons += p->ms_last_add;
+    return rc;
+}
+
+extern "C" int cgrt_ppm_session_add_photon_rays(cgrt_ppm_session *p, const cgrt_photon_rays *pr) {
+    if (const int rc = check_photon_rays(pr)) return rc;
+    if (!p || pr->n > LLONG_MAX - p->done) return fail(CGRT_ERR_INVALID, "bad argument");
+    if (pr->n == 0) return CGRT_OK;
+    ON_DEVICE(p->s->device);
+    if (p->img_pending) HIP_TRY(hipStreamWaitEvent(0, p->img_b, 0));  // a gather on a caller's stream reads hp
+    // the producer stream does not wait for the null stream: arrays a kernel on the null stream still writes must be complete
+    if (p->pp.st) HIP_TRY(hipStreamSynchronize(0));
+    Timer tm;
+    tm.start();
+    const int rc = p->photons(p->done + pr->n, false, pr);
+    // also when a batch failed: nothing traced ahead from pr's arrays outlives the call
+    p->ahead_first = -1;
+    if (p->pp.st) {
+        const hipError_t e = hipStreamSynchronize(p->pp.st);
+        if (e != hipSuccess && rc == CGRT_OK) return fail(CGRT_ERR_DEVICE, std::string("producer stream: ") + hipGetErrorString(e));
+    }
+    p->ms_last_add = tm.stop();
     p->ms_photons += p->ms_last_add;
     return rc;
 }

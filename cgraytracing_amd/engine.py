@@ -483,6 +483,49 @@ class Scene:
         idx = np.nonzero(va)[0]
         return np.concatenate([(first + idx // 8)[:, None].astype(np.float64), ev[idx]], axis=1)
 
+    def emit_photons(self, first, count, photon_seed=777, light=(0.0, 19.999, 20.0), jitter=2.0, power=700.0, stream=None):
+        """cgrt_photon_emit: the built-in emitter's photons [first, first + count) as device tensors (org [n,3], dirs [n,3],
+        flux [n,3] float64; keys [n] int64 (bit pattern uint64); draws [n] int32 (bit pattern uint32)) -- what
+        PpmSession.add_photon_rays takes.  Fed to a session with the same photon_seed at photons_done == first they are
+        add_photons(count) bit for bit.  Asynchronous on torch's current stream (or `stream`)."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        n = int(count)
+        org, dirs, flux = (torch.empty((n, 3), dtype=torch.float64, device=dev) for _ in range(3))
+        keys = torch.empty((n,), dtype=torch.int64, device=dev)
+        draws = torch.empty((n,), dtype=torch.int32, device=dev)
+        ph = _capi.Photons(_d3(light), jitter, power, 0.7, 0, 1000001, 0, photon_seed, 0.0, 0)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            check(self._L.cgrt_photon_emit(C.byref(ph), int(first), n, org.data_ptr(), dirs.data_ptr(), flux.data_ptr(),
+                                           keys.data_ptr(), draws.data_ptr(), C.c_void_p(st)))
+        return org, dirs, flux, keys, draws
+
+    def photon_ray_events(self, org, dirs, flux, keys=None, draws=None, max_depth=5, photon_seed=777, first_index=0):
+        """Verification probe (cgrt_photon_ray_events): the diffuse hits of caller-supplied photons (numpy arrays: org, dirs,
+        flux [n,3]; keys uint64 [n] and draws uint32 [n] or None) as photon_events returns them: [m,10] = photon (first_index +
+        position), P, n, flux in slot order."""
+        org, dirs, flux = (np.ascontiguousarray(a, np.float64).reshape(-1, 3) for a in (org, dirs, flux))
+        n = len(org)
+        if len(dirs) != n or len(flux) != n:
+            raise ValueError("photon_ray_events: org, dirs and flux differ in length")
+        if keys is not None:
+            keys = np.ascontiguousarray(keys, np.uint64)
+        if draws is not None:
+            draws = np.ascontiguousarray(draws, np.uint32)
+        for name, a in (("keys", keys), ("draws", draws)):
+            if a is not None and a.shape != (n,):
+                raise ValueError("photon_ray_events: %s must have one entry per photon" % name)
+        pr = _capi.PhotonRays(n, org.ctypes.data, dirs.ctypes.data, flux.ctypes.data, keys.ctypes.data if keys is not None else None,
+                              draws.ctypes.data if draws is not None else None)
+        ev = np.zeros((max(n, 1) * 8, 9), np.float64)
+        va = np.zeros(max(n, 1) * 8, np.uint8)
+        check(self._L.cgrt_photon_ray_events(self._h, C.byref(pr), photon_seed, int(first_index), max_depth, ev.ctypes.data,
+                                             va.ctypes.data))
+        idx = np.nonzero(va)[0]
+        return np.concatenate([(first_index + idx // 8)[:, None].astype(np.float64), ev[idx]], axis=1)
+
     def surface_colors(self, obj, pts):
         """objs[obj]->getSurfaceColor(P) on the device for each row of pts [n,3] (function-level probe)."""
         pts = np.ascontiguousarray(pts, np.float64)
@@ -550,6 +593,35 @@ class PpmSession:
         check(self._L.cgrt_ppm_session_add_photons(self._h, int(n)))
         return self
 
+    def add_photon_rays(self, org, dirs, flux, keys=None, draws=None):
+        """cgrt_ppm_session_add_photon_rays: photons whose start the caller made (a spot, area or coloured light, several
+        lights).  org, dirs, flux: contiguous float64 [n,3] tensors on the scene's device; keys int64 [n] (bit pattern uint64) and
+        draws int32 [n] (bit pattern uint32) or None (the stream (photon_seed, photon index) from its start).  The photons take
+        the indices [photons_done, photons_done + n) -- a photon with dirs == 0 goes nowhere and still counts -- and the gather
+        divides by photons_done.  Waits for torch's current stream (the tensors' producer), returns when the photons are
+        applied; Scene.emit_photons makes the built-in light's photons in this form."""
+        import torch
+
+        dev = torch.device("cuda", self._scene.device)
+        for name, t in (("org", org), ("dirs", dirs), ("flux", flux)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == 3 and
+                    t.is_contiguous() and t.device == dev):
+                raise ValueError("add_photon_rays: %s must be a contiguous float64 [n,3] tensor on %s" % (name, dev))
+        n = org.shape[0]
+        if dirs.shape[0] != n or flux.shape[0] != n:
+            raise ValueError("add_photon_rays: org, dirs and flux differ in length")
+        for name, t, dt in (("keys", keys, torch.int64), ("draws", draws, torch.int32)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == (n,) and
+                                      t.is_contiguous() and t.device == dev):
+                raise ValueError("add_photon_rays: %s must be a contiguous %s [n] tensor on %s" % (name, dt, dev))
+        if n == 0:
+            return self
+        pr = _capi.PhotonRays(n, org.data_ptr(), dirs.data_ptr(), flux.data_ptr(), keys.data_ptr() if keys is not None else None,
+                              draws.data_ptr() if draws is not None else None)
+        torch.cuda.current_stream(dev).synchronize()  # the session traces on streams of its own
+        check(self._L.cgrt_ppm_session_add_photon_rays(self._h, C.byref(pr)))
+        return self
+
     def info(self):
         inf = _capi.PpmSessionInfo()
         check(self._L.cgrt_ppm_session_get_info(self._h, C.byref(inf)))
@@ -612,6 +684,20 @@ def camera_rays_host(width, height, spp=1, camera=None, seed=12345, rows=None, r
     keys = np.zeros(n, np.uint64)
     check(_capi.lib().cgrt_camera_rays_host(C.byref(cc), C.byref(g), org.ctypes.data, dirs.ctypes.data, keys.ctypes.data))
     return org, dirs, keys
+
+
+def emit_photons_host(first, count, photon_seed=777, light=(0.0, 19.999, 20.0), jitter=2.0, power=700.0):
+    """cgrt_photon_emit_host: the built-in emitter's photons [first, first + count) evaluated on the host -- no GPU and no scene
+    needed.  Returns numpy arrays (org [n,3], dirs [n,3], flux [n,3] float64, keys [n] uint64, draws [n] uint32): the same bits
+    Scene.emit_photons makes on the device."""
+    n = int(count)
+    org, dirs, flux = (np.zeros((max(n, 0), 3), np.float64) for _ in range(3))
+    keys = np.zeros(max(n, 0), np.uint64)
+    draws = np.zeros(max(n, 0), np.uint32)
+    ph = _capi.Photons(_d3(light), jitter, power, 0.7, 0, 1000001, 0, photon_seed, 0.0, 0)
+    check(_capi.lib().cgrt_photon_emit_host(C.byref(ph), int(first), n, org.ctypes.data, dirs.ctypes.data, flux.ctypes.data,
+                                            keys.ctypes.data, draws.ctypes.data))
+    return org, dirs, flux, keys, draws
 
 
 def render(objs, width=1024, height=768, num_of_samples=1, camera=None, max_depth=5, seed=12345, device=0):

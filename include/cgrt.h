@@ -36,7 +36,9 @@ extern "C" {
                             112: cgrt_scene_set_build, cgrt_scene_build_info (row f3: structures built on the device);
                             added since without a new number, like the cgrt_ppm_session_* calls: cgrt_trace_rays,
                             cgrt_trace_rays_host, cgrt_trace_rays_variant, cgrt_camera_rays, cgrt_camera_rays_host (caller-supplied rays);
-                            cgrt_trace_rays_hitpoints, cgrt_ppm_session_create_rays (photon mapping of caller-supplied rays) */
+                            cgrt_trace_rays_hitpoints, cgrt_ppm_session_create_rays (photon mapping of caller-supplied rays);
+                            cgrt_ppm_session_add_photon_rays, cgrt_photon_emit, cgrt_photon_emit_host, cgrt_photon_ray_events
+                            (caller-supplied photons) */
 
 enum {
     CGRT_OK = 0,
@@ -423,6 +425,42 @@ int cgrt_ppm_session_create_rays(const cgrt_scene *s, const cgrt_rays *rays, con
 void cgrt_ppm_session_destroy(cgrt_ppm_session *p);
 /* Traces photons [done, done + count) and applies them; returns when they are applied.  count >= 0. */
 int cgrt_ppm_session_add_photons(cgrt_ppm_session *p, int64_t count);
+/* ---- caller-supplied photons: light a session from any emitter ---------------------------------------------------------
+ * cgrt_ppm_session_add_photons traces the photons of the reference's one jittered point light (cgrt_photons.light / jitter /
+ * power).  cgrt_ppm_session_add_photon_rays traces photons whose start the caller made: spot, area, coloured or several
+ * lights, a light in a fixture.  Past its start a photon runs trace(flag=false) unchanged (main.cpp:101-165). */
+typedef struct cgrt_photon_rays {
+    int64_t n;              /* photons; 0 is valid and does nothing; more than 2^36: CGRT_ERR_LIMIT                        */
+    const double *org3;     /* [n][3]                                                                                      */
+    const double *dir3;     /* [n][3] used as given (unit length is the caller's contract).  Exactly (0,0,0): the photon is
+                               emitted but goes nowhere -- not traced, no event, yet COUNTED (an emitter that sends part of
+                               its power where no photon is wanted keeps its normalisation)                                */
+    const double *flux3;    /* [n][3] the flux trace(flag=false) starts with (main.cpp:246: 700*4*PI in each channel)       */
+    const uint64_t *keys;   /* [n] or NULL: key of the stream the photon's bounces draw from (half-sphere directions, the
+                               glass roulette, Bezier starts).  NULL: stream_key(session seed, photon index, 0, 'phot'), the
+                               built-in emitter's                                                                          */
+    const uint32_t *draws;  /* [n] or NULL: draws of that stream already consumed (Stream::n of cgrt_rng.hpp).  NULL: 0      */
+} cgrt_photon_rays;
+/* The photons take the indices [photons_done, photons_done + n) and are applied in that order; photons_done advances by n,
+ * photons with dir = 0 included, and the gather stays flux / (PI * r2 * photons_done * spp).  The depth limit, alpha, hashsize,
+ * initial_radius, batch and pair_cap are the session's; a batch is applied whole or not at all, and the result does not depend
+ * on how a photon set is split over calls, batches or halvings.  Calls of add_photons and add_photon_rays may be mixed on one
+ * session.  pr's arrays are DEVICE pointers on the scene's device (written on the null stream or finished), read before the call
+ * returns.  No batch is traced ahead when the call ends (the next photons are not known), and a batch that an earlier
+ * add_photons traced ahead is dropped.  Multi-GPU: every rank is given the same photons. */
+int cgrt_ppm_session_add_photon_rays(cgrt_ppm_session *p, const cgrt_photon_rays *pr);
+/* The built-in emitter as a producer of such photons: origin, direction, flux, stream key and stream position of photons
+ * [first, first + count) of ph (light, jitter, power and seed are read) -- the values of main.cpp:240-246 as
+ * cgrt_ppm_session_add_photons computes them (one inline function is the kernel's emission and both forms here).  draws is the
+ * stream position behind the rejection-sampled direction: at least 5, and it differs per photon.  add_photon_rays of these
+ * arrays at photons_done = first is add_photons(count) bit for bit.  Any pointer may be NULL; count > 2^36: CGRT_ERR_LIMIT.
+ * DEVICE pointers on the current device, asynchronous on `stream`. */
+int cgrt_photon_emit(const cgrt_photons *ph, int64_t first, int64_t count, double *org3, double *dir3, double *flux3,
+                     uint64_t *keys, uint32_t *draws, void *stream);
+/* The same bits evaluated on the HOST into host buffers; needs no GPU. */
+int cgrt_photon_emit_host(const cgrt_photons *ph, int64_t first, int64_t count, double *org3, double *dir3, double *flux3,
+                          uint64_t *keys, uint32_t *draws);
+
 /* Final gather at the current photon count (main.cpp:252-258), as cgrt_ppm_result.image / .rgb8.  HOST buffers; either may be
  * NULL.  CGRT_ERR_INVALID before the first photon (the reference's flux / (PI r2 0)); rgb8 with stripes: CGRT_ERR_UNSUPPORTED. */
 int cgrt_ppm_session_image(const cgrt_ppm_session *p, double *image, uint8_t *rgb8);
@@ -454,6 +492,11 @@ int cgrt_write_png(const char *path, int width, int height, const uint8_t *rgb8)
  * path segment; valid = one byte per slot.  HOST buffers. */
 int cgrt_photon_events(const cgrt_scene *s, const cgrt_photons *ph, int max_depth, int64_t first, int32_t count,
                        double *events9, uint8_t *valid);
+
+/* The same probe for caller-supplied photons: pr's arrays are HOST pointers here, pr->n <= 2^20; seed and first_index make the
+ * default stream key (seed, first_index + i) where pr->keys is NULL.  events9 = n*8 slots, valid = n*8 bytes, as above. */
+int cgrt_photon_ray_events(const cgrt_scene *s, const cgrt_photon_rays *pr, uint64_t seed, int64_t first_index, int max_depth,
+                           double *events9, uint8_t *valid);
 
 /* Function-level probe used by parity tests: objs[obj]->intersect(org, dir, len, normal) for n rays on the
  * device (host pointers; keys: per-ray stream key for Bezier draws, may be NULL). */

@@ -477,6 +477,9 @@ class PpmSession {
 
     // traces photons [photons_done(), photons_done() + n) and applies them
     void add_photons(long long n) { check(cgrt_ppm_session_add_photons(session_, n)); }
+    // caller-supplied photons (cgrt_ppm_session_add_photon_rays): pr's arrays are DEVICE pointers on the scene's device, read before
+    // the call returns; the photons take the indices [photons_done(), photons_done() + pr.n), photons with dir = 0 included
+    void add_photon_rays(const cgrt_photon_rays &pr) { check(cgrt_ppm_session_add_photon_rays(session_, &pr)); }
     long long photons_done() const { return (long long)info().photons_done; }
     // the gathered image (doubles, row 0 = bottom) and the bytes main.cpp:403-411 hands to stbi_write_png
     void image(std::vector<double> &image, std::vector<unsigned char> &image_data) const {
