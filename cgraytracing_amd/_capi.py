@@ -102,6 +102,7 @@ class PhotonRays(C.Structure):
 RAYS_STATS = 1
 RAYS_NO_SIGN_PASS = 2
 RAYS_HITPOINTS = 4
+PROBE_SQRT, PROBE_NORMALIZED, PROBE_SPHERE_LEN = 0, 1, 2  # cgrt_math_probe's op
 
 # every symbol include/cgrt.h declares, with its signature
 _DP = C.POINTER(C.c_double)
@@ -171,6 +172,7 @@ SIGNATURES = {
     "cgrt_camera_rays_host": (C.c_int, [C.POINTER(Camera), C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cgrt_intersect_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cgrt_math_probe": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 _lib = None

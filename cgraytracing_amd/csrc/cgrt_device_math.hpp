@@ -37,6 +37,10 @@ __device__ __forceinline__ V3 cross(V3 a, V3 b) {
 // the corrections do not underflow) and a final select for x = 0 / +inf: 20 VALU instructions, 7 of them range handling.  When no
 // active lane of the wave has such an x (nor a negative one or a NaN) the wrapping does nothing and is left out; otherwise the
 // whole wave takes the library form.  Same bits either way; a sphere-scene ray takes 4-5 square roots.
+// Tested on its own (cgrt_math_probe -> math_probe_kernel, tests/test_gpu_device_math.py) against the exactly rounded root from
+// integer arithmetic: every double whose root lies within 2^-50 ulp of a rounding midpoint at every exponent of the range,
+// squares and their neighbours, both ends of the range, zeros, subnormals, inf, NaN, negatives -- in the short form and in the
+// library form -- and waves with one lane, 63 lanes or the last live lane out of range, and a partial last wave.
 __device__ __forceinline__ double sqrt_cr(double x) {
     if (__ballot(!(x >= 0x1p-767 && x <= 0x1p1000)) != 0ull) return sqrt(x);
     const double y = __builtin_amdgcn_rsq(x);
@@ -57,6 +61,9 @@ __device__ __forceinline__ double sqrt_cr(double x) {
 // of squares puts len in [2^-384, 2^500], where hipcc's expansion of 1.0 / len (v_div_scale, v_rcp_f64, two refinements, one
 // residual correction, v_div_fmas, v_div_fixup: 11 instructions) scales nothing and fixes nothing up -- what is left is the 7
 // instructions below, the same bits.
+// Tested by the same file against the expression above in IEEE double: sums of squares on the root's hard cases, underflowing
+// to 0 or a subnormal, overflowing to inf, NaN components, lengths with mantissas next to 1 and next to 2 (where 1 / len lies
+// next to a representable number, resp. a midpoint), the same wave compositions.
 __device__ __forceinline__ V3 normalized(V3 a) {
     const double s2 = a.x * a.x + a.y * a.y + a.z * a.z;
     if (__ballot(!(s2 >= 0x1p-767 && s2 <= 0x1p1000)) != 0ull) {

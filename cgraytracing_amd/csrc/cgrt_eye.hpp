@@ -1086,4 +1086,23 @@ __global__ void surface_colors_kernel(DeviceScene sc, int obj, const double *__r
     out[3 * i + 2] = f.z;
 }
 
+// function-level probe of the device math (cgrt_math_probe): element i runs on thread i % 256 of block i / 256, so elements
+// 64k .. 64k+63 are the lanes of one wave; a lane with i >= n returns BEFORE the call, so the ballots of sqrt_cr / normalized see
+// the live lanes of the last wave only.  Calls the inlines the render kernels call.
+__global__ void math_probe_kernel(int op, const double *__restrict__ in, long long n, double *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (op == CGRT_PROBE_SQRT) {  // (wave-uniform branches)
+        out[i] = sqrt_cr(in[i]);
+    } else if (op == CGRT_PROBE_NORMALIZED) {
+        const V3 v = normalized(ld3(in + 3 * i));
+        out[3 * i] = v.x;
+        out[3 * i + 1] = v.y;
+        out[3 * i + 2] = v.z;
+    } else {  // CGRT_PROBE_SPHERE_LEN: centre(3), r2, origin(3), direction(3)
+        const double *p = in + 10 * i;
+        out[i] = sphere_len(ld3(p), p[3], ld3(p + 4), ld3(p + 7));
+    }
+}
+
 #endif

@@ -1549,6 +1549,27 @@ int cgrt_lens_samples(uint64_t seed, const int64_t *pixel, const int32_t *sample
     return CGRT_OK;
 }
 
+int cgrt_math_probe(int device, int op, const double *in, int64_t n, double *out) {
+    if (op != CGRT_PROBE_SQRT && op != CGRT_PROBE_NORMALIZED && op != CGRT_PROBE_SPHERE_LEN)
+        return fail(CGRT_ERR_INVALID, "cgrt_math_probe: unknown op");
+    if (!in || !out) return fail(CGRT_ERR_INVALID, "cgrt_math_probe: null buffer");
+    if (n < 0) return fail(CGRT_ERR_INVALID, "cgrt_math_probe: negative n");
+    if (n > ((int64_t)1 << 28)) return fail(CGRT_ERR_LIMIT, "cgrt_math_probe: more than 2^28 elements");
+    if (n == 0) return CGRT_OK;
+    const size_t n_in = op == CGRT_PROBE_SQRT ? 1 : (op == CGRT_PROBE_NORMALIZED ? 3 : 10), n_out = op == CGRT_PROBE_NORMALIZED ? 3 : 1;
+    ON_DEVICE(device);
+    DevBuf b_in, b_out;
+    HIP_TRY(b_in.alloc((size_t)n * n_in * sizeof(double)));
+    HIP_TRY(b_out.alloc((size_t)n * n_out * sizeof(double)));
+    HIP_TRY(hipMemcpy(b_in.p, in, (size_t)n * n_in * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(math_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, b_in.as<double>(), (long long)n,
+                       b_out.as<double>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, b_out.p, (size_t)n * n_out * sizeof(double), hipMemcpyDeviceToHost));
+    return CGRT_OK;
+}
+
 }  // extern "C"
 
 #include "cgrt_photon.hpp"

@@ -70,6 +70,7 @@ __device__ __forceinline__ bool mesh_may_hit(const ObjRec &ob, V3 o, V3 d) {
 }
 
 // Sphere::intersect, objects.h:45-68: the hit distance, or +inf-like kInf (never < nearest) on a miss
+// (tests/test_gpu_device_math.py probes it with exact tangents, r2 - d2 == +-1 ulp, origins on the surface and sub-2^-767 radii)
 __device__ __forceinline__ double sphere_len(V3 centre, double r2, V3 o, V3 d) {
     const V3 l = centre - o;
     const double tca = dot(l, d);

@@ -720,6 +720,21 @@ def tonemap_rgb8(image, device=0):
     return out
 
 
+def math_probe(op, values, device=0):
+    """cgrt_math_probe: the kernels' own inline device math on a numpy array (function-level probe).  op "sqrt": [n] -> [n];
+    "normalized": [n,3] -> [n,3]; "sphere_len": [n,10] = centre, radius2, origin, direction -> [n].  Elements 64k .. 64k+63
+    are the lanes of one wave."""
+    code, cols = {"sqrt": (_capi.PROBE_SQRT, 1), "normalized": (_capi.PROBE_NORMALIZED, 3),
+                  "sphere_len": (_capi.PROBE_SPHERE_LEN, 10)}[op]
+    values = np.ascontiguousarray(values, np.float64)
+    if values.shape[1:] != (() if cols == 1 else (cols,)):
+        raise ValueError("math_probe(%r): expected shape [n%s], got %r" % (op, "" if cols == 1 else ",%d" % cols, values.shape))
+    n = values.shape[0]
+    out = np.zeros((n, 3) if cols == 3 else (n,), np.float64)
+    check(_capi.lib().cgrt_math_probe(device, code, values.ctypes.data, n, out.ctypes.data))
+    return out
+
+
 def write_png(path, rgb8):
     """stbi_write_png's role at main.cpp:412: [H,W,3] uint8, top row first."""
     rgb8 = np.ascontiguousarray(rgb8, np.uint8)

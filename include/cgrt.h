@@ -526,6 +526,20 @@ int cgrt_scene_last_tile_order(const cgrt_scene *s, uint32_t *plan5, uint32_t *l
  * tests pin the stream against the reference's sampler without a GPU. */
 int cgrt_lens_samples(uint64_t seed, const int64_t *pixel, const int32_t *sample, int n, double radius, double *out3);
 
+/* Function-level probe of the device math the fp64 parity rests on (tests/test_gpu_device_math.py): the very inline
+ * functions the render kernels call, evaluated on `device` for n elements.  HOST buffers.
+ *   CGRT_PROBE_SQRT        in[n]     -> out[n]    = the kernels' fp64 square root (sqrt(), correctly rounded)
+ *   CGRT_PROBE_NORMALIZED  in[n][3]  -> out[n][3] = Vec3::normalize (vec3.h:35-43)
+ *   CGRT_PROBE_SPHERE_LEN  in[n][10] -> out[n]    = len of Sphere::intersect (objects.h:45-68) for {centre(3), radius2,
+ *                                                   rayorig(3), raydir(3)}; a miss gives 1e10 (the kernels' "no hit yet")
+ * Launch geometry is part of the contract, because these functions decide per WAVE which form they take: element i is handled
+ * by thread i % 256 of block i / 256, so elements 64k .. 64k+63 are the 64 lanes of one wave, and a lane with i >= n leaves
+ * before the call -- the last wave decides with its live lanes only.
+ * CGRT_ERR_INVALID: unknown op, null pointer, n < 0 (checked before any device is touched); n == 0 does nothing;
+ * more than 2^28 elements: CGRT_ERR_LIMIT. */
+enum { CGRT_PROBE_SQRT = 0, CGRT_PROBE_NORMALIZED = 1, CGRT_PROBE_SPHERE_LEN = 2 };
+int cgrt_math_probe(int device, int op, const double *in, int64_t n, double *out);
+
 #ifdef __cplusplus
 }
 #endif

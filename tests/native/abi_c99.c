@@ -25,6 +25,8 @@ int cgrt_abi_smoke(void) {
         if (cgrt_ppm_render(s, &cam, &g, &ph, &out) != CGRT_ERR_INVALID) return 5; /* uncommitted scene */
         if (cgrt_tonemap_rgb8(0, 0, 4, 4, 0) != CGRT_ERR_INVALID) return 6;          /* null buffers */
         if (cgrt_write_png(0, 4, 4, 0) != CGRT_ERR_INVALID) return 7;
+        if (cgrt_math_probe(0, CGRT_PROBE_SQRT, 0, 4, 0) != CGRT_ERR_INVALID) return 8;  /* null buffers */
+        if (cgrt_math_probe(0, CGRT_PROBE_SPHERE_LEN, col, 0, c) != CGRT_OK) return 9;     /* nothing to do */
     }
     rc = cgrt_trace_grid_host(s, &cam, &g, 0, 0, 0); /* uncommitted scene: must be refused, not crash */
     cgrt_scene_destroy(s);

@@ -66,6 +66,32 @@ def test_error_reporting_without_gpu_or_bad_args():
     big.close()
 
 
+def test_math_probe_symbol_and_errors():
+    """cgrt_math_probe (the device-math probe of tests/test_gpu_device_math.py) is exported and bound, and refuses an unknown
+    op, null buffers and n < 0 before it touches a device; n == 0 does nothing, and needs no device either."""
+    import cgraytracing_amd as cg
+    from cgraytracing_amd import _capi
+    assert "cgrt_math_probe" in _capi.SIGNATURES and hasattr(C.CDLL(_capi.LIB_PATH), "cgrt_math_probe")
+    L = _capi.lib()
+    buf, out = np.ones(30), np.full(30, -7.0)
+    for op in (_capi.PROBE_SQRT, _capi.PROBE_NORMALIZED, _capi.PROBE_SPHERE_LEN):
+        assert L.cgrt_math_probe(0, op, None, 3, out.ctypes.data) == -1 and b"null" in L.cgrt_last_error()
+        assert L.cgrt_math_probe(0, op, buf.ctypes.data, 3, None) == -1 and b"null" in L.cgrt_last_error()
+        assert L.cgrt_math_probe(0, op, buf.ctypes.data, -1, out.ctypes.data) == -1 and b"negative" in L.cgrt_last_error()
+        assert L.cgrt_math_probe(0, op, buf.ctypes.data, 0, out.ctypes.data) == 0
+        assert L.cgrt_math_probe(0, op, buf.ctypes.data, (1 << 28) + 1, out.ctypes.data) == -5
+    for op in (-1, 3):
+        assert L.cgrt_math_probe(0, op, buf.ctypes.data, 3, out.ctypes.data) == -1 and b"op" in L.cgrt_last_error()
+    assert (out == -7.0).all()
+    with pytest.raises(KeyError):
+        cg.math_probe("cbrt", buf)
+    with pytest.raises(ValueError):
+        cg.math_probe("normalized", buf)
+    with pytest.raises(ValueError):
+        cg.math_probe("sphere_len", buf.reshape(10, 3))
+    assert cg.math_probe("sqrt", np.zeros(0)).shape == (0,) and cg.math_probe("normalized", np.zeros((0, 3))).shape == (0, 3)
+
+
 def test_malformed_mesh_is_io_error(tmp_path):
     import cgraytracing_amd as cg
     from cgraytracing_amd import _capi
