@@ -566,7 +566,7 @@ static size_t eye_lds(const EyeFlags &f, const DeviceScene &d) {
 }
 // primary_walk_kernel (cgrt_primwalk.hpp): `staged` objects | the wide walk's stack entries
 static constexpr size_t primary_walk_lds(size_t staged) { return staged * sizeof(ObjRec) + kWideStackLds; }
-// photon_trace_kernel (cgrt_photon.hpp): `resident` objects | one staging record per wave (SPILL) | one BezLds per wave (BEZ),
+// photon_trace_kernel (cgrt_photon_trace.hpp): `resident` objects | one staging record per wave (SPILL) | one BezLds per wave (BEZ),
 // or else, without SPILL, the first entries of the wide walk's stack where photon_lds_stack asks for them
 static constexpr size_t photon_lds(size_t resident, bool spill, bool bez, bool wide_stack) {
     return (resident + (spill ? kThreads / 64 : 0)) * sizeof(ObjRec) + (bez ? (kThreads / 64) * sizeof(BezLds) : 0) +
@@ -1321,6 +1321,31 @@ __global__ void unpermute_stripes_kernel(const float *__restrict__ shares, int n
     frame[(size_t)h * row_floats + x] = v;
 }
 
+// What both Hitpoint captures end with: wait for the kernel, read how many records it produced (*count; 0 on failure) and hand
+// the buffer over (*d_rec_out, unless cap == 0)
+static int capture_finish(const char *what, DevBuf &b_rec, DevBuf &b_cnt, uint64_t cap, double **d_rec_out, uint64_t *count) {
+    *count = 0;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(CGRT_ERR_DEVICE, std::string(what) + hipGetErrorString(e));
+    unsigned long long n = 0;
+    if (hipMemcpy(&n, b_cnt.p, sizeof(n), hipMemcpyDeviceToHost) != hipSuccess) return fail(CGRT_ERR_DEVICE, "hitpoint count copy");
+    *count = n;
+    if (cap && d_rec_out) *d_rec_out = reinterpret_cast<double *>(b_rec.release());
+    return CGRT_OK;
+}
+// and what both host entry points do with a capture's outcome: the count, the first `cap` records to the host, the buffer freed
+static int hitpoints_to_host(int rc, double *d_rec, uint64_t n, double *hp10, uint64_t cap, uint64_t *count) {
+    if (rc == CGRT_OK) {
+        *count = n;
+        const uint64_t m = n < cap ? n : cap;
+        if (m && hipMemcpy(hp10, d_rec, (size_t)m * 10 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(CGRT_ERR_DEVICE, "hitpoint copy");
+    }
+    if (d_rec) (void)hipFree(d_rec);
+    return rc;
+}
+
 // The ray-buffer form of hitpoints_device below: capture_rays_kernel over rays' DEVICE arrays (pixel: DEVICE, or nullptr)
 // into a device buffer of `cap` records; *count = Hitpoints produced.  *d_rec_out is hipMalloc'ed here (caller frees) unless
 // cap == 0.  Runs on the null stream and synchronises.
@@ -1357,14 +1382,7 @@ static int ray_hitpoints_device(const cgrt_scene *s, const cgrt_rays *rays, cons
     const long long wgs = std::max(1ll, std::min((n_blocks + waves_per_wg - 1) / waves_per_wg, 2 * chip));
     int rc = launch_checked(e->fn, L.what(), s->device, dim3((unsigned)wgs), dim3((unsigned)L.k.nt), L.lds, 0, L.dev, rp, sink);
     if (rc) return rc;
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipDeviceSynchronize();
-    if (err != hipSuccess) return fail(CGRT_ERR_DEVICE, std::string("ray hitpoint kernel: ") + hipGetErrorString(err));
-    unsigned long long n = 0;
-    if (hipMemcpy(&n, b_cnt.p, sizeof(n), hipMemcpyDeviceToHost) != hipSuccess) return fail(CGRT_ERR_DEVICE, "hitpoint count copy");
-    *count = n;
-    if (cap && d_rec_out) *d_rec_out = reinterpret_cast<double *>(b_rec.release());
-    return CGRT_OK;
+    return capture_finish("ray hitpoint kernel: ", b_rec, b_cnt, cap, d_rec_out, count);
 }
 
 // Eye pass with Hitpoint capture into a device buffer of `cap` records (10 doubles each); *count = hitpoints produced.
@@ -1387,15 +1405,7 @@ static int hitpoints_device(const cgrt_scene *s, const cgrt_camera *cam, const c
     int rc = launch_eye(L, false, s->device, g, dim3((unsigned)tile_grid_blocks(g.W, g.rows, g.xcd_tiles != 0)), 0, d_rgb, nullptr,
                         nullptr, HitpointSink{d_rec, d_cnt, (unsigned long long)cap});
     if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) rc = fail(CGRT_ERR_DEVICE, std::string("hitpoint kernel: ") + hipGetErrorString(e));
-    unsigned long long n = 0;
-    if (rc == CGRT_OK && hipMemcpy(&n, d_cnt, sizeof(n), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(CGRT_ERR_DEVICE, "hitpoint count copy");
-    *count = n;
-    if (rc == CGRT_OK && cap && d_rec_out) *d_rec_out = reinterpret_cast<double *>(b_rec.release());
-    return rc;
+    return capture_finish("hitpoint kernel: ", b_rec, b_cnt, cap, d_rec_out, count);
 }
 
 extern "C" {
@@ -1409,14 +1419,7 @@ int cgrt_trace_grid_hitpoints(const cgrt_scene *s, const cgrt_camera *cam, const
     double *d_rec = nullptr;
     uint64_t n = 0;
     rc = hitpoints_device(s, cam, grid, cap, &d_rec, &n);
-    if (rc == CGRT_OK) {
-        *count = n;
-        const uint64_t m = n < cap ? n : cap;
-        if (m && hipMemcpy(hp10, d_rec, (size_t)m * 10 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(CGRT_ERR_DEVICE, "hitpoint copy");
-    }
-    if (d_rec) (void)hipFree(d_rec);
-    return rc;
+    return hitpoints_to_host(rc, d_rec, n, hp10, cap, count);
 }
 
 int cgrt_trace_rays_hitpoints(const cgrt_scene *s, const cgrt_rays *rays, double *hp10, uint64_t cap, uint64_t *count) {
@@ -1427,14 +1430,7 @@ int cgrt_trace_rays_hitpoints(const cgrt_scene *s, const cgrt_rays *rays, double
     double *d_rec = nullptr;
     uint64_t n = 0;
     rc = ray_hitpoints_device(s, rays, nullptr, cap, &d_rec, &n);
-    if (rc == CGRT_OK) {
-        *count = n;
-        const uint64_t m = n < cap ? n : cap;
-        if (m && hipMemcpy(hp10, d_rec, (size_t)m * 10 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(CGRT_ERR_DEVICE, "hitpoint copy");
-    }
-    if (d_rec) (void)hipFree(d_rec);
-    return rc;
+    return hitpoints_to_host(rc, d_rec, n, hp10, cap, count);
 }
 
 int cgrt_unpermute_stripes(const float *shares, int n_present, int nshares, int width, int height, int stripe_rows,
@@ -1572,7 +1568,13 @@ int cgrt_math_probe(int device, int op, const double *in, int64_t n, double *out
 
 }  // extern "C"
 
-#include "cgrt_photon.hpp"
+// the photon pass, the session and the image output
+#include "cgrt_ppm_plan.h"
+#include "cgrt_ppm_table.hpp"
+#include "cgrt_photon_trace.hpp"
+#include "cgrt_ppm_apply.hpp"
+#include "cgrt_ppm_session.hpp"
+#include "cgrt_output.hpp"
 
 #ifdef CGRT_UTIL
 // development aid (make exp NAME=util DEFS=-DCGRT_UTIL; tools/util_probe.py): lane-utilisation probes, see UTILP in cgrt_device_math.hpp

@@ -1,0 +1,450 @@
+// Photon pass: cgrt_ppm_session -- the state of a photon-mapping run -- its stages (eye, table,
+// photons in batches as PpmSchedule of cgrt_ppm_plan.h decides, gather) and the cgrt_ppm_* entry points.
+//
+// Reference: render() main.cpp:223-258 + trace(flag=false) main.cpp:101-128,158-165 + Hashtable hash.h:20-70.
+// The reference runs eight OpenMP threads that race on the hitpoints and seed rand() from the clock, so its
+// output is not reproducible even against itself.  The semantics implemented -- and pinned bit for bit by the
+// oracle and by golden vectors from the compiled reference run on ONE thread -- are its serial meaning:
+// photons 0..N-1 one after another, photon i drawing from the keyed stream (seed, i, 0, 'phot') in the
+// reference's call order, each diffuse hit updating the hitpoints of the 27 surrounding hash cells.
+//
+// A hitpoint's evolution (r2, n, flux) depends only on the ORDERED list of photon events that reach it, and
+// photon paths do not depend on the hitpoints.  So the serial result is computed in parallel as
+//   1. photon_trace_kernel   : one lane per photon; every diffuse hit appends an event {P, n, flux} at a slot
+//                              derived from (photon, segment), i.e. in serial order;
+//   2. photon_pairs_kernel   : one lane per event; walks the reference's own candidate set -- the buckets the 27
+//                              cells hash to (hash.h:35-37), collisions included -- and emits (hitpoint, order)
+//                              pairs that pass the static tests (normal, distance against the radius the hitpoint
+//                              had at the start of the batch, which only shrinks);
+//   3. radix sort of the pairs by (hitpoint, order)                                     [rocprim]
+//   4. photon_apply_kernel   : one lane per hitpoint; replays its events in order with the reference's update
+//                              (main.cpp:116-122), re-checking the distance against the current radius.
+// Hitpoints are kept sorted by (bucket, emission order) = the reference's table order, which is also the order of
+// its final gather (main.cpp:252-258); the image is summed per pixel in that order.
+#include <climits>
+#include <memory>
+
+namespace {
+struct Timer {  // device time between two points of the null stream
+    hipEvent_t a = nullptr, b = nullptr;
+    Timer() { (void)hipEventCreate(&a); (void)hipEventCreate(&b); }
+    ~Timer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    void start() { (void)hipEventRecord(a, 0); }
+    double stop() {
+        (void)hipEventRecord(b, 0);
+        (void)hipEventSynchronize(b);
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, a, b);
+        return (double)ms;
+    }
+};
+}  // namespace
+
+// ---- the stages of render() main.cpp:169-258, shared by cgrt_ppm_render (one call) and a live cgrt_ppm_session ----------
+// eye(): the Hitpoint records of a grid or of a ray buffer; table(): the reference's table order and the per-pixel index over
+// them (PpmTable).  photon_setup() + photons(last): photons [done, last) in batches.  gather(): the image at the current
+// photon count.  Photon i always draws from the keyed stream
+// (seed, i) and a hitpoint replays its events in photon order, so the state after photons [0, a) then [a, b) is the state
+// after [0, b): how the photons are split into calls and batches never shows in the result.
+struct cgrt_ppm_session {
+    const cgrt_scene *s = nullptr;
+    cgrt_photons ph{};
+    // the image the session gathers into, the gather's normaliser and the photons' depth limit: a grid session's grid.width,
+    // .rows, .spp, .max_depth; a ray session's cgrt_ray_pixels and rays->max_depth
+    int width = 0, rows = 0, spp = 1, max_depth = 0;
+    bool striped = false;  // grid session over block-cyclic rows: no rgb8
+    bool lookahead = false;  // session: trace the next batch on the producer stream when a call ends
+    PpmTable tab;            // the hitpoints in table order and the per-pixel index
+    int64_t dev_bytes = 0;  // what this state allocated itself (the table, sort scratch and producer buffers are added by bytes())
+    DevBuf pk0, pk1, pv0, pv1, npairs;          // (hitpoint, event) pairs of one batch
+    DevBuf img, rgb8;                           // session: device image of cgrt_ppm_session_image (host outputs)
+    GrowBuf main_tmp;
+    PhotonProducer pp;  // declared last of the buffers: its destructor waits for its stream before they are freed
+    PpmSchedule sched;  // the setup, which photons are applied (sched.done), the batch size, the batch traced ahead
+    uint64_t n_events = 0, n_pairs = 0;
+    double ms_eye = 0, ms_table = 0, ms_photons = 0, ms_last_add = 0;
+    mutable double ms_last_image = 0;
+    mutable hipEvent_t img_a = nullptr, img_b = nullptr;  // session: brackets the last gather (on the stream it ran on)
+    mutable bool img_pending = false;                     // img_b recorded, ms_last_image not yet read from it
+
+    ~cgrt_ppm_session() {
+        if (img_b) (void)hipEventSynchronize(img_b);
+        if (img_a) (void)hipEventDestroy(img_a);
+        if (img_b) (void)hipEventDestroy(img_b);
+    }
+    hipError_t take(DevBuf &b, size_t bytes) {
+        dev_bytes += (int64_t)bytes;
+        return b.alloc(bytes);
+    }
+    int64_t bytes() const { return dev_bytes + tab.dev_bytes + sched.setup.producer_bytes + (int64_t)main_tmp.cap + (int64_t)pp.tmp.cap; }
+    void frame(int width_, int rows_, int spp_, int max_depth_, bool striped_) {
+        width = width_; rows = rows_; spp = spp_; max_depth = max_depth_;
+        striped = striped_;
+    }
+    template <class Capture> int eye(const cgrt_scene *s_, const cgrt_photons *ph_, Capture capture, DevBuf &rec);
+    int table(DevBuf &rec, const int64_t *ray_pixel, bool rays);
+    int photon_setup(bool session);
+    int photons(long long last, bool keep_ahead, const cgrt_photon_rays *pr = nullptr);
+    int gather(double *d_img, unsigned char *d_rgb8, hipStream_t st) const;
+};
+
+// ---- eye pass: hitpoint records, device resident (count first, then capture).  capture(cap, &d_rec, &count) is
+// hitpoints_device over a grid or ray_hitpoints_device over a ray buffer; frame() has been called ----
+template <class Capture>
+int cgrt_ppm_session::eye(const cgrt_scene *s_, const cgrt_photons *ph_, Capture capture, DevBuf &rec) {
+    s = s_; ph = *ph_;
+    Timer tm;
+    tm.start();
+    uint64_t nhp = 0;
+    int rc = capture(0, nullptr, &nhp);
+    if (rc) return rc;
+    tab.npix = (long long)rows * width;
+    tab.n = (size_t)nhp;
+    if (tab.n >= (1ull << 31)) return fail(CGRT_ERR_LIMIT, "photon pass: more than 2^31 hitpoints");
+    if (tab.n) {
+        double *d_rec = nullptr;
+        rc = capture(nhp, &d_rec, &nhp);
+        rec.p = d_rec;
+        if (rc) return rc;
+    }
+    ms_eye = tm.stop();
+    return CGRT_OK;
+}
+static auto grid_capture(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid) {
+    return [=](uint64_t cap, double **d_rec, uint64_t *count) { return hitpoints_device(s, cam, grid, cap, d_rec, count); };
+}
+
+int cgrt_ppm_session::table(DevBuf &rec, const int64_t *ray_pixel, bool rays) {
+    Timer tm;
+    tm.start();
+    if (const int rc = tab.build(rec, ph, spp, ray_pixel, rays, main_tmp)) return rc;
+    ms_table = tm.stop();
+    return CGRT_OK;
+}
+
+// Batch size, pair buffers and the producer (ppm_setup decides)
+int cgrt_ppm_session::photon_setup(bool session) {
+    sched.start(ppm_setup(ph, tab.n, session, photon_overlap_allowed()));
+    const PpmSetup &setup = sched.setup;
+    if (setup.nbuf)
+        if (const int rc = pp.init(setup.nbuf, (size_t)setup.batch * kSegStride, setup.overlap)) return rc;
+    HIP_TRY(take(pk0, (size_t)setup.pair_cap * 8)); HIP_TRY(take(pk1, (size_t)setup.pair_cap * 8));
+    HIP_TRY(take(pv0, (size_t)setup.pair_cap * 4)); HIP_TRY(take(pv1, (size_t)setup.pair_cap * 4));
+    HIP_TRY(take(npairs, 16));
+    return CGRT_OK;
+}
+
+// Photons [done, last), applied on the null stream, batch by batch as `sched` decides.  keep_ahead: when the range is done,
+// the next batch from `done` is enqueued on the producer stream for the next call; otherwise nothing is traced beyond `last`
+// and the producer stream is drained.
+// pr: the photons [done, last) are the caller's (pr->n = last - done; DEVICE arrays) instead of the built-in emitter's.  Inside the
+// call batch k+1 is traced under batch k's replay as ever; a batch traced ahead by an earlier add_photons is not pr's and is
+// dropped, and the caller passes keep_ahead = false: the photons after `last` are not known, and the drain is what makes pr's
+// arrays read before the call returns.
+int cgrt_ppm_session::photons(long long last, bool keep_ahead, const cgrt_photon_rays *pr) {
+    if (!sched.begin(last, pr != nullptr, tab.n == 0)) return CGRT_OK;  // no hitpoint can change: nothing to trace
+    const long long call_first = sched.done;
+    // enqueue batch b on the producer; from: the caller's arrays, read at photon b.first of this call, or null: the emitter
+    auto produce = [&](const PpmBatch &b, const cgrt_photon_rays *from) {
+        const PhotonArgs pa = photon_args(ph, b.first, b.count, max_depth);
+        if (!from) return pp.produce(s, pa, tab.ha, b.buf);
+        const size_t k = (size_t)(b.first - call_first);
+        PhotonRayArgs ra;
+        ra.org = from->org3 + 3 * k;
+        ra.dir = from->dir3 + 3 * k;
+        ra.flux = from->flux3 + 3 * k;
+        ra.keys = from->keys ? reinterpret_cast<const unsigned long long *>(from->keys) + k : nullptr;
+        ra.draws = from->draws ? from->draws + k : nullptr;
+        return pp.produce(s, pa, tab.ha, b.buf, &ra);
+    };
+    const int T = 256;
+    const unsigned nb = (unsigned)((tab.n + T - 1) / T);
+    int rc = CGRT_OK;
+    while (sched.more()) {
+        const PpmBatch b = sched.next();
+        const int nslots = b.count * kSegStride, cur = b.buf;
+        if (!b.reuse && (rc = produce(b, pr))) return rc;
+        // the NEXT batch now, so that it is traced under this batch's search, sort and replay
+        const PpmBatch nx = sched.following(b);
+        if (nx.count) {
+            if ((rc = produce(nx, pr))) return rc;
+            sched.set_ahead(nx);
+        }
+        if (pp.st) HIP_TRY(hipStreamWaitEvent(0, pp.produced[cur], 0));
+        HIP_TRY(hipMemsetAsync(npairs.p, 0, 16, 0));
+        hipLaunchKernelGGL(photon_pairs_kernel, dim3((nslots + T - 1) / T), dim3(T), 0, 0, pp.ev[cur].as<double>(),
+                           pp.ek1[cur].as<unsigned int>(), pp.eo1[cur].as<unsigned int>(), nslots, tab.ha, tab.hps.as<double>(),
+                           tab.bstart.as<int>(), pk0.as<unsigned long long>(), pv0.as<unsigned int>(), npairs.as<unsigned long long>(),
+                           sched.setup.pair_cap);
+        HIP_TRY(hipGetLastError());
+        unsigned long long np2[2] = {0, 0};  // pairs (the full 64-bit count, stored or not), events
+        HIP_TRY(hipMemcpy(np2, npairs.p, 16, hipMemcpyDeviceToHost));
+        const PpmOutcome o = sched.counted(b, np2[0]);
+        if (o != kPpmApplied) {  // nothing has been applied yet
+            if ((rc = pp.release(cur))) return rc;
+            if (o == kPpmLimit) return fail(CGRT_ERR_LIMIT, "photon pass: one photon's pairs exceed the pair buffer");
+            continue;
+        }
+        const unsigned int np = (unsigned int)np2[0];  // <= pair_cap <= 2^27
+        n_events += np2[1];
+        if (np != 0) {
+            n_pairs += np;
+            rc = sort_pairs(main_tmp, pk0.as<unsigned long long>(), pk1.as<unsigned long long>(), pv0.as<unsigned int>(),
+                            pv1.as<unsigned int>(), np, sched.setup.pair_key_bits);
+            if (rc) return rc;
+            hipLaunchKernelGGL(photon_apply_kernel, dim3(nb), dim3(T), 0, 0, pk1.as<unsigned long long>(), pv1.as<unsigned int>(), np,
+                               pp.ev[cur].as<double>(), ph.alpha, tab.hp.as<double>(), tab.hps.as<double>(), (long long)tab.n);
+            HIP_TRY(hipGetLastError());
+        }
+        if ((rc = pp.release(cur))) return rc;
+    }
+    bool drain = false;
+    const PpmBatch ahead = sched.end(keep_ahead, &drain);  // the lookahead is the built-in emitter's, whoever's the call's photons were
+    if (ahead.count) {
+        if ((rc = produce(ahead, nullptr))) return rc;
+        sched.set_ahead(ahead);
+    }
+    if (drain && pp.st) HIP_TRY(hipStreamSynchronize(pp.st));
+    return CGRT_OK;
+}
+
+// The image at `done` photons into device buffers (either may be null), enqueued on `st`.
+int cgrt_ppm_session::gather(double *d_img, unsigned char *d_rgb8, hipStream_t st) const {
+    const int T = 256;
+    hipLaunchKernelGGL(ppm_gather_kernel, dim3((unsigned)((tab.npix + T - 1) / T)), dim3(T), 0, st,
+                       static_cast<const unsigned int *>(tab.pix_start.p), static_cast<const unsigned int *>(tab.order.p),
+                       static_cast<const double *>(tab.hp.p), (double)sched.done * spp, tab.npix, width, rows, d_img, d_rgb8);
+    HIP_TRY(hipGetLastError());
+    return CGRT_OK;
+}
+
+static int check_photons(const cgrt_photons *ph) {
+    if (ph->nphotons < 0 || ph->hashsize < 1 || ph->hashsize > (1 << 20) || ph->batch < 0 || !(ph->initial_radius >= 0) ||
+        ph->pair_cap < 0)
+        return fail(CGRT_ERR_INVALID, "bad photon parameters");
+    return CGRT_OK;
+}
+
+extern "C" int cgrt_ppm_render(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid,
+                               const cgrt_photons *ph, cgrt_ppm_result *out) {
+    int rc = check_grid(s, cam, grid);
+    if (rc) return rc;
+    if (!ph || !out) return fail(CGRT_ERR_INVALID, "null argument");
+    if ((rc = check_photons(ph))) return rc;
+    if (grid->stripe_nranks > 1 && out->rgb8)
+        return fail(CGRT_ERR_UNSUPPORTED, "photon pass: rgb8 needs contiguous rows; tone-map the assembled frame (cgrt_tonemap_rgb8)");
+    ON_DEVICE(s->device);
+    cgrt_ppm_session run;
+    run.frame(grid->width, grid->rows, grid->spp, grid->max_depth, grid->stripe_nranks > 1);
+    {
+        DevBuf rec;
+        rc = run.eye(s, ph, grid_capture(s, cam, grid), rec);
+        out->ms_eye = run.ms_eye;
+        if (rc == CGRT_OK) rc = run.table(rec, nullptr, false);
+        out->ms_table = run.ms_table;
+        if (rc) return rc;
+    }
+    // ---- photons, in batches ----
+    Timer tm;
+    tm.start();
+    rc = run.photon_setup(false);
+    if (rc == CGRT_OK) rc = run.photons(ph->nphotons, false);
+    out->n_events = run.n_events;
+    out->n_pairs = run.n_pairs;
+    out->n_batch_halvings = run.sched.n_halvings;
+    if (rc) return rc;
+    out->ms_photons = tm.stop();
+    // ---- final gather + tone map ----
+    tm.start();
+    const long long npix = run.tab.npix;
+    DevBuf img, rgb8;
+    HIP_TRY(img.alloc((size_t)npix * 3 * sizeof(double)));
+    if (out->rgb8) HIP_TRY(rgb8.alloc((size_t)npix * 3));
+    rc = run.gather(img.as<double>(), out->rgb8 ? rgb8.as<unsigned char>() : nullptr, 0);
+    if (rc) return rc;
+    out->ms_gather = tm.stop();
+    if (out->image) HIP_TRY(hipMemcpy(out->image, img.p, (size_t)npix * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out->rgb8) HIP_TRY(hipMemcpy(out->rgb8, rgb8.p, (size_t)npix * 3, hipMemcpyDeviceToHost));
+    out->hp_count = run.tab.n;
+    if (out->hp16 && out->hp_cap) {
+        const size_t m = run.tab.n < out->hp_cap ? run.tab.n : (size_t)out->hp_cap;
+        HIP_TRY(hipMemcpy(out->hp16, run.tab.hp.p, m * 16 * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return CGRT_OK;
+}
+
+// ---- resumable photon mapping: the state above, kept between calls -------------------------------------------------
+// What both creators do behind their argument checks: the session and its events, the eye pass (capture: see eye()), the table
+// (ray_pixel, rays: see PpmTable::build), the photon buffers and ph->nphotons photons.
+template <class Capture>
+static int session_create(const cgrt_scene *s, const cgrt_photons *ph, int flags, int width, int rows, int spp, int max_depth,
+                          bool striped, Capture capture, const int64_t *ray_pixel, bool rays, cgrt_ppm_session **out) {
+    ON_DEVICE(s->device);
+    std::unique_ptr<cgrt_ppm_session> p(new (std::nothrow) cgrt_ppm_session());
+    if (!p) return fail(CGRT_ERR_LIMIT, "out of host memory");
+    p->lookahead = !(flags & CGRT_PPM_SESSION_NO_LOOKAHEAD);
+    p->frame(width, rows, spp, max_depth, striped);
+    HIP_TRY(hipEventCreate(&p->img_a));
+    HIP_TRY(hipEventCreate(&p->img_b));
+    int rc = CGRT_OK;
+    {
+        DevBuf rec;
+        if ((rc = p->eye(s, ph, capture, rec))) return rc;
+        if ((rc = p->table(rec, ray_pixel, rays))) return rc;
+        if (rays) HIP_TRY(hipDeviceSynchronize());  // ray_pixel and the records are read before the call returns
+    }
+    Timer tm;
+    tm.start();
+    rc = p->photon_setup(true);
+    if (rc == CGRT_OK) rc = p->photons(p->ph.nphotons, p->lookahead);
+    p->ms_last_add = tm.stop();
+    p->ms_photons = p->ms_last_add;
+    if (rc) return rc;
+    *out = p.release();
+    return CGRT_OK;
+}
+
+extern "C" int cgrt_ppm_session_create(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid,
+                                       const cgrt_photons *ph, int flags, cgrt_ppm_session **out) {
+    if (!out) return fail(CGRT_ERR_INVALID, "null argument");
+    *out = nullptr;
+    int rc = check_grid(s, cam, grid);
+    if (rc) return rc;
+    if (!ph) return fail(CGRT_ERR_INVALID, "null argument");
+    if ((rc = check_photons(ph))) return rc;
+    if (flags & ~CGRT_PPM_SESSION_NO_LOOKAHEAD) return fail(CGRT_ERR_INVALID, "unknown session flags");
+    return session_create(s, ph, flags, grid->width, grid->rows, grid->spp, grid->max_depth, grid->stripe_nranks > 1,
+                          grid_capture(s, cam, grid), nullptr, false, out);
+}
+
+extern "C" int cgrt_ppm_session_create_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_pixels *px,
+                                            const cgrt_photons *ph, int flags, cgrt_ppm_session **out) {
+    if (!out) return fail(CGRT_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!s || !rays || !px || !ph) return fail(CGRT_ERR_INVALID, "null argument");
+    if (px->width <= 0 || px->rows <= 0 || px->spp <= 0) return fail(CGRT_ERR_INVALID, "ray pixels: width, rows and spp must be positive");
+    if ((long long)px->width * px->rows >= (1ll << 31)) return fail(CGRT_ERR_LIMIT, "ray pixels: 2^31 texels or more");
+    int rc = check_photons(ph);
+    if (rc) return rc;
+    if (flags & ~CGRT_PPM_SESSION_NO_LOOKAHEAD) return fail(CGRT_ERR_INVALID, "unknown session flags");
+    if ((rc = check_capture_rays(s, rays))) return rc;  // (the last of the checks: it is the one that looks at the scene's state)
+    const auto capture = [=](uint64_t cap, double **d_rec, uint64_t *count) {
+        return ray_hitpoints_device(s, rays, px->pixel, cap, d_rec, count);
+    };
+    return session_create(s, ph, flags, px->width, px->rows, px->spp, rays->max_depth, false, capture, px->pixel, true, out);
+}
+
+extern "C" void cgrt_ppm_session_destroy(cgrt_ppm_session *p) {
+    if (!p) return;
+    DeviceGuard g(p->s->device);
+    if (g.err == hipSuccess) (void)hipStreamSynchronize(0);
+    delete p;  // waits for the last gather and the producer stream (lookahead) before freeing
+}
+
+// `count` more photons: the built-in emitter's, or (pr) the caller's
+static int session_add(cgrt_ppm_session *p, long long count, const cgrt_photon_rays *pr) {
+    ON_DEVICE(p->s->device);
+    if (p->img_pending) HIP_TRY(hipStreamWaitEvent(0, p->img_b, 0));  // a gather on a caller's stream reads hp
+    // the producer stream does not wait for the null stream: arrays a kernel on the null stream still writes must be complete
+    if (pr && p->pp.st) HIP_TRY(hipStreamSynchronize(0));
+    Timer tm;
+    tm.start();
+    const int rc = p->photons(p->sched.done + count, pr ? false : p->lookahead, pr);
+    if (pr) {  // also when a batch failed: nothing traced ahead from pr's arrays outlives the call
+        p->sched.drop_ahead();
+        if (p->pp.st) {
+            const hipError_t e = hipStreamSynchronize(p->pp.st);
+            if (e != hipSuccess && rc == CGRT_OK) return fail(CGRT_ERR_DEVICE, std::string("producer stream: ") + hipGetErrorString(e));
+        }
+    }
+    p->ms_last_add = tm.stop();  // also when a batch failed: what was applied before it has finished
+    p->ms_photons += p->ms_last_add;
+    return rc;
+}
+
+extern "C" int cgrt_ppm_session_add_photons(cgrt_ppm_session *p, int64_t count) {
+    if (!p || count < 0 || count > LLONG_MAX - p->sched.done) return fail(CGRT_ERR_INVALID, "bad argument");
+    return session_add(p, count, nullptr);
+}
+
+extern "C" int cgrt_ppm_session_add_photon_rays(cgrt_ppm_session *p, const cgrt_photon_rays *pr) {
+    if (const int rc = check_photon_rays(pr)) return rc;
+    if (!p || pr->n > LLONG_MAX - p->sched.done) return fail(CGRT_ERR_INVALID, "bad argument");
+    if (pr->n == 0) return CGRT_OK;
+    return session_add(p, pr->n, pr);
+}
+
+static int session_image_args(const cgrt_ppm_session *p, const uint8_t *rgb8) {
+    if (!p) return fail(CGRT_ERR_INVALID, "null session");
+    if (p->sched.done == 0) return fail(CGRT_ERR_INVALID, "photon session: no photon yet (the image would be flux / (PI r2 0))");
+    if (rgb8 && p->striped)
+        return fail(CGRT_ERR_UNSUPPORTED, "photon session: rgb8 needs contiguous rows; tone-map the assembled frame (cgrt_tonemap_rgb8)");
+    return CGRT_OK;
+}
+
+extern "C" int cgrt_ppm_session_image(const cgrt_ppm_session *cp, double *image, uint8_t *rgb8) {
+    int rc = session_image_args(cp, rgb8);
+    if (rc) return rc;
+    cgrt_ppm_session *p = const_cast<cgrt_ppm_session *>(cp);  // the image buffers are scratch, not state
+    ON_DEVICE(p->s->device);
+    const size_t npix = (size_t)p->tab.npix;
+    if (image && !p->img.p) HIP_TRY(p->take(p->img, npix * 3 * sizeof(double)));
+    if (rgb8 && !p->rgb8.p) HIP_TRY(p->take(p->rgb8, npix * 3));
+    HIP_TRY(hipEventRecord(p->img_a, 0));
+    rc = p->gather(image ? p->img.as<double>() : nullptr, rgb8 ? p->rgb8.as<unsigned char>() : nullptr, 0);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(p->img_b, 0));
+    HIP_TRY(hipEventSynchronize(p->img_b));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, p->img_a, p->img_b));
+    p->ms_last_image = ms;
+    p->img_pending = false;
+    if (image) HIP_TRY(hipMemcpy(image, p->img.p, npix * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (rgb8) HIP_TRY(hipMemcpy(rgb8, p->rgb8.p, npix * 3, hipMemcpyDeviceToHost));
+    return CGRT_OK;
+}
+
+extern "C" int cgrt_ppm_session_image_device(const cgrt_ppm_session *p, double *image, uint8_t *rgb8, void *stream) {
+    int rc = session_image_args(p, rgb8);
+    if (rc) return rc;
+    ON_DEVICE(p->s->device);
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipEventRecord(p->img_a, st));
+    if ((rc = p->gather(image, rgb8, st))) return rc;
+    HIP_TRY(hipEventRecord(p->img_b, st));
+    p->img_pending = true;  // the next add_photons waits for it; get_info reads its time
+    return CGRT_OK;
+}
+
+extern "C" int cgrt_ppm_session_hitpoints(const cgrt_ppm_session *p, double *hp16, uint64_t cap, uint64_t *count) {
+    if (!p || !count || (cap > 0 && !hp16)) return fail(CGRT_ERR_INVALID, "bad argument");
+    ON_DEVICE(p->s->device);
+    *count = p->tab.n;
+    const size_t m = p->tab.n < cap ? p->tab.n : (size_t)cap;
+    if (m) HIP_TRY(hipMemcpy(hp16, p->tab.hp.p, m * 16 * sizeof(double), hipMemcpyDeviceToHost));
+    return CGRT_OK;
+}
+
+extern "C" int cgrt_ppm_session_get_info(const cgrt_ppm_session *p, cgrt_ppm_session_info *out) {
+    if (!p || !out) return fail(CGRT_ERR_INVALID, "null argument");
+    if (p->img_pending) {
+        ON_DEVICE(p->s->device);
+        HIP_TRY(hipEventSynchronize(p->img_b));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, p->img_a, p->img_b));
+        p->ms_last_image = ms;
+        p->img_pending = false;
+    }
+    out->photons_done = p->sched.done;
+    out->hp_count = p->tab.n;
+    out->n_events = p->n_events;
+    out->n_pairs = p->n_pairs;
+    out->n_batch_halvings = p->sched.n_halvings;
+    out->device_bytes = p->bytes();
+    out->ms_eye = p->ms_eye;
+    out->ms_table = p->ms_table;
+    out->ms_photons = p->ms_photons;
+    out->ms_last_add = p->ms_last_add;
+    out->ms_last_image = p->ms_last_image;
+    return CGRT_OK;
+}

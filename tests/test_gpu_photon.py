@@ -63,7 +63,7 @@ def test_pair_buffer_overflow_path_matches_reference_golden(gpu_ready, case):
 
 def test_producer_stream_overlap_is_invisible(gpu_ready, monkeypatch):
     """With more photons than one batch the next batch is traced on a second stream while the current one is searched and
-    replayed (cgrt_photon.hpp PhotonProducer), enqueued BEFORE the current batch's pair count is known.  Checked here: the
+    replayed (cgrt_ppm_apply.hpp PhotonProducer), enqueued BEFORE the current batch's pair count is known.  Checked here: the
     overlapped run equals the single-stream run (CGRT_PHOTON_OVERLAP=0) and the reference golden bit for bit, also when
     the pair buffer overflows so that batches enqueued ahead no longer match the plan and are produced again."""
     import cgraytracing_amd as cg

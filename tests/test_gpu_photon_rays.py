@@ -122,7 +122,7 @@ def test_emitted_photons_through_add_photon_rays_equal_add_photons(gpu_ready, ca
             ses.add_photons(nph - k)
             a_two = _state(ses)
     assert a["n_events"] > 0 and a["n_pairs"] > 0 and a["hp"][:, 15].max() > 0
-    # n_pairs counts the candidates that pass the radius each Hitpoint had when their BATCH began (cgrt_photon.hpp, step 2), so
+    # n_pairs counts the candidates that pass the radius each Hitpoint had when their BATCH began (cgrt_ppm_session.hpp, step 2), so
     # unlike everything else it depends on where the batches begin, through either door: 1961 against 1966 on c2_48x36 between
     # one call and the chunked calls.  It is compared where the batches are the same -- the old door fed in the same calls -- and
     # everything else also against the single add_photons call.
