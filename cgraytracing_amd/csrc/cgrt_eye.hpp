@@ -16,6 +16,18 @@ struct Pending {  // a refracted child waiting for its turn (main.cpp:157)
 // pending-ray storage (LDS levels, sibling registers) is compiled out and occupancy goes up.
 // SPH: every object is a sphere (C1/C2-type scenes): specialised object loop.
 // HPS: additionally append every Hitpoint {f, pos, normal} (hitpoints.h:6-20, main.cpp:87-98) to a global stream.
+// DIFF (SPH without GLASS): the terminal-diffuse body for tiles none of whose rays can meet a reflecting or refracting sphere
+// (class 3 of tile_order_kernel): every ray ends at its first hit with adj == (1, 1, 1), so neither the hit point, the normal,
+// the material dispatch nor any pending-ray state exists in it.
+#ifndef CGRT_DIFF_WAVES
+#define CGRT_DIFF_WAVES 8
+#endif
+#ifndef CGRT_DIFF_DOF_WAVES
+#define CGRT_DIFF_DOF_WAVES 6
+#endif
+// waves per SIMD the DIFF variants are compiled for: the pinhole one fits 8 (52 VGPRs); the thin-lens one spills 4 VGPRs at 8
+// (64) and is compiled for 6
+static constexpr int kDiffWaves = CGRT_DIFF_WAVES, kDiffDofWaves = CGRT_DIFF_DOF_WAVES;
 #ifndef CGRT_BEZ_WAVES
 #define CGRT_BEZ_WAVES 2
 #endif
@@ -80,11 +92,13 @@ __device__ __forceinline__ bool wave_has_tile(const GridParams &g, int tile_bloc
 // wave owns one wave tile (16x4 pixels, one per lane) and every lane runs its pixel's samples; true -- the waves serve the
 // queue of heavy-tile items, lanes drawing (pixel, sample) units.  tile_block / tile_grid: this workgroup's index among the
 // tile workgroups and their number (the launch may put heavy workgroups in front of them).
-template <bool TREES, bool BEZ, bool DOF, bool GLASS, bool SPH, bool STATS, bool HPS, int NT, bool HEAVY, bool SPILL = false, bool HFONLY = false>
+template <bool TREES, bool BEZ, bool DOF, bool GLASS, bool SPH, bool STATS, bool HPS, int NT, bool HEAVY, bool SPILL = false, bool HFONLY = false,
+          bool DIFF = false>
 __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const GridParams &g, float *__restrict__ rgb,
                                                 uint32_t *__restrict__ nhit_out, unsigned long long *__restrict__ counters,
                                                 const HitpointSink &hps, int tile_block, int tile_grid) {
     using TG = TileGeom<NT>;
+    static_assert(!DIFF || (SPH && !GLASS && !HPS && !HEAVY && !STATS && !SPILL), "DIFF: the sphere loop, first hits only");
     const long long tl_t0 = g.timeline ? wall_clock64() : 0;
     if (!HEAVY && !g.timeline) {  // (the timeline, a development aid, wants a record from every workgroup)
         if (!__syncthreads_or((int)wave_has_tile<NT>(g, tile_block, tile_grid))) return;
@@ -317,30 +331,37 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
             pre_valid = false;
         }
         const SceneHit hit =
-            intersect_scene<TREES, BEZ, SPH, STATS, SPILL, PRE, HFONLY>(lobjs, sc.n_lds, sc.n_objs, sc, o, d, rk, have, aux, my_nodes, my_tris);
+            intersect_scene<TREES, BEZ, SPH, STATS, SPILL, PRE, HFONLY, !SPH>(lobjs, sc.n_lds, sc.n_objs, sc, o, d, rk, have, aux, my_nodes, my_tris);
         if (have) {
             my_rays++;
             have = false;
             if (hit.id >= 0) {
                 const ObjMat ob = load_mat<SPILL>(lobjs, sc.n_lds, sc.objs, hit.id);
-                const V3 P = o + d * hit.t;  // main.cpp:68
-                V3 n = hit.n;
-                const V3 n_old = n;
+                // hit point, normal and side.  SPH: the walk leaves the sphere's normal to the branches that use it -- the ray
+                // that ends on a diffuse sphere needs none of this (normalized and sqrt_cr ballot over the lanes that are there)
+                V3 P = o, n = d, n_old = d;
                 bool into = true;
-                if (dot(n, d) > 0) {  // main.cpp:73-76
-                    n = -n;
-                    into = false;
-                }
+                auto surface = [&]() {
+                    P = o + d * hit.t;  // main.cpp:68
+                    n = SPH ? normalized(P - load_centre<SPILL>(lobjs, sc.n_lds, sc.objs, hit.id)) : hit.n;  // objects.h:65-66
+                    n_old = n;
+                    into = true;
+                    if (dot(n, d) > 0) {  // main.cpp:73-76
+                        n = -n;
+                        into = false;
+                    }
+                };
+                if (!SPH) surface();
                 V3 f = ob.col;  // getSurfaceColor
-                if (ob.kind == KIND_PLANE && ob.tex >= 0) {
+                if (!SPH && ob.kind == KIND_PLANE && ob.tex >= 0) {
                     V3 c;
                     if (texture_color(sc.texs[ob.tex], sc.texels, P, c)) f = c;  // objects.h:533-539
                 }
                 const double refl = ob.refl, transp = ob.transp;
-                if (refl < kEps && transp < kEps) {
+                if (DIFF || (refl < kEps && transp < kEps)) {
                     UTIL(heavy ? 7 : 12);
-                    // diffuse: the reference stores Hitpoint{f*adj,...} (main.cpp:85-100); we accumulate it
-                    const V3 hf = mulv(f, adj);
+                    // diffuse: the reference stores Hitpoint{f*adj,...} (main.cpp:85-100); we accumulate it (DIFF: adj is 1)
+                    const V3 hf = DIFF ? f : mulv(f, adj);
                     if (heavy) {
                         // deferred: the value is added in deferred_sum_kernel, in this (sample, emission) position
                         double *q = g.dvals + ((((size_t)unit_rank * g.spp + unit_smp) * g.maxhp + hp_seq) * 64 + unit_pix) * 3;
@@ -353,6 +374,7 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
                         acc_b += hf.z;
                     }
                     my_hits++;
+                    if (HPS && SPH) surface();
                     if (HPS) {
                         // one atomic per wave, not per lane (same-address atomics are served one after the other): the lanes
                         // that are here take consecutive places behind the count their first lane fetched
@@ -374,6 +396,7 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
                     }
                     if (HPS || heavy) hp_seq++;
                 } else if (depth_left > 1) {
+                    if (SPH) surface();
                     if (transp < kEps) {
                         // mirror, main.cpp:129-134
                         const V3 nd = d - n * 2.0 * dot(n, d);
@@ -569,23 +592,44 @@ __device__ __forceinline__ void wg_counters_end(const unsigned long long *wg, un
 }
 
 // One launch = tile workgroups only (probe, image order, Hitpoint capture) ...
-template <bool TREES, bool BEZ, bool DOF, bool GLASS, bool SPH, bool STATS, bool HPS = false, int NT = 256, bool SPILL = false, bool HFONLY = false>
-__global__ __launch_bounds__(NT, BEZ ? kBezWaves : ((TREES && !HFONLY) ? kTreeWaves : 4)) void trace_grid_kernel(DeviceScene sc, GridParams g, float *__restrict__ rgb,
+template <bool TREES, bool BEZ, bool DOF, bool GLASS, bool SPH, bool STATS, bool HPS = false, int NT = 256, bool SPILL = false, bool HFONLY = false,
+          bool DIFF = false>
+__global__ __launch_bounds__(NT, DIFF ? (DOF ? kDiffDofWaves : kDiffWaves) : BEZ ? kBezWaves : ((TREES && !HFONLY) ? kTreeWaves : 4)) void trace_grid_kernel(DeviceScene sc, GridParams g, float *__restrict__ rgb,
                                                              uint32_t *__restrict__ nhit_out,
                                                              unsigned long long *__restrict__ counters,
                                                              HitpointSink hps = HitpointSink{nullptr, nullptr, 0}) {
-    __shared__ unsigned long long wg_cnt[CGRT_NCOUNTERS];
-    unsigned long long *wc = wg_counters_begin(wg_cnt, counters);
-    // tile_order: the workgroup's tile comes from tile_order_kernel's list (the body's tile-queue entry: a literal tile number)
+    // tile_order: the workgroup's tile comes from tile_order_kernel's list (the body's tile-queue entry: a literal tile number).
+    // A pair of launches shares the list (kOrderFull: the entries of classes 0-2, kOrderDiffuse: those of class 3, the DIFF
+    // variant); the host does not know where class 3 begins, so both are launched over all tiles and a workgroup beyond its
+    // launch's part leaves here, before anything else.
     int tile_block = (int)blockIdx.x, tile_grid = (int)gridDim.x;
     if (g.tile_order) {
-        tile_block = (int)load_uniform(g.border + blockIdx.x);
+        unsigned entry = blockIdx.x;
+        if (g.tile_order != kOrderAll) {
+            const unsigned first_diffuse = load_uniform(g.plan + 3);
+            if (g.tile_order == kOrderDiffuse) entry += first_diffuse;
+            if (g.tile_order == kOrderDiffuse ? entry >= load_uniform(g.plan + kOrderClasses) : entry >= first_diffuse) return;
+        }
+        tile_block = (int)load_uniform(g.border + entry);
         tile_grid = -1;
+#ifdef CGRT_DIFF_ONE_LAUNCH  // EXPERIMENT (make exp NAME=diff1 DEFS=-DCGRT_DIFF_ONE_LAUNCH): one launch over the
+        // whole list, its class-3 workgroups branching into the DIFF body here -- at the full kernel's registers
+        if (SPH && GLASS && !STATS && !HPS && !SPILL && g.tile_order == kOrderAll && blockIdx.x >= load_uniform(g.plan + 3)) {
+            __shared__ unsigned long long wg_cnt1[CGRT_NCOUNTERS];
+            unsigned long long *wc1 = wg_counters_begin(wg_cnt1, counters);
+            trace_grid_body<TREES, BEZ, DOF, false, SPH, false, false, NT, false, false, HFONLY, SPH && GLASS && !STATS && !HPS && !SPILL>(
+                sc, g, rgb, nhit_out, wc1, hps, tile_block, tile_grid);
+            wg_counters_end(wg_cnt1, counters);
+            return;
+        }
+#endif
 #ifdef CGRT_TILE_ORDER_PRIO  // EXPERIMENT (make exp): issue priority for the workgroups of classes 0-2, for the whole tile
         if (blockIdx.x < load_uniform(g.plan + 3)) __builtin_amdgcn_s_setprio(3);
 #endif
     }
-    trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid);
+    __shared__ unsigned long long wg_cnt[CGRT_NCOUNTERS];
+    unsigned long long *wc = wg_counters_begin(wg_cnt, counters);
+    trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid);
     wg_counters_end(wg_cnt, counters);
 }
 // ... or the scheduled form: the first g.heavy_blocks workgroups serve the heavy tiles' unit queue, the others are the tile
@@ -760,11 +804,16 @@ __global__ void classify_kernel(DeviceScene sc, GridParams g, unsigned char *__r
 // workgroup index it gets changes, so image, hit counts and counters are bit for bit the row-major launch's.
 //   class 0: the tile's centre direction hits a refracting sphere itself     class 2: ... a sphere that only reflects
 //   class 1: some primary ray of the tile may touch a refracting sphere      class 3: everything else
-// (1 and 2 by the test above over the tile's wave tiles; a doubtful case only moves a tile forward).  One thread per wave tile
+// (1 and 2 by the test above over the tile's wave tiles; a doubtful case moves a tile forward, never into class 3).  One thread per wave tile
 // classes it; the last workgroup through (plan[kOrderArrived], reset for the next launch) folds the wave tiles into tiles
 // and writes list[] = a stable counting sort by class, row-major within a class, plan[c] = tiles of classes < c (c = 0..4).
-// The sorting pass reads back only class bytes its own thread wrote, so list[] is a permutation of the tiles whatever it saw
-// of the other workgroups' bytes.
+// The sorting pass reads back only tile-class bytes its own thread wrote, so list[] is a permutation of the tiles in any case.
+// Class 3 is more than a place in the order: in a sphere-only scene its tiles are rendered by the terminal-diffuse variant
+// (trace_grid_kernel<..., DIFF>), which is exact only where no ray of the tile can meet a special sphere.  So the test must err
+// towards classes 1 / 2 alone -- it does: cone 1.5 x the corner angle, the bound grown by the lens blur, anything behind or around
+// the camera doubtful -- and the last workgroup must see every other workgroup's wave-tile classes: each workgroup fences its
+// wcls[] stores before its thread 0 counts it in at plan[kOrderArrived] (device-scope atomic), and the last one fences again
+// before it reads them.
 __global__ __launch_bounds__(1024) void tile_order_kernel(GridParams g, OrderSpheres sp, int tiles_x, int tiles_y, uint32_t *__restrict__ plan,
                                                           uint32_t *__restrict__ list, unsigned char *__restrict__ tcls,
                                                           unsigned char *__restrict__ wcls) {

@@ -5,6 +5,7 @@
 #ifndef CGRT_FRAME_H
 #define CGRT_FRAME_H
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
@@ -46,7 +47,9 @@ struct GridParams {
     const unsigned char *light;
     // tile_order != 0 (set only by the image-order launch of a sphere scene that ran tile_order_kernel, never by a probe, a
     // light or a scheduled launch): trace_grid_kernel's workgroup b renders tile border[b] (ty * tiles_x + tx), the tiles that
-    // may see a refracting or reflecting sphere first; plan[c] = workgroups of classes < c (kOrderSpheresMax below)
+    // may see a refracting or reflecting sphere first; plan[c] = workgroups of classes < c (kOrderSpheresMax below).  kOrderAll:
+    // every entry of the list; kOrderFull / kOrderDiffuse: one of a pair of launches over the list -- the entries of classes
+    // 0-2, resp. workgroup b renders entry plan[3] + b (class 3: the terminal-diffuse variant, on the handle's second stream)
     int32_t light_mode, tile_order;
     const uint32_t *order;
     // Tile queue of the scheduled launch (chunks == 1): border[0..plan[3]) = the tiles (ty * tiles_x + tx) with at least one
@@ -83,12 +86,31 @@ static constexpr int kTileW = 32, kTileH = 8, kThreads = 256;
 // plan[kOrderPlanWords] | list[n_tiles] | tile class[n_tiles] (bytes) | wave-tile class[n_wt] (bytes); plan[c], c = 0..4 = tiles of
 // classes < c, plan[kOrderArrived] = the workgroups of tile_order_kernel that are through (0 between launches).
 static constexpr int kOrderSpheresMax = 16, kOrderClasses = 4, kOrderPlanWords = 8, kOrderArrived = 5;
+static constexpr int kOrderAll = 1, kOrderFull = 2, kOrderDiffuse = 3;  // GridParams::tile_order
 struct OrderSpheres {
     double s[kOrderSpheresMax][4];  // centre, radius
     uint32_t n, transp;             // transp: bit i set = sphere i refracts (transp >= kEps), else it only reflects
 };
 static constexpr size_t order_pad(size_t b) { return (b + 255) & ~(size_t)255; }
 inline size_t tile_order_bytes(size_t n_tiles, size_t n_wt) { return order_pad((kOrderPlanWords + n_tiles) * sizeof(uint32_t)) + order_pad(n_tiles) + order_pad(n_wt); }
+// True when no tile of any grid seen from `cam` can be of class 3: some special sphere fails cone_clear_of (cgrt_eye.hpp) by
+// one of its tests that do not look at the tile -- it reaches the lens plane, or its bound, grown by the lens blur, holds the
+// camera.  The same expressions as on the device; a last-bit difference would only cost an idle launch or leave class-3 tiles
+// to the full variant.
+inline bool order_all_special(const OrderSpheres &sp, const cgrt_camera &cam) {
+    for (uint32_t i = 0; i < sp.n; i++) {
+        double r = sp.s[i][3] * (1 + 1e-9) + 1e-6;
+        if (cam.lens_radius > 0) {
+            const double f = cam.focus_plane - cam.cam[2];
+            const double s_lo = (sp.s[i][2] - r - cam.cam[2]) / f, s_hi = (sp.s[i][2] + r - cam.cam[2]) / f;
+            if (!(f > 0) || !(s_lo > 0)) return true;
+            r += cam.lens_radius * std::max(std::fabs(1 - s_lo), std::fabs(1 - s_hi));
+        }
+        const double vx = sp.s[i][0] - cam.cam[0], vy = sp.s[i][1] - cam.cam[1], vz = sp.s[i][2] - cam.cam[2];
+        if (!(std::sqrt(vx * vx + vy * vy + vz * vz) > r)) return true;
+    }
+    return false;
+}
 static constexpr int kWaveTileW = 16, kWaveTileH = 4;  // one pixel per lane
 // blockIdx -> tile, XCD-aware (tile_of_block, cgrt_grid.hpp): super-tiles of kSuperW x kSuperH tiles dealt to kXcds L2 groups
 static constexpr int kXcds = 8, kSuperW = 4, kSuperH = 4, kSuperTiles = kSuperW * kSuperH;

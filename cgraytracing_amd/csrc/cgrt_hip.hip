@@ -88,6 +88,9 @@ struct cgrt_scene {
     bool order_ok = false;
     mutable GrowBuf order_buf;
     mutable size_t order_tiles = 0;
+    // the terminal-diffuse launch over the order's class-3 tiles (sphere-only scenes; it runs on aux_stream beside the main
+    // launch): whether the last launch issued one
+    mutable bool diffuse_issued = false;
     size_t mem_total = 0;                // memory of the scene's device (read at commit; bounds the deferred-value budget)
     int n_cu = 256;                      // compute units of the scene's device (read at commit; wave slots of the scheduler)
     // second stream + fork/join events for the light-tile launch that runs beside the full one (created at commit)
@@ -338,17 +341,26 @@ static int upload_scene(cgrt_scene *s, SceneLayout &L, const CommitKnobs &k, Dev
     return CGRT_OK;
 }
 
-// the light-tile launch's stream and fork/join events; without them every tile is rendered by the full variant
-static void open_light_stream(cgrt_scene *s, AuxPriority priority, DeviceScene &d) {
-    if (!d.light_ok || s->aux_stream) return;
+// the light-tile / diffuse-tile launch's stream and fork/join events; without them every tile is rendered by the full variant
+// (diffuse: a sphere-only scene the tile order serves, whose class-3 tiles get the terminal-diffuse variant)
+static void open_light_stream(cgrt_scene *s, AuxPriority priority, DeviceScene &d, bool diffuse) {
+    if (!(d.light_ok || diffuse) || s->aux_stream) return;
     // the light launch yields to the scheduled one: lowest stream priority
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
     const int prio = priority == AUX_SAME ? 0 : priority == AUX_HIGH ? prio_greatest : prio_least;
     if (hipStreamCreateWithPriority(&s->aux_stream, hipStreamNonBlocking, prio) != hipSuccess ||
         hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming) != hipSuccess)
+        hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming) != hipSuccess) {
+        // all three or none: aux_stream != nullptr is what the launches ask
+        (void)hipGetLastError();
+        if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
+        if (s->ev_join) (void)hipEventDestroy(s->ev_join);
+        if (s->aux_stream) (void)hipStreamDestroy(s->aux_stream);
+        s->ev_fork = s->ev_join = nullptr;
+        s->aux_stream = nullptr;
         d.light_ok = 0;
+    }
 }
 
 // A commit that fails leaves the scene open, with no device memory and with H.cover as before (the device builds append to it):
@@ -376,8 +388,6 @@ int cgrt_scene_commit(cgrt_scene *s, int device) {
         return rc;
     }
     scene_traits(H, L.trees, knobs, d);
-    open_light_stream(s, knobs.aux_priority, d);
-    s->dev = d;
     {   // the spheres tile_order_kernel orders an image-order launch by
         OrderSpheres &os = s->order_spheres;
         os = OrderSpheres{};
@@ -394,6 +404,8 @@ int cgrt_scene_commit(cgrt_scene *s, int device) {
         os.n = (uint32_t)std::min(special, (size_t)kOrderSpheresMax);
         s->order_ok = !d.has_mesh && !d.has_bezier && special >= 1 && special <= (size_t)kOrderSpheresMax;
     }
+    open_light_stream(s, knobs.aux_priority, d, s->order_ok && d.all_spheres != 0);
+    s->dev = d;
     s->committed = true;
     s->tree_recs = std::move(L.trees);
     size_t fr = 0, tot = 0;
@@ -534,9 +546,10 @@ static constexpr size_t kWideStackLds = (size_t)kThreads * kWideLdsDepth * sizeo
 struct EyeFlags {
     bool trees, bez, dof, glass, sph, stats, hps, spill, hfonly;
     int nt;  // threads per workgroup: 256 (32x8-pixel tiles) or 64 (Bezier scenes: one-wave workgroups on 16x4 tiles)
+    bool diff = false;  // the terminal-diffuse body (sphere scenes' class-3 tiles)
     constexpr int id() const {
         return (int)trees | (int)bez << 1 | (int)dof << 2 | (int)glass << 3 | (int)sph << 4 | (int)stats << 5 | (int)hps << 6 |
-               (int)spill << 7 | (int)hfonly << 8 | (nt == 64 ? 1 << 9 : 0);
+               (int)spill << 7 | (int)hfonly << 8 | (nt == 64 ? 1 << 9 : 0) | (int)diff << 10;
     }
 };
 // image order, the probe and the scheduled form: Bezier scenes share the tree-capable variants (one-wave workgroups)
@@ -549,6 +562,8 @@ static constexpr EyeFlags spill_sph_flags(bool dof, bool glass) { return {false,
 static constexpr EyeFlags general_flags(bool dof, bool hps, bool spill) { return {true, true, dof, true, false, false, hps, spill, false, kThreads}; }
 // the light tiles: no Bezier or pending-ray code; with trees beside bump-mapped planes, or only their height-field walk (hfonly)
 static constexpr EyeFlags light_flags(bool trees, bool dof, bool hfonly) { return {trees, false, dof, false, false, false, false, false, hfonly, kThreads}; }
+// the diffuse tiles of a sphere-only scene: the sphere loop, every ray ends at its first hit
+static constexpr EyeFlags diffuse_flags(bool dof) { return {false, false, dof, false, true, false, false, false, false, kThreads, true}; }
 
 // Dynamic LDS of an eye-pass launch, in the order of trace_grid_body's carve-up (cgrt_eye.hpp): pending-ray levels (GLASS) |
 // `resident` objects | one staging record per wave (SPILL) | one BezLds per wave (BEZ) | the cached tree's `cached_nodes`
@@ -676,10 +691,10 @@ struct EyeKernels {
     GridKernel grid;    // trace_grid_kernel
     SchedKernel sched;  // trace_grid_sched_kernel where the scheduled form runs these flags, else nullptr
 };
-template <int T, int B, int D, int G, int P, int S, int H = 0, int NT = kThreads, int SP = 0, int HF = 0>
+template <int T, int B, int D, int G, int P, int S, int H = 0, int NT = kThreads, int SP = 0, int HF = 0, int DF = 0>
 static constexpr EyeKernels gk() {  // trace_grid_kernel only
-    return {EyeFlags{T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, SP != 0, HF != 0, NT}.id(),
-            &trace_grid_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, NT, SP != 0, HF != 0>, nullptr};
+    return {EyeFlags{T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, SP != 0, HF != 0, NT, DF != 0}.id(),
+            &trace_grid_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, NT, SP != 0, HF != 0, DF != 0>, nullptr};
 }
 template <int T, int B, int D, int G, int P, int S, int NT = kThreads>
 static constexpr EyeKernels gsk() {  // both forms
@@ -687,7 +702,7 @@ static constexpr EyeKernels gsk() {  // both forms
     e.sched = &trace_grid_sched_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, NT>;
     return e;
 }
-//                        TREES BEZ DOF GLASS SPH STATS [HPS NT SPILL HFONLY]
+//                        TREES BEZ DOF GLASS SPH STATS [HPS NT SPILL HFONLY DIFF]
 static const EyeKernels kEyeKernels[] = {
     // image order, the probe and the scheduled form (the light variants are the tree and plain ones without GLASS or STATS)
     gsk<1, 1, 0, 0, 0, 0, 64>(), gsk<1, 1, 0, 1, 0, 0, 64>(), gsk<1, 1, 1, 0, 0, 0, 64>(), gsk<1, 1, 1, 1, 0, 0, 64>(),
@@ -701,6 +716,8 @@ static const EyeKernels kEyeKernels[] = {
     gk<1, 1, 0, 1, 0, 0, 1, 256, 0>(), gk<1, 1, 1, 1, 0, 0, 1, 256, 0>(), gk<1, 1, 0, 1, 0, 0, 1, 256, 1>(), gk<1, 1, 1, 1, 0, 0, 1, 256, 1>(),
     // light tiles beside bump-mapped planes that need only the height-field walk
     gk<1, 0, 0, 0, 0, 0, 0, 256, 0, 1>(), gk<1, 0, 1, 0, 0, 0, 0, 256, 0, 1>(),
+    // diffuse tiles of sphere-only scenes (class 3 of the tile order)
+    gk<0, 0, 0, 0, 1, 0, 0, 256, 0, 0, 1>(), gk<0, 0, 1, 0, 1, 0, 0, 256, 0, 0, 1>(),
 };
 static const EyeKernels *eye_kernels(const EyeFlags &f) {
     for (const EyeKernels &e : kEyeKernels)
@@ -730,7 +747,7 @@ static int general_resident(const cgrt_scene *s, bool dof, bool hps) {
 }
 
 // ---- the eye pass's launch plan ----
-enum class EyeForm { Image, Sched, SpillSph, SpillGen, Capture, Light, LightHF };
+enum class EyeForm { Image, Sched, SpillSph, SpillGen, Capture, Light, LightHF, Diffuse };
 // One launch of the eye pass: which kernel (form and template flags), the scene as it sees it and its dynamic LDS
 struct EyeLaunch {
     EyeForm form;
@@ -739,7 +756,8 @@ struct EyeLaunch {
     size_t lds;       // dynamic LDS bytes
     const char *what() const {  // the launch's name in a refusal
         static const char *const names[] = {"eye pass", "eye pass", "eye pass, SPILL (spheres)", "eye pass, SPILL (general)",
-                                            "Hitpoint capture", "eye pass, light tiles", "eye pass, light tiles (HFONLY)"};
+                                            "Hitpoint capture", "eye pass, light tiles", "eye pass, light tiles (HFONLY)",
+                                            "eye pass, diffuse tiles"};
         return form <= EyeForm::Sched && k.bez ? "eye pass (Bezier)" : names[(int)form];
     }
 };
@@ -791,6 +809,34 @@ static EyeLaunch light_launch(const DeviceScene &d, bool dof, const EyeKnobs &kn
     L.dev = d;
     L.lds = eye_lds(L.k, d);
     return L;
+}
+// The diffuse tiles' launch beside an image-order launch of a sphere-only scene (class 3 of tile_order_kernel's list): the
+// terminal-diffuse variant, the object list its only LDS.  It is issued when the main launch is the plain sphere variant in
+// tile order (eye_launch: no SPILL, no STATS; not the Hitpoint capture, a probe, a split-sample or a timeline launch), the
+// caller asks for it (CGRT_GRID_DIFFUSE_TILES) and some tile can be of class 3 at all (order_all_special).  These conditions contain those of
+// the tile order itself (cgrt_trace_grid: image order, one chunk -- no CGRT_GRID_SPLIT_SAMPLES --, row-major tiles -- a sphere
+// scene has no mesh --, 256 threads, order_ok), so the launch and cgrt_trace_grid_diffuse_variant decide by this alone.
+static bool diffuse_wanted(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, const EyeLaunch &L, const EyeKnobs &kn) {
+    return L.form == EyeForm::Image && L.k.sph && !L.k.spill && !L.k.stats && L.k.nt == kThreads && s->order_ok && s->aux_stream &&
+           (grid->flags & CGRT_GRID_DIFFUSE_TILES) && !(grid->flags & (CGRT_GRID_NO_TILE_ORDER | CGRT_GRID_SPLIT_SAMPLES)) && !kn.timeline_file &&
+           !order_all_special(s->order_spheres, *cam);
+}
+static EyeLaunch diffuse_launch(const DeviceScene &d, bool dof) {
+    EyeLaunch L;
+    L.form = EyeForm::Diffuse;
+    L.k = diffuse_flags(dof);
+    L.dev = d;
+    L.lds = eye_lds(L.k, d);
+    return L;
+}
+static void diffuse_name(const EyeLaunch &L, char *name, size_t cap) {
+    std::snprintf(name, cap, "trace_grid_kernel<TREES=0,BEZ=0,DOF=%d,GLASS=0,SPH=1,STATS=0,HPS=0,NT=%d,DIFF=1>", (int)L.k.dof, L.k.nt);
+}
+// What launch_eye would refuse, asked ahead of a launch that must not be left half issued
+static int check_eye(const EyeLaunch &L, int device) {
+    const EyeKernels *e = eye_kernels(L.k);
+    if (!e) return fail(CGRT_ERR_UNSUPPORTED, std::string(L.what()) + ": no kernel built for this variant");
+    return lds_check(reinterpret_cast<const void *>(e->grid), L.lds, device, L.what());
 }
 // Launches the plan's kernel: trace_grid_sched_kernel when `sched`, else trace_grid_kernel
 static int launch_eye(const EyeLaunch &L, bool sched, int device, const GridParams &g, dim3 gd, hipStream_t st, float *rgb,
@@ -918,7 +964,7 @@ static int order_tiles(const cgrt_scene *s, const FramePlan &p, GridParams &g, h
     hipLaunchKernelGGL(tile_order_kernel, dim3(blocks), dim3(1024), 0, st, g, s->order_spheres, tiles_x, tiles_y, plan, list, tcls, wcls);
     g.plan = plan;
     g.border = list;
-    g.tile_order = 1;
+    g.tile_order = kOrderAll;
     s->order_tiles = n;
     return CGRT_OK;
 }
@@ -988,6 +1034,7 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     const size_t n_blocks = (size_t)p.heavy_blocks + p.grid_dim;
     // image order, one workgroup per tile with all its samples, row-major: the tiles that see a mirror or glass sphere first
     s->order_tiles = 0;
+    s->diffuse_issued = false;
     if (L.form == EyeForm::Image && p.chunks == 1 && !p.xcd_tiles && L.k.nt == kThreads && s->order_ok &&
         !(grid->flags & CGRT_GRID_NO_TILE_ORDER) && (rc = order_tiles(s, p, g, st)))
         return rc;
@@ -1001,13 +1048,32 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
         hipLaunchKernelGGL(pixel_const_kernel, dim3((unsigned)p.kmax), dim3(64), 0, st, g);
         if (g.prim_len && (rc = primary_walk(s, L, g, st, cnt))) return rc;
         if ((rc = launch_eye(L, true, s->device, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) return rc;
+#ifdef CGRT_DIFF_ONE_LAUNCH  // EXPERIMENT: the class-3 workgroups take the DIFF body inside the one launch (cgrt_eye.hpp)
+    } else if (false) {
+#else
+    } else if (g.tile_order && diffuse_wanted(s, cam, grid, L, kn)) {
+#endif
+        // The list's class 0-2 entries by this launch, its class-3 entries by the terminal-diffuse variant on the second stream,
+        // started behind it (fork / join events, lowest priority: the arrangement of the light-tile launch).  Where class 3
+        // begins is known on the device only: both launches span the list, workgroups beyond their part leave at once.
+        const EyeLaunch DL = diffuse_launch(d, L.k.dof);
+        if ((rc = check_eye(DL, s->device))) return rc;  // before the main launch goes out with only its part of the list
+        GridParams gd = g;
+        g.tile_order = kOrderFull;
+        gd.tile_order = kOrderDiffuse;
+        HIP_TRY(hipEventRecord(s->ev_fork, st));
+        if ((rc = launch_eye(L, false, s->device, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) return rc;
+        HIP_TRY(hipStreamWaitEvent(s->aux_stream, s->ev_fork, 0));
+        if ((rc = launch_eye(DL, false, s->device, gd, dim3((unsigned)n_blocks), s->aux_stream, rgb, nhit, cnt))) return rc;
+        HIP_TRY(hipEventRecord(s->ev_join, s->aux_stream));
+        s->diffuse_issued = true;
     } else if ((rc = launch_eye(L, false, s->device, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) {
         return rc;
     }
     if (p.chunks > 1)
         hipLaunchKernelGGL(finalize_chunks_kernel, dim3((unsigned)(((size_t)g.rows * g.W + 255) / 256)), dim3(256), 0, st, g, rgb, nhit);
     if (p.heavy_blocks > 0) hipLaunchKernelGGL(deferred_sum_kernel, dim3((unsigned)p.kmax), dim3(64), 0, st, g, rgb, nhit);  // (4)
-    if (g.light) HIP_TRY(hipStreamWaitEvent(st, s->ev_join, 0));  // the caller's stream continues when both launches are done
+    if (g.light || s->diffuse_issued) HIP_TRY(hipStreamWaitEvent(st, s->ev_join, 0));  // the caller's stream continues when both launches are done
     const hipError_t launch_err = hipGetLastError();
     if (g.timeline && launch_err == hipSuccess && (rc = write_timeline(kn.timeline_file, timeline, n_blocks, p, L.k.nt, st))) return rc;
     if (launch_err != hipSuccess) return fail(CGRT_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(launch_err));
@@ -1026,6 +1092,31 @@ int cgrt_scene_last_tile_order(const cgrt_scene *s, uint32_t *plan5, uint32_t *l
     if (plan5) HIP_TRY(hipMemcpy(plan5, base, (kOrderClasses + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (list) HIP_TRY(hipMemcpy(list, base + kOrderPlanWords * sizeof(uint32_t), n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (cls) HIP_TRY(hipMemcpy(cls, base + order_pad((kOrderPlanWords + n) * sizeof(uint32_t)), n, hipMemcpyDeviceToHost));
+    return CGRT_OK;
+}
+
+int cgrt_trace_grid_diffuse_variant(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, char *name, size_t cap) {
+    int rc = check_grid(s, cam, grid);
+    if (rc) return rc;
+    if (!name || cap == 0) return fail(CGRT_ERR_INVALID, "null name buffer");
+    ON_DEVICE(s->device);
+    const EyeKnobs kn = eye_knobs();
+    const EyeLaunch L = eye_launch(s, cam, grid, kn, false);
+    name[0] = 0;
+    if (diffuse_wanted(s, cam, grid, L, kn)) diffuse_name(diffuse_launch(s->dev, L.k.dof), name, cap);
+    return CGRT_OK;
+}
+
+int cgrt_scene_last_diffuse_tiles(const cgrt_scene *s, int64_t *n_tiles) {
+    if (!s || !n_tiles) return fail(CGRT_ERR_INVALID, "null argument");
+    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+    ON_DEVICE(s->device);
+    *n_tiles = 0;
+    if (!s->diffuse_issued || s->order_tiles == 0) return CGRT_OK;
+    uint32_t plan[kOrderClasses + 1];
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(plan, s->order_buf.p, sizeof(plan), hipMemcpyDeviceToHost));
+    *n_tiles = (int64_t)plan[kOrderClasses] - (int64_t)plan[3];
     return CGRT_OK;
 }
 

@@ -252,7 +252,8 @@ __device__ __forceinline__ TreeHit tree_hit(const DeviceScene &sc, const LdsAux 
 // sc.objs, in the same order, so ties still go to the earlier object (main.cpp:57).
 // SPILL: the kernel variants for such scenes (n_objs > n_lds); without it the list is the whole scene and none of the code for
 // the others exists.
-template <bool TREES, bool BEZ, bool SPH, bool STATS, bool SPILL = false, bool PRE = false, bool HFONLY = false>
+// NRM = false (SPH only): best.n is left unset -- the eye pass derives a sphere's normal itself, in the branches that use it.
+template <bool TREES, bool BEZ, bool SPH, bool STATS, bool SPILL = false, bool PRE = false, bool HFONLY = false, bool NRM = true>
 __device__ __forceinline__ SceneHit intersect_scene(const ObjRec *__restrict__ objs, int n_lds, int n_objs, const DeviceScene &sc,
                                                     V3 o, V3 d, RayKey &rk, bool on, const LdsAux &aux,
                                                     uint32_t &n_node, uint32_t &n_tri) {
@@ -278,7 +279,7 @@ __device__ __forceinline__ SceneHit intersect_scene(const ObjRec *__restrict__ o
                 best.id = i;
             }
         }
-        if (best.id >= 0) best.n = normalized((o + d * best.t) - load_centre<SPILL>(objs, n_lds, sc.objs, best.id));  // objects.h:65-66
+        if (NRM && best.id >= 0) best.n = normalized((o + d * best.t) - load_centre<SPILL>(objs, n_lds, sc.objs, best.id));  // objects.h:65-66
         return best;
     }
     // 1/d for the box tests: three fp64 divisions (~100 instructions), paid only by waves that reach a tree

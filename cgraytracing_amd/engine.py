@@ -156,10 +156,13 @@ class Scene:
 
     def trace_grid(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                    stripe=None, sample_offset=0, spp_total=None, out=None, nhit=None, counters=None, stream=None,
-                   stats=False, accumulate=False, split_samples=False, reorder=True, force_reorder=False, tile_order=True):
+                   stats=False, accumulate=False, split_samples=False, reorder=True, force_reorder=False, tile_order=True,
+                   diffuse_tiles=False):
         """Asynchronous launch on torch's current stream (or `stream`).  reorder=False: CGRT_GRID_NO_REORDER (tiles in image
         order instead of heaviest-first; same image).  tile_order=False: CGRT_GRID_NO_TILE_ORDER (an image-order launch starts
-        its tiles row-major instead of mirror / glass tiles first; same image).  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
+        its tiles row-major instead of mirror / glass tiles first; same image).  diffuse_tiles=True: CGRT_GRID_DIFFUSE_TILES (a
+        sphere-only scene's tiles that see no mirror or glass are rendered by the terminal-diffuse launch beside the main one,
+        not by the full kernel; same image, off by default).  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
         workgroups share a tile's samples; reproducible, fp64 summation order differs from the sample-by-sample sum).  Returns (rgb, nhit, counters) torch
         tensors on the scene's device: float32 [rows,width,3], int32 [rows,width] (bit pattern uint32),
         int64 [8] (counters are ADDED to)."""
@@ -178,7 +181,8 @@ class Scene:
         assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (rows, width, 3)
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (2 if accumulate else 0) | (4 if split_samples else 0) |
-                              (0 if reorder else 8) | (16 if force_reorder else 0) | (0 if tile_order else 64))
+                              (0 if reorder else 8) | (16 if force_reorder else 0) | (0 if tile_order else 64) |
+                              (128 if diffuse_tiles else 0))
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         check(self._L.cgrt_trace_grid(self._h, C.byref(cc), C.byref(g), out.data_ptr(),
                                       nhit.data_ptr() if nhit is not None else None,
@@ -308,7 +312,7 @@ class Scene:
 
     def trace_grid_host(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                         stripe=None, sample_offset=0, spp_total=None, stats=False, split_samples=False, reorder=True,
-                        force_reorder=False, tile_order=True):
+                        force_reorder=False, tile_order=True, diffuse_tiles=False):
         """Synchronous form with numpy outputs (no torch needed): dict(rgb, nhit, counters)."""
         rows = height - row_offset if rows is None else rows
         rgb = np.zeros((rows, width, 3), np.float32)
@@ -316,7 +320,7 @@ class Scene:
         cnt = np.zeros((_capi.CGRT_NCOUNTERS,), np.uint64)
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (4 if split_samples else 0) | (0 if reorder else 8) |
-                              (16 if force_reorder else 0) | (0 if tile_order else 64))
+                              (16 if force_reorder else 0) | (0 if tile_order else 64) | (128 if diffuse_tiles else 0))
         check(self._L.cgrt_trace_grid_host(self._h, C.byref(cc), C.byref(g), rgb.ctypes.data, nhit.ctypes.data,
                                            cnt.ctypes.data))
         return dict(rgb=rgb, nhit=nhit, counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]),
@@ -333,6 +337,13 @@ class Scene:
         plan, lst, cls = np.zeros(5, np.uint32), np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint8)
         check(self._L.cgrt_scene_last_tile_order(self._h, plan.ctypes.data, lst.ctypes.data, cls.ctypes.data, n.value, C.byref(n)))
         return dict(plan=plan, list=lst, cls=cls)
+
+    def last_diffuse_tiles(self):
+        """Tiles the terminal-diffuse launch of this scene's last trace_grid / trace_grid_host rendered
+        (cgrt_scene_last_diffuse_tiles; synchronises the device); 0: that call issued none."""
+        n = C.c_int64()
+        check(self._L.cgrt_scene_last_diffuse_tiles(self._h, C.byref(n)))
+        return int(n.value)
 
     def trace_grid_hitpoints(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None,
                              row_offset=0, cap=None):
@@ -542,6 +553,16 @@ class Scene:
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, 0, 0, stripe, 0, None, flags)
         buf = C.create_string_buffer(160)
         check(self._L.cgrt_trace_grid_variant(self._h, C.byref(cc), C.byref(g), buf, len(buf)))
+        return buf.value.decode()
+
+    def diffuse_variant(self, width, height, spp=1, camera=None, max_depth=5, rows=None, stripe=None, flags=0):
+        """Name of the terminal-diffuse kernel instantiation this grid launches beside kernel_variant's with
+        flags including 128 (CGRT_GRID_DIFFUSE_TILES; sphere-only scenes in tile order: the tiles that see no mirror or glass),
+        or "" when it launches none."""
+        rows = height if rows is None else rows
+        cc, g = self._structs(camera, width, height, rows, spp, max_depth, 0, 0, stripe, 0, None, flags)
+        buf = C.create_string_buffer(160)
+        check(self._L.cgrt_trace_grid_diffuse_variant(self._h, C.byref(cc), C.byref(g), buf, len(buf)))
         return buf.value.decode()
 
     def intersect_rays(self, obj, org, dirs, keys=None):

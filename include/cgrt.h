@@ -99,6 +99,13 @@ enum {
                                  such a sphere in front of the others (refracting first), and the tiles are started in that
                                  order, so that the frame's longest tiles do not start late.  Every pixel is computed by
                                  the same code either way: image, hit counts and counters are identical                */
+    CGRT_GRID_DIFFUSE_TILES = 128, /* image-order launches of sphere-only scenes in tile order, opt-in: the tiles none of whose
+                                 primary rays can reach a reflecting or refracting sphere (class 3 of the order) are rendered by
+                                 a second launch beside the main one, with a variant in which every ray ends at its first hit
+                                 (no normal, no material dispatch, no pending-ray storage; more waves per SIMD).  Same image,
+                                 hit counts and counters either way; cgrt_scene_last_diffuse_tiles reads back how many tiles
+                                 it took.  Off by default: it executes fewer instructions, but on the measured frame the
+                                 longest workgroup bounds the frame and runs slower beside the denser launch */
     CGRT_GRID_HITPOINTS = 32, /* cgrt_trace_grid_variant only: name the launch of the Hitpoint capture
                                  (cgrt_trace_grid_hitpoints, the eye pass of cgrt_ppm_render) instead of cgrt_trace_grid's;
                                  ignored by the other calls                                                            */
@@ -520,6 +527,12 @@ int cgrt_trace_grid_variant(const cgrt_scene *s, const cgrt_camera *cam, const c
  * see a reflecting sphere, 3 the rest), list[i] = the tile (ty * ceil(width / 32) + tx) workgroup i rendered, cls[t] = class
  * of tile t. */
 int cgrt_scene_last_tile_order(const cgrt_scene *s, uint32_t *plan5, uint32_t *list, uint8_t *cls, int64_t cap, int64_t *n_tiles);
+
+/* The terminal-diffuse launch beside cgrt_trace_grid's main launch (see CGRT_GRID_DIFFUSE_TILES): the name of its kernel
+ * instantiation for (scene, cam, grid), or an empty string when the grid launches none; and, for the LAST cgrt_trace_grid on
+ * the handle, the number of tiles that launch rendered (synchronises the device; 0: none was issued). */
+int cgrt_trace_grid_diffuse_variant(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, char *name, size_t cap);
+int cgrt_scene_last_diffuse_tiles(const cgrt_scene *s, int64_t *n_tiles);
 
 /* Host evaluation of the lens stream (cgrt_rng.hpp, the same inline code the kernel runs): writes
  * uniform_sampling_circle(radius) (sampling.h:35-43) for n (pixel, sample) pairs as 3 doubles each.  Lets CPU-only
