@@ -102,7 +102,7 @@ class PhotonRays(C.Structure):
 RAYS_STATS = 1
 RAYS_NO_SIGN_PASS = 2
 RAYS_HITPOINTS = 4
-PROBE_SQRT, PROBE_NORMALIZED, PROBE_SPHERE_LEN = 0, 1, 2  # cgrt_math_probe's op
+PROBE_SQRT, PROBE_NORMALIZED, PROBE_SPHERE_LEN, PROBE_SPHERE_LEN_PAIR = 0, 1, 2, 4  # cgrt_math_probe's op (3 is none)
 
 # every symbol include/cgrt.h declares, with its signature
 _DP = C.POINTER(C.c_double)
@@ -166,6 +166,7 @@ SIGNATURES = {
     "cgrt_scene_last_tile_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "cgrt_trace_grid_diffuse_variant": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
     "cgrt_scene_last_diffuse_tiles": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "cgrt_scene_last_inkernel_diffuse_tiles": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "cgrt_trace_rays": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(RayResults), C.c_void_p, C.c_void_p]),
     "cgrt_trace_rays_host": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(RayResults), C.c_void_p]),
     "cgrt_trace_rays_variant": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(RayResults), C.c_char_p, C.c_size_t]),

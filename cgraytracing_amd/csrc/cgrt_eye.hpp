@@ -16,6 +16,9 @@ struct Pending {  // a refracted child waiting for its turn (main.cpp:157)
 // pending-ray storage (LDS levels, sibling registers) is compiled out and occupancy goes up.
 // SPH: every object is a sphere (C1/C2-type scenes): specialised object loop.
 // HPS: additionally append every Hitpoint {f, pos, normal} (hitpoints.h:6-20, main.cpp:87-98) to a global stream.
+// PAIR (SPH with GLASS, the variants the tile order serves): the sphere loop takes two spheres a trip as two independent
+// instruction chains (sphere_len_pair) -- the frame ends with a few waves over the glass sphere, each alone on its SIMD and bound
+// by its own dependent fp64 chain.
 // DIFF (SPH without GLASS): the terminal-diffuse body for tiles none of whose rays can meet a reflecting or refracting sphere
 // (class 3 of tile_order_kernel): every ray ends at its first hit with adj == (1, 1, 1), so neither the hit point, the normal,
 // the material dispatch nor any pending-ray state exists in it.
@@ -93,12 +96,13 @@ __device__ __forceinline__ bool wave_has_tile(const GridParams &g, int tile_bloc
 // queue of heavy-tile items, lanes drawing (pixel, sample) units.  tile_block / tile_grid: this workgroup's index among the
 // tile workgroups and their number (the launch may put heavy workgroups in front of them).
 template <bool TREES, bool BEZ, bool DOF, bool GLASS, bool SPH, bool STATS, bool HPS, int NT, bool HEAVY, bool SPILL = false, bool HFONLY = false,
-          bool DIFF = false>
+          bool DIFF = false, bool PAIR = false>
 __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const GridParams &g, float *__restrict__ rgb,
                                                 uint32_t *__restrict__ nhit_out, unsigned long long *__restrict__ counters,
                                                 const HitpointSink &hps, int tile_block, int tile_grid) {
     using TG = TileGeom<NT>;
     static_assert(!DIFF || (SPH && !GLASS && !HPS && !HEAVY && !STATS && !SPILL), "DIFF: the sphere loop, first hits only");
+    static_assert(!PAIR || (SPH && GLASS && !HPS && !HEAVY && !STATS && !SPILL), "PAIR: the glass sphere variants of the tile order");
     const long long tl_t0 = g.timeline ? wall_clock64() : 0;
     if (!HEAVY && !g.timeline) {  // (the timeline, a development aid, wants a record from every workgroup)
         if (!__syncthreads_or((int)wave_has_tile<NT>(g, tile_block, tile_grid))) return;
@@ -331,7 +335,7 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
             pre_valid = false;
         }
         const SceneHit hit =
-            intersect_scene<TREES, BEZ, SPH, STATS, SPILL, PRE, HFONLY, !SPH>(lobjs, sc.n_lds, sc.n_objs, sc, o, d, rk, have, aux, my_nodes, my_tris);
+            intersect_scene<TREES, BEZ, SPH, STATS, SPILL, PRE, HFONLY, !SPH, PAIR>(lobjs, sc.n_lds, sc.n_objs, sc, o, d, rk, have, aux, my_nodes, my_tris);
         if (have) {
             my_rays++;
             have = false;
@@ -593,7 +597,7 @@ __device__ __forceinline__ void wg_counters_end(const unsigned long long *wg, un
 
 // One launch = tile workgroups only (probe, image order, Hitpoint capture) ...
 template <bool TREES, bool BEZ, bool DOF, bool GLASS, bool SPH, bool STATS, bool HPS = false, int NT = 256, bool SPILL = false, bool HFONLY = false,
-          bool DIFF = false>
+          bool DIFF = false, bool PAIR = false>
 __global__ __launch_bounds__(NT, DIFF ? (DOF ? kDiffDofWaves : kDiffWaves) : BEZ ? kBezWaves : ((TREES && !HFONLY) ? kTreeWaves : 4)) void trace_grid_kernel(DeviceScene sc, GridParams g, float *__restrict__ rgb,
                                                              uint32_t *__restrict__ nhit_out,
                                                              unsigned long long *__restrict__ counters,
@@ -605,31 +609,22 @@ __global__ __launch_bounds__(NT, DIFF ? (DOF ? kDiffDofWaves : kDiffWaves) : BEZ
     int tile_block = (int)blockIdx.x, tile_grid = (int)gridDim.x;
     if (g.tile_order) {
         unsigned entry = blockIdx.x;
-        if (g.tile_order != kOrderAll) {
+        if (g.tile_order == kOrderFull || g.tile_order == kOrderDiffuse) {
             const unsigned first_diffuse = load_uniform(g.plan + 3);
             if (g.tile_order == kOrderDiffuse) entry += first_diffuse;
             if (g.tile_order == kOrderDiffuse ? entry >= load_uniform(g.plan + kOrderClasses) : entry >= first_diffuse) return;
         }
         tile_block = (int)load_uniform(g.border + entry);
         tile_grid = -1;
-#ifdef CGRT_DIFF_ONE_LAUNCH  // EXPERIMENT (make exp NAME=diff1 DEFS=-DCGRT_DIFF_ONE_LAUNCH): one launch over the
-        // whole list, its class-3 workgroups branching into the DIFF body here -- at the full kernel's registers
-        if (SPH && GLASS && !STATS && !HPS && !SPILL && g.tile_order == kOrderAll && blockIdx.x >= load_uniform(g.plan + 3)) {
-            __shared__ unsigned long long wg_cnt1[CGRT_NCOUNTERS];
-            unsigned long long *wc1 = wg_counters_begin(wg_cnt1, counters);
-            trace_grid_body<TREES, BEZ, DOF, false, SPH, false, false, NT, false, false, HFONLY, SPH && GLASS && !STATS && !HPS && !SPILL>(
-                sc, g, rgb, nhit_out, wc1, hps, tile_block, tile_grid);
-            wg_counters_end(wg_cnt1, counters);
-            return;
-        }
-#endif
-#ifdef CGRT_TILE_ORDER_PRIO  // EXPERIMENT (make exp): issue priority for the workgroups of classes 0-2, for the whole tile
-        if (blockIdx.x < load_uniform(g.plan + 3)) __builtin_amdgcn_s_setprio(3);
-#endif
     }
     __shared__ unsigned long long wg_cnt[CGRT_NCOUNTERS];
     unsigned long long *wc = wg_counters_begin(wg_cnt, counters);
-    trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid);
+    // kOrderAllDiffuse (PAIR variants only): one launch over the whole list whose class-3 workgroups take the terminal-diffuse
+    // body here (workgroup-uniform), at this kernel's registers -- 12 % fewer VALU instructions a frame and no second launch
+    if (PAIR && g.tile_order == kOrderAllDiffuse && blockIdx.x >= load_uniform(g.plan + 3))
+        trace_grid_body<false, false, DOF, false, true, false, false, NT, false, false, false, true>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid);
+    else
+        trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF, PAIR>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid);
     wg_counters_end(wg_cnt, counters);
 }
 // ... or the scheduled form: the first g.heavy_blocks workgroups serve the heavy tiles' unit queue, the others are the tile
@@ -1148,9 +1143,12 @@ __global__ void math_probe_kernel(int op, const double *__restrict__ in, long lo
         out[3 * i] = v.x;
         out[3 * i + 1] = v.y;
         out[3 * i + 2] = v.z;
-    } else {  // CGRT_PROBE_SPHERE_LEN: centre(3), r2, origin(3), direction(3)
+    } else if (op == CGRT_PROBE_SPHERE_LEN) {  // centre(3), r2, origin(3), direction(3)
         const double *p = in + 10 * i;
         out[i] = sphere_len(ld3(p), p[3], ld3(p + 4), ld3(p + 7));
+    } else {  // CGRT_PROBE_SPHERE_LEN_PAIR: centre A(3), r2 A, centre B(3), r2 B, origin(3), direction(3)
+        const double *p = in + 14 * i;
+        sphere_len_pair(ld3(p), p[3], ld3(p + 4), p[7], ld3(p + 8), ld3(p + 11), out[2 * i], out[2 * i + 1]);
     }
 }
 

@@ -49,7 +49,8 @@ struct GridParams {
     // light or a scheduled launch): trace_grid_kernel's workgroup b renders tile border[b] (ty * tiles_x + tx), the tiles that
     // may see a refracting or reflecting sphere first; plan[c] = workgroups of classes < c (kOrderSpheresMax below).  kOrderAll:
     // every entry of the list; kOrderFull / kOrderDiffuse: one of a pair of launches over the list -- the entries of classes
-    // 0-2, resp. workgroup b renders entry plan[3] + b (class 3: the terminal-diffuse variant, on the handle's second stream)
+    // 0-2, resp. workgroup b renders entry plan[3] + b (class 3: the terminal-diffuse variant, on the handle's second stream);
+    // kOrderAllDiffuse: every entry, the workgroups from plan[3] on by the terminal-diffuse body inside the same kernel
     int32_t light_mode, tile_order;
     const uint32_t *order;
     // Tile queue of the scheduled launch (chunks == 1): border[0..plan[3]) = the tiles (ty * tiles_x + tx) with at least one
@@ -86,7 +87,7 @@ static constexpr int kTileW = 32, kTileH = 8, kThreads = 256;
 // plan[kOrderPlanWords] | list[n_tiles] | tile class[n_tiles] (bytes) | wave-tile class[n_wt] (bytes); plan[c], c = 0..4 = tiles of
 // classes < c, plan[kOrderArrived] = the workgroups of tile_order_kernel that are through (0 between launches).
 static constexpr int kOrderSpheresMax = 16, kOrderClasses = 4, kOrderPlanWords = 8, kOrderArrived = 5;
-static constexpr int kOrderAll = 1, kOrderFull = 2, kOrderDiffuse = 3;  // GridParams::tile_order
+static constexpr int kOrderAll = 1, kOrderFull = 2, kOrderDiffuse = 3, kOrderAllDiffuse = 4;  // GridParams::tile_order
 struct OrderSpheres {
     double s[kOrderSpheresMax][4];  // centre, radius
     uint32_t n, transp;             // transp: bit i set = sphere i refracts (transp >= kEps), else it only reflects

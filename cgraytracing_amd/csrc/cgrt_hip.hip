@@ -91,6 +91,8 @@ struct cgrt_scene {
     // the terminal-diffuse launch over the order's class-3 tiles (sphere-only scenes; it runs on aux_stream beside the main
     // launch): whether the last launch issued one
     mutable bool diffuse_issued = false;
+    // ... and whether its class-3 workgroups took the terminal-diffuse body inside the main launch instead (kOrderAllDiffuse)
+    mutable bool diffuse_in_kernel = false;
     size_t mem_total = 0;                // memory of the scene's device (read at commit; bounds the deferred-value budget)
     int n_cu = 256;                      // compute units of the scene's device (read at commit; wave slots of the scheduler)
     // second stream + fork/join events for the light-tile launch that runs beside the full one (created at commit)
@@ -547,9 +549,10 @@ struct EyeFlags {
     bool trees, bez, dof, glass, sph, stats, hps, spill, hfonly;
     int nt;  // threads per workgroup: 256 (32x8-pixel tiles) or 64 (Bezier scenes: one-wave workgroups on 16x4 tiles)
     bool diff = false;  // the terminal-diffuse body (sphere scenes' class-3 tiles)
+    bool pair = false;  // the sphere loop two spheres a trip, class-3 tiles by the diffuse body in the same launch (glass sphere scenes)
     constexpr int id() const {
         return (int)trees | (int)bez << 1 | (int)dof << 2 | (int)glass << 3 | (int)sph << 4 | (int)stats << 5 | (int)hps << 6 |
-               (int)spill << 7 | (int)hfonly << 8 | (nt == 64 ? 1 << 9 : 0) | (int)diff << 10;
+               (int)spill << 7 | (int)hfonly << 8 | (nt == 64 ? 1 << 9 : 0) | (int)diff << 10 | (int)pair << 11;
     }
 };
 // image order, the probe and the scheduled form: Bezier scenes share the tree-capable variants (one-wave workgroups)
@@ -691,10 +694,10 @@ struct EyeKernels {
     GridKernel grid;    // trace_grid_kernel
     SchedKernel sched;  // trace_grid_sched_kernel where the scheduled form runs these flags, else nullptr
 };
-template <int T, int B, int D, int G, int P, int S, int H = 0, int NT = kThreads, int SP = 0, int HF = 0, int DF = 0>
+template <int T, int B, int D, int G, int P, int S, int H = 0, int NT = kThreads, int SP = 0, int HF = 0, int DF = 0, int PR = 0>
 static constexpr EyeKernels gk() {  // trace_grid_kernel only
-    return {EyeFlags{T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, SP != 0, HF != 0, NT, DF != 0}.id(),
-            &trace_grid_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, NT, SP != 0, HF != 0, DF != 0>, nullptr};
+    return {EyeFlags{T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, SP != 0, HF != 0, NT, DF != 0, PR != 0}.id(),
+            &trace_grid_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, NT, SP != 0, HF != 0, DF != 0, PR != 0>, nullptr};
 }
 template <int T, int B, int D, int G, int P, int S, int NT = kThreads>
 static constexpr EyeKernels gsk() {  // both forms
@@ -702,7 +705,7 @@ static constexpr EyeKernels gsk() {  // both forms
     e.sched = &trace_grid_sched_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, NT>;
     return e;
 }
-//                        TREES BEZ DOF GLASS SPH STATS [HPS NT SPILL HFONLY DIFF]
+//                        TREES BEZ DOF GLASS SPH STATS [HPS NT SPILL HFONLY DIFF PAIR]
 static const EyeKernels kEyeKernels[] = {
     // image order, the probe and the scheduled form (the light variants are the tree and plain ones without GLASS or STATS)
     gsk<1, 1, 0, 0, 0, 0, 64>(), gsk<1, 1, 0, 1, 0, 0, 64>(), gsk<1, 1, 1, 0, 0, 0, 64>(), gsk<1, 1, 1, 1, 0, 0, 64>(),
@@ -718,6 +721,8 @@ static const EyeKernels kEyeKernels[] = {
     gk<1, 0, 0, 0, 0, 0, 0, 256, 0, 1>(), gk<1, 0, 1, 0, 0, 0, 0, 256, 0, 1>(),
     // diffuse tiles of sphere-only scenes (class 3 of the tile order)
     gk<0, 0, 0, 0, 1, 0, 0, 256, 0, 0, 1>(), gk<0, 0, 1, 0, 1, 0, 0, 256, 0, 0, 1>(),
+    // glass sphere scenes in image order: the pair loop, the class-3 tiles' diffuse body inside
+    gk<0, 0, 0, 1, 1, 0, 0, 256, 0, 0, 0, 1>(), gk<0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 1>(),
 };
 static const EyeKernels *eye_kernels(const EyeFlags &f) {
     for (const EyeKernels &e : kEyeKernels)
@@ -795,6 +800,9 @@ static EyeLaunch eye_launch(const cgrt_scene *s, const cgrt_camera *cam, const c
         const bool reorder = grid->spp >= 4 && !(grid->flags & CGRT_GRID_NO_REORDER) && n_wt > 1 && n_wt < (1u << 30) &&
                              (!plain_scene || (grid->flags & CGRT_GRID_FORCE_REORDER) || kn.force_reorder);
         L.form = reorder ? EyeForm::Sched : EyeForm::Image;
+        // The image-order launch of a glass sphere scene the tile order serves (order_ok): its last waves, over the glass sphere,
+        // each alone on a SIMD, are bound by the sphere loop's dependent chain -- two spheres a trip
+        L.k.pair = L.form == EyeForm::Image && L.k.sph && L.k.glass && !L.k.stats && s->order_ok && !(grid->flags & CGRT_GRID_NO_SPHERE_PAIRS);
     }
     L.lds = eye_lds(L.k, L.dev) + (L.form == EyeForm::Image || L.form == EyeForm::Sched ? (size_t)kn.lds_pad : 0);
     return L;
@@ -1004,9 +1012,9 @@ int cgrt_trace_grid_variant(const cgrt_scene *s, const cgrt_camera *cam, const c
     const EyeLaunch L = eye_launch(s, cam, grid, eye_knobs(), (grid->flags & CGRT_GRID_HITPOINTS) != 0);
     const EyeFlags &k = L.k;
     const bool sched = L.form == EyeForm::Sched;
-    std::snprintf(name, cap, "trace_grid_%skernel<TREES=%d,BEZ=%d,DOF=%d,GLASS=%d,SPH=%d,STATS=%d,%sNT=%d%s>", sched ? "sched_" : "",
+    std::snprintf(name, cap, "trace_grid_%skernel<TREES=%d,BEZ=%d,DOF=%d,GLASS=%d,SPH=%d,STATS=%d,%s%sNT=%d%s>", sched ? "sched_" : "",
                   (int)k.trees, (int)k.bez, (int)k.dof, (int)k.glass, (int)k.sph, (int)k.stats,
-                  sched ? "" : (k.hps ? "HPS=1," : "HPS=0,"), k.nt, k.spill ? ",SPILL=1" : "");
+                  sched ? "" : (k.hps ? "HPS=1," : "HPS=0,"), k.pair ? "PAIR=1," : "", k.nt, k.spill ? ",SPILL=1" : "");
     return CGRT_OK;
 }
 
@@ -1035,6 +1043,7 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     // image order, one workgroup per tile with all its samples, row-major: the tiles that see a mirror or glass sphere first
     s->order_tiles = 0;
     s->diffuse_issued = false;
+    s->diffuse_in_kernel = false;
     if (L.form == EyeForm::Image && p.chunks == 1 && !p.xcd_tiles && L.k.nt == kThreads && s->order_ok &&
         !(grid->flags & CGRT_GRID_NO_TILE_ORDER) && (rc = order_tiles(s, p, g, st)))
         return rc;
@@ -1048,11 +1057,7 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
         hipLaunchKernelGGL(pixel_const_kernel, dim3((unsigned)p.kmax), dim3(64), 0, st, g);
         if (g.prim_len && (rc = primary_walk(s, L, g, st, cnt))) return rc;
         if ((rc = launch_eye(L, true, s->device, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) return rc;
-#ifdef CGRT_DIFF_ONE_LAUNCH  // EXPERIMENT: the class-3 workgroups take the DIFF body inside the one launch (cgrt_eye.hpp)
-    } else if (false) {
-#else
     } else if (g.tile_order && diffuse_wanted(s, cam, grid, L, kn)) {
-#endif
         // The list's class 0-2 entries by this launch, its class-3 entries by the terminal-diffuse variant on the second stream,
         // started behind it (fork / join events, lowest priority: the arrangement of the light-tile launch).  Where class 3
         // begins is known on the device only: both launches span the list, workgroups beyond their part leave at once.
@@ -1067,8 +1072,14 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
         if ((rc = launch_eye(DL, false, s->device, gd, dim3((unsigned)n_blocks), s->aux_stream, rgb, nhit, cnt))) return rc;
         HIP_TRY(hipEventRecord(s->ev_join, s->aux_stream));
         s->diffuse_issued = true;
-    } else if ((rc = launch_eye(L, false, s->device, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) {
-        return rc;
+    } else {
+        // The pair variant in tile order: the list's class-3 workgroups take the terminal-diffuse body inside this launch (where
+        // some tile can be of class 3 at all)
+        if (g.tile_order && L.k.pair && !order_all_special(s->order_spheres, *cam)) {
+            g.tile_order = kOrderAllDiffuse;
+            s->diffuse_in_kernel = true;
+        }
+        if ((rc = launch_eye(L, false, s->device, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) return rc;
     }
     if (p.chunks > 1)
         hipLaunchKernelGGL(finalize_chunks_kernel, dim3((unsigned)(((size_t)g.rows * g.W + 255) / 256)), dim3(256), 0, st, g, rgb, nhit);
@@ -1107,18 +1118,21 @@ int cgrt_trace_grid_diffuse_variant(const cgrt_scene *s, const cgrt_camera *cam,
     return CGRT_OK;
 }
 
-int cgrt_scene_last_diffuse_tiles(const cgrt_scene *s, int64_t *n_tiles) {
+// the class-3 tiles of the last launch's order, when that launch gave them to the terminal-diffuse body in the form asked for
+static int last_class3_tiles(const cgrt_scene *s, bool in_kernel, int64_t *n_tiles) {
     if (!s || !n_tiles) return fail(CGRT_ERR_INVALID, "null argument");
     if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
     ON_DEVICE(s->device);
     *n_tiles = 0;
-    if (!s->diffuse_issued || s->order_tiles == 0) return CGRT_OK;
+    if (!(in_kernel ? s->diffuse_in_kernel : s->diffuse_issued) || s->order_tiles == 0) return CGRT_OK;
     uint32_t plan[kOrderClasses + 1];
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(plan, s->order_buf.p, sizeof(plan), hipMemcpyDeviceToHost));
     *n_tiles = (int64_t)plan[kOrderClasses] - (int64_t)plan[3];
     return CGRT_OK;
 }
+int cgrt_scene_last_diffuse_tiles(const cgrt_scene *s, int64_t *n_tiles) { return last_class3_tiles(s, false, n_tiles); }
+int cgrt_scene_last_inkernel_diffuse_tiles(const cgrt_scene *s, int64_t *n_tiles) { return last_class3_tiles(s, true, n_tiles); }
 
 }  // extern "C"
 
@@ -1637,13 +1651,14 @@ int cgrt_lens_samples(uint64_t seed, const int64_t *pixel, const int32_t *sample
 }
 
 int cgrt_math_probe(int device, int op, const double *in, int64_t n, double *out) {
-    if (op != CGRT_PROBE_SQRT && op != CGRT_PROBE_NORMALIZED && op != CGRT_PROBE_SPHERE_LEN)
+    if (op != CGRT_PROBE_SQRT && op != CGRT_PROBE_NORMALIZED && op != CGRT_PROBE_SPHERE_LEN && op != CGRT_PROBE_SPHERE_LEN_PAIR)
         return fail(CGRT_ERR_INVALID, "cgrt_math_probe: unknown op");
     if (!in || !out) return fail(CGRT_ERR_INVALID, "cgrt_math_probe: null buffer");
     if (n < 0) return fail(CGRT_ERR_INVALID, "cgrt_math_probe: negative n");
     if (n > ((int64_t)1 << 28)) return fail(CGRT_ERR_LIMIT, "cgrt_math_probe: more than 2^28 elements");
     if (n == 0) return CGRT_OK;
-    const size_t n_in = op == CGRT_PROBE_SQRT ? 1 : (op == CGRT_PROBE_NORMALIZED ? 3 : 10), n_out = op == CGRT_PROBE_NORMALIZED ? 3 : 1;
+    const size_t n_in = op == CGRT_PROBE_SQRT ? 1 : (op == CGRT_PROBE_NORMALIZED ? 3 : (op == CGRT_PROBE_SPHERE_LEN ? 10 : 14)),
+                 n_out = op == CGRT_PROBE_NORMALIZED ? 3 : (op == CGRT_PROBE_SPHERE_LEN_PAIR ? 2 : 1);
     ON_DEVICE(device);
     DevBuf b_in, b_out;
     HIP_TRY(b_in.alloc((size_t)n * n_in * sizeof(double)));

@@ -88,6 +88,58 @@ __device__ __forceinline__ double sphere_len(V3 centre, double r2, V3 o, V3 d) {
 }
 __device__ __forceinline__ double sphere_len(const ObjRec &ob, V3 o, V3 d) { return sphere_len(ld3(ob.a), ob.s0, o, d); }
 
+// sphere_len of two spheres A and B at once, as two independent instruction chains in one basic block: sphere_len alone is one
+// dependent fp64 chain behind two exec-mask branches and sqrt_cr's ballot, and a wave that is alone on its SIMD (the glass
+// sphere's tiles at the end of a frame) waits out every link of it.  Here both (l, tca, l2, d2) chains are computed by all
+// lanes, the tests become selects, one wave-level decision covers "some lane needs a root of A or of B", and the two roots
+// run side by side.  Every len is the result of sphere_len's operations in sphere_len's order; what is computed beyond that
+// (d2 of a lane that fails the first test, the root of 1.0 in a lane that needs none) is discarded.  (Taking the roots side by
+// side only where BOTH spheres have a lane that needs one, and a lone one as sphere_len does, executes fewer instructions and
+// was measured slower: 3.285-3.287 against 3.239-3.252 ms)
+// sqrt_cr's choice of form is kept per sphere: the library form is taken for a sphere exactly when a lane that needs THAT
+// sphere's root has its argument outside [2^-767, 2^1000] -- the lanes sqrt_cr's ballot sees in sphere_len -- and then that
+// sphere goes through sqrt_cr itself under its own lanes' mask.  Called by all lanes of the wave.
+// (cgrt_math_probe's CGRT_PROBE_SPHERE_LEN_PAIR; tests/test_gpu_sphere_pair_math.py compares it with sphere_len bit for bit)
+__device__ __forceinline__ void sphere_len_pair(V3 cA, double r2A, V3 cB, double r2B, V3 o, V3 d, double &lenA, double &lenB) {
+    const V3 lA = cA - o, lB = cB - o;
+    const double tcaA = dot(lA, d), tcaB = dot(lB, d);
+    const double l2A = dot(lA, lA), l2B = dot(lB, lB);
+    const double d2A = l2A - tcaA * tcaA, d2B = l2B - tcaB * tcaB;
+    const bool rootA = !(tcaA < 0 && l2A > r2A) && !(d2A > r2A), rootB = !(tcaB < 0 && l2B > r2B) && !(d2B > r2B);
+    lenA = kInf;
+    lenB = kInf;
+    if (__ballot(rootA || rootB) == 0ull) return;
+    const double xA = rootA ? r2A - d2A : 1.0, xB = rootB ? r2B - d2B : 1.0;
+    double gA, gB;
+    if (__ballot(!(xA >= 0x1p-767 && xA <= 0x1p1000) || !(xB >= 0x1p-767 && xB <= 0x1p1000)) == 0ull) {
+        // sqrt_cr's short form, twice
+        const double yA = __builtin_amdgcn_rsq(xA), yB = __builtin_amdgcn_rsq(xB);
+        gA = xA * yA;
+        gB = xB * yB;
+        double hA = yA * 0.5, hB = yB * 0.5;
+        const double rA = __builtin_fma(-hA, gA, 0.5), rB = __builtin_fma(-hB, gB, 0.5);
+        gA = __builtin_fma(gA, rA, gA);
+        gB = __builtin_fma(gB, rB, gB);
+        double eA = __builtin_fma(-gA, gA, xA), eB = __builtin_fma(-gB, gB, xB);
+        hA = __builtin_fma(hA, rA, hA);
+        hB = __builtin_fma(hB, rB, hB);
+        gA = __builtin_fma(eA, hA, gA);
+        gB = __builtin_fma(eB, hB, gB);
+        eA = __builtin_fma(-gA, gA, xA);
+        eB = __builtin_fma(-gB, gB, xB);
+        gA = __builtin_fma(eA, hA, gA);
+        gB = __builtin_fma(eB, hB, gB);
+    } else {
+        // some lane's argument needs the range handling: each sphere as sphere_len does it, under the mask of its own lanes
+        gA = gB = 0;
+        if (rootA) gA = sqrt_cr(xA);
+        if (rootB) gB = sqrt_cr(xB);
+    }
+    const double t0A = tcaA - gA, t1A = tcaA + gA, t0B = tcaB - gB, t1B = tcaB + gB;
+    if (rootA) lenA = (t0A < 0) ? t1A : t0A;
+    if (rootB) lenB = (t0B < 0) ? t1B : t0B;
+}
+
 // Plane::intersect's distance, objects.h:505-507: len = ((p - o) . n) / (d . n).  For a normal that is exactly +-e_k the two dot
 // products are +-(p_k - o_k) and +-d_k to the bit -- the other products are +-0 and adding +-0 to a non-zero double changes
 // nothing -- and (-x) / (-y) rounds like x / y, so len is (p_k - o_k) / d_k: one subtraction and the division instead of three
@@ -253,7 +305,9 @@ __device__ __forceinline__ TreeHit tree_hit(const DeviceScene &sc, const LdsAux 
 // SPILL: the kernel variants for such scenes (n_objs > n_lds); without it the list is the whole scene and none of the code for
 // the others exists.
 // NRM = false (SPH only): best.n is left unset -- the eye pass derives a sphere's normal itself, in the branches that use it.
-template <bool TREES, bool BEZ, bool SPH, bool STATS, bool SPILL = false, bool PRE = false, bool HFONLY = false, bool NRM = true>
+// PAIR (SPH without SPILL): the sphere loop takes the spheres two at a time (sphere_len_pair); the same (t, id).
+template <bool TREES, bool BEZ, bool SPH, bool STATS, bool SPILL = false, bool PRE = false, bool HFONLY = false, bool NRM = true,
+          bool PAIR = false>
 __device__ __forceinline__ SceneHit intersect_scene(const ObjRec *__restrict__ objs, int n_lds, int n_objs, const DeviceScene &sc,
                                                     V3 o, V3 d, RayKey &rk, bool on, const LdsAux &aux,
                                                     uint32_t &n_node, uint32_t &n_tri) {
@@ -264,7 +318,25 @@ __device__ __forceinline__ SceneHit intersect_scene(const ObjRec *__restrict__ o
     int nsrc = 0;  // 0: sphere (normal derived after the loop), 1: stored in best.n
     if (SPH) {
         // scenes made of spheres only: no kind dispatch, nothing but (t, id) carried round the loop
-        for (int i = 0; i < n_lds; i++) {
+        static_assert(!PAIR || (SPH && !SPILL), "PAIR: the LDS-resident sphere loop");
+        int i_single = 0;
+        if (PAIR) {
+            for (int i = 0; i + 1 < n_lds; i += 2) {
+                double lenA, lenB;
+                const ObjRec &A = objs[i], &B = objs[i + 1];
+                sphere_len_pair(ld3(A.a), A.s0, ld3(B.a), B.s0, o, d, lenA, lenB);
+                if (lenA < best.t) {  // A before B, each with the strict <: a tie goes to the earlier object (main.cpp:57)
+                    best.t = lenA;
+                    best.id = i;
+                }
+                if (lenB < best.t) {
+                    best.t = lenB;
+                    best.id = i + 1;
+                }
+            }
+            i_single = n_lds & ~1;  // an odd last sphere
+        }
+        for (int i = i_single; i < n_lds; i++) {
             const double len = sphere_len(objs[i], o, d);
             if (len < best.t) {
                 best.t = len;

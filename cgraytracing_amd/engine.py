@@ -157,12 +157,13 @@ class Scene:
     def trace_grid(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                    stripe=None, sample_offset=0, spp_total=None, out=None, nhit=None, counters=None, stream=None,
                    stats=False, accumulate=False, split_samples=False, reorder=True, force_reorder=False, tile_order=True,
-                   diffuse_tiles=False):
+                   diffuse_tiles=False, sphere_pairs=True):
         """Asynchronous launch on torch's current stream (or `stream`).  reorder=False: CGRT_GRID_NO_REORDER (tiles in image
         order instead of heaviest-first; same image).  tile_order=False: CGRT_GRID_NO_TILE_ORDER (an image-order launch starts
         its tiles row-major instead of mirror / glass tiles first; same image).  diffuse_tiles=True: CGRT_GRID_DIFFUSE_TILES (a
         sphere-only scene's tiles that see no mirror or glass are rendered by the terminal-diffuse launch beside the main one,
-        not by the full kernel; same image, off by default).  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
+        not by the full kernel; same image, off by default).  sphere_pairs=False: CGRT_GRID_NO_SPHERE_PAIRS (a glass sphere
+        scene's kernel tests one sphere at a time and renders every tile with the full body; same image).  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
         workgroups share a tile's samples; reproducible, fp64 summation order differs from the sample-by-sample sum).  Returns (rgb, nhit, counters) torch
         tensors on the scene's device: float32 [rows,width,3], int32 [rows,width] (bit pattern uint32),
         int64 [8] (counters are ADDED to)."""
@@ -182,7 +183,7 @@ class Scene:
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (2 if accumulate else 0) | (4 if split_samples else 0) |
                               (0 if reorder else 8) | (16 if force_reorder else 0) | (0 if tile_order else 64) |
-                              (128 if diffuse_tiles else 0))
+                              (128 if diffuse_tiles else 0) | (0 if sphere_pairs else 256))
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         check(self._L.cgrt_trace_grid(self._h, C.byref(cc), C.byref(g), out.data_ptr(),
                                       nhit.data_ptr() if nhit is not None else None,
@@ -312,7 +313,7 @@ class Scene:
 
     def trace_grid_host(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                         stripe=None, sample_offset=0, spp_total=None, stats=False, split_samples=False, reorder=True,
-                        force_reorder=False, tile_order=True, diffuse_tiles=False):
+                        force_reorder=False, tile_order=True, diffuse_tiles=False, sphere_pairs=True):
         """Synchronous form with numpy outputs (no torch needed): dict(rgb, nhit, counters)."""
         rows = height - row_offset if rows is None else rows
         rgb = np.zeros((rows, width, 3), np.float32)
@@ -320,7 +321,8 @@ class Scene:
         cnt = np.zeros((_capi.CGRT_NCOUNTERS,), np.uint64)
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (4 if split_samples else 0) | (0 if reorder else 8) |
-                              (16 if force_reorder else 0) | (0 if tile_order else 64) | (128 if diffuse_tiles else 0))
+                              (16 if force_reorder else 0) | (0 if tile_order else 64) | (128 if diffuse_tiles else 0) |
+                              (0 if sphere_pairs else 256))
         check(self._L.cgrt_trace_grid_host(self._h, C.byref(cc), C.byref(g), rgb.ctypes.data, nhit.ctypes.data,
                                            cnt.ctypes.data))
         return dict(rgb=rgb, nhit=nhit, counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]),
@@ -343,6 +345,13 @@ class Scene:
         (cgrt_scene_last_diffuse_tiles; synchronises the device); 0: that call issued none."""
         n = C.c_int64()
         check(self._L.cgrt_scene_last_diffuse_tiles(self._h, C.byref(n)))
+        return int(n.value)
+
+    def last_inkernel_diffuse_tiles(self):
+        """Tiles of this scene's last trace_grid / trace_grid_host whose workgroups ran the terminal-diffuse body inside the
+        main launch (cgrt_scene_last_inkernel_diffuse_tiles; synchronises the device); 0: none did."""
+        n = C.c_int64()
+        check(self._L.cgrt_scene_last_inkernel_diffuse_tiles(self._h, C.byref(n)))
         return int(n.value)
 
     def trace_grid_hitpoints(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None,
@@ -743,15 +752,15 @@ def tonemap_rgb8(image, device=0):
 
 def math_probe(op, values, device=0):
     """cgrt_math_probe: the kernels' own inline device math on a numpy array (function-level probe).  op "sqrt": [n] -> [n];
-    "normalized": [n,3] -> [n,3]; "sphere_len": [n,10] = centre, radius2, origin, direction -> [n].  Elements 64k .. 64k+63
-    are the lanes of one wave."""
+    "normalized": [n,3] -> [n,3]; "sphere_len": [n,10] = centre, radius2, origin, direction -> [n]; "sphere_len_pair": [n,14]
+    = centre A, radius2 A, centre B, radius2 B, origin, direction -> [n,2].  Elements 64k .. 64k+63 are the lanes of one wave."""
     code, cols = {"sqrt": (_capi.PROBE_SQRT, 1), "normalized": (_capi.PROBE_NORMALIZED, 3),
-                  "sphere_len": (_capi.PROBE_SPHERE_LEN, 10)}[op]
+                  "sphere_len": (_capi.PROBE_SPHERE_LEN, 10), "sphere_len_pair": (_capi.PROBE_SPHERE_LEN_PAIR, 14)}[op]
     values = np.ascontiguousarray(values, np.float64)
     if values.shape[1:] != (() if cols == 1 else (cols,)):
         raise ValueError("math_probe(%r): expected shape [n%s], got %r" % (op, "" if cols == 1 else ",%d" % cols, values.shape))
     n = values.shape[0]
-    out = np.zeros((n, 3) if cols == 3 else (n,), np.float64)
+    out = np.zeros((n, 3) if cols == 3 else ((n, 2) if cols == 14 else (n,)), np.float64)
     check(_capi.lib().cgrt_math_probe(device, code, values.ctypes.data, n, out.ctypes.data))
     return out
 

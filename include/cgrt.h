@@ -106,6 +106,13 @@ enum {
                                  hit counts and counters either way; cgrt_scene_last_diffuse_tiles reads back how many tiles
                                  it took.  Off by default: it executes fewer instructions, but on the measured frame the
                                  longest workgroup bounds the frame and runs slower beside the denser launch */
+    CGRT_GRID_NO_SPHERE_PAIRS = 256, /* image-order launches of sphere-only scenes with a refracting sphere that the tile order
+                                 serves: by default their kernel tests the spheres two at a time, as two independent
+                                 instruction chains (",PAIR=1," in cgrt_trace_grid_variant's name), and in tile order the
+                                 class-3 tiles -- those CGRT_GRID_DIFFUSE_TILES would hand to a second launch -- take the
+                                 terminal-diffuse body inside that one launch (cgrt_scene_last_inkernel_diffuse_tiles).  This
+                                 flag restores the loop over one sphere at a time and the full body for every tile.  Same
+                                 image, hit counts and counters either way; it exists to test one against the other      */
     CGRT_GRID_HITPOINTS = 32, /* cgrt_trace_grid_variant only: name the launch of the Hitpoint capture
                                  (cgrt_trace_grid_hitpoints, the eye pass of cgrt_ppm_render) instead of cgrt_trace_grid's;
                                  ignored by the other calls                                                            */
@@ -533,6 +540,9 @@ int cgrt_scene_last_tile_order(const cgrt_scene *s, uint32_t *plan5, uint32_t *l
  * the handle, the number of tiles that launch rendered (synchronises the device; 0: none was issued). */
 int cgrt_trace_grid_diffuse_variant(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, char *name, size_t cap);
 int cgrt_scene_last_diffuse_tiles(const cgrt_scene *s, int64_t *n_tiles);
+/* The same count for the one-launch form (see CGRT_GRID_NO_SPHERE_PAIRS): the tiles of the LAST cgrt_trace_grid on the handle
+ * whose workgroups ran the terminal-diffuse body inside the main launch (synchronises the device; 0: none did). */
+int cgrt_scene_last_inkernel_diffuse_tiles(const cgrt_scene *s, int64_t *n_tiles);
 
 /* Host evaluation of the lens stream (cgrt_rng.hpp, the same inline code the kernel runs): writes
  * uniform_sampling_circle(radius) (sampling.h:35-43) for n (pixel, sample) pairs as 3 doubles each.  Lets CPU-only
@@ -545,12 +555,14 @@ int cgrt_lens_samples(uint64_t seed, const int64_t *pixel, const int32_t *sample
  *   CGRT_PROBE_NORMALIZED  in[n][3]  -> out[n][3] = Vec3::normalize (vec3.h:35-43)
  *   CGRT_PROBE_SPHERE_LEN  in[n][10] -> out[n]    = len of Sphere::intersect (objects.h:45-68) for {centre(3), radius2,
  *                                                   rayorig(3), raydir(3)}; a miss gives 1e10 (the kernels' "no hit yet")
+ *   CGRT_PROBE_SPHERE_LEN_PAIR in[n][14] -> out[n][2] = the same for two spheres at once, as the pair loop computes them:
+ *                                                   {centre A(3), radius2 A, centre B(3), radius2 B, rayorig(3), raydir(3)}
  * Launch geometry is part of the contract, because these functions decide per WAVE which form they take: element i is handled
  * by thread i % 256 of block i / 256, so elements 64k .. 64k+63 are the 64 lanes of one wave, and a lane with i >= n leaves
  * before the call -- the last wave decides with its live lanes only.
  * CGRT_ERR_INVALID: unknown op, null pointer, n < 0 (checked before any device is touched); n == 0 does nothing;
  * more than 2^28 elements: CGRT_ERR_LIMIT. */
-enum { CGRT_PROBE_SQRT = 0, CGRT_PROBE_NORMALIZED = 1, CGRT_PROBE_SPHERE_LEN = 2 };
+enum { CGRT_PROBE_SQRT = 0, CGRT_PROBE_NORMALIZED = 1, CGRT_PROBE_SPHERE_LEN = 2, CGRT_PROBE_SPHERE_LEN_PAIR = 4 /* 3: not an op */ };
 int cgrt_math_probe(int device, int op, const double *in, int64_t n, double *out);
 
 #ifdef __cplusplus
