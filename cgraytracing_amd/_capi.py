@@ -90,6 +90,10 @@ class RayResults(C.Structure):
                 ("hit_normal3", C.c_void_p)]
 
 
+class HitAttributes(C.Structure):
+    _fields_ = [("prim", C.c_void_p), ("uv2", C.c_void_p), ("color3", C.c_void_p), ("material2", C.c_void_p)]
+
+
 class RayPixels(C.Structure):
     _fields_ = [("width", C.c_int32), ("rows", C.c_int32), ("spp", C.c_int32), ("pad_", C.c_int32), ("pixel", C.c_void_p)]
 
@@ -169,6 +173,8 @@ SIGNATURES = {
     "cgrt_scene_last_inkernel_diffuse_tiles": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "cgrt_trace_rays": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(RayResults), C.c_void_p, C.c_void_p]),
     "cgrt_trace_rays_host": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(RayResults), C.c_void_p]),
+    "cgrt_ray_hit_attributes": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.c_void_p, C.c_void_p, C.POINTER(HitAttributes), C.c_void_p]),
+    "cgrt_ray_hit_attributes_host": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.c_void_p, C.c_void_p, C.POINTER(HitAttributes)]),
     "cgrt_trace_rays_variant": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(RayResults), C.c_char_p, C.c_size_t]),
     "cgrt_trace_rays_hitpoints": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cgrt_camera_rays": (C.c_int, [C.POINTER(Camera), C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

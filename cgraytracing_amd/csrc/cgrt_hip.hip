@@ -40,6 +40,7 @@
 #include "cgrt_eye.hpp"
 #include "cgrt_primwalk.hpp"
 #include "cgrt_rays.hpp"
+#include "cgrt_hit_attr.hpp"
 
 using namespace cgrt;
 
@@ -100,6 +101,9 @@ struct cgrt_scene {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     cgrt_build_info build_info{};  // filled by cgrt_scene_commit
     std::vector<TreeRec> tree_recs;  // host copy of dev.trees (where a device-built tree's records live)
+    // cgrt_ray_hit_attributes' prim: per record of dev.tris the triangle's index in its tree's construction order.  Built and
+    // uploaded by the first call that asks for prim (a scene that never asks pays nothing); immutable afterwards
+    mutable GrowBuf tri_ids;
 };
 
 static thread_local std::string g_err;
@@ -180,12 +184,13 @@ int cgrt_scene_create(cgrt_scene **out) {
 
 void cgrt_scene_destroy(cgrt_scene *s) {
     if (!s) return;
-    if (!s->allocs.empty() || s->scratch.p || s->order_buf.p || s->aux_stream) {
+    if (!s->allocs.empty() || s->scratch.p || s->order_buf.p || s->tri_ids.p || s->aux_stream) {
         DeviceGuard g(s->device);
         if (g.err == hipSuccess) {
             for (void *p : s->allocs) (void)hipFree(p);
             s->scratch.release();
             s->order_buf.release();
+            s->tri_ids.release();
             if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
             if (s->ev_join) (void)hipEventDestroy(s->ev_join);
             if (s->aux_stream) (void)hipStreamDestroy(s->aux_stream);
@@ -448,7 +453,7 @@ int cgrt_scene_get_stats(const cgrt_scene *s, cgrt_scene_stats *out) {
     bytes += 56 * out->n_nodes + 72 * out->n_triangles;
     for (auto &t : H.textures) bytes += 3 * (int64_t)t.rows * t.cols;
     out->scene_bytes_fp64 = bytes;
-    out->device_bytes = s->device_bytes + (int64_t)s->scratch.cap + (int64_t)s->order_buf.cap;  // uploaded scene + the handle's launch scratch
+    out->device_bytes = s->device_bytes + (int64_t)s->scratch.cap + (int64_t)s->order_buf.cap + (int64_t)s->tri_ids.cap;  // uploaded scene + the handle's launch scratch (+ the hit-attribute table once asked for)
     out->committed = s->committed ? 1 : 0;
     return CGRT_OK;
 }
@@ -1409,6 +1414,109 @@ int cgrt_camera_rays_host(const cgrt_camera *cam, const cgrt_grid *grid, double 
                 if (keys) keys[i] = c.key;
             }
     return CGRT_OK;
+}
+
+}  // extern "C"
+
+// ---- hit attributes of caller-supplied rays (cgrt_hit_attr.hpp) ----
+static int check_hit_attributes(const cgrt_scene *s, const cgrt_rays *r, const int32_t *hit_obj, const double *hit_t,
+                                const cgrt_hit_attributes *out) {
+    if (!s || !r || !out || !hit_obj || !hit_t) return fail(CGRT_ERR_INVALID, "null argument");
+    if (r->n < 0) return fail(CGRT_ERR_INVALID, "negative ray count");
+    if (r->n > 0 && (!r->org3 || !r->dir3)) return fail(CGRT_ERR_INVALID, "null org3 / dir3");
+    if (r->n > kMaxRays) return fail(CGRT_ERR_LIMIT, "more than 2^36 rays in one call");
+    if (r->n > 0 && !s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");  // (no rays: nothing is looked at)
+    return CGRT_OK;
+}
+
+// The table behind `prim`: a host-built tree's tris[] are in the reference's leaf order (HostTree::leaf_ids maps it to
+// construction order), a device-built tree's in construction order already (cgrt_devbuild.hpp).
+static int need_tri_ids(const cgrt_scene *s) {
+    if (s->tri_ids.p) return CGRT_OK;
+    size_t total = 0;
+    for (const TreeRec &tr : s->tree_recs) total = std::max(total, (size_t)tr.tri_begin + (size_t)tr.ntris);
+    std::vector<int32_t> ids(std::max(total, (size_t)1), -1);
+    for (size_t ti = 0; ti < s->tree_recs.size(); ti++) {
+        const TreeRec &tr = s->tree_recs[ti];
+        const HostTree &T = s->host.trees[ti];
+        for (size_t k = 0; k < (size_t)tr.ntris; k++)
+            ids[(size_t)tr.tri_begin + k] = T.dev_kind ? (int32_t)k : T.leaf_ids[k];
+    }
+    if (s->tri_ids.need(ids.size() * sizeof(int32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(CGRT_ERR_DEVICE, "cannot allocate the hit-attribute triangle table");
+    }
+    const hipError_t e = hipMemcpy(s->tri_ids.p, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        s->tri_ids.release();
+        return fail(CGRT_ERR_DEVICE, std::string("hit-attribute triangle table: ") + hipGetErrorString(e));
+    }
+    return CGRT_OK;
+}
+
+extern "C" {
+
+int cgrt_ray_hit_attributes(const cgrt_scene *s, const cgrt_rays *rays, const int32_t *hit_obj, const double *hit_t,
+                            const cgrt_hit_attributes *out, void *stream) {
+    int rc = check_hit_attributes(s, rays, hit_obj, hit_t, out);
+    if (rc) return rc;
+    if (rays->n == 0 || (!out->prim && !out->uv2 && !out->color3 && !out->material2)) return CGRT_OK;
+    ON_DEVICE(s->device);
+    if (out->prim && (rc = need_tri_ids(s))) return rc;
+    HitAttrParams hp{};
+    hp.n = rays->n;
+    hp.org = rays->org3;
+    hp.dir = rays->dir3;
+    hp.hit_obj = hit_obj;
+    hp.hit_t = hit_t;
+    hp.prim = out->prim;
+    hp.uv = out->uv2;
+    hp.color = out->color3;
+    hp.material = out->material2;
+    hp.tri_ids = out->prim ? reinterpret_cast<const int32_t *>(s->tri_ids.p) : nullptr;
+    hipLaunchKernelGGL(ray_hit_attributes_kernel, dim3((unsigned)((rays->n + 255) / 256)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), s->dev, hp);
+    HIP_TRY(hipGetLastError());
+    return CGRT_OK;
+}
+
+int cgrt_ray_hit_attributes_host(const cgrt_scene *s, const cgrt_rays *rays, const int32_t *hit_obj, const double *hit_t,
+                                 const cgrt_hit_attributes *out) {
+    int rc = check_hit_attributes(s, rays, hit_obj, hit_t, out);
+    if (rc) return rc;
+    const size_t n = (size_t)rays->n;
+    if (n == 0) return CGRT_OK;
+    ON_DEVICE(s->device);
+    DevBuf b_o, b_d, b_obj, b_t, b_prim, b_uv, b_col, b_mat;
+    cgrt_rays dr = *rays;
+    cgrt_hit_attributes dout{};
+    HIP_TRY(b_o.alloc(n * 24));
+    HIP_TRY(b_d.alloc(n * 24));
+    HIP_TRY(b_obj.alloc(n * 4));
+    HIP_TRY(b_t.alloc(n * 8));
+    HIP_TRY(hipMemcpy(b_o.p, rays->org3, n * 24, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_d.p, rays->dir3, n * 24, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_obj.p, hit_obj, n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_t.p, hit_t, n * 8, hipMemcpyHostToDevice));
+    dr.org3 = b_o.as<double>();
+    dr.dir3 = b_d.as<double>();
+    dr.keys = nullptr;
+    if (out->prim) { HIP_TRY(b_prim.alloc(n * 4)); dout.prim = b_prim.as<int32_t>(); }
+    if (out->uv2) { HIP_TRY(b_uv.alloc(n * 16)); dout.uv2 = b_uv.as<double>(); }
+    if (out->color3) { HIP_TRY(b_col.alloc(n * 24)); dout.color3 = b_col.as<double>(); }
+    if (out->material2) { HIP_TRY(b_mat.alloc(n * 16)); dout.material2 = b_mat.as<double>(); }
+    rc = cgrt_ray_hit_attributes(s, &dr, b_obj.as<int32_t>(), b_t.as<double>(), &dout, nullptr);
+    if (rc == CGRT_OK) {
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess) rc = fail(CGRT_ERR_DEVICE, std::string("kernel: ") + hipGetErrorString(e));
+    }
+    if (rc == CGRT_OK) {
+        if (out->prim) HIP_TRY(hipMemcpy(out->prim, b_prim.p, n * 4, hipMemcpyDeviceToHost));
+        if (out->uv2) HIP_TRY(hipMemcpy(out->uv2, b_uv.p, n * 16, hipMemcpyDeviceToHost));
+        if (out->color3) HIP_TRY(hipMemcpy(out->color3, b_col.p, n * 24, hipMemcpyDeviceToHost));
+        if (out->material2) HIP_TRY(hipMemcpy(out->material2, b_mat.p, n * 16, hipMemcpyDeviceToHost));
+    }
+    return rc;
 }
 
 }  // extern "C"

@@ -302,6 +302,89 @@ class Scene:
         res.update(counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]), nhp=int(cnt[_capi.CNT_HITPOINTS]))
         return res
 
+    # ---- hit attributes of caller-supplied rays ----
+    _ATTR_WANT = ("prim", "uv", "color", "material")
+
+    def hit_attributes(self, org, dirs, hit_obj, hit_t, want=("prim", "uv", "color", "material"), out=None, stream=None):
+        """cgrt_ray_hit_attributes on torch tensors: org, dirs float64 [n,3], hit_obj int32 [n] and hit_t float64 [n] -- the
+        last two as trace_rays(want=("hit",)) wrote them for the same rays --, all contiguous on the scene's device.  want:
+        which attributes -- "prim" (int32 [n]: the triangle's index in its mesh's or bump floor's construction order, -1 where
+        the hit is no triangle), "uv" (float64 [n,2]: the hit point is (1-u-v)*pa + u*pb + v*pc), "color" (float64 [n,3]:
+        getSurfaceColor at the hit) and "material" (float64 [n,2]: reflection, transparency).  out: dict of preallocated
+        result tensors to write into.  Asynchronous on torch's current stream (or `stream`).  Returns a dict of the tensors."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        for name, t in (("org", org), ("dirs", dirs)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == 3 and
+                    t.is_contiguous() and t.device == dev):
+                raise ValueError("hit_attributes: %s must be a contiguous float64 [n,3] tensor on %s" % (name, dev))
+        n = org.shape[0]
+        if dirs.shape[0] != n:
+            raise ValueError("hit_attributes: org and dirs differ in length")
+        for name, t, dtype in (("hit_obj", hit_obj, torch.int32), ("hit_t", hit_t, torch.float64)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == (n,) and t.is_contiguous() and
+                    t.device == dev):
+                raise ValueError("hit_attributes: %s must be a contiguous %s [n] tensor on %s" % (name, dtype, dev))
+        want = tuple(want)
+        if not want or any(w not in self._ATTR_WANT for w in want):
+            raise ValueError("hit_attributes: want is a non-empty subset of %r" % (self._ATTR_WANT,))
+        shapes = dict(prim=((n,), torch.int32), uv=((n, 2), torch.float64), color=((n, 3), torch.float64),
+                      material=((n, 2), torch.float64))
+        res = {}
+        for name in self._ATTR_WANT:
+            if name not in want:
+                continue
+            shape, dtype = shapes[name]
+            t = out.get(name) if out else None
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=dev)
+            elif not (isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and
+                      t.device == dev):
+                raise ValueError("hit_attributes: out[%r] must be a contiguous %s %r tensor on %s" % (name, dtype, shape, dev))
+            res[name] = t
+        if n == 0:
+            return res
+        ptr = lambda k: res[k].data_ptr() if k in res else None
+        r = _capi.Rays(n, org.data_ptr(), dirs.data_ptr(), None, 0, 0, 1, 0)
+        o = _capi.HitAttributes(ptr("prim"), ptr("uv"), ptr("color"), ptr("material"))
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(self._L.cgrt_ray_hit_attributes(self._h, C.byref(r), hit_obj.data_ptr(), hit_t.data_ptr(), C.byref(o), C.c_void_p(st)))
+        return res
+
+    def hit_attributes_host(self, org, dirs, hit_obj, hit_t, want=("prim", "uv", "color", "material")):
+        """Synchronous form of hit_attributes on numpy arrays (no torch needed): dict of the arrays in `want`."""
+        org = np.ascontiguousarray(org, np.float64)
+        dirs = np.ascontiguousarray(dirs, np.float64)
+        if org.ndim != 2 or org.shape[1] != 3 or dirs.shape != org.shape:
+            raise ValueError("hit_attributes_host: org and dirs must be [n,3] arrays of one length")
+        n = len(org)
+        hit_obj = np.ascontiguousarray(hit_obj)
+        hit_t = np.ascontiguousarray(hit_t)
+        if hit_obj.dtype != np.int32 or hit_obj.shape != (n,):
+            raise ValueError("hit_attributes_host: hit_obj must be an int32 [n] array")
+        if hit_t.dtype != np.float64 or hit_t.shape != (n,):
+            raise ValueError("hit_attributes_host: hit_t must be a float64 [n] array")
+        want = tuple(want)
+        if not want or any(w not in self._ATTR_WANT for w in want):
+            raise ValueError("hit_attributes_host: want is a non-empty subset of %r" % (self._ATTR_WANT,))
+        res = {}
+        if "prim" in want:
+            res["prim"] = np.full(n, -1, np.int32)
+        if "uv" in want:
+            res["uv"] = np.zeros((n, 2), np.float64)
+        if "color" in want:
+            res["color"] = np.zeros((n, 3), np.float64)
+        if "material" in want:
+            res["material"] = np.zeros((n, 2), np.float64)
+        if n == 0:
+            return res
+        ptr = lambda k: res[k].ctypes.data if k in res else None
+        r = _capi.Rays(n, org.ctypes.data, dirs.ctypes.data, None, 0, 0, 1, 0)
+        o = _capi.HitAttributes(ptr("prim"), ptr("uv"), ptr("color"), ptr("material"))
+        check(self._L.cgrt_ray_hit_attributes_host(self._h, C.byref(r), hit_obj.ctypes.data, hit_t.ctypes.data, C.byref(o)))
+        return res
+
     def rays_variant(self, max_depth=5, want=("acc", "nhit", "hit"), stats=False):
         """Name of the trace_rays_kernel instantiation trace_rays launches for these arguments (cgrt_trace_rays_variant)."""
         full = 1 if ("acc" in want or "nhit" in want) else None

@@ -18,7 +18,7 @@
  * Threading: launches on ONE scene handle must be ordered by the caller (same stream, or events between streams) --
  * a handle owns device scratch that consecutive launches reuse (CGRT_GRID_SPLIT_SAMPLES chunk sums; the schedule of a
  * cost-ordered frame; the tile order of an image-order one; the queue counter of cgrt_trace_rays, cgrt_trace_rays_hitpoints and cgrt_ppm_session_create_rays, which
- * are such launches).
+ * are such launches; cgrt_ray_hit_attributes is one too: its first call that asks for `prim` builds a table the handle keeps).
  * All geometry is IEEE double, like the reference (Vec3 = 3 x double, vec3.h:11-30).
  */
 #ifndef CGRT_H
@@ -38,7 +38,8 @@ extern "C" {
                             cgrt_trace_rays_host, cgrt_trace_rays_variant, cgrt_camera_rays, cgrt_camera_rays_host (caller-supplied rays);
                             cgrt_trace_rays_hitpoints, cgrt_ppm_session_create_rays (photon mapping of caller-supplied rays);
                             cgrt_ppm_session_add_photon_rays, cgrt_photon_emit, cgrt_photon_emit_host, cgrt_photon_ray_events
-                            (caller-supplied photons) */
+                            (caller-supplied photons); cgrt_hit_attributes, cgrt_ray_hit_attributes, cgrt_ray_hit_attributes_host
+                            (hit attributes of caller-supplied rays) */
 
 enum {
     CGRT_OK = 0,
@@ -302,6 +303,50 @@ int cgrt_trace_rays_host(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_
 /* Name of the trace_rays_kernel instantiation cgrt_trace_rays would launch for (scene, rays, out), as cgrt_trace_grid_variant
  * names the eye pass's; only rays->n, max_depth, flags and which of out's pointers are NULL matter (no pointer is read). */
 int cgrt_trace_rays_variant(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_results *out, char *name, size_t cap);
+
+/* ---- hit attributes: what a caller needs to shade the hits of a nearest-hit query ----------------------------------
+ * cgrt_trace_rays tells which object a ray hits, where and with which normal.  This call adds, per ray, the triangle and
+ * the point on it, the reference's surface colour at the hit and the object's material.  It is a pass of its own behind the
+ * query: hit_obj / hit_t are what cgrt_trace_rays wrote for the same rays (both required); of `rays` only n, org3 and dir3
+ * are read.  Per ray i:
+ *   a MISS -- hit_obj[i] outside [0, n_objs); -1 is the query's -- gives prim = -1 and zeros in every other array;
+ *   color3    objs[hit_obj]->getSurfaceColor(P), P = org + dir * hit_t (main.cpp:68,77): the bits cgrt_surface_colors(hit_obj,
+ *             P) gives -- the flat colour, except on a textured plane, which takes Texture::color inside the texture
+ *             rectangle;
+ *   material2 the object's reflection and transparency as given to its constructor;
+ *   prim      hit object a TriangleMesh: the triangle's index in CONSTRUCTION order -- the order of
+ *             cgrt_scene_add_mesh_triangles' tri9, of a file's faces and of cgrt_scene_tree_dump's tri9.  A plane with a bump
+ *             floor, hit on its displacement mesh: the index in the bump mesh's construction order (objects.h:485-497), which
+ *             is 2 * (i * (cols/3 - 1) + j) + k for triangle k of cell row i, column j, k = 0 for (a,b,c) and 1 for (d,b,c);
+ *             again the order of that tree's tri9.  -1 in every other case: sphere, Bezier object, plain plane, the flat part of
+ *             a bump plane, or an object none of whose triangles returns exactly hit_t (distances that are not the query's).
+ *             Where several triangles of the object return exactly hit_t, prim is the one the scene walk's own tie rule picks
+ *             (host-built tree: the reference's -- first inside a leaf, last leaf across leaves, objects.h:281,297;
+ *             device-built: the lower construction index), so hit_normal3 is that triangle's normal up to sign;
+ *   uv2       for prim >= 0 the reference's own quotients u = det3/det1, v = det4/det1 of Triangle::intersect
+ *             (objects.h:101-105; determinants associated as vec3.h:95-97, e1 = pa-pb, e2 = pa-pc, s = pa-org).  By Cramer's
+ *             rule the hit point is (1-u-v)*pa + u*pb + v*pc: interpolate per-vertex data with these weights.  Zeros where
+ *             prim = -1.
+ * n == 0 is valid and does nothing (the scene is not even looked at); more than 2^36 rays: CGRT_ERR_LIMIT.  A null scene,
+ * an uncommitted scene, null rays, out, hit_obj or hit_t: CGRT_ERR_INVALID, before any device is touched. */
+typedef struct cgrt_hit_attributes {   /* every pointer may be NULL: only the arrays asked for are written */
+    int32_t *prim;       /* [n]    */
+    double  *uv2;        /* [n][2] */
+    double  *color3;     /* [n][3] */
+    double  *material2;  /* [n][2]  {reflection, transparency} */
+} cgrt_hit_attributes;   /* 32 bytes */
+
+/* DEVICE pointers on the scene's device; asynchronous on `stream`.  With prim or uv2 the winning object's tree is walked
+ * again per ray (an opaque owner's walk is pruned at hit_t, a transparent owner's costs what the query's cost); color3 and
+ * material2 alone walk nothing.  The first call on a handle that asks for prim builds the leaf-to-construction table on the
+ * host and uploads it with a blocking copy (4 bytes per triangle, owned by the handle, counted in
+ * cgrt_scene_stats.device_bytes from then on): make that call outside a stream capture.  A launch on the scene handle
+ * (Threading above). */
+int cgrt_ray_hit_attributes(const cgrt_scene *s, const cgrt_rays *rays, const int32_t *hit_obj, const double *hit_t,
+                            const cgrt_hit_attributes *out, void *stream);
+/* HOST pointers: allocates device buffers, runs, synchronises and copies back, like cgrt_trace_rays_host. */
+int cgrt_ray_hit_attributes_host(const cgrt_scene *s, const cgrt_rays *rays, const int32_t *hit_obj, const double *hit_t,
+                                 const cgrt_hit_attributes *out);
 
 /* The primary rays cgrt_trace_grid starts for sample `sample_offset + k`, k in [0, spp), of every pixel of the grid's rows
  * (contiguous or striped): ray index = (k * rows + local row) * width + w.  org3 / dir3 / keys as in cgrt_rays (any may be

@@ -368,6 +368,39 @@ inline void trace_rays(const std::vector<Object *> &objs, const std::vector<doub
     }
 }
 
+// What a host program needs to shade the hits trace_rays reported (cgrt_ray_hit_attributes_host): per ray the triangle of a
+// mesh or bump floor in construction order (-1 where the hit is no triangle) with the point on it -- (1-u-v)*pa + u*pb + v*pc
+// --, getSurfaceColor at the hit and the object's (reflection, transparency).  `hits` is the RayHit trace_rays filled for the
+// same org3 / dir3.
+struct HitAttributes {
+    std::vector<int32_t> prim;               // 1 per ray
+    std::vector<double> uv, color, material; // 2, 3 and 2 per ray
+};
+inline void hit_attributes(const std::vector<Object *> &objs, const std::vector<double> &org3, const std::vector<double> &dir3,
+                           const RayHit &hits, HitAttributes &attr, int device = 0) {
+    if (org3.size() != dir3.size() || org3.size() % 3) throw Error(CGRT_ERR_INVALID, "hit_attributes: org3 / dir3 are n x 3 doubles");
+    const size_t n = org3.size() / 3;
+    if (hits.obj.size() != n || hits.t.size() != n) throw Error(CGRT_ERR_INVALID, "hit_attributes: hits holds one entry per ray");
+    attr.prim.assign(n, -1);
+    attr.uv.assign(2 * n, 0.0);
+    attr.color.assign(3 * n, 0.0);
+    attr.material.assign(2 * n, 0.0);
+    if (n == 0) return;
+    SceneBuilder sb;
+    for (const Object *o : objs) o->add_to(sb);
+    check(cgrt_scene_commit(sb.scene, device));
+    cgrt_rays r{};
+    r.n = (int64_t)n;
+    r.org3 = org3.data();
+    r.dir3 = dir3.data();
+    cgrt_hit_attributes out{};
+    out.prim = attr.prim.data();
+    out.uv2 = attr.uv.data();
+    out.color3 = attr.color.data();
+    out.material2 = attr.material.data();
+    check(cgrt_ray_hit_attributes_host(sb.scene, &r, hits.obj.data(), hits.t.data(), &out));
+}
+
 // ---- the whole of render() + main()'s PNG loop: main.cpp:169-258, 403-412 ---------------------------------------
 // Photon-pass constants of the reference as runtime fields with the same defaults.
 struct PhotonParams {
