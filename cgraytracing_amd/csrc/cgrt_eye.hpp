@@ -2,6 +2,7 @@
 #ifndef CGRT_EYE_HPP
 #define CGRT_EYE_HPP
 #include "cgrt_scene_walk.hpp"
+#include "cgrt_sphere_mask.h"
 
 // =====================================================================================================
 // the eye pass
@@ -194,6 +195,14 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
         s_end = (g.chunks > 1) ? ((chunk + 1) * g.chunk_spp < g.spp ? (chunk + 1) * g.chunk_spp : g.spp) : g.spp;
         set_pixel(lane & 15, lane >> 4);
     }
+    // DIFF: the spheres a primary ray of this wave tile can meet at all (GridParams::wmask, tile_order_kernel): wave-uniform, read
+    // once through the scalar cache
+    const bool masked = DIFF && g.wmask != nullptr;
+    uint32_t smask = 0u;
+    if (masked) {
+        smask = load_uniform(g.wmask + __builtin_amdgcn_readfirstlane(have_tile ? wy * wtiles_x + wx : 0));
+        if (sc.n_lds < 32) smask &= (1u << sc.n_lds) - 1u;
+    }
     uint64_t k_smp = 0;  // key of the sample whose ray tree this lane is tracing
 
     double acc_r = 0, acc_g = 0, acc_b = 0;
@@ -335,7 +344,8 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
             pre_valid = false;
         }
         const SceneHit hit =
-            intersect_scene<TREES, BEZ, SPH, STATS, SPILL, PRE, HFONLY, !SPH, PAIR>(lobjs, sc.n_lds, sc.n_objs, sc, o, d, rk, have, aux, my_nodes, my_tris);
+            intersect_scene<TREES, BEZ, SPH, STATS, SPILL, PRE, HFONLY, !SPH, PAIR, DIFF>(lobjs, sc.n_lds, sc.n_objs, sc, o, d, rk, have, aux, my_nodes, my_tris,
+                                                                                          masked, smask);
         if (have) {
             my_rays++;
             have = false;
@@ -722,48 +732,10 @@ __global__ void finalize_chunks_kernel(GridParams g, float *__restrict__ rgb, ui
 // deviation over its depth range.  A mesh is bounded by its cover spheres (DeviceScene::cover: up to 64 spheres over
 // median-split groups of its triangles -- a long thin mesh fills little of one sphere around all of it).  Anything doubtful
 // (object behind or around the camera, rows beyond the image) is FULL.
-// The test itself, shared by classify_kernel and tile_order_kernel.  pixel_dir: the pinhole direction of pixel (w, local row j).
-__device__ __forceinline__ V3 pixel_dir(const GridParams &g, V3 cam, int w, int j) {
-    const int h = global_row(g, j);
-    const double px = (2.0 * ((double)w / g.W) - 1) * g.half_width;
-    const double py = (2.0 * ((double)h / g.H) - 1) * g.half_width * g.H / g.W;
-    return normalized(mk(px, py, 0) - cam);
-}
-struct TileCone {  // the cone around a wave tile's pinhole directions: axis dc, half-angle alpha
-    V3 cam, dc;
-    double alpha;
-};
-__device__ __forceinline__ TileCone wave_tile_cone(const GridParams &g, int wx, int wy) {
-    TileCone tc;
-    tc.cam = mk(g.cam[0], g.cam[1], g.cam[2]);
-    const int w0 = wx * kWaveTileW, j0 = wy * kWaveTileH;
-    // corners one pixel beyond the tile on every side (pixels are sampled at their lower-left corner; the margin also covers
-    // the curvature of the angle function along the edges)
-    const V3 c00 = pixel_dir(g, tc.cam, w0 - 1, j0 - 1), c10 = pixel_dir(g, tc.cam, w0 + kWaveTileW, j0 - 1),
-             c01 = pixel_dir(g, tc.cam, w0 - 1, j0 + kWaveTileH), c11 = pixel_dir(g, tc.cam, w0 + kWaveTileW, j0 + kWaveTileH);
-    tc.dc = normalized((c00 + c10) + (c01 + c11));
-    double cmin = fmin(fmin(dot(tc.dc, c00), dot(tc.dc, c10)), fmin(dot(tc.dc, c01), dot(tc.dc, c11)));
-    cmin = fmin(1.0, fmax(-1.0, cmin));
-    tc.alpha = 1.5 * acos(cmin) + 1e-6;
-    return tc;
-}
-// the stripe mapping keeps a wave tile's four rows adjacent (stripes are multiples of 8 rows), so the corners bound it
-// false: the sphere (c, r) may be touched by a primary ray of the tile
-__device__ __forceinline__ bool cone_clear_of(const GridParams &g, const TileCone &tc, V3 c, double r) {
-    r = r * (1 + 1e-9) + 1e-6;
-    if (g.lens_radius > 0) {
-        const double f = g.focus_plane - tc.cam.z;
-        const double s_lo = (c.z - r - tc.cam.z) / f, s_hi = (c.z + r - tc.cam.z) / f;
-        if (!(f > 0) || !(s_lo > 0)) return false;  // object reaches the lens plane or behind it
-        r += g.lens_radius * fmax(fabs(1 - s_lo), fabs(1 - s_hi));
-    }
-    const V3 v = c - tc.cam;
-    const double dist = sqrt(dot(v, v));
-    if (!(dist > r)) return false;
-    double ct = dot(tc.dc, v) / dist;
-    ct = fmin(1.0, fmax(-1.0, ct));
-    return !(acos(ct) <= tc.alpha + asin(r / dist) + 1e-6);
-}
+// The test itself -- pixel_dir, wave_tile_cone, cone_clear_of -- is shared by classify_kernel, tile_order_kernel and the CPU test
+// of the sphere masks: cgrt_sphere_mask.h (plain C++; the stripe mapping keeps a wave tile's four rows adjacent, so the corners
+// one pixel beyond the tile bound it).
+__device__ __forceinline__ Vec3d vec3d(V3 a) { return vec3d(a.x, a.y, a.z); }
 
 __global__ void classify_kernel(DeviceScene sc, GridParams g, unsigned char *__restrict__ light, int n_wt) {
     const int wt = blockIdx.x * blockDim.x + threadIdx.x;
@@ -771,7 +743,7 @@ __global__ void classify_kernel(DeviceScene sc, GridParams g, unsigned char *__r
     const int wtiles_x = (g.W + kWaveTileW - 1) / kWaveTileW;
     const TileCone tc = wave_tile_cone(g, wt % wtiles_x, wt / wtiles_x);
     bool is_light = true;
-    auto clear_of = [&](V3 c, double r) { return cone_clear_of(g, tc, c, r); };
+    auto clear_of = [&](V3 c, double r) { return cone_clear_of(g, tc, vec3d(c), r); };
     for (int i = 0; i < sc.n_objs && is_light; i++) {
         const ObjRec &ob = sc.objs[i];
         if (ob.kind == KIND_SPHERE) {
@@ -809,18 +781,32 @@ __global__ void classify_kernel(DeviceScene sc, GridParams g, unsigned char *__r
 // the camera doubtful -- and the last workgroup must see every other workgroup's wave-tile classes: each workgroup fences its
 // wcls[] stores before its thread 0 counts it in at plan[kOrderArrived] (device-scope atomic), and the last one fences again
 // before it reads them.
-__global__ __launch_bounds__(1024) void tile_order_kernel(GridParams g, OrderSpheres sp, int tiles_x, int tiles_y, uint32_t *__restrict__ plan,
-                                                          uint32_t *__restrict__ list, unsigned char *__restrict__ tcls,
-                                                          unsigned char *__restrict__ wcls) {
+// Sphere masks (wmask != nullptr: a scene of at most 32 spheres and nothing else): the same thread also writes wmask[wave tile],
+// bit i set = sphere i of sc.objs is a CANDIDATE -- some primary ray of the wave tile may get a distance from sphere_len
+// (sphere_surely_missed, cgrt_sphere_mask.h, says no for the others).  The terminal-diffuse body walks only the set bits; its
+// workgroups read masks of their own wave tiles, written by this launch, which has ended when theirs begins.
+__global__ __launch_bounds__(1024) void tile_order_kernel(GridParams g, OrderSpheres sp, DeviceScene sc, int tiles_x, int tiles_y,
+                                                          uint32_t *__restrict__ plan, uint32_t *__restrict__ list,
+                                                          unsigned char *__restrict__ tcls, unsigned char *__restrict__ wcls,
+                                                          uint32_t *__restrict__ wmask) {
     constexpr int NT = 1024;
     const int wtiles_x = (g.W + kWaveTileW - 1) / kWaveTileW, wtiles_y = (g.rows + kWaveTileH - 1) / kWaveTileH;
     const int n_wt = wtiles_x * wtiles_y, n = tiles_x * tiles_y, tid = threadIdx.x;
     for (int wt = blockIdx.x * NT + tid; wt < n_wt; wt += gridDim.x * NT) {
-        const TileCone tc = wave_tile_cone(g, wt % wtiles_x, wt / wtiles_x);
+        TileRays tr;
+        if (wmask) tr = wave_tile_rays(g, wt % wtiles_x, wt / wtiles_x);
+        else tr.cone = wave_tile_cone(g, wt % wtiles_x, wt / wtiles_x);
+        const TileCone &tc = tr.cone;
         int c = 3;
         for (unsigned i = 0; i < sp.n; i++)
-            if (!cone_clear_of(g, tc, mk(sp.s[i][0], sp.s[i][1], sp.s[i][2]), sp.s[i][3])) c = min(c, ((sp.transp >> i) & 1u) ? 1 : 2);
+            if (!cone_clear_of(g, tc, vec3d(sp.s[i][0], sp.s[i][1], sp.s[i][2]), sp.s[i][3])) c = min(c, ((sp.transp >> i) & 1u) ? 1 : 2);
         wcls[wt] = (unsigned char)c;
+        if (wmask) {
+            uint32_t m = 0;
+            for (int i = 0; i < sc.n_objs && i < 32; i++)
+                if (!sphere_surely_missed(g, tr, vec3d(sc.objs[i].a[0], sc.objs[i].a[1], sc.objs[i].a[2]), sc.objs[i].s0)) m |= 1u << i;
+            wmask[wt] = m;
+        }
     }
     __shared__ unsigned last_s;
     __shared__ uint32_t pos[kOrderClasses][NT];
@@ -832,7 +818,7 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(GridParams g, OrderSph
     __threadfence();
     // thread t sorts the tiles [t0, t1): counts per class, a scan over the threads, then the tiles in order
     const int per = (n + NT - 1) / NT, t0 = min(n, tid * per), t1 = min(n, t0 + per);
-    const V3 cam = mk(g.cam[0], g.cam[1], g.cam[2]);
+    const Vec3d cam = vec3d(g.cam[0], g.cam[1], g.cam[2]);
     for (int c = 0; c < kOrderClasses; c++) pos[c][tid] = 0;
     for (int t = t0; t < t1; t++) {
         const int tx = t % tiles_x, ty = t / tiles_x;
@@ -844,12 +830,12 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(GridParams g, OrderSph
             }
         c = max(c, 1);
         if (c == 1) {
-            const V3 d = pixel_dir(g, cam, tx * kTileW + kTileW / 2, ty * kTileH + kTileH / 2);
+            const Vec3d d = pixel_dir(g, cam, tx * kTileW + kTileW / 2, ty * kTileH + kTileH / 2);
             for (unsigned i = 0; i < sp.n; i++) {
                 if (!((sp.transp >> i) & 1u)) continue;
-                const V3 v = mk(sp.s[i][0], sp.s[i][1], sp.s[i][2]) - cam;
-                const double along = dot(d, v);
-                if (along > 0 && along * along - dot(v, v) + sp.s[i][3] * sp.s[i][3] >= 0) c = 0;
+                const Vec3d v = vec3d(sp.s[i][0] - cam.x, sp.s[i][1] - cam.y, sp.s[i][2] - cam.z);
+                const double along = dot3d(d, v);
+                if (along > 0 && along * along - dot3d(v, v) + sp.s[i][3] * sp.s[i][3] >= 0) c = 0;
             }
         }
         tcls[t] = (unsigned char)c;

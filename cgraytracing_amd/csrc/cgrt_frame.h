@@ -52,6 +52,10 @@ struct GridParams {
     // 0-2, resp. workgroup b renders entry plan[3] + b (class 3: the terminal-diffuse variant, on the handle's second stream);
     // kOrderAllDiffuse: every entry, the workgroups from plan[3] on by the terminal-diffuse body inside the same kernel
     int32_t light_mode, tile_order;
+    // wmask != nullptr (tile-order launches of a scene of at most 32 spheres and nothing else): wmask[wave tile] = the spheres some
+    // primary ray of the wave tile may meet, bit i = object i (tile_order_kernel, cgrt_sphere_mask.h); the terminal-diffuse body
+    // tests only those.  nullptr: every sphere.
+    const uint32_t *wmask;
     const uint32_t *order;
     // Tile queue of the scheduled launch (chunks == 1): border[0..plan[3]) = the tiles (ty * tiles_x + tx) with at least one
     // wave tile that is neither heavy nor light, costliest first (plan_kernel); plan[4] = next entry.  The launch is then
@@ -79,13 +83,14 @@ struct GridParams {
     uint64_t seed;
     double cam[3], half_width, focus_plane, lens_radius;
 };
-static_assert(sizeof(GridParams) == 280, "GridParams is a kernel argument: its layout is fixed");
+static_assert(sizeof(GridParams) == 288, "GridParams is a kernel argument: its layout is fixed");
 
 static constexpr int kTileW = 32, kTileH = 8, kThreads = 256;
 // Tile order of image-order launches (tile_order_kernel, cgrt_eye.hpp): the special spheres -- those that reflect or refract --
 // travel as a kernel argument; a scene with more of them than this is left in row-major order.  The handle's order buffer is
-// plan[kOrderPlanWords] | list[n_tiles] | tile class[n_tiles] (bytes) | wave-tile class[n_wt] (bytes); plan[c], c = 0..4 = tiles of
-// classes < c, plan[kOrderArrived] = the workgroups of tile_order_kernel that are through (0 between launches).
+// plan[kOrderPlanWords] | list[n_tiles] | tile class[n_tiles] (bytes) | wave-tile class[n_wt] (bytes) | wave-tile sphere mask[n_wt]
+// (words; GridParams::wmask), each part padded to 256 bytes; plan[c], c = 0..4 = tiles of classes < c, plan[kOrderArrived] = the
+// workgroups of tile_order_kernel that are through (0 between launches).
 static constexpr int kOrderSpheresMax = 16, kOrderClasses = 4, kOrderPlanWords = 8, kOrderArrived = 5;
 static constexpr int kOrderAll = 1, kOrderFull = 2, kOrderDiffuse = 3, kOrderAllDiffuse = 4;  // GridParams::tile_order
 struct OrderSpheres {
@@ -93,7 +98,10 @@ struct OrderSpheres {
     uint32_t n, transp;             // transp: bit i set = sphere i refracts (transp >= kEps), else it only reflects
 };
 static constexpr size_t order_pad(size_t b) { return (b + 255) & ~(size_t)255; }
-inline size_t tile_order_bytes(size_t n_tiles, size_t n_wt) { return order_pad((kOrderPlanWords + n_tiles) * sizeof(uint32_t)) + order_pad(n_tiles) + order_pad(n_wt); }
+inline size_t tile_order_bytes(size_t n_tiles, size_t n_wt) {
+    return order_pad((kOrderPlanWords + n_tiles) * sizeof(uint32_t)) + order_pad(n_tiles) + order_pad(n_wt) + order_pad(n_wt * sizeof(uint32_t));
+}
+static constexpr int kSphereMaskMax = 32;  // spheres a wave tile's mask word holds
 // True when no tile of any grid seen from `cam` can be of class 3: some special sphere fails cone_clear_of (cgrt_eye.hpp) by
 // one of its tests that do not look at the tile -- it reaches the lens plane, or its bound, grown by the lens blur, holds the
 // camera.  The same expressions as on the device; a last-bit difference would only cost an idle launch or leave class-3 tiles
@@ -104,7 +112,7 @@ inline bool order_all_special(const OrderSpheres &sp, const cgrt_camera &cam) {
         if (cam.lens_radius > 0) {
             const double f = cam.focus_plane - cam.cam[2];
             const double s_lo = (sp.s[i][2] - r - cam.cam[2]) / f, s_hi = (sp.s[i][2] + r - cam.cam[2]) / f;
-            if (!(f > 0) || !(s_lo > 0)) return true;
+            if (!(f > 0) || !(s_lo > 0) || !(cam.cam[2] < 0)) return true;
             r += cam.lens_radius * std::max(std::fabs(1 - s_lo), std::fabs(1 - s_hi));
         }
         const double vx = sp.s[i][0] - cam.cam[0], vy = sp.s[i][1] - cam.cam[1], vz = sp.s[i][2] - cam.cam[2];
@@ -166,6 +174,7 @@ struct EyeKnobs {
     int pw_refill = 16, pw_rounds = 8;
     int lds_pad = 0;  // LDS_PAD: extra dynamic LDS bytes of the main launch
     bool no_hfonly = false, no_tile_queue = false, plan_dump = false;
+    bool no_order_reuse = false;  // NO_ORDER_REUSE: tile_order_kernel in front of every tile-order launch (order_tiles)
     const char *timeline_file = nullptr;  // TIMELINE_FILE (nullptr: off)
 };
 inline const char *env_str(const char *name) { const char *e = std::getenv(name); return e ? e : ""; }
@@ -187,6 +196,7 @@ inline EyeKnobs eye_knobs() {
         k.no_hfonly = env_on("CGRT_NO_HFONLY");
         k.no_tile_queue = env_on("CGRT_NO_TILE_QUEUE");
         k.plan_dump = env_on("CGRT_PLAN_DUMP");
+        k.no_order_reuse = env_on("CGRT_NO_ORDER_REUSE");
         return k;
     }();
     EyeKnobs k = once;

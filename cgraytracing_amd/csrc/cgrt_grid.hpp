@@ -3,6 +3,7 @@
 #define CGRT_GRID_HPP
 #include "cgrt_device_math.hpp"
 #include "cgrt_frame.h"  // GridParams, the workgroup / tile constants
+#include "cgrt_sphere_mask.h"  // global_row
 
 static constexpr uint32_t kNoWaveTile = 0xffffffffu;
 // Pending refracted rays (main.cpp:157) of a lane, newest last:
@@ -19,15 +20,6 @@ static constexpr int kLdsLevels = 2;
 static constexpr size_t kLevelBytes = (size_t)kThreads * (kPendDoubles * sizeof(double) + sizeof(uint32_t));
 static constexpr size_t kStackBytes = (size_t)kLdsLevels * kLevelBytes;
 static constexpr size_t kTileBytes = (size_t)8 * 32 * 3 * sizeof(float);
-
-// local row -> global row (cgrt.h: block-cyclic stripes)
-__host__ __device__ __forceinline__ int global_row(const GridParams &g, int j) {
-    if (g.stripe_nranks > 1) {
-        int S = g.stripe_rows;
-        return ((j / S) * g.stripe_nranks + g.stripe_rank) * S + (j % S);
-    }
-    return g.row_offset + j;
-}
 
 // Workgroup shapes.  NT = 256: four waves on a 32x8-pixel tile (2x2 sub-tiles of 16x4).  NT = 64: ONE wave on a 16x4 tile --
 // a workgroup's wave slots and LDS are only handed on when its LAST wave retires, so with four very unequal waves (a

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -89,6 +90,23 @@ struct cgrt_scene {
     bool order_ok = false;
     mutable GrowBuf order_buf;
     mutable size_t order_tiles = 0;
+    // ... the wave tiles it wrote sphere masks for (0: none), and what the buffer holds: the order depends on nothing but
+    // OrderKey, so a launch with the key of the buffer's contents runs no ordering kernel (order_reused).  ev_order is recorded
+    // behind the kernel on order_stream; a reusing launch on another stream waits for it.  commit_gen: this commit's number.
+    mutable size_t mask_wtiles = 0;
+    struct OrderKey {
+        double cam[3], half_width, focus_plane, lens_radius;
+        int32_t W, H, rows, row_offset, stripe_rows, stripe_rank, stripe_nranks, masks;
+        uint64_t commit_gen;
+        const void *buf;
+    };
+    static_assert(sizeof(OrderKey) == 96, "OrderKey is compared as bytes: no padding");
+    mutable OrderKey order_key{};
+    mutable bool order_valid = false, order_reused = false;
+    mutable bool order_captured = false;  // a launch on this handle was captured into a graph: its replays rewrite the buffer at times the handle does not see, so nothing is reused any more
+    mutable hipEvent_t ev_order = nullptr;
+    mutable hipStream_t order_stream = nullptr;
+    uint64_t commit_gen = 0;
     // the terminal-diffuse launch over the order's class-3 tiles (sphere-only scenes; it runs on aux_stream beside the main
     // launch): whether the last launch issued one
     mutable bool diffuse_issued = false;
@@ -184,7 +202,7 @@ int cgrt_scene_create(cgrt_scene **out) {
 
 void cgrt_scene_destroy(cgrt_scene *s) {
     if (!s) return;
-    if (!s->allocs.empty() || s->scratch.p || s->order_buf.p || s->tri_ids.p || s->aux_stream) {
+    if (!s->allocs.empty() || s->scratch.p || s->order_buf.p || s->tri_ids.p || s->aux_stream || s->ev_order) {
         DeviceGuard g(s->device);
         if (g.err == hipSuccess) {
             for (void *p : s->allocs) (void)hipFree(p);
@@ -193,6 +211,7 @@ void cgrt_scene_destroy(cgrt_scene *s) {
             s->tri_ids.release();
             if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
             if (s->ev_join) (void)hipEventDestroy(s->ev_join);
+            if (s->ev_order) (void)hipEventDestroy(s->ev_order);
             if (s->aux_stream) (void)hipStreamDestroy(s->aux_stream);
         }
     }
@@ -414,6 +433,9 @@ int cgrt_scene_commit(cgrt_scene *s, int device) {
     open_light_stream(s, knobs.aux_priority, d, s->order_ok && d.all_spheres != 0);
     s->dev = d;
     s->committed = true;
+    static std::atomic<uint64_t> commits{0};
+    s->commit_gen = ++commits;  // what an earlier commit left in the order buffer is not this scene's
+    s->order_valid = false;
     s->tree_recs = std::move(L.trees);
     size_t fr = 0, tot = 0;
     s->mem_total = hipMemGetInfo(&fr, &tot) == hipSuccess ? tot : ((size_t)32 << 30);
@@ -961,24 +983,66 @@ static int primary_walk(const cgrt_scene *s, const EyeLaunch &L, const GridParam
 // The tile order of an image-order launch over a scene with reflecting or refracting spheres (tile_order_kernel, cgrt_eye.hpp):
 // one small launch in front of the eye launch, on its stream, that lists the tiles the costly ones first; g then maps the
 // eye launch's workgroups through the list.  The buffer is launch scratch of the handle, written and read on this stream.
-static int order_tiles(const cgrt_scene *s, const FramePlan &p, GridParams &g, hipStream_t st) {
+// masks: the launch also writes the wave tiles' sphere masks (GridParams::wmask) for the terminal-diffuse body.
+// The kernel reads the camera, the frame geometry (W, H, rows, row offset, stripe) and the committed scene, nothing else: when
+// the buffer still holds the result for exactly these (cgrt_scene::OrderKey -- the passes of a progressive render, the frames of
+// a still camera) nothing is launched and g points at it.  The eye launch only reads the buffer (plan[0..4], the list, the
+// masks; plan[kOrderArrived] is back at 0 when the kernel ends), so it is as the kernel left it.  The contents are not trusted
+// beyond a commit, a reallocation, a cgrt_trace_grid that returned an error (it drops the key on every such exit) or a stream capture (a captured
+// launch runs later, or never, and again at every replay: from the first capture on, the handle neither reuses nor leaves a key).
+// One handle serves one stream at a time (cgrt.h, "Threading"): a launch with another key rewrites the buffer, and the event only
+// orders a reusing launch behind the kernel that wrote it, not a rewrite behind another stream's readers.
+// no_reuse (CGRT_NO_ORDER_REUSE=1, a measurement aid): every launch runs the kernel.
+static int order_tiles(const cgrt_scene *s, const FramePlan &p, GridParams &g, bool masks, bool no_reuse, hipStream_t st) {
     const int tiles_x = (g.W + kTileW - 1) / kTileW, tiles_y = (g.rows + kTileH - 1) / kTileH;
-    const size_t n = (size_t)tiles_x * tiles_y;
-    const void *before = s->order_buf.p;
-    if (s->order_buf.need(tile_order_bytes(n, p.n_wt)) != hipSuccess) {
+    const size_t n = (size_t)tiles_x * tiles_y, bytes = tile_order_bytes(n, p.n_wt);
+    const bool grown = bytes > s->order_buf.cap;
+    if (grown) s->order_valid = false;
+    if (s->order_buf.need(bytes) != hipSuccess) {
         (void)hipGetLastError();
         return fail(CGRT_ERR_DEVICE, "cannot allocate launch scratch (tile order)");
     }
     unsigned char *base = reinterpret_cast<unsigned char *>(s->order_buf.p);
     uint32_t *plan = reinterpret_cast<uint32_t *>(base), *list = plan + kOrderPlanWords;
     unsigned char *tcls = base + order_pad((kOrderPlanWords + n) * sizeof(uint32_t)), *wcls = tcls + order_pad(n);
-    if (s->order_buf.p != before) HIP_TRY(hipMemsetAsync(plan, 0, kOrderPlanWords * sizeof(uint32_t), st));  // plan[kOrderArrived]
-    const unsigned blocks = (unsigned)std::min((p.n_wt + 1023) / 1024, (size_t)64);
-    hipLaunchKernelGGL(tile_order_kernel, dim3(blocks), dim3(1024), 0, st, g, s->order_spheres, tiles_x, tiles_y, plan, list, tcls, wcls);
+    uint32_t *wmask = masks ? reinterpret_cast<uint32_t *>(wcls + order_pad(p.n_wt)) : nullptr;
+    cgrt_scene::OrderKey key{{g.cam[0], g.cam[1], g.cam[2]}, g.half_width, g.focus_plane, g.lens_radius, g.W, g.H, g.rows, g.row_offset,
+                             g.stripe_rows, g.stripe_rank, g.stripe_nranks, masks ? 1 : 0, s->commit_gen, s->order_buf.p};
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &capturing) != hipSuccess) {
+        (void)hipGetLastError();
+        capturing = hipStreamCaptureStatusActive;  // unknown: as if it were
+    }
+    if (capturing != hipStreamCaptureStatusNone) s->order_captured = true;
+    const bool plain = !s->order_captured && !no_reuse;
+    s->order_reused = plain && s->order_valid && std::memcmp(&key, &s->order_key, sizeof(key)) == 0;
+    if (s->order_reused) {
+        if (st != s->order_stream) HIP_TRY(hipStreamWaitEvent(st, s->ev_order, 0));
+    } else {
+        s->order_valid = false;
+        if (grown) HIP_TRY(hipMemsetAsync(plan, 0, kOrderPlanWords * sizeof(uint32_t), st));  // plan[kOrderArrived]
+        const unsigned blocks = (unsigned)std::min((p.n_wt + 1023) / 1024, (size_t)64);
+        hipLaunchKernelGGL(tile_order_kernel, dim3(blocks), dim3(1024), 0, st, g, s->order_spheres, s->dev, tiles_x, tiles_y, plan, list, tcls, wcls, wmask);
+        if (plain && hipPeekAtLastError() == hipSuccess) {
+            if (!s->ev_order && hipEventCreateWithFlags(&s->ev_order, hipEventDisableTiming) != hipSuccess) {
+                (void)hipGetLastError();
+                s->ev_order = nullptr;
+            }
+            if (s->ev_order && hipEventRecord(s->ev_order, st) == hipSuccess) {
+                s->order_key = key;
+                s->order_stream = st;
+                s->order_valid = true;
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+    }
     g.plan = plan;
     g.border = list;
+    g.wmask = wmask;
     g.tile_order = kOrderAll;
     s->order_tiles = n;
+    s->mask_wtiles = masks ? p.n_wt : 0;
     return CGRT_OK;
 }
 
@@ -1047,10 +1111,21 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     const size_t n_blocks = (size_t)p.heavy_blocks + p.grid_dim;
     // image order, one workgroup per tile with all its samples, row-major: the tiles that see a mirror or glass sphere first
     s->order_tiles = 0;
+    s->mask_wtiles = 0;
+    s->order_reused = false;
     s->diffuse_issued = false;
     s->diffuse_in_kernel = false;
+    // sphere masks: where a terminal-diffuse body will run (either form) over a list of at most 32 spheres, all of them in LDS
+    const bool diffuse_body = diffuse_wanted(s, cam, grid, L, kn) || (L.k.pair && !order_all_special(s->order_spheres, *cam));
+    const bool masks = diffuse_body && d.all_spheres != 0 && d.n_objs <= kSphereMaskMax && d.n_objs == d.n_lds && !(grid->flags & CGRT_GRID_NO_SPHERE_MASKS);
+    // every exit with an error from here on drops the stored order's key (order_tiles): only a call that went through leaves one
+    struct DropKey {
+        const cgrt_scene *s;
+        bool through = false;
+        ~DropKey() { if (!through) s->order_valid = false; }
+    } drop_key{s};
     if (L.form == EyeForm::Image && p.chunks == 1 && !p.xcd_tiles && L.k.nt == kThreads && s->order_ok &&
-        !(grid->flags & CGRT_GRID_NO_TILE_ORDER) && (rc = order_tiles(s, p, g, st)))
+        !(grid->flags & CGRT_GRID_NO_TILE_ORDER) && (rc = order_tiles(s, p, g, masks, kn.no_order_reuse, st)))
         return rc;
     DevBuf timeline;
     if (kn.timeline_file) {
@@ -1093,6 +1168,7 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     const hipError_t launch_err = hipGetLastError();
     if (g.timeline && launch_err == hipSuccess && (rc = write_timeline(kn.timeline_file, timeline, n_blocks, p, L.k.nt, st))) return rc;
     if (launch_err != hipSuccess) return fail(CGRT_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(launch_err));
+    drop_key.through = true;
     return kn.plan_dump && g.plan && !g.tile_order ? dump_plan(p, g, st) : CGRT_OK;
 }
 
@@ -1108,6 +1184,27 @@ int cgrt_scene_last_tile_order(const cgrt_scene *s, uint32_t *plan5, uint32_t *l
     if (plan5) HIP_TRY(hipMemcpy(plan5, base, (kOrderClasses + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (list) HIP_TRY(hipMemcpy(list, base + kOrderPlanWords * sizeof(uint32_t), n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (cls) HIP_TRY(hipMemcpy(cls, base + order_pad((kOrderPlanWords + n) * sizeof(uint32_t)), n, hipMemcpyDeviceToHost));
+    return CGRT_OK;
+}
+
+int cgrt_scene_last_sphere_masks(const cgrt_scene *s, uint32_t *masks, int64_t cap, int64_t *n_wave_tiles) {
+    if (!s || !n_wave_tiles) return fail(CGRT_ERR_INVALID, "null argument");
+    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+    ON_DEVICE(s->device);
+    const size_t n_wt = s->mask_wtiles, n = s->order_tiles;
+    *n_wave_tiles = (int64_t)n_wt;
+    if (n_wt == 0 || n == 0 || !masks || cap < (int64_t)n_wt) return CGRT_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    const unsigned char *base = reinterpret_cast<const unsigned char *>(s->order_buf.p);
+    HIP_TRY(hipMemcpy(masks, base + order_pad((kOrderPlanWords + n) * sizeof(uint32_t)) + order_pad(n) + order_pad(n_wt), n_wt * sizeof(uint32_t),
+                      hipMemcpyDeviceToHost));
+    return CGRT_OK;
+}
+
+int cgrt_scene_last_tile_order_reused(const cgrt_scene *s, int32_t *reused) {
+    if (!s || !reused) return fail(CGRT_ERR_INVALID, "null argument");
+    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+    *reused = s->order_reused ? 1 : 0;
     return CGRT_OK;
 }
 

@@ -306,11 +306,14 @@ __device__ __forceinline__ TreeHit tree_hit(const DeviceScene &sc, const LdsAux 
 // the others exists.
 // NRM = false (SPH only): best.n is left unset -- the eye pass derives a sphere's normal itself, in the branches that use it.
 // PAIR (SPH without SPILL): the sphere loop takes the spheres two at a time (sphere_len_pair); the same (t, id).
+// MASKED (SPH without SPILL and PAIR: the terminal-diffuse body): with `masked` (wave-uniform) the loop visits only the spheres
+// whose bit is set in `mask` (wave-uniform; bits below n_lds), in ascending order -- ties still go to the earlier sphere.  Every
+// sphere left out returns kInf for every ray the wave can trace (GridParams::wmask), so (t, id) are those of the full loop.
 template <bool TREES, bool BEZ, bool SPH, bool STATS, bool SPILL = false, bool PRE = false, bool HFONLY = false, bool NRM = true,
-          bool PAIR = false>
+          bool PAIR = false, bool MASKED = false>
 __device__ __forceinline__ SceneHit intersect_scene(const ObjRec *__restrict__ objs, int n_lds, int n_objs, const DeviceScene &sc,
                                                     V3 o, V3 d, RayKey &rk, bool on, const LdsAux &aux,
-                                                    uint32_t &n_node, uint32_t &n_tri) {
+                                                    uint32_t &n_node, uint32_t &n_tri, bool masked = false, uint32_t mask = 0u) {
     SceneHit best;
     best.t = kInf;  // `nearest = INF`, main.cpp:54
     best.id = -1;
@@ -319,6 +322,18 @@ __device__ __forceinline__ SceneHit intersect_scene(const ObjRec *__restrict__ o
     if (SPH) {
         // scenes made of spheres only: no kind dispatch, nothing but (t, id) carried round the loop
         static_assert(!PAIR || (SPH && !SPILL), "PAIR: the LDS-resident sphere loop");
+        static_assert(!MASKED || (SPH && !SPILL && !PAIR && !NRM), "MASKED: the terminal-diffuse body's sphere loop");
+        if (MASKED && masked) {
+            for (uint32_t m = mask; m != 0u; m &= m - 1u) {
+                const int i = __builtin_ctz(m);
+                const double len = sphere_len(objs[i], o, d);
+                if (len < best.t) {
+                    best.t = len;
+                    best.id = i;
+                }
+            }
+            return best;
+        }
         int i_single = 0;
         if (PAIR) {
             for (int i = 0; i + 1 < n_lds; i += 2) {

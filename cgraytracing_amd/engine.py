@@ -157,13 +157,14 @@ class Scene:
     def trace_grid(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                    stripe=None, sample_offset=0, spp_total=None, out=None, nhit=None, counters=None, stream=None,
                    stats=False, accumulate=False, split_samples=False, reorder=True, force_reorder=False, tile_order=True,
-                   diffuse_tiles=False, sphere_pairs=True):
+                   diffuse_tiles=False, sphere_pairs=True, sphere_masks=True):
         """Asynchronous launch on torch's current stream (or `stream`).  reorder=False: CGRT_GRID_NO_REORDER (tiles in image
         order instead of heaviest-first; same image).  tile_order=False: CGRT_GRID_NO_TILE_ORDER (an image-order launch starts
         its tiles row-major instead of mirror / glass tiles first; same image).  diffuse_tiles=True: CGRT_GRID_DIFFUSE_TILES (a
         sphere-only scene's tiles that see no mirror or glass are rendered by the terminal-diffuse launch beside the main one,
         not by the full kernel; same image, off by default).  sphere_pairs=False: CGRT_GRID_NO_SPHERE_PAIRS (a glass sphere
-        scene's kernel tests one sphere at a time and renders every tile with the full body; same image).  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
+        scene's kernel tests one sphere at a time and renders every tile with the full body; same image).  sphere_masks=False:
+        CGRT_GRID_NO_SPHERE_MASKS (the terminal-diffuse body tests every sphere, not only its wave tile's candidates; same image).  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
         workgroups share a tile's samples; reproducible, fp64 summation order differs from the sample-by-sample sum).  Returns (rgb, nhit, counters) torch
         tensors on the scene's device: float32 [rows,width,3], int32 [rows,width] (bit pattern uint32),
         int64 [8] (counters are ADDED to)."""
@@ -183,7 +184,7 @@ class Scene:
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (2 if accumulate else 0) | (4 if split_samples else 0) |
                               (0 if reorder else 8) | (16 if force_reorder else 0) | (0 if tile_order else 64) |
-                              (128 if diffuse_tiles else 0) | (0 if sphere_pairs else 256))
+                              (128 if diffuse_tiles else 0) | (0 if sphere_pairs else 256) | (0 if sphere_masks else 512))
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         check(self._L.cgrt_trace_grid(self._h, C.byref(cc), C.byref(g), out.data_ptr(),
                                       nhit.data_ptr() if nhit is not None else None,
@@ -396,7 +397,7 @@ class Scene:
 
     def trace_grid_host(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                         stripe=None, sample_offset=0, spp_total=None, stats=False, split_samples=False, reorder=True,
-                        force_reorder=False, tile_order=True, diffuse_tiles=False, sphere_pairs=True):
+                        force_reorder=False, tile_order=True, diffuse_tiles=False, sphere_pairs=True, sphere_masks=True):
         """Synchronous form with numpy outputs (no torch needed): dict(rgb, nhit, counters)."""
         rows = height - row_offset if rows is None else rows
         rgb = np.zeros((rows, width, 3), np.float32)
@@ -405,7 +406,7 @@ class Scene:
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (4 if split_samples else 0) | (0 if reorder else 8) |
                               (16 if force_reorder else 0) | (0 if tile_order else 64) | (128 if diffuse_tiles else 0) |
-                              (0 if sphere_pairs else 256))
+                              (0 if sphere_pairs else 256) | (0 if sphere_masks else 512))
         check(self._L.cgrt_trace_grid_host(self._h, C.byref(cc), C.byref(g), rgb.ctypes.data, nhit.ctypes.data,
                                            cnt.ctypes.data))
         return dict(rgb=rgb, nhit=nhit, counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]),
@@ -422,6 +423,25 @@ class Scene:
         plan, lst, cls = np.zeros(5, np.uint32), np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint8)
         check(self._L.cgrt_scene_last_tile_order(self._h, plan.ctypes.data, lst.ctypes.data, cls.ctypes.data, n.value, C.byref(n)))
         return dict(plan=plan, list=lst, cls=cls)
+
+    def last_sphere_masks(self):
+        """The sphere masks of this scene's last trace_grid / trace_grid_host (cgrt_scene_last_sphere_masks; synchronises the
+        device): None when that launch wrote none, else uint32 [wave tiles], bit i = sphere i may be met by a primary ray of
+        the 16x4 wave tile wy * ceil(width / 16) + wx."""
+        n = C.c_int64()
+        check(self._L.cgrt_scene_last_sphere_masks(self._h, None, 0, C.byref(n)))
+        if n.value == 0:
+            return None
+        masks = np.zeros(n.value, np.uint32)
+        check(self._L.cgrt_scene_last_sphere_masks(self._h, masks.ctypes.data, n.value, C.byref(n)))
+        return masks
+
+    def last_tile_order_reused(self):
+        """True when this scene's last trace_grid / trace_grid_host ran no ordering kernel because the handle still held the
+        order of the same camera and frame geometry (cgrt_scene_last_tile_order_reused)."""
+        f = C.c_int32()
+        check(self._L.cgrt_scene_last_tile_order_reused(self._h, C.byref(f)))
+        return bool(f.value)
 
     def last_diffuse_tiles(self):
         """Tiles the terminal-diffuse launch of this scene's last trace_grid / trace_grid_host rendered

@@ -114,6 +114,12 @@ enum {
                                  terminal-diffuse body inside that one launch (cgrt_scene_last_inkernel_diffuse_tiles).  This
                                  flag restores the loop over one sphere at a time and the full body for every tile.  Same
                                  image, hit counts and counters either way; it exists to test one against the other      */
+    CGRT_GRID_NO_SPHERE_MASKS = 512, /* the terminal-diffuse body (CGRT_GRID_DIFFUSE_TILES, or inside the main launch: see
+                                 CGRT_GRID_NO_SPHERE_PAIRS) over a scene of at most 32 spheres and nothing else: by default the
+                                 ordering kernel also finds, per 16x4-pixel wave tile, the spheres that some primary ray of the
+                                 tile may meet, and the body tests only those (cgrt_scene_last_sphere_masks).  This flag
+                                 restores the loop over every sphere.  Same image, hit counts and counters either way; it
+                                 exists to test one against the other                                                  */
     CGRT_GRID_HITPOINTS = 32, /* cgrt_trace_grid_variant only: name the launch of the Hitpoint capture
                                  (cgrt_trace_grid_hitpoints, the eye pass of cgrt_ppm_render) instead of cgrt_trace_grid's;
                                  ignored by the other calls                                                            */
@@ -579,6 +585,20 @@ int cgrt_trace_grid_variant(const cgrt_scene *s, const cgrt_camera *cam, const c
  * see a reflecting sphere, 3 the rest), list[i] = the tile (ty * ceil(width / 32) + tx) workgroup i rendered, cls[t] = class
  * of tile t. */
 int cgrt_scene_last_tile_order(const cgrt_scene *s, uint32_t *plan5, uint32_t *list, uint8_t *cls, int64_t cap, int64_t *n_tiles);
+
+/* The sphere masks of that launch (see CGRT_GRID_NO_SPHERE_MASKS): *n_wave_tiles = the number of 16x4 wave tiles
+ * (ceil(width / 16) x ceil(rows / 4), numbered wy * ceil(width / 16) + wx) it wrote a mask for, 0 when it wrote none.  With
+ * cap >= *n_wave_tiles: synchronises the device and copies them to HOST memory; bit i of masks[wave tile] = sphere i (in the
+ * order the objects were added) may be met by a primary ray of the wave tile. */
+int cgrt_scene_last_sphere_masks(const cgrt_scene *s, uint32_t *masks, int64_t cap, int64_t *n_wave_tiles);
+/* Whether the LAST cgrt_trace_grid on the handle ran no ordering kernel because the order (and masks) it had computed for the
+ * same camera, frame geometry, rows and stripe were still in the handle's buffer: *reused = 1, else 0.  An order depends on
+ * nothing else -- not on the seed, the samples or the depth -- so the passes of a progressive render compute it once.
+ * The stored order lives in the handle's launch scratch: as for every launch on a handle, the caller orders launches on one
+ * handle, and launches of one handle that are in flight together on different streams must use the same camera and frame.
+ * A handle one of whose launches was captured into a graph (hipStreamBeginCapture) reuses nothing from then on: a captured
+ * launch runs later, and again at every replay. */
+int cgrt_scene_last_tile_order_reused(const cgrt_scene *s, int32_t *reused);
 
 /* The terminal-diffuse launch beside cgrt_trace_grid's main launch (see CGRT_GRID_DIFFUSE_TILES): the name of its kernel
  * instantiation for (scene, cam, grid), or an empty string when the grid launches none; and, for the LAST cgrt_trace_grid on
