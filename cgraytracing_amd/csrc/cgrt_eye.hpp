@@ -108,9 +108,23 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
     if (!HEAVY && !g.timeline) {  // (the timeline, a development aid, wants a record from every workgroup)
         if (!__syncthreads_or((int)wave_has_tile<NT>(g, tile_block, tile_grid))) return;
     }
-    // LDS carve-up: [ pending-ray levels (GLASS) | objs | Bezier scratch | node cache ]
+    // LDS carve-up, written out here: wg_lds()'s regions for wg_ask_trace(NT, TREES, BEZ, GLASS, SPILL, HFONLY) (cgrt_wg_lds.h, whose
+    // total the launch requested; the static_assert below holds the two together) -- this body's code generation is measured to
+    // the percent and did not keep its speed through the shared wg_lds_carve.
+    // WALK: HFONLY walks height fields only and has neither node cache nor wide-walk stack.
+    constexpr size_t level_bytes = pending_level_bytes(NT), stack_bytes = (size_t)kLdsLevels * level_bytes;
+    constexpr bool WALK = TREES && !HFONLY;
+    {   // the header's layout for 3 objects, 5 cached nodes and a wide tree has the regions and sizes written out below
+        constexpr WgLds chk = wg_lds(wg_ask_trace(NT, TREES, BEZ, GLASS, SPILL, HFONLY), 3, 5, true);
+        static_assert(chk.pending == 0 && chk.objs == (GLASS ? stack_bytes : 0) && chk.staging - chk.objs == 3 * sizeof(ObjRec) &&
+                          chk.bez - chk.staging == (SPILL ? (NT / 64) * sizeof(ObjRec) : 0) &&
+                          chk.nodes - chk.bez == (BEZ ? (NT / 64) * sizeof(BezLds) : 0) &&
+                          chk.wstack - chk.nodes == (WALK ? 5 * sizeof(NodeRec) : 0) && chk.has.nodes == WALK &&
+                          chk.has.wstack == (WALK && !GLASS && !BEZ),
+                      "trace_grid_body's carve-up and cgrt_wg_lds.h");
+    }
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    ObjRec *lobjs = reinterpret_cast<ObjRec *>(lds_raw + (GLASS ? TG::stack_bytes : 0));  // n_objs records
+    ObjRec *lobjs = reinterpret_cast<ObjRec *>(lds_raw + (GLASS ? stack_bytes : 0));  // n_objs records
     // BEZ: one BezLds per wave behind the object list (16-byte aligned: ObjRec is 128 B)
     unsigned char *lrest = reinterpret_cast<unsigned char *>(lobjs + sc.n_lds);
     LdsAux aux;
@@ -122,12 +136,12 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
     if (BEZ) lrest += (NT / 64) * sizeof(BezLds);
     // TREES: node cache behind that (32-byte records, region is 16-byte aligned)
     NodeRec *lnodes = reinterpret_cast<NodeRec *>(lrest);
-    aux.lnodes = (TREES && sc.cached_tree >= 0) ? lnodes : nullptr;
+    aux.lnodes = (WALK && sc.cached_tree >= 0) ? lnodes : nullptr;
     // TREES without glass or Bezier (their LDS is spoken for): the first entries of the wide walk's stack, behind the node cache
-    aux.wstack = (TREES && !GLASS && !BEZ && sc.has_wide)
+    aux.wstack = (WALK && !GLASS && !BEZ && sc.has_wide)
                      ? reinterpret_cast<uint2 *>(lrest + ((sc.cached_tree >= 0 ? (size_t)sc.cached_nodes * sizeof(NodeRec) : 0)))
                      : nullptr;
-    if (TREES && sc.cached_tree >= 0) {
+    if (WALK && sc.cached_tree >= 0) {
         const uint4 *src = reinterpret_cast<const uint4 *>(sc.nodes + sc.trees[sc.cached_tree].node_begin);
         uint4 *dst = reinterpret_cast<uint4 *>(lnodes);
         const int n16 = sc.cached_nodes * (int)(sizeof(NodeRec) / 16);
@@ -212,7 +226,7 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
     Pending deep[2];   // third stack level (scratch; indexed dynamically so that it stays out of registers)
     Pending sib;       // refracted sibling of a leaf-level glass hit (registers)
     bool sib_valid = false;
-    unsigned char *lslot = lds_raw;  // level L, field f of this thread: lslot + L*TG::level_bytes + (f*NT + tid)*8
+    unsigned char *lslot = lds_raw;  // level L, field f of this thread: lslot + L*level_bytes + (f*NT + tid)*8
     int sp = 0;
     int s = (g.chunks > 1) ? chunk * g.chunk_spp : 0;  // next sample to start
     bool have = false;
@@ -450,12 +464,12 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
                                 sib_valid = true;
                             } else {
                                 if (sp < kLdsLevels) {
-                                    double *q = reinterpret_cast<double *>(lslot + sp * TG::level_bytes) + threadIdx.x;
+                                    double *q = reinterpret_cast<double *>(lslot + sp * level_bytes) + threadIdx.x;
                                     q[0 * NT] = pe.o.x; q[1 * NT] = pe.o.y; q[2 * NT] = pe.o.z;
                                     q[3 * NT] = pe.d.x; q[4 * NT] = pe.d.y; q[5 * NT] = pe.d.z;
                                     q[6 * NT] = pe.adj.x; q[7 * NT] = pe.adj.y; q[8 * NT] = pe.adj.z;
                                     // depth_left <= 4 and path < 32: one word
-                                    reinterpret_cast<uint32_t *>(lslot + sp * TG::level_bytes +
+                                    reinterpret_cast<uint32_t *>(lslot + sp * level_bytes +
                                                                  kPendDoubles * NT * sizeof(double))[threadIdx.x] =
                                         ((uint32_t)pe.depth_left << 8) | pe.path;
                                 } else {
@@ -486,12 +500,12 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
                 UTIL(heavy ? 10 : 14);
                 --sp;
                 if (sp < kLdsLevels) {
-                    const double *q = reinterpret_cast<const double *>(lslot + sp * TG::level_bytes) + threadIdx.x;
+                    const double *q = reinterpret_cast<const double *>(lslot + sp * level_bytes) + threadIdx.x;
                     o = mk(q[0 * NT], q[1 * NT], q[2 * NT]);
                     d = mk(q[3 * NT], q[4 * NT], q[5 * NT]);
                     adj = mk(q[6 * NT], q[7 * NT], q[8 * NT]);
                     const uint32_t meta = reinterpret_cast<const uint32_t *>(
-                        lslot + sp * TG::level_bytes + kPendDoubles * NT * sizeof(double))[threadIdx.x];
+                        lslot + sp * level_bytes + kPendDoubles * NT * sizeof(double))[threadIdx.x];
                     depth_left = (int)(meta >> 8);
                     path = meta & 0xffu;
                 } else {

@@ -6,21 +6,6 @@
 #include "cgrt_sphere_mask.h"  // global_row
 
 static constexpr uint32_t kNoWaveTile = 0xffffffffu;
-// Pending refracted rays (main.cpp:157) of a lane, newest last:
-//   * a glass hit whose children are leaves of the recursion (depth_left == 2) keeps the refracted child in
-//     REGISTERS (it is consumed right after the reflected child, before any other push) -- in a full glass tree
-//     that is 8 of the 15 pushes;
-//   * the first two other levels live in LDS: per level 9 doubles + one packed (depth, path) word per thread,
-//     layout [level][field][thread] (conflict-free), 2 x 19 456 B = 38 912 B per workgroup;
-//   * a third level (three nested glass hits with all siblings waiting) spills to scratch memory.
-// The output needs no LDS (each wave transposes its 16x4 tile with lane shuffles), so stack + objs stays under 40 KiB and
-// FOUR workgroups fit a CU's 160 KiB: occupancy 4 waves/SIMD instead of 3, worth ~10 % on C2.
-static constexpr int kPendDoubles = 9;
-static constexpr int kLdsLevels = 2;
-static constexpr size_t kLevelBytes = (size_t)kThreads * (kPendDoubles * sizeof(double) + sizeof(uint32_t));
-static constexpr size_t kStackBytes = (size_t)kLdsLevels * kLevelBytes;
-static constexpr size_t kTileBytes = (size_t)8 * 32 * 3 * sizeof(float);
-
 // Workgroup shapes.  NT = 256: four waves on a 32x8-pixel tile (2x2 sub-tiles of 16x4).  NT = 64: ONE wave on a 16x4 tile --
 // a workgroup's wave slots and LDS are only handed on when its LAST wave retires, so with four very unequal waves (a
 // Bezier vase covering part of a tile: a wave over it works ~100x longer than its neighbours) slots idle; with one wave
@@ -29,11 +14,7 @@ template <int NT>
 struct TileGeom {
     static_assert(NT == 256 || NT == 64, "workgroup = 4 waves or 1 wave");
     static constexpr int W = NT == 256 ? 32 : 16, H = NT == 256 ? 8 : 4;
-    static constexpr size_t level_bytes = (size_t)NT * (kPendDoubles * sizeof(double) + sizeof(uint32_t));
-    static constexpr size_t stack_bytes = (size_t)kLdsLevels * level_bytes;
-    static constexpr size_t tile_bytes = (size_t)W * H * 3 * sizeof(float);
 };
-static_assert(TileGeom<256>::level_bytes == kLevelBytes && TileGeom<256>::tile_bytes == kTileBytes, "TileGeom<256>");
 
 // blockIdx -> tile, XCD-aware.  Workgroups are dealt round-robin to the 8 XCDs, each with a private 4 MiB L2, so the
 // blocks b, b+8, b+16, ... share an L2.  Tiles are grouped in super-tiles of kSuperW x kSuperH tiles (128 x 32 pixels);

@@ -569,7 +569,8 @@ int cgrt_scene_tree_dump(const cgrt_scene *s, int t, int32_t *node_lr_size, int3
 // more than the default 64 KiB where needed.  The static bytes are the compiler's (hipFuncGetAttributes); the static_asserts
 // use kStaticLdsAllowance.
 static constexpr size_t kStaticLdsAllowance = 512;  // the eye kernels have 336 B (ROCm 7.2): wg_cnt, tile_entry, tl_rays, ...
-static constexpr size_t kWideStackLds = (size_t)kThreads * kWideLdsDepth * sizeof(uint2);
+static_assert(sizeof(BezLds) == kBezLdsBytes, "cgrt_wg_lds.h: BezLds");
+static_assert(sizeof(uint2) == 8 && sizeof(Pending) == kPendDoubles * sizeof(double) + 2 * sizeof(uint32_t), "cgrt_wg_lds.h: stack entries");
 
 // The template flags of a trace_grid_kernel / trace_grid_sched_kernel instantiation
 struct EyeFlags {
@@ -595,27 +596,16 @@ static constexpr EyeFlags light_flags(bool trees, bool dof, bool hfonly) { retur
 // the diffuse tiles of a sphere-only scene: the sphere loop, every ray ends at its first hit
 static constexpr EyeFlags diffuse_flags(bool dof) { return {false, false, dof, false, true, false, false, false, false, kThreads, true}; }
 
-// Dynamic LDS of an eye-pass launch, in the order of trace_grid_body's carve-up (cgrt_eye.hpp): pending-ray levels (GLASS) |
-// `resident` objects | one staging record per wave (SPILL) | one BezLds per wave (BEZ) | the cached tree's `cached_nodes`
-// (TREES) | the first entries of the wide walk's stack (TREES without GLASS or BEZ, when the scene has a wide tree).  The
-// HFONLY variant walks height fields only and gets neither of the last two.
+// Dynamic LDS of a launch: the total of the layout its kernel carves up (wg_lds, cgrt_wg_lds.h) for the variant's flags.
+static constexpr WgLdsAsk eye_ask(const EyeFlags &f) { return wg_ask_trace(f.nt, f.trees, f.bez, f.glass, f.spill, f.hfonly); }
 static constexpr size_t eye_lds(const EyeFlags &f, size_t resident, size_t cached_nodes, bool wide) {
-    const size_t waves = (size_t)f.nt / 64;
-    const bool walk = f.trees && !f.hfonly;
-    return (f.glass ? (f.nt == 64 ? TileGeom<64>::stack_bytes : TileGeom<kThreads>::stack_bytes) : 0) +
-           (resident + (f.spill ? waves : 0)) * sizeof(ObjRec) + (f.bez ? waves * sizeof(BezLds) : 0) +
-           (walk ? cached_nodes * sizeof(NodeRec) : 0) + (walk && !f.glass && !f.bez && wide ? kWideStackLds : 0);
+    return wg_lds(eye_ask(f), resident, cached_nodes, wide).total;
 }
-static size_t eye_lds(const EyeFlags &f, const DeviceScene &d) {
-    return eye_lds(f, (size_t)d.n_lds, d.cached_tree >= 0 ? (size_t)d.cached_nodes : 0, d.has_wide != 0);
-}
-// primary_walk_kernel (cgrt_primwalk.hpp): `staged` objects | the wide walk's stack entries
-static constexpr size_t primary_walk_lds(size_t staged) { return staged * sizeof(ObjRec) + kWideStackLds; }
-// photon_trace_kernel (cgrt_photon_trace.hpp): `resident` objects | one staging record per wave (SPILL) | one BezLds per wave (BEZ),
-// or else, without SPILL, the first entries of the wide walk's stack where photon_lds_stack asks for them
+static size_t eye_lds(const EyeFlags &f, const DeviceScene &d) { return wg_lds(eye_ask(f), d).total; }
+// primary_walk_kernel stages `staged` objects; photon_trace_kernel takes the stack where photon_lds_stack asks for it
+static constexpr size_t primary_walk_lds(size_t staged) { return wg_lds(wg_ask_primary_walk(), staged, 0, true).total; }
 static constexpr size_t photon_lds(size_t resident, bool spill, bool bez, bool wide_stack) {
-    return (resident + (spill ? kThreads / 64 : 0)) * sizeof(ObjRec) + (bez ? (kThreads / 64) * sizeof(BezLds) : 0) +
-           (!bez && !spill && wide_stack ? kWideStackLds : 0);
+    return wg_lds(wg_ask_photon(bez, spill), resident, 0, wide_stack).total;
 }
 
 // The template flags of a trace_rays_kernel instantiation (cgrt_rays.hpp)
@@ -627,18 +617,11 @@ struct RayFlags {
                (nt == 64 ? 1 << 7 : 0);
     }
 };
-// trace_rays_kernel: the carve-up of the eye pass (eye_lds) at the kernel's workgroup size -- pending-ray levels (GLASS) |
-// `resident` objects | one staging record per wave (SPILL) | one BezLds per wave (BEZ) | the cached tree (TREES) | the first
-// entries of the wide walk's stack (TREES without GLASS or BEZ, when the scene has a wide tree)
+static constexpr WgLdsAsk rays_ask(const RayFlags &f) { return wg_ask_trace(f.nt, f.trees, f.bez, f.glass, f.spill, false); }
 static constexpr size_t rays_lds(const RayFlags &f, size_t resident, size_t cached_nodes, bool wide) {
-    const size_t waves = (size_t)f.nt / 64;
-    return (f.glass ? (size_t)kLdsLevels * f.nt * (kPendDoubles * sizeof(double) + sizeof(uint32_t)) : 0) +
-           (resident + (f.spill ? waves : 0)) * sizeof(ObjRec) + (f.bez ? waves * sizeof(BezLds) : 0) +
-           (f.trees ? cached_nodes * sizeof(NodeRec) : 0) + (f.trees && !f.glass && !f.bez && wide ? kWideStackLds : 0);
+    return wg_lds(rays_ask(f), resident, cached_nodes, wide).total;
 }
-static size_t rays_lds(const RayFlags &f, const DeviceScene &d) {
-    return rays_lds(f, (size_t)d.n_lds, d.cached_tree >= 0 ? (size_t)d.cached_nodes : 0, d.has_wide != 0);
-}
+static size_t rays_lds(const RayFlags &f, const DeviceScene &d) { return wg_lds(rays_ask(f), d).total; }
 
 static constexpr bool fits_lds(size_t dyn) { return dyn + kStaticLdsAllowance <= kLdsBytes; }
 // Every launch that stages kLdsObjsMax objects fits beside its other LDS (the general variant lowers its count instead):
@@ -834,8 +817,8 @@ static EyeLaunch eye_launch(const cgrt_scene *s, const cgrt_camera *cam, const c
     L.lds = eye_lds(L.k, L.dev) + (L.form == EyeForm::Image || L.form == EyeForm::Sched ? (size_t)kn.lds_pad : 0);
     return L;
 }
-// The light tiles' launch beside the scheduled form (classify_kernel): bump-mapped planes take the tree-capable variant (the
-// same LDS carve-up as the main launch's), or only its height-field walk where that is all they need.
+// The light tiles' launch beside the scheduled form (classify_kernel): bump-mapped planes take the tree-capable variant, or
+// only its height-field walk where that is all they need (HFONLY: no node cache and no wide-walk stack in its LDS).
 static EyeLaunch light_launch(const DeviceScene &d, bool dof, const EyeKnobs &kn) {
     const bool trees = d.light_trees != 0, hf = trees && d.light_hf_only && !kn.no_hfonly;
     EyeLaunch L;

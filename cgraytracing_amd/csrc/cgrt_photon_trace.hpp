@@ -76,21 +76,14 @@ __host__ __device__ inline bool photon_lds_stack(const DeviceScene &sc) { return
 template <bool BEZ, bool SPILL = false, bool RAYS = false>
 __global__ __launch_bounds__(kThreads, BEZ ? 2 : kPhotonWaves) void photon_trace_kernel(DeviceScene sc, PhotonArgs pa, double *__restrict__ events,
                                                                    unsigned char *__restrict__ valid, PhotonRayArgs ra) {
+    // dynamic LDS: the object list, then a staging record per wave (SPILL), a BezLds per wave (BEZ; the Newton starts continue the
+    // photon's own stream) or, with neither, the first entries of the 4-wide walk's stack where photon_lds_stack asks for them
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    ObjRec *lobjs = reinterpret_cast<ObjRec *>(lds_raw);
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(sc.objs);
-        uint4 *dst = reinterpret_cast<uint4 *>(lobjs);
-        const int n16 = sc.n_lds * (int)(sizeof(ObjRec) / 16);
-        for (int k = threadIdx.x; k < n16; k += kThreads) dst[k] = src[k];
-    }
+    const WgLdsPtrs lds = wg_lds_carve(wg_lds(wg_ask_photon(BEZ, SPILL), (size_t)sc.n_lds, 0, photon_lds_stack(sc)), lds_raw);
+    ObjRec *const lobjs = lds.lobjs;
+    const LdsAux aux = lds.aux;
+    wg_stage16<kThreads>(lobjs, sc.objs, sc.n_lds * (int)(sizeof(ObjRec) / 16));
     __syncthreads();
-    unsigned char *lrest = lds_raw + obj_list_lds(sc, kThreads / 64);
-    // BEZ: one BezLds per wave behind the object list; the Newton starts continue the photon's own stream
-    LdsAux aux{BEZ ? reinterpret_cast<volatile BezLds *>(lrest) + (threadIdx.x >> 6) : nullptr, nullptr};
-    if (SPILL) aux.spill = lobjs + sc.n_lds + (threadIdx.x >> 6);
-    // without Bezier objects: the first entries of the 4-wide walk's stack live in LDS behind the object list, as in the eye pass
-    if (!BEZ && !SPILL && photon_lds_stack(sc)) aux.wstack = reinterpret_cast<uint2 *>(lrest);  // (the SPILL launch reserves no room for it)
     const int p = blockIdx.x * kThreads + threadIdx.x;
     bool alive = p < pa.count;
     Stream rs(photon_key(pa.seed, (uint64_t)(pa.first + (alive ? p : 0))));

@@ -40,15 +40,11 @@ struct PrimWalkArgs {
 template <bool DOF>
 __global__ __launch_bounds__(kThreads, 4) void primary_walk_kernel(DeviceScene sc, GridParams g, PrimWalkArgs pw) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    ObjRec *lobjs = reinterpret_cast<ObjRec *>(lds_raw);
     const int n_stage = pw.finish ? sc.n_objs : pw.obj + 1;  // the mesh's record; all of them when units are finished here
-    uint2 *lstack = reinterpret_cast<uint2 *>(lobjs + n_stage);  // [entry][thread], kWideLdsDepth entries; deeper ones in scratch
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(sc.objs);
-        uint4 *dst = reinterpret_cast<uint4 *>(lobjs);
-        const int n16 = n_stage * (int)(sizeof(ObjRec) / 16);
-        for (int k = threadIdx.x; k < n16; k += kThreads) dst[k] = src[k];
-    }
+    const WgLdsPtrs lds = wg_lds_carve(wg_lds(wg_ask_primary_walk(), (size_t)n_stage, 0, true), lds_raw);
+    ObjRec *const lobjs = lds.lobjs;
+    uint2 *const lstack = lds.aux.wstack;  // [entry][thread], kWideLdsDepth entries; deeper ones in scratch
+    wg_stage16<kThreads>(lobjs, sc.objs, n_stage * (int)(sizeof(ObjRec) / 16));
     __syncthreads();
     const int lane = threadIdx.x & 63, tid = threadIdx.x;
     const unsigned long long lanes_below = (1ull << lane) - 1ull;

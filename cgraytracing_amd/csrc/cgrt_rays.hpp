@@ -122,43 +122,23 @@ __device__ __forceinline__ RayStep shade_step(const DeviceScene &sc, const ObjRe
 // lanes were doing.
 // FIRST: nearest-hit query -- one scene walk per ray, no shading, no pending-ray code.
 // CAPTURE: every Hitpoint is also appended to `sink` (capture_rays_kernel below); false compiles all of that away.
-// LDS carve-up as trace_grid_body's: [ pending-ray levels (GLASS) | objs | staging record per wave (SPILL) | BezLds per wave (BEZ)
-// | node cache (TREES) | wide-walk stack (TREES without GLASS or BEZ) ]; rays_lds() in cgrt_hip.hip is its size.
+// Dynamic LDS: wg_ask_trace's layout (cgrt_wg_lds.h), as the eye pass.
 template <bool TREES, bool BEZ, bool GLASS, bool SPH, bool STATS, bool SPILL, bool FIRST, int NT, bool CAPTURE>
 __device__ __forceinline__ void trace_rays_body(const DeviceScene &sc, const RayParams &rp, unsigned long long *wc, const RaySink &sink) {
     static_assert(NT == 256 || NT == 64, "workgroup = 4 waves or 1 wave");
     static_assert(!(FIRST && GLASS), "a nearest-hit query has no pending rays");
     static_assert(!(CAPTURE && (FIRST || STATS)), "Hitpoints come from the full trace; the capture counts nothing");
-    constexpr size_t level_bytes = (size_t)NT * (kPendDoubles * sizeof(double) + sizeof(uint32_t));
-    constexpr size_t stack_bytes = (size_t)kLdsLevels * level_bytes;
+    constexpr size_t level_bytes = pending_level_bytes(NT);
 
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    ObjRec *lobjs = reinterpret_cast<ObjRec *>(lds_raw + (GLASS ? stack_bytes : 0));
-    unsigned char *lrest = reinterpret_cast<unsigned char *>(lobjs + sc.n_lds);
-    LdsAux aux;
-    if (SPILL) {
-        aux.spill = reinterpret_cast<ObjRec *>(lrest) + (threadIdx.x >> 6);
-        lrest += (NT / 64) * sizeof(ObjRec);
-    }
-    aux.bl = BEZ ? reinterpret_cast<volatile BezLds *>(lrest) + (threadIdx.x >> 6) : nullptr;
-    if (BEZ) lrest += (NT / 64) * sizeof(BezLds);
-    NodeRec *lnodes = reinterpret_cast<NodeRec *>(lrest);
-    aux.lnodes = (TREES && sc.cached_tree >= 0) ? lnodes : nullptr;
-    aux.wstack = (TREES && !GLASS && !BEZ && sc.has_wide)
-                     ? reinterpret_cast<uint2 *>(lrest + ((sc.cached_tree >= 0 ? (size_t)sc.cached_nodes * sizeof(NodeRec) : 0)))
-                     : nullptr;
-    if (TREES && sc.cached_tree >= 0) {
-        const uint4 *src = reinterpret_cast<const uint4 *>(sc.nodes + sc.trees[sc.cached_tree].node_begin);
-        uint4 *dst = reinterpret_cast<uint4 *>(lnodes);
-        const int n16 = sc.cached_nodes * (int)(sizeof(NodeRec) / 16);
-        for (int k = threadIdx.x; k < n16; k += NT) dst[k] = src[k];
-    }
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(sc.objs);
-        uint4 *dst = reinterpret_cast<uint4 *>(lobjs);
-        const int n16 = sc.n_lds * (int)(sizeof(ObjRec) / 16);
-        for (int k = threadIdx.x; k < n16; k += NT) dst[k] = src[k];
-    }
+    const WgLds lay = wg_lds(wg_ask_trace(NT, TREES, BEZ, GLASS, SPILL, false), sc);
+    const WgLdsPtrs lds = wg_lds_carve(lay, lds_raw);
+    ObjRec *const lobjs = lds.lobjs;
+    const LdsAux aux = lds.aux;
+    if (lay.has.nodes)
+        wg_stage16<NT>(const_cast<NodeRec *>(aux.lnodes), sc.nodes + sc.trees[sc.cached_tree].node_begin,
+                       sc.cached_nodes * (int)(sizeof(NodeRec) / 16));
+    wg_stage16<NT>(lobjs, sc.objs, sc.n_lds * (int)(sizeof(ObjRec) / 16));
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
@@ -190,7 +170,7 @@ __device__ __forceinline__ void trace_rays_body(const DeviceScene &sc, const Ray
     Pending deep[2];  // third stack level (scratch)
     Pending sib;      // refracted sibling of a leaf-level glass hit (registers)
     bool sib_valid = false;
-    unsigned char *lslot = lds_raw;  // level L, field f of this thread: lslot + L*level_bytes + (f*NT + tid)*8
+    unsigned char *lslot = lds.pending;  // level L, field f of this thread: lslot + L*level_bytes + (f*NT + tid)*8
     int sp = 0;
 
     while (true) {
@@ -398,7 +378,7 @@ __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) voi
     wg_counters_end(wg_cnt, counters);
 }
 // The capture form: the full trace of every ray that has a texel, its Hitpoints appended to `sink`; rp's result pointers are
-// null and nothing is counted.  Same LDS carve-up and occupancy as trace_rays_kernel<..., STATS=false, FIRST=false, NT>.
+// null and nothing is counted.  Same LDS layout and occupancy as trace_rays_kernel<..., STATS=false, FIRST=false, NT>.
 template <bool TREES, bool BEZ, bool GLASS, bool SPH, bool SPILL, int NT>
 __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) void capture_rays_kernel(DeviceScene sc, RayParams rp, RaySink sink) {
     trace_rays_body<TREES, BEZ, GLASS, SPH, false, SPILL, false, NT, true>(sc, rp, nullptr, sink);

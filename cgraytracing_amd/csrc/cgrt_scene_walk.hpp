@@ -3,6 +3,7 @@
 #define CGRT_SCENE_WALK_HPP
 #include "cgrt_bezier.hpp"
 #include "cgrt_traverse.hpp"
+#include "cgrt_wg_lds.h"
 
 // =====================================================================================================
 // Texture::color, texture.h:39-72 (nearest texel, three axis-aligned orientations, d.x tested first)
@@ -244,12 +245,6 @@ __device__ __forceinline__ V3 load_centre(const ObjRec *__restrict__ lobjs, int 
     return ld3(gobjs[id].a);
 }
 
-// bytes of LDS the object list takes in a workgroup: the resident records and, when some objects are not resident, one staging
-// record per wave
-__host__ __device__ inline size_t obj_list_lds(const DeviceScene &sc, int waves) {
-    return ((size_t)sc.n_lds + (sc.n_objs > sc.n_lds ? (size_t)waves : 0)) * sizeof(ObjRec);
-}
-
 // per-workgroup LDS resources handed down to the scene walk
 struct LdsAux {
     volatile BezLds *bl;    // this wave's Bezier scratch (BEZ variants) or nullptr
@@ -257,6 +252,33 @@ struct LdsAux {
     uint2 *wstack = nullptr;  // LDS part of the 4-wide walk's stack ([entry][thread]), or nullptr
     ObjRec *spill = nullptr;  // this wave's staging record for objects beyond the LDS list (scenes with more than kLdsObjsMax objects)
 };
+
+// A workgroup's dynamic LDS as pointers, for every body but trace_grid_body (which writes it out).  `l` is wg_lds() of the kernel's ask
+// and the launch's numbers (cgrt_wg_lds.h) -- the function whose `total` the host requested; a region the launch does not
+// have (l.has) gives nullptr.
+struct WgLdsPtrs {
+    ObjRec *lobjs;           // the resident object list
+    LdsAux aux;              // this wave's staging record and BezLds, the node cache, the wide walk's stack
+    unsigned char *pending;  // base of the pending-ray levels (cgrt_wg_lds.h)
+};
+__device__ __forceinline__ WgLdsPtrs wg_lds_carve(const WgLds &l, unsigned char *lds_raw) {
+    const int wave = threadIdx.x >> 6;
+    WgLdsPtrs p;
+    p.pending = lds_raw + l.pending;
+    p.lobjs = reinterpret_cast<ObjRec *>(lds_raw + l.objs);
+    p.aux.spill = l.has.staging ? reinterpret_cast<ObjRec *>(lds_raw + l.staging) + wave : nullptr;
+    p.aux.bl = l.has.bez ? reinterpret_cast<volatile BezLds *>(lds_raw + l.bez) + wave : nullptr;
+    p.aux.lnodes = l.has.nodes ? reinterpret_cast<NodeRec *>(lds_raw + l.nodes) : nullptr;
+    p.aux.wstack = l.has.wstack ? reinterpret_cast<uint2 *>(lds_raw + l.wstack) : nullptr;
+    return p;
+}
+// The workgroup's NT threads copy n16 16-byte pieces (global -> LDS staging of object records and tree nodes)
+template <int NT>
+__device__ __forceinline__ void wg_stage16(void *dst, const void *src, int n16) {
+    const uint4 *s = reinterpret_cast<const uint4 *>(src);
+    uint4 *d = reinterpret_cast<uint4 *>(dst);
+    for (int k = threadIdx.x; k < n16; k += NT) d[k] = s[k];
+}
 
 // tree traversal entry; `on` = this lane really has a ray for this tree (all lanes of the wave call it).
 // A wave-synchronous variant (one shared node sequence, records fetched through the scalar cache) was measured

@@ -2,7 +2,7 @@
 
 Up to kLdsObjsMax = 768 objects are staged in LDS by every workgroup; the SPILL variants read the rest from HBM.  How many fit
 depends on what else a launch keeps in LDS, so the counts below straddle each launch family's limit.  The arithmetic, from
-cgrt_types.h / cgrt_grid.hpp / cgrt_bezier.hpp: ObjRec 128 B; pending-ray levels kStackBytes = 38 912 B; BezLds 7 872 B, one
+cgrt_types.h / cgrt_wg_lds.h / cgrt_bezier.hpp: ObjRec 128 B; pending-ray levels 2 x 19 456 = 38 912 B; BezLds 7 872 B, one
 per wave (4 waves); the cached tree <= 256 x 32 B (the glass bunny's 255 nodes: 8 160 B; an opaque mesh's triangle-level
 hierarchy is larger and not cached); the wide walk's stack 256 x 16 x 8 = 32 768 B; a workgroup may use 163 840 B, its
 kernel's static __shared__ included (the eye kernels: S = 336 B).
