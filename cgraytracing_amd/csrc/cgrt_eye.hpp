@@ -92,16 +92,26 @@ __device__ __forceinline__ bool wave_has_tile(const GridParams &g, int tile_bloc
     return true;
 }
 
+// A workgroup's part in the sample relay (cgrt_relay.h), workgroup-uniform: slot >= 0 -- it renders chunk `chunk` of the
+// relayed tile in slot `slot` of the relay area, samples [s0, s1); slot < 0: not relayed, all the launch's samples.
+struct RelayWg {
+    int slot = -1, chunk = 0, s0 = 0, s1 = 0;
+};
+
 // The body of the eye pass for one workgroup.  HEAVY selects how the waves get their work (see GridParams): false -- each
 // wave owns one wave tile (16x4 pixels, one per lane) and every lane runs its pixel's samples; true -- the waves serve the
 // queue of heavy-tile items, lanes drawing (pixel, sample) units.  tile_block / tile_grid: this workgroup's index among the
 // tile workgroups and their number (the launch may put heavy workgroups in front of them).
+// PARK (PAIR variants, chunks >= 1 of a relayed tile): a Hitpoint value is not added but stored, slot after slot, in the lane's
+// stream of the relay area; the body keeps no sums.  A relayed workgroup (rw.slot >= 0; PAIR with or without PARK) leaves its
+// sums or counts in the area, and the last of the tile's workgroups to arrive adds them up in chunk order and stores the pixels.
 template <bool TREES, bool BEZ, bool DOF, bool GLASS, bool SPH, bool STATS, bool HPS, int NT, bool HEAVY, bool SPILL = false, bool HFONLY = false,
-          bool DIFF = false, bool PAIR = false>
+          bool DIFF = false, bool PAIR = false, bool PARK = false>
 __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const GridParams &g, float *__restrict__ rgb,
                                                 uint32_t *__restrict__ nhit_out, unsigned long long *__restrict__ counters,
-                                                const HitpointSink &hps, int tile_block, int tile_grid) {
+                                                const HitpointSink &hps, int tile_block, int tile_grid, const RelayWg rw = RelayWg{}) {
     using TG = TileGeom<NT>;
+    static_assert(!PARK || (PAIR && NT == kRelayThreads), "PARK: a relayed tile's later chunks");
     static_assert(!DIFF || (SPH && !GLASS && !HPS && !HEAVY && !STATS && !SPILL), "DIFF: the sphere loop, first hits only");
     static_assert(!PAIR || (SPH && GLASS && !HPS && !HEAVY && !STATS && !SPILL), "PAIR: the glass sphere variants of the tile order");
     const long long tl_t0 = g.timeline ? wall_clock64() : 0;
@@ -206,7 +216,7 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
         // belongs to the other launch of a light / full pair (the probe leaves the light tiles out: they are never heavy)
         if (have_tile && g.hidx && g.hidx[wy * wtiles_x + wx] >= 0) have_tile = false;
         if (have_tile && g.light && (g.light[wy * wtiles_x + wx] != 0) != (g.light_mode != 0)) have_tile = false;
-        s_end = (g.chunks > 1) ? ((chunk + 1) * g.chunk_spp < g.spp ? (chunk + 1) * g.chunk_spp : g.spp) : g.spp;
+        s_end = (g.chunks > 1) ? ((chunk + 1) * g.chunk_spp < g.spp ? (chunk + 1) * g.chunk_spp : g.spp) : (PAIR && rw.slot >= 0 ? rw.s1 : g.spp);
         set_pixel(lane & 15, lane >> 4);
     }
     // DIFF: the spheres a primary ray of this wave tile can meet at all (GridParams::wmask, tile_order_kernel): wave-uniform, read
@@ -228,7 +238,13 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
     bool sib_valid = false;
     unsigned char *lslot = lds_raw;  // level L, field f of this thread: lslot + L*level_bytes + (f*NT + tid)*8
     int sp = 0;
-    int s = (g.chunks > 1) ? chunk * g.chunk_spp : 0;  // next sample to start
+    int s = (g.chunks > 1) ? chunk * g.chunk_spp : (PAIR && rw.slot >= 0 ? rw.s0 : 0);  // next sample to start
+    // PARK: the lane's stream -- value i at park[i * 3 * NT + {0, NT, 2 NT}] -- and the values it holds
+    double *park = nullptr;
+    uint32_t park_n = 0;
+    if (PARK)
+        park = reinterpret_cast<double *>(g.relay + relay_layout((size_t)g.relay_cap, g.relay_k, g.relay_slots).rvals) +
+               ((size_t)rw.slot * (size_t)(g.relay_k - 1) + (size_t)(rw.chunk - 1)) * (size_t)g.relay_slots * (3 * NT) + threadIdx.x;
     bool have = false;
     V3 o = camorg, d = pdir, adj = mk(1, 1, 1);
     int depth_left = 0;
@@ -396,6 +412,14 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
                         q[0] = hf.x;
                         q[1] = hf.y;
                         q[2] = hf.z;
+                    } else if (PARK) {
+                        if (park_n < (uint32_t)g.relay_slots) {  // (always: relay_slots bounds a chunk's ray trees)
+                            double *q = park + (size_t)park_n * (3 * NT);
+                            q[0] = hf.x;
+                            q[NT] = hf.y;
+                            q[2 * NT] = hf.z;
+                        }
+                        park_n++;
                     } else {
                         acc_r += hf.x;
                         acc_g += hf.y;
@@ -542,6 +566,84 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
             if (g.partial_nhit) g.partial_nhit[px] = my_hits;
         }
     } else {
+        uint32_t px_hits = my_hits;  // the pixel's Hitpoints (a relayed tile: of all its chunks)
+        bool store = true;
+        if (PAIR && rw.slot >= 0) {
+            // ---- relay: leave this chunk's results in the tile's slot, publish them, count in; the last workgroup in adds
+            // the chunks up.  Nobody waits for anybody (cgrt_relay.h).
+            const size_t slot = (size_t)rw.slot, k = (size_t)g.relay_k;
+            const RelayLayout rl = relay_layout((size_t)g.relay_cap, g.relay_k, g.relay_slots);  // (here, not across the ray loop)
+            uint32_t *arrive = reinterpret_cast<uint32_t *>(g.relay) + slot;
+            double *racc = reinterpret_cast<double *>(g.relay + rl.racc) + slot * (3 * NT) + threadIdx.x;
+            uint32_t *rhits = reinterpret_cast<uint32_t *>(g.relay + rl.rhits) + slot * k * NT + threadIdx.x;
+            uint32_t *rcount = reinterpret_cast<uint32_t *>(g.relay + rl.rcount) + slot * (k - 1) * NT + threadIdx.x;
+            if (PARK) {
+                rcount[(size_t)(rw.chunk - 1) * NT] = park_n;
+            } else {
+                racc[0] = acc_r;
+                racc[NT] = acc_g;
+                racc[2 * NT] = acc_b;
+            }
+            rhits[(size_t)rw.chunk * NT] = my_hits;
+            // publish: every wave's stores are out, then one agent-scope release in front of the ticket (the XCDs' L2s are
+            // not coherent with one another: nothing narrower makes the values visible to a workgroup on another XCD)
+            __shared__ unsigned int relay_last;
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                const unsigned int ticket = __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const bool last = ticket == (unsigned int)g.relay_k - 1u;
+                if (last) {
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __hip_atomic_store(arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next launch
+                }
+                relay_last = last ? 1u : 0u;
+            }
+            __syncthreads();
+            store = relay_last != 0u;
+            if (store) {
+                // chunk 0's sums, then chunk 1's values in emission order, chunk 2's, ...: acc_r += hf.x; acc_g += hf.y;
+                // acc_b += hf.z of the unsplit loop, addition for addition.  A batch of slots is loaded whole (the loop bound is
+                // the wave's largest count, the area holds every slot) and added where the lane has a value.
+                acc_r = racc[0];
+                acc_g = racc[NT];
+                acc_b = racc[2 * NT];
+                px_hits = rhits[0];
+                for (int c = 1; c < g.relay_k; c++) {
+                    px_hits += rhits[(size_t)c * NT];
+                    uint32_t n = rcount[(size_t)(c - 1) * NT];
+                    if (n > (uint32_t)g.relay_slots) n = (uint32_t)g.relay_slots;
+                    uint32_t n_max = n;
+                    for (int off = 32; off > 0; off >>= 1) {
+                        const uint32_t o2 = (uint32_t)__shfl_xor((int)n_max, off);
+                        n_max = o2 > n_max ? o2 : n_max;
+                    }
+                    n_max = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_max);
+                    const double *q = reinterpret_cast<const double *>(g.relay + rl.rvals) +
+                                      (slot * (k - 1) + (size_t)(c - 1)) * (size_t)g.relay_slots * (3 * NT) + threadIdx.x;
+                    for (uint32_t i0 = 0; i0 < n_max; i0 += kRelayBatch) {
+                        double v[kRelayBatch][3];
+#pragma unroll
+                        for (int u = 0; u < kRelayBatch; u++) {
+                            v[u][0] = q[(size_t)(i0 + u) * (3 * NT)];
+                            v[u][1] = q[(size_t)(i0 + u) * (3 * NT) + NT];
+                            v[u][2] = q[(size_t)(i0 + u) * (3 * NT) + 2 * NT];
+                        }
+#pragma unroll
+                        for (int u = 0; u < kRelayBatch; u++) {
+                            if (i0 + u < n) {
+                                acc_r += v[u][0];
+                                acc_g += v[u][1];
+                                acc_b += v[u][2];
+                            }
+                        }
+                    }
+                }
+            }
+        }
         // ---- store: the wave's 16x4 pixels are 4 rows of 48 contiguous floats; lane l of pass k writes float k*64 + l of
         // the tile, fetched from the lane that owns that pixel (three ds_bpermute shuffles per pass, no LDS, no barrier).
         // A store instruction then covers 256 contiguous bytes of a row (192 + 64 of the next).
@@ -555,12 +657,12 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
             const float a0 = __shfl(v0, src), a1 = __shfl(v1, src), a2 = __shfl(v2, src);
             const float v = ch == 0 ? a0 : (ch == 1 ? a1 : a2);
             const int jj = wy * kWaveTileH + row, ww = wx * kWaveTileW + c / 3;
-            if (have_tile && jj < g.rows && ww < g.W) {
+            if (store && have_tile && jj < g.rows && ww < g.W) {
                 float *dst = rgb + ((size_t)jj * g.W + ww) * 3 + ch;
                 *dst = g.accumulate ? *dst + v : v;  // progressive passes add into the fp32 frame
             }
         }
-        if (nhit_out && have_tile && (w < g.W) && (j < g.rows)) nhit_out[(size_t)j * g.W + w] = my_hits;
+        if (store && nhit_out && have_tile && (w < g.W) && (j < g.rows)) nhit_out[(size_t)j * g.W + w] = px_hits;
     }
 
     if (g.timeline) {  // development aid: when and where this workgroup ran
@@ -630,13 +732,28 @@ __global__ __launch_bounds__(NT, DIFF ? (DOF ? kDiffDofWaves : kDiffWaves) : BEZ
     // A pair of launches shares the list (kOrderFull: the entries of classes 0-2, kOrderDiffuse: those of class 3, the DIFF
     // variant); the host does not know where class 3 begins, so both are launched over all tiles and a workgroup beyond its
     // launch's part leaves here, before anything else.
+    // The sample relay (PAIR variants, g.relay_k > 1; cgrt_relay.h): the list's first entries -- classes 0 and 1, as many as the
+    // relay area holds -- are rendered by relay_k workgroups each; the launch spans relay_cap such entries, the host not knowing
+    // plan[2], and a workgroup whose entry lies beyond the list leaves here.  Index arithmetic on uniform values only.
     int tile_block = (int)blockIdx.x, tile_grid = (int)gridDim.x;
+    unsigned entry = blockIdx.x;
+    RelayWg rw;
     if (g.tile_order) {
-        unsigned entry = blockIdx.x;
         if (g.tile_order == kOrderFull || g.tile_order == kOrderDiffuse) {
             const unsigned first_diffuse = load_uniform(g.plan + 3);
             if (g.tile_order == kOrderDiffuse) entry += first_diffuse;
             if (g.tile_order == kOrderDiffuse ? entry >= load_uniform(g.plan + kOrderClasses) : entry >= first_diffuse) return;
+        } else if (PAIR && g.relay_k > 1) {
+            const unsigned special = load_uniform(g.plan + 2), n_split = special < (unsigned)g.relay_cap ? special : (unsigned)g.relay_cap;
+            const RelayBlock rb = relay_block(blockIdx.x, (unsigned)g.relay_k, n_split);
+            entry = rb.entry;
+            if (entry >= load_uniform(g.plan + kOrderClasses)) return;
+            if (rb.split) {
+                rw.slot = (int)entry;
+                rw.chunk = rb.chunk;
+                rw.s0 = relay_first_sample(rb.chunk, g.relay_chunk_spp);
+                rw.s1 = relay_end_sample(rb.chunk, g.relay_chunk_spp, g.spp);
+            }
         }
         tile_block = (int)load_uniform(g.border + entry);
         tile_grid = -1;
@@ -645,10 +762,12 @@ __global__ __launch_bounds__(NT, DIFF ? (DOF ? kDiffDofWaves : kDiffWaves) : BEZ
     unsigned long long *wc = wg_counters_begin(wg_cnt, counters);
     // kOrderAllDiffuse (PAIR variants only): one launch over the whole list whose class-3 workgroups take the terminal-diffuse
     // body here (workgroup-uniform), at this kernel's registers -- 12 % fewer VALU instructions a frame and no second launch
-    if (PAIR && g.tile_order == kOrderAllDiffuse && blockIdx.x >= load_uniform(g.plan + 3))
+    if (PAIR && g.tile_order == kOrderAllDiffuse && entry >= load_uniform(g.plan + 3))
         trace_grid_body<false, false, DOF, false, true, false, false, NT, false, false, false, true>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid);
+    else if (PAIR && rw.chunk > 0)  // a relayed tile's later chunks park their values
+        trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF, PAIR, PAIR>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid, rw);
     else
-        trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF, PAIR>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid);
+        trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF, PAIR>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid, rw);
     wg_counters_end(wg_cnt, counters);
 }
 // ... or the scheduled form: the first g.heavy_blocks workgroups serve the heavy tiles' unit queue, the others are the tile

@@ -11,6 +11,7 @@
 #include <cstdlib>
 
 #include "../../include/cgrt.h"
+#include "cgrt_relay.h"
 
 // =====================================================================================================
 // kernel parameters
@@ -82,8 +83,14 @@ struct GridParams {
     double inv_spp_total;
     uint64_t seed;
     double cam[3], half_width, focus_plane, lens_radius;
+    // The sample relay (cgrt_relay.h; tile-order launches of the PAIR variants only): relay_k > 1 -- the first
+    // min(plan[2], relay_cap) entries of the list are rendered by relay_k workgroups each, chunk c taking relay_chunk_spp samples
+    // from c * relay_chunk_spp on; `relay` is the handle's relay area, laid out for (relay_cap, relay_k, relay_slots).
+    // relay_k <= 1: every entry by one workgroup.
+    unsigned char *relay;
+    int32_t relay_k, relay_chunk_spp, relay_cap, relay_slots;
 };
-static_assert(sizeof(GridParams) == 288, "GridParams is a kernel argument: its layout is fixed");
+static_assert(sizeof(GridParams) == 312, "GridParams is a kernel argument: its layout is fixed");
 
 static constexpr int kTileW = 32, kTileH = 8, kThreads = 256;
 // Tile order of image-order launches (tile_order_kernel, cgrt_eye.hpp): the special spheres -- those that reflect or refract --
@@ -175,6 +182,8 @@ struct EyeKnobs {
     int lds_pad = 0;  // LDS_PAD: extra dynamic LDS bytes of the main launch
     bool no_hfonly = false, no_tile_queue = false, plan_dump = false;
     bool no_order_reuse = false;  // NO_ORDER_REUSE: tile_order_kernel in front of every tile-order launch (order_tiles)
+    int relay_chunks = kRelayDefaultChunks;  // RELAY_CHUNKS: most workgroups a relayed tile's samples are cut into (2..4)
+    long long relay_tiles = 0;           // RELAY_TILES: > 0: at most this many tiles are relayed (the relay area's capacity)
     const char *timeline_file = nullptr;  // TIMELINE_FILE (nullptr: off)
 };
 inline const char *env_str(const char *name) { const char *e = std::getenv(name); return e ? e : ""; }
@@ -197,6 +206,8 @@ inline EyeKnobs eye_knobs() {
         k.no_tile_queue = env_on("CGRT_NO_TILE_QUEUE");
         k.plan_dump = env_on("CGRT_PLAN_DUMP");
         k.no_order_reuse = env_on("CGRT_NO_ORDER_REUSE");
+        k.relay_chunks = std::min(std::max(env_positive("CGRT_RELAY_CHUNKS", kRelayDefaultChunks), 2), kRelayMaxChunks);
+        k.relay_tiles = std::atoll(env_str("CGRT_RELAY_TILES"));
         return k;
     }();
     EyeKnobs k = once;
@@ -219,6 +230,7 @@ struct FrameInputs {
     EyeKnobs knobs;
     size_t mem_total;
     int n_cu, waves_per_simd;  // waves_per_simd: the scheduled kernel's occupancy (kBezWaves, kSchedTreeWaves or 4)
+    bool relay = false;        // the launch may relay samples (relay_wanted: an image-order launch in tile order, PAIR variant)
 };
 
 // A part of the launch scratch; bytes == 0: not used by this frame (its pointer is nullptr)
@@ -262,7 +274,21 @@ struct FramePlan {
     int wave_slots = 0, items_per_tile = 1, heavy_blocks = 0;
     unsigned long long plan_div = 0;  // plan_kernel: heavy when cost x spp > total x spp / plan_div
     ScratchLayout scratch;
+    // The sample relay (cgrt_relay.h): relay_k > 1 when the launch relays -- workgroups per relayed tile, samples per workgroup,
+    // slots per parked stream, bytes of the relay area per tile, tiles the area is to hold and its bytes (the area lives on the
+    // handle beside the scratch; a launch whose area cannot be had goes without the relay, grid_dim workgroups; with it,
+    // relay_grid(grid_dim, relay_k, relay_cap))
+    int relay_k = 1, relay_chunk_spp = 0, relay_slots = 0;
+    size_t relay_tile_bytes = 0, relay_cap = 0, relay_bytes = 0;
 };
+
+// Whether a launch of n_tiles tiles relays samples by default: at 32 samples or more (two chunks of 16), and with every workgroup
+// slot of the device -- four 256-thread workgroups a CU -- taken at least once, so that the extra workgroups find the chip full
+// of other work; CGRT_GRID_SAMPLE_RELAY lifts the second condition, CGRT_GRID_NO_SAMPLE_RELAY switches the relay off.
+inline bool relay_engaged(int32_t flags, int32_t spp, size_t n_tiles, int n_cu) {
+    if ((flags & CGRT_GRID_NO_SAMPLE_RELAY) || spp < 2 * kRelayMinChunkSpp) return false;
+    return (flags & CGRT_GRID_SAMPLE_RELAY) || n_tiles >= (size_t)4 * (size_t)n_cu;
+}
 
 static constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -291,6 +317,19 @@ inline FramePlan frame_plan(const FrameInputs &in, size_t kmax) {
     p.tile_blocks = one_wave ? tile_grid_blocks(gr.width, gr.rows, false, kWaveTileW, kWaveTileH)
                              : tile_grid_blocks(gr.width, gr.rows, p.xcd_tiles);
     p.grid_dim = (size_t)p.tile_blocks * p.chunks;
+    if (in.relay && p.chunks == 1 && !p.xcd_tiles && !one_wave && relay_engaged(gr.flags, gr.spp, (size_t)p.tile_blocks, in.n_cu)) {
+        const RelayChunks rc = relay_chunks(gr.spp, (gr.flags & CGRT_GRID_SAMPLE_RELAY_4) ? kRelayMaxChunks : kn.relay_chunks);
+        if (rc.k > 1) {
+            p.relay_slots = relay_slots(rc.chunk_spp, gr.max_depth);
+            p.relay_tile_bytes = relay_tile_bytes(rc.k, p.relay_slots);
+            p.relay_cap = relay_cap((size_t)p.tile_blocks, rc.k, p.relay_slots, relay_budget(in.mem_total), kn.relay_tiles);
+            if (p.relay_cap > 0) {
+                p.relay_k = rc.k;
+                p.relay_chunk_spp = rc.chunk_spp;
+                p.relay_bytes = relay_layout(p.relay_cap, rc.k, p.relay_slots).total;
+            }
+        }
+    }
     p.wtiles_x = (gr.width + kWaveTileW - 1) / kWaveTileW;
     p.wtiles_y = (gr.rows + kWaveTileH - 1) / kWaveTileH;
     p.n_wt = (size_t)p.wtiles_x * p.wtiles_y;

@@ -112,6 +112,20 @@ struct cgrt_scene {
     mutable bool diffuse_issued = false;
     // ... and whether its class-3 workgroups took the terminal-diffuse body inside the main launch instead (kOrderAllDiffuse)
     mutable bool diffuse_in_kernel = false;
+    // The sample relay's area (cgrt_relay.h; launch scratch like `scratch`, allocated by the first launch that relays, sized by the
+    // largest): relay_refused -- the smallest size the device has refused (such a launch goes unrelayed); relay_zeroed -- the
+    // arrival words known to be 0 (the kernel leaves them so; a launch that failed on the way does not vouch for it:
+    // relay_dirty); ev_relay is recorded behind a relaying launch on relay_stream, and a relaying launch on another stream waits
+    // for it -- the area is one.  last_relay_*: what the last cgrt_trace_grid relayed with (k == 0: it did not).
+    mutable GrowBuf relay_buf;
+    mutable size_t relay_refused = 0, relay_zeroed = 0;
+    mutable bool relay_dirty = false;
+    mutable hipEvent_t ev_relay = nullptr;
+    mutable hipStream_t relay_stream = nullptr;
+    mutable bool relay_recorded = false;
+    mutable int last_relay_k = 0;
+    mutable size_t last_relay_cap = 0;
+    mutable int last_relay_slots = 0;
     size_t mem_total = 0;                // memory of the scene's device (read at commit; bounds the deferred-value budget)
     int n_cu = 256;                      // compute units of the scene's device (read at commit; wave slots of the scheduler)
     // second stream + fork/join events for the light-tile launch that runs beside the full one (created at commit)
@@ -202,16 +216,18 @@ int cgrt_scene_create(cgrt_scene **out) {
 
 void cgrt_scene_destroy(cgrt_scene *s) {
     if (!s) return;
-    if (!s->allocs.empty() || s->scratch.p || s->order_buf.p || s->tri_ids.p || s->aux_stream || s->ev_order) {
+    if (!s->allocs.empty() || s->scratch.p || s->order_buf.p || s->relay_buf.p || s->tri_ids.p || s->aux_stream || s->ev_order || s->ev_relay) {
         DeviceGuard g(s->device);
         if (g.err == hipSuccess) {
             for (void *p : s->allocs) (void)hipFree(p);
             s->scratch.release();
             s->order_buf.release();
+            s->relay_buf.release();
             s->tri_ids.release();
             if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
             if (s->ev_join) (void)hipEventDestroy(s->ev_join);
             if (s->ev_order) (void)hipEventDestroy(s->ev_order);
+            if (s->ev_relay) (void)hipEventDestroy(s->ev_relay);
             if (s->aux_stream) (void)hipStreamDestroy(s->aux_stream);
         }
     }
@@ -1029,14 +1045,64 @@ static int order_tiles(const cgrt_scene *s, const FramePlan &p, GridParams &g, b
     return CGRT_OK;
 }
 
+// The sample relay of a tile-order launch of the PAIR variants (cgrt_relay.h; the plan has relay_k > 1): the handle's relay area
+// and g's relay fields.  Returns false -- the launch goes unrelayed, which is no error -- when the stream is being captured (the
+// area, its event and the handle's record of both belong to launches that run now), or the area cannot be had.  The arrival
+// words are 0 whenever no launch is in flight: zeroed here when the area is new or grown, when more of them are needed than
+// were zeroed, or after a launch that did not go through; reset by the kernel otherwise.
+static bool relay_prepare(const cgrt_scene *s, const FramePlan &p, GridParams &g, hipStream_t st) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &capturing) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    if (capturing != hipStreamCaptureStatusNone) return false;
+    if (s->relay_refused && p.relay_bytes >= s->relay_refused) return false;
+    if (p.relay_bytes > s->relay_buf.cap) {
+        // the launches that use the old area are through before it is freed
+        if (s->relay_recorded && hipEventSynchronize(s->ev_relay) != hipSuccess) (void)hipGetLastError();
+        s->relay_zeroed = 0;
+        if (s->relay_buf.need(p.relay_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            s->relay_refused = p.relay_bytes;
+            return false;
+        }
+    }
+    if (!s->ev_relay && hipEventCreateWithFlags(&s->ev_relay, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        s->ev_relay = nullptr;
+        return false;
+    }
+    if (s->relay_recorded && st != s->relay_stream && hipStreamWaitEvent(st, s->ev_relay, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    if (s->relay_dirty || p.relay_cap > s->relay_zeroed) {
+        if (hipMemsetAsync(s->relay_buf.p, 0, p.relay_cap * sizeof(uint32_t), st) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+    }
+    s->relay_zeroed = p.relay_cap;  // (the words beyond this launch's lie in its arrays)
+    s->relay_dirty = true;  // until the launch is through (cgrt_trace_grid)
+    g.relay = reinterpret_cast<unsigned char *>(s->relay_buf.p);
+    g.relay_k = p.relay_k;
+    g.relay_chunk_spp = p.relay_chunk_spp;
+    g.relay_cap = (int32_t)p.relay_cap;
+    g.relay_slots = p.relay_slots;
+    return true;
+}
+
 // development aid: CGRT_TIMELINE_FILE=path makes a launch synchronous and dumps, per workgroup, when and where it ran
 // (GridParams::timeline), behind a header {workgroups, threads per workgroup, chunks, xcd_tiles} (tools/timeline_probe.py)
-static int write_timeline(const char *file, const DevBuf &tl, size_t n_blocks, const FramePlan &p, int nt, hipStream_t st) {
+static int write_timeline(const char *file, const DevBuf &tl, size_t n_blocks, const FramePlan &p, int nt, int relay_k, hipStream_t st) {
     std::vector<unsigned long long> rec(n_blocks * 4);
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipMemcpy(rec.data(), tl.p, rec.size() * 8, hipMemcpyDeviceToHost));
     if (FILE *f = std::fopen(file, "wb")) {
-        const unsigned long long head[4] = {n_blocks, (unsigned long long)nt, (unsigned long long)p.chunks, (unsigned long long)p.xcd_tiles};
+        // (a relaying launch: relay_k << 32 | relay_cap in the xcd_tiles word, which is 0 for every tile-order launch)
+        const unsigned long long head[4] = {n_blocks, (unsigned long long)nt, (unsigned long long)p.chunks,
+                                            relay_k > 1 ? ((unsigned long long)relay_k << 32 | (unsigned long long)p.relay_cap) : (unsigned long long)p.xcd_tiles};
         std::fwrite(head, 8, 4, f);
         std::fwrite(rec.data(), 8, rec.size(), f);
         std::fclose(f);
@@ -1082,16 +1148,21 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     const EyeKnobs kn = eye_knobs();
     const EyeLaunch L = eye_launch(s, cam, grid, kn, false);
     const DeviceScene &d = s->dev;
+    // the sample relay: the one-launch tile-order form of the PAIR variants (the conditions of order_tiles below, and no second
+    // launch for the class-3 tiles); frame_plan adds the sample count, the tile count and the flags
+    const bool relay_form = L.form == EyeForm::Image && L.k.pair && L.k.nt == kThreads && s->order_ok &&
+                            !(grid->flags & (CGRT_GRID_NO_TILE_ORDER | CGRT_GRID_SPLIT_SAMPLES)) && !diffuse_wanted(s, cam, grid, L, kn);
     const FrameInputs in{*grid, *cam, L.form == EyeForm::Sched, L.k.spill, L.k.stats, L.k.glass, L.k.nt, d.has_mesh != 0,
                          d.has_bezier != 0, d.prim_finish != 0, d.light_ok != 0, d.prim_obj, kn, s->mem_total, s->n_cu,
-                         L.k.nt == 64 ? kBezWaves : (L.k.trees ? kSchedTreeWaves : 4)};
+                         L.k.nt == 64 ? kBezWaves : (L.k.trees ? kSchedTreeWaves : 4), relay_form};
     FramePlan p;
     if ((rc = fit_scratch(s, in, p))) return rc;
     GridParams g = frame_params(in, p);
     unsigned char *scratch = reinterpret_cast<unsigned char *>(s->scratch.p);
     if (p.heavy_blocks > 0 && (rc = probe_and_plan(s, L, kn, p, g, scratch, st, rgb, nhit, cnt))) return rc;
     p.scratch.place(g, scratch, nhit != nullptr);
-    const size_t n_blocks = (size_t)p.heavy_blocks + p.grid_dim;
+    size_t n_blocks = (size_t)p.heavy_blocks + p.grid_dim;
+    s->last_relay_k = 0;
     // image order, one workgroup per tile with all its samples, row-major: the tiles that see a mirror or glass sphere first
     s->order_tiles = 0;
     s->mask_wtiles = 0;
@@ -1105,11 +1176,19 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     struct DropKey {
         const cgrt_scene *s;
         bool through = false;
-        ~DropKey() { if (!through) s->order_valid = false; }
+        bool relayed = false;
+        ~DropKey() {
+            if (!through) s->order_valid = false;
+            if (relayed && through) s->relay_dirty = false;  // (else the arrival words are zeroed before they are used again)
+        }
     } drop_key{s};
     if (L.form == EyeForm::Image && p.chunks == 1 && !p.xcd_tiles && L.k.nt == kThreads && s->order_ok &&
         !(grid->flags & CGRT_GRID_NO_TILE_ORDER) && (rc = order_tiles(s, p, g, masks, kn.no_order_reuse, st)))
         return rc;
+    if (g.tile_order && p.relay_k > 1 && relay_prepare(s, p, g, st)) {
+        drop_key.relayed = true;
+        n_blocks = relay_grid(p.grid_dim, p.relay_k, p.relay_cap);
+    }
     DevBuf timeline;
     if (kn.timeline_file) {
         HIP_TRY(timeline.alloc(n_blocks * 32));
@@ -1149,8 +1228,16 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     if (p.heavy_blocks > 0) hipLaunchKernelGGL(deferred_sum_kernel, dim3((unsigned)p.kmax), dim3(64), 0, st, g, rgb, nhit);  // (4)
     if (g.light || s->diffuse_issued) HIP_TRY(hipStreamWaitEvent(st, s->ev_join, 0));  // the caller's stream continues when both launches are done
     const hipError_t launch_err = hipGetLastError();
-    if (g.timeline && launch_err == hipSuccess && (rc = write_timeline(kn.timeline_file, timeline, n_blocks, p, L.k.nt, st))) return rc;
+    if (g.timeline && launch_err == hipSuccess && (rc = write_timeline(kn.timeline_file, timeline, n_blocks, p, L.k.nt, g.relay_k, st))) return rc;
     if (launch_err != hipSuccess) return fail(CGRT_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(launch_err));
+    if (drop_key.relayed) {
+        HIP_TRY(hipEventRecord(s->ev_relay, st));
+        s->relay_stream = st;
+        s->relay_recorded = true;
+        s->last_relay_k = g.relay_k;
+        s->last_relay_cap = (size_t)g.relay_cap;
+        s->last_relay_slots = g.relay_slots;
+    }
     drop_key.through = true;
     return kn.plan_dump && g.plan && !g.tile_order ? dump_plan(p, g, st) : CGRT_OK;
 }
@@ -1214,6 +1301,27 @@ static int last_class3_tiles(const cgrt_scene *s, bool in_kernel, int64_t *n_til
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(plan, s->order_buf.p, sizeof(plan), hipMemcpyDeviceToHost));
     *n_tiles = (int64_t)plan[kOrderClasses] - (int64_t)plan[3];
+    return CGRT_OK;
+}
+int cgrt_scene_last_sample_relay(const cgrt_scene *s, int64_t *tiles, int32_t *chunks, int64_t *parked_values) {
+    if (!s || !tiles || !chunks || !parked_values) return fail(CGRT_ERR_INVALID, "null argument");
+    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+    ON_DEVICE(s->device);
+    *tiles = *parked_values = 0;
+    *chunks = 0;
+    if (s->last_relay_k <= 1 || s->order_tiles == 0) return CGRT_OK;
+    uint32_t plan[kOrderClasses + 1];
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(plan, s->order_buf.p, sizeof(plan), hipMemcpyDeviceToHost));
+    const size_t n_split = std::min((size_t)plan[2], s->last_relay_cap);
+    *tiles = (int64_t)n_split;
+    if (n_split == 0) return CGRT_OK;
+    *chunks = s->last_relay_k;
+    // rcount[tile][chunk - 1][thread] of the first n_split tiles is one run of words
+    std::vector<uint32_t> cnt(n_split * (size_t)(s->last_relay_k - 1) * kRelayThreads);
+    const RelayLayout rl = relay_layout(s->last_relay_cap, s->last_relay_k, s->last_relay_slots);
+    HIP_TRY(hipMemcpy(cnt.data(), reinterpret_cast<const unsigned char *>(s->relay_buf.p) + rl.rcount, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (uint32_t c : cnt) *parked_values += (int64_t)c;
     return CGRT_OK;
 }
 int cgrt_scene_last_diffuse_tiles(const cgrt_scene *s, int64_t *n_tiles) { return last_class3_tiles(s, false, n_tiles); }

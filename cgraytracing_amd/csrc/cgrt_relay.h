@@ -1,0 +1,97 @@
+// The sample relay of tile-order launches, in plain C++ (no HIP): how a tile's samples are cut into chunks, which workgroup of
+// the launch renders which (entry, chunk), and where a split tile's values lie in the handle's relay area.  The host plans with
+// these functions (cgrt_trace_grid, cgrt_hip.hip), trace_grid_kernel (cgrt_eye.hpp) maps its workgroups with the same ones, and
+// tests/native/relay_map.cpp checks them on the CPU.  DESIGN.md section 4.6.
+//
+// A lane of trace_grid_body owns a pixel and runs its samples one after the other, so a wave lasts as long as its costliest
+// pixel: on a refracting sphere ~11 rays a sample, ~700 dependent scene walks at 64 samples.  The relay cuts that chain: the
+// first n_split entries of tile_order_kernel's list (classes 0 and 1: some primary ray may meet a refracting sphere) are each
+// rendered by K workgroups, chunk c taking samples [c * chunk_spp, ...).  Chunk 0 sums its samples as ever; a chunk >= 1 parks
+// every Hitpoint value f * adj in its own stream, in emission order; the last of the K workgroups to finish adds the streams to
+// chunk 0's sums in chunk order -- the sequence of additions of the unsplit loop, so the same bits -- and stores the pixels.
+#ifndef CGRT_RELAY_H
+#define CGRT_RELAY_H
+#include <cstddef>
+#include <cstdint>
+
+#include "cgrt_rng.hpp"  // CGRT_HD
+
+static constexpr int kRelayMaxChunks = 4, kRelayMinChunkSpp = 16, kRelayThreads = 256;
+static constexpr int kRelayDefaultChunks = 2;  // most chunks unless the launch asks for kRelayMaxChunks (measured: DESIGN.md section 6)
+static constexpr int kRelayBatch = 8;  // stream slots the summing workgroup loads at a time (slots is a multiple of it)
+
+// K and the samples of a chunk: K = min(max_chunks, spp / 16), chunk_spp = ceil(spp / K), K again from chunk_spp (the last chunk
+// may be short, none is empty).  K == 1: no relay (spp < 32).
+struct RelayChunks {
+    int32_t k, chunk_spp;
+};
+CGRT_HD RelayChunks relay_chunks(int32_t spp, int32_t max_chunks = kRelayMaxChunks) {
+    int32_t k = spp / kRelayMinChunkSpp;
+    if (k > max_chunks) k = max_chunks;
+    if (k > kRelayMaxChunks) k = kRelayMaxChunks;
+    if (k < 2) return RelayChunks{1, spp};
+    const int32_t cs = (spp + k - 1) / k;
+    return RelayChunks{(spp + cs - 1) / cs, cs};
+}
+// samples [first, end) of chunk c
+CGRT_HD int32_t relay_first_sample(int32_t c, int32_t chunk_spp) { return c * chunk_spp; }
+CGRT_HD int32_t relay_end_sample(int32_t c, int32_t chunk_spp, int32_t spp) { return (c + 1) * chunk_spp < spp ? (c + 1) * chunk_spp : spp; }
+
+// Slots of a parked stream: a sample's ray tree of depth max_depth ends in at most 2^(max_depth - 1) Hitpoints (every level but
+// the last may double the rays; a ray at the last level ends), so chunk_spp * 2^(max_depth - 1) is never exceeded; rounded up to
+// the summing loop's batch.
+CGRT_HD int32_t relay_slots(int32_t chunk_spp, int32_t max_depth) {
+    const int32_t s = chunk_spp << (max_depth - 1);
+    return (s + kRelayBatch - 1) / kRelayBatch * kRelayBatch;
+}
+
+// Which (entry of the list, chunk) workgroup b renders: the first k * n_split workgroups are the split entries' chunks, chunk by
+// chunk within an entry; the others render one unsplit entry each.  The caller drops a workgroup whose entry is beyond the list.
+struct RelayBlock {
+    uint32_t entry;
+    int32_t chunk;
+    bool split;
+};
+CGRT_HD RelayBlock relay_block(uint32_t b, uint32_t k, uint32_t n_split) {
+    if (b < k * n_split) return RelayBlock{b / k, (int32_t)(b % k), true};
+    return RelayBlock{b - (k - 1) * n_split, 0, false};
+}
+// Workgroups of the launch: the host does not know how many entries are of class 0 or 1 (plan[2]), so it launches for cap_split.
+CGRT_HD size_t relay_grid(size_t n_tiles, int32_t k, size_t cap_split) { return n_tiles + (size_t)(k - 1) * cap_split; }
+
+// The relay area for cap_split tiles, 256 threads a tile (thread t = pixel t of the tile), array after array:
+//   arrive[cap]                     uint32   workgroups of the tile that are through (0 between launches), padded to 256 bytes
+//   racc  [cap][3][256]             double   chunk 0's sums r, g, b
+//   rhits [cap][k][256]             uint32   Hitpoints of each chunk
+//   rcount[cap][k-1][256]           uint32   values parked by chunk c >= 1
+//   rvals [cap][k-1][slots][3][256] double   chunk c's stream: value i of pixel t at [i][0..2][t]
+struct RelayLayout {
+    size_t racc, rhits, rcount, rvals, total;  // byte offsets; arrive is at 0
+};
+CGRT_HD size_t relay_tile_bytes(int32_t k, int32_t slots) {
+    const size_t t = kRelayThreads;
+    return sizeof(uint32_t) + 3 * t * sizeof(double) + (size_t)k * t * sizeof(uint32_t) + (size_t)(k - 1) * t * sizeof(uint32_t) +
+           (size_t)(k - 1) * (size_t)slots * 3 * t * sizeof(double);
+}
+CGRT_HD RelayLayout relay_layout(size_t cap, int32_t k, int32_t slots) {
+    const size_t t = kRelayThreads;
+    RelayLayout l;
+    l.racc = (cap * sizeof(uint32_t) + 255) & ~(size_t)255;
+    l.rhits = l.racc + cap * 3 * t * sizeof(double);
+    l.rcount = l.rhits + cap * (size_t)k * t * sizeof(uint32_t);
+    l.rvals = l.rcount + cap * (size_t)(k - 1) * t * sizeof(uint32_t);
+    l.total = l.rvals + cap * (size_t)(k - 1) * (size_t)slots * 3 * t * sizeof(double);
+    return l;
+}
+// Tiles the area may hold: 4 GiB, at most an eighth of the device's memory; bound > 0 (CGRT_RELAY_TILES): at most that many
+static constexpr size_t kRelayBudget = (size_t)4 << 30;
+CGRT_HD size_t relay_budget(size_t mem_total) { return mem_total / 8 < kRelayBudget ? mem_total / 8 : kRelayBudget; }
+CGRT_HD size_t relay_cap(size_t n_tiles, int32_t k, int32_t slots, size_t budget, long long bound = 0) {
+    size_t cap = budget / relay_tile_bytes(k, slots);
+    if (cap > n_tiles) cap = n_tiles;
+    if (bound > 0 && cap > (size_t)bound) cap = (size_t)bound;
+    while (cap > 0 && relay_layout(cap, k, slots).total > budget) cap--;  // (the arrival words' padding)
+    return cap;
+}
+
+#endif

@@ -19,6 +19,17 @@ def _d3(v):
     return (C.c_double * 3)(*[float(x) for x in v])
 
 
+
+def _relay_flag(sample_relay):
+    """CGRT_GRID_SAMPLE_RELAY / _NO_SAMPLE_RELAY / _SAMPLE_RELAY_4 for trace_grid's sample_relay=None|True|False|2|4"""
+    if sample_relay is None:
+        return 0
+    if sample_relay is True or sample_relay is False:
+        return 1024 if sample_relay else 2048
+    if int(sample_relay) not in (2, 4):
+        raise ValueError("sample_relay: None, True, False, 2 or 4")
+    return 1024 | (4096 if int(sample_relay) == 4 else 0)
+
 class Scene:
     """Owns a cgrt_scene handle.  `objs` order is the reference's `objs` order.  commit=False keeps the scene
     on the host only (mesh loading / tree build can then be inspected without a GPU)."""
@@ -157,14 +168,18 @@ class Scene:
     def trace_grid(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                    stripe=None, sample_offset=0, spp_total=None, out=None, nhit=None, counters=None, stream=None,
                    stats=False, accumulate=False, split_samples=False, reorder=True, force_reorder=False, tile_order=True,
-                   diffuse_tiles=False, sphere_pairs=True, sphere_masks=True):
+                   diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None):
         """Asynchronous launch on torch's current stream (or `stream`).  reorder=False: CGRT_GRID_NO_REORDER (tiles in image
         order instead of heaviest-first; same image).  tile_order=False: CGRT_GRID_NO_TILE_ORDER (an image-order launch starts
         its tiles row-major instead of mirror / glass tiles first; same image).  diffuse_tiles=True: CGRT_GRID_DIFFUSE_TILES (a
         sphere-only scene's tiles that see no mirror or glass are rendered by the terminal-diffuse launch beside the main one,
         not by the full kernel; same image, off by default).  sphere_pairs=False: CGRT_GRID_NO_SPHERE_PAIRS (a glass sphere
         scene's kernel tests one sphere at a time and renders every tile with the full body; same image).  sphere_masks=False:
-        CGRT_GRID_NO_SPHERE_MASKS (the terminal-diffuse body tests every sphere, not only its wave tile's candidates; same image).  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
+        CGRT_GRID_NO_SPHERE_MASKS (the terminal-diffuse body tests every sphere, not only its wave tile's candidates; same image).
+        sample_relay: None -- a glass sphere scene's launch of at least 4 tiles per compute unit and 32 samples renders the tiles
+        that may see a refracting sphere by 2 workgroups each, summed in sample order (same image; last_sample_relay);
+        True or 2: CGRT_GRID_SAMPLE_RELAY (whatever the tile count); 4: that with CGRT_GRID_SAMPLE_RELAY_4 (up to 4 workgroups a
+        tile); False: CGRT_GRID_NO_SAMPLE_RELAY.  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
         workgroups share a tile's samples; reproducible, fp64 summation order differs from the sample-by-sample sum).  Returns (rgb, nhit, counters) torch
         tensors on the scene's device: float32 [rows,width,3], int32 [rows,width] (bit pattern uint32),
         int64 [8] (counters are ADDED to)."""
@@ -184,7 +199,7 @@ class Scene:
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (2 if accumulate else 0) | (4 if split_samples else 0) |
                               (0 if reorder else 8) | (16 if force_reorder else 0) | (0 if tile_order else 64) |
-                              (128 if diffuse_tiles else 0) | (0 if sphere_pairs else 256) | (0 if sphere_masks else 512))
+                              (128 if diffuse_tiles else 0) | (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay))
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         check(self._L.cgrt_trace_grid(self._h, C.byref(cc), C.byref(g), out.data_ptr(),
                                       nhit.data_ptr() if nhit is not None else None,
@@ -397,7 +412,7 @@ class Scene:
 
     def trace_grid_host(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                         stripe=None, sample_offset=0, spp_total=None, stats=False, split_samples=False, reorder=True,
-                        force_reorder=False, tile_order=True, diffuse_tiles=False, sphere_pairs=True, sphere_masks=True):
+                        force_reorder=False, tile_order=True, diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None):
         """Synchronous form with numpy outputs (no torch needed): dict(rgb, nhit, counters)."""
         rows = height - row_offset if rows is None else rows
         rgb = np.zeros((rows, width, 3), np.float32)
@@ -406,7 +421,7 @@ class Scene:
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (4 if split_samples else 0) | (0 if reorder else 8) |
                               (16 if force_reorder else 0) | (0 if tile_order else 64) | (128 if diffuse_tiles else 0) |
-                              (0 if sphere_pairs else 256) | (0 if sphere_masks else 512))
+                              (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay))
         check(self._L.cgrt_trace_grid_host(self._h, C.byref(cc), C.byref(g), rgb.ctypes.data, nhit.ctypes.data,
                                            cnt.ctypes.data))
         return dict(rgb=rgb, nhit=nhit, counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]),
@@ -442,6 +457,14 @@ class Scene:
         f = C.c_int32()
         check(self._L.cgrt_scene_last_tile_order_reused(self._h, C.byref(f)))
         return bool(f.value)
+
+    def last_sample_relay(self):
+        """What this scene's last trace_grid / trace_grid_host relayed (cgrt_scene_last_sample_relay; synchronises the device):
+        dict(tiles: tiles rendered by several workgroups (0: none), chunks: workgroups of each, parked_values: Hitpoint values
+        that went through the relay area, 24 bytes each)."""
+        t, k, v = C.c_int64(), C.c_int32(), C.c_int64()
+        check(self._L.cgrt_scene_last_sample_relay(self._h, C.byref(t), C.byref(k), C.byref(v)))
+        return dict(tiles=int(t.value), chunks=int(k.value), parked_values=int(v.value))
 
     def last_diffuse_tiles(self):
         """Tiles the terminal-diffuse launch of this scene's last trace_grid / trace_grid_host rendered

@@ -120,6 +120,21 @@ enum {
                                  tile may meet, and the body tests only those (cgrt_scene_last_sphere_masks).  This flag
                                  restores the loop over every sphere.  Same image, hit counts and counters either way; it
                                  exists to test one against the other                                                  */
+    CGRT_GRID_SAMPLE_RELAY = 1024, /* the sample relay of the one-launch form above (",PAIR=1," in tile order; not with
+                                 CGRT_GRID_DIFFUSE_TILES or CGRT_GRID_SPLIT_SAMPLES), at 32 samples or more: the tiles some
+                                 primary ray of which may meet a refracting sphere are rendered by 2 workgroups (up to 4: CGRT_GRID_SAMPLE_RELAY_4), each
+                                 with a contiguous chunk of >= 16 samples.  The first sums its chunk; the others park their
+                                 Hitpoint values in emission order in an area on the scene handle (sized by the largest
+                                 launch: at most 4 GiB and an eighth of the device; without it the launch goes unrelayed), and
+                                 the last of a tile's workgroups to finish adds them to the first chunk's sums in chunk order
+                                 inside the launch -- the unsplit loop's sequence of additions, so image, hit counts, rays
+                                 and Hitpoints are bit-identical; CGRT_CNT_WAVE_ITERS differs (see there).  By default the
+                                 relay is engaged when the launch has at least 4 tiles per compute unit; this flag engages
+                                 it whatever the tile count (cgrt_scene_last_sample_relay tells what a launch did) ... */
+    CGRT_GRID_NO_SAMPLE_RELAY = 2048, /* ... and this one switches it off                                              */
+    CGRT_GRID_SAMPLE_RELAY_4 = 4096, /* the relay cuts a tile's samples into up to 4 chunks instead of 2, the default: measured
+                                 on the 1920x1080 frame at 64 samples, two workgroups a tile gain more than four, which park
+                                 half as many values again                                        */
     CGRT_GRID_HITPOINTS = 32, /* cgrt_trace_grid_variant only: name the launch of the Hitpoint capture
                                  (cgrt_trace_grid_hitpoints, the eye pass of cgrt_ppm_render) instead of cgrt_trace_grid's;
                                  ignored by the other calls                                                            */
@@ -136,7 +151,10 @@ enum {
 enum {
     CGRT_CNT_RAYS = 0,      /* trace() invocations past the depth test (main.cpp:46)                     */
     CGRT_CNT_HITPOINTS = 1, /* Hitpoints the reference would have inserted (main.cpp:98)                 */
-    CGRT_CNT_WAVE_ITERS = 2,/* wavefront loop iterations (x64 = lane slots; lane utilisation = rays/slots)*/
+    CGRT_CNT_WAVE_ITERS = 2,/* wavefront loop iterations (x64 = lane slots; lane utilisation = rays/slots).
+                               A measurement of the launch as it ran, not of the image: a launch that relays samples
+                               (CGRT_GRID_SAMPLE_RELAY) runs a relayed tile's samples in several shorter waves and
+                               counts their iterations, so it differs from the unrelayed launch's                */
     CGRT_CNT_NODE_TESTS = 3,/* tree nodes visited (lane granularity)                                     */
     CGRT_CNT_TRI_TESTS = 4, /* triangle tests                                                            */
     CGRT_NCOUNTERS = 8
@@ -608,6 +626,10 @@ int cgrt_scene_last_diffuse_tiles(const cgrt_scene *s, int64_t *n_tiles);
 /* The same count for the one-launch form (see CGRT_GRID_NO_SPHERE_PAIRS): the tiles of the LAST cgrt_trace_grid on the handle
  * whose workgroups ran the terminal-diffuse body inside the main launch (synchronises the device; 0: none did). */
 int cgrt_scene_last_inkernel_diffuse_tiles(const cgrt_scene *s, int64_t *n_tiles);
+/* The sample relay of the LAST cgrt_trace_grid on the handle (see CGRT_GRID_SAMPLE_RELAY; synchronises the device): *tiles =
+ * the tiles it rendered by several workgroups (0: it did not relay), *chunks = the workgroups of each, *parked_values = the
+ * Hitpoint values (3 doubles each) that went through the relay area. */
+int cgrt_scene_last_sample_relay(const cgrt_scene *s, int64_t *tiles, int32_t *chunks, int64_t *parked_values);
 
 /* Host evaluation of the lens stream (cgrt_rng.hpp, the same inline code the kernel runs): writes
  * uniform_sampling_circle(radius) (sampling.h:35-43) for n (pixel, sample) pairs as 3 doubles each.  Lets CPU-only

@@ -41,6 +41,13 @@ def timeline(sc, cam, **kw):
     tx = (tl[:, 3] & np.uint64(0xffff)).astype(int) // 2
     ty = ((tl[:, 3] >> np.uint64(16)) & np.uint64(0xffff)).astype(int) // 2
     rays = (tl[:, 3] >> np.uint64(32)).astype(np.int64)
+    # a launch that relays samples (cgrt_relay.h) left relay_k << 32 | relay_cap in the header: its first relay_k * n_split
+    # workgroups are (entry i // relay_k, chunk i % relay_k), n_split = min(plan[2], relay_cap); blk becomes the order's entry
+    relay_k, relay_cap = int(raw[3]) >> 32, int(raw[3]) & 0xffffffff
+    order = sc.last_tile_order()
+    if relay_k > 1 and order is not None:
+        n_split = min(int(order["plan"][2]), relay_cap)
+        blk = np.where(blk < relay_k * n_split, blk // relay_k, blk - (relay_k - 1) * n_split)
     return a, b, tx, ty, rays, blk, r
 
 
@@ -89,7 +96,7 @@ def main():
                      "longest_rays": int(rays[i]), "five_longest_us": [round(float(x), 1) for x in top[:5]],
                      "p99_us": round(float(np.percentile(dur, 99)), 1)}}
     if order is not None:
-        is3 = blk >= int(order["plan"][3])  # workgroup i rendered the order's entry i; class 3 begins at plan[3]
+        is3 = blk >= int(order["plan"][3])  # blk: the order's entry a workgroup rendered; class 3 begins at plan[3]
         doc["frame"]["class_bounds"] = [int(x) for x in order["plan"]]
         doc["frame"]["class3_last_end_us"] = round(float(b[is3].max()), 1) if is3.any() else None
         doc["frame"]["class012_last_end_us"] = round(float(b[~is3].max()), 1) if (~is3).any() else None

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Development aid (not a test): when and where every workgroup of one trace_grid launch ran.
 
-  python tools/timeline_probe.py c3|c4|c2|c5band [--spp N] [--split] [--natural] [--out gpurun_out/tl.json]
+  python tools/timeline_probe.py c3|c4|c2|c5band [--spp N] [--split] [--natural] [--relay on|off] [--out tl.json]
 
 Sets CGRT_TIMELINE_FILE so that libcgrt.so records, per workgroup, {start, end} on the 100 MHz wall clock, the hardware
 id (XCC, SE, CU) and the rays it traced, then prints: launch span, concurrency over time (resident workgroups in 20 time
@@ -24,6 +24,7 @@ def main():
     split = "--split" in sys.argv
     natural = "--natural" in sys.argv  # CGRT_GRID_NO_REORDER
     out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
+    relay = {"on": True, "off": False}[sys.argv[sys.argv.index("--relay") + 1]] if "--relay" in sys.argv else None  # sample_relay
     import cgraytracing_amd as cg
     import scenes
     cam = scenes.cam_dof()
@@ -42,13 +43,17 @@ def main():
     sc.trace_grid_host(W, H, 1, cam, 5, 12345, rows=rows, row_offset=row_offset)  # warm-up
     tf = tempfile.mktemp(suffix=".tl")
     os.environ["CGRT_TIMELINE_FILE"] = tf
-    r = sc.trace_grid_host(W, H, spp, cam, 5, 12345, rows=rows, row_offset=row_offset, split_samples=split, reorder=not natural)
+    r = sc.trace_grid_host(W, H, spp, cam, 5, 12345, rows=rows, row_offset=row_offset, split_samples=split, reorder=not natural,
+                           **({} if relay is None else {"sample_relay": relay}))
     del os.environ["CGRT_TIMELINE_FILE"]
     tile_order = sc.last_tile_order() if hasattr(sc, "last_tile_order") else None  # image-order launches of sphere scenes
+    relayed = sc.last_sample_relay() if hasattr(sc, "last_sample_relay") else None
     sc.close()
     raw = np.fromfile(tf, dtype=np.uint64)
     os.unlink(tf)
     nblk, nthr, chunks, xcd_tiles = [int(x) for x in raw[:4]]
+    # a launch that relays samples (cgrt_relay.h) writes relay_k << 32 | relay_cap there (its tiles are row-major: xcd_tiles 0)
+    relay_k, relay_cap, xcd_tiles = (xcd_tiles >> 32, xcd_tiles & 0xffffffff, 0) if xcd_tiles >> 32 else (1, 0, xcd_tiles)
     tl = raw[4:].reshape(nblk, 4)
     ran = tl[:, 1] > 0
     t0 = tl[ran, 0].astype(np.int64)
@@ -92,10 +97,25 @@ def main():
                                       "started_after_half": int((late & (a > 0.5 * span)).sum())}
     half = 0.5 * max(conc)
     doc["fraction_of_span_below_half_peak_concurrency"] = round(sum(1 for c in conc if c < half) / bins, 2)
-    if tile_order is not None and nblk == len(tile_order["list"]):
-        # workgroup i rendered tile list[i]; plan[c] = workgroups of classes < c (classes 0-2: tiles that may see a glass / mirror sphere)
+    if tile_order is not None and nblk == len(tile_order["list"]) + (relay_k - 1) * relay_cap:
+        # workgroup i rendered tile list[i]; plan[c] = workgroups of classes < c (classes 0-2: tiles that may see a glass / mirror sphere).
+        # With the relay (relay_block, cgrt_relay.h): the first relay_k * n_split workgroups are (entry i // relay_k, chunk i % relay_k),
+        # workgroup i behind them is entry i - (relay_k - 1) * n_split; workgroups beyond the list left at once and have no record.
         plan = [int(x) for x in tile_order["plan"]]
         blk = np.nonzero(ran)[0]
+        n_split = min(plan[2], relay_cap) if relay_k > 1 else 0
+        split_blk = blk < relay_k * n_split
+        chunk = np.where(split_blk, blk % relay_k, 0)
+        blk = np.where(split_blk, blk // relay_k, blk - (relay_k - 1) * n_split)  # the entry
+        if relay_k > 1:
+            ent_rays = np.bincount(blk, weights=rays, minlength=plan[4])
+            heavy = int(np.argmax(ent_rays))  # the entry with the most rays: the glass sphere's centre tile
+            doc["sample_relay"] = {"chunks": relay_k, "capacity_tiles": relay_cap, "split_tiles": n_split, "last": relayed,
+                                   "workgroups_launched": nblk, "workgroups_beyond_the_list": int(nblk - ran.sum()),
+                                   "split_workgroup_us": {"mean": round(float(dur[split_blk].mean()), 1), "max": round(float(dur[split_blk].max()), 1)} if split_blk.any() else None,
+                                   "heaviest_entry": {"entry": heavy, "tile": int(tile_order["list"][heavy]), "rays": int(ent_rays[heavy]),
+                                                      "workgroups": [{"chunk": int(chunk[i]), "start_us": round(float(a[i]), 1), "end_us": round(float(b[i]), 1),
+                                                                      "rays": int(rays[i])} for i in np.nonzero(blk == heavy)[0]]}}
         c0, c3 = blk < plan[1], blk >= plan[3]
         doc["tile_order"] = {"class_bounds": plan,
                              "class0_last_start_us": round(float(a[c0].max()), 1) if c0.any() else None,
