@@ -732,9 +732,10 @@ __global__ __launch_bounds__(NT, DIFF ? (DOF ? kDiffDofWaves : kDiffWaves) : BEZ
     // A pair of launches shares the list (kOrderFull: the entries of classes 0-2, kOrderDiffuse: those of class 3, the DIFF
     // variant); the host does not know where class 3 begins, so both are launched over all tiles and a workgroup beyond its
     // launch's part leaves here, before anything else.
-    // The sample relay (PAIR variants, g.relay_k > 1; cgrt_relay.h): the list's first entries -- classes 0 and 1, as many as the
-    // relay area holds -- are rendered by relay_k workgroups each; the launch spans relay_cap such entries, the host not knowing
-    // plan[2], and a workgroup whose entry lies beyond the list leaves here.  Index arithmetic on uniform values only.
+    // The sample relay (PAIR variants, g.relay_k > 1; cgrt_relay.h): the list's first entries -- classes 0 and 1, with
+    // g.relay_extent class 2 as well, as many as the relay area holds -- are rendered by relay_k workgroups each, in the order
+    // g.relay_order names; the launch spans relay_cap such entries, the host knowing neither plan[2] nor plan[3], and a
+    // workgroup whose entry lies beyond the list leaves here.  Index arithmetic on uniform values only.
     int tile_block = (int)blockIdx.x, tile_grid = (int)gridDim.x;
     unsigned entry = blockIdx.x;
     RelayWg rw;
@@ -744,10 +745,11 @@ __global__ __launch_bounds__(NT, DIFF ? (DOF ? kDiffDofWaves : kDiffWaves) : BEZ
             if (g.tile_order == kOrderDiffuse) entry += first_diffuse;
             if (g.tile_order == kOrderDiffuse ? entry >= load_uniform(g.plan + kOrderClasses) : entry >= first_diffuse) return;
         } else if (PAIR && g.relay_k > 1) {
-            const unsigned special = load_uniform(g.plan + 2), n_split = special < (unsigned)g.relay_cap ? special : (unsigned)g.relay_cap;
-            const RelayBlock rb = relay_block(blockIdx.x, (unsigned)g.relay_k, n_split);
+            const unsigned n_tiles = load_uniform(g.plan + kOrderClasses);
+            const RelayBlock rb = relay_block_ordered(blockIdx.x, (unsigned)g.relay_k, load_uniform(g.plan + 2), load_uniform(g.plan + 3), n_tiles,
+                                                      (unsigned)g.relay_cap, g.relay_extent, g.relay_order);
             entry = rb.entry;
-            if (entry >= load_uniform(g.plan + kOrderClasses)) return;
+            if (entry >= n_tiles) return;
             if (rb.split) {
                 rw.slot = (int)entry;
                 rw.chunk = rb.chunk;

@@ -9,6 +9,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
+#include <string>
 
 #include "../../include/cgrt.h"
 #include "cgrt_relay.h"
@@ -84,13 +85,15 @@ struct GridParams {
     uint64_t seed;
     double cam[3], half_width, focus_plane, lens_radius;
     // The sample relay (cgrt_relay.h; tile-order launches of the PAIR variants only): relay_k > 1 -- the first
-    // min(plan[2], relay_cap) entries of the list are rendered by relay_k workgroups each, chunk c taking relay_chunk_spp samples
-    // from c * relay_chunk_spp on; `relay` is the handle's relay area, laid out for (relay_cap, relay_k, relay_slots).
-    // relay_k <= 1: every entry by one workgroup.
+    // min(plan[2], relay_cap) entries of the list (relay_extent == kRelayMirror: min(plan[3], relay_cap), the class-2 tiles too)
+    // are rendered by relay_k workgroups each, chunk c taking relay_chunk_spp samples from c * relay_chunk_spp on, the workgroups
+    // in the order relay_order names (relay_block_ordered); `relay` is the handle's relay area, laid out for (relay_cap,
+    // relay_k, relay_slots).  relay_k <= 1: every entry by one workgroup.
     unsigned char *relay;
     int32_t relay_k, relay_chunk_spp, relay_cap, relay_slots;
+    int32_t relay_extent, relay_order;
 };
-static_assert(sizeof(GridParams) == 312, "GridParams is a kernel argument: its layout is fixed");
+static_assert(sizeof(GridParams) == 320, "GridParams is a kernel argument: its layout is fixed");
 
 static constexpr int kTileW = 32, kTileH = 8, kThreads = 256;
 // Tile order of image-order launches (tile_order_kernel, cgrt_eye.hpp): the special spheres -- those that reflect or refract --
@@ -184,11 +187,21 @@ struct EyeKnobs {
     bool no_order_reuse = false;  // NO_ORDER_REUSE: tile_order_kernel in front of every tile-order launch (order_tiles)
     int relay_chunks = kRelayDefaultChunks;  // RELAY_CHUNKS: most workgroups a relayed tile's samples are cut into (2..4)
     long long relay_tiles = 0;           // RELAY_TILES: > 0: at most this many tiles are relayed (the relay area's capacity)
+    int relay_mirror = -1;  // RELAY_MIRROR: 0 / 1: the relay's extent where the launch's flags name none (-1: unset)
+    int relay_order = -1;   // RELAY_ORDER: chunks_first / mirror_first / interleaved (or 0 / 1 / 2), likewise
     const char *timeline_file = nullptr;  // TIMELINE_FILE (nullptr: off)
 };
 inline const char *env_str(const char *name) { const char *e = std::getenv(name); return e ? e : ""; }
 inline bool env_on(const char *name) { const char *e = env_str(name); return *e && *e != '0'; }
 inline int env_positive(const char *name, int def) { const int v = std::atoi(env_str(name)); return v > 0 ? v : def; }
+// CGRT_RELAY_ORDER's value: a name or its number; -1: none of them
+inline int relay_order_named(const char *e) {
+    const std::string v(e);
+    if (v == "chunks_first" || v == "0") return kRelayChunksFirst;
+    if (v == "mirror_first" || v == "1") return kRelayMirrorFirst;
+    if (v == "interleaved" || v == "2") return kRelayInterleaved;
+    return -1;
+}
 // Read once per process, at the first launch, except CGRT_TIMELINE_FILE, which every launch reads.
 inline EyeKnobs eye_knobs() {
     static const EyeKnobs once = [] {
@@ -208,6 +221,8 @@ inline EyeKnobs eye_knobs() {
         k.no_order_reuse = env_on("CGRT_NO_ORDER_REUSE");
         k.relay_chunks = std::min(std::max(env_positive("CGRT_RELAY_CHUNKS", kRelayDefaultChunks), 2), kRelayMaxChunks);
         k.relay_tiles = std::atoll(env_str("CGRT_RELAY_TILES"));
+        if (*env_str("CGRT_RELAY_MIRROR")) k.relay_mirror = env_on("CGRT_RELAY_MIRROR") ? 1 : 0;
+        k.relay_order = relay_order_named(env_str("CGRT_RELAY_ORDER"));
         return k;
     }();
     EyeKnobs k = once;
@@ -280,6 +295,7 @@ struct FramePlan {
     // relay_grid(grid_dim, relay_k, relay_cap))
     int relay_k = 1, relay_chunk_spp = 0, relay_slots = 0;
     size_t relay_tile_bytes = 0, relay_cap = 0, relay_bytes = 0;
+    int relay_extent = kRelayGlass, relay_order = kRelayChunksFirst;  // relay_block_ordered's; both 0 unless relay_k > 1
 };
 
 // Whether a launch of n_tiles tiles relays samples by default: at 32 samples or more (two chunks of 16), and with every workgroup
@@ -288,6 +304,24 @@ struct FramePlan {
 inline bool relay_engaged(int32_t flags, int32_t spp, size_t n_tiles, int n_cu) {
     if ((flags & CGRT_GRID_NO_SAMPLE_RELAY) || spp < 2 * kRelayMinChunkSpp) return false;
     return (flags & CGRT_GRID_SAMPLE_RELAY) || n_tiles >= (size_t)4 * (size_t)n_cu;
+}
+
+// The form of an engaged relay (relay_block_ordered's extent and order).  What the launch's flags name holds; where they name
+// none, the knob CGRT_RELAY_MIRROR / CGRT_RELAY_ORDER; where neither does, a launch that asked for the relay
+// (CGRT_GRID_SAMPLE_RELAY) relays classes 0 and 1, chunk workgroups first -- what that flag has always meant -- and only the
+// launch that relays by default takes the measured form (kRelayDefaultExtent / kRelayDefaultOrder).
+static constexpr int kRelayDefaultExtent = kRelayMirror, kRelayDefaultOrder = kRelayInterleaved;
+inline int relay_extent_of(int32_t flags, const EyeKnobs &kn) {
+    if (flags & CGRT_GRID_RELAY_MIRROR) return kRelayMirror;
+    if (flags & CGRT_GRID_RELAY_NO_MIRROR) return kRelayGlass;
+    if (kn.relay_mirror >= 0) return kn.relay_mirror ? kRelayMirror : kRelayGlass;
+    return (flags & CGRT_GRID_SAMPLE_RELAY) ? kRelayGlass : kRelayDefaultExtent;
+}
+inline int relay_order_of(int32_t flags, const EyeKnobs &kn) {
+    const int32_t f = flags & CGRT_GRID_RELAY_ORDER_MASK;
+    if (f) return f == CGRT_GRID_RELAY_MIRROR_FIRST ? kRelayMirrorFirst : f == CGRT_GRID_RELAY_INTERLEAVED ? kRelayInterleaved : kRelayChunksFirst;
+    if (kn.relay_order >= 0) return kn.relay_order;
+    return (flags & CGRT_GRID_SAMPLE_RELAY) ? kRelayChunksFirst : kRelayDefaultOrder;
 }
 
 static constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -327,6 +361,8 @@ inline FramePlan frame_plan(const FrameInputs &in, size_t kmax) {
                 p.relay_k = rc.k;
                 p.relay_chunk_spp = rc.chunk_spp;
                 p.relay_bytes = relay_layout(p.relay_cap, rc.k, p.relay_slots).total;
+                p.relay_extent = relay_extent_of(gr.flags, kn);
+                p.relay_order = relay_order_of(gr.flags, kn);
             }
         }
     }

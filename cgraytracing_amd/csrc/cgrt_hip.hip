@@ -126,6 +126,7 @@ struct cgrt_scene {
     mutable int last_relay_k = 0;
     mutable size_t last_relay_cap = 0;
     mutable int last_relay_slots = 0;
+    mutable int last_relay_extent = 0, last_relay_order = 0;
     size_t mem_total = 0;                // memory of the scene's device (read at commit; bounds the deferred-value budget)
     int n_cu = 256;                      // compute units of the scene's device (read at commit; wave slots of the scheduler)
     // second stream + fork/join events for the light-tile launch that runs beside the full one (created at commit)
@@ -1090,6 +1091,8 @@ static bool relay_prepare(const cgrt_scene *s, const FramePlan &p, GridParams &g
     g.relay_chunk_spp = p.relay_chunk_spp;
     g.relay_cap = (int32_t)p.relay_cap;
     g.relay_slots = p.relay_slots;
+    g.relay_extent = p.relay_extent;
+    g.relay_order = p.relay_order;
     return true;
 }
 
@@ -1100,9 +1103,11 @@ static int write_timeline(const char *file, const DevBuf &tl, size_t n_blocks, c
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipMemcpy(rec.data(), tl.p, rec.size() * 8, hipMemcpyDeviceToHost));
     if (FILE *f = std::fopen(file, "wb")) {
-        // (a relaying launch: relay_k << 32 | relay_cap in the xcd_tiles word, which is 0 for every tile-order launch)
+        // (a relaying launch: relay_k << 32 | extent << 40 | order << 41 | relay_cap in the xcd_tiles word, which is 0 for every
+        // tile-order launch)
+        const unsigned long long form = (unsigned long long)relay_k | (unsigned long long)p.relay_extent << 8 | (unsigned long long)p.relay_order << 9;
         const unsigned long long head[4] = {n_blocks, (unsigned long long)nt, (unsigned long long)p.chunks,
-                                            relay_k > 1 ? ((unsigned long long)relay_k << 32 | (unsigned long long)p.relay_cap) : (unsigned long long)p.xcd_tiles};
+                                            relay_k > 1 ? (form << 32 | (unsigned long long)p.relay_cap) : (unsigned long long)p.xcd_tiles};
         std::fwrite(head, 8, 4, f);
         std::fwrite(rec.data(), 8, rec.size(), f);
         std::fclose(f);
@@ -1237,6 +1242,8 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
         s->last_relay_k = g.relay_k;
         s->last_relay_cap = (size_t)g.relay_cap;
         s->last_relay_slots = g.relay_slots;
+        s->last_relay_extent = g.relay_extent;
+        s->last_relay_order = g.relay_order;
     }
     drop_key.through = true;
     return kn.plan_dump && g.plan && !g.tile_order ? dump_plan(p, g, st) : CGRT_OK;
@@ -1313,7 +1320,7 @@ int cgrt_scene_last_sample_relay(const cgrt_scene *s, int64_t *tiles, int32_t *c
     uint32_t plan[kOrderClasses + 1];
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(plan, s->order_buf.p, sizeof(plan), hipMemcpyDeviceToHost));
-    const size_t n_split = std::min((size_t)plan[2], s->last_relay_cap);
+    const size_t n_split = relay_split_entries(plan[2], plan[3], (uint32_t)s->last_relay_cap, s->last_relay_extent);  // the entries in fact split
     *tiles = (int64_t)n_split;
     if (n_split == 0) return CGRT_OK;
     *chunks = s->last_relay_k;
@@ -1322,6 +1329,14 @@ int cgrt_scene_last_sample_relay(const cgrt_scene *s, int64_t *tiles, int32_t *c
     const RelayLayout rl = relay_layout(s->last_relay_cap, s->last_relay_k, s->last_relay_slots);
     HIP_TRY(hipMemcpy(cnt.data(), reinterpret_cast<const unsigned char *>(s->relay_buf.p) + rl.rcount, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (uint32_t c : cnt) *parked_values += (int64_t)c;
+    return CGRT_OK;
+}
+int cgrt_scene_last_relay_form(const cgrt_scene *s, int32_t *mirror, int32_t *order) {
+    if (!s || !mirror || !order) return fail(CGRT_ERR_INVALID, "null argument");
+    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+    const bool relayed = s->last_relay_k > 1 && s->order_tiles != 0;
+    *mirror = relayed ? (s->last_relay_extent == kRelayMirror ? 1 : 0) : -1;
+    *order = relayed ? s->last_relay_order : -1;
     return CGRT_OK;
 }
 int cgrt_scene_last_diffuse_tiles(const cgrt_scene *s, int64_t *n_tiles) { return last_class3_tiles(s, false, n_tiles); }

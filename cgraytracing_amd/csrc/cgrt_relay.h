@@ -1,14 +1,15 @@
 // The sample relay of tile-order launches, in plain C++ (no HIP): how a tile's samples are cut into chunks, which workgroup of
 // the launch renders which (entry, chunk), and where a split tile's values lie in the handle's relay area.  The host plans with
 // these functions (cgrt_trace_grid, cgrt_hip.hip), trace_grid_kernel (cgrt_eye.hpp) maps its workgroups with the same ones, and
-// tests/native/relay_map.cpp checks them on the CPU.  DESIGN.md section 4.6.
+// tests/native/relay_map.cpp and relay_order.cpp check them on the CPU.  DESIGN.md section 4.6.
 //
 // A lane of trace_grid_body owns a pixel and runs its samples one after the other, so a wave lasts as long as its costliest
 // pixel: on a refracting sphere ~11 rays a sample, ~700 dependent scene walks at 64 samples.  The relay cuts that chain: the
-// first n_split entries of tile_order_kernel's list (classes 0 and 1: some primary ray may meet a refracting sphere) are each
-// rendered by K workgroups, chunk c taking samples [c * chunk_spp, ...).  Chunk 0 sums its samples as ever; a chunk >= 1 parks
-// every Hitpoint value f * adj in its own stream, in emission order; the last of the K workgroups to finish adds the streams to
-// chunk 0's sums in chunk order -- the sequence of additions of the unsplit loop, so the same bits -- and stores the pixels.
+// first n_split entries of tile_order_kernel's list (classes 0 and 1: some primary ray may meet a refracting sphere; with the
+// mirror extent class 2 as well: relay_block_ordered) are each rendered by K workgroups, chunk c taking samples
+// [c * chunk_spp, ...).  Chunk 0 sums its samples as ever; a chunk >= 1 parks every Hitpoint value f * adj in its own stream,
+// in emission order; the last of the K workgroups to finish adds the streams to chunk 0's sums in chunk order -- the sequence
+// of additions of the unsplit loop, so the same bits -- and stores the pixels.
 #ifndef CGRT_RELAY_H
 #define CGRT_RELAY_H
 #include <cstddef>
@@ -58,6 +59,53 @@ CGRT_HD RelayBlock relay_block(uint32_t b, uint32_t k, uint32_t n_split) {
 }
 // Workgroups of the launch: the host does not know how many entries are of class 0 or 1 (plan[2]), so it launches for cap_split.
 CGRT_HD size_t relay_grid(size_t n_tiles, int32_t k, size_t cap_split) { return n_tiles + (size_t)(k - 1) * cap_split; }
+
+// The launch map with an extent and an order.  The extent names the split entries -- a prefix of the
+// list either way, so slot = entry, the relay area and the arrival words are the same for both:
+//   kRelayGlass    entries [0, min(n01, cap)): the tiles that may see a refracting sphere (classes 0 and 1; relay_block's)
+//   kRelayMirror   entries [0, min(n012, cap)): the class-2 tiles -- a reflecting sphere only -- as well; where cap ends inside
+//                  a class the entries beyond it are unsplit
+// The order says where the workgroups of the class-2 entries [n01, n012) stand among those of the entries [0, n01); each of the
+// two sequences runs through its entries ascending, a split entry's k workgroups chunk by chunk, an unsplit entry's one:
+//   kRelayChunksFirst   classes 0-1, then class 2 (with kRelayGlass: relay_block)
+//   kRelayMirrorFirst   class 2, then classes 0-1
+//   kRelayInterleaved   merged in proportion: with a workgroups of classes 0-1 and m of class 2, position p of the merged run
+//                       takes the next class-2 workgroup exactly when floor((p + 1) m / (a + m)) > floor(p m / (a + m)), so every
+//                       prefix holds both kinds within one workgroup of their share
+// Class 3 follows in entry order.  n01 = plan[2] <= n012 = plan[3] <= n_tiles; a workgroup beyond the list gets entry >= n_tiles
+// and the caller drops it.
+static constexpr int kRelayGlass = 0, kRelayMirror = 1;
+static constexpr int kRelayChunksFirst = 0, kRelayMirrorFirst = 1, kRelayInterleaved = 2;
+CGRT_HD uint32_t relay_split_entries(uint32_t n01, uint32_t n012, uint32_t cap, int extent) {
+    const uint32_t n = extent == kRelayMirror ? n012 : n01;
+    return n < cap ? n : cap;
+}
+CGRT_HD RelayBlock relay_block_ordered(uint32_t b, uint32_t k, uint32_t n01, uint32_t n012, uint32_t n_tiles, uint32_t cap, int extent, int order) {
+    const uint32_t n_split = relay_split_entries(n01, n012, cap, extent);
+    const uint32_t s_a = n_split < n01 ? n_split : n01, s_m = n_split - s_a;  // split entries of classes 0-1, of class 2
+    // (32-bit throughout: t <= relay_grid, which the launch's grid dimension holds; only the interleaved product is wider)
+    const uint32_t a = n01 + (k - 1) * s_a, m = (n012 - n01) + (k - 1) * s_m, t = a + m;  // workgroups of classes 0-1, of class 2
+    if (b >= t) {  // class 3 (t = n012 + (k - 1) n_split), or beyond the list
+        const uint32_t e = n012 + (b - t);
+        return RelayBlock{e < n_tiles ? e : n_tiles, 0, false};
+    }
+    bool mirror;  // the workgroup is the i-th of class 2, else the i-th of classes 0-1
+    uint32_t i;
+    if (order == kRelayInterleaved) {
+        const uint64_t pm = (uint64_t)b * m, q = pm / t;  // q = class-2 workgroups in front of position b
+        mirror = pm - q * t + m >= t;
+        i = mirror ? (uint32_t)q : b - (uint32_t)q;
+    } else if (order == kRelayMirrorFirst) {
+        mirror = b < m;
+        i = mirror ? b : b - m;
+    } else {
+        mirror = b >= a;
+        i = mirror ? b - a : b;
+    }
+    const uint32_t first = mirror ? n01 : 0u, s = mirror ? s_m : s_a;
+    if (i < k * s) return RelayBlock{first + i / k, (int32_t)(i % k), true};
+    return RelayBlock{first + (i - (k - 1) * s), 0, false};
+}
 
 // The relay area for cap_split tiles, 256 threads a tile (thread t = pixel t of the tile), array after array:
 //   arrive[cap]                     uint32   workgroups of the tile that are through (0 between launches), padded to 256 bytes

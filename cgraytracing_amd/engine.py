@@ -20,15 +20,25 @@ def _d3(v):
 
 
 
-def _relay_flag(sample_relay):
-    """CGRT_GRID_SAMPLE_RELAY / _NO_SAMPLE_RELAY / _SAMPLE_RELAY_4 for trace_grid's sample_relay=None|True|False|2|4"""
+_RELAY_ORDERS = ("chunks_first", "mirror_first", "interleaved")  # CGRT_GRID_RELAY_CHUNKS_FIRST / _MIRROR_FIRST / _INTERLEAVED
+
+
+def _relay_flag(sample_relay, relay_mirror=None, relay_order=None):
+    """CGRT_GRID_SAMPLE_RELAY / _NO_SAMPLE_RELAY / _SAMPLE_RELAY_4 for trace_grid's sample_relay=None|True|False|2|4, with
+    CGRT_GRID_RELAY_MIRROR / _NO_MIRROR for relay_mirror=None|True|False and the order field for relay_order=None|a name"""
+    form = 0 if relay_mirror is None else (8192 if relay_mirror else 16384)
+    if relay_order is not None:
+        if relay_order not in _RELAY_ORDERS:
+            raise ValueError("relay_order: None, " + ", ".join(repr(o) for o in _RELAY_ORDERS))
+        form |= 32768 * (1 + _RELAY_ORDERS.index(relay_order))
     if sample_relay is None:
-        return 0
+        return form
     if sample_relay is True or sample_relay is False:
-        return 1024 if sample_relay else 2048
+        return form | (1024 if sample_relay else 2048)
     if int(sample_relay) not in (2, 4):
         raise ValueError("sample_relay: None, True, False, 2 or 4")
-    return 1024 | (4096 if int(sample_relay) == 4 else 0)
+    return form | 1024 | (4096 if int(sample_relay) == 4 else 0)
+
 
 class Scene:
     """Owns a cgrt_scene handle.  `objs` order is the reference's `objs` order.  commit=False keeps the scene
@@ -168,7 +178,8 @@ class Scene:
     def trace_grid(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                    stripe=None, sample_offset=0, spp_total=None, out=None, nhit=None, counters=None, stream=None,
                    stats=False, accumulate=False, split_samples=False, reorder=True, force_reorder=False, tile_order=True,
-                   diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None):
+                   diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None,
+                   relay_mirror=None, relay_order=None):
         """Asynchronous launch on torch's current stream (or `stream`).  reorder=False: CGRT_GRID_NO_REORDER (tiles in image
         order instead of heaviest-first; same image).  tile_order=False: CGRT_GRID_NO_TILE_ORDER (an image-order launch starts
         its tiles row-major instead of mirror / glass tiles first; same image).  diffuse_tiles=True: CGRT_GRID_DIFFUSE_TILES (a
@@ -177,9 +188,12 @@ class Scene:
         scene's kernel tests one sphere at a time and renders every tile with the full body; same image).  sphere_masks=False:
         CGRT_GRID_NO_SPHERE_MASKS (the terminal-diffuse body tests every sphere, not only its wave tile's candidates; same image).
         sample_relay: None -- a glass sphere scene's launch of at least 4 tiles per compute unit and 32 samples renders the tiles
-        that may see a refracting sphere by 2 workgroups each, summed in sample order (same image; last_sample_relay);
+        that may see a refracting or a reflecting sphere by 2 workgroups each, summed in sample order (same image; last_sample_relay);
         True or 2: CGRT_GRID_SAMPLE_RELAY (whatever the tile count); 4: that with CGRT_GRID_SAMPLE_RELAY_4 (up to 4 workgroups a
-        tile); False: CGRT_GRID_NO_SAMPLE_RELAY.  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
+        tile); False: CGRT_GRID_NO_SAMPLE_RELAY.  relay_mirror: True -- the relay takes the tiles that see only a mirror sphere
+        too (CGRT_GRID_RELAY_MIRROR), False -- it does not; relay_order: "chunks_first", "mirror_first" or "interleaved" -- where
+        those tiles' workgroups start among the glass tiles'; None: what sample_relay has always meant when it is given, the
+        measured form when it is not (last_relay_form tells).  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
         workgroups share a tile's samples; reproducible, fp64 summation order differs from the sample-by-sample sum).  Returns (rgb, nhit, counters) torch
         tensors on the scene's device: float32 [rows,width,3], int32 [rows,width] (bit pattern uint32),
         int64 [8] (counters are ADDED to)."""
@@ -199,7 +213,7 @@ class Scene:
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (2 if accumulate else 0) | (4 if split_samples else 0) |
                               (0 if reorder else 8) | (16 if force_reorder else 0) | (0 if tile_order else 64) |
-                              (128 if diffuse_tiles else 0) | (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay))
+                              (128 if diffuse_tiles else 0) | (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order))
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         check(self._L.cgrt_trace_grid(self._h, C.byref(cc), C.byref(g), out.data_ptr(),
                                       nhit.data_ptr() if nhit is not None else None,
@@ -412,7 +426,8 @@ class Scene:
 
     def trace_grid_host(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                         stripe=None, sample_offset=0, spp_total=None, stats=False, split_samples=False, reorder=True,
-                        force_reorder=False, tile_order=True, diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None):
+                        force_reorder=False, tile_order=True, diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None,
+                        relay_mirror=None, relay_order=None):
         """Synchronous form with numpy outputs (no torch needed): dict(rgb, nhit, counters)."""
         rows = height - row_offset if rows is None else rows
         rgb = np.zeros((rows, width, 3), np.float32)
@@ -421,7 +436,7 @@ class Scene:
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (4 if split_samples else 0) | (0 if reorder else 8) |
                               (16 if force_reorder else 0) | (0 if tile_order else 64) | (128 if diffuse_tiles else 0) |
-                              (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay))
+                              (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order))
         check(self._L.cgrt_trace_grid_host(self._h, C.byref(cc), C.byref(g), rgb.ctypes.data, nhit.ctypes.data,
                                            cnt.ctypes.data))
         return dict(rgb=rgb, nhit=nhit, counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]),
@@ -465,6 +480,13 @@ class Scene:
         t, k, v = C.c_int64(), C.c_int32(), C.c_int64()
         check(self._L.cgrt_scene_last_sample_relay(self._h, C.byref(t), C.byref(k), C.byref(v)))
         return dict(tiles=int(t.value), chunks=int(k.value), parked_values=int(v.value))
+
+    def last_relay_form(self):
+        """The form of that relay (cgrt_scene_last_relay_form): None when the launch did not relay, else dict(mirror: the tiles
+        that see only a mirror sphere were relayed too, order: "chunks_first", "mirror_first" or "interleaved")."""
+        m, o = C.c_int32(), C.c_int32()
+        check(self._L.cgrt_scene_last_relay_form(self._h, C.byref(m), C.byref(o)))
+        return None if m.value < 0 else dict(mirror=bool(m.value), order=_RELAY_ORDERS[o.value])
 
     def last_diffuse_tiles(self):
         """Tiles the terminal-diffuse launch of this scene's last trace_grid / trace_grid_host rendered

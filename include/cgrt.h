@@ -129,12 +129,25 @@ enum {
                                  the last of a tile's workgroups to finish adds them to the first chunk's sums in chunk order
                                  inside the launch -- the unsplit loop's sequence of additions, so image, hit counts, rays
                                  and Hitpoints are bit-identical; CGRT_CNT_WAVE_ITERS differs (see there).  By default the
-                                 relay is engaged when the launch has at least 4 tiles per compute unit; this flag engages
-                                 it whatever the tile count (cgrt_scene_last_sample_relay tells what a launch did) ... */
+                                 relay is engaged when the launch has at least 4 tiles per compute unit, and then in the form
+                                 measured fastest (CGRT_GRID_RELAY_MIRROR, interleaved); this flag engages it whatever the
+                                 tile count, for those tiles only (cgrt_scene_last_sample_relay tells what a launch did) ... */
     CGRT_GRID_NO_SAMPLE_RELAY = 2048, /* ... and this one switches it off                                              */
     CGRT_GRID_SAMPLE_RELAY_4 = 4096, /* the relay cuts a tile's samples into up to 4 chunks instead of 2, the default: measured
                                  on the 1920x1080 frame at 64 samples, two workgroups a tile gain more than four, which park
                                  half as many values again                                        */
+    CGRT_GRID_RELAY_MIRROR = 8192, /* the relay's extent: the tiles that may see a reflecting sphere only (class 2 of the tile
+                                 order) are rendered by several workgroups too -- every tile in front of class 3, as many as
+                                 the area holds ... */
+    CGRT_GRID_RELAY_NO_MIRROR = 16384, /* ... or only those that may see a refracting sphere.  Neither flag: a launch with
+                                 CGRT_GRID_SAMPLE_RELAY relays the latter, a launch that relays by default the extent
+                                 measured to be the faster.  Same bits either way                  */
+    CGRT_GRID_RELAY_CHUNKS_FIRST = 32768, /* the relay's launch order, a two-bit field (CGRT_GRID_RELAY_ORDER_MASK): the workgroups
+                                 of the tiles that may see a refracting sphere in front of those of class 2 ...          */
+    CGRT_GRID_RELAY_MIRROR_FIRST = 65536, /* ... behind them ...                                                           */
+    CGRT_GRID_RELAY_INTERLEAVED = 98304, /* ... or the two merged in proportion.  0: chunks first with CGRT_GRID_SAMPLE_RELAY,
+                                 the measured order by default.  cgrt_scene_last_relay_form tells what a launch used       */
+    CGRT_GRID_RELAY_ORDER_MASK = 98304,
     CGRT_GRID_HITPOINTS = 32, /* cgrt_trace_grid_variant only: name the launch of the Hitpoint capture
                                  (cgrt_trace_grid_hitpoints, the eye pass of cgrt_ppm_render) instead of cgrt_trace_grid's;
                                  ignored by the other calls                                                            */
@@ -630,6 +643,9 @@ int cgrt_scene_last_inkernel_diffuse_tiles(const cgrt_scene *s, int64_t *n_tiles
  * the tiles it rendered by several workgroups (0: it did not relay), *chunks = the workgroups of each, *parked_values = the
  * Hitpoint values (3 doubles each) that went through the relay area. */
 int cgrt_scene_last_sample_relay(const cgrt_scene *s, int64_t *tiles, int32_t *chunks, int64_t *parked_values);
+/* The form of that relay: *mirror = 1 when the class-2 tiles were relayed too (CGRT_GRID_RELAY_MIRROR), *order = 0 chunks
+ * first, 1 mirror first, 2 interleaved; both -1 when the launch did not relay. */
+int cgrt_scene_last_relay_form(const cgrt_scene *s, int32_t *mirror, int32_t *order);
 
 /* Host evaluation of the lens stream (cgrt_rng.hpp, the same inline code the kernel runs): writes
  * uniform_sampling_circle(radius) (sampling.h:35-43) for n (pixel, sample) pairs as 3 doubles each.  Lets CPU-only

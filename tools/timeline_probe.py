@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Development aid (not a test): when and where every workgroup of one trace_grid launch ran.
 
-  python tools/timeline_probe.py c3|c4|c2|c5band [--spp N] [--split] [--natural] [--relay on|off] [--out tl.json]
+  python tools/timeline_probe.py c3|c4|c2|c5band [--spp N] [--split] [--natural] [--relay on|off] [--mirror on|off]
+                                 [--order chunks_first|mirror_first|interleaved] [--out tl.json]
 
 Sets CGRT_TIMELINE_FILE so that libcgrt.so records, per workgroup, {start, end} on the 100 MHz wall clock, the hardware
 id (XCC, SE, CU) and the rays it traced, then prints: launch span, concurrency over time (resident workgroups in 20 time
@@ -25,6 +26,11 @@ def main():
     natural = "--natural" in sys.argv  # CGRT_GRID_NO_REORDER
     out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
     relay = {"on": True, "off": False}[sys.argv[sys.argv.index("--relay") + 1]] if "--relay" in sys.argv else None  # sample_relay
+    form = {}  # relay_mirror / relay_order
+    if "--mirror" in sys.argv:
+        form["relay_mirror"] = {"on": True, "off": False}[sys.argv[sys.argv.index("--mirror") + 1]]
+    if "--order" in sys.argv:
+        form["relay_order"] = sys.argv[sys.argv.index("--order") + 1]
     import cgraytracing_amd as cg
     import scenes
     cam = scenes.cam_dof()
@@ -44,16 +50,19 @@ def main():
     tf = tempfile.mktemp(suffix=".tl")
     os.environ["CGRT_TIMELINE_FILE"] = tf
     r = sc.trace_grid_host(W, H, spp, cam, 5, 12345, rows=rows, row_offset=row_offset, split_samples=split, reorder=not natural,
-                           **({} if relay is None else {"sample_relay": relay}))
+                           **dict({} if relay is None else {"sample_relay": relay}, **form))
     del os.environ["CGRT_TIMELINE_FILE"]
     tile_order = sc.last_tile_order() if hasattr(sc, "last_tile_order") else None  # image-order launches of sphere scenes
     relayed = sc.last_sample_relay() if hasattr(sc, "last_sample_relay") else None
+    relay_form = sc.last_relay_form() if hasattr(sc, "last_relay_form") else None
     sc.close()
     raw = np.fromfile(tf, dtype=np.uint64)
     os.unlink(tf)
     nblk, nthr, chunks, xcd_tiles = [int(x) for x in raw[:4]]
-    # a launch that relays samples (cgrt_relay.h) writes relay_k << 32 | relay_cap there (its tiles are row-major: xcd_tiles 0)
-    relay_k, relay_cap, xcd_tiles = (xcd_tiles >> 32, xcd_tiles & 0xffffffff, 0) if xcd_tiles >> 32 else (1, 0, xcd_tiles)
+    # a launch that relays samples (cgrt_relay.h) writes (relay_k | extent << 8 | order << 9) << 32 | relay_cap there (its tiles
+    # are row-major: xcd_tiles 0)
+    relay_k, relay_extent, relay_order, relay_cap, xcd_tiles = ((xcd_tiles >> 32) & 255, (xcd_tiles >> 40) & 1, (xcd_tiles >> 41) & 3,
+                                                                 xcd_tiles & 0xffffffff, 0) if xcd_tiles >> 32 else (1, 0, 0, 0, xcd_tiles)
     tl = raw[4:].reshape(nblk, 4)
     ran = tl[:, 1] > 0
     t0 = tl[ran, 0].astype(np.int64)
@@ -99,18 +108,35 @@ def main():
     doc["fraction_of_span_below_half_peak_concurrency"] = round(sum(1 for c in conc if c < half) / bins, 2)
     if tile_order is not None and nblk == len(tile_order["list"]) + (relay_k - 1) * relay_cap:
         # workgroup i rendered tile list[i]; plan[c] = workgroups of classes < c (classes 0-2: tiles that may see a glass / mirror sphere).
-        # With the relay (relay_block, cgrt_relay.h): the first relay_k * n_split workgroups are (entry i // relay_k, chunk i % relay_k),
-        # workgroup i behind them is entry i - (relay_k - 1) * n_split; workgroups beyond the list left at once and have no record.
+        # With the relay: relay_block_ordered (cgrt_relay.h), written out for arrays; workgroups beyond the list left at once and
+        # have no record.
         plan = [int(x) for x in tile_order["plan"]]
-        blk = np.nonzero(ran)[0]
-        n_split = min(plan[2], relay_cap) if relay_k > 1 else 0
-        split_blk = blk < relay_k * n_split
-        chunk = np.where(split_blk, blk % relay_k, 0)
-        blk = np.where(split_blk, blk // relay_k, blk - (relay_k - 1) * n_split)  # the entry
+        blk = np.nonzero(ran)[0].astype(np.int64)
+        n01, n012 = plan[2], plan[3]
+        n_split = min(n012 if relay_extent else n01, relay_cap) if relay_k > 1 else 0
+        k = relay_k
+        s_a = min(n_split, n01)
+        s_m = n_split - s_a
+        n_a, n_m = n01 + (k - 1) * s_a, n012 - n01 + (k - 1) * s_m
+        t = n_a + n_m
+        if relay_order == 2:
+            q = blk * n_m // max(t, 1)
+            mirror = blk * n_m - q * t + n_m >= t
+            i = np.where(mirror, q, blk - q)
+        elif relay_order == 1:
+            mirror = blk < n_m
+            i = np.where(mirror, blk, blk - n_m)
+        else:
+            mirror = blk >= n_a
+            i = np.where(mirror, blk - n_a, blk)
+        first, s_of = np.where(mirror, n01, 0), np.where(mirror, s_m, s_a)
+        split_blk = (blk < t) & (i < k * s_of)
+        chunk = np.where(split_blk, i % k, 0)
+        blk = np.where(blk >= t, n012 + blk - t, np.where(split_blk, first + i // k, first + i - (k - 1) * s_of))  # the entry
         if relay_k > 1:
             ent_rays = np.bincount(blk, weights=rays, minlength=plan[4])
             heavy = int(np.argmax(ent_rays))  # the entry with the most rays: the glass sphere's centre tile
-            doc["sample_relay"] = {"chunks": relay_k, "capacity_tiles": relay_cap, "split_tiles": n_split, "last": relayed,
+            doc["sample_relay"] = {"chunks": relay_k, "capacity_tiles": relay_cap, "split_tiles": n_split, "last": relayed, "form": relay_form,
                                    "workgroups_launched": nblk, "workgroups_beyond_the_list": int(nblk - ran.sum()),
                                    "split_workgroup_us": {"mean": round(float(dur[split_blk].mean()), 1), "max": round(float(dur[split_blk].max()), 1)} if split_blk.any() else None,
                                    "heaviest_entry": {"entry": heavy, "tile": int(tile_order["list"][heavy]), "rays": int(ent_rays[heavy]),
@@ -123,6 +149,16 @@ def main():
                              "class3_first_start_us": round(float(a[c3].min()), 1) if c3.any() else None,
                              "class3_last_end_us": round(float(b[c3].max()), 1) if c3.any() else None,
                              "class012_last_end_us": round(float(b[~c3].max()), 1) if (~c3).any() else None}
+        # per class (class 2: its split and its unsplit workgroups apart): first start, last start, last end
+        def span_of(sel):
+            return {"workgroups": int(sel.sum()), "first_start_us": round(float(a[sel].min()), 1), "last_start_us": round(float(a[sel].max()), 1),
+                    "last_end_us": round(float(b[sel].max()), 1), "mean_us": round(float(dur[sel].mean()), 1),
+                    "max_us": round(float(dur[sel].max()), 1)} if sel.any() else None
+        cls = np.searchsorted(np.asarray(plan[1:4]), blk, side="right")
+        doc["tile_order"]["classes"] = {"class0": span_of(cls == 0), "class1": span_of(cls == 1), "class2_split": span_of((cls == 2) & split_blk),
+                                        "class2_unsplit": span_of((cls == 2) & ~split_blk), "class3": span_of(cls == 3)}
+        end012, end3 = doc["tile_order"]["class012_last_end_us"], doc["tile_order"]["class3_last_end_us"]
+        doc["tile_order"]["classes_0_2_end_no_later_than_class_3"] = bool(end012 is not None and end3 is not None and end012 <= end3)
     print(json.dumps(doc, indent=1))
     if out:
         json.dump(doc, open(out, "w"), indent=1)
