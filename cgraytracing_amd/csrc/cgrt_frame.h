@@ -1,6 +1,7 @@
 // The host side of an eye-pass launch in plain C++ (no HIP): the kernel parameters, the workgroup / tile constants, the
-// environment switches and the frame plan -- sample chunks, tile counts, heavy-tile capacity, scheduling and where each
-// array lies in the handle's launch scratch.  cgrt_trace_grid (cgrt_hip.hip) launches what frame_plan decides;
+// environment switches and the frame plan -- sample chunks, tile counts, heavy-tile capacity, scheduling, the tile order of a
+// sphere scene (whether it runs, who renders its class-3 tiles, the sphere masks, the sample relay) and where each array lies
+// in the handle's launch scratch and in its order buffer.  cgrt_trace_grid (cgrt_hip.hip) launches what frame_plan decides;
 // tests/native/frame_plan.cpp checks it on the CPU.
 #ifndef CGRT_FRAME_H
 #define CGRT_FRAME_H
@@ -97,7 +98,7 @@ static_assert(sizeof(GridParams) == 320, "GridParams is a kernel argument: its l
 
 static constexpr int kTileW = 32, kTileH = 8, kThreads = 256;
 // Tile order of image-order launches (tile_order_kernel, cgrt_eye.hpp): the special spheres -- those that reflect or refract --
-// travel as a kernel argument; a scene with more of them than this is left in row-major order.  The handle's order buffer is
+// travel as a kernel argument; a scene with more of them than this is left in row-major order.  The handle's order buffer (TileOrderLayout) is
 // plan[kOrderPlanWords] | list[n_tiles] | tile class[n_tiles] (bytes) | wave-tile class[n_wt] (bytes) | wave-tile sphere mask[n_wt]
 // (words; GridParams::wmask), each part padded to 256 bytes; plan[c], c = 0..4 = tiles of classes < c, plan[kOrderArrived] = the
 // workgroups of tile_order_kernel that are through (0 between launches).
@@ -107,9 +108,31 @@ struct OrderSpheres {
     double s[kOrderSpheresMax][4];  // centre, radius
     uint32_t n, transp;             // transp: bit i set = sphere i refracts (transp >= kEps), else it only reflects
 };
-static constexpr size_t order_pad(size_t b) { return (b + 255) & ~(size_t)255; }
-inline size_t tile_order_bytes(size_t n_tiles, size_t n_wt) {
-    return order_pad((kOrderPlanWords + n_tiles) * sizeof(uint32_t)) + order_pad(n_tiles) + order_pad(n_wt) + order_pad(n_wt * sizeof(uint32_t));
+static constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// A part of a launch buffer of the handle; bytes == 0: not used by this frame (its pointer is nullptr)
+struct Region {
+    size_t at, bytes;
+    template <class T> T *in(unsigned char *base) const { return bytes ? reinterpret_cast<T *>(base + at) : nullptr; }
+};
+// Where the parts of the order buffer lie, in bytes from its start
+struct TileOrderLayout {
+    Region plan{}, list{}, tile_cls{}, wave_cls{}, wmask{};
+    size_t total = 0;  // bytes to allocate
+};
+inline TileOrderLayout tile_order_layout(size_t n_tiles, size_t n_wt) {
+    TileOrderLayout L;
+    size_t end = 0;  // the list follows the plan at once; every other part starts on 256 bytes
+    const auto take = [&end](size_t bytes) { end += bytes; return Region{end - bytes, bytes}; };
+    L.plan = take(kOrderPlanWords * sizeof(uint32_t));
+    L.list = take(n_tiles * sizeof(uint32_t));
+    end = align256(end);
+    L.tile_cls = take(n_tiles);
+    end = align256(end);
+    L.wave_cls = take(n_wt);
+    end = align256(end);
+    L.wmask = take(n_wt * sizeof(uint32_t));
+    L.total = align256(end);
+    return L;
 }
 static constexpr int kSphereMaskMax = 32;  // spheres a wave tile's mask word holds
 // True when no tile of any grid seen from `cam` can be of class 3: some special sphere fails cone_clear_of (cgrt_eye.hpp) by
@@ -245,14 +268,15 @@ struct FrameInputs {
     EyeKnobs knobs;
     size_t mem_total;
     int n_cu, waves_per_simd;  // waves_per_simd: the scheduled kernel's occupancy (kBezWaves, kSchedTreeWaves or 4)
-    bool relay = false;        // the launch may relay samples (relay_wanted: an image-order launch in tile order, PAIR variant)
+    // What the tile order asks (TileOrderPlan): the eye launch's form == Image and its kernel's flags SPH and PAIR; the scene's
+    // order_ok (spheres and planes, 1..kOrderSpheresMax special spheres), whether the handle has its second stream, whether all
+    // its objects are spheres, how many there are and how many of them lie in LDS; order_all_special for this camera
+    bool image = false, sph = false, pair = false;
+    bool order_ok = false, aux_stream = false, all_spheres = false;
+    int n_objs = 0, n_lds = 0;
+    bool all_special = false;
 };
 
-// A part of the launch scratch; bytes == 0: not used by this frame (its pointer is nullptr)
-struct Region {
-    size_t at, bytes;
-    template <class T> T *in(unsigned char *base) const { return bytes ? reinterpret_cast<T *>(base + at) : nullptr; }
-};
 // Where each array of a launch lies in the handle's scratch, in bytes from its start: the chunk sums, then (scheduled
 // launches) the schedule arrays and the deferred arrays of kmax heavy tiles, one array after another.
 struct ScratchLayout {
@@ -275,6 +299,16 @@ struct ScratchLayout {
     }
 };
 
+// The tile order of an image-order launch of a sphere scene (tile_order_kernel; GridParams::tile_order)
+struct TileOrderPlan {
+    bool on = false;  // the launch runs through the ordered list (order_tiles)
+    // who renders the list's class-3 tiles, those that see no mirror or glass: the eye launch's own body like every other tile
+    // (kOrderAll), the terminal-diffuse variant in a launch of its own on the second stream (kOrderFull + kOrderDiffuse), or the
+    // terminal-diffuse body inside the PAIR variant (kOrderAllDiffuse)
+    enum Class3 { None, SecondLaunch, InKernel } class3 = None;
+    bool masks = false;  // tile_order_kernel writes the wave tiles' sphere masks (GridParams::wmask)
+};
+
 struct FramePlan {
     int chunks = 1, chunk_spp = 0;  // CGRT_GRID_SPLIT_SAMPLES: workgroups per tile, samples per workgroup
     bool xcd_tiles = false;         // XCD-aware super-tiles, else row-major (tile_of_block)
@@ -289,6 +323,7 @@ struct FramePlan {
     int wave_slots = 0, items_per_tile = 1, heavy_blocks = 0;
     unsigned long long plan_div = 0;  // plan_kernel: heavy when cost x spp > total x spp / plan_div
     ScratchLayout scratch;
+    TileOrderPlan order;
     // The sample relay (cgrt_relay.h): relay_k > 1 when the launch relays -- workgroups per relayed tile, samples per workgroup,
     // slots per parked stream, bytes of the relay area per tile, tiles the area is to hold and its bytes (the area lives on the
     // handle beside the scratch; a launch whose area cannot be had goes without the relay, grid_dim workgroups; with it,
@@ -324,8 +359,6 @@ inline int relay_order_of(int32_t flags, const EyeKnobs &kn) {
     return (flags & CGRT_GRID_SAMPLE_RELAY) ? kRelayChunksFirst : kRelayDefaultOrder;
 }
 
-static constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // The launch at capacity kmax (0 when it is not scheduled): a function of the inputs and kmax only
 inline FramePlan frame_plan(const FrameInputs &in, size_t kmax) {
     const cgrt_grid &gr = in.grid;
@@ -351,7 +384,27 @@ inline FramePlan frame_plan(const FrameInputs &in, size_t kmax) {
     p.tile_blocks = one_wave ? tile_grid_blocks(gr.width, gr.rows, false, kWaveTileW, kWaveTileH)
                              : tile_grid_blocks(gr.width, gr.rows, p.xcd_tiles);
     p.grid_dim = (size_t)p.tile_blocks * p.chunks;
-    if (in.relay && p.chunks == 1 && !p.xcd_tiles && !one_wave && relay_engaged(gr.flags, gr.spp, (size_t)p.tile_blocks, in.n_cu)) {
+    // The tile order: image order, one workgroup per tile with all its samples, row-major, 256 threads.  The second launch for
+    // class 3 is for the plain sphere variant (no SPILL, no STATS; not a timeline launch, which is one launch) where the caller
+    // asks for it and the handle has the stream; otherwise the PAIR variant renders class 3 by the body it carries.  Neither
+    // where no tile can be of class 3 at all (all_special).  Sphere masks: where a terminal-diffuse body runs, in either form,
+    // over a list of at most 32 spheres, all of them in LDS.  The relay is the PAIR variant's, in its one-launch forms.  A launch
+    // that asks for split samples and gets one chunk (fewer than 32 samples, or sums beyond 4 GiB) keeps the tile order, without
+    // the second launch and without the relay.  (For a committed scene `on` takes nothing from what the second launch asks by
+    // itself: order_ok means no mesh, hence row-major tiles, and without split_asked there is one chunk.)
+    TileOrderPlan &o = p.order;
+    const bool split_asked = (gr.flags & CGRT_GRID_SPLIT_SAMPLES) != 0;
+    o.on = in.image && p.chunks == 1 && !p.xcd_tiles && in.nt == kThreads && in.order_ok && !(gr.flags & CGRT_GRID_NO_TILE_ORDER);
+    if (o.on && !in.all_special) {
+        if (in.sph && !in.spill && !in.stats && in.aux_stream && (gr.flags & CGRT_GRID_DIFFUSE_TILES) && !split_asked && !kn.timeline_file)
+            o.class3 = TileOrderPlan::SecondLaunch;
+        else if (in.pair)
+            o.class3 = TileOrderPlan::InKernel;
+    }
+    o.masks = o.class3 != TileOrderPlan::None && in.all_spheres && in.n_objs <= kSphereMaskMax && in.n_objs == in.n_lds &&
+              !(gr.flags & CGRT_GRID_NO_SPHERE_MASKS);
+    if (o.on && in.pair && o.class3 != TileOrderPlan::SecondLaunch && !split_asked &&
+        relay_engaged(gr.flags, gr.spp, (size_t)p.tile_blocks, in.n_cu)) {
         const RelayChunks rc = relay_chunks(gr.spp, (gr.flags & CGRT_GRID_SAMPLE_RELAY_4) ? kRelayMaxChunks : kn.relay_chunks);
         if (rc.k > 1) {
             p.relay_slots = relay_slots(rc.chunk_spp, gr.max_depth);

@@ -72,73 +72,6 @@ struct GrowBuf {
     }
 };
 
-struct cgrt_scene {
-    HostScene host;
-    bool committed = false;
-    int device = -1;
-    DeviceScene dev{};
-    std::vector<void *> allocs;
-    int64_t device_bytes = 0;
-    // launch scratch (chunk sums, schedule, deferred Hitpoint values: ScratchLayout); reused by later launches on this handle
-    // (launches on one handle are ordered by the caller: cgrt.h, "Threading")
-    mutable GrowBuf scratch;
-    mutable size_t scratch_refused = 0;  // smallest scratch size this device has refused (0: none yet): not asked for again
-    // tile order of image-order launches (tile_order_kernel): the scene's reflecting / refracting spheres (read at commit;
-    // order_ok: the scene is spheres and planes with 1..kOrderSpheresMax of them), the order buffer -- launch scratch like
-    // `scratch`, kept apart so that the frame plan's layout stays what it is -- and the tiles the last launch ordered (0: none)
-    OrderSpheres order_spheres{};
-    bool order_ok = false;
-    mutable GrowBuf order_buf;
-    mutable size_t order_tiles = 0;
-    // ... the wave tiles it wrote sphere masks for (0: none), and what the buffer holds: the order depends on nothing but
-    // OrderKey, so a launch with the key of the buffer's contents runs no ordering kernel (order_reused).  ev_order is recorded
-    // behind the kernel on order_stream; a reusing launch on another stream waits for it.  commit_gen: this commit's number.
-    mutable size_t mask_wtiles = 0;
-    struct OrderKey {
-        double cam[3], half_width, focus_plane, lens_radius;
-        int32_t W, H, rows, row_offset, stripe_rows, stripe_rank, stripe_nranks, masks;
-        uint64_t commit_gen;
-        const void *buf;
-    };
-    static_assert(sizeof(OrderKey) == 96, "OrderKey is compared as bytes: no padding");
-    mutable OrderKey order_key{};
-    mutable bool order_valid = false, order_reused = false;
-    mutable bool order_captured = false;  // a launch on this handle was captured into a graph: its replays rewrite the buffer at times the handle does not see, so nothing is reused any more
-    mutable hipEvent_t ev_order = nullptr;
-    mutable hipStream_t order_stream = nullptr;
-    uint64_t commit_gen = 0;
-    // the terminal-diffuse launch over the order's class-3 tiles (sphere-only scenes; it runs on aux_stream beside the main
-    // launch): whether the last launch issued one
-    mutable bool diffuse_issued = false;
-    // ... and whether its class-3 workgroups took the terminal-diffuse body inside the main launch instead (kOrderAllDiffuse)
-    mutable bool diffuse_in_kernel = false;
-    // The sample relay's area (cgrt_relay.h; launch scratch like `scratch`, allocated by the first launch that relays, sized by the
-    // largest): relay_refused -- the smallest size the device has refused (such a launch goes unrelayed); relay_zeroed -- the
-    // arrival words known to be 0 (the kernel leaves them so; a launch that failed on the way does not vouch for it:
-    // relay_dirty); ev_relay is recorded behind a relaying launch on relay_stream, and a relaying launch on another stream waits
-    // for it -- the area is one.  last_relay_*: what the last cgrt_trace_grid relayed with (k == 0: it did not).
-    mutable GrowBuf relay_buf;
-    mutable size_t relay_refused = 0, relay_zeroed = 0;
-    mutable bool relay_dirty = false;
-    mutable hipEvent_t ev_relay = nullptr;
-    mutable hipStream_t relay_stream = nullptr;
-    mutable bool relay_recorded = false;
-    mutable int last_relay_k = 0;
-    mutable size_t last_relay_cap = 0;
-    mutable int last_relay_slots = 0;
-    mutable int last_relay_extent = 0, last_relay_order = 0;
-    size_t mem_total = 0;                // memory of the scene's device (read at commit; bounds the deferred-value budget)
-    int n_cu = 256;                      // compute units of the scene's device (read at commit; wave slots of the scheduler)
-    // second stream + fork/join events for the light-tile launch that runs beside the full one (created at commit)
-    hipStream_t aux_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    cgrt_build_info build_info{};  // filled by cgrt_scene_commit
-    std::vector<TreeRec> tree_recs;  // host copy of dev.trees (where a device-built tree's records live)
-    // cgrt_ray_hit_attributes' prim: per record of dev.tris the triangle's index in its tree's construction order.  Built and
-    // uploaded by the first call that asks for prim (a scene that never asks pays nothing); immutable afterwards
-    mutable GrowBuf tri_ids;
-};
-
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) {
     g_err = msg;
@@ -185,6 +118,34 @@ struct DevBuf {  // RAII for device temporaries: freed on every return path
     template <class T> T *as() { return reinterpret_cast<T *>(p); }
 };
 
+#include "cgrt_tile_order.hpp"
+
+struct cgrt_scene {
+    HostScene host;
+    bool committed = false;
+    int device = -1;
+    DeviceScene dev{};
+    std::vector<void *> allocs;
+    int64_t device_bytes = 0;
+    // launch scratch (chunk sums, schedule, deferred Hitpoint values: ScratchLayout); reused by later launches on this handle
+    // (launches on one handle are ordered by the caller: cgrt.h, "Threading")
+    mutable GrowBuf scratch;
+    mutable size_t scratch_refused = 0;  // smallest scratch size this device has refused (0: none yet): not asked for again
+    // what a sphere scene's tile-order launches keep on the handle (cgrt_tile_order.hpp)
+    mutable TileOrderState order;
+    mutable RelayState relay;
+    size_t mem_total = 0;                // memory of the scene's device (read at commit; bounds the deferred-value budget)
+    int n_cu = 256;                      // compute units of the scene's device (read at commit; wave slots of the scheduler)
+    // second stream + fork/join events for the light-tile launch that runs beside the full one (created at commit)
+    hipStream_t aux_stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    cgrt_build_info build_info{};  // filled by cgrt_scene_commit
+    std::vector<TreeRec> tree_recs;  // host copy of dev.trees (where a device-built tree's records live)
+    // cgrt_ray_hit_attributes' prim: per record of dev.tris the triangle's index in its tree's construction order.  Built and
+    // uploaded by the first call that asks for prim (a scene that never asks pays nothing); immutable afterwards
+    mutable GrowBuf tri_ids;
+};
+
 template <class T>
 static int upload(cgrt_scene *s, const std::vector<T> &v, const T **out, size_t extra = 0) {  // extra: records of room behind v
     *out = nullptr;
@@ -217,18 +178,16 @@ int cgrt_scene_create(cgrt_scene **out) {
 
 void cgrt_scene_destroy(cgrt_scene *s) {
     if (!s) return;
-    if (!s->allocs.empty() || s->scratch.p || s->order_buf.p || s->relay_buf.p || s->tri_ids.p || s->aux_stream || s->ev_order || s->ev_relay) {
+    if (!s->allocs.empty() || s->scratch.p || s->order.buf.p || s->relay.buf.p || s->tri_ids.p || s->aux_stream || s->order.ev || s->relay.ev) {
         DeviceGuard g(s->device);
         if (g.err == hipSuccess) {
             for (void *p : s->allocs) (void)hipFree(p);
             s->scratch.release();
-            s->order_buf.release();
-            s->relay_buf.release();
+            s->order.release();
+            s->relay.release();
             s->tri_ids.release();
             if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
             if (s->ev_join) (void)hipEventDestroy(s->ev_join);
-            if (s->ev_order) (void)hipEventDestroy(s->ev_order);
-            if (s->ev_relay) (void)hipEventDestroy(s->ev_relay);
             if (s->aux_stream) (void)hipStreamDestroy(s->aux_stream);
         }
     }
@@ -432,7 +391,7 @@ int cgrt_scene_commit(cgrt_scene *s, int device) {
     }
     scene_traits(H, L.trees, knobs, d);
     {   // the spheres tile_order_kernel orders an image-order launch by
-        OrderSpheres &os = s->order_spheres;
+        OrderSpheres &os = s->order.spheres;
         os = OrderSpheres{};
         size_t special = 0;
         for (const ObjRec &o : H.objs) {
@@ -445,14 +404,14 @@ int cgrt_scene_commit(cgrt_scene *s, int device) {
             special++;
         }
         os.n = (uint32_t)std::min(special, (size_t)kOrderSpheresMax);
-        s->order_ok = !d.has_mesh && !d.has_bezier && special >= 1 && special <= (size_t)kOrderSpheresMax;
+        s->order.ok = !d.has_mesh && !d.has_bezier && special >= 1 && special <= (size_t)kOrderSpheresMax;
     }
-    open_light_stream(s, knobs.aux_priority, d, s->order_ok && d.all_spheres != 0);
+    open_light_stream(s, knobs.aux_priority, d, s->order.ok && d.all_spheres != 0);
     s->dev = d;
     s->committed = true;
     static std::atomic<uint64_t> commits{0};
-    s->commit_gen = ++commits;  // what an earlier commit left in the order buffer is not this scene's
-    s->order_valid = false;
+    s->order.commit_gen = ++commits;  // what an earlier commit left in the order buffer is not this scene's
+    s->order.valid = false;
     s->tree_recs = std::move(L.trees);
     size_t fr = 0, tot = 0;
     s->mem_total = hipMemGetInfo(&fr, &tot) == hipSuccess ? tot : ((size_t)32 << 30);
@@ -492,7 +451,7 @@ int cgrt_scene_get_stats(const cgrt_scene *s, cgrt_scene_stats *out) {
     bytes += 56 * out->n_nodes + 72 * out->n_triangles;
     for (auto &t : H.textures) bytes += 3 * (int64_t)t.rows * t.cols;
     out->scene_bytes_fp64 = bytes;
-    out->device_bytes = s->device_bytes + (int64_t)s->scratch.cap + (int64_t)s->order_buf.cap + (int64_t)s->tri_ids.cap;  // uploaded scene + the handle's launch scratch (+ the hit-attribute table once asked for)
+    out->device_bytes = s->device_bytes + (int64_t)s->scratch.cap + (int64_t)s->order.buf.cap + (int64_t)s->tri_ids.cap;  // uploaded scene + the handle's launch scratch (+ the hit-attribute table once asked for)
     out->committed = s->committed ? 1 : 0;
     return CGRT_OK;
 }
@@ -829,7 +788,7 @@ static EyeLaunch eye_launch(const cgrt_scene *s, const cgrt_camera *cam, const c
         L.form = reorder ? EyeForm::Sched : EyeForm::Image;
         // The image-order launch of a glass sphere scene the tile order serves (order_ok): its last waves, over the glass sphere,
         // each alone on a SIMD, are bound by the sphere loop's dependent chain -- two spheres a trip
-        L.k.pair = L.form == EyeForm::Image && L.k.sph && L.k.glass && !L.k.stats && s->order_ok && !(grid->flags & CGRT_GRID_NO_SPHERE_PAIRS);
+        L.k.pair = L.form == EyeForm::Image && L.k.sph && L.k.glass && !L.k.stats && s->order.ok && !(grid->flags & CGRT_GRID_NO_SPHERE_PAIRS);
     }
     L.lds = eye_lds(L.k, L.dev) + (L.form == EyeForm::Image || L.form == EyeForm::Sched ? (size_t)kn.lds_pad : 0);
     return L;
@@ -846,16 +805,7 @@ static EyeLaunch light_launch(const DeviceScene &d, bool dof, const EyeKnobs &kn
     return L;
 }
 // The diffuse tiles' launch beside an image-order launch of a sphere-only scene (class 3 of tile_order_kernel's list): the
-// terminal-diffuse variant, the object list its only LDS.  It is issued when the main launch is the plain sphere variant in
-// tile order (eye_launch: no SPILL, no STATS; not the Hitpoint capture, a probe, a split-sample or a timeline launch), the
-// caller asks for it (CGRT_GRID_DIFFUSE_TILES) and some tile can be of class 3 at all (order_all_special).  These conditions contain those of
-// the tile order itself (cgrt_trace_grid: image order, one chunk -- no CGRT_GRID_SPLIT_SAMPLES --, row-major tiles -- a sphere
-// scene has no mesh --, 256 threads, order_ok), so the launch and cgrt_trace_grid_diffuse_variant decide by this alone.
-static bool diffuse_wanted(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, const EyeLaunch &L, const EyeKnobs &kn) {
-    return L.form == EyeForm::Image && L.k.sph && !L.k.spill && !L.k.stats && L.k.nt == kThreads && s->order_ok && s->aux_stream &&
-           (grid->flags & CGRT_GRID_DIFFUSE_TILES) && !(grid->flags & (CGRT_GRID_NO_TILE_ORDER | CGRT_GRID_SPLIT_SAMPLES)) && !kn.timeline_file &&
-           !order_all_special(s->order_spheres, *cam);
-}
+// terminal-diffuse variant, the object list its only LDS.  frame_plan decides when it is issued (TileOrderPlan::SecondLaunch).
 static EyeLaunch diffuse_launch(const DeviceScene &d, bool dof) {
     EyeLaunch L;
     L.form = EyeForm::Diffuse;
@@ -912,6 +862,24 @@ static int fit_scratch(const cgrt_scene *s, const FrameInputs &in, FramePlan &p)
         p = frame_plan(in, p.kmax / 2);
     }
     return CGRT_OK;
+}
+
+// What frame_plan needs of cgrt_trace_grid's launch L, as plain values
+static FrameInputs frame_inputs(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, const EyeLaunch &L, const EyeKnobs &kn) {
+    const DeviceScene &d = s->dev;
+    FrameInputs in{*grid, *cam, L.form == EyeForm::Sched, L.k.spill, L.k.stats, L.k.glass, L.k.nt, d.has_mesh != 0,
+                   d.has_bezier != 0, d.prim_finish != 0, d.light_ok != 0, d.prim_obj, kn, s->mem_total, s->n_cu,
+                   L.k.nt == 64 ? kBezWaves : (L.k.trees ? kSchedTreeWaves : 4)};
+    in.image = L.form == EyeForm::Image;
+    in.sph = L.k.sph;
+    in.pair = L.k.pair;
+    in.order_ok = s->order.ok;
+    in.aux_stream = s->aux_stream != nullptr;
+    in.all_spheres = d.all_spheres != 0;
+    in.n_objs = d.n_objs;
+    in.n_lds = d.n_lds;
+    in.all_special = order_all_special(s->order.spheres, *cam);
+    return in;
 }
 
 // Cost-aware scheduling ("classify -> probe -> plan -> render -> ordered sum"; DESIGN.md sections 4.6-4.7).  A frame's cost
@@ -980,134 +948,18 @@ static int primary_walk(const cgrt_scene *s, const EyeLaunch &L, const GridParam
                           dim3((unsigned)s->n_cu * 4), dim3(kThreads), primary_walk_lds(staged), st, s->dev, g, pw);
 }
 
-// The tile order of an image-order launch over a scene with reflecting or refracting spheres (tile_order_kernel, cgrt_eye.hpp):
-// one small launch in front of the eye launch, on its stream, that lists the tiles the costly ones first; g then maps the
-// eye launch's workgroups through the list.  The buffer is launch scratch of the handle, written and read on this stream.
-// masks: the launch also writes the wave tiles' sphere masks (GridParams::wmask) for the terminal-diffuse body.
-// The kernel reads the camera, the frame geometry (W, H, rows, row offset, stripe) and the committed scene, nothing else: when
-// the buffer still holds the result for exactly these (cgrt_scene::OrderKey -- the passes of a progressive render, the frames of
-// a still camera) nothing is launched and g points at it.  The eye launch only reads the buffer (plan[0..4], the list, the
-// masks; plan[kOrderArrived] is back at 0 when the kernel ends), so it is as the kernel left it.  The contents are not trusted
-// beyond a commit, a reallocation, a cgrt_trace_grid that returned an error (it drops the key on every such exit) or a stream capture (a captured
-// launch runs later, or never, and again at every replay: from the first capture on, the handle neither reuses nor leaves a key).
-// One handle serves one stream at a time (cgrt.h, "Threading"): a launch with another key rewrites the buffer, and the event only
-// orders a reusing launch behind the kernel that wrote it, not a rewrite behind another stream's readers.
-// no_reuse (CGRT_NO_ORDER_REUSE=1, a measurement aid): every launch runs the kernel.
-static int order_tiles(const cgrt_scene *s, const FramePlan &p, GridParams &g, bool masks, bool no_reuse, hipStream_t st) {
-    const int tiles_x = (g.W + kTileW - 1) / kTileW, tiles_y = (g.rows + kTileH - 1) / kTileH;
-    const size_t n = (size_t)tiles_x * tiles_y, bytes = tile_order_bytes(n, p.n_wt);
-    const bool grown = bytes > s->order_buf.cap;
-    if (grown) s->order_valid = false;
-    if (s->order_buf.need(bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(CGRT_ERR_DEVICE, "cannot allocate launch scratch (tile order)");
-    }
-    unsigned char *base = reinterpret_cast<unsigned char *>(s->order_buf.p);
-    uint32_t *plan = reinterpret_cast<uint32_t *>(base), *list = plan + kOrderPlanWords;
-    unsigned char *tcls = base + order_pad((kOrderPlanWords + n) * sizeof(uint32_t)), *wcls = tcls + order_pad(n);
-    uint32_t *wmask = masks ? reinterpret_cast<uint32_t *>(wcls + order_pad(p.n_wt)) : nullptr;
-    cgrt_scene::OrderKey key{{g.cam[0], g.cam[1], g.cam[2]}, g.half_width, g.focus_plane, g.lens_radius, g.W, g.H, g.rows, g.row_offset,
-                             g.stripe_rows, g.stripe_rank, g.stripe_nranks, masks ? 1 : 0, s->commit_gen, s->order_buf.p};
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &capturing) != hipSuccess) {
-        (void)hipGetLastError();
-        capturing = hipStreamCaptureStatusActive;  // unknown: as if it were
-    }
-    if (capturing != hipStreamCaptureStatusNone) s->order_captured = true;
-    const bool plain = !s->order_captured && !no_reuse;
-    s->order_reused = plain && s->order_valid && std::memcmp(&key, &s->order_key, sizeof(key)) == 0;
-    if (s->order_reused) {
-        if (st != s->order_stream) HIP_TRY(hipStreamWaitEvent(st, s->ev_order, 0));
-    } else {
-        s->order_valid = false;
-        if (grown) HIP_TRY(hipMemsetAsync(plan, 0, kOrderPlanWords * sizeof(uint32_t), st));  // plan[kOrderArrived]
-        const unsigned blocks = (unsigned)std::min((p.n_wt + 1023) / 1024, (size_t)64);
-        hipLaunchKernelGGL(tile_order_kernel, dim3(blocks), dim3(1024), 0, st, g, s->order_spheres, s->dev, tiles_x, tiles_y, plan, list, tcls, wcls, wmask);
-        if (plain && hipPeekAtLastError() == hipSuccess) {
-            if (!s->ev_order && hipEventCreateWithFlags(&s->ev_order, hipEventDisableTiming) != hipSuccess) {
-                (void)hipGetLastError();
-                s->ev_order = nullptr;
-            }
-            if (s->ev_order && hipEventRecord(s->ev_order, st) == hipSuccess) {
-                s->order_key = key;
-                s->order_stream = st;
-                s->order_valid = true;
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-    }
-    g.plan = plan;
-    g.border = list;
-    g.wmask = wmask;
-    g.tile_order = kOrderAll;
-    s->order_tiles = n;
-    s->mask_wtiles = masks ? p.n_wt : 0;
-    return CGRT_OK;
-}
-
-// The sample relay of a tile-order launch of the PAIR variants (cgrt_relay.h; the plan has relay_k > 1): the handle's relay area
-// and g's relay fields.  Returns false -- the launch goes unrelayed, which is no error -- when the stream is being captured (the
-// area, its event and the handle's record of both belong to launches that run now), or the area cannot be had.  The arrival
-// words are 0 whenever no launch is in flight: zeroed here when the area is new or grown, when more of them are needed than
-// were zeroed, or after a launch that did not go through; reset by the kernel otherwise.
-static bool relay_prepare(const cgrt_scene *s, const FramePlan &p, GridParams &g, hipStream_t st) {
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &capturing) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    if (capturing != hipStreamCaptureStatusNone) return false;
-    if (s->relay_refused && p.relay_bytes >= s->relay_refused) return false;
-    if (p.relay_bytes > s->relay_buf.cap) {
-        // the launches that use the old area are through before it is freed
-        if (s->relay_recorded && hipEventSynchronize(s->ev_relay) != hipSuccess) (void)hipGetLastError();
-        s->relay_zeroed = 0;
-        if (s->relay_buf.need(p.relay_bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            s->relay_refused = p.relay_bytes;
-            return false;
-        }
-    }
-    if (!s->ev_relay && hipEventCreateWithFlags(&s->ev_relay, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
-        s->ev_relay = nullptr;
-        return false;
-    }
-    if (s->relay_recorded && st != s->relay_stream && hipStreamWaitEvent(st, s->ev_relay, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    if (s->relay_dirty || p.relay_cap > s->relay_zeroed) {
-        if (hipMemsetAsync(s->relay_buf.p, 0, p.relay_cap * sizeof(uint32_t), st) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-    }
-    s->relay_zeroed = p.relay_cap;  // (the words beyond this launch's lie in its arrays)
-    s->relay_dirty = true;  // until the launch is through (cgrt_trace_grid)
-    g.relay = reinterpret_cast<unsigned char *>(s->relay_buf.p);
-    g.relay_k = p.relay_k;
-    g.relay_chunk_spp = p.relay_chunk_spp;
-    g.relay_cap = (int32_t)p.relay_cap;
-    g.relay_slots = p.relay_slots;
-    g.relay_extent = p.relay_extent;
-    g.relay_order = p.relay_order;
-    return true;
-}
-
 // development aid: CGRT_TIMELINE_FILE=path makes a launch synchronous and dumps, per workgroup, when and where it ran
 // (GridParams::timeline), behind a header {workgroups, threads per workgroup, chunks, xcd_tiles} (tools/timeline_probe.py)
-static int write_timeline(const char *file, const DevBuf &tl, size_t n_blocks, const FramePlan &p, int nt, int relay_k, hipStream_t st) {
+static int write_timeline(const char *file, const DevBuf &tl, size_t n_blocks, const GridParams &g, int nt, hipStream_t st) {
     std::vector<unsigned long long> rec(n_blocks * 4);
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipMemcpy(rec.data(), tl.p, rec.size() * 8, hipMemcpyDeviceToHost));
     if (FILE *f = std::fopen(file, "wb")) {
         // (a relaying launch: relay_k << 32 | extent << 40 | order << 41 | relay_cap in the xcd_tiles word, which is 0 for every
         // tile-order launch)
-        const unsigned long long form = (unsigned long long)relay_k | (unsigned long long)p.relay_extent << 8 | (unsigned long long)p.relay_order << 9;
-        const unsigned long long head[4] = {n_blocks, (unsigned long long)nt, (unsigned long long)p.chunks,
-                                            relay_k > 1 ? (form << 32 | (unsigned long long)p.relay_cap) : (unsigned long long)p.xcd_tiles};
+        const unsigned long long form = (unsigned long long)g.relay_k | (unsigned long long)g.relay_extent << 8 | (unsigned long long)g.relay_order << 9;
+        const unsigned long long head[4] = {n_blocks, (unsigned long long)nt, (unsigned long long)g.chunks,
+                                            g.relay_k > 1 ? (form << 32 | (unsigned long long)g.relay_cap) : (unsigned long long)g.xcd_tiles};
         std::fwrite(head, 8, 4, f);
         std::fwrite(rec.data(), 8, rec.size(), f);
         std::fclose(f);
@@ -1152,14 +1004,7 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     ON_DEVICE(s->device);
     const EyeKnobs kn = eye_knobs();
     const EyeLaunch L = eye_launch(s, cam, grid, kn, false);
-    const DeviceScene &d = s->dev;
-    // the sample relay: the one-launch tile-order form of the PAIR variants (the conditions of order_tiles below, and no second
-    // launch for the class-3 tiles); frame_plan adds the sample count, the tile count and the flags
-    const bool relay_form = L.form == EyeForm::Image && L.k.pair && L.k.nt == kThreads && s->order_ok &&
-                            !(grid->flags & (CGRT_GRID_NO_TILE_ORDER | CGRT_GRID_SPLIT_SAMPLES)) && !diffuse_wanted(s, cam, grid, L, kn);
-    const FrameInputs in{*grid, *cam, L.form == EyeForm::Sched, L.k.spill, L.k.stats, L.k.glass, L.k.nt, d.has_mesh != 0,
-                         d.has_bezier != 0, d.prim_finish != 0, d.light_ok != 0, d.prim_obj, kn, s->mem_total, s->n_cu,
-                         L.k.nt == 64 ? kBezWaves : (L.k.trees ? kSchedTreeWaves : 4), relay_form};
+    const FrameInputs in = frame_inputs(s, cam, grid, L, kn);
     FramePlan p;
     if ((rc = fit_scratch(s, in, p))) return rc;
     GridParams g = frame_params(in, p);
@@ -1167,32 +1012,14 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     if (p.heavy_blocks > 0 && (rc = probe_and_plan(s, L, kn, p, g, scratch, st, rgb, nhit, cnt))) return rc;
     p.scratch.place(g, scratch, nhit != nullptr);
     size_t n_blocks = (size_t)p.heavy_blocks + p.grid_dim;
-    s->last_relay_k = 0;
-    // image order, one workgroup per tile with all its samples, row-major: the tiles that see a mirror or glass sphere first
-    s->order_tiles = 0;
-    s->mask_wtiles = 0;
-    s->order_reused = false;
-    s->diffuse_issued = false;
-    s->diffuse_in_kernel = false;
-    // sphere masks: where a terminal-diffuse body will run (either form) over a list of at most 32 spheres, all of them in LDS
-    const bool diffuse_body = diffuse_wanted(s, cam, grid, L, kn) || (L.k.pair && !order_all_special(s->order_spheres, *cam));
-    const bool masks = diffuse_body && d.all_spheres != 0 && d.n_objs <= kSphereMaskMax && d.n_objs == d.n_lds && !(grid->flags & CGRT_GRID_NO_SPHERE_MASKS);
-    // every exit with an error from here on drops the stored order's key (order_tiles): only a call that went through leaves one
-    struct DropKey {
-        const cgrt_scene *s;
-        bool through = false;
-        bool relayed = false;
-        ~DropKey() {
-            if (!through) s->order_valid = false;
-            if (relayed && through) s->relay_dirty = false;  // (else the arrival words are zeroed before they are used again)
+    TileOrderGuard guard(s->order, s->relay);
+    if (p.order.on) {  // the tiles that see a mirror or glass sphere first; where the plan says so, their samples relayed
+        const Capturing capturing = stream_capturing(st);
+        if ((rc = order_tiles(s->order, s->dev, p, g, kn.no_order_reuse, capturing, st))) return rc;
+        if (p.relay_k > 1 && relay_prepare(s->relay, p, g, capturing, st)) {
+            guard.relayed = true;
+            n_blocks = relay_grid(p.grid_dim, p.relay_k, p.relay_cap);
         }
-    } drop_key{s};
-    if (L.form == EyeForm::Image && p.chunks == 1 && !p.xcd_tiles && L.k.nt == kThreads && s->order_ok &&
-        !(grid->flags & CGRT_GRID_NO_TILE_ORDER) && (rc = order_tiles(s, p, g, masks, kn.no_order_reuse, st)))
-        return rc;
-    if (g.tile_order && p.relay_k > 1 && relay_prepare(s, p, g, st)) {
-        drop_key.relayed = true;
-        n_blocks = relay_grid(p.grid_dim, p.relay_k, p.relay_cap);
     }
     DevBuf timeline;
     if (kn.timeline_file) {
@@ -1204,11 +1031,11 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
         hipLaunchKernelGGL(pixel_const_kernel, dim3((unsigned)p.kmax), dim3(64), 0, st, g);
         if (g.prim_len && (rc = primary_walk(s, L, g, st, cnt))) return rc;
         if ((rc = launch_eye(L, true, s->device, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) return rc;
-    } else if (g.tile_order && diffuse_wanted(s, cam, grid, L, kn)) {
+    } else if (p.order.class3 == TileOrderPlan::SecondLaunch) {
         // The list's class 0-2 entries by this launch, its class-3 entries by the terminal-diffuse variant on the second stream,
         // started behind it (fork / join events, lowest priority: the arrangement of the light-tile launch).  Where class 3
         // begins is known on the device only: both launches span the list, workgroups beyond their part leave at once.
-        const EyeLaunch DL = diffuse_launch(d, L.k.dof);
+        const EyeLaunch DL = diffuse_launch(s->dev, L.k.dof);
         if ((rc = check_eye(DL, s->device))) return rc;  // before the main launch goes out with only its part of the list
         GridParams gd = g;
         g.tile_order = kOrderFull;
@@ -1218,70 +1045,60 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
         HIP_TRY(hipStreamWaitEvent(s->aux_stream, s->ev_fork, 0));
         if ((rc = launch_eye(DL, false, s->device, gd, dim3((unsigned)n_blocks), s->aux_stream, rgb, nhit, cnt))) return rc;
         HIP_TRY(hipEventRecord(s->ev_join, s->aux_stream));
-        s->diffuse_issued = true;
     } else {
-        // The pair variant in tile order: the list's class-3 workgroups take the terminal-diffuse body inside this launch (where
-        // some tile can be of class 3 at all)
-        if (g.tile_order && L.k.pair && !order_all_special(s->order_spheres, *cam)) {
-            g.tile_order = kOrderAllDiffuse;
-            s->diffuse_in_kernel = true;
-        }
+        // The pair variant in tile order: the list's class-3 workgroups take the terminal-diffuse body inside this launch
+        if (p.order.class3 == TileOrderPlan::InKernel) g.tile_order = kOrderAllDiffuse;
         if ((rc = launch_eye(L, false, s->device, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) return rc;
     }
     if (p.chunks > 1)
         hipLaunchKernelGGL(finalize_chunks_kernel, dim3((unsigned)(((size_t)g.rows * g.W + 255) / 256)), dim3(256), 0, st, g, rgb, nhit);
     if (p.heavy_blocks > 0) hipLaunchKernelGGL(deferred_sum_kernel, dim3((unsigned)p.kmax), dim3(64), 0, st, g, rgb, nhit);  // (4)
-    if (g.light || s->diffuse_issued) HIP_TRY(hipStreamWaitEvent(st, s->ev_join, 0));  // the caller's stream continues when both launches are done
+    if (g.light || p.order.class3 == TileOrderPlan::SecondLaunch) HIP_TRY(hipStreamWaitEvent(st, s->ev_join, 0));  // the caller's stream continues when both launches are done
     const hipError_t launch_err = hipGetLastError();
-    if (g.timeline && launch_err == hipSuccess && (rc = write_timeline(kn.timeline_file, timeline, n_blocks, p, L.k.nt, g.relay_k, st))) return rc;
+    if (g.timeline && launch_err == hipSuccess && (rc = write_timeline(kn.timeline_file, timeline, n_blocks, g, L.k.nt, st))) return rc;
     if (launch_err != hipSuccess) return fail(CGRT_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(launch_err));
-    if (drop_key.relayed) {
-        HIP_TRY(hipEventRecord(s->ev_relay, st));
-        s->relay_stream = st;
-        s->relay_recorded = true;
-        s->last_relay_k = g.relay_k;
-        s->last_relay_cap = (size_t)g.relay_cap;
-        s->last_relay_slots = g.relay_slots;
-        s->last_relay_extent = g.relay_extent;
-        s->last_relay_order = g.relay_order;
-    }
-    drop_key.through = true;
+    if ((rc = guard.commit(g, st))) return rc;
     return kn.plan_dump && g.plan && !g.tile_order ? dump_plan(p, g, st) : CGRT_OK;
 }
 
+// what the last cgrt_trace_grid on the handle did (cgrt_tile_order.hpp)
+#define NEED_COMMITTED(s, args_ok)                                           \
+    if (!(s) || !(args_ok)) return fail(CGRT_ERR_INVALID, "null argument"); \
+    if (!(s)->committed) return fail(CGRT_ERR_INVALID, "scene not committed")
+
 int cgrt_scene_last_tile_order(const cgrt_scene *s, uint32_t *plan5, uint32_t *list, uint8_t *cls, int64_t cap, int64_t *n_tiles) {
-    if (!s || !n_tiles) return fail(CGRT_ERR_INVALID, "null argument");
-    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+    NEED_COMMITTED(s, n_tiles);
     ON_DEVICE(s->device);
-    const size_t n = s->order_tiles;
-    *n_tiles = (int64_t)n;
-    if (n == 0 || cap < (int64_t)n) return CGRT_OK;
-    HIP_TRY(hipDeviceSynchronize());
-    const unsigned char *base = reinterpret_cast<const unsigned char *>(s->order_buf.p);
-    if (plan5) HIP_TRY(hipMemcpy(plan5, base, (kOrderClasses + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (list) HIP_TRY(hipMemcpy(list, base + kOrderPlanWords * sizeof(uint32_t), n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (cls) HIP_TRY(hipMemcpy(cls, base + order_pad((kOrderPlanWords + n) * sizeof(uint32_t)), n, hipMemcpyDeviceToHost));
-    return CGRT_OK;
+    return last_tile_order(s->order, plan5, list, cls, cap, n_tiles);
 }
-
 int cgrt_scene_last_sphere_masks(const cgrt_scene *s, uint32_t *masks, int64_t cap, int64_t *n_wave_tiles) {
-    if (!s || !n_wave_tiles) return fail(CGRT_ERR_INVALID, "null argument");
-    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+    NEED_COMMITTED(s, n_wave_tiles);
     ON_DEVICE(s->device);
-    const size_t n_wt = s->mask_wtiles, n = s->order_tiles;
-    *n_wave_tiles = (int64_t)n_wt;
-    if (n_wt == 0 || n == 0 || !masks || cap < (int64_t)n_wt) return CGRT_OK;
-    HIP_TRY(hipDeviceSynchronize());
-    const unsigned char *base = reinterpret_cast<const unsigned char *>(s->order_buf.p);
-    HIP_TRY(hipMemcpy(masks, base + order_pad((kOrderPlanWords + n) * sizeof(uint32_t)) + order_pad(n) + order_pad(n_wt), n_wt * sizeof(uint32_t),
-                      hipMemcpyDeviceToHost));
+    return last_sphere_masks(s->order, masks, cap, n_wave_tiles);
+}
+int cgrt_scene_last_tile_order_reused(const cgrt_scene *s, int32_t *reused) {
+    NEED_COMMITTED(s, reused);
+    *reused = s->order.reused ? 1 : 0;
     return CGRT_OK;
 }
-
-int cgrt_scene_last_tile_order_reused(const cgrt_scene *s, int32_t *reused) {
-    if (!s || !reused) return fail(CGRT_ERR_INVALID, "null argument");
-    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
-    *reused = s->order_reused ? 1 : 0;
+int cgrt_scene_last_diffuse_tiles(const cgrt_scene *s, int64_t *n_tiles) {
+    NEED_COMMITTED(s, n_tiles);
+    ON_DEVICE(s->device);
+    return last_class3_tiles(s->order, TileOrderPlan::SecondLaunch, n_tiles);
+}
+int cgrt_scene_last_inkernel_diffuse_tiles(const cgrt_scene *s, int64_t *n_tiles) {
+    NEED_COMMITTED(s, n_tiles);
+    ON_DEVICE(s->device);
+    return last_class3_tiles(s->order, TileOrderPlan::InKernel, n_tiles);
+}
+int cgrt_scene_last_sample_relay(const cgrt_scene *s, int64_t *tiles, int32_t *chunks, int64_t *parked_values) {
+    NEED_COMMITTED(s, tiles && chunks && parked_values);
+    ON_DEVICE(s->device);
+    return last_sample_relay(s->order, s->relay, tiles, chunks, parked_values);
+}
+int cgrt_scene_last_relay_form(const cgrt_scene *s, int32_t *mirror, int32_t *order) {
+    NEED_COMMITTED(s, mirror && order);
+    last_relay_form(s->order, s->relay, mirror, order);
     return CGRT_OK;
 }
 
@@ -1293,54 +1110,10 @@ int cgrt_trace_grid_diffuse_variant(const cgrt_scene *s, const cgrt_camera *cam,
     const EyeKnobs kn = eye_knobs();
     const EyeLaunch L = eye_launch(s, cam, grid, kn, false);
     name[0] = 0;
-    if (diffuse_wanted(s, cam, grid, L, kn)) diffuse_name(diffuse_launch(s->dev, L.k.dof), name, cap);
+    if (frame_plan(frame_inputs(s, cam, grid, L, kn), 0).order.class3 == TileOrderPlan::SecondLaunch)
+        diffuse_name(diffuse_launch(s->dev, L.k.dof), name, cap);
     return CGRT_OK;
 }
-
-// the class-3 tiles of the last launch's order, when that launch gave them to the terminal-diffuse body in the form asked for
-static int last_class3_tiles(const cgrt_scene *s, bool in_kernel, int64_t *n_tiles) {
-    if (!s || !n_tiles) return fail(CGRT_ERR_INVALID, "null argument");
-    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
-    ON_DEVICE(s->device);
-    *n_tiles = 0;
-    if (!(in_kernel ? s->diffuse_in_kernel : s->diffuse_issued) || s->order_tiles == 0) return CGRT_OK;
-    uint32_t plan[kOrderClasses + 1];
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(plan, s->order_buf.p, sizeof(plan), hipMemcpyDeviceToHost));
-    *n_tiles = (int64_t)plan[kOrderClasses] - (int64_t)plan[3];
-    return CGRT_OK;
-}
-int cgrt_scene_last_sample_relay(const cgrt_scene *s, int64_t *tiles, int32_t *chunks, int64_t *parked_values) {
-    if (!s || !tiles || !chunks || !parked_values) return fail(CGRT_ERR_INVALID, "null argument");
-    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
-    ON_DEVICE(s->device);
-    *tiles = *parked_values = 0;
-    *chunks = 0;
-    if (s->last_relay_k <= 1 || s->order_tiles == 0) return CGRT_OK;
-    uint32_t plan[kOrderClasses + 1];
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(plan, s->order_buf.p, sizeof(plan), hipMemcpyDeviceToHost));
-    const size_t n_split = relay_split_entries(plan[2], plan[3], (uint32_t)s->last_relay_cap, s->last_relay_extent);  // the entries in fact split
-    *tiles = (int64_t)n_split;
-    if (n_split == 0) return CGRT_OK;
-    *chunks = s->last_relay_k;
-    // rcount[tile][chunk - 1][thread] of the first n_split tiles is one run of words
-    std::vector<uint32_t> cnt(n_split * (size_t)(s->last_relay_k - 1) * kRelayThreads);
-    const RelayLayout rl = relay_layout(s->last_relay_cap, s->last_relay_k, s->last_relay_slots);
-    HIP_TRY(hipMemcpy(cnt.data(), reinterpret_cast<const unsigned char *>(s->relay_buf.p) + rl.rcount, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (uint32_t c : cnt) *parked_values += (int64_t)c;
-    return CGRT_OK;
-}
-int cgrt_scene_last_relay_form(const cgrt_scene *s, int32_t *mirror, int32_t *order) {
-    if (!s || !mirror || !order) return fail(CGRT_ERR_INVALID, "null argument");
-    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
-    const bool relayed = s->last_relay_k > 1 && s->order_tiles != 0;
-    *mirror = relayed ? (s->last_relay_extent == kRelayMirror ? 1 : 0) : -1;
-    *order = relayed ? s->last_relay_order : -1;
-    return CGRT_OK;
-}
-int cgrt_scene_last_diffuse_tiles(const cgrt_scene *s, int64_t *n_tiles) { return last_class3_tiles(s, false, n_tiles); }
-int cgrt_scene_last_inkernel_diffuse_tiles(const cgrt_scene *s, int64_t *n_tiles) { return last_class3_tiles(s, true, n_tiles); }
 
 }  // extern "C"
 

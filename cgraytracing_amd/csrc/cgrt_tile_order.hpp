@@ -1,0 +1,282 @@
+// The host side of a sphere scene's tile-order launch: what the handle keeps for it between launches (the order buffer and the
+// sample relay's area, each with the event and stream that order their users), the two steps that prepare a launch
+// (order_tiles, relay_prepare), the guard that closes a cgrt_trace_grid over both, and what the cgrt_scene_last_* read-backs
+// report.  What a launch does is frame_plan's decision (TileOrderPlan, cgrt_frame.h).  Part of libcgrt.so (cgrt_hip.hip).
+#ifndef CGRT_TILE_ORDER_HPP
+#define CGRT_TILE_ORDER_HPP
+
+enum class Capturing { None, Active, Unknown };
+static Capturing stream_capturing(hipStream_t st) {
+    hipStreamCaptureStatus c = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &c) != hipSuccess) {
+        (void)hipGetLastError();
+        return Capturing::Unknown;
+    }
+    return c == hipStreamCaptureStatusNone ? Capturing::None : Capturing::Active;
+}
+
+// Tile order of image-order launches (tile_order_kernel): the scene's reflecting / refracting spheres (read at commit; ok: the
+// scene is spheres and planes with 1..kOrderSpheresMax of them), the order buffer (TileOrderLayout) -- launch scratch like the
+// handle's `scratch`, kept apart so that the frame plan's layout stays what it is -- and what the last cgrt_trace_grid did: the
+// tiles it ordered (0: none), the wave tiles it wrote sphere masks for (0: none), where the parts lie, and who rendered class 3.
+// What the buffer holds: the order depends on nothing but Key, so a launch with the key of the buffer's contents runs no
+// ordering kernel (reused).  ev is recorded behind the kernel on `stream`; a reusing launch on another stream waits for it.
+// commit_gen: this commit's number.
+struct TileOrderState {
+    OrderSpheres spheres{};
+    bool ok = false;
+    GrowBuf buf;
+    struct Key {
+        double cam[3], half_width, focus_plane, lens_radius;
+        int32_t W, H, rows, row_offset, stripe_rows, stripe_rank, stripe_nranks, masks;
+        uint64_t commit_gen;
+        const void *buf;
+    };
+    static_assert(sizeof(Key) == 96, "Key is compared as bytes: no padding");
+    Key key{};
+    uint64_t commit_gen = 0;
+    bool valid = false, reused = false;
+    bool captured = false;  // a launch on this handle was captured into a graph: its replays rewrite the buffer at times the handle does not see, so nothing is reused any more
+    hipEvent_t ev = nullptr;
+    hipStream_t stream = nullptr;
+    size_t tiles = 0, mask_wtiles = 0;
+    TileOrderLayout at;
+    TileOrderPlan::Class3 class3 = TileOrderPlan::None;
+
+    void begin_launch() {
+        tiles = mask_wtiles = 0;
+        reused = false;
+        class3 = TileOrderPlan::None;
+    }
+    void release() {
+        buf.release();
+        if (ev) (void)hipEventDestroy(ev);
+        ev = nullptr;
+    }
+    template <class T> int read(const Region &r, T *dst, size_t count) const {
+        HIP_TRY(hipMemcpy(dst, reinterpret_cast<const unsigned char *>(buf.p) + r.at, count * sizeof(T), hipMemcpyDeviceToHost));
+        return CGRT_OK;
+    }
+};
+
+// The sample relay's area (cgrt_relay.h; launch scratch like `scratch`, allocated by the first launch that relays, sized by the
+// largest): refused -- the smallest size the device has refused (such a launch goes unrelayed); zeroed -- the arrival words
+// known to be 0 (the kernel leaves them so; a launch that failed on the way does not vouch for it: dirty); ev is recorded
+// behind a relaying launch on `stream`, and a relaying launch on another stream waits for it -- the area is one.  last: what the
+// last cgrt_trace_grid relayed with (k == 0: it did not).
+struct RelayState {
+    GrowBuf buf;
+    size_t refused = 0, zeroed = 0;
+    bool dirty = false;
+    hipEvent_t ev = nullptr;
+    hipStream_t stream = nullptr;
+    bool recorded = false;
+    struct Last {
+        int k = 0;
+        size_t cap = 0;
+        int slots = 0, extent = 0, order = 0;
+    } last;
+
+    void begin_launch() { last = Last{}; }
+    void release() {
+        buf.release();
+        if (ev) (void)hipEventDestroy(ev);
+        ev = nullptr;
+    }
+};
+
+// The tile order of an image-order launch over a scene with reflecting or refracting spheres (tile_order_kernel, cgrt_eye.hpp):
+// one small launch in front of the eye launch, on its stream, that lists the tiles the costly ones first; g then maps the
+// eye launch's workgroups through the list.  The buffer is launch scratch of the handle, written and read on this stream.
+// p.order.masks: the launch also writes the wave tiles' sphere masks (GridParams::wmask) for the terminal-diffuse body.
+// The kernel reads the camera, the frame geometry (W, H, rows, row offset, stripe) and the committed scene, nothing else: when
+// the buffer still holds the result for exactly these (TileOrderState::Key -- the passes of a progressive render, the frames of
+// a still camera) nothing is launched and g points at it.  The eye launch only reads the buffer (plan[0..4], the list, the
+// masks; plan[kOrderArrived] is back at 0 when the kernel ends), so it is as the kernel left it.  The contents are not trusted
+// beyond a commit, a reallocation, a cgrt_trace_grid that returned an error (TileOrderGuard drops the key on every such exit) or
+// a stream capture (a captured launch runs later, or never, and again at every replay: from the first capture on, the handle
+// neither reuses nor leaves a key; a stream whose state cannot be asked counts as captured).
+// One handle serves one stream at a time (cgrt.h, "Threading"): a launch with another key rewrites the buffer, and the event only
+// orders a reusing launch behind the kernel that wrote it, not a rewrite behind another stream's readers.
+// no_reuse (CGRT_NO_ORDER_REUSE=1, a measurement aid): every launch runs the kernel.
+static int order_tiles(TileOrderState &o, const DeviceScene &dev, const FramePlan &p, GridParams &g, bool no_reuse, Capturing capturing,
+                       hipStream_t st) {
+    const int tiles_x = (g.W + kTileW - 1) / kTileW, tiles_y = (g.rows + kTileH - 1) / kTileH;
+    const size_t n = (size_t)tiles_x * tiles_y;
+    const TileOrderLayout at = tile_order_layout(n, p.n_wt);
+    const bool grown = at.total > o.buf.cap, masks = p.order.masks;
+    if (grown) o.valid = false;
+    if (o.buf.need(at.total) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(CGRT_ERR_DEVICE, "cannot allocate launch scratch (tile order)");
+    }
+    unsigned char *base = reinterpret_cast<unsigned char *>(o.buf.p);
+    uint32_t *plan = at.plan.in<uint32_t>(base), *list = at.list.in<uint32_t>(base);
+    uint32_t *wmask = masks ? at.wmask.in<uint32_t>(base) : nullptr;
+    const TileOrderState::Key key{{g.cam[0], g.cam[1], g.cam[2]}, g.half_width, g.focus_plane, g.lens_radius, g.W, g.H, g.rows, g.row_offset,
+                                  g.stripe_rows, g.stripe_rank, g.stripe_nranks, masks ? 1 : 0, o.commit_gen, o.buf.p};
+    if (capturing != Capturing::None) o.captured = true;
+    const bool plain = !o.captured && !no_reuse;
+    o.reused = plain && o.valid && std::memcmp(&key, &o.key, sizeof(key)) == 0;
+    if (o.reused) {
+        if (st != o.stream) HIP_TRY(hipStreamWaitEvent(st, o.ev, 0));
+    } else {
+        o.valid = false;
+        if (grown) HIP_TRY(hipMemsetAsync(plan, 0, at.plan.bytes, st));  // plan[kOrderArrived]
+        const unsigned blocks = (unsigned)std::min((p.n_wt + 1023) / 1024, (size_t)64);
+        hipLaunchKernelGGL(tile_order_kernel, dim3(blocks), dim3(1024), 0, st, g, o.spheres, dev, tiles_x, tiles_y, plan, list,
+                           at.tile_cls.in<unsigned char>(base), at.wave_cls.in<unsigned char>(base), wmask);
+        if (plain && hipPeekAtLastError() == hipSuccess) {
+            if (!o.ev && hipEventCreateWithFlags(&o.ev, hipEventDisableTiming) != hipSuccess) {
+                (void)hipGetLastError();
+                o.ev = nullptr;
+            }
+            if (o.ev && hipEventRecord(o.ev, st) == hipSuccess) {
+                o.key = key;
+                o.stream = st;
+                o.valid = true;
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+    }
+    g.plan = plan;
+    g.border = list;
+    g.wmask = wmask;
+    g.tile_order = kOrderAll;
+    o.tiles = n;
+    o.mask_wtiles = masks ? p.n_wt : 0;
+    o.at = at;
+    o.class3 = p.order.class3;
+    return CGRT_OK;
+}
+
+// The sample relay of a tile-order launch of the PAIR variants (cgrt_relay.h; the plan has relay_k > 1): the handle's relay area
+// and g's relay fields.  Returns false -- the launch goes unrelayed, which is no error -- when the stream is being captured (the
+// area, its event and the handle's record of both belong to launches that run now) or its state cannot be asked, or the area
+// cannot be had.  The arrival words are 0 whenever no launch is in flight: zeroed here when the area is new or grown, when more
+// of them are needed than were zeroed, or after a launch that did not go through; reset by the kernel otherwise.
+static bool relay_prepare(RelayState &r, const FramePlan &p, GridParams &g, Capturing capturing, hipStream_t st) {
+    if (capturing != Capturing::None) return false;
+    if (r.refused && p.relay_bytes >= r.refused) return false;
+    if (p.relay_bytes > r.buf.cap) {
+        // the launches that use the old area are through before it is freed
+        if (r.recorded && hipEventSynchronize(r.ev) != hipSuccess) (void)hipGetLastError();
+        r.zeroed = 0;
+        if (r.buf.need(p.relay_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            r.refused = p.relay_bytes;
+            return false;
+        }
+    }
+    if (!r.ev && hipEventCreateWithFlags(&r.ev, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        r.ev = nullptr;
+        return false;
+    }
+    if (r.recorded && st != r.stream && hipStreamWaitEvent(st, r.ev, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    if (r.dirty || p.relay_cap > r.zeroed) {
+        if (hipMemsetAsync(r.buf.p, 0, p.relay_cap * sizeof(uint32_t), st) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+    }
+    r.zeroed = p.relay_cap;  // (the words beyond this launch's lie in its arrays)
+    r.dirty = true;          // until the launch is through (TileOrderGuard::commit)
+    g.relay = reinterpret_cast<unsigned char *>(r.buf.p);
+    g.relay_k = p.relay_k;
+    g.relay_chunk_spp = p.relay_chunk_spp;
+    g.relay_cap = (int32_t)p.relay_cap;
+    g.relay_slots = p.relay_slots;
+    g.relay_extent = p.relay_extent;
+    g.relay_order = p.relay_order;
+    return true;
+}
+
+// A cgrt_trace_grid's hold on both states, from the point where it starts to touch them: the last launch's record is cleared,
+// and every exit without commit drops the stored order's key -- only a call that went through leaves one -- and leaves the
+// relay area dirty, so that its arrival words are zeroed before they are used again.
+struct TileOrderGuard {
+    TileOrderState &order;
+    RelayState &relay;
+    bool relayed = false, through = false;
+    TileOrderGuard(TileOrderState &o, RelayState &r) : order(o), relay(r) {
+        order.begin_launch();
+        relay.begin_launch();
+    }
+    TileOrderGuard(const TileOrderGuard &) = delete;
+    TileOrderGuard &operator=(const TileOrderGuard &) = delete;
+    ~TileOrderGuard() {
+        if (!through) order.valid = false;
+    }
+    // the launch g went out on st without an error
+    int commit(const GridParams &g, hipStream_t st) {
+        if (relayed) {
+            HIP_TRY(hipEventRecord(relay.ev, st));
+            relay.stream = st;
+            relay.recorded = true;
+            relay.last = RelayState::Last{g.relay_k, (size_t)g.relay_cap, g.relay_slots, g.relay_extent, g.relay_order};
+            relay.dirty = false;
+        }
+        through = true;
+        return CGRT_OK;
+    }
+};
+
+// ---- what the last cgrt_trace_grid on the handle did (the cgrt_scene_last_* entry points, on the scene's device) ----
+static int last_tile_order(const TileOrderState &o, uint32_t *plan5, uint32_t *list, uint8_t *cls, int64_t cap, int64_t *n_tiles) {
+    const size_t n = o.tiles;
+    *n_tiles = (int64_t)n;
+    if (n == 0 || cap < (int64_t)n) return CGRT_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    int rc = CGRT_OK;
+    if (plan5 && (rc = o.read(o.at.plan, plan5, kOrderClasses + 1))) return rc;
+    if (list && (rc = o.read(o.at.list, list, n))) return rc;
+    return cls ? o.read(o.at.tile_cls, cls, n) : CGRT_OK;
+}
+static int last_sphere_masks(const TileOrderState &o, uint32_t *masks, int64_t cap, int64_t *n_wave_tiles) {
+    const size_t n_wt = o.mask_wtiles;
+    *n_wave_tiles = (int64_t)n_wt;
+    if (n_wt == 0 || o.tiles == 0 || !masks || cap < (int64_t)n_wt) return CGRT_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    return o.read(o.at.wmask, masks, n_wt);
+}
+// the class-3 tiles of the last launch's order, when that launch gave them to the terminal-diffuse body in the form asked for
+static int last_class3_tiles(const TileOrderState &o, TileOrderPlan::Class3 form, int64_t *n_tiles) {
+    *n_tiles = 0;
+    if (o.class3 != form || o.tiles == 0) return CGRT_OK;
+    uint32_t plan[kOrderClasses + 1];
+    HIP_TRY(hipDeviceSynchronize());
+    if (int rc = o.read(o.at.plan, plan, kOrderClasses + 1)) return rc;
+    *n_tiles = (int64_t)plan[kOrderClasses] - (int64_t)plan[3];
+    return CGRT_OK;
+}
+static int last_sample_relay(const TileOrderState &o, const RelayState &r, int64_t *tiles, int32_t *chunks, int64_t *parked_values) {
+    *tiles = *parked_values = 0;
+    *chunks = 0;
+    const RelayState::Last &l = r.last;
+    if (l.k <= 1 || o.tiles == 0) return CGRT_OK;
+    uint32_t plan[kOrderClasses + 1];
+    HIP_TRY(hipDeviceSynchronize());
+    if (int rc = o.read(o.at.plan, plan, kOrderClasses + 1)) return rc;
+    const size_t n_split = relay_split_entries(plan[2], plan[3], (uint32_t)l.cap, l.extent);  // the entries in fact split
+    *tiles = (int64_t)n_split;
+    if (n_split == 0) return CGRT_OK;
+    *chunks = l.k;
+    // rcount[tile][chunk - 1][thread] of the first n_split tiles is one run of words
+    std::vector<uint32_t> cnt(n_split * (size_t)(l.k - 1) * kRelayThreads);
+    const RelayLayout rl = relay_layout(l.cap, l.k, l.slots);
+    HIP_TRY(hipMemcpy(cnt.data(), reinterpret_cast<const unsigned char *>(r.buf.p) + rl.rcount, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (uint32_t c : cnt) *parked_values += (int64_t)c;
+    return CGRT_OK;
+}
+static void last_relay_form(const TileOrderState &o, const RelayState &r, int32_t *mirror, int32_t *order) {
+    const bool relayed = r.last.k > 1 && o.tiles != 0;
+    *mirror = relayed ? (r.last.extent == kRelayMirror ? 1 : 0) : -1;
+    *order = relayed ? r.last.order : -1;
+}
+
+#endif

@@ -1,6 +1,6 @@
 // The host side of cgrt_trace_grid (cgrt_frame.h: frame_plan, max_heavy_tiles, fit_heavy_tiles, frame_params,
-// ScratchLayout::place, eye_knobs): sample chunks, tile counts, heavy-tile capacity, scheduling and the scratch layout, against
-// values written out by hand from the rules.  CPU build under ASan + UBSan, driven by tests/test_frame_plan_host.py.
+// ScratchLayout::place, tile_order_layout, eye_knobs): sample chunks, tile counts, heavy-tile capacity, scheduling, the scratch
+// layout, the tile order of a sphere scene and its buffer's layout, against values written out by hand from the rules.  CPU build under ASan + UBSan, driven by tests/test_frame_plan_host.py.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -295,6 +295,167 @@ static void scheduled() {
     CHECK_EQ(g.items_per_tile, 1);
 }
 
+// 200 x 117 at 32 spp, depth 5: the image-order launch of a glass sphere scene -- ten spheres and nothing else, all in LDS, two of
+// them special, some tile clear of both -- by the PAIR variant, on a handle with its second stream.  7 x 15 = 105 tiles.
+static FrameInputs spheres(int W = 200, int rows = 117, int spp = 32) {
+    FrameInputs in = frame(W, rows, spp);
+    in.sched = false;
+    in.has_mesh = false;
+    in.image = in.sph = in.pair = in.order_ok = in.aux_stream = in.all_spheres = true;
+    in.n_objs = in.n_lds = 10;
+    return in;
+}
+#define CHECK_ORDER(in_, on_, class3_, masks_, relay_k_)          \
+    do {                                                          \
+        const FramePlan q_ = frame_plan(in_, 0);                  \
+        CHECK_EQ(q_.order.on, on_);                               \
+        CHECK_EQ(q_.order.class3, TileOrderPlan::class3_);        \
+        CHECK_EQ(q_.order.masks, masks_);                         \
+        CHECK_EQ(q_.relay_k, relay_k_);                           \
+    } while (0)
+
+static void tile_order() {
+    FrameInputs in = spheres();
+    CHECK_EQ(frame_plan(in, 0).tile_blocks, 105);
+    // the pair variant: class 3 inside the kernel, with masks; 105 tiles are fewer than 4 x 256, so the relay only on request
+    CHECK_ORDER(in, 1, InKernel, 1, 1);
+    in.grid.flags = CGRT_GRID_SAMPLE_RELAY;
+    CHECK_ORDER(in, 1, InKernel, 1, 2);
+    CHECK_EQ(frame_plan(in, 0).relay_extent, kRelayGlass);
+    CHECK_EQ(frame_plan(in, 0).relay_order, kRelayChunksFirst);
+    {   // 1920 x 1080: 8100 tiles take every workgroup slot of 256 CUs: relayed by default, in the measured form
+        const FramePlan p = frame_plan(spheres(1920, 1080), 0);
+        CHECK_EQ(p.tile_blocks, 8100);
+        CHECK_EQ(p.order.on, 1);
+        CHECK_EQ(p.order.class3, TileOrderPlan::InKernel);
+        CHECK_EQ(p.order.masks, 1);
+        CHECK_EQ(p.relay_k, 2);
+        CHECK_EQ(p.relay_chunk_spp, 16);
+        CHECK_EQ(p.relay_extent, kRelayMirror);
+        CHECK_EQ(p.relay_order, kRelayInterleaved);
+    }
+    // the second launch for class 3, on request: one launch each for the two parts of the list, so nothing is relayed
+    in.grid.flags = CGRT_GRID_DIFFUSE_TILES | CGRT_GRID_SAMPLE_RELAY;
+    CHECK_ORDER(in, 1, SecondLaunch, 1, 1);
+    {
+        FrameInputs big = spheres(1920, 1080);
+        big.grid.flags = CGRT_GRID_DIFFUSE_TILES;
+        CHECK_ORDER(big, 1, SecondLaunch, 1, 1);
+    }
+    // ... which needs the second stream, and is not taken for a timeline (one launch): the pair variant's own body then
+    in.grid.flags = CGRT_GRID_DIFFUSE_TILES;
+    in.aux_stream = false;
+    CHECK_ORDER(in, 1, InKernel, 1, 1);
+    in.aux_stream = true;
+    in.knobs.timeline_file = "tl.bin";
+    CHECK_ORDER(in, 1, InKernel, 1, 1);
+    in.knobs.timeline_file = nullptr;
+    CHECK_ORDER(in, 1, SecondLaunch, 1, 1);
+    // ... nor by a STATS or a SPILL kernel
+    in.stats = true;
+    CHECK_ORDER(in, 1, InKernel, 1, 1);
+    in.stats = false;
+    in.spill = true;
+    CHECK_ORDER(in, 1, InKernel, 1, 1);
+    in.spill = false;
+    // no tile order on request: row-major, nothing for class 3, no masks, no relay -- whatever kernel eye_launch chose
+    for (const int32_t f : {0, (int32_t)CGRT_GRID_DIFFUSE_TILES, (int32_t)CGRT_GRID_SAMPLE_RELAY}) {
+        in.grid.flags = CGRT_GRID_NO_TILE_ORDER | f;
+        CHECK_EQ(in.pair, 1);
+        CHECK_ORDER(in, 0, None, 0, 1);
+    }
+    // split samples: two chunks of 16, which the tile order does not serve
+    in.grid.flags = CGRT_GRID_SPLIT_SAMPLES;
+    CHECK_EQ(frame_plan(in, 0).chunks, 2);
+    CHECK_ORDER(in, 0, None, 0, 1);
+    in.grid.flags = CGRT_GRID_SPLIT_SAMPLES | CGRT_GRID_DIFFUSE_TILES | CGRT_GRID_SAMPLE_RELAY;
+    CHECK_ORDER(in, 0, None, 0, 1);
+    // asked for with fewer than 32 samples: one chunk in tile order, but neither the second launch nor (at any sample count) the relay
+    in.grid.spp = 31;
+    CHECK_EQ(frame_plan(in, 0).chunks, 1);
+    CHECK_ORDER(in, 1, InKernel, 1, 1);
+    // a mirror-only sphere scene (no PAIR variant): class 3 by the second launch or like every other tile, then without masks
+    FrameInputs mi = spheres();
+    mi.glass = mi.pair = false;
+    CHECK_ORDER(mi, 1, None, 0, 1);
+    mi.grid.flags = CGRT_GRID_SAMPLE_RELAY;  // the relay is the PAIR variant's
+    CHECK_ORDER(mi, 1, None, 0, 1);
+    mi.grid.flags = CGRT_GRID_DIFFUSE_TILES;
+    CHECK_ORDER(mi, 1, SecondLaunch, 1, 1);
+    // no tile can be of class 3: no diffuse body in any form, no masks; the relay stays
+    for (FrameInputs a : {spheres(), mi}) {
+        a.all_special = true;
+        for (const int32_t f : {0, (int32_t)CGRT_GRID_DIFFUSE_TILES}) {
+            a.grid.flags = f;
+            CHECK_ORDER(a, 1, None, 0, 1);
+        }
+    }
+    in = spheres();
+    in.all_special = true;
+    in.grid.flags = CGRT_GRID_SAMPLE_RELAY;
+    CHECK_ORDER(in, 1, None, 0, 2);
+    // masks: at most 32 objects, all of them spheres, all of them in LDS, and not switched off
+    in = spheres();
+    in.n_objs = in.n_lds = 32;
+    CHECK_ORDER(in, 1, InKernel, 1, 1);
+    in.n_objs = in.n_lds = 33;
+    CHECK_ORDER(in, 1, InKernel, 0, 1);
+    in.n_objs = 32;
+    in.n_lds = 31;
+    CHECK_ORDER(in, 1, InKernel, 0, 1);
+    in.n_lds = 32;
+    in.all_spheres = false;
+    CHECK_ORDER(in, 1, InKernel, 0, 1);
+    in.all_spheres = true;
+    in.grid.flags = CGRT_GRID_NO_SPHERE_MASKS;
+    CHECK_ORDER(in, 1, InKernel, 0, 1);
+    in.grid.flags = CGRT_GRID_NO_SPHERE_MASKS | CGRT_GRID_DIFFUSE_TILES;
+    CHECK_ORDER(in, 1, SecondLaunch, 0, 1);
+    // the tile order is for 256-thread workgroups of an image-order launch over row-major tiles of a scene it can order
+    in = spheres();
+    in.grid.flags = CGRT_GRID_DIFFUSE_TILES | CGRT_GRID_SAMPLE_RELAY;
+    FrameInputs off = in;
+    off.nt = 64;
+    CHECK_ORDER(off, 0, None, 0, 1);
+    off = in;
+    off.order_ok = false;
+    CHECK_ORDER(off, 0, None, 0, 1);
+    off = in;
+    off.image = false;
+    CHECK_ORDER(off, 0, None, 0, 1);
+    off = in;
+    off.has_mesh = true;  // XCD super-tiles
+    CHECK_EQ(frame_plan(off, 0).xcd_tiles, 1);
+    CHECK_ORDER(off, 0, None, 0, 1);
+}
+
+// plan[8] and the list share the first part; every part starts on 256 bytes
+static void order_layout() {
+    const struct {
+        size_t n, n_wt, tile_cls, wave_cls, wmask, total;
+    } cases[] = {
+        {1, 1, 256, 512, 768, 1024},      // 36, 1, 1 and 4 bytes: a 256 each
+        {28, 60, 256, 512, 768, 1024},    // 144, 28, 60 and 240 bytes
+        // 32 672 -> 128 x 256; 8 160 -> 32 x 256; 32 640 -> 128 x 256; 130 560 = 510 x 256
+        {8160, 32640, 32768, 32768 + 8192, 32768 + 8192 + 32768, 204288},
+    };
+    for (const auto &c : cases) {
+        const TileOrderLayout L = tile_order_layout(c.n, c.n_wt);
+        CHECK_EQ(L.plan.at, 0);
+        CHECK_EQ(L.plan.bytes, 32);
+        CHECK_EQ(L.list.at, 32);
+        CHECK_EQ(L.list.bytes, 4 * c.n);
+        CHECK_EQ(L.tile_cls.at, c.tile_cls);
+        CHECK_EQ(L.tile_cls.bytes, c.n);
+        CHECK_EQ(L.wave_cls.at, c.wave_cls);
+        CHECK_EQ(L.wave_cls.bytes, c.n_wt);
+        CHECK_EQ(L.wmask.at, c.wmask);
+        CHECK_EQ(L.wmask.bytes, 4 * c.n_wt);
+        CHECK_EQ(L.wmask.at % 4, 0);
+        CHECK_EQ(L.total, c.total);
+    }
+}
+
 static void fitting() {
     const FrameInputs in = frame();
     const size_t need = frame_plan(in, 8152).scratch.total;
@@ -338,6 +499,8 @@ int main() {
     scratch_layout();
     scheduled();
     fitting();
+    tile_order();
+    order_layout();
     knobs();
     std::printf("ok: %d failed checks\n", g_failed);
     return g_failed != 0;

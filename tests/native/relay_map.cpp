@@ -158,7 +158,7 @@ int main() {
         in.n_cu = 256;
         in.waves_per_simd = 4;
         CHECK_EQ(frame_plan(in, 0).relay_k, 1);  // not a relay launch
-        in.relay = true;
+        in.image = in.sph = in.pair = in.order_ok = true;  // the PAIR variant in tile order
         {   // by default two chunks: 32 samples each, 512 slots, 3.15 MB a tile
             const FramePlan q = frame_plan(in, 0);
             CHECK_EQ(q.relay_k, 2);

@@ -156,7 +156,7 @@ int main() {
         in.mem_total = 288000000000ull;
         in.n_cu = 256;
         in.waves_per_simd = 4;
-        in.relay = true;
+        in.image = in.sph = in.pair = in.order_ok = true;  // the PAIR variant in tile order
         CHECK_EQ(in.knobs.relay_mirror, -1);
         CHECK_EQ(in.knobs.relay_order, -1);
         {   // the default launch: the measured form

@@ -140,3 +140,39 @@ def test_camera_inside_a_grown_bound(gpu_ready, orc):
 
 def test_diffuse_only_scene_takes_no_extra_launch(gpu_ready):
     _both(scenes.scene_c1(), W0, H0, 8, scenes.cam_dof(), expect_order=False)
+
+
+def test_row_major_launch_between_two_relayed_ones(gpu_ready):
+    """One handle: a relayed, masked launch with class 3 inside the kernel, then a row-major launch, then the first again.  Every
+    read-back of the row-major launch says "none", and the third launch reports what the first did -- from the order the buffer
+    still holds, which the launch between them did not touch -- with the same bits."""
+    import cgraytracing_amd as cg
+    cam = scenes.cam_dof()
+    sc = cg.Scene(scenes.scene_c2())
+
+    def report():
+        return dict(order=sc.last_tile_order(), masks=sc.last_sphere_masks(), reused=sc.last_tile_order_reused(),
+                    relay=sc.last_sample_relay(), form=sc.last_relay_form(), diffuse=sc.last_diffuse_tiles(),
+                    inkernel=sc.last_inkernel_diffuse_tiles())
+    try:
+        first, did = _launch(sc, W0, H0, 32, cam, True, sample_relay=True), report()
+        _launch(sc, W0, H0, 4, cam, False)
+        none = report()
+        again, did_again = _launch(sc, W0, H0, 32, cam, True, sample_relay=True), report()
+    finally:
+        sc.close()
+    _check_order(did["order"], 7, 15)
+    assert did["masks"] is not None and len(did["masks"]) == 13 * 30
+    assert did["relay"]["tiles"] == did["order"]["plan"][2] > 0 and did["relay"]["chunks"] == 2 and did["relay"]["parked_values"] > 0
+    assert did["form"] == dict(mirror=False, order="chunks_first")
+    assert did["diffuse"] == 0 and did["inkernel"] == did["order"]["plan"][4] - did["order"]["plan"][3] > 0
+    assert not did["reused"]
+    assert none == dict(order=None, masks=None, reused=False, relay=dict(tiles=0, chunks=0, parked_values=0), form=None, diffuse=0,
+                        inkernel=0)
+    assert did_again["reused"]
+    for k in ("plan", "list", "cls"):
+        assert np.array_equal(did_again["order"][k], did["order"][k])
+    assert np.array_equal(did_again["masks"], did["masks"])
+    assert all(did_again[k] == did[k] for k in ("relay", "form", "diffuse", "inkernel"))
+    for a, b, what in zip(first, again, ("rgb", "nhit", "counters")):
+        assert np.array_equal(a, b), "%s differs between the first launch and its repeat" % what
