@@ -1,6 +1,7 @@
 // The eye pass: trace_grid_kernel and the function-level probe kernel.  Part of libcgrt.so (cgrt_hip.hip).
 #ifndef CGRT_EYE_HPP
 #define CGRT_EYE_HPP
+#include "cgrt_lens_stage.h"
 #include "cgrt_scene_walk.hpp"
 #include "cgrt_sphere_mask.h"
 
@@ -105,8 +106,10 @@ struct RelayWg {
 // PARK (PAIR variants, chunks >= 1 of a relayed tile): a Hitpoint value is not added but stored, slot after slot, in the lane's
 // stream of the relay area; the body keeps no sums.  A relayed workgroup (rw.slot >= 0; PAIR with or without PARK) leaves its
 // sums or counts in the area, and the last of the tile's workgroups to arrive adds them up in chunk order and stores the pixels.
+// LSTAGE (DIFF with DOF, the body inside the PAIR variants' launch only): with g.lens_batch the wave stages its lens draws in
+// batches (cgrt_lens_stage.h), in the part of the launch's LDS that holds the PAIR body's pending-ray levels.
 template <bool TREES, bool BEZ, bool DOF, bool GLASS, bool SPH, bool STATS, bool HPS, int NT, bool HEAVY, bool SPILL = false, bool HFONLY = false,
-          bool DIFF = false, bool PAIR = false, bool PARK = false>
+          bool DIFF = false, bool PAIR = false, bool PARK = false, bool LSTAGE = false>
 __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const GridParams &g, float *__restrict__ rgb,
                                                 uint32_t *__restrict__ nhit_out, unsigned long long *__restrict__ counters,
                                                 const HitpointSink &hps, int tile_block, int tile_grid, const RelayWg rw = RelayWg{}) {
@@ -114,6 +117,10 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
     static_assert(!PARK || (PAIR && NT == kRelayThreads), "PARK: a relayed tile's later chunks");
     static_assert(!DIFF || (SPH && !GLASS && !HPS && !HEAVY && !STATS && !SPILL), "DIFF: the sphere loop, first hits only");
     static_assert(!PAIR || (SPH && GLASS && !HPS && !HEAVY && !STATS && !SPILL), "PAIR: the glass sphere variants of the tile order");
+    static_assert(!LSTAGE || (DIFF && DOF && !PAIR), "LSTAGE: the thin-lens terminal-diffuse body inside a PAIR launch");
+    // (the launch asked for the PAIR body's LDS -- pending-ray levels, then the object list; this body's object list lies at the
+    // start and its batches behind it: they fit where the levels are, so the request and the occupancy stay what they were)
+    static_assert(!LSTAGE || lens_batch_lds(NT) <= (size_t)kLdsLevels * pending_level_bytes(NT), "the lens batches fit the PAIR launch's pending-ray levels");
     const long long tl_t0 = g.timeline ? wall_clock64() : 0;
     if (!HEAVY && !g.timeline) {  // (the timeline, a development aid, wants a record from every workgroup)
         if (!__syncthreads_or((int)wave_has_tile<NT>(g, tile_block, tile_grid))) return;
@@ -259,14 +266,47 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
     double pre_len = 0;
     int32_t pre_tri = -1;
 
+    // Lens stage (cgrt_lens_stage.h).  A wave of this body starts the same sample in all its lanes every iteration, so its lanes
+    // run out of staged draws together: samples [batch_first, batch_end) of the pixel are in the lane's slots, slot b of this
+    // thread at lens_slot[b * NT].  A lane reads only its own slots: no barrier.
+    const bool staging = LSTAGE && g.lens_batch != 0;
+    uint64_t *const lens_slot = reinterpret_cast<uint64_t *>(lrest) + threadIdx.x;
+    static_assert(lens_slot_at(1, 0, NT) == NT * sizeof(uint64_t) && lens_slot_at(0, 1, NT) == sizeof(uint64_t), "lens_slot's strides");
+    int batch_first = 0, batch_end = 0;
+    auto stage_lens = [&](int first, int count) {  // wave-uniform: samples first .. first + count - 1, count <= kLensBatch
+        uint32_t rejected = 0u;
+        for (int b = 0; b < count; b++) {  // phase A: attempt 1 of every sample, no divergence (a lane without a pixel included)
+            const LensSlot a = lens_stage_first(k_pix, (uint64_t)(g.sample_offset + first + b));
+            lens_slot[b * NT] = a.v;
+            rejected |= a.done ? 0u : (1u << b);
+        }
+        if (!live) rejected = 0u;
+        while (__ballot(rejected != 0u) != 0ull) {  // phase B: every lane with rejects retries its lowest rejected sample
+            if (rejected != 0u) {
+                const int b = __ffs((int)rejected) - 1;
+                const LensSlot a = lens_stage_retry(lens_slot[b * NT]);
+                lens_slot[b * NT] = a.v;
+                if (a.done) rejected &= rejected - 1u;
+            }
+        }
+        batch_first = first;
+        batch_end = first + count;
+    };
     auto start_sample = [&](int smp) {  // main.cpp:204-209
-        k_smp = sample_key(k_pix, (uint64_t)(g.sample_offset + smp));
-        if (DOF) {
+        if (LSTAGE && staging) {
+            double sx, sy;
+            lens_point(lens_slot[(smp - batch_first) * NT], sx, sy);
+            o = camorg + mk(sx, sy, 0) * g.lens_radius;
+            d = normalized(pof - o);
+            k_smp = 0;  // (a sphere scene draws nothing else from the sample's streams)
+        } else if (DOF) {
+            k_smp = sample_key(k_pix, (uint64_t)(g.sample_offset + smp));
             double sx, sy;
             lens_disc(k_smp, sx, sy);  // purpose 0: the lens stream's key is the sample key
             o = camorg + mk(sx, sy, 0) * g.lens_radius;
             d = normalized(pof - o);
         } else {
+            k_smp = sample_key(k_pix, (uint64_t)(g.sample_offset + smp));
             o = camorg;
             d = pdir;
         }
@@ -353,6 +393,16 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
                 continue;                                         // drew nothing traceable (item boundary, pixels outside the image)
             }
         } else {
+            if (LSTAGE && staging) {
+                // the lanes that start a sample are all at the same one; when it lies beyond the batch, the wave stages the next
+                const unsigned long long starting = __ballot(!have && live && s < s_end);
+                if (starting != 0ull) {
+                    const int first = __builtin_amdgcn_readlane(s, (int)__ffsll((long long)starting) - 1);
+                    // (wave-uniform: `first` is a scalar and batch_end is set in stage_lens alone, by every lane alike -- the
+                    // ballot loop in there needs the whole wave)
+                    if (first >= batch_end) stage_lens(first, min(kLensBatch, s_end - first));
+                }
+            }
             if (!have && live && s < s_end) {
                 // start the next sample of this lane's pixel
                 start_sample(s);
@@ -765,7 +815,7 @@ __global__ __launch_bounds__(NT, DIFF ? (DOF ? kDiffDofWaves : kDiffWaves) : BEZ
     // kOrderAllDiffuse (PAIR variants only): one launch over the whole list whose class-3 workgroups take the terminal-diffuse
     // body here (workgroup-uniform), at this kernel's registers -- 12 % fewer VALU instructions a frame and no second launch
     if (PAIR && g.tile_order == kOrderAllDiffuse && entry >= load_uniform(g.plan + 3))
-        trace_grid_body<false, false, DOF, false, true, false, false, NT, false, false, false, true>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid);
+        trace_grid_body<false, false, DOF, false, true, false, false, NT, false, false, false, true, false, false, DOF>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid);
     else if (PAIR && rw.chunk > 0)  // a relayed tile's later chunks park their values
         trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF, PAIR, PAIR>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid, rw);
     else

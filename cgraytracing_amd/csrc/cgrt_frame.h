@@ -1,6 +1,6 @@
 // The host side of an eye-pass launch in plain C++ (no HIP): the kernel parameters, the workgroup / tile constants, the
 // environment switches and the frame plan -- sample chunks, tile counts, heavy-tile capacity, scheduling, the tile order of a
-// sphere scene (whether it runs, who renders its class-3 tiles, the sphere masks, the sample relay) and where each array lies
+// sphere scene (whether it runs, who renders its class-3 tiles, the sphere masks, the lens stage, the sample relay) and where each array lies
 // in the handle's launch scratch and in its order buffer.  cgrt_trace_grid (cgrt_hip.hip) launches what frame_plan decides;
 // tests/native/frame_plan.cpp checks it on the CPU.
 #ifndef CGRT_FRAME_H
@@ -9,10 +9,12 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <string>
 
 #include "../../include/cgrt.h"
+#include "cgrt_lens_stage.h"
 #include "cgrt_relay.h"
 
 // =====================================================================================================
@@ -93,8 +95,11 @@ struct GridParams {
     unsigned char *relay;
     int32_t relay_k, relay_chunk_spp, relay_cap, relay_slots;
     int32_t relay_extent, relay_order;
+    // lens_batch != 0 (the PAIR variants' kOrderAllDiffuse launch of a thin-lens camera): a wave of the terminal-diffuse body inside
+    // that launch stages the lens draws of its next kLensBatch samples per lane in LDS (cgrt_lens_stage.h); 0: lens_disc per sample
+    int32_t lens_batch, pad_;
 };
-static_assert(sizeof(GridParams) == 320, "GridParams is a kernel argument: its layout is fixed");
+static_assert(sizeof(GridParams) == 328, "GridParams is a kernel argument: its layout is fixed");
 
 static constexpr int kTileW = 32, kTileH = 8, kThreads = 256;
 // Tile order of image-order launches (tile_order_kernel, cgrt_eye.hpp): the special spheres -- those that reflect or refract --
@@ -212,6 +217,7 @@ struct EyeKnobs {
     long long relay_tiles = 0;           // RELAY_TILES: > 0: at most this many tiles are relayed (the relay area's capacity)
     int relay_mirror = -1;  // RELAY_MIRROR: 0 / 1: the relay's extent where the launch's flags name none (-1: unset)
     int relay_order = -1;   // RELAY_ORDER: chunks_first / mirror_first / interleaved (or 0 / 1 / 2), likewise
+    int lens_stage = -1;    // LENS_STAGE: off / lds (kLensStageOff / kLensStageLds), where the launch's flags do not switch it off (-1: unset)
     const char *timeline_file = nullptr;  // TIMELINE_FILE (nullptr: off)
 };
 inline const char *env_str(const char *name) { const char *e = std::getenv(name); return e ? e : ""; }
@@ -223,6 +229,16 @@ inline int relay_order_named(const char *e) {
     if (v == "chunks_first" || v == "0") return kRelayChunksFirst;
     if (v == "mirror_first" || v == "1") return kRelayMirrorFirst;
     if (v == "interleaved" || v == "2") return kRelayInterleaved;
+    return -1;
+}
+// Lens points staged ahead of the sample loop (cgrt_lens_stage.h; TileOrderPlan::lens_stage): per-lane batches in LDS
+static constexpr int kLensStageOff = 0, kLensStageLds = 1;
+static constexpr int kLensStageDefault = kLensStageLds;  // the measured form
+// CGRT_LENS_STAGE's value; -1: none of them
+inline int lens_stage_named(const char *e) {
+    const std::string v(e);
+    if (v == "off" || v == "0") return kLensStageOff;
+    if (v == "lds" || v == "1") return kLensStageLds;
     return -1;
 }
 // Read once per process, at the first launch, except CGRT_TIMELINE_FILE, which every launch reads.
@@ -246,6 +262,11 @@ inline EyeKnobs eye_knobs() {
         k.relay_tiles = std::atoll(env_str("CGRT_RELAY_TILES"));
         if (*env_str("CGRT_RELAY_MIRROR")) k.relay_mirror = env_on("CGRT_RELAY_MIRROR") ? 1 : 0;
         k.relay_order = relay_order_named(env_str("CGRT_RELAY_ORDER"));
+        k.lens_stage = lens_stage_named(env_str("CGRT_LENS_STAGE"));
+        // (`area` and `both` name forms that exist only as profiles/experiments/lens_stage_area.patch: said aloud, so that no
+        // A/B run takes the default for them)
+        if (k.lens_stage < 0 && *env_str("CGRT_LENS_STAGE"))
+            std::fprintf(stderr, "cgrt: CGRT_LENS_STAGE=%s names no form of this library (off, lds): the default is used\n", env_str("CGRT_LENS_STAGE"));
         return k;
     }();
     EyeKnobs k = once;
@@ -307,6 +328,8 @@ struct TileOrderPlan {
     // terminal-diffuse body inside the PAIR variant (kOrderAllDiffuse)
     enum Class3 { None, SecondLaunch, InKernel } class3 = None;
     bool masks = false;  // tile_order_kernel writes the wave tiles' sphere masks (GridParams::wmask)
+    // kLensStageLds: the terminal-diffuse body inside the launch stages its lens draws in batches (GridParams::lens_batch)
+    int lens_stage = kLensStageOff;
 };
 
 struct FramePlan {
@@ -403,6 +426,11 @@ inline FramePlan frame_plan(const FrameInputs &in, size_t kmax) {
     }
     o.masks = o.class3 != TileOrderPlan::None && in.all_spheres && in.n_objs <= kSphereMaskMax && in.n_objs == in.n_lds &&
               !(gr.flags & CGRT_GRID_NO_SPHERE_MASKS);
+    // Lens stage: the thin-lens terminal-diffuse body INSIDE the launch, whose batches lie in the launch's pending-ray levels;
+    // the second launch's variant asks for no such LDS and draws sample by sample.  CGRT_GRID_NO_LENS_STAGE switches it off;
+    // otherwise the knob CGRT_LENS_STAGE holds, and the default where it names nothing.
+    if (o.class3 == TileOrderPlan::InKernel && in.cam.lens_radius > 0 && !(gr.flags & CGRT_GRID_NO_LENS_STAGE))
+        o.lens_stage = kn.lens_stage >= 0 ? kn.lens_stage : kLensStageDefault;
     if (o.on && in.pair && o.class3 != TileOrderPlan::SecondLaunch && !split_asked &&
         relay_engaged(gr.flags, gr.spp, (size_t)p.tile_blocks, in.n_cu)) {
         const RelayChunks rc = relay_chunks(gr.spp, (gr.flags & CGRT_GRID_SAMPLE_RELAY_4) ? kRelayMaxChunks : kn.relay_chunks);
@@ -502,6 +530,7 @@ inline GridParams frame_params(const FrameInputs &in, const FramePlan &p) {
     g.pw_rounds = in.knobs.pw_rounds;
     g.items_per_tile = p.items_per_tile;
     g.heavy_blocks = p.heavy_blocks;
+    g.lens_batch = p.order.lens_stage == kLensStageLds ? 1 : 0;
     if (p.heavy_blocks > 0 && p.use_prim) {
         g.prim_obj = in.prim_obj;
         g.prim_done = p.prim_done ? 1 : 0;

@@ -1091,6 +1091,11 @@ int cgrt_scene_last_inkernel_diffuse_tiles(const cgrt_scene *s, int64_t *n_tiles
     ON_DEVICE(s->device);
     return last_class3_tiles(s->order, TileOrderPlan::InKernel, n_tiles);
 }
+int cgrt_scene_last_lens_stage(const cgrt_scene *s, int64_t *lds_tiles, int64_t *area_tiles) {
+    NEED_COMMITTED(s, lds_tiles && area_tiles);
+    ON_DEVICE(s->device);
+    return last_lens_stage(s->order, lds_tiles, area_tiles);
+}
 int cgrt_scene_last_sample_relay(const cgrt_scene *s, int64_t *tiles, int32_t *chunks, int64_t *parked_values) {
     NEED_COMMITTED(s, tiles && chunks && parked_values);
     ON_DEVICE(s->device);

@@ -42,11 +42,13 @@ struct TileOrderState {
     size_t tiles = 0, mask_wtiles = 0;
     TileOrderLayout at;
     TileOrderPlan::Class3 class3 = TileOrderPlan::None;
+    int lens_stage = kLensStageOff;  // how that launch's in-kernel terminal-diffuse body drew its lens points
 
     void begin_launch() {
         tiles = mask_wtiles = 0;
         reused = false;
         class3 = TileOrderPlan::None;
+        lens_stage = kLensStageOff;
     }
     void release() {
         buf.release();
@@ -148,6 +150,7 @@ static int order_tiles(TileOrderState &o, const DeviceScene &dev, const FramePla
     o.mask_wtiles = masks ? p.n_wt : 0;
     o.at = at;
     o.class3 = p.order.class3;
+    o.lens_stage = p.order.lens_stage;
     return CGRT_OK;
 }
 
@@ -253,6 +256,11 @@ static int last_class3_tiles(const TileOrderState &o, TileOrderPlan::Class3 form
     if (int rc = o.read(o.at.plan, plan, kOrderClasses + 1)) return rc;
     *n_tiles = (int64_t)plan[kOrderClasses] - (int64_t)plan[3];
     return CGRT_OK;
+}
+// the tiles of the last launch whose workgroups staged their lens draws in LDS batches: its in-kernel class-3 tiles
+static int last_lens_stage(const TileOrderState &o, int64_t *lds_tiles, int64_t *area_tiles) {
+    *lds_tiles = *area_tiles = 0;
+    return o.lens_stage == kLensStageLds ? last_class3_tiles(o, TileOrderPlan::InKernel, lds_tiles) : CGRT_OK;
 }
 static int last_sample_relay(const TileOrderState &o, const RelayState &r, int64_t *tiles, int32_t *chunks, int64_t *parked_values) {
     *tiles = *parked_values = 0;

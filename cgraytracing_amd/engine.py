@@ -179,7 +179,7 @@ class Scene:
                    stripe=None, sample_offset=0, spp_total=None, out=None, nhit=None, counters=None, stream=None,
                    stats=False, accumulate=False, split_samples=False, reorder=True, force_reorder=False, tile_order=True,
                    diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None,
-                   relay_mirror=None, relay_order=None):
+                   relay_mirror=None, relay_order=None, lens_stage=True):
         """Asynchronous launch on torch's current stream (or `stream`).  reorder=False: CGRT_GRID_NO_REORDER (tiles in image
         order instead of heaviest-first; same image).  tile_order=False: CGRT_GRID_NO_TILE_ORDER (an image-order launch starts
         its tiles row-major instead of mirror / glass tiles first; same image).  diffuse_tiles=True: CGRT_GRID_DIFFUSE_TILES (a
@@ -193,7 +193,9 @@ class Scene:
         tile); False: CGRT_GRID_NO_SAMPLE_RELAY.  relay_mirror: True -- the relay takes the tiles that see only a mirror sphere
         too (CGRT_GRID_RELAY_MIRROR), False -- it does not; relay_order: "chunks_first", "mirror_first" or "interleaved" -- where
         those tiles' workgroups start among the glass tiles'; None: what sample_relay has always meant when it is given, the
-        measured form when it is not (last_relay_form tells).  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
+        measured form when it is not (last_relay_form tells).  lens_stage=False: CGRT_GRID_NO_LENS_STAGE (the thin-lens
+        terminal-diffuse body inside the main launch draws every lens point by its own rejection loop instead of staging 16
+        samples' draws ahead; same image; last_lens_stage).  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
         workgroups share a tile's samples; reproducible, fp64 summation order differs from the sample-by-sample sum).  Returns (rgb, nhit, counters) torch
         tensors on the scene's device: float32 [rows,width,3], int32 [rows,width] (bit pattern uint32),
         int64 [8] (counters are ADDED to)."""
@@ -213,7 +215,8 @@ class Scene:
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (2 if accumulate else 0) | (4 if split_samples else 0) |
                               (0 if reorder else 8) | (16 if force_reorder else 0) | (0 if tile_order else 64) |
-                              (128 if diffuse_tiles else 0) | (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order))
+                              (128 if diffuse_tiles else 0) | (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order) |
+                              (0 if lens_stage else 131072))
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         check(self._L.cgrt_trace_grid(self._h, C.byref(cc), C.byref(g), out.data_ptr(),
                                       nhit.data_ptr() if nhit is not None else None,
@@ -427,7 +430,7 @@ class Scene:
     def trace_grid_host(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                         stripe=None, sample_offset=0, spp_total=None, stats=False, split_samples=False, reorder=True,
                         force_reorder=False, tile_order=True, diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None,
-                        relay_mirror=None, relay_order=None):
+                        relay_mirror=None, relay_order=None, lens_stage=True):
         """Synchronous form with numpy outputs (no torch needed): dict(rgb, nhit, counters)."""
         rows = height - row_offset if rows is None else rows
         rgb = np.zeros((rows, width, 3), np.float32)
@@ -436,7 +439,8 @@ class Scene:
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (4 if split_samples else 0) | (0 if reorder else 8) |
                               (16 if force_reorder else 0) | (0 if tile_order else 64) | (128 if diffuse_tiles else 0) |
-                              (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order))
+                              (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order) |
+                              (0 if lens_stage else 131072))
         check(self._L.cgrt_trace_grid_host(self._h, C.byref(cc), C.byref(g), rgb.ctypes.data, nhit.ctypes.data,
                                            cnt.ctypes.data))
         return dict(rgb=rgb, nhit=nhit, counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]),
@@ -487,6 +491,13 @@ class Scene:
         m, o = C.c_int32(), C.c_int32()
         check(self._L.cgrt_scene_last_relay_form(self._h, C.byref(m), C.byref(o)))
         return None if m.value < 0 else dict(mirror=bool(m.value), order=_RELAY_ORDERS[o.value])
+
+    def last_lens_stage(self):
+        """Lens points staged ahead by this scene's last trace_grid / trace_grid_host (cgrt_scene_last_lens_stage; synchronises
+        the device): dict(lds_tiles: tiles whose workgroups staged their lens draws in LDS batches, area_tiles: always 0)."""
+        a, b = C.c_int64(), C.c_int64()
+        check(self._L.cgrt_scene_last_lens_stage(self._h, C.byref(a), C.byref(b)))
+        return dict(lds_tiles=int(a.value), area_tiles=int(b.value))
 
     def last_diffuse_tiles(self):
         """Tiles the terminal-diffuse launch of this scene's last trace_grid / trace_grid_host rendered

@@ -148,6 +148,14 @@ enum {
     CGRT_GRID_RELAY_INTERLEAVED = 98304, /* ... or the two merged in proportion.  0: chunks first with CGRT_GRID_SAMPLE_RELAY,
                                  the measured order by default.  cgrt_scene_last_relay_form tells what a launch used       */
     CGRT_GRID_RELAY_ORDER_MASK = 98304,
+    CGRT_GRID_NO_LENS_STAGE = 131072, /* the terminal-diffuse body inside the main launch (see CGRT_GRID_NO_SPHERE_PAIRS) under a
+                                 thin-lens camera: by default a wave finds the accepted lens draws of its next 16 samples
+                                 ahead of their use -- attempt 1 of every sample without divergence, then the rejected ones,
+                                 every lane on its own (sample, attempt) stream -- and keeps them in LDS the launch already
+                                 owns (cgrt_scene_last_lens_stage).  This flag restores one rejection loop per sample, run at
+                                 the pace of the wave's unluckiest lane.  The same lens points: same image, hit counts and
+                                 counters either way; it exists to test one against the other.  The second launch of
+                                 CGRT_GRID_DIFFUSE_TILES always draws sample by sample                                    */
     CGRT_GRID_HITPOINTS = 32, /* cgrt_trace_grid_variant only: name the launch of the Hitpoint capture
                                  (cgrt_trace_grid_hitpoints, the eye pass of cgrt_ppm_render) instead of cgrt_trace_grid's;
                                  ignored by the other calls                                                            */
@@ -646,6 +654,10 @@ int cgrt_scene_last_sample_relay(const cgrt_scene *s, int64_t *tiles, int32_t *c
 /* The form of that relay: *mirror = 1 when the class-2 tiles were relayed too (CGRT_GRID_RELAY_MIRROR), *order = 0 chunks
  * first, 1 mirror first, 2 interleaved; both -1 when the launch did not relay. */
 int cgrt_scene_last_relay_form(const cgrt_scene *s, int32_t *mirror, int32_t *order);
+/* Lens points staged ahead of the sample loop by the LAST cgrt_trace_grid on the handle (see CGRT_GRID_NO_LENS_STAGE;
+ * synchronises the device): *lds_tiles = the tiles whose workgroups staged their lens draws in LDS batches, *area_tiles = the
+ * tiles that staged them in device memory (no launch does: always 0).  Both 0: every lens point came from the per-sample loop. */
+int cgrt_scene_last_lens_stage(const cgrt_scene *s, int64_t *lds_tiles, int64_t *area_tiles);
 
 /* Host evaluation of the lens stream (cgrt_rng.hpp, the same inline code the kernel runs): writes
  * uniform_sampling_circle(radius) (sampling.h:35-43) for n (pixel, sample) pairs as 3 doubles each.  Lets CPU-only
