@@ -94,6 +94,10 @@ class HitAttributes(C.Structure):
     _fields_ = [("prim", C.c_void_p), ("uv2", C.c_void_p), ("color3", C.c_void_p), ("material2", C.c_void_p)]
 
 
+class Occlusion(C.Structure):
+    _fields_ = [("tmax", C.c_void_p), ("occluded", C.c_void_p)]
+
+
 class RayPixels(C.Structure):
     _fields_ = [("width", C.c_int32), ("rows", C.c_int32), ("spp", C.c_int32), ("pad_", C.c_int32), ("pixel", C.c_void_p)]
 
@@ -106,6 +110,7 @@ class PhotonRays(C.Structure):
 RAYS_STATS = 1
 RAYS_NO_SIGN_PASS = 2
 RAYS_HITPOINTS = 4
+RAYS_SKIP_TRANSPARENT = 8
 PROBE_SQRT, PROBE_NORMALIZED, PROBE_SPHERE_LEN, PROBE_SPHERE_LEN_PAIR = 0, 1, 2, 4  # cgrt_math_probe's op (3 is none)
 
 # every symbol include/cgrt.h declares, with its signature
@@ -182,6 +187,9 @@ SIGNATURES = {
     "cgrt_ray_hit_attributes_host": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.c_void_p, C.c_void_p, C.POINTER(HitAttributes)]),
     "cgrt_trace_rays_variant": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(RayResults), C.c_char_p, C.c_size_t]),
     "cgrt_trace_rays_hitpoints": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cgrt_occlusion_rays": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(Occlusion), C.c_void_p, C.c_void_p]),
+    "cgrt_occlusion_rays_host": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(Occlusion), C.c_void_p]),
+    "cgrt_occlusion_rays_variant": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.c_char_p, C.c_size_t]),
     "cgrt_camera_rays": (C.c_int, [C.POINTER(Camera), C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cgrt_camera_rays_host": (C.c_int, [C.POINTER(Camera), C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cgrt_intersect_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,

@@ -41,6 +41,7 @@
 #include "cgrt_eye.hpp"
 #include "cgrt_primwalk.hpp"
 #include "cgrt_rays.hpp"
+#include "cgrt_occlusion.hpp"
 #include "cgrt_hit_attr.hpp"
 
 using namespace cgrt;
@@ -1253,6 +1254,38 @@ static int check_camera_rays(const cgrt_camera *cam, const cgrt_grid *g) {
     return CGRT_OK;
 }
 
+// The instantiations of occlusion_rays_kernel (cgrt_occlusion.hpp) that are launched: one for every nearest-hit entry of
+// kRaysKernels, whose launch plan (rays_launch with first = true) cgrt_occlusion_rays shares -- flags, resident objects, LDS.
+using OcclusionKernel = void (*)(DeviceScene, OccParams, unsigned long long *);
+struct OcclusionKernels {
+    int id;  // RayFlags::id() of the nearest-hit query's launch for the same scene
+    OcclusionKernel fn;
+};
+template <int T, int B, int P, int S, int SP, int NT = kThreads>
+static constexpr OcclusionKernels ok() {
+    return {RayFlags{T != 0, B != 0, false, P != 0, S != 0, SP != 0, true, NT}.id(),
+            &occlusion_rays_kernel<T != 0, B != 0, P != 0, S != 0, SP != 0, NT>};
+}
+//                                    TREES BEZ SPH STATS SPILL [NT]
+static const OcclusionKernels kOcclusionKernels[] = {
+    ok<1, 1, 0, 0, 0, 64>(), ok<1, 0, 0, 0, 0>(), ok<1, 0, 0, 1, 0>(), ok<0, 0, 1, 0, 0>(),
+    ok<0, 0, 0, 0, 0>(), ok<0, 0, 1, 0, 1>(), ok<1, 1, 0, 0, 1>(),
+};
+static const OcclusionKernels *occlusion_kernels(const RayFlags &f) {
+    for (const OcclusionKernels &e : kOcclusionKernels)
+        if (e.id == f.id()) return &e;
+    return nullptr;
+}
+static int check_occlusion(const cgrt_scene *s, const cgrt_rays *r, const cgrt_occlusion *occ) {
+    if (!s || !r || !occ) return fail(CGRT_ERR_INVALID, "null argument");
+    if (r->n < 0) return fail(CGRT_ERR_INVALID, "negative ray count");
+    if (r->n > 0 && (!r->org3 || !r->dir3)) return fail(CGRT_ERR_INVALID, "null org3 / dir3");
+    if (!occ->occluded) return fail(CGRT_ERR_INVALID, "null occluded");
+    if (r->n > kMaxRays) return fail(CGRT_ERR_LIMIT, "more than 2^36 rays in one call");
+    if (r->n > 0 && !s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");  // (no rays: nothing is looked at)
+    return CGRT_OK;
+}
+
 extern "C" {
 
 int cgrt_trace_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_results *out, uint64_t *counters, void *stream) {
@@ -1363,6 +1396,97 @@ int cgrt_trace_rays_host(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_
         if (out->hit_obj) HIP_TRY(hipMemcpy(out->hit_obj, b_obj.p, n * 4, hipMemcpyDeviceToHost));
         if (out->hit_t) HIP_TRY(hipMemcpy(out->hit_t, b_t.p, n * 8, hipMemcpyDeviceToHost));
         if (out->hit_normal3) HIP_TRY(hipMemcpy(out->hit_normal3, b_n.p, n * 24, hipMemcpyDeviceToHost));
+        if (counters) HIP_TRY(hipMemcpy(counters, b_cnt.p, CGRT_NCOUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    return rc;
+}
+
+int cgrt_occlusion_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_occlusion *occ, uint64_t *counters, void *stream) {
+    int rc = check_occlusion(s, rays, occ);
+    if (rc) return rc;
+    if (rays->n == 0) return CGRT_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    ON_DEVICE(s->device);
+    const RaysLaunch L = rays_launch(s, 1, (rays->flags & CGRT_RAYS_STATS) != 0, true);
+    const OcclusionKernels *e = occlusion_kernels(L.k);
+    if (!e) return fail(CGRT_ERR_UNSUPPORTED, std::string(L.what()) + ": no occlusion kernel built for this variant");
+    // the queue's head lives in the handle's launch scratch, as cgrt_trace_rays'
+    if (s->scratch.need(256) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(CGRT_ERR_DEVICE, "cannot allocate launch scratch (ray queue)");
+    }
+    HIP_TRY(hipMemsetAsync(s->scratch.p, 0, sizeof(unsigned int), st));
+    OccParams rp{};
+    rp.n = rays->n;
+    rp.org = rays->org3;
+    rp.dir = rays->dir3;
+    rp.keys = reinterpret_cast<const unsigned long long *>(rays->keys);
+    rp.first_index = rays->first_index;
+    rp.seed = rays->seed;
+    rp.tmax = occ->tmax;
+    rp.occluded = occ->occluded;
+    rp.queue = reinterpret_cast<unsigned int *>(s->scratch.p);
+    rp.skip_transparent = (rays->flags & CGRT_RAYS_SKIP_TRANSPARENT) != 0;
+    // persistent workgroups, sized as cgrt_trace_rays sizes them
+    const long long waves_per_wg = L.k.nt / 64, n_blocks = (rays->n + 63) / 64;
+    const long long chip = (long long)s->n_cu * 4 * (L.k.bez ? kBezWaves : (L.k.trees ? kTreeWaves : 4)) / waves_per_wg;
+    const long long wgs = std::max(1ll, std::min((n_blocks + waves_per_wg - 1) / waves_per_wg, 2 * chip));
+    if ((rc = launch_checked(e->fn, L.what(), s->device, dim3((unsigned)wgs), dim3((unsigned)L.k.nt), L.lds, st, L.dev, rp,
+                             reinterpret_cast<unsigned long long *>(counters))))
+        return rc;
+    HIP_TRY(hipGetLastError());
+    return CGRT_OK;
+}
+
+int cgrt_occlusion_rays_variant(const cgrt_scene *s, const cgrt_rays *rays, char *name, size_t cap) {
+    if (!s || !rays || !name || cap == 0) return fail(CGRT_ERR_INVALID, "null argument");
+    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+    ON_DEVICE(s->device);
+    const RayFlags k = rays_launch(s, 1, (rays->flags & CGRT_RAYS_STATS) != 0, true).k;
+    std::snprintf(name, cap, "occlusion_rays_kernel<TREES=%d,BEZ=%d,SPH=%d,STATS=%d,SPILL=%d,NT=%d>", (int)k.trees, (int)k.bez, (int)k.sph,
+                  (int)k.stats, (int)k.spill, k.nt);
+    return CGRT_OK;
+}
+
+int cgrt_occlusion_rays_host(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_occlusion *occ, uint64_t *counters) {
+    int rc = check_occlusion(s, rays, occ);
+    if (rc) return rc;
+    const size_t n = (size_t)rays->n;
+    if (n == 0) {
+        if (counters) std::memset(counters, 0, CGRT_NCOUNTERS * sizeof(uint64_t));
+        return CGRT_OK;
+    }
+    ON_DEVICE(s->device);
+    DevBuf b_o, b_d, b_k, b_t, b_occ, b_cnt;
+    cgrt_rays dr = *rays;
+    cgrt_occlusion docc{};
+    HIP_TRY(b_o.alloc(n * 24));
+    HIP_TRY(b_d.alloc(n * 24));
+    HIP_TRY(hipMemcpy(b_o.p, rays->org3, n * 24, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_d.p, rays->dir3, n * 24, hipMemcpyHostToDevice));
+    dr.org3 = b_o.as<double>();
+    dr.dir3 = b_d.as<double>();
+    if (rays->keys) {
+        HIP_TRY(b_k.alloc(n * 8));
+        HIP_TRY(hipMemcpy(b_k.p, rays->keys, n * 8, hipMemcpyHostToDevice));
+        dr.keys = b_k.as<uint64_t>();
+    }
+    if (occ->tmax) {
+        HIP_TRY(b_t.alloc(n * 8));
+        HIP_TRY(hipMemcpy(b_t.p, occ->tmax, n * 8, hipMemcpyHostToDevice));
+        docc.tmax = b_t.as<double>();
+    }
+    HIP_TRY(b_occ.alloc(n));
+    docc.occluded = b_occ.as<uint8_t>();
+    HIP_TRY(b_cnt.alloc(CGRT_NCOUNTERS * sizeof(uint64_t)));
+    HIP_TRY(hipMemset(b_cnt.p, 0, CGRT_NCOUNTERS * sizeof(uint64_t)));
+    rc = cgrt_occlusion_rays(s, &dr, &docc, b_cnt.as<uint64_t>(), nullptr);
+    if (rc == CGRT_OK) {
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess) rc = fail(CGRT_ERR_DEVICE, std::string("kernel: ") + hipGetErrorString(e));
+    }
+    if (rc == CGRT_OK) {
+        HIP_TRY(hipMemcpy(occ->occluded, b_occ.p, n, hipMemcpyDeviceToHost));
         if (counters) HIP_TRY(hipMemcpy(counters, b_cnt.p, CGRT_NCOUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
     return rc;

@@ -418,6 +418,79 @@ class Scene:
         check(self._L.cgrt_ray_hit_attributes_host(self._h, C.byref(r), hit_obj.ctypes.data, hit_t.ctypes.data, C.byref(o)))
         return res
 
+    # ---- occlusion queries of caller-supplied rays ----
+    def occluded(self, org, dirs, tmax=None, keys=None, seed=12345, first_index=0, skip_transparent=False, stats=False, out=None,
+                 stream=None):
+        """cgrt_occlusion_rays on torch tensors: org, dirs float64 [n,3] contiguous on the scene's device, tmax float64 [n] or
+        None (no limit), keys int64 [n] or None.  occluded[i] = 1 exactly when some object's intersect() length is < tmax[i]
+        -- hit_obj >= 0 and hit_t < tmax of trace_rays(want=("hit",)) on the same rays --, else 0; a NaN tmax, a tmax <= 0
+        (unless an object returns a length below zero: a ray starting on a sphere's surface) and a dirs row of zeros give 0.  skip_transparent: objects with transparency >= 1e-4 are no occluders (shadow rays through
+        glass).  out: a preallocated uint8 [n] tensor, or a dict holding one as "occluded".  Asynchronous on torch's current
+        stream (or `stream`).  Returns {"occluded": uint8 [n], "counters": int64 [8]}."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        for name, t in (("org", org), ("dirs", dirs)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == 3 and
+                    t.is_contiguous() and t.device == dev):
+                raise ValueError("occluded: %s must be a contiguous float64 [n,3] tensor on %s" % (name, dev))
+        n = org.shape[0]
+        if dirs.shape[0] != n:
+            raise ValueError("occluded: org and dirs differ in length")
+        if tmax is not None and not (isinstance(tmax, torch.Tensor) and tmax.dtype == torch.float64 and tuple(tmax.shape) == (n,) and
+                                     tmax.is_contiguous() and tmax.device == dev):
+            raise ValueError("occluded: tmax must be a contiguous float64 [n] tensor on %s" % (dev,))
+        if keys is not None and not (isinstance(keys, torch.Tensor) and keys.dtype == torch.int64 and tuple(keys.shape) == (n,) and
+                                     keys.is_contiguous() and keys.device == dev):
+            raise ValueError("occluded: keys must be a contiguous int64 [n] tensor on %s" % (dev,))
+        occ = out.get("occluded") if isinstance(out, dict) else out
+        if occ is None:
+            occ = torch.empty((n,), dtype=torch.uint8, device=dev)
+        elif not (isinstance(occ, torch.Tensor) and occ.dtype == torch.uint8 and tuple(occ.shape) == (n,) and occ.is_contiguous() and
+                  occ.device == dev):
+            raise ValueError("occluded: out must be a contiguous uint8 [n] tensor on %s" % (dev,))
+        counters = torch.zeros((_capi.CGRT_NCOUNTERS,), dtype=torch.int64, device=dev)
+        res = {"occluded": occ, "counters": counters}
+        if n == 0:
+            return res
+        r = _capi.Rays(n, org.data_ptr(), dirs.data_ptr(), keys.data_ptr() if keys is not None else None, first_index, seed, 1,
+                       (_capi.RAYS_STATS if stats else 0) | (_capi.RAYS_SKIP_TRANSPARENT if skip_transparent else 0))
+        o = _capi.Occlusion(tmax.data_ptr() if tmax is not None else None, occ.data_ptr())
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(self._L.cgrt_occlusion_rays(self._h, C.byref(r), C.byref(o), counters.data_ptr(), C.c_void_p(st)))
+        return res
+
+    def occluded_host(self, org, dirs, tmax=None, keys=None, seed=12345, first_index=0, skip_transparent=False, stats=False):
+        """Synchronous form of occluded on numpy arrays (no torch needed): dict(occluded (uint8 [n]), counters (uint64 [8]),
+        nrays)."""
+        org = np.ascontiguousarray(org, np.float64).reshape(-1, 3)
+        dirs = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
+        n = len(org)
+        if len(dirs) != n:
+            raise ValueError("occluded_host: org and dirs differ in length")
+        if tmax is not None:
+            tmax = np.ascontiguousarray(tmax, np.float64)
+            if tmax.shape != (n,):
+                raise ValueError("occluded_host: tmax must have one entry per ray")
+        if keys is not None:
+            keys = np.ascontiguousarray(keys, np.uint64)
+            if keys.shape != (n,):
+                raise ValueError("occluded_host: keys must have one entry per ray")
+        occ = np.zeros(max(n, 1), np.uint8)
+        cnt = np.zeros((_capi.CGRT_NCOUNTERS,), np.uint64)
+        r = _capi.Rays(n, org.ctypes.data, dirs.ctypes.data, keys.ctypes.data if keys is not None else None, first_index, seed, 1,
+                       (_capi.RAYS_STATS if stats else 0) | (_capi.RAYS_SKIP_TRANSPARENT if skip_transparent else 0))
+        o = _capi.Occlusion(tmax.ctypes.data if tmax is not None else None, occ.ctypes.data)
+        check(self._L.cgrt_occlusion_rays_host(self._h, C.byref(r), C.byref(o), cnt.ctypes.data))
+        return dict(occluded=occ[:n], counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]))
+
+    def occlusion_variant(self, stats=False):
+        """Name of the occlusion_rays_kernel instantiation occluded launches on this scene (cgrt_occlusion_rays_variant)."""
+        r = _capi.Rays(1, None, None, None, 0, 0, 1, _capi.RAYS_STATS if stats else 0)
+        buf = C.create_string_buffer(160)
+        check(self._L.cgrt_occlusion_rays_variant(self._h, C.byref(r), buf, len(buf)))
+        return buf.value.decode()
+
     def rays_variant(self, max_depth=5, want=("acc", "nhit", "hit"), stats=False):
         """Name of the trace_rays_kernel instantiation trace_rays launches for these arguments (cgrt_trace_rays_variant)."""
         full = 1 if ("acc" in want or "nhit" in want) else None

@@ -18,7 +18,7 @@
  * Threading: launches on ONE scene handle must be ordered by the caller (same stream, or events between streams) --
  * a handle owns device scratch that consecutive launches reuse (CGRT_GRID_SPLIT_SAMPLES chunk sums; the schedule of a
  * cost-ordered frame; the tile order of an image-order one; the queue counter of cgrt_trace_rays, cgrt_trace_rays_hitpoints and cgrt_ppm_session_create_rays, which
- * are such launches; cgrt_ray_hit_attributes is one too: its first call that asks for `prim` builds a table the handle keeps).
+ * are such launches (cgrt_occlusion_rays uses that counter too); cgrt_ray_hit_attributes is one too: its first call that asks for `prim` builds a table the handle keeps).
  * All geometry is IEEE double, like the reference (Vec3 = 3 x double, vec3.h:11-30).
  */
 #ifndef CGRT_H
@@ -39,7 +39,8 @@ extern "C" {
                             cgrt_trace_rays_hitpoints, cgrt_ppm_session_create_rays (photon mapping of caller-supplied rays);
                             cgrt_ppm_session_add_photon_rays, cgrt_photon_emit, cgrt_photon_emit_host, cgrt_photon_ray_events
                             (caller-supplied photons); cgrt_hit_attributes, cgrt_ray_hit_attributes, cgrt_ray_hit_attributes_host
-                            (hit attributes of caller-supplied rays) */
+                            (hit attributes of caller-supplied rays); cgrt_occlusion, CGRT_RAYS_SKIP_TRANSPARENT,
+                            cgrt_occlusion_rays, cgrt_occlusion_rays_host, cgrt_occlusion_rays_variant (occlusion queries) */
 
 enum {
     CGRT_OK = 0,
@@ -313,9 +314,11 @@ enum {
     CGRT_RAYS_STATS = 1,       /* also count tree-node and triangle tests, like CGRT_GRID_STATS                              */
     CGRT_RAYS_NO_SIGN_PASS = 2,/* hit_normal3 of an opaque mesh: skip the pass that gives it the reference's sign (below); the
                                   vector is then right up to its sign, and the call costs one unpruned mesh walk per ray less */
-    CGRT_RAYS_HITPOINTS = 4    /* cgrt_trace_rays_variant only: name the launch of the Hitpoint capture (cgrt_trace_rays_hitpoints,
+    CGRT_RAYS_HITPOINTS = 4,   /* cgrt_trace_rays_variant only: name the launch of the Hitpoint capture (cgrt_trace_rays_hitpoints,
                                   the eye stage of cgrt_ppm_session_create_rays) instead of cgrt_trace_rays'; `out` is then not
                                   looked at and may be NULL.  Ignored by the other calls, as CGRT_GRID_HITPOINTS is              */
+    CGRT_RAYS_SKIP_TRANSPARENT = 8 /* cgrt_occlusion_rays only: objects with transparency >= 1e-4 are no occluders (shadow rays
+                                  through glass).  Ignored by the other calls                                                  */
 };
 
 typedef struct cgrt_ray_results {   /* every pointer may be NULL: only the arrays asked for are written */
@@ -392,6 +395,38 @@ int cgrt_ray_hit_attributes(const cgrt_scene *s, const cgrt_rays *rays, const in
 /* HOST pointers: allocates device buffers, runs, synchronises and copies back, like cgrt_trace_rays_host. */
 int cgrt_ray_hit_attributes_host(const cgrt_scene *s, const cgrt_rays *rays, const int32_t *hit_obj, const double *hit_t,
                                  const cgrt_hit_attributes *out);
+
+/* ---- occlusion queries: "is anything between these two points?" ----------------------------------------------------
+ * Shadow rays to a light, ambient occlusion, mutual visibility, culling a custom emitter's photons.  Per ray i
+ *   occluded[i] = 1 exactly when some occluder's intersect() returns len < tmax[i] (strict), else 0,
+ * where len is the value the nearest-hit query computes for that object and that ray, bit for bit.  The occluders are all
+ * objects of the scene; with CGRT_RAYS_SKIP_TRANSPARENT those whose transparency is < 1e-4 (the "opaque" of the scene walk).
+ * Without the flag this is hit_obj[i] >= 0 && hit_t[i] < tmax[i] of cgrt_trace_rays on the same org3, dir3 and keys /
+ * first_index / seed; with it, the same expression over the scene without its transparent objects.  A tmax that is NaN
+ * gives 0, and so does a tmax <= 0 wherever no object returns a length below zero (Sphere::intersect can, by a few ulps, for
+ * a ray that starts on the sphere's surface, objects.h:45-68: the identity with the query holds there too); such a ray
+ * still counts as traced.  A dir of exactly (0,0,0) marks a ray that is NOT traced: it gives 0 and is not counted, as in
+ * cgrt_trace_rays.  Nothing but the bit is returned -- no blocker, no distance: which blocker a walk meets
+ * first depends on the walk's order, the bit does not, so a ray's result does not depend on the other rays of the call, on
+ * their order or on how a ray set is split over calls (with keys, or first_index, kept alike).
+ * Of `rays`, max_depth is not looked at; CGRT_RAYS_NO_SIGN_PASS and CGRT_RAYS_HITPOINTS are ignored; CGRT_RAYS_STATS counts
+ * node and triangle tests.  counters (may be NULL) are ADDED to: CGRT_CNT_RAYS by the rays traced, _WAVE_ITERS as usual;
+ * _HITPOINTS is untouched.
+ * A null scene, null rays or occ, a negative n, a null occluded: CGRT_ERR_INVALID; more than 2^36 rays: CGRT_ERR_LIMIT;
+ * n == 0 is valid and does nothing (the scene is not even looked at); otherwise an uncommitted scene: CGRT_ERR_INVALID -- all
+ * before any device is touched. */
+typedef struct cgrt_occlusion {
+    const double *tmax;   /* [n] or NULL.  NULL: no limit (the kernels' 1e10 "no hit yet"); larger values mean the same      */
+    uint8_t *occluded;    /* [n] required: 1 or 0                                                                          */
+} cgrt_occlusion;         /* 16 bytes */
+
+/* DEVICE pointers on the scene's device; asynchronous on `stream`.  This is a launch on the scene handle (Threading above):
+ * it uses the handle's ray-queue counter, like cgrt_trace_rays. */
+int cgrt_occlusion_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_occlusion *occ, uint64_t *counters, void *stream);
+/* HOST pointers: allocates device buffers, runs, synchronises and copies back (counters are overwritten). */
+int cgrt_occlusion_rays_host(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_occlusion *occ, uint64_t *counters);
+/* Name of the occlusion_rays_kernel instantiation cgrt_occlusion_rays would launch for (scene, rays); only rays->flags matters. */
+int cgrt_occlusion_rays_variant(const cgrt_scene *s, const cgrt_rays *rays, char *name, size_t cap);
 
 /* The primary rays cgrt_trace_grid starts for sample `sample_offset + k`, k in [0, spp), of every pixel of the grid's rows
  * (contiguous or striped): ray index = (k * rows + local row) * width + w.  org3 / dir3 / keys as in cgrt_rays (any may be

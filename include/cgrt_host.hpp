@@ -401,6 +401,34 @@ inline void hit_attributes(const std::vector<Object *> &objs, const std::vector<
     check(cgrt_ray_hit_attributes_host(sb.scene, &r, hits.obj.data(), hits.t.data(), &out));
 }
 
+// "Is anything between these two points?" (cgrt_occlusion_rays_host): occ[i] = 1 exactly when some object's intersect() gives
+// a length < tmax[i] for ray i -- the nearest hit trace_rays would report lies before tmax[i] --, else 0.  An empty tmax means
+// no limit.  skip_transparent: objects with transparency >= 1e-4 block nothing (shadow rays through glass).  `seed` keys the
+// Bezier draws as trace_rays' does.
+inline void occluded(const std::vector<Object *> &objs, const std::vector<double> &org3, const std::vector<double> &dir3,
+                     const std::vector<double> &tmax, std::vector<uint8_t> &occ, bool skip_transparent = false, uint64_t seed = 12345,
+                     int device = 0) {
+    if (org3.size() != dir3.size() || org3.size() % 3) throw Error(CGRT_ERR_INVALID, "occluded: org3 / dir3 are n x 3 doubles");
+    const size_t n = org3.size() / 3;
+    if (!tmax.empty() && tmax.size() != n) throw Error(CGRT_ERR_INVALID, "occluded: tmax holds one entry per ray, or none");
+    occ.assign(n, 0);
+    if (n == 0) return;
+    SceneBuilder sb;
+    for (const Object *o : objs) o->add_to(sb);
+    check(cgrt_scene_commit(sb.scene, device));
+    cgrt_rays r{};
+    r.n = (int64_t)n;
+    r.org3 = org3.data();
+    r.dir3 = dir3.data();
+    r.seed = seed;
+    r.max_depth = 1;
+    r.flags = skip_transparent ? CGRT_RAYS_SKIP_TRANSPARENT : 0;
+    cgrt_occlusion out{};
+    out.tmax = tmax.empty() ? nullptr : tmax.data();
+    out.occluded = occ.data();
+    check(cgrt_occlusion_rays_host(sb.scene, &r, &out, nullptr));
+}
+
 // ---- the whole of render() + main()'s PNG loop: main.cpp:169-258, 403-412 ---------------------------------------
 // Photon-pass constants of the reference as runtime fields with the same defaults.
 struct PhotonParams {
