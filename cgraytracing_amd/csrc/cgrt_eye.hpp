@@ -4,6 +4,7 @@
 #include "cgrt_lens_stage.h"
 #include "cgrt_scene_walk.hpp"
 #include "cgrt_sphere_mask.h"
+#include "cgrt_sure_first.h"
 
 // =====================================================================================================
 // the eye pass
@@ -234,6 +235,14 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
         smask = load_uniform(g.wmask + __builtin_amdgcn_readfirstlane(have_tile ? wy * wtiles_x + wx : 0));
         if (sc.n_lds < 32) smask &= (1u << sc.n_lds) - 1u;
     }
+    // DIFF: the sphere every primary ray of this wave tile hits first, where sure_first_kernel has proven one (GridParams::wsure;
+    // wave-uniform, the byte's word read through the scalar cache): kSureNone -- trace
+    uint32_t sure = (uint32_t)kSureNone;
+    if (DIFF && g.wsure != nullptr && have_tile) {
+        const uint32_t wt = (uint32_t)__builtin_amdgcn_readfirstlane(wy * wtiles_x + wx);
+        sure = (load_uniform(reinterpret_cast<const uint32_t *>(g.wsure) + (wt >> 2)) >> ((wt & 3u) * 8u)) & 0xffu;
+        if (sure >= (uint32_t)sc.n_lds) sure = (uint32_t)kSureNone;
+    }
     uint64_t k_smp = 0;  // key of the sample whose ray tree this lane is tracing
 
     double acc_r = 0, acc_g = 0, acc_b = 0;
@@ -321,6 +330,23 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
     // (wave-uniform); a lane remembers the item of the unit it is tracing in unit_rank (the wave may have moved on)
     bool queue_empty = false;
     unsigned item_ahead = 0, n_items_total = 0;
+    if (DIFF && sure != (uint32_t)kSureNone) {
+        // A sure wave tile: every ray of every sample of every live lane ends on sphere `sure` and contributes its colour, so the
+        // sample loop below has nothing to decide.  What it would have done is done here -- hf added once per sample, one
+        // addition after the other (the sums' bits are the loop's), a ray and a Hitpoint counted per lane and sample, an iteration
+        // per sample while any lane is live -- and with s at s_end the loop is left at its first test: no lens draw, no staging.
+        const V3 hf = load_mat<false>(lobjs, sc.n_lds, sc.objs, (int)sure).col;
+        if (__ballot(live && s < s_end) != 0ull) wave_iters += (uint32_t)(s_end - s);
+        if (live) {
+            for (int k = s; k < s_end; k++) {
+                acc_r += hf.x;
+                acc_g += hf.y;
+                acc_b += hf.z;
+            }
+            if (s < s_end) my_hits = my_rays = (uint32_t)(s_end - s);
+        }
+        s = s_end;
+    }
     if (heavy) {
         n_items_total = load_uniform(g.plan) * (unsigned)g.items_per_tile;
         if (lane == 0) item_ahead = atomicAdd(&g.plan[2], 1u);
@@ -1048,6 +1074,26 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(GridParams g, OrderSph
         plan[kOrderClasses] = (uint32_t)n;
         plan[kOrderArrived] = 0;
     }
+}
+
+// Sure tiles (wsure, GridParams::wsure; behind tile_order_kernel on its stream, where the launch has sphere masks): one thread per wave
+// tile.  A wave tile of a class-3 TILE -- the terminal-diffuse body renders no other, and only tile_order_kernel's last workgroup
+// knows the tiles' classes, which is why this is a kernel of its own -- gets the sphere that every primary ray of it hits first
+// (sphere_sure_first, cgrt_sure_first.h, over the wave tile's mask), every other wave tile kSureNone.
+__global__ __launch_bounds__(256) void sure_first_kernel(GridParams g, DeviceScene sc, int tiles_x, const unsigned char *__restrict__ tcls,
+                                                         const uint32_t *__restrict__ wmask, unsigned char *__restrict__ wsure) {
+    const int wtiles_x = (g.W + kWaveTileW - 1) / kWaveTileW, wtiles_y = (g.rows + kWaveTileH - 1) / kWaveTileH;
+    const int wt = blockIdx.x * blockDim.x + threadIdx.x;
+    if (wt >= wtiles_x * wtiles_y) return;
+    const int wx = wt % wtiles_x, wy = wt / wtiles_x;
+    int win = -1;
+    if (tcls[(wy / (kTileH / kWaveTileH)) * tiles_x + wx / (kTileW / kWaveTileW)] == 3) {
+        const TileRays tr = wave_tile_rays(g, wx, wy);
+        const ObjRec *objs = sc.objs;
+        win = sphere_sure_first(g, tr, sc.n_objs, [objs](int i) { return SureSphere{vec3d(objs[i].a[0], objs[i].a[1], objs[i].a[2]), objs[i].s0}; },
+                                wmask[wt]);
+    }
+    wsure[wt] = (unsigned char)(win >= 0 ? win : kSureNone);
 }
 
 // ---- cost-aware scheduling: plan and ordered sum (GridParams, "Cost-aware scheduling") ------------------------------------

@@ -98,14 +98,18 @@ struct GridParams {
     // lens_batch != 0 (the PAIR variants' kOrderAllDiffuse launch of a thin-lens camera): a wave of the terminal-diffuse body inside
     // that launch stages the lens draws of its next kLensBatch samples per lane in LDS (cgrt_lens_stage.h); 0: lens_disc per sample
     int32_t lens_batch, pad_;
+    // wsure != nullptr (tile-order launches that have masks, unless switched off): wsure[wave tile] = the sphere that EVERY primary
+    // ray of the wave tile hits first (sure_first_kernel, cgrt_sure_first.h), or kSureNone; set only for wave tiles of class-3
+    // tiles.  A wave of the terminal-diffuse body whose tile has one adds that sphere's colour per sample and traces nothing.
+    const unsigned char *wsure;
 };
-static_assert(sizeof(GridParams) == 328, "GridParams is a kernel argument: its layout is fixed");
+static_assert(sizeof(GridParams) == 336, "GridParams is a kernel argument: its layout is fixed");
 
 static constexpr int kTileW = 32, kTileH = 8, kThreads = 256;
 // Tile order of image-order launches (tile_order_kernel, cgrt_eye.hpp): the special spheres -- those that reflect or refract --
 // travel as a kernel argument; a scene with more of them than this is left in row-major order.  The handle's order buffer (TileOrderLayout) is
 // plan[kOrderPlanWords] | list[n_tiles] | tile class[n_tiles] (bytes) | wave-tile class[n_wt] (bytes) | wave-tile sphere mask[n_wt]
-// (words; GridParams::wmask), each part padded to 256 bytes; plan[c], c = 0..4 = tiles of classes < c, plan[kOrderArrived] = the
+// (words; GridParams::wmask) | wave-tile sure sphere[n_wt] (bytes; GridParams::wsure; only where asked for), each part padded to 256 bytes; plan[c], c = 0..4 = tiles of classes < c, plan[kOrderArrived] = the
 // workgroups of tile_order_kernel that are through (0 between launches).
 static constexpr int kOrderSpheresMax = 16, kOrderClasses = 4, kOrderPlanWords = 8, kOrderArrived = 5;
 static constexpr int kOrderAll = 1, kOrderFull = 2, kOrderDiffuse = 3, kOrderAllDiffuse = 4;  // GridParams::tile_order
@@ -121,10 +125,10 @@ struct Region {
 };
 // Where the parts of the order buffer lie, in bytes from its start
 struct TileOrderLayout {
-    Region plan{}, list{}, tile_cls{}, wave_cls{}, wmask{};
+    Region plan{}, list{}, tile_cls{}, wave_cls{}, wmask{}, wsure{};
     size_t total = 0;  // bytes to allocate
 };
-inline TileOrderLayout tile_order_layout(size_t n_tiles, size_t n_wt) {
+inline TileOrderLayout tile_order_layout(size_t n_tiles, size_t n_wt, bool sure = false) {
     TileOrderLayout L;
     size_t end = 0;  // the list follows the plan at once; every other part starts on 256 bytes
     const auto take = [&end](size_t bytes) { end += bytes; return Region{end - bytes, bytes}; };
@@ -136,6 +140,10 @@ inline TileOrderLayout tile_order_layout(size_t n_tiles, size_t n_wt) {
     L.wave_cls = take(n_wt);
     end = align256(end);
     L.wmask = take(n_wt * sizeof(uint32_t));
+    if (sure) {  // (read a word at a time: the part ends on 256 bytes like the others)
+        end = align256(end);
+        L.wsure = take(n_wt);
+    }
     L.total = align256(end);
     return L;
 }
@@ -212,6 +220,7 @@ struct EyeKnobs {
     int pw_refill = 16, pw_rounds = 8;
     int lds_pad = 0;  // LDS_PAD: extra dynamic LDS bytes of the main launch
     bool no_hfonly = false, no_tile_queue = false, plan_dump = false;
+    bool no_sure_tiles = false;   // NO_SURE_TILES: as CGRT_GRID_NO_SURE_TILES on every launch (a measurement aid)
     bool no_order_reuse = false;  // NO_ORDER_REUSE: tile_order_kernel in front of every tile-order launch (order_tiles)
     int relay_chunks = kRelayDefaultChunks;  // RELAY_CHUNKS: most workgroups a relayed tile's samples are cut into (2..4)
     long long relay_tiles = 0;           // RELAY_TILES: > 0: at most this many tiles are relayed (the relay area's capacity)
@@ -258,6 +267,7 @@ inline EyeKnobs eye_knobs() {
         k.no_tile_queue = env_on("CGRT_NO_TILE_QUEUE");
         k.plan_dump = env_on("CGRT_PLAN_DUMP");
         k.no_order_reuse = env_on("CGRT_NO_ORDER_REUSE");
+        k.no_sure_tiles = env_on("CGRT_NO_SURE_TILES");
         k.relay_chunks = std::min(std::max(env_positive("CGRT_RELAY_CHUNKS", kRelayDefaultChunks), 2), kRelayMaxChunks);
         k.relay_tiles = std::atoll(env_str("CGRT_RELAY_TILES"));
         if (*env_str("CGRT_RELAY_MIRROR")) k.relay_mirror = env_on("CGRT_RELAY_MIRROR") ? 1 : 0;
@@ -328,6 +338,9 @@ struct TileOrderPlan {
     // terminal-diffuse body inside the PAIR variant (kOrderAllDiffuse)
     enum Class3 { None, SecondLaunch, InKernel } class3 = None;
     bool masks = false;  // tile_order_kernel writes the wave tiles' sphere masks (GridParams::wmask)
+    // sure_first_kernel writes the sphere every ray of a class-3 wave tile hits first (GridParams::wsure): wherever there are masks,
+    // unless CGRT_GRID_NO_SURE_TILES or the knob CGRT_NO_SURE_TILES switches it off
+    bool sure = false;
     // kLensStageLds: the terminal-diffuse body inside the launch stages its lens draws in batches (GridParams::lens_batch)
     int lens_stage = kLensStageOff;
 };
@@ -426,6 +439,7 @@ inline FramePlan frame_plan(const FrameInputs &in, size_t kmax) {
     }
     o.masks = o.class3 != TileOrderPlan::None && in.all_spheres && in.n_objs <= kSphereMaskMax && in.n_objs == in.n_lds &&
               !(gr.flags & CGRT_GRID_NO_SPHERE_MASKS);
+    o.sure = o.masks && !(gr.flags & CGRT_GRID_NO_SURE_TILES) && !kn.no_sure_tiles;
     // Lens stage: the thin-lens terminal-diffuse body INSIDE the launch, whose batches lie in the launch's pending-ray levels;
     // the second launch's variant asks for no such LDS and draws sample by sample.  CGRT_GRID_NO_LENS_STAGE switches it off;
     // otherwise the knob CGRT_LENS_STAGE holds, and the default where it names nothing.

@@ -1077,6 +1077,11 @@ int cgrt_scene_last_sphere_masks(const cgrt_scene *s, uint32_t *masks, int64_t c
     ON_DEVICE(s->device);
     return last_sphere_masks(s->order, masks, cap, n_wave_tiles);
 }
+int cgrt_scene_last_sure_tiles(const cgrt_scene *s, uint8_t *sure, int64_t cap, int64_t *n_wave_tiles) {
+    NEED_COMMITTED(s, n_wave_tiles);
+    ON_DEVICE(s->device);
+    return last_sure_tiles(s->order, sure, cap, n_wave_tiles);
+}
 int cgrt_scene_last_tile_order_reused(const cgrt_scene *s, int32_t *reused) {
     NEED_COMMITTED(s, reused);
     *reused = s->order.reused ? 1 : 0;

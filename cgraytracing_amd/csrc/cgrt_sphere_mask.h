@@ -132,6 +132,7 @@ CGRT_HD Interval unit_component(Interval k, Interval a, Interval b) {
 struct TileRays {   // the boxes around a wave tile's primary rays
     Interval o[3];  // origins
     Interval d[3];  // directions
+    Interval q[3];  // targets: the focal-plane points (lens) or image-plane points (pinhole) every ray of the tile passes through
     bool ok;        // false: no bound (f <= 0 with a lens, something not finite): every sphere is a candidate
     TileCone cone;
 };
@@ -162,6 +163,7 @@ CGRT_HD TileRays wave_tile_rays(const GridParams &g, int wx, int wy) {
         q[2].lo = fmin(q[2].lo, p.z); q[2].hi = fmax(q[2].hi, p.z);
     }
     Interval v[3];
+    for (int k = 0; k < 3; k++) t.q[k] = q[k];
     for (int k = 0; k < 3; k++) v[k] = Interval{q[k].lo - t.o[k].hi, q[k].hi - t.o[k].lo};
     t.d[0] = unit_component(v[0], v[1], v[2]);
     t.d[1] = unit_component(v[1], v[0], v[2]);

@@ -18,7 +18,8 @@ static Capturing stream_capturing(hipStream_t st) {
 // Tile order of image-order launches (tile_order_kernel): the scene's reflecting / refracting spheres (read at commit; ok: the
 // scene is spheres and planes with 1..kOrderSpheresMax of them), the order buffer (TileOrderLayout) -- launch scratch like the
 // handle's `scratch`, kept apart so that the frame plan's layout stays what it is -- and what the last cgrt_trace_grid did: the
-// tiles it ordered (0: none), the wave tiles it wrote sphere masks for (0: none), where the parts lie, and who rendered class 3.
+// tiles it ordered (0: none), the wave tiles it wrote sphere masks for (0: none) and sure spheres for (0: none), where the parts
+// lie, and who rendered class 3.  Key::masks: bit 0 -- masks asked for, bit 1 -- sure tiles asked for.
 // What the buffer holds: the order depends on nothing but Key, so a launch with the key of the buffer's contents runs no
 // ordering kernel (reused).  ev is recorded behind the kernel on `stream`; a reusing launch on another stream waits for it.
 // commit_gen: this commit's number.
@@ -39,13 +40,13 @@ struct TileOrderState {
     bool captured = false;  // a launch on this handle was captured into a graph: its replays rewrite the buffer at times the handle does not see, so nothing is reused any more
     hipEvent_t ev = nullptr;
     hipStream_t stream = nullptr;
-    size_t tiles = 0, mask_wtiles = 0;
+    size_t tiles = 0, mask_wtiles = 0, sure_wtiles = 0;
     TileOrderLayout at;
     TileOrderPlan::Class3 class3 = TileOrderPlan::None;
     int lens_stage = kLensStageOff;  // how that launch's in-kernel terminal-diffuse body drew its lens points
 
     void begin_launch() {
-        tiles = mask_wtiles = 0;
+        tiles = mask_wtiles = sure_wtiles = 0;
         reused = false;
         class3 = TileOrderPlan::None;
         lens_stage = kLensStageOff;
@@ -90,7 +91,8 @@ struct RelayState {
 // The tile order of an image-order launch over a scene with reflecting or refracting spheres (tile_order_kernel, cgrt_eye.hpp):
 // one small launch in front of the eye launch, on its stream, that lists the tiles the costly ones first; g then maps the
 // eye launch's workgroups through the list.  The buffer is launch scratch of the handle, written and read on this stream.
-// p.order.masks: the launch also writes the wave tiles' sphere masks (GridParams::wmask) for the terminal-diffuse body.
+// p.order.masks: the launch also writes the wave tiles' sphere masks (GridParams::wmask) for the terminal-diffuse body;
+// p.order.sure: sure_first_kernel follows it and writes the sure spheres (GridParams::wsure), kept and reused with the rest.
 // The kernel reads the camera, the frame geometry (W, H, rows, row offset, stripe) and the committed scene, nothing else: when
 // the buffer still holds the result for exactly these (TileOrderState::Key -- the passes of a progressive render, the frames of
 // a still camera) nothing is launched and g points at it.  The eye launch only reads the buffer (plan[0..4], the list, the
@@ -105,8 +107,9 @@ static int order_tiles(TileOrderState &o, const DeviceScene &dev, const FramePla
                        hipStream_t st) {
     const int tiles_x = (g.W + kTileW - 1) / kTileW, tiles_y = (g.rows + kTileH - 1) / kTileH;
     const size_t n = (size_t)tiles_x * tiles_y;
-    const TileOrderLayout at = tile_order_layout(n, p.n_wt);
-    const bool grown = at.total > o.buf.cap, masks = p.order.masks;
+    const bool masks = p.order.masks, sure = masks && p.order.sure;
+    const TileOrderLayout at = tile_order_layout(n, p.n_wt, sure);
+    const bool grown = at.total > o.buf.cap;
     if (grown) o.valid = false;
     if (o.buf.need(at.total) != hipSuccess) {
         (void)hipGetLastError();
@@ -115,8 +118,9 @@ static int order_tiles(TileOrderState &o, const DeviceScene &dev, const FramePla
     unsigned char *base = reinterpret_cast<unsigned char *>(o.buf.p);
     uint32_t *plan = at.plan.in<uint32_t>(base), *list = at.list.in<uint32_t>(base);
     uint32_t *wmask = masks ? at.wmask.in<uint32_t>(base) : nullptr;
+    unsigned char *wsure = sure ? at.wsure.in<unsigned char>(base) : nullptr;
     const TileOrderState::Key key{{g.cam[0], g.cam[1], g.cam[2]}, g.half_width, g.focus_plane, g.lens_radius, g.W, g.H, g.rows, g.row_offset,
-                                  g.stripe_rows, g.stripe_rank, g.stripe_nranks, masks ? 1 : 0, o.commit_gen, o.buf.p};
+                                  g.stripe_rows, g.stripe_rank, g.stripe_nranks, (masks ? 1 : 0) | (sure ? 2 : 0), o.commit_gen, o.buf.p};
     if (capturing != Capturing::None) o.captured = true;
     const bool plain = !o.captured && !no_reuse;
     o.reused = plain && o.valid && std::memcmp(&key, &o.key, sizeof(key)) == 0;
@@ -128,6 +132,9 @@ static int order_tiles(TileOrderState &o, const DeviceScene &dev, const FramePla
         const unsigned blocks = (unsigned)std::min((p.n_wt + 1023) / 1024, (size_t)64);
         hipLaunchKernelGGL(tile_order_kernel, dim3(blocks), dim3(1024), 0, st, g, o.spheres, dev, tiles_x, tiles_y, plan, list,
                            at.tile_cls.in<unsigned char>(base), at.wave_cls.in<unsigned char>(base), wmask);
+        if (sure)
+            hipLaunchKernelGGL(sure_first_kernel, dim3((unsigned)((p.n_wt + 255) / 256)), dim3(256), 0, st, g, dev, tiles_x,
+                               at.tile_cls.in<unsigned char>(base), wmask, wsure);
         if (plain && hipPeekAtLastError() == hipSuccess) {
             if (!o.ev && hipEventCreateWithFlags(&o.ev, hipEventDisableTiming) != hipSuccess) {
                 (void)hipGetLastError();
@@ -145,9 +152,11 @@ static int order_tiles(TileOrderState &o, const DeviceScene &dev, const FramePla
     g.plan = plan;
     g.border = list;
     g.wmask = wmask;
+    g.wsure = wsure;
     g.tile_order = kOrderAll;
     o.tiles = n;
     o.mask_wtiles = masks ? p.n_wt : 0;
+    o.sure_wtiles = sure ? p.n_wt : 0;
     o.at = at;
     o.class3 = p.order.class3;
     o.lens_stage = p.order.lens_stage;
@@ -246,6 +255,13 @@ static int last_sphere_masks(const TileOrderState &o, uint32_t *masks, int64_t c
     if (n_wt == 0 || o.tiles == 0 || !masks || cap < (int64_t)n_wt) return CGRT_OK;
     HIP_TRY(hipDeviceSynchronize());
     return o.read(o.at.wmask, masks, n_wt);
+}
+static int last_sure_tiles(const TileOrderState &o, uint8_t *sure, int64_t cap, int64_t *n_wave_tiles) {
+    const size_t n_wt = o.sure_wtiles;
+    *n_wave_tiles = (int64_t)n_wt;
+    if (n_wt == 0 || o.tiles == 0 || !sure || cap < (int64_t)n_wt) return CGRT_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    return o.read(o.at.wsure, sure, n_wt);
 }
 // the class-3 tiles of the last launch's order, when that launch gave them to the terminal-diffuse body in the form asked for
 static int last_class3_tiles(const TileOrderState &o, TileOrderPlan::Class3 form, int64_t *n_tiles) {

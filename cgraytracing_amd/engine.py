@@ -179,7 +179,7 @@ class Scene:
                    stripe=None, sample_offset=0, spp_total=None, out=None, nhit=None, counters=None, stream=None,
                    stats=False, accumulate=False, split_samples=False, reorder=True, force_reorder=False, tile_order=True,
                    diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None,
-                   relay_mirror=None, relay_order=None, lens_stage=True):
+                   relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True):
         """Asynchronous launch on torch's current stream (or `stream`).  reorder=False: CGRT_GRID_NO_REORDER (tiles in image
         order instead of heaviest-first; same image).  tile_order=False: CGRT_GRID_NO_TILE_ORDER (an image-order launch starts
         its tiles row-major instead of mirror / glass tiles first; same image).  diffuse_tiles=True: CGRT_GRID_DIFFUSE_TILES (a
@@ -195,7 +195,9 @@ class Scene:
         those tiles' workgroups start among the glass tiles'; None: what sample_relay has always meant when it is given, the
         measured form when it is not (last_relay_form tells).  lens_stage=False: CGRT_GRID_NO_LENS_STAGE (the thin-lens
         terminal-diffuse body inside the main launch draws every lens point by its own rejection loop instead of staging 16
-        samples' draws ahead; same image; last_lens_stage).  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
+        samples' draws ahead; same image; last_lens_stage).  sure_tiles=False: CGRT_GRID_NO_SURE_TILES (a wave of the
+        terminal-diffuse body traces its samples even where every ray of its 16x4 wave tile provably hits the same sphere first;
+        same image, hit counts and counters; sphere_masks=False implies it; last_sure_tiles).  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
         workgroups share a tile's samples; reproducible, fp64 summation order differs from the sample-by-sample sum).  Returns (rgb, nhit, counters) torch
         tensors on the scene's device: float32 [rows,width,3], int32 [rows,width] (bit pattern uint32),
         int64 [8] (counters are ADDED to)."""
@@ -216,7 +218,7 @@ class Scene:
                               spp_total, (1 if stats else 0) | (2 if accumulate else 0) | (4 if split_samples else 0) |
                               (0 if reorder else 8) | (16 if force_reorder else 0) | (0 if tile_order else 64) |
                               (128 if diffuse_tiles else 0) | (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order) |
-                              (0 if lens_stage else 131072))
+                              (0 if lens_stage else 131072) | (0 if sure_tiles else 262144))
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         check(self._L.cgrt_trace_grid(self._h, C.byref(cc), C.byref(g), out.data_ptr(),
                                       nhit.data_ptr() if nhit is not None else None,
@@ -503,7 +505,7 @@ class Scene:
     def trace_grid_host(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                         stripe=None, sample_offset=0, spp_total=None, stats=False, split_samples=False, reorder=True,
                         force_reorder=False, tile_order=True, diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None,
-                        relay_mirror=None, relay_order=None, lens_stage=True):
+                        relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True):
         """Synchronous form with numpy outputs (no torch needed): dict(rgb, nhit, counters)."""
         rows = height - row_offset if rows is None else rows
         rgb = np.zeros((rows, width, 3), np.float32)
@@ -513,7 +515,7 @@ class Scene:
                               spp_total, (1 if stats else 0) | (4 if split_samples else 0) | (0 if reorder else 8) |
                               (16 if force_reorder else 0) | (0 if tile_order else 64) | (128 if diffuse_tiles else 0) |
                               (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order) |
-                              (0 if lens_stage else 131072))
+                              (0 if lens_stage else 131072) | (0 if sure_tiles else 262144))
         check(self._L.cgrt_trace_grid_host(self._h, C.byref(cc), C.byref(g), rgb.ctypes.data, nhit.ctypes.data,
                                            cnt.ctypes.data))
         return dict(rgb=rgb, nhit=nhit, counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]),
@@ -542,6 +544,18 @@ class Scene:
         masks = np.zeros(n.value, np.uint32)
         check(self._L.cgrt_scene_last_sphere_masks(self._h, masks.ctypes.data, n.value, C.byref(n)))
         return masks
+
+    def last_sure_tiles(self):
+        """The sure tiles of this scene's last trace_grid / trace_grid_host (cgrt_scene_last_sure_tiles; synchronises the device):
+        None when that launch wrote none, else uint8 [wave tiles]: the sphere every primary ray of the 16x4 wave tile
+        wy * ceil(width / 16) + wx hits first, or 255 (none proven, or its 32x8 tile is not of class 3)."""
+        n = C.c_int64()
+        check(self._L.cgrt_scene_last_sure_tiles(self._h, None, 0, C.byref(n)))
+        if n.value == 0:
+            return None
+        sure = np.zeros(n.value, np.uint8)
+        check(self._L.cgrt_scene_last_sure_tiles(self._h, sure.ctypes.data, n.value, C.byref(n)))
+        return sure
 
     def last_tile_order_reused(self):
         """True when this scene's last trace_grid / trace_grid_host ran no ordering kernel because the handle still held the

@@ -157,6 +157,14 @@ enum {
                                  the pace of the wave's unluckiest lane.  The same lens points: same image, hit counts and
                                  counters either way; it exists to test one against the other.  The second launch of
                                  CGRT_GRID_DIFFUSE_TILES always draws sample by sample                                    */
+    CGRT_GRID_NO_SURE_TILES = 262144, /* the terminal-diffuse body, where it has sphere masks (see CGRT_GRID_NO_SPHERE_MASKS, which
+                                 implies this flag): by default a second small kernel behind the ordering kernel proves, per
+                                 16x4-pixel wave tile of a class-3 tile, whether every primary ray of it -- any pixel, any lens
+                                 point -- hits one and the same sphere first (most wave tiles that lie inside one wall), and
+                                 such a wave adds that sphere's colour once per sample, addition after addition, without
+                                 tracing anything (cgrt_scene_last_sure_tiles).  This flag restores the sample loop.  Same
+                                 image, hit counts and counters either way -- CGRT_CNT_RAYS keeps counting the rays the loop
+                                 would have traced; it exists to test one against the other                              */
     CGRT_GRID_HITPOINTS = 32, /* cgrt_trace_grid_variant only: name the launch of the Hitpoint capture
                                  (cgrt_trace_grid_hitpoints, the eye pass of cgrt_ppm_render) instead of cgrt_trace_grid's;
                                  ignored by the other calls                                                            */
@@ -665,6 +673,10 @@ int cgrt_scene_last_tile_order(const cgrt_scene *s, uint32_t *plan5, uint32_t *l
  * cap >= *n_wave_tiles: synchronises the device and copies them to HOST memory; bit i of masks[wave tile] = sphere i (in the
  * order the objects were added) may be met by a primary ray of the wave tile. */
 int cgrt_scene_last_sphere_masks(const cgrt_scene *s, uint32_t *masks, int64_t cap, int64_t *n_wave_tiles);
+/* The sure tiles of that launch (see CGRT_GRID_NO_SURE_TILES), in the same form: sure[wave tile] = the sphere every primary ray of
+ * the wave tile hits first, or 255 -- none proven, or the wave tile's 32x8 tile is not of class 3.  *n_wave_tiles = 0 when the
+ * launch wrote none. */
+int cgrt_scene_last_sure_tiles(const cgrt_scene *s, uint8_t *sure, int64_t cap, int64_t *n_wave_tiles);
 /* Whether the LAST cgrt_trace_grid on the handle ran no ordering kernel because the order (and masks) it had computed for the
  * same camera, frame geometry, rows and stripe were still in the handle's buffer: *reused = 1, else 0.  An order depends on
  * nothing else -- not on the seed, the samples or the depth -- so the passes of a progressive render compute it once.
