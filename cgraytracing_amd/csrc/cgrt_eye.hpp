@@ -107,10 +107,12 @@ struct RelayWg {
 // PARK (PAIR variants, chunks >= 1 of a relayed tile): a Hitpoint value is not added but stored, slot after slot, in the lane's
 // stream of the relay area; the body keeps no sums.  A relayed workgroup (rw.slot >= 0; PAIR with or without PARK) leaves its
 // sums or counts in the area, and the last of the tile's workgroups to arrive adds them up in chunk order and stores the pixels.
+// COST (the PAIR variants with a start table, trace_grid_kernel's START): the body also serves as the relay's cost probe
+// (g.probe == 2) and leaves the wave's iteration count; every other variant is spared the test.
 // LSTAGE (DIFF with DOF, the body inside the PAIR variants' launch only): with g.lens_batch the wave stages its lens draws in
 // batches (cgrt_lens_stage.h), in the part of the launch's LDS that holds the PAIR body's pending-ray levels.
 template <bool TREES, bool BEZ, bool DOF, bool GLASS, bool SPH, bool STATS, bool HPS, int NT, bool HEAVY, bool SPILL = false, bool HFONLY = false,
-          bool DIFF = false, bool PAIR = false, bool PARK = false, bool LSTAGE = false>
+          bool DIFF = false, bool PAIR = false, bool PARK = false, bool LSTAGE = false, bool COST = false>
 __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const GridParams &g, float *__restrict__ rgb,
                                                 uint32_t *__restrict__ nhit_out, unsigned long long *__restrict__ counters,
                                                 const HitpointSink &hps, int tile_block, int tile_grid, const RelayWg rw = RelayWg{}) {
@@ -119,6 +121,7 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
     static_assert(!DIFF || (SPH && !GLASS && !HPS && !HEAVY && !STATS && !SPILL), "DIFF: the sphere loop, first hits only");
     static_assert(!PAIR || (SPH && GLASS && !HPS && !HEAVY && !STATS && !SPILL), "PAIR: the glass sphere variants of the tile order");
     static_assert(!LSTAGE || (DIFF && DOF && !PAIR), "LSTAGE: the thin-lens terminal-diffuse body inside a PAIR launch");
+    static_assert(!COST || PAIR, "COST: the PAIR variants with a start table");
     // (the launch asked for the PAIR body's LDS -- pending-ray levels, then the object list; this body's object list lies at the
     // start and its batches behind it: they fit where the levels are, so the request and the occupancy stay what they were)
     static_assert(!LSTAGE || lens_batch_lds(NT) <= (size_t)kLdsLevels * pending_level_bytes(NT), "the lens batches fit the PAIR launch's pending-ray levels");
@@ -626,7 +629,8 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
         if (lane == 0 && have_tile) {
             const long long dt = (long long)clock64() - cost_t0;
             const uint32_t wt = (uint32_t)(wy * wtiles_x + wx);
-            g.cost[wt] = dt > 0 ? (dt < 0xffffffffll ? (uint32_t)dt : 0xffffffffu) : 1u;
+            // (probe == 2, the relay's cost start, COST variants only: the wave's iterations, which no clock enters)
+            g.cost[wt] = (COST && g.probe == 2) ? wave_iters : dt > 0 ? (dt < 0xffffffffll ? (uint32_t)dt : 0xffffffffu) : 1u;
         }
         return;  // no counters: the render launch that follows counts these rays
     }
@@ -799,7 +803,7 @@ __device__ __forceinline__ void wg_counters_end(const unsigned long long *wg, un
 
 // One launch = tile workgroups only (probe, image order, Hitpoint capture) ...
 template <bool TREES, bool BEZ, bool DOF, bool GLASS, bool SPH, bool STATS, bool HPS = false, int NT = 256, bool SPILL = false, bool HFONLY = false,
-          bool DIFF = false, bool PAIR = false>
+          bool DIFF = false, bool PAIR = false, bool START = false>
 __global__ __launch_bounds__(NT, DIFF ? (DOF ? kDiffDofWaves : kDiffWaves) : BEZ ? kBezWaves : ((TREES && !HFONLY) ? kTreeWaves : 4)) void trace_grid_kernel(DeviceScene sc, GridParams g, float *__restrict__ rgb,
                                                              uint32_t *__restrict__ nhit_out,
                                                              unsigned long long *__restrict__ counters,
@@ -822,8 +826,21 @@ __global__ __launch_bounds__(NT, DIFF ? (DOF ? kDiffDofWaves : kDiffWaves) : BEZ
             if (g.tile_order == kOrderDiffuse ? entry >= load_uniform(g.plan + kOrderClasses) : entry >= first_diffuse) return;
         } else if (PAIR && g.relay_k > 1) {
             const unsigned n_tiles = load_uniform(g.plan + kOrderClasses);
-            const RelayBlock rb = relay_block_ordered(blockIdx.x, (unsigned)g.relay_k, load_uniform(g.plan + 2), load_uniform(g.plan + 3), n_tiles,
-                                                      (unsigned)g.relay_cap, g.relay_extent, g.relay_order);
+            const unsigned n01 = load_uniform(g.plan + 2), n012 = load_uniform(g.plan + 3);
+            RelayBlock rb{n_tiles, 0, false};
+            // START (a variant of its own beside each PAIR variant: the launch with a start table and its cost probe, so that the
+            // variant without one keeps its code): the workgroups of classes 0-2 in the order the table names (cgrt_relay.h),
+            // the others as ever
+            bool tabled = false;
+            if (START && g.relay_start_at != 0u) {
+                const unsigned n_split = relay_split_entries(n01, n012, (unsigned)g.relay_cap, g.relay_extent);
+                tabled = blockIdx.x < n012 + ((unsigned)g.relay_k - 1u) * n_split;
+                if (tabled) {
+                    rb = relay_start_block(load_uniform(g.plan + g.relay_start_at + blockIdx.x), n_split);
+                    if (rb.chunk >= g.relay_k) return;  // (no table names a chunk the area has not)
+                }
+            }
+            if (!tabled) rb = relay_block_ordered(blockIdx.x, (unsigned)g.relay_k, n01, n012, n_tiles, (unsigned)g.relay_cap, g.relay_extent, g.relay_order);
             entry = rb.entry;
             if (entry >= n_tiles) return;
             if (rb.split) {
@@ -843,9 +860,9 @@ __global__ __launch_bounds__(NT, DIFF ? (DOF ? kDiffDofWaves : kDiffWaves) : BEZ
     if (PAIR && g.tile_order == kOrderAllDiffuse && entry >= load_uniform(g.plan + 3))
         trace_grid_body<false, false, DOF, false, true, false, false, NT, false, false, false, true, false, false, DOF>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid);
     else if (PAIR && rw.chunk > 0)  // a relayed tile's later chunks park their values
-        trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF, PAIR, PAIR>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid, rw);
+        trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF, PAIR, PAIR, false, START>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid, rw);
     else
-        trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF, PAIR>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid, rw);
+        trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF, PAIR, false, false, START>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid, rw);
     wg_counters_end(wg_cnt, counters);
 }
 // ... or the scheduled form: the first g.heavy_blocks workgroups serve the heavy tiles' unit queue, the others are the tile
@@ -1094,6 +1111,48 @@ __global__ __launch_bounds__(256) void sure_first_kernel(GridParams g, DeviceSce
                                 wmask[wt]);
     }
     wsure[wt] = (unsigned char)(win >= 0 ? win : kSureNone);
+}
+
+// The relay's start table by cost (cgrt_relay.h, "The start order by cost"; behind the cost probe on its stream).  Two launches of
+// ceil(words / 256) workgroups, `words` being what the host knows to bound t (relay_start_words); threads beyond t store nothing.
+// relay_weight_kernel: thread i writes weight[i] of item i.  relay_start_kernel: thread i counts the items that start before
+// item i -- all t of them, read a workgroup's worth at a time through LDS -- and writes the item's word at that rank; the order
+// is total, so the ranks are a permutation of [0, t) and every word of the table is written once.
+struct RelayStartArgs {
+    RelayItems r;
+    uint32_t tiles_x, wtiles_x, wtiles_y;
+};
+__device__ __forceinline__ RelayItems relay_items_of(const RelayStartArgs &a, const uint32_t *plan) {
+    RelayItems r = a.r;
+    r.n01 = plan[2];
+    r.n012 = plan[3];
+    r.n_tiles = plan[kOrderClasses];
+    return r;
+}
+__global__ __launch_bounds__(kRelayThreads) void relay_weight_kernel(RelayStartArgs a, const uint32_t *__restrict__ plan, const uint32_t *__restrict__ list,
+                                                                     const uint32_t *__restrict__ wcost, unsigned long long *__restrict__ weight) {
+    const RelayItems r = relay_items_of(a, plan);
+    const uint32_t i = blockIdx.x * kRelayThreads + threadIdx.x;
+    if (i >= relay_items_total(r)) return;
+    const RelayBlock b = relay_item(i, r);
+    weight[i] = relay_item_weight(b, relay_tile_cost(wcost, list[b.entry], a.tiles_x, a.wtiles_x, a.wtiles_y), r);
+}
+__global__ __launch_bounds__(kRelayThreads) void relay_start_kernel(RelayStartArgs a, const uint32_t *__restrict__ plan,
+                                                                    const unsigned long long *__restrict__ weight, uint32_t *__restrict__ start) {
+    const RelayItems r = relay_items_of(a, plan);
+    const uint32_t t = relay_items_total(r), i = blockIdx.x * kRelayThreads + threadIdx.x;
+    if (blockIdx.x * kRelayThreads >= t) return;  // the whole workgroup: no barrier is missed
+    __shared__ unsigned long long w_s[kRelayThreads];
+    const unsigned long long wi = i < t ? weight[i] : 0ull;
+    uint32_t rank = 0;
+    for (uint32_t j0 = 0; j0 < t; j0 += kRelayThreads) {
+        __syncthreads();  // every thread is done with the previous batch
+        if (j0 + threadIdx.x < t) w_s[threadIdx.x] = weight[j0 + threadIdx.x];
+        __syncthreads();
+        const uint32_t n = min((uint32_t)kRelayThreads, t - j0);
+        for (uint32_t u = 0; u < n; u++) rank += relay_item_before(w_s[u], j0 + u, wi, i) ? 1u : 0u;
+    }
+    if (i < t) start[rank] = relay_start_word(relay_item(i, r));
 }
 
 // ---- cost-aware scheduling: plan and ordered sum (GridParams, "Cost-aware scheduling") ------------------------------------

@@ -33,7 +33,8 @@ struct GridParams {
     // Cost-aware scheduling (cgrt_hip.hip, "classify -> probe -> plan -> render -> ordered sum").  The unit of
     // bookkeeping is a WAVE TILE of 16x4 pixels, numbered wy * ceil(W/16) + wx over the local rows.
     //   probe != 0 : trace this launch's first sample only to measure it -- nothing is stored except cost[wave tile] =
-    //                shader-clock ticks the wave spent on it.
+    //                shader-clock ticks the wave spent on it.  probe == 2 (the relay's cost start, cgrt_relay.h): cost[wave tile] =
+    //                the wave's iterations over the launch's samples -- a count, the same in every run.
     //   render     : order[0..K) = the HEAVY wave tiles (plan_kernel), plan[0] = K, hidx[wave tile] = rank among them or -1.
     //                The first heavy_blocks workgroups of the render launch (the unit-form body; they loop until the queue
     //                is empty) serve the heavy tiles through a queue of ITEMS (plan[2] = next item; item = heavy tile rank *
@@ -97,7 +98,10 @@ struct GridParams {
     int32_t relay_extent, relay_order;
     // lens_batch != 0 (the PAIR variants' kOrderAllDiffuse launch of a thin-lens camera): a wave of the terminal-diffuse body inside
     // that launch stages the lens draws of its next kLensBatch samples per lane in LDS (cgrt_lens_stage.h); 0: lens_disc per sample
-    int32_t lens_batch, pad_;
+    int32_t lens_batch;
+    // relay_start_at != 0 (a relaying launch with a start table, cgrt_relay.h): plan[relay_start_at + b] = entry << 2 | chunk of
+    // workgroup b < t (relay_items_total), in place of relay_block_ordered; the table is a part of the order buffer like plan
+    uint32_t relay_start_at;
     // wsure != nullptr (tile-order launches that have masks, unless switched off): wsure[wave tile] = the sphere that EVERY primary
     // ray of the wave tile hits first (sure_first_kernel, cgrt_sure_first.h), or kSureNone; set only for wave tiles of class-3
     // tiles.  A wave of the terminal-diffuse body whose tile has one adds that sphere's colour per sample and traces nothing.
@@ -126,9 +130,12 @@ struct Region {
 // Where the parts of the order buffer lie, in bytes from its start
 struct TileOrderLayout {
     Region plan{}, list{}, tile_cls{}, wave_cls{}, wmask{}, wsure{};
+    // start_words > 0 (the relay's cost start, cgrt_relay.h), behind everything else: the wave tiles' probe costs, the items'
+    // weights (8 bytes each) and the start table, start_words each of the two
+    Region wcost{}, weight{}, start{};
     size_t total = 0;  // bytes to allocate
 };
-inline TileOrderLayout tile_order_layout(size_t n_tiles, size_t n_wt, bool sure = false) {
+inline TileOrderLayout tile_order_layout(size_t n_tiles, size_t n_wt, bool sure = false, size_t start_words = 0) {
     TileOrderLayout L;
     size_t end = 0;  // the list follows the plan at once; every other part starts on 256 bytes
     const auto take = [&end](size_t bytes) { end += bytes; return Region{end - bytes, bytes}; };
@@ -143,6 +150,14 @@ inline TileOrderLayout tile_order_layout(size_t n_tiles, size_t n_wt, bool sure 
     if (sure) {  // (read a word at a time: the part ends on 256 bytes like the others)
         end = align256(end);
         L.wsure = take(n_wt);
+    }
+    if (start_words) {
+        end = align256(end);
+        L.wcost = take(n_wt * sizeof(uint32_t));
+        end = align256(end);
+        L.weight = take(start_words * sizeof(uint64_t));
+        end = align256(end);
+        L.start = take(start_words * sizeof(uint32_t));
     }
     L.total = align256(end);
     return L;
@@ -226,6 +241,8 @@ struct EyeKnobs {
     long long relay_tiles = 0;           // RELAY_TILES: > 0: at most this many tiles are relayed (the relay area's capacity)
     int relay_mirror = -1;  // RELAY_MIRROR: 0 / 1: the relay's extent where the launch's flags name none (-1: unset)
     int relay_order = -1;   // RELAY_ORDER: chunks_first / mirror_first / interleaved (or 0 / 1 / 2), likewise
+    int relay_start = -1;   // RELAY_START: list / cost (kRelayStartList / kRelayStartCost), where the launch's flags name neither (-1: unset)
+    int relay_probe_spp = kRelayProbeSpp;  // RELAY_PROBE_SPP: samples of the cost probe (1, 2 or 4; a measurement aid)
     int lens_stage = -1;    // LENS_STAGE: off / lds (kLensStageOff / kLensStageLds), where the launch's flags do not switch it off (-1: unset)
     const char *timeline_file = nullptr;  // TIMELINE_FILE (nullptr: off)
 };
@@ -238,6 +255,13 @@ inline int relay_order_named(const char *e) {
     if (v == "chunks_first" || v == "0") return kRelayChunksFirst;
     if (v == "mirror_first" || v == "1") return kRelayMirrorFirst;
     if (v == "interleaved" || v == "2") return kRelayInterleaved;
+    return -1;
+}
+// CGRT_RELAY_START's value; -1: none of them
+inline int relay_start_named(const char *e) {
+    const std::string v(e);
+    if (v == "list" || v == "0") return kRelayStartList;
+    if (v == "cost" || v == "1") return kRelayStartCost;
     return -1;
 }
 // Lens points staged ahead of the sample loop (cgrt_lens_stage.h; TileOrderPlan::lens_stage): per-lane batches in LDS
@@ -272,6 +296,13 @@ inline EyeKnobs eye_knobs() {
         k.relay_tiles = std::atoll(env_str("CGRT_RELAY_TILES"));
         if (*env_str("CGRT_RELAY_MIRROR")) k.relay_mirror = env_on("CGRT_RELAY_MIRROR") ? 1 : 0;
         k.relay_order = relay_order_named(env_str("CGRT_RELAY_ORDER"));
+        k.relay_start = relay_start_named(env_str("CGRT_RELAY_START"));
+        if (k.relay_start < 0 && *env_str("CGRT_RELAY_START"))
+            std::fprintf(stderr, "cgrt: CGRT_RELAY_START=%s names no start order of this library (list, cost): the default is used\n", env_str("CGRT_RELAY_START"));
+        {
+            const int ps = std::atoi(env_str("CGRT_RELAY_PROBE_SPP"));
+            if (ps == 1 || ps == 2 || ps == 4) k.relay_probe_spp = ps;
+        }
         k.lens_stage = lens_stage_named(env_str("CGRT_LENS_STAGE"));
         // (`area` and `both` name forms that exist only as profiles/experiments/lens_stage_area.patch: said aloud, so that no
         // A/B run takes the default for them)
@@ -367,6 +398,10 @@ struct FramePlan {
     int relay_k = 1, relay_chunk_spp = 0, relay_slots = 0;
     size_t relay_tile_bytes = 0, relay_cap = 0, relay_bytes = 0;
     int relay_extent = kRelayGlass, relay_order = kRelayChunksFirst;  // relay_block_ordered's; both 0 unless relay_k > 1
+    // kRelayStartCost: the workgroups of classes 0-2 start by probed cost (cgrt_relay.h), through a table of start_words words
+    // in the order buffer; relay_order stays the order of a launch that has to go without the table.  List unless relay_k > 1
+    int relay_start = kRelayStartList, relay_probe_spp = 0;
+    size_t relay_start_words = 0;
 };
 
 // Whether a launch of n_tiles tiles relays samples by default: at 32 samples or more (two chunks of 16), and with every workgroup
@@ -393,6 +428,17 @@ inline int relay_order_of(int32_t flags, const EyeKnobs &kn) {
     if (f) return f == CGRT_GRID_RELAY_MIRROR_FIRST ? kRelayMirrorFirst : f == CGRT_GRID_RELAY_INTERLEAVED ? kRelayInterleaved : kRelayChunksFirst;
     if (kn.relay_order >= 0) return kn.relay_order;
     return (flags & CGRT_GRID_SAMPLE_RELAY) ? kRelayChunksFirst : kRelayDefaultOrder;
+}
+
+// Whether an engaged relay starts its workgroups by cost: what the launch's flags say; else the knob CGRT_RELAY_START; else the
+// launch that relays by default and names no order (the rule that gives kRelayDefaultOrder) does, a launch that names one
+// -- by flag or knob -- or asked for the relay gets the list it named.
+inline int relay_start_of(int32_t flags, const EyeKnobs &kn) {
+    if (flags & CGRT_GRID_NO_RELAY_COST_START) return kRelayStartList;
+    if (flags & CGRT_GRID_RELAY_COST_START) return kRelayStartCost;
+    if (kn.relay_start >= 0) return kn.relay_start;
+    const bool names_order = (flags & CGRT_GRID_RELAY_ORDER_MASK) || kn.relay_order >= 0;
+    return !names_order && !(flags & CGRT_GRID_SAMPLE_RELAY) ? kRelayStartCost : kRelayStartList;
 }
 
 // The launch at capacity kmax (0 when it is not scheduled): a function of the inputs and kmax only
@@ -458,6 +504,11 @@ inline FramePlan frame_plan(const FrameInputs &in, size_t kmax) {
                 p.relay_bytes = relay_layout(p.relay_cap, rc.k, p.relay_slots).total;
                 p.relay_extent = relay_extent_of(gr.flags, kn);
                 p.relay_order = relay_order_of(gr.flags, kn);
+                p.relay_start = (size_t)p.tile_blocks < kRelayStartMaxTiles ? relay_start_of(gr.flags, kn) : kRelayStartList;
+                if (p.relay_start == kRelayStartCost) {
+                    p.relay_probe_spp = std::min(kn.relay_probe_spp, (int)gr.spp);
+                    p.relay_start_words = relay_start_words((size_t)p.tile_blocks, rc.k, p.relay_cap);
+                }
             }
         }
     }

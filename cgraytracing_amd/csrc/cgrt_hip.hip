@@ -555,9 +555,10 @@ struct EyeFlags {
     int nt;  // threads per workgroup: 256 (32x8-pixel tiles) or 64 (Bezier scenes: one-wave workgroups on 16x4 tiles)
     bool diff = false;  // the terminal-diffuse body (sphere scenes' class-3 tiles)
     bool pair = false;  // the sphere loop two spheres a trip, class-3 tiles by the diffuse body in the same launch (glass sphere scenes)
+    bool start = false;  // a PAIR variant's twin that reads the relay's start table and serves as its cost probe (cgrt_relay.h)
     constexpr int id() const {
         return (int)trees | (int)bez << 1 | (int)dof << 2 | (int)glass << 3 | (int)sph << 4 | (int)stats << 5 | (int)hps << 6 |
-               (int)spill << 7 | (int)hfonly << 8 | (nt == 64 ? 1 << 9 : 0) | (int)diff << 10 | (int)pair << 11;
+               (int)spill << 7 | (int)hfonly << 8 | (nt == 64 ? 1 << 9 : 0) | (int)diff << 10 | (int)pair << 11 | (int)start << 12;
     }
 };
 // image order, the probe and the scheduled form: Bezier scenes share the tree-capable variants (one-wave workgroups)
@@ -681,10 +682,10 @@ struct EyeKernels {
     GridKernel grid;    // trace_grid_kernel
     SchedKernel sched;  // trace_grid_sched_kernel where the scheduled form runs these flags, else nullptr
 };
-template <int T, int B, int D, int G, int P, int S, int H = 0, int NT = kThreads, int SP = 0, int HF = 0, int DF = 0, int PR = 0>
+template <int T, int B, int D, int G, int P, int S, int H = 0, int NT = kThreads, int SP = 0, int HF = 0, int DF = 0, int PR = 0, int ST = 0>
 static constexpr EyeKernels gk() {  // trace_grid_kernel only
-    return {EyeFlags{T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, SP != 0, HF != 0, NT, DF != 0, PR != 0}.id(),
-            &trace_grid_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, NT, SP != 0, HF != 0, DF != 0, PR != 0>, nullptr};
+    return {EyeFlags{T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, SP != 0, HF != 0, NT, DF != 0, PR != 0, ST != 0}.id(),
+            &trace_grid_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, NT, SP != 0, HF != 0, DF != 0, PR != 0, ST != 0>, nullptr};
 }
 template <int T, int B, int D, int G, int P, int S, int NT = kThreads>
 static constexpr EyeKernels gsk() {  // both forms
@@ -692,7 +693,7 @@ static constexpr EyeKernels gsk() {  // both forms
     e.sched = &trace_grid_sched_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, NT>;
     return e;
 }
-//                        TREES BEZ DOF GLASS SPH STATS [HPS NT SPILL HFONLY DIFF PAIR]
+//                        TREES BEZ DOF GLASS SPH STATS [HPS NT SPILL HFONLY DIFF PAIR START]
 static const EyeKernels kEyeKernels[] = {
     // image order, the probe and the scheduled form (the light variants are the tree and plain ones without GLASS or STATS)
     gsk<1, 1, 0, 0, 0, 0, 64>(), gsk<1, 1, 0, 1, 0, 0, 64>(), gsk<1, 1, 1, 0, 0, 0, 64>(), gsk<1, 1, 1, 1, 0, 0, 64>(),
@@ -710,6 +711,8 @@ static const EyeKernels kEyeKernels[] = {
     gk<0, 0, 0, 0, 1, 0, 0, 256, 0, 0, 1>(), gk<0, 0, 1, 0, 1, 0, 0, 256, 0, 0, 1>(),
     // glass sphere scenes in image order: the pair loop, the class-3 tiles' diffuse body inside
     gk<0, 0, 0, 1, 1, 0, 0, 256, 0, 0, 0, 1>(), gk<0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 1>(),
+    // ... and their twins for a launch whose relay starts by cost: the start table's map, the cost probe
+    gk<0, 0, 0, 1, 1, 0, 0, 256, 0, 0, 0, 1, 1>(), gk<0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 1, 1>(),
 };
 static const EyeKernels *eye_kernels(const EyeFlags &f) {
     for (const EyeKernels &e : kEyeKernels)
@@ -933,6 +936,68 @@ static int probe_and_plan(const cgrt_scene *s, const EyeLaunch &L, const EyeKnob
     return CGRT_OK;
 }
 
+// The relay's start order by cost (cgrt_relay.h; behind order_tiles and relay_prepare on their stream, when the plan has
+// relay_start == kRelayStartCost and the launch relays).  The probe is the launch's own kernel over entries [0, plan[3]) of the
+// list -- the START twin of it, which the frame then runs too (kOrderFull: the workgroups beyond leave at once) -- with the first relay_probe_spp samples of every pixel from sample 0,
+// the launch's seed and depth, no relay; it stores nothing but each wave's iteration count.  Two small kernels turn the costs
+// into the table, and g maps its workgroups of classes 0-2 through it.  Costs and table stay in the order buffer and are reused
+// with the order, as long as what else they depend on (TileOrderState::CostKey, TableKey) is the same; where only the table's
+// key differs the probe is not run again.
+static EyeLaunch start_twin(EyeLaunch L) {
+    L.k.start = true;
+    return L;
+}
+static int relay_cost_start(const cgrt_scene *s, const EyeLaunch &L, const FramePlan &p, GridParams &g, hipStream_t st) {
+    TileOrderState &o = s->order;
+    const TileOrderLayout &at = o.at;
+    unsigned char *base = reinterpret_cast<unsigned char *>(o.buf.p);
+    uint32_t *wcost = at.wcost.in<uint32_t>(base), *start = at.start.in<uint32_t>(base);
+    unsigned long long *weight = at.weight.in<unsigned long long>(base);
+    if (!wcost || !start || !weight) return CGRT_OK;  // (the layout has no table: the launch goes by its list)
+    const TileOrderState::CostKey ck{g.seed, g.max_depth, p.relay_probe_spp};
+    const TileOrderState::TableKey tk{g.spp, g.relay_k, g.relay_chunk_spp, g.relay_cap, g.relay_extent, 0};
+    const bool have_cost = o.reused && o.cost_valid && std::memcmp(&ck, &o.cost_key, sizeof(ck)) == 0;
+    const bool have_table = have_cost && o.table_valid && std::memcmp(&tk, &o.table_key, sizeof(tk)) == 0;
+    o.cost_valid = o.table_valid = false;
+    if (!have_cost) {
+        HIP_TRY(hipMemsetAsync(wcost, 0, at.wcost.bytes, st));
+        GridParams gp = g;
+        gp.probe = 2;
+        gp.cost = wcost;
+        gp.spp = gp.chunk_spp = p.relay_probe_spp;
+        gp.sample_offset = 0;
+        gp.accumulate = 0;
+        gp.tile_order = kOrderFull;
+        gp.relay = nullptr;
+        gp.relay_k = 0;
+        gp.relay_start_at = 0;
+        if (int rc = launch_eye(start_twin(L), false, s->device, gp, dim3((unsigned)p.grid_dim), st, nullptr, nullptr, nullptr)) return rc;
+    }
+    if (!have_table) {
+        const int tiles_x = (g.W + kTileW - 1) / kTileW;
+        const RelayStartArgs a{RelayItems{(uint32_t)g.relay_k, 0, 0, 0, (uint32_t)g.relay_cap, g.relay_extent, g.relay_chunk_spp, g.spp},
+                               (uint32_t)tiles_x, (uint32_t)p.wtiles_x, (uint32_t)p.wtiles_y};
+        const dim3 grid((unsigned)((p.relay_start_words + kRelayThreads - 1) / kRelayThreads));
+        hipLaunchKernelGGL(relay_weight_kernel, grid, dim3(kRelayThreads), 0, st, a, g.plan, g.border, wcost, weight);
+        hipLaunchKernelGGL(relay_start_kernel, grid, dim3(kRelayThreads), 0, st, a, g.plan, weight, start);
+    }
+    // the order's event now stands behind the table too (a reusing launch on another stream waits for it)
+    if (o.valid && (have_table || (hipPeekAtLastError() == hipSuccess && hipEventRecord(o.ev, st) == hipSuccess))) {
+        if (!have_table) o.stream = st;
+        o.cost_key = ck;
+        o.table_key = tk;
+        o.cost_valid = o.table_valid = true;
+    } else if (o.valid) {
+        (void)hipGetLastError();
+        o.valid = false;
+    }
+    g.relay_start_at = (uint32_t)((at.start.at - at.plan.at) / sizeof(uint32_t));
+    o.start_words = p.relay_start_words;
+    o.start_wtiles = p.n_wt;
+    o.start_reused = have_table;
+    return CGRT_OK;
+}
+
 // The heavy units' primary rays against the mesh, as a walk-only kernel with lane refill (cgrt_primwalk.hpp): a chip's worth
 // of persistent workgroups at 4 waves per SIMD
 static int primary_walk(const cgrt_scene *s, const EyeLaunch &L, const GridParams &g, hipStream_t st, unsigned long long *cnt) {
@@ -1020,6 +1085,7 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
         if (p.relay_k > 1 && relay_prepare(s->relay, p, g, capturing, st)) {
             guard.relayed = true;
             n_blocks = relay_grid(p.grid_dim, p.relay_k, p.relay_cap);
+            if (p.relay_start == kRelayStartCost && (rc = relay_cost_start(s, L, p, g, st))) return rc;
         }
     }
     DevBuf timeline;
@@ -1049,7 +1115,8 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     } else {
         // The pair variant in tile order: the list's class-3 workgroups take the terminal-diffuse body inside this launch
         if (p.order.class3 == TileOrderPlan::InKernel) g.tile_order = kOrderAllDiffuse;
-        if ((rc = launch_eye(L, false, s->device, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) return rc;
+        // (a launch with a start table runs the variant that reads it: the twin of L's, the kernel its probe ran)
+        if ((rc = launch_eye(g.relay_start_at ? start_twin(L) : L, false, s->device, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) return rc;
     }
     if (p.chunks > 1)
         hipLaunchKernelGGL(finalize_chunks_kernel, dim3((unsigned)(((size_t)g.rows * g.W + 255) / 256)), dim3(256), 0, st, g, rgb, nhit);
@@ -1111,6 +1178,13 @@ int cgrt_scene_last_relay_form(const cgrt_scene *s, int32_t *mirror, int32_t *or
     NEED_COMMITTED(s, mirror && order);
     last_relay_form(s->order, s->relay, mirror, order);
     return CGRT_OK;
+}
+
+int cgrt_scene_last_relay_start(const cgrt_scene *s, uint32_t *start, int64_t start_cap, uint32_t *wcost, int64_t cost_cap, int64_t *t,
+                                int64_t *n_wave_tiles, int32_t *reused) {
+    NEED_COMMITTED(s, t && n_wave_tiles && reused);
+    ON_DEVICE(s->device);
+    return last_relay_start(s->order, s->relay, start, start_cap, wcost, cost_cap, t, n_wave_tiles, reused);
 }
 
 int cgrt_trace_grid_diffuse_variant(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, char *name, size_t cap) {
@@ -1846,6 +1920,25 @@ int cgrt_surface_colors(const cgrt_scene *s, int obj, const double *points3, int
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(colors3, b_c.p, (size_t)n * 24, hipMemcpyDeviceToHost));
+    return CGRT_OK;
+}
+
+int cgrt_relay_start_host(int32_t k, int32_t chunk_spp, int32_t spp, int64_t cap, int32_t extent, int64_t n01, int64_t n012, int64_t n_tiles,
+                          const uint32_t *list, const uint32_t *wcost, int32_t width, int32_t rows, uint32_t *start, int64_t start_cap,
+                          int64_t *t) {
+    if (!t || !list || !wcost || k < 2 || k > kRelayMaxChunks || chunk_spp <= 0 || spp <= 0 || cap < 0 || width <= 0 || rows <= 0 || n01 < 0 ||
+        n01 > n012 || n012 > n_tiles || (size_t)n_tiles >= kRelayStartMaxTiles || (extent != kRelayGlass && extent != kRelayMirror))
+        return fail(CGRT_ERR_INVALID, "bad argument");
+    const uint32_t tiles_x = (uint32_t)((width + kTileW - 1) / kTileW), tiles_y = (uint32_t)((rows + kTileH - 1) / kTileH);
+    const uint32_t wtiles_x = (uint32_t)((width + kWaveTileW - 1) / kWaveTileW), wtiles_y = (uint32_t)((rows + kWaveTileH - 1) / kWaveTileH);
+    if ((int64_t)tiles_x * tiles_y != n_tiles) return fail(CGRT_ERR_INVALID, "n_tiles is not the grid's tile count");
+    for (int64_t e = 0; e < n012; e++)
+        if (list[e] >= (uint32_t)n_tiles) return fail(CGRT_ERR_INVALID, "list names a tile beyond the grid");
+    const RelayItems r{(uint32_t)k, (uint32_t)n01, (uint32_t)n012, (uint32_t)n_tiles, (uint32_t)std::min<int64_t>(cap, n_tiles), extent, chunk_spp, spp};
+    *t = (int64_t)relay_items_total(r);
+    if (!start || start_cap < *t || *t == 0) return CGRT_OK;
+    std::vector<uint64_t> weight((size_t)*t);
+    relay_start_table(r, list, wcost, tiles_x, wtiles_x, wtiles_y, weight.data(), start);
     return CGRT_OK;
 }
 

@@ -1,7 +1,7 @@
 // The sample relay of tile-order launches, in plain C++ (no HIP): how a tile's samples are cut into chunks, which workgroup of
 // the launch renders which (entry, chunk), and where a split tile's values lie in the handle's relay area.  The host plans with
 // these functions (cgrt_trace_grid, cgrt_hip.hip), trace_grid_kernel (cgrt_eye.hpp) maps its workgroups with the same ones, and
-// tests/native/relay_map.cpp and relay_order.cpp check them on the CPU.  DESIGN.md section 4.6.
+// tests/native/relay_map.cpp, relay_order.cpp and relay_start.cpp check them on the CPU.  DESIGN.md section 4.6.
 //
 // A lane of trace_grid_body owns a pixel and runs its samples one after the other, so a wave lasts as long as its costliest
 // pixel: on a refracting sphere ~11 rays a sample, ~700 dependent scene walks at 64 samples.  The relay cuts that chain: the
@@ -105,6 +105,66 @@ CGRT_HD RelayBlock relay_block_ordered(uint32_t b, uint32_t k, uint32_t n01, uin
     const uint32_t first = mirror ? n01 : 0u, s = mirror ? s_m : s_a;
     if (i < k * s) return RelayBlock{first + i / k, (int32_t)(i % k), true};
     return RelayBlock{first + (i - (k - 1) * s), 0, false};
+}
+
+// The start order by cost.  The hardware starts workgroups in index order, so index order is a list
+// schedule, and a list schedule is good when the long jobs come first; the class is a poor estimate of a workgroup's length
+// (within one class they differ by a factor of four to six).  A probe leaves a cost per wave tile (the wave's iterations over
+// the first kRelayProbeSpp samples of its pixels: a count, the same in every run); the ITEMS are the workgroups of classes 0-2,
+// exactly those relay_block_ordered gives to b < t, numbered as kRelayChunksFirst does -- entries ascending, a split entry's k
+// chunks one after the other, so item order is (entry, chunk) order; an item's weight is its tile's cost (the largest of its
+// waves': a workgroup lasts as long as its longest wave) times the samples it runs; the table sends workgroup b to the item of
+// rank b in descending weight, ties in item order.  A total order: every rank is a count, no atomics.  Class 3 and the
+// workgroups beyond the list follow as in every other form.
+static constexpr int kRelayStartList = 0, kRelayStartCost = 1;  // FramePlan::relay_start
+static constexpr int kRelayProbeSpp = 2;                        // samples of the cost probe (measured: DESIGN.md section 6)
+struct RelayItems {
+    uint32_t k, n01, n012, n_tiles, cap;
+    int32_t extent, chunk_spp, spp;
+};
+CGRT_HD uint32_t relay_items_total(const RelayItems &r) {  // t: the workgroups of classes 0-2
+    return r.n012 + (r.k - 1) * relay_split_entries(r.n01, r.n012, r.cap, r.extent);
+}
+CGRT_HD RelayBlock relay_item(uint32_t i, const RelayItems &r) {
+    return relay_block_ordered(i, r.k, r.n01, r.n012, r.n_tiles, r.cap, r.extent, kRelayChunksFirst);
+}
+CGRT_HD uint64_t relay_item_weight(const RelayBlock &b, uint32_t tile_cost, const RelayItems &r) {
+    const int32_t samples = b.split ? relay_end_sample(b.chunk, r.chunk_spp, r.spp) - relay_first_sample(b.chunk, r.chunk_spp) : r.spp;
+    return (uint64_t)tile_cost * (uint64_t)(samples > 0 ? samples : 0);
+}
+// item j starts before item i
+CGRT_HD bool relay_item_before(uint64_t wj, uint32_t j, uint64_t wi, uint32_t i) { return wj > wi || (wj == wi && j < i); }
+// a word of the table, and the workgroup it names (the entries in front of n_split are the split ones)
+CGRT_HD uint32_t relay_start_word(const RelayBlock &b) { return b.entry << 2 | (uint32_t)b.chunk; }
+CGRT_HD RelayBlock relay_start_block(uint32_t word, uint32_t n_split) { return RelayBlock{word >> 2, (int32_t)(word & 3u), (word >> 2) < n_split}; }
+static_assert(kRelayMaxChunks <= 4, "a table word holds the chunk in two bits");
+// Tiles a table can name (entry << 2 in a word) and workgroups it may have to hold: the host knows neither n01 nor n012
+static constexpr size_t kRelayStartMaxTiles = (size_t)1 << 30;
+CGRT_HD size_t relay_start_words(size_t n_tiles, int32_t k, size_t cap_split) { return relay_grid(n_tiles, k, cap_split); }
+// The cost of tile `tile` (ty * tiles_x + tx) from its wave tiles' costs: 2 x 2 wave tiles of 16x4 pixels, those inside the grid
+CGRT_HD uint32_t relay_tile_cost(const uint32_t *wcost, uint32_t tile, uint32_t tiles_x, uint32_t wtiles_x, uint32_t wtiles_y) {
+    const uint32_t tx = tile % tiles_x, ty = tile / tiles_x;
+    uint32_t c = 0;
+    for (uint32_t w = 0; w < 4; w++) {
+        const uint32_t wx = 2 * tx + (w & 1u), wy = 2 * ty + (w >> 1);
+        if (wx < wtiles_x && wy < wtiles_y && wcost[wy * wtiles_x + wx] > c) c = wcost[wy * wtiles_x + wx];
+    }
+    return c;
+}
+// The whole table on the host (the device spreads the same counts over workgroups: relay_start_kernel): weight[i] of item i,
+// start[rank] = its word.  Both arrays hold relay_items_total words.
+inline void relay_start_table(const RelayItems &r, const uint32_t *list, const uint32_t *wcost, uint32_t tiles_x, uint32_t wtiles_x,
+                              uint32_t wtiles_y, uint64_t *weight, uint32_t *start) {
+    const uint32_t t = relay_items_total(r);
+    for (uint32_t i = 0; i < t; i++) {
+        const RelayBlock b = relay_item(i, r);
+        weight[i] = relay_item_weight(b, relay_tile_cost(wcost, list[b.entry], tiles_x, wtiles_x, wtiles_y), r);
+    }
+    for (uint32_t i = 0; i < t; i++) {
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < t; j++) rank += relay_item_before(weight[j], j, weight[i], i) ? 1u : 0u;
+        start[rank] = relay_start_word(relay_item(i, r));
+    }
 }
 
 // The relay area for cap_split tiles, 256 threads a tile (thread t = pixel t of the tile), array after array:

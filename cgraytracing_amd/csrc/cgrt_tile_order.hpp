@@ -44,10 +44,27 @@ struct TileOrderState {
     TileOrderLayout at;
     TileOrderPlan::Class3 class3 = TileOrderPlan::None;
     int lens_stage = kLensStageOff;  // how that launch's in-kernel terminal-diffuse body drew its lens points
+    // The relay's cost start (cgrt_relay.h; relay_cost_start, cgrt_hip.hip): the probe's costs and the start table lie behind the
+    // rest of the buffer and are kept with the order -- never beyond it: a launch that did not reuse the order has neither.  The
+    // costs depend, beyond Key, on CostKey; the table on the costs and on TableKey.  start_words: the table's part in the last
+    // launch (0: it had none), start_wtiles its wave tiles, start_reused: it ran neither probe nor ranking.
+    struct CostKey {
+        uint64_t seed;
+        int32_t max_depth, probe_spp;
+    };
+    struct TableKey {
+        int32_t spp, k, chunk_spp, cap, extent, pad_;
+    };
+    static_assert(sizeof(CostKey) == 16 && sizeof(TableKey) == 24, "compared as bytes: no padding");
+    CostKey cost_key{};
+    TableKey table_key{};
+    bool cost_valid = false, table_valid = false, start_reused = false;
+    size_t start_words = 0, start_wtiles = 0;
 
     void begin_launch() {
         tiles = mask_wtiles = sure_wtiles = 0;
-        reused = false;
+        start_words = start_wtiles = 0;
+        reused = start_reused = false;
         class3 = TileOrderPlan::None;
         lens_stage = kLensStageOff;
     }
@@ -108,7 +125,7 @@ static int order_tiles(TileOrderState &o, const DeviceScene &dev, const FramePla
     const int tiles_x = (g.W + kTileW - 1) / kTileW, tiles_y = (g.rows + kTileH - 1) / kTileH;
     const size_t n = (size_t)tiles_x * tiles_y;
     const bool masks = p.order.masks, sure = masks && p.order.sure;
-    const TileOrderLayout at = tile_order_layout(n, p.n_wt, sure);
+    const TileOrderLayout at = tile_order_layout(n, p.n_wt, sure, p.relay_start_words);
     const bool grown = at.total > o.buf.cap;
     if (grown) o.valid = false;
     if (o.buf.need(at.total) != hipSuccess) {
@@ -127,7 +144,7 @@ static int order_tiles(TileOrderState &o, const DeviceScene &dev, const FramePla
     if (o.reused) {
         if (st != o.stream) HIP_TRY(hipStreamWaitEvent(st, o.ev, 0));
     } else {
-        o.valid = false;
+        o.valid = o.cost_valid = o.table_valid = false;  // (costs and table are of the order they were found for)
         if (grown) HIP_TRY(hipMemsetAsync(plan, 0, at.plan.bytes, st));  // plan[kOrderArrived]
         const unsigned blocks = (unsigned)std::min((p.n_wt + 1023) / 1024, (size_t)64);
         hipLaunchKernelGGL(tile_order_kernel, dim3(blocks), dim3(1024), 0, st, g, o.spheres, dev, tiles_x, tiles_y, plan, list,
@@ -295,6 +312,27 @@ static int last_sample_relay(const TileOrderState &o, const RelayState &r, int64
     const RelayLayout rl = relay_layout(l.cap, l.k, l.slots);
     HIP_TRY(hipMemcpy(cnt.data(), reinterpret_cast<const unsigned char *>(r.buf.p) + rl.rcount, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (uint32_t c : cnt) *parked_values += (int64_t)c;
+    return CGRT_OK;
+}
+// the start table of the last launch, its wave tiles' probe costs and the workgroups it ordered
+static int last_relay_start(const TileOrderState &o, const RelayState &r, uint32_t *start, int64_t start_cap, uint32_t *wcost, int64_t cost_cap,
+                            int64_t *t, int64_t *n_wave_tiles, int32_t *reused) {
+    *t = *n_wave_tiles = 0;
+    *reused = 0;
+    if (o.start_words == 0 || o.tiles == 0 || r.last.k <= 1) return CGRT_OK;
+    uint32_t plan[kOrderClasses + 1];
+    HIP_TRY(hipDeviceSynchronize());
+    if (int rc = o.read(o.at.plan, plan, kOrderClasses + 1)) return rc;
+    const RelayItems ri{(uint32_t)r.last.k, plan[2], plan[3], plan[kOrderClasses], (uint32_t)r.last.cap, r.last.extent, 0, 0};
+    const size_t n = relay_items_total(ri);
+    if (n > o.start_words) return fail(CGRT_ERR_DEVICE, "relay start table: more workgroups than the table holds");
+    *t = (int64_t)n;
+    *n_wave_tiles = (int64_t)o.start_wtiles;
+    *reused = o.start_reused ? 1 : 0;
+    if (start && start_cap >= (int64_t)n && n > 0)
+        if (int rc = o.read(o.at.start, start, n)) return rc;
+    if (wcost && cost_cap >= (int64_t)o.start_wtiles && o.start_wtiles > 0)
+        if (int rc = o.read(o.at.wcost, wcost, o.start_wtiles)) return rc;
     return CGRT_OK;
 }
 static void last_relay_form(const TileOrderState &o, const RelayState &r, int32_t *mirror, int32_t *order) {

@@ -23,10 +23,18 @@ def _d3(v):
 _RELAY_ORDERS = ("chunks_first", "mirror_first", "interleaved")  # CGRT_GRID_RELAY_CHUNKS_FIRST / _MIRROR_FIRST / _INTERLEAVED
 
 
-def _relay_flag(sample_relay, relay_mirror=None, relay_order=None):
+_RELAY_STARTS = ("list", "cost")  # CGRT_GRID_NO_RELAY_COST_START / CGRT_GRID_RELAY_COST_START
+
+
+def _relay_flag(sample_relay, relay_mirror=None, relay_order=None, relay_start=None):
     """CGRT_GRID_SAMPLE_RELAY / _NO_SAMPLE_RELAY / _SAMPLE_RELAY_4 for trace_grid's sample_relay=None|True|False|2|4, with
-    CGRT_GRID_RELAY_MIRROR / _NO_MIRROR for relay_mirror=None|True|False and the order field for relay_order=None|a name"""
+    CGRT_GRID_RELAY_MIRROR / _NO_MIRROR for relay_mirror=None|True|False, the order field for relay_order=None|a name and
+    CGRT_GRID_RELAY_COST_START / _NO_RELAY_COST_START for relay_start=None|"cost"|"list"."""
     form = 0 if relay_mirror is None else (8192 if relay_mirror else 16384)
+    if relay_start is not None:
+        if relay_start not in _RELAY_STARTS:
+            raise ValueError("relay_start: None, " + ", ".join(repr(o) for o in _RELAY_STARTS))
+        form |= 524288 if relay_start == "cost" else 1048576
     if relay_order is not None:
         if relay_order not in _RELAY_ORDERS:
             raise ValueError("relay_order: None, " + ", ".join(repr(o) for o in _RELAY_ORDERS))
@@ -38,6 +46,22 @@ def _relay_flag(sample_relay, relay_mirror=None, relay_order=None):
     if int(sample_relay) not in (2, 4):
         raise ValueError("sample_relay: None, True, False, 2 or 4")
     return form | 1024 | (4096 if int(sample_relay) == 4 else 0)
+
+
+def relay_start_host(k, chunk_spp, spp, cap, mirror, plan, tile_list, wcost, width, rows):
+    """The relay's start table on the host (cgrt_relay_start_host; no GPU): for last_tile_order()'s plan and list, an area of
+    `cap` tiles relayed by k workgroups of chunk_spp samples out of spp (mirror: the class-2 tiles too) and the wave tiles' costs
+    of a width x rows grid, uint32 [t]: entry << 2 | chunk of workgroup b -- what last_relay_start()["start"] holds."""
+    lib = _capi.lib()
+    lst, wc = np.ascontiguousarray(tile_list, np.uint32), np.ascontiguousarray(wcost, np.uint32)
+    assert wc.size == ((width + 15) // 16) * ((rows + 3) // 4) and lst.size == int(plan[4])
+    args = (int(k), int(chunk_spp), int(spp), int(cap), 1 if mirror else 0, int(plan[2]), int(plan[3]), int(plan[4]), lst.ctypes.data,
+            wc.ctypes.data, int(width), int(rows))
+    t = C.c_int64()
+    check(lib.cgrt_relay_start_host(*args, None, 0, C.byref(t)))
+    start = np.zeros(max(t.value, 1), np.uint32)
+    check(lib.cgrt_relay_start_host(*args, start.ctypes.data, start.size, C.byref(t)))
+    return start[:t.value]
 
 
 class Scene:
@@ -179,7 +203,7 @@ class Scene:
                    stripe=None, sample_offset=0, spp_total=None, out=None, nhit=None, counters=None, stream=None,
                    stats=False, accumulate=False, split_samples=False, reorder=True, force_reorder=False, tile_order=True,
                    diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None,
-                   relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True):
+                   relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True, relay_start=None):
         """Asynchronous launch on torch's current stream (or `stream`).  reorder=False: CGRT_GRID_NO_REORDER (tiles in image
         order instead of heaviest-first; same image).  tile_order=False: CGRT_GRID_NO_TILE_ORDER (an image-order launch starts
         its tiles row-major instead of mirror / glass tiles first; same image).  diffuse_tiles=True: CGRT_GRID_DIFFUSE_TILES (a
@@ -193,7 +217,10 @@ class Scene:
         tile); False: CGRT_GRID_NO_SAMPLE_RELAY.  relay_mirror: True -- the relay takes the tiles that see only a mirror sphere
         too (CGRT_GRID_RELAY_MIRROR), False -- it does not; relay_order: "chunks_first", "mirror_first" or "interleaved" -- where
         those tiles' workgroups start among the glass tiles'; None: what sample_relay has always meant when it is given, the
-        measured form when it is not (last_relay_form tells).  lens_stage=False: CGRT_GRID_NO_LENS_STAGE (the thin-lens
+        measured form when it is not (last_relay_form tells).  relay_start: "cost" -- the relay's workgroups of classes 0-2 start
+        longest first by a probed cost (CGRT_GRID_RELAY_COST_START; same image, hit counts and counters; last_relay_start),
+        "list" -- in the order named (CGRT_GRID_NO_RELAY_COST_START); None: by cost where the launch relays by default and names
+        no order.  lens_stage=False: CGRT_GRID_NO_LENS_STAGE (the thin-lens
         terminal-diffuse body inside the main launch draws every lens point by its own rejection loop instead of staging 16
         samples' draws ahead; same image; last_lens_stage).  sure_tiles=False: CGRT_GRID_NO_SURE_TILES (a wave of the
         terminal-diffuse body traces its samples even where every ray of its 16x4 wave tile provably hits the same sphere first;
@@ -217,7 +244,7 @@ class Scene:
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (2 if accumulate else 0) | (4 if split_samples else 0) |
                               (0 if reorder else 8) | (16 if force_reorder else 0) | (0 if tile_order else 64) |
-                              (128 if diffuse_tiles else 0) | (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order) |
+                              (128 if diffuse_tiles else 0) | (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order, relay_start) |
                               (0 if lens_stage else 131072) | (0 if sure_tiles else 262144))
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         check(self._L.cgrt_trace_grid(self._h, C.byref(cc), C.byref(g), out.data_ptr(),
@@ -505,7 +532,7 @@ class Scene:
     def trace_grid_host(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                         stripe=None, sample_offset=0, spp_total=None, stats=False, split_samples=False, reorder=True,
                         force_reorder=False, tile_order=True, diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None,
-                        relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True):
+                        relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True, relay_start=None):
         """Synchronous form with numpy outputs (no torch needed): dict(rgb, nhit, counters)."""
         rows = height - row_offset if rows is None else rows
         rgb = np.zeros((rows, width, 3), np.float32)
@@ -514,7 +541,7 @@ class Scene:
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (4 if split_samples else 0) | (0 if reorder else 8) |
                               (16 if force_reorder else 0) | (0 if tile_order else 64) | (128 if diffuse_tiles else 0) |
-                              (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order) |
+                              (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order, relay_start) |
                               (0 if lens_stage else 131072) | (0 if sure_tiles else 262144))
         check(self._L.cgrt_trace_grid_host(self._h, C.byref(cc), C.byref(g), rgb.ctypes.data, nhit.ctypes.data,
                                            cnt.ctypes.data))
@@ -578,6 +605,19 @@ class Scene:
         m, o = C.c_int32(), C.c_int32()
         check(self._L.cgrt_scene_last_relay_form(self._h, C.byref(m), C.byref(o)))
         return None if m.value < 0 else dict(mirror=bool(m.value), order=_RELAY_ORDERS[o.value])
+
+    def last_relay_start(self):
+        """The start table of that relay (cgrt_scene_last_relay_start; synchronises the device): None when the launch had none,
+        else dict(t: workgroups of classes 0-2, start [t] uint32: entry << 2 | chunk of workgroup b, wcost [wave tiles] uint32:
+        the probe's iteration counts, reused: probe and ranking were an earlier launch's)."""
+        t, n, r = C.c_int64(), C.c_int64(), C.c_int32()
+        check(self._L.cgrt_scene_last_relay_start(self._h, None, 0, None, 0, C.byref(t), C.byref(n), C.byref(r)))
+        if n.value == 0:
+            return None
+        start, wcost = np.zeros(max(t.value, 1), np.uint32), np.zeros(n.value, np.uint32)
+        check(self._L.cgrt_scene_last_relay_start(self._h, start.ctypes.data, start.size, wcost.ctypes.data, n.value, C.byref(t),
+                                                  C.byref(n), C.byref(r)))
+        return dict(t=int(t.value), start=start[:t.value], wcost=wcost, reused=bool(r.value))
 
     def last_lens_stage(self):
         """Lens points staged ahead by this scene's last trace_grid / trace_grid_host (cgrt_scene_last_lens_stage; synchronises

@@ -149,6 +149,13 @@ enum {
     CGRT_GRID_RELAY_INTERLEAVED = 98304, /* ... or the two merged in proportion.  0: chunks first with CGRT_GRID_SAMPLE_RELAY,
                                  the measured order by default.  cgrt_scene_last_relay_form tells what a launch used       */
     CGRT_GRID_RELAY_ORDER_MASK = 98304,
+    CGRT_GRID_RELAY_COST_START = 524288, /* the relay's workgroups of classes 0-2 start longest first, by a probed cost: once per
+                                 camera, seed and depth the launch's kernel runs the first samples of those tiles storing
+                                 nothing but each wave's iteration count, and a small kernel ranks the workgroups by tile cost
+                                 x samples (cgrt_scene_last_relay_start).  The same workgroups run the same bodies: image, hit
+                                 counts and all counters are identical.  The default of a launch that relays by default and
+                                 names no order; a launch on a captured stream goes without ...                          */
+    CGRT_GRID_NO_RELAY_COST_START = 1048576, /* ... and this one switches it off: the order the flags above name           */
     CGRT_GRID_NO_LENS_STAGE = 131072, /* the terminal-diffuse body inside the main launch (see CGRT_GRID_NO_SPHERE_PAIRS) under a
                                  thin-lens camera: by default a wave finds the accepted lens draws of its next 16 samples
                                  ahead of their use -- attempt 1 of every sample without divergence, then the rejected ones,
@@ -701,10 +708,25 @@ int cgrt_scene_last_sample_relay(const cgrt_scene *s, int64_t *tiles, int32_t *c
 /* The form of that relay: *mirror = 1 when the class-2 tiles were relayed too (CGRT_GRID_RELAY_MIRROR), *order = 0 chunks
  * first, 1 mirror first, 2 interleaved; both -1 when the launch did not relay. */
 int cgrt_scene_last_relay_form(const cgrt_scene *s, int32_t *mirror, int32_t *order);
+/* The start table of that relay (see CGRT_GRID_RELAY_COST_START; synchronises the device): *t = the workgroups of classes 0-2
+ * it ordered by cost, 0 when the launch had no table; *n_wave_tiles = the wave tiles of the launch, *reused = 1 when probe and
+ * table were those of an earlier launch.  With start_cap >= *t: start[b] = entry << 2 | chunk of workgroup b, to HOST memory;
+ * with cost_cap >= *n_wave_tiles: wcost[wave tile] = the probe's iteration count (0: not probed, a class-3 tile). */
+int cgrt_scene_last_relay_start(const cgrt_scene *s, uint32_t *start, int64_t start_cap, uint32_t *wcost, int64_t cost_cap, int64_t *t,
+                                int64_t *n_wave_tiles, int32_t *reused);
 /* Lens points staged ahead of the sample loop by the LAST cgrt_trace_grid on the handle (see CGRT_GRID_NO_LENS_STAGE;
  * synchronises the device): *lds_tiles = the tiles whose workgroups staged their lens draws in LDS batches, *area_tiles = the
  * tiles that staged them in device memory (no launch does: always 0).  Both 0: every lens point came from the per-sample loop. */
 int cgrt_scene_last_lens_stage(const cgrt_scene *s, int64_t *lds_tiles, int64_t *area_tiles);
+
+/* Host evaluation of that table (cgrt_relay.h, the same inline code the kernels run; no GPU): for a list of n_tiles entries,
+ * the first n01 of class 0 or 1 and the first n012 of classes 0-2 (cgrt_scene_last_tile_order's plan[2], plan[3], plan[4] and
+ * list), an area of cap tiles relayed by k workgroups of chunk_spp samples each out of spp, extent 0 (classes 0 and 1) or 1
+ * (class 2 too), and the wave tiles' costs of a grid `width` pixels wide and `rows` high: writes start[b] for b < *t, when
+ * start_cap >= *t.  Lets a test recompute the table a launch read back. */
+int cgrt_relay_start_host(int32_t k, int32_t chunk_spp, int32_t spp, int64_t cap, int32_t extent, int64_t n01, int64_t n012, int64_t n_tiles,
+                          const uint32_t *list, const uint32_t *wcost, int32_t width, int32_t rows, uint32_t *start, int64_t start_cap,
+                          int64_t *t);
 
 /* Host evaluation of the lens stream (cgrt_rng.hpp, the same inline code the kernel runs): writes
  * uniform_sampling_circle(radius) (sampling.h:35-43) for n (pixel, sample) pairs as 3 doubles each.  Lets CPU-only

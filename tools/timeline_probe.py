@@ -2,7 +2,7 @@
 """Development aid (not a test): when and where every workgroup of one trace_grid launch ran.
 
   python tools/timeline_probe.py c3|c4|c2|c5band [--spp N] [--split] [--natural] [--relay on|off] [--mirror on|off]
-                                 [--order chunks_first|mirror_first|interleaved] [--out tl.json]
+                                 [--order chunks_first|mirror_first|interleaved] [--start list|cost] [--out tl.json]
 
 Sets CGRT_TIMELINE_FILE so that libcgrt.so records, per workgroup, {start, end} on the 100 MHz wall clock, the hardware
 id (XCC, SE, CU) and the rays it traced, then prints: launch span, concurrency over time (resident workgroups in 20 time
@@ -31,6 +31,8 @@ def main():
         form["relay_mirror"] = {"on": True, "off": False}[sys.argv[sys.argv.index("--mirror") + 1]]
     if "--order" in sys.argv:
         form["relay_order"] = sys.argv[sys.argv.index("--order") + 1]
+    if "--start" in sys.argv:  # relay_start
+        form["relay_start"] = sys.argv[sys.argv.index("--start") + 1]
     import cgraytracing_amd as cg
     import scenes
     cam = scenes.cam_dof()
@@ -55,6 +57,7 @@ def main():
     tile_order = sc.last_tile_order() if hasattr(sc, "last_tile_order") else None  # image-order launches of sphere scenes
     relayed = sc.last_sample_relay() if hasattr(sc, "last_sample_relay") else None
     relay_form = sc.last_relay_form() if hasattr(sc, "last_relay_form") else None
+    relay_start = sc.last_relay_start() if hasattr(sc, "last_relay_start") else None  # the start table by cost, where the launch had one
     sc.close()
     raw = np.fromfile(tf, dtype=np.uint64)
     os.unlink(tf)
@@ -132,7 +135,35 @@ def main():
         first, s_of = np.where(mirror, n01, 0), np.where(mirror, s_m, s_a)
         split_blk = (blk < t) & (i < k * s_of)
         chunk = np.where(split_blk, i % k, 0)
+        in_table = blk < t
         blk = np.where(blk >= t, n012 + blk - t, np.where(split_blk, first + i // k, first + i - (k - 1) * s_of))  # the entry
+        if relay_start is not None and relay_start["t"] == t:
+            # the workgroups of classes 0-2 went through the start table (cgrt_relay.h): word = entry << 2 | chunk
+            word = relay_start["start"].astype(np.int64)[np.minimum(np.nonzero(ran)[0], t - 1)]
+            blk = np.where(in_table, word >> 2, blk)
+            chunk = np.where(in_table, word & 3, chunk)
+            split_blk = in_table & (blk < n_split)
+            # an item's weight (tile cost x samples) against what its workgroup took: Spearman's rank correlation
+            tx, wtx, wty = (W + 31) // 32, (W + 15) // 16, ((rows or H) + 3) // 4
+            wc = relay_start["wcost"].reshape(wty, wtx).astype(np.int64)
+            tiles = tile_order["list"].astype(np.int64)[np.minimum(blk, plan[4] - 1)]
+            cost = np.zeros(len(blk), np.int64)
+            for dy in range(2):
+                for dx in range(2):
+                    wy, wx = 2 * (tiles // tx) + dy, 2 * (tiles % tx) + dx
+                    cost = np.maximum(cost, np.where((wy < wty) & (wx < wtx), wc[np.minimum(wy, wty - 1), np.minimum(wx, wtx - 1)], 0))
+            cs = -(-spp // k)
+            weight = cost * np.where(split_blk, np.minimum((chunk + 1) * cs, spp) - chunk * cs, spp)
+            def ranks(v):
+                o = np.argsort(v, kind="stable")
+                r = np.empty(len(v))
+                r[o] = np.arange(len(v))
+                u, inv = np.unique(v, return_inverse=True)  # ties: the mean rank
+                return (np.bincount(inv, weights=r) / np.bincount(inv))[inv]
+            doc["cost_start"] = {"items": int(in_table.sum()), "reused": relay_start["reused"], "largest_wave_cost": int(wc.max()),
+                                 "spearman_weight_vs_workgroup_us": round(float(np.corrcoef(ranks(weight[in_table]), ranks(dur[in_table]))[0, 1]), 4),
+                                 "first_workgroups_us": [round(float(x), 1) for x in dur[in_table][:8]],
+                                 "last_workgroups_us": [round(float(x), 1) for x in dur[in_table][-8:]]}
         if relay_k > 1:
             ent_rays = np.bincount(blk, weights=rays, minlength=plan[4])
             heavy = int(np.argmax(ent_rays))  # the entry with the most rays: the glass sphere's centre tile
