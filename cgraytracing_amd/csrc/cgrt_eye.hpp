@@ -96,9 +96,23 @@ __device__ __forceinline__ bool wave_has_tile(const GridParams &g, int tile_bloc
 
 // A workgroup's part in the sample relay (cgrt_relay.h), workgroup-uniform: slot >= 0 -- it renders chunk `chunk` of the
 // relayed tile in slot `slot` of the relay area, samples [s0, s1); slot < 0: not relayed, all the launch's samples.
+// boost (the START variants only): the tile is promoted -- slot is its slot of the boost area, whose form relay_form gives.
 struct RelayWg {
-    int slot = -1, chunk = 0, s0 = 0, s1 = 0;
+    int slot = -1, chunk = 0, s0 = 0, s1 = 0, boost = 0;
 };
+// The area a relayed workgroup's tile lies in and its form (workgroup-uniform; asked for at each point of use, so that nothing
+// of it lives across the ray loop): the launch's base form, or for a promoted tile the boost area's.  Without COST -- the
+// variants that read no table -- the expressions are the base form's, as they stood.
+struct RelayForm {
+    unsigned char *area;
+    size_t cap;
+    int k, slots;
+};
+template <bool COST>
+__device__ __forceinline__ RelayForm relay_form(const GridParams &g, const RelayWg &rw) {
+    if (COST && rw.boost) return RelayForm{g.relay + g.relay_boost_off, (size_t)g.boost_cap, g.boost_k, g.boost_slots};
+    return RelayForm{g.relay, (size_t)g.relay_cap, g.relay_k, g.relay_slots};
+}
 
 // The body of the eye pass for one workgroup.  HEAVY selects how the waves get their work (see GridParams): false -- each
 // wave owns one wave tile (16x4 pixels, one per lane) and every lane runs its pixel's samples; true -- the waves serve the
@@ -261,9 +275,11 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
     // PARK: the lane's stream -- value i at park[i * 3 * NT + {0, NT, 2 NT}] -- and the values it holds
     double *park = nullptr;
     uint32_t park_n = 0;
-    if (PARK)
-        park = reinterpret_cast<double *>(g.relay + relay_layout((size_t)g.relay_cap, g.relay_k, g.relay_slots).rvals) +
-               ((size_t)rw.slot * (size_t)(g.relay_k - 1) + (size_t)(rw.chunk - 1)) * (size_t)g.relay_slots * (3 * NT) + threadIdx.x;
+    if (PARK) {
+        const RelayForm rf = relay_form<COST>(g, rw);
+        park = reinterpret_cast<double *>(rf.area + relay_layout(rf.cap, rf.k, rf.slots).rvals) +
+               ((size_t)rw.slot * (size_t)(rf.k - 1) + (size_t)(rw.chunk - 1)) * (size_t)rf.slots * (3 * NT) + threadIdx.x;
+    }
     bool have = false;
     V3 o = camorg, d = pdir, adj = mk(1, 1, 1);
     int depth_left = 0;
@@ -492,7 +508,7 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
                         q[1] = hf.y;
                         q[2] = hf.z;
                     } else if (PARK) {
-                        if (park_n < (uint32_t)g.relay_slots) {  // (always: relay_slots bounds a chunk's ray trees)
+                        if (park_n < (uint32_t)relay_form<COST>(g, rw).slots) {  // (always: the slots bound a chunk's ray trees)
                             double *q = park + (size_t)park_n * (3 * NT);
                             q[0] = hf.x;
                             q[NT] = hf.y;
@@ -651,12 +667,13 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
         if (PAIR && rw.slot >= 0) {
             // ---- relay: leave this chunk's results in the tile's slot, publish them, count in; the last workgroup in adds
             // the chunks up.  Nobody waits for anybody (cgrt_relay.h).
-            const size_t slot = (size_t)rw.slot, k = (size_t)g.relay_k;
-            const RelayLayout rl = relay_layout((size_t)g.relay_cap, g.relay_k, g.relay_slots);  // (here, not across the ray loop)
-            uint32_t *arrive = reinterpret_cast<uint32_t *>(g.relay) + slot;
-            double *racc = reinterpret_cast<double *>(g.relay + rl.racc) + slot * (3 * NT) + threadIdx.x;
-            uint32_t *rhits = reinterpret_cast<uint32_t *>(g.relay + rl.rhits) + slot * k * NT + threadIdx.x;
-            uint32_t *rcount = reinterpret_cast<uint32_t *>(g.relay + rl.rcount) + slot * (k - 1) * NT + threadIdx.x;
+            const RelayForm rf = relay_form<COST>(g, rw);  // (here, not across the ray loop; a promoted tile: the boost area's)
+            const size_t slot = (size_t)rw.slot, k = (size_t)rf.k;
+            const RelayLayout rl = relay_layout(rf.cap, rf.k, rf.slots);
+            uint32_t *arrive = reinterpret_cast<uint32_t *>(rf.area) + slot;
+            double *racc = reinterpret_cast<double *>(rf.area + rl.racc) + slot * (3 * NT) + threadIdx.x;
+            uint32_t *rhits = reinterpret_cast<uint32_t *>(rf.area + rl.rhits) + slot * k * NT + threadIdx.x;
+            uint32_t *rcount = reinterpret_cast<uint32_t *>(rf.area + rl.rcount) + slot * (k - 1) * NT + threadIdx.x;
             if (PARK) {
                 rcount[(size_t)(rw.chunk - 1) * NT] = park_n;
             } else {
@@ -674,7 +691,7 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 const unsigned int ticket = __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const bool last = ticket == (unsigned int)g.relay_k - 1u;
+                const bool last = ticket == (unsigned int)rf.k - 1u;
                 if (last) {
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -692,18 +709,18 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
                 acc_g = racc[NT];
                 acc_b = racc[2 * NT];
                 px_hits = rhits[0];
-                for (int c = 1; c < g.relay_k; c++) {
+                for (int c = 1; c < rf.k; c++) {
                     px_hits += rhits[(size_t)c * NT];
                     uint32_t n = rcount[(size_t)(c - 1) * NT];
-                    if (n > (uint32_t)g.relay_slots) n = (uint32_t)g.relay_slots;
+                    if (n > (uint32_t)rf.slots) n = (uint32_t)rf.slots;
                     uint32_t n_max = n;
                     for (int off = 32; off > 0; off >>= 1) {
                         const uint32_t o2 = (uint32_t)__shfl_xor((int)n_max, off);
                         n_max = o2 > n_max ? o2 : n_max;
                     }
                     n_max = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_max);
-                    const double *q = reinterpret_cast<const double *>(g.relay + rl.rvals) +
-                                      (slot * (k - 1) + (size_t)(c - 1)) * (size_t)g.relay_slots * (3 * NT) + threadIdx.x;
+                    const double *q = reinterpret_cast<const double *>(rf.area + rl.rvals) +
+                                      (slot * (k - 1) + (size_t)(c - 1)) * (size_t)rf.slots * (3 * NT) + threadIdx.x;
                     for (uint32_t i0 = 0; i0 < n_max; i0 += kRelayBatch) {
                         double v[kRelayBatch][3];
 #pragma unroll
@@ -832,22 +849,33 @@ __global__ __launch_bounds__(NT, DIFF ? (DOF ? kDiffDofWaves : kDiffWaves) : BEZ
             // variant without one keeps its code): the workgroups of classes 0-2 in the order the table names (cgrt_relay.h),
             // the others as ever
             bool tabled = false;
+            // With promoted tiles (g.relay_boost_at; cgrt_relay.h) the table has `items` workgroups, more than the base form's
+            // t0 by the promoted tiles' extra chunks: the workgroups behind it are shifted by the difference, and a split entry's
+            // bslot word says whether its tile is promoted and where in the boost area it lies.
+            unsigned b = blockIdx.x, bslot = 0u;
             if (START && g.relay_start_at != 0u) {
                 const unsigned n_split = relay_split_entries(n01, n012, (unsigned)g.relay_cap, g.relay_extent);
-                tabled = blockIdx.x < n012 + ((unsigned)g.relay_k - 1u) * n_split;
+                const unsigned t0 = n012 + ((unsigned)g.relay_k - 1u) * n_split;
+                const unsigned items = g.relay_boost_at != 0u ? load_uniform(g.plan + g.relay_boost_at + kBoostItems) : t0;
+                tabled = b < items;
                 if (tabled) {
-                    rb = relay_start_block(load_uniform(g.plan + g.relay_start_at + blockIdx.x), n_split);
-                    if (rb.chunk >= g.relay_k) return;  // (no table names a chunk the area has not)
+                    rb = relay_start_block(load_uniform(g.plan + g.relay_start_at + b), n_split);
+                    if (g.relay_boost_at != 0u && rb.split) bslot = load_uniform(g.plan + g.relay_boost_at + kBoostHead + rb.entry);
+                    if (rb.chunk >= (bslot != 0u ? g.boost_k : g.relay_k) || bslot > (unsigned)g.boost_cap) return;  // (no table names a chunk or a slot the area has not)
+                } else {
+                    b -= items - t0;
                 }
             }
-            if (!tabled) rb = relay_block_ordered(blockIdx.x, (unsigned)g.relay_k, n01, n012, n_tiles, (unsigned)g.relay_cap, g.relay_extent, g.relay_order);
+            if (!tabled) rb = relay_block_ordered(b, (unsigned)g.relay_k, n01, n012, n_tiles, (unsigned)g.relay_cap, g.relay_extent, g.relay_order);
             entry = rb.entry;
             if (entry >= n_tiles) return;
             if (rb.split) {
-                rw.slot = (int)entry;
+                const int cs = START && bslot != 0u ? g.boost_chunk_spp : g.relay_chunk_spp;
+                rw.slot = START && bslot != 0u ? (int)(bslot - 1u) : (int)entry;
+                rw.boost = START && bslot != 0u ? 1 : 0;
                 rw.chunk = rb.chunk;
-                rw.s0 = relay_first_sample(rb.chunk, g.relay_chunk_spp);
-                rw.s1 = relay_end_sample(rb.chunk, g.relay_chunk_spp, g.spp);
+                rw.s0 = relay_first_sample(rb.chunk, cs);
+                rw.s1 = relay_end_sample(rb.chunk, cs, g.spp);
             }
         }
         tile_block = (int)load_uniform(g.border + entry);
@@ -1153,6 +1181,82 @@ __global__ __launch_bounds__(kRelayThreads) void relay_start_kernel(RelayStartAr
         for (uint32_t u = 0; u < n; u++) rank += relay_item_before(w_s[u], j0 + u, wi, i) ? 1u : 0u;
     }
     if (i < t) start[rank] = relay_start_word(relay_item(i, r));
+}
+
+// The same table with promoted tiles (cgrt_relay.h, "Four chunks for the heaviest tiles"), four launches in place of the two, `head`
+// zeroed in front of them.  relay_boost_cost_kernel: thread e < n012 writes ecost[e], the entry's tile cost, and adds cost x spp to
+// S (an integer sum: any order is exact).  relay_boost_promote_kernel: thread e < n_split ranks its entry among the candidates --
+// all n_split keys, a workgroup's worth at a time through LDS -- and writes bslot[e]; the promoted are counted.
+// relay_boost_weight_kernel: thread v writes weight[v] of virtual item v = entry * k_boost + chunk (kRelayNoItem where the
+// entry has no such chunk), and one thread leaves the item count in the head.  relay_boost_start_kernel: relay_start_kernel over
+// the virtual items, those that are none skipped.  O(n^2 / 256) a thread as before, n = k_boost * n012.
+struct RelayBoostArgs {
+    RelayStartArgs a;
+    RelayBoost b;
+};
+__global__ __launch_bounds__(kRelayThreads) void relay_boost_cost_kernel(RelayBoostArgs ba, const uint32_t *__restrict__ plan, const uint32_t *__restrict__ list,
+                                                                         const uint32_t *__restrict__ wcost, uint32_t *__restrict__ ecost,
+                                                                         uint32_t *__restrict__ head) {
+    const RelayItems r = relay_items_of(ba.a, plan);
+    const uint32_t e = blockIdx.x * kRelayThreads + threadIdx.x;
+    if (e >= r.n012) return;
+    const uint32_t c = relay_tile_cost(wcost, list[e], ba.a.tiles_x, ba.a.wtiles_x, ba.a.wtiles_y);
+    ecost[e] = c;
+    if (c) atomicAdd(reinterpret_cast<unsigned long long *>(head + kBoostS), (unsigned long long)c * (unsigned long long)r.spp);
+}
+__global__ __launch_bounds__(kRelayThreads) void relay_boost_promote_kernel(RelayBoostArgs ba, const uint32_t *__restrict__ plan,
+                                                                            const uint32_t *__restrict__ ecost, uint32_t *__restrict__ head,
+                                                                            uint32_t *__restrict__ bslot) {
+    const RelayItems r = relay_items_of(ba.a, plan);
+    const uint32_t n_split = relay_split_entries(r.n01, r.n012, r.cap, r.extent), e = blockIdx.x * kRelayThreads + threadIdx.x;
+    if (blockIdx.x * kRelayThreads >= n_split) return;  // the whole workgroup: no barrier is missed
+    const uint64_t S = *reinterpret_cast<const unsigned long long *>(head + kBoostS);
+    __shared__ unsigned long long k_s[kRelayThreads];
+    const uint32_t ce = e < n_split ? ecost[e] : 0u;
+    const uint64_t ke = relay_boost_key(e < n_split && relay_boost_candidate(ce, r, ba.b, S), ce);
+    uint32_t rank = 0;
+    for (uint32_t j0 = 0; j0 < n_split; j0 += kRelayThreads) {
+        __syncthreads();  // every thread is done with the previous batch
+        if (j0 + threadIdx.x < n_split) {
+            const uint32_t cj = ecost[j0 + threadIdx.x];
+            k_s[threadIdx.x] = relay_boost_key(relay_boost_candidate(cj, r, ba.b, S), cj);
+        }
+        __syncthreads();
+        const uint32_t n = min((uint32_t)kRelayThreads, n_split - j0);
+        for (uint32_t u = 0; u < n; u++) rank += relay_item_before(k_s[u], j0 + u, ke, e) ? 1u : 0u;
+    }
+    if (e >= n_split) return;
+    const bool promoted = ke != 0 && rank < ba.b.cap;
+    bslot[e] = promoted ? rank + 1u : 0u;
+    if (promoted) atomicAdd(head + kBoostPromoted, 1u);
+}
+__global__ __launch_bounds__(kRelayThreads) void relay_boost_weight_kernel(RelayBoostArgs ba, const uint32_t *__restrict__ plan,
+                                                                           const uint32_t *__restrict__ ecost, const uint32_t *__restrict__ bslot,
+                                                                           uint32_t *__restrict__ head, unsigned long long *__restrict__ weight) {
+    const RelayItems r = relay_items_of(ba.a, plan);
+    const uint32_t n_split = relay_split_entries(r.n01, r.n012, r.cap, r.extent), v = blockIdx.x * kRelayThreads + threadIdx.x;
+    if (v == 0) head[kBoostItems] = relay_boost_items(r, ba.b, head[kBoostPromoted]);
+    if (v >= r.n012 * ba.b.k) return;
+    const uint32_t e = v / ba.b.k, c = v % ba.b.k;
+    const bool promoted = e < n_split && bslot[e] != 0u;
+    weight[v] = relay_boost_weight(c, relay_boost_chunks(e, promoted, n_split, r, ba.b), promoted, ecost[e], r, ba.b);
+}
+__global__ __launch_bounds__(kRelayThreads) void relay_boost_start_kernel(RelayBoostArgs ba, const uint32_t *__restrict__ plan,
+                                                                          const unsigned long long *__restrict__ weight, uint32_t *__restrict__ start) {
+    const RelayItems r = relay_items_of(ba.a, plan);
+    const uint32_t nv = r.n012 * ba.b.k, v = blockIdx.x * kRelayThreads + threadIdx.x;
+    if (blockIdx.x * kRelayThreads >= nv) return;  // the whole workgroup: no barrier is missed
+    __shared__ unsigned long long w_s[kRelayThreads];
+    const unsigned long long wv = v < nv ? weight[v] : kRelayNoItem;
+    uint32_t rank = 0;
+    for (uint32_t j0 = 0; j0 < nv; j0 += kRelayThreads) {
+        __syncthreads();  // every thread is done with the previous batch
+        if (j0 + threadIdx.x < nv) w_s[threadIdx.x] = weight[j0 + threadIdx.x];
+        __syncthreads();
+        const uint32_t n = min((uint32_t)kRelayThreads, nv - j0);
+        for (uint32_t u = 0; u < n; u++) rank += relay_boost_before(w_s[u], j0 + u, wv, v) ? 1u : 0u;
+    }
+    if (wv != kRelayNoItem) start[rank] = relay_start_word(RelayBlock{v / ba.b.k, (int32_t)(v % ba.b.k), false});
 }
 
 // ---- cost-aware scheduling: plan and ordered sum (GridParams, "Cost-aware scheduling") ------------------------------------

@@ -106,8 +106,17 @@ struct GridParams {
     // ray of the wave tile hits first (sure_first_kernel, cgrt_sure_first.h), or kSureNone; set only for wave tiles of class-3
     // tiles.  A wave of the terminal-diffuse body whose tile has one adds that sphere's colour per sample and traces nothing.
     const unsigned char *wsure;
+    // relay_boost_at != 0 (a launch with a start table that promotes its heaviest tiles to boost_k chunks, cgrt_relay.h):
+    // plan[relay_boost_at + kBoostItems] = the table's items, plan[relay_boost_at + kBoostHead + e] = bslot[e] of split entry e.
+    // A promoted tile's chunks have boost_chunk_spp samples and boost_slots slots a stream, and its slot lies in the boost area,
+    // laid out for (boost_cap, boost_k, boost_slots) at relay + relay_boost_off.
+    uint64_t relay_boost_off;
+    uint32_t relay_boost_at;
+    int32_t boost_k, boost_chunk_spp, boost_cap, boost_slots, pad_boost_;
 };
-static_assert(sizeof(GridParams) == 336, "GridParams is a kernel argument: its layout is fixed");
+static_assert(sizeof(GridParams) == 368, "GridParams is a kernel argument: its layout is fixed");
+// the head of the order buffer's boost part, in words: S (two words), the promoted entries, the table's items; bslot follows
+static constexpr int kBoostS = 0, kBoostPromoted = 2, kBoostItems = 3, kBoostHead = 4;
 
 static constexpr int kTileW = 32, kTileH = 8, kThreads = 256;
 // Tile order of image-order launches (tile_order_kernel, cgrt_eye.hpp): the special spheres -- those that reflect or refract --
@@ -133,9 +142,14 @@ struct TileOrderLayout {
     // start_words > 0 (the relay's cost start, cgrt_relay.h), behind everything else: the wave tiles' probe costs, the items'
     // weights (8 bytes each) and the start table, start_words each of the two
     Region wcost{}, weight{}, start{};
+    // boost_words > 0 (a start table with promoted tiles, cgrt_relay.h), behind those: head and bslot (kBoostHead + split_cap words),
+    // the entries' costs, the virtual items' weights (n_tiles * boost_k) and the table the launch reads instead of `start`
+    // (start_words + boost_words)
+    Region boost{}, ecost{}, bweight{}, bstart{};
     size_t total = 0;  // bytes to allocate
 };
-inline TileOrderLayout tile_order_layout(size_t n_tiles, size_t n_wt, bool sure = false, size_t start_words = 0) {
+inline TileOrderLayout tile_order_layout(size_t n_tiles, size_t n_wt, bool sure = false, size_t start_words = 0, size_t boost_words = 0,
+                                         size_t split_cap = 0, int boost_k = 0) {
     TileOrderLayout L;
     size_t end = 0;  // the list follows the plan at once; every other part starts on 256 bytes
     const auto take = [&end](size_t bytes) { end += bytes; return Region{end - bytes, bytes}; };
@@ -158,6 +172,16 @@ inline TileOrderLayout tile_order_layout(size_t n_tiles, size_t n_wt, bool sure 
         L.weight = take(start_words * sizeof(uint64_t));
         end = align256(end);
         L.start = take(start_words * sizeof(uint32_t));
+    }
+    if (start_words && boost_words) {
+        end = align256(end);
+        L.boost = take((kBoostHead + split_cap) * sizeof(uint32_t));
+        end = align256(end);
+        L.ecost = take(n_tiles * sizeof(uint32_t));
+        end = align256(end);
+        L.bweight = take(n_tiles * (size_t)boost_k * sizeof(uint64_t));
+        end = align256(end);
+        L.bstart = take((start_words + boost_words) * sizeof(uint32_t));
     }
     L.total = align256(end);
     return L;
@@ -243,6 +267,11 @@ struct EyeKnobs {
     int relay_order = -1;   // RELAY_ORDER: chunks_first / mirror_first / interleaved (or 0 / 1 / 2), likewise
     int relay_start = -1;   // RELAY_START: list / cost (kRelayStartList / kRelayStartCost), where the launch's flags name neither (-1: unset)
     int relay_probe_spp = kRelayProbeSpp;  // RELAY_PROBE_SPP: samples of the cost probe (1, 2 or 4; a measurement aid)
+    // RELAY_BOOST: off, or num/den -- the promotion threshold (cgrt_relay.h; a measurement aid); RELAY_BOOST_TILES: >= 0: at most
+    // this many tiles are promoted (the boost area's capacity)
+    bool relay_boost_off = false;
+    uint32_t relay_boost_num = kRelayBoostNum, relay_boost_den = kRelayBoostDen;
+    long long relay_boost_tiles = -1;
     int lens_stage = -1;    // LENS_STAGE: off / lds (kLensStageOff / kLensStageLds), where the launch's flags do not switch it off (-1: unset)
     const char *timeline_file = nullptr;  // TIMELINE_FILE (nullptr: off)
 };
@@ -264,6 +293,25 @@ inline int relay_start_named(const char *e) {
     if (v == "cost" || v == "1") return kRelayStartCost;
     return -1;
 }
+// CGRT_RELAY_BOOST's value: "" (nothing set), off / 0, or num/den; false: none of them (nothing is changed)
+inline bool relay_boost_named(const char *e, bool &off, uint32_t &num, uint32_t &den) {
+    const std::string v(e);
+    if (v.empty()) return true;
+    if (v == "off" || v == "0") {
+        off = true;
+        return true;
+    }
+    const size_t slash = v.find('/');
+    if (slash == std::string::npos || slash == 0 || slash + 1 >= v.size()) return false;
+    for (size_t i = 0; i < v.size(); i++)
+        if (i != slash && (v[i] < '0' || v[i] > '9')) return false;
+    if (slash > 6 || v.size() - slash - 1 > 6) return false;
+    const unsigned long n = std::strtoul(v.c_str(), nullptr, 10), d = std::strtoul(v.c_str() + slash + 1, nullptr, 10);
+    if (n > kRelayBoostMaxTerm || d < 1 || d > kRelayBoostMaxTerm) return false;
+    num = (uint32_t)n;
+    den = (uint32_t)d;
+    return true;
+}
 // Lens points staged ahead of the sample loop (cgrt_lens_stage.h; TileOrderPlan::lens_stage): per-lane batches in LDS
 static constexpr int kLensStageOff = 0, kLensStageLds = 1;
 static constexpr int kLensStageDefault = kLensStageLds;  // the measured form
@@ -274,7 +322,8 @@ inline int lens_stage_named(const char *e) {
     if (v == "lds" || v == "1") return kLensStageLds;
     return -1;
 }
-// Read once per process, at the first launch, except CGRT_TIMELINE_FILE, which every launch reads.
+// Read once per process, at the first launch, except CGRT_TIMELINE_FILE, CGRT_RELAY_BOOST and CGRT_RELAY_BOOST_TILES, which every
+// launch reads.
 inline EyeKnobs eye_knobs() {
     static const EyeKnobs once = [] {
         EyeKnobs k;
@@ -312,6 +361,15 @@ inline EyeKnobs eye_knobs() {
     }();
     EyeKnobs k = once;
     k.timeline_file = *env_str("CGRT_TIMELINE_FILE") ? env_str("CGRT_TIMELINE_FILE") : nullptr;
+    // (the promotion knobs too: a threshold sweep or a test sets them between the launches of one process)
+    if (!relay_boost_named(env_str("CGRT_RELAY_BOOST"), k.relay_boost_off, k.relay_boost_num, k.relay_boost_den)) {
+        static bool said = false;
+        if (!said)
+            std::fprintf(stderr, "cgrt: CGRT_RELAY_BOOST=%s is neither off nor a threshold num/den (integers, num <= %u, 1 <= den <= %u): the default is used\n",
+                         env_str("CGRT_RELAY_BOOST"), kRelayBoostMaxTerm, kRelayBoostMaxTerm);
+        said = true;
+    }
+    if (*env_str("CGRT_RELAY_BOOST_TILES")) k.relay_boost_tiles = std::max(std::atoll(env_str("CGRT_RELAY_BOOST_TILES")), 0ll);
     return k;
 }
 
@@ -402,6 +460,14 @@ struct FramePlan {
     // in the order buffer; relay_order stays the order of a launch that has to go without the table.  List unless relay_k > 1
     int relay_start = kRelayStartList, relay_probe_spp = 0;
     size_t relay_start_words = 0;
+    // Promotion (cgrt_relay.h): relay_boost -- a launch with a start table renders its heaviest split tiles by boost_k > relay_k
+    // workgroups of boost_chunk_spp samples each, parked in boost_slots slots a stream in an area of their own for boost_cap
+    // tiles (boost_bytes, behind the base area); the table may then have boost_words more words and the launch boost_grid more
+    // workgroups; the threshold is boost_num / boost_den of a workgroup slot's even share, over boost_wg_slots slots
+    bool relay_boost = false;
+    int boost_k = 0, boost_chunk_spp = 0, boost_slots = 0, boost_wg_slots = 0;
+    size_t boost_cap = 0, boost_bytes = 0, boost_words = 0, boost_grid = 0;
+    uint32_t boost_num = 0, boost_den = 1;
 };
 
 // Whether a launch of n_tiles tiles relays samples by default: at 32 samples or more (two chunks of 16), and with every workgroup
@@ -439,6 +505,18 @@ inline int relay_start_of(int32_t flags, const EyeKnobs &kn) {
     if (kn.relay_start >= 0) return kn.relay_start;
     const bool names_order = (flags & CGRT_GRID_RELAY_ORDER_MASK) || kn.relay_order >= 0;
     return !names_order && !(flags & CGRT_GRID_SAMPLE_RELAY) ? kRelayStartCost : kRelayStartList;
+}
+
+// Whether a launch with a start table promotes: CGRT_GRID_NO_RELAY_BOOST, then CGRT_GRID_RELAY_BOOST, then the knob's `off`;
+// otherwise exactly the launch that starts by cost by default does (relay_start_of's last rule).
+static constexpr int kRelayWgPerCu = 4;  // resident workgroups a compute unit of the START variants (256 threads, 4 waves a SIMD)
+inline bool relay_boost_of(int32_t flags, const EyeKnobs &kn) {
+    if (flags & CGRT_GRID_NO_RELAY_BOOST) return false;
+    if (flags & CGRT_GRID_RELAY_BOOST) return true;
+    if (kn.relay_boost_off) return false;
+    if ((flags & (CGRT_GRID_NO_RELAY_COST_START | CGRT_GRID_RELAY_COST_START)) || kn.relay_start >= 0) return false;
+    const bool names_order = (flags & CGRT_GRID_RELAY_ORDER_MASK) || kn.relay_order >= 0;
+    return !names_order && !(flags & CGRT_GRID_SAMPLE_RELAY);
 }
 
 // The launch at capacity kmax (0 when it is not scheduled): a function of the inputs and kmax only
@@ -508,6 +586,24 @@ inline FramePlan frame_plan(const FrameInputs &in, size_t kmax) {
                 if (p.relay_start == kRelayStartCost) {
                     p.relay_probe_spp = std::min(kn.relay_probe_spp, (int)gr.spp);
                     p.relay_start_words = relay_start_words((size_t)p.tile_blocks, rc.k, p.relay_cap);
+                    const RelayChunks rb = relay_chunks(gr.spp, kRelayMaxChunks);
+                    if (rb.k > rc.k && relay_boost_of(gr.flags, kn) && kn.relay_boost_tiles != 0) {
+                        const int bslots = relay_slots(rb.chunk_spp, gr.max_depth);
+                        const size_t base = align256(p.relay_bytes);
+                        const size_t bcap = relay_cap(p.relay_cap, rb.k, bslots, relay_boost_budget(in.mem_total, base), kn.relay_boost_tiles);
+                        if (bcap > 0) {
+                            p.relay_boost = true;
+                            p.boost_k = rb.k;
+                            p.boost_chunk_spp = rb.chunk_spp;
+                            p.boost_slots = bslots;
+                            p.boost_wg_slots = in.n_cu * kRelayWgPerCu;
+                            p.boost_cap = bcap;
+                            p.boost_bytes = relay_layout(bcap, rb.k, bslots).total;
+                            p.boost_words = p.boost_grid = relay_boost_extra(rc.k, rb.k, bcap);
+                            p.boost_num = kn.relay_boost_num;
+                            p.boost_den = kn.relay_boost_den;
+                        }
+                    }
                 }
             }
         }

@@ -954,8 +954,15 @@ static int relay_cost_start(const cgrt_scene *s, const EyeLaunch &L, const Frame
     uint32_t *wcost = at.wcost.in<uint32_t>(base), *start = at.start.in<uint32_t>(base);
     unsigned long long *weight = at.weight.in<unsigned long long>(base);
     if (!wcost || !start || !weight) return CGRT_OK;  // (the layout has no table: the launch goes by its list)
+    // promoted tiles (cgrt_relay.h): the table is the promoted form's, in its own parts of the buffer
+    uint32_t *head = at.boost.in<uint32_t>(base), *ecost = at.ecost.in<uint32_t>(base), *bstart = at.bstart.in<uint32_t>(base);
+    unsigned long long *bweight = at.bweight.in<unsigned long long>(base);
+    const bool boost = p.relay_boost && g.boost_k > g.relay_k && head && ecost && bstart && bweight;
+    const RelayBoost rb = boost ? RelayBoost{(uint32_t)p.boost_k, (uint32_t)p.boost_cap, p.boost_chunk_spp, p.boost_num, p.boost_den, (uint32_t)p.boost_wg_slots}
+                                : RelayBoost{};
     const TileOrderState::CostKey ck{g.seed, g.max_depth, p.relay_probe_spp};
-    const TileOrderState::TableKey tk{g.spp, g.relay_k, g.relay_chunk_spp, g.relay_cap, g.relay_extent, 0};
+    const TileOrderState::TableKey tk{g.spp, g.relay_k, g.relay_chunk_spp, g.relay_cap, g.relay_extent, (int32_t)rb.k, (int32_t)rb.cap,
+                                      (int32_t)rb.num, (int32_t)rb.den, (int32_t)rb.slots};
     const bool have_cost = o.reused && o.cost_valid && std::memcmp(&ck, &o.cost_key, sizeof(ck)) == 0;
     const bool have_table = have_cost && o.table_valid && std::memcmp(&tk, &o.table_key, sizeof(tk)) == 0;
     o.cost_valid = o.table_valid = false;
@@ -970,7 +977,7 @@ static int relay_cost_start(const cgrt_scene *s, const EyeLaunch &L, const Frame
         gp.tile_order = kOrderFull;
         gp.relay = nullptr;
         gp.relay_k = 0;
-        gp.relay_start_at = 0;
+        gp.relay_start_at = gp.relay_boost_at = 0;
         if (int rc = launch_eye(start_twin(L), false, s->device, gp, dim3((unsigned)p.grid_dim), st, nullptr, nullptr, nullptr)) return rc;
     }
     if (!have_table) {
@@ -978,8 +985,19 @@ static int relay_cost_start(const cgrt_scene *s, const EyeLaunch &L, const Frame
         const RelayStartArgs a{RelayItems{(uint32_t)g.relay_k, 0, 0, 0, (uint32_t)g.relay_cap, g.relay_extent, g.relay_chunk_spp, g.spp},
                                (uint32_t)tiles_x, (uint32_t)p.wtiles_x, (uint32_t)p.wtiles_y};
         const dim3 grid((unsigned)((p.relay_start_words + kRelayThreads - 1) / kRelayThreads));
-        hipLaunchKernelGGL(relay_weight_kernel, grid, dim3(kRelayThreads), 0, st, a, g.plan, g.border, wcost, weight);
-        hipLaunchKernelGGL(relay_start_kernel, grid, dim3(kRelayThreads), 0, st, a, g.plan, weight, start);
+        if (boost) {
+            const RelayBoostArgs ba{a, rb};
+            const auto blocks = [](size_t threads) { return dim3((unsigned)((threads + kRelayThreads - 1) / kRelayThreads)); };
+            const size_t n_tiles = (size_t)p.tile_blocks;
+            HIP_TRY(hipMemsetAsync(head, 0, kBoostHead * sizeof(uint32_t), st));
+            hipLaunchKernelGGL(relay_boost_cost_kernel, blocks(n_tiles), dim3(kRelayThreads), 0, st, ba, g.plan, g.border, wcost, ecost, head);
+            hipLaunchKernelGGL(relay_boost_promote_kernel, blocks(p.relay_cap), dim3(kRelayThreads), 0, st, ba, g.plan, ecost, head, head + kBoostHead);
+            hipLaunchKernelGGL(relay_boost_weight_kernel, blocks(n_tiles * rb.k), dim3(kRelayThreads), 0, st, ba, g.plan, ecost, head + kBoostHead, head, bweight);
+            hipLaunchKernelGGL(relay_boost_start_kernel, blocks(n_tiles * rb.k), dim3(kRelayThreads), 0, st, ba, g.plan, bweight, bstart);
+        } else {
+            hipLaunchKernelGGL(relay_weight_kernel, grid, dim3(kRelayThreads), 0, st, a, g.plan, g.border, wcost, weight);
+            hipLaunchKernelGGL(relay_start_kernel, grid, dim3(kRelayThreads), 0, st, a, g.plan, weight, start);
+        }
     }
     // the order's event now stands behind the table too (a reusing launch on another stream waits for it)
     if (o.valid && (have_table || (hipPeekAtLastError() == hipSuccess && hipEventRecord(o.ev, st) == hipSuccess))) {
@@ -991,7 +1009,9 @@ static int relay_cost_start(const cgrt_scene *s, const EyeLaunch &L, const Frame
         (void)hipGetLastError();
         o.valid = false;
     }
-    g.relay_start_at = (uint32_t)((at.start.at - at.plan.at) / sizeof(uint32_t));
+    g.relay_start_at = (uint32_t)(((boost ? at.bstart.at : at.start.at) - at.plan.at) / sizeof(uint32_t));
+    g.relay_boost_at = boost ? (uint32_t)((at.boost.at - at.plan.at) / sizeof(uint32_t)) : 0u;
+    o.boost = rb;
     o.start_words = p.relay_start_words;
     o.start_wtiles = p.n_wt;
     o.start_reused = have_table;
@@ -1086,6 +1106,7 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
             guard.relayed = true;
             n_blocks = relay_grid(p.grid_dim, p.relay_k, p.relay_cap);
             if (p.relay_start == kRelayStartCost && (rc = relay_cost_start(s, L, p, g, st))) return rc;
+            if (g.relay_boost_at) n_blocks += p.boost_grid;  // (the promoted tiles' extra chunks, as many as the boost area holds)
         }
     }
     DevBuf timeline;
@@ -1185,6 +1206,13 @@ int cgrt_scene_last_relay_start(const cgrt_scene *s, uint32_t *start, int64_t st
     NEED_COMMITTED(s, t && n_wave_tiles && reused);
     ON_DEVICE(s->device);
     return last_relay_start(s->order, s->relay, start, start_cap, wcost, cost_cap, t, n_wave_tiles, reused);
+}
+
+int cgrt_scene_last_relay_boost(const cgrt_scene *s, int64_t *promoted, int32_t *k_boost, int64_t *boost_cap, uint64_t *cost_sum, int32_t *num,
+                                int32_t *den, int32_t *wg_slots, uint32_t *bslot, int64_t slot_cap) {
+    NEED_COMMITTED(s, promoted && k_boost && boost_cap && cost_sum && num && den && wg_slots);
+    ON_DEVICE(s->device);
+    return last_relay_boost(s->order, s->relay, promoted, k_boost, boost_cap, cost_sum, num, den, wg_slots, bslot, slot_cap);
 }
 
 int cgrt_trace_grid_diffuse_variant(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, char *name, size_t cap) {
@@ -1939,6 +1967,35 @@ int cgrt_relay_start_host(int32_t k, int32_t chunk_spp, int32_t spp, int64_t cap
     if (!start || start_cap < *t || *t == 0) return CGRT_OK;
     std::vector<uint64_t> weight((size_t)*t);
     relay_start_table(r, list, wcost, tiles_x, wtiles_x, wtiles_y, weight.data(), start);
+    return CGRT_OK;
+}
+
+int cgrt_relay_boost_host(int32_t k, int32_t chunk_spp, int32_t spp, int64_t cap, int32_t extent, int64_t n01, int64_t n012, int64_t n_tiles,
+                          const uint32_t *list, const uint32_t *wcost, int32_t width, int32_t rows, int32_t k_boost, int32_t boost_chunk_spp,
+                          int64_t boost_cap, int32_t num, int32_t den, int32_t wg_slots, uint32_t *start, int64_t start_cap, uint32_t *bslot,
+                          int64_t slot_cap, int64_t *t, int64_t *promoted, uint64_t *cost_sum) {
+    if (!t || !promoted || !cost_sum || !list || !wcost || k < 2 || k > kRelayMaxChunks || chunk_spp <= 0 || spp <= 0 || cap < 0 || width <= 0 ||
+        rows <= 0 || n01 < 0 || n01 > n012 || n012 > n_tiles || (size_t)n_tiles >= kRelayStartMaxTiles ||
+        (extent != kRelayGlass && extent != kRelayMirror) || k_boost < k || k_boost > kRelayMaxChunks || boost_chunk_spp <= 0 || boost_cap < 0 ||
+        num < 0 || (uint32_t)num > kRelayBoostMaxTerm || den < 1 || (uint32_t)den > kRelayBoostMaxTerm || wg_slots < 1)
+        return fail(CGRT_ERR_INVALID, "bad argument");
+    const uint32_t tiles_x = (uint32_t)((width + kTileW - 1) / kTileW), tiles_y = (uint32_t)((rows + kTileH - 1) / kTileH);
+    const uint32_t wtiles_x = (uint32_t)((width + kWaveTileW - 1) / kWaveTileW), wtiles_y = (uint32_t)((rows + kWaveTileH - 1) / kWaveTileH);
+    if ((int64_t)tiles_x * tiles_y != n_tiles) return fail(CGRT_ERR_INVALID, "n_tiles is not the grid's tile count");
+    for (int64_t e = 0; e < n012; e++)
+        if (list[e] >= (uint32_t)n_tiles) return fail(CGRT_ERR_INVALID, "list names a tile beyond the grid");
+    const RelayItems r{(uint32_t)k, (uint32_t)n01, (uint32_t)n012, (uint32_t)n_tiles, (uint32_t)std::min<int64_t>(cap, n_tiles), extent, chunk_spp, spp};
+    const RelayBoost b{(uint32_t)k_boost, (uint32_t)std::min<int64_t>(boost_cap, n_tiles), boost_chunk_spp, (uint32_t)num, (uint32_t)den, (uint32_t)wg_slots};
+    const size_t n_split = relay_split_entries(r.n01, r.n012, r.cap, r.extent);
+    const size_t most = relay_items_total(r) + relay_boost_extra(k, k_boost, std::min<size_t>(b.cap, n_split));
+    std::vector<uint64_t> weight(most + 1);
+    std::vector<uint32_t> table(most + 1), slots(n_split + 1);
+    const RelayBoosted out = relay_boost_table(r, b, list, wcost, tiles_x, wtiles_x, wtiles_y, slots.data(), weight.data(), table.data());
+    *t = (int64_t)out.items;
+    *promoted = (int64_t)out.promoted;
+    *cost_sum = out.S;
+    if (start && start_cap >= *t) std::copy(table.begin(), table.begin() + out.items, start);
+    if (bslot && slot_cap >= (int64_t)n_split) std::copy(slots.begin(), slots.begin() + n_split, bslot);
     return CGRT_OK;
 }
 

@@ -1,7 +1,7 @@
 // The sample relay of tile-order launches, in plain C++ (no HIP): how a tile's samples are cut into chunks, which workgroup of
 // the launch renders which (entry, chunk), and where a split tile's values lie in the handle's relay area.  The host plans with
 // these functions (cgrt_trace_grid, cgrt_hip.hip), trace_grid_kernel (cgrt_eye.hpp) maps its workgroups with the same ones, and
-// tests/native/relay_map.cpp, relay_order.cpp and relay_start.cpp check them on the CPU.  DESIGN.md section 4.6.
+// tests/native/relay_map.cpp, relay_order.cpp, relay_start.cpp and relay_boost.cpp check them on the CPU.  DESIGN.md section 4.6.
 //
 // A lane of trace_grid_body owns a pixel and runs its samples one after the other, so a wave lasts as long as its costliest
 // pixel: on a refracting sphere ~11 rays a sample, ~700 dependent scene walks at 64 samples.  The relay cuts that chain: the
@@ -165,6 +165,102 @@ inline void relay_start_table(const RelayItems &r, const uint32_t *list, const u
         for (uint32_t j = 0; j < t; j++) rank += relay_item_before(weight[j], j, weight[i], i) ? 1u : 0u;
         start[rank] = relay_start_word(relay_item(i, r));
     }
+}
+
+// Four chunks for the heaviest tiles ("Promotion").  The start order cannot shorten an item, and the
+// frame ends with the long items that found a slot late; a launch that starts by cost therefore renders the split entries whose
+// items are long -- the PROMOTED ones -- by k_boost = relay_chunks(spp, kRelayMaxChunks).k workgroups instead of k, the others
+// as before.  Entry e < n_split (a split entry) is a CANDIDATE when
+//     cost_e * base chunk samples * slots * den  >  num * S,     S = sum of cost_e * spp over the entries of classes 0-2,
+// that is when its base item alone would hold one of the device's `slots` workgroup slots for more than num/den of the frame's
+// even share S / slots.  Integers throughout (64 bits: probe costs are iteration counts of a few samples, far below 2^32, num
+// and den at most kRelayBoostMaxTerm), so host and device find the same set.  Promoted tiles park in an area of their own that
+// holds `cap` of them: the candidates are ranked by cost, descending, ties in entry order (relay_item_before), the first `cap`
+// are promoted, and a promoted entry's rank is its slot in that area.  bslot[e] = slot + 1, 0 for an entry that is not promoted:
+// a word per split entry in the order buffer, which is how a workgroup learns its tile's form.
+// The items of the table are then, in (entry, chunk) order, a promoted entry's k_boost chunks of boost chunk_spp samples, any
+// other split entry's k chunks, an unsplit entry's one; weight and total order as above.  The ranking kernels number them by the
+// VIRTUAL index v = entry * k_boost + chunk, chunks an entry has not being skipped: the same order without a prefix sum.
+static constexpr uint32_t kRelayBoostMaxTerm = 4096;            // num and den of the threshold
+static constexpr uint32_t kRelayBoostNum = 3, kRelayBoostDen = 4;  // the default threshold (measured: DESIGN.md section 6)
+static constexpr uint64_t kRelayNoItem = ~(uint64_t)0;          // weight of a virtual index that is no item
+// (a word per split entry rather than a bit of the table word: the workgroup needs the tile's boost slot, not only the fact)
+static_assert(kRelayStartMaxTiles <= ((size_t)1 << 32) - 1, "bslot[e] = boost slot + 1 <= tiles of a table, in a 32-bit word");
+struct RelayBoost {
+    uint32_t k, cap;    // chunks of a promoted tile; tiles the boost area holds
+    int32_t chunk_spp;  // samples of a promoted tile's chunk
+    uint32_t num, den, slots;
+};
+CGRT_HD bool relay_boost_candidate(uint32_t cost, const RelayItems &r, const RelayBoost &b, uint64_t S) {
+    return b.k > r.k && (uint64_t)cost * (uint64_t)r.chunk_spp * (uint64_t)b.slots * (uint64_t)b.den > (uint64_t)b.num * S;
+}
+// the ranking key of a split entry among the candidates: 0 stands before nothing and is no candidate
+CGRT_HD uint64_t relay_boost_key(bool candidate, uint32_t cost) { return candidate ? (uint64_t)cost + 1u : 0u; }
+// chunks of entry e, and the samples of its chunk c
+CGRT_HD uint32_t relay_boost_chunks(uint32_t e, bool promoted, uint32_t n_split, const RelayItems &r, const RelayBoost &b) {
+    return promoted ? b.k : e < n_split ? r.k : 1u;
+}
+CGRT_HD uint64_t relay_boost_weight(uint32_t c, uint32_t chunks, bool promoted, uint32_t cost, const RelayItems &r, const RelayBoost &b) {
+    if (c >= chunks) return kRelayNoItem;
+    const int32_t cs = promoted ? b.chunk_spp : r.chunk_spp;
+    const int32_t samples = chunks > 1 ? relay_end_sample((int32_t)c, cs, r.spp) - relay_first_sample((int32_t)c, cs) : r.spp;
+    return (uint64_t)cost * (uint64_t)(samples > 0 ? samples : 0);
+}
+// virtual index j stands before virtual index i (both with their weights)
+CGRT_HD bool relay_boost_before(uint64_t wj, uint32_t j, uint64_t wi, uint32_t i) { return wj != kRelayNoItem && relay_item_before(wj, j, wi, i); }
+// items of the table with `promoted` promoted entries, and the words a launch must hold for them (the host knows no count)
+CGRT_HD uint32_t relay_boost_items(const RelayItems &r, const RelayBoost &b, uint32_t promoted) { return relay_items_total(r) + (b.k - r.k) * promoted; }
+CGRT_HD size_t relay_boost_extra(int32_t k, int32_t k_boost, size_t cap_boost) { return (size_t)(k_boost - k) * cap_boost; }
+// The whole computation on the host (the device: relay_boost_*_kernel, cgrt_eye.hpp).  bslot holds n_split words, weight and
+// start relay_items_total(r) + relay_boost_extra(r.k, b.k, min(b.cap, n_split)) at most; returns S, the promoted entries and
+// the items.  Nothing promoted: relay_start_table's table, word for word.
+struct RelayBoosted {
+    uint64_t S;
+    uint32_t promoted, items;
+};
+inline RelayBoosted relay_boost_table(const RelayItems &r, const RelayBoost &b, const uint32_t *list, const uint32_t *wcost, uint32_t tiles_x,
+                                      uint32_t wtiles_x, uint32_t wtiles_y, uint32_t *bslot, uint64_t *weight, uint32_t *start) {
+    const uint32_t n_split = relay_split_entries(r.n01, r.n012, r.cap, r.extent);
+    RelayBoosted out{0, 0, 0};
+    for (uint32_t e = 0; e < r.n012; e++) out.S += (uint64_t)relay_tile_cost(wcost, list[e], tiles_x, wtiles_x, wtiles_y) * (uint64_t)r.spp;
+    const auto key = [&](uint32_t e) {
+        const uint32_t c = relay_tile_cost(wcost, list[e], tiles_x, wtiles_x, wtiles_y);
+        return relay_boost_key(relay_boost_candidate(c, r, b, out.S), c);
+    };
+    for (uint32_t e = 0; e < n_split; e++) {
+        const uint64_t ke = key(e);
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < n_split; j++) rank += relay_item_before(key(j), j, ke, e) ? 1u : 0u;
+        bslot[e] = ke != 0 && rank < b.cap ? rank + 1u : 0u;
+        out.promoted += bslot[e] ? 1u : 0u;
+    }
+    // the items in (entry, chunk) order, then every item's rank
+    uint32_t t = 0;
+    for (uint32_t e = 0; e < r.n012; e++) {
+        const bool p = e < n_split && bslot[e] != 0;
+        const uint32_t kc = relay_boost_chunks(e, p, n_split, r, b), cost = relay_tile_cost(wcost, list[e], tiles_x, wtiles_x, wtiles_y);
+        for (uint32_t c = 0; c < kc; c++) {
+            weight[t] = relay_boost_weight(c, kc, p, cost, r, b);
+            start[t++] = relay_start_word(RelayBlock{e, (int32_t)c, kc > 1});  // (parked here, ranked below)
+        }
+    }
+    out.items = t;
+    uint32_t *word = new uint32_t[t ? t : 1];
+    for (uint32_t i = 0; i < t; i++) word[i] = start[i];
+    for (uint32_t i = 0; i < t; i++) {
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < t; j++) rank += relay_item_before(weight[j], j, weight[i], i) ? 1u : 0u;
+        start[rank] = word[i];
+    }
+    delete[] word;
+    return out;
+}
+// The boost area: relay_layout(cap, k_boost, slots) behind the base area in the handle's buffer, 3 GiB at most, both areas
+// together within an eighth of the device's memory; bound >= 0 (CGRT_RELAY_BOOST_TILES): at most that many tiles
+static constexpr size_t kRelayBoostBudget = (size_t)3 << 30;
+CGRT_HD size_t relay_boost_budget(size_t mem_total, size_t base_bytes) {
+    const size_t left = mem_total / 8 > base_bytes ? mem_total / 8 - base_bytes : 0;
+    return left < kRelayBoostBudget ? left : kRelayBoostBudget;
 }
 
 // The relay area for cap_split tiles, 256 threads a tile (thread t = pixel t of the tile), array after array:

@@ -52,18 +52,22 @@ struct TileOrderState {
         uint64_t seed;
         int32_t max_depth, probe_spp;
     };
+    // (boost_k == 0: a table without promoted tiles, in `start`; else the promoted form's, in `bstart`, with what it depends on)
     struct TableKey {
-        int32_t spp, k, chunk_spp, cap, extent, pad_;
+        int32_t spp, k, chunk_spp, cap, extent, boost_k, boost_cap, boost_num, boost_den, boost_wg_slots;
     };
-    static_assert(sizeof(CostKey) == 16 && sizeof(TableKey) == 24, "compared as bytes: no padding");
+    static_assert(sizeof(CostKey) == 16 && sizeof(TableKey) == 40, "compared as bytes: no padding");
     CostKey cost_key{};
     TableKey table_key{};
     bool cost_valid = false, table_valid = false, start_reused = false;
     size_t start_words = 0, start_wtiles = 0;
+    // the last launch's table was the promoted form's (RelayBoost of it, with the threshold; k == 0: it was not)
+    RelayBoost boost{};
 
     void begin_launch() {
         tiles = mask_wtiles = sure_wtiles = 0;
         start_words = start_wtiles = 0;
+        boost = RelayBoost{};
         reused = start_reused = false;
         class3 = TileOrderPlan::None;
         lens_stage = kLensStageOff;
@@ -87,6 +91,7 @@ struct TileOrderState {
 struct RelayState {
     GrowBuf buf;
     size_t refused = 0, zeroed = 0;
+    size_t boost_zeroed = 0, boost_zeroed_at = 0;  // the boost area's arrival words known to be 0, and where that area began
     bool dirty = false;
     hipEvent_t ev = nullptr;
     hipStream_t stream = nullptr;
@@ -95,6 +100,9 @@ struct RelayState {
         int k = 0;
         size_t cap = 0;
         int slots = 0, extent = 0, order = 0;
+        // promoted tiles: the boost area at boost_off, laid out for (boost_cap, boost_k, boost_slots); boost_k == 0: none
+        int boost_k = 0, boost_slots = 0;
+        size_t boost_cap = 0, boost_off = 0;
     } last;
 
     void begin_launch() { last = Last{}; }
@@ -125,7 +133,7 @@ static int order_tiles(TileOrderState &o, const DeviceScene &dev, const FramePla
     const int tiles_x = (g.W + kTileW - 1) / kTileW, tiles_y = (g.rows + kTileH - 1) / kTileH;
     const size_t n = (size_t)tiles_x * tiles_y;
     const bool masks = p.order.masks, sure = masks && p.order.sure;
-    const TileOrderLayout at = tile_order_layout(n, p.n_wt, sure, p.relay_start_words);
+    const TileOrderLayout at = tile_order_layout(n, p.n_wt, sure, p.relay_start_words, p.relay_boost ? p.boost_words : 0, p.relay_cap, p.boost_k);
     const bool grown = at.total > o.buf.cap;
     if (grown) o.valid = false;
     if (o.buf.need(at.total) != hipSuccess) {
@@ -187,14 +195,16 @@ static int order_tiles(TileOrderState &o, const DeviceScene &dev, const FramePla
 // of them are needed than were zeroed, or after a launch that did not go through; reset by the kernel otherwise.
 static bool relay_prepare(RelayState &r, const FramePlan &p, GridParams &g, Capturing capturing, hipStream_t st) {
     if (capturing != Capturing::None) return false;
-    if (r.refused && p.relay_bytes >= r.refused) return false;
-    if (p.relay_bytes > r.buf.cap) {
+    // (with promoted tiles the boost area follows the base area in the one buffer)
+    const size_t boost_at = align256(p.relay_bytes), bytes = p.relay_boost ? boost_at + p.boost_bytes : p.relay_bytes;
+    if (r.refused && bytes >= r.refused) return false;
+    if (bytes > r.buf.cap) {
         // the launches that use the old area are through before it is freed
         if (r.recorded && hipEventSynchronize(r.ev) != hipSuccess) (void)hipGetLastError();
-        r.zeroed = 0;
-        if (r.buf.need(p.relay_bytes) != hipSuccess) {
+        r.zeroed = r.boost_zeroed = 0;
+        if (r.buf.need(bytes) != hipSuccess) {
             (void)hipGetLastError();
-            r.refused = p.relay_bytes;
+            r.refused = bytes;
             return false;
         }
     }
@@ -214,6 +224,23 @@ static bool relay_prepare(RelayState &r, const FramePlan &p, GridParams &g, Capt
         }
     }
     r.zeroed = p.relay_cap;  // (the words beyond this launch's lie in its arrays)
+    if (p.relay_boost) {
+        if (r.dirty || boost_at != r.boost_zeroed_at || p.boost_cap > r.boost_zeroed) {
+            if (hipMemsetAsync(reinterpret_cast<unsigned char *>(r.buf.p) + boost_at, 0, p.boost_cap * sizeof(uint32_t), st) != hipSuccess) {
+                (void)hipGetLastError();
+                return false;
+            }
+        }
+        r.boost_zeroed = p.boost_cap;
+        r.boost_zeroed_at = boost_at;
+        g.relay_boost_off = boost_at;
+        g.boost_k = p.boost_k;
+        g.boost_chunk_spp = p.boost_chunk_spp;
+        g.boost_cap = (int32_t)p.boost_cap;
+        g.boost_slots = p.boost_slots;
+    } else {
+        r.boost_zeroed = 0;  // (this launch's arrays may lie over them)
+    }
     r.dirty = true;          // until the launch is through (TileOrderGuard::commit)
     g.relay = reinterpret_cast<unsigned char *>(r.buf.p);
     g.relay_k = p.relay_k;
@@ -248,6 +275,12 @@ struct TileOrderGuard {
             relay.stream = st;
             relay.recorded = true;
             relay.last = RelayState::Last{g.relay_k, (size_t)g.relay_cap, g.relay_slots, g.relay_extent, g.relay_order};
+            if (g.relay_boost_at) {
+                relay.last.boost_k = g.boost_k;
+                relay.last.boost_slots = g.boost_slots;
+                relay.last.boost_cap = (size_t)g.boost_cap;
+                relay.last.boost_off = (size_t)g.relay_boost_off;
+            }
             relay.dirty = false;
         }
         through = true;
@@ -311,7 +344,47 @@ static int last_sample_relay(const TileOrderState &o, const RelayState &r, int64
     std::vector<uint32_t> cnt(n_split * (size_t)(l.k - 1) * kRelayThreads);
     const RelayLayout rl = relay_layout(l.cap, l.k, l.slots);
     HIP_TRY(hipMemcpy(cnt.data(), reinterpret_cast<const unsigned char *>(r.buf.p) + rl.rcount, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (uint32_t c : cnt) *parked_values += (int64_t)c;
+    if (l.boost_k == 0 || o.boost.k == 0) {
+        for (uint32_t c : cnt) *parked_values += (int64_t)c;
+        return CGRT_OK;
+    }
+    // promoted tiles: their counts lie in the boost area, at their boost slots (the base slot's are of an earlier launch)
+    std::vector<uint32_t> bslot(n_split);
+    if (int rc = o.read(Region{o.at.boost.at + kBoostHead * sizeof(uint32_t), 0}, bslot.data(), n_split)) return rc;
+    const size_t per = (size_t)(l.boost_k - 1) * kRelayThreads;
+    std::vector<uint32_t> bcnt(l.boost_cap * per);
+    const RelayLayout bl = relay_layout(l.boost_cap, l.boost_k, l.boost_slots);
+    HIP_TRY(hipMemcpy(bcnt.data(), reinterpret_cast<const unsigned char *>(r.buf.p) + l.boost_off + bl.rcount, bcnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < n_split; e++) {
+        if (bslot[e] == 0) {
+            for (size_t i = 0; i < (size_t)(l.k - 1) * kRelayThreads; i++) *parked_values += (int64_t)cnt[e * (size_t)(l.k - 1) * kRelayThreads + i];
+        } else if (bslot[e] <= l.boost_cap) {
+            for (size_t i = 0; i < per; i++) *parked_values += (int64_t)bcnt[(size_t)(bslot[e] - 1) * per + i];
+        }
+    }
+    return CGRT_OK;
+}
+// promotion in the last launch: the head of the boost part and, where asked for, bslot of the relayed entries
+static int last_relay_boost(const TileOrderState &o, const RelayState &r, int64_t *promoted, int32_t *k_boost, int64_t *boost_cap, uint64_t *cost_sum,
+                            int32_t *num, int32_t *den, int32_t *wg_slots, uint32_t *bslot, int64_t slot_cap) {
+    *promoted = *boost_cap = 0;
+    *k_boost = *num = *den = *wg_slots = 0;
+    *cost_sum = 0;
+    if (o.boost.k == 0 || r.last.boost_k == 0 || o.start_words == 0 || o.tiles == 0) return CGRT_OK;
+    uint32_t plan[kOrderClasses + 1], head[kBoostHead];
+    HIP_TRY(hipDeviceSynchronize());
+    if (int rc = o.read(o.at.plan, plan, kOrderClasses + 1)) return rc;
+    if (int rc = o.read(o.at.boost, head, kBoostHead)) return rc;
+    *promoted = (int64_t)head[kBoostPromoted];
+    *k_boost = (int32_t)o.boost.k;
+    *boost_cap = (int64_t)o.boost.cap;
+    *cost_sum = (uint64_t)head[kBoostS] | (uint64_t)head[kBoostS + 1] << 32;
+    *num = (int32_t)o.boost.num;
+    *den = (int32_t)o.boost.den;
+    *wg_slots = (int32_t)o.boost.slots;
+    const size_t n_split = relay_split_entries(plan[2], plan[3], (uint32_t)r.last.cap, r.last.extent);
+    if (bslot && n_split > 0 && slot_cap >= (int64_t)n_split)
+        return o.read(Region{o.at.boost.at + kBoostHead * sizeof(uint32_t), 0}, bslot, n_split);
     return CGRT_OK;
 }
 // the start table of the last launch, its wave tiles' probe costs and the workgroups it ordered
@@ -324,13 +397,20 @@ static int last_relay_start(const TileOrderState &o, const RelayState &r, uint32
     HIP_TRY(hipDeviceSynchronize());
     if (int rc = o.read(o.at.plan, plan, kOrderClasses + 1)) return rc;
     const RelayItems ri{(uint32_t)r.last.k, plan[2], plan[3], plan[kOrderClasses], (uint32_t)r.last.cap, r.last.extent, 0, 0};
-    const size_t n = relay_items_total(ri);
-    if (n > o.start_words) return fail(CGRT_ERR_DEVICE, "relay start table: more workgroups than the table holds");
+    size_t n = relay_items_total(ri);
+    const bool boosted = o.boost.k != 0 && r.last.boost_k != 0;  // the promoted form's table: its own part, its count in the head
+    if (boosted) {
+        uint32_t head[kBoostHead];
+        if (int rc = o.read(o.at.boost, head, kBoostHead)) return rc;
+        n = head[kBoostItems];
+    }
+    if (n > (boosted ? o.at.bstart.bytes / sizeof(uint32_t) : o.start_words))
+        return fail(CGRT_ERR_DEVICE, "relay start table: more workgroups than the table holds");
     *t = (int64_t)n;
     *n_wave_tiles = (int64_t)o.start_wtiles;
     *reused = o.start_reused ? 1 : 0;
     if (start && start_cap >= (int64_t)n && n > 0)
-        if (int rc = o.read(o.at.start, start, n)) return rc;
+        if (int rc = o.read(boosted ? o.at.bstart : o.at.start, start, n)) return rc;
     if (wcost && cost_cap >= (int64_t)o.start_wtiles && o.start_wtiles > 0)
         if (int rc = o.read(o.at.wcost, wcost, o.start_wtiles)) return rc;
     return CGRT_OK;

@@ -26,11 +26,14 @@ _RELAY_ORDERS = ("chunks_first", "mirror_first", "interleaved")  # CGRT_GRID_REL
 _RELAY_STARTS = ("list", "cost")  # CGRT_GRID_NO_RELAY_COST_START / CGRT_GRID_RELAY_COST_START
 
 
-def _relay_flag(sample_relay, relay_mirror=None, relay_order=None, relay_start=None):
+def _relay_flag(sample_relay, relay_mirror=None, relay_order=None, relay_start=None, relay_boost=None):
     """CGRT_GRID_SAMPLE_RELAY / _NO_SAMPLE_RELAY / _SAMPLE_RELAY_4 for trace_grid's sample_relay=None|True|False|2|4, with
     CGRT_GRID_RELAY_MIRROR / _NO_MIRROR for relay_mirror=None|True|False, the order field for relay_order=None|a name and
-    CGRT_GRID_RELAY_COST_START / _NO_RELAY_COST_START for relay_start=None|"cost"|"list"."""
+    CGRT_GRID_RELAY_COST_START / _NO_RELAY_COST_START for relay_start=None|"cost"|"list" and CGRT_GRID_RELAY_BOOST /
+    _NO_RELAY_BOOST for relay_boost=None|True|False."""
     form = 0 if relay_mirror is None else (8192 if relay_mirror else 16384)
+    if relay_boost is not None:
+        form |= 2097152 if relay_boost else 4194304
     if relay_start is not None:
         if relay_start not in _RELAY_STARTS:
             raise ValueError("relay_start: None, " + ", ".join(repr(o) for o in _RELAY_STARTS))
@@ -46,6 +49,25 @@ def _relay_flag(sample_relay, relay_mirror=None, relay_order=None, relay_start=N
     if int(sample_relay) not in (2, 4):
         raise ValueError("sample_relay: None, True, False, 2 or 4")
     return form | 1024 | (4096 if int(sample_relay) == 4 else 0)
+
+
+def relay_boost_host(k, chunk_spp, spp, cap, mirror, plan, tile_list, wcost, width, rows, k_boost, boost_chunk_spp, boost_cap, num, den,
+                     wg_slots):
+    """The promoted set and its start table on the host (cgrt_relay_boost_host; no GPU): relay_start_host's arguments, then a
+    promoted tile's k_boost workgroups of boost_chunk_spp samples, the second area's boost_cap tiles and the threshold num / den
+    over wg_slots workgroup slots.  dict(start [t] uint32, bslot [relayed tiles] uint32, promoted, S) -- what last_relay_start()
+    and last_relay_boost() hold for such a launch."""
+    lib = _capi.lib()
+    lst, wc = np.ascontiguousarray(tile_list, np.uint32), np.ascontiguousarray(wcost, np.uint32)
+    assert wc.size == ((width + 15) // 16) * ((rows + 3) // 4) and lst.size == int(plan[4])
+    args = (int(k), int(chunk_spp), int(spp), int(cap), 1 if mirror else 0, int(plan[2]), int(plan[3]), int(plan[4]), lst.ctypes.data,
+            wc.ctypes.data, int(width), int(rows), int(k_boost), int(boost_chunk_spp), int(boost_cap), int(num), int(den), int(wg_slots))
+    t, p, S = C.c_int64(), C.c_int64(), C.c_uint64()
+    n_split = min(int(plan[3]) if mirror else int(plan[2]), int(cap))
+    start = np.zeros(max(int(plan[3]) + (int(k_boost) - 1) * n_split, 1), np.uint32)
+    bslot = np.zeros(max(n_split, 1), np.uint32)
+    check(lib.cgrt_relay_boost_host(*args, start.ctypes.data, start.size, bslot.ctypes.data, bslot.size, C.byref(t), C.byref(p), C.byref(S)))
+    return dict(start=start[:t.value], bslot=bslot[:n_split], promoted=int(p.value), S=int(S.value))
 
 
 def relay_start_host(k, chunk_spp, spp, cap, mirror, plan, tile_list, wcost, width, rows):
@@ -203,7 +225,7 @@ class Scene:
                    stripe=None, sample_offset=0, spp_total=None, out=None, nhit=None, counters=None, stream=None,
                    stats=False, accumulate=False, split_samples=False, reorder=True, force_reorder=False, tile_order=True,
                    diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None,
-                   relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True, relay_start=None):
+                   relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True, relay_start=None, relay_boost=None):
         """Asynchronous launch on torch's current stream (or `stream`).  reorder=False: CGRT_GRID_NO_REORDER (tiles in image
         order instead of heaviest-first; same image).  tile_order=False: CGRT_GRID_NO_TILE_ORDER (an image-order launch starts
         its tiles row-major instead of mirror / glass tiles first; same image).  diffuse_tiles=True: CGRT_GRID_DIFFUSE_TILES (a
@@ -220,7 +242,9 @@ class Scene:
         measured form when it is not (last_relay_form tells).  relay_start: "cost" -- the relay's workgroups of classes 0-2 start
         longest first by a probed cost (CGRT_GRID_RELAY_COST_START; same image, hit counts and counters; last_relay_start),
         "list" -- in the order named (CGRT_GRID_NO_RELAY_COST_START); None: by cost where the launch relays by default and names
-        no order.  lens_stage=False: CGRT_GRID_NO_LENS_STAGE (the thin-lens
+        no order.  relay_boost: True -- a launch with that table at 48 samples or more renders its heaviest relayed tiles by 3 or 4
+        workgroups instead of 2 (CGRT_GRID_RELAY_BOOST; same image, hit counts, rays and Hitpoints; last_relay_boost), False --
+        CGRT_GRID_NO_RELAY_BOOST; None: where the launch starts by cost by default.  lens_stage=False: CGRT_GRID_NO_LENS_STAGE (the thin-lens
         terminal-diffuse body inside the main launch draws every lens point by its own rejection loop instead of staging 16
         samples' draws ahead; same image; last_lens_stage).  sure_tiles=False: CGRT_GRID_NO_SURE_TILES (a wave of the
         terminal-diffuse body traces its samples even where every ray of its 16x4 wave tile provably hits the same sphere first;
@@ -244,7 +268,7 @@ class Scene:
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (2 if accumulate else 0) | (4 if split_samples else 0) |
                               (0 if reorder else 8) | (16 if force_reorder else 0) | (0 if tile_order else 64) |
-                              (128 if diffuse_tiles else 0) | (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order, relay_start) |
+                              (128 if diffuse_tiles else 0) | (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order, relay_start, relay_boost) |
                               (0 if lens_stage else 131072) | (0 if sure_tiles else 262144))
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         check(self._L.cgrt_trace_grid(self._h, C.byref(cc), C.byref(g), out.data_ptr(),
@@ -532,7 +556,7 @@ class Scene:
     def trace_grid_host(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                         stripe=None, sample_offset=0, spp_total=None, stats=False, split_samples=False, reorder=True,
                         force_reorder=False, tile_order=True, diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None,
-                        relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True, relay_start=None):
+                        relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True, relay_start=None, relay_boost=None):
         """Synchronous form with numpy outputs (no torch needed): dict(rgb, nhit, counters)."""
         rows = height - row_offset if rows is None else rows
         rgb = np.zeros((rows, width, 3), np.float32)
@@ -541,7 +565,7 @@ class Scene:
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (1 if stats else 0) | (4 if split_samples else 0) | (0 if reorder else 8) |
                               (16 if force_reorder else 0) | (0 if tile_order else 64) | (128 if diffuse_tiles else 0) |
-                              (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order, relay_start) |
+                              (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order, relay_start, relay_boost) |
                               (0 if lens_stage else 131072) | (0 if sure_tiles else 262144))
         check(self._L.cgrt_trace_grid_host(self._h, C.byref(cc), C.byref(g), rgb.ctypes.data, nhit.ctypes.data,
                                            cnt.ctypes.data))
@@ -618,6 +642,22 @@ class Scene:
         check(self._L.cgrt_scene_last_relay_start(self._h, start.ctypes.data, start.size, wcost.ctypes.data, n.value, C.byref(t),
                                                   C.byref(n), C.byref(r)))
         return dict(t=int(t.value), start=start[:t.value], wcost=wcost, reused=bool(r.value))
+
+    def last_relay_boost(self):
+        """Promotion in that launch (cgrt_scene_last_relay_boost; synchronises the device): None when the launch promoted by no
+        table, else dict(promoted: tiles rendered by k_boost workgroups, k_boost, boost_cap: tiles the second area held, S: the
+        sum of tile cost x samples over classes 0-2, num, den: the threshold, wg_slots, bslot [relayed tiles] uint32: boost
+        slot + 1 of list entry e, 0 where it was not promoted)."""
+        p, k, cap, S = C.c_int64(), C.c_int32(), C.c_int64(), C.c_uint64()
+        num, den, ws = C.c_int32(), C.c_int32(), C.c_int32()
+        tiles = self.last_sample_relay()["tiles"]
+        bslot = np.zeros(max(tiles, 1), np.uint32)
+        check(self._L.cgrt_scene_last_relay_boost(self._h, C.byref(p), C.byref(k), C.byref(cap), C.byref(S), C.byref(num), C.byref(den),
+                                                  C.byref(ws), bslot.ctypes.data, bslot.size))
+        if k.value == 0:
+            return None
+        return dict(promoted=int(p.value), k_boost=int(k.value), boost_cap=int(cap.value), S=int(S.value), num=int(num.value),
+                    den=int(den.value), wg_slots=int(ws.value), bslot=bslot[:tiles])
 
     def last_lens_stage(self):
         """Lens points staged ahead by this scene's last trace_grid / trace_grid_host (cgrt_scene_last_lens_stage; synchronises

@@ -156,6 +156,16 @@ enum {
                                  counts and all counters are identical.  The default of a launch that relays by default and
                                  names no order; a launch on a captured stream goes without ...                          */
     CGRT_GRID_NO_RELAY_COST_START = 1048576, /* ... and this one switches it off: the order the flags above name           */
+    CGRT_GRID_RELAY_BOOST = 2097152, /* a launch with a start table (see CGRT_GRID_RELAY_COST_START) at 48 samples or more: the
+                                 relayed tiles whose workgroups are long -- tile cost x samples of a chunk above a share of
+                                 the frame's work per workgroup slot (CGRT_RELAY_BOOST=num/den, default 3/4) -- are PROMOTED:
+                                 rendered by 3 or 4 workgroups of >= 16 samples instead of 2, parked in a second area on the
+                                 handle (at most 3 GiB, both areas within an eighth of the device; the heaviest tiles where it
+                                 is short, CGRT_RELAY_BOOST_TILES bounds it).  The additions keep the unsplit loop's order:
+                                 image, hit counts, rays and Hitpoints are bit-identical, CGRT_CNT_WAVE_ITERS differs.  A
+                                 launch without a table promotes nothing (cgrt_scene_last_relay_boost tells) ...          */
+    CGRT_GRID_NO_RELAY_BOOST = 4194304, /* ... and this one switches promotion off (as the knob CGRT_RELAY_BOOST=off does where
+                                 no flag speaks); off wins                                                               */
     CGRT_GRID_NO_LENS_STAGE = 131072, /* the terminal-diffuse body inside the main launch (see CGRT_GRID_NO_SPHERE_PAIRS) under a
                                  thin-lens camera: by default a wave finds the accepted lens draws of its next 16 samples
                                  ahead of their use -- attempt 1 of every sample without divergence, then the rejected ones,
@@ -711,7 +721,9 @@ int cgrt_scene_last_relay_form(const cgrt_scene *s, int32_t *mirror, int32_t *or
 /* The start table of that relay (see CGRT_GRID_RELAY_COST_START; synchronises the device): *t = the workgroups of classes 0-2
  * it ordered by cost, 0 when the launch had no table; *n_wave_tiles = the wave tiles of the launch, *reused = 1 when probe and
  * table were those of an earlier launch.  With start_cap >= *t: start[b] = entry << 2 | chunk of workgroup b, to HOST memory;
- * with cost_cap >= *n_wave_tiles: wcost[wave tile] = the probe's iteration count (0: not probed, a class-3 tile). */
+ * with cost_cap >= *n_wave_tiles: wcost[wave tile] = the probe's iteration count (0: not probed, a class-3 tile).  A launch with
+ * promoted tiles (cgrt_scene_last_relay_boost) returns its full table: a promoted tile's chunks 0 .. k_boost - 1 are all in it
+ * and *t is the true count of its workgroups. */
 int cgrt_scene_last_relay_start(const cgrt_scene *s, uint32_t *start, int64_t start_cap, uint32_t *wcost, int64_t cost_cap, int64_t *t,
                                 int64_t *n_wave_tiles, int32_t *reused);
 /* Lens points staged ahead of the sample loop by the LAST cgrt_trace_grid on the handle (see CGRT_GRID_NO_LENS_STAGE;
@@ -727,6 +739,24 @@ int cgrt_scene_last_lens_stage(const cgrt_scene *s, int64_t *lds_tiles, int64_t 
 int cgrt_relay_start_host(int32_t k, int32_t chunk_spp, int32_t spp, int64_t cap, int32_t extent, int64_t n01, int64_t n012, int64_t n_tiles,
                           const uint32_t *list, const uint32_t *wcost, int32_t width, int32_t rows, uint32_t *start, int64_t start_cap,
                           int64_t *t);
+
+/* Promotion in that launch (see CGRT_GRID_RELAY_BOOST; synchronises the device): *promoted = the tiles rendered by *k_boost
+ * workgroups (0: none, or the launch did not promote), *boost_cap = the tiles the second area held, *cost_sum = S, the sum of
+ * tile cost x samples over the tiles of classes 0-2 that the threshold *num / *den refers to, *wg_slots = the workgroup slots
+ * it counted.  With slot_cap >= the launch's relayed tiles (cgrt_scene_last_sample_relay's *tiles): bslot[e] = boost slot + 1 of
+ * list entry e, 0 where it was not promoted, to HOST memory.  For such a launch cgrt_scene_last_relay_start returns the whole
+ * table, a promoted tile's *k_boost chunks included, with *t the true count of its workgroups; cgrt_scene_last_sample_relay
+ * keeps *chunks as the base count, and *parked_values counts what went through both areas. */
+int cgrt_scene_last_relay_boost(const cgrt_scene *s, int64_t *promoted, int32_t *k_boost, int64_t *boost_cap, uint64_t *cost_sum,
+                                int32_t *num, int32_t *den, int32_t *wg_slots, uint32_t *bslot, int64_t slot_cap);
+/* Host evaluation of the promoted set and its table (cgrt_relay.h; no GPU): cgrt_relay_start_host's arguments, then a promoted
+ * tile's k_boost workgroups of boost_chunk_spp samples, the second area's boost_cap tiles and the threshold num / den over
+ * wg_slots workgroup slots.  Writes start[b] for b < *t when start_cap >= *t, and bslot[e] for the relayed entries when
+ * slot_cap >= their number; *promoted and *cost_sum as above. */
+int cgrt_relay_boost_host(int32_t k, int32_t chunk_spp, int32_t spp, int64_t cap, int32_t extent, int64_t n01, int64_t n012, int64_t n_tiles,
+                          const uint32_t *list, const uint32_t *wcost, int32_t width, int32_t rows, int32_t k_boost, int32_t boost_chunk_spp,
+                          int64_t boost_cap, int32_t num, int32_t den, int32_t wg_slots, uint32_t *start, int64_t start_cap, uint32_t *bslot,
+                          int64_t slot_cap, int64_t *t, int64_t *promoted, uint64_t *cost_sum);
 
 /* Host evaluation of the lens stream (cgrt_rng.hpp, the same inline code the kernel runs): writes
  * uniform_sampling_circle(radius) (sampling.h:35-43) for n (pixel, sample) pairs as 3 doubles each.  Lets CPU-only
