@@ -43,6 +43,16 @@ class Grid(C.Structure):
                 ("max_depth", C.c_int32), ("flags", C.c_int32), ("seed", C.c_uint64)]
 
 
+# Grid.flags: one name per CGRT_GRID_* enumerator of include/cgrt.h (tests/test_capi_host.py compares them with the header)
+GRID_STATS, GRID_ACCUMULATE, GRID_SPLIT_SAMPLES, GRID_NO_REORDER, GRID_FORCE_REORDER, GRID_HITPOINTS = 1, 2, 4, 8, 16, 32
+GRID_NO_TILE_ORDER, GRID_DIFFUSE_TILES, GRID_NO_SPHERE_PAIRS, GRID_NO_SPHERE_MASKS = 64, 128, 256, 512
+GRID_SAMPLE_RELAY, GRID_NO_SAMPLE_RELAY, GRID_SAMPLE_RELAY_4 = 1024, 2048, 4096
+GRID_RELAY_MIRROR, GRID_RELAY_NO_MIRROR = 8192, 16384
+GRID_RELAY_CHUNKS_FIRST, GRID_RELAY_MIRROR_FIRST, GRID_RELAY_INTERLEAVED, GRID_RELAY_ORDER_MASK = 32768, 65536, 98304, 98304
+GRID_NO_LENS_STAGE, GRID_NO_SURE_TILES = 131072, 262144
+GRID_RELAY_COST_START, GRID_NO_RELAY_COST_START, GRID_RELAY_BOOST, GRID_NO_RELAY_BOOST = 524288, 1048576, 2097152, 4194304
+
+
 class Photons(C.Structure):
     _fields_ = [("light", C.c_double * 3), ("jitter", C.c_double), ("power", C.c_double), ("alpha", C.c_double),
                 ("nphotons", C.c_int64), ("hashsize", C.c_int32), ("batch", C.c_int32), ("seed", C.c_uint64),

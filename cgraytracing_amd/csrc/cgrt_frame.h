@@ -1,7 +1,8 @@
 // The host side of an eye-pass launch in plain C++ (no HIP): the kernel parameters, the workgroup / tile constants, the
 // environment switches and the frame plan -- sample chunks, tile counts, heavy-tile capacity, scheduling, the tile order of a
-// sphere scene (whether it runs, who renders its class-3 tiles, the sphere masks, the lens stage, the sample relay) and where each array lies
-// in the handle's launch scratch and in its order buffer.  cgrt_trace_grid (cgrt_hip.hip) launches what frame_plan decides;
+// sphere scene (whether it runs, who renders its class-3 tiles, the sphere masks, the lens stage), its sample relay (RelayPlan:
+// the one decision of its form, its two areas and everything derived from them) and where each array lies in the handle's
+// launch scratch and in its order buffer.  cgrt_trace_grid (cgrt_hip.hip) launches what frame_plan decides;
 // tests/native/frame_plan.cpp checks it on the CPU.
 #ifndef CGRT_FRAME_H
 #define CGRT_FRAME_H
@@ -142,10 +143,11 @@ struct TileOrderLayout {
     // start_words > 0 (the relay's cost start, cgrt_relay.h), behind everything else: the wave tiles' probe costs, the items'
     // weights (8 bytes each) and the start table, start_words each of the two
     Region wcost{}, weight{}, start{};
-    // boost_words > 0 (a start table with promoted tiles, cgrt_relay.h), behind those: head and bslot (kBoostHead + split_cap words),
-    // the entries' costs, the virtual items' weights (n_tiles * boost_k) and the table the launch reads instead of `start`
-    // (start_words + boost_words)
-    Region boost{}, ecost{}, bweight{}, bstart{};
+    // boost_words > 0 (a start table with promoted tiles, cgrt_relay.h), behind those: head and bslot (kBoostHead + split_cap words;
+    // `bslot` names the words behind the head), the entries' costs, the virtual items' weights (n_tiles * boost_k) and the table
+    // the launch reads instead of `start` (start_words + boost_words)
+    Region boost{}, bslot{}, ecost{}, bweight{}, bstart{};
+    uint32_t word(const Region &r) const { return (uint32_t)((r.at - plan.at) / sizeof(uint32_t)); }  // where a part begins, in words of plan[]
     size_t total = 0;  // bytes to allocate
 };
 inline TileOrderLayout tile_order_layout(size_t n_tiles, size_t n_wt, bool sure = false, size_t start_words = 0, size_t boost_words = 0,
@@ -176,6 +178,7 @@ inline TileOrderLayout tile_order_layout(size_t n_tiles, size_t n_wt, bool sure 
     if (start_words && boost_words) {
         end = align256(end);
         L.boost = take((kBoostHead + split_cap) * sizeof(uint32_t));
+        L.bslot = Region{L.boost.at + kBoostHead * sizeof(uint32_t), split_cap * sizeof(uint32_t)};
         end = align256(end);
         L.ecost = take(n_tiles * sizeof(uint32_t));
         end = align256(end);
@@ -434,6 +437,122 @@ struct TileOrderPlan {
     int lens_stage = kLensStageOff;
 };
 
+// Whether a launch of n_tiles tiles relays samples by default: at 32 samples or more (two chunks of 16), and with every workgroup
+// slot of the device -- four 256-thread workgroups a CU -- taken at least once, so that the extra workgroups find the chip full
+// of other work; CGRT_GRID_SAMPLE_RELAY lifts the second condition, CGRT_GRID_NO_SAMPLE_RELAY switches the relay off.
+inline bool relay_engaged(int32_t flags, int32_t spp, size_t n_tiles, int n_cu) {
+    if ((flags & CGRT_GRID_NO_SAMPLE_RELAY) || spp < 2 * kRelayMinChunkSpp) return false;
+    return (flags & CGRT_GRID_SAMPLE_RELAY) || n_tiles >= (size_t)4 * (size_t)n_cu;
+}
+
+// The form of an engaged relay: relay_block_ordered's extent and order, whether the workgroups start by cost, and whether a launch
+// that does promotes.  For each: what the launch's flags name holds (off before on); else the knob (CGRT_RELAY_MIRROR / _ORDER /
+// _START / _BOOST=off); else a launch that asked for the relay (CGRT_GRID_SAMPLE_RELAY) relays classes 0 and 1, chunk workgroups
+// first, from the list -- what that flag has always meant -- and one that names an order, by flag or knob, gets the list it named;
+// only the launch that relays by default and names no order takes the measured form (kRelayDefaultExtent / kRelayDefaultOrder,
+// by cost), and it promotes unless it names a start, by flag or knob.
+static constexpr int kRelayDefaultExtent = kRelayMirror, kRelayDefaultOrder = kRelayInterleaved;
+struct RelayRule { int extent, order, start; bool boost; };
+inline RelayRule relay_rule(int32_t f, const EyeKnobs &kn) {
+    const bool asked = (f & CGRT_GRID_SAMPLE_RELAY) != 0;  // the launch asked for the relay
+    const int32_t order_flag = f & CGRT_GRID_RELAY_ORDER_MASK;
+    const bool measured = !asked && !order_flag && kn.relay_order < 0;  // it names no order either
+    const bool names_start = (f & (CGRT_GRID_NO_RELAY_COST_START | CGRT_GRID_RELAY_COST_START)) || kn.relay_start >= 0;
+    RelayRule r;
+    r.extent = (f & CGRT_GRID_RELAY_MIRROR) ? kRelayMirror : (f & CGRT_GRID_RELAY_NO_MIRROR) ? kRelayGlass
+               : kn.relay_mirror >= 0 ? (kn.relay_mirror ? kRelayMirror : kRelayGlass) : asked ? kRelayGlass : kRelayDefaultExtent;
+    r.order = order_flag ? (order_flag == CGRT_GRID_RELAY_MIRROR_FIRST ? kRelayMirrorFirst : order_flag == CGRT_GRID_RELAY_INTERLEAVED ? kRelayInterleaved : kRelayChunksFirst)
+              : kn.relay_order >= 0 ? kn.relay_order : asked ? kRelayChunksFirst : kRelayDefaultOrder;
+    r.start = (f & CGRT_GRID_NO_RELAY_COST_START) ? kRelayStartList : (f & CGRT_GRID_RELAY_COST_START) ? kRelayStartCost
+              : kn.relay_start >= 0 ? kn.relay_start : measured ? kRelayStartCost : kRelayStartList;
+    r.boost = (f & CGRT_GRID_NO_RELAY_BOOST) ? false : (f & CGRT_GRID_RELAY_BOOST) ? true : !kn.relay_boost_off && !names_start && measured;
+    return r;
+}
+
+// The sample relay of a launch (cgrt_relay.h).  An area of the handle's relay buffer holds `cap` tiles, each rendered by k
+// workgroups of chunk_spp samples that park in `slots` slots a stream; `bytes` is relay_layout(cap, k, slots).total.
+struct RelayArea {
+    int k = 0, chunk_spp = 0, slots = 0;
+    size_t cap = 0, bytes = 0;
+};
+static constexpr int kRelayWgPerCu = 4;  // resident workgroups a compute unit of the START variants (256 threads, 4 waves a SIMD)
+struct RelayPlan {
+    // base.k > 1: the launch relays (the buffer lives on the handle; a launch that cannot have it goes without the relay).
+    // boost.k > base.k: it promotes -- its heaviest split tiles by boost.k workgroups, parked in an area of their own behind the base area
+    RelayArea base{1, 0, 0, 0, 0}, boost;
+    int spp = 0, extent = kRelayGlass, order = kRelayChunksFirst;  // the launch's samples; relay_block_ordered's extent and order
+    // kRelayStartCost: the workgroups of classes 0-2 start by probed cost, through a table of start_words words in the order
+    // buffer, probed with probe_spp samples; `order` stays the order of a launch that has to go without the table
+    int start = kRelayStartList, probe_spp = 0;
+    // promotion: the words the table may have more, which are also the workgroups the launch has more; the threshold is num / den
+    // of a workgroup slot's even share, over wg_slots slots
+    size_t start_words = 0, boost_words = 0;
+    uint32_t num = 0, den = 1;
+    int wg_slots = 0;
+    bool relays() const { return base.k > 1; }
+    bool boosts() const { return boost.k > base.k; }
+    // the handle's relay buffer: the base area, then (boosts()) the boost area
+    size_t boost_at() const { return align256(base.bytes); }
+    size_t bytes() const { return boosts() ? boost_at() + boost.bytes : base.bytes; }
+    // workgroups of a launch over n_tiles tiles; `boosted`: it has the promoted form's table
+    size_t grid(size_t n_tiles, bool boosted) const { return relay_grid(n_tiles, base.k, base.cap) + (boosted ? boost_words : 0); }
+    RelayBoost boost_rule() const {
+        return boosts() ? RelayBoost{(uint32_t)boost.k, (uint32_t)boost.cap, boost.chunk_spp, num, den, (uint32_t)wg_slots} : RelayBoost{};
+    }
+    RelayItems items(uint32_t n01, uint32_t n012, uint32_t n_tiles) const {
+        return RelayItems{(uint32_t)base.k, n01, n012, n_tiles, (uint32_t)base.cap, extent, base.chunk_spp, spp};
+    }
+    TileOrderLayout order_layout(size_t n_tiles, size_t n_wt, bool sure) const {
+        return tile_order_layout(n_tiles, n_wt, sure, start_words, boost_words, base.cap, boost.k);
+    }
+    // g's relay fields, for the buffer at `buf`
+    void place(GridParams &g, unsigned char *buf) const {
+        g.relay = buf;
+        g.relay_k = base.k;
+        g.relay_chunk_spp = base.chunk_spp;
+        g.relay_cap = (int32_t)base.cap;
+        g.relay_slots = base.slots;
+        g.relay_extent = extent;
+        g.relay_order = order;
+        if (!boosts()) return;
+        g.relay_boost_off = boost_at();
+        g.boost_k = boost.k;
+        g.boost_chunk_spp = boost.chunk_spp;
+        g.boost_cap = (int32_t)boost.cap;
+        g.boost_slots = boost.slots;
+    }
+};
+// The relay of a launch that may have one (frame_plan: the PAIR variant's one-launch tile order) over n_tiles tiles
+inline RelayPlan relay_plan(const cgrt_grid &gr, const EyeKnobs &kn, size_t n_tiles, int n_cu, size_t mem_total) {
+    RelayPlan r;
+    if (!relay_engaged(gr.flags, gr.spp, n_tiles, n_cu)) return r;
+    const auto area = [&gr](const RelayChunks &c, size_t tiles, size_t budget, long long bound) {
+        RelayArea a{c.k, c.chunk_spp, relay_slots(c.chunk_spp, gr.max_depth), 0, 0};
+        a.cap = relay_cap(tiles, a.k, a.slots, budget, bound);
+        a.bytes = relay_layout(a.cap, a.k, a.slots).total;
+        return a;
+    };
+    const RelayChunks rc = relay_chunks(gr.spp, (gr.flags & CGRT_GRID_SAMPLE_RELAY_4) ? kRelayMaxChunks : kn.relay_chunks);
+    const RelayArea base = rc.k > 1 ? area(rc, n_tiles, relay_budget(mem_total), kn.relay_tiles) : RelayArea{};
+    if (base.cap == 0) return r;  // (fewer than 32 samples, or no room for a tile)
+    const RelayRule f = relay_rule(gr.flags, kn);
+    r.base = base;
+    r.spp = gr.spp, r.extent = f.extent, r.order = f.order;
+    r.start = n_tiles < kRelayStartMaxTiles ? f.start : kRelayStartList;
+    if (r.start != kRelayStartCost) return r;
+    r.probe_spp = std::min(kn.relay_probe_spp, (int)gr.spp);
+    r.start_words = relay_start_words(n_tiles, base.k, base.cap);
+    const RelayChunks rb = relay_chunks(gr.spp, kRelayMaxChunks);
+    if (rb.k <= rc.k || !f.boost || kn.relay_boost_tiles == 0) return r;
+    const RelayArea boost = area(rb, base.cap, relay_boost_budget(mem_total, r.boost_at()), kn.relay_boost_tiles);
+    if (boost.cap == 0) return r;
+    r.boost = boost;
+    r.boost_words = relay_boost_extra(base.k, boost.k, boost.cap);
+    r.num = kn.relay_boost_num, r.den = kn.relay_boost_den;
+    r.wg_slots = n_cu * kRelayWgPerCu;
+    return r;
+}
+
 struct FramePlan {
     int chunks = 1, chunk_spp = 0;  // CGRT_GRID_SPLIT_SAMPLES: workgroups per tile, samples per workgroup
     bool xcd_tiles = false;         // XCD-aware super-tiles, else row-major (tile_of_block)
@@ -449,75 +568,8 @@ struct FramePlan {
     unsigned long long plan_div = 0;  // plan_kernel: heavy when cost x spp > total x spp / plan_div
     ScratchLayout scratch;
     TileOrderPlan order;
-    // The sample relay (cgrt_relay.h): relay_k > 1 when the launch relays -- workgroups per relayed tile, samples per workgroup,
-    // slots per parked stream, bytes of the relay area per tile, tiles the area is to hold and its bytes (the area lives on the
-    // handle beside the scratch; a launch whose area cannot be had goes without the relay, grid_dim workgroups; with it,
-    // relay_grid(grid_dim, relay_k, relay_cap))
-    int relay_k = 1, relay_chunk_spp = 0, relay_slots = 0;
-    size_t relay_tile_bytes = 0, relay_cap = 0, relay_bytes = 0;
-    int relay_extent = kRelayGlass, relay_order = kRelayChunksFirst;  // relay_block_ordered's; both 0 unless relay_k > 1
-    // kRelayStartCost: the workgroups of classes 0-2 start by probed cost (cgrt_relay.h), through a table of start_words words
-    // in the order buffer; relay_order stays the order of a launch that has to go without the table.  List unless relay_k > 1
-    int relay_start = kRelayStartList, relay_probe_spp = 0;
-    size_t relay_start_words = 0;
-    // Promotion (cgrt_relay.h): relay_boost -- a launch with a start table renders its heaviest split tiles by boost_k > relay_k
-    // workgroups of boost_chunk_spp samples each, parked in boost_slots slots a stream in an area of their own for boost_cap
-    // tiles (boost_bytes, behind the base area); the table may then have boost_words more words and the launch boost_grid more
-    // workgroups; the threshold is boost_num / boost_den of a workgroup slot's even share, over boost_wg_slots slots
-    bool relay_boost = false;
-    int boost_k = 0, boost_chunk_spp = 0, boost_slots = 0, boost_wg_slots = 0;
-    size_t boost_cap = 0, boost_bytes = 0, boost_words = 0, boost_grid = 0;
-    uint32_t boost_num = 0, boost_den = 1;
+    RelayPlan relay;  // the sample relay of the launch (relay.relays()), decided by relay_plan
 };
-
-// Whether a launch of n_tiles tiles relays samples by default: at 32 samples or more (two chunks of 16), and with every workgroup
-// slot of the device -- four 256-thread workgroups a CU -- taken at least once, so that the extra workgroups find the chip full
-// of other work; CGRT_GRID_SAMPLE_RELAY lifts the second condition, CGRT_GRID_NO_SAMPLE_RELAY switches the relay off.
-inline bool relay_engaged(int32_t flags, int32_t spp, size_t n_tiles, int n_cu) {
-    if ((flags & CGRT_GRID_NO_SAMPLE_RELAY) || spp < 2 * kRelayMinChunkSpp) return false;
-    return (flags & CGRT_GRID_SAMPLE_RELAY) || n_tiles >= (size_t)4 * (size_t)n_cu;
-}
-
-// The form of an engaged relay (relay_block_ordered's extent and order).  What the launch's flags name holds; where they name
-// none, the knob CGRT_RELAY_MIRROR / CGRT_RELAY_ORDER; where neither does, a launch that asked for the relay
-// (CGRT_GRID_SAMPLE_RELAY) relays classes 0 and 1, chunk workgroups first -- what that flag has always meant -- and only the
-// launch that relays by default takes the measured form (kRelayDefaultExtent / kRelayDefaultOrder).
-static constexpr int kRelayDefaultExtent = kRelayMirror, kRelayDefaultOrder = kRelayInterleaved;
-inline int relay_extent_of(int32_t flags, const EyeKnobs &kn) {
-    if (flags & CGRT_GRID_RELAY_MIRROR) return kRelayMirror;
-    if (flags & CGRT_GRID_RELAY_NO_MIRROR) return kRelayGlass;
-    if (kn.relay_mirror >= 0) return kn.relay_mirror ? kRelayMirror : kRelayGlass;
-    return (flags & CGRT_GRID_SAMPLE_RELAY) ? kRelayGlass : kRelayDefaultExtent;
-}
-inline int relay_order_of(int32_t flags, const EyeKnobs &kn) {
-    const int32_t f = flags & CGRT_GRID_RELAY_ORDER_MASK;
-    if (f) return f == CGRT_GRID_RELAY_MIRROR_FIRST ? kRelayMirrorFirst : f == CGRT_GRID_RELAY_INTERLEAVED ? kRelayInterleaved : kRelayChunksFirst;
-    if (kn.relay_order >= 0) return kn.relay_order;
-    return (flags & CGRT_GRID_SAMPLE_RELAY) ? kRelayChunksFirst : kRelayDefaultOrder;
-}
-
-// Whether an engaged relay starts its workgroups by cost: what the launch's flags say; else the knob CGRT_RELAY_START; else the
-// launch that relays by default and names no order (the rule that gives kRelayDefaultOrder) does, a launch that names one
-// -- by flag or knob -- or asked for the relay gets the list it named.
-inline int relay_start_of(int32_t flags, const EyeKnobs &kn) {
-    if (flags & CGRT_GRID_NO_RELAY_COST_START) return kRelayStartList;
-    if (flags & CGRT_GRID_RELAY_COST_START) return kRelayStartCost;
-    if (kn.relay_start >= 0) return kn.relay_start;
-    const bool names_order = (flags & CGRT_GRID_RELAY_ORDER_MASK) || kn.relay_order >= 0;
-    return !names_order && !(flags & CGRT_GRID_SAMPLE_RELAY) ? kRelayStartCost : kRelayStartList;
-}
-
-// Whether a launch with a start table promotes: CGRT_GRID_NO_RELAY_BOOST, then CGRT_GRID_RELAY_BOOST, then the knob's `off`;
-// otherwise exactly the launch that starts by cost by default does (relay_start_of's last rule).
-static constexpr int kRelayWgPerCu = 4;  // resident workgroups a compute unit of the START variants (256 threads, 4 waves a SIMD)
-inline bool relay_boost_of(int32_t flags, const EyeKnobs &kn) {
-    if (flags & CGRT_GRID_NO_RELAY_BOOST) return false;
-    if (flags & CGRT_GRID_RELAY_BOOST) return true;
-    if (kn.relay_boost_off) return false;
-    if ((flags & (CGRT_GRID_NO_RELAY_COST_START | CGRT_GRID_RELAY_COST_START)) || kn.relay_start >= 0) return false;
-    const bool names_order = (flags & CGRT_GRID_RELAY_ORDER_MASK) || kn.relay_order >= 0;
-    return !names_order && !(flags & CGRT_GRID_SAMPLE_RELAY);
-}
 
 // The launch at capacity kmax (0 when it is not scheduled): a function of the inputs and kmax only
 inline FramePlan frame_plan(const FrameInputs &in, size_t kmax) {
@@ -569,45 +621,8 @@ inline FramePlan frame_plan(const FrameInputs &in, size_t kmax) {
     // otherwise the knob CGRT_LENS_STAGE holds, and the default where it names nothing.
     if (o.class3 == TileOrderPlan::InKernel && in.cam.lens_radius > 0 && !(gr.flags & CGRT_GRID_NO_LENS_STAGE))
         o.lens_stage = kn.lens_stage >= 0 ? kn.lens_stage : kLensStageDefault;
-    if (o.on && in.pair && o.class3 != TileOrderPlan::SecondLaunch && !split_asked &&
-        relay_engaged(gr.flags, gr.spp, (size_t)p.tile_blocks, in.n_cu)) {
-        const RelayChunks rc = relay_chunks(gr.spp, (gr.flags & CGRT_GRID_SAMPLE_RELAY_4) ? kRelayMaxChunks : kn.relay_chunks);
-        if (rc.k > 1) {
-            p.relay_slots = relay_slots(rc.chunk_spp, gr.max_depth);
-            p.relay_tile_bytes = relay_tile_bytes(rc.k, p.relay_slots);
-            p.relay_cap = relay_cap((size_t)p.tile_blocks, rc.k, p.relay_slots, relay_budget(in.mem_total), kn.relay_tiles);
-            if (p.relay_cap > 0) {
-                p.relay_k = rc.k;
-                p.relay_chunk_spp = rc.chunk_spp;
-                p.relay_bytes = relay_layout(p.relay_cap, rc.k, p.relay_slots).total;
-                p.relay_extent = relay_extent_of(gr.flags, kn);
-                p.relay_order = relay_order_of(gr.flags, kn);
-                p.relay_start = (size_t)p.tile_blocks < kRelayStartMaxTiles ? relay_start_of(gr.flags, kn) : kRelayStartList;
-                if (p.relay_start == kRelayStartCost) {
-                    p.relay_probe_spp = std::min(kn.relay_probe_spp, (int)gr.spp);
-                    p.relay_start_words = relay_start_words((size_t)p.tile_blocks, rc.k, p.relay_cap);
-                    const RelayChunks rb = relay_chunks(gr.spp, kRelayMaxChunks);
-                    if (rb.k > rc.k && relay_boost_of(gr.flags, kn) && kn.relay_boost_tiles != 0) {
-                        const int bslots = relay_slots(rb.chunk_spp, gr.max_depth);
-                        const size_t base = align256(p.relay_bytes);
-                        const size_t bcap = relay_cap(p.relay_cap, rb.k, bslots, relay_boost_budget(in.mem_total, base), kn.relay_boost_tiles);
-                        if (bcap > 0) {
-                            p.relay_boost = true;
-                            p.boost_k = rb.k;
-                            p.boost_chunk_spp = rb.chunk_spp;
-                            p.boost_slots = bslots;
-                            p.boost_wg_slots = in.n_cu * kRelayWgPerCu;
-                            p.boost_cap = bcap;
-                            p.boost_bytes = relay_layout(bcap, rb.k, bslots).total;
-                            p.boost_words = p.boost_grid = relay_boost_extra(rc.k, rb.k, bcap);
-                            p.boost_num = kn.relay_boost_num;
-                            p.boost_den = kn.relay_boost_den;
-                        }
-                    }
-                }
-            }
-        }
-    }
+    if (o.on && in.pair && o.class3 != TileOrderPlan::SecondLaunch && !split_asked)
+        p.relay = relay_plan(gr, kn, (size_t)p.tile_blocks, in.n_cu, in.mem_total);
     p.wtiles_x = (gr.width + kWaveTileW - 1) / kWaveTileW;
     p.wtiles_y = (gr.rows + kWaveTileH - 1) / kWaveTileH;
     p.n_wt = (size_t)p.wtiles_x * p.wtiles_y;

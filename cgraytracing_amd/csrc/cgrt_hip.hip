@@ -936,42 +936,23 @@ static int probe_and_plan(const cgrt_scene *s, const EyeLaunch &L, const EyeKnob
     return CGRT_OK;
 }
 
-// The relay's start order by cost (cgrt_relay.h; behind order_tiles and relay_prepare on their stream, when the plan has
-// relay_start == kRelayStartCost and the launch relays).  The probe is the launch's own kernel over entries [0, plan[3]) of the
-// list -- the START twin of it, which the frame then runs too (kOrderFull: the workgroups beyond leave at once) -- with the first relay_probe_spp samples of every pixel from sample 0,
-// the launch's seed and depth, no relay; it stores nothing but each wave's iteration count.  Two small kernels turn the costs
-// into the table, and g maps its workgroups of classes 0-2 through it.  Costs and table stay in the order buffer and are reused
-// with the order, as long as what else they depend on (TileOrderState::CostKey, TableKey) is the same; where only the table's
-// key differs the probe is not run again.
+// The probe of the relay's start order by cost, between the two host steps of cgrt_tile_order.hpp (cost_start_begin,
+// cost_start_rank): the START twin of the launch's own kernel, which the frame then runs too, over entries [0, plan[3]) of the
+// list (kOrderFull: the workgroups beyond leave at once) with the first probe_spp samples of every pixel from sample 0, the
+// launch's seed and depth, no relay.
 static EyeLaunch start_twin(EyeLaunch L) {
     L.k.start = true;
     return L;
 }
 static int relay_cost_start(const cgrt_scene *s, const EyeLaunch &L, const FramePlan &p, GridParams &g, hipStream_t st) {
-    TileOrderState &o = s->order;
-    const TileOrderLayout &at = o.at;
-    unsigned char *base = reinterpret_cast<unsigned char *>(o.buf.p);
-    uint32_t *wcost = at.wcost.in<uint32_t>(base), *start = at.start.in<uint32_t>(base);
-    unsigned long long *weight = at.weight.in<unsigned long long>(base);
-    if (!wcost || !start || !weight) return CGRT_OK;  // (the layout has no table: the launch goes by its list)
-    // promoted tiles (cgrt_relay.h): the table is the promoted form's, in its own parts of the buffer
-    uint32_t *head = at.boost.in<uint32_t>(base), *ecost = at.ecost.in<uint32_t>(base), *bstart = at.bstart.in<uint32_t>(base);
-    unsigned long long *bweight = at.bweight.in<unsigned long long>(base);
-    const bool boost = p.relay_boost && g.boost_k > g.relay_k && head && ecost && bstart && bweight;
-    const RelayBoost rb = boost ? RelayBoost{(uint32_t)p.boost_k, (uint32_t)p.boost_cap, p.boost_chunk_spp, p.boost_num, p.boost_den, (uint32_t)p.boost_wg_slots}
-                                : RelayBoost{};
-    const TileOrderState::CostKey ck{g.seed, g.max_depth, p.relay_probe_spp};
-    const TileOrderState::TableKey tk{g.spp, g.relay_k, g.relay_chunk_spp, g.relay_cap, g.relay_extent, (int32_t)rb.k, (int32_t)rb.cap,
-                                      (int32_t)rb.num, (int32_t)rb.den, (int32_t)rb.slots};
-    const bool have_cost = o.reused && o.cost_valid && std::memcmp(&ck, &o.cost_key, sizeof(ck)) == 0;
-    const bool have_table = have_cost && o.table_valid && std::memcmp(&tk, &o.table_key, sizeof(tk)) == 0;
-    o.cost_valid = o.table_valid = false;
-    if (!have_cost) {
-        HIP_TRY(hipMemsetAsync(wcost, 0, at.wcost.bytes, st));
+    CostStart c;
+    if (int rc = cost_start_begin(s->order, p.relay, g, st, c)) return rc;
+    if (!c.wcost) return CGRT_OK;
+    if (!c.have_cost) {
         GridParams gp = g;
         gp.probe = 2;
-        gp.cost = wcost;
-        gp.spp = gp.chunk_spp = p.relay_probe_spp;
+        gp.cost = c.wcost;
+        gp.spp = gp.chunk_spp = p.relay.probe_spp;
         gp.sample_offset = 0;
         gp.accumulate = 0;
         gp.tile_order = kOrderFull;
@@ -980,42 +961,7 @@ static int relay_cost_start(const cgrt_scene *s, const EyeLaunch &L, const Frame
         gp.relay_start_at = gp.relay_boost_at = 0;
         if (int rc = launch_eye(start_twin(L), false, s->device, gp, dim3((unsigned)p.grid_dim), st, nullptr, nullptr, nullptr)) return rc;
     }
-    if (!have_table) {
-        const int tiles_x = (g.W + kTileW - 1) / kTileW;
-        const RelayStartArgs a{RelayItems{(uint32_t)g.relay_k, 0, 0, 0, (uint32_t)g.relay_cap, g.relay_extent, g.relay_chunk_spp, g.spp},
-                               (uint32_t)tiles_x, (uint32_t)p.wtiles_x, (uint32_t)p.wtiles_y};
-        const dim3 grid((unsigned)((p.relay_start_words + kRelayThreads - 1) / kRelayThreads));
-        if (boost) {
-            const RelayBoostArgs ba{a, rb};
-            const auto blocks = [](size_t threads) { return dim3((unsigned)((threads + kRelayThreads - 1) / kRelayThreads)); };
-            const size_t n_tiles = (size_t)p.tile_blocks;
-            HIP_TRY(hipMemsetAsync(head, 0, kBoostHead * sizeof(uint32_t), st));
-            hipLaunchKernelGGL(relay_boost_cost_kernel, blocks(n_tiles), dim3(kRelayThreads), 0, st, ba, g.plan, g.border, wcost, ecost, head);
-            hipLaunchKernelGGL(relay_boost_promote_kernel, blocks(p.relay_cap), dim3(kRelayThreads), 0, st, ba, g.plan, ecost, head, head + kBoostHead);
-            hipLaunchKernelGGL(relay_boost_weight_kernel, blocks(n_tiles * rb.k), dim3(kRelayThreads), 0, st, ba, g.plan, ecost, head + kBoostHead, head, bweight);
-            hipLaunchKernelGGL(relay_boost_start_kernel, blocks(n_tiles * rb.k), dim3(kRelayThreads), 0, st, ba, g.plan, bweight, bstart);
-        } else {
-            hipLaunchKernelGGL(relay_weight_kernel, grid, dim3(kRelayThreads), 0, st, a, g.plan, g.border, wcost, weight);
-            hipLaunchKernelGGL(relay_start_kernel, grid, dim3(kRelayThreads), 0, st, a, g.plan, weight, start);
-        }
-    }
-    // the order's event now stands behind the table too (a reusing launch on another stream waits for it)
-    if (o.valid && (have_table || (hipPeekAtLastError() == hipSuccess && hipEventRecord(o.ev, st) == hipSuccess))) {
-        if (!have_table) o.stream = st;
-        o.cost_key = ck;
-        o.table_key = tk;
-        o.cost_valid = o.table_valid = true;
-    } else if (o.valid) {
-        (void)hipGetLastError();
-        o.valid = false;
-    }
-    g.relay_start_at = (uint32_t)(((boost ? at.bstart.at : at.start.at) - at.plan.at) / sizeof(uint32_t));
-    g.relay_boost_at = boost ? (uint32_t)((at.boost.at - at.plan.at) / sizeof(uint32_t)) : 0u;
-    o.boost = rb;
-    o.start_words = p.relay_start_words;
-    o.start_wtiles = p.n_wt;
-    o.start_reused = have_table;
-    return CGRT_OK;
+    return cost_start_rank(s->order, p, c, g, st);
 }
 
 // The heavy units' primary rays against the mesh, as a walk-only kernel with lane refill (cgrt_primwalk.hpp): a chip's worth
@@ -1102,11 +1048,11 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     if (p.order.on) {  // the tiles that see a mirror or glass sphere first; where the plan says so, their samples relayed
         const Capturing capturing = stream_capturing(st);
         if ((rc = order_tiles(s->order, s->dev, p, g, kn.no_order_reuse, capturing, st))) return rc;
-        if (p.relay_k > 1 && relay_prepare(s->relay, p, g, capturing, st)) {
-            guard.relayed = true;
-            n_blocks = relay_grid(p.grid_dim, p.relay_k, p.relay_cap);
-            if (p.relay_start == kRelayStartCost && (rc = relay_cost_start(s, L, p, g, st))) return rc;
-            if (g.relay_boost_at) n_blocks += p.boost_grid;  // (the promoted tiles' extra chunks, as many as the boost area holds)
+        if (p.relay.relays() && relay_prepare(s->relay, p.relay, g, capturing, st)) {
+            guard.relayed = &p.relay;
+            if (p.relay.start == kRelayStartCost && (rc = relay_cost_start(s, L, p, g, st))) return rc;
+            // (with the promoted form's table: the promoted tiles' extra chunks too, as many as the boost area holds)
+            n_blocks = p.relay.grid(p.grid_dim, g.relay_boost_at != 0);
         }
     }
     DevBuf timeline;
@@ -1951,22 +1897,32 @@ int cgrt_surface_colors(const cgrt_scene *s, int obj, const double *points3, int
     return CGRT_OK;
 }
 
+// The arguments the two host tables share, checked: the items and the grid's tile arithmetic
+static int relay_host_args(bool others_ok, int32_t k, int32_t chunk_spp, int32_t spp, int64_t cap, int32_t extent, int64_t n01, int64_t n012, int64_t n_tiles,
+                           const uint32_t *list, const uint32_t *wcost, int32_t width, int32_t rows, RelayStartArgs &a) {
+    if (!others_ok || !list || !wcost || k < 2 || k > kRelayMaxChunks || chunk_spp <= 0 || spp <= 0 || cap < 0 || width <= 0 || rows <= 0 ||
+        n01 < 0 || n01 > n012 || n012 > n_tiles || (size_t)n_tiles >= kRelayStartMaxTiles || (extent != kRelayGlass && extent != kRelayMirror))
+        return fail(CGRT_ERR_INVALID, "bad argument");
+    const uint32_t tiles_y = (uint32_t)((rows + kTileH - 1) / kTileH);
+    a.tiles_x = (uint32_t)((width + kTileW - 1) / kTileW);
+    a.wtiles_x = (uint32_t)((width + kWaveTileW - 1) / kWaveTileW);
+    a.wtiles_y = (uint32_t)((rows + kWaveTileH - 1) / kWaveTileH);
+    if ((int64_t)a.tiles_x * tiles_y != n_tiles) return fail(CGRT_ERR_INVALID, "n_tiles is not the grid's tile count");
+    for (int64_t e = 0; e < n012; e++)
+        if (list[e] >= (uint32_t)n_tiles) return fail(CGRT_ERR_INVALID, "list names a tile beyond the grid");
+    a.r = RelayItems{(uint32_t)k, (uint32_t)n01, (uint32_t)n012, (uint32_t)n_tiles, (uint32_t)std::min<int64_t>(cap, n_tiles), extent, chunk_spp, spp};
+    return CGRT_OK;
+}
+
 int cgrt_relay_start_host(int32_t k, int32_t chunk_spp, int32_t spp, int64_t cap, int32_t extent, int64_t n01, int64_t n012, int64_t n_tiles,
                           const uint32_t *list, const uint32_t *wcost, int32_t width, int32_t rows, uint32_t *start, int64_t start_cap,
                           int64_t *t) {
-    if (!t || !list || !wcost || k < 2 || k > kRelayMaxChunks || chunk_spp <= 0 || spp <= 0 || cap < 0 || width <= 0 || rows <= 0 || n01 < 0 ||
-        n01 > n012 || n012 > n_tiles || (size_t)n_tiles >= kRelayStartMaxTiles || (extent != kRelayGlass && extent != kRelayMirror))
-        return fail(CGRT_ERR_INVALID, "bad argument");
-    const uint32_t tiles_x = (uint32_t)((width + kTileW - 1) / kTileW), tiles_y = (uint32_t)((rows + kTileH - 1) / kTileH);
-    const uint32_t wtiles_x = (uint32_t)((width + kWaveTileW - 1) / kWaveTileW), wtiles_y = (uint32_t)((rows + kWaveTileH - 1) / kWaveTileH);
-    if ((int64_t)tiles_x * tiles_y != n_tiles) return fail(CGRT_ERR_INVALID, "n_tiles is not the grid's tile count");
-    for (int64_t e = 0; e < n012; e++)
-        if (list[e] >= (uint32_t)n_tiles) return fail(CGRT_ERR_INVALID, "list names a tile beyond the grid");
-    const RelayItems r{(uint32_t)k, (uint32_t)n01, (uint32_t)n012, (uint32_t)n_tiles, (uint32_t)std::min<int64_t>(cap, n_tiles), extent, chunk_spp, spp};
-    *t = (int64_t)relay_items_total(r);
+    RelayStartArgs a;
+    if (int rc = relay_host_args(t != nullptr, k, chunk_spp, spp, cap, extent, n01, n012, n_tiles, list, wcost, width, rows, a)) return rc;
+    *t = (int64_t)relay_items_total(a.r);
     if (!start || start_cap < *t || *t == 0) return CGRT_OK;
     std::vector<uint64_t> weight((size_t)*t);
-    relay_start_table(r, list, wcost, tiles_x, wtiles_x, wtiles_y, weight.data(), start);
+    relay_start_table(a.r, list, wcost, a.tiles_x, a.wtiles_x, a.wtiles_y, weight.data(), start);
     return CGRT_OK;
 }
 
@@ -1974,23 +1930,17 @@ int cgrt_relay_boost_host(int32_t k, int32_t chunk_spp, int32_t spp, int64_t cap
                           const uint32_t *list, const uint32_t *wcost, int32_t width, int32_t rows, int32_t k_boost, int32_t boost_chunk_spp,
                           int64_t boost_cap, int32_t num, int32_t den, int32_t wg_slots, uint32_t *start, int64_t start_cap, uint32_t *bslot,
                           int64_t slot_cap, int64_t *t, int64_t *promoted, uint64_t *cost_sum) {
-    if (!t || !promoted || !cost_sum || !list || !wcost || k < 2 || k > kRelayMaxChunks || chunk_spp <= 0 || spp <= 0 || cap < 0 || width <= 0 ||
-        rows <= 0 || n01 < 0 || n01 > n012 || n012 > n_tiles || (size_t)n_tiles >= kRelayStartMaxTiles ||
-        (extent != kRelayGlass && extent != kRelayMirror) || k_boost < k || k_boost > kRelayMaxChunks || boost_chunk_spp <= 0 || boost_cap < 0 ||
-        num < 0 || (uint32_t)num > kRelayBoostMaxTerm || den < 1 || (uint32_t)den > kRelayBoostMaxTerm || wg_slots < 1)
-        return fail(CGRT_ERR_INVALID, "bad argument");
-    const uint32_t tiles_x = (uint32_t)((width + kTileW - 1) / kTileW), tiles_y = (uint32_t)((rows + kTileH - 1) / kTileH);
-    const uint32_t wtiles_x = (uint32_t)((width + kWaveTileW - 1) / kWaveTileW), wtiles_y = (uint32_t)((rows + kWaveTileH - 1) / kWaveTileH);
-    if ((int64_t)tiles_x * tiles_y != n_tiles) return fail(CGRT_ERR_INVALID, "n_tiles is not the grid's tile count");
-    for (int64_t e = 0; e < n012; e++)
-        if (list[e] >= (uint32_t)n_tiles) return fail(CGRT_ERR_INVALID, "list names a tile beyond the grid");
-    const RelayItems r{(uint32_t)k, (uint32_t)n01, (uint32_t)n012, (uint32_t)n_tiles, (uint32_t)std::min<int64_t>(cap, n_tiles), extent, chunk_spp, spp};
+    const bool boost_ok = t && promoted && cost_sum && k_boost >= k && k_boost <= kRelayMaxChunks && boost_chunk_spp > 0 && boost_cap >= 0 && num >= 0 &&
+                          (uint32_t)num <= kRelayBoostMaxTerm && den >= 1 && (uint32_t)den <= kRelayBoostMaxTerm && wg_slots >= 1;
+    RelayStartArgs a;
+    if (int rc = relay_host_args(boost_ok, k, chunk_spp, spp, cap, extent, n01, n012, n_tiles, list, wcost, width, rows, a)) return rc;
+    const RelayItems &r = a.r;
     const RelayBoost b{(uint32_t)k_boost, (uint32_t)std::min<int64_t>(boost_cap, n_tiles), boost_chunk_spp, (uint32_t)num, (uint32_t)den, (uint32_t)wg_slots};
     const size_t n_split = relay_split_entries(r.n01, r.n012, r.cap, r.extent);
     const size_t most = relay_items_total(r) + relay_boost_extra(k, k_boost, std::min<size_t>(b.cap, n_split));
     std::vector<uint64_t> weight(most + 1);
     std::vector<uint32_t> table(most + 1), slots(n_split + 1);
-    const RelayBoosted out = relay_boost_table(r, b, list, wcost, tiles_x, wtiles_x, wtiles_y, slots.data(), weight.data(), table.data());
+    const RelayBoosted out = relay_boost_table(r, b, list, wcost, a.tiles_x, a.wtiles_x, a.wtiles_y, slots.data(), weight.data(), table.data());
     *t = (int64_t)out.items;
     *promoted = (int64_t)out.promoted;
     *cost_sum = out.S;

@@ -116,7 +116,7 @@ CGRT_HD RelayBlock relay_block_ordered(uint32_t b, uint32_t k, uint32_t n01, uin
 // waves': a workgroup lasts as long as its longest wave) times the samples it runs; the table sends workgroup b to the item of
 // rank b in descending weight, ties in item order.  A total order: every rank is a count, no atomics.  Class 3 and the
 // workgroups beyond the list follow as in every other form.
-static constexpr int kRelayStartList = 0, kRelayStartCost = 1;  // FramePlan::relay_start
+static constexpr int kRelayStartList = 0, kRelayStartCost = 1;  // RelayPlan::start
 static constexpr int kRelayProbeSpp = 2;                        // samples of the cost probe (measured: DESIGN.md section 6)
 struct RelayItems {
     uint32_t k, n01, n012, n_tiles, cap;

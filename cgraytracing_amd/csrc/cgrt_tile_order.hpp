@@ -1,7 +1,8 @@
 // The host side of a sphere scene's tile-order launch: what the handle keeps for it between launches (the order buffer and the
-// sample relay's area, each with the event and stream that order their users), the two steps that prepare a launch
-// (order_tiles, relay_prepare), the guard that closes a cgrt_trace_grid over both, and what the cgrt_scene_last_* read-backs
-// report.  What a launch does is frame_plan's decision (TileOrderPlan, cgrt_frame.h).  Part of libcgrt.so (cgrt_hip.hip).
+// sample relay's area, each with the event and stream that order their users), the steps that prepare a launch (order_tiles,
+// relay_prepare, and the cost start's two: cost_start_begin and cost_start_rank, with the probe between them launched by
+// cgrt_hip.hip), the guard that closes a cgrt_trace_grid over both, and what the cgrt_scene_last_* read-backs report.  What a
+// launch does is frame_plan's decision (TileOrderPlan, RelayPlan; cgrt_frame.h).  Part of libcgrt.so (cgrt_hip.hip).
 #ifndef CGRT_TILE_ORDER_HPP
 #define CGRT_TILE_ORDER_HPP
 
@@ -44,17 +45,22 @@ struct TileOrderState {
     TileOrderLayout at;
     TileOrderPlan::Class3 class3 = TileOrderPlan::None;
     int lens_stage = kLensStageOff;  // how that launch's in-kernel terminal-diffuse body drew its lens points
-    // The relay's cost start (cgrt_relay.h; relay_cost_start, cgrt_hip.hip): the probe's costs and the start table lie behind the
+    // The relay's cost start (cgrt_relay.h; cost_start_begin, cost_start_rank): the probe's costs and the start table lie behind the
     // rest of the buffer and are kept with the order -- never beyond it: a launch that did not reuse the order has neither.  The
     // costs depend, beyond Key, on CostKey; the table on the costs and on TableKey.  start_words: the table's part in the last
     // launch (0: it had none), start_wtiles its wave tiles, start_reused: it ran neither probe nor ranking.
     struct CostKey {
         uint64_t seed;
         int32_t max_depth, probe_spp;
+        static CostKey of(const RelayPlan &r, const GridParams &g) { return CostKey{g.seed, g.max_depth, r.probe_spp}; }
     };
     // (boost_k == 0: a table without promoted tiles, in `start`; else the promoted form's, in `bstart`, with what it depends on)
     struct TableKey {
         int32_t spp, k, chunk_spp, cap, extent, boost_k, boost_cap, boost_num, boost_den, boost_wg_slots;
+        static TableKey of(const RelayPlan &r) {
+            const RelayBoost b = r.boost_rule();
+            return TableKey{r.spp, r.base.k, r.base.chunk_spp, (int32_t)r.base.cap, r.extent, (int32_t)b.k, (int32_t)b.cap, (int32_t)b.num, (int32_t)b.den, (int32_t)b.slots};
+        }
     };
     static_assert(sizeof(CostKey) == 16 && sizeof(TableKey) == 40, "compared as bytes: no padding");
     CostKey cost_key{};
@@ -65,8 +71,7 @@ struct TileOrderState {
     RelayBoost boost{};
 
     void begin_launch() {
-        tiles = mask_wtiles = sure_wtiles = 0;
-        start_words = start_wtiles = 0;
+        tiles = mask_wtiles = sure_wtiles = start_words = start_wtiles = 0;
         boost = RelayBoost{};
         reused = start_reused = false;
         class3 = TileOrderPlan::None;
@@ -81,13 +86,17 @@ struct TileOrderState {
         HIP_TRY(hipMemcpy(dst, reinterpret_cast<const unsigned char *>(buf.p) + r.at, count * sizeof(T), hipMemcpyDeviceToHost));
         return CGRT_OK;
     }
+    int read_plan(uint32_t *plan) const {  // plan[0 .. kOrderClasses] of the last launch, once the device is through with it
+        HIP_TRY(hipDeviceSynchronize());
+        return read(at.plan, plan, kOrderClasses + 1);
+    }
 };
 
 // The sample relay's area (cgrt_relay.h; launch scratch like `scratch`, allocated by the first launch that relays, sized by the
 // largest): refused -- the smallest size the device has refused (such a launch goes unrelayed); zeroed -- the arrival words
 // known to be 0 (the kernel leaves them so; a launch that failed on the way does not vouch for it: dirty); ev is recorded
-// behind a relaying launch on `stream`, and a relaying launch on another stream waits for it -- the area is one.  last: what the
-// last cgrt_trace_grid relayed with (k == 0: it did not).
+// behind a relaying launch on `stream`, and a relaying launch on another stream waits for it -- the area is one.  last: the plan
+// the last cgrt_trace_grid relayed with (one that does not relay: it did not); its boost part only where that launch promoted.
 struct RelayState {
     GrowBuf buf;
     size_t refused = 0, zeroed = 0;
@@ -96,16 +105,9 @@ struct RelayState {
     hipEvent_t ev = nullptr;
     hipStream_t stream = nullptr;
     bool recorded = false;
-    struct Last {
-        int k = 0;
-        size_t cap = 0;
-        int slots = 0, extent = 0, order = 0;
-        // promoted tiles: the boost area at boost_off, laid out for (boost_cap, boost_k, boost_slots); boost_k == 0: none
-        int boost_k = 0, boost_slots = 0;
-        size_t boost_cap = 0, boost_off = 0;
-    } last;
+    RelayPlan last;
 
-    void begin_launch() { last = Last{}; }
+    void begin_launch() { last = RelayPlan{}; }
     void release() {
         buf.release();
         if (ev) (void)hipEventDestroy(ev);
@@ -133,7 +135,7 @@ static int order_tiles(TileOrderState &o, const DeviceScene &dev, const FramePla
     const int tiles_x = (g.W + kTileW - 1) / kTileW, tiles_y = (g.rows + kTileH - 1) / kTileH;
     const size_t n = (size_t)tiles_x * tiles_y;
     const bool masks = p.order.masks, sure = masks && p.order.sure;
-    const TileOrderLayout at = tile_order_layout(n, p.n_wt, sure, p.relay_start_words, p.relay_boost ? p.boost_words : 0, p.relay_cap, p.boost_k);
+    const TileOrderLayout at = p.relay.order_layout(n, p.n_wt, sure);
     const bool grown = at.total > o.buf.cap;
     if (grown) o.valid = false;
     if (o.buf.need(at.total) != hipSuccess) {
@@ -188,68 +190,110 @@ static int order_tiles(TileOrderState &o, const DeviceScene &dev, const FramePla
     return CGRT_OK;
 }
 
-// The sample relay of a tile-order launch of the PAIR variants (cgrt_relay.h; the plan has relay_k > 1): the handle's relay area
-// and g's relay fields.  Returns false -- the launch goes unrelayed, which is no error -- when the stream is being captured (the
-// area, its event and the handle's record of both belong to launches that run now) or its state cannot be asked, or the area
-// cannot be had.  The arrival words are 0 whenever no launch is in flight: zeroed here when the area is new or grown, when more
-// of them are needed than were zeroed, or after a launch that did not go through; reset by the kernel otherwise.
-static bool relay_prepare(RelayState &r, const FramePlan &p, GridParams &g, Capturing capturing, hipStream_t st) {
+// The sample relay of a tile-order launch of the PAIR variants (cgrt_relay.h; p.relays()): the handle's relay area and g's relay
+// fields.  Returns false -- the launch goes unrelayed, which is no error -- when the stream is being captured (the area, its
+// event and the handle's record of both belong to launches that run now) or its state cannot be asked, or the area cannot be
+// had.  The arrival words are 0 whenever no launch is in flight: zeroed here when the area is new or grown, when more of them
+// are needed than were zeroed, or after a launch that did not go through; reset by the kernel otherwise.
+static bool relay_prepare(RelayState &r, const RelayPlan &p, GridParams &g, Capturing capturing, hipStream_t st) {
     if (capturing != Capturing::None) return false;
-    // (with promoted tiles the boost area follows the base area in the one buffer)
-    const size_t boost_at = align256(p.relay_bytes), bytes = p.relay_boost ? boost_at + p.boost_bytes : p.relay_bytes;
+    const auto ok = [](hipError_t e) { return e == hipSuccess || ((void)hipGetLastError(), false); };
+    const size_t bytes = p.bytes(), boost_at = p.boost_at();
     if (r.refused && bytes >= r.refused) return false;
     if (bytes > r.buf.cap) {
-        // the launches that use the old area are through before it is freed
-        if (r.recorded && hipEventSynchronize(r.ev) != hipSuccess) (void)hipGetLastError();
+        if (r.recorded) (void)ok(hipEventSynchronize(r.ev));  // the launches that use the old area are through before it is freed
         r.zeroed = r.boost_zeroed = 0;
-        if (r.buf.need(bytes) != hipSuccess) {
-            (void)hipGetLastError();
+        if (!ok(r.buf.need(bytes))) {
             r.refused = bytes;
             return false;
         }
     }
-    if (!r.ev && hipEventCreateWithFlags(&r.ev, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
+    if (!r.ev && !ok(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming))) {
         r.ev = nullptr;
         return false;
     }
-    if (r.recorded && st != r.stream && hipStreamWaitEvent(st, r.ev, 0) != hipSuccess) {
-        (void)hipGetLastError();
+    if (r.recorded && st != r.stream && !ok(hipStreamWaitEvent(st, r.ev, 0))) return false;
+    unsigned char *buf = reinterpret_cast<unsigned char *>(r.buf.p);
+    if ((r.dirty || p.base.cap > r.zeroed) && !ok(hipMemsetAsync(buf, 0, p.base.cap * sizeof(uint32_t), st))) return false;
+    r.zeroed = p.base.cap;  // (the words beyond this launch's lie in its arrays)
+    if (p.boosts() && (r.dirty || boost_at != r.boost_zeroed_at || p.boost.cap > r.boost_zeroed) &&
+        !ok(hipMemsetAsync(buf + boost_at, 0, p.boost.cap * sizeof(uint32_t), st)))
         return false;
-    }
-    if (r.dirty || p.relay_cap > r.zeroed) {
-        if (hipMemsetAsync(r.buf.p, 0, p.relay_cap * sizeof(uint32_t), st) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-    }
-    r.zeroed = p.relay_cap;  // (the words beyond this launch's lie in its arrays)
-    if (p.relay_boost) {
-        if (r.dirty || boost_at != r.boost_zeroed_at || p.boost_cap > r.boost_zeroed) {
-            if (hipMemsetAsync(reinterpret_cast<unsigned char *>(r.buf.p) + boost_at, 0, p.boost_cap * sizeof(uint32_t), st) != hipSuccess) {
-                (void)hipGetLastError();
-                return false;
-            }
-        }
-        r.boost_zeroed = p.boost_cap;
-        r.boost_zeroed_at = boost_at;
-        g.relay_boost_off = boost_at;
-        g.boost_k = p.boost_k;
-        g.boost_chunk_spp = p.boost_chunk_spp;
-        g.boost_cap = (int32_t)p.boost_cap;
-        g.boost_slots = p.boost_slots;
-    } else {
-        r.boost_zeroed = 0;  // (this launch's arrays may lie over them)
-    }
-    r.dirty = true;          // until the launch is through (TileOrderGuard::commit)
-    g.relay = reinterpret_cast<unsigned char *>(r.buf.p);
-    g.relay_k = p.relay_k;
-    g.relay_chunk_spp = p.relay_chunk_spp;
-    g.relay_cap = (int32_t)p.relay_cap;
-    g.relay_slots = p.relay_slots;
-    g.relay_extent = p.relay_extent;
-    g.relay_order = p.relay_order;
+    r.boost_zeroed = p.boosts() ? p.boost.cap : 0;  // (without a boost area this launch's arrays may lie over the words)
+    r.boost_zeroed_at = p.boosts() ? boost_at : r.boost_zeroed_at;
+    r.dirty = true;  // until the launch is through (TileOrderGuard::commit)
+    p.place(g, buf);
     return true;
+}
+
+// The relay's start order by cost (cgrt_relay.h; behind order_tiles and relay_prepare on their stream, when the plan has
+// start == kRelayStartCost and the launch relays), in two steps with the probe between them.  The probe is the launch's own
+// kernel over entries [0, plan[3]) of the list with the first probe_spp samples of every pixel; it stores nothing but each wave's
+// iteration count in wcost (relay_cost_start, cgrt_hip.hip).  Ranking kernels turn the costs into the table, and g maps its
+// workgroups of classes 0-2 through it.  Costs and table stay in the order buffer and are reused with the order, as long as what
+// else they depend on (CostKey, TableKey) is the same; where only the table's key differs the probe is not run again.
+struct CostStart {
+    uint32_t *wcost = nullptr;  // where the probe leaves its costs; nullptr: the layout has no table, the launch goes by its list
+    bool have_cost = false, have_table = false;  // what the buffer still holds
+    TileOrderState::CostKey cost_key{};  // this launch's
+    TileOrderState::TableKey table_key{};
+};
+// what is still valid; costs that are not are zeroed for the probe
+static int cost_start_begin(TileOrderState &o, const RelayPlan &r, const GridParams &g, hipStream_t st, CostStart &c) {
+    c.wcost = o.at.wcost.in<uint32_t>(reinterpret_cast<unsigned char *>(o.buf.p));
+    if (!c.wcost) return CGRT_OK;
+    c.cost_key = TileOrderState::CostKey::of(r, g);
+    c.table_key = TileOrderState::TableKey::of(r);
+    c.have_cost = o.reused && o.cost_valid && std::memcmp(&c.cost_key, &o.cost_key, sizeof(c.cost_key)) == 0;
+    c.have_table = c.have_cost && o.table_valid && std::memcmp(&c.table_key, &o.table_key, sizeof(c.table_key)) == 0;
+    o.cost_valid = o.table_valid = false;
+    if (!c.have_cost) HIP_TRY(hipMemsetAsync(c.wcost, 0, o.at.wcost.bytes, st));
+    return CGRT_OK;
+}
+// rank (unless the table is still valid) and record: the keys, g's table and the launch's record.  With promoted tiles
+// (p.relay.boosts()) the table is the promoted form's, in its own parts of the buffer.
+static int cost_start_rank(TileOrderState &o, const FramePlan &p, const CostStart &c, GridParams &g, hipStream_t st) {
+    const RelayPlan &r = p.relay;
+    const TileOrderLayout &at = o.at;
+    unsigned char *base = reinterpret_cast<unsigned char *>(o.buf.p);
+    const bool boost = r.boosts();
+    if (!c.have_table) {
+        const RelayStartArgs a{r.items(0, 0, 0), (uint32_t)((g.W + kTileW - 1) / kTileW), (uint32_t)p.wtiles_x, (uint32_t)p.wtiles_y};
+        const auto blocks = [](size_t threads) { return dim3((unsigned)((threads + kRelayThreads - 1) / kRelayThreads)); };
+        const dim3 nt(kRelayThreads);
+        if (boost) {
+            const RelayBoostArgs ba{a, r.boost_rule()};
+            const size_t n_tiles = (size_t)p.tile_blocks, n_virtual = n_tiles * (size_t)r.boost.k;
+            uint32_t *head = at.boost.in<uint32_t>(base), *bslot = at.bslot.in<uint32_t>(base), *ecost = at.ecost.in<uint32_t>(base);
+            unsigned long long *bweight = at.bweight.in<unsigned long long>(base);
+            HIP_TRY(hipMemsetAsync(head, 0, kBoostHead * sizeof(uint32_t), st));
+            hipLaunchKernelGGL(relay_boost_cost_kernel, blocks(n_tiles), nt, 0, st, ba, g.plan, g.border, c.wcost, ecost, head);
+            hipLaunchKernelGGL(relay_boost_promote_kernel, blocks(r.base.cap), nt, 0, st, ba, g.plan, ecost, head, bslot);
+            hipLaunchKernelGGL(relay_boost_weight_kernel, blocks(n_virtual), nt, 0, st, ba, g.plan, ecost, bslot, head, bweight);
+            hipLaunchKernelGGL(relay_boost_start_kernel, blocks(n_virtual), nt, 0, st, ba, g.plan, bweight, at.bstart.in<uint32_t>(base));
+        } else {
+            unsigned long long *weight = at.weight.in<unsigned long long>(base);
+            hipLaunchKernelGGL(relay_weight_kernel, blocks(r.start_words), nt, 0, st, a, g.plan, g.border, c.wcost, weight);
+            hipLaunchKernelGGL(relay_start_kernel, blocks(r.start_words), nt, 0, st, a, g.plan, weight, at.start.in<uint32_t>(base));
+        }
+    }
+    // the order's event now stands behind the table too (a reusing launch on another stream waits for it)
+    if (o.valid && (c.have_table || (hipPeekAtLastError() == hipSuccess && hipEventRecord(o.ev, st) == hipSuccess))) {
+        if (!c.have_table) o.stream = st;
+        o.cost_key = c.cost_key;
+        o.table_key = c.table_key;
+        o.cost_valid = o.table_valid = true;
+    } else if (o.valid) {
+        (void)hipGetLastError();
+        o.valid = false;
+    }
+    g.relay_start_at = at.word(boost ? at.bstart : at.start);
+    g.relay_boost_at = boost ? at.word(at.boost) : 0u;
+    o.boost = r.boost_rule();
+    o.start_words = r.start_words;
+    o.start_wtiles = p.n_wt;
+    o.start_reused = c.have_table;
+    return CGRT_OK;
 }
 
 // A cgrt_trace_grid's hold on both states, from the point where it starts to touch them: the last launch's record is cleared,
@@ -258,7 +302,8 @@ static bool relay_prepare(RelayState &r, const FramePlan &p, GridParams &g, Capt
 struct TileOrderGuard {
     TileOrderState &order;
     RelayState &relay;
-    bool relayed = false, through = false;
+    const RelayPlan *relayed = nullptr;  // the plan relay_prepare placed in the launch (nullptr: it goes unrelayed)
+    bool through = false;
     TileOrderGuard(TileOrderState &o, RelayState &r) : order(o), relay(r) {
         order.begin_launch();
         relay.begin_launch();
@@ -274,13 +319,8 @@ struct TileOrderGuard {
             HIP_TRY(hipEventRecord(relay.ev, st));
             relay.stream = st;
             relay.recorded = true;
-            relay.last = RelayState::Last{g.relay_k, (size_t)g.relay_cap, g.relay_slots, g.relay_extent, g.relay_order};
-            if (g.relay_boost_at) {
-                relay.last.boost_k = g.boost_k;
-                relay.last.boost_slots = g.boost_slots;
-                relay.last.boost_cap = (size_t)g.boost_cap;
-                relay.last.boost_off = (size_t)g.relay_boost_off;
-            }
+            relay.last = *relayed;
+            if (!g.relay_boost_at) relay.last.boost = RelayArea{};  // (it had no promoted table: nothing lies in the boost area)
             relay.dirty = false;
         }
         through = true;
@@ -293,10 +333,9 @@ static int last_tile_order(const TileOrderState &o, uint32_t *plan5, uint32_t *l
     const size_t n = o.tiles;
     *n_tiles = (int64_t)n;
     if (n == 0 || cap < (int64_t)n) return CGRT_OK;
-    HIP_TRY(hipDeviceSynchronize());
-    int rc = CGRT_OK;
-    if (plan5 && (rc = o.read(o.at.plan, plan5, kOrderClasses + 1))) return rc;
-    if (list && (rc = o.read(o.at.list, list, n))) return rc;
+    uint32_t plan[kOrderClasses + 1];
+    int rc = o.read_plan(plan5 ? plan5 : plan);
+    if (rc || (list && (rc = o.read(o.at.list, list, n)))) return rc;
     return cls ? o.read(o.at.tile_cls, cls, n) : CGRT_OK;
 }
 static int last_sphere_masks(const TileOrderState &o, uint32_t *masks, int64_t cap, int64_t *n_wave_tiles) {
@@ -318,8 +357,7 @@ static int last_class3_tiles(const TileOrderState &o, TileOrderPlan::Class3 form
     *n_tiles = 0;
     if (o.class3 != form || o.tiles == 0) return CGRT_OK;
     uint32_t plan[kOrderClasses + 1];
-    HIP_TRY(hipDeviceSynchronize());
-    if (int rc = o.read(o.at.plan, plan, kOrderClasses + 1)) return rc;
+    if (int rc = o.read_plan(plan)) return rc;
     *n_tiles = (int64_t)plan[kOrderClasses] - (int64_t)plan[3];
     return CGRT_OK;
 }
@@ -331,36 +369,33 @@ static int last_lens_stage(const TileOrderState &o, int64_t *lds_tiles, int64_t 
 static int last_sample_relay(const TileOrderState &o, const RelayState &r, int64_t *tiles, int32_t *chunks, int64_t *parked_values) {
     *tiles = *parked_values = 0;
     *chunks = 0;
-    const RelayState::Last &l = r.last;
-    if (l.k <= 1 || o.tiles == 0) return CGRT_OK;
+    const RelayPlan &l = r.last;
+    if (!l.relays() || o.tiles == 0) return CGRT_OK;
     uint32_t plan[kOrderClasses + 1];
-    HIP_TRY(hipDeviceSynchronize());
-    if (int rc = o.read(o.at.plan, plan, kOrderClasses + 1)) return rc;
-    const size_t n_split = relay_split_entries(plan[2], plan[3], (uint32_t)l.cap, l.extent);  // the entries in fact split
+    if (int rc = o.read_plan(plan)) return rc;
+    const size_t n_split = relay_split_entries(plan[2], plan[3], (uint32_t)l.base.cap, l.extent);  // the entries in fact split
     *tiles = (int64_t)n_split;
     if (n_split == 0) return CGRT_OK;
-    *chunks = l.k;
+    *chunks = l.base.k;
     // rcount[tile][chunk - 1][thread] of the first n_split tiles is one run of words
-    std::vector<uint32_t> cnt(n_split * (size_t)(l.k - 1) * kRelayThreads);
-    const RelayLayout rl = relay_layout(l.cap, l.k, l.slots);
-    HIP_TRY(hipMemcpy(cnt.data(), reinterpret_cast<const unsigned char *>(r.buf.p) + rl.rcount, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (l.boost_k == 0 || o.boost.k == 0) {
+    const size_t per_base = (size_t)(l.base.k - 1) * kRelayThreads;
+    std::vector<uint32_t> cnt(n_split * per_base);
+    const unsigned char *area = reinterpret_cast<const unsigned char *>(r.buf.p);
+    HIP_TRY(hipMemcpy(cnt.data(), area + relay_layout(l.base.cap, l.base.k, l.base.slots).rcount, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (l.boost.k == 0 || o.boost.k == 0) {
         for (uint32_t c : cnt) *parked_values += (int64_t)c;
         return CGRT_OK;
     }
     // promoted tiles: their counts lie in the boost area, at their boost slots (the base slot's are of an earlier launch)
     std::vector<uint32_t> bslot(n_split);
-    if (int rc = o.read(Region{o.at.boost.at + kBoostHead * sizeof(uint32_t), 0}, bslot.data(), n_split)) return rc;
-    const size_t per = (size_t)(l.boost_k - 1) * kRelayThreads;
-    std::vector<uint32_t> bcnt(l.boost_cap * per);
-    const RelayLayout bl = relay_layout(l.boost_cap, l.boost_k, l.boost_slots);
-    HIP_TRY(hipMemcpy(bcnt.data(), reinterpret_cast<const unsigned char *>(r.buf.p) + l.boost_off + bl.rcount, bcnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (int rc = o.read(o.at.bslot, bslot.data(), n_split)) return rc;
+    const size_t per = (size_t)(l.boost.k - 1) * kRelayThreads;
+    std::vector<uint32_t> bcnt(l.boost.cap * per);
+    HIP_TRY(hipMemcpy(bcnt.data(), area + l.boost_at() + relay_layout(l.boost.cap, l.boost.k, l.boost.slots).rcount, bcnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (size_t e = 0; e < n_split; e++) {
-        if (bslot[e] == 0) {
-            for (size_t i = 0; i < (size_t)(l.k - 1) * kRelayThreads; i++) *parked_values += (int64_t)cnt[e * (size_t)(l.k - 1) * kRelayThreads + i];
-        } else if (bslot[e] <= l.boost_cap) {
-            for (size_t i = 0; i < per; i++) *parked_values += (int64_t)bcnt[(size_t)(bslot[e] - 1) * per + i];
-        }
+        if (bslot[e] > l.boost.cap) continue;
+        const uint32_t *v = bslot[e] ? &bcnt[(size_t)(bslot[e] - 1) * per] : &cnt[e * per_base];
+        for (size_t i = 0; i < (bslot[e] ? per : per_base); i++) *parked_values += (int64_t)v[i];
     }
     return CGRT_OK;
 }
@@ -370,10 +405,9 @@ static int last_relay_boost(const TileOrderState &o, const RelayState &r, int64_
     *promoted = *boost_cap = 0;
     *k_boost = *num = *den = *wg_slots = 0;
     *cost_sum = 0;
-    if (o.boost.k == 0 || r.last.boost_k == 0 || o.start_words == 0 || o.tiles == 0) return CGRT_OK;
+    if (o.boost.k == 0 || r.last.boost.k == 0 || o.start_words == 0 || o.tiles == 0) return CGRT_OK;
     uint32_t plan[kOrderClasses + 1], head[kBoostHead];
-    HIP_TRY(hipDeviceSynchronize());
-    if (int rc = o.read(o.at.plan, plan, kOrderClasses + 1)) return rc;
+    if (int rc = o.read_plan(plan)) return rc;
     if (int rc = o.read(o.at.boost, head, kBoostHead)) return rc;
     *promoted = (int64_t)head[kBoostPromoted];
     *k_boost = (int32_t)o.boost.k;
@@ -382,9 +416,8 @@ static int last_relay_boost(const TileOrderState &o, const RelayState &r, int64_
     *num = (int32_t)o.boost.num;
     *den = (int32_t)o.boost.den;
     *wg_slots = (int32_t)o.boost.slots;
-    const size_t n_split = relay_split_entries(plan[2], plan[3], (uint32_t)r.last.cap, r.last.extent);
-    if (bslot && n_split > 0 && slot_cap >= (int64_t)n_split)
-        return o.read(Region{o.at.boost.at + kBoostHead * sizeof(uint32_t), 0}, bslot, n_split);
+    const size_t n_split = relay_split_entries(plan[2], plan[3], (uint32_t)r.last.base.cap, r.last.extent);
+    if (bslot && n_split > 0 && slot_cap >= (int64_t)n_split) return o.read(o.at.bslot, bslot, n_split);
     return CGRT_OK;
 }
 // the start table of the last launch, its wave tiles' probe costs and the workgroups it ordered
@@ -392,13 +425,11 @@ static int last_relay_start(const TileOrderState &o, const RelayState &r, uint32
                             int64_t *t, int64_t *n_wave_tiles, int32_t *reused) {
     *t = *n_wave_tiles = 0;
     *reused = 0;
-    if (o.start_words == 0 || o.tiles == 0 || r.last.k <= 1) return CGRT_OK;
+    if (o.start_words == 0 || o.tiles == 0 || !r.last.relays()) return CGRT_OK;
     uint32_t plan[kOrderClasses + 1];
-    HIP_TRY(hipDeviceSynchronize());
-    if (int rc = o.read(o.at.plan, plan, kOrderClasses + 1)) return rc;
-    const RelayItems ri{(uint32_t)r.last.k, plan[2], plan[3], plan[kOrderClasses], (uint32_t)r.last.cap, r.last.extent, 0, 0};
-    size_t n = relay_items_total(ri);
-    const bool boosted = o.boost.k != 0 && r.last.boost_k != 0;  // the promoted form's table: its own part, its count in the head
+    if (int rc = o.read_plan(plan)) return rc;
+    size_t n = relay_items_total(r.last.items(plan[2], plan[3], plan[kOrderClasses]));
+    const bool boosted = o.boost.k != 0 && r.last.boost.k != 0;  // the promoted form's table: its own part, its count in the head
     if (boosted) {
         uint32_t head[kBoostHead];
         if (int rc = o.read(o.at.boost, head, kBoostHead)) return rc;
@@ -416,7 +447,7 @@ static int last_relay_start(const TileOrderState &o, const RelayState &r, uint32
     return CGRT_OK;
 }
 static void last_relay_form(const TileOrderState &o, const RelayState &r, int32_t *mirror, int32_t *order) {
-    const bool relayed = r.last.k > 1 && o.tiles != 0;
+    const bool relayed = r.last.relays() && o.tiles != 0;
     *mirror = relayed ? (r.last.extent == kRelayMirror ? 1 : 0) : -1;
     *order = relayed ? r.last.order : -1;
 }

@@ -19,11 +19,16 @@ def _d3(v):
     return (C.c_double * 3)(*[float(x) for x in v])
 
 
-
 _RELAY_ORDERS = ("chunks_first", "mirror_first", "interleaved")  # CGRT_GRID_RELAY_CHUNKS_FIRST / _MIRROR_FIRST / _INTERLEAVED
-
-
 _RELAY_STARTS = ("list", "cost")  # CGRT_GRID_NO_RELAY_COST_START / CGRT_GRID_RELAY_COST_START
+
+
+def _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles):
+    """The CGRT_GRID_* flags of trace_grid's switches, the relay's apart (_relay_flag)."""
+    on = (stats, _capi.GRID_STATS), (split_samples, _capi.GRID_SPLIT_SAMPLES), (force_reorder, _capi.GRID_FORCE_REORDER), (diffuse_tiles, _capi.GRID_DIFFUSE_TILES)
+    off = ((reorder, _capi.GRID_NO_REORDER), (tile_order, _capi.GRID_NO_TILE_ORDER), (sphere_pairs, _capi.GRID_NO_SPHERE_PAIRS),
+           (sphere_masks, _capi.GRID_NO_SPHERE_MASKS), (lens_stage, _capi.GRID_NO_LENS_STAGE), (sure_tiles, _capi.GRID_NO_SURE_TILES))
+    return sum(f for v, f in on if v) | sum(f for v, f in off if not v)
 
 
 def _relay_flag(sample_relay, relay_mirror=None, relay_order=None, relay_start=None, relay_boost=None):
@@ -31,24 +36,24 @@ def _relay_flag(sample_relay, relay_mirror=None, relay_order=None, relay_start=N
     CGRT_GRID_RELAY_MIRROR / _NO_MIRROR for relay_mirror=None|True|False, the order field for relay_order=None|a name and
     CGRT_GRID_RELAY_COST_START / _NO_RELAY_COST_START for relay_start=None|"cost"|"list" and CGRT_GRID_RELAY_BOOST /
     _NO_RELAY_BOOST for relay_boost=None|True|False."""
-    form = 0 if relay_mirror is None else (8192 if relay_mirror else 16384)
+    form = 0 if relay_mirror is None else (_capi.GRID_RELAY_MIRROR if relay_mirror else _capi.GRID_RELAY_NO_MIRROR)
     if relay_boost is not None:
-        form |= 2097152 if relay_boost else 4194304
+        form |= _capi.GRID_RELAY_BOOST if relay_boost else _capi.GRID_NO_RELAY_BOOST
     if relay_start is not None:
         if relay_start not in _RELAY_STARTS:
             raise ValueError("relay_start: None, " + ", ".join(repr(o) for o in _RELAY_STARTS))
-        form |= 524288 if relay_start == "cost" else 1048576
+        form |= _capi.GRID_RELAY_COST_START if relay_start == "cost" else _capi.GRID_NO_RELAY_COST_START
     if relay_order is not None:
         if relay_order not in _RELAY_ORDERS:
             raise ValueError("relay_order: None, " + ", ".join(repr(o) for o in _RELAY_ORDERS))
-        form |= 32768 * (1 + _RELAY_ORDERS.index(relay_order))
+        form |= (_capi.GRID_RELAY_CHUNKS_FIRST, _capi.GRID_RELAY_MIRROR_FIRST, _capi.GRID_RELAY_INTERLEAVED)[_RELAY_ORDERS.index(relay_order)]
     if sample_relay is None:
         return form
     if sample_relay is True or sample_relay is False:
-        return form | (1024 if sample_relay else 2048)
+        return form | (_capi.GRID_SAMPLE_RELAY if sample_relay else _capi.GRID_NO_SAMPLE_RELAY)
     if int(sample_relay) not in (2, 4):
         raise ValueError("sample_relay: None, True, False, 2 or 4")
-    return form | 1024 | (4096 if int(sample_relay) == 4 else 0)
+    return form | _capi.GRID_SAMPLE_RELAY | (_capi.GRID_SAMPLE_RELAY_4 if int(sample_relay) == 4 else 0)
 
 
 def relay_boost_host(k, chunk_spp, spp, cap, mirror, plan, tile_list, wcost, width, rows, k_boost, boost_chunk_spp, boost_cap, num, den,
@@ -266,10 +271,9 @@ class Scene:
             counters = torch.zeros((_capi.CGRT_NCOUNTERS,), dtype=torch.int64, device=dev)
         assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (rows, width, 3)
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
-                              spp_total, (1 if stats else 0) | (2 if accumulate else 0) | (4 if split_samples else 0) |
-                              (0 if reorder else 8) | (16 if force_reorder else 0) | (0 if tile_order else 64) |
-                              (128 if diffuse_tiles else 0) | (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order, relay_start, relay_boost) |
-                              (0 if lens_stage else 131072) | (0 if sure_tiles else 262144))
+                              spp_total, (_capi.GRID_ACCUMULATE if accumulate else 0) |
+                              _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles) |
+                              _relay_flag(sample_relay, relay_mirror, relay_order, relay_start, relay_boost))
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         check(self._L.cgrt_trace_grid(self._h, C.byref(cc), C.byref(g), out.data_ptr(),
                                       nhit.data_ptr() if nhit is not None else None,
@@ -563,10 +567,9 @@ class Scene:
         nhit = np.zeros((rows, width), np.uint32)
         cnt = np.zeros((_capi.CGRT_NCOUNTERS,), np.uint64)
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
-                              spp_total, (1 if stats else 0) | (4 if split_samples else 0) | (0 if reorder else 8) |
-                              (16 if force_reorder else 0) | (0 if tile_order else 64) | (128 if diffuse_tiles else 0) |
-                              (0 if sphere_pairs else 256) | (0 if sphere_masks else 512) | _relay_flag(sample_relay, relay_mirror, relay_order, relay_start, relay_boost) |
-                              (0 if lens_stage else 131072) | (0 if sure_tiles else 262144))
+                              spp_total,
+                              _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles) |
+                              _relay_flag(sample_relay, relay_mirror, relay_order, relay_start, relay_boost))
         check(self._L.cgrt_trace_grid_host(self._h, C.byref(cc), C.byref(g), rgb.ctypes.data, nhit.ctypes.data,
                                            cnt.ctypes.data))
         return dict(rgb=rgb, nhit=nhit, counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]),
@@ -884,7 +887,7 @@ class Scene:
         """Name of the trace_grid_kernel instantiation this grid launches (what a rocprofv3 kernel trace shows).
         hitpoints: the one the Hitpoint capture launches (trace_grid_hitpoints, the eye pass of ppm_render)."""
         rows = height if rows is None else rows
-        flags |= 32 if hitpoints else 0  # CGRT_GRID_HITPOINTS
+        flags |= _capi.GRID_HITPOINTS if hitpoints else 0
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, 0, 0, stripe, 0, None, flags)
         buf = C.create_string_buffer(160)
         check(self._L.cgrt_trace_grid_variant(self._h, C.byref(cc), C.byref(g), buf, len(buf)))

@@ -311,7 +311,7 @@ static FrameInputs spheres(int W = 200, int rows = 117, int spp = 32) {
         CHECK_EQ(q_.order.on, on_);                               \
         CHECK_EQ(q_.order.class3, TileOrderPlan::class3_);        \
         CHECK_EQ(q_.order.masks, masks_);                         \
-        CHECK_EQ(q_.relay_k, relay_k_);                           \
+        CHECK_EQ(q_.relay.base.k, relay_k_);                           \
     } while (0)
 
 static void tile_order() {
@@ -321,18 +321,18 @@ static void tile_order() {
     CHECK_ORDER(in, 1, InKernel, 1, 1);
     in.grid.flags = CGRT_GRID_SAMPLE_RELAY;
     CHECK_ORDER(in, 1, InKernel, 1, 2);
-    CHECK_EQ(frame_plan(in, 0).relay_extent, kRelayGlass);
-    CHECK_EQ(frame_plan(in, 0).relay_order, kRelayChunksFirst);
+    CHECK_EQ(frame_plan(in, 0).relay.extent, kRelayGlass);
+    CHECK_EQ(frame_plan(in, 0).relay.order, kRelayChunksFirst);
     {   // 1920 x 1080: 8100 tiles take every workgroup slot of 256 CUs: relayed by default, in the measured form
         const FramePlan p = frame_plan(spheres(1920, 1080), 0);
         CHECK_EQ(p.tile_blocks, 8100);
         CHECK_EQ(p.order.on, 1);
         CHECK_EQ(p.order.class3, TileOrderPlan::InKernel);
         CHECK_EQ(p.order.masks, 1);
-        CHECK_EQ(p.relay_k, 2);
-        CHECK_EQ(p.relay_chunk_spp, 16);
-        CHECK_EQ(p.relay_extent, kRelayMirror);
-        CHECK_EQ(p.relay_order, kRelayInterleaved);
+        CHECK_EQ(p.relay.base.k, 2);
+        CHECK_EQ(p.relay.base.chunk_spp, 16);
+        CHECK_EQ(p.relay.extent, kRelayMirror);
+        CHECK_EQ(p.relay.order, kRelayInterleaved);
     }
     // the second launch for class 3, on request: one launch each for the two parts of the list, so nothing is relayed
     in.grid.flags = CGRT_GRID_DIFFUSE_TILES | CGRT_GRID_SAMPLE_RELAY;

@@ -281,7 +281,7 @@ static void plan() {
     // it depends neither on the relay nor on the masks
     in = c2;
     in.grid.flags = CGRT_GRID_NO_SAMPLE_RELAY | CGRT_GRID_NO_SPHERE_MASKS;
-    CHECK_EQ(frame_plan(in, 0).relay_k, 1);
+    CHECK_EQ(frame_plan(in, 0).relay.base.k, 1);
     CHECK_EQ(stage_of(in), kLensStageLds);
     in = c2;
     in.grid.spp = in.grid.spp_total = 1;
@@ -305,8 +305,8 @@ static void plan() {
     const FramePlan a = frame_plan(c2, 0), b = frame_plan(in, 0);
     CHECK_EQ(a.grid_dim, b.grid_dim);
     CHECK_EQ(a.scratch.total, b.scratch.total);
-    CHECK_EQ(a.relay_k, b.relay_k);
-    CHECK_EQ(a.relay_bytes, b.relay_bytes);
+    CHECK_EQ(a.relay.base.k, b.relay.base.k);
+    CHECK_EQ(a.relay.base.bytes, b.relay.base.bytes);
     CHECK_EQ(a.order.masks, b.order.masks);
 }
 

@@ -229,98 +229,98 @@ static void frame_plan_part() {
         FrameInputs off = spheres(1920, 1080, 64);
         off.grid.flags = CGRT_GRID_NO_RELAY_BOOST;
         const FramePlan q = frame_plan(off, 0);
-        CHECK_EQ(p.relay_boost, 1);
-        CHECK_EQ(q.relay_boost, 0);
-        CHECK_EQ(p.boost_k, 4);
-        CHECK_EQ(p.boost_chunk_spp, 16);
-        CHECK_EQ(p.boost_slots, relay_slots(16, 5));
-        CHECK_EQ(p.boost_wg_slots, 1024);
-        CHECK_EQ(p.boost_num, kRelayBoostNum);
-        CHECK_EQ(p.boost_den, kRelayBoostDen);
-        CHECK(p.boost_cap > 0 && p.boost_cap <= p.relay_cap);
-        CHECK_EQ(p.boost_cap, relay_cap(p.relay_cap, 4, p.boost_slots, kRelayBoostBudget));
-        CHECK(p.boost_bytes <= kRelayBoostBudget && align256(p.relay_bytes) + p.boost_bytes <= spheres().mem_total / 8);
-        CHECK_EQ(p.boost_words, 2 * p.boost_cap);
-        CHECK_EQ(p.boost_grid, 2 * p.boost_cap);
+        CHECK_EQ(p.relay.boosts(), 1);
+        CHECK_EQ(q.relay.boosts(), 0);
+        CHECK_EQ(p.relay.boost.k, 4);
+        CHECK_EQ(p.relay.boost.chunk_spp, 16);
+        CHECK_EQ(p.relay.boost.slots, relay_slots(16, 5));
+        CHECK_EQ(p.relay.wg_slots, 1024);
+        CHECK_EQ(p.relay.num, kRelayBoostNum);
+        CHECK_EQ(p.relay.den, kRelayBoostDen);
+        CHECK(p.relay.boost.cap > 0 && p.relay.boost.cap <= p.relay.base.cap);
+        CHECK_EQ(p.relay.boost.cap, relay_cap(p.relay.base.cap, 4, p.relay.boost.slots, kRelayBoostBudget));
+        CHECK(p.relay.boost.bytes <= kRelayBoostBudget && align256(p.relay.base.bytes) + p.relay.boost.bytes <= spheres().mem_total / 8);
+        CHECK_EQ(p.relay.boost_words, 2 * p.relay.boost.cap);
+        CHECK_EQ(p.relay.grid(p.grid_dim, true) - p.relay.grid(p.grid_dim, false), 2 * p.relay.boost.cap);
         for (const FramePlan *f : {&p, &q}) {
-            CHECK_EQ(f->relay_k, 2);
-            CHECK_EQ(f->relay_chunk_spp, 32);
-            CHECK_EQ(f->relay_start, kRelayStartCost);
-            CHECK_EQ(f->relay_order, kRelayInterleaved);
-            CHECK_EQ(f->relay_extent, kRelayMirror);
+            CHECK_EQ(f->relay.base.k, 2);
+            CHECK_EQ(f->relay.base.chunk_spp, 32);
+            CHECK_EQ(f->relay.start, kRelayStartCost);
+            CHECK_EQ(f->relay.order, kRelayInterleaved);
+            CHECK_EQ(f->relay.extent, kRelayMirror);
             CHECK_EQ(f->grid_dim, 8100);
-            CHECK_EQ(f->relay_start_words, relay_grid(f->grid_dim, f->relay_k, f->relay_cap));
+            CHECK_EQ(f->relay.start_words, relay_grid(f->grid_dim, f->relay.base.k, f->relay.base.cap));
         }
-        CHECK_EQ(p.relay_cap, q.relay_cap);
-        CHECK_EQ(p.relay_bytes, q.relay_bytes);
+        CHECK_EQ(p.relay.base.cap, q.relay.base.cap);
+        CHECK_EQ(p.relay.base.bytes, q.relay.base.bytes);
         // the order buffer: the new parts lie behind the old ones, which do not move
-        const TileOrderLayout a = tile_order_layout(8100, p.n_wt, true, p.relay_start_words),
-                              c = tile_order_layout(8100, p.n_wt, true, p.relay_start_words, p.boost_words, p.relay_cap, p.boost_k);
+        const TileOrderLayout a = tile_order_layout(8100, p.n_wt, true, p.relay.start_words),
+                              c = tile_order_layout(8100, p.n_wt, true, p.relay.start_words, p.relay.boost_words, p.relay.base.cap, p.relay.boost.k);
         CHECK_EQ(a.boost.bytes + a.ecost.bytes + a.bweight.bytes + a.bstart.bytes, 0);
         CHECK_EQ(c.start.at, a.start.at);
         CHECK_EQ(c.wcost.at, a.wcost.at);
         CHECK_EQ(c.weight.at, a.weight.at);
-        CHECK(c.boost.at >= a.total && c.boost.at % 256 == 0 && c.boost.bytes == (kBoostHead + p.relay_cap) * 4);
+        CHECK(c.boost.at >= a.total && c.boost.at % 256 == 0 && c.boost.bytes == (kBoostHead + p.relay.base.cap) * 4);
         CHECK(c.ecost.at >= c.boost.at + c.boost.bytes && c.ecost.bytes == 8100 * 4);
         CHECK(c.bweight.at >= c.ecost.at + c.ecost.bytes && c.bweight.at % 8 == 0 && c.bweight.bytes == 8100 * 4 * 8);
-        CHECK(c.bstart.at >= c.bweight.at + c.bweight.bytes && c.bstart.bytes == (p.relay_start_words + p.boost_words) * 4);
+        CHECK(c.bstart.at >= c.bweight.at + c.bweight.bytes && c.bstart.bytes == (p.relay.start_words + p.relay.boost_words) * 4);
         CHECK(c.total >= c.bstart.at + c.bstart.bytes);
     }
     for (int spp : {32, 40}) {  // k_boost == relay_k: nothing to promote to, asked for or not
         FrameInputs in = spheres(1920, 1080, spp);
-        CHECK_EQ(frame_plan(in, 0).relay_boost, 0);
+        CHECK_EQ(frame_plan(in, 0).relay.boosts(), 0);
         in.grid.flags = CGRT_GRID_RELAY_BOOST;
-        CHECK_EQ(frame_plan(in, 0).relay_boost, 0);
-        CHECK_EQ(frame_plan(in, 0).relay_start, kRelayStartCost);
+        CHECK_EQ(frame_plan(in, 0).relay.boosts(), 0);
+        CHECK_EQ(frame_plan(in, 0).relay.start, kRelayStartCost);
     }
     {   // 48 samples: three chunks
         const FramePlan p = frame_plan(spheres(1920, 1080, 48), 0);
-        CHECK_EQ(p.relay_boost, 1);
-        CHECK_EQ(p.boost_k, 3);
-        CHECK_EQ(p.boost_chunk_spp, 16);
-        CHECK_EQ(p.relay_k, 2);
+        CHECK_EQ(p.relay.boosts(), 1);
+        CHECK_EQ(p.relay.boost.k, 3);
+        CHECK_EQ(p.relay.boost.chunk_spp, 16);
+        CHECK_EQ(p.relay.base.k, 2);
     }
     {   // flags and knob, flags before the knob; off wins
         FrameInputs in = spheres(1920, 1080, 64);
         in.knobs.relay_boost_off = true;
-        CHECK_EQ(frame_plan(in, 0).relay_boost, 0);
+        CHECK_EQ(frame_plan(in, 0).relay.boosts(), 0);
         in.grid.flags = CGRT_GRID_RELAY_BOOST;
-        CHECK_EQ(frame_plan(in, 0).relay_boost, 1);
+        CHECK_EQ(frame_plan(in, 0).relay.boosts(), 1);
         in.grid.flags = CGRT_GRID_RELAY_BOOST | CGRT_GRID_NO_RELAY_BOOST;
-        CHECK_EQ(frame_plan(in, 0).relay_boost, 0);
+        CHECK_EQ(frame_plan(in, 0).relay.boosts(), 0);
         in.knobs.relay_boost_off = false;
-        CHECK_EQ(frame_plan(in, 0).relay_boost, 0);
+        CHECK_EQ(frame_plan(in, 0).relay.boosts(), 0);
         in.grid.flags = 0;
         in.knobs.relay_boost_num = 3;
         in.knobs.relay_boost_den = 8;
-        CHECK_EQ(frame_plan(in, 0).boost_num, 3);
-        CHECK_EQ(frame_plan(in, 0).boost_den, 8);
+        CHECK_EQ(frame_plan(in, 0).relay.num, 3);
+        CHECK_EQ(frame_plan(in, 0).relay.den, 8);
         in.knobs.relay_boost_tiles = 5;
-        CHECK_EQ(frame_plan(in, 0).boost_cap, 5);
+        CHECK_EQ(frame_plan(in, 0).relay.boost.cap, 5);
         in.knobs.relay_boost_tiles = 0;
-        CHECK_EQ(frame_plan(in, 0).relay_boost, 0);
+        CHECK_EQ(frame_plan(in, 0).relay.boosts(), 0);
     }
     {   // a cost start asked for by flag or knob is not the default launch: promotion has to be asked for too
         FrameInputs in = spheres(1920, 1080, 64);
         in.grid.flags = CGRT_GRID_RELAY_COST_START;
-        CHECK_EQ(frame_plan(in, 0).relay_start, kRelayStartCost);
-        CHECK_EQ(frame_plan(in, 0).relay_boost, 0);
+        CHECK_EQ(frame_plan(in, 0).relay.start, kRelayStartCost);
+        CHECK_EQ(frame_plan(in, 0).relay.boosts(), 0);
         in.grid.flags = CGRT_GRID_RELAY_COST_START | CGRT_GRID_RELAY_BOOST;
-        CHECK_EQ(frame_plan(in, 0).relay_boost, 1);
+        CHECK_EQ(frame_plan(in, 0).relay.boosts(), 1);
         in.grid.flags = CGRT_GRID_SAMPLE_RELAY | CGRT_GRID_RELAY_COST_START | CGRT_GRID_RELAY_BOOST;
         in.grid.width = 200;
         in.grid.height = in.grid.rows = 117;
-        CHECK_EQ(frame_plan(in, 0).relay_boost, 1);
+        CHECK_EQ(frame_plan(in, 0).relay.boosts(), 1);
     }
     {   // a list start never promotes
         FrameInputs in = spheres(1920, 1080, 64);
         in.grid.flags = CGRT_GRID_NO_RELAY_COST_START | CGRT_GRID_RELAY_BOOST;
-        CHECK_EQ(frame_plan(in, 0).relay_boost, 0);
+        CHECK_EQ(frame_plan(in, 0).relay.boosts(), 0);
         in.grid.flags = CGRT_GRID_RELAY_INTERLEAVED | CGRT_GRID_RELAY_BOOST;
-        CHECK_EQ(frame_plan(in, 0).relay_start, kRelayStartList);
-        CHECK_EQ(frame_plan(in, 0).relay_boost, 0);
+        CHECK_EQ(frame_plan(in, 0).relay.start, kRelayStartList);
+        CHECK_EQ(frame_plan(in, 0).relay.boosts(), 0);
         in.grid.flags = CGRT_GRID_NO_SAMPLE_RELAY | CGRT_GRID_RELAY_BOOST;
-        CHECK_EQ(frame_plan(in, 0).relay_boost, 0);
+        CHECK_EQ(frame_plan(in, 0).relay.boosts(), 0);
     }
     {   // the knob's values
         bool off = false;

@@ -157,52 +157,52 @@ int main() {
         in.mem_total = 288000000000ull;
         in.n_cu = 256;
         in.waves_per_simd = 4;
-        CHECK_EQ(frame_plan(in, 0).relay_k, 1);  // not a relay launch
+        CHECK_EQ(frame_plan(in, 0).relay.base.k, 1);  // not a relay launch
         in.image = in.sph = in.pair = in.order_ok = true;  // the PAIR variant in tile order
         {   // by default two chunks: 32 samples each, 512 slots, 3.15 MB a tile
             const FramePlan q = frame_plan(in, 0);
-            CHECK_EQ(q.relay_k, 2);
-            CHECK_EQ(q.relay_chunk_spp, 32);
-            CHECK_EQ(q.relay_slots, 512);
-            CHECK_EQ(q.relay_tile_bytes, 4 + 6144 + 2048 + 1024 + 512 * 6144);
-            CHECK_EQ(q.relay_cap, ((size_t)4 << 30) / q.relay_tile_bytes);
+            CHECK_EQ(q.relay.base.k, 2);
+            CHECK_EQ(q.relay.base.chunk_spp, 32);
+            CHECK_EQ(q.relay.base.slots, 512);
+            CHECK_EQ(relay_tile_bytes(q.relay.base.k, q.relay.base.slots), 4 + 6144 + 2048 + 1024 + 512 * 6144);
+            CHECK_EQ(q.relay.base.cap, ((size_t)4 << 30) / relay_tile_bytes(q.relay.base.k, q.relay.base.slots));
         }
         in.grid.flags = CGRT_GRID_SAMPLE_RELAY_4;
         const FramePlan p = frame_plan(in, 0);
-        CHECK_EQ(p.relay_k, 4);
-        CHECK_EQ(p.relay_chunk_spp, 16);
-        CHECK_EQ(p.relay_slots, 256);
-        CHECK_EQ(p.relay_tile_bytes, 4731908);
-        CHECK_EQ(p.relay_cap, 907);
-        CHECK_EQ(p.relay_bytes, relay_layout(907, 4, 256).total);
+        CHECK_EQ(p.relay.base.k, 4);
+        CHECK_EQ(p.relay.base.chunk_spp, 16);
+        CHECK_EQ(p.relay.base.slots, 256);
+        CHECK_EQ(relay_tile_bytes(p.relay.base.k, p.relay.base.slots), 4731908);
+        CHECK_EQ(p.relay.base.cap, 907);
+        CHECK_EQ(p.relay.base.bytes, relay_layout(907, 4, 256).total);
         CHECK_EQ(p.grid_dim, 8100);  // the surplus is added when the area is there
-        CHECK_EQ(relay_grid(p.grid_dim, p.relay_k, p.relay_cap), 8100 + 3 * 907);
+        CHECK_EQ(relay_grid(p.grid_dim, p.relay.base.k, p.relay.base.cap), 8100 + 3 * 907);
         FrameInputs small = in;  // 200 x 117: 105 tiles < 4 x 256
         small.grid.width = 200;
         small.grid.height = small.grid.rows = 117;
-        CHECK_EQ(frame_plan(small, 0).relay_k, 1);
+        CHECK_EQ(frame_plan(small, 0).relay.base.k, 1);
         small.grid.flags = CGRT_GRID_SAMPLE_RELAY;
-        CHECK_EQ(frame_plan(small, 0).relay_k, 2);
+        CHECK_EQ(frame_plan(small, 0).relay.base.k, 2);
         small.grid.flags = CGRT_GRID_SAMPLE_RELAY | CGRT_GRID_SAMPLE_RELAY_4;
-        CHECK_EQ(frame_plan(small, 0).relay_k, 4);
-        CHECK_EQ(frame_plan(small, 0).relay_cap, 105);
+        CHECK_EQ(frame_plan(small, 0).relay.base.k, 4);
+        CHECK_EQ(frame_plan(small, 0).relay.base.cap, 105);
         small.grid.flags = CGRT_GRID_SAMPLE_RELAY | CGRT_GRID_SAMPLE_RELAY_4 | CGRT_GRID_NO_SAMPLE_RELAY;
-        CHECK_EQ(frame_plan(small, 0).relay_k, 1);
+        CHECK_EQ(frame_plan(small, 0).relay.base.k, 1);
         in.grid.flags = CGRT_GRID_NO_SAMPLE_RELAY;
-        CHECK_EQ(frame_plan(in, 0).relay_k, 1);
+        CHECK_EQ(frame_plan(in, 0).relay.base.k, 1);
         in.grid.flags = CGRT_GRID_SAMPLE_RELAY_4;
         in.grid.spp = 31;
-        CHECK_EQ(frame_plan(in, 0).relay_k, 1);
+        CHECK_EQ(frame_plan(in, 0).relay.base.k, 1);
         in.grid.spp = 70;
-        CHECK_EQ(frame_plan(in, 0).relay_k, 4);
-        CHECK_EQ(frame_plan(in, 0).relay_chunk_spp, 18);
+        CHECK_EQ(frame_plan(in, 0).relay.base.k, 4);
+        CHECK_EQ(frame_plan(in, 0).relay.base.chunk_spp, 18);
         in.knobs.relay_tiles = 3;
-        CHECK_EQ(frame_plan(in, 0).relay_cap, 3);
+        CHECK_EQ(frame_plan(in, 0).relay.base.cap, 3);
         in.grid.flags = 0;
-        CHECK_EQ(frame_plan(in, 0).relay_k, 2);
-        CHECK_EQ(frame_plan(in, 0).relay_chunk_spp, 35);
+        CHECK_EQ(frame_plan(in, 0).relay.base.k, 2);
+        CHECK_EQ(frame_plan(in, 0).relay.base.chunk_spp, 35);
         in.knobs.relay_chunks = 3;
-        CHECK_EQ(frame_plan(in, 0).relay_k, 3);
+        CHECK_EQ(frame_plan(in, 0).relay.base.k, 3);
     }
     std::printf("ok: %d failed checks of %lld\n", g_failed, g_checks);
     return g_failed ? 1 : 0;

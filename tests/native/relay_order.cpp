@@ -161,57 +161,57 @@ int main() {
         CHECK_EQ(in.knobs.relay_order, -1);
         {   // the default launch: the measured form
             const FramePlan p = frame_plan(in, 0);
-            CHECK_EQ(p.relay_k, 2);
-            CHECK_EQ(p.relay_extent, kRelayDefaultExtent);
-            CHECK_EQ(p.relay_order, kRelayDefaultOrder);
-            CHECK_EQ(p.relay_cap, 1361);  // 1 247 tiles of classes 0-2 fit
+            CHECK_EQ(p.relay.base.k, 2);
+            CHECK_EQ(p.relay.extent, kRelayDefaultExtent);
+            CHECK_EQ(p.relay.order, kRelayDefaultOrder);
+            CHECK_EQ(p.relay.base.cap, 1361);  // 1 247 tiles of classes 0-2 fit
         }
         const int32_t asked[] = {CGRT_GRID_SAMPLE_RELAY, CGRT_GRID_SAMPLE_RELAY | CGRT_GRID_SAMPLE_RELAY_4};
         for (const int32_t f : asked) {
             in.grid.flags = f;
-            CHECK_EQ(frame_plan(in, 0).relay_extent, kRelayGlass);
-            CHECK_EQ(frame_plan(in, 0).relay_order, kRelayChunksFirst);
+            CHECK_EQ(frame_plan(in, 0).relay.extent, kRelayGlass);
+            CHECK_EQ(frame_plan(in, 0).relay.order, kRelayChunksFirst);
             in.grid.flags = f | CGRT_GRID_RELAY_MIRROR | CGRT_GRID_RELAY_INTERLEAVED;
-            CHECK_EQ(frame_plan(in, 0).relay_extent, kRelayMirror);
-            CHECK_EQ(frame_plan(in, 0).relay_order, kRelayInterleaved);
+            CHECK_EQ(frame_plan(in, 0).relay.extent, kRelayMirror);
+            CHECK_EQ(frame_plan(in, 0).relay.order, kRelayInterleaved);
             in.grid.flags = f | CGRT_GRID_RELAY_MIRROR_FIRST;
-            CHECK_EQ(frame_plan(in, 0).relay_extent, kRelayGlass);
-            CHECK_EQ(frame_plan(in, 0).relay_order, kRelayMirrorFirst);
+            CHECK_EQ(frame_plan(in, 0).relay.extent, kRelayGlass);
+            CHECK_EQ(frame_plan(in, 0).relay.order, kRelayMirrorFirst);
             in.grid.flags = f | CGRT_GRID_RELAY_CHUNKS_FIRST | CGRT_GRID_RELAY_NO_MIRROR;
-            CHECK_EQ(frame_plan(in, 0).relay_extent, kRelayGlass);
-            CHECK_EQ(frame_plan(in, 0).relay_order, kRelayChunksFirst);
+            CHECK_EQ(frame_plan(in, 0).relay.extent, kRelayGlass);
+            CHECK_EQ(frame_plan(in, 0).relay.order, kRelayChunksFirst);
         }
         in.grid.flags = CGRT_GRID_RELAY_MIRROR | CGRT_GRID_RELAY_MIRROR_FIRST;  // the default gate, the form named
-        CHECK_EQ(frame_plan(in, 0).relay_k, 2);
-        CHECK_EQ(frame_plan(in, 0).relay_extent, kRelayMirror);
-        CHECK_EQ(frame_plan(in, 0).relay_order, kRelayMirrorFirst);
+        CHECK_EQ(frame_plan(in, 0).relay.base.k, 2);
+        CHECK_EQ(frame_plan(in, 0).relay.extent, kRelayMirror);
+        CHECK_EQ(frame_plan(in, 0).relay.order, kRelayMirrorFirst);
         in.grid.flags = CGRT_GRID_NO_SAMPLE_RELAY | CGRT_GRID_RELAY_MIRROR | CGRT_GRID_RELAY_INTERLEAVED;  // not engaged: today's form
-        CHECK_EQ(frame_plan(in, 0).relay_k, 1);
-        CHECK_EQ(frame_plan(in, 0).relay_extent, 0);
-        CHECK_EQ(frame_plan(in, 0).relay_order, 0);
+        CHECK_EQ(frame_plan(in, 0).relay.base.k, 1);
+        CHECK_EQ(frame_plan(in, 0).relay.extent, 0);
+        CHECK_EQ(frame_plan(in, 0).relay.order, 0);
         FrameInputs small = in;  // 200 x 117: below the gate nothing is relayed, whatever form is named
         small.grid.width = 200;
         small.grid.height = small.grid.rows = 117;
         small.grid.flags = CGRT_GRID_RELAY_MIRROR | CGRT_GRID_RELAY_INTERLEAVED;
-        CHECK_EQ(frame_plan(small, 0).relay_k, 1);
-        CHECK_EQ(frame_plan(small, 0).relay_extent, 0);
-        CHECK_EQ(frame_plan(small, 0).relay_order, 0);
+        CHECK_EQ(frame_plan(small, 0).relay.base.k, 1);
+        CHECK_EQ(frame_plan(small, 0).relay.extent, 0);
+        CHECK_EQ(frame_plan(small, 0).relay.order, 0);
         // the knobs: where the flags name nothing
         in.knobs.relay_mirror = 1;
         in.knobs.relay_order = kRelayInterleaved;
         for (const int32_t f : {0, (int32_t)CGRT_GRID_SAMPLE_RELAY}) {
             in.grid.flags = f;
-            CHECK_EQ(frame_plan(in, 0).relay_extent, kRelayMirror);
-            CHECK_EQ(frame_plan(in, 0).relay_order, kRelayInterleaved);
+            CHECK_EQ(frame_plan(in, 0).relay.extent, kRelayMirror);
+            CHECK_EQ(frame_plan(in, 0).relay.order, kRelayInterleaved);
             in.grid.flags = f | CGRT_GRID_RELAY_NO_MIRROR | CGRT_GRID_RELAY_CHUNKS_FIRST;
-            CHECK_EQ(frame_plan(in, 0).relay_extent, kRelayGlass);
-            CHECK_EQ(frame_plan(in, 0).relay_order, kRelayChunksFirst);
+            CHECK_EQ(frame_plan(in, 0).relay.extent, kRelayGlass);
+            CHECK_EQ(frame_plan(in, 0).relay.order, kRelayChunksFirst);
         }
         in.knobs.relay_mirror = 0;
         in.knobs.relay_order = kRelayChunksFirst;
         in.grid.flags = 0;
-        CHECK_EQ(frame_plan(in, 0).relay_extent, kRelayGlass);
-        CHECK_EQ(frame_plan(in, 0).relay_order, kRelayChunksFirst);
+        CHECK_EQ(frame_plan(in, 0).relay.extent, kRelayGlass);
+        CHECK_EQ(frame_plan(in, 0).relay.order, kRelayChunksFirst);
         CHECK_EQ(relay_order_named("chunks_first"), kRelayChunksFirst);
         CHECK_EQ(relay_order_named("mirror_first"), kRelayMirrorFirst);
         CHECK_EQ(relay_order_named("interleaved"), kRelayInterleaved);

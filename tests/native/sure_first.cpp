@@ -359,7 +359,7 @@ int main(int argc, char **argv) {
         FrameInputs off = in;
         off.grid.flags = CGRT_GRID_NO_SURE_TILES;
         CHECK(frame_plan(off, 0).order.masks && !frame_plan(off, 0).order.sure, "CGRT_GRID_NO_SURE_TILES");
-        CHECK(frame_plan(off, 0).relay_k == on.relay_k && frame_plan(off, 0).relay_order == on.relay_order, "the flag changed the relay");
+        CHECK(frame_plan(off, 0).relay.base.k == on.relay.base.k && frame_plan(off, 0).relay.order == on.relay.order, "the flag changed the relay");
         off.grid.flags = CGRT_GRID_NO_SPHERE_MASKS;
         CHECK(!frame_plan(off, 0).order.masks && !frame_plan(off, 0).order.sure, "CGRT_GRID_NO_SPHERE_MASKS implies it");
         off.grid.flags = CGRT_GRID_DIFFUSE_TILES;

@@ -33,6 +33,17 @@ def test_library_exports_every_declared_symbol():
     assert _capi.lib().cgrt_version() == 112
 
 
+def test_grid_flags_match_header():
+    """Every CGRT_GRID_* enumerator of include/cgrt.h has its name in _capi (GRID_*) with the header's value, and _capi names
+    no other; read from the header's text, nothing is loaded."""
+    from cgraytracing_amd import _capi
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "cgrt.h")).read(), flags=re.S)
+    declared = {name: int(value) for name, value in re.findall(r"\bCGRT_(GRID_[A-Z0-9_]+)\s*=\s*(\d+)", hdr)}
+    assert len(declared) >= 25 and declared["GRID_RELAY_ORDER_MASK"] == 98304
+    named = {name: getattr(_capi, name) for name in dir(_capi) if name.startswith("GRID_")}
+    assert named == declared, sorted(set(named.items()) ^ set(declared.items()))
+
+
 def test_struct_layouts_match_header():
     from cgraytracing_amd import _capi
     assert C.sizeof(_capi.Camera) == 48

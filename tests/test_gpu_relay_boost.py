@@ -223,6 +223,45 @@ def test_reuse_and_stale_tables(gpu_ready):
         _same(got, _launch(sc, W, H, 70, cam, 5, "list", seed=SEED + 1, relay_mirror=True), "promotion off")
 
 
+def test_forms_in_turn_on_one_handle(gpu_ready):
+    """What the handle keeps between launches -- the record of the last launch, the two keys, the zeroed extents of both areas --
+    through five forms in turn on one Scene: C2 at 96 x 56 (21 tiles) and 48 samples, the smallest count with a promoted form
+    (3 chunks against 2).  Every launch is the unrelayed one's bit for bit (rgb, nhit, rays, Hitpoints), and the read-backs
+    report the form that launch asked for, nothing for the unrelayed one."""
+    import cgraytracing_amd as cg
+    W, H, spp, cam = 96, 56, 48, scenes.cam_dof()
+    form = dict(mirror=False, order="chunks_first")  # what sample_relay=True has always meant
+    with cg.Scene(scenes.scene_c2()) as sc:
+        def reads():
+            return sc.last_sample_relay(), sc.last_relay_form(), sc.last_relay_start(), sc.last_relay_boost()
+        got = []
+        got.append(_launch(sc, W, H, spp, cam, 5, "cost", True))  # 1: by cost, promoting
+        bo, st, did = _check_boost(sc, W, H, spp, False, "1: cost, boost")
+        n_split = did["tiles"]
+        assert n_split > 0 and did["chunks"] == 2 and bo["k_boost"] == 3 and bo["boost_cap"] >= n_split, (did, bo)
+        assert sc.last_relay_form() == form and not st["reused"]
+        got.append(_launch(sc, W, H, spp, cam, 5, "cost", False))  # 2: by cost, two chunks a tile throughout
+        did2, form2, st2, bo2 = reads()
+        assert did2["tiles"] == n_split and did2["chunks"] == 2 and form2 == form and bo2 is None, (did2, form2, bo2)
+        assert st2 is not None and not st2["reused"] and st2["t"] == int(sc.last_tile_order()["plan"][3]) + n_split, st2
+        assert np.array_equal(st2["wcost"], st["wcost"])
+        assert did2["parked_values"] <= did["parked_values"]
+        got.append(_launch(sc, W, H, spp, cam, 5, "list"))  # 3: from the list
+        did3, form3, st3, bo3 = reads()
+        assert did3 == did2 and form3 == form and st3 is None and bo3 is None, (did3, form3, st3, bo3)
+        with knob(None, 1):  # 4: promoting again, into an area for one tile
+            got.append(_launch(sc, W, H, spp, cam, 5, "cost", True))
+            bo4, st4, did4 = _check_boost(sc, W, H, spp, False, "4: cost, boost, one tile")
+        assert bo4["boost_cap"] == 1 and bo4["promoted"] <= 1 and did4["tiles"] == n_split and sc.last_relay_form() == form, (bo4, did4)
+        assert not st4["reused"] and np.array_equal(st4["wcost"], st["wcost"])
+        want = _launch(sc, W, H, spp, cam, 5, None, None, relay=False)  # 5: no relay
+        did5, form5, st5, bo5 = reads()
+        assert did5 == dict(tiles=0, chunks=0, parked_values=0) and form5 is None and st5 is None and bo5 is None, (did5, form5, st5, bo5)
+        for i, g in enumerate(got):
+            assert np.array_equal(g[0], want[0]) and np.array_equal(g[1], want[1]), "launch %d: image or nhit differs from the unrelayed launch's" % (i + 1)
+            assert np.array_equal(g[2][:2], want[2][:2]), "launch %d: rays / Hitpoints %s vs %s" % (i + 1, g[2], want[2])
+
+
 @pytest.mark.parametrize("cam_name,cam", DEEP_SCENES[1][2], ids=[c[0] for c in DEEP_SCENES[1][2]])
 def test_full_depth_trees(gpu_ready, cam_name, cam):
     """The camera inside a glass sphere (test_gpu_deep_trees' sphere scene): every tile is of class 0 and many rays reach the

@@ -33,5 +33,6 @@ def test_frame_plan_relay_start(tmp_path):
     """spheres(1920, 1080) plans the cost start with the interleaved order behind it; an order named by flag or by knob, a relay
     asked for by flag, no relay, the second launch and fewer than 32 samples give the list; the flags and the knob
     CGRT_RELAY_START switch it either way, flags before the knob; the probe never has more samples than the launch; the table's
-    words are the launch's workgroups."""
+    words are the launch's workgroups.  The four form decisions (extent, order, start, promotion) equal the header's rules,
+    restated by the test, for every combination of the relay's flags and knobs (31 104 of them)."""
     _run(tmp_path, "frame_plan_start")
