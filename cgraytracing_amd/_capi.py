@@ -51,6 +51,7 @@ GRID_RELAY_MIRROR, GRID_RELAY_NO_MIRROR = 8192, 16384
 GRID_RELAY_CHUNKS_FIRST, GRID_RELAY_MIRROR_FIRST, GRID_RELAY_INTERLEAVED, GRID_RELAY_ORDER_MASK = 32768, 65536, 98304, 98304
 GRID_NO_LENS_STAGE, GRID_NO_SURE_TILES = 131072, 262144
 GRID_RELAY_COST_START, GRID_NO_RELAY_COST_START, GRID_RELAY_BOOST, GRID_NO_RELAY_BOOST = 524288, 1048576, 2097152, 4194304
+GRID_NO_LENS_TABLE, GRID_LENS_TABLE = 8388608, 16777216
 
 
 class Photons(C.Structure):
@@ -198,6 +199,7 @@ SIGNATURES = {
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                         C.POINTER(C.c_uint64)]),
     "cgrt_scene_last_lens_stage": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "cgrt_scene_last_lens_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "cgrt_scene_last_tile_order_reused": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "cgrt_trace_grid_diffuse_variant": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
     "cgrt_scene_last_diffuse_tiles": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

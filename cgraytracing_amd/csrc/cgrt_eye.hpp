@@ -125,12 +125,17 @@ __device__ __forceinline__ RelayForm relay_form(const GridParams &g, const Relay
 // (g.probe == 2) and leaves the wave's iteration count; every other variant is spared the test.
 // LSTAGE (DIFF with DOF, the body inside the PAIR variants' launch only): with g.lens_batch the wave stages its lens draws in
 // batches (cgrt_lens_stage.h), in the part of the launch's LDS that holds the PAIR body's pending-ray levels.
+// LTAB (the full and the parking body of the thin-lens PAIR variants' table-reading twins): the lens draws of this workgroup's
+// samples lie in the lens table (cgrt_lens_stage.h), lens_row = table[entry][0][0] of its list entry (workgroup-uniform); the body
+// computes no sample key and runs no rejection loop.
 template <bool TREES, bool BEZ, bool DOF, bool GLASS, bool SPH, bool STATS, bool HPS, int NT, bool HEAVY, bool SPILL = false, bool HFONLY = false,
-          bool DIFF = false, bool PAIR = false, bool PARK = false, bool LSTAGE = false, bool COST = false>
+          bool DIFF = false, bool PAIR = false, bool PARK = false, bool LSTAGE = false, bool COST = false, bool LTAB = false>
 __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const GridParams &g, float *__restrict__ rgb,
                                                 uint32_t *__restrict__ nhit_out, unsigned long long *__restrict__ counters,
-                                                const HitpointSink &hps, int tile_block, int tile_grid, const RelayWg rw = RelayWg{}) {
+                                                const HitpointSink &hps, int tile_block, int tile_grid, const RelayWg rw = RelayWg{},
+                                                const uint64_t *__restrict__ lens_row = nullptr) {
     using TG = TileGeom<NT>;
+    static_assert(!LTAB || (PAIR && DOF && !LSTAGE), "LTAB: the thin-lens PAIR variants' full and parking bodies");
     static_assert(!PARK || (PAIR && NT == kRelayThreads), "PARK: a relayed tile's later chunks");
     static_assert(!DIFF || (SPH && !GLASS && !HPS && !HEAVY && !STATS && !SPILL), "DIFF: the sphere loop, first hits only");
     static_assert(!PAIR || (SPH && GLASS && !HPS && !HEAVY && !STATS && !SPILL), "PAIR: the glass sphere variants of the tile order");
@@ -320,8 +325,19 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
         batch_first = first;
         batch_end = first + count;
     };
+    // LTAB: the draw of the next sample this thread starts, row `smp` of the table entry at lens_row[smp * NT + thread] -- a
+    // workgroup-uniform base and a 32-bit index; loaded here and again at each start, a sample ahead of its use
+    uint64_t z_next = 0;
+    if (LTAB && s < s_end) z_next = lens_row[(uint32_t)s * (uint32_t)NT + threadIdx.x];
     auto start_sample = [&](int smp) {  // main.cpp:204-209
-        if (LSTAGE && staging) {
+        if (LTAB) {
+            double sx, sy;
+            lens_point(z_next, sx, sy);
+            o = camorg + mk(sx, sy, 0) * g.lens_radius;
+            d = normalized(pof - o);
+            k_smp = 0;  // (a sphere scene draws nothing else from the sample's streams)
+            if (smp + 1 < s_end) z_next = lens_row[(uint32_t)(smp + 1) * (uint32_t)NT + threadIdx.x];
+        } else if (LSTAGE && staging) {
             double sx, sy;
             lens_point(lens_slot[(smp - batch_first) * NT], sx, sy);
             o = camorg + mk(sx, sy, 0) * g.lens_radius;
@@ -820,7 +836,7 @@ __device__ __forceinline__ void wg_counters_end(const unsigned long long *wg, un
 
 // One launch = tile workgroups only (probe, image order, Hitpoint capture) ...
 template <bool TREES, bool BEZ, bool DOF, bool GLASS, bool SPH, bool STATS, bool HPS = false, int NT = 256, bool SPILL = false, bool HFONLY = false,
-          bool DIFF = false, bool PAIR = false, bool START = false>
+          bool DIFF = false, bool PAIR = false, bool START = false, bool LTAB = false>
 __global__ __launch_bounds__(NT, DIFF ? (DOF ? kDiffDofWaves : kDiffWaves) : BEZ ? kBezWaves : ((TREES && !HFONLY) ? kTreeWaves : 4)) void trace_grid_kernel(DeviceScene sc, GridParams g, float *__restrict__ rgb,
                                                              uint32_t *__restrict__ nhit_out,
                                                              unsigned long long *__restrict__ counters,
@@ -887,7 +903,16 @@ __global__ __launch_bounds__(NT, DIFF ? (DOF ? kDiffDofWaves : kDiffWaves) : BEZ
     // body here (workgroup-uniform), at this kernel's registers -- 12 % fewer VALU instructions a frame and no second launch
     if (PAIR && g.tile_order == kOrderAllDiffuse && entry >= load_uniform(g.plan + 3))
         trace_grid_body<false, false, DOF, false, true, false, false, NT, false, false, false, true, false, false, DOF>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid);
-    else if (PAIR && rw.chunk > 0)  // a relayed tile's later chunks park their values
+    // LTAB (a twin of its own beside each thin-lens PAIR variant, so that a launch without a lens table keeps its code): the
+    // workgroups of classes 0-2 whose entry the table holds run the bodies that read it (workgroup-uniform); the table's rows have
+    // lens_table_spp samples.  The cost probe is given no table (relay_cost_start, cgrt_hip.hip)
+    else if (LTAB && g.lens_table != nullptr && entry < (unsigned)g.lens_table_cap && entry < load_uniform(g.plan + 3)) {
+        const uint64_t *lens_row = g.lens_table + (size_t)entry * (size_t)g.lens_table_spp * NT;
+        if (rw.chunk > 0)
+            trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF, PAIR, PAIR, false, START, LTAB>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid, rw, lens_row);
+        else
+            trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF, PAIR, false, false, START, LTAB>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid, rw, lens_row);
+    } else if (PAIR && rw.chunk > 0)  // a relayed tile's later chunks park their values
         trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF, PAIR, PAIR, false, START>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid, rw);
     else
         trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF, PAIR, false, false, START>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid, rw);
@@ -1118,6 +1143,33 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(GridParams g, OrderSph
     if (tid == 0) {
         plan[kOrderClasses] = (uint32_t)n;
         plan[kOrderArrived] = 0;
+    }
+}
+
+// The lens table (cgrt_lens_stage.h; behind tile_order_kernel and ahead of the frame -- lens_table_prepare, cgrt_tile_order.hpp, puts it
+// on the handle's second stream, beside the cost probe and the ranking kernels, where there is one): one workgroup
+// of kThreads threads per list entry below the table's capacity; an entry of class 3 -- the terminal-diffuse body reads no table --
+// leaves at once.  Thread t of the workgroup has the pixel thread t of the entry's tile workgroup has in trace_grid_body: the tile
+// from the list (a literal tile number, row-major), the 2x2 wave tiles, lane & 15 and lane >> 4, global_row, pixel_key of the global
+// pixel.  It writes table[entry][s][t] for every sample s of the launch, a batch of kLensTableBatch at a time: the accepted draw of
+// sample sample_offset + s, or 0 where the thread has no live pixel.  Ordinary vector stores; a thread reads back only its own.
+__global__ __launch_bounds__(kThreads) void lens_table_kernel(GridParams g, uint64_t *__restrict__ table) {
+    constexpr int NT = kThreads;
+    const unsigned entry = blockIdx.x;
+    if (entry >= (unsigned)g.lens_table_cap || entry >= load_uniform(g.plan + 3)) return;  // workgroup-uniform
+    const int tile = (int)load_uniform(g.border + entry), tiles_x = (g.W + kTileW - 1) / kTileW;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wtiles_x = (g.W + kWaveTileW - 1) / kWaveTileW, wtiles_y = (g.rows + kWaveTileH - 1) / kWaveTileH;
+    const int wx = (tile % tiles_x) * (kTileW / kWaveTileW) + (wave & 1), wy = (tile / tiles_x) * (kTileH / kWaveTileH) + (wave >> 1);
+    const int w = wx * kWaveTileW + (lane & 15), j = wy * kWaveTileH + (lane >> 4), h = global_row(g, j);
+    const bool live = wx < wtiles_x && wy < wtiles_y && w < g.W && j < g.rows && h < g.H;
+    const uint64_t k_pix = pixel_key(g.seed, (uint64_t)h * (uint64_t)g.W + (uint64_t)w);
+    for (int first = 0; first < g.spp; first += kLensTableBatch) {
+        const int count = min(kLensTableBatch, g.spp - first);
+        uint64_t *row = table + lens_table_at(entry, first, (int)threadIdx.x, g.spp, NT) / sizeof(uint64_t);
+        uint32_t rejected = lens_table_first(k_pix, (uint64_t)(g.sample_offset + first), count, live, row, NT);
+        while (__ballot(rejected != 0u) != 0ull)
+            if (rejected != 0u) rejected = lens_table_retry(rejected, row, NT);
     }
 }
 

@@ -1,6 +1,6 @@
 // The host side of an eye-pass launch in plain C++ (no HIP): the kernel parameters, the workgroup / tile constants, the
 // environment switches and the frame plan -- sample chunks, tile counts, heavy-tile capacity, scheduling, the tile order of a
-// sphere scene (whether it runs, who renders its class-3 tiles, the sphere masks, the lens stage), its sample relay (RelayPlan:
+// sphere scene (whether it runs, who renders its class-3 tiles, the sphere masks, the lens stage, the lens table), its sample relay (RelayPlan:
 // the one decision of its form, its two areas and everything derived from them) and where each array lies in the handle's
 // launch scratch and in its order buffer.  cgrt_trace_grid (cgrt_hip.hip) launches what frame_plan decides;
 // tests/native/frame_plan.cpp checks it on the CPU.
@@ -114,8 +114,13 @@ struct GridParams {
     uint64_t relay_boost_off;
     uint32_t relay_boost_at;
     int32_t boost_k, boost_chunk_spp, boost_cap, boost_slots, pad_boost_;
+    // lens_table != nullptr (the one-launch tile-order PAIR variants under a thin lens, their table-reading twins; cgrt_lens_stage.h):
+    // the full and the parking body of the workgroups of list entries < lens_table_cap take their samples' lens draws from
+    // table[entry][sample][thread], lens_table_spp samples an entry, written by lens_table_kernel ahead of the frame
+    const uint64_t *lens_table;
+    int32_t lens_table_cap, lens_table_spp;
 };
-static_assert(sizeof(GridParams) == 368, "GridParams is a kernel argument: its layout is fixed");
+static_assert(sizeof(GridParams) == 384, "GridParams is a kernel argument: its layout is fixed");
 // the head of the order buffer's boost part, in words: S (two words), the promoted entries, the table's items; bslot follows
 static constexpr int kBoostS = 0, kBoostPromoted = 2, kBoostItems = 3, kBoostHead = 4;
 
@@ -276,6 +281,9 @@ struct EyeKnobs {
     uint32_t relay_boost_num = kRelayBoostNum, relay_boost_den = kRelayBoostDen;
     long long relay_boost_tiles = -1;
     int lens_stage = -1;    // LENS_STAGE: off / lds (kLensStageOff / kLensStageLds), where the launch's flags do not switch it off (-1: unset)
+    int lens_table = -1;    // LENS_TABLE: off / on (on: written by every launch that needs it), where the launch's flags say neither (-1: unset)
+    long long lens_table_bytes = 0;  // LENS_TABLE_BYTES: >= 0 where set: the lens table's byte budget (default kLensTableBudget)
+    bool lens_table_bytes_set = false;
     const char *timeline_file = nullptr;  // TIMELINE_FILE (nullptr: off)
 };
 inline const char *env_str(const char *name) { const char *e = std::getenv(name); return e ? e : ""; }
@@ -325,6 +333,16 @@ inline int lens_stage_named(const char *e) {
     if (v == "lds" || v == "1") return kLensStageLds;
     return -1;
 }
+// The lens table of classes 0-2 (cgrt_lens_stage.h; TileOrderPlan::lens_table_cap).  CGRT_LENS_TABLE's value; -1: none of them
+// Unset, a launch reads the table where it holds its draws and writes it only where the cost probe hides the writing: written
+// with nothing beside it, the table costs a frame more than it saves (the measured form)
+static constexpr bool kLensTableAlways = false;
+inline int lens_table_named(const char *e) {
+    const std::string v(e);
+    if (v == "off" || v == "0") return 0;
+    if (v == "on" || v == "1") return 1;
+    return -1;
+}
 // Read once per process, at the first launch, except CGRT_TIMELINE_FILE, CGRT_RELAY_BOOST and CGRT_RELAY_BOOST_TILES, which every
 // launch reads.
 inline EyeKnobs eye_knobs() {
@@ -360,6 +378,13 @@ inline EyeKnobs eye_knobs() {
         // A/B run takes the default for them)
         if (k.lens_stage < 0 && *env_str("CGRT_LENS_STAGE"))
             std::fprintf(stderr, "cgrt: CGRT_LENS_STAGE=%s names no form of this library (off, lds): the default is used\n", env_str("CGRT_LENS_STAGE"));
+        k.lens_table = lens_table_named(env_str("CGRT_LENS_TABLE"));
+        if (k.lens_table < 0 && *env_str("CGRT_LENS_TABLE"))
+            std::fprintf(stderr, "cgrt: CGRT_LENS_TABLE=%s is neither off nor on: the default is used\n", env_str("CGRT_LENS_TABLE"));
+        if (*env_str("CGRT_LENS_TABLE_BYTES")) {
+            k.lens_table_bytes = std::max(std::atoll(env_str("CGRT_LENS_TABLE_BYTES")), 0ll);
+            k.lens_table_bytes_set = true;
+        }
         return k;
     }();
     EyeKnobs k = once;
@@ -435,6 +460,12 @@ struct TileOrderPlan {
     bool sure = false;
     // kLensStageLds: the terminal-diffuse body inside the launch stages its lens draws in batches (GridParams::lens_batch)
     int lens_stage = kLensStageOff;
+    // lens_table_cap > 0: lens_table_kernel writes the lens draws of the list's first lens_table_cap entries, as far as they are of
+    // classes 0-2, into a table of lens_table_bytes on the handle, and the launch runs the table-reading twin of its kernel
+    // (GridParams::lens_table; a launch that cannot have the table goes without).  lens_table_always: a launch that does not find
+    // its draws in the table writes them wherever it stands; false: only beside its cost probe, and otherwise it goes without
+    size_t lens_table_cap = 0, lens_table_bytes = 0;
+    bool lens_table_always = false;
 };
 
 // Whether a launch of n_tiles tiles relays samples by default: at 32 samples or more (two chunks of 16), and with every workgroup
@@ -623,6 +654,18 @@ inline FramePlan frame_plan(const FrameInputs &in, size_t kmax) {
         o.lens_stage = kn.lens_stage >= 0 ? kn.lens_stage : kLensStageDefault;
     if (o.on && in.pair && o.class3 != TileOrderPlan::SecondLaunch && !split_asked)
         p.relay = relay_plan(gr, kn, (size_t)p.tile_blocks, in.n_cu, in.mem_total);
+    // Lens table: the same launches as the relay's, whether or not they relay, under a thin lens -- the full and the parking body
+    // read their draws from the handle's table.  CGRT_GRID_NO_LENS_TABLE switches it off and CGRT_GRID_LENS_TABLE has every
+    // launch write what it does not find; otherwise the knob CGRT_LENS_TABLE holds (off, on: the same two), and where it names
+    // nothing a launch writes the table only beside its cost probe (kLensTableAlways).  None of them touches the LDS stage of
+    // class 3 above, nor does that one's flag touch the table.
+    const int lens_table = (gr.flags & CGRT_GRID_NO_LENS_TABLE) ? 0 : (gr.flags & CGRT_GRID_LENS_TABLE) ? 1 : kn.lens_table;
+    if (o.on && in.pair && o.class3 != TileOrderPlan::SecondLaunch && !split_asked && in.cam.lens_radius > 0 && lens_table != 0) {
+        const size_t budget = kn.lens_table_bytes_set ? (size_t)kn.lens_table_bytes : kLensTableBudget;
+        o.lens_table_cap = lens_table_cap((size_t)p.tile_blocks, gr.spp, kThreads, budget);
+        o.lens_table_bytes = lens_table_bytes(o.lens_table_cap, gr.spp, kThreads);
+        o.lens_table_always = o.lens_table_cap > 0 && (lens_table > 0 || kLensTableAlways);
+    }
     p.wtiles_x = (gr.width + kWaveTileW - 1) / kWaveTileW;
     p.wtiles_y = (gr.rows + kWaveTileH - 1) / kWaveTileH;
     p.n_wt = (size_t)p.wtiles_x * p.wtiles_y;
@@ -707,6 +750,8 @@ inline GridParams frame_params(const FrameInputs &in, const FramePlan &p) {
     g.items_per_tile = p.items_per_tile;
     g.heavy_blocks = p.heavy_blocks;
     g.lens_batch = p.order.lens_stage == kLensStageLds ? 1 : 0;
+    g.lens_table_cap = (int32_t)p.order.lens_table_cap;  // (the table itself: lens_table_prepare, which clears this where there is none)
+    g.lens_table_spp = p.order.lens_table_cap ? in.grid.spp : 0;
     if (p.heavy_blocks > 0 && p.use_prim) {
         g.prim_obj = in.prim_obj;
         g.prim_done = p.prim_done ? 1 : 0;

@@ -135,6 +135,7 @@ struct cgrt_scene {
     // what a sphere scene's tile-order launches keep on the handle (cgrt_tile_order.hpp)
     mutable TileOrderState order;
     mutable RelayState relay;
+    mutable LensTableState lens;
     size_t mem_total = 0;                // memory of the scene's device (read at commit; bounds the deferred-value budget)
     int n_cu = 256;                      // compute units of the scene's device (read at commit; wave slots of the scheduler)
     // second stream + fork/join events for the light-tile launch that runs beside the full one (created at commit)
@@ -179,13 +180,14 @@ int cgrt_scene_create(cgrt_scene **out) {
 
 void cgrt_scene_destroy(cgrt_scene *s) {
     if (!s) return;
-    if (!s->allocs.empty() || s->scratch.p || s->order.buf.p || s->relay.buf.p || s->tri_ids.p || s->aux_stream || s->order.ev || s->relay.ev) {
+    if (!s->allocs.empty() || s->scratch.p || s->order.buf.p || s->relay.buf.p || s->lens.buf.p || s->lens.ev || s->tri_ids.p || s->aux_stream || s->order.ev || s->relay.ev) {
         DeviceGuard g(s->device);
         if (g.err == hipSuccess) {
             for (void *p : s->allocs) (void)hipFree(p);
             s->scratch.release();
             s->order.release();
             s->relay.release();
+            s->lens.release();
             s->tri_ids.release();
             if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
             if (s->ev_join) (void)hipEventDestroy(s->ev_join);
@@ -556,9 +558,10 @@ struct EyeFlags {
     bool diff = false;  // the terminal-diffuse body (sphere scenes' class-3 tiles)
     bool pair = false;  // the sphere loop two spheres a trip, class-3 tiles by the diffuse body in the same launch (glass sphere scenes)
     bool start = false;  // a PAIR variant's twin that reads the relay's start table and serves as its cost probe (cgrt_relay.h)
+    bool ltab = false;  // a thin-lens PAIR variant's twin whose full and parking bodies read the lens table (cgrt_lens_stage.h)
     constexpr int id() const {
         return (int)trees | (int)bez << 1 | (int)dof << 2 | (int)glass << 3 | (int)sph << 4 | (int)stats << 5 | (int)hps << 6 |
-               (int)spill << 7 | (int)hfonly << 8 | (nt == 64 ? 1 << 9 : 0) | (int)diff << 10 | (int)pair << 11 | (int)start << 12;
+               (int)spill << 7 | (int)hfonly << 8 | (nt == 64 ? 1 << 9 : 0) | (int)diff << 10 | (int)pair << 11 | (int)start << 12 | (int)ltab << 13;
     }
 };
 // image order, the probe and the scheduled form: Bezier scenes share the tree-capable variants (one-wave workgroups)
@@ -682,10 +685,10 @@ struct EyeKernels {
     GridKernel grid;    // trace_grid_kernel
     SchedKernel sched;  // trace_grid_sched_kernel where the scheduled form runs these flags, else nullptr
 };
-template <int T, int B, int D, int G, int P, int S, int H = 0, int NT = kThreads, int SP = 0, int HF = 0, int DF = 0, int PR = 0, int ST = 0>
+template <int T, int B, int D, int G, int P, int S, int H = 0, int NT = kThreads, int SP = 0, int HF = 0, int DF = 0, int PR = 0, int ST = 0, int LT = 0>
 static constexpr EyeKernels gk() {  // trace_grid_kernel only
-    return {EyeFlags{T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, SP != 0, HF != 0, NT, DF != 0, PR != 0, ST != 0}.id(),
-            &trace_grid_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, NT, SP != 0, HF != 0, DF != 0, PR != 0, ST != 0>, nullptr};
+    return {EyeFlags{T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, SP != 0, HF != 0, NT, DF != 0, PR != 0, ST != 0, LT != 0}.id(),
+            &trace_grid_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, NT, SP != 0, HF != 0, DF != 0, PR != 0, ST != 0, LT != 0>, nullptr};
 }
 template <int T, int B, int D, int G, int P, int S, int NT = kThreads>
 static constexpr EyeKernels gsk() {  // both forms
@@ -693,7 +696,7 @@ static constexpr EyeKernels gsk() {  // both forms
     e.sched = &trace_grid_sched_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, NT>;
     return e;
 }
-//                        TREES BEZ DOF GLASS SPH STATS [HPS NT SPILL HFONLY DIFF PAIR START]
+//                        TREES BEZ DOF GLASS SPH STATS [HPS NT SPILL HFONLY DIFF PAIR START LTAB]
 static const EyeKernels kEyeKernels[] = {
     // image order, the probe and the scheduled form (the light variants are the tree and plain ones without GLASS or STATS)
     gsk<1, 1, 0, 0, 0, 0, 64>(), gsk<1, 1, 0, 1, 0, 0, 64>(), gsk<1, 1, 1, 0, 0, 0, 64>(), gsk<1, 1, 1, 1, 0, 0, 64>(),
@@ -713,6 +716,8 @@ static const EyeKernels kEyeKernels[] = {
     gk<0, 0, 0, 1, 1, 0, 0, 256, 0, 0, 0, 1>(), gk<0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 1>(),
     // ... and their twins for a launch whose relay starts by cost: the start table's map, the cost probe
     gk<0, 0, 0, 1, 1, 0, 0, 256, 0, 0, 0, 1, 1>(), gk<0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 1, 1>(),
+    // ... and the thin-lens ones' twins, plain and START, for a launch with a lens table: the bodies that read it
+    gk<0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 1, 0, 1>(), gk<0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 1, 1, 1>(),
 };
 static const EyeKernels *eye_kernels(const EyeFlags &f) {
     for (const EyeKernels &e : kEyeKernels)
@@ -939,9 +944,14 @@ static int probe_and_plan(const cgrt_scene *s, const EyeLaunch &L, const EyeKnob
 // The probe of the relay's start order by cost, between the two host steps of cgrt_tile_order.hpp (cost_start_begin,
 // cost_start_rank): the START twin of the launch's own kernel, which the frame then runs too, over entries [0, plan[3]) of the
 // list (kOrderFull: the workgroups beyond leave at once) with the first probe_spp samples of every pixel from sample 0, the
-// launch's seed and depth, no relay.
+// launch's seed and depth, no relay, no lens table.
 static EyeLaunch start_twin(EyeLaunch L) {
     L.k.start = true;
+    return L;
+}
+// ... and of a launch with a lens table: the twin whose full and parking bodies read it (of the plain or of the START variant)
+static EyeLaunch table_twin(EyeLaunch L) {
+    L.k.ltab = true;
     return L;
 }
 static int relay_cost_start(const cgrt_scene *s, const EyeLaunch &L, const FramePlan &p, GridParams &g, hipStream_t st) {
@@ -959,6 +969,10 @@ static int relay_cost_start(const cgrt_scene *s, const EyeLaunch &L, const Frame
         gp.relay = nullptr;
         gp.relay_k = 0;
         gp.relay_start_at = gp.relay_boost_at = 0;
+        // (L is the launch's kernel without a lens table: the probe draws its lens points by the loop -- its samples start at 0
+        // whatever the launch's offset, and the table is mostly being written beside it; the counts are the same either way)
+        gp.lens_table = nullptr;
+        gp.lens_table_cap = gp.lens_table_spp = 0;
         if (int rc = launch_eye(start_twin(L), false, s->device, gp, dim3((unsigned)p.grid_dim), st, nullptr, nullptr, nullptr)) return rc;
     }
     return cost_start_rank(s->order, p, c, g, st);
@@ -1035,25 +1049,34 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     // launch on the scene's device whatever the caller's current device is (one host thread may drive several GPUs)
     ON_DEVICE(s->device);
     const EyeKnobs kn = eye_knobs();
-    const EyeLaunch L = eye_launch(s, cam, grid, kn, false);
-    const FrameInputs in = frame_inputs(s, cam, grid, L, kn);
+    const EyeLaunch L0 = eye_launch(s, cam, grid, kn, false);
+    const FrameInputs in = frame_inputs(s, cam, grid, L0, kn);
     FramePlan p;
     if ((rc = fit_scratch(s, in, p))) return rc;
     GridParams g = frame_params(in, p);
     unsigned char *scratch = reinterpret_cast<unsigned char *>(s->scratch.p);
-    if (p.heavy_blocks > 0 && (rc = probe_and_plan(s, L, kn, p, g, scratch, st, rgb, nhit, cnt))) return rc;
+    if (p.heavy_blocks > 0 && (rc = probe_and_plan(s, L0, kn, p, g, scratch, st, rgb, nhit, cnt))) return rc;
     p.scratch.place(g, scratch, nhit != nullptr);
     size_t n_blocks = (size_t)p.heavy_blocks + p.grid_dim;
     TileOrderGuard guard(s->order, s->relay);
+    LensTableGuard lens(s->lens, st);
+    bool tabled = false;  // the launch reads the handle's lens table
+    EyeLaunch L = L0;
     if (p.order.on) {  // the tiles that see a mirror or glass sphere first; where the plan says so, their samples relayed
         const Capturing capturing = stream_capturing(st);
         if ((rc = order_tiles(s->order, s->dev, p, g, kn.no_order_reuse, capturing, st))) return rc;
+        // the lens draws of classes 0-2, ahead of the probe and the frame, which then run the kernel's table-reading twin
+        // (written only beside the cost probe, unless the plan says always; a launch without a table runs the kernels without one)
+        const bool beside_probe = p.relay.relays() && p.relay.start == kRelayStartCost && cost_probe_due(s->order, p.relay, g);
+        if (p.order.lens_table_cap > 0 && (tabled = lens_table_prepare(s->lens, s->order, p, g, kn.no_order_reuse, beside_probe, capturing, st, s->aux_stream)))
+            L = table_twin(L0);
         if (p.relay.relays() && relay_prepare(s->relay, p.relay, g, capturing, st)) {
             guard.relayed = &p.relay;
-            if (p.relay.start == kRelayStartCost && (rc = relay_cost_start(s, L, p, g, st))) return rc;
+            if (p.relay.start == kRelayStartCost && (rc = relay_cost_start(s, L0, p, g, st))) return rc;
             // (with the promoted form's table: the promoted tiles' extra chunks too, as many as the boost area holds)
             n_blocks = p.relay.grid(p.grid_dim, g.relay_boost_at != 0);
         }
+        if ((rc = lens_table_join(s->lens, st))) return rc;  // the frame reads the table
     }
     DevBuf timeline;
     if (kn.timeline_file) {
@@ -1093,6 +1116,7 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     if (g.timeline && launch_err == hipSuccess && (rc = write_timeline(kn.timeline_file, timeline, n_blocks, g, L.k.nt, st))) return rc;
     if (launch_err != hipSuccess) return fail(CGRT_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(launch_err));
     if ((rc = guard.commit(g, st))) return rc;
+    if ((rc = lens.commit(tabled))) return rc;
     return kn.plan_dump && g.plan && !g.tile_order ? dump_plan(p, g, st) : CGRT_OK;
 }
 
@@ -1135,6 +1159,11 @@ int cgrt_scene_last_lens_stage(const cgrt_scene *s, int64_t *lds_tiles, int64_t 
     NEED_COMMITTED(s, lds_tiles && area_tiles);
     ON_DEVICE(s->device);
     return last_lens_stage(s->order, lds_tiles, area_tiles);
+}
+int cgrt_scene_last_lens_table(const cgrt_scene *s, int64_t *entries, int64_t *capacity, int32_t *reused) {
+    NEED_COMMITTED(s, entries && capacity && reused);
+    ON_DEVICE(s->device);
+    return last_lens_table(s->order, s->lens, entries, capacity, reused);
 }
 int cgrt_scene_last_sample_relay(const cgrt_scene *s, int64_t *tiles, int32_t *chunks, int64_t *parked_values) {
     NEED_COMMITTED(s, tiles && chunks && parked_values);

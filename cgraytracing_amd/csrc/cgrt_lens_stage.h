@@ -63,4 +63,47 @@ CGRT_HD LensSlot lens_stage_retry(uint64_t ctr) {
     return LensSlot{ok ? z : ctr, ok};
 }
 
+// The lens table (device memory on the scene handle; the full and the parking body of the thin-lens PAIR variants, classes 0-2 of
+// the tile order, which have neither LDS nor registers to spare for a stager): lens_table_kernel (cgrt_eye.hpp), a small kernel
+// ahead of the frame, finds the accepted draw of every (pixel, sample) of the launch by the two phases above over batches of up to
+// kLensTableBatch samples and leaves it in table[entry][sample][thread] -- uint64_t, a workgroup's threads contiguous; entry = the
+// tile-order list entry, sample = the launch's sample number (sample_offset goes into the draw, not into the index), thread = the
+// body's threadIdx.x, so the pixel mapping is the body's own.  A body that reads the table needs neither the pixel key nor
+// sample_key nor the rejection loop.  The table holds the list's first `cap` entries; a workgroup beyond them keeps the per-sample
+// loop (workgroup-uniform).  The draws depend on seed, sample_offset, spp and the pixel set, their place on the order list: the
+// table is kept with the tile order and reused while all of these stand (cgrt_tile_order.hpp).
+static constexpr int kLensTableBatch = 32;
+static_assert(kLensTableBatch <= 32, "a thread's reject word is 32 bits");
+static constexpr size_t kLensTableBudget = (size_t)256 << 20;  // default budget in bytes (knob CGRT_LENS_TABLE_BYTES)
+CGRT_HD constexpr size_t lens_table_entry_bytes(int spp, int threads) { return (size_t)spp * (size_t)threads * sizeof(uint64_t); }
+// the byte offset of table[entry][sample][t]
+CGRT_HD constexpr size_t lens_table_at(size_t entry, int sample, int t, int spp, int threads) {
+    return entry * lens_table_entry_bytes(spp, threads) + ((size_t)sample * (size_t)threads + (size_t)t) * sizeof(uint64_t);
+}
+// entries the table holds: as many of the list's n_tiles entries as the budget pays for
+CGRT_HD constexpr size_t lens_table_cap(size_t n_tiles, int spp, int threads, size_t budget) {
+    return budget / lens_table_entry_bytes(spp, threads) < n_tiles ? budget / lens_table_entry_bytes(spp, threads) : n_tiles;
+}
+CGRT_HD constexpr size_t lens_table_bytes(size_t cap, int spp, int threads) { return cap * lens_table_entry_bytes(spp, threads); }
+
+// lens_table_kernel's per-thread routine for one batch: samples first .. first + count - 1 (sample_offset included in `first`),
+// count <= kLensTableBatch, of the pixel with key k_pix, written to row[b * stride].  Phase A (lens_table_first) returns the
+// thread's reject word; a thread with no live pixel writes 0 and rejects nothing.  Phase B: while any thread of the wave has a bit
+// left, each of those runs lens_table_retry on its lowest rejected sample.
+CGRT_HD uint32_t lens_table_first(uint64_t k_pix, uint64_t first, int count, bool live, uint64_t *row, size_t stride) {
+    uint32_t rejected = 0u;
+    for (int b = 0; b < count; b++) {
+        const LensSlot a = lens_stage_first(k_pix, first + (uint64_t)b);
+        row[(size_t)b * stride] = live ? a.v : 0ull;
+        rejected |= a.done ? 0u : (1u << b);
+    }
+    return live ? rejected : 0u;
+}
+CGRT_HD uint32_t lens_table_retry(uint32_t rejected, uint64_t *row, size_t stride) {  // rejected != 0
+    const int b = __builtin_ctz(rejected);
+    const LensSlot a = lens_stage_retry(row[(size_t)b * stride]);
+    row[(size_t)b * stride] = a.v;
+    return a.done ? rejected & (rejected - 1u) : rejected;
+}
+
 #endif

@@ -1,7 +1,7 @@
 // The host side of a sphere scene's tile-order launch: what the handle keeps for it between launches (the order buffer and the
 // sample relay's area, each with the event and stream that order their users), the steps that prepare a launch (order_tiles,
-// relay_prepare, and the cost start's two: cost_start_begin and cost_start_rank, with the probe between them launched by
-// cgrt_hip.hip), the guard that closes a cgrt_trace_grid over both, and what the cgrt_scene_last_* read-backs report.  What a
+// relay_prepare, the lens table's lens_table_prepare / _join and LensTableGuard, and the cost start's two: cost_start_begin and
+// cost_start_rank, with the probe between them launched by cgrt_hip.hip), the guard that closes a cgrt_trace_grid over both, and what the cgrt_scene_last_* read-backs report.  What a
 // launch does is frame_plan's decision (TileOrderPlan, RelayPlan; cgrt_frame.h).  Part of libcgrt.so (cgrt_hip.hip).
 #ifndef CGRT_TILE_ORDER_HPP
 #define CGRT_TILE_ORDER_HPP
@@ -238,13 +238,21 @@ struct CostStart {
     TileOrderState::CostKey cost_key{};  // this launch's
     TileOrderState::TableKey table_key{};
 };
+// whether the buffer still holds this launch's costs (else relay_cost_start runs the probe)
+static bool costs_kept(const TileOrderState &o, const TileOrderState::CostKey &k) {
+    return o.reused && o.cost_valid && std::memcmp(&k, &o.cost_key, sizeof(k)) == 0;
+}
+// ... asked ahead of cost_start_begin, behind order_tiles, of a launch whose relay starts by cost: the probe will run
+static bool cost_probe_due(const TileOrderState &o, const RelayPlan &r, const GridParams &g) {
+    return o.at.wcost.in<uint32_t>(reinterpret_cast<unsigned char *>(o.buf.p)) != nullptr && !costs_kept(o, TileOrderState::CostKey::of(r, g));
+}
 // what is still valid; costs that are not are zeroed for the probe
 static int cost_start_begin(TileOrderState &o, const RelayPlan &r, const GridParams &g, hipStream_t st, CostStart &c) {
     c.wcost = o.at.wcost.in<uint32_t>(reinterpret_cast<unsigned char *>(o.buf.p));
     if (!c.wcost) return CGRT_OK;
     c.cost_key = TileOrderState::CostKey::of(r, g);
     c.table_key = TileOrderState::TableKey::of(r);
-    c.have_cost = o.reused && o.cost_valid && std::memcmp(&c.cost_key, &o.cost_key, sizeof(c.cost_key)) == 0;
+    c.have_cost = costs_kept(o, c.cost_key);
     c.have_table = c.have_cost && o.table_valid && std::memcmp(&c.table_key, &o.table_key, sizeof(c.table_key)) == 0;
     o.cost_valid = o.table_valid = false;
     if (!c.have_cost) HIP_TRY(hipMemsetAsync(c.wcost, 0, o.at.wcost.bytes, st));
@@ -295,6 +303,146 @@ static int cost_start_rank(TileOrderState &o, const FramePlan &p, const CostStar
     o.start_reused = c.have_table;
     return CGRT_OK;
 }
+
+// The lens table (cgrt_lens_stage.h; launch scratch like the relay area: allocated by the first launch that uses it, sized by the
+// largest, freed with the scene; not a part of FramePlan::scratch).  refused: the smallest size the device has refused (such a
+// launch goes without a table).  ev is recorded behind every launch that read the table, on `stream`; a launch on another stream
+// waits for it before it reads or rewrites the table -- the table is one.  What it holds: the draws depend on seed, sample_offset,
+// spp and the pixel set, their place on the order list, so the table is kept with the tile order -- valid while the order is
+// reused and Key, which holds the order's own key, is the same.  cap, reused: the last launch's (cap == 0: it read no table).
+// A launch that has to write the table does so on the handle's second stream where it has one (ev_fork / ev_built; joining: the
+// launch's stream has yet to wait for it).  Beside the cost probe and the ranking kernels, which leave most of the device idle,
+// that costs the frame nothing; with nothing beside it the kernel takes longer than the frame gains, so unless the plan says
+// lens_table_always a launch writes the table only where its probe is due and otherwise goes without one.
+struct LensTableState {
+    GrowBuf buf;
+    size_t refused = 0;
+    hipEvent_t ev = nullptr, ev_fork = nullptr, ev_built = nullptr;
+    bool joining = false;
+    hipStream_t stream = nullptr;
+    bool recorded = false;
+    struct Key {
+        TileOrderState::Key order;
+        uint64_t seed;
+        int32_t sample_offset, spp;
+        uint64_t cap;
+        const void *buf;
+    };
+    static_assert(sizeof(Key) == 128, "Key is compared as bytes: no padding");
+    Key key{}, pending{};
+    bool valid = false, keep = false, reused = false;
+    size_t cap = 0;
+
+    void begin_launch() {
+        cap = 0;
+        reused = keep = joining = false;
+    }
+    void release() {
+        buf.release();
+        for (hipEvent_t *e : {&ev, &ev_fork, &ev_built}) {
+            if (*e) (void)hipEventDestroy(*e);
+            *e = nullptr;
+        }
+    }
+};
+// st waits for the table where it is being written on the second stream (ahead of the frame; a no-op otherwise)
+static int lens_table_join(LensTableState &t, hipStream_t st) {
+    if (!t.joining) return CGRT_OK;
+    t.joining = false;
+    HIP_TRY(hipStreamWaitEvent(st, t.ev_built, 0));
+    return CGRT_OK;
+}
+// The lens table of a launch whose plan has one (p.order.lens_table_cap > 0; behind order_tiles on its stream), and g's fields.
+// Returns false -- the launch's bodies of classes 0-2 draw sample by sample, in the kernels without a table, which is no error --
+// when the stream is being captured or its state cannot be asked, or the table cannot be had.  Unless the table still holds this
+// launch's draws, lens_table_kernel writes them here: on `aux` (the handle's second stream; nullptr: on st), behind what st holds
+// so far -- the ordering kernel, and every earlier reader of the table -- and lens_table_join makes st wait for it ahead of the
+// frame.  beside_probe: the launch's cost probe is due (cost_probe_due); without it, and without lens_table_always, a launch
+// that would have to write the table goes without one too, and the table stays what it was.
+// no_reuse (CGRT_NO_ORDER_REUSE=1): every launch writes them.
+static bool lens_table_prepare(LensTableState &t, const TileOrderState &o, const FramePlan &p, GridParams &g, bool no_reuse, bool beside_probe,
+                               Capturing capturing, hipStream_t st, hipStream_t aux) {
+    const auto ok = [](hipError_t e) { return e == hipSuccess || ((void)hipGetLastError(), false); };
+    const auto none = [&g] {
+        g.lens_table = nullptr;
+        g.lens_table_cap = g.lens_table_spp = 0;
+        return false;
+    };
+    const size_t bytes = p.order.lens_table_bytes, cap = p.order.lens_table_cap;
+    if (capturing != Capturing::None || bytes == 0) return none();
+    if (t.refused && bytes >= t.refused) return none();
+    const bool may_write = p.order.lens_table_always || beside_probe;
+    if (bytes > t.buf.cap) {
+        if (!may_write) return none();  // (a table that small holds nothing of this launch's)
+        // the launches that read the old table, and a kernel that wrote it for a launch that failed, are through before it is freed
+        if (t.recorded) (void)ok(hipEventSynchronize(t.ev));
+        if (t.ev_built) (void)ok(hipEventSynchronize(t.ev_built));
+        t.valid = false;
+        if (!ok(t.buf.need(bytes))) {
+            t.refused = bytes;
+            return none();
+        }
+    }
+    if (!t.ev && !ok(hipEventCreateWithFlags(&t.ev, hipEventDisableTiming))) {
+        t.ev = nullptr;
+        return none();
+    }
+    if (t.recorded && st != t.stream && !ok(hipStreamWaitEvent(st, t.ev, 0))) return none();
+    // (o.valid: the order's key is this launch's -- order_tiles leaves none behind a capture or under no_reuse)
+    const LensTableState::Key key{o.key, g.seed, g.sample_offset, g.spp, (uint64_t)cap, t.buf.p};
+    t.keep = o.valid && !no_reuse;
+    t.reused = t.keep && o.reused && t.valid && std::memcmp(&key, &t.key, sizeof(key)) == 0;
+    if (!t.reused && !may_write) return none();
+    if (!t.reused) {
+        t.valid = false;
+        const auto event = [&ok](hipEvent_t &e) { return e || ok(hipEventCreateWithFlags(&e, hipEventDisableTiming)) || (e = nullptr, false); };
+        hipStream_t ks = st;
+        if (aux && event(t.ev_fork) && event(t.ev_built) && ok(hipEventRecord(t.ev_fork, st)) && ok(hipStreamWaitEvent(aux, t.ev_fork, 0))) ks = aux;
+        hipLaunchKernelGGL(lens_table_kernel, dim3((unsigned)cap), dim3(kThreads), 0, ks, g, reinterpret_cast<uint64_t *>(t.buf.p));
+        const bool launched = ok(hipPeekAtLastError());
+        if (ks != st) {
+            if (ok(hipEventRecord(t.ev_built, ks))) t.joining = true;
+            else (void)ok(hipStreamSynchronize(ks));  // (no event to wait for: the table is written before st goes on)
+        }
+        if (!launched) {
+            (void)lens_table_join(t, st);
+            return none();
+        }
+    }
+    g.lens_table = reinterpret_cast<const uint64_t *>(t.buf.p);
+    t.pending = key;
+    t.cap = cap;
+    return true;
+}
+// A cgrt_trace_grid's hold on the table, like TileOrderGuard's on the order: the last launch's record is cleared, and an exit
+// without commit leaves neither a key nor a record of a table read, and st behind a kernel still writing on the second stream.
+struct LensTableGuard {
+    LensTableState &t;
+    hipStream_t st;
+    bool through = false;
+    LensTableGuard(LensTableState &table, hipStream_t stream) : t(table), st(stream) { t.begin_launch(); }
+    LensTableGuard(const LensTableGuard &) = delete;
+    LensTableGuard &operator=(const LensTableGuard &) = delete;
+    ~LensTableGuard() {
+        if (through) return;
+        if (lens_table_join(t, st) != CGRT_OK) (void)hipGetLastError();
+        t.valid = t.reused = false;
+        t.cap = 0;
+    }
+    // the launch went out on st without an error; tabled: it reads the table
+    int commit(bool tabled) {
+        through = true;
+        if (!tabled) return CGRT_OK;
+        HIP_TRY(hipEventRecord(t.ev, st));
+        t.stream = st;
+        t.recorded = true;
+        if (t.keep) {
+            t.key = t.pending;
+            t.valid = true;
+        }
+        return CGRT_OK;
+    }
+};
 
 // A cgrt_trace_grid's hold on both states, from the point where it starts to touch them: the last launch's record is cleared,
 // and every exit without commit drops the stored order's key -- only a call that went through leaves one -- and leaves the
@@ -365,6 +513,19 @@ static int last_class3_tiles(const TileOrderState &o, TileOrderPlan::Class3 form
 static int last_lens_stage(const TileOrderState &o, int64_t *lds_tiles, int64_t *area_tiles) {
     *lds_tiles = *area_tiles = 0;
     return o.lens_stage == kLensStageLds ? last_class3_tiles(o, TileOrderPlan::InKernel, lds_tiles) : CGRT_OK;
+}
+// the list entries of the last launch whose workgroups read their lens draws from the table -- its entries of classes 0-2 below
+// the table's capacity --, that capacity, and whether the launch found the table written
+static int last_lens_table(const TileOrderState &o, const LensTableState &t, int64_t *entries, int64_t *capacity, int32_t *reused) {
+    *entries = *capacity = 0;
+    *reused = 0;
+    if (t.cap == 0 || o.tiles == 0) return CGRT_OK;
+    uint32_t plan[kOrderClasses + 1];
+    if (int rc = o.read_plan(plan)) return rc;
+    *entries = (int64_t)std::min((size_t)plan[3], t.cap);
+    *capacity = (int64_t)t.cap;
+    *reused = t.reused ? 1 : 0;
+    return CGRT_OK;
 }
 static int last_sample_relay(const TileOrderState &o, const RelayState &r, int64_t *tiles, int32_t *chunks, int64_t *parked_values) {
     *tiles = *parked_values = 0;

@@ -23,12 +23,13 @@ _RELAY_ORDERS = ("chunks_first", "mirror_first", "interleaved")  # CGRT_GRID_REL
 _RELAY_STARTS = ("list", "cost")  # CGRT_GRID_NO_RELAY_COST_START / CGRT_GRID_RELAY_COST_START
 
 
-def _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles):
+def _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles, lens_table=None):
     """The CGRT_GRID_* flags of trace_grid's switches, the relay's apart (_relay_flag)."""
     on = (stats, _capi.GRID_STATS), (split_samples, _capi.GRID_SPLIT_SAMPLES), (force_reorder, _capi.GRID_FORCE_REORDER), (diffuse_tiles, _capi.GRID_DIFFUSE_TILES)
     off = ((reorder, _capi.GRID_NO_REORDER), (tile_order, _capi.GRID_NO_TILE_ORDER), (sphere_pairs, _capi.GRID_NO_SPHERE_PAIRS),
            (sphere_masks, _capi.GRID_NO_SPHERE_MASKS), (lens_stage, _capi.GRID_NO_LENS_STAGE), (sure_tiles, _capi.GRID_NO_SURE_TILES))
-    return sum(f for v, f in on if v) | sum(f for v, f in off if not v)
+    table = 0 if lens_table is None else _capi.GRID_LENS_TABLE if lens_table else _capi.GRID_NO_LENS_TABLE
+    return sum(f for v, f in on if v) | sum(f for v, f in off if not v) | table
 
 
 def _relay_flag(sample_relay, relay_mirror=None, relay_order=None, relay_start=None, relay_boost=None):
@@ -230,7 +231,7 @@ class Scene:
                    stripe=None, sample_offset=0, spp_total=None, out=None, nhit=None, counters=None, stream=None,
                    stats=False, accumulate=False, split_samples=False, reorder=True, force_reorder=False, tile_order=True,
                    diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None,
-                   relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True, relay_start=None, relay_boost=None):
+                   relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True, relay_start=None, relay_boost=None, lens_table=None):
         """Asynchronous launch on torch's current stream (or `stream`).  reorder=False: CGRT_GRID_NO_REORDER (tiles in image
         order instead of heaviest-first; same image).  tile_order=False: CGRT_GRID_NO_TILE_ORDER (an image-order launch starts
         its tiles row-major instead of mirror / glass tiles first; same image).  diffuse_tiles=True: CGRT_GRID_DIFFUSE_TILES (a
@@ -251,7 +252,11 @@ class Scene:
         workgroups instead of 2 (CGRT_GRID_RELAY_BOOST; same image, hit counts, rays and Hitpoints; last_relay_boost), False --
         CGRT_GRID_NO_RELAY_BOOST; None: where the launch starts by cost by default.  lens_stage=False: CGRT_GRID_NO_LENS_STAGE (the thin-lens
         terminal-diffuse body inside the main launch draws every lens point by its own rejection loop instead of staging 16
-        samples' draws ahead; same image; last_lens_stage).  sure_tiles=False: CGRT_GRID_NO_SURE_TILES (a wave of the
+        samples' draws ahead; same image; last_lens_stage).  lens_table=False: CGRT_GRID_NO_LENS_TABLE (under a thin lens the tiles that
+        may see a mirror or a glass sphere run the rejection loop per sample instead of reading their lens draws from the table a
+        small kernel writes ahead of the frame; same image, hit counts and counters; last_lens_table), True: CGRT_GRID_LENS_TABLE
+        (a launch that does not find its draws in the table writes them wherever it stands), None: it writes them only beside
+        its cost probe and otherwise goes without a table.  sure_tiles=False: CGRT_GRID_NO_SURE_TILES (a wave of the
         terminal-diffuse body traces its samples even where every ray of its 16x4 wave tile provably hits the same sphere first;
         same image, hit counts and counters; sphere_masks=False implies it; last_sure_tiles).  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
         workgroups share a tile's samples; reproducible, fp64 summation order differs from the sample-by-sample sum).  Returns (rgb, nhit, counters) torch
@@ -272,7 +277,7 @@ class Scene:
         assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (rows, width, 3)
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (_capi.GRID_ACCUMULATE if accumulate else 0) |
-                              _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles) |
+                              _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles, lens_table) |
                               _relay_flag(sample_relay, relay_mirror, relay_order, relay_start, relay_boost))
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         check(self._L.cgrt_trace_grid(self._h, C.byref(cc), C.byref(g), out.data_ptr(),
@@ -560,7 +565,7 @@ class Scene:
     def trace_grid_host(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                         stripe=None, sample_offset=0, spp_total=None, stats=False, split_samples=False, reorder=True,
                         force_reorder=False, tile_order=True, diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None,
-                        relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True, relay_start=None, relay_boost=None):
+                        relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True, relay_start=None, relay_boost=None, lens_table=None):
         """Synchronous form with numpy outputs (no torch needed): dict(rgb, nhit, counters)."""
         rows = height - row_offset if rows is None else rows
         rgb = np.zeros((rows, width, 3), np.float32)
@@ -568,7 +573,7 @@ class Scene:
         cnt = np.zeros((_capi.CGRT_NCOUNTERS,), np.uint64)
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total,
-                              _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles) |
+                              _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles, lens_table) |
                               _relay_flag(sample_relay, relay_mirror, relay_order, relay_start, relay_boost))
         check(self._L.cgrt_trace_grid_host(self._h, C.byref(cc), C.byref(g), rgb.ctypes.data, nhit.ctypes.data,
                                            cnt.ctypes.data))
@@ -661,6 +666,14 @@ class Scene:
             return None
         return dict(promoted=int(p.value), k_boost=int(k.value), boost_cap=int(cap.value), S=int(S.value), num=int(num.value),
                     den=int(den.value), wg_slots=int(ws.value), bslot=bslot[:tiles])
+
+    def last_lens_table(self):
+        """The lens table in this scene's last trace_grid / trace_grid_host (cgrt_scene_last_lens_table; synchronises the device):
+        dict(entries: tile-order list entries whose workgroups read their lens draws from the table, capacity: the entries the table
+        held, reused: the launch found it written by an earlier one).  All zero: the launch read no table."""
+        a, b, r = C.c_int64(), C.c_int64(), C.c_int32()
+        check(self._L.cgrt_scene_last_lens_table(self._h, C.byref(a), C.byref(b), C.byref(r)))
+        return dict(entries=int(a.value), capacity=int(b.value), reused=bool(r.value))
 
     def last_lens_stage(self):
         """Lens points staged ahead by this scene's last trace_grid / trace_grid_host (cgrt_scene_last_lens_stage; synchronises

@@ -174,6 +174,26 @@ enum {
                                  the pace of the wave's unluckiest lane.  The same lens points: same image, hit counts and
                                  counters either way; it exists to test one against the other.  The second launch of
                                  CGRT_GRID_DIFFUSE_TILES always draws sample by sample                                    */
+    CGRT_GRID_NO_LENS_TABLE = 8388608, /* the full and the parking body of a glass sphere scene's one-launch tile order (see
+                                 CGRT_GRID_NO_SPHERE_PAIRS) under a thin-lens camera: by default a small kernel ahead of the
+                                 frame finds the accepted lens draw of every sample of the tiles that may see a mirror or a
+                                 glass sphere and leaves it in a table on the handle (8 bytes a pixel and sample, at most
+                                 CGRT_LENS_TABLE_BYTES, default 256 MiB; the list's first entries where it is short), and those
+                                 tiles' workgroups read their draws there instead of running the rejection loop in lockstep.
+                                 The table is kept with the tile order and reused while order, seed, sample_offset and spp
+                                 stand (cgrt_scene_last_lens_table): the gain is that of a launch repeated with exactly these.
+                                 Writing the table costs more than reading it saves in one frame, so by default a launch
+                                 writes it only where that is hidden: on the handle's second stream, beside the cost probe of a
+                                 relay that starts by cost (see CGRT_GRID_RELAY_COST_START) -- the first frame of a camera or
+                                 a seed.  A launch that finds neither its draws in the table nor a probe to write them beside
+                                 -- a pass of a progressive render, whose sample_offset moves -- runs the loop, in the kernels
+                                 that have no table code, as under this flag or the knob CGRT_LENS_TABLE=off.  The same lens
+                                 points: same image, hit counts and counters either way.  Independent of
+                                 CGRT_GRID_NO_LENS_STAGE, which is class 3's.  A captured launch, or one whose table cannot be
+                                 allocated, goes without                                                                   */
+    CGRT_GRID_LENS_TABLE = 16777216, /* ... and with this flag (or the knob CGRT_LENS_TABLE=on) every such launch that does not
+                                 find its draws in the table writes them, ahead of its frame, whether or not anything hides
+                                 that: for tests and measurements.  CGRT_GRID_NO_LENS_TABLE wins over it                    */
     CGRT_GRID_NO_SURE_TILES = 262144, /* the terminal-diffuse body, where it has sphere masks (see CGRT_GRID_NO_SPHERE_MASKS, which
                                  implies this flag): by default a second small kernel behind the ordering kernel proves, per
                                  16x4-pixel wave tile of a class-3 tile, whether every primary ray of it -- any pixel, any lens
@@ -730,6 +750,12 @@ int cgrt_scene_last_relay_start(const cgrt_scene *s, uint32_t *start, int64_t st
  * synchronises the device): *lds_tiles = the tiles whose workgroups staged their lens draws in LDS batches, *area_tiles = the
  * tiles that staged them in device memory (no launch does: always 0).  Both 0: every lens point came from the per-sample loop. */
 int cgrt_scene_last_lens_stage(const cgrt_scene *s, int64_t *lds_tiles, int64_t *area_tiles);
+/* The lens table of the LAST cgrt_trace_grid on the handle (see CGRT_GRID_NO_LENS_TABLE; synchronises the device): *entries = the
+ * entries of the tile-order list whose workgroups read their lens draws from the table (its tiles of classes 0-2 below the
+ * capacity), *capacity = the entries the table held (CGRT_LENS_TABLE_BYTES / (spp x 2048 bytes), at most the tiles), *reused = 1
+ * when the launch found the table written by an earlier one (same order, seed, sample_offset, spp and capacity) and ran no
+ * lens_table_kernel.  All 0: the launch read no table, or it returned an error. */
+int cgrt_scene_last_lens_table(const cgrt_scene *s, int64_t *entries, int64_t *capacity, int32_t *reused);
 
 /* Host evaluation of that table (cgrt_relay.h, the same inline code the kernels run; no GPU): for a list of n_tiles entries,
  * the first n01 of class 0 or 1 and the first n012 of classes 0-2 (cgrt_scene_last_tile_order's plan[2], plan[3], plan[4] and

@@ -5,7 +5,7 @@
 
 Runs `make -C cgraytracing_amd/csrc asm` (hipcc -S --cuda-device-only -Rpass-analysis=kernel-resource-usage, the same
 flags as the product build; cross-compiles for gfx950 without a GPU) and parses the compiler's remarks.  The template
-arguments of trace_grid_kernel are decoded from the mangled name: <TREES,BEZ,DOF,GLASS,SPH,STATS,HPS,NT,SPILL,HFONLY,DIFF,PAIR[,START]>."""
+arguments of trace_grid_kernel are decoded from the mangled name: <TREES,BEZ,DOF,GLASS,SPH,STATS,HPS,NT,SPILL,HFONLY,DIFF,PAIR[,START[,LTAB]]>."""
 import json
 import os
 import re
@@ -16,6 +16,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def demangle_variant(name):
+    m = re.match(r"_Z17trace_grid_kernelIL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)ELi(\d+)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EE", name)
+    if m:
+        t = [int(x) for x in m.groups()]
+        if t[-1] == 0:  # (the names the earlier tables have for it)
+            if t[-2] == 0:
+                return "trace_grid_kernel<TREES=%d,BEZ=%d,DOF=%d,GLASS=%d,SPH=%d,STATS=%d,HPS=%d,NT=%d,SPILL=%d,HFONLY=%d,DIFF=%d,PAIR=%d>" % tuple(t[:-2])
+            return "trace_grid_kernel<TREES=%d,BEZ=%d,DOF=%d,GLASS=%d,SPH=%d,STATS=%d,HPS=%d,NT=%d,SPILL=%d,HFONLY=%d,DIFF=%d,PAIR=%d,START=%d>" % tuple(t[:-1])
+        return "trace_grid_kernel<TREES=%d,BEZ=%d,DOF=%d,GLASS=%d,SPH=%d,STATS=%d,HPS=%d,NT=%d,SPILL=%d,HFONLY=%d,DIFF=%d,PAIR=%d,START=%d,LTAB=%d>" % tuple(t)
     m = re.match(r"_Z17trace_grid_kernelIL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)ELi(\d+)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EE", name)
     if m:
         t = [int(x) for x in m.groups()]
