@@ -5,6 +5,7 @@
 #include "cgrt_scene_walk.hpp"
 #include "cgrt_sphere_mask.h"
 #include "cgrt_sure_first.h"
+#include "cgrt_variants.h"
 
 // =====================================================================================================
 // the eye pass
@@ -34,18 +35,7 @@ struct Pending {  // a refracted child waiting for its turn (main.cpp:157)
 // waves per SIMD the DIFF variants are compiled for: the pinhole one fits 8 (52 VGPRs); the thin-lens one spills 4 VGPRs at 8
 // (64) and is compiled for 6
 static constexpr int kDiffWaves = CGRT_DIFF_WAVES, kDiffDofWaves = CGRT_DIFF_DOF_WAVES;
-#ifndef CGRT_BEZ_WAVES
-#define CGRT_BEZ_WAVES 2
-#endif
-static constexpr int kBezWaves = CGRT_BEZ_WAVES;  // waves per SIMD the Bezier variants are compiled for
-#ifndef CGRT_TREE_WAVES
-#define CGRT_TREE_WAVES 3
-#endif
-#ifndef CGRT_SCHED_TREE_WAVES
-#define CGRT_SCHED_TREE_WAVES CGRT_TREE_WAVES
-#endif
-static constexpr int kTreeWaves = CGRT_TREE_WAVES;             // ... the tree-capable tile kernels
-static constexpr int kSchedTreeWaves = CGRT_SCHED_TREE_WAVES;  // ... the tree-capable scheduled kernels (unit queue + tile queue)
+// (kBezWaves, kTreeWaves and kSchedTreeWaves, the other variants' occupancies, stand in cgrt_variants.h: the launch plans read them)
 
 // uniform_sampling_circle (sampling.h:35-43) on a sample's lens stream (cgrt_rng.hpp): attempt j takes the two draws of the
 // splitmix output z_j = fin64(key + (j + 1) G) -- what Stream::pair returns at position 2j, with the 64-bit multiply of the

@@ -118,6 +118,50 @@ struct DevBuf {  // RAII for device temporaries: freed on every return path
     void *release() { void *q = p; p = nullptr; return q; }
     template <class T> T *as() { return reinterpret_cast<T *>(p); }
 };
+// Host staging of a *_host entry point: device copies of its inputs, device room for its outputs, and after the call the wait
+// and the copies back.  A failed allocation or upload is kept (error()) and makes the later ones no-ops; all is freed on return.
+class HostStage {
+    struct Back { void *host; const void *dev; size_t bytes; };
+    std::vector<void *> bufs;
+    std::vector<Back> backs;
+    int rc_ = CGRT_OK;
+    void *alloc(size_t bytes, const void *from, bool zeroed) {
+        void *p = nullptr;
+        if (rc_) return nullptr;
+        hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
+        if (e == hipSuccess) bufs.push_back(p);
+        if (e == hipSuccess && from) e = hipMemcpy(p, from, bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess && zeroed) e = hipMemset(p, 0, bytes);
+        if (e != hipSuccess) rc_ = fail(CGRT_ERR_DEVICE, std::string("host staging: ") + hipGetErrorString(e));
+        return rc_ ? nullptr : p;
+    }
+public:
+    HostStage() = default;
+    HostStage(const HostStage &) = delete;
+    HostStage &operator=(const HostStage &) = delete;
+    ~HostStage() { for (void *p : bufs) (void)hipFree(p); }
+    int error() const { return rc_; }
+    // the device copy of `bytes` at host (nullptr where host is: an optional input stays null)
+    template <class T> T *in(const T *host, size_t bytes) { return host ? static_cast<T *>(alloc(bytes, host, false)) : nullptr; }
+    // device room for an output, copied to host by finish (nullptr where host is: an optional output stays null) ...
+    template <class T> T *out(T *host, size_t bytes, bool zeroed = false) { return host ? out_always(host, bytes, zeroed) : nullptr; }
+    // ... and for one the kernels write whether the caller wants it or not
+    template <class T> T *out_always(T *host, size_t bytes, bool zeroed = false) {
+        T *p = static_cast<T *>(alloc(bytes, nullptr, zeroed));
+        if (p && host) backs.push_back({host, p, bytes});
+        return p;
+    }
+    // after the call that returned rc: waits for the kernels and, only if all went well, copies the outputs back
+    int finish(int rc) {
+        if (rc == CGRT_OK) {
+            const hipError_t e = hipDeviceSynchronize();
+            if (e != hipSuccess) rc = fail(CGRT_ERR_DEVICE, std::string("kernel: ") + hipGetErrorString(e));
+        }
+        if (rc == CGRT_OK)
+            for (const Back &b : backs) HIP_TRY(hipMemcpy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost));
+        return rc;
+    }
+};
 
 #include "cgrt_tile_order.hpp"
 
@@ -543,90 +587,11 @@ int cgrt_scene_tree_dump(const cgrt_scene *s, int t, int32_t *node_lr_size, int3
 
 // ---- LDS of a launch ----
 // A workgroup may use at most a CU's LDS (MI355X: 160 KiB): the kernel's static __shared__ bytes plus the dynamic bytes of
-// the launch.  Each launch family's dynamic bytes come from one function below, and every launch goes through
+// the launch.  Each launch family's dynamic bytes come from one function of cgrt_variants.h, and every launch goes through
 // launch_checked, which refuses a launch that would not fit (CGRT_ERR_LIMIT, naming the launch and the bytes) and asks for
-// more than the default 64 KiB where needed.  The static bytes are the compiler's (hipFuncGetAttributes); the static_asserts
-// use kStaticLdsAllowance.
-static constexpr size_t kStaticLdsAllowance = 512;  // the eye kernels have 336 B (ROCm 7.2): wg_cnt, tile_entry, tl_rays, ...
+// more than the default 64 KiB where needed.  The static bytes are the compiler's (hipFuncGetAttributes).
 static_assert(sizeof(BezLds) == kBezLdsBytes, "cgrt_wg_lds.h: BezLds");
 static_assert(sizeof(uint2) == 8 && sizeof(Pending) == kPendDoubles * sizeof(double) + 2 * sizeof(uint32_t), "cgrt_wg_lds.h: stack entries");
-
-// The template flags of a trace_grid_kernel / trace_grid_sched_kernel instantiation
-struct EyeFlags {
-    bool trees, bez, dof, glass, sph, stats, hps, spill, hfonly;
-    int nt;  // threads per workgroup: 256 (32x8-pixel tiles) or 64 (Bezier scenes: one-wave workgroups on 16x4 tiles)
-    bool diff = false;  // the terminal-diffuse body (sphere scenes' class-3 tiles)
-    bool pair = false;  // the sphere loop two spheres a trip, class-3 tiles by the diffuse body in the same launch (glass sphere scenes)
-    bool start = false;  // a PAIR variant's twin that reads the relay's start table and serves as its cost probe (cgrt_relay.h)
-    bool ltab = false;  // a thin-lens PAIR variant's twin whose full and parking bodies read the lens table (cgrt_lens_stage.h)
-    constexpr int id() const {
-        return (int)trees | (int)bez << 1 | (int)dof << 2 | (int)glass << 3 | (int)sph << 4 | (int)stats << 5 | (int)hps << 6 |
-               (int)spill << 7 | (int)hfonly << 8 | (nt == 64 ? 1 << 9 : 0) | (int)diff << 10 | (int)pair << 11 | (int)start << 12 | (int)ltab << 13;
-    }
-};
-// image order, the probe and the scheduled form: Bezier scenes share the tree-capable variants (one-wave workgroups)
-static constexpr EyeFlags image_flags(bool trees, bool bez, bool dof, bool glass, bool sph, bool stats) {
-    return {trees, bez, dof, glass, sph, stats, false, false, false, bez ? 64 : kThreads};
-}
-// the sphere loop reading the objects beyond the LDS list from `objs`
-static constexpr EyeFlags spill_sph_flags(bool dof, bool glass) { return {false, false, dof, glass, true, false, false, true, false, kThreads}; }
-// the most general body (trees, Bezier, pending rays): the Hitpoint capture (hps) and the eye pass's SPILL form
-static constexpr EyeFlags general_flags(bool dof, bool hps, bool spill) { return {true, true, dof, true, false, false, hps, spill, false, kThreads}; }
-// the light tiles: no Bezier or pending-ray code; with trees beside bump-mapped planes, or only their height-field walk (hfonly)
-static constexpr EyeFlags light_flags(bool trees, bool dof, bool hfonly) { return {trees, false, dof, false, false, false, false, false, hfonly, kThreads}; }
-// the diffuse tiles of a sphere-only scene: the sphere loop, every ray ends at its first hit
-static constexpr EyeFlags diffuse_flags(bool dof) { return {false, false, dof, false, true, false, false, false, false, kThreads, true}; }
-
-// Dynamic LDS of a launch: the total of the layout its kernel carves up (wg_lds, cgrt_wg_lds.h) for the variant's flags.
-static constexpr WgLdsAsk eye_ask(const EyeFlags &f) { return wg_ask_trace(f.nt, f.trees, f.bez, f.glass, f.spill, f.hfonly); }
-static constexpr size_t eye_lds(const EyeFlags &f, size_t resident, size_t cached_nodes, bool wide) {
-    return wg_lds(eye_ask(f), resident, cached_nodes, wide).total;
-}
-static size_t eye_lds(const EyeFlags &f, const DeviceScene &d) { return wg_lds(eye_ask(f), d).total; }
-// primary_walk_kernel stages `staged` objects; photon_trace_kernel takes the stack where photon_lds_stack asks for it
-static constexpr size_t primary_walk_lds(size_t staged) { return wg_lds(wg_ask_primary_walk(), staged, 0, true).total; }
-static constexpr size_t photon_lds(size_t resident, bool spill, bool bez, bool wide_stack) {
-    return wg_lds(wg_ask_photon(bez, spill), resident, 0, wide_stack).total;
-}
-
-// The template flags of a trace_rays_kernel instantiation (cgrt_rays.hpp)
-struct RayFlags {
-    bool trees, bez, glass, sph, stats, spill, first;
-    int nt;  // threads per workgroup: 256, or 64 (Bezier scenes: one BezLds per workgroup, as the eye pass's one-wave form)
-    constexpr int id() const {
-        return (int)trees | (int)bez << 1 | (int)glass << 2 | (int)sph << 3 | (int)stats << 4 | (int)spill << 5 | (int)first << 6 |
-               (nt == 64 ? 1 << 7 : 0);
-    }
-};
-static constexpr WgLdsAsk rays_ask(const RayFlags &f) { return wg_ask_trace(f.nt, f.trees, f.bez, f.glass, f.spill, false); }
-static constexpr size_t rays_lds(const RayFlags &f, size_t resident, size_t cached_nodes, bool wide) {
-    return wg_lds(rays_ask(f), resident, cached_nodes, wide).total;
-}
-static size_t rays_lds(const RayFlags &f, const DeviceScene &d) { return wg_lds(rays_ask(f), d).total; }
-
-static constexpr bool fits_lds(size_t dyn) { return dyn + kStaticLdsAllowance <= kLdsBytes; }
-// Every launch that stages kLdsObjsMax objects fits beside its other LDS (the general variant lowers its count instead):
-// the eye pass without SPILL, with and without glass (the light variants are the latter), ...
-static_assert(fits_lds(eye_lds(image_flags(true, false, false, true, false, false), kLdsObjsMax, kNodeCache, true)) &&
-                  fits_lds(eye_lds(image_flags(true, false, false, false, false, false), kLdsObjsMax, kNodeCache, true)),
-              "eye pass, 256-thread and light variants");
-// ... the one-wave Bezier variants, the sphere-only SPILL variant, ...
-static_assert(fits_lds(eye_lds(image_flags(true, true, false, true, false, false), kLdsObjsMax, kNodeCache, true)),
-              "eye pass, one-wave Bezier variants");
-static_assert(fits_lds(eye_lds(spill_sph_flags(false, true), kLdsObjsMax, 0, false)), "eye pass, SPILL_SPH");
-// ... primary_walk_kernel (all objects staged when it finishes units; it runs only when none is spilled), the photon launches
-static_assert(fits_lds(primary_walk_lds(kLdsObjsMax)), "primary_walk_kernel");
-static_assert(fits_lds(photon_lds(kLdsObjsMax, true, true, false)), "photon_trace_kernel");
-// ... and the ray-list launches: trees with and without pending rays, the one-wave Bezier form, the sphere loop with SPILL
-static_assert(fits_lds(rays_lds(RayFlags{true, false, true, false, false, false, false, kThreads}, kLdsObjsMax, kNodeCache, true)) &&
-                  fits_lds(rays_lds(RayFlags{true, false, false, false, false, false, false, kThreads}, kLdsObjsMax, kNodeCache, true)) &&
-                  fits_lds(rays_lds(RayFlags{true, true, true, false, false, false, false, 64}, kLdsObjsMax, kNodeCache, true)) &&
-                  fits_lds(rays_lds(RayFlags{false, false, true, true, false, true, false, kThreads}, kLdsObjsMax, 0, false)),
-              "trace_rays_kernel");
-static_assert(fits_lds(rays_lds(RayFlags{true, true, true, false, false, true, false, kThreads}, 600, kNodeCache, false)),
-              "trace_rays_kernel, general variant: resident objects");
-// The general variant keeps at least 600 objects resident whatever the scene.
-static_assert(fits_lds(eye_lds(general_flags(false, false, true), 600, kNodeCache, false)), "general variant: resident objects");
 
 static size_t device_lds_bytes(int device) {
     static std::mutex mu;
@@ -676,8 +641,16 @@ static int launch_checked(void (*fn)(P...), const char *what, int device, dim3 g
     return CGRT_OK;
 }
 
-// The instantiations of the eye kernels that are launched -- only these are compiled (every combination of the flags would
-// multiply the library's build time and size).
+// A dispatch table's row for a variant's flags, by id() (the eye kernels' table below, the ray-list kernels' in
+// cgrt_ray_queries.hpp); nullptr: no such instantiation was compiled
+template <class Row, size_t N, class Flags>
+static const Row *variant_row(const Row (&table)[N], const Flags &f) {
+    for (const Row &e : table)
+        if (e.id == f.id()) return &e;
+    return nullptr;
+}
+
+// The instantiations of the eye kernels that are launched: CGRT_EYE_VARIANTS (cgrt_variants.h), expanded.
 using GridKernel = void (*)(DeviceScene, GridParams, float *, uint32_t *, unsigned long long *, HitpointSink);
 using SchedKernel = void (*)(DeviceScene, GridParams, float *, uint32_t *, unsigned long long *);
 struct EyeKernels {
@@ -685,55 +658,19 @@ struct EyeKernels {
     GridKernel grid;    // trace_grid_kernel
     SchedKernel sched;  // trace_grid_sched_kernel where the scheduled form runs these flags, else nullptr
 };
-template <int T, int B, int D, int G, int P, int S, int H = 0, int NT = kThreads, int SP = 0, int HF = 0, int DF = 0, int PR = 0, int ST = 0, int LT = 0>
-static constexpr EyeKernels gk() {  // trace_grid_kernel only
-    return {EyeFlags{T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, SP != 0, HF != 0, NT, DF != 0, PR != 0, ST != 0, LT != 0}.id(),
-            &trace_grid_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, NT, SP != 0, HF != 0, DF != 0, PR != 0, ST != 0, LT != 0>, nullptr};
+template <bool SCHED, bool T, bool B, bool D, bool G, bool P, bool S, int NT>
+static constexpr SchedKernel sched_kernel() {
+    if constexpr (SCHED) return &trace_grid_sched_kernel<T, B, D, G, P, S, NT>;
+    else return nullptr;
 }
-template <int T, int B, int D, int G, int P, int S, int NT = kThreads>
-static constexpr EyeKernels gsk() {  // both forms
-    EyeKernels e = gk<T, B, D, G, P, S, 0, NT>();
-    e.sched = &trace_grid_sched_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, NT>;
-    return e;
-}
-//                        TREES BEZ DOF GLASS SPH STATS [HPS NT SPILL HFONLY DIFF PAIR START LTAB]
-static const EyeKernels kEyeKernels[] = {
-    // image order, the probe and the scheduled form (the light variants are the tree and plain ones without GLASS or STATS)
-    gsk<1, 1, 0, 0, 0, 0, 64>(), gsk<1, 1, 0, 1, 0, 0, 64>(), gsk<1, 1, 1, 0, 0, 0, 64>(), gsk<1, 1, 1, 1, 0, 0, 64>(),
-    gsk<1, 0, 0, 0, 0, 0>(), gsk<1, 0, 0, 1, 0, 0>(), gsk<1, 0, 1, 0, 0, 0>(), gsk<1, 0, 1, 1, 0, 0>(),
-    gsk<1, 0, 0, 0, 0, 1>(), gsk<1, 0, 0, 1, 0, 1>(), gsk<1, 0, 1, 0, 0, 1>(), gsk<1, 0, 1, 1, 0, 1>(),
-    gsk<0, 0, 0, 0, 1, 0>(), gsk<0, 0, 0, 1, 1, 0>(), gsk<0, 0, 1, 0, 1, 0>(), gsk<0, 0, 1, 1, 1, 0>(),
-    gsk<0, 0, 0, 0, 0, 0>(), gsk<0, 0, 0, 1, 0, 0>(), gsk<0, 0, 1, 0, 0, 0>(), gsk<0, 0, 1, 1, 0, 0>(),
-    // SPILL: spheres, and the general body; the Hitpoint capture (general, HPS) with and without SPILL
-    gk<0, 0, 0, 0, 1, 0, 0, 256, 1>(), gk<0, 0, 0, 1, 1, 0, 0, 256, 1>(), gk<0, 0, 1, 0, 1, 0, 0, 256, 1>(), gk<0, 0, 1, 1, 1, 0, 0, 256, 1>(),
-    gk<1, 1, 0, 1, 0, 0, 0, 256, 1>(), gk<1, 1, 1, 1, 0, 0, 0, 256, 1>(),
-    gk<1, 1, 0, 1, 0, 0, 1, 256, 0>(), gk<1, 1, 1, 1, 0, 0, 1, 256, 0>(), gk<1, 1, 0, 1, 0, 0, 1, 256, 1>(), gk<1, 1, 1, 1, 0, 0, 1, 256, 1>(),
-    // light tiles beside bump-mapped planes that need only the height-field walk
-    gk<1, 0, 0, 0, 0, 0, 0, 256, 0, 1>(), gk<1, 0, 1, 0, 0, 0, 0, 256, 0, 1>(),
-    // diffuse tiles of sphere-only scenes (class 3 of the tile order)
-    gk<0, 0, 0, 0, 1, 0, 0, 256, 0, 0, 1>(), gk<0, 0, 1, 0, 1, 0, 0, 256, 0, 0, 1>(),
-    // glass sphere scenes in image order: the pair loop, the class-3 tiles' diffuse body inside
-    gk<0, 0, 0, 1, 1, 0, 0, 256, 0, 0, 0, 1>(), gk<0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 1>(),
-    // ... and their twins for a launch whose relay starts by cost: the start table's map, the cost probe
-    gk<0, 0, 0, 1, 1, 0, 0, 256, 0, 0, 0, 1, 1>(), gk<0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 1, 1>(),
-    // ... and the thin-lens ones' twins, plain and START, for a launch with a lens table: the bodies that read it
-    gk<0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 1, 0, 1>(), gk<0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 1, 1, 1>(),
-};
-static const EyeKernels *eye_kernels(const EyeFlags &f) {
-    for (const EyeKernels &e : kEyeKernels)
-        if (e.id == f.id()) return &e;
-    return nullptr;
-}
+#define CGRT_X(T, B, D, G, P, S, H, NT, SP, HF, DF, PR, ST, LT, SCHED)                                                                      \
+    {EyeFlags{T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, SP != 0, HF != 0, NT, DF != 0, PR != 0, ST != 0, LT != 0}.id(),       \
+     &trace_grid_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, NT, SP != 0, HF != 0, DF != 0, PR != 0, ST != 0, LT != 0>, \
+     sched_kernel<SCHED != 0, T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, NT>()},
+static const EyeKernels kEyeKernels[] = {CGRT_EYE_VARIANTS(CGRT_X)};
+#undef CGRT_X
+static const EyeKernels *eye_kernels(const EyeFlags &f) { return variant_row(kEyeKernels, f); }
 
-// The launch's copy of the scene with `resident` objects in LDS.  A run of planes tested as a group (plane_run) is read from
-// the LDS list, so it ends inside it: a shorter run is the same test over fewer planes.
-static DeviceScene with_resident(const DeviceScene &d, int resident) {
-    DeviceScene c = d;
-    c.n_lds = resident;
-    if (c.prun_end > resident) c.prun_end = resident;
-    if (c.prun_end - c.prun_begin < 3) c.prun_begin = c.prun_end = 0;
-    return c;
-}
 // Objects the most general variant (the Hitpoint capture, or the eye pass's SPILL form) keeps resident: the scene's n_lds when
 // its list fits beside the variant's other LDS, else as many as fit beside one staging record per wave (the SPILL variant
 // then reads the rest from `objs`).
@@ -842,12 +779,12 @@ static int launch_eye(const EyeLaunch &L, bool sched, int device, const GridPara
     return fail(CGRT_ERR_UNSUPPORTED, std::string(L.what()) + ": no kernel built for this variant");
 }
 
-static int check_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *g) {
-    if (!s || !cam || !g) return fail(CGRT_ERR_INVALID, "null argument");
-    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+// A grid's rows, samples and stripes and the camera's lens: what an eye pass reads (traced: spp_total and max_depth too) and
+// what cgrt_camera_rays does
+static int check_grid_rows(const cgrt_camera *cam, const cgrt_grid *g, bool traced) {
     if (g->width <= 0 || g->height <= 0 || g->rows <= 0) return fail(CGRT_ERR_INVALID, "empty grid");
-    if (g->spp <= 0 || g->spp_total <= 0 || g->sample_offset < 0) return fail(CGRT_ERR_INVALID, "bad sample range");
-    if (g->max_depth < 1 || g->max_depth > kMaxDepth) return fail(CGRT_ERR_INVALID, "max_depth must be 1..5");
+    if (g->spp <= 0 || (traced && g->spp_total <= 0) || g->sample_offset < 0) return fail(CGRT_ERR_INVALID, "bad sample range");
+    if (traced && (g->max_depth < 1 || g->max_depth > kMaxDepth)) return fail(CGRT_ERR_INVALID, "max_depth must be 1..5");
     if (g->stripe_nranks > 1) {
         if (g->stripe_rows <= 0 || g->stripe_rows % kTileH != 0)
             return fail(CGRT_ERR_INVALID, "stripe_rows must be a positive multiple of 8");
@@ -857,6 +794,11 @@ static int check_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_gr
     }
     if (!(cam->lens_radius >= 0)) return fail(CGRT_ERR_INVALID, "lens_radius must be >= 0");
     return CGRT_OK;
+}
+static int check_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *g) {
+    if (!s || !cam || !g) return fail(CGRT_ERR_INVALID, "null argument");
+    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+    return check_grid_rows(cam, g, true);
 }
 
 // ---- cgrt_trace_grid's stages ----
@@ -1206,509 +1148,6 @@ int cgrt_trace_grid_diffuse_variant(const cgrt_scene *s, const cgrt_camera *cam,
 }  // extern "C"
 
 
-// =====================================================================================================
-// caller-supplied rays (cgrt_rays.hpp)
-// =====================================================================================================
-// The instantiations of trace_rays_kernel that are launched (rays_launch below) -- only these are compiled.
-using RaysKernel = void (*)(DeviceScene, RayParams, unsigned long long *);
-struct RaysKernels {
-    int id;  // RayFlags::id()
-    RaysKernel fn;
-};
-template <int T, int B, int G, int P, int S, int SP, int F, int NT = kThreads>
-static constexpr RaysKernels rk() {
-    return {RayFlags{T != 0, B != 0, G != 0, P != 0, S != 0, SP != 0, F != 0, NT}.id(),
-            &trace_rays_kernel<T != 0, B != 0, G != 0, P != 0, S != 0, SP != 0, F != 0, NT>};
-}
-//                          TREES BEZ GLASS SPH STATS SPILL FIRST [NT]
-static const RaysKernels kRaysKernels[] = {
-    // the full trace: Bezier scenes (one-wave workgroups), meshes / bump floors (with and without STATS), spheres, plain scenes
-    rk<1, 1, 0, 0, 0, 0, 0, 64>(), rk<1, 1, 1, 0, 0, 0, 0, 64>(),
-    rk<1, 0, 0, 0, 0, 0, 0>(), rk<1, 0, 1, 0, 0, 0, 0>(), rk<1, 0, 0, 0, 1, 0, 0>(), rk<1, 0, 1, 0, 1, 0, 0>(),
-    rk<0, 0, 0, 1, 0, 0, 0>(), rk<0, 0, 1, 1, 0, 0, 0>(), rk<0, 0, 0, 0, 0, 0, 0>(), rk<0, 0, 1, 0, 0, 0, 0>(),
-    // SPILL: spheres, and the general body
-    rk<0, 0, 0, 1, 0, 1, 0>(), rk<0, 0, 1, 1, 0, 1, 0>(), rk<1, 1, 1, 0, 0, 1, 0>(),
-    // the nearest-hit query: no GLASS variants
-    rk<1, 1, 0, 0, 0, 0, 1, 64>(), rk<1, 0, 0, 0, 0, 0, 1>(), rk<1, 0, 0, 0, 1, 0, 1>(), rk<0, 0, 0, 1, 0, 0, 1>(),
-    rk<0, 0, 0, 0, 0, 0, 1>(), rk<0, 0, 0, 1, 0, 1, 1>(), rk<1, 1, 0, 0, 0, 1, 1>(),
-};
-static const RaysKernels *rays_kernels(const RayFlags &f) {
-    for (const RaysKernels &e : kRaysKernels)
-        if (e.id == f.id()) return &e;
-    return nullptr;
-}
-// The instantiations of capture_rays_kernel: one for every full-trace entry above without STATS (rays_launch(stats = false,
-// first = false) chooses among exactly these).
-using CaptureKernel = void (*)(DeviceScene, RayParams, RaySink);
-struct CaptureKernels {
-    int id;  // RayFlags::id() of the trace_rays_kernel it is the capture form of
-    CaptureKernel fn;
-};
-template <int T, int B, int G, int P, int SP, int NT = kThreads>
-static constexpr CaptureKernels ck() {
-    return {RayFlags{T != 0, B != 0, G != 0, P != 0, false, SP != 0, false, NT}.id(),
-            &capture_rays_kernel<T != 0, B != 0, G != 0, P != 0, SP != 0, NT>};
-}
-//                                TREES BEZ GLASS SPH SPILL [NT]
-static const CaptureKernels kCaptureKernels[] = {
-    ck<1, 1, 0, 0, 0, 64>(), ck<1, 1, 1, 0, 0, 64>(),
-    ck<1, 0, 0, 0, 0>(), ck<1, 0, 1, 0, 0>(),
-    ck<0, 0, 0, 1, 0>(), ck<0, 0, 1, 1, 0>(), ck<0, 0, 0, 0, 0>(), ck<0, 0, 1, 0, 0>(),
-    // SPILL: spheres, and the general body
-    ck<0, 0, 0, 1, 1>(), ck<0, 0, 1, 1, 1>(), ck<1, 1, 1, 0, 1>(),
-};
-static const CaptureKernels *capture_kernels(const RayFlags &f) {
-    for (const CaptureKernels &e : kCaptureKernels)
-        if (e.id == f.id()) return &e;
-    return nullptr;
-}
-
-// One launch of trace_rays_kernel: the flags chosen from the scene's traits the way eye_launch chooses the eye pass's
-struct RaysLaunch {
-    RayFlags k;
-    DeviceScene dev;  // the general variant's copy holds its resident objects (with_resident)
-    size_t lds;
-    const char *what() const {
-        return k.spill ? (k.sph ? "ray list, SPILL (spheres)" : "ray list, SPILL (general)") : (k.bez ? "ray list (Bezier)" : "ray list");
-    }
-};
-static RaysLaunch rays_launch(const cgrt_scene *s, int max_depth, bool stats, bool first) {
-    const DeviceScene &d = s->dev;
-    const bool glass = !first && d.has_glass != 0 && max_depth > 1;
-    const bool spill = d.n_objs > d.n_lds;
-    RaysLaunch L;
-    L.dev = d;
-    if (spill && !d.all_spheres) {
-        // the most general body, with as many objects resident as fit beside its other LDS; the rest are read from `objs`
-        L.k = RayFlags{true, true, !first, false, false, true, first, kThreads};
-        const RaysKernels *e = rays_kernels(L.k);
-        const size_t st = e ? kernel_static_lds(reinterpret_cast<const void *>(e->fn)) : kStaticLdsAllowance;
-        const size_t lim = device_lds_bytes(s->device);
-        if (rays_lds(L.k, d) + st > lim) {
-            const long long room = (long long)lim - (long long)(st + rays_lds(L.k, with_resident(d, 0)));
-            L.dev = with_resident(d, (int)std::max(0ll, std::min(room / (long long)sizeof(ObjRec), (long long)d.n_lds)));
-        }
-    } else if (spill) {
-        L.k = RayFlags{false, false, glass, true, false, true, first, kThreads};
-    } else {
-        const bool bez = d.has_bezier != 0, trees = d.has_mesh != 0 || bez;
-        L.k = RayFlags{trees, bez, glass, !trees && d.all_spheres != 0, stats && d.has_mesh != 0 && !bez, false, first, bez ? 64 : kThreads};
-    }
-    L.lds = rays_lds(L.k, L.dev);
-    return L;
-}
-
-static constexpr long long kMaxRays = 1ll << 36;  // blocks of 64 rays are numbered in 32 bits with room for the waves' last draws
-
-static int check_rays(const cgrt_scene *s, const cgrt_rays *r, const cgrt_ray_results *out) {
-    if (!s || !r || !out) return fail(CGRT_ERR_INVALID, "null argument");
-    if (r->n < 0) return fail(CGRT_ERR_INVALID, "negative ray count");
-    if (r->n > 0 && (!r->org3 || !r->dir3)) return fail(CGRT_ERR_INVALID, "null org3 / dir3");
-    if ((out->acc3 || out->nhit) && (r->max_depth < 1 || r->max_depth > kMaxDepth)) return fail(CGRT_ERR_INVALID, "max_depth must be 1..5");
-    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
-    if (r->n > kMaxRays) return fail(CGRT_ERR_LIMIT, "more than 2^36 rays in one call");
-    return CGRT_OK;
-}
-// What the Hitpoint capture reads of a ray set: every ray is traced in full, so max_depth always counts
-static int check_capture_rays(const cgrt_scene *s, const cgrt_rays *r) {
-    if (!s || !r) return fail(CGRT_ERR_INVALID, "null argument");
-    if (r->n < 0) return fail(CGRT_ERR_INVALID, "negative ray count");
-    if (r->n > 0 && (!r->org3 || !r->dir3)) return fail(CGRT_ERR_INVALID, "null org3 / dir3");
-    if (r->max_depth < 1 || r->max_depth > kMaxDepth) return fail(CGRT_ERR_INVALID, "max_depth must be 1..5");
-    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
-    if (r->n > kMaxRays) return fail(CGRT_ERR_LIMIT, "more than 2^36 rays in one call");
-    return CGRT_OK;
-}
-// The rows / stripes / samples of a grid that cgrt_camera_rays reads (max_depth, spp_total and flags are not looked at)
-static int check_camera_rays(const cgrt_camera *cam, const cgrt_grid *g) {
-    if (!cam || !g) return fail(CGRT_ERR_INVALID, "null argument");
-    if (g->width <= 0 || g->height <= 0 || g->rows <= 0) return fail(CGRT_ERR_INVALID, "empty grid");
-    if (g->spp <= 0 || g->sample_offset < 0) return fail(CGRT_ERR_INVALID, "bad sample range");
-    if (g->stripe_nranks > 1) {
-        if (g->stripe_rows <= 0 || g->stripe_rows % kTileH != 0)
-            return fail(CGRT_ERR_INVALID, "stripe_rows must be a positive multiple of 8");
-        if (g->stripe_rank < 0 || g->stripe_rank >= g->stripe_nranks) return fail(CGRT_ERR_INVALID, "bad stripe_rank");
-    } else if (g->row_offset < 0) {
-        return fail(CGRT_ERR_INVALID, "bad row_offset");
-    }
-    if (!(cam->lens_radius >= 0)) return fail(CGRT_ERR_INVALID, "lens_radius must be >= 0");
-    if ((long long)g->spp * g->rows > (1ll << 38) / g->width) return fail(CGRT_ERR_LIMIT, "more than 2^38 camera rays in one call");
-    return CGRT_OK;
-}
-
-// The instantiations of occlusion_rays_kernel (cgrt_occlusion.hpp) that are launched: one for every nearest-hit entry of
-// kRaysKernels, whose launch plan (rays_launch with first = true) cgrt_occlusion_rays shares -- flags, resident objects, LDS.
-using OcclusionKernel = void (*)(DeviceScene, OccParams, unsigned long long *);
-struct OcclusionKernels {
-    int id;  // RayFlags::id() of the nearest-hit query's launch for the same scene
-    OcclusionKernel fn;
-};
-template <int T, int B, int P, int S, int SP, int NT = kThreads>
-static constexpr OcclusionKernels ok() {
-    return {RayFlags{T != 0, B != 0, false, P != 0, S != 0, SP != 0, true, NT}.id(),
-            &occlusion_rays_kernel<T != 0, B != 0, P != 0, S != 0, SP != 0, NT>};
-}
-//                                    TREES BEZ SPH STATS SPILL [NT]
-static const OcclusionKernels kOcclusionKernels[] = {
-    ok<1, 1, 0, 0, 0, 64>(), ok<1, 0, 0, 0, 0>(), ok<1, 0, 0, 1, 0>(), ok<0, 0, 1, 0, 0>(),
-    ok<0, 0, 0, 0, 0>(), ok<0, 0, 1, 0, 1>(), ok<1, 1, 0, 0, 1>(),
-};
-static const OcclusionKernels *occlusion_kernels(const RayFlags &f) {
-    for (const OcclusionKernels &e : kOcclusionKernels)
-        if (e.id == f.id()) return &e;
-    return nullptr;
-}
-static int check_occlusion(const cgrt_scene *s, const cgrt_rays *r, const cgrt_occlusion *occ) {
-    if (!s || !r || !occ) return fail(CGRT_ERR_INVALID, "null argument");
-    if (r->n < 0) return fail(CGRT_ERR_INVALID, "negative ray count");
-    if (r->n > 0 && (!r->org3 || !r->dir3)) return fail(CGRT_ERR_INVALID, "null org3 / dir3");
-    if (!occ->occluded) return fail(CGRT_ERR_INVALID, "null occluded");
-    if (r->n > kMaxRays) return fail(CGRT_ERR_LIMIT, "more than 2^36 rays in one call");
-    if (r->n > 0 && !s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");  // (no rays: nothing is looked at)
-    return CGRT_OK;
-}
-
-extern "C" {
-
-int cgrt_trace_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_results *out, uint64_t *counters, void *stream) {
-    int rc = check_rays(s, rays, out);
-    if (rc) return rc;
-    if (rays->n == 0) return CGRT_OK;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    ON_DEVICE(s->device);
-    const bool first = !out->acc3 && !out->nhit;  // nearest-hit query: one scene walk per ray
-    const RaysLaunch L = rays_launch(s, rays->max_depth, (rays->flags & CGRT_RAYS_STATS) != 0, first);
-    const RaysKernels *e = rays_kernels(L.k);
-    if (!e) return fail(CGRT_ERR_UNSUPPORTED, std::string(L.what()) + ": no kernel built for this variant");
-    // the queue's head lives in the handle's launch scratch (launches on one handle are ordered by the caller)
-    // (and, where the normals' signs are recounted below without the caller asking for hit_obj, the winners)
-    const bool sign_pass = out->hit_normal3 && L.dev.has_wide && !(rays->flags & CGRT_RAYS_NO_SIGN_PASS);
-    const size_t own_obj = sign_pass && !out->hit_obj ? (size_t)rays->n * sizeof(int32_t) : 0;
-    if (s->scratch.need(256 + own_obj) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(CGRT_ERR_DEVICE, "cannot allocate launch scratch (ray queue)");
-    }
-    HIP_TRY(hipMemsetAsync(s->scratch.p, 0, sizeof(unsigned int), st));
-    RayParams rp{};
-    rp.n = rays->n;
-    rp.org = rays->org3;
-    rp.dir = rays->dir3;
-    rp.keys = reinterpret_cast<const unsigned long long *>(rays->keys);
-    rp.first_index = rays->first_index;
-    rp.seed = rays->seed;
-    rp.max_depth = rays->max_depth;
-    rp.acc = out->acc3;
-    rp.nhit = out->nhit;
-    rp.hit_obj = own_obj ? reinterpret_cast<int32_t *>(reinterpret_cast<unsigned char *>(s->scratch.p) + 256) : out->hit_obj;
-    rp.hit_t = out->hit_t;
-    rp.hit_normal = out->hit_normal3;
-    rp.queue = reinterpret_cast<unsigned int *>(s->scratch.p);
-    // persistent workgroups: at most two chips' worth at the kernel's occupancy, fewer when the rays are few
-    const long long waves_per_wg = L.k.nt / 64, n_blocks = (rays->n + 63) / 64;
-    const long long chip = (long long)s->n_cu * 4 * (L.k.bez ? kBezWaves : (L.k.trees ? kTreeWaves : 4)) / waves_per_wg;
-    const long long wgs = std::max(1ll, std::min((n_blocks + waves_per_wg - 1) / waves_per_wg, 2 * chip));
-    if ((rc = launch_checked(e->fn, L.what(), s->device, dim3((unsigned)wgs), dim3((unsigned)L.k.nt), L.lds, st, L.dev, rp,
-                             reinterpret_cast<unsigned long long *>(counters))))
-        return rc;
-    // an opaque mesh's normal gets the reference's sign (ray_normal_sign_kernel)
-    if (sign_pass) hipLaunchKernelGGL(ray_normal_sign_kernel, dim3((unsigned)((rays->n + 255) / 256)), dim3(256), 0, st, L.dev, rp);
-    HIP_TRY(hipGetLastError());
-    return CGRT_OK;
-}
-
-int cgrt_trace_rays_variant(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_results *out, char *name, size_t cap) {
-    if (!s || !rays || !name || cap == 0 || (!out && !(rays->flags & CGRT_RAYS_HITPOINTS))) return fail(CGRT_ERR_INVALID, "null argument");
-    if (rays->flags & CGRT_RAYS_HITPOINTS) {  // the capture's launch: out is not looked at
-        if (rays->max_depth < 1 || rays->max_depth > kMaxDepth) return fail(CGRT_ERR_INVALID, "max_depth must be 1..5");
-        if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
-        ON_DEVICE(s->device);
-        const RayFlags k = rays_launch(s, rays->max_depth, false, false).k;
-        std::snprintf(name, cap, "capture_rays_kernel<TREES=%d,BEZ=%d,GLASS=%d,SPH=%d,SPILL=%d,NT=%d>", (int)k.trees, (int)k.bez,
-                      (int)k.glass, (int)k.sph, (int)k.spill, k.nt);
-        return CGRT_OK;
-    }
-    const bool first = !out->acc3 && !out->nhit;
-    if (!first && (rays->max_depth < 1 || rays->max_depth > kMaxDepth)) return fail(CGRT_ERR_INVALID, "max_depth must be 1..5");
-    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
-    ON_DEVICE(s->device);
-    const RayFlags k = rays_launch(s, rays->max_depth, (rays->flags & CGRT_RAYS_STATS) != 0, first).k;
-    std::snprintf(name, cap, "trace_rays_kernel<TREES=%d,BEZ=%d,GLASS=%d,SPH=%d,STATS=%d,SPILL=%d,FIRST=%d,NT=%d>", (int)k.trees, (int)k.bez,
-                  (int)k.glass, (int)k.sph, (int)k.stats, (int)k.spill, (int)k.first, k.nt);
-    return CGRT_OK;
-}
-
-int cgrt_trace_rays_host(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_results *out, uint64_t *counters) {
-    int rc = check_rays(s, rays, out);
-    if (rc) return rc;
-    const size_t n = (size_t)rays->n;
-    if (n == 0) {
-        if (counters) std::memset(counters, 0, CGRT_NCOUNTERS * sizeof(uint64_t));
-        return CGRT_OK;
-    }
-    ON_DEVICE(s->device);
-    DevBuf b_o, b_d, b_k, b_acc, b_nhit, b_obj, b_t, b_n, b_cnt;
-    cgrt_rays dr = *rays;
-    cgrt_ray_results dout{};
-    HIP_TRY(b_o.alloc(n * 24));
-    HIP_TRY(b_d.alloc(n * 24));
-    HIP_TRY(hipMemcpy(b_o.p, rays->org3, n * 24, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b_d.p, rays->dir3, n * 24, hipMemcpyHostToDevice));
-    dr.org3 = b_o.as<double>();
-    dr.dir3 = b_d.as<double>();
-    if (rays->keys) {
-        HIP_TRY(b_k.alloc(n * 8));
-        HIP_TRY(hipMemcpy(b_k.p, rays->keys, n * 8, hipMemcpyHostToDevice));
-        dr.keys = b_k.as<uint64_t>();
-    }
-    if (out->acc3) { HIP_TRY(b_acc.alloc(n * 24)); dout.acc3 = b_acc.as<double>(); }
-    if (out->nhit) { HIP_TRY(b_nhit.alloc(n * 4)); dout.nhit = b_nhit.as<uint32_t>(); }
-    if (out->hit_obj) { HIP_TRY(b_obj.alloc(n * 4)); dout.hit_obj = b_obj.as<int32_t>(); }
-    if (out->hit_t) { HIP_TRY(b_t.alloc(n * 8)); dout.hit_t = b_t.as<double>(); }
-    if (out->hit_normal3) { HIP_TRY(b_n.alloc(n * 24)); dout.hit_normal3 = b_n.as<double>(); }
-    HIP_TRY(b_cnt.alloc(CGRT_NCOUNTERS * sizeof(uint64_t)));
-    HIP_TRY(hipMemset(b_cnt.p, 0, CGRT_NCOUNTERS * sizeof(uint64_t)));
-    rc = cgrt_trace_rays(s, &dr, &dout, b_cnt.as<uint64_t>(), nullptr);
-    if (rc == CGRT_OK) {
-        const hipError_t e = hipDeviceSynchronize();
-        if (e != hipSuccess) rc = fail(CGRT_ERR_DEVICE, std::string("kernel: ") + hipGetErrorString(e));
-    }
-    if (rc == CGRT_OK) {
-        if (out->acc3) HIP_TRY(hipMemcpy(out->acc3, b_acc.p, n * 24, hipMemcpyDeviceToHost));
-        if (out->nhit) HIP_TRY(hipMemcpy(out->nhit, b_nhit.p, n * 4, hipMemcpyDeviceToHost));
-        if (out->hit_obj) HIP_TRY(hipMemcpy(out->hit_obj, b_obj.p, n * 4, hipMemcpyDeviceToHost));
-        if (out->hit_t) HIP_TRY(hipMemcpy(out->hit_t, b_t.p, n * 8, hipMemcpyDeviceToHost));
-        if (out->hit_normal3) HIP_TRY(hipMemcpy(out->hit_normal3, b_n.p, n * 24, hipMemcpyDeviceToHost));
-        if (counters) HIP_TRY(hipMemcpy(counters, b_cnt.p, CGRT_NCOUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
-    return rc;
-}
-
-int cgrt_occlusion_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_occlusion *occ, uint64_t *counters, void *stream) {
-    int rc = check_occlusion(s, rays, occ);
-    if (rc) return rc;
-    if (rays->n == 0) return CGRT_OK;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    ON_DEVICE(s->device);
-    const RaysLaunch L = rays_launch(s, 1, (rays->flags & CGRT_RAYS_STATS) != 0, true);
-    const OcclusionKernels *e = occlusion_kernels(L.k);
-    if (!e) return fail(CGRT_ERR_UNSUPPORTED, std::string(L.what()) + ": no occlusion kernel built for this variant");
-    // the queue's head lives in the handle's launch scratch, as cgrt_trace_rays'
-    if (s->scratch.need(256) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(CGRT_ERR_DEVICE, "cannot allocate launch scratch (ray queue)");
-    }
-    HIP_TRY(hipMemsetAsync(s->scratch.p, 0, sizeof(unsigned int), st));
-    OccParams rp{};
-    rp.n = rays->n;
-    rp.org = rays->org3;
-    rp.dir = rays->dir3;
-    rp.keys = reinterpret_cast<const unsigned long long *>(rays->keys);
-    rp.first_index = rays->first_index;
-    rp.seed = rays->seed;
-    rp.tmax = occ->tmax;
-    rp.occluded = occ->occluded;
-    rp.queue = reinterpret_cast<unsigned int *>(s->scratch.p);
-    rp.skip_transparent = (rays->flags & CGRT_RAYS_SKIP_TRANSPARENT) != 0;
-    // persistent workgroups, sized as cgrt_trace_rays sizes them
-    const long long waves_per_wg = L.k.nt / 64, n_blocks = (rays->n + 63) / 64;
-    const long long chip = (long long)s->n_cu * 4 * (L.k.bez ? kBezWaves : (L.k.trees ? kTreeWaves : 4)) / waves_per_wg;
-    const long long wgs = std::max(1ll, std::min((n_blocks + waves_per_wg - 1) / waves_per_wg, 2 * chip));
-    if ((rc = launch_checked(e->fn, L.what(), s->device, dim3((unsigned)wgs), dim3((unsigned)L.k.nt), L.lds, st, L.dev, rp,
-                             reinterpret_cast<unsigned long long *>(counters))))
-        return rc;
-    HIP_TRY(hipGetLastError());
-    return CGRT_OK;
-}
-
-int cgrt_occlusion_rays_variant(const cgrt_scene *s, const cgrt_rays *rays, char *name, size_t cap) {
-    if (!s || !rays || !name || cap == 0) return fail(CGRT_ERR_INVALID, "null argument");
-    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
-    ON_DEVICE(s->device);
-    const RayFlags k = rays_launch(s, 1, (rays->flags & CGRT_RAYS_STATS) != 0, true).k;
-    std::snprintf(name, cap, "occlusion_rays_kernel<TREES=%d,BEZ=%d,SPH=%d,STATS=%d,SPILL=%d,NT=%d>", (int)k.trees, (int)k.bez, (int)k.sph,
-                  (int)k.stats, (int)k.spill, k.nt);
-    return CGRT_OK;
-}
-
-int cgrt_occlusion_rays_host(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_occlusion *occ, uint64_t *counters) {
-    int rc = check_occlusion(s, rays, occ);
-    if (rc) return rc;
-    const size_t n = (size_t)rays->n;
-    if (n == 0) {
-        if (counters) std::memset(counters, 0, CGRT_NCOUNTERS * sizeof(uint64_t));
-        return CGRT_OK;
-    }
-    ON_DEVICE(s->device);
-    DevBuf b_o, b_d, b_k, b_t, b_occ, b_cnt;
-    cgrt_rays dr = *rays;
-    cgrt_occlusion docc{};
-    HIP_TRY(b_o.alloc(n * 24));
-    HIP_TRY(b_d.alloc(n * 24));
-    HIP_TRY(hipMemcpy(b_o.p, rays->org3, n * 24, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b_d.p, rays->dir3, n * 24, hipMemcpyHostToDevice));
-    dr.org3 = b_o.as<double>();
-    dr.dir3 = b_d.as<double>();
-    if (rays->keys) {
-        HIP_TRY(b_k.alloc(n * 8));
-        HIP_TRY(hipMemcpy(b_k.p, rays->keys, n * 8, hipMemcpyHostToDevice));
-        dr.keys = b_k.as<uint64_t>();
-    }
-    if (occ->tmax) {
-        HIP_TRY(b_t.alloc(n * 8));
-        HIP_TRY(hipMemcpy(b_t.p, occ->tmax, n * 8, hipMemcpyHostToDevice));
-        docc.tmax = b_t.as<double>();
-    }
-    HIP_TRY(b_occ.alloc(n));
-    docc.occluded = b_occ.as<uint8_t>();
-    HIP_TRY(b_cnt.alloc(CGRT_NCOUNTERS * sizeof(uint64_t)));
-    HIP_TRY(hipMemset(b_cnt.p, 0, CGRT_NCOUNTERS * sizeof(uint64_t)));
-    rc = cgrt_occlusion_rays(s, &dr, &docc, b_cnt.as<uint64_t>(), nullptr);
-    if (rc == CGRT_OK) {
-        const hipError_t e = hipDeviceSynchronize();
-        if (e != hipSuccess) rc = fail(CGRT_ERR_DEVICE, std::string("kernel: ") + hipGetErrorString(e));
-    }
-    if (rc == CGRT_OK) {
-        HIP_TRY(hipMemcpy(occ->occluded, b_occ.p, n, hipMemcpyDeviceToHost));
-        if (counters) HIP_TRY(hipMemcpy(counters, b_cnt.p, CGRT_NCOUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
-    return rc;
-}
-
-int cgrt_camera_rays(const cgrt_camera *cam, const cgrt_grid *grid, double *org3, double *dir3, uint64_t *keys, void *stream) {
-    int rc = check_camera_rays(cam, grid);
-    if (rc) return rc;
-    const GridParams g = grid_params(cam, grid);
-    const long long total = (long long)grid->spp * grid->rows * grid->width;
-    hipLaunchKernelGGL(camera_rays_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), g,
-                       org3, dir3, reinterpret_cast<unsigned long long *>(keys), total);
-    HIP_TRY(hipGetLastError());
-    return CGRT_OK;
-}
-
-int cgrt_camera_rays_host(const cgrt_camera *cam, const cgrt_grid *grid, double *org3, double *dir3, uint64_t *keys) {
-    int rc = check_camera_rays(cam, grid);
-    if (rc) return rc;
-    const GridParams g = grid_params(cam, grid);
-    size_t i = 0;
-    for (int k = 0; k < grid->spp; k++)
-        for (int j = 0; j < grid->rows; j++)
-            for (int w = 0; w < grid->width; w++, i++) {
-                const CameraRay c = camera_ray(g, j, w, g.sample_offset + k);
-                for (int a = 0; a < 3; a++) {
-                    if (org3) org3[3 * i + a] = c.o[a];
-                    if (dir3) dir3[3 * i + a] = c.d[a];
-                }
-                if (keys) keys[i] = c.key;
-            }
-    return CGRT_OK;
-}
-
-}  // extern "C"
-
-// ---- hit attributes of caller-supplied rays (cgrt_hit_attr.hpp) ----
-static int check_hit_attributes(const cgrt_scene *s, const cgrt_rays *r, const int32_t *hit_obj, const double *hit_t,
-                                const cgrt_hit_attributes *out) {
-    if (!s || !r || !out || !hit_obj || !hit_t) return fail(CGRT_ERR_INVALID, "null argument");
-    if (r->n < 0) return fail(CGRT_ERR_INVALID, "negative ray count");
-    if (r->n > 0 && (!r->org3 || !r->dir3)) return fail(CGRT_ERR_INVALID, "null org3 / dir3");
-    if (r->n > kMaxRays) return fail(CGRT_ERR_LIMIT, "more than 2^36 rays in one call");
-    if (r->n > 0 && !s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");  // (no rays: nothing is looked at)
-    return CGRT_OK;
-}
-
-// The table behind `prim`: a host-built tree's tris[] are in the reference's leaf order (HostTree::leaf_ids maps it to
-// construction order), a device-built tree's in construction order already (cgrt_devbuild.hpp).
-static int need_tri_ids(const cgrt_scene *s) {
-    if (s->tri_ids.p) return CGRT_OK;
-    size_t total = 0;
-    for (const TreeRec &tr : s->tree_recs) total = std::max(total, (size_t)tr.tri_begin + (size_t)tr.ntris);
-    std::vector<int32_t> ids(std::max(total, (size_t)1), -1);
-    for (size_t ti = 0; ti < s->tree_recs.size(); ti++) {
-        const TreeRec &tr = s->tree_recs[ti];
-        const HostTree &T = s->host.trees[ti];
-        for (size_t k = 0; k < (size_t)tr.ntris; k++)
-            ids[(size_t)tr.tri_begin + k] = T.dev_kind ? (int32_t)k : T.leaf_ids[k];
-    }
-    if (s->tri_ids.need(ids.size() * sizeof(int32_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(CGRT_ERR_DEVICE, "cannot allocate the hit-attribute triangle table");
-    }
-    const hipError_t e = hipMemcpy(s->tri_ids.p, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        s->tri_ids.release();
-        return fail(CGRT_ERR_DEVICE, std::string("hit-attribute triangle table: ") + hipGetErrorString(e));
-    }
-    return CGRT_OK;
-}
-
-extern "C" {
-
-int cgrt_ray_hit_attributes(const cgrt_scene *s, const cgrt_rays *rays, const int32_t *hit_obj, const double *hit_t,
-                            const cgrt_hit_attributes *out, void *stream) {
-    int rc = check_hit_attributes(s, rays, hit_obj, hit_t, out);
-    if (rc) return rc;
-    if (rays->n == 0 || (!out->prim && !out->uv2 && !out->color3 && !out->material2)) return CGRT_OK;
-    ON_DEVICE(s->device);
-    if (out->prim && (rc = need_tri_ids(s))) return rc;
-    HitAttrParams hp{};
-    hp.n = rays->n;
-    hp.org = rays->org3;
-    hp.dir = rays->dir3;
-    hp.hit_obj = hit_obj;
-    hp.hit_t = hit_t;
-    hp.prim = out->prim;
-    hp.uv = out->uv2;
-    hp.color = out->color3;
-    hp.material = out->material2;
-    hp.tri_ids = out->prim ? reinterpret_cast<const int32_t *>(s->tri_ids.p) : nullptr;
-    hipLaunchKernelGGL(ray_hit_attributes_kernel, dim3((unsigned)((rays->n + 255) / 256)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), s->dev, hp);
-    HIP_TRY(hipGetLastError());
-    return CGRT_OK;
-}
-
-int cgrt_ray_hit_attributes_host(const cgrt_scene *s, const cgrt_rays *rays, const int32_t *hit_obj, const double *hit_t,
-                                 const cgrt_hit_attributes *out) {
-    int rc = check_hit_attributes(s, rays, hit_obj, hit_t, out);
-    if (rc) return rc;
-    const size_t n = (size_t)rays->n;
-    if (n == 0) return CGRT_OK;
-    ON_DEVICE(s->device);
-    DevBuf b_o, b_d, b_obj, b_t, b_prim, b_uv, b_col, b_mat;
-    cgrt_rays dr = *rays;
-    cgrt_hit_attributes dout{};
-    HIP_TRY(b_o.alloc(n * 24));
-    HIP_TRY(b_d.alloc(n * 24));
-    HIP_TRY(b_obj.alloc(n * 4));
-    HIP_TRY(b_t.alloc(n * 8));
-    HIP_TRY(hipMemcpy(b_o.p, rays->org3, n * 24, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b_d.p, rays->dir3, n * 24, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b_obj.p, hit_obj, n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b_t.p, hit_t, n * 8, hipMemcpyHostToDevice));
-    dr.org3 = b_o.as<double>();
-    dr.dir3 = b_d.as<double>();
-    dr.keys = nullptr;
-    if (out->prim) { HIP_TRY(b_prim.alloc(n * 4)); dout.prim = b_prim.as<int32_t>(); }
-    if (out->uv2) { HIP_TRY(b_uv.alloc(n * 16)); dout.uv2 = b_uv.as<double>(); }
-    if (out->color3) { HIP_TRY(b_col.alloc(n * 24)); dout.color3 = b_col.as<double>(); }
-    if (out->material2) { HIP_TRY(b_mat.alloc(n * 16)); dout.material2 = b_mat.as<double>(); }
-    rc = cgrt_ray_hit_attributes(s, &dr, b_obj.as<int32_t>(), b_t.as<double>(), &dout, nullptr);
-    if (rc == CGRT_OK) {
-        const hipError_t e = hipDeviceSynchronize();
-        if (e != hipSuccess) rc = fail(CGRT_ERR_DEVICE, std::string("kernel: ") + hipGetErrorString(e));
-    }
-    if (rc == CGRT_OK) {
-        if (out->prim) HIP_TRY(hipMemcpy(out->prim, b_prim.p, n * 4, hipMemcpyDeviceToHost));
-        if (out->uv2) HIP_TRY(hipMemcpy(out->uv2, b_uv.p, n * 16, hipMemcpyDeviceToHost));
-        if (out->color3) HIP_TRY(hipMemcpy(out->color3, b_col.p, n * 24, hipMemcpyDeviceToHost));
-        if (out->material2) HIP_TRY(hipMemcpy(out->material2, b_mat.p, n * 16, hipMemcpyDeviceToHost));
-    }
-    return rc;
-}
-
-}  // extern "C"
-
-
 // Row e: global row h of the frame = local row (stripe / nshares) * S + h % S of share stripe % nshares (the inverse of
 // global_row()); one workgroup column per 256 floats of a row, blockIdx.y = the row.  Rows of absent shares are zeroed.
 __global__ void unpermute_stripes_kernel(const float *__restrict__ shares, int n_present, int nshares, int row_floats, int S,
@@ -1746,45 +1185,6 @@ static int hitpoints_to_host(int rc, double *d_rec, uint64_t n, double *hp10, ui
     return rc;
 }
 
-// The ray-buffer form of hitpoints_device below: capture_rays_kernel over rays' DEVICE arrays (pixel: DEVICE, or nullptr)
-// into a device buffer of `cap` records; *count = Hitpoints produced.  *d_rec_out is hipMalloc'ed here (caller frees) unless
-// cap == 0.  Runs on the null stream and synchronises.
-static int ray_hitpoints_device(const cgrt_scene *s, const cgrt_rays *rays, const int64_t *pixel, uint64_t cap, double **d_rec_out,
-                                uint64_t *count) {
-    *count = 0;
-    if (rays->n == 0) return CGRT_OK;
-    const RaysLaunch L = rays_launch(s, rays->max_depth, false, false);
-    const CaptureKernels *e = capture_kernels(L.k);
-    if (!e) return fail(CGRT_ERR_UNSUPPORTED, std::string(L.what()) + ": no capture kernel built for this variant");
-    DevBuf b_rec, b_cnt;
-    HIP_TRY(b_rec.alloc((cap ? cap : 1) * 10 * sizeof(double)));
-    HIP_TRY(b_cnt.alloc(sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(b_cnt.p, 0, sizeof(unsigned long long)));
-    // the queue's head lives in the handle's launch scratch, as cgrt_trace_rays'
-    if (s->scratch.need(256) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(CGRT_ERR_DEVICE, "cannot allocate launch scratch (ray queue)");
-    }
-    HIP_TRY(hipMemsetAsync(s->scratch.p, 0, sizeof(unsigned int), 0));
-    RayParams rp{};
-    rp.n = rays->n;
-    rp.org = rays->org3;
-    rp.dir = rays->dir3;
-    rp.keys = reinterpret_cast<const unsigned long long *>(rays->keys);
-    rp.first_index = rays->first_index;
-    rp.seed = rays->seed;
-    rp.max_depth = rays->max_depth;
-    rp.queue = reinterpret_cast<unsigned int *>(s->scratch.p);
-    const RaySink sink{b_rec.as<double>(), b_cnt.as<unsigned long long>(), (unsigned long long)cap,
-                       reinterpret_cast<const long long *>(pixel)};
-    const long long waves_per_wg = L.k.nt / 64, n_blocks = (rays->n + 63) / 64;
-    const long long chip = (long long)s->n_cu * 4 * (L.k.bez ? kBezWaves : (L.k.trees ? kTreeWaves : 4)) / waves_per_wg;
-    const long long wgs = std::max(1ll, std::min((n_blocks + waves_per_wg - 1) / waves_per_wg, 2 * chip));
-    int rc = launch_checked(e->fn, L.what(), s->device, dim3((unsigned)wgs), dim3((unsigned)L.k.nt), L.lds, 0, L.dev, rp, sink);
-    if (rc) return rc;
-    return capture_finish("ray hitpoint kernel: ", b_rec, b_cnt, cap, d_rec_out, count);
-}
-
 // Eye pass with Hitpoint capture into a device buffer of `cap` records (10 doubles each); *count = hitpoints produced.
 // *d_rec_out is hipMalloc'ed here (caller frees) unless cap == 0.
 static int hitpoints_device(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, uint64_t cap,
@@ -1808,6 +1208,10 @@ static int hitpoints_device(const cgrt_scene *s, const cgrt_camera *cam, const c
     return capture_finish("hitpoint kernel: ", b_rec, b_cnt, cap, d_rec_out, count);
 }
 
+// caller-supplied rays: the ray-list kernels' table, launch path, checks and entry points
+#include "cgrt_rays_plan.h"
+#include "cgrt_ray_queries.hpp"
+
 extern "C" {
 
 int cgrt_trace_grid_hitpoints(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, double *hp10,
@@ -1819,17 +1223,6 @@ int cgrt_trace_grid_hitpoints(const cgrt_scene *s, const cgrt_camera *cam, const
     double *d_rec = nullptr;
     uint64_t n = 0;
     rc = hitpoints_device(s, cam, grid, cap, &d_rec, &n);
-    return hitpoints_to_host(rc, d_rec, n, hp10, cap, count);
-}
-
-int cgrt_trace_rays_hitpoints(const cgrt_scene *s, const cgrt_rays *rays, double *hp10, uint64_t cap, uint64_t *count) {
-    int rc = check_capture_rays(s, rays);
-    if (rc) return rc;
-    if (!count || (cap > 0 && !hp10)) return fail(CGRT_ERR_INVALID, "null output");
-    ON_DEVICE(s->device);
-    double *d_rec = nullptr;
-    uint64_t n = 0;
-    rc = ray_hitpoints_device(s, rays, nullptr, cap, &d_rec, &n);
     return hitpoints_to_host(rc, d_rec, n, hp10, cap, count);
 }
 
@@ -1853,27 +1246,12 @@ int cgrt_trace_grid_host(const cgrt_scene *s, const cgrt_camera *cam, const cgrt
     if (!rgb) return fail(CGRT_ERR_INVALID, "null rgb");
     ON_DEVICE(s->device);
     const size_t npx = (size_t)grid->rows * grid->width;
-    DevBuf b_rgb, b_nhit, b_cnt;
-    HIP_TRY(b_rgb.alloc(npx * 3 * sizeof(float)));
-    HIP_TRY(b_nhit.alloc(npx * sizeof(uint32_t)));
-    HIP_TRY(b_cnt.alloc(CGRT_NCOUNTERS * sizeof(uint64_t)));
-    float *d_rgb = b_rgb.as<float>();
-    uint32_t *d_nhit = b_nhit.as<uint32_t>();
-    uint64_t *d_cnt = b_cnt.as<uint64_t>();
-    HIP_TRY(hipMemset(d_rgb, 0, npx * 3 * sizeof(float)));
-    HIP_TRY(hipMemset(d_nhit, 0, npx * sizeof(uint32_t)));
-    HIP_TRY(hipMemset(d_cnt, 0, CGRT_NCOUNTERS * sizeof(uint64_t)));
-    rc = cgrt_trace_grid(s, cam, grid, d_rgb, d_nhit, d_cnt, nullptr);
-    if (rc == CGRT_OK) {
-        hipError_t e = hipDeviceSynchronize();
-        if (e != hipSuccess) rc = fail(CGRT_ERR_DEVICE, std::string("kernel: ") + hipGetErrorString(e));
-    }
-    if (rc == CGRT_OK) {
-        HIP_TRY(hipMemcpy(rgb, d_rgb, npx * 3 * sizeof(float), hipMemcpyDeviceToHost));
-        if (nhit) HIP_TRY(hipMemcpy(nhit, d_nhit, npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (counters) HIP_TRY(hipMemcpy(counters, d_cnt, CGRT_NCOUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
-    return rc;
+    HostStage hs;
+    float *d_rgb = hs.out(rgb, npx * 3 * sizeof(float), true);
+    uint32_t *d_nhit = hs.out_always(nhit, npx * sizeof(uint32_t), true);
+    uint64_t *d_cnt = hs.out_always(counters, CGRT_NCOUNTERS * sizeof(uint64_t), true);
+    if ((rc = hs.error())) return rc;
+    return hs.finish(cgrt_trace_grid(s, cam, grid, d_rgb, d_nhit, d_cnt, nullptr));
 }
 
 int cgrt_intersect_rays(const cgrt_scene *s, int obj, const double *org3, const double *dir3, const uint64_t *keys,
@@ -1883,30 +1261,16 @@ int cgrt_intersect_rays(const cgrt_scene *s, int obj, const double *org3, const 
         return fail(CGRT_ERR_INVALID, "bad argument");
     if (n == 0) return CGRT_OK;
     ON_DEVICE(s->device);
-    DevBuf b_o, b_d, b_len, b_n, b_hit, b_keys;
-    HIP_TRY(b_o.alloc((size_t)n * 24));
-    HIP_TRY(b_d.alloc((size_t)n * 24));
-    HIP_TRY(b_len.alloc((size_t)n * 8));
-    HIP_TRY(b_n.alloc((size_t)n * 24));
-    HIP_TRY(b_hit.alloc((size_t)n * 4));
-    double *d_o = b_o.as<double>(), *d_d = b_d.as<double>(), *d_len = b_len.as<double>(), *d_n = b_n.as<double>();
-    int32_t *d_hit = b_hit.as<int32_t>();
-    HIP_TRY(hipMemcpy(d_o, org3, (size_t)n * 24, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_d, dir3, (size_t)n * 24, hipMemcpyHostToDevice));
-    unsigned long long *d_keys = nullptr;
-    if (keys) {
-        HIP_TRY(b_keys.alloc((size_t)n * 8));
-        d_keys = b_keys.as<unsigned long long>();
-        HIP_TRY(hipMemcpy(d_keys, keys, (size_t)n * 8, hipMemcpyHostToDevice));
-    }
+    HostStage hs;
+    const double *d_o = hs.in(org3, (size_t)n * 24), *d_d = hs.in(dir3, (size_t)n * 24);
+    const unsigned long long *d_keys = reinterpret_cast<const unsigned long long *>(hs.in(keys, (size_t)n * 8));
+    int32_t *d_hit = hs.out(hit, (size_t)n * 4);
+    double *d_len = hs.out(len, (size_t)n * 8), *d_n = hs.out(normal3, (size_t)n * 24);
+    if (const int rc = hs.error()) return rc;
     hipLaunchKernelGGL(intersect_rays_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, s->dev, obj, d_o, d_d, d_keys, n,
                        d_hit, d_len, d_n);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(hit, d_hit, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(len, d_len, (size_t)n * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(normal3, d_n, (size_t)n * 24, hipMemcpyDeviceToHost));
-    return CGRT_OK;
+    return hs.finish(CGRT_OK);
 }
 
 int cgrt_surface_colors(const cgrt_scene *s, int obj, const double *points3, int n, double *colors3) {
@@ -1914,16 +1278,13 @@ int cgrt_surface_colors(const cgrt_scene *s, int obj, const double *points3, int
     if (obj < 0 || obj >= s->dev.n_objs || n < 0 || (n > 0 && (!points3 || !colors3))) return fail(CGRT_ERR_INVALID, "bad argument");
     if (n == 0) return CGRT_OK;
     ON_DEVICE(s->device);
-    DevBuf b_p, b_c;
-    HIP_TRY(b_p.alloc((size_t)n * 24));
-    HIP_TRY(b_c.alloc((size_t)n * 24));
-    HIP_TRY(hipMemcpy(b_p.p, points3, (size_t)n * 24, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(surface_colors_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, s->dev, obj, b_p.as<double>(), n,
-                       b_c.as<double>());
+    HostStage hs;
+    const double *d_p = hs.in(points3, (size_t)n * 24);
+    double *d_c = hs.out(colors3, (size_t)n * 24);
+    if (const int rc = hs.error()) return rc;
+    hipLaunchKernelGGL(surface_colors_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, s->dev, obj, d_p, n, d_c);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(colors3, b_c.p, (size_t)n * 24, hipMemcpyDeviceToHost));
-    return CGRT_OK;
+    return hs.finish(CGRT_OK);
 }
 
 // The arguments the two host tables share, checked: the items and the grid's tile arithmetic
@@ -2007,16 +1368,13 @@ int cgrt_math_probe(int device, int op, const double *in, int64_t n, double *out
     const size_t n_in = op == CGRT_PROBE_SQRT ? 1 : (op == CGRT_PROBE_NORMALIZED ? 3 : (op == CGRT_PROBE_SPHERE_LEN ? 10 : 14)),
                  n_out = op == CGRT_PROBE_NORMALIZED ? 3 : (op == CGRT_PROBE_SPHERE_LEN_PAIR ? 2 : 1);
     ON_DEVICE(device);
-    DevBuf b_in, b_out;
-    HIP_TRY(b_in.alloc((size_t)n * n_in * sizeof(double)));
-    HIP_TRY(b_out.alloc((size_t)n * n_out * sizeof(double)));
-    HIP_TRY(hipMemcpy(b_in.p, in, (size_t)n * n_in * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(math_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, b_in.as<double>(), (long long)n,
-                       b_out.as<double>());
+    HostStage hs;
+    const double *d_in = hs.in(in, (size_t)n * n_in * sizeof(double));
+    double *d_out = hs.out(out, (size_t)n * n_out * sizeof(double));
+    if (const int rc = hs.error()) return rc;
+    hipLaunchKernelGGL(math_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, d_in, (long long)n, d_out);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, b_out.p, (size_t)n * n_out * sizeof(double), hipMemcpyDeviceToHost));
-    return CGRT_OK;
+    return hs.finish(CGRT_OK);
 }
 
 }  // extern "C"

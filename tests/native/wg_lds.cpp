@@ -5,7 +5,7 @@
 #include <cstdlib>
 #include <initializer_list>
 
-#include "cgrt_wg_lds.h"
+#include "cgrt_variants.h"
 
 static int g_failed = 0;
 #define CHECK_EQ(a, b)                                                                                          \
@@ -17,35 +17,17 @@ static int g_failed = 0;
         }                                                                                                       \
     } while (0)
 
-// The flag tuples of cgrt_hip.hip's kernel tables, transcribed.
-struct Eye { int T, B, D, G, P, S, H, NT, SP, HF, DF, PR; };
-static const Eye kEye[] = {  // kEyeKernels: TREES BEZ DOF GLASS SPH STATS HPS NT SPILL HFONLY DIFF PAIR
-    {1, 1, 0, 0, 0, 0, 0, 64, 0, 0, 0, 0}, {1, 1, 0, 1, 0, 0, 0, 64, 0, 0, 0, 0}, {1, 1, 1, 0, 0, 0, 0, 64, 0, 0, 0, 0}, {1, 1, 1, 1, 0, 0, 0, 64, 0, 0, 0, 0},
-    {1, 0, 0, 0, 0, 0, 0, 256, 0, 0, 0, 0}, {1, 0, 0, 1, 0, 0, 0, 256, 0, 0, 0, 0}, {1, 0, 1, 0, 0, 0, 0, 256, 0, 0, 0, 0}, {1, 0, 1, 1, 0, 0, 0, 256, 0, 0, 0, 0},
-    {1, 0, 0, 0, 0, 1, 0, 256, 0, 0, 0, 0}, {1, 0, 0, 1, 0, 1, 0, 256, 0, 0, 0, 0}, {1, 0, 1, 0, 0, 1, 0, 256, 0, 0, 0, 0}, {1, 0, 1, 1, 0, 1, 0, 256, 0, 0, 0, 0},
-    {0, 0, 0, 0, 1, 0, 0, 256, 0, 0, 0, 0}, {0, 0, 0, 1, 1, 0, 0, 256, 0, 0, 0, 0}, {0, 0, 1, 0, 1, 0, 0, 256, 0, 0, 0, 0}, {0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 0},
-    {0, 0, 0, 0, 0, 0, 0, 256, 0, 0, 0, 0}, {0, 0, 0, 1, 0, 0, 0, 256, 0, 0, 0, 0}, {0, 0, 1, 0, 0, 0, 0, 256, 0, 0, 0, 0}, {0, 0, 1, 1, 0, 0, 0, 256, 0, 0, 0, 0},
-    {0, 0, 0, 0, 1, 0, 0, 256, 1, 0, 0, 0}, {0, 0, 0, 1, 1, 0, 0, 256, 1, 0, 0, 0}, {0, 0, 1, 0, 1, 0, 0, 256, 1, 0, 0, 0}, {0, 0, 1, 1, 1, 0, 0, 256, 1, 0, 0, 0},
-    {1, 1, 0, 1, 0, 0, 0, 256, 1, 0, 0, 0}, {1, 1, 1, 1, 0, 0, 0, 256, 1, 0, 0, 0},
-    {1, 1, 0, 1, 0, 0, 1, 256, 0, 0, 0, 0}, {1, 1, 1, 1, 0, 0, 1, 256, 0, 0, 0, 0}, {1, 1, 0, 1, 0, 0, 1, 256, 1, 0, 0, 0}, {1, 1, 1, 1, 0, 0, 1, 256, 1, 0, 0, 0},
-    {1, 0, 0, 0, 0, 0, 0, 256, 0, 1, 0, 0}, {1, 0, 1, 0, 0, 0, 0, 256, 0, 1, 0, 0},
-    {0, 0, 0, 0, 1, 0, 0, 256, 0, 0, 1, 0}, {0, 0, 1, 0, 1, 0, 0, 256, 0, 0, 1, 0},
-    {0, 0, 0, 1, 1, 0, 0, 256, 0, 0, 0, 1}, {0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 1},
-};
+// The flag tuples of the compiled kernels: the two lists of cgrt_variants.h, expanded (the capture and occlusion kernels take
+// their trace_rays_kernel's flags and LDS)
+struct Eye { int T, B, D, G, P, S, H, NT, SP, HF, DF, PR, ST, LT, SCHED; };
+#define X(...) {__VA_ARGS__},
+static const Eye kEye[] = {CGRT_EYE_VARIANTS(X)};
 struct Rays { int T, B, G, P, S, SP, F, NT; };
-static const Rays kRays[] = {  // kRaysKernels: TREES BEZ GLASS SPH STATS SPILL FIRST NT
-    {1, 1, 0, 0, 0, 0, 0, 64}, {1, 1, 1, 0, 0, 0, 0, 64},
-    {1, 0, 0, 0, 0, 0, 0, 256}, {1, 0, 1, 0, 0, 0, 0, 256}, {1, 0, 0, 0, 1, 0, 0, 256}, {1, 0, 1, 0, 1, 0, 0, 256},
-    {0, 0, 0, 1, 0, 0, 0, 256}, {0, 0, 1, 1, 0, 0, 0, 256}, {0, 0, 0, 0, 0, 0, 0, 256}, {0, 0, 1, 0, 0, 0, 0, 256},
-    {0, 0, 0, 1, 0, 1, 0, 256}, {0, 0, 1, 1, 0, 1, 0, 256}, {1, 1, 1, 0, 0, 1, 0, 256},
-    {1, 1, 0, 0, 0, 0, 1, 64}, {1, 0, 0, 0, 0, 0, 1, 256}, {1, 0, 0, 0, 1, 0, 1, 256}, {0, 0, 0, 1, 0, 0, 1, 256},
-    {0, 0, 0, 0, 0, 0, 1, 256}, {0, 0, 0, 1, 0, 1, 1, 256}, {1, 1, 0, 0, 0, 1, 1, 256},
-    // kCaptureKernels: TREES BEZ GLASS SPH SPILL NT (STATS = FIRST = 0)
-    {1, 1, 0, 0, 0, 0, 0, 64}, {1, 1, 1, 0, 0, 0, 0, 64},
-    {1, 0, 0, 0, 0, 0, 0, 256}, {1, 0, 1, 0, 0, 0, 0, 256},
-    {0, 0, 0, 1, 0, 0, 0, 256}, {0, 0, 1, 1, 0, 0, 0, 256}, {0, 0, 0, 0, 0, 0, 0, 256}, {0, 0, 1, 0, 0, 0, 0, 256},
-    {0, 0, 0, 1, 0, 1, 0, 256}, {0, 0, 1, 1, 0, 1, 0, 256}, {1, 1, 1, 0, 0, 1, 0, 256},
-};
+static const Rays kRays[] = {CGRT_RAY_VARIANTS(X)};
+#undef X
+static EyeFlags eye_flags(const Eye &e) {
+    return {e.T != 0, e.B != 0, e.D != 0, e.G != 0, e.P != 0, e.S != 0, e.H != 0, e.SP != 0, e.HF != 0, e.NT, e.DF != 0, e.PR != 0, e.ST != 0, e.LT != 0};
+}
 static const int kCounts[] = {0, 1, 255, 257, 600, 727, 768};
 
 // regions in the documented order, each 16-byte aligned, of the given sizes (so disjoint), the total the end of the last one
@@ -103,6 +85,23 @@ static int resident_limit(const WgLdsAsk &a, int nodes, int st) {
 int main() {
     for (const Eye &e : kEye) check_trace(e.T, e.B, e.G, e.SP, e.HF, e.NT);
     for (const Rays &r : kRays) check_trace(r.T, r.B, r.G, r.SP, 0, r.NT);
+    // a START or LTAB twin is its PAIR parent with another body: the parent is compiled too, and the twin's LDS is the parent's
+    int twins = 0;
+    for (const Eye &e : kEye) {
+        if (!e.ST && !e.LT) continue;
+        twins++;
+        CHECK_EQ(e.PR, 1);
+        Eye parent = e;
+        parent.ST = parent.LT = 0;
+        int found = 0;
+        for (const Eye &p : kEye) found += eye_flags(p).id() == eye_flags(parent).id();
+        CHECK_EQ(found, 1);
+        for (int n : kCounts)
+            for (int nodes : {0, 255})
+                for (int wide = 0; wide < 2; wide++)
+                    CHECK_EQ(eye_lds(eye_flags(e), (size_t)n, (size_t)nodes, wide != 0), eye_lds(eye_flags(parent), (size_t)n, (size_t)nodes, wide != 0));
+    }
+    CHECK_EQ(twins, 4);
     // an HFONLY variant of any other shape has no tree regions either
     for (int G = 0; G < 2; G++)
         for (int B = 0; B < 2; B++) check_trace(1, B, G, 0, 1, B ? 64 : 256);

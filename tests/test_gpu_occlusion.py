@@ -6,7 +6,6 @@ and the strict `<` is met on every hit.  Every wave holds all five kinds: lanes 
 lanes never done share the walks.  Where the oracle is slow or statistical (Bezier objects, a thousand objects) the same
 construction runs on the GPU's own nearest-hit query."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -316,18 +315,16 @@ def test_example_shadow_rays(gpu_ready, tmp_path):
 
 
 def _table_variants():
-    """The flag tuples (TREES, BEZ, SPH, STATS, SPILL, NT) of kOcclusionKernels, read from cgrt_hip.hip itself."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "cgraytracing_amd", "csrc", "cgrt_hip.hip")).read()
-    body = src[src.index("static const OcclusionKernels kOcclusionKernels[] = {"):]
-    body = body[:body.index("};")]
-    out = [tuple(int(x) for x in m.split(",")) for m in re.findall(r"ok<([\d,\s]+)>\(\)", body)]
+    """The flag tuples (TREES, BEZ, SPH, STATS, SPILL, NT) of the occlusion kernels: one per FIRST entry of CGRT_RAY_VARIANTS,
+    read from cgrt_variants.h itself."""
+    import variants
+    out = variants.occlusion_variants()
     assert len(out) >= 7
-    return {v if len(v) == 6 else v + (256,) for v in out}
+    return set(out)
 
 
 def test_every_table_entry_is_launched(gpu_ready, monkeypatch):
-    """Every instantiation in kOcclusionKernels (the table is read from the source) is launched on a small grid of camera rays
+    """Every instantiation of occlusion_rays_kernel (the list is read from the source) is launched on a small grid of camera rays
     by the scenes and flags the tests of this file use, gives the answer of the nearest-hit query there, and nothing outside
     the table is ever asked for."""
     import cgraytracing_amd as cg

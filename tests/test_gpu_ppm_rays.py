@@ -4,7 +4,6 @@ order contract and the capture kernel are checked against trace_rays, which test
 look-at camera's session is checked end to end against a numpy replay of the reference's photon loop over the oracle's hits."""
 import math
 import os
-import re
 import subprocess
 import sys
 
@@ -323,7 +322,7 @@ def test_edge_cases(gpu_ready, orc):
             assert img.max() > 0 and np.array_equal(ses.rgb8(), orc.tonemap(img))
 
 
-# (label, scene, max_depth): between them every instantiation of kCaptureKernels
+# (label, scene, max_depth): between them every instantiation of capture_rays_kernel
 CAPTURE_LAUNCHES = [
     ("bezier_mirror", lambda: _bezier_scene(False), 5), ("bezier_glass", lambda: _bezier_scene(True), 5),
     ("dragon_depth1", scenes.scene_dragon, 1), ("c3_glass_bunny", lambda: scenes.scene_c3(True), 5),
@@ -336,17 +335,16 @@ CAPTURE_LAUNCHES = [
 
 
 def _capture_table():
-    """The flag tuples (TREES, BEZ, GLASS, SPH, SPILL, NT) of kCaptureKernels, read from cgrt_hip.hip itself."""
-    src = open(os.path.join(ROOT, "cgraytracing_amd", "csrc", "cgrt_hip.hip")).read()
-    body = src[src.index("static const CaptureKernels kCaptureKernels[] = {"):]
-    body = body[:body.index("};")]
-    out = [tuple(int(x) for x in m.split(",")) for m in re.findall(r"ck<([\d,\s]+)>\(\)", body)]
+    """The flag tuples (TREES, BEZ, GLASS, SPH, SPILL, NT) of the capture kernels: one per full-trace entry of CGRT_RAY_VARIANTS
+    without STATS, read from cgrt_variants.h itself."""
+    import variants
+    out = variants.capture_variants()
     assert len(out) >= 11
-    return {v if len(v) == 6 else v + (256,) for v in out}
+    return set(out)
 
 
 def test_every_capture_instantiation_is_launched(gpu_ready):
-    """Every instantiation in kCaptureKernels is launched on a small set of camera rays and produces trace_rays' Hitpoint count
+    """Every instantiation of capture_rays_kernel is launched on a small set of camera rays and produces trace_rays' Hitpoint count
     and sums; nothing outside the table is asked for.  room_800 (more objects than LDS holds, the SPILL capture of the general
     body) also runs as a session against the grid session."""
     import cgraytracing_amd as cg

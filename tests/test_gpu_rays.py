@@ -3,8 +3,6 @@
 The camera's own rays, traced as a ray list, must give the oracle's eye pass per ray in fp64, bit for bit: the ray kernel adds a
 ray tree's Hitpoint values in the lane, in the reference's emission order.  Rays no camera makes are checked against the
 oracle's per-object intersect() composed as main.cpp:52-62 composes it, and against getSurfaceColor at depth 1."""
-import os
-import re
 
 import numpy as np
 import pytest
@@ -186,18 +184,15 @@ def test_stats_counters(gpu_ready, name, mk, cam, W, H):
 
 
 def _table_variants():
-    """The flag tuples (TREES, BEZ, GLASS, SPH, STATS, SPILL, FIRST, NT) of kRaysKernels, read from cgrt_hip.hip itself."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "cgraytracing_amd", "csrc", "cgrt_hip.hip")).read()
-    body = src[src.index("static const RaysKernels kRaysKernels[] = {"):]
-    body = body[:body.index("};")]
-    out = [tuple(int(x) for x in m.split(",")) for m in re.findall(r"rk<([\d,\s]+)>\(\)", body)]
+    """The flag tuples (TREES, BEZ, GLASS, SPH, STATS, SPILL, FIRST, NT) of CGRT_RAY_VARIANTS, read from cgrt_variants.h itself."""
+    import variants
+    out = variants.ray_variants()
     assert len(out) >= 20
-    return {v if len(v) == 8 else v + (256,) for v in out}
+    return set(out)
 
 
 def test_every_table_entry_is_launched(gpu_ready, monkeypatch):
-    """Every instantiation in kRaysKernels (the table is read from the source) is launched here on a small grid of camera rays
+    """Every instantiation in CGRT_RAY_VARIANTS (the list is read from the source) is launched here on a small grid of camera rays
     -- by the scenes, depths and flags that the tests of this file trace against the oracle -- and nothing outside the table
     is ever asked for; a nearest-hit query and a full trace of the same rays agree on the hits."""
     import cgraytracing_amd as cg
@@ -445,7 +440,7 @@ def test_more_objects_than_lds_holds(gpu_ready, orc, monkeypatch):
     object counts on either side of the LDS limit.
     CGRT_ERR_LIMIT for a launch whose LDS does not fit is not asserted: no scene reaches it -- the general variant lowers its
     resident count until it fits, the sphere variant's and the others' worst case (kLdsObjsMax objects) is a static_assert of
-    cgrt_hip.hip, and the ray launches take no LDS padding knob -- so launch_checked's refusal stays a guard without a case."""
+    cgrt_variants.h, and the ray launches take no LDS padding knob -- so launch_checked's refusal stays a guard without a case."""
     import cgraytracing_amd as cg
     cam = scenes.cam_dof()
 

@@ -8,7 +8,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_wg_lds_layout_matches_the_written_out_byte_counts(tmp_path):
-    """Every flag tuple of kEyeKernels, kRaysKernels and kCaptureKernels, the photon forms and the primary walk at 0, 1, 255,
+    """Every flag tuple of CGRT_EYE_VARIANTS and CGRT_RAY_VARIANTS (cgrt_variants.h, walked by the program; the four START / LTAB
+    twins' LDS equal to their PAIR parents'), the photon forms and the primary walk at 0, 1, 255,
     257, 600, 727 and 768 objects, with and without a 255-node cached tree and a wide tree: regions in the documented order,
     16-byte aligned and disjoint, the total the end of the last one and equal to the literal formula (ObjRec 128 B, pending
     levels 38 912 B at 256 threads and a quarter at 64, BezLds 7 872 B per wave, node 32 B, wide stack 32 768 B); the general
