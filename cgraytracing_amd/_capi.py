@@ -109,6 +109,13 @@ class Occlusion(C.Structure):
     _fields_ = [("tmax", C.c_void_p), ("occluded", C.c_void_p)]
 
 
+class Bounce(C.Structure):
+    _fields_ = [("adj3", C.c_void_p), ("path", C.c_void_p), ("step", C.c_void_p), ("hit_obj", C.c_void_p), ("hit_t", C.c_void_p),
+                ("pos3", C.c_void_p), ("normal3", C.c_void_p), ("value3", C.c_void_p), ("child_org3", C.c_void_p),
+                ("child_dir3", C.c_void_p), ("child_adj3", C.c_void_p), ("child_path", C.c_void_p), ("child_keys", C.c_void_p),
+                ("reserved", C.c_void_p * 2)]  # 15 pointers, 120 bytes
+
+
 class RayPixels(C.Structure):
     _fields_ = [("width", C.c_int32), ("rows", C.c_int32), ("spp", C.c_int32), ("pad_", C.c_int32), ("pixel", C.c_void_p)]
 
@@ -122,6 +129,7 @@ RAYS_STATS = 1
 RAYS_NO_SIGN_PASS = 2
 RAYS_HITPOINTS = 4
 RAYS_SKIP_TRANSPARENT = 8
+STEP_NONE, STEP_HITPOINT, STEP_REFLECT, STEP_SPLIT = 0, 1, 2, 3  # cgrt_bounce.step
 PROBE_SQRT, PROBE_NORMALIZED, PROBE_SPHERE_LEN, PROBE_SPHERE_LEN_PAIR = 0, 1, 2, 4  # cgrt_math_probe's op (3 is none)
 
 # every symbol include/cgrt.h declares, with its signature
@@ -213,6 +221,9 @@ SIGNATURES = {
     "cgrt_occlusion_rays": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(Occlusion), C.c_void_p, C.c_void_p]),
     "cgrt_occlusion_rays_host": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(Occlusion), C.c_void_p]),
     "cgrt_occlusion_rays_variant": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.c_char_p, C.c_size_t]),
+    "cgrt_bounce_rays": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(Bounce), C.c_void_p, C.c_void_p]),
+    "cgrt_bounce_rays_host": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(Bounce), C.c_void_p]),
+    "cgrt_bounce_rays_variant": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.c_char_p, C.c_size_t]),
     "cgrt_camera_rays": (C.c_int, [C.POINTER(Camera), C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cgrt_camera_rays_host": (C.c_int, [C.POINTER(Camera), C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cgrt_intersect_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,

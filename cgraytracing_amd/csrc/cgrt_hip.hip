@@ -42,6 +42,7 @@
 #include "cgrt_primwalk.hpp"
 #include "cgrt_rays.hpp"
 #include "cgrt_occlusion.hpp"
+#include "cgrt_bounce.hpp"
 #include "cgrt_hit_attr.hpp"
 
 using namespace cgrt;

@@ -1,24 +1,27 @@
 // Caller-supplied rays: the ray-list kernels' dispatch table (cgrt_variants.h), their one launch path over rays_plan
 // (cgrt_rays_plan.h), the argument checks and the C entry points -- full trace and nearest-hit query, Hitpoint capture, occlusion,
-// camera rays, hit attributes.  Part of libcgrt.so; included by cgrt_hip.hip, which has the handle, the checked launch and the
+// bounce, camera rays, hit attributes.  Part of libcgrt.so; included by cgrt_hip.hip, which has the handle, the checked launch and the
 // host staging.
 
-// The table's rows: a variant's trace_rays_kernel and, where the variant has one, its capture and occlusion forms
+// The table's rows: a variant's trace_rays_kernel and, where the variant has one, its capture, occlusion and bounce forms
 using RaysKernel = void (*)(DeviceScene, RayParams, unsigned long long *);
 using CaptureKernel = void (*)(DeviceScene, RayParams, RaySink);
 using OcclusionKernel = void (*)(DeviceScene, OccParams, unsigned long long *);
+using BounceKernel = void (*)(DeviceScene, BounceParams, unsigned long long *);
 struct RayKernels {
     int id;  // RayFlags::id()
     RaysKernel trace;
     CaptureKernel capture;      // nullptr unless has_capture
     OcclusionKernel occlusion;  // nullptr unless has_occlusion
+    BounceKernel bounce;        // nullptr unless has_bounce
 };
 template <bool T, bool B, bool G, bool P, bool S, bool SP, bool F, int NT>
 static constexpr RayKernels ray_kernels_row() {
     constexpr RayFlags f{T, B, G, P, S, SP, F, NT};
-    RayKernels r{f.id(), &trace_rays_kernel<T, B, G, P, S, SP, F, NT>, nullptr, nullptr};
+    RayKernels r{f.id(), &trace_rays_kernel<T, B, G, P, S, SP, F, NT>, nullptr, nullptr, nullptr};
     if constexpr (has_capture(f)) r.capture = &capture_rays_kernel<T, B, G, P, SP, NT>;
     if constexpr (has_occlusion(f)) r.occlusion = &occlusion_rays_kernel<T, B, P, S, SP, NT>;
+    if constexpr (has_bounce(f)) r.bounce = &bounce_rays_kernel<T, B, P, S, SP, NT>;
     return r;
 }
 #define CGRT_X(T, B, G, P, S, SP, F, NT) ray_kernels_row<T != 0, B != 0, G != 0, P != 0, S != 0, SP != 0, F != 0, NT>(),
@@ -40,11 +43,12 @@ static RaysPlan rays_plan_for(const cgrt_scene *s, const cgrt_rays *rays, RaysKi
 }
 // ... refused where no kernel of `kind` was built for the plan's variant
 static int rays_launch(const cgrt_scene *s, const cgrt_rays *rays, RaysKind kind, RaysLaunch &L) {
-    static const char *const form[] = {"", "", "capture ", "occlusion "};
+    static const char *const form[] = {"", "", "capture ", "occlusion ", "bounce "};
     L.plan = rays_plan_for(s, rays, kind);
     L.dev = with_resident(s->dev, L.plan.resident);
     L.row = variant_row(kRayKernels, L.plan.k);
-    if (!L.row || (kind == RaysKind::Capture && !L.row->capture) || (kind == RaysKind::Occlusion && !L.row->occlusion))
+    if (!L.row || (kind == RaysKind::Capture && !L.row->capture) || (kind == RaysKind::Occlusion && !L.row->occlusion) ||
+        (kind == RaysKind::Bounce && !L.row->bounce))
         return fail(CGRT_ERR_UNSUPPORTED, std::string(L.plan.what()) + ": no " + form[(int)kind] + "kernel built for this variant");
     return CGRT_OK;
 }
@@ -59,7 +63,7 @@ static int ray_queue(const cgrt_scene *s, size_t tail, hipStream_t st, unsigned 
     *queue = reinterpret_cast<unsigned int *>(s->scratch.p);
     return CGRT_OK;
 }
-// what RayParams and OccParams both read of a ray list
+// what RayParams, OccParams and BounceParams all read of a ray list
 template <class P>
 static void fill_ray_inputs(P &p, const cgrt_rays *r, unsigned int *queue) {
     p.n = r->n;
@@ -99,6 +103,13 @@ static int check_rays(const cgrt_scene *s, const cgrt_rays *r, const cgrt_ray_re
 static int check_capture_rays(const cgrt_scene *s, const cgrt_rays *r) { return check_ray_list(s, r, true, nullptr, true, true); }
 static int check_occlusion(const cgrt_scene *s, const cgrt_rays *r, const cgrt_occlusion *occ) {
     return check_ray_list(s, r, occ != nullptr, occ && !occ->occluded ? "null occluded" : nullptr, false, false);
+}
+static int check_bounce(const cgrt_scene *s, const cgrt_rays *r, const cgrt_bounce *b) {
+    return check_ray_list(s, r, b != nullptr, nullptr, false, false);
+}
+static bool bounce_asks(const cgrt_bounce *b) {
+    return b->step || b->hit_obj || b->hit_t || b->pos3 || b->normal3 || b->value3 || b->child_org3 || b->child_dir3 || b->child_adj3 ||
+           b->child_path || b->child_keys;
 }
 static int check_hit_attributes(const cgrt_scene *s, const cgrt_rays *r, const int32_t *hit_obj, const double *hit_t,
                                 const cgrt_hit_attributes *out) {
@@ -282,6 +293,74 @@ int cgrt_occlusion_rays_host(const cgrt_scene *s, const cgrt_rays *rays, const c
     uint64_t *d_cnt = hs.out_always(counters, kCounterBytes, true);
     if ((rc = hs.error())) return rc;
     return hs.finish(cgrt_occlusion_rays(s, &dr, &docc, d_cnt, nullptr));
+}
+
+int cgrt_bounce_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_bounce *b, uint64_t *counters, void *stream) {
+    int rc = check_bounce(s, rays, b);
+    if (rc) return rc;
+    if (rays->n == 0 || !bounce_asks(b)) return CGRT_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    ON_DEVICE(s->device);
+    RaysLaunch L;
+    if ((rc = rays_launch(s, rays, RaysKind::Bounce, L))) return rc;
+    unsigned int *queue = nullptr;
+    if ((rc = ray_queue(s, 0, st, &queue))) return rc;
+    BounceParams bp{};
+    fill_ray_inputs(bp, rays, queue);
+    bp.adj = b->adj3;
+    bp.path = b->path;
+    bp.step = b->step;
+    bp.hit_obj = b->hit_obj;
+    bp.hit_t = b->hit_t;
+    bp.pos = b->pos3;
+    bp.normal = b->normal3;
+    bp.value = b->value3;
+    bp.child_org = b->child_org3;
+    bp.child_dir = b->child_dir3;
+    bp.child_adj = b->child_adj3;
+    bp.child_path = b->child_path;
+    bp.child_keys = reinterpret_cast<unsigned long long *>(b->child_keys);
+    if ((rc = launch_rays(s, L, L.row->bounce, st, bp, reinterpret_cast<unsigned long long *>(counters)))) return rc;
+    HIP_TRY(hipGetLastError());
+    return CGRT_OK;
+}
+
+int cgrt_bounce_rays_variant(const cgrt_scene *s, const cgrt_rays *rays, char *name, size_t cap) {
+    if (!s || !rays || !name || cap == 0) return fail(CGRT_ERR_INVALID, "null argument");
+    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+    ON_DEVICE(s->device);
+    rays_plan_for(s, rays, RaysKind::Bounce).name(RaysKind::Bounce, name, cap);
+    return CGRT_OK;
+}
+
+int cgrt_bounce_rays_host(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_bounce *b, uint64_t *counters) {
+    int rc = check_bounce(s, rays, b);
+    if (rc) return rc;
+    const size_t n = (size_t)rays->n;
+    if (n == 0 || !bounce_asks(b)) {
+        if (counters) std::memset(counters, 0, kCounterBytes);
+        return CGRT_OK;
+    }
+    ON_DEVICE(s->device);
+    HostStage hs;
+    const cgrt_rays dr = stage_rays(hs, rays, true);
+    cgrt_bounce db{};
+    db.adj3 = hs.in(b->adj3, n * 24);
+    db.path = hs.in(b->path, n * 4);
+    db.step = hs.out(b->step, n);
+    db.hit_obj = hs.out(b->hit_obj, n * 4);
+    db.hit_t = hs.out(b->hit_t, n * 8);
+    db.pos3 = hs.out(b->pos3, n * 24);
+    db.normal3 = hs.out(b->normal3, n * 24);
+    db.value3 = hs.out(b->value3, n * 24);
+    db.child_org3 = hs.out(b->child_org3, 2 * n * 24);
+    db.child_dir3 = hs.out(b->child_dir3, 2 * n * 24);
+    db.child_adj3 = hs.out(b->child_adj3, 2 * n * 24);
+    db.child_path = hs.out(b->child_path, 2 * n * 4);
+    db.child_keys = hs.out(b->child_keys, 2 * n * 8);
+    uint64_t *d_cnt = hs.out_always(counters, kCounterBytes, true);
+    if ((rc = hs.error())) return rc;
+    return hs.finish(cgrt_bounce_rays(s, &dr, &db, d_cnt, nullptr));
 }
 
 int cgrt_camera_rays(const cgrt_camera *cam, const cgrt_grid *grid, double *org3, double *dir3, uint64_t *keys, void *stream) {

@@ -80,7 +80,7 @@ static constexpr EyeFlags diffuse_flags(bool dof) { return {false, false, dof, f
     /* ... and the thin-lens ones' twins, plain and START, for a launch with a lens table: the bodies that read it */                \
     X(0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 1, 0, 1, 0) X(0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 1, 1, 1, 0)
 
-// ---- the ray-list kernels (cgrt_rays.hpp, cgrt_occlusion.hpp) ----
+// ---- the ray-list kernels (cgrt_rays.hpp, cgrt_occlusion.hpp, cgrt_bounce.hpp) ----
 // The template flags of a trace_rays_kernel instantiation
 struct RayFlags {
     bool trees, bez, glass, sph, stats, spill, first;
@@ -102,11 +102,13 @@ struct RayFlags {
     /* the nearest-hit query: no GLASS variants */                                                                                    \
     X(1, 1, 0, 0, 0, 0, 1, 64) X(1, 0, 0, 0, 0, 0, 1, 256) X(1, 0, 0, 0, 1, 0, 1, 256) X(0, 0, 0, 1, 0, 0, 1, 256)                    \
     X(0, 0, 0, 0, 0, 0, 1, 256) X(0, 0, 0, 1, 0, 1, 1, 256) X(1, 1, 0, 0, 0, 1, 1, 256)
-// The two derived families share a variant's flags, launch plan and table row:
+// The three derived families share a variant's flags, launch plan and table row:
 // capture_rays_kernel<TREES, BEZ, GLASS, SPH, SPILL, NT> exists for every full-trace variant without STATS, ...
 static constexpr bool has_capture(const RayFlags &f) { return !f.stats && !f.first; }
-// ... occlusion_rays_kernel<TREES, BEZ, SPH, STATS, SPILL, NT> for every nearest-hit variant (none of which has GLASS)
+// ... occlusion_rays_kernel<TREES, BEZ, SPH, STATS, SPILL, NT> for every nearest-hit variant (none of which has GLASS), ...
 static constexpr bool has_occlusion(const RayFlags &f) { return f.first; }
+// ... and so does bounce_rays_kernel<TREES, BEZ, SPH, STATS, SPILL, NT>: one walk per ray, then one step of trace()
+static constexpr bool has_bounce(const RayFlags &f) { return f.first; }
 
 // ---- LDS of a launch ----
 // A workgroup may use at most a CU's LDS (MI355X: 160 KiB): the kernel's static __shared__ bytes plus the dynamic bytes of

@@ -553,6 +553,121 @@ class Scene:
         check(self._L.cgrt_occlusion_rays_variant(self._h, C.byref(r), buf, len(buf)))
         return buf.value.decode()
 
+    # ---- bounce queries of caller-supplied rays: one step of trace() ----
+    _BOUNCE = ("step", "hit_obj", "hit_t", "pos", "normal", "value", "child_org", "child_dir", "child_adj", "child_path", "child_keys")
+    _BOUNCE_GROUPS = {"hit": ("hit_obj", "hit_t"), "children": ("child_org", "child_dir", "child_adj", "child_path", "child_keys")}
+
+    def _bounce_want(self, what, want):
+        names = []
+        for w in tuple(want):
+            for k in self._BOUNCE_GROUPS.get(w, (w,)):
+                if k not in self._BOUNCE:
+                    raise ValueError("%s: want is a non-empty subset of %r" % (what, self._BOUNCE + tuple(self._BOUNCE_GROUPS)))
+                names.append(k)
+        if not names:
+            raise ValueError("%s: want is a non-empty subset of %r" % (what, self._BOUNCE + tuple(self._BOUNCE_GROUPS)))
+        return [k for k in self._BOUNCE if k in names]
+
+    def bounce(self, org, dirs, adj=None, path=None, keys=None, seed=12345, first_index=0,
+               want=("step", "hit", "pos", "normal", "value", "children"), stats=False, out=None, stream=None, counters=None):
+        """cgrt_bounce_rays on torch tensors: one scene walk per ray, then exactly the step trace() takes at the hit.  org, dirs
+        float64 [n,3] contiguous on the scene's device; adj float64 [n,3] or None (the ray's throughput, (1,1,1)); path int32 [n]
+        or None (position in the ray tree: root 1, reflected child 2p, refracted child 2p+1); keys int64 [n] or None.  want:
+        which results -- "step" (uint8 [n]: _capi.STEP_NONE / _HITPOINT / _REFLECT / _SPLIT), "hit_obj" (int32 [n]), "hit_t"
+        (float64 [n]), "pos", "normal" (float64 [n,3]: the hit point and the normal after trace()'s flip), "value" (float64
+        [n,3]: f * adj of a Hitpoint, else 0), "child_org", "child_dir", "child_adj" (float64 [2n,3]), "child_path" (int32
+        [2n]), "child_keys" (int64 [2n]): row i the reflected child of ray i, row n + i the refracted one, zeros where there is
+        none -- the five can be passed back as the next level's org, dirs, adj, path, keys as they are (dirs = 0 rows are not
+        traced) or compacted first.  "hit" and "children" name the groups.  There is no depth limit: the caller's loop decides.
+        out: dict of preallocated result tensors to write into.  Asynchronous on torch's current stream (or `stream`); counters
+        (int64 [8]) are ADDED to.  Returns a dict of the tensors and "counters"."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        n = self._ray_tensors("bounce", org, dirs, keys)
+        if adj is not None and not (isinstance(adj, torch.Tensor) and adj.dtype == torch.float64 and tuple(adj.shape) == (n, 3) and
+                                    adj.is_contiguous() and adj.device == dev):
+            raise ValueError("bounce: adj must be a contiguous float64 [n,3] tensor on %s" % (dev,))
+        if path is not None and not (isinstance(path, torch.Tensor) and path.dtype == torch.int32 and tuple(path.shape) == (n,) and
+                                     path.is_contiguous() and path.device == dev):
+            raise ValueError("bounce: path must be a contiguous int32 [n] tensor on %s" % (dev,))
+        names = self._bounce_want("bounce", want)
+        shapes = dict(step=((n,), torch.uint8), hit_obj=((n,), torch.int32), hit_t=((n,), torch.float64), pos=((n, 3), torch.float64),
+                      normal=((n, 3), torch.float64), value=((n, 3), torch.float64), child_org=((2 * n, 3), torch.float64),
+                      child_dir=((2 * n, 3), torch.float64), child_adj=((2 * n, 3), torch.float64), child_path=((2 * n,), torch.int32),
+                      child_keys=((2 * n,), torch.int64))
+        res = {}
+        for name in names:
+            shape, dtype = shapes[name]
+            t = out.get(name) if out else None
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=dev)
+            elif not (isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and
+                      t.device == dev):
+                raise ValueError("bounce: out[%r] must be a contiguous %s %r tensor on %s" % (name, dtype, shape, dev))
+            res[name] = t
+        if counters is None:
+            counters = torch.zeros((_capi.CGRT_NCOUNTERS,), dtype=torch.int64, device=dev)
+        elif not (counters.dtype == torch.int64 and counters.numel() == _capi.CGRT_NCOUNTERS and counters.is_contiguous() and
+                  counters.device == dev):
+            raise ValueError("bounce: counters must be a contiguous int64 [8] tensor on %s" % (dev,))
+        res["counters"] = counters
+        if n == 0:
+            return res
+        ptr = lambda k: res[k].data_ptr() if k in res else None
+        r = _capi.Rays(n, org.data_ptr(), dirs.data_ptr(), keys.data_ptr() if keys is not None else None, first_index, seed, 1,
+                       _capi.RAYS_STATS if stats else 0)
+        b = _capi.Bounce(adj.data_ptr() if adj is not None else None, path.data_ptr() if path is not None else None,
+                         *[ptr(k) for k in self._BOUNCE])
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(self._L.cgrt_bounce_rays(self._h, C.byref(r), C.byref(b), counters.data_ptr(), C.c_void_p(st)))
+        return res
+
+    def bounce_host(self, org, dirs, adj=None, path=None, keys=None, seed=12345, first_index=0,
+                    want=("step", "hit", "pos", "normal", "value", "children"), stats=False):
+        """Synchronous form of bounce on numpy arrays (no torch needed): dict of the arrays in `want` (child_path uint32,
+        child_keys uint64), counters (uint64 [8]), nrays, nhp."""
+        org = np.ascontiguousarray(org, np.float64).reshape(-1, 3)
+        dirs = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
+        n = len(org)
+        if len(dirs) != n:
+            raise ValueError("bounce_host: org and dirs differ in length")
+        if adj is not None:
+            adj = np.ascontiguousarray(adj, np.float64)
+            if adj.shape != (n, 3):
+                raise ValueError("bounce_host: adj must be an [n,3] array")
+        if path is not None:
+            path = np.ascontiguousarray(path, np.uint32)
+            if path.shape != (n,):
+                raise ValueError("bounce_host: path must have one entry per ray")
+        if keys is not None:
+            keys = np.ascontiguousarray(keys, np.uint64)
+            if keys.shape != (n,):
+                raise ValueError("bounce_host: keys must have one entry per ray")
+        names = self._bounce_want("bounce_host", want)
+        make = dict(step=lambda: np.zeros(n, np.uint8), hit_obj=lambda: np.full(n, -1, np.int32), hit_t=lambda: np.zeros(n, np.float64),
+                    pos=lambda: np.zeros((n, 3), np.float64), normal=lambda: np.zeros((n, 3), np.float64),
+                    value=lambda: np.zeros((n, 3), np.float64), child_org=lambda: np.zeros((2 * n, 3), np.float64),
+                    child_dir=lambda: np.zeros((2 * n, 3), np.float64), child_adj=lambda: np.zeros((2 * n, 3), np.float64),
+                    child_path=lambda: np.zeros(2 * n, np.uint32), child_keys=lambda: np.zeros(2 * n, np.uint64))
+        res = {k: make[k]() for k in names}
+        cnt = np.zeros((_capi.CGRT_NCOUNTERS,), np.uint64)
+        ptr = lambda k: res[k].ctypes.data if k in res else None
+        r = _capi.Rays(n, org.ctypes.data, dirs.ctypes.data, keys.ctypes.data if keys is not None else None, first_index, seed, 1,
+                       _capi.RAYS_STATS if stats else 0)
+        b = _capi.Bounce(adj.ctypes.data if adj is not None else None, path.ctypes.data if path is not None else None,
+                         *[ptr(k) for k in self._BOUNCE])
+        check(self._L.cgrt_bounce_rays_host(self._h, C.byref(r), C.byref(b), cnt.ctypes.data))
+        res.update(counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]), nhp=int(cnt[_capi.CNT_HITPOINTS]))
+        return res
+
+    def bounce_variant(self, stats=False):
+        """Name of the bounce_rays_kernel instantiation bounce launches on this scene (cgrt_bounce_rays_variant)."""
+        r = _capi.Rays(1, None, None, None, 0, 0, 1, _capi.RAYS_STATS if stats else 0)
+        buf = C.create_string_buffer(160)
+        check(self._L.cgrt_bounce_rays_variant(self._h, C.byref(r), buf, len(buf)))
+        return buf.value.decode()
+
     def rays_variant(self, max_depth=5, want=("acc", "nhit", "hit"), stats=False):
         """Name of the trace_rays_kernel instantiation trace_rays launches for these arguments (cgrt_trace_rays_variant)."""
         full = 1 if ("acc" in want or "nhit" in want) else None

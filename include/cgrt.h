@@ -18,7 +18,7 @@
  * Threading: launches on ONE scene handle must be ordered by the caller (same stream, or events between streams) --
  * a handle owns device scratch that consecutive launches reuse (CGRT_GRID_SPLIT_SAMPLES chunk sums; the schedule of a
  * cost-ordered frame; the tile order of an image-order one; the queue counter of cgrt_trace_rays, cgrt_trace_rays_hitpoints and cgrt_ppm_session_create_rays, which
- * are such launches (cgrt_occlusion_rays uses that counter too); cgrt_ray_hit_attributes is one too: its first call that asks for `prim` builds a table the handle keeps).
+ * are such launches (cgrt_occlusion_rays and cgrt_bounce_rays use that counter too); cgrt_ray_hit_attributes is one too: its first call that asks for `prim` builds a table the handle keeps).
  * All geometry is IEEE double, like the reference (Vec3 = 3 x double, vec3.h:11-30).
  */
 #ifndef CGRT_H
@@ -40,7 +40,9 @@ extern "C" {
                             cgrt_ppm_session_add_photon_rays, cgrt_photon_emit, cgrt_photon_emit_host, cgrt_photon_ray_events
                             (caller-supplied photons); cgrt_hit_attributes, cgrt_ray_hit_attributes, cgrt_ray_hit_attributes_host
                             (hit attributes of caller-supplied rays); cgrt_occlusion, CGRT_RAYS_SKIP_TRANSPARENT,
-                            cgrt_occlusion_rays, cgrt_occlusion_rays_host, cgrt_occlusion_rays_variant (occlusion queries) */
+                            cgrt_occlusion_rays, cgrt_occlusion_rays_host, cgrt_occlusion_rays_variant (occlusion queries);
+                            cgrt_bounce, CGRT_STEP_*, cgrt_bounce_rays, cgrt_bounce_rays_host, cgrt_bounce_rays_variant
+                            (bounce queries) */
 
 enum {
     CGRT_OK = 0,
@@ -472,6 +474,71 @@ int cgrt_occlusion_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_o
 int cgrt_occlusion_rays_host(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_occlusion *occ, uint64_t *counters);
 /* Name of the occlusion_rays_kernel instantiation cgrt_occlusion_rays would launch for (scene, rays); only rays->flags matters. */
 int cgrt_occlusion_rays_variant(const cgrt_scene *s, const cgrt_rays *rays, char *name, size_t cap);
+
+/* ---- bounce queries: one step of trace() for caller-supplied rays ---------------------------------------------------
+ * The step between a hit and the next rays, for integrators written on top of the library.  Per ray i: one scene walk -- the
+ * nearest-hit query's, keyed by (key, path[i]) --, then exactly what trace() does at that hit (main.cpp:64-157): the normal
+ * flip, getSurfaceColor, and either the Hitpoint's value f * adj or the child rays with their throughput -- the mirror
+ * direction, the Fresnel split with its Re and 1 - Re weights, total internal reflection, the 1e-4 offsets of the child
+ * origins.  The expressions are those of cgrt_trace_rays' kernels in their order (one shared function), so a depth loop over
+ * this call -- root rays with adj = (1,1,1) and path 1, the children fed back level by level -- visits the ray tree of
+ * cgrt_trace_rays and produces its Hitpoints bit for bit: summed per root in emission order (depth first, the reflected
+ * subtree before the refracted one; by path: compare the bits behind the leading 1, a prefix before its extensions) they
+ * give acc3, and their {value3, pos3, normal3} are the records of cgrt_trace_rays_hitpoints.  Between two levels the caller
+ * may do what the library does not: go deeper than 5, attenuate, cull, stop a subtree, shade some objects itself.
+ *   THERE IS NO DEPTH LIMIT in this call: rays->max_depth is not looked at, a mirror or glass hit always yields its
+ *   children, and the caller decides when to stop.
+ *   step[i]   CGRT_STEP_NONE      a miss, or a ray that is not traced: dir = (0,0,0), as in every ray-list call, or a path of
+ *                                 0 or >= 2^31; hit_obj = -1 and zeros in every other array; a ray not traced is not counted
+ *             CGRT_STEP_HITPOINT  reflection < 1e-4 and transparency < 1e-4: value3 = f * adj (main.cpp:88); no child
+ *             CGRT_STEP_REFLECT   a mirror (child_adj = f * adj * reflection, main.cpp:129-134), or total internal reflection
+ *                                 in glass, where child_adj IS adj3[i], bit for bit (main.cpp:144): the reflected child only
+ *             CGRT_STEP_SPLIT     glass: the reflected child with f * adj * Re and the refracted one with f * adj * (1 - Re)
+ *   Child slots: slot i of the [2n] arrays is the reflected child of ray i, slot n + i its refracted child.  An absent child
+ *   is zeros in child_org3 / child_dir3 / child_adj3, child_path 0 and child_keys 0 -- dir = 0 is the "not a ray" mark, so the
+ *   five child arrays can be passed straight back as the next call's org3 / dir3 / adj3 / path / keys with n' = 2n; a caller
+ *   may instead compact them first.  child_path is 2p for the reflected and 2p + 1 for the refracted child of a ray at
+ *   path p (root 1): with the ray's key it keys a Bezier object's draws, as in the full trace.  child_keys is the parent's key
+ *   (keys[i], or the one derived from seed and first_index + i).
+ * A ray's results do not depend on the other rays of the call, on their order or on how a ray set is split over calls (with
+ * keys, or first_index, kept alike).  Of `rays`, max_depth is not looked at; CGRT_RAYS_STATS counts node and triangle tests;
+ * the other flags are ignored.  hit_normal3's sign pass has no part here: trace() turns an opaque owner's normal against the
+ * ray in any case.  counters (may be NULL) are ADDED to: CGRT_CNT_RAYS by the rays traced, _HITPOINTS by the
+ * CGRT_STEP_HITPOINT steps, _WAVE_ITERS as usual.
+ * A null scene, null rays or bounce, a negative n: CGRT_ERR_INVALID; more than 2^36 rays: CGRT_ERR_LIMIT; n == 0 is valid and
+ * does nothing (the scene is not even looked at); otherwise an uncommitted scene: CGRT_ERR_INVALID -- all before any device is
+ * touched.  With every output pointer NULL the call returns CGRT_OK and launches nothing. */
+enum {
+    CGRT_STEP_NONE = 0,      /* miss, or a ray that is not traced (dir = 0)                                                  */
+    CGRT_STEP_HITPOINT = 1,  /* diffuse hit: value3 = f * adj (main.cpp:88); no child                                        */
+    CGRT_STEP_REFLECT = 2,   /* mirror, or total internal reflection: the reflected child only                               */
+    CGRT_STEP_SPLIT = 3      /* glass: reflected and refracted child                                                         */
+};
+typedef struct cgrt_bounce {
+    /* in, each may be NULL */
+    const double   *adj3;       /* [n][3] the ray's throughput, trace()'s adj; NULL: (1,1,1)                                 */
+    const uint32_t *path;       /* [n] position in the ray tree: root 1, reflected child 2p, refracted 2p+1; NULL: 1;
+                                   0 or >= 2^31: CGRT_STEP_NONE, not traced                                                  */
+    /* out, each may be NULL; only the arrays asked for are written */
+    uint8_t  *step;             /* [n] CGRT_STEP_*                                                                           */
+    int32_t  *hit_obj;          /* [n] as cgrt_ray_results                                                                   */
+    double   *hit_t;            /* [n]                                                                                       */
+    double   *pos3, *normal3;   /* [n][3] P = org + dir * t and the normal AFTER the flip of main.cpp:73-76, for every hit;
+                                   zeros for CGRT_STEP_NONE                                                                  */
+    double   *value3;           /* [n][3] f * adj for CGRT_STEP_HITPOINT, else zeros                                         */
+    double   *child_org3, *child_dir3, *child_adj3;  /* [2n][3] the child slots (above)                                      */
+    uint32_t *child_path;       /* [2n] 2p / 2p+1; 0 for an absent child                                                     */
+    uint64_t *child_keys;       /* [2n] the parent's key; 0 for an absent child                                              */
+    void     *reserved[2];      /* not looked at; set to NULL: room for two more arrays without another layout               */
+} cgrt_bounce;                  /* 15 pointers, 120 bytes */
+
+/* DEVICE pointers on the scene's device; asynchronous on `stream`.  This is a launch on the scene handle (Threading above):
+ * it uses the handle's ray-queue counter, like cgrt_trace_rays. */
+int cgrt_bounce_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_bounce *bounce, uint64_t *counters, void *stream);
+/* HOST pointers: allocates device buffers, runs, synchronises and copies back (counters are overwritten). */
+int cgrt_bounce_rays_host(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_bounce *bounce, uint64_t *counters);
+/* Name of the bounce_rays_kernel instantiation cgrt_bounce_rays would launch for (scene, rays); only rays->flags matters. */
+int cgrt_bounce_rays_variant(const cgrt_scene *s, const cgrt_rays *rays, char *name, size_t cap);
 
 /* The primary rays cgrt_trace_grid starts for sample `sample_offset + k`, k in [0, spp), of every pixel of the grid's rows
  * (contiguous or striped): ray index = (k * rows + local row) * width + w.  org3 / dir3 / keys as in cgrt_rays (any may be

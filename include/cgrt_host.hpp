@@ -429,6 +429,66 @@ inline void occluded(const std::vector<Object *> &objs, const std::vector<double
     check(cgrt_occlusion_rays_host(sb.scene, &r, &out, nullptr));
 }
 
+// One step of trace() per ray (cgrt_bounce_rays_host): the nearest hit, then what trace() does there -- a Hitpoint's value
+// f * adj, or the child rays with their throughput.  Feed child_org / child_dir / child_adj / child_path / child_keys back as
+// the next level's org3 / dir3 / adj3 / path / keys (rows with dir = 0 are absent children and are not traced), as deep as the
+// caller likes; the Hitpoint values of a root's tree, summed depth first with the reflected subtree before the refracted one,
+// are trace_rays' sum for that root.
+struct BounceLevel {
+    std::vector<uint8_t> step;                                      // [n] CGRT_STEP_*
+    std::vector<int32_t> obj;                                       // [n] nearest object, -1 for none
+    std::vector<double> t, pos, normal, value;                      // [n], [n][3] x 3
+    std::vector<double> child_org, child_dir, child_adj;            // [2n][3]: row i reflected, row n + i refracted child
+    std::vector<uint32_t> child_path;                               // [2n]
+    std::vector<uint64_t> child_keys;                               // [2n]
+};
+// adj3 / path / keys: empty for the roots' defaults -- (1,1,1), 1, the keys derived from `seed`
+inline void bounce(const std::vector<Object *> &objs, const std::vector<double> &org3, const std::vector<double> &dir3,
+                   const std::vector<double> &adj3, const std::vector<uint32_t> &path, const std::vector<uint64_t> &keys,
+                   BounceLevel &out, uint64_t seed = 12345, int device = 0) {
+    if (org3.size() != dir3.size() || org3.size() % 3) throw Error(CGRT_ERR_INVALID, "bounce: org3 / dir3 are n x 3 doubles");
+    const size_t n = org3.size() / 3;
+    if ((!adj3.empty() && adj3.size() != 3 * n) || (!path.empty() && path.size() != n) || (!keys.empty() && keys.size() != n))
+        throw Error(CGRT_ERR_INVALID, "bounce: adj3, path and keys hold one entry per ray, or none");
+    out.step.assign(n, 0);
+    out.obj.assign(n, -1);
+    out.t.assign(n, 0.0);
+    out.pos.assign(3 * n, 0.0);
+    out.normal.assign(3 * n, 0.0);
+    out.value.assign(3 * n, 0.0);
+    out.child_org.assign(6 * n, 0.0);
+    out.child_dir.assign(6 * n, 0.0);
+    out.child_adj.assign(6 * n, 0.0);
+    out.child_path.assign(2 * n, 0u);
+    out.child_keys.assign(2 * n, 0u);
+    if (n == 0) return;
+    SceneBuilder sb;
+    for (const Object *o : objs) o->add_to(sb);
+    check(cgrt_scene_commit(sb.scene, device));
+    cgrt_rays r{};
+    r.n = (int64_t)n;
+    r.org3 = org3.data();
+    r.dir3 = dir3.data();
+    r.keys = keys.empty() ? nullptr : keys.data();
+    r.seed = seed;
+    r.max_depth = 1;
+    cgrt_bounce b{};
+    b.adj3 = adj3.empty() ? nullptr : adj3.data();
+    b.path = path.empty() ? nullptr : path.data();
+    b.step = out.step.data();
+    b.hit_obj = out.obj.data();
+    b.hit_t = out.t.data();
+    b.pos3 = out.pos.data();
+    b.normal3 = out.normal.data();
+    b.value3 = out.value.data();
+    b.child_org3 = out.child_org.data();
+    b.child_dir3 = out.child_dir.data();
+    b.child_adj3 = out.child_adj.data();
+    b.child_path = out.child_path.data();
+    b.child_keys = out.child_keys.data();
+    check(cgrt_bounce_rays_host(sb.scene, &r, &b, nullptr));
+}
+
 // ---- the whole of render() + main()'s PNG loop: main.cpp:169-258, 403-412 ---------------------------------------
 // Photon-pass constants of the reference as runtime fields with the same defaults.
 struct PhotonParams {
