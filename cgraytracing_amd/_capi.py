@@ -116,6 +116,15 @@ class Bounce(C.Structure):
                 ("reserved", C.c_void_p * 2)]  # 15 pointers, 120 bytes
 
 
+class Wavefront(C.Structure):
+    _fields_ = [("max_depth", C.c_int32), ("pad_", C.c_int32), ("min_adj", C.c_double), ("work_bytes", C.c_int64),
+                ("acc3", C.c_void_p), ("nhit", C.c_void_p), ("hp9", C.c_void_p), ("hp_ray", C.c_void_p), ("hp_path", C.c_void_p),
+                ("hp_cap", C.c_uint64), ("reserved", C.c_void_p * 2)]  # 88 bytes
+
+
+WAVEFRONT_MAX_DEPTH = 31
+
+
 class RayPixels(C.Structure):
     _fields_ = [("width", C.c_int32), ("rows", C.c_int32), ("spp", C.c_int32), ("pad_", C.c_int32), ("pixel", C.c_void_p)]
 
@@ -224,6 +233,11 @@ SIGNATURES = {
     "cgrt_bounce_rays": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(Bounce), C.c_void_p, C.c_void_p]),
     "cgrt_bounce_rays_host": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(Bounce), C.c_void_p]),
     "cgrt_bounce_rays_variant": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.c_char_p, C.c_size_t]),
+    "cgrt_wavefront_rays": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(Wavefront), C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "cgrt_wavefront_rays_host": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(Wavefront), C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cgrt_wavefront_rays_variant": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.c_char_p, C.c_size_t]),
+    "cgrt_scene_last_wavefront": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "cgrt_scene_last_wavefront_rays": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cgrt_camera_rays": (C.c_int, [C.POINTER(Camera), C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cgrt_camera_rays_host": (C.c_int, [C.POINTER(Camera), C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cgrt_intersect_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,

@@ -43,6 +43,7 @@
 #include "cgrt_rays.hpp"
 #include "cgrt_occlusion.hpp"
 #include "cgrt_bounce.hpp"
+#include "cgrt_wavefront.hpp"
 #include "cgrt_hit_attr.hpp"
 
 using namespace cgrt;
@@ -191,6 +192,9 @@ struct cgrt_scene {
     // cgrt_ray_hit_attributes' prim: per record of dev.tris the triangle's index in its tree's construction order.  Built and
     // uploaded by the first call that asks for prim (a scene that never asks pays nothing); immutable afterwards
     mutable GrowBuf tri_ids;
+    // cgrt_wavefront_rays: ray queues and parked Hitpoints, the sort's temporary storage, and what the last call did
+    mutable GrowBuf wavefront_work, wavefront_sort;
+    mutable WavefrontLast wavefront_last;
 };
 
 template <class T>

@@ -1,27 +1,30 @@
 // Caller-supplied rays: the ray-list kernels' dispatch table (cgrt_variants.h), their one launch path over rays_plan
 // (cgrt_rays_plan.h), the argument checks and the C entry points -- full trace and nearest-hit query, Hitpoint capture, occlusion,
-// bounce, camera rays, hit attributes.  Part of libcgrt.so; included by cgrt_hip.hip, which has the handle, the checked launch and the
+// bounce, wavefront trace, camera rays, hit attributes.  Part of libcgrt.so; included by cgrt_hip.hip, which has the handle, the checked launch and the
 // host staging.
 
-// The table's rows: a variant's trace_rays_kernel and, where the variant has one, its capture, occlusion and bounce forms
+// The table's rows: a variant's trace_rays_kernel and, where the variant has one, its capture, occlusion, bounce and wavefront forms
 using RaysKernel = void (*)(DeviceScene, RayParams, unsigned long long *);
 using CaptureKernel = void (*)(DeviceScene, RayParams, RaySink);
 using OcclusionKernel = void (*)(DeviceScene, OccParams, unsigned long long *);
 using BounceKernel = void (*)(DeviceScene, BounceParams, unsigned long long *);
+using WavefrontKernel = void (*)(DeviceScene, WavefrontParams, unsigned long long *);
 struct RayKernels {
     int id;  // RayFlags::id()
     RaysKernel trace;
     CaptureKernel capture;      // nullptr unless has_capture
     OcclusionKernel occlusion;  // nullptr unless has_occlusion
     BounceKernel bounce;        // nullptr unless has_bounce
+    WavefrontKernel wavefront;  // nullptr unless has_bounce
 };
 template <bool T, bool B, bool G, bool P, bool S, bool SP, bool F, int NT>
 static constexpr RayKernels ray_kernels_row() {
     constexpr RayFlags f{T, B, G, P, S, SP, F, NT};
-    RayKernels r{f.id(), &trace_rays_kernel<T, B, G, P, S, SP, F, NT>, nullptr, nullptr, nullptr};
+    RayKernels r{f.id(), &trace_rays_kernel<T, B, G, P, S, SP, F, NT>, nullptr, nullptr, nullptr, nullptr};
     if constexpr (has_capture(f)) r.capture = &capture_rays_kernel<T, B, G, P, SP, NT>;
     if constexpr (has_occlusion(f)) r.occlusion = &occlusion_rays_kernel<T, B, P, S, SP, NT>;
     if constexpr (has_bounce(f)) r.bounce = &bounce_rays_kernel<T, B, P, S, SP, NT>;
+    if constexpr (has_bounce(f)) r.wavefront = &wavefront_step_kernel<T, B, P, S, SP, NT>;
     return r;
 }
 #define CGRT_X(T, B, G, P, S, SP, F, NT) ray_kernels_row<T != 0, B != 0, G != 0, P != 0, S != 0, SP != 0, F != 0, NT>(),
@@ -43,12 +46,12 @@ static RaysPlan rays_plan_for(const cgrt_scene *s, const cgrt_rays *rays, RaysKi
 }
 // ... refused where no kernel of `kind` was built for the plan's variant
 static int rays_launch(const cgrt_scene *s, const cgrt_rays *rays, RaysKind kind, RaysLaunch &L) {
-    static const char *const form[] = {"", "", "capture ", "occlusion ", "bounce "};
+    static const char *const form[] = {"", "", "capture ", "occlusion ", "bounce ", "wavefront "};
     L.plan = rays_plan_for(s, rays, kind);
     L.dev = with_resident(s->dev, L.plan.resident);
     L.row = variant_row(kRayKernels, L.plan.k);
     if (!L.row || (kind == RaysKind::Capture && !L.row->capture) || (kind == RaysKind::Occlusion && !L.row->occlusion) ||
-        (kind == RaysKind::Bounce && !L.row->bounce))
+        (kind == RaysKind::Bounce && !L.row->bounce) || (kind == RaysKind::Wavefront && !L.row->wavefront))
         return fail(CGRT_ERR_UNSUPPORTED, std::string(L.plan.what()) + ": no " + form[(int)kind] + "kernel built for this variant");
     return CGRT_OK;
 }
@@ -63,7 +66,7 @@ static int ray_queue(const cgrt_scene *s, size_t tail, hipStream_t st, unsigned 
     *queue = reinterpret_cast<unsigned int *>(s->scratch.p);
     return CGRT_OK;
 }
-// what RayParams, OccParams and BounceParams all read of a ray list
+// what RayParams, OccParams, BounceParams and WavefrontParams all read of a ray list
 template <class P>
 static void fill_ray_inputs(P &p, const cgrt_rays *r, unsigned int *queue) {
     p.n = r->n;
@@ -106,6 +109,16 @@ static int check_occlusion(const cgrt_scene *s, const cgrt_rays *r, const cgrt_o
 }
 static int check_bounce(const cgrt_scene *s, const cgrt_rays *r, const cgrt_bounce *b) {
     return check_ray_list(s, r, b != nullptr, nullptr, false, false);
+}
+static int check_wavefront(const cgrt_scene *s, const cgrt_rays *r, const cgrt_wavefront *wf) {
+    const char *own = nullptr;
+    if (wf) {
+        if (wf->max_depth < 1 || wf->max_depth > kWavefrontMaxDepth) own = "max_depth must be 1..31";
+        else if (!(wf->min_adj >= 0.0)) own = "min_adj must be >= 0";
+        else if (wf->work_bytes < 0) own = "negative work_bytes";
+        else if (wf->hp_cap > 0 && !wf->hp9 && !wf->hp_ray && !wf->hp_path) own = "hp_cap > 0 with null hp9, hp_ray and hp_path";
+    }
+    return check_ray_list(s, r, wf != nullptr, own, false, false);
 }
 static bool bounce_asks(const cgrt_bounce *b) {
     return b->step || b->hit_obj || b->hit_t || b->pos3 || b->normal3 || b->value3 || b->child_org3 || b->child_dir3 || b->child_adj3 ||
@@ -181,6 +194,205 @@ static int need_tri_ids(const cgrt_scene *s) {
         s->tri_ids.release();
         return fail(CGRT_ERR_DEVICE, std::string("hit-attribute triangle table: ") + hipGetErrorString(e));
     }
+    return CGRT_OK;
+}
+
+// ---- the wavefront trace (cgrt_wavefront.hpp, cgrt_wavefront_plan.h) ----
+// What the host reads back after every level: the slots asked for in the next level's queue and in the parked list, and the
+// slice's own counters.  It lives behind the queue's head in the handle's launch scratch (+256).
+struct WavefrontControl {
+    unsigned long long next_count, parked_count, cnt[CGRT_NCOUNTERS];
+};
+// The work memory carved into the two ray queues, the parked list and the sort's outputs: wavefront_bytes_used() bytes, the
+// 8-byte arrays ahead of the 4-byte ones
+struct WavefrontMem {
+    WavefrontQueue q[2];
+    WavefrontParked parked;
+    unsigned long long *key_out;
+    uint32_t *idx_out;
+};
+static WavefrontMem wavefront_carve(void *base, const WavefrontCaps &c, bool hp) {
+    unsigned char *p = static_cast<unsigned char *>(base);
+    auto take = [&p](size_t bytes) {
+        void *r = p;
+        p += bytes;
+        return r;
+    };
+    const size_t Q = (size_t)c.rays, P = (size_t)c.parked;
+    WavefrontMem m{};
+    for (WavefrontQueue &q : m.q) {
+        q.org = static_cast<double *>(take(Q * 24));
+        q.dir = static_cast<double *>(take(Q * 24));
+        q.adj = static_cast<double *>(take(Q * 24));
+    }
+    m.parked.val = static_cast<double *>(take(P * 24));
+    if (hp) {
+        m.parked.pos = static_cast<double *>(take(P * 24));
+        m.parked.nrm = static_cast<double *>(take(P * 24));
+    }
+    for (WavefrontQueue &q : m.q) q.key = static_cast<unsigned long long *>(take(Q * 8));
+    m.parked.key = static_cast<unsigned long long *>(take(P * 8));
+    m.key_out = static_cast<unsigned long long *>(take(P * 8));
+    for (WavefrontQueue &q : m.q) {
+        q.path = static_cast<uint32_t *>(take(Q * 4));
+        q.root = static_cast<uint32_t *>(take(Q * 4));
+    }
+    m.parked.idx = static_cast<uint32_t *>(take(P * 4));
+    m.idx_out = static_cast<uint32_t *>(take(P * 4));
+    m.parked.path = static_cast<uint32_t *>(take(P * 4));
+    return m;
+}
+
+// One slice's levels: roots [b, b + c) of the caller's arrays, level by level until max_depth, an empty level or an overflow.
+// *h is the control block as the last level left it, level_rays[] the rays each level traced.
+static int wavefront_levels(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_wavefront *wf, const WavefrontMem &mem,
+                            const WavefrontCaps &caps, bool park, long long b, long long c, unsigned int *queue, WavefrontControl *d_ctl,
+                            hipStream_t st, WavefrontControl *h, long long *level_rays, bool *overflow) {
+    *overflow = false;
+    HIP_TRY(hipMemsetAsync(d_ctl, 0, sizeof(WavefrontControl), st));
+    long long n_in = c;
+    unsigned long long rays_before = 0;
+    for (int level = 1; level <= wf->max_depth; level++) {
+        HIP_TRY(hipMemsetAsync(queue, 0, sizeof(unsigned int), st));
+        if (level > 1) HIP_TRY(hipMemsetAsync(&d_ctl->next_count, 0, sizeof(unsigned long long), st));
+        cgrt_rays lr = *rays;
+        lr.n = n_in;
+        RaysLaunch L;
+        int rc = rays_launch(s, &lr, RaysKind::Wavefront, L);
+        if (rc) return rc;
+        WavefrontParams wp{};
+        wp.n = n_in;
+        wp.queue = queue;
+        wp.seed = rays->seed;
+        if (level == 1) {  // the caller's arrays
+            wp.org = rays->org3 + 3 * b;
+            wp.dir = rays->dir3 + 3 * b;
+            wp.keys = rays->keys ? reinterpret_cast<const unsigned long long *>(rays->keys) + b : nullptr;
+            wp.first_index = rays->first_index + b;
+        } else {
+            const WavefrontQueue &in = mem.q[level & 1];
+            wp.org = in.org;
+            wp.dir = in.dir;
+            wp.adj = in.adj;
+            wp.keys = in.key;
+            wp.path = in.path;
+            wp.root = in.root;
+        }
+        wp.next = mem.q[(level + 1) & 1];
+        wp.next_cap = (unsigned long long)caps.rays;
+        if (park) wp.parked = mem.parked;
+        wp.parked_cap = (unsigned long long)caps.parked;
+        wp.next_count = &d_ctl->next_count;
+        wp.parked_count = &d_ctl->parked_count;
+        wp.min_adj = wf->min_adj;
+        wp.last = level == wf->max_depth;
+        if ((rc = launch_rays(s, L, L.row->wavefront, st, wp, d_ctl->cnt))) return rc;
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h, d_ctl, sizeof(WavefrontControl), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        level_rays[level - 1] = (long long)(h->cnt[CGRT_CNT_RAYS] - rays_before);
+        rays_before = h->cnt[CGRT_CNT_RAYS];
+        if (h->next_count > (unsigned long long)caps.rays || h->parked_count > (unsigned long long)caps.parked) {
+            *overflow = true;
+            return CGRT_OK;
+        }
+        if (h->next_count == 0) break;
+        n_in = (long long)h->next_count;
+    }
+    return CGRT_OK;
+}
+
+// The slices of a call (WavefrontSlices): each one's levels, then the sort of its parked Hitpoints and their sums
+static int wavefront_run(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_wavefront *wf, unsigned long long *counters,
+                         uint64_t *hp_count, hipStream_t st) {
+    const bool hp = wf->hp_cap > 0 && wf->hp9;
+    const bool park = wf->acc3 || wf->nhit || wf->hp_cap > 0;
+    const long long work = wf->work_bytes ? wf->work_bytes : wavefront_default_work(rays->n, (long long)s->mem_total, hp);
+    const WavefrontCaps caps = wavefront_caps(work, hp);
+    WavefrontLast &last = s->wavefront_last;
+    last = WavefrontLast{};
+    if (caps.rays < 1 || caps.parked < 1)
+        return fail(CGRT_ERR_LIMIT, "wavefront trace: one ray needs at least " + std::to_string(wavefront_bytes_for(1, 1, hp)) +
+                                        " bytes of work memory, " + std::to_string(work) + " given");
+    if (s->wavefront_work.need((size_t)wavefront_bytes_used(caps, hp)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(CGRT_ERR_DEVICE, "cannot allocate " + std::to_string(wavefront_bytes_used(caps, hp)) + " bytes of wavefront work memory");
+    }
+    const WavefrontMem mem = wavefront_carve(s->wavefront_work.p, caps, hp);
+    unsigned int *queue = nullptr;
+    int rc = ray_queue(s, 256, st, &queue);
+    if (rc) return rc;
+    WavefrontControl *d_ctl = reinterpret_cast<WavefrontControl *>(reinterpret_cast<unsigned char *>(s->scratch.p) + 256);
+    static_assert(sizeof(WavefrontControl) <= 256, "the control block is the ray queue's tail");
+
+    unsigned long long hp_total = 0;
+    for (WavefrontSlices sl(rays->n, caps); !sl.done();) {
+        const long long b = sl.begin, c = sl.count();
+        WavefrontControl h{};
+        long long level_rays[kWavefrontMaxDepth] = {};
+        bool overflow = false;
+        if ((rc = wavefront_levels(s, rays, wf, mem, caps, park, b, c, queue, d_ctl, st, &h, level_rays, &overflow))) return rc;
+        if (overflow) {
+            const bool again = sl.overflowed();
+            last.slices = sl.slices;
+            last.halvings = sl.halvings;
+            if (again) continue;
+            const long long need = wavefront_bytes_for((long long)std::max(h.next_count, 1ull), (long long)std::max(h.parked_count, 1ull), hp);
+            return fail(CGRT_ERR_LIMIT, "wavefront trace: the tree of ray " + std::to_string(b) + " needs at least " + std::to_string(need) +
+                                            " bytes of work memory, " + std::to_string(work) + " given");
+        }
+        // nothing of the slice has been written so far: zeros for the roots without Hitpoints, then the sums in emission order
+        if (wf->acc3) HIP_TRY(hipMemsetAsync(wf->acc3 + 3 * b, 0, (size_t)c * 24, st));
+        if (wf->nhit) HIP_TRY(hipMemsetAsync(wf->nhit + b, 0, (size_t)c * 4, st));
+        const long long m = park ? (long long)h.parked_count : 0;
+        if (m > 0) {
+            size_t tmp_bytes = 0;
+            int deepest = 0;  // the slice's deepest level with a ray: no Hitpoint lies below it
+            for (int l = 0; l < kWavefrontMaxDepth; l++)
+                if (level_rays[l] > 0) deepest = l + 1;
+            const unsigned begin_bit = (unsigned)wavefront_key_begin_bit(deepest), end_bit = (unsigned)wavefront_key_end_bit(c);
+            HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, mem.parked.key, mem.key_out, mem.parked.idx, mem.idx_out, (unsigned)m,
+                                              begin_bit, end_bit, st));
+            if (s->wavefront_sort.need(tmp_bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(CGRT_ERR_DEVICE, "cannot allocate the wavefront sort's temporary storage");
+            }
+            HIP_TRY(rocprim::radix_sort_pairs(s->wavefront_sort.p, tmp_bytes, mem.parked.key, mem.key_out, mem.parked.idx, mem.idx_out,
+                                              (unsigned)m, begin_bit, end_bit, st));
+            WavefrontSumParams sp{};
+            sp.m = m;
+            sp.key = mem.key_out;
+            sp.idx = mem.idx_out;
+            sp.val = mem.parked.val;
+            sp.pos = mem.parked.pos;
+            sp.nrm = mem.parked.nrm;
+            sp.path = mem.parked.path;
+            sp.first_root = b;
+            sp.acc3 = wf->acc3;
+            sp.nhit = wf->nhit;
+            sp.hp9 = wf->hp9;
+            sp.hp_ray = reinterpret_cast<long long *>(wf->hp_ray);
+            sp.hp_path = wf->hp_path;
+            sp.hp_base = hp_total;
+            sp.hp_cap = wf->hp_cap;
+            hipLaunchKernelGGL(wavefront_sum_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, sp);
+            HIP_TRY(hipGetLastError());
+        }
+        if (counters) {
+            hipLaunchKernelGGL(wavefront_add_counters_kernel, dim3(1), dim3(64), 0, st, counters, d_ctl->cnt);
+            HIP_TRY(hipGetLastError());
+        }
+        hp_total += h.cnt[CGRT_CNT_HITPOINTS];
+        sl.finished();
+        last.slices = sl.slices;
+        last.halvings = sl.halvings;
+        for (int l = 0; l < kWavefrontMaxDepth; l++) {
+            last.rays[l] += level_rays[l];
+            if (level_rays[l] > 0 && l + 1 > last.levels) last.levels = l + 1;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (hp_count) *hp_count = hp_total;
     return CGRT_OK;
 }
 
@@ -361,6 +573,61 @@ int cgrt_bounce_rays_host(const cgrt_scene *s, const cgrt_rays *rays, const cgrt
     uint64_t *d_cnt = hs.out_always(counters, kCounterBytes, true);
     if ((rc = hs.error())) return rc;
     return hs.finish(cgrt_bounce_rays(s, &dr, &db, d_cnt, nullptr));
+}
+
+int cgrt_wavefront_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_wavefront *wf, uint64_t *counters, uint64_t *hp_count,
+                        void *stream) {
+    int rc = check_wavefront(s, rays, wf);
+    if (rc) return rc;
+    if (hp_count) *hp_count = 0;
+    if (rays->n == 0) return CGRT_OK;
+    ON_DEVICE(s->device);
+    return wavefront_run(s, rays, wf, reinterpret_cast<unsigned long long *>(counters), hp_count, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cgrt_wavefront_rays_variant(const cgrt_scene *s, const cgrt_rays *rays, char *name, size_t cap) {
+    if (!s || !rays || !name || cap == 0) return fail(CGRT_ERR_INVALID, "null argument");
+    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+    ON_DEVICE(s->device);
+    rays_plan_for(s, rays, RaysKind::Wavefront).name(RaysKind::Wavefront, name, cap);
+    return CGRT_OK;
+}
+
+int cgrt_wavefront_rays_host(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_wavefront *wf, uint64_t *counters, uint64_t *hp_count) {
+    int rc = check_wavefront(s, rays, wf);
+    if (rc) return rc;
+    if (hp_count) *hp_count = 0;
+    const size_t n = (size_t)rays->n;
+    if (n == 0) {
+        if (counters) std::memset(counters, 0, kCounterBytes);
+        return CGRT_OK;
+    }
+    ON_DEVICE(s->device);
+    HostStage hs;
+    const cgrt_rays dr = stage_rays(hs, rays, true);
+    cgrt_wavefront dw = *wf;
+    dw.acc3 = hs.out(wf->acc3, n * 24);
+    dw.nhit = hs.out(wf->nhit, n * 4);
+    dw.hp9 = hs.out(wf->hp9, (size_t)wf->hp_cap * 72, true);
+    dw.hp_ray = hs.out(wf->hp_ray, (size_t)wf->hp_cap * 8, true);
+    dw.hp_path = hs.out(wf->hp_path, (size_t)wf->hp_cap * 4, true);
+    uint64_t *d_cnt = hs.out_always(counters, kCounterBytes, true);
+    if ((rc = hs.error())) return rc;
+    return hs.finish(cgrt_wavefront_rays(s, &dr, &dw, d_cnt, hp_count, nullptr));
+}
+
+int cgrt_scene_last_wavefront(const cgrt_scene *s, int64_t *slices, int64_t *halvings, int32_t *levels) {
+    NEED_COMMITTED(s, true);
+    if (slices) *slices = s->wavefront_last.slices;
+    if (halvings) *halvings = s->wavefront_last.halvings;
+    if (levels) *levels = s->wavefront_last.levels;
+    return CGRT_OK;
+}
+
+int cgrt_scene_last_wavefront_rays(const cgrt_scene *s, int64_t *rays31) {
+    NEED_COMMITTED(s, rays31);
+    for (int l = 0; l < kWavefrontMaxDepth; l++) rays31[l] = s->wavefront_last.rays[l];
+    return CGRT_OK;
 }
 
 int cgrt_camera_rays(const cgrt_camera *cam, const cgrt_grid *grid, double *org3, double *dir3, uint64_t *keys, void *stream) {

@@ -1,7 +1,8 @@
 // The launch plan of a ray-list query in plain C++ (no HIP): from the scene's traits, what is asked and three numbers of the
 // device, the kernel variant (RayFlags, cgrt_variants.h), the objects resident in LDS, the dynamic LDS bytes, the persistent
-// workgroups and the names.  cgrt_trace_rays, the Hitpoint capture over a ray buffer, cgrt_occlusion_rays and cgrt_bounce_rays
-// (cgrt_ray_queries.hpp) launch what rays_plan decides; tests/native/rays_plan.cpp and bounce_plan.cpp check it on the CPU.
+// workgroups and the names.  cgrt_trace_rays, the Hitpoint capture over a ray buffer, cgrt_occlusion_rays, cgrt_bounce_rays and
+// every level of cgrt_wavefront_rays (cgrt_ray_queries.hpp) launch what rays_plan decides; tests/native/rays_plan.cpp,
+// bounce_plan.cpp and wavefront_plan.cpp check it on the CPU.
 #ifndef CGRT_RAYS_PLAN_H
 #define CGRT_RAYS_PLAN_H
 #include <algorithm>
@@ -9,7 +10,8 @@
 
 #include "cgrt_variants.h"
 
-enum class RaysKind { Full, First, Capture, Occlusion, Bounce };  // full trace, nearest-hit query, Hitpoint capture, any-hit query, one step of trace()
+// full trace, nearest-hit query, Hitpoint capture, any-hit query, one step of trace(), one level of the wavefront trace
+enum class RaysKind { Full, First, Capture, Occlusion, Bounce, Wavefront };
 struct RaysAsk {
     int max_depth;
     bool stats;  // CGRT_RAYS_STATS (the capture has no STATS form)
@@ -21,8 +23,11 @@ struct RaysDevice {
     size_t lds_limit;       // what a workgroup may use, static + dynamic
     size_t general_static;  // static LDS of the general variant's trace_rays_kernel (rays_general_flags); read only where rays_general
 };
-// the occlusion and the bounce query share the nearest-hit query's plan -- flags, resident objects, LDS
-static constexpr bool rays_first(RaysKind k) { return k == RaysKind::First || k == RaysKind::Occlusion || k == RaysKind::Bounce; }
+// the occlusion query, the bounce query and the wavefront trace's levels share the nearest-hit query's plan -- flags, resident
+// objects, LDS
+static constexpr bool rays_first(RaysKind k) {
+    return k == RaysKind::First || k == RaysKind::Occlusion || k == RaysKind::Bounce || k == RaysKind::Wavefront;
+}
 // More top-level objects than the LDS list holds, not all of them spheres: the most general body (trees, Bezier, pending rays
 // unless only the first hit is asked for), with as many objects resident as fit beside its other LDS; the rest are read from `objs`
 static constexpr bool rays_general(const cgrt::DeviceScene &d) { return d.n_objs > d.n_lds && !d.all_spheres; }
@@ -48,6 +53,9 @@ struct RaysPlan {
                           (int)k.sph, (int)k.stats, (int)k.spill, k.nt);
         else if (kind == RaysKind::Bounce)
             std::snprintf(buf, cap, "bounce_rays_kernel<TREES=%d,BEZ=%d,SPH=%d,STATS=%d,SPILL=%d,NT=%d>", (int)k.trees, (int)k.bez,
+                          (int)k.sph, (int)k.stats, (int)k.spill, k.nt);
+        else if (kind == RaysKind::Wavefront)
+            std::snprintf(buf, cap, "wavefront_step_kernel<TREES=%d,BEZ=%d,SPH=%d,STATS=%d,SPILL=%d,NT=%d>", (int)k.trees, (int)k.bez,
                           (int)k.sph, (int)k.stats, (int)k.spill, k.nt);
         else
             std::snprintf(buf, cap, "trace_rays_kernel<TREES=%d,BEZ=%d,GLASS=%d,SPH=%d,STATS=%d,SPILL=%d,FIRST=%d,NT=%d>", (int)k.trees,

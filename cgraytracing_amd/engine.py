@@ -668,6 +668,134 @@ class Scene:
         check(self._L.cgrt_bounce_rays_variant(self._h, C.byref(r), buf, len(buf)))
         return buf.value.decode()
 
+    # ---- wavefront trace of caller-supplied rays: any depth, the depth loop inside the library ----
+    _WAVEFRONT = ("acc", "nhit", "hp")
+
+    def _wavefront_want(self, what, want):
+        want = tuple(want)
+        if any(w not in self._WAVEFRONT for w in want):
+            raise ValueError("%s: want is a subset of %r" % (what, self._WAVEFRONT))
+        return want
+
+    def last_wavefront(self):
+        """What the last wavefront call on this scene did (cgrt_scene_last_wavefront, _rays): dict(slices, halvings, levels,
+        rays_per_level (the rays traced at levels 1 .. levels))."""
+        sl, hv, lv = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        check(self._L.cgrt_scene_last_wavefront(self._h, C.byref(sl), C.byref(hv), C.byref(lv)))
+        rays = np.zeros(_capi.WAVEFRONT_MAX_DEPTH, np.int64)
+        check(self._L.cgrt_scene_last_wavefront_rays(self._h, rays.ctypes.data))
+        return dict(slices=int(sl.value), halvings=int(hv.value), levels=int(lv.value), rays_per_level=[int(x) for x in rays[:lv.value]])
+
+    def wavefront(self, org, dirs, keys=None, max_depth=8, min_adj=0.0, seed=12345, first_index=0, want=("acc", "nhit"), hp_cap=None,
+                  work_bytes=0, stats=False, out=None, stream=None, counters=None):
+        """cgrt_wavefront_rays on torch tensors: every ray traced to max_depth levels (1..31) as a wavefront on the device -- the
+        depth loop over bounce with its compaction and its emission-order sum, inside the library.  org, dirs float64 [n,3]
+        contiguous on the scene's device, keys int64 [n] or None.  min_adj: a child whose throughput has max(x,y,z) < min_adj
+        is not spawned (0 drops nothing).  want: "acc" (float64 [n,3]) and "nhit" (int32 [n]) as trace_rays gives them for
+        max_depth <= 5; "hp": the Hitpoint records by ray, then emission order -- hp9 (float64 [m,9]: value, pos, normal), hp_ray
+        (int64 [m]), hp_path (int32 [m]), m = min(hp_count, hp_cap); hp_cap defaults to 4n.  work_bytes: device work memory
+        (0 = automatic); the results never depend on it.  out: dict of preallocated tensors (acc, nhit; hp9, hp_ray, hp_path
+        of hp_cap rows).  The call runs on torch's current stream (or `stream`) and SYNCHRONISES it; counters (int64 [8]) are
+        ADDED to.  Returns a dict of the tensors, "counters", "hp_count" and last_wavefront()'s entries."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        n = self._ray_tensors("wavefront", org, dirs, keys)
+        want = self._wavefront_want("wavefront", want)
+        if not (isinstance(max_depth, int) and 1 <= max_depth <= _capi.WAVEFRONT_MAX_DEPTH):
+            raise ValueError("wavefront: max_depth must be 1..%d" % _capi.WAVEFRONT_MAX_DEPTH)
+        if not (min_adj >= 0.0) or work_bytes < 0 or (hp_cap is not None and hp_cap < 0):
+            raise ValueError("wavefront: min_adj, work_bytes and hp_cap must be >= 0")
+        cap = int(hp_cap if hp_cap is not None else 4 * n) if "hp" in want else 0
+        shapes = {}
+        if "acc" in want:
+            shapes["acc"] = ((n, 3), torch.float64)
+        if "nhit" in want:
+            shapes["nhit"] = ((n,), torch.int32)
+        if cap > 0:
+            shapes.update(hp9=((cap, 9), torch.float64), hp_ray=((cap,), torch.int64), hp_path=((cap,), torch.int32))
+        res = {}
+        for name, (shape, dtype) in shapes.items():
+            t = out.get(name) if out else None
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=dev)
+            elif not (isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and
+                      t.device == dev):
+                raise ValueError("wavefront: out[%r] must be a contiguous %s %r tensor on %s" % (name, dtype, shape, dev))
+            res[name] = t
+        if counters is None:
+            counters = torch.zeros((_capi.CGRT_NCOUNTERS,), dtype=torch.int64, device=dev)
+        elif not (counters.dtype == torch.int64 and counters.numel() == _capi.CGRT_NCOUNTERS and counters.is_contiguous() and
+                  counters.device == dev):
+            raise ValueError("wavefront: counters must be a contiguous int64 [8] tensor on %s" % (dev,))
+        ptr = lambda k: res[k].data_ptr() if k in res else None
+        r = _capi.Rays(n, org.data_ptr(), dirs.data_ptr(), keys.data_ptr() if keys is not None else None, first_index, seed, 1,
+                       _capi.RAYS_STATS if stats else 0)
+        w = _capi.Wavefront(max_depth, 0, float(min_adj), int(work_bytes), ptr("acc"), ptr("nhit"), ptr("hp9"), ptr("hp_ray"),
+                            ptr("hp_path"), cap)
+        cnt = C.c_uint64(0)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(self._L.cgrt_wavefront_rays(self._h, C.byref(r), C.byref(w), counters.data_ptr(), C.byref(cnt), C.c_void_p(st)))
+        m = min(int(cnt.value), cap)
+        for k in ("hp9", "hp_ray", "hp_path"):
+            if k in res:
+                res[k] = res[k][:m]
+        if "hp" in want and cap == 0:
+            res.update(hp9=torch.empty((0, 9), dtype=torch.float64, device=dev), hp_ray=torch.empty((0,), dtype=torch.int64, device=dev),
+                       hp_path=torch.empty((0,), dtype=torch.int32, device=dev))
+        res.update(counters=counters, hp_count=int(cnt.value))
+        res.update(self.last_wavefront() if n > 0 else dict(slices=0, halvings=0, levels=0, rays_per_level=[]))
+        return res
+
+    def wavefront_host(self, org, dirs, keys=None, max_depth=8, min_adj=0.0, seed=12345, first_index=0, want=("acc", "nhit"),
+                       hp_cap=None, work_bytes=0, stats=False):
+        """Synchronous form of wavefront on numpy arrays (no torch needed): dict of acc, nhit (uint32), hp9, hp_ray, hp_path
+        (uint32) -- those in `want` --, counters (uint64 [8]), nrays, nhp, hp_count and last_wavefront()'s entries."""
+        org = np.ascontiguousarray(org, np.float64).reshape(-1, 3)
+        dirs = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
+        n = len(org)
+        if len(dirs) != n:
+            raise ValueError("wavefront_host: org and dirs differ in length")
+        if keys is not None:
+            keys = np.ascontiguousarray(keys, np.uint64)
+            if keys.shape != (n,):
+                raise ValueError("wavefront_host: keys must have one entry per ray")
+        want = self._wavefront_want("wavefront_host", want)
+        if not (isinstance(max_depth, int) and 1 <= max_depth <= _capi.WAVEFRONT_MAX_DEPTH):
+            raise ValueError("wavefront_host: max_depth must be 1..%d" % _capi.WAVEFRONT_MAX_DEPTH)
+        if not (min_adj >= 0.0) or work_bytes < 0 or (hp_cap is not None and hp_cap < 0):
+            raise ValueError("wavefront_host: min_adj, work_bytes and hp_cap must be >= 0")
+        cap = int(hp_cap if hp_cap is not None else 4 * n) if "hp" in want else 0
+        res = {}
+        if "acc" in want:
+            res["acc"] = np.zeros((n, 3), np.float64)
+        if "nhit" in want:
+            res["nhit"] = np.zeros(n, np.uint32)
+        if "hp" in want:
+            res.update(hp9=np.zeros((cap, 9), np.float64), hp_ray=np.zeros(cap, np.int64), hp_path=np.zeros(cap, np.uint32))
+        cnt = np.zeros((_capi.CGRT_NCOUNTERS,), np.uint64)
+        ptr = lambda k: res[k].ctypes.data if k in res and res[k].size else None
+        r = _capi.Rays(n, org.ctypes.data, dirs.ctypes.data, keys.ctypes.data if keys is not None else None, first_index, seed, 1,
+                       _capi.RAYS_STATS if stats else 0)
+        w = _capi.Wavefront(max_depth, 0, float(min_adj), int(work_bytes), ptr("acc"), ptr("nhit"), ptr("hp9"), ptr("hp_ray"),
+                            ptr("hp_path"), cap)
+        hpc = C.c_uint64(0)
+        check(self._L.cgrt_wavefront_rays_host(self._h, C.byref(r), C.byref(w), cnt.ctypes.data, C.byref(hpc)))
+        m = min(int(hpc.value), cap)
+        for k in ("hp9", "hp_ray", "hp_path"):
+            if k in res:
+                res[k] = res[k][:m]
+        res.update(counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]), nhp=int(cnt[_capi.CNT_HITPOINTS]), hp_count=int(hpc.value))
+        res.update(self.last_wavefront() if n > 0 else dict(slices=0, halvings=0, levels=0, rays_per_level=[]))
+        return res
+
+    def wavefront_variant(self, stats=False):
+        """Name of the wavefront_step_kernel instantiation wavefront launches on this scene (cgrt_wavefront_rays_variant)."""
+        r = _capi.Rays(1, None, None, None, 0, 0, 1, _capi.RAYS_STATS if stats else 0)
+        buf = C.create_string_buffer(160)
+        check(self._L.cgrt_wavefront_rays_variant(self._h, C.byref(r), buf, len(buf)))
+        return buf.value.decode()
+
     def rays_variant(self, max_depth=5, want=("acc", "nhit", "hit"), stats=False):
         """Name of the trace_rays_kernel instantiation trace_rays launches for these arguments (cgrt_trace_rays_variant)."""
         full = 1 if ("acc" in want or "nhit" in want) else None

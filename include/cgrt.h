@@ -18,7 +18,8 @@
  * Threading: launches on ONE scene handle must be ordered by the caller (same stream, or events between streams) --
  * a handle owns device scratch that consecutive launches reuse (CGRT_GRID_SPLIT_SAMPLES chunk sums; the schedule of a
  * cost-ordered frame; the tile order of an image-order one; the queue counter of cgrt_trace_rays, cgrt_trace_rays_hitpoints and cgrt_ppm_session_create_rays, which
- * are such launches (cgrt_occlusion_rays and cgrt_bounce_rays use that counter too); cgrt_ray_hit_attributes is one too: its first call that asks for `prim` builds a table the handle keeps).
+ * are such launches (cgrt_occlusion_rays and cgrt_bounce_rays use that counter too); cgrt_ray_hit_attributes is one too: its first call that asks for `prim` builds a table the handle keeps;
+ * cgrt_wavefront_rays uses the queue counter and keeps its work memory on the handle, and it synchronises its stream, so it cannot be stream-captured).
  * All geometry is IEEE double, like the reference (Vec3 = 3 x double, vec3.h:11-30).
  */
 #ifndef CGRT_H
@@ -42,7 +43,9 @@ extern "C" {
                             (hit attributes of caller-supplied rays); cgrt_occlusion, CGRT_RAYS_SKIP_TRANSPARENT,
                             cgrt_occlusion_rays, cgrt_occlusion_rays_host, cgrt_occlusion_rays_variant (occlusion queries);
                             cgrt_bounce, CGRT_STEP_*, cgrt_bounce_rays, cgrt_bounce_rays_host, cgrt_bounce_rays_variant
-                            (bounce queries) */
+                            (bounce queries); cgrt_wavefront, cgrt_wavefront_rays, cgrt_wavefront_rays_host,
+                            cgrt_wavefront_rays_variant, cgrt_scene_last_wavefront, cgrt_scene_last_wavefront_rays
+                            (wavefront trace) */
 
 enum {
     CGRT_OK = 0,
@@ -539,6 +542,64 @@ int cgrt_bounce_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_boun
 int cgrt_bounce_rays_host(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_bounce *bounce, uint64_t *counters);
 /* Name of the bounce_rays_kernel instantiation cgrt_bounce_rays would launch for (scene, rays); only rays->flags matters. */
 int cgrt_bounce_rays_variant(const cgrt_scene *s, const cgrt_rays *rays, char *name, size_t cap);
+
+/* ---- wavefront trace: caller-supplied rays to any depth, inside the library -----------------------------------------
+ * The depth loop over cgrt_bounce_rays, on the device: every ray of the list is traced to wf->max_depth levels (1..31, as far
+ * as path < 2^31 reaches), one launch per level.  A level's surviving children are appended to a ray queue in device work
+ * memory, its Hitpoints are parked with their place in the ray tree; after the last level (or the first empty one) the parked
+ * Hitpoints are sorted into emission order and each ray's values are added in that order in fp64 from 0.  For max_depth <= 5
+ * acc3, nhit, CGRT_CNT_RAYS / _HITPOINTS and the records are cgrt_trace_rays' and cgrt_trace_rays_hitpoints' bit for bit; for
+ * any depth they are those of the caller's loop over cgrt_bounce_rays summed in emission order.
+ *   Rays: every rule of the ray-list calls holds -- dir = (0,0,0) marks a ray that is not traced and not counted, with zero
+ *   results; keys, or first_index and seed, key the draws; at most 2^36 rays; CGRT_RAYS_STATS counts node and triangle tests;
+ *   the other flags and rays->max_depth are not looked at.
+ *   min_adj: a child whose throughput has max(x, y, z) < min_adj is not spawned (the test is strict: 0 drops nothing, and
+ *   children with adj == 0 are kept -- the full trace's bits and counts).
+ *   work_bytes: the rays are processed in slices in ray order; a slice whose queue or parked list does not fit the work memory
+ *   is redone in halves (nothing of it has been written, its counters are added only when it finishes).  The results never
+ *   depend on work_bytes.  A single ray whose tree does not fit: CGRT_ERR_LIMIT, the message names the bytes needed and given.
+ *   0 = room for a level of 2n rays and 8n Hitpoints, at most min(1 GiB, an eighth of the device's memory).
+ *   Records: hp9 / hp_ray / hp_path get all rays' Hitpoints by ray index, then emission order; records at or beyond hp_cap
+ *   are dropped, *hp_count counts them all.
+ * counters (may be NULL) are ADDED to: CGRT_CNT_RAYS and _HITPOINTS are deterministic and equal the bounce loop's sums;
+ * CGRT_CNT_WAVE_ITERS measures the run and may differ from run to run (the order in which waves append to the queues is not
+ * fixed, so a level's rays meet different lanes; no result depends on that order).
+ * A null scene, rays or wf, a negative n, max_depth outside 1..31, a negative or NaN min_adj, a negative work_bytes, hp_cap > 0
+ * with hp9, hp_ray and hp_path all NULL: CGRT_ERR_INVALID; more than 2^36 rays: CGRT_ERR_LIMIT; n == 0 is valid and does
+ * nothing (the scene is not even looked at); otherwise an uncommitted scene: CGRT_ERR_INVALID -- all before any device is
+ * touched. */
+typedef struct cgrt_wavefront {
+    int32_t  max_depth;   /* 1..31; rays->max_depth is not looked at                                                       */
+    int32_t  pad_;
+    double   min_adj;     /* >= 0; a child whose child_adj has max(x,y,z) < min_adj (strict) is not spawned; 0 drops nothing */
+    int64_t  work_bytes;  /* device work memory for ray queues and parked Hitpoints; 0 = automatic.  The result never
+                             depends on it                                                                                 */
+    /* out, DEVICE pointers (HOST in the _host form), each may be NULL */
+    double   *acc3;       /* [n][3] as cgrt_ray_results.acc3: fp64 sum from 0 in emission order                            */
+    uint32_t *nhit;       /* [n]                                                                                           */
+    double   *hp9;        /* [hp_cap][9] {value3, pos3, normal3 after the flip}                                            */
+    int64_t  *hp_ray;     /* [hp_cap] the record's ray                                                                     */
+    uint32_t *hp_path;    /* [hp_cap] its place in the ray's tree                                                          */
+    uint64_t  hp_cap;     /* records beyond it are dropped (the last ones); *hp_count still counts them                    */
+    void     *reserved[2];/* not looked at; set to NULL                                                                    */
+} cgrt_wavefront;         /* 88 bytes */
+
+/* DEVICE pointers on the scene's device.  The call enqueues on `stream` and SYNCHRONISES it: the host reads a few counters
+ * back after every level of every slice, and once at the end.  It therefore cannot be captured into a graph.  This is a launch
+ * on the scene handle (Threading above): it uses the handle's ray-queue counter and work memory the handle keeps.
+ * hp_count (HOST, may be NULL): Hitpoints produced. */
+int cgrt_wavefront_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_wavefront *wf, uint64_t *counters,
+                        uint64_t *hp_count, void *stream);
+/* HOST pointers: allocates device buffers, runs, synchronises and copies back (counters are overwritten). */
+int cgrt_wavefront_rays_host(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_wavefront *wf, uint64_t *counters,
+                             uint64_t *hp_count);
+/* Name of the wavefront_step_kernel instantiation cgrt_wavefront_rays would launch for (scene, rays); only rays->flags
+ * matters. */
+int cgrt_wavefront_rays_variant(const cgrt_scene *s, const cgrt_rays *rays, char *name, size_t cap);
+/* What the last cgrt_wavefront_rays on the handle did: slices finished, slices redone in halves, and the deepest level that
+ * traced a ray; rays31 (may be NULL): rays traced per level, [31], over the finished slices.  Any pointer may be NULL. */
+int cgrt_scene_last_wavefront(const cgrt_scene *s, int64_t *slices, int64_t *halvings, int32_t *levels);
+int cgrt_scene_last_wavefront_rays(const cgrt_scene *s, int64_t *rays31);
 
 /* The primary rays cgrt_trace_grid starts for sample `sample_offset + k`, k in [0, spp), of every pixel of the grid's rows
  * (contiguous or striped): ray index = (k * rows + local row) * width + w.  org3 / dir3 / keys as in cgrt_rays (any may be

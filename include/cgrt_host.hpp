@@ -489,6 +489,61 @@ inline void bounce(const std::vector<Object *> &objs, const std::vector<double> 
     check(cgrt_bounce_rays_host(sb.scene, &r, &b, nullptr));
 }
 
+// The depth loop over bounce() inside the library (cgrt_wavefront_rays_host): every ray traced to max_depth levels (1..31), its
+// Hitpoint values summed in emission order -- trace_rays' sum for max_depth <= 5, and beyond.  min_adj: a child whose throughput
+// has max(x, y, z) < min_adj is not spawned.  hp_cap > 0: the Hitpoint records too, by ray, then emission order.
+struct WavefrontResult {
+    std::vector<double> acc;        // [n][3]
+    std::vector<uint32_t> nhit;     // [n]
+    std::vector<double> hp9;        // [min(hp_count, hp_cap)][9] value, pos, normal
+    std::vector<int64_t> hp_ray;    // the record's ray
+    std::vector<uint32_t> hp_path;  // its place in the ray's tree
+    uint64_t hp_count = 0, rays = 0;
+    int64_t slices = 0, halvings = 0;
+    int32_t levels = 0;
+};
+inline void wavefront(const std::vector<Object *> &objs, const std::vector<double> &org3, const std::vector<double> &dir3,
+                      const std::vector<uint64_t> &keys, int max_depth, WavefrontResult &out, double min_adj = 0.0, uint64_t hp_cap = 0,
+                      uint64_t seed = 12345, int64_t work_bytes = 0, int device = 0) {
+    if (org3.size() != dir3.size() || org3.size() % 3) throw Error(CGRT_ERR_INVALID, "wavefront: org3 / dir3 are n x 3 doubles");
+    const size_t n = org3.size() / 3;
+    if (!keys.empty() && keys.size() != n) throw Error(CGRT_ERR_INVALID, "wavefront: keys hold one entry per ray, or none");
+    out = WavefrontResult();
+    out.acc.assign(3 * n, 0.0);
+    out.nhit.assign(n, 0u);
+    out.hp9.assign(9 * (size_t)hp_cap, 0.0);
+    out.hp_ray.assign((size_t)hp_cap, 0);
+    out.hp_path.assign((size_t)hp_cap, 0u);
+    SceneBuilder sb;
+    for (const Object *o : objs) o->add_to(sb);
+    if (n > 0) check(cgrt_scene_commit(sb.scene, device));
+    cgrt_rays r{};
+    r.n = (int64_t)n;
+    r.org3 = org3.data();
+    r.dir3 = dir3.data();
+    r.keys = keys.empty() ? nullptr : keys.data();
+    r.seed = seed;
+    r.max_depth = 1;
+    cgrt_wavefront w{};
+    w.max_depth = max_depth;
+    w.min_adj = min_adj;
+    w.work_bytes = work_bytes;
+    w.acc3 = out.acc.data();
+    w.nhit = out.nhit.data();
+    w.hp9 = hp_cap ? out.hp9.data() : nullptr;
+    w.hp_ray = hp_cap ? out.hp_ray.data() : nullptr;
+    w.hp_path = hp_cap ? out.hp_path.data() : nullptr;
+    w.hp_cap = hp_cap;
+    uint64_t counters[CGRT_NCOUNTERS] = {};
+    check(cgrt_wavefront_rays_host(sb.scene, &r, &w, counters, &out.hp_count));
+    out.rays = counters[CGRT_CNT_RAYS];
+    const size_t m = (size_t)(out.hp_count < hp_cap ? out.hp_count : hp_cap);
+    out.hp9.resize(9 * m);
+    out.hp_ray.resize(m);
+    out.hp_path.resize(m);
+    if (n > 0) check(cgrt_scene_last_wavefront(sb.scene, &out.slices, &out.halvings, &out.levels));
+}
+
 // ---- the whole of render() + main()'s PNG loop: main.cpp:169-258, 403-412 ---------------------------------------
 // Photon-pass constants of the reference as runtime fields with the same defaults.
 struct PhotonParams {

@@ -70,6 +70,10 @@ def demangle_variant(name):
     if m:
         t = [int(x) for x in m.groups()]
         return "bounce_rays_kernel<TREES=%d,BEZ=%d,SPH=%d,STATS=%d,SPILL=%d,NT=%d>" % tuple(t)
+    m = re.match(r"_Z21wavefront_step_kernelIL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)ELi(\d+)EE", name)
+    if m:
+        t = [int(x) for x in m.groups()]
+        return "wavefront_step_kernel<TREES=%d,BEZ=%d,SPH=%d,STATS=%d,SPILL=%d,NT=%d>" % tuple(t)
     m = re.search(r"19photon_trace_kernelILb(\d)ELb(\d)ELb(\d)EE", name)
     if m:
         return "photon_trace_kernel<BEZ=%s,SPILL=%s,RAYS=%s>" % m.groups()
