@@ -52,6 +52,7 @@ GRID_RELAY_CHUNKS_FIRST, GRID_RELAY_MIRROR_FIRST, GRID_RELAY_INTERLEAVED, GRID_R
 GRID_NO_LENS_STAGE, GRID_NO_SURE_TILES = 131072, 262144
 GRID_RELAY_COST_START, GRID_NO_RELAY_COST_START, GRID_RELAY_BOOST, GRID_NO_RELAY_BOOST = 524288, 1048576, 2097152, 4194304
 GRID_NO_LENS_TABLE, GRID_LENS_TABLE = 8388608, 16777216
+GRID_NO_INSIDE_TRIPS = 33554432
 
 
 class Photons(C.Structure):
@@ -140,6 +141,7 @@ RAYS_HITPOINTS = 4
 RAYS_SKIP_TRANSPARENT = 8
 STEP_NONE, STEP_HITPOINT, STEP_REFLECT, STEP_SPLIT = 0, 1, 2, 3  # cgrt_bounce.step
 PROBE_SQRT, PROBE_NORMALIZED, PROBE_SPHERE_LEN, PROBE_SPHERE_LEN_PAIR = 0, 1, 2, 4  # cgrt_math_probe's op (3 is none)
+PROBE_INSIDE_LOOP = 5  # cgrt_inside_probe's op
 
 # every symbol include/cgrt.h declares, with its signature
 _DP = C.POINTER(C.c_double)
@@ -243,6 +245,8 @@ SIGNATURES = {
     "cgrt_intersect_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "cgrt_math_probe": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "cgrt_scene_inside_spheres": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "cgrt_inside_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 _lib = None

@@ -1087,6 +1087,17 @@ void scene_traits(const HostScene &H, const std::vector<TreeRec> &trees, const C
             d.prun_end = j;
         }
     }
+    // rays that start inside a refracting sphere (cgrt_inside_sphere.h): a sphere-only scene whose list is all in LDS
+    d.inside = InsideTrait{};
+    if (d.all_spheres && d.n_objs == d.n_lds && d.n_objs <= kInsideSpheresMax) {
+        std::vector<InsideBall> balls;
+        std::vector<double> transp;
+        for (const ObjRec &o : objs) {
+            balls.push_back(InsideBall{{o.a[0], o.a[1], o.a[2]}, o.s0});
+            transp.push_back(o.transp);
+        }
+        d.inside = inside_trait(balls.data(), transp.data(), d.n_objs, true);
+    }
 }
 
 }  // namespace cgrt

@@ -1580,4 +1580,31 @@ __global__ void math_probe_kernel(int op, const double *__restrict__ in, long lo
     }
 }
 
+// function-level probe of the inside trips (cgrt_inside_probe, CGRT_PROBE_INSIDE_LOOP): the PAIR variants' sphere loop over a
+// committed sphere scene, once without candidates -- the pair loop -- and once with the trait `guarded`, for n rays
+// {origin(3), direction(3)} laid out over the waves as math_probe_kernel's elements are.  out[n][5] = t and id of the pair loop,
+// t and id of the guarded loop, and 1 where the element's wave took the one-by-one loop.  The object list is read from memory.
+__global__ void inside_loop_probe_kernel(DeviceScene sc, InsideTrait guarded, const double *__restrict__ in, long long n, double *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const V3 o = ld3(in + 6 * i), d = ld3(in + 6 * i + 3);
+    RayKey rk{0, 1, false, 0u};
+    LdsAux aux;
+    aux.bl = nullptr;
+    aux.lnodes = nullptr;
+    uint32_t nn = 0, nt = 0;
+    sc.inside = InsideTrait{};
+    const SceneHit a = intersect_scene<false, false, true, false, false, false, false, false, true>(sc.objs, sc.n_lds, sc.n_objs, sc, o, d, rk, true, aux, nn, nt);
+    sc.inside = guarded;
+    const SceneHit b = intersect_scene<false, false, true, false, false, false, false, false, true>(sc.objs, sc.n_lds, sc.n_objs, sc, o, d, rk, true, aux, nn, nt);
+    bool took = false;
+    for (int k = 0; k < kInsideMax && k < guarded.n && !took; k++)
+        took = __ballot(!starts_inside(o, ld3(sc.objs[guarded.idx[k]].a), guarded.rin2[k])) == 0ull;
+    out[5 * i] = a.t;
+    out[5 * i + 1] = (double)a.id;
+    out[5 * i + 2] = b.t;
+    out[5 * i + 3] = (double)b.id;
+    out[5 * i + 4] = took ? 1.0 : 0.0;
+}
+
 #endif

@@ -284,6 +284,7 @@ struct EyeKnobs {
     int lens_table = -1;    // LENS_TABLE: off / on (on: written by every launch that needs it), where the launch's flags say neither (-1: unset)
     long long lens_table_bytes = 0;  // LENS_TABLE_BYTES: >= 0 where set: the lens table's byte budget (default kLensTableBudget)
     bool lens_table_bytes_set = false;
+    bool no_inside_trips = false;  // INSIDE_TRIPS=off: as CGRT_GRID_NO_INSIDE_TRIPS on every launch (a measurement aid)
     const char *timeline_file = nullptr;  // TIMELINE_FILE (nullptr: off)
 };
 inline const char *env_str(const char *name) { const char *e = std::getenv(name); return e ? e : ""; }
@@ -384,6 +385,12 @@ inline EyeKnobs eye_knobs() {
         if (*env_str("CGRT_LENS_TABLE_BYTES")) {
             k.lens_table_bytes = std::max(std::atoll(env_str("CGRT_LENS_TABLE_BYTES")), 0ll);
             k.lens_table_bytes_set = true;
+        }
+        {
+            const std::string v(env_str("CGRT_INSIDE_TRIPS"));
+            k.no_inside_trips = v == "off" || v == "0";
+            if (!v.empty() && !k.no_inside_trips && v != "on" && v != "1")
+                std::fprintf(stderr, "cgrt: CGRT_INSIDE_TRIPS=%s is neither off nor on: the default is used\n", v.c_str());
         }
         return k;
     }();

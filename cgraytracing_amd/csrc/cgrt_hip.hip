@@ -704,6 +704,17 @@ struct EyeLaunch {
     }
 };
 
+// The scene's inside spheres whose guarded loop pays (cgrt_inside_sphere.h): what a PAIR launch hands its kernel
+static InsideTrait inside_paying(const DeviceScene &d) {
+    InsideTrait t{};
+    for (int k = 0; k < d.inside.n; k++)
+        if (inside_pays(d.inside, k, d.n_lds)) {
+            t.idx[t.n] = d.inside.idx[k], t.mask[t.n] = d.inside.mask[k], t.rin2[t.n] = d.inside.rin2[k];
+            t.n++;
+        }
+    return t;
+}
+
 // The eye pass's main launch for (scene, camera, grid): the Hitpoint capture (capture), else cgrt_trace_grid's.
 static EyeLaunch eye_launch(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, const EyeKnobs &kn, bool capture) {
     const DeviceScene &d = s->dev;
@@ -741,6 +752,10 @@ static EyeLaunch eye_launch(const cgrt_scene *s, const cgrt_camera *cam, const c
         // each alone on a SIMD, are bound by the sphere loop's dependent chain -- two spheres a trip
         L.k.pair = L.form == EyeForm::Image && L.k.sph && L.k.glass && !L.k.stats && s->order.ok && !(grid->flags & CGRT_GRID_NO_SPHERE_PAIRS);
     }
+    // Inside trips (cgrt_inside_sphere.h): the PAIR kernels get the scene's candidates whose guarded loop pays -- none under
+    // CGRT_GRID_NO_INSIDE_TRIPS or the knob CGRT_INSIDE_TRIPS=off, which is the pair loop alone in the same kernel
+    L.dev.inside = InsideTrait{};
+    if (L.k.pair && !(grid->flags & CGRT_GRID_NO_INSIDE_TRIPS) && !kn.no_inside_trips) L.dev.inside = inside_paying(d);
     L.lds = eye_lds(L.k, L.dev) + (L.form == EyeForm::Image || L.form == EyeForm::Sched ? (size_t)kn.lds_pad : 0);
     return L;
 }
@@ -1112,6 +1127,13 @@ int cgrt_scene_last_lens_table(const cgrt_scene *s, int64_t *entries, int64_t *c
     ON_DEVICE(s->device);
     return last_lens_table(s->order, s->lens, entries, capacity, reused);
 }
+int cgrt_scene_inside_spheres(const cgrt_scene *s, int32_t *index, uint32_t *mask, double *rin2, int32_t cap, int32_t *n) {
+    NEED_COMMITTED(s, n && (cap <= 0 || (index && mask && rin2)));
+    const InsideTrait &t = s->dev.inside;
+    *n = t.n;
+    for (int k = 0; k < t.n && k < cap; k++) index[k] = t.idx[k], mask[k] = t.mask[k], rin2[k] = t.rin2[k];
+    return CGRT_OK;
+}
 int cgrt_scene_last_sample_relay(const cgrt_scene *s, int64_t *tiles, int32_t *chunks, int64_t *parked_values) {
     NEED_COMMITTED(s, tiles && chunks && parked_values);
     ON_DEVICE(s->device);
@@ -1378,6 +1400,25 @@ int cgrt_math_probe(int device, int op, const double *in, int64_t n, double *out
     double *d_out = hs.out(out, (size_t)n * n_out * sizeof(double));
     if (const int rc = hs.error()) return rc;
     hipLaunchKernelGGL(math_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, d_in, (long long)n, d_out);
+    HIP_TRY(hipGetLastError());
+    return hs.finish(CGRT_OK);
+}
+
+int cgrt_inside_probe(const cgrt_scene *s, int op, const double *rays, int64_t n, double *out) {
+    NEED_COMMITTED(s, rays && out);
+    if (op != CGRT_PROBE_INSIDE_LOOP) return fail(CGRT_ERR_INVALID, "cgrt_inside_probe: unknown op");
+    if (n < 0) return fail(CGRT_ERR_INVALID, "cgrt_inside_probe: negative n");
+    if (n > ((int64_t)1 << 28)) return fail(CGRT_ERR_LIMIT, "cgrt_inside_probe: more than 2^28 elements");
+    const DeviceScene &d = s->dev;
+    if (!d.all_spheres || d.n_objs < 1 || d.n_objs != d.n_lds)
+        return fail(CGRT_ERR_UNSUPPORTED, "cgrt_inside_probe: the pair loop serves sphere-only scenes whose list is resident");
+    if (n == 0) return CGRT_OK;
+    ON_DEVICE(s->device);
+    HostStage hs;
+    const double *d_in = hs.in(rays, (size_t)n * 6 * sizeof(double));
+    double *d_out = hs.out(out, (size_t)n * 5 * sizeof(double));
+    if (const int rc = hs.error()) return rc;
+    hipLaunchKernelGGL(inside_loop_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d, inside_paying(d), d_in, (long long)n, d_out);
     HIP_TRY(hipGetLastError());
     return hs.finish(CGRT_OK);
 }

@@ -358,6 +358,25 @@ __device__ __forceinline__ SceneHit intersect_scene(const ObjRec *__restrict__ o
         }
         int i_single = 0;
         if (PAIR) {
+            // Inside trips (cgrt_inside_sphere.h): when every lane that has a ray starts it inside refracting sphere sc.inside.idx[k]
+            // -- the refracted child of an entering ray, the reflected child of a ray inside: 28 % of C2's trips --, no sphere
+            // outside sc.inside.mask[k] can be its first hit, and the wave takes the mask's spheres one by one: sphere_len and
+            // sphere_len_pair give the same len bit for bit, so (t, id) are the pair loop's.  The test is geometric (it proves its
+            // premise for any ray, and the body has no register for a tag); the count is a kernel argument, 0 for a scene
+            // without the trait or a launch with the feature off: one scalar compare.
+            for (int k = 0; k < kInsideMax && k < sc.inside.n; k++) {
+                const bool in = starts_inside(o, ld3(objs[sc.inside.idx[k]].a), sc.inside.rin2[k]);
+                if (__ballot(on && !in) != 0ull) continue;
+                for (uint32_t m = sc.inside.mask[k]; m != 0u; m &= m - 1u) {
+                    const int i = __builtin_ctz(m);
+                    const double len = sphere_len(objs[i], o, d);
+                    if (len < best.t) {
+                        best.t = len;
+                        best.id = i;
+                    }
+                }
+                return best;
+            }
             for (int i = 0; i + 1 < n_lds; i += 2) {
                 double lenA, lenB;
                 const ObjRec &A = objs[i], &B = objs[i + 1];

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "cgrt_inside_sphere.h"
+
 namespace cgrt {
 
 // Reference constants (main.cpp:24-25, objects.h:15,143-144).
@@ -207,6 +209,9 @@ struct DeviceScene {
     int32_t single_ray;     // every plane and sphere is diffuse and there is no mesh and no Bezier object: every ray tree is one ray
     int32_t light_hf_only;  // light_trees and every plane's tree is an opaque bump floor with a grid (hfield): the light variant needs the
                             // height-field walk and nothing else of the tree code (HFONLY)
+    InsideTrait inside;     // all_spheres with at most kInsideMax refracting spheres, all in LDS: which spheres a ray that starts inside
+                            // one of them can hit first (cgrt_inside_sphere.h).  The handle's copy holds every candidate
+                            // (cgrt_scene_inside_spheres); a PAIR launch's copy those whose guarded loop pays, or none (eye_launch)
 };
 
 }  // namespace cgrt

@@ -23,11 +23,12 @@ _RELAY_ORDERS = ("chunks_first", "mirror_first", "interleaved")  # CGRT_GRID_REL
 _RELAY_STARTS = ("list", "cost")  # CGRT_GRID_NO_RELAY_COST_START / CGRT_GRID_RELAY_COST_START
 
 
-def _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles, lens_table=None):
+def _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles, lens_table=None, inside_trips=True):
     """The CGRT_GRID_* flags of trace_grid's switches, the relay's apart (_relay_flag)."""
     on = (stats, _capi.GRID_STATS), (split_samples, _capi.GRID_SPLIT_SAMPLES), (force_reorder, _capi.GRID_FORCE_REORDER), (diffuse_tiles, _capi.GRID_DIFFUSE_TILES)
     off = ((reorder, _capi.GRID_NO_REORDER), (tile_order, _capi.GRID_NO_TILE_ORDER), (sphere_pairs, _capi.GRID_NO_SPHERE_PAIRS),
-           (sphere_masks, _capi.GRID_NO_SPHERE_MASKS), (lens_stage, _capi.GRID_NO_LENS_STAGE), (sure_tiles, _capi.GRID_NO_SURE_TILES))
+           (sphere_masks, _capi.GRID_NO_SPHERE_MASKS), (lens_stage, _capi.GRID_NO_LENS_STAGE), (sure_tiles, _capi.GRID_NO_SURE_TILES),
+           (inside_trips, _capi.GRID_NO_INSIDE_TRIPS))
     table = 0 if lens_table is None else _capi.GRID_LENS_TABLE if lens_table else _capi.GRID_NO_LENS_TABLE
     return sum(f for v, f in on if v) | sum(f for v, f in off if not v) | table
 
@@ -231,7 +232,8 @@ class Scene:
                    stripe=None, sample_offset=0, spp_total=None, out=None, nhit=None, counters=None, stream=None,
                    stats=False, accumulate=False, split_samples=False, reorder=True, force_reorder=False, tile_order=True,
                    diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None,
-                   relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True, relay_start=None, relay_boost=None, lens_table=None):
+                   relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True, relay_start=None, relay_boost=None, lens_table=None,
+                   inside_trips=True):
         """Asynchronous launch on torch's current stream (or `stream`).  reorder=False: CGRT_GRID_NO_REORDER (tiles in image
         order instead of heaviest-first; same image).  tile_order=False: CGRT_GRID_NO_TILE_ORDER (an image-order launch starts
         its tiles row-major instead of mirror / glass tiles first; same image).  diffuse_tiles=True: CGRT_GRID_DIFFUSE_TILES (a
@@ -258,7 +260,10 @@ class Scene:
         (a launch that does not find its draws in the table writes them wherever it stands), None: it writes them only beside
         its cost probe and otherwise goes without a table.  sure_tiles=False: CGRT_GRID_NO_SURE_TILES (a wave of the
         terminal-diffuse body traces its samples even where every ray of its 16x4 wave tile provably hits the same sphere first;
-        same image, hit counts and counters; sphere_masks=False implies it; last_sure_tiles).  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
+        same image, hit counts and counters; sphere_masks=False implies it; last_sure_tiles).  inside_trips=False:
+        CGRT_GRID_NO_INSIDE_TRIPS (a glass sphere scene's pair kernel tests every sphere in every iteration, also where all its
+        lanes' rays start inside the refracting sphere and can only leave it; same image, hit counts and counters;
+        inside_spheres).  split_samples: CGRT_GRID_SPLIT_SAMPLES (several
         workgroups share a tile's samples; reproducible, fp64 summation order differs from the sample-by-sample sum).  Returns (rgb, nhit, counters) torch
         tensors on the scene's device: float32 [rows,width,3], int32 [rows,width] (bit pattern uint32),
         int64 [8] (counters are ADDED to)."""
@@ -277,7 +282,7 @@ class Scene:
         assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (rows, width, 3)
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (_capi.GRID_ACCUMULATE if accumulate else 0) |
-                              _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles, lens_table) |
+                              _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles, lens_table, inside_trips) |
                               _relay_flag(sample_relay, relay_mirror, relay_order, relay_start, relay_boost))
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         check(self._L.cgrt_trace_grid(self._h, C.byref(cc), C.byref(g), out.data_ptr(),
@@ -808,7 +813,8 @@ class Scene:
     def trace_grid_host(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                         stripe=None, sample_offset=0, spp_total=None, stats=False, split_samples=False, reorder=True,
                         force_reorder=False, tile_order=True, diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None,
-                        relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True, relay_start=None, relay_boost=None, lens_table=None):
+                        relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True, relay_start=None, relay_boost=None, lens_table=None,
+                   inside_trips=True):
         """Synchronous form with numpy outputs (no torch needed): dict(rgb, nhit, counters)."""
         rows = height - row_offset if rows is None else rows
         rgb = np.zeros((rows, width, 3), np.float32)
@@ -816,7 +822,7 @@ class Scene:
         cnt = np.zeros((_capi.CGRT_NCOUNTERS,), np.uint64)
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total,
-                              _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles, lens_table) |
+                              _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles, lens_table, inside_trips) |
                               _relay_flag(sample_relay, relay_mirror, relay_order, relay_start, relay_boost))
         check(self._L.cgrt_trace_grid_host(self._h, C.byref(cc), C.byref(g), rgb.ctypes.data, nhit.ctypes.data,
                                            cnt.ctypes.data))
@@ -858,6 +864,27 @@ class Scene:
         sure = np.zeros(n.value, np.uint8)
         check(self._L.cgrt_scene_last_sure_tiles(self._h, sure.ctypes.data, n.value, C.byref(n)))
         return sure
+
+    def inside_spheres(self):
+        """The committed scene's inside spheres (cgrt_scene_inside_spheres; a scene trait, no launch): a list of
+        dict(index: the refracting sphere's place in the object list, mask: bit j = sphere j can be the first hit of a ray that
+        starts inside it -- all bits: the unchanged loop --, rin2: the squared radius below which an origin counts as inside).
+        Empty: the scene has no such trait (several refracting spheres, more than 32 objects, an object that is no sphere)."""
+        n = C.c_int32()
+        check(self._L.cgrt_scene_inside_spheres(self._h, None, None, None, 0, C.byref(n)))
+        idx, mask, rin2 = np.zeros(max(n.value, 1), np.int32), np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.float64)
+        check(self._L.cgrt_scene_inside_spheres(self._h, idx.ctypes.data, mask.ctypes.data, rin2.ctypes.data, n.value, C.byref(n)))
+        return [dict(index=int(idx[k]), mask=int(mask[k]), rin2=float(rin2[k])) for k in range(n.value)]
+
+    def inside_probe(self, rays):
+        """cgrt_inside_probe(CGRT_PROBE_INSIDE_LOOP): the pair kernels' sphere loop over this scene for rays [n,6] = origin,
+        direction; elements 64k .. 64k+63 are the lanes of one wave.  Returns float64 [n,5]: t, id of the pair loop, t, id of
+        the guarded loop, 1 where the element's wave took the one-by-one loop."""
+        rays = np.ascontiguousarray(rays, np.float64)
+        assert rays.ndim == 2 and rays.shape[1] == 6
+        out = np.zeros((rays.shape[0], 5), np.float64)
+        check(self._L.cgrt_inside_probe(self._h, _capi.PROBE_INSIDE_LOOP, rays.ctypes.data, rays.shape[0], out.ctypes.data))
+        return out
 
     def last_tile_order_reused(self):
         """True when this scene's last trace_grid / trace_grid_host ran no ordering kernel because the handle still held the

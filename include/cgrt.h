@@ -207,6 +207,13 @@ enum {
                                  tracing anything (cgrt_scene_last_sure_tiles).  This flag restores the sample loop.  Same
                                  image, hit counts and counters either way -- CGRT_CNT_RAYS keeps counting the rays the loop
                                  would have traced; it exists to test one against the other                              */
+    CGRT_GRID_NO_INSIDE_TRIPS = 33554432, /* the full and the parking body of a glass sphere scene's ",PAIR=1," launch: by default
+                                 an iteration in which every lane's ray starts inside the scene's refracting sphere (the
+                                 refracted child of an entering ray, the reflected child of a ray inside) tests only the
+                                 spheres that ray can hit first -- the sphere itself and those not provably disjoint from it
+                                 (cgrt_scene_inside_spheres) -- instead of all of them two at a time.  This flag, or the knob
+                                 CGRT_INSIDE_TRIPS=off, restores the pair loop in the same kernel.  Same image, hit counts and
+                                 counters either way, CGRT_CNT_WAVE_ITERS included                                       */
     CGRT_GRID_HITPOINTS = 32, /* cgrt_trace_grid_variant only: name the launch of the Hitpoint capture
                                  (cgrt_trace_grid_hitpoints, the eye pass of cgrt_ppm_render) instead of cgrt_trace_grid's;
                                  ignored by the other calls                                                            */
@@ -884,6 +891,12 @@ int cgrt_scene_last_lens_stage(const cgrt_scene *s, int64_t *lds_tiles, int64_t 
  * when the launch found the table written by an earlier one (same order, seed, sample_offset, spp and capacity) and ran no
  * lens_table_kernel.  All 0: the launch read no table, or it returned an error. */
 int cgrt_scene_last_lens_table(const cgrt_scene *s, int64_t *entries, int64_t *capacity, int32_t *reused);
+/* The committed scene's inside spheres (see CGRT_GRID_NO_INSIDE_TRIPS; a scene trait: no launch, no device): *n = its refracting
+ * spheres as the trait holds them -- 0 for a scene with more than one, with more than 32 objects or with an object that is no
+ * sphere -- and for k < min(*n, cap): index[k] = the sphere's place in the object list, mask[k] = bit j set for every sphere j a ray
+ * that starts inside it can hit first (itself, and every sphere not provably disjoint from it; all bits: the unchanged loop),
+ * rin2[k] = the squared radius below which an origin counts as inside (0: none does). */
+int cgrt_scene_inside_spheres(const cgrt_scene *s, int32_t *index, uint32_t *mask, double *rin2, int32_t cap, int32_t *n);
 
 /* Host evaluation of that table (cgrt_relay.h, the same inline code the kernels run; no GPU): for a list of n_tiles entries,
  * the first n01 of class 0 or 1 and the first n012 of classes 0-2 (cgrt_scene_last_tile_order's plan[2], plan[3], plan[4] and
@@ -932,6 +945,15 @@ int cgrt_lens_samples(uint64_t seed, const int64_t *pixel, const int32_t *sample
  * more than 2^28 elements: CGRT_ERR_LIMIT. */
 enum { CGRT_PROBE_SQRT = 0, CGRT_PROBE_NORMALIZED = 1, CGRT_PROBE_SPHERE_LEN = 2, CGRT_PROBE_SPHERE_LEN_PAIR = 4 /* 3: not an op */ };
 int cgrt_math_probe(int device, int op, const double *in, int64_t n, double *out);
+/* The same for a routine that needs a scene: CGRT_PROBE_INSIDE_LOOP runs the ",PAIR=1," kernels' sphere loop over the committed
+ * scene's spheres for n rays {rayorig(3), raydir(3)}, laid out over the waves as above, once as the pair loop alone and once with
+ * the scene's inside spheres (see CGRT_GRID_NO_INSIDE_TRIPS), as a launch with the feature on hands them to its kernel:
+ *   out[n][5] = {t, id of the pair loop (1e10, -1: no hit), t, id of the guarded loop, 1 where the element's wave took the
+ *                one-by-one loop over the mask, else 0}
+ * CGRT_ERR_UNSUPPORTED: the scene is not one the pair loop serves (an object that is no sphere, or more than the resident list
+ * holds); CGRT_ERR_INVALID / CGRT_ERR_LIMIT as cgrt_math_probe. */
+enum { CGRT_PROBE_INSIDE_LOOP = 5 };
+int cgrt_inside_probe(const cgrt_scene *s, int op, const double *rays, int64_t n, double *out);
 
 #ifdef __cplusplus
 }
