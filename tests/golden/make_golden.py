@@ -6,6 +6,7 @@ HIP path) to the reference everywhere else.
     python tests/golden/make_golden.py            # everything
     python tests/golden/make_golden.py loader t1  # (internal) one reference file-load per process, quirk Q9
     python tests/golden/make_golden.py oracle_vs_ref  # only oracle_vs_ref.npz (tests/test_oracle_vs_ref.py)
+    python tests/golden/make_golden.py planes_general  # only planes_general.npz (tests/test_planes_general_host.py)
 
 Contents of each trace fixture: acc_sum [H,W,3] f64 (sum of hp.f per pixel, emission order), nhit [H,W],
 nrays, and the emission-ordered hitpoint stream hp [n,9] = f, pos, normal with hp_pix / hp_smp.
@@ -145,6 +146,57 @@ def write_oracle_vs_ref(ref):
     np.savez_compressed(os.path.join(HERE, "oracle_vs_ref.npz"), **g)
 
 
+PLANES_SEED = 20261  # tests/test_planes_general_host.py, tests/test_gpu_planes_general.py: the seed of every plane's ray classes
+
+
+def planes_general_frames():
+    """tests/test_planes_general_host.py: frames through trace() with planes in general position; 64x48, spp 2, depth 5, thin lens.
+    front_tie_room carries its vase behind the back wall (scenes.hidden_vase), where no ray reaches it first: the reference's
+    Bezier draws inside trace() are not path-keyed, so a frame whose rays could hit the vase would only agree statistically."""
+    rooms = scenes.run_rooms()
+    return [(name, rooms[name]) for name in ("tilted_room", "front_tie_room", "nonunit_room")]
+
+
+def planes_general_record(be):
+    """What one backend answers to the cases of tests/test_planes_general_host.py, as counts and digests.  Per plane of
+    scenes.general_planes() and ray class of scenes.plane_ray_classes(), and for scenes.bump_floor_plane() with the classes of
+    scenes.bump_parallel_rays(): [rays, hits as intersect() returns them (len > 0, +inf
+    included), hits with len < 1e10 -- those that trace() can accept --] and the sha256 of the hit flags, of len on the hits and of
+    the normal on the hits (the misses' len is -inf, NaN or <= 0 and stays out).  Per frame: [nrays, hitpoints] and the
+    array_digest of acc_sum and of the hitpoint stream."""
+    names, counts, digests = [], [], []
+    cases = [(pname, plane, scenes.plane_ray_classes(plane, PLANES_SEED)) for pname, plane in scenes.general_planes()]
+    cases.append(("bump_floor", scenes.bump_floor_plane(), scenes.bump_parallel_rays(PLANES_SEED)))
+    for pname, plane, classes in cases:
+        s = BackendScene(be, [plane])
+        for cls, (org, dirs) in sorted(classes.items()):
+            hit, ln, nv = s.intersect_batch(0, org, dirs)
+            m = hit != 0
+            names.append("%s/%s" % (pname, cls))
+            counts.append([len(org), int(m.sum()), int((m & (ln < scenes.K_INF)).sum())])
+            digests.append([hashlib.sha256(np.ascontiguousarray(hit, np.int32).tobytes()).digest(),
+                            bytes.fromhex(array_digest(ln[m])), bytes.fromhex(array_digest(nv[m]))])
+        s.close()
+    g = dict(names=np.array(names, "S40"), counts=np.array(counts, np.int64),
+             digests=np.frombuffer(b"".join(b"".join(d) for d in digests), np.uint8).reshape(len(names), 3, 32).copy())
+    fnames, fcounts, fdigests = [], [], []
+    for name, objs in planes_general_frames():
+        s = BackendScene(be, objs)
+        r = s.trace_grid(scenes.cam_dof(), 64, 48, 2, 5, seed=PLANES_SEED, capture=True)
+        s.close()
+        fnames.append(name)
+        fcounts.append([r["nrays"], len(r["hp"])])
+        fdigests.append(bytes.fromhex(array_digest(r["acc_sum"])) + bytes.fromhex(array_digest(r["hp"])))
+    g.update(frame_names=np.array(fnames, "S40"), frame_counts=np.array(fcounts, np.int64),
+             frame_digests=np.frombuffer(b"".join(fdigests), np.uint8).reshape(len(fnames), 2, 32).copy())
+    return g
+
+
+def write_planes_general(ref):
+    """planes_general.npz: the compiled reference's planes_general_record()"""
+    np.savez_compressed(os.path.join(HERE, "planes_general.npz"), **planes_general_record(ref))
+
+
 def fingerprint(nodes, leaf):
     sizes = nodes[:, 2]
     leaves = sizes[sizes < 10]
@@ -217,6 +269,8 @@ def main():
     ref = Backend("ref")
     if len(sys.argv) > 1 and sys.argv[1] == "oracle_vs_ref":
         return write_oracle_vs_ref(ref)
+    if len(sys.argv) > 1 and sys.argv[1] == "planes_general":
+        return write_planes_general(ref)
     meta = {}
     # `only NAME...`: (re)generate just these trace fixtures and merge their entries into trace_meta.json
     only = set(sys.argv[2:]) if len(sys.argv) > 2 and sys.argv[1] == "only" else None
@@ -324,6 +378,7 @@ def main():
     timg = tonemap_input()
     np.savez_compressed(os.path.join(HERE, "tonemap.npz"), image=timg, rgb8=ref.tonemap(timg))
     write_oracle_vs_ref(ref)
+    write_planes_general(ref)
     # ---- loaders: one process per file ----
     write_test_meshes()
     for name in LOADER_CASES:
