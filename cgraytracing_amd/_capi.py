@@ -130,6 +130,12 @@ class RayPixels(C.Structure):
     _fields_ = [("width", C.c_int32), ("rows", C.c_int32), ("spp", C.c_int32), ("pad_", C.c_int32), ("pixel", C.c_void_p)]
 
 
+class Hitpoints(C.Structure):
+    _fields_ = [("n", C.c_int64), ("hp9", C.c_void_p), ("ray", C.c_void_p), ("path", C.c_void_p), ("pixel", C.c_void_p),
+                ("width", C.c_int32), ("rows", C.c_int32), ("spp", C.c_int32), ("max_depth", C.c_int32),
+                ("reserved", C.c_void_p * 2)]  # 72 bytes
+
+
 class PhotonRays(C.Structure):
     _fields_ = [("n", C.c_int64), ("org3", C.c_void_p), ("dir3", C.c_void_p), ("flux3", C.c_void_p), ("keys", C.c_void_p),
                 ("draws", C.c_void_p)]
@@ -180,6 +186,8 @@ SIGNATURES = {
                                           C.POINTER(C.c_void_p)]),
     "cgrt_ppm_session_create_rays": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.POINTER(RayPixels), C.POINTER(Photons), C.c_int,
                                                C.POINTER(C.c_void_p)]),
+    "cgrt_ppm_session_create_hitpoints": (C.c_int, [C.c_void_p, C.POINTER(Hitpoints), C.POINTER(Photons), C.c_int,
+                                                    C.POINTER(C.c_void_p)]),
     "cgrt_ppm_session_destroy": (None, [C.c_void_p]),
     "cgrt_ppm_session_add_photons": (C.c_int, [C.c_void_p, C.c_int64]),
     "cgrt_ppm_session_add_photon_rays": (C.c_int, [C.c_void_p, C.POINTER(PhotonRays)]),

@@ -1427,6 +1427,7 @@ int cgrt_inside_probe(const cgrt_scene *s, int op, const double *rays, int64_t n
 
 // the photon pass, the session and the image output
 #include "cgrt_ppm_plan.h"
+#include "cgrt_hp_order.h"
 #include "cgrt_ppm_table.hpp"
 #include "cgrt_photon_trace.hpp"
 #include "cgrt_ppm_apply.hpp"

@@ -50,7 +50,7 @@ struct cgrt_ppm_session {
     const cgrt_scene *s = nullptr;
     cgrt_photons ph{};
     // the image the session gathers into, the gather's normaliser and the photons' depth limit: a grid session's grid.width,
-    // .rows, .spp, .max_depth; a ray session's cgrt_ray_pixels and rays->max_depth
+    // .rows, .spp, .max_depth; a ray session's cgrt_ray_pixels and rays->max_depth; a hitpoint session's cgrt_hitpoints fields
     int width = 0, rows = 0, spp = 1, max_depth = 0;
     bool striped = false;  // grid session over block-cyclic rows: no rgb8
     bool lookahead = false;  // session: trace the next batch on the producer stream when a call ends
@@ -83,6 +83,7 @@ struct cgrt_ppm_session {
     }
     template <class Capture> int eye(const cgrt_scene *s_, const cgrt_photons *ph_, Capture capture, DevBuf &rec);
     int table(DevBuf &rec, const int64_t *ray_pixel, bool rays);
+    int table(const cgrt_scene *s_, const cgrt_photons *ph_, const cgrt_hitpoints &in);
     int photon_setup(bool session);
     int photons(long long last, bool keep_ahead, const cgrt_photon_rays *pr = nullptr);
     int gather(double *d_img, unsigned char *d_rgb8, hipStream_t st) const;
@@ -118,6 +119,17 @@ int cgrt_ppm_session::table(DevBuf &rec, const int64_t *ray_pixel, bool rays) {
     Timer tm;
     tm.start();
     if (const int rc = tab.build(rec, ph, spp, ray_pixel, rays, main_tmp)) return rc;
+    ms_table = tm.stop();
+    return CGRT_OK;
+}
+
+// The table of a session whose Hitpoints are the caller's records: there is no eye stage (ms_eye stays 0); frame() has been called
+int cgrt_ppm_session::table(const cgrt_scene *s_, const cgrt_photons *ph_, const cgrt_hitpoints &in) {
+    s = s_; ph = *ph_;
+    tab.npix = (long long)rows * width;
+    Timer tm;
+    tm.start();
+    if (const int rc = tab.build(in, ph, main_tmp)) return rc;
     ms_table = tm.stop();
     return CGRT_OK;
 }
@@ -274,11 +286,13 @@ extern "C" int cgrt_ppm_render(const cgrt_scene *s, const cgrt_camera *cam, cons
 }
 
 // ---- resumable photon mapping: the state above, kept between calls -------------------------------------------------
-// What both creators do behind their argument checks: the session and its events, the eye pass (capture: see eye()), the table
-// (ray_pixel, rays: see PpmTable::build), the photon buffers and ph->nphotons photons.
+// What the creators do behind their argument checks: the session and its events, the eye pass (capture: see eye()), the table
+// (ray_pixel, rays: see PpmTable::build) -- or, with hps, no eye pass and the table of the caller's records --, the photon
+// buffers and ph->nphotons photons.
 template <class Capture>
 static int session_create(const cgrt_scene *s, const cgrt_photons *ph, int flags, int width, int rows, int spp, int max_depth,
-                          bool striped, Capture capture, const int64_t *ray_pixel, bool rays, cgrt_ppm_session **out) {
+                          bool striped, Capture capture, const int64_t *ray_pixel, bool rays, cgrt_ppm_session **out,
+                          const cgrt_hitpoints *hps = nullptr) {
     ON_DEVICE(s->device);
     std::unique_ptr<cgrt_ppm_session> p(new (std::nothrow) cgrt_ppm_session());
     if (!p) return fail(CGRT_ERR_LIMIT, "out of host memory");
@@ -287,7 +301,10 @@ static int session_create(const cgrt_scene *s, const cgrt_photons *ph, int flags
     HIP_TRY(hipEventCreate(&p->img_a));
     HIP_TRY(hipEventCreate(&p->img_b));
     int rc = CGRT_OK;
-    {
+    if (hps) {
+        if ((rc = p->table(s, ph, *hps))) return rc;
+        HIP_TRY(hipDeviceSynchronize());  // the records are read before the call returns
+    } else {
         DevBuf rec;
         if ((rc = p->eye(s, ph, capture, rec))) return rc;
         if ((rc = p->table(rec, ray_pixel, rays))) return rc;
@@ -332,6 +349,26 @@ extern "C" int cgrt_ppm_session_create_rays(const cgrt_scene *s, const cgrt_rays
         return ray_hitpoints_device(s, rays, px->pixel, cap, d_rec, count);
     };
     return session_create(s, ph, flags, px->width, px->rows, px->spp, rays->max_depth, false, capture, px->pixel, true, out);
+}
+
+extern "C" int cgrt_ppm_session_create_hitpoints(const cgrt_scene *s, const cgrt_hitpoints *hps, const cgrt_photons *ph, int flags,
+                                                 cgrt_ppm_session **out) {
+    if (!out) return fail(CGRT_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!s || !hps || !ph) return fail(CGRT_ERR_INVALID, "null argument");
+    if (hps->n < 0) return fail(CGRT_ERR_INVALID, "hitpoints: negative record count");
+    if (hps->n > 0 && !hps->hp9) return fail(CGRT_ERR_INVALID, "hitpoints: null hp9");
+    if (hps->width <= 0 || hps->rows <= 0 || hps->spp <= 0) return fail(CGRT_ERR_INVALID, "hitpoints: width, rows and spp must be positive");
+    if (hps->max_depth < 1 || hps->max_depth > kMaxDepth) return fail(CGRT_ERR_INVALID, "hitpoints: max_depth must be 1..5");
+    int rc = check_photons(ph);
+    if (rc) return rc;
+    if (flags & ~CGRT_PPM_SESSION_NO_LOOKAHEAD) return fail(CGRT_ERR_INVALID, "unknown session flags");
+    if ((long long)hps->width * hps->rows >= (1ll << 31)) return fail(CGRT_ERR_LIMIT, "hitpoints: 2^31 texels or more");
+    if (hps->n >= (1ll << 31)) return fail(CGRT_ERR_LIMIT, "hitpoints: 2^31 records or more");
+    // (the last of the checks: it is the one that looks at the scene's state) whatever n is: the session traces photons through it
+    if (!s->committed) return fail(CGRT_ERR_INVALID, "scene not committed");
+    const auto no_eye = [](uint64_t, double **, uint64_t *) { return CGRT_OK; };
+    return session_create(s, ph, flags, hps->width, hps->rows, hps->spp, hps->max_depth, false, no_eye, nullptr, false, out, hps);
 }
 
 extern "C" void cgrt_ppm_session_destroy(cgrt_ppm_session *p) {

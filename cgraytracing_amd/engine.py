@@ -1096,6 +1096,63 @@ class Scene:
         self._sessions.add(ses)
         return ses
 
+    def ppm_session_hitpoints(self, hp9, ray=None, path=None, pixel=None, *, width, rows, spp=1, max_depth=5, nphotons=0,
+                              photon_seed=777, hashsize=1000001, light=(0.0, 19.999, 20.0), jitter=2.0, power=700.0, alpha=0.7,
+                              batch=0, initial_radius=0.0, pair_cap=0, lookahead=True):
+        """A live photon-mapping render over caller-supplied Hitpoint records (cgrt_ppm_session_create_hitpoints): hp9 float64
+        [n,9] (value = f * adj, pos, normal after the flip: wavefront's hp9), ray int64 [n] (the record's ray or probe id; None:
+        its index), path int32 or uint32 [n] (its place in the ray's tree; None: the root), pixel int64 [n] (the texel it gathers
+        into; None: ray % (width * rows)) -- contiguous tensors on the scene's device.  A record without a texel in the image,
+        with path 0, a negative ray or a non-finite pos is dropped.  spp is the gather's normaliser and max_depth the PHOTONS'
+        depth limit (1..5).  Returns a PpmSession; hitpoints()[:, 0] is the ray id, [:, 1] the record's rank within its ray.  The
+        records wavefront(max_depth <= 5, want=("hp",)) returns give ppm_session_rays' session on the same rays bit for bit."""
+        ph = _capi.Photons(_d3(light), jitter, power, alpha, nphotons, hashsize, batch, photon_seed, initial_radius, pair_cap)
+        if not self.stats()["committed"]:  # the library's own answer (no tensor is looked at)
+            check(self._L.cgrt_ppm_session_create_hitpoints(self._h, C.byref(_capi.Hitpoints(0, None, None, None, None, width, rows,
+                                                                                             spp, max_depth)),
+                                                            C.byref(ph), 0, C.byref(C.c_void_p())))
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        if not (isinstance(hp9, torch.Tensor) and hp9.dtype == torch.float64 and hp9.dim() == 2 and hp9.shape[1] == 9 and
+                hp9.is_contiguous() and hp9.device == dev):
+            raise ValueError("ppm_session_hitpoints: hp9 must be a contiguous float64 [n,9] tensor on %s" % (dev,))
+        n = hp9.shape[0]
+        uint32 = getattr(torch, "uint32", torch.int32)
+        for name, t, dts in (("ray", ray, (torch.int64,)), ("path", path, (torch.int32, uint32)), ("pixel", pixel, (torch.int64,))):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype in dts and tuple(t.shape) == (n,) and
+                                      t.is_contiguous() and t.device == dev):
+                raise ValueError("ppm_session_hitpoints: %s must be a contiguous %s [n] tensor on %s" % (name, dts[0], dev))
+        ptr = lambda t: t.data_ptr() if t is not None and n > 0 else None
+        hps = _capi.Hitpoints(n, ptr(hp9), ptr(ray), ptr(path), ptr(pixel), width, rows, spp, max_depth)
+        h = C.c_void_p()
+        torch.cuda.current_stream(dev).synchronize()  # the table build runs on the null stream
+        check(self._L.cgrt_ppm_session_create_hitpoints(self._h, C.byref(hps), C.byref(ph),
+                                                        0 if lookahead else _capi.PPM_SESSION_NO_LOOKAHEAD, C.byref(h)))
+        ses = PpmSession(self, h, width, rows, spp)
+        self._sessions.add(ses)
+        return ses
+
+    def ppm_session_wavefront(self, org, dirs, keys=None, *, width, rows, spp=1, pixel=None, eye_depth=12, min_adj=0.0, max_depth=5,
+                              seed=12345, first_index=0, work_bytes=0, **photon_kw):
+        """Photon mapping behind an eye pass of any depth: wavefront(max_depth=eye_depth, min_adj) traces the rays' trees (1..31
+        levels) and their Hitpoint records start a ppm_session_hitpoints session whose photons run to max_depth (1..5).  The
+        wavefront runs twice: once without record arrays to learn the number of Hitpoints, once with room for exactly that
+        many.  pixel (int64 [n], per RAY; None: ray i belongs to texel i % (width * rows)) is mapped to the records; a ray with
+        a negative texel contributes nothing.  photon_kw: ppm_session_hitpoints' photon keywords (nphotons, photon_seed, batch,
+        ...).  Returns (PpmSession, wavefront's dict with hp9, hp_ray, hp_path).  At eye_depth <= 5 the session is
+        ppm_session_rays' on the same rays bit for bit."""
+        self._ray_tensors("ppm_session_wavefront", org, dirs, keys, pixel)
+        count = self.wavefront(org, dirs, keys, max_depth=eye_depth, min_adj=min_adj, seed=seed, first_index=first_index, want=(),
+                               work_bytes=work_bytes)["hp_count"]
+        wf = self.wavefront(org, dirs, keys, max_depth=eye_depth, min_adj=min_adj, seed=seed, first_index=first_index, want=("hp",),
+                            hp_cap=count, work_bytes=work_bytes)
+        assert wf["hp_count"] == count and wf["hp9"].shape[0] == count  # the trace is deterministic
+        rec_pixel = pixel[wf["hp_ray"]].contiguous() if pixel is not None else None
+        ses = self.ppm_session_hitpoints(wf["hp9"], wf["hp_ray"], wf["hp_path"], rec_pixel, width=width, rows=rows, spp=spp,
+                                         max_depth=max_depth, **photon_kw)
+        return ses, wf
+
     def capture_variant(self, max_depth=5):
         """Name of the capture_rays_kernel instantiation trace_rays_hitpoints / ppm_session_rays launch (cgrt_trace_rays_variant
         with CGRT_RAYS_HITPOINTS)."""

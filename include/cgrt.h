@@ -45,7 +45,8 @@ extern "C" {
                             cgrt_bounce, CGRT_STEP_*, cgrt_bounce_rays, cgrt_bounce_rays_host, cgrt_bounce_rays_variant
                             (bounce queries); cgrt_wavefront, cgrt_wavefront_rays, cgrt_wavefront_rays_host,
                             cgrt_wavefront_rays_variant, cgrt_scene_last_wavefront, cgrt_scene_last_wavefront_rays
-                            (wavefront trace) */
+                            (wavefront trace); cgrt_hitpoints, cgrt_ppm_session_create_hitpoints (photon mapping of
+                            caller-supplied Hitpoints) */
 
 enum {
     CGRT_OK = 0,
@@ -740,6 +741,40 @@ typedef struct cgrt_ray_pixels {
  * grid session's.  The eye stage is a launch on the scene handle (Threading above).  2^31 Hitpoints or more: CGRT_ERR_LIMIT. */
 int cgrt_ppm_session_create_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_pixels *px,
                                  const cgrt_photons *ph, int flags, cgrt_ppm_session **out);
+/* A session whose Hitpoints are caller-supplied RECORDS instead of the library's own full trace of a grid or of rays: the
+ * records cgrt_wavefront_rays returns (any eye depth to 31, min_adj), records a caller shaded or culled between bounce levels,
+ * or Hitpoints that come from no ray at all (irradiance probes at given points and normals).  There is no eye stage. */
+typedef struct cgrt_hitpoints {
+    int64_t n;              /* records; 0 is valid (a session whose image is zero); 2^31 or more: CGRT_ERR_LIMIT      */
+    const double   *hp9;    /* [n][9] {value3 = f*adj, pos3, normal3 after the flip}: cgrt_wavefront.hp9's layout;
+                               required when n > 0                                                                     */
+    const int64_t  *ray;    /* [n] or NULL: id of the ray (or probe) the record belongs to, 0 .. 2^36-1; NULL: i        */
+    const uint32_t *path;   /* [n] or NULL: place in that ray's tree (cgrt_bounce: root 1, 2p, 2p+1); NULL: 1          */
+    const int64_t  *pixel;  /* [n] or NULL: texel the record gathers into; NULL: ray % (width*rows)                    */
+    int32_t width, rows;    /* the image, as cgrt_ray_pixels (npix < 2^31, row 0 = bottom)                             */
+    int32_t spp;            /* the gather's normaliser (>= 1)                                                          */
+    int32_t max_depth;      /* the PHOTONS' depth limit, 1..5 (a ray session takes it from rays->max_depth)            */
+    void *reserved[2];      /* not looked at; NULL                                                                     */
+} cgrt_hitpoints;           /* 72 bytes */
+/* The arrays are DEVICE pointers on the scene's device, written on the null stream or finished before the call; they are read
+ * before the call returns (it runs on the null stream and synchronises, like cgrt_ppm_session_create_rays).
+ * Dropped records: a record whose texel is negative or >= npix, whose path is 0 or >= 2^31, whose ray is negative or >= 2^36,
+ * or whose pos has a coordinate that is not finite is dropped -- not kept, not counted, in no result.
+ * cgrt_ppm_session_info.hp_count is the number of records kept.
+ * Order contract: inside a hash bucket (the bucket of pos) the kept records stand by texel ascending, then by ray ascending,
+ * then by path in emission order (the paths compared as bit strings behind their leading 1, reflected before refracted, a
+ * prefix before its extensions), then by position in the input.  The result depends on the set of records, never on their
+ * order in the arrays; input order matters only among records equal in texel, ray and path.  Any number of records per ray.
+ * hp16[0] is the record's ray; hp16[1] is its rank among the kept records of that ray in the order above (a double with no
+ * 4-bit limit).
+ * Equivalence: all records cgrt_wavefront_rays returns at max_depth <= 5 for a ray set, passed with pixel NULL or pixel[i] =
+ * ray_pixel[ray[i]], give cgrt_ppm_session_create_rays' session on those rays bit for bit: image, rgb8, hitpoints, n_events.
+ * Every cgrt_ppm_session_* call works on the session as on a ray session; its ms_eye is 0.
+ * Before any device is touched: a null s, hps, ph or out, n < 0, n > 0 with a null hp9, non-positive width, rows or spp,
+ * max_depth outside 1..5, unknown flags, bad ph, an uncommitted scene (whatever n is: the session traces photons through
+ * it): CGRT_ERR_INVALID; npix >= 2^31 or n >= 2^31: CGRT_ERR_LIMIT. */
+int cgrt_ppm_session_create_hitpoints(const cgrt_scene *s, const cgrt_hitpoints *hps, const cgrt_photons *ph,
+                                      int flags, cgrt_ppm_session **out);
 /* Waits for anything in flight, then frees the session.  NULL is ignored. */
 void cgrt_ppm_session_destroy(cgrt_ppm_session *p);
 /* Traces photons [done, done + count) and applies them; returns when they are applied.  count >= 0. */

@@ -647,6 +647,19 @@ class PpmSession {
         const cgrt_photons ph = photons(pp);
         check(cgrt_ppm_session_create_rays(sb_.scene, &rays, &px, &ph, lookahead ? 0 : CGRT_PPM_SESSION_NO_LOOKAHEAD, &session_));
     }
+    // The same live render over caller-supplied Hitpoint records (cgrt_ppm_session_create_hitpoints): the records of a wavefront
+    // trace of any depth, records shaded or culled by the caller, or probes at given points and normals.  hps' arrays are DEVICE
+    // pointers on device `device`, read before the constructor returns; hps names the image that image() fills (hps.width x
+    // hps.rows, row 0 = bottom) and the photons' depth limit.  For all records of cgrt_wavefront_rays at max_depth <= 5 the
+    // session is the ray constructor's on the same rays, bit for bit.
+    PpmSession(const std::vector<Object *> &objs, const cgrt_hitpoints &hps, const PhotonParams &pp, int device = 0,
+               bool lookahead = true)
+        : width_(hps.width), height_(hps.rows), session_(nullptr) {
+        for (const Object *o : objs) o->add_to(sb_);
+        check(cgrt_scene_commit(sb_.scene, device));
+        const cgrt_photons ph = photons(pp);
+        check(cgrt_ppm_session_create_hitpoints(sb_.scene, &hps, &ph, lookahead ? 0 : CGRT_PPM_SESSION_NO_LOOKAHEAD, &session_));
+    }
     ~PpmSession() { cgrt_ppm_session_destroy(session_); }  // before sb_ destroys the scene
     PpmSession(const PpmSession &) = delete;
     PpmSession &operator=(const PpmSession &) = delete;
