@@ -77,6 +77,12 @@ class PpmSessionInfo(C.Structure):
 PPM_SESSION_NO_LOOKAHEAD = 1
 
 
+class SppmSessionInfo(C.Structure):
+    _fields_ = [("passes", C.c_int64), ("photons_done", C.c_int64), ("hp_count", C.c_uint64), ("n_events", C.c_uint64),
+                ("n_pairs", C.c_uint64), ("n_batch_halvings", C.c_uint64), ("device_bytes", C.c_int64), ("ms_eye", C.c_double),
+                ("ms_table", C.c_double), ("ms_photons", C.c_double), ("ms_update", C.c_double)]
+
+
 class SceneStats(C.Structure):
     _fields_ = [("n_objects", C.c_int32), ("n_spheres", C.c_int32), ("n_planes", C.c_int32),
                 ("n_meshes", C.c_int32), ("n_beziers", C.c_int32), ("n_textures", C.c_int32),
@@ -200,6 +206,18 @@ SIGNATURES = {
     "cgrt_ppm_session_image_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cgrt_ppm_session_hitpoints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cgrt_ppm_session_get_info": (C.c_int, [C.c_void_p, C.POINTER(PpmSessionInfo)]),
+    "cgrt_sppm_session_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Photons), C.c_int32,
+                                           C.POINTER(C.c_void_p)]),
+    "cgrt_sppm_session_destroy": (None, [C.c_void_p]),
+    "cgrt_sppm_session_pass_grid": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Grid), C.c_int64]),
+    "cgrt_sppm_session_pass_rays": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.c_void_p, C.c_int64]),
+    "cgrt_sppm_session_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cgrt_sppm_session_image_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cgrt_sppm_session_pixels": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cgrt_sppm_session_last_hitpoints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cgrt_sppm_session_get_info": (C.c_int, [C.c_void_p, C.POINTER(SppmSessionInfo)]),
+    "cgrt_sppm_update_host": (C.c_int, [C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_void_p]),
+    "cgrt_sppm_check_host": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Photons), C.c_int32, C.POINTER(Grid)]),
     "cgrt_tonemap_rgb8": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "cgrt_write_png": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_void_p]),
     "cgrt_photon_events": (C.c_int, [C.c_void_p, C.POINTER(Photons), C.c_int, C.c_int64, C.c_int32, C.c_void_p,

@@ -40,6 +40,57 @@ struct Timer {  // device time between two points of the null stream
 };
 }  // namespace
 
+// ---- the batch loop of every photon stage (cgrt_ppm_session::photons; a pass of cgrt_sppm_session) ---------------------------
+// The pair buffers of one batch: the search writes (k0, v0), the sort (k1, v1); npairs = {pairs, events} of the batch
+struct PairBufs {
+    unsigned long long *k0, *k1;
+    unsigned int *v0, *v1;
+    unsigned long long *npairs;
+};
+// The photons of the call `sched` has begun, against table `tab`, applied on the null stream batch by batch as `sched` decides.
+// produce(batch) enqueues a batch on the producer.  apply(np, buf) launches what consumes an applied batch: its np pairs sorted
+// by (hitpoint, slot) in (pb.k1, pb.v1) and the events of buffer buf.  n_events, n_pairs: added to for every applied batch.
+template <class Produce, class Apply>
+static int photon_batches(PpmSchedule &sched, PhotonProducer &pp, PpmTable &tab, const PairBufs &pb, GrowBuf &tmp, uint64_t &n_events,
+                          uint64_t &n_pairs, Produce produce, Apply apply) {
+    const int T = 256;
+    int rc = CGRT_OK;
+    while (sched.more()) {
+        const PpmBatch b = sched.next();
+        const int nslots = b.count * kSegStride, cur = b.buf;
+        if (!b.reuse && (rc = produce(b))) return rc;
+        // the NEXT batch now, so that it is traced under this batch's search, sort and replay
+        const PpmBatch nx = sched.following(b);
+        if (nx.count) {
+            if ((rc = produce(nx))) return rc;
+            sched.set_ahead(nx);
+        }
+        if (pp.st) HIP_TRY(hipStreamWaitEvent(0, pp.produced[cur], 0));
+        HIP_TRY(hipMemsetAsync(pb.npairs, 0, 16, 0));
+        hipLaunchKernelGGL(photon_pairs_kernel, dim3((nslots + T - 1) / T), dim3(T), 0, 0, pp.ev[cur].as<double>(),
+                           pp.ek1[cur].as<unsigned int>(), pp.eo1[cur].as<unsigned int>(), nslots, tab.ha, tab.hps.as<double>(),
+                           tab.bstart.as<int>(), pb.k0, pb.v0, pb.npairs, sched.setup.pair_cap);
+        HIP_TRY(hipGetLastError());
+        unsigned long long np2[2] = {0, 0};  // pairs (the full 64-bit count, stored or not), events
+        HIP_TRY(hipMemcpy(np2, pb.npairs, 16, hipMemcpyDeviceToHost));
+        const PpmOutcome o = sched.counted(b, np2[0]);
+        if (o != kPpmApplied) {  // nothing has been applied yet
+            if ((rc = pp.release(cur))) return rc;
+            if (o == kPpmLimit) return fail(CGRT_ERR_LIMIT, "photon pass: one photon's pairs exceed the pair buffer");
+            continue;
+        }
+        const unsigned int np = (unsigned int)np2[0];  // <= pair_cap <= 2^27
+        n_events += np2[1];
+        if (np != 0) {
+            n_pairs += np;
+            if ((rc = sort_pairs(tmp, pb.k0, pb.k1, pb.v0, pb.v1, np, sched.setup.pair_key_bits))) return rc;
+            if ((rc = apply(np, cur))) return rc;
+        }
+        if ((rc = pp.release(cur))) return rc;
+    }
+    return CGRT_OK;
+}
+
 // ---- the stages of render() main.cpp:169-258, shared by cgrt_ppm_render (one call) and a live cgrt_ppm_session ----------
 // eye(): the Hitpoint records of a grid or of a ray buffer; table(): the reference's table order and the per-pixel index over
 // them (PpmTable).  photon_setup() + photons(last): photons [done, last) in batches.  gather(): the image at the current
@@ -171,45 +222,17 @@ int cgrt_ppm_session::photons(long long last, bool keep_ahead, const cgrt_photon
     };
     const int T = 256;
     const unsigned nb = (unsigned)((tab.n + T - 1) / T);
-    int rc = CGRT_OK;
-    while (sched.more()) {
-        const PpmBatch b = sched.next();
-        const int nslots = b.count * kSegStride, cur = b.buf;
-        if (!b.reuse && (rc = produce(b, pr))) return rc;
-        // the NEXT batch now, so that it is traced under this batch's search, sort and replay
-        const PpmBatch nx = sched.following(b);
-        if (nx.count) {
-            if ((rc = produce(nx, pr))) return rc;
-            sched.set_ahead(nx);
-        }
-        if (pp.st) HIP_TRY(hipStreamWaitEvent(0, pp.produced[cur], 0));
-        HIP_TRY(hipMemsetAsync(npairs.p, 0, 16, 0));
-        hipLaunchKernelGGL(photon_pairs_kernel, dim3((nslots + T - 1) / T), dim3(T), 0, 0, pp.ev[cur].as<double>(),
-                           pp.ek1[cur].as<unsigned int>(), pp.eo1[cur].as<unsigned int>(), nslots, tab.ha, tab.hps.as<double>(),
-                           tab.bstart.as<int>(), pk0.as<unsigned long long>(), pv0.as<unsigned int>(), npairs.as<unsigned long long>(),
-                           sched.setup.pair_cap);
-        HIP_TRY(hipGetLastError());
-        unsigned long long np2[2] = {0, 0};  // pairs (the full 64-bit count, stored or not), events
-        HIP_TRY(hipMemcpy(np2, npairs.p, 16, hipMemcpyDeviceToHost));
-        const PpmOutcome o = sched.counted(b, np2[0]);
-        if (o != kPpmApplied) {  // nothing has been applied yet
-            if ((rc = pp.release(cur))) return rc;
-            if (o == kPpmLimit) return fail(CGRT_ERR_LIMIT, "photon pass: one photon's pairs exceed the pair buffer");
-            continue;
-        }
-        const unsigned int np = (unsigned int)np2[0];  // <= pair_cap <= 2^27
-        n_events += np2[1];
-        if (np != 0) {
-            n_pairs += np;
-            rc = sort_pairs(main_tmp, pk0.as<unsigned long long>(), pk1.as<unsigned long long>(), pv0.as<unsigned int>(),
-                            pv1.as<unsigned int>(), np, sched.setup.pair_key_bits);
-            if (rc) return rc;
-            hipLaunchKernelGGL(photon_apply_kernel, dim3(nb), dim3(T), 0, 0, pk1.as<unsigned long long>(), pv1.as<unsigned int>(), np,
-                               pp.ev[cur].as<double>(), ph.alpha, tab.hp.as<double>(), tab.hps.as<double>(), (long long)tab.n);
+    const PairBufs pb{pk0.as<unsigned long long>(), pk1.as<unsigned long long>(), pv0.as<unsigned int>(), pv1.as<unsigned int>(),
+                      npairs.as<unsigned long long>()};
+    int rc = photon_batches(
+        sched, pp, tab, pb, main_tmp, n_events, n_pairs, [&](const PpmBatch &b) { return produce(b, pr); },
+        [&](unsigned int np, int cur) -> int {  // 4. the ordered replay
+            hipLaunchKernelGGL(photon_apply_kernel, dim3(nb), dim3(T), 0, 0, pb.k1, pb.v1, np, pp.ev[cur].as<double>(), ph.alpha,
+                               tab.hp.as<double>(), tab.hps.as<double>(), (long long)tab.n);
             HIP_TRY(hipGetLastError());
-        }
-        if ((rc = pp.release(cur))) return rc;
-    }
+            return CGRT_OK;
+        });
+    if (rc) return rc;
     bool drain = false;
     const PpmBatch ahead = sched.end(keep_ahead, &drain);  // the lookahead is the built-in emitter's, whoever's the call's photons were
     if (ahead.count) {

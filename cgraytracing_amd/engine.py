@@ -1031,6 +1031,23 @@ class Scene:
         self._sessions.add(ses)
         return ses
 
+    def sppm_session(self, width, height, spp=1, camera=None, photon_depth=5, max_depth=5, seed=12345, photon_seed=777,
+                     hashsize=1000001, light=(0.0, 19.999, 20.0), jitter=2.0, power=700.0, alpha=0.7, batch=0, rows=None,
+                     row_offset=0, stripe=None, initial_radius=0.0, pair_cap=0):
+        """Stochastic progressive photon mapping (cgrt_sppm_session): N, R2 and tau belong to the texel, every pass traces
+        fresh eye samples and fresh photons, memory does not grow with the passes.  Returns an SppmSession without a pass;
+        add_passes(n, photons_per_pass) renders with `camera` (kept here; max_depth is the eye depth, seed the lens streams')
+        at sample_offset = passes * spp, add_pass_rays with the caller's rays.  rows / row_offset / stripe: this rank's share
+        of a width x height frame as in ppm_session (every rank traces all photons)."""
+        rows = height if rows is None else rows
+        ph = _capi.Photons(_d3(light), jitter, power, alpha, 0, hashsize, batch, photon_seed, initial_radius, pair_cap)
+        h = C.c_void_p()
+        check(self._L.cgrt_sppm_session_create(self._h, width, rows, spp, photon_depth, C.byref(ph), 0, C.byref(h)))
+        ses = SppmSession(self, h, width, rows, spp, dict(camera=camera, height=height, max_depth=max_depth, seed=seed,
+                                                          row_offset=row_offset, stripe=stripe))
+        self._sessions.add(ses)
+        return ses
+
     def _ray_tensors(self, what, org, dirs, keys, pixel=None):
         """The argument checks of trace_rays for the ray-buffer calls; returns n."""
         import torch
@@ -1365,6 +1382,117 @@ class PpmSession:
         hp = np.zeros((max(n, 1), 16), np.float64)
         cnt = C.c_uint64(0)
         check(self._L.cgrt_ppm_session_hitpoints(self._h, hp.ctypes.data, n, C.byref(cnt)))
+        return hp[:n]
+
+
+class SppmSession:
+    """Owns a cgrt_sppm_session (Scene.sppm_session).  Holds a reference to its Scene, which therefore outlives it; closing the
+    Scene closes its sessions first."""
+
+    def __init__(self, scene, h, width, rows, spp, grid):
+        self._scene = scene
+        self._L = scene._L
+        self._h = h
+        self.width, self.rows, self.spp = width, rows, spp
+        self._grid = grid  # what add_passes renders with
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.cgrt_sppm_session_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def add_passes(self, n, photons_per_pass, flags=0):
+        """n passes of the session's camera, each with `photons_per_pass` fresh photons: pass k (counted over the session's
+        life) traces samples k * spp .. k * spp + spp - 1 of every pixel.  flags: CGRT_GRID_* scheduling flags of the eye pass."""
+        g = self._grid
+        for _ in range(int(n)):
+            cc, cg = self._scene._structs(g["camera"], self.width, g["height"], self.rows, self.spp, g["max_depth"], g["seed"],
+                                          g["row_offset"], g["stripe"], self.info()["passes"] * self.spp, None, flags)
+            check(self._L.cgrt_sppm_session_pass_grid(self._h, C.byref(cc), C.byref(cg), int(photons_per_pass)))
+        return self
+
+    def add_pass_rays(self, org, dirs, nphotons, keys=None, pixel=None, max_depth=5, seed=12345, first_index=0):
+        """One pass over caller-supplied rays (cgrt_sppm_session_pass_rays): org, dirs, keys as for trace_rays; ray i gathers
+        into texel pixel[i] (int64 [n] on the scene's device; negative: not traced), or i % (width * rows) without `pixel` --
+        camera_rays' order.  max_depth is the eye depth.  Waits for torch's current stream, returns when the pass is applied."""
+        import torch
+
+        n = self._scene._ray_tensors("add_pass_rays", org, dirs, keys, pixel)
+        r = _capi.Rays(n, org.data_ptr(), dirs.data_ptr(), keys.data_ptr() if keys is not None else None, first_index, seed,
+                       max_depth, 0)
+        torch.cuda.current_stream(org.device).synchronize()  # the pass runs on the null stream
+        check(self._L.cgrt_sppm_session_pass_rays(self._h, C.byref(r), pixel.data_ptr() if pixel is not None else None,
+                                                  int(nphotons)))
+        return self
+
+    def info(self):
+        inf = _capi.SppmSessionInfo()
+        check(self._L.cgrt_sppm_session_get_info(self._h, C.byref(inf)))
+        return {f: getattr(inf, f) for f, _ in inf._fields_}
+
+    @property
+    def passes(self):
+        return self.info()["passes"]
+
+    @property
+    def photons_done(self):
+        return self.info()["photons_done"]
+
+    def image(self):
+        """[rows, W, 3] float64, row 0 = bottom: tau / (PI * R2 * photons_done * spp)."""
+        img = np.zeros((self.rows, self.width, 3), np.float64)
+        check(self._L.cgrt_sppm_session_image(self._h, img.ctypes.data, None))
+        return img
+
+    def rgb8(self):
+        """[rows, W, 3] uint8, top row first (contiguous rows only)."""
+        out = np.zeros((self.rows, self.width, 3), np.uint8)
+        check(self._L.cgrt_sppm_session_image(self._h, None, out.ctypes.data))
+        return out
+
+    def image_tensor(self, out=None, rgb8_out=None, stream=None):
+        """The image as a float64 [rows, W, 3] torch tensor on the scene's device, written on torch's current stream (or
+        `stream`) without a host copy.  rgb8_out (uint8 [rows, W, 3], optional) receives the tone-mapped bytes in the same
+        pass.  Returns `out`."""
+        import torch
+
+        dev = torch.device("cuda", self._scene.device)
+        if out is None:
+            out = torch.empty((self.rows, self.width, 3), dtype=torch.float64, device=dev)
+        assert out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (self.rows, self.width, 3)
+        if rgb8_out is not None:
+            assert rgb8_out.is_contiguous() and rgb8_out.dtype == torch.uint8 and rgb8_out.numel() == self.rows * self.width * 3
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(self._L.cgrt_sppm_session_image_device(self._h, out.data_ptr(),
+                                                     rgb8_out.data_ptr() if rgb8_out is not None else None, C.c_void_p(st)))
+        return out
+
+    def pixels(self):
+        """[rows * W, 8] float64: per texel {N, R2, tau[3], M_p of the last pass, Hitpoints of the last pass, 0}."""
+        px = np.zeros((self.rows * self.width, 8), np.float64)
+        check(self._L.cgrt_sppm_session_pixels(self._h, px.ctypes.data))
+        return px
+
+    def last_hitpoints(self):
+        """[n, 16]: the last pass's table in PpmSession.hitpoints()' layout and order, flux = Phi_h, r2 = the radius the pass
+        searched with, n = M_h."""
+        n = self.info()["hp_count"]
+        hp = np.zeros((max(n, 1), 16), np.float64)
+        cnt = C.c_uint64(0)
+        check(self._L.cgrt_sppm_session_last_hitpoints(self._h, hp.ctypes.data, n, C.byref(cnt)))
         return hp[:n]
 
 

@@ -46,7 +46,8 @@ extern "C" {
                             (bounce queries); cgrt_wavefront, cgrt_wavefront_rays, cgrt_wavefront_rays_host,
                             cgrt_wavefront_rays_variant, cgrt_scene_last_wavefront, cgrt_scene_last_wavefront_rays
                             (wavefront trace); cgrt_hitpoints, cgrt_ppm_session_create_hitpoints (photon mapping of
-                            caller-supplied Hitpoints) */
+                            caller-supplied Hitpoints); the cgrt_sppm_session_ calls, cgrt_sppm_update_host, cgrt_sppm_check_host
+                            (stochastic progressive photon mapping) */
 
 enum {
     CGRT_OK = 0,
@@ -831,6 +832,83 @@ typedef struct cgrt_ppm_session_info {
     double ms_last_add, ms_last_image;                      /* the last add_photons (or create), the last gather     */
 } cgrt_ppm_session_info;
 int cgrt_ppm_session_get_info(const cgrt_ppm_session *p, cgrt_ppm_session_info *out);
+
+/* ---- stochastic progressive photon mapping (Hachisuka & Jensen 2009): an eye pass per photon pass -----------------------
+ * Every cgrt_ppm_session keeps its eye pass's Hitpoints for the whole render, each with a radius, count and flux of its own:
+ * memory grows with the sample count, and depth of field, antialiasing and glass edges never converge past that fixed sample
+ * set.  Here the statistics belong to the TEXEL, every pass traces fresh eye samples and a fresh photon batch, and the texel's
+ * radius shrinks once per pass: memory is one pass's Hitpoints plus 8 doubles per texel, whatever the number of passes.
+ * A session owns, per texel p of a width x rows image, N (starts 0), R2 (starts r0^2; r0 and the hash cell length come from
+ * initial_radius as for every photon session) and tau[3] (starts 0); and photons_done and passes (start 0).  A pass takes an
+ * eye-ray set and a photon count M >= 0:
+ *   1. Capture: the Hitpoints of the rays as cgrt_ppm_session_create (a grid) or cgrt_ppm_session_create_rays (rays) captures
+ *      them, in the same table (bucket order, per-pixel index); every Hitpoint searches with its texel's current R2.
+ *   2. Photons [photons_done, photons_done + M) of the session's keyed stream (seed, i), traced and searched in batches as
+ *      cgrt_ppm_session_add_photons does.  The radius is constant during a pass, so the pairs that pass the search's two tests
+ *      -- dot(n_h, n_e) > 1e-4 and |pos - P|^2 <= R2 -- are the accepted set.  The candidate multiset is the photon pass's
+ *      own, the reference's two quirks included: hash cells slightly shorter than r0 (hash.h:25-26; a photon within R2 of a
+ *      Hitpoint but two cells away is not a candidate) and a bucket walked once per colliding cell (hash.h:35-37; with a small
+ *      hashsize a photon can count twice for one Hitpoint).
+ *   3. Per Hitpoint h, a left fold from 0 over its pairs in slot order (photon, then path segment), across the batches:
+ *      Phi_h = Phi_h + f_h * flux_e * (1 / PI);  M_h += 1.
+ *   4. Per texel, a left fold from 0 over its Hitpoints in the per-pixel index order: Phi_p += Phi_h;  M_p += M_h.
+ *   5. Only where M_p > 0, in fp64, in this order:  Nn = N + alpha * M_p;  g = Nn / (N + M_p);  R2 = R2 * g;
+ *      tau = (tau + Phi_p) * g;  N = Nn.
+ *   6. photons_done += M; passes += 1 -- also when the rays produce no Hitpoint; M = 0 captures, counts the pass and changes
+ *      nothing else of the texels' N, R2 and tau.
+ * image[p] = tau * (1 / (PI * R2 * (photons_done * spp))), row 0 = bottom; rgb8 as cgrt_ppm_session_image's.
+ * A batch is applied whole or not at all; the state after a pass does not depend on batch, pair_cap or halvings; a failing pass
+ * leaves the texels, photons_done and passes of the pass before (its Hitpoints are gone: last_hitpoints then gives none) and
+ * the session usable.  A texel's history depends only on its own rays and on all photons, so block-cyclic stripes give the rows
+ * of the full frame, every rank tracing all photons.  Radii only shrink, which keeps the session's hash grid valid: alpha
+ * must lie in (0, 1].
+ * Lifetime, ordering and streams as for cgrt_ppm_session: passes, image and pixels run on the null stream and synchronise;
+ * image_device runs on the caller's stream and the next pass waits for it.  Device memory: the texels, the last pass's table
+ * (freed before the next pass captures), the pair buffers (they grow to the largest pass's need), two event buffers. */
+typedef struct cgrt_sppm_session cgrt_sppm_session; /* opaque */
+/* ph->nphotons is not looked at; ph's other fields are fixed for the session's life.  photon_depth: the photons' depth limit,
+ * 1..5.  flags: 0.  Before any device is touched: a null ph, s or out, non-positive width, rows or spp, photon_depth outside
+ * 1..5, bad ph (as cgrt_ppm_session_create), alpha not in (0, 1] (NaN included), flags != 0, an uncommitted scene (the last of
+ * the checks): CGRT_ERR_INVALID; 2^31 texels or more: CGRT_ERR_LIMIT. */
+int cgrt_sppm_session_create(const cgrt_scene *s, int32_t width, int32_t rows, int32_t spp, int32_t photon_depth,
+                             const cgrt_photons *ph, int32_t flags, cgrt_sppm_session **out);
+/* Waits for anything in flight, then frees the session.  NULL is ignored. */
+void cgrt_sppm_session_destroy(cgrt_sppm_session *p);
+/* A pass whose eye rays are the built-in camera's: grid->width, rows and spp must be the session's; sample_offset, seed,
+ * max_depth (the eye depth) and the scheduling flags are the caller's (a renderer passes sample_offset = passes * spp).  The
+ * first pass fixes the stripes (stripe_rows, stripe_rank, stripe_nranks; a contiguous grid is one value whatever those fields
+ * hold); a later pass with other stripes is CGRT_ERR_INVALID, as are a grid cgrt_ppm_session_create refuses and nphotons < 0
+ * -- all before any device is touched. */
+int cgrt_sppm_session_pass_grid(cgrt_sppm_session *p, const cgrt_camera *cam, const cgrt_grid *grid, int64_t nphotons);
+/* A pass over caller-supplied rays: ray i belongs to texel pixel[i] ([n] DEVICE int64; negative: the ray is not traced), or
+ * with pixel == NULL to texel i % (width * rows).  Every rule of cgrt_ppm_session_create_rays holds: DEVICE arrays read before
+ * the call returns, dir = (0,0,0) is not traced, keys, the order contract; rays->max_depth is the eye depth, 1..5. */
+int cgrt_sppm_session_pass_rays(cgrt_sppm_session *p, const cgrt_rays *rays, const int64_t *pixel, int64_t nphotons);
+/* The image at the current state.  HOST buffers; either may be NULL.  CGRT_ERR_INVALID before the first photon (tau / (PI R2 0));
+ * rgb8 on a striped session: CGRT_ERR_UNSUPPORTED. */
+int cgrt_sppm_session_image(const cgrt_sppm_session *p, double *image, uint8_t *rgb8);
+/* Same into DEVICE buffers on the session's device, enqueued on `stream` (a hipStream_t as void*, NULL = null stream). */
+int cgrt_sppm_session_image_device(const cgrt_sppm_session *p, double *image, uint8_t *rgb8, void *stream);
+/* The texels: px8 is a HOST buffer of [width * rows][8] doubles = {N, R2, tau[3], M_p of the last pass, Hitpoints of the last
+ * pass, 0}. */
+int cgrt_sppm_session_pixels(const cgrt_sppm_session *p, double *px8);
+/* Up to cap hp16 records of the LAST pass's table, in cgrt_ppm_session_hitpoints' layout and order, with flux = Phi_h, r2 = the
+ * radius the pass searched with, n = M_h; *count = its Hitpoints. */
+int cgrt_sppm_session_last_hitpoints(const cgrt_sppm_session *p, double *hp16, uint64_t cap, uint64_t *count);
+typedef struct cgrt_sppm_session_info {
+    int64_t passes, photons_done;
+    uint64_t hp_count;                            /* Hitpoints of the last pass                                        */
+    uint64_t n_events, n_pairs, n_batch_halvings; /* as cgrt_ppm_result; sums over all passes so far                   */
+    int64_t device_bytes;                         /* device memory the session holds now                               */
+    double ms_eye, ms_table, ms_photons, ms_update; /* device time of the last pass's four stages, milliseconds        */
+} cgrt_sppm_session_info;
+int cgrt_sppm_session_get_info(const cgrt_sppm_session *p, cgrt_sppm_session_info *out);
+/* Host only, no GPU.  cgrt_sppm_update_host: step 5 for one texel, the very function the kernel calls; out5 = {N, R2, tau[3]}.
+ * cgrt_sppm_check_host: the argument checks of cgrt_sppm_session_create that need no scene and, where grid is not NULL, of a
+ * first pass's grid against such a session. */
+int cgrt_sppm_update_host(double N, double R2, const double *tau3, double M, const double *phi3, double alpha, double *out5);
+int cgrt_sppm_check_host(int32_t width, int32_t rows, int32_t spp, int32_t photon_depth, const cgrt_photons *ph, int32_t flags,
+                         const cgrt_grid *grid);
 
 /* ---- row f2 of SURVEY.md section 8: tone map, flip, PNG (util.h:45-47, main.cpp:403-412) ----------------------
  * rgb8[(height-1-h)*width + w][c] = int(pow(1 - exp(-image[h][w][c]), 1/2.2) * 255 + .5) computed on `device`;

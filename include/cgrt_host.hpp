@@ -700,6 +700,80 @@ class PpmSession {
     cgrt_ppm_session *session_;
 };
 
+// Stochastic progressive photon mapping (cgrt_sppm_session): the statistics belong to the pixel, every pass traces
+// rp.num_of_samples fresh eye samples per pixel and a fresh photon batch, and memory does not grow with the passes.  Pass k
+// traces the samples k * num_of_samples .. of rp's camera; pp.num_photon / pp.num_threads are not used: add_passes says how many
+// photons a pass traces.  pp.alpha must lie in (0, 1].
+class SppmSession {
+  public:
+    SppmSession(const std::vector<Object *> &objs, const RenderParams &rp, const PhotonParams &pp, int photon_depth = 5)
+        : width_(rp.width), height_(rp.height), session_(nullptr), grid_() {
+        for (const Object *o : objs) o->add_to(sb_);
+        check(cgrt_scene_commit(sb_.scene, rp.device));
+        rp.camorg.get(cam_.cam);
+        cam_.half_width = 10.0;
+        cam_.focus_plane = rp.focus_plane;
+        cam_.lens_radius = rp.depth_of_field ? rp.radius : 0.0;
+        grid_.width = rp.width;
+        grid_.height = rp.height;
+        grid_.rows = rp.height;
+        grid_.stripe_nranks = 1;
+        grid_.spp = rp.num_of_samples;
+        grid_.spp_total = rp.num_of_samples;
+        grid_.max_depth = rp.max_depth;
+        grid_.seed = rp.seed;
+        cgrt_photons ph{};
+        pp.lightorg.get(ph.light);
+        ph.jitter = pp.jitter;
+        ph.power = pp.power;
+        ph.alpha = pp.alpha;
+        ph.hashsize = pp.hashsize;
+        ph.seed = pp.seed;
+        ph.initial_radius = pp.initial_radius;
+        check(cgrt_sppm_session_create(sb_.scene, rp.width, rp.height, rp.num_of_samples, photon_depth, &ph, 0, &session_));
+    }
+    ~SppmSession() { cgrt_sppm_session_destroy(session_); }  // before sb_ destroys the scene
+    SppmSession(const SppmSession &) = delete;
+    SppmSession &operator=(const SppmSession &) = delete;
+
+    // n passes of the camera, each with photons_per_pass fresh photons
+    void add_passes(int n, long long photons_per_pass) {
+        for (int k = 0; k < n; k++) {
+            grid_.sample_offset = (int32_t)(info().passes * grid_.spp);
+            check(cgrt_sppm_session_pass_grid(session_, &cam_, &grid_, photons_per_pass));
+        }
+    }
+    // one pass over caller-supplied rays (cgrt_sppm_session_pass_rays): DEVICE arrays on the scene's device; pixel may be null
+    void add_pass_rays(const cgrt_rays &rays, const int64_t *pixel, long long nphotons) {
+        check(cgrt_sppm_session_pass_rays(session_, &rays, pixel, nphotons));
+    }
+    long long passes() const { return (long long)info().passes; }
+    long long photons_done() const { return (long long)info().photons_done; }
+    // the image (doubles, row 0 = bottom) and the bytes main.cpp:403-411 hands to stbi_write_png
+    void image(std::vector<double> &image, std::vector<unsigned char> &image_data) const {
+        image.assign((size_t)width_ * height_ * 3, 0.0);
+        image_data.assign((size_t)width_ * height_ * 3, 0);
+        check(cgrt_sppm_session_image(session_, image.data(), image_data.data()));
+    }
+    // per pixel {N, R2, tau[3], M_p and Hitpoints of the last pass, 0}
+    void pixels(std::vector<double> &px8) const {
+        px8.assign((size_t)width_ * height_ * 8, 0.0);
+        check(cgrt_sppm_session_pixels(session_, px8.data()));
+    }
+    cgrt_sppm_session_info info() const {
+        cgrt_sppm_session_info inf{};
+        check(cgrt_sppm_session_get_info(session_, &inf));
+        return inf;
+    }
+
+  private:
+    int width_, height_;
+    SceneBuilder sb_;
+    cgrt_sppm_session *session_;
+    cgrt_camera cam_;
+    cgrt_grid grid_;
+};
+
 // stbi_write_png("test.png", width, height, 3, image_data, width * 3), main.cpp:412
 inline void write_png(const char *path, int width, int height, const std::vector<unsigned char> &image_data) {
     check(cgrt_write_png(path, width, height, image_data.data()));
