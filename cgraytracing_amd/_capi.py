@@ -36,6 +36,11 @@ class Camera(C.Structure):
                 ("lens_radius", C.c_double)]
 
 
+class PosedCamera(C.Structure):  # cgrt_posed_camera: with GRID_POSED a call's camera argument points at its `base`
+    _fields_ = [("base", Camera), ("origin", C.c_double * 3), ("right", C.c_double * 3), ("up", C.c_double * 3),
+                ("forward", C.c_double * 3)]  # 144 bytes
+
+
 class Grid(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("rows", C.c_int32), ("row_offset", C.c_int32),
                 ("stripe_rows", C.c_int32), ("stripe_rank", C.c_int32), ("stripe_nranks", C.c_int32),
@@ -53,6 +58,7 @@ GRID_NO_LENS_STAGE, GRID_NO_SURE_TILES = 131072, 262144
 GRID_RELAY_COST_START, GRID_NO_RELAY_COST_START, GRID_RELAY_BOOST, GRID_NO_RELAY_BOOST = 524288, 1048576, 2097152, 4194304
 GRID_NO_LENS_TABLE, GRID_LENS_TABLE = 8388608, 16777216
 GRID_NO_INSIDE_TRIPS = 33554432
+GRID_POSED = 67108864
 
 
 class Photons(C.Structure):
@@ -160,6 +166,8 @@ _DP = C.POINTER(C.c_double)
 SIGNATURES = {
     "cgrt_version": (C.c_int, []),
     "cgrt_last_error": (C.c_char_p, []),
+    # (the posed camera; a library built before it has no such symbol and is refused at load)
+    "cgrt_look_at": (C.c_int, [_DP, _DP, _DP, C.c_double, C.c_double, C.c_double, C.POINTER(PosedCamera)]),
     "cgrt_scene_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "cgrt_scene_destroy": (None, [C.c_void_p]),
     "cgrt_scene_set_build": (C.c_int, [C.c_void_p, C.c_int]),

@@ -52,6 +52,13 @@ __host__ __device__ __forceinline__ void lens_disc(uint64_t k_smp, double &sx, d
     }
 }
 
+// A point of the camera's frame in the world (pose_point, cgrt_frame.h): the POSE kernels' primary rays start from these
+__device__ __forceinline__ V3 pose_v(const GridParams &g, const V3 &p) {
+    V3 w;
+    pose_point(g, p.x, p.y, p.z, w.x, w.y, w.z);
+    return w;
+}
+
 struct HitpointSink {
     double *rec;                // cap x 10 doubles: f(3) pos(3) normal(3) label
     unsigned long long *count;  // appended so far (may exceed cap: then the tail was dropped)
@@ -118,8 +125,11 @@ __device__ __forceinline__ RelayForm relay_form(const GridParams &g, const Relay
 // LTAB (the full and the parking body of the thin-lens PAIR variants' table-reading twins): the lens draws of this workgroup's
 // samples lie in the lens table (cgrt_lens_stage.h), lens_row = table[entry][0][0] of its list entry (workgroup-uniform); the body
 // computes no sample key and runs no rejection loop.
+// POSE (the kernels of a launch with CGRT_GRID_POSED, cgrt.h): the camera's frame stands in the world (g.pose_*); a pixel's
+// direction and focus point, the eye and every lens point are the images of the frame's points under pose_point, the direction
+// normalised from those (cgrt_frame.h has the definition).  Without POSE none of it is compiled.
 template <bool TREES, bool BEZ, bool DOF, bool GLASS, bool SPH, bool STATS, bool HPS, int NT, bool HEAVY, bool SPILL = false, bool HFONLY = false,
-          bool DIFF = false, bool PAIR = false, bool PARK = false, bool LSTAGE = false, bool COST = false, bool LTAB = false>
+          bool DIFF = false, bool PAIR = false, bool PARK = false, bool LSTAGE = false, bool COST = false, bool LTAB = false, bool POSE = false>
 __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const GridParams &g, float *__restrict__ rgb,
                                                 uint32_t *__restrict__ nhit_out, unsigned long long *__restrict__ counters,
                                                 const HitpointSink &hps, int tile_block, int tile_grid, const RelayWg rw = RelayWg{},
@@ -131,6 +141,7 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
     static_assert(!PAIR || (SPH && GLASS && !HPS && !HEAVY && !STATS && !SPILL), "PAIR: the glass sphere variants of the tile order");
     static_assert(!LSTAGE || (DIFF && DOF && !PAIR), "LSTAGE: the thin-lens terminal-diffuse body inside a PAIR launch");
     static_assert(!COST || PAIR, "COST: the PAIR variants with a start table");
+    static_assert(!POSE || (!DIFF && !PAIR && !LSTAGE && !LTAB), "POSE: no body of the tile order, whose tests stand in the built-in frame");
     // (the launch asked for the PAIR body's LDS -- pending-ray levels, then the object list; this body's object list lies at the
     // start and its batches behind it: they fit where the levels are, so the request and the occupancy stay what they were)
     static_assert(!LSTAGE || lens_batch_lds(NT) <= (size_t)kLdsLevels * pending_level_bytes(NT), "the lens batches fit the PAIR launch's pending-ray levels");
@@ -191,6 +202,7 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int wtiles_x = (g.W + kWaveTileW - 1) / kWaveTileW, wtiles_y = (g.rows + kWaveTileH - 1) / kWaveTileH;
     const V3 camorg = mk(g.cam[0], g.cam[1], g.cam[2]);
+    const V3 camw = POSE ? pose_v(g, camorg) : camorg;  // the eye in the world
     // HEAVY: this launch's waves serve the queue of heavy-tile items instead of owning a tile each (its own kernel variant:
     // the per-unit pixel state costs registers the tile variant does not have to spare).
     constexpr bool heavy = HEAVY;
@@ -212,6 +224,10 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
         const double py = (2.0 * ((double)h / g.H) - 1) * g.half_width * g.H / g.W;
         pdir = normalized(mk(px, py, 0) - camorg);
         pof = pdir * ((g.focus_plane - camorg.z) / pdir.z) + camorg;
+        if (POSE) {  // both from here on in the world
+            pof = pose_v(g, pof);
+            pdir = normalized(pose_v(g, mk(px, py, 0)) - camw);
+        }
         k_pix = pixel_key(g.seed, (uint64_t)h * (uint64_t)g.W + (uint64_t)w);
     };
     if (!heavy) {
@@ -338,10 +354,11 @@ __device__ __forceinline__ void trace_grid_body(const DeviceScene &sc, const Gri
             double sx, sy;
             lens_disc(k_smp, sx, sy);  // purpose 0: the lens stream's key is the sample key
             o = camorg + mk(sx, sy, 0) * g.lens_radius;
+            if (POSE) o = pose_v(g, o);
             d = normalized(pof - o);
         } else {
             k_smp = sample_key(k_pix, (uint64_t)(g.sample_offset + smp));
-            o = camorg;
+            o = POSE ? camw : camorg;
             d = pdir;
         }
         adj = mk(1, 1, 1);
@@ -826,7 +843,7 @@ __device__ __forceinline__ void wg_counters_end(const unsigned long long *wg, un
 
 // One launch = tile workgroups only (probe, image order, Hitpoint capture) ...
 template <bool TREES, bool BEZ, bool DOF, bool GLASS, bool SPH, bool STATS, bool HPS = false, int NT = 256, bool SPILL = false, bool HFONLY = false,
-          bool DIFF = false, bool PAIR = false, bool START = false, bool LTAB = false>
+          bool DIFF = false, bool PAIR = false, bool START = false, bool LTAB = false, bool POSE = false>
 __global__ __launch_bounds__(NT, DIFF ? (DOF ? kDiffDofWaves : kDiffWaves) : BEZ ? kBezWaves : ((TREES && !HFONLY) ? kTreeWaves : 4)) void trace_grid_kernel(DeviceScene sc, GridParams g, float *__restrict__ rgb,
                                                              uint32_t *__restrict__ nhit_out,
                                                              unsigned long long *__restrict__ counters,
@@ -842,7 +859,7 @@ __global__ __launch_bounds__(NT, DIFF ? (DOF ? kDiffDofWaves : kDiffWaves) : BEZ
     int tile_block = (int)blockIdx.x, tile_grid = (int)gridDim.x;
     unsigned entry = blockIdx.x;
     RelayWg rw;
-    if (g.tile_order) {
+    if (!POSE && g.tile_order) {  // (a posed launch has no tile order, cgrt_frame.h)
         if (g.tile_order == kOrderFull || g.tile_order == kOrderDiffuse) {
             const unsigned first_diffuse = load_uniform(g.plan + 3);
             if (g.tile_order == kOrderDiffuse) entry += first_diffuse;
@@ -905,14 +922,14 @@ __global__ __launch_bounds__(NT, DIFF ? (DOF ? kDiffDofWaves : kDiffWaves) : BEZ
     } else if (PAIR && rw.chunk > 0)  // a relayed tile's later chunks park their values
         trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF, PAIR, PAIR, false, START>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid, rw);
     else
-        trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF, PAIR, false, false, START>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid, rw);
+        trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, false, SPILL, HFONLY, DIFF, PAIR, false, false, START, false, POSE>(sc, g, rgb, nhit_out, wc, hps, tile_block, tile_grid, rw);
     wg_counters_end(wg_cnt, counters);
 }
 // ... or the scheduled form: the first g.heavy_blocks workgroups serve the heavy tiles' unit queue, the others are the tile
 // workgroups.  Two bodies in one kernel: the dispatcher starts workgroups in index order, so the heavy work starts first and
 // tile workgroups take over the slots as the heavy waves retire -- no seam between two launches.  Each body keeps its own
 // register allocation (the paths are disjoint); the kernel's register and scratch sizes are the larger of the two.
-template <bool TREES, bool BEZ, bool DOF, bool GLASS, bool SPH, bool STATS, int NT = 256>
+template <bool TREES, bool BEZ, bool DOF, bool GLASS, bool SPH, bool STATS, int NT = 256, bool POSE = false>
 __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kSchedTreeWaves : 4)) void trace_grid_sched_kernel(DeviceScene sc, GridParams g,
                                                                                          float *__restrict__ rgb,
                                                                                          uint32_t *__restrict__ nhit_out,
@@ -926,11 +943,10 @@ __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kSchedTreeWaves : 4)
         // moment its wave ends, and measured on a C5 band the queue form bought nothing (34.6 vs 34.9 ms) while its larger
         // kernel cost 4 %
         if (heavy_first)
-            trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, false, NT, true>(sc, g, rgb, nhit_out, wc, none, 0, 1);
+            trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, false, NT, true, false, false, false, false, false, false, false, false, POSE>(sc, g, rgb, nhit_out, wc, none, 0, 1);
         else
-            trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, false, NT, false>(sc, g, rgb, nhit_out, wc, none,
-                                                                                  (int)blockIdx.x - g.heavy_blocks,
-                                                                                  (int)gridDim.x - g.heavy_blocks);
+            trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, false, NT, false, false, false, false, false, false, false, false, false, POSE>(
+                sc, g, rgb, nhit_out, wc, none, (int)blockIdx.x - g.heavy_blocks, (int)gridDim.x - g.heavy_blocks);
         wg_counters_end(wg_cnt, counters);
         return;
     }
@@ -942,7 +958,7 @@ __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kSchedTreeWaves : 4)
     for (int phase = 0; phase < 2; phase++) {
         if ((phase == 0) == heavy_first) {
             if (queued || heavy_first)
-                trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, false, NT, true>(sc, g, rgb, nhit_out, wc, none, 0, 1);
+                trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, false, NT, true, false, false, false, false, false, false, false, false, POSE>(sc, g, rgb, nhit_out, wc, none, 0, 1);
         } else {
             const unsigned n_entries = queued ? load_uniform(g.plan + 3) : (heavy_first ? 0u : 1u);
             unsigned served = 0;
@@ -955,7 +971,7 @@ __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kSchedTreeWaves : 4)
                     e = tile_entry;
                 }
                 if (e >= n_entries) break;
-                trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, false, NT, false>(
+                trace_grid_body<TREES, BEZ, DOF, GLASS, SPH, STATS, false, NT, false, false, false, false, false, false, false, false, false, POSE>(
                     sc, g, rgb, nhit_out, wc, none, queued ? (int)g.border[e] : (int)blockIdx.x - g.heavy_blocks,
                     queued ? -1 : (int)gridDim.x - g.heavy_blocks);
             }
@@ -1438,6 +1454,8 @@ __global__ __launch_bounds__(1024) void plan_kernel(const uint32_t *__restrict__
 }
 
 // The per-pixel camera constants of the heavy tiles (what set_pixel computes), one 64-thread workgroup per heavy tile.
+// POSE: a posed launch's -- direction and focus point in the world, as set_pixel has them there.
+template <bool POSE = false>
 __global__ __launch_bounds__(64) void pixel_const_kernel(GridParams g) {
     const unsigned hr = blockIdx.x;
     if (hr >= g.plan[0]) return;
@@ -1450,8 +1468,12 @@ __global__ __launch_bounds__(64) void pixel_const_kernel(GridParams g) {
     // main.cpp:188-189,198,203 -- the same expressions as set_pixel
     const double px = (2.0 * ((double)w / g.W) - 1) * g.half_width;
     const double py = (2.0 * ((double)h / g.H) - 1) * g.half_width * g.H / g.W;
-    const V3 pdir = normalized(mk(px, py, 0) - camorg);
-    const V3 pof = pdir * ((g.focus_plane - camorg.z) / pdir.z) + camorg;
+    V3 pdir = normalized(mk(px, py, 0) - camorg);
+    V3 pof = pdir * ((g.focus_plane - camorg.z) / pdir.z) + camorg;
+    if (POSE) {
+        pof = pose_v(g, pof);
+        pdir = normalized(pose_v(g, mk(px, py, 0)) - pose_v(g, camorg));
+    }
     const uint64_t k_pix = pixel_key(g.seed, (uint64_t)h * (uint64_t)g.W + (uint64_t)w);
     double *pc = g.pconst + (size_t)hr * (7 * 64) + p;
     pc[0 * 64] = pdir.x; pc[1 * 64] = pdir.y; pc[2 * 64] = pdir.z;

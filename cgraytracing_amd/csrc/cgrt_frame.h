@@ -119,8 +119,97 @@ struct GridParams {
     // table[entry][sample][thread], lens_table_spp samples an entry, written by lens_table_kernel ahead of the frame
     const uint64_t *lens_table;
     int32_t lens_table_cap, lens_table_spp;
+    // posed != 0 (CGRT_GRID_POSED; the POSE kernels, camera_ray): the camera's frame in the world -- `cam`, half_width, focus_plane
+    // and lens_radius above are the camera in that frame, and the primary rays start from pose_point's images of its points.
+    // posed == 0: the identity frame (origin 0, the unit axes), which no kernel reads.
+    double pose_origin[3], pose_right[3], pose_up[3], pose_forward[3];
+    int32_t posed, pad_pose_;
 };
-static_assert(sizeof(GridParams) == 384, "GridParams is a kernel argument: its layout is fixed");
+static_assert(sizeof(GridParams) == 488, "GridParams is a kernel argument: its layout is fixed");
+static_assert(offsetof(GridParams, pose_origin) == 384, "the pose is appended: no earlier field moves");
+
+#if defined(__HIPCC__)
+#define CGRT_HD __host__ __device__ __forceinline__
+#else
+#define CGRT_HD inline
+#endif
+// ---- the posed camera (cgrt_posed_camera, cgrt.h) ----
+// M(p) = ((origin + right * p.x) + up * p.y) + forward * p.z, per component in exactly this order; the library is built without
+// contraction, so host and device give the same bits.  For the identity frame every product is p's component or a zero and
+// every sum adds zeros: M(p) == p (a component of -0 comes out as +0, the same value).
+// The one definition of a posed primary ray, used by trace_grid_body and pixel_const_kernel (cgrt_eye.hpp) and by camera_ray
+// (cgrt_rays.hpp): in the camera's own frame nothing changes -- the pixel point pix = (px, py, 0), the eye cam, the focus point
+// pof = pdir * ((focus_plane - cam.z) / pdir.z) + cam with pdir = normalized(pix - cam), the lens point o = cam + (sx, sy, 0) *
+// lens_radius -- and the ray is made of the images of those points:
+//     pinhole:   origin M(cam), direction normalized(M(pix) - M(cam))
+//     thin lens: origin M(o),   direction normalized(M(pof) - M(o))       (M(pof) once per pixel, M(o) once per sample)
+// The direction is normalised from world points: unit to the standard of the built-in camera's, whatever the basis's last bits.
+CGRT_HD void pose_point(const GridParams &g, double x, double y, double z, double &wx, double &wy, double &wz) {
+    wx = ((g.pose_origin[0] + g.pose_right[0] * x) + g.pose_up[0] * y) + g.pose_forward[0] * z;
+    wy = ((g.pose_origin[1] + g.pose_right[1] * x) + g.pose_up[1] * y) + g.pose_forward[1] * z;
+    wz = ((g.pose_origin[2] + g.pose_right[2] * x) + g.pose_up[2] * y) + g.pose_forward[2] * z;
+}
+
+// What is wrong with the camera of (cam, grid), or nullptr: with CGRT_GRID_POSED `cam` is the base of a cgrt_posed_camera whose
+// 12 numbers must be finite, its axes of length 1 within kPoseTol and orthogonal within kPoseTol (no handedness is asked: a
+// mirrored basis mirrors the image).  The one validation of a pose, asked by every entry before grid_params reads it.
+static constexpr double kPoseTol = 1e-9;
+inline const char *pose_error(const cgrt_camera *cam, const cgrt_grid *grid) {
+    if (!(grid->flags & CGRT_GRID_POSED)) return nullptr;
+    const cgrt_posed_camera *pc = reinterpret_cast<const cgrt_posed_camera *>(cam);
+    const double *ax[3] = {pc->right, pc->up, pc->forward};
+    for (int k = 0; k < 3; k++) {
+        if (!std::isfinite(pc->origin[k])) return "posed camera: origin is not finite";
+        for (int a = 0; a < 3; a++)
+            if (!std::isfinite(ax[a][k])) return "posed camera: a basis vector is not finite";
+    }
+    const auto dot3 = [](const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
+    for (int a = 0; a < 3; a++)
+        if (!(std::fabs(std::sqrt(dot3(ax[a], ax[a])) - 1.0) <= kPoseTol)) return "posed camera: right, up and forward must have length 1 (within 1e-9)";
+    for (int a = 0; a < 3; a++)
+        if (!(std::fabs(dot3(ax[a], ax[(a + 1) % 3])) <= kPoseTol)) return "posed camera: right, up and forward must be orthogonal (dot products within 1e-9)";
+    return nullptr;
+}
+
+// cgrt_look_at (cgrt.h) in plain fp64; nullptr, or what is wrong with the arguments
+inline const char *look_at_camera(const double eye[3], const double target[3], const double up_hint[3], double fov_x_deg,
+                                  double focus_distance, double lens_radius, cgrt_posed_camera *out) {
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(eye[k]) || !std::isfinite(target[k]) || !std::isfinite(up_hint[k])) return "cgrt_look_at: eye, target and up_hint must be finite";
+    if (!(fov_x_deg > 0 && fov_x_deg < 180)) return "cgrt_look_at: fov_x_deg must lie in (0, 180)";
+    if (!(focus_distance > 0) || !std::isfinite(focus_distance)) return "cgrt_look_at: focus_distance must be positive";
+    if (!(lens_radius >= 0) || !std::isfinite(lens_radius)) return "cgrt_look_at: lens_radius must be >= 0";
+    const auto norm3 = [](const double *v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
+    const auto cross3 = [](const double *a, const double *b, double *c) {
+        c[0] = a[1] * b[2] - a[2] * b[1];
+        c[1] = a[2] * b[0] - a[0] * b[2];
+        c[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    double f[3] = {target[0] - eye[0], target[1] - eye[1], target[2] - eye[2]}, r[3], u[3];
+    const double D = norm3(f);
+    if (!(D > 0) || !std::isfinite(D)) return "cgrt_look_at: eye and target coincide";
+    for (int k = 0; k < 3; k++) f[k] /= D;
+    cross3(up_hint, f, r);
+    const double rl = norm3(r), ul = norm3(up_hint);
+    // (parallel: the sine of the angle between hint and view below 1e-12)
+    if (!(ul > 0) || !(rl > 1e-12 * ul)) return "cgrt_look_at: up_hint is zero or parallel to the view";
+    for (int k = 0; k < 3; k++) r[k] /= rl;
+    cross3(f, r, u);
+    cgrt_posed_camera pc;
+    pc.base.cam[0] = pc.base.cam[1] = 0.0;
+    pc.base.cam[2] = -D;
+    pc.base.half_width = D * std::tan(fov_x_deg * (3.14159265358979323846 / 360.0));
+    pc.base.focus_plane = focus_distance - D;
+    pc.base.lens_radius = lens_radius;
+    for (int k = 0; k < 3; k++) {
+        pc.origin[k] = target[k];
+        pc.right[k] = r[k];
+        pc.up[k] = u[k];
+        pc.forward[k] = f[k];
+    }
+    *out = pc;
+    return nullptr;
+}
 // the head of the order buffer's boost part, in words: S (two words), the promoted entries, the table's items; bslot follows
 static constexpr int kBoostS = 0, kBoostPromoted = 2, kBoostItems = 3, kBoostHead = 4;
 
@@ -227,7 +316,8 @@ inline int tile_grid_blocks(int W, int rows, bool xcd_tiles, int tile_w = kTileW
 
 // The GridParams of a launch over `grid` seen from `cam`, every scheduling, chunk and primary-walk field at its default:
 // row-major tiles, one workgroup per tile with all its samples, no probe, no light split, nothing deferred or walked ahead
-// (fields not named here are 0 / nullptr).
+// (fields not named here are 0 / nullptr).  With CGRT_GRID_POSED `cam` is the base of a cgrt_posed_camera that pose_error has
+// passed; without it no byte behind the cgrt_camera is read and the frame is the identity.
 inline GridParams grid_params(const cgrt_camera *cam, const cgrt_grid *grid) {
     GridParams g{};
     g.W = grid->width;
@@ -255,6 +345,17 @@ inline GridParams grid_params(const cgrt_camera *cam, const cgrt_grid *grid) {
     g.prim_obj = -1;
     g.pw_refill = 16;
     g.pw_rounds = 8;
+    g.pose_right[0] = g.pose_up[1] = g.pose_forward[2] = 1.0;
+    if (grid->flags & CGRT_GRID_POSED) {
+        const cgrt_posed_camera *pc = reinterpret_cast<const cgrt_posed_camera *>(cam);
+        for (int k = 0; k < 3; k++) {
+            g.pose_origin[k] = pc->origin[k];
+            g.pose_right[k] = pc->right[k];
+            g.pose_up[k] = pc->up[k];
+            g.pose_forward[k] = pc->forward[k];
+        }
+        g.posed = 1;
+    }
     return g;
 }
 
@@ -430,6 +531,11 @@ struct FrameInputs {
     bool order_ok = false, aux_stream = false, all_spheres = false;
     int n_objs = 0, n_lds = 0;
     bool all_special = false;
+    // CGRT_GRID_POSED: the launch runs the POSE kernels; the tile order and what hangs on it, the light-tile split and the
+    // primary walk reason about rays in the built-in frame and are left out (cgrt.h).  posed_cam: the whole camera of such a
+    // launch (its base is `cam` above), which frame_params reads; unposed launches leave it alone
+    bool posed = false;
+    cgrt_posed_camera posed_cam{};
 };
 
 // Where each array of a launch lies in the handle's scratch, in bytes from its start: the chunk sums, then (scheduled
@@ -644,7 +750,7 @@ inline FramePlan frame_plan(const FrameInputs &in, size_t kmax) {
     // itself: order_ok means no mesh, hence row-major tiles, and without split_asked there is one chunk.)
     TileOrderPlan &o = p.order;
     const bool split_asked = (gr.flags & CGRT_GRID_SPLIT_SAMPLES) != 0;
-    o.on = in.image && p.chunks == 1 && !p.xcd_tiles && in.nt == kThreads && in.order_ok && !(gr.flags & CGRT_GRID_NO_TILE_ORDER);
+    o.on = in.image && p.chunks == 1 && !p.xcd_tiles && in.nt == kThreads && in.order_ok && !(gr.flags & CGRT_GRID_NO_TILE_ORDER) && !in.posed;
     if (o.on && !in.all_special) {
         if (in.sph && !in.spill && !in.stats && in.aux_stream && (gr.flags & CGRT_GRID_DIFFUSE_TILES) && !split_asked && !kn.timeline_file)
             o.class3 = TileOrderPlan::SecondLaunch;
@@ -677,7 +783,7 @@ inline FramePlan frame_plan(const FrameInputs &in, size_t kmax) {
     p.wtiles_y = (gr.rows + kWaveTileH - 1) / kWaveTileH;
     p.n_wt = (size_t)p.wtiles_x * p.wtiles_y;
     // primary-ray mesh hits of the heavy tiles' units (cgrt_primwalk.hpp): a double and an int per unit
-    p.use_prim = in.sched && in.prim_obj >= 0 && !kn.no_primwalk && !(gr.flags & CGRT_GRID_STATS);
+    p.use_prim = in.sched && in.prim_obj >= 0 && !kn.no_primwalk && !(gr.flags & CGRT_GRID_STATS) && !in.posed;
     // per heavy tile: its Hitpoint values [spp][maxhp][64 px][3], their counts [spp][64 px] (padded to 8 bytes), the pixel
     // constants [7][64] and, with the primary walk, its distances and triangles [spp][64]
     const size_t units = (size_t)gr.spp * 64;
@@ -699,7 +805,7 @@ inline FramePlan frame_plan(const FrameInputs &in, size_t kmax) {
     const size_t np = (p.n_wt + 8) * sizeof(uint32_t), sched_bytes = align256(4 * np + 64 * sizeof(uint32_t) + align256(p.n_wt));
     L.total += sched_bytes + (p.kmax ? p.kmax * p.tile_bytes + 256 : 0);
     if (p.kmax == 0) return p;
-    p.split_light = in.light_ok && p.chunks == 1 && !in.stats;
+    p.split_light = in.light_ok && p.chunks == 1 && !in.stats && !in.posed;
     // tiles through a queue too (GridParams::border) unless their samples are split over workgroups or the workgroups are
     // single waves (trace_grid_sched_kernel)
     p.tile_queue = p.chunks == 1 && !one_wave && !kn.no_tile_queue;
@@ -746,7 +852,7 @@ inline size_t fit_heavy_tiles(const FrameInputs &in, size_t kmax, size_t refused
 
 // The launch's GridParams, scratch not yet placed
 inline GridParams frame_params(const FrameInputs &in, const FramePlan &p) {
-    GridParams g = grid_params(&in.cam, &in.grid);
+    GridParams g = grid_params(in.posed ? &in.posed_cam.base : &in.cam, &in.grid);
     g.xcd_tiles = p.xcd_tiles ? 1 : 0;
     g.chunks = p.chunks;
     g.chunk_spp = p.chunk_spp;

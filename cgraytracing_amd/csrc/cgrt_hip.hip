@@ -216,6 +216,13 @@ static int upload(cgrt_scene *s, const std::vector<T> &v, const T **out, size_t 
 extern "C" {
 
 int cgrt_version(void) { return CGRT_VERSION; }
+
+int cgrt_look_at(const double eye[3], const double target[3], const double up_hint[3], double fov_x_deg, double focus_distance,
+                 double lens_radius, cgrt_posed_camera *out) {
+    if (!eye || !target || !up_hint || !out) return fail(CGRT_ERR_INVALID, "cgrt_look_at: null argument");
+    if (const char *bad = look_at_camera(eye, target, up_hint, fov_x_deg, focus_distance, lens_radius, out)) return fail(CGRT_ERR_INVALID, bad);
+    return CGRT_OK;
+}
 const char *cgrt_last_error(void) { return g_err.c_str(); }
 
 int cgrt_scene_create(cgrt_scene **out) {
@@ -674,14 +681,27 @@ static constexpr SchedKernel sched_kernel() {
      sched_kernel<SCHED != 0, T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, NT>()},
 static const EyeKernels kEyeKernels[] = {CGRT_EYE_VARIANTS(CGRT_X)};
 #undef CGRT_X
-static const EyeKernels *eye_kernels(const EyeFlags &f) { return variant_row(kEyeKernels, f); }
+// ... and those of a posed launch: CGRT_EYE_POSED_VARIANTS, every one with POSE
+template <bool SCHED, bool T, bool B, bool D, bool G, bool P, bool S, int NT>
+static constexpr SchedKernel sched_posed_kernel() {
+    if constexpr (SCHED) return &trace_grid_sched_kernel<T, B, D, G, P, S, NT, true>;
+    else return nullptr;
+}
+#define CGRT_X(T, B, D, G, P, S, H, NT, SP, HF, DF, PR, ST, LT, SCHED)                                                                            \
+    {EyeFlags{T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, SP != 0, HF != 0, NT, DF != 0, PR != 0, ST != 0, LT != 0, true}.id(),       \
+     &trace_grid_kernel<T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, H != 0, NT, SP != 0, HF != 0, DF != 0, PR != 0, ST != 0, LT != 0, true>, \
+     sched_posed_kernel<SCHED != 0, T != 0, B != 0, D != 0, G != 0, P != 0, S != 0, NT>()},
+static const EyeKernels kEyePosedKernels[] = {CGRT_EYE_POSED_VARIANTS(CGRT_X)};
+#undef CGRT_X
+static const EyeKernels *eye_kernels(const EyeFlags &f) { return f.pose ? variant_row(kEyePosedKernels, f) : variant_row(kEyeKernels, f); }
 
 // Objects the most general variant (the Hitpoint capture, or the eye pass's SPILL form) keeps resident: the scene's n_lds when
 // its list fits beside the variant's other LDS, else as many as fit beside one staging record per wave (the SPILL variant
 // then reads the rest from `objs`).
-static int general_resident(const cgrt_scene *s, bool dof, bool hps) {
+static int general_resident(const cgrt_scene *s, bool dof, bool hps, bool posed) {
     const DeviceScene &d = s->dev;
-    const size_t st = kernel_static_lds(reinterpret_cast<const void *>(eye_kernels(general_flags(dof, hps, true))->grid));
+    const EyeFlags gf = general_flags(dof, hps, true);
+    const size_t st = kernel_static_lds(reinterpret_cast<const void *>(eye_kernels(posed ? posed_flags(gf) : gf)->grid));
     const size_t lim = device_lds_bytes(s->device);
     if (eye_lds(general_flags(dof, hps, d.n_objs > d.n_lds), d) + st <= lim) return d.n_lds;
     const long long room = (long long)lim - (long long)(st + eye_lds(general_flags(dof, hps, true), with_resident(d, 0)));
@@ -689,7 +709,6 @@ static int general_resident(const cgrt_scene *s, bool dof, bool hps) {
 }
 
 // ---- the eye pass's launch plan ----
-enum class EyeForm { Image, Sched, SpillSph, SpillGen, Capture, Light, LightHF, Diffuse };
 // One launch of the eye pass: which kernel (form and template flags), the scene as it sees it and its dynamic LDS
 struct EyeLaunch {
     EyeForm form;
@@ -718,39 +737,17 @@ static InsideTrait inside_paying(const DeviceScene &d) {
 // The eye pass's main launch for (scene, camera, grid): the Hitpoint capture (capture), else cgrt_trace_grid's.
 static EyeLaunch eye_launch(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, const EyeKnobs &kn, bool capture) {
     const DeviceScene &d = s->dev;
-    const bool dof = cam->lens_radius > 0, glass = d.has_glass != 0 && grid->max_depth > 1;
-    const bool spill = d.n_objs > d.n_lds;  // more top-level objects than the LDS list holds (kLdsObjsMax)
+    // which kernel: eye_choice (cgrt_variants.h), in plain C++ so that tests/native/posed_plan.cpp can walk it
+    const EyeSceneTraits traits{d.all_spheres != 0, d.has_mesh != 0, d.has_bezier != 0, d.has_glass != 0, d.single_ray != 0, s->order.ok, d.n_objs, d.n_lds};
+    const EyeChoice c = eye_choice(traits, *cam, *grid, kn.force_reorder, capture);
     EyeLaunch L;
+    L.form = c.form;
+    L.k = c.k;
     L.dev = d;
-    if (capture || (spill && !d.all_spheres)) {
-        // the most general variant serves every scene, with as many objects resident as fit beside its other LDS; the
-        // capture is a verification / hand-off path, not the hot path
-        L.form = capture ? EyeForm::Capture : EyeForm::SpillGen;
-        L.dev = with_resident(d, general_resident(s, dof, capture));
-        L.k = general_flags(dof, capture, L.dev.n_objs > L.dev.n_lds);
-    } else if (spill) {
-        L.form = EyeForm::SpillSph;
-        L.k = spill_sph_flags(dof, glass);
-    } else {
-        const bool bez = d.has_bezier != 0, trees = d.has_mesh != 0 || bez;
-        L.k = image_flags(trees, bez, dof, glass, !trees && d.all_spheres != 0,
-                          (grid->flags & CGRT_GRID_STATS) != 0 && d.has_mesh != 0 && !bez);
-        // Scenes of spheres and plain planes are left in image order: without a tree or a Newton solve behind a ray, a tile's
-        // cost varies only with the size of its ray trees (<= 31 rays per sample), the per-lane sample loop already keeps 97 %
-        // of the lanes busy, and measured on C2 the unit queue costs 13 % more VALU instructions (at 93 % VALU busy) and 0.9 GB
-        // of deferred values per frame for a gain within the noise (4.0-4.2 ms either way); a room of five planes, 4096x4096
-        // spp 4: 2.2 ms scheduled (probe and plan for nothing), 1.0 ms in image order.
-        // The same holds when every ray tree is a single ray (diffuse planes, bump-mapped or not, and diffuse spheres): a room
-        // with the stone floor, 8192 x 512 rows at spp 16: floor band 7.7 ms scheduled (every tile of a uniform frame counts as
-        // heavy), 5.4 ms in image order; wall band 4.0 and 1.7 ms.
-        const bool plain_scene = (d.has_mesh == 0 && d.has_bezier == 0) || d.single_ray != 0;  // has_mesh: any tree, a bump floor's included
-        const size_t n_wt = (size_t)((grid->width + kWaveTileW - 1) / kWaveTileW) * ((grid->rows + kWaveTileH - 1) / kWaveTileH);
-        const bool reorder = grid->spp >= 4 && !(grid->flags & CGRT_GRID_NO_REORDER) && n_wt > 1 && n_wt < (1u << 30) &&
-                             (!plain_scene || (grid->flags & CGRT_GRID_FORCE_REORDER) || kn.force_reorder);
-        L.form = reorder ? EyeForm::Sched : EyeForm::Image;
-        // The image-order launch of a glass sphere scene the tile order serves (order_ok): its last waves, over the glass sphere,
-        // each alone on a SIMD, are bound by the sphere loop's dependent chain -- two spheres a trip
-        L.k.pair = L.form == EyeForm::Image && L.k.sph && L.k.glass && !L.k.stats && s->order.ok && !(grid->flags & CGRT_GRID_NO_SPHERE_PAIRS);
+    if (L.form == EyeForm::Capture || L.form == EyeForm::SpillGen) {
+        // the most general variant keeps as many objects resident as fit beside its other LDS, and spills only the rest
+        L.dev = with_resident(d, general_resident(s, L.k.dof, capture, L.k.pose));
+        L.k.spill = L.dev.n_objs > L.dev.n_lds;
     }
     // Inside trips (cgrt_inside_sphere.h): the PAIR kernels get the scene's candidates whose guarded loop pays -- none under
     // CGRT_GRID_NO_INSIDE_TRIPS or the knob CGRT_INSIDE_TRIPS=off, which is the pair loop alone in the same kernel
@@ -813,6 +810,7 @@ static int check_grid_rows(const cgrt_camera *cam, const cgrt_grid *g, bool trac
         return fail(CGRT_ERR_INVALID, "bad row_offset");
     }
     if (!(cam->lens_radius >= 0)) return fail(CGRT_ERR_INVALID, "lens_radius must be >= 0");
+    if (const char *bad = pose_error(cam, g)) return fail(CGRT_ERR_INVALID, bad);  // CGRT_GRID_POSED: cam is a cgrt_posed_camera's base
     return CGRT_OK;
 }
 static int check_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *g) {
@@ -850,6 +848,8 @@ static FrameInputs frame_inputs(const cgrt_scene *s, const cgrt_camera *cam, con
     in.n_objs = d.n_objs;
     in.n_lds = d.n_lds;
     in.all_special = order_all_special(s->order.spheres, *cam);
+    in.posed = L.k.pose;
+    if (in.posed) in.posed_cam = *reinterpret_cast<const cgrt_posed_camera *>(cam);
     return in;
 }
 
@@ -995,9 +995,10 @@ int cgrt_trace_grid_variant(const cgrt_scene *s, const cgrt_camera *cam, const c
     const EyeLaunch L = eye_launch(s, cam, grid, eye_knobs(), (grid->flags & CGRT_GRID_HITPOINTS) != 0);
     const EyeFlags &k = L.k;
     const bool sched = L.form == EyeForm::Sched;
-    std::snprintf(name, cap, "trace_grid_%skernel<TREES=%d,BEZ=%d,DOF=%d,GLASS=%d,SPH=%d,STATS=%d,%s%sNT=%d%s>", sched ? "sched_" : "",
+    if (!eye_kernels(k)) return fail(CGRT_ERR_UNSUPPORTED, std::string(L.what()) + ": no kernel built for this variant");
+    std::snprintf(name, cap, "trace_grid_%skernel<TREES=%d,BEZ=%d,DOF=%d,GLASS=%d,SPH=%d,STATS=%d,%s%sNT=%d%s%s>", sched ? "sched_" : "",
                   (int)k.trees, (int)k.bez, (int)k.dof, (int)k.glass, (int)k.sph, (int)k.stats,
-                  sched ? "" : (k.hps ? "HPS=1," : "HPS=0,"), k.pair ? "PAIR=1," : "", k.nt, k.spill ? ",SPILL=1" : "");
+                  sched ? "" : (k.hps ? "HPS=1," : "HPS=0,"), k.pair ? "PAIR=1," : "", k.nt, k.spill ? ",SPILL=1" : "", k.pose ? ",POSE=1" : "");
     return CGRT_OK;
 }
 
@@ -1012,6 +1013,7 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     ON_DEVICE(s->device);
     const EyeKnobs kn = eye_knobs();
     const EyeLaunch L0 = eye_launch(s, cam, grid, kn, false);
+    if (L0.k.pose && (rc = check_eye(L0, s->device))) return rc;  // (not every form has a POSE kernel: refused before anything is launched)
     const FrameInputs in = frame_inputs(s, cam, grid, L0, kn);
     FramePlan p;
     if ((rc = fit_scratch(s, in, p))) return rc;
@@ -1047,7 +1049,8 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
         g.timeline = timeline.as<unsigned long long>();
     }
     if (p.heavy_blocks > 0) {  // (3) heavy workgroups in front, the tile workgroups behind them, one launch
-        hipLaunchKernelGGL(pixel_const_kernel, dim3((unsigned)p.kmax), dim3(64), 0, st, g);
+        if (L.k.pose) hipLaunchKernelGGL(pixel_const_kernel<true>, dim3((unsigned)p.kmax), dim3(64), 0, st, g);
+        else hipLaunchKernelGGL(pixel_const_kernel<false>, dim3((unsigned)p.kmax), dim3(64), 0, st, g);
         if (g.prim_len && (rc = primary_walk(s, L, g, st, cnt))) return rc;
         if ((rc = launch_eye(L, true, s->device, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) return rc;
     } else if (p.order.class3 == TileOrderPlan::SecondLaunch) {

@@ -445,12 +445,41 @@ __host__ __device__ __forceinline__ CameraRay camera_ray(const GridParams &g, in
     c.o[2] = g.cam[2];
     c.d[0] = c.d[1] = c.d[2] = 0.0;
     c.key = 0;
-    if (h >= g.H) return c;  // a row beyond the image (stripe padding): dir = 0, not to be traced
+    if (h >= g.H) {  // a row beyond the image (stripe padding): dir = 0, not to be traced; the origin is the eye
+        if (g.posed) pose_point(g, g.cam[0], g.cam[1], g.cam[2], c.o[0], c.o[1], c.o[2]);
+        return c;
+    }
     const double px = (2.0 * ((double)w / g.W) - 1) * g.half_width;
     const double py = (2.0 * ((double)h / g.H) - 1) * g.half_width * g.H / g.W;
     double dx = px - g.cam[0], dy = py - g.cam[1], dz = 0 - g.cam[2];
     camera_normalize(dx, dy, dz);
     c.key = sample_key(pixel_key(g.seed, (uint64_t)h * (uint64_t)g.W + (uint64_t)w), (uint64_t)smp);
+    if (g.posed) {
+        // A posed camera (pose_point, cgrt_frame.h, where the definition stands): the same points of the camera's frame, the ray
+        // made of their images -- what set_pixel / start_sample of the POSE kernels do, expression for expression.
+        double ex, ey, ez, tx, ty, tz;  // the ray's origin and the point it aims at, in the world
+        if (g.lens_radius > 0) {
+            const double pf = (g.focus_plane - g.cam[2]) / dz;
+            pose_point(g, dx * pf + g.cam[0], dy * pf + g.cam[1], dz * pf + g.cam[2], tx, ty, tz);
+            double sx, sy;
+            lens_disc(c.key, sx, sy);
+            pose_point(g, g.cam[0] + sx * g.lens_radius, g.cam[1] + sy * g.lens_radius, g.cam[2] + 0 * g.lens_radius, ex, ey, ez);
+        } else {
+            pose_point(g, px, py, 0, tx, ty, tz);
+            pose_point(g, g.cam[0], g.cam[1], g.cam[2], ex, ey, ez);
+        }
+        c.o[0] = ex;
+        c.o[1] = ey;
+        c.o[2] = ez;
+        dx = tx - ex;
+        dy = ty - ey;
+        dz = tz - ez;
+        camera_normalize(dx, dy, dz);
+        c.d[0] = dx;
+        c.d[1] = dy;
+        c.d[2] = dz;
+        return c;
+    }
     if (g.lens_radius > 0) {
         const double pf = (g.focus_plane - g.cam[2]) / dz;  // pof = pdir * pf + camorg
         const double fx = dx * pf + g.cam[0], fy = dy * pf + g.cam[1], fz = dz * pf + g.cam[2];

@@ -30,9 +30,10 @@ struct EyeFlags {
     bool pair = false;  // the sphere loop two spheres a trip, class-3 tiles by the diffuse body in the same launch (glass sphere scenes)
     bool start = false;  // a PAIR variant's twin that reads the relay's start table and serves as its cost probe (cgrt_relay.h)
     bool ltab = false;  // a thin-lens PAIR variant's twin whose full and parking bodies read the lens table (cgrt_lens_stage.h)
+    bool pose = false;  // the kernels of a posed launch (CGRT_GRID_POSED): primary rays from the camera's frame in the world
     constexpr int id() const {
         return (int)trees | (int)bez << 1 | (int)dof << 2 | (int)glass << 3 | (int)sph << 4 | (int)stats << 5 | (int)hps << 6 |
-               (int)spill << 7 | (int)hfonly << 8 | (nt == 64 ? 1 << 9 : 0) | (int)diff << 10 | (int)pair << 11 | (int)start << 12 | (int)ltab << 13;
+               (int)spill << 7 | (int)hfonly << 8 | (nt == 64 ? 1 << 9 : 0) | (int)diff << 10 | (int)pair << 11 | (int)start << 12 | (int)ltab << 13 | (int)pose << 14;
     }
 };
 // image order, the probe and the scheduled form: Bezier scenes share the tree-capable variants (one-wave workgroups)
@@ -79,6 +80,87 @@ static constexpr EyeFlags diffuse_flags(bool dof) { return {false, false, dof, f
     X(0, 0, 0, 1, 1, 0, 0, 256, 0, 0, 0, 1, 1, 0, 0) X(0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 1, 1, 0, 0)                               \
     /* ... and the thin-lens ones' twins, plain and START, for a launch with a lens table: the bodies that read it */                \
     X(0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 1, 0, 1, 0) X(0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 1, 1, 1, 0)
+
+// The instantiations with POSE that are launched (a list of its own: the one above is walked column by column by tools and
+// tests), the same columns: the forms a posed launch can take -- image order for every scene class, the scheduled form for scenes
+// with a tree or a Bezier object (sphere and plain scenes are never scheduled under a pose), SPILL and the Hitpoint capture.  No
+// STATS, DIFF, PAIR, START, LTAB or HFONLY form: a posed launch has no tile order and no light split (cgrt_frame.h).  The
+// spheres' SPILL form comes with GLASS only (eye_launch asks for it whatever the scene).
+//    TREES BEZ DOF GLASS SPH STATS HPS NT SPILL HFONLY DIFF PAIR START LTAB | SCHED
+#define CGRT_EYE_POSED_VARIANTS(X)                                                                                                  \
+    /* image order and the scheduled form: Bezier (one wave), trees, spheres, plain scenes */                                       \
+    X(1, 1, 0, 0, 0, 0, 0, 64, 0, 0, 0, 0, 0, 0, 1) X(1, 1, 0, 1, 0, 0, 0, 64, 0, 0, 0, 0, 0, 0, 1)                                 \
+    X(1, 1, 1, 0, 0, 0, 0, 64, 0, 0, 0, 0, 0, 0, 1) X(1, 1, 1, 1, 0, 0, 0, 64, 0, 0, 0, 0, 0, 0, 1)                                 \
+    X(1, 0, 0, 0, 0, 0, 0, 256, 0, 0, 0, 0, 0, 0, 1) X(1, 0, 0, 1, 0, 0, 0, 256, 0, 0, 0, 0, 0, 0, 1)                               \
+    X(1, 0, 1, 0, 0, 0, 0, 256, 0, 0, 0, 0, 0, 0, 1) X(1, 0, 1, 1, 0, 0, 0, 256, 0, 0, 0, 0, 0, 0, 1)                               \
+    X(0, 0, 0, 0, 1, 0, 0, 256, 0, 0, 0, 0, 0, 0, 0) X(0, 0, 0, 1, 1, 0, 0, 256, 0, 0, 0, 0, 0, 0, 0)                               \
+    X(0, 0, 1, 0, 1, 0, 0, 256, 0, 0, 0, 0, 0, 0, 0) X(0, 0, 1, 1, 1, 0, 0, 256, 0, 0, 0, 0, 0, 0, 0)                               \
+    X(0, 0, 0, 0, 0, 0, 0, 256, 0, 0, 0, 0, 0, 0, 0) X(0, 0, 0, 1, 0, 0, 0, 256, 0, 0, 0, 0, 0, 0, 0)                               \
+    X(0, 0, 1, 0, 0, 0, 0, 256, 0, 0, 0, 0, 0, 0, 0) X(0, 0, 1, 1, 0, 0, 0, 256, 0, 0, 0, 0, 0, 0, 0)                               \
+    /* SPILL: spheres (GLASS), and the general body; the Hitpoint capture (general, HPS) with and without SPILL */                  \
+    X(0, 0, 0, 1, 1, 0, 0, 256, 1, 0, 0, 0, 0, 0, 0) X(0, 0, 1, 1, 1, 0, 0, 256, 1, 0, 0, 0, 0, 0, 0)                               \
+    X(1, 1, 0, 1, 0, 0, 0, 256, 1, 0, 0, 0, 0, 0, 0) X(1, 1, 1, 1, 0, 0, 0, 256, 1, 0, 0, 0, 0, 0, 0)                               \
+    X(1, 1, 0, 1, 0, 0, 1, 256, 0, 0, 0, 0, 0, 0, 0) X(1, 1, 1, 1, 0, 0, 1, 256, 0, 0, 0, 0, 0, 0, 0)                               \
+    X(1, 1, 0, 1, 0, 0, 1, 256, 1, 0, 0, 0, 0, 0, 0) X(1, 1, 1, 1, 0, 0, 1, 256, 1, 0, 0, 0, 0, 0, 0)
+// a variant's posed form
+static constexpr EyeFlags posed_flags(EyeFlags f) {
+    f.pose = true;
+    return f;
+}
+
+// ---- the eye pass's choice of kernel ----
+enum class EyeForm { Image, Sched, SpillSph, SpillGen, Capture, Light, LightHF, Diffuse };
+// What the choice reads of a committed scene (DeviceScene's traits and the handle's order_ok), and the choice
+struct EyeSceneTraits {
+    bool all_spheres, has_mesh, has_bezier, has_glass, single_ray, order_ok;
+    int n_objs, n_lds;
+};
+struct EyeChoice {
+    EyeForm form;
+    EyeFlags k;
+};
+// The form and the template flags of the eye pass's main launch for (scene, camera, grid): the Hitpoint capture (capture), else
+// cgrt_trace_grid's.  The general forms (Capture, SpillGen) come back with k.spill set; eye_launch (cgrt_hip.hip) clears it where
+// the scene's objects all stay resident.  force_reorder: the knob CGRT_FORCE_REORDER.
+// A posed launch (CGRT_GRID_POSED) takes the same form with the POSE kernels of CGRT_EYE_POSED_VARIANTS, except: sphere and plain
+// scenes stay in image order whatever the flags ask, without the pair loop (there is no tile order for it to serve), and the
+// spheres' SPILL form is compiled with GLASS only.  No STATS kernel has POSE: such a launch is refused as unsupported.
+static inline EyeChoice eye_choice(const EyeSceneTraits &d, const cgrt_camera &cam, const cgrt_grid &grid, bool force_reorder, bool capture) {
+    const bool dof = cam.lens_radius > 0, glass = d.has_glass && grid.max_depth > 1;
+    const bool spill = d.n_objs > d.n_lds;  // more top-level objects than the LDS list holds (kLdsObjsMax)
+    const bool posed = (grid.flags & CGRT_GRID_POSED) != 0;
+    EyeChoice c{};
+    if (capture || (spill && !d.all_spheres)) {
+        // the most general variant serves every scene, with as many objects resident as fit beside its other LDS; the
+        // capture is a verification / hand-off path, not the hot path
+        c.form = capture ? EyeForm::Capture : EyeForm::SpillGen;
+        c.k = general_flags(dof, capture, true);
+    } else if (spill) {
+        c.form = EyeForm::SpillSph;
+        c.k = spill_sph_flags(dof, glass || posed);
+    } else {
+        const bool bez = d.has_bezier, trees = d.has_mesh || bez;
+        c.k = image_flags(trees, bez, dof, glass, !trees && d.all_spheres, (grid.flags & CGRT_GRID_STATS) != 0 && d.has_mesh && !bez);
+        // Scenes of spheres and plain planes are left in image order: without a tree or a Newton solve behind a ray, a tile's
+        // cost varies only with the size of its ray trees (<= 31 rays per sample), the per-lane sample loop already keeps 97 %
+        // of the lanes busy, and measured on C2 the unit queue costs 13 % more VALU instructions (at 93 % VALU busy) and 0.9 GB
+        // of deferred values per frame for a gain within the noise (4.0-4.2 ms either way); a room of five planes, 4096x4096
+        // spp 4: 2.2 ms scheduled (probe and plan for nothing), 1.0 ms in image order.
+        // The same holds when every ray tree is a single ray (diffuse planes, bump-mapped or not, and diffuse spheres): a room
+        // with the stone floor, 8192 x 512 rows at spp 16: floor band 7.7 ms scheduled (every tile of a uniform frame counts as
+        // heavy), 5.4 ms in image order; wall band 4.0 and 1.7 ms.
+        const bool plain_scene = (!d.has_mesh && !d.has_bezier) || d.single_ray;  // has_mesh: any tree, a bump floor's included
+        const size_t n_wt = (size_t)((grid.width + kWaveTileW - 1) / kWaveTileW) * ((grid.rows + kWaveTileH - 1) / kWaveTileH);
+        const bool reorder = grid.spp >= 4 && !(grid.flags & CGRT_GRID_NO_REORDER) && n_wt > 1 && n_wt < (1u << 30) &&
+                             (!plain_scene || (!posed && ((grid.flags & CGRT_GRID_FORCE_REORDER) || force_reorder)));
+        c.form = reorder ? EyeForm::Sched : EyeForm::Image;
+        // The image-order launch of a glass sphere scene the tile order serves (order_ok): its last waves, over the glass sphere,
+        // each alone on a SIMD, are bound by the sphere loop's dependent chain -- two spheres a trip
+        c.k.pair = c.form == EyeForm::Image && c.k.sph && c.k.glass && !c.k.stats && d.order_ok && !(grid.flags & CGRT_GRID_NO_SPHERE_PAIRS) && !posed;
+    }
+    c.k.pose = posed;
+    return c;
+}
 
 // ---- the ray-list kernels (cgrt_rays.hpp, cgrt_occlusion.hpp, cgrt_bounce.hpp) ----
 // The template flags of a trace_rays_kernel instantiation

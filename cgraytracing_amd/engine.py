@@ -19,6 +19,18 @@ def _d3(v):
     return (C.c_double * 3)(*[float(x) for x in v])
 
 
+def _ccamera(camera):
+    """(the cgrt_camera a call is given, the grid flag that goes with it): a Camera with a pose becomes a cgrt_posed_camera
+    and the call gets its `base` -- a view into the same memory, which keeps the whole struct alive -- with CGRT_GRID_POSED."""
+    camera = camera or Camera()
+    base = _CCamera(_d3(camera.cam), camera.half_width, camera.focus_plane, camera.lens_radius)
+    if getattr(camera, "pose", None) is None:
+        return base, 0
+    origin, right, up, forward = camera.pose
+    pc = _capi.PosedCamera(base, _d3(origin), _d3(right), _d3(up), _d3(forward))
+    return pc.base, _capi.GRID_POSED
+
+
 _RELAY_ORDERS = ("chunks_first", "mirror_first", "interleaved")  # CGRT_GRID_RELAY_CHUNKS_FIRST / _MIRROR_FIRST / _INTERLEAVED
 _RELAY_STARTS = ("list", "cost")  # CGRT_GRID_NO_RELAY_COST_START / CGRT_GRID_RELAY_COST_START
 
@@ -221,11 +233,10 @@ class Scene:
     # ---- the hot path ----
     def _structs(self, camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                  spp_total, flags):
-        camera = camera or Camera()
-        cc = _CCamera(_d3(camera.cam), camera.half_width, camera.focus_plane, camera.lens_radius)
+        cc, posed = _ccamera(camera)
         s_rows, s_rank, s_n = stripe if stripe else (0, 0, 1)
         g = _CGrid(width, height, rows, row_offset, s_rows, s_rank, s_n, spp, sample_offset,
-                   spp_total if spp_total else spp, max_depth, flags, seed)
+                   spp_total if spp_total else spp, max_depth, flags | posed, seed)
         return cc, g
 
     def trace_grid(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
@@ -1501,10 +1512,9 @@ def camera_rays_host(width, height, spp=1, camera=None, seed=12345, rows=None, r
     Returns (org [n,3] float64, dirs [n,3] float64, keys [n] uint64) numpy arrays, n = spp * rows * width, ray index =
     (k * rows + local row) * width + w; the same bits Scene.camera_rays makes on the device."""
     rows = height - row_offset if rows is None else rows
-    camera = camera or Camera()
-    cc = _CCamera(_d3(camera.cam), camera.half_width, camera.focus_plane, camera.lens_radius)
+    cc, posed = _ccamera(camera)
     s_rows, s_rank, s_n = stripe if stripe else (0, 0, 1)
-    g = _CGrid(width, height, rows, row_offset, s_rows, s_rank, s_n, spp, sample_offset, spp, 1, 0, seed)
+    g = _CGrid(width, height, rows, row_offset, s_rows, s_rank, s_n, spp, sample_offset, spp, 1, posed, seed)
     n = spp * rows * width
     org = np.zeros((n, 3), np.float64)
     dirs = np.zeros((n, 3), np.float64)

@@ -126,10 +126,34 @@ class Bezier(Object):
 
 class Camera:
     """Camera constants of render() (main.cpp:178-181,188-206).  lens_radius == 0 selects the
-    pinhole call (main.cpp:209), > 0 the thin-lens call (main.cpp:207)."""
+    pinhole call (main.cpp:209), > 0 the thin-lens call (main.cpp:207).
+    pose: None -- the built-in frame (image plane z = 0, view along +z) --, or (origin, right, up, forward): where the
+    camera's own frame stands in the world (cgrt_posed_camera; orthonormal axes, checked by the library).  Every method
+    that takes a Camera passes the pose on and sets CGRT_GRID_POSED itself."""
 
-    def __init__(self, cam=(0.0, 0.0, -10.0), half_width=10.0, focus_plane=20.0, lens_radius=0.0):
+    def __init__(self, cam=(0.0, 0.0, -10.0), half_width=10.0, focus_plane=20.0, lens_radius=0.0, pose=None):
         self.cam = _v3(cam)
         self.half_width = float(half_width)
         self.focus_plane = float(focus_plane)
         self.lens_radius = float(lens_radius)
+        if pose is not None:
+            pose = tuple(tuple(float(x) for x in v) for v in pose)
+            if len(pose) != 4 or any(len(v) != 3 for v in pose):
+                raise ValueError("Camera: pose is (origin, right, up, forward), four 3-vectors")
+        self.pose = pose
+
+    @classmethod
+    def look_at(cls, eye, target, up=(0.0, 1.0, 0.0), fov_x_deg=90.0, focus_distance=None, lens_radius=0.0):
+        """cgrt_look_at: the camera at `eye` whose image centre looks at `target`, row 0 at the bottom, horizontal field of
+        view fov_x_deg; the plane of sharp focus lies focus_distance from the eye (default: through the target)."""
+        import ctypes as C
+
+        from . import _capi
+
+        e, t, u = ((C.c_double * 3)(*[float(x) for x in v]) for v in (eye, target, up))
+        if focus_distance is None:
+            focus_distance = sum((float(a) - float(b)) ** 2 for a, b in zip(target, eye)) ** 0.5
+        pc = _capi.PosedCamera()
+        _capi.check(_capi.lib().cgrt_look_at(e, t, u, float(fov_x_deg), float(focus_distance), float(lens_radius), C.byref(pc)))
+        return cls(tuple(pc.base.cam), pc.base.half_width, pc.base.focus_plane, pc.base.lens_radius,
+                   pose=(tuple(pc.origin), tuple(pc.right), tuple(pc.up), tuple(pc.forward)))

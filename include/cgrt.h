@@ -47,7 +47,9 @@ extern "C" {
                             cgrt_wavefront_rays_variant, cgrt_scene_last_wavefront, cgrt_scene_last_wavefront_rays
                             (wavefront trace); cgrt_hitpoints, cgrt_ppm_session_create_hitpoints (photon mapping of
                             caller-supplied Hitpoints); the cgrt_sppm_session_ calls, cgrt_sppm_update_host, cgrt_sppm_check_host
-                            (stochastic progressive photon mapping) */
+                            (stochastic progressive photon mapping); cgrt_posed_camera, CGRT_GRID_POSED, cgrt_look_at
+                            (posed camera: a library without them has no cgrt_look_at symbol, and CGRT_GRID_POSED was an
+                            unknown bit that it ignored) */
 
 enum {
     CGRT_OK = 0,
@@ -68,6 +70,36 @@ typedef struct cgrt_camera {
     double lens_radius; /* main.cpp:179: 1.5.  0 selects the pinhole call main.cpp:209, >0 the thin-lens
                            call main.cpp:207 with neworg = cam + disc(radius) (sampling.h:35-43)         */
 } cgrt_camera;
+
+/* A camera with a position and an orientation: `base` is the camera IN ITS OWN FRAME, exactly as above (image plane z = 0 of
+ * that frame, view along its +z), and the frame is placed in the world: a point p of the frame lies at
+ *     M(p) = ((origin + right * p.x) + up * p.y) + forward * p.z          (per component, in this order, no contraction).
+ * A pinhole ray starts at M(cam) towards M(pixel); a thin-lens ray starts at M(lens point) towards M(focus point): the
+ * direction is normalised from WORLD points, so it is unit to the standard of the built-in camera's whatever the last bits of
+ * the basis are.  Keys, lens draws and sample order are the built-in camera's.  For the identity frame (origin 0, unit axes)
+ * every M(p) is p and the rays are the built-in camera's, bit for bit.
+ * WITH CGRT_GRID_POSED IN grid->flags, THE `cam` ARGUMENT OF EVERY ENTRY THAT TAKES (cam, grid) POINTS AT THE `base` OF A
+ * cgrt_posed_camera (the sockaddr idiom): cgrt_trace_grid and its _host and _variant forms, cgrt_trace_grid_hitpoints,
+ * cgrt_camera_rays and cgrt_camera_rays_host, cgrt_ppm_render, cgrt_ppm_session_create, cgrt_sppm_session_pass_grid.
+ * WITHOUT THE FLAG NOTHING CHANGES AND NO BYTE BEYOND THE 48 OF cgrt_camera IS READ.
+ * The 12 numbers must be finite, every axis of length 1 within 1e-9 and every pair of axes orthogonal within 1e-9 (dot
+ * product), else CGRT_ERR_INVALID.  No handedness is demanded: a mirrored basis (right x up = -forward) mirrors the image. */
+typedef struct cgrt_posed_camera {
+    cgrt_camera base;  /* the camera in ITS OWN frame, exactly as cgrt_camera                                  */
+    double origin[3];  /* world position of the camera frame's (0,0,0)                                         */
+    double right[3], up[3], forward[3]; /* world directions of the frame's +x, +y, +z: orthonormal               */
+} cgrt_posed_camera;   /* 144 bytes */
+
+/* Host only, plain fp64: fills `out` so that the eye lies at `eye`, the centre of the image looks at `target`, the
+ * horizontal field of view is fov_x_deg, the plane of sharp focus lies focus_distance from the eye along `forward` and row 0
+ * is the bottom row:  forward = normalize(target - eye), right = normalize(up_hint x forward), up = forward x right,
+ * and with D = |target - eye|: origin = target (the image plane passes through the target), base = {cam (0,0,-D), half_width
+ * D tan(fov_x/2), focus_plane focus_distance - D, lens_radius}.  With eye (0,0,-10), target (0,0,0), up_hint (0,1,0) and 90
+ * degrees this is the built-in camera's frame (origin 0, the unit axes) and its eye.  The eye maps to M(base.cam) = target -
+ * forward * D, which is `eye` up to the rounding of that expression.  CGRT_ERR_INVALID: eye == target, up_hint parallel to the view or zero,
+ * fov_x_deg outside (0, 180), focus_distance not > 0, lens_radius negative, anything not finite. */
+int cgrt_look_at(const double eye[3], const double target[3], const double up_hint[3], double fov_x_deg, double focus_distance,
+                 double lens_radius, cgrt_posed_camera *out);
 
 /* Which part of the W x H x spp grid one call renders.  Compile-time constants of the reference
  * (width,height main.cpp:28-29; MAX_DEPTH :35; num_of_samples :177) become fields here. */
@@ -216,6 +248,21 @@ enum {
                                  (cgrt_scene_inside_spheres) -- instead of all of them two at a time.  This flag, or the knob
                                  CGRT_INSIDE_TRIPS=off, restores the pair loop in the same kernel.  Same image, hit counts and
                                  counters either way, CGRT_CNT_WAVE_ITERS included                                       */
+    CGRT_GRID_POSED = 67108864, /* 1 << 26: `cam` points at the `base` of a cgrt_posed_camera (see there), whose frame the primary
+                                 rays start from.  A posed launch runs kernels of its own (",POSE=1" in cgrt_trace_grid_variant's
+                                 name) in the image-order form CGRT_GRID_NO_TILE_ORDER gives, or cost-scheduled where the scene
+                                 has a mesh, a bump floor or a Bezier object (the probe traces real rays).  What reasons about
+                                 rays in the built-in frame is NOT USED by a posed launch in this version: the tile order of
+                                 sphere scenes, sphere masks, sure tiles, the in-launch diffuse body and the pair loop
+                                 (CGRT_GRID_DIFFUSE_TILES, _NO_SPHERE_PAIRS), the sample relay with its cost start and boost,
+                                 the lens stage and the lens table; nor the light-tile split and the primary walk of scheduled
+                                 launches (every tile is rendered by the full variant, no walk ahead), nor CGRT_GRID_FORCE_REORDER.
+                                 Flags that ask for these are IGNORED, not refused -- each is "the same image either way" by
+                                 its own contract --, the cgrt_scene_last_* readers report that nothing was taken, and the
+                                 handle's cached tile order, cost probe and lens table, keyed by the built-in camera's six
+                                 numbers, are neither reused nor overwritten.  CGRT_GRID_SPLIT_SAMPLES is supported with a
+                                 pose (the same chunks, the same sums); CGRT_GRID_STATS on a mesh scene has no posed kernel:
+                                 CGRT_ERR_UNSUPPORTED                                                                     */
     CGRT_GRID_HITPOINTS = 32, /* cgrt_trace_grid_variant only: name the launch of the Hitpoint capture
                                  (cgrt_trace_grid_hitpoints, the eye pass of cgrt_ppm_render) instead of cgrt_trace_grid's;
                                  ignored by the other calls                                                            */

@@ -288,6 +288,53 @@ struct RenderParams {
     bool depth_of_field = false;          // false: the committed pinhole call (main.cpp:209); true: main.cpp:207
     uint64_t seed = 12345;
     int device = 0;
+    double half_width = 10.0;             // the literal 10.0 of main.cpp:188-189
+    // The posed camera (cgrt_posed_camera): camorg, half_width, focus_plane and radius describe the camera in its own frame;
+    // set_pose / look_at place that frame in the world.  Unset, the frame is the built-in one and nothing changes.
+    bool posed = false;
+    double pose_origin[3] = {0, 0, 0}, pose_right[3] = {1, 0, 0}, pose_up[3] = {0, 1, 0}, pose_forward[3] = {0, 0, 1};
+    void set_pose(const Vec3 &origin, const Vec3 &right, const Vec3 &up, const Vec3 &forward) {
+        origin.get(pose_origin);
+        right.get(pose_right);
+        up.get(pose_up);
+        forward.get(pose_forward);
+        posed = true;
+    }
+    // cgrt_look_at: the eye at `eye`, the image centre on `target`, horizontal field of view fov_x_deg, sharp at
+    // focus_distance from the eye (the lens stays `radius`, used when depth_of_field is set)
+    void look_at(const Vec3 &eye, const Vec3 &target, const Vec3 &up_hint, double fov_x_deg, double focus_distance) {
+        double e[3], t[3], u[3];
+        eye.get(e);
+        target.get(t);
+        up_hint.get(u);
+        cgrt_posed_camera pc;
+        check(cgrt_look_at(e, t, u, fov_x_deg, focus_distance, radius, &pc));
+        camorg = Vec3(pc.base.cam[0], pc.base.cam[1], pc.base.cam[2]);
+        half_width = pc.base.half_width;
+        focus_plane = pc.base.focus_plane;
+        for (int k = 0; k < 3; k++) {
+            pose_origin[k] = pc.origin[k];
+            pose_right[k] = pc.right[k];
+            pose_up[k] = pc.up[k];
+            pose_forward[k] = pc.forward[k];
+        }
+        posed = true;
+    }
+    // The camera of a call over grid g: pc filled from these fields, CGRT_GRID_POSED set in g where a pose is; what to pass
+    const cgrt_camera *camera(cgrt_posed_camera &pc, cgrt_grid &g) const {
+        camorg.get(pc.base.cam);
+        pc.base.half_width = half_width;
+        pc.base.focus_plane = focus_plane;
+        pc.base.lens_radius = depth_of_field ? radius : 0.0;
+        for (int k = 0; k < 3; k++) {
+            pc.origin[k] = pose_origin[k];
+            pc.right[k] = pose_right[k];
+            pc.up[k] = pose_up[k];
+            pc.forward[k] = pose_forward[k];
+        }
+        if (posed) g.flags |= CGRT_GRID_POSED;
+        return &pc.base;
+    }
 };
 struct RenderStats {
     uint64_t rays = 0, hitpoints = 0;
@@ -301,12 +348,9 @@ inline void render(const std::vector<Object *> &objs, const RenderParams &rp, st
     SceneBuilder sb;
     for (const Object *o : objs) o->add_to(sb);
     check(cgrt_scene_commit(sb.scene, rp.device));
-    cgrt_camera cam;
-    rp.camorg.get(cam.cam);
-    cam.half_width = 10.0;
-    cam.focus_plane = rp.focus_plane;
-    cam.lens_radius = rp.depth_of_field ? rp.radius : 0.0;
     cgrt_grid g{};
+    cgrt_posed_camera pc;
+    const cgrt_camera *cam = rp.camera(pc, g);
     g.width = rp.width;
     g.height = rp.height;
     g.rows = rp.height;
@@ -317,7 +361,7 @@ inline void render(const std::vector<Object *> &objs, const RenderParams &rp, st
     g.seed = rp.seed;
     image.assign((size_t)rp.width * rp.height * 3, 0.f);
     uint64_t cnt[CGRT_NCOUNTERS] = {0};
-    check(cgrt_trace_grid_host(sb.scene, &cam, &g, image.data(), nullptr, cnt));
+    check(cgrt_trace_grid_host(sb.scene, cam, &g, image.data(), nullptr, cnt));
     if (stats) {
         stats->rays = cnt[CGRT_CNT_RAYS];
         stats->hitpoints = cnt[CGRT_CNT_HITPOINTS];
@@ -572,12 +616,9 @@ inline void render_ppm(const std::vector<Object *> &objs, const RenderParams &rp
     SceneBuilder sb;
     for (const Object *o : objs) o->add_to(sb);
     check(cgrt_scene_commit(sb.scene, rp.device));
-    cgrt_camera cam;
-    rp.camorg.get(cam.cam);
-    cam.half_width = 10.0;
-    cam.focus_plane = rp.focus_plane;
-    cam.lens_radius = rp.depth_of_field ? rp.radius : 0.0;
     cgrt_grid g{};
+    cgrt_posed_camera pc;
+    const cgrt_camera *cam = rp.camera(pc, g);
     g.width = rp.width;
     g.height = rp.height;
     g.rows = rp.height;
@@ -600,7 +641,7 @@ inline void render_ppm(const std::vector<Object *> &objs, const RenderParams &rp
     cgrt_ppm_result out{};
     out.image = image.data();
     out.rgb8 = image_data.data();
-    check(cgrt_ppm_render(sb.scene, &cam, &g, &ph, &out));
+    check(cgrt_ppm_render(sb.scene, cam, &g, &ph, &out));
     if (stats) {
         stats->hitpoints = out.hp_count;
         stats->photon_events = out.n_events;
@@ -618,12 +659,9 @@ class PpmSession {
         : width_(rp.width), height_(rp.height), session_(nullptr) {
         for (const Object *o : objs) o->add_to(sb_);
         check(cgrt_scene_commit(sb_.scene, rp.device));
-        cgrt_camera cam;
-        rp.camorg.get(cam.cam);
-        cam.half_width = 10.0;
-        cam.focus_plane = rp.focus_plane;
-        cam.lens_radius = rp.depth_of_field ? rp.radius : 0.0;
         cgrt_grid g{};
+        cgrt_posed_camera pc;
+        const cgrt_camera *cam = rp.camera(pc, g);
         g.width = rp.width;
         g.height = rp.height;
         g.rows = rp.height;
@@ -633,7 +671,7 @@ class PpmSession {
         g.max_depth = rp.max_depth;
         g.seed = rp.seed;
         const cgrt_photons ph = photons(pp);
-        check(cgrt_ppm_session_create(sb_.scene, &cam, &g, &ph, lookahead ? 0 : CGRT_PPM_SESSION_NO_LOOKAHEAD, &session_));
+        check(cgrt_ppm_session_create(sb_.scene, cam, &g, &ph, lookahead ? 0 : CGRT_PPM_SESSION_NO_LOOKAHEAD, &session_));
     }
     // The same live render over caller-supplied rays (cgrt_ppm_session_create_rays): any camera, or probe rays.  rays' arrays
     // and px.pixel are DEVICE pointers on device `device`, read before the constructor returns; px names the image that
@@ -710,10 +748,7 @@ class SppmSession {
         : width_(rp.width), height_(rp.height), session_(nullptr), grid_() {
         for (const Object *o : objs) o->add_to(sb_);
         check(cgrt_scene_commit(sb_.scene, rp.device));
-        rp.camorg.get(cam_.cam);
-        cam_.half_width = 10.0;
-        cam_.focus_plane = rp.focus_plane;
-        cam_.lens_radius = rp.depth_of_field ? rp.radius : 0.0;
+        rp.camera(cam_, grid_);
         grid_.width = rp.width;
         grid_.height = rp.height;
         grid_.rows = rp.height;
@@ -740,7 +775,7 @@ class SppmSession {
     void add_passes(int n, long long photons_per_pass) {
         for (int k = 0; k < n; k++) {
             grid_.sample_offset = (int32_t)(info().passes * grid_.spp);
-            check(cgrt_sppm_session_pass_grid(session_, &cam_, &grid_, photons_per_pass));
+            check(cgrt_sppm_session_pass_grid(session_, &cam_.base, &grid_, photons_per_pass));
         }
     }
     // one pass over caller-supplied rays (cgrt_sppm_session_pass_rays): DEVICE arrays on the scene's device; pixel may be null
@@ -770,7 +805,7 @@ class SppmSession {
     int width_, height_;
     SceneBuilder sb_;
     cgrt_sppm_session *session_;
-    cgrt_camera cam_;
+    cgrt_posed_camera cam_;  // the camera with its pose (RenderParams::camera)
     cgrt_grid grid_;
 };
 

@@ -103,11 +103,7 @@ inline void render_sharded(const std::vector<Object *> &objs, const RenderParams
             SceneBuilder sb;  // the scene is replicated: every GPU builds and uploads its own copy
             for (const Object *o : objs) o->add_to(sb);
             check(cgrt_scene_commit(sb.scene, dev));
-            cgrt_camera cam;
-            rp.camorg.get(cam.cam);
-            cam.half_width = 10.0;
-            cam.focus_plane = rp.focus_plane;
-            cam.lens_radius = rp.depth_of_field ? rp.radius : 0.0;
+            cgrt_posed_camera pc;
             cgrt_grid g{};
             g.width = W;
             g.height = H;
@@ -118,6 +114,7 @@ inline void render_sharded(const std::vector<Object *> &objs, const RenderParams
             g.spp = g.spp_total = rp.num_of_samples;
             g.max_depth = rp.max_depth;
             g.seed = rp.seed;
+            const cgrt_camera *cam = rp.camera(pc, g);  // (with its pose, where rp has one)
             struct Tmp {  // this worker's temporaries, released on its error paths too
                 uint64_t *d_cnt = nullptr;
                 hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -134,7 +131,7 @@ inline void render_sharded(const std::vector<Object *> &objs, const RenderParams
             CGRT_HIP_OK(hipEventCreate(&t.e0));
             CGRT_HIP_OK(hipEventCreate(&t.e1));
             CGRT_HIP_OK(hipEventRecord(t.e0, st));
-            check(cgrt_trace_grid(sb.scene, &cam, &g, R.d_rgb[(size_t)r], nullptr, t.d_cnt, st));
+            check(cgrt_trace_grid(sb.scene, cam, &g, R.d_rgb[(size_t)r], nullptr, t.d_cnt, st));
             CGRT_HIP_OK(hipEventRecord(t.e1, st));
             CGRT_HIP_OK(hipStreamSynchronize(st));
             float el = 0;

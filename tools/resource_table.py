@@ -5,7 +5,8 @@
 
 Runs `make -C cgraytracing_amd/csrc asm` (hipcc -S --cuda-device-only -Rpass-analysis=kernel-resource-usage, the same
 flags as the product build; cross-compiles for gfx950 without a GPU) and parses the compiler's remarks.  The template
-arguments of trace_grid_kernel are decoded from the mangled name: <TREES,BEZ,DOF,GLASS,SPH,STATS,HPS,NT,SPILL,HFONLY,DIFF,PAIR[,START[,LTAB]]>."""
+arguments of trace_grid_kernel are decoded from the mangled name: <TREES,BEZ,DOF,GLASS,SPH,STATS,HPS,NT,SPILL,HFONLY,DIFF,PAIR[,START[,LTAB]]>
+[,POSE=1]."""
 import json
 import os
 import re
@@ -16,6 +17,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def demangle_variant(name):
+    # POSE, the last template argument of the eye kernels (a posed launch's): an instantiation without it keeps the name it had
+    # before the argument existed, one with it gets ",POSE=1" appended
+    m = re.match(r"(_Z17trace_grid_kernelI(?:L?b\dE){7}Li\d+E(?:L?b\dE){6})L?b(\d)E(E.*)$", name)
+    if not m:
+        m = re.match(r"(_Z23trace_grid_sched_kernelI(?:L?b\dE){6}Li\d+E)L?b(\d)E(E.*)$", name)
+    if m:
+        base = demangle_variant(m.group(1) + m.group(3))
+        return base[:-1] + ",POSE=1>" if m.group(2) == "1" else base
+    m = re.match(r"_Z18pixel_const_kernelIL?b(\d)EE", name)
+    if m:
+        return "pixel_const_kernel<POSE=1>" if m.group(1) == "1" else "pixel_const_kernel"
     m = re.match(r"_Z17trace_grid_kernelIL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)ELi(\d+)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)EE", name)
     if m:
         t = [int(x) for x in m.groups()]
