@@ -2,13 +2,14 @@
 launches the eye pass (the loop nest of main.cpp:185-219) on the GPU."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import weakref
 
 import numpy as np
 
-from . import _capi
+from . import _buffers, _capi
 from ._capi import Camera as _CCamera
 from ._capi import Grid as _CGrid
 from ._capi import check
@@ -35,39 +36,110 @@ _RELAY_ORDERS = ("chunks_first", "mirror_first", "interleaved")  # CGRT_GRID_REL
 _RELAY_STARTS = ("list", "cost")  # CGRT_GRID_NO_RELAY_COST_START / CGRT_GRID_RELAY_COST_START
 
 
-def _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles, lens_table=None, inside_trips=True):
-    """The CGRT_GRID_* flags of trace_grid's switches, the relay's apart (_relay_flag)."""
-    on = (stats, _capi.GRID_STATS), (split_samples, _capi.GRID_SPLIT_SAMPLES), (force_reorder, _capi.GRID_FORCE_REORDER), (diffuse_tiles, _capi.GRID_DIFFUSE_TILES)
-    off = ((reorder, _capi.GRID_NO_REORDER), (tile_order, _capi.GRID_NO_TILE_ORDER), (sphere_pairs, _capi.GRID_NO_SPHERE_PAIRS),
-           (sphere_masks, _capi.GRID_NO_SPHERE_MASKS), (lens_stage, _capi.GRID_NO_LENS_STAGE), (sure_tiles, _capi.GRID_NO_SURE_TILES),
-           (inside_trips, _capi.GRID_NO_INSIDE_TRIPS))
-    table = 0 if lens_table is None else _capi.GRID_LENS_TABLE if lens_table else _capi.GRID_NO_LENS_TABLE
-    return sum(f for v, f in on if v) | sum(f for v, f in off if not v) | table
-
-
-def _relay_flag(sample_relay, relay_mirror=None, relay_order=None, relay_start=None, relay_boost=None):
-    """CGRT_GRID_SAMPLE_RELAY / _NO_SAMPLE_RELAY / _SAMPLE_RELAY_4 for trace_grid's sample_relay=None|True|False|2|4, with
-    CGRT_GRID_RELAY_MIRROR / _NO_MIRROR for relay_mirror=None|True|False, the order field for relay_order=None|a name and
-    CGRT_GRID_RELAY_COST_START / _NO_RELAY_COST_START for relay_start=None|"cost"|"list" and CGRT_GRID_RELAY_BOOST /
-    _NO_RELAY_BOOST for relay_boost=None|True|False."""
-    form = 0 if relay_mirror is None else (_capi.GRID_RELAY_MIRROR if relay_mirror else _capi.GRID_RELAY_NO_MIRROR)
+def _grid_flags(stats=False, split_samples=False, reorder=True, force_reorder=False, tile_order=True, diffuse_tiles=False, sphere_pairs=True,
+                sphere_masks=True, sample_relay=None, relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True, relay_start=None,
+                relay_boost=None, lens_table=None, inside_trips=True):
+    """The CGRT_GRID_* flags of trace_grid's scheduling switches, in the order of its signature.  The relay's: CGRT_GRID_SAMPLE_RELAY
+    / _NO_SAMPLE_RELAY / _SAMPLE_RELAY_4 for sample_relay=None|True|False|2|4, CGRT_GRID_RELAY_MIRROR / _NO_MIRROR for
+    relay_mirror=None|True|False, the order field for relay_order=None|a name, CGRT_GRID_RELAY_COST_START / _NO_RELAY_COST_START
+    for relay_start=None|"cost"|"list" and CGRT_GRID_RELAY_BOOST / _NO_RELAY_BOOST for relay_boost=None|True|False."""
+    f = ((_capi.GRID_STATS if stats else 0) | (_capi.GRID_SPLIT_SAMPLES if split_samples else 0) | (0 if reorder else _capi.GRID_NO_REORDER) |
+         (_capi.GRID_FORCE_REORDER if force_reorder else 0) | (0 if tile_order else _capi.GRID_NO_TILE_ORDER) |
+         (_capi.GRID_DIFFUSE_TILES if diffuse_tiles else 0) | (0 if sphere_pairs else _capi.GRID_NO_SPHERE_PAIRS) |
+         (0 if sphere_masks else _capi.GRID_NO_SPHERE_MASKS) | (0 if lens_stage else _capi.GRID_NO_LENS_STAGE) |
+         (0 if sure_tiles else _capi.GRID_NO_SURE_TILES) | (0 if inside_trips else _capi.GRID_NO_INSIDE_TRIPS))
+    if lens_table is not None:
+        f |= _capi.GRID_LENS_TABLE if lens_table else _capi.GRID_NO_LENS_TABLE
+    if relay_mirror is not None:
+        f |= _capi.GRID_RELAY_MIRROR if relay_mirror else _capi.GRID_RELAY_NO_MIRROR
     if relay_boost is not None:
-        form |= _capi.GRID_RELAY_BOOST if relay_boost else _capi.GRID_NO_RELAY_BOOST
+        f |= _capi.GRID_RELAY_BOOST if relay_boost else _capi.GRID_NO_RELAY_BOOST
     if relay_start is not None:
         if relay_start not in _RELAY_STARTS:
             raise ValueError("relay_start: None, " + ", ".join(repr(o) for o in _RELAY_STARTS))
-        form |= _capi.GRID_RELAY_COST_START if relay_start == "cost" else _capi.GRID_NO_RELAY_COST_START
+        f |= _capi.GRID_RELAY_COST_START if relay_start == "cost" else _capi.GRID_NO_RELAY_COST_START
     if relay_order is not None:
         if relay_order not in _RELAY_ORDERS:
             raise ValueError("relay_order: None, " + ", ".join(repr(o) for o in _RELAY_ORDERS))
-        form |= (_capi.GRID_RELAY_CHUNKS_FIRST, _capi.GRID_RELAY_MIRROR_FIRST, _capi.GRID_RELAY_INTERLEAVED)[_RELAY_ORDERS.index(relay_order)]
+        f |= (_capi.GRID_RELAY_CHUNKS_FIRST, _capi.GRID_RELAY_MIRROR_FIRST, _capi.GRID_RELAY_INTERLEAVED)[_RELAY_ORDERS.index(relay_order)]
     if sample_relay is None:
-        return form
+        return f
     if sample_relay is True or sample_relay is False:
-        return form | (_capi.GRID_SAMPLE_RELAY if sample_relay else _capi.GRID_NO_SAMPLE_RELAY)
+        return f | (_capi.GRID_SAMPLE_RELAY if sample_relay else _capi.GRID_NO_SAMPLE_RELAY)
     if int(sample_relay) not in (2, 4):
         raise ValueError("sample_relay: None, True, False, 2 or 4")
-    return form | _capi.GRID_SAMPLE_RELAY | (_capi.GRID_SAMPLE_RELAY_4 if int(sample_relay) == 4 else 0)
+    return f | _capi.GRID_SAMPLE_RELAY | (_capi.GRID_SAMPLE_RELAY_4 if int(sample_relay) == 4 else 0)
+
+
+def _photons(light, jitter, power, alpha=0.7, nphotons=0, hashsize=1000001, batch=0, photon_seed=777, initial_radius=0.0, pair_cap=0):
+    return _capi.Photons(_d3(light), jitter, power, alpha, nphotons, hashsize, batch, photon_seed, initial_radius, pair_cap)
+
+
+def _variant_name(fn, *args):
+    """The kernel instantiation's name a cgrt_*_variant entry point writes for `args`."""
+    buf = C.create_string_buffer(160)
+    check(fn(*args, buf, len(buf)))
+    return buf.value.decode()
+
+
+def _hitpoint_records(rec, count, cap):
+    """10-column Hitpoint records: (hp [m,9], label >> 4, label & 15) of the m = min(count, cap) that were written."""
+    m = min(int(count), cap)
+    lab = rec[:m, 9].astype(np.int64)
+    return rec[:m, :9].copy(), lab >> 4, lab & 15
+
+
+def _photon_event_rows(first, ev, va):
+    """A photon-event probe's answer: the valid slots' [photon, P, n, flux] rows in slot order, 8 slots a photon from `first`."""
+    idx = np.nonzero(va)[0]
+    return np.concatenate([(first + idx // 8)[:, None].astype(np.float64), ev[idx]], axis=1)
+
+
+# ---- caller-supplied rays: one table per query, from which its torch form and its numpy form are both made ----
+# spec: result -> (rows, cols, (torch, numpy) dtype, numpy fill), see _buffers; want: what `want` may name, groups: the names that
+# stand for several results; host_counts: what the numpy form adds from its counters; skip_empty: whether the (torch, numpy)
+# form returns before the library call when there are no rays; coerce: whether the numpy form makes its inputs fit or refuses.
+_Query = collections.namedtuple("_Query", "fn spec want groups host_counts skip_empty coerce empty_want inputs",
+                                defaults=({}, (), (True, False), True, False, None))
+_F64, _I32, _I64, _U8, _U32, _U64 = _buffers.F64, _buffers.I32, _buffers.I64, _buffers.U8, _buffers.U32, _buffers.U64
+_N3, _2N3 = ("n", 3, _F64, 0), ("2n", 3, _F64, 0)
+_TRACE_RAYS = _Query("cgrt_trace_rays", dict(acc=_N3, nhit=("n", None, _U32, 0), hit_obj=("n", None, _I32, 0), hit_t=("n", None, _F64, 0),
+                                             hit_normal=_N3),
+                     ("acc", "nhit", "hit"), {"hit": ("hit_obj", "hit_t", "hit_normal")}, ("nrays", "nhp"))
+_HIT_ATTRIBUTES = _Query("cgrt_ray_hit_attributes", dict(prim=("n", None, _I32, -1), uv=("n", 2, _F64, 0), color=_N3, material=("n", 2, _F64, 0)),
+                         ("prim", "uv", "color", "material"), skip_empty=(True, True), coerce=False)
+_OCCLUDED = _Query("cgrt_occlusion_rays", dict(occluded=(("n", "max(n,1)"), None, _U8, 0)), (), host_counts=("nrays",))
+_BOUNCE = _Query("cgrt_bounce_rays", dict(step=("n", None, _U8, 0), hit_obj=("n", None, _I32, -1), hit_t=("n", None, _F64, 0), pos=_N3, normal=_N3,
+                                          value=_N3, child_org=_2N3, child_dir=_2N3, child_adj=_2N3, child_path=("2n", None, _U32, 0),
+                                          child_keys=("2n", None, _U64, 0)),
+                 ("step", "hit_obj", "hit_t", "pos", "normal", "value", "child_org", "child_dir", "child_adj", "child_path", "child_keys", "hit",
+                  "children"),
+                 {"hit": ("hit_obj", "hit_t"), "children": ("child_org", "child_dir", "child_adj", "child_path", "child_keys")}, ("nrays", "nhp"),
+                 inputs=(("keys", "adj", "path"), ("adj", "path", "keys")))  # the order the (torch, numpy) form checks them in
+_WAVEFRONT = _Query("cgrt_wavefront_rays", dict(acc=_N3, nhit=("n", None, _U32, 0), hp9=("cap", 9, _F64, 0), hp_ray=("cap", None, _I64, 0),
+                                                hp_path=("cap", None, _U32, 0)),
+                    ("acc", "nhit", "hp"), {"hp": ("hp9", "hp_ray", "hp_path")}, ("nrays", "nhp"), skip_empty=(False, False), empty_want=True)
+_CAMERA_RAYS = dict(org=_N3, dirs=_N3, keys=("n", None, _U64, 0))
+_PHOTON_RAYS = dict(org=_N3, dirs=_N3, flux=_N3, keys=("n", None, _U64, 0), draws=("n", None, _U32, 0))
+_INPUT = dict(keys=(_U64, None), adj=(_F64, 3), path=(_U32, None))  # bounce's optional per-ray inputs -> (dtype, cols)
+_HOST_COUNTS = dict(nrays=_capi.CNT_RAYS, nhp=_capi.CNT_HITPOINTS)
+
+
+def _want(what, q, want):
+    """The results `want` asks of the query q, in the table's order."""
+    want = tuple(want)
+    if (not want and not q.empty_want) or any(w not in q.want for w in want):
+        raise ValueError("%s: want is a %ssubset of %r" % (what, "" if q.empty_want else "non-empty ", q.want))
+    names = [k for w in want for k in q.groups.get(w, (w,))]
+    return [k for k in q.spec if k in names]
+
+
+def _with_counters(A, q, res, cnt):
+    """The result dict with its counters, and in the numpy form what is read out of them."""
+    res["counters"] = cnt
+    if A.host:
+        res.update({k: int(cnt[_HOST_COUNTS[k]]) for k in q.host_counts})
+    return res
 
 
 def relay_boost_host(k, chunk_spp, spp, cap, mirror, plan, tile_list, wcost, width, rows, k_boost, boost_chunk_spp, boost_cap, num, den,
@@ -105,7 +177,24 @@ def relay_start_host(k, chunk_spp, spp, cap, mirror, plan, tile_list, wcost, wid
     return start[:t.value]
 
 
-class Scene:
+class _Closing:
+    """An owner of a library handle: close() also ends a `with` block and comes with collection."""
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class Scene(_Closing):
     """Owns a cgrt_scene handle.  `objs` order is the reference's `objs` order.  commit=False keeps the scene
     on the host only (mesh loading / tree build can then be inspected without a GPU)."""
 
@@ -166,19 +255,6 @@ class Scene:
         if getattr(self, "_h", None):
             self._L.cgrt_scene_destroy(self._h)
             self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
     # ---- introspection ----
     def stats(self):
@@ -293,8 +369,9 @@ class Scene:
         assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (rows, width, 3)
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total, (_capi.GRID_ACCUMULATE if accumulate else 0) |
-                              _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles, lens_table, inside_trips) |
-                              _relay_flag(sample_relay, relay_mirror, relay_order, relay_start, relay_boost))
+                              _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks,
+                                          sample_relay, relay_mirror, relay_order, lens_stage, sure_tiles, relay_start, relay_boost, lens_table,
+                                          inside_trips))
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         check(self._L.cgrt_trace_grid(self._h, C.byref(cc), C.byref(g), out.data_ptr(),
                                       nhit.data_ptr() if nhit is not None else None,
@@ -302,7 +379,34 @@ class Scene:
         return out, nhit, counters
 
     # ---- caller-supplied rays ----
-    _WANT = ("acc", "nhit", "hit")
+    def _torch(self):
+        return _buffers.Torch(self.device)
+
+    def _rays(self, A, n, org, dirs, keys, first_index, seed, max_depth, flags):
+        return _capi.Rays(n, A.ptr(org), A.ptr(dirs), A.ptr(keys), first_index, seed, max_depth, flags)
+
+    def _query(self, A, q, n, stream, *args):
+        """The library call of query q in A's form -- unless there are no rays and that form then goes without the call."""
+        if n > 0 or not q.skip_empty[A.form]:
+            check(getattr(self._L, q.fn + A.suffix)(self._h, *args, *A.stream(stream)))
+
+    def _ray_tensors(self, what, org, dirs, keys, pixel=None):
+        """The argument checks of trace_rays for the ray-buffer calls; returns n."""
+        A = self._torch()
+        n = A.rays(what, org=org, dirs=dirs)[0]
+        A.per_ray(what, "keys", keys, n, _I64)
+        A.per_ray(what, "pixel", pixel, n, _I64)
+        return n
+
+    def _unless_committed(self, call):
+        """An uncommitted scene gets the library's own answer from the empty call `call`, before any tensor is looked at."""
+        if not self.stats()["committed"]:
+            check(call())
+
+    def _open_session(self, cls, h, *args):
+        ses = cls(self, h, *args)
+        self._sessions.add(ses)
+        return ses
 
     def camera_rays(self, width, height, spp=1, camera=None, seed=12345, rows=None, row_offset=0, stripe=None,
                     sample_offset=0, stream=None):
@@ -310,19 +414,13 @@ class Scene:
         (cgrt_camera_rays), made on the device: (org [n,3] float64, dirs [n,3] float64, keys [n] int64 (bit pattern uint64))
         torch tensors, n = spp * rows * width, ray index = (k * rows + local row) * width + w.  Rows beyond `height` of a
         striped grid have dirs = 0 and are not traced by trace_rays."""
-        import torch
-
+        A = self._torch()
         rows = height - row_offset if rows is None else rows
-        dev = torch.device("cuda", self.device)
-        n = spp * rows * width
-        org = torch.empty((n, 3), dtype=torch.float64, device=dev)
-        dirs = torch.empty((n, 3), dtype=torch.float64, device=dev)
-        keys = torch.empty((n,), dtype=torch.int64, device=dev)
+        org, dirs, keys = A.results("camera_rays", _CAMERA_RAYS, _CAMERA_RAYS, None, spp * rows * width).values()
         cc, g = self._structs(camera, width, height, rows, spp, 1, seed, row_offset, stripe, sample_offset, None, 0)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            check(self._L.cgrt_camera_rays(C.byref(cc), C.byref(g), org.data_ptr(), dirs.data_ptr(), keys.data_ptr(),
-                                           C.c_void_p(st)))
+        st = A.stream(stream)
+        with A.torch.cuda.device(A.dev):
+            check(self._L.cgrt_camera_rays(C.byref(cc), C.byref(g), org.data_ptr(), dirs.data_ptr(), keys.data_ptr(), *st))
         return org, dirs, keys
 
     def trace_rays(self, org, dirs, keys=None, max_depth=5, seed=12345, first_index=0, want=("acc", "nhit", "hit"),
@@ -334,88 +432,29 @@ class Scene:
         current stream (or `stream`); counters (int64 [8]) are ADDED to.  sign_pass=False: CGRT_RAYS_NO_SIGN_PASS (an opaque
         mesh's hit_normal is then right up to its sign; saves an unpruned mesh walk per ray).  Returns a dict of the tensors
         and "counters"."""
-        import torch
+        return self._trace_rays(self._torch(), "trace_rays", org, dirs, keys, max_depth, seed, first_index, want, counters, stream, stats, out,
+                                sign_pass)
 
-        dev = torch.device("cuda", self.device)
-        for name, t in (("org", org), ("dirs", dirs)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == 3 and
-                    t.is_contiguous() and t.device == dev):
-                raise ValueError("trace_rays: %s must be a contiguous float64 [n,3] tensor on %s" % (name, dev))
-        n = org.shape[0]
-        if dirs.shape[0] != n:
-            raise ValueError("trace_rays: org and dirs differ in length")
-        if keys is not None and not (isinstance(keys, torch.Tensor) and keys.dtype == torch.int64 and tuple(keys.shape) == (n,) and
-                                     keys.is_contiguous() and keys.device == dev):
-            raise ValueError("trace_rays: keys must be a contiguous int64 [n] tensor on %s" % (dev,))
-        want = tuple(want)
-        if not want or any(w not in self._WANT for w in want):
-            raise ValueError("trace_rays: want is a non-empty subset of %r" % (self._WANT,))
-        shapes = {}
-        if "acc" in want:
-            shapes["acc"] = ((n, 3), torch.float64)
-        if "nhit" in want:
-            shapes["nhit"] = ((n,), torch.int32)
-        if "hit" in want:
-            shapes.update(hit_obj=((n,), torch.int32), hit_t=((n,), torch.float64), hit_normal=((n, 3), torch.float64))
-        res = {}
-        for name, (shape, dtype) in shapes.items():
-            t = out.get(name) if out else None
-            if t is None:
-                t = torch.empty(shape, dtype=dtype, device=dev)
-            elif not (t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev):
-                raise ValueError("trace_rays: out[%r] must be a contiguous %s %r tensor on %s" % (name, dtype, shape, dev))
-            res[name] = t
-        if counters is None:
-            counters = torch.zeros((_capi.CGRT_NCOUNTERS,), dtype=torch.int64, device=dev)
-        elif not (counters.dtype == torch.int64 and counters.numel() == _capi.CGRT_NCOUNTERS and counters.is_contiguous() and
-                  counters.device == dev):
-            raise ValueError("trace_rays: counters must be a contiguous int64 [8] tensor on %s" % (dev,))
-        res["counters"] = counters
-        if n == 0:
-            return res
-        ptr = lambda k: res[k].data_ptr() if k in res else None
-        r = _capi.Rays(n, org.data_ptr(), dirs.data_ptr(), keys.data_ptr() if keys is not None else None, first_index, seed,
-                       max_depth, (_capi.RAYS_STATS if stats else 0) | (0 if sign_pass else _capi.RAYS_NO_SIGN_PASS))
-        o = _capi.RayResults(ptr("acc"), ptr("nhit"), ptr("hit_obj"), ptr("hit_t"), ptr("hit_normal"))
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        check(self._L.cgrt_trace_rays(self._h, C.byref(r), C.byref(o), counters.data_ptr(), C.c_void_p(st)))
-        return res
+    def _trace_rays(self, A, what, org, dirs, keys, max_depth, seed, first_index, want, counters, stream, stats, out, sign_pass):
+        q = _TRACE_RAYS
+        n, org, dirs = A.rays(what, org=org, dirs=dirs)
+        keys = A.per_ray(what, "keys", keys, n, _U64)
+        res = A.results(what, q.spec, _want(what, q, want), out, n)
+        cnt = A.counters(what, counters)
+        r = self._rays(A, n, org, dirs, keys, first_index, seed, max_depth,
+                       (_capi.RAYS_STATS if stats else 0) | (0 if sign_pass else _capi.RAYS_NO_SIGN_PASS))
+        o = _capi.RayResults(*[A.ptr(res.get(k)) for k in q.spec])
+        self._query(A, q, n, stream, C.byref(r), C.byref(o), A.ptr(cnt))
+        return _with_counters(A, q, res, cnt)
 
     def trace_rays_host(self, org, dirs, keys=None, max_depth=5, seed=12345, first_index=0, want=("acc", "nhit", "hit"),
                         stats=False, sign_pass=True):
         """Synchronous form of trace_rays on numpy arrays (no torch needed): dict(acc, nhit (uint32), hit_obj, hit_t,
         hit_normal -- those in `want` --, counters (uint64 [8]), nrays, nhp)."""
-        org = np.ascontiguousarray(org, np.float64).reshape(-1, 3)
-        dirs = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
-        n = len(org)
-        if len(dirs) != n:
-            raise ValueError("trace_rays_host: org and dirs differ in length")
-        if keys is not None:
-            keys = np.ascontiguousarray(keys, np.uint64)
-            if keys.shape != (n,):
-                raise ValueError("trace_rays_host: keys must have one entry per ray")
-        want = tuple(want)
-        if not want or any(w not in self._WANT for w in want):
-            raise ValueError("trace_rays_host: want is a non-empty subset of %r" % (self._WANT,))
-        res = {}
-        if "acc" in want:
-            res["acc"] = np.zeros((n, 3), np.float64)
-        if "nhit" in want:
-            res["nhit"] = np.zeros(n, np.uint32)
-        if "hit" in want:
-            res.update(hit_obj=np.zeros(n, np.int32), hit_t=np.zeros(n, np.float64), hit_normal=np.zeros((n, 3), np.float64))
-        cnt = np.zeros((_capi.CGRT_NCOUNTERS,), np.uint64)
-        ptr = lambda k: res[k].ctypes.data if k in res else None
-        r = _capi.Rays(n, org.ctypes.data, dirs.ctypes.data, keys.ctypes.data if keys is not None else None, first_index, seed,
-                       max_depth, (_capi.RAYS_STATS if stats else 0) | (0 if sign_pass else _capi.RAYS_NO_SIGN_PASS))
-        o = _capi.RayResults(ptr("acc"), ptr("nhit"), ptr("hit_obj"), ptr("hit_t"), ptr("hit_normal"))
-        check(self._L.cgrt_trace_rays_host(self._h, C.byref(r), C.byref(o), cnt.ctypes.data))
-        res.update(counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]), nhp=int(cnt[_capi.CNT_HITPOINTS]))
-        return res
+        return self._trace_rays(_buffers.NUMPY, "trace_rays_host", org, dirs, keys, max_depth, seed, first_index, want, None, None, stats, None,
+                                sign_pass)
 
     # ---- hit attributes of caller-supplied rays ----
-    _ATTR_WANT = ("prim", "uv", "color", "material")
-
     def hit_attributes(self, org, dirs, hit_obj, hit_t, want=("prim", "uv", "color", "material"), out=None, stream=None):
         """cgrt_ray_hit_attributes on torch tensors: org, dirs float64 [n,3], hit_obj int32 [n] and hit_t float64 [n] -- the
         last two as trace_rays(want=("hit",)) wrote them for the same rays --, all contiguous on the scene's device.  want:
@@ -423,78 +462,22 @@ class Scene:
         the hit is no triangle), "uv" (float64 [n,2]: the hit point is (1-u-v)*pa + u*pb + v*pc), "color" (float64 [n,3]:
         getSurfaceColor at the hit) and "material" (float64 [n,2]: reflection, transparency).  out: dict of preallocated
         result tensors to write into.  Asynchronous on torch's current stream (or `stream`).  Returns a dict of the tensors."""
-        import torch
+        return self._hit_attributes(self._torch(), "hit_attributes", org, dirs, hit_obj, hit_t, want, out, stream)
 
-        dev = torch.device("cuda", self.device)
-        for name, t in (("org", org), ("dirs", dirs)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == 3 and
-                    t.is_contiguous() and t.device == dev):
-                raise ValueError("hit_attributes: %s must be a contiguous float64 [n,3] tensor on %s" % (name, dev))
-        n = org.shape[0]
-        if dirs.shape[0] != n:
-            raise ValueError("hit_attributes: org and dirs differ in length")
-        for name, t, dtype in (("hit_obj", hit_obj, torch.int32), ("hit_t", hit_t, torch.float64)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == (n,) and t.is_contiguous() and
-                    t.device == dev):
-                raise ValueError("hit_attributes: %s must be a contiguous %s [n] tensor on %s" % (name, dtype, dev))
-        want = tuple(want)
-        if not want or any(w not in self._ATTR_WANT for w in want):
-            raise ValueError("hit_attributes: want is a non-empty subset of %r" % (self._ATTR_WANT,))
-        shapes = dict(prim=((n,), torch.int32), uv=((n, 2), torch.float64), color=((n, 3), torch.float64),
-                      material=((n, 2), torch.float64))
-        res = {}
-        for name in self._ATTR_WANT:
-            if name not in want:
-                continue
-            shape, dtype = shapes[name]
-            t = out.get(name) if out else None
-            if t is None:
-                t = torch.empty(shape, dtype=dtype, device=dev)
-            elif not (isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and
-                      t.device == dev):
-                raise ValueError("hit_attributes: out[%r] must be a contiguous %s %r tensor on %s" % (name, dtype, shape, dev))
-            res[name] = t
-        if n == 0:
-            return res
-        ptr = lambda k: res[k].data_ptr() if k in res else None
-        r = _capi.Rays(n, org.data_ptr(), dirs.data_ptr(), None, 0, 0, 1, 0)
-        o = _capi.HitAttributes(ptr("prim"), ptr("uv"), ptr("color"), ptr("material"))
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        check(self._L.cgrt_ray_hit_attributes(self._h, C.byref(r), hit_obj.data_ptr(), hit_t.data_ptr(), C.byref(o), C.c_void_p(st)))
+    def _hit_attributes(self, A, what, org, dirs, hit_obj, hit_t, want, out, stream):
+        q = _HIT_ATTRIBUTES
+        n, org, dirs = A.rays(what, coerce=q.coerce, org=org, dirs=dirs)
+        hit_obj = A.per_ray(what, "hit_obj", hit_obj, n, ("torch.int32", "int32"), required=True, coerce=q.coerce)
+        hit_t = A.per_ray(what, "hit_t", hit_t, n, ("torch.float64", "float64"), required=True, coerce=q.coerce)
+        res = A.results(what, q.spec, _want(what, q, want), out, n)
+        r = self._rays(A, n, org, dirs, None, 0, 0, 1, 0)
+        o = _capi.HitAttributes(*[A.ptr(res.get(k)) for k in q.spec])
+        self._query(A, q, n, stream, C.byref(r), A.ptr(hit_obj), A.ptr(hit_t), C.byref(o))
         return res
 
     def hit_attributes_host(self, org, dirs, hit_obj, hit_t, want=("prim", "uv", "color", "material")):
         """Synchronous form of hit_attributes on numpy arrays (no torch needed): dict of the arrays in `want`."""
-        org = np.ascontiguousarray(org, np.float64)
-        dirs = np.ascontiguousarray(dirs, np.float64)
-        if org.ndim != 2 or org.shape[1] != 3 or dirs.shape != org.shape:
-            raise ValueError("hit_attributes_host: org and dirs must be [n,3] arrays of one length")
-        n = len(org)
-        hit_obj = np.ascontiguousarray(hit_obj)
-        hit_t = np.ascontiguousarray(hit_t)
-        if hit_obj.dtype != np.int32 or hit_obj.shape != (n,):
-            raise ValueError("hit_attributes_host: hit_obj must be an int32 [n] array")
-        if hit_t.dtype != np.float64 or hit_t.shape != (n,):
-            raise ValueError("hit_attributes_host: hit_t must be a float64 [n] array")
-        want = tuple(want)
-        if not want or any(w not in self._ATTR_WANT for w in want):
-            raise ValueError("hit_attributes_host: want is a non-empty subset of %r" % (self._ATTR_WANT,))
-        res = {}
-        if "prim" in want:
-            res["prim"] = np.full(n, -1, np.int32)
-        if "uv" in want:
-            res["uv"] = np.zeros((n, 2), np.float64)
-        if "color" in want:
-            res["color"] = np.zeros((n, 3), np.float64)
-        if "material" in want:
-            res["material"] = np.zeros((n, 2), np.float64)
-        if n == 0:
-            return res
-        ptr = lambda k: res[k].ctypes.data if k in res else None
-        r = _capi.Rays(n, org.ctypes.data, dirs.ctypes.data, None, 0, 0, 1, 0)
-        o = _capi.HitAttributes(ptr("prim"), ptr("uv"), ptr("color"), ptr("material"))
-        check(self._L.cgrt_ray_hit_attributes_host(self._h, C.byref(r), hit_obj.ctypes.data, hit_t.ctypes.data, C.byref(o)))
-        return res
+        return self._hit_attributes(_buffers.NUMPY, "hit_attributes_host", org, dirs, hit_obj, hit_t, want, None, None)
 
     # ---- occlusion queries of caller-supplied rays ----
     def occluded(self, org, dirs, tmax=None, keys=None, seed=12345, first_index=0, skip_transparent=False, stats=False, out=None,
@@ -505,85 +488,39 @@ class Scene:
         (unless an object returns a length below zero: a ray starting on a sphere's surface) and a dirs row of zeros give 0.  skip_transparent: objects with transparency >= 1e-4 are no occluders (shadow rays through
         glass).  out: a preallocated uint8 [n] tensor, or a dict holding one as "occluded".  Asynchronous on torch's current
         stream (or `stream`).  Returns {"occluded": uint8 [n], "counters": int64 [8]}."""
-        import torch
+        return self._occluded(self._torch(), "occluded", org, dirs, tmax, keys, seed, first_index, skip_transparent, stats,
+                              out.get("occluded") if isinstance(out, dict) else out, stream)
 
-        dev = torch.device("cuda", self.device)
-        for name, t in (("org", org), ("dirs", dirs)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == 3 and
-                    t.is_contiguous() and t.device == dev):
-                raise ValueError("occluded: %s must be a contiguous float64 [n,3] tensor on %s" % (name, dev))
-        n = org.shape[0]
-        if dirs.shape[0] != n:
-            raise ValueError("occluded: org and dirs differ in length")
-        if tmax is not None and not (isinstance(tmax, torch.Tensor) and tmax.dtype == torch.float64 and tuple(tmax.shape) == (n,) and
-                                     tmax.is_contiguous() and tmax.device == dev):
-            raise ValueError("occluded: tmax must be a contiguous float64 [n] tensor on %s" % (dev,))
-        if keys is not None and not (isinstance(keys, torch.Tensor) and keys.dtype == torch.int64 and tuple(keys.shape) == (n,) and
-                                     keys.is_contiguous() and keys.device == dev):
-            raise ValueError("occluded: keys must be a contiguous int64 [n] tensor on %s" % (dev,))
-        occ = out.get("occluded") if isinstance(out, dict) else out
+    def _occluded(self, A, what, org, dirs, tmax, keys, seed, first_index, skip_transparent, stats, occ, stream):
+        q = _OCCLUDED
+        n, org, dirs = A.rays(what, org=org, dirs=dirs)
+        tmax = A.per_ray(what, "tmax", tmax, n, _F64)
+        keys = A.per_ray(what, "keys", keys, n, _U64)
+        occ = A.per_ray(what, "out", occ, n, _U8)
         if occ is None:
-            occ = torch.empty((n,), dtype=torch.uint8, device=dev)
-        elif not (isinstance(occ, torch.Tensor) and occ.dtype == torch.uint8 and tuple(occ.shape) == (n,) and occ.is_contiguous() and
-                  occ.device == dev):
-            raise ValueError("occluded: out must be a contiguous uint8 [n] tensor on %s" % (dev,))
-        counters = torch.zeros((_capi.CGRT_NCOUNTERS,), dtype=torch.int64, device=dev)
-        res = {"occluded": occ, "counters": counters}
-        if n == 0:
-            return res
-        r = _capi.Rays(n, org.data_ptr(), dirs.data_ptr(), keys.data_ptr() if keys is not None else None, first_index, seed, 1,
+            occ = A.results(what, q.spec, q.spec, None, n)["occluded"]
+        cnt = A.counters(what)
+        res = {"occluded": occ if len(occ) == n else occ[:n]}  # (the numpy form's array is never empty)
+        r = self._rays(A, n, org, dirs, keys, first_index, seed, 1,
                        (_capi.RAYS_STATS if stats else 0) | (_capi.RAYS_SKIP_TRANSPARENT if skip_transparent else 0))
-        o = _capi.Occlusion(tmax.data_ptr() if tmax is not None else None, occ.data_ptr())
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        check(self._L.cgrt_occlusion_rays(self._h, C.byref(r), C.byref(o), counters.data_ptr(), C.c_void_p(st)))
-        return res
+        o = _capi.Occlusion(A.ptr(tmax), A.ptr(occ))
+        self._query(A, q, n, stream, C.byref(r), C.byref(o), A.ptr(cnt))
+        return _with_counters(A, q, res, cnt)
 
     def occluded_host(self, org, dirs, tmax=None, keys=None, seed=12345, first_index=0, skip_transparent=False, stats=False):
         """Synchronous form of occluded on numpy arrays (no torch needed): dict(occluded (uint8 [n]), counters (uint64 [8]),
         nrays)."""
-        org = np.ascontiguousarray(org, np.float64).reshape(-1, 3)
-        dirs = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
-        n = len(org)
-        if len(dirs) != n:
-            raise ValueError("occluded_host: org and dirs differ in length")
-        if tmax is not None:
-            tmax = np.ascontiguousarray(tmax, np.float64)
-            if tmax.shape != (n,):
-                raise ValueError("occluded_host: tmax must have one entry per ray")
-        if keys is not None:
-            keys = np.ascontiguousarray(keys, np.uint64)
-            if keys.shape != (n,):
-                raise ValueError("occluded_host: keys must have one entry per ray")
-        occ = np.zeros(max(n, 1), np.uint8)
-        cnt = np.zeros((_capi.CGRT_NCOUNTERS,), np.uint64)
-        r = _capi.Rays(n, org.ctypes.data, dirs.ctypes.data, keys.ctypes.data if keys is not None else None, first_index, seed, 1,
-                       (_capi.RAYS_STATS if stats else 0) | (_capi.RAYS_SKIP_TRANSPARENT if skip_transparent else 0))
-        o = _capi.Occlusion(tmax.ctypes.data if tmax is not None else None, occ.ctypes.data)
-        check(self._L.cgrt_occlusion_rays_host(self._h, C.byref(r), C.byref(o), cnt.ctypes.data))
-        return dict(occluded=occ[:n], counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]))
+        return self._occluded(_buffers.NUMPY, "occluded_host", org, dirs, tmax, keys, seed, first_index, skip_transparent, stats, None, None)
 
     def occlusion_variant(self, stats=False):
         """Name of the occlusion_rays_kernel instantiation occluded launches on this scene (cgrt_occlusion_rays_variant)."""
-        r = _capi.Rays(1, None, None, None, 0, 0, 1, _capi.RAYS_STATS if stats else 0)
-        buf = C.create_string_buffer(160)
-        check(self._L.cgrt_occlusion_rays_variant(self._h, C.byref(r), buf, len(buf)))
-        return buf.value.decode()
+        return self._rays_variant_name(self._L.cgrt_occlusion_rays_variant, stats)
+
+    def _rays_variant_name(self, fn, stats, max_depth=1, *results, flags=0):
+        r = _capi.Rays(1, None, None, None, 0, 0, max_depth, flags | (_capi.RAYS_STATS if stats else 0))
+        return _variant_name(fn, self._h, C.byref(r), *results)
 
     # ---- bounce queries of caller-supplied rays: one step of trace() ----
-    _BOUNCE = ("step", "hit_obj", "hit_t", "pos", "normal", "value", "child_org", "child_dir", "child_adj", "child_path", "child_keys")
-    _BOUNCE_GROUPS = {"hit": ("hit_obj", "hit_t"), "children": ("child_org", "child_dir", "child_adj", "child_path", "child_keys")}
-
-    def _bounce_want(self, what, want):
-        names = []
-        for w in tuple(want):
-            for k in self._BOUNCE_GROUPS.get(w, (w,)):
-                if k not in self._BOUNCE:
-                    raise ValueError("%s: want is a non-empty subset of %r" % (what, self._BOUNCE + tuple(self._BOUNCE_GROUPS)))
-                names.append(k)
-        if not names:
-            raise ValueError("%s: want is a non-empty subset of %r" % (what, self._BOUNCE + tuple(self._BOUNCE_GROUPS)))
-        return [k for k in self._BOUNCE if k in names]
-
     def bounce(self, org, dirs, adj=None, path=None, keys=None, seed=12345, first_index=0,
                want=("step", "hit", "pos", "normal", "value", "children"), stats=False, out=None, stream=None, counters=None):
         """cgrt_bounce_rays on torch tensors: one scene walk per ray, then exactly the step trace() takes at the hit.  org, dirs
@@ -597,102 +534,32 @@ class Scene:
         traced) or compacted first.  "hit" and "children" name the groups.  There is no depth limit: the caller's loop decides.
         out: dict of preallocated result tensors to write into.  Asynchronous on torch's current stream (or `stream`); counters
         (int64 [8]) are ADDED to.  Returns a dict of the tensors and "counters"."""
-        import torch
+        return self._bounce(self._torch(), "bounce", org, dirs, adj, path, keys, seed, first_index, want, stats, out, stream, counters)
 
-        dev = torch.device("cuda", self.device)
-        n = self._ray_tensors("bounce", org, dirs, keys)
-        if adj is not None and not (isinstance(adj, torch.Tensor) and adj.dtype == torch.float64 and tuple(adj.shape) == (n, 3) and
-                                    adj.is_contiguous() and adj.device == dev):
-            raise ValueError("bounce: adj must be a contiguous float64 [n,3] tensor on %s" % (dev,))
-        if path is not None and not (isinstance(path, torch.Tensor) and path.dtype == torch.int32 and tuple(path.shape) == (n,) and
-                                     path.is_contiguous() and path.device == dev):
-            raise ValueError("bounce: path must be a contiguous int32 [n] tensor on %s" % (dev,))
-        names = self._bounce_want("bounce", want)
-        shapes = dict(step=((n,), torch.uint8), hit_obj=((n,), torch.int32), hit_t=((n,), torch.float64), pos=((n, 3), torch.float64),
-                      normal=((n, 3), torch.float64), value=((n, 3), torch.float64), child_org=((2 * n, 3), torch.float64),
-                      child_dir=((2 * n, 3), torch.float64), child_adj=((2 * n, 3), torch.float64), child_path=((2 * n,), torch.int32),
-                      child_keys=((2 * n,), torch.int64))
-        res = {}
-        for name in names:
-            shape, dtype = shapes[name]
-            t = out.get(name) if out else None
-            if t is None:
-                t = torch.empty(shape, dtype=dtype, device=dev)
-            elif not (isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and
-                      t.device == dev):
-                raise ValueError("bounce: out[%r] must be a contiguous %s %r tensor on %s" % (name, dtype, shape, dev))
-            res[name] = t
-        if counters is None:
-            counters = torch.zeros((_capi.CGRT_NCOUNTERS,), dtype=torch.int64, device=dev)
-        elif not (counters.dtype == torch.int64 and counters.numel() == _capi.CGRT_NCOUNTERS and counters.is_contiguous() and
-                  counters.device == dev):
-            raise ValueError("bounce: counters must be a contiguous int64 [8] tensor on %s" % (dev,))
-        res["counters"] = counters
-        if n == 0:
-            return res
-        ptr = lambda k: res[k].data_ptr() if k in res else None
-        r = _capi.Rays(n, org.data_ptr(), dirs.data_ptr(), keys.data_ptr() if keys is not None else None, first_index, seed, 1,
-                       _capi.RAYS_STATS if stats else 0)
-        b = _capi.Bounce(adj.data_ptr() if adj is not None else None, path.data_ptr() if path is not None else None,
-                         *[ptr(k) for k in self._BOUNCE])
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        check(self._L.cgrt_bounce_rays(self._h, C.byref(r), C.byref(b), counters.data_ptr(), C.c_void_p(st)))
-        return res
+    def _bounce(self, A, what, org, dirs, adj, path, keys, seed, first_index, want, stats, out, stream, counters):
+        q = _BOUNCE
+        n, org, dirs = A.rays(what, org=org, dirs=dirs)
+        given = dict(adj=adj, path=path, keys=keys)
+        for name in q.inputs[A.form]:
+            given[name] = A.per_ray(what, name, given[name], n, *_INPUT[name])
+        res = A.results(what, q.spec, _want(what, q, want), out, n)
+        cnt = A.counters(what, counters)
+        r = self._rays(A, n, org, dirs, given["keys"], first_index, seed, 1, _capi.RAYS_STATS if stats else 0)
+        b = _capi.Bounce(A.ptr(given["adj"]), A.ptr(given["path"]), *[A.ptr(res.get(k)) for k in q.spec])
+        self._query(A, q, n, stream, C.byref(r), C.byref(b), A.ptr(cnt))
+        return _with_counters(A, q, res, cnt)
 
     def bounce_host(self, org, dirs, adj=None, path=None, keys=None, seed=12345, first_index=0,
                     want=("step", "hit", "pos", "normal", "value", "children"), stats=False):
         """Synchronous form of bounce on numpy arrays (no torch needed): dict of the arrays in `want` (child_path uint32,
         child_keys uint64), counters (uint64 [8]), nrays, nhp."""
-        org = np.ascontiguousarray(org, np.float64).reshape(-1, 3)
-        dirs = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
-        n = len(org)
-        if len(dirs) != n:
-            raise ValueError("bounce_host: org and dirs differ in length")
-        if adj is not None:
-            adj = np.ascontiguousarray(adj, np.float64)
-            if adj.shape != (n, 3):
-                raise ValueError("bounce_host: adj must be an [n,3] array")
-        if path is not None:
-            path = np.ascontiguousarray(path, np.uint32)
-            if path.shape != (n,):
-                raise ValueError("bounce_host: path must have one entry per ray")
-        if keys is not None:
-            keys = np.ascontiguousarray(keys, np.uint64)
-            if keys.shape != (n,):
-                raise ValueError("bounce_host: keys must have one entry per ray")
-        names = self._bounce_want("bounce_host", want)
-        make = dict(step=lambda: np.zeros(n, np.uint8), hit_obj=lambda: np.full(n, -1, np.int32), hit_t=lambda: np.zeros(n, np.float64),
-                    pos=lambda: np.zeros((n, 3), np.float64), normal=lambda: np.zeros((n, 3), np.float64),
-                    value=lambda: np.zeros((n, 3), np.float64), child_org=lambda: np.zeros((2 * n, 3), np.float64),
-                    child_dir=lambda: np.zeros((2 * n, 3), np.float64), child_adj=lambda: np.zeros((2 * n, 3), np.float64),
-                    child_path=lambda: np.zeros(2 * n, np.uint32), child_keys=lambda: np.zeros(2 * n, np.uint64))
-        res = {k: make[k]() for k in names}
-        cnt = np.zeros((_capi.CGRT_NCOUNTERS,), np.uint64)
-        ptr = lambda k: res[k].ctypes.data if k in res else None
-        r = _capi.Rays(n, org.ctypes.data, dirs.ctypes.data, keys.ctypes.data if keys is not None else None, first_index, seed, 1,
-                       _capi.RAYS_STATS if stats else 0)
-        b = _capi.Bounce(adj.ctypes.data if adj is not None else None, path.ctypes.data if path is not None else None,
-                         *[ptr(k) for k in self._BOUNCE])
-        check(self._L.cgrt_bounce_rays_host(self._h, C.byref(r), C.byref(b), cnt.ctypes.data))
-        res.update(counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]), nhp=int(cnt[_capi.CNT_HITPOINTS]))
-        return res
+        return self._bounce(_buffers.NUMPY, "bounce_host", org, dirs, adj, path, keys, seed, first_index, want, stats, None, None, None)
 
     def bounce_variant(self, stats=False):
         """Name of the bounce_rays_kernel instantiation bounce launches on this scene (cgrt_bounce_rays_variant)."""
-        r = _capi.Rays(1, None, None, None, 0, 0, 1, _capi.RAYS_STATS if stats else 0)
-        buf = C.create_string_buffer(160)
-        check(self._L.cgrt_bounce_rays_variant(self._h, C.byref(r), buf, len(buf)))
-        return buf.value.decode()
+        return self._rays_variant_name(self._L.cgrt_bounce_rays_variant, stats)
 
     # ---- wavefront trace of caller-supplied rays: any depth, the depth loop inside the library ----
-    _WAVEFRONT = ("acc", "nhit", "hp")
-
-    def _wavefront_want(self, what, want):
-        want = tuple(want)
-        if any(w not in self._WAVEFRONT for w in want):
-            raise ValueError("%s: want is a subset of %r" % (what, self._WAVEFRONT))
-        return want
-
     def last_wavefront(self):
         """What the last wavefront call on this scene did (cgrt_scene_last_wavefront, _rays): dict(slices, halvings, levels,
         rays_per_level (the rays traced at levels 1 .. levels))."""
@@ -713,119 +580,58 @@ class Scene:
         (0 = automatic); the results never depend on it.  out: dict of preallocated tensors (acc, nhit; hp9, hp_ray, hp_path
         of hp_cap rows).  The call runs on torch's current stream (or `stream`) and SYNCHRONISES it; counters (int64 [8]) are
         ADDED to.  Returns a dict of the tensors, "counters", "hp_count" and last_wavefront()'s entries."""
-        import torch
+        return self._wavefront(self._torch(), "wavefront", org, dirs, keys, max_depth, min_adj, seed, first_index, want, hp_cap, work_bytes,
+                               stats, out, stream, counters)
 
-        dev = torch.device("cuda", self.device)
-        n = self._ray_tensors("wavefront", org, dirs, keys)
-        want = self._wavefront_want("wavefront", want)
+    def _wavefront(self, A, what, org, dirs, keys, max_depth, min_adj, seed, first_index, want, hp_cap, work_bytes, stats, out, stream,
+                   counters):
+        q = _WAVEFRONT
+        n, org, dirs = A.rays(what, org=org, dirs=dirs)
+        keys = A.per_ray(what, "keys", keys, n, _U64)
+        names = _want(what, q, want)
         if not (isinstance(max_depth, int) and 1 <= max_depth <= _capi.WAVEFRONT_MAX_DEPTH):
-            raise ValueError("wavefront: max_depth must be 1..%d" % _capi.WAVEFRONT_MAX_DEPTH)
+            raise ValueError("%s: max_depth must be 1..%d" % (what, _capi.WAVEFRONT_MAX_DEPTH))
         if not (min_adj >= 0.0) or work_bytes < 0 or (hp_cap is not None and hp_cap < 0):
-            raise ValueError("wavefront: min_adj, work_bytes and hp_cap must be >= 0")
-        cap = int(hp_cap if hp_cap is not None else 4 * n) if "hp" in want else 0
-        shapes = {}
-        if "acc" in want:
-            shapes["acc"] = ((n, 3), torch.float64)
-        if "nhit" in want:
-            shapes["nhit"] = ((n,), torch.int32)
+            raise ValueError("%s: min_adj, work_bytes and hp_cap must be >= 0" % what)
+        hp = [k for k in names if k in q.groups["hp"]]
+        cap = int(hp_cap if hp_cap is not None else 4 * n) if hp else 0
+        res = A.results(what, q.spec, [k for k in names if cap > 0 or k not in hp], out, n, cap)
+        cnt = A.counters(what, counters)
+        ptr = lambda k: A.ptr(res[k]) if k in res and len(res[k]) else None
+        r = self._rays(A, n, org, dirs, keys, first_index, seed, 1, _capi.RAYS_STATS if stats else 0)
+        w = _capi.Wavefront(max_depth, 0, float(min_adj), int(work_bytes), *[ptr(k) for k in q.spec], cap)
+        count = C.c_uint64(0)
+        self._query(A, q, n, stream, C.byref(r), C.byref(w), A.ptr(cnt), C.byref(count))
         if cap > 0:
-            shapes.update(hp9=((cap, 9), torch.float64), hp_ray=((cap,), torch.int64), hp_path=((cap,), torch.int32))
-        res = {}
-        for name, (shape, dtype) in shapes.items():
-            t = out.get(name) if out else None
-            if t is None:
-                t = torch.empty(shape, dtype=dtype, device=dev)
-            elif not (isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and
-                      t.device == dev):
-                raise ValueError("wavefront: out[%r] must be a contiguous %s %r tensor on %s" % (name, dtype, shape, dev))
-            res[name] = t
-        if counters is None:
-            counters = torch.zeros((_capi.CGRT_NCOUNTERS,), dtype=torch.int64, device=dev)
-        elif not (counters.dtype == torch.int64 and counters.numel() == _capi.CGRT_NCOUNTERS and counters.is_contiguous() and
-                  counters.device == dev):
-            raise ValueError("wavefront: counters must be a contiguous int64 [8] tensor on %s" % (dev,))
-        ptr = lambda k: res[k].data_ptr() if k in res else None
-        r = _capi.Rays(n, org.data_ptr(), dirs.data_ptr(), keys.data_ptr() if keys is not None else None, first_index, seed, 1,
-                       _capi.RAYS_STATS if stats else 0)
-        w = _capi.Wavefront(max_depth, 0, float(min_adj), int(work_bytes), ptr("acc"), ptr("nhit"), ptr("hp9"), ptr("hp_ray"),
-                            ptr("hp_path"), cap)
-        cnt = C.c_uint64(0)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        check(self._L.cgrt_wavefront_rays(self._h, C.byref(r), C.byref(w), counters.data_ptr(), C.byref(cnt), C.c_void_p(st)))
-        m = min(int(cnt.value), cap)
-        for k in ("hp9", "hp_ray", "hp_path"):
-            if k in res:
-                res[k] = res[k][:m]
-        if "hp" in want and cap == 0:
-            res.update(hp9=torch.empty((0, 9), dtype=torch.float64, device=dev), hp_ray=torch.empty((0,), dtype=torch.int64, device=dev),
-                       hp_path=torch.empty((0,), dtype=torch.int32, device=dev))
-        res.update(counters=counters, hp_count=int(cnt.value))
+            res.update({k: res[k][:min(int(count.value), cap)] for k in hp})
+        else:
+            res.update(A.results(what, q.spec, hp, None, n))
+        res["hp_count"] = int(count.value)
         res.update(self.last_wavefront() if n > 0 else dict(slices=0, halvings=0, levels=0, rays_per_level=[]))
-        return res
+        return _with_counters(A, q, res, cnt)
 
     def wavefront_host(self, org, dirs, keys=None, max_depth=8, min_adj=0.0, seed=12345, first_index=0, want=("acc", "nhit"),
                        hp_cap=None, work_bytes=0, stats=False):
         """Synchronous form of wavefront on numpy arrays (no torch needed): dict of acc, nhit (uint32), hp9, hp_ray, hp_path
         (uint32) -- those in `want` --, counters (uint64 [8]), nrays, nhp, hp_count and last_wavefront()'s entries."""
-        org = np.ascontiguousarray(org, np.float64).reshape(-1, 3)
-        dirs = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
-        n = len(org)
-        if len(dirs) != n:
-            raise ValueError("wavefront_host: org and dirs differ in length")
-        if keys is not None:
-            keys = np.ascontiguousarray(keys, np.uint64)
-            if keys.shape != (n,):
-                raise ValueError("wavefront_host: keys must have one entry per ray")
-        want = self._wavefront_want("wavefront_host", want)
-        if not (isinstance(max_depth, int) and 1 <= max_depth <= _capi.WAVEFRONT_MAX_DEPTH):
-            raise ValueError("wavefront_host: max_depth must be 1..%d" % _capi.WAVEFRONT_MAX_DEPTH)
-        if not (min_adj >= 0.0) or work_bytes < 0 or (hp_cap is not None and hp_cap < 0):
-            raise ValueError("wavefront_host: min_adj, work_bytes and hp_cap must be >= 0")
-        cap = int(hp_cap if hp_cap is not None else 4 * n) if "hp" in want else 0
-        res = {}
-        if "acc" in want:
-            res["acc"] = np.zeros((n, 3), np.float64)
-        if "nhit" in want:
-            res["nhit"] = np.zeros(n, np.uint32)
-        if "hp" in want:
-            res.update(hp9=np.zeros((cap, 9), np.float64), hp_ray=np.zeros(cap, np.int64), hp_path=np.zeros(cap, np.uint32))
-        cnt = np.zeros((_capi.CGRT_NCOUNTERS,), np.uint64)
-        ptr = lambda k: res[k].ctypes.data if k in res and res[k].size else None
-        r = _capi.Rays(n, org.ctypes.data, dirs.ctypes.data, keys.ctypes.data if keys is not None else None, first_index, seed, 1,
-                       _capi.RAYS_STATS if stats else 0)
-        w = _capi.Wavefront(max_depth, 0, float(min_adj), int(work_bytes), ptr("acc"), ptr("nhit"), ptr("hp9"), ptr("hp_ray"),
-                            ptr("hp_path"), cap)
-        hpc = C.c_uint64(0)
-        check(self._L.cgrt_wavefront_rays_host(self._h, C.byref(r), C.byref(w), cnt.ctypes.data, C.byref(hpc)))
-        m = min(int(hpc.value), cap)
-        for k in ("hp9", "hp_ray", "hp_path"):
-            if k in res:
-                res[k] = res[k][:m]
-        res.update(counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]), nhp=int(cnt[_capi.CNT_HITPOINTS]), hp_count=int(hpc.value))
-        res.update(self.last_wavefront() if n > 0 else dict(slices=0, halvings=0, levels=0, rays_per_level=[]))
-        return res
+        return self._wavefront(_buffers.NUMPY, "wavefront_host", org, dirs, keys, max_depth, min_adj, seed, first_index, want, hp_cap,
+                               work_bytes, stats, None, None, None)
 
     def wavefront_variant(self, stats=False):
         """Name of the wavefront_step_kernel instantiation wavefront launches on this scene (cgrt_wavefront_rays_variant)."""
-        r = _capi.Rays(1, None, None, None, 0, 0, 1, _capi.RAYS_STATS if stats else 0)
-        buf = C.create_string_buffer(160)
-        check(self._L.cgrt_wavefront_rays_variant(self._h, C.byref(r), buf, len(buf)))
-        return buf.value.decode()
+        return self._rays_variant_name(self._L.cgrt_wavefront_rays_variant, stats)
 
     def rays_variant(self, max_depth=5, want=("acc", "nhit", "hit"), stats=False):
         """Name of the trace_rays_kernel instantiation trace_rays launches for these arguments (cgrt_trace_rays_variant)."""
         full = 1 if ("acc" in want or "nhit" in want) else None
-        r = _capi.Rays(1, None, None, None, 0, 0, max_depth, _capi.RAYS_STATS if stats else 0)
         o = _capi.RayResults(full, None, 1 if "hit" in want else None, None, None)
-        buf = C.create_string_buffer(160)
-        check(self._L.cgrt_trace_rays_variant(self._h, C.byref(r), C.byref(o), buf, len(buf)))
-        return buf.value.decode()
+        return self._rays_variant_name(self._L.cgrt_trace_rays_variant, stats, max_depth, C.byref(o))
 
     def trace_grid_host(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, rows=None, row_offset=0,
                         stripe=None, sample_offset=0, spp_total=None, stats=False, split_samples=False, reorder=True,
                         force_reorder=False, tile_order=True, diffuse_tiles=False, sphere_pairs=True, sphere_masks=True, sample_relay=None,
                         relay_mirror=None, relay_order=None, lens_stage=True, sure_tiles=True, relay_start=None, relay_boost=None, lens_table=None,
-                   inside_trips=True):
+                        inside_trips=True):
         """Synchronous form with numpy outputs (no torch needed): dict(rgb, nhit, counters)."""
         rows = height - row_offset if rows is None else rows
         rgb = np.zeros((rows, width, 3), np.float32)
@@ -833,8 +639,9 @@ class Scene:
         cnt = np.zeros((_capi.CGRT_NCOUNTERS,), np.uint64)
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, sample_offset,
                               spp_total,
-                              _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks, lens_stage, sure_tiles, lens_table, inside_trips) |
-                              _relay_flag(sample_relay, relay_mirror, relay_order, relay_start, relay_boost))
+                              _grid_flags(stats, split_samples, reorder, force_reorder, tile_order, diffuse_tiles, sphere_pairs, sphere_masks,
+                                          sample_relay, relay_mirror, relay_order, lens_stage, sure_tiles, relay_start, relay_boost, lens_table,
+                                          inside_trips))
         check(self._L.cgrt_trace_grid_host(self._h, C.byref(cc), C.byref(g), rgb.ctypes.data, nhit.ctypes.data,
                                            cnt.ctypes.data))
         return dict(rgb=rgb, nhit=nhit, counters=cnt, nrays=int(cnt[_capi.CNT_RAYS]),
@@ -987,11 +794,8 @@ class Scene:
         n = C.c_uint64(0)
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, None, 0, None, 0)
         check(self._L.cgrt_trace_grid_hitpoints(self._h, C.byref(cc), C.byref(g), rec.ctypes.data, cap, C.byref(n)))
-        m = min(int(n.value), cap)
-        lab = rec[:m, 9].astype(np.int64)
-        seq, lab = lab & 15, lab >> 4
-        return dict(hp=rec[:m, :9].copy(), pix=lab % (rows * width), smp=lab // (rows * width), seq=seq,
-                    count=int(n.value))
+        hp, lab, seq = _hitpoint_records(rec, n.value, cap)
+        return dict(hp=hp, pix=lab % (rows * width), smp=lab // (rows * width), seq=seq, count=int(n.value))
 
     def ppm_render(self, width, height, spp=1, camera=None, max_depth=5, seed=12345, nphotons=100000, photon_seed=777,
                    hashsize=1000001, light=(0.0, 19.999, 20.0), jitter=2.0, power=700.0, alpha=0.7, batch=0,
@@ -1007,7 +811,7 @@ class Scene:
         want_hitpoints: hp [n,16]; with want_rgb8 (contiguous rows only): rgb8 [rows,W,3] uint8, top row first)."""
         rows = height if rows is None else rows
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, 0, None, 0)
-        ph = _capi.Photons(_d3(light), jitter, power, alpha, nphotons, hashsize, batch, photon_seed, initial_radius, pair_cap)
+        ph = _photons(light, jitter, power, alpha, nphotons, hashsize, batch, photon_seed, initial_radius, pair_cap)
         height = rows
         img = np.zeros((height, width, 3), np.float64)
         cap = height * width * spp * 16 if want_hitpoints else 0
@@ -1034,13 +838,11 @@ class Scene:
         traced ahead for the next call)."""
         rows = height if rows is None else rows
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, seed, row_offset, stripe, 0, None, 0)
-        ph = _capi.Photons(_d3(light), jitter, power, alpha, nphotons, hashsize, batch, photon_seed, initial_radius, pair_cap)
+        ph = _photons(light, jitter, power, alpha, nphotons, hashsize, batch, photon_seed, initial_radius, pair_cap)
         h = C.c_void_p()
         check(self._L.cgrt_ppm_session_create(self._h, C.byref(cc), C.byref(g), C.byref(ph),
                                               0 if lookahead else _capi.PPM_SESSION_NO_LOOKAHEAD, C.byref(h)))
-        ses = PpmSession(self, h, width, rows, spp)
-        self._sessions.add(ses)
-        return ses
+        return self._open_session(PpmSession, h, width, rows, spp)
 
     def sppm_session(self, width, height, spp=1, camera=None, photon_depth=5, max_depth=5, seed=12345, photon_seed=777,
                      hashsize=1000001, light=(0.0, 19.999, 20.0), jitter=2.0, power=700.0, alpha=0.7, batch=0, rows=None,
@@ -1051,49 +853,26 @@ class Scene:
         at sample_offset = passes * spp, add_pass_rays with the caller's rays.  rows / row_offset / stripe: this rank's share
         of a width x height frame as in ppm_session (every rank traces all photons)."""
         rows = height if rows is None else rows
-        ph = _capi.Photons(_d3(light), jitter, power, alpha, 0, hashsize, batch, photon_seed, initial_radius, pair_cap)
+        ph = _photons(light, jitter, power, alpha, 0, hashsize, batch, photon_seed, initial_radius, pair_cap)
         h = C.c_void_p()
         check(self._L.cgrt_sppm_session_create(self._h, width, rows, spp, photon_depth, C.byref(ph), 0, C.byref(h)))
-        ses = SppmSession(self, h, width, rows, spp, dict(camera=camera, height=height, max_depth=max_depth, seed=seed,
-                                                          row_offset=row_offset, stripe=stripe))
-        self._sessions.add(ses)
-        return ses
-
-    def _ray_tensors(self, what, org, dirs, keys, pixel=None):
-        """The argument checks of trace_rays for the ray-buffer calls; returns n."""
-        import torch
-
-        dev = torch.device("cuda", self.device)
-        for name, t in (("org", org), ("dirs", dirs)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == 3 and
-                    t.is_contiguous() and t.device == dev):
-                raise ValueError("%s: %s must be a contiguous float64 [n,3] tensor on %s" % (what, name, dev))
-        n = org.shape[0]
-        if dirs.shape[0] != n:
-            raise ValueError("%s: org and dirs differ in length" % what)
-        for name, t in (("keys", keys), ("pixel", pixel)):
-            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.int64 and tuple(t.shape) == (n,) and
-                                      t.is_contiguous() and t.device == dev):
-                raise ValueError("%s: %s must be a contiguous int64 [n] tensor on %s" % (what, name, dev))
-        return n
+        return self._open_session(SppmSession, h, width, rows, spp, dict(camera=camera, height=height, max_depth=max_depth, seed=seed,
+                                                                         row_offset=row_offset, stripe=stripe))
 
     def trace_rays_hitpoints(self, org, dirs, keys=None, max_depth=5, seed=12345, first_index=0, cap=None):
         """cgrt_trace_rays_hitpoints: the Hitpoints of the rays' trees (torch tensors as for trace_rays), unordered:
         dict(hp [m,9] = f, pos, normal (after the flip of main.cpp:73-76); ray [m]; seq [m] (position in the ray tree's
         emission order); count (Hitpoints produced; m = min(count, cap))).  Synchronous."""
-        if not self.stats()["committed"]:
-            check(self._L.cgrt_trace_rays_hitpoints(self._h, C.byref(_capi.Rays(0, None, None, None, 0, 0, max_depth, 0)), None, 0,
-                                                    C.byref(C.c_uint64(0))))
+        self._unless_committed(lambda: self._L.cgrt_trace_rays_hitpoints(
+            self._h, C.byref(_capi.Rays(0, None, None, None, 0, 0, max_depth, 0)), None, 0, C.byref(C.c_uint64(0))))
         n = self._ray_tensors("trace_rays_hitpoints", org, dirs, keys)
         cap = int(cap if cap is not None else n * 16)
         rec = np.zeros((max(cap, 1), 10), np.float64)
         cnt = C.c_uint64(0)
-        r = _capi.Rays(n, org.data_ptr(), dirs.data_ptr(), keys.data_ptr() if keys is not None else None, first_index, seed,
-                       max_depth, 0)
+        r = self._rays(self._torch(), n, org, dirs, keys, first_index, seed, max_depth, 0)
         check(self._L.cgrt_trace_rays_hitpoints(self._h, C.byref(r), rec.ctypes.data, cap, C.byref(cnt)))
-        m = min(int(cnt.value), cap)
-        lab = rec[:m, 9].astype(np.int64)
-        return dict(hp=rec[:m, :9].copy(), ray=lab >> 4, seq=lab & 15, count=int(cnt.value))
+        hp, ray, seq = _hitpoint_records(rec, cnt.value, cap)
+        return dict(hp=hp, ray=ray, seq=seq, count=int(cnt.value))
 
     def ppm_session_rays(self, org, dirs, keys=None, *, width, rows, spp=1, pixel=None, max_depth=5, seed=12345, first_index=0,
                          nphotons=0, photon_seed=777, hashsize=1000001, light=(0.0, 19.999, 20.0), jitter=2.0, power=700.0,
@@ -1103,26 +882,20 @@ class Scene:
         device; negative: the ray is not traced), or i % (width * rows) without `pixel` -- camera_rays' order.  spp is the
         gather's normaliser (rays per texel).  Returns a PpmSession; its hitpoints()[:, 0] is the ray index.  For
         camera_rays(width, rows, spp, ...) without `pixel` the session equals ppm_session on that grid bit for bit."""
-        if not self.stats()["committed"]:  # the library's own answer (no tensor is looked at)
-            check(self._L.cgrt_ppm_session_create_rays(self._h, C.byref(_capi.Rays(0, None, None, None, 0, 0, max_depth, 0)),
-                                                       C.byref(_capi.RayPixels(width, rows, spp, 0, None)),
-                                                       C.byref(_capi.Photons(_d3(light), jitter, power, alpha, 0, hashsize, batch,
-                                                                             photon_seed, initial_radius, pair_cap)),
-                                                       0, C.byref(C.c_void_p())))
+        self._unless_committed(lambda: self._L.cgrt_ppm_session_create_rays(
+            self._h, C.byref(_capi.Rays(0, None, None, None, 0, 0, max_depth, 0)), C.byref(_capi.RayPixels(width, rows, spp, 0, None)),
+            C.byref(_photons(light, jitter, power, alpha, 0, hashsize, batch, photon_seed, initial_radius, pair_cap)), 0,
+            C.byref(C.c_void_p())))
         n = self._ray_tensors("ppm_session_rays", org, dirs, keys, pixel)
-        r = _capi.Rays(n, org.data_ptr(), dirs.data_ptr(), keys.data_ptr() if keys is not None else None, first_index, seed,
-                       max_depth, 0)
-        px = _capi.RayPixels(width, rows, spp, 0, pixel.data_ptr() if pixel is not None else None)
-        ph = _capi.Photons(_d3(light), jitter, power, alpha, nphotons, hashsize, batch, photon_seed, initial_radius, pair_cap)
+        A = self._torch()
+        r = self._rays(A, n, org, dirs, keys, first_index, seed, max_depth, 0)
+        px = _capi.RayPixels(width, rows, spp, 0, A.ptr(pixel))
+        ph = _photons(light, jitter, power, alpha, nphotons, hashsize, batch, photon_seed, initial_radius, pair_cap)
         h = C.c_void_p()
-        import torch
-
-        torch.cuda.current_stream(org.device).synchronize()  # the session's eye stage runs on the null stream
+        A.torch.cuda.current_stream(org.device).synchronize()  # the session's eye stage runs on the null stream
         check(self._L.cgrt_ppm_session_create_rays(self._h, C.byref(r), C.byref(px), C.byref(ph),
                                                    0 if lookahead else _capi.PPM_SESSION_NO_LOOKAHEAD, C.byref(h)))
-        ses = PpmSession(self, h, width, rows, spp)
-        self._sessions.add(ses)
-        return ses
+        return self._open_session(PpmSession, h, width, rows, spp)
 
     def ppm_session_hitpoints(self, hp9, ray=None, path=None, pixel=None, *, width, rows, spp=1, max_depth=5, nphotons=0,
                               photon_seed=777, hashsize=1000001, light=(0.0, 19.999, 20.0), jitter=2.0, power=700.0, alpha=0.7,
@@ -1134,32 +907,23 @@ class Scene:
         with path 0, a negative ray or a non-finite pos is dropped.  spp is the gather's normaliser and max_depth the PHOTONS'
         depth limit (1..5).  Returns a PpmSession; hitpoints()[:, 0] is the ray id, [:, 1] the record's rank within its ray.  The
         records wavefront(max_depth <= 5, want=("hp",)) returns give ppm_session_rays' session on the same rays bit for bit."""
-        ph = _capi.Photons(_d3(light), jitter, power, alpha, nphotons, hashsize, batch, photon_seed, initial_radius, pair_cap)
-        if not self.stats()["committed"]:  # the library's own answer (no tensor is looked at)
-            check(self._L.cgrt_ppm_session_create_hitpoints(self._h, C.byref(_capi.Hitpoints(0, None, None, None, None, width, rows,
-                                                                                             spp, max_depth)),
-                                                            C.byref(ph), 0, C.byref(C.c_void_p())))
-        import torch
-
-        dev = torch.device("cuda", self.device)
-        if not (isinstance(hp9, torch.Tensor) and hp9.dtype == torch.float64 and hp9.dim() == 2 and hp9.shape[1] == 9 and
-                hp9.is_contiguous() and hp9.device == dev):
-            raise ValueError("ppm_session_hitpoints: hp9 must be a contiguous float64 [n,9] tensor on %s" % (dev,))
+        what = "ppm_session_hitpoints"
+        ph = _photons(light, jitter, power, alpha, nphotons, hashsize, batch, photon_seed, initial_radius, pair_cap)
+        self._unless_committed(lambda: self._L.cgrt_ppm_session_create_hitpoints(
+            self._h, C.byref(_capi.Hitpoints(0, None, None, None, None, width, rows, spp, max_depth)), C.byref(ph), 0, C.byref(C.c_void_p())))
+        A = self._torch()
+        A.per_ray(what, "hp9", hp9, None, _F64, 9, required=True)
         n = hp9.shape[0]
-        uint32 = getattr(torch, "uint32", torch.int32)
-        for name, t, dts in (("ray", ray, (torch.int64,)), ("path", path, (torch.int32, uint32)), ("pixel", pixel, (torch.int64,))):
-            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype in dts and tuple(t.shape) == (n,) and
-                                      t.is_contiguous() and t.device == dev):
-                raise ValueError("ppm_session_hitpoints: %s must be a contiguous %s [n] tensor on %s" % (name, dts[0], dev))
-        ptr = lambda t: t.data_ptr() if t is not None and n > 0 else None
+        A.per_ray(what, "ray", ray, n, ("torch.int64",))
+        A.per_ray(what, "path", path, n, (("torch.int32", "torch.uint32"),))
+        A.per_ray(what, "pixel", pixel, n, ("torch.int64",))
+        ptr = lambda t: A.ptr(t) if n > 0 else None
         hps = _capi.Hitpoints(n, ptr(hp9), ptr(ray), ptr(path), ptr(pixel), width, rows, spp, max_depth)
         h = C.c_void_p()
-        torch.cuda.current_stream(dev).synchronize()  # the table build runs on the null stream
+        A.torch.cuda.current_stream(A.dev).synchronize()  # the table build runs on the null stream
         check(self._L.cgrt_ppm_session_create_hitpoints(self._h, C.byref(hps), C.byref(ph),
                                                         0 if lookahead else _capi.PPM_SESSION_NO_LOOKAHEAD, C.byref(h)))
-        ses = PpmSession(self, h, width, rows, spp)
-        self._sessions.add(ses)
-        return ses
+        return self._open_session(PpmSession, h, width, rows, spp)
 
     def ppm_session_wavefront(self, org, dirs, keys=None, *, width, rows, spp=1, pixel=None, eye_depth=12, min_adj=0.0, max_depth=5,
                               seed=12345, first_index=0, work_bytes=0, **photon_kw):
@@ -1184,64 +948,37 @@ class Scene:
     def capture_variant(self, max_depth=5):
         """Name of the capture_rays_kernel instantiation trace_rays_hitpoints / ppm_session_rays launch (cgrt_trace_rays_variant
         with CGRT_RAYS_HITPOINTS)."""
-        r = _capi.Rays(1, None, None, None, 0, 0, max_depth, _capi.RAYS_HITPOINTS)
-        buf = C.create_string_buffer(160)
-        check(self._L.cgrt_trace_rays_variant(self._h, C.byref(r), None, buf, len(buf)))
-        return buf.value.decode()
+        return self._rays_variant_name(self._L.cgrt_trace_rays_variant, False, max_depth, None, flags=_capi.RAYS_HITPOINTS)
 
     def photon_events(self, first, count, max_depth=5, photon_seed=777, light=(0.0, 19.999, 20.0), jitter=2.0,
                       power=700.0):
         """Verification probe: diffuse hits of photons [first, first+count): [n,10] = photon, P, n, flux in serial
         order (slot order)."""
-        ph = _capi.Photons(_d3(light), jitter, power, 0.7, count, 1000001, 0, photon_seed, 0.0, 0)
+        ph = _photons(light, jitter, power, nphotons=count, photon_seed=photon_seed)
         ev = np.zeros((count * 8, 9), np.float64)
         va = np.zeros(count * 8, np.uint8)
         check(self._L.cgrt_photon_events(self._h, C.byref(ph), max_depth, first, count, ev.ctypes.data, va.ctypes.data))
-        idx = np.nonzero(va)[0]
-        return np.concatenate([(first + idx // 8)[:, None].astype(np.float64), ev[idx]], axis=1)
+        return _photon_event_rows(first, ev, va)
 
     def emit_photons(self, first, count, photon_seed=777, light=(0.0, 19.999, 20.0), jitter=2.0, power=700.0, stream=None):
         """cgrt_photon_emit: the built-in emitter's photons [first, first + count) as device tensors (org [n,3], dirs [n,3],
         flux [n,3] float64; keys [n] int64 (bit pattern uint64); draws [n] int32 (bit pattern uint32)) -- what
         PpmSession.add_photon_rays takes.  Fed to a session with the same photon_seed at photons_done == first they are
         add_photons(count) bit for bit.  Asynchronous on torch's current stream (or `stream`)."""
-        import torch
-
-        dev = torch.device("cuda", self.device)
-        n = int(count)
-        org, dirs, flux = (torch.empty((n, 3), dtype=torch.float64, device=dev) for _ in range(3))
-        keys = torch.empty((n,), dtype=torch.int64, device=dev)
-        draws = torch.empty((n,), dtype=torch.int32, device=dev)
-        ph = _capi.Photons(_d3(light), jitter, power, 0.7, 0, 1000001, 0, photon_seed, 0.0, 0)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            check(self._L.cgrt_photon_emit(C.byref(ph), int(first), n, org.data_ptr(), dirs.data_ptr(), flux.data_ptr(),
-                                           keys.data_ptr(), draws.data_ptr(), C.c_void_p(st)))
-        return org, dirs, flux, keys, draws
+        A = self._torch()
+        with A.torch.cuda.device(A.dev):
+            return _emit_photons(A, self._L.cgrt_photon_emit, first, int(count), int(count), photon_seed, light, jitter, power, stream)
 
     def photon_ray_events(self, org, dirs, flux, keys=None, draws=None, max_depth=5, photon_seed=777, first_index=0):
         """Verification probe (cgrt_photon_ray_events): the diffuse hits of caller-supplied photons (numpy arrays: org, dirs,
         flux [n,3]; keys uint64 [n] and draws uint32 [n] or None) as photon_events returns them: [m,10] = photon (first_index +
         position), P, n, flux in slot order."""
-        org, dirs, flux = (np.ascontiguousarray(a, np.float64).reshape(-1, 3) for a in (org, dirs, flux))
-        n = len(org)
-        if len(dirs) != n or len(flux) != n:
-            raise ValueError("photon_ray_events: org, dirs and flux differ in length")
-        if keys is not None:
-            keys = np.ascontiguousarray(keys, np.uint64)
-        if draws is not None:
-            draws = np.ascontiguousarray(draws, np.uint32)
-        for name, a in (("keys", keys), ("draws", draws)):
-            if a is not None and a.shape != (n,):
-                raise ValueError("photon_ray_events: %s must have one entry per photon" % name)
-        pr = _capi.PhotonRays(n, org.ctypes.data, dirs.ctypes.data, flux.ctypes.data, keys.ctypes.data if keys is not None else None,
-                              draws.ctypes.data if draws is not None else None)
-        ev = np.zeros((max(n, 1) * 8, 9), np.float64)
-        va = np.zeros(max(n, 1) * 8, np.uint8)
+        pr = _photon_rays(_buffers.NUMPY, "photon_ray_events", org, dirs, flux, keys, draws, _U64, _U32)
+        ev = np.zeros((max(pr.n, 1) * 8, 9), np.float64)
+        va = np.zeros(max(pr.n, 1) * 8, np.uint8)
         check(self._L.cgrt_photon_ray_events(self._h, C.byref(pr), photon_seed, int(first_index), max_depth, ev.ctypes.data,
                                              va.ctypes.data))
-        idx = np.nonzero(va)[0]
-        return np.concatenate([(first_index + idx // 8)[:, None].astype(np.float64), ev[idx]], axis=1)
+        return _photon_event_rows(first_index, ev, va)
 
     def surface_colors(self, obj, pts):
         """objs[obj]->getSurfaceColor(P) on the device for each row of pts [n,3] (function-level probe)."""
@@ -1257,9 +994,7 @@ class Scene:
         rows = height if rows is None else rows
         flags |= _capi.GRID_HITPOINTS if hitpoints else 0
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, 0, 0, stripe, 0, None, flags)
-        buf = C.create_string_buffer(160)
-        check(self._L.cgrt_trace_grid_variant(self._h, C.byref(cc), C.byref(g), buf, len(buf)))
-        return buf.value.decode()
+        return _variant_name(self._L.cgrt_trace_grid_variant, self._h, C.byref(cc), C.byref(g))
 
     def diffuse_variant(self, width, height, spp=1, camera=None, max_depth=5, rows=None, stripe=None, flags=0):
         """Name of the terminal-diffuse kernel instantiation this grid launches beside kernel_variant's with
@@ -1267,9 +1002,7 @@ class Scene:
         or "" when it launches none."""
         rows = height if rows is None else rows
         cc, g = self._structs(camera, width, height, rows, spp, max_depth, 0, 0, stripe, 0, None, flags)
-        buf = C.create_string_buffer(160)
-        check(self._L.cgrt_trace_grid_diffuse_variant(self._h, C.byref(cc), C.byref(g), buf, len(buf)))
-        return buf.value.decode()
+        return _variant_name(self._L.cgrt_trace_grid_diffuse_variant, self._h, C.byref(cc), C.byref(g))
 
     def intersect_rays(self, obj, org, dirs, keys=None):
         org = np.ascontiguousarray(org, np.float64)
@@ -1287,9 +1020,28 @@ class Scene:
         return hit, ln, nv
 
 
-class PpmSession:
-    """Owns a cgrt_ppm_session (Scene.ppm_session).  Holds a reference to its Scene, which therefore outlives it; closing the
-    Scene closes its sessions first."""
+def _photon_rays(A, what, org, dirs, flux, keys, draws, keys_dtype, draws_dtype):
+    """The cgrt_photon_rays of a caller's photons, checked (or coerced) by the adapter A."""
+    n, org, dirs, flux = A.rays(what, org=org, dirs=dirs, flux=flux)
+    keys = A.per_ray(what, "keys", keys, n, keys_dtype, per="photon")
+    draws = A.per_ray(what, "draws", draws, n, draws_dtype, per="photon")
+    pr = _capi.PhotonRays(n, A.ptr(org), A.ptr(dirs), A.ptr(flux), A.ptr(keys), A.ptr(draws))
+    pr.buffers = org, dirs, flux, keys, draws  # coerced copies live as long as the struct that points into them
+    return pr
+
+
+def _emit_photons(A, fn, first, n, rows, photon_seed, light, jitter, power, stream=None):
+    """The built-in emitter's photons [first, first + n) written by `fn` into buffers of `rows` rows that A makes."""
+    res = A.results("emit_photons", _PHOTON_RAYS, _PHOTON_RAYS, None, rows)
+    ph = _photons(light, jitter, power, photon_seed=photon_seed)
+    check(fn(C.byref(ph), int(first), n, *[A.ptr(x) for x in res.values()], *A.stream(stream)))
+    return tuple(res.values())
+
+
+class _Session(_Closing):
+    """Owns a session handle of the library.  Holds a reference to its Scene, which therefore outlives it; closing the Scene
+    closes its sessions first.  A subclass names the C prefix of its entry points, its info struct and its Hitpoint getter."""
+    _PREFIX = _INFO = _HITPOINTS = None
 
     def __init__(self, scene, h, width, rows, spp):
         self._scene = scene
@@ -1297,23 +1049,61 @@ class PpmSession:
         self._h = h
         self.width, self.rows, self.spp = width, rows, spp
 
+    def _fn(self, name):
+        return getattr(self._L, self._PREFIX + name)
+
     def close(self):
         if getattr(self, "_h", None):
-            self._L.cgrt_ppm_session_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def info(self):
+        inf = self._INFO()
+        check(self._fn("get_info")(self._h, C.byref(inf)))
+        return {f: getattr(inf, f) for f, _ in inf._fields_}
 
-    def __enter__(self):
-        return self
+    @property
+    def photons_done(self):
+        return self.info()["photons_done"]
 
-    def __exit__(self, *exc):
-        self.close()
-        return False
+    def image(self):
+        """[rows, W, 3] float64, row 0 = bottom: ppm_render(nphotons=photons_done)["image"] of a PpmSession,
+        tau / (PI * R2 * photons_done * spp) of an SppmSession."""
+        img = np.zeros((self.rows, self.width, 3), np.float64)
+        check(self._fn("image")(self._h, img.ctypes.data, None))
+        return img
+
+    def rgb8(self):
+        """[rows, W, 3] uint8, top row first (contiguous rows only): ppm_render(..., want_rgb8=True)["rgb8"]."""
+        out = np.zeros((self.rows, self.width, 3), np.uint8)
+        check(self._fn("image")(self._h, None, out.ctypes.data))
+        return out
+
+    def image_tensor(self, out=None, rgb8_out=None, stream=None):
+        """The image as a float64 [rows, W, 3] torch tensor on the scene's device, gathered on torch's current stream (or
+        `stream`) without a host copy.  rgb8_out (uint8 [rows, W, 3], optional) receives the tone-mapped bytes in the same
+        pass.  Returns `out`."""
+        A = self._scene._torch()
+        torch = A.torch
+        if out is None:
+            out = torch.empty((self.rows, self.width, 3), dtype=torch.float64, device=A.dev)
+        assert out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (self.rows, self.width, 3)
+        if rgb8_out is not None:
+            assert rgb8_out.is_contiguous() and rgb8_out.dtype == torch.uint8 and rgb8_out.numel() == self.rows * self.width * 3
+        check(self._fn("image_device")(self._h, out.data_ptr(), A.ptr(rgb8_out), *A.stream(stream)))
+        return out
+
+    def _hitpoint_dump(self):
+        """[n, 16] float64: the records of the session's Hitpoint table."""
+        n = self.info()["hp_count"]
+        hp = np.zeros((max(n, 1), 16), np.float64)
+        check(self._fn(self._HITPOINTS)(self._h, hp.ctypes.data, n, C.byref(C.c_uint64(0))))
+        return hp[:n]
+
+
+class PpmSession(_Session):
+    """Owns a cgrt_ppm_session (Scene.ppm_session)."""
+    _PREFIX, _INFO, _HITPOINTS = "cgrt_ppm_session_", _capi.PpmSessionInfo, "hitpoints"
 
     def add_photons(self, n):
         """Traces photons [photons_done, photons_done + n) and applies them; returns when they are applied."""
@@ -1327,103 +1117,26 @@ class PpmSession:
         the indices [photons_done, photons_done + n) -- a photon with dirs == 0 goes nowhere and still counts -- and the gather
         divides by photons_done.  Waits for torch's current stream (the tensors' producer), returns when the photons are
         applied; Scene.emit_photons makes the built-in light's photons in this form."""
-        import torch
-
-        dev = torch.device("cuda", self._scene.device)
-        for name, t in (("org", org), ("dirs", dirs), ("flux", flux)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == 3 and
-                    t.is_contiguous() and t.device == dev):
-                raise ValueError("add_photon_rays: %s must be a contiguous float64 [n,3] tensor on %s" % (name, dev))
-        n = org.shape[0]
-        if dirs.shape[0] != n or flux.shape[0] != n:
-            raise ValueError("add_photon_rays: org, dirs and flux differ in length")
-        for name, t, dt in (("keys", keys, torch.int64), ("draws", draws, torch.int32)):
-            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == (n,) and
-                                      t.is_contiguous() and t.device == dev):
-                raise ValueError("add_photon_rays: %s must be a contiguous %s [n] tensor on %s" % (name, dt, dev))
-        if n == 0:
+        A = self._scene._torch()
+        pr = _photon_rays(A, "add_photon_rays", org, dirs, flux, keys, draws, ("torch.int64",), ("torch.int32",))
+        if pr.n == 0:
             return self
-        pr = _capi.PhotonRays(n, org.data_ptr(), dirs.data_ptr(), flux.data_ptr(), keys.data_ptr() if keys is not None else None,
-                              draws.data_ptr() if draws is not None else None)
-        torch.cuda.current_stream(dev).synchronize()  # the session traces on streams of its own
+        A.torch.cuda.current_stream(A.dev).synchronize()  # the session traces on streams of its own
         check(self._L.cgrt_ppm_session_add_photon_rays(self._h, C.byref(pr)))
         return self
 
-    def info(self):
-        inf = _capi.PpmSessionInfo()
-        check(self._L.cgrt_ppm_session_get_info(self._h, C.byref(inf)))
-        return {f: getattr(inf, f) for f, _ in inf._fields_}
-
-    @property
-    def photons_done(self):
-        return self.info()["photons_done"]
-
-    def image(self):
-        """[rows, W, 3] float64, row 0 = bottom: ppm_render(nphotons=photons_done)["image"]."""
-        img = np.zeros((self.rows, self.width, 3), np.float64)
-        check(self._L.cgrt_ppm_session_image(self._h, img.ctypes.data, None))
-        return img
-
-    def rgb8(self):
-        """[rows, W, 3] uint8, top row first (contiguous rows only): ppm_render(..., want_rgb8=True)["rgb8"]."""
-        out = np.zeros((self.rows, self.width, 3), np.uint8)
-        check(self._L.cgrt_ppm_session_image(self._h, None, out.ctypes.data))
-        return out
-
-    def image_tensor(self, out=None, rgb8_out=None, stream=None):
-        """The image as a float64 [rows, W, 3] torch tensor on the scene's device, gathered on torch's current stream (or
-        `stream`) without a host copy.  rgb8_out (uint8 [rows, W, 3], optional) receives the tone-mapped bytes in the same
-        pass.  Returns `out`."""
-        import torch
-
-        dev = torch.device("cuda", self._scene.device)
-        if out is None:
-            out = torch.empty((self.rows, self.width, 3), dtype=torch.float64, device=dev)
-        assert out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (self.rows, self.width, 3)
-        if rgb8_out is not None:
-            assert rgb8_out.is_contiguous() and rgb8_out.dtype == torch.uint8 and rgb8_out.numel() == self.rows * self.width * 3
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        check(self._L.cgrt_ppm_session_image_device(self._h, out.data_ptr(),
-                                                    rgb8_out.data_ptr() if rgb8_out is not None else None, C.c_void_p(st)))
-        return out
-
     def hitpoints(self):
         """[n, 16] of the current state: ppm_render(want_hitpoints=True)["hp"] at photons_done photons."""
-        n = self.info()["hp_count"]
-        hp = np.zeros((max(n, 1), 16), np.float64)
-        cnt = C.c_uint64(0)
-        check(self._L.cgrt_ppm_session_hitpoints(self._h, hp.ctypes.data, n, C.byref(cnt)))
-        return hp[:n]
+        return self._hitpoint_dump()
 
 
-class SppmSession:
-    """Owns a cgrt_sppm_session (Scene.sppm_session).  Holds a reference to its Scene, which therefore outlives it; closing the
-    Scene closes its sessions first."""
+class SppmSession(_Session):
+    """Owns a cgrt_sppm_session (Scene.sppm_session)."""
+    _PREFIX, _INFO, _HITPOINTS = "cgrt_sppm_session_", _capi.SppmSessionInfo, "last_hitpoints"
 
     def __init__(self, scene, h, width, rows, spp, grid):
-        self._scene = scene
-        self._L = scene._L
-        self._h = h
-        self.width, self.rows, self.spp = width, rows, spp
+        super().__init__(scene, h, width, rows, spp)
         self._grid = grid  # what add_passes renders with
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.cgrt_sppm_session_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
     def add_passes(self, n, photons_per_pass, flags=0):
         """n passes of the session's camera, each with `photons_per_pass` fresh photons: pass k (counted over the session's
@@ -1439,57 +1152,16 @@ class SppmSession:
         """One pass over caller-supplied rays (cgrt_sppm_session_pass_rays): org, dirs, keys as for trace_rays; ray i gathers
         into texel pixel[i] (int64 [n] on the scene's device; negative: not traced), or i % (width * rows) without `pixel` --
         camera_rays' order.  max_depth is the eye depth.  Waits for torch's current stream, returns when the pass is applied."""
-        import torch
-
         n = self._scene._ray_tensors("add_pass_rays", org, dirs, keys, pixel)
-        r = _capi.Rays(n, org.data_ptr(), dirs.data_ptr(), keys.data_ptr() if keys is not None else None, first_index, seed,
-                       max_depth, 0)
-        torch.cuda.current_stream(org.device).synchronize()  # the pass runs on the null stream
-        check(self._L.cgrt_sppm_session_pass_rays(self._h, C.byref(r), pixel.data_ptr() if pixel is not None else None,
-                                                  int(nphotons)))
+        A = self._scene._torch()
+        r = self._scene._rays(A, n, org, dirs, keys, first_index, seed, max_depth, 0)
+        A.torch.cuda.current_stream(org.device).synchronize()  # the pass runs on the null stream
+        check(self._L.cgrt_sppm_session_pass_rays(self._h, C.byref(r), A.ptr(pixel), int(nphotons)))
         return self
-
-    def info(self):
-        inf = _capi.SppmSessionInfo()
-        check(self._L.cgrt_sppm_session_get_info(self._h, C.byref(inf)))
-        return {f: getattr(inf, f) for f, _ in inf._fields_}
 
     @property
     def passes(self):
         return self.info()["passes"]
-
-    @property
-    def photons_done(self):
-        return self.info()["photons_done"]
-
-    def image(self):
-        """[rows, W, 3] float64, row 0 = bottom: tau / (PI * R2 * photons_done * spp)."""
-        img = np.zeros((self.rows, self.width, 3), np.float64)
-        check(self._L.cgrt_sppm_session_image(self._h, img.ctypes.data, None))
-        return img
-
-    def rgb8(self):
-        """[rows, W, 3] uint8, top row first (contiguous rows only)."""
-        out = np.zeros((self.rows, self.width, 3), np.uint8)
-        check(self._L.cgrt_sppm_session_image(self._h, None, out.ctypes.data))
-        return out
-
-    def image_tensor(self, out=None, rgb8_out=None, stream=None):
-        """The image as a float64 [rows, W, 3] torch tensor on the scene's device, written on torch's current stream (or
-        `stream`) without a host copy.  rgb8_out (uint8 [rows, W, 3], optional) receives the tone-mapped bytes in the same
-        pass.  Returns `out`."""
-        import torch
-
-        dev = torch.device("cuda", self._scene.device)
-        if out is None:
-            out = torch.empty((self.rows, self.width, 3), dtype=torch.float64, device=dev)
-        assert out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (self.rows, self.width, 3)
-        if rgb8_out is not None:
-            assert rgb8_out.is_contiguous() and rgb8_out.dtype == torch.uint8 and rgb8_out.numel() == self.rows * self.width * 3
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        check(self._L.cgrt_sppm_session_image_device(self._h, out.data_ptr(),
-                                                     rgb8_out.data_ptr() if rgb8_out is not None else None, C.c_void_p(st)))
-        return out
 
     def pixels(self):
         """[rows * W, 8] float64: per texel {N, R2, tau[3], M_p of the last pass, Hitpoints of the last pass, 0}."""
@@ -1500,11 +1172,7 @@ class SppmSession:
     def last_hitpoints(self):
         """[n, 16]: the last pass's table in PpmSession.hitpoints()' layout and order, flux = Phi_h, r2 = the radius the pass
         searched with, n = M_h."""
-        n = self.info()["hp_count"]
-        hp = np.zeros((max(n, 1), 16), np.float64)
-        cnt = C.c_uint64(0)
-        check(self._L.cgrt_sppm_session_last_hitpoints(self._h, hp.ctypes.data, n, C.byref(cnt)))
-        return hp[:n]
+        return self._hitpoint_dump()
 
 
 def camera_rays_host(width, height, spp=1, camera=None, seed=12345, rows=None, row_offset=0, stripe=None, sample_offset=0):
@@ -1515,10 +1183,7 @@ def camera_rays_host(width, height, spp=1, camera=None, seed=12345, rows=None, r
     cc, posed = _ccamera(camera)
     s_rows, s_rank, s_n = stripe if stripe else (0, 0, 1)
     g = _CGrid(width, height, rows, row_offset, s_rows, s_rank, s_n, spp, sample_offset, spp, 1, posed, seed)
-    n = spp * rows * width
-    org = np.zeros((n, 3), np.float64)
-    dirs = np.zeros((n, 3), np.float64)
-    keys = np.zeros(n, np.uint64)
+    org, dirs, keys = _buffers.NUMPY.results("camera_rays_host", _CAMERA_RAYS, _CAMERA_RAYS, None, spp * rows * width).values()
     check(_capi.lib().cgrt_camera_rays_host(C.byref(cc), C.byref(g), org.ctypes.data, dirs.ctypes.data, keys.ctypes.data))
     return org, dirs, keys
 
@@ -1527,14 +1192,8 @@ def emit_photons_host(first, count, photon_seed=777, light=(0.0, 19.999, 20.0), 
     """cgrt_photon_emit_host: the built-in emitter's photons [first, first + count) evaluated on the host -- no GPU and no scene
     needed.  Returns numpy arrays (org [n,3], dirs [n,3], flux [n,3] float64, keys [n] uint64, draws [n] uint32): the same bits
     Scene.emit_photons makes on the device."""
-    n = int(count)
-    org, dirs, flux = (np.zeros((max(n, 0), 3), np.float64) for _ in range(3))
-    keys = np.zeros(max(n, 0), np.uint64)
-    draws = np.zeros(max(n, 0), np.uint32)
-    ph = _capi.Photons(_d3(light), jitter, power, 0.7, 0, 1000001, 0, photon_seed, 0.0, 0)
-    check(_capi.lib().cgrt_photon_emit_host(C.byref(ph), int(first), n, org.ctypes.data, dirs.ctypes.data, flux.ctypes.data,
-                                            keys.ctypes.data, draws.ctypes.data))
-    return org, dirs, flux, keys, draws
+    return _emit_photons(_buffers.NUMPY, _capi.lib().cgrt_photon_emit_host, first, int(count), max(int(count), 0), photon_seed, light, jitter,
+                         power)
 
 
 def render(objs, width=1024, height=768, num_of_samples=1, camera=None, max_depth=5, seed=12345, device=0):
