@@ -4,7 +4,6 @@ compiled reference's); the order contract, the defaults, the per-record texels a
 session; and eye depths past 5 and rays with more than 16 Hitpoints are checked end to end against a numpy replay of the
 reference's photon loop over the oracle's photon hits, whose table is built with Python's own comparison of the paths' bit
 strings."""
-import math
 import os
 import subprocess
 import sys
@@ -14,7 +13,8 @@ import pytest
 
 import scenes
 from backends import BackendScene
-from test_gpu_ppm_rays import EPS, LOOKAT_PHOTONS, PI_REF, _dot, _ray_to_ps
+from ppm_design import _bits, replay_expected
+from test_gpu_ppm_rays import LOOKAT_PHOTONS, _ray_to_ps
 from test_gpu_ppm_session import _canon, _feed
 
 pytestmark = pytest.mark.gpu
@@ -28,7 +28,6 @@ ORDER_CASE = "c2_dof_32x24"
 DEEP_W, DEEP_H, DEEP_EYE = 24, 18, 12  # test 8's rays and eye depth
 DEEP_PHOTONS = LOOKAT_PHOTONS         # at least half of test 8's Hitpoints receive a photon (asserted there)
 MANY_DEPTH = 24                       # test 9's eye depth
-HASHSIZE = 1000001
 
 
 def _dev(sc):
@@ -227,66 +226,7 @@ def test_mixed_photon_sources(gpu_ready):
     assert np.array_equal(img, b["img"]) and np.array_equal(hp, b["hp"])
 
 
-# ---- the replay: main.cpp:103-125 and 252-258 over arbitrary records -------------------------------------------------
-def _hash_np(ix, iy, iz):  # hash.h:35-37, wrapping 32-bit products
-    m = 0xFFFFFFFF
-    return ((((ix & m) * 73856093) & m) ^ (((iy & m) * 19349663) & m) ^ (((iz & m) * 83492791) & m)) % HASHSIZE
-
-
-def _coord_np(P, cl):  # hash.h:38-42
-    return [np.floor((P[:, k] - off) / cl).astype(np.int64) for k, off in enumerate((-35.0, -35.0, -15.0))]
-
-
-def _bits(path):
-    """the path's bits behind its leading 1 as text: Python compares strings lexicographically, a prefix first"""
-    return bin(int(path))[3:]
-
-
-def replay_expected(ray, path, hp9, texel, events, npix, spp, nphotons, alpha=0.7):
-    """From the records and the oracle's photon events alone: the table in the order contract (bucket of pos, texel, ray, path
-    as a bit string, input position), each record's rank within its ray, the replay of main.cpp:103-125 over the events in
-    photon order, and the gathered image of main.cpp:252-258.  Returns (table [n,16] as hitpoints(), image [npix,3])."""
-    r0 = 200.0 / 768
-    cl = 70.0 / math.ceil(70.0 / r0)  # hash.h:25-26
-    n = len(ray)
-    bucket = _hash_np(*_coord_np(hp9[:, 3:6], cl)) if n else np.zeros(0, np.int64)
-    order = sorted(range(n), key=lambda i: (int(bucket[i]), int(texel[i]), int(ray[i]), _bits(path[i]), i))
-    rank, seen = {}, {}
-    for i in sorted(range(n), key=lambda i: (int(ray[i]), _bits(path[i]), i)):
-        rank[i] = seen.get(int(ray[i]), 0)
-        seen[int(ray[i])] = rank[i] + 1
-    hps = [dict(f=[float(v) for v in hp9[i, 0:3]], pos=[float(v) for v in hp9[i, 3:6]], n=[float(v) for v in hp9[i, 6:9]],
-                flux=[0.0, 0.0, 0.0], r2=r0 * r0, cnt=0, i=i) for i in order]
-    buckets = {}
-    for h in hps:
-        buckets.setdefault(int(bucket[h["i"]]), []).append(h)
-    # the 27 buckets of every event; only events that meet an occupied bucket can change anything
-    ix, iy, iz = _coord_np(events[:, 1:4], cl)
-    cells = np.stack([_hash_np(ix - 1 + dx, iy - 1 + dy, iz - 1 + dz) for dx in range(3) for dy in range(3) for dz in range(3)], axis=1)
-    live = np.isin(cells, np.fromiter(buckets.keys(), np.int64, len(buckets)))
-    for e in np.nonzero(live.any(axis=1))[0]:
-        ev = events[e]
-        Pe, ne, fe = [float(v) for v in ev[1:4]], [float(v) for v in ev[4:7]], [float(v) for v in ev[7:10]]
-        for c in np.nonzero(live[e])[0]:  # in the reference's dx, dy, dz order; a bucket met twice is walked twice
-            for h in buckets[int(cells[e, c])]:
-                dd = [h["pos"][0] - Pe[0], h["pos"][1] - Pe[1], h["pos"][2] - Pe[2]]
-                if _dot(h["n"], ne) > EPS and _dot(dd, dd) <= h["r2"]:  # main.cpp:116
-                    g = (h["cnt"] * alpha + alpha) / (h["cnt"] * alpha + 1.0)  # main.cpp:119
-                    h["r2"] *= g
-                    h["cnt"] += 1
-                    h["flux"] = [(h["flux"][k] + (h["f"][k] * fe[k]) * (1.0 / PI_REF)) * g for k in range(3)]  # main.cpp:122
-    table = np.zeros((n, 16))
-    image = np.zeros((npix, 3))
-    norm = float(nphotons) * spp
-    for k, h in enumerate(hps):
-        i = h["i"]
-        table[k] = [int(ray[i]), rank[i]] + h["f"] + h["pos"] + h["n"] + h["flux"] + [h["r2"], h["cnt"]]
-        s = 1.0 / (PI_REF * h["r2"] * norm)  # main.cpp:256
-        for c in range(3):
-            image[int(texel[i]), c] += h["flux"][c] * s
-    return table, image
-
-
+# ---- the replay (main.cpp:103-125 and 252-258 over arbitrary records) is tests/ppm_design.py's replay_expected ----------------
 _EVENTS = {}
 
 
@@ -317,8 +257,8 @@ def _deep(orc):
         with sc.ppm_session_hitpoints(wf["hp9"], wf["hp_ray"], wf["hp_path"], width=W, rows=H, spp=1, max_depth=5, batch=30000) as ses:
             ses.add_photons(DEEP_PHOTONS)
             img, hp, inf = ses.image(), ses.hitpoints(), ses.info()
-    table, image = replay_expected(rec["ray"], rec["path"], rec["hp9"], rec["ray"] % (W * H), _c2_events(orc, DEEP_PHOTONS), W * H, 1,
-                                   DEEP_PHOTONS)
+    table, image, _ = replay_expected(rec["ray"], rec["path"], rec["hp9"], rec["ray"] % (W * H), _c2_events(orc, DEEP_PHOTONS), W * H, 1,
+                                      DEEP_PHOTONS)
     _DEEP.update(rec=rec, n5=n5, img=img, hp=hp, inf=inf, table=table, image=image)
     return _DEEP
 
@@ -377,8 +317,8 @@ def test_more_than_16_hitpoints_on_one_ray(gpu_ready, orc):
         row = mine[mine[:, 1] == k]
         assert len(row) == 1 and np.array_equal(row[0, 2:11], rec["hp9"][i])
     assert [_bits(p) for p in rec["path"][rec["ray"] == big]] == sorted(_bits(p) for p in rec["path"][rec["ray"] == big])
-    table, image = replay_expected(rec["ray"][sh], rec["path"][sh], rec["hp9"][sh], rec["ray"][sh] % (W * H),
-                                   _c2_events(orc, DEEP_PHOTONS), W * H, 1, DEEP_PHOTONS)
+    table, image, _ = replay_expected(rec["ray"][sh], rec["path"][sh], rec["hp9"][sh], rec["ray"][sh] % (W * H),
+                                      _c2_events(orc, DEEP_PHOTONS), W * H, 1, DEEP_PHOTONS)
     assert hp.shape == table.shape and np.array_equal(hp, table)
     assert np.array_equal(img.reshape(-1, 3), image) and (table[:, 15] > 0).any()
 
