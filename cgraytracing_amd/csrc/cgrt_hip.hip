@@ -195,6 +195,9 @@ struct cgrt_scene {
     // cgrt_wavefront_rays: ray queues and parked Hitpoints, the sort's temporary storage, and what the last call did
     mutable GrowBuf wavefront_work, wavefront_sort;
     mutable WavefrontLast wavefront_last;
+    // the eye kernels the last eye pass on the handle launched (launch_eye, primary_walk), probes included: host state, cleared
+    // by every entry point that runs an eye pass, read by cgrt_scene_last_eye_launches
+    mutable EyeLaunchLog eye_log;
 };
 
 template <class T>
@@ -786,14 +789,17 @@ static int check_eye(const EyeLaunch &L, int device) {
     if (!e) return fail(CGRT_ERR_UNSUPPORTED, std::string(L.what()) + ": no kernel built for this variant");
     return lds_check(reinterpret_cast<const void *>(e->grid), L.lds, device, L.what());
 }
-// Launches the plan's kernel: trace_grid_sched_kernel when `sched`, else trace_grid_kernel
-static int launch_eye(const EyeLaunch &L, bool sched, int device, const GridParams &g, dim3 gd, hipStream_t st, float *rgb,
+// Launches the plan's kernel on the scene's device: trace_grid_sched_kernel when `sched`, else trace_grid_kernel.  A launch that
+// went out is noted in the handle's eye_log.
+static int launch_eye(const EyeLaunch &L, bool sched, const cgrt_scene *s, const GridParams &g, dim3 gd, hipStream_t st, float *rgb,
                       uint32_t *nhit, unsigned long long *cnt, HitpointSink sink = HitpointSink{nullptr, nullptr, 0}) {
     const dim3 block((unsigned)L.k.nt);
     const EyeKernels *e = eye_kernels(L.k);
-    if (e && sched && e->sched) return launch_checked(e->sched, L.what(), device, gd, block, L.lds, st, L.dev, g, rgb, nhit, cnt);
-    if (e && !sched) return launch_checked(e->grid, L.what(), device, gd, block, L.lds, st, L.dev, g, rgb, nhit, cnt, sink);
-    return fail(CGRT_ERR_UNSUPPORTED, std::string(L.what()) + ": no kernel built for this variant");
+    if (!e || (sched && !e->sched)) return fail(CGRT_ERR_UNSUPPORTED, std::string(L.what()) + ": no kernel built for this variant");
+    const int rc = sched ? launch_checked(e->sched, L.what(), s->device, gd, block, L.lds, st, L.dev, g, rgb, nhit, cnt)
+                         : launch_checked(e->grid, L.what(), s->device, gd, block, L.lds, st, L.dev, g, rgb, nhit, cnt, sink);
+    if (rc == CGRT_OK) s->eye_log.add(sched ? kEyeSched : kEyeGrid, L.k);
+    return rc;
 }
 
 // A grid's rows, samples and stripes and the camera's lens: what an eye pass reads (traced: spp_total and max_depth too) and
@@ -878,7 +884,7 @@ static int probe_and_plan(const cgrt_scene *s, const EyeLaunch &L, const EyeKnob
     gp.probe = 1;
     gp.cost = at.cost.in<uint32_t>(scratch);
     gp.light = light;  // light tiles are not probed (plan_kernel counts them as zero); their cost entries stay unwritten
-    int rc = launch_eye(L, false, s->device, gp, dim3((unsigned)p.tile_blocks), st, nullptr, nullptr, nullptr);
+    int rc = launch_eye(L, false, s, gp, dim3((unsigned)p.tile_blocks), st, nullptr, nullptr, nullptr);
     if (rc) return rc;
     if (light) {
         // The light tiles: the variant without tree / Bezier / pending-ray code on the second stream, beside everything that
@@ -891,7 +897,7 @@ static int probe_and_plan(const cgrt_scene *s, const EyeLaunch &L, const EyeKnob
         gl.xcd_tiles = 0;
         HIP_TRY(hipEventRecord(s->ev_fork, st));
         HIP_TRY(hipStreamWaitEvent(s->aux_stream, s->ev_fork, 0));
-        if ((rc = launch_eye(light_launch(s->dev, L.k.dof, kn), false, s->device, gl,
+        if ((rc = launch_eye(light_launch(s->dev, L.k.dof, kn), false, s, gl,
                              dim3((unsigned)tile_grid_blocks(g.W, g.rows, false)), s->aux_stream, rgb, nhit, cnt)))
             return rc;
         HIP_TRY(hipEventRecord(s->ev_join, s->aux_stream));
@@ -935,7 +941,7 @@ static int relay_cost_start(const cgrt_scene *s, const EyeLaunch &L, const Frame
         // whatever the launch's offset, and the table is mostly being written beside it; the counts are the same either way)
         gp.lens_table = nullptr;
         gp.lens_table_cap = gp.lens_table_spp = 0;
-        if (int rc = launch_eye(start_twin(L), false, s->device, gp, dim3((unsigned)p.grid_dim), st, nullptr, nullptr, nullptr)) return rc;
+        if (int rc = launch_eye(start_twin(L), false, s, gp, dim3((unsigned)p.grid_dim), st, nullptr, nullptr, nullptr)) return rc;
     }
     return cost_start_rank(s->order, p, c, g, st);
 }
@@ -952,8 +958,14 @@ static int primary_walk(const cgrt_scene *s, const EyeLaunch &L, const GridParam
     pw.pad_ = 0;
     pw.counters = cnt;
     const size_t staged = (size_t)(pw.finish ? s->dev.n_objs : pw.obj + 1);  // all objects when it finishes units
-    return launch_checked(L.k.dof ? &primary_walk_kernel<true> : &primary_walk_kernel<false>, "primary_walk_kernel", s->device,
-                          dim3((unsigned)s->n_cu * 4), dim3(kThreads), primary_walk_lds(staged), st, s->dev, g, pw);
+    const int rc = launch_checked(L.k.dof ? &primary_walk_kernel<true> : &primary_walk_kernel<false>, "primary_walk_kernel", s->device,
+                                  dim3((unsigned)s->n_cu * 4), dim3(kThreads), primary_walk_lds(staged), st, s->dev, g, pw);
+    if (rc == CGRT_OK) {
+        EyeFlags walk{};  // (its one template flag)
+        walk.dof = L.k.dof;
+        s->eye_log.add(kEyePrimaryWalk, walk);
+    }
+    return rc;
 }
 
 // development aid: CGRT_TIMELINE_FILE=path makes a launch synchronous and dumps, per workgroup, when and where it ran
@@ -1012,6 +1024,7 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
     // launch on the scene's device whatever the caller's current device is (one host thread may drive several GPUs)
     ON_DEVICE(s->device);
     const EyeKnobs kn = eye_knobs();
+    s->eye_log.clear();
     const EyeLaunch L0 = eye_launch(s, cam, grid, kn, false);
     if (L0.k.pose && (rc = check_eye(L0, s->device))) return rc;  // (not every form has a POSE kernel: refused before anything is launched)
     const FrameInputs in = frame_inputs(s, cam, grid, L0, kn);
@@ -1052,7 +1065,7 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
         if (L.k.pose) hipLaunchKernelGGL(pixel_const_kernel<true>, dim3((unsigned)p.kmax), dim3(64), 0, st, g);
         else hipLaunchKernelGGL(pixel_const_kernel<false>, dim3((unsigned)p.kmax), dim3(64), 0, st, g);
         if (g.prim_len && (rc = primary_walk(s, L, g, st, cnt))) return rc;
-        if ((rc = launch_eye(L, true, s->device, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) return rc;
+        if ((rc = launch_eye(L, true, s, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) return rc;
     } else if (p.order.class3 == TileOrderPlan::SecondLaunch) {
         // The list's class 0-2 entries by this launch, its class-3 entries by the terminal-diffuse variant on the second stream,
         // started behind it (fork / join events, lowest priority: the arrangement of the light-tile launch).  Where class 3
@@ -1063,15 +1076,15 @@ int cgrt_trace_grid(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid
         g.tile_order = kOrderFull;
         gd.tile_order = kOrderDiffuse;
         HIP_TRY(hipEventRecord(s->ev_fork, st));
-        if ((rc = launch_eye(L, false, s->device, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) return rc;
+        if ((rc = launch_eye(L, false, s, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) return rc;
         HIP_TRY(hipStreamWaitEvent(s->aux_stream, s->ev_fork, 0));
-        if ((rc = launch_eye(DL, false, s->device, gd, dim3((unsigned)n_blocks), s->aux_stream, rgb, nhit, cnt))) return rc;
+        if ((rc = launch_eye(DL, false, s, gd, dim3((unsigned)n_blocks), s->aux_stream, rgb, nhit, cnt))) return rc;
         HIP_TRY(hipEventRecord(s->ev_join, s->aux_stream));
     } else {
         // The pair variant in tile order: the list's class-3 workgroups take the terminal-diffuse body inside this launch
         if (p.order.class3 == TileOrderPlan::InKernel) g.tile_order = kOrderAllDiffuse;
         // (a launch with a start table runs the variant that reads it: the twin of L's, the kernel its probe ran)
-        if ((rc = launch_eye(g.relay_start_at ? start_twin(L) : L, false, s->device, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) return rc;
+        if ((rc = launch_eye(g.relay_start_at ? start_twin(L) : L, false, s, g, dim3((unsigned)n_blocks), st, rgb, nhit, cnt))) return rc;
     }
     if (p.chunks > 1)
         hipLaunchKernelGGL(finalize_chunks_kernel, dim3((unsigned)(((size_t)g.rows * g.W + 255) / 256)), dim3(256), 0, st, g, rgb, nhit);
@@ -1162,6 +1175,14 @@ int cgrt_scene_last_relay_boost(const cgrt_scene *s, int64_t *promoted, int32_t 
     return last_relay_boost(s->order, s->relay, promoted, k_boost, boost_cap, cost_sum, num, den, wg_slots, bslot, slot_cap);
 }
 
+int cgrt_scene_last_eye_launches(const cgrt_scene *s, int32_t *rows, int64_t cap, int64_t *n) {
+    NEED_COMMITTED(s, n && (cap <= 0 || rows));
+    const EyeLaunchLog &log = s->eye_log;
+    *n = log.n;
+    for (int i = 0; i < log.n && i < cap; i++) log.row(i, rows + (size_t)i * kEyeLogCols);
+    return log.overflow ? fail(CGRT_ERR_LIMIT, "eye pass: more launches than the handle's record holds") : CGRT_OK;
+}
+
 int cgrt_trace_grid_diffuse_variant(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, char *name, size_t cap) {
     int rc = check_grid(s, cam, grid);
     if (rc) return rc;
@@ -1219,6 +1240,7 @@ static int hitpoints_to_host(int rc, double *d_rec, uint64_t n, double *hp10, ui
 // *d_rec_out is hipMalloc'ed here (caller frees) unless cap == 0.
 static int hitpoints_device(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, uint64_t cap,
                             double **d_rec_out, uint64_t *count) {
+    s->eye_log.clear();
     GridParams g = grid_params(cam, grid);  // capture keeps one workgroup per tile
     g.accumulate = 0;
     g.xcd_tiles = (s->dev.has_mesh && !s->dev.has_bezier) ? 1 : 0;
@@ -1232,7 +1254,7 @@ static int hitpoints_device(const cgrt_scene *s, const cgrt_camera *cam, const c
     unsigned long long *d_cnt = b_cnt.as<unsigned long long>();
     HIP_TRY(hipMemset(d_cnt, 0, sizeof(unsigned long long)));
     const EyeLaunch L = eye_launch(s, cam, grid, eye_knobs(), true);
-    int rc = launch_eye(L, false, s->device, g, dim3((unsigned)tile_grid_blocks(g.W, g.rows, g.xcd_tiles != 0)), 0, d_rgb, nullptr,
+    int rc = launch_eye(L, false, s, g, dim3((unsigned)tile_grid_blocks(g.W, g.rows, g.xcd_tiles != 0)), 0, d_rgb, nullptr,
                         nullptr, HitpointSink{d_rec, d_cnt, (unsigned long long)cap});
     if (rc) return rc;
     return capture_finish("hitpoint kernel: ", b_rec, b_cnt, cap, d_rec_out, count);

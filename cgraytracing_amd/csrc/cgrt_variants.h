@@ -108,6 +108,32 @@ static constexpr EyeFlags posed_flags(EyeFlags f) {
     return f;
 }
 
+// The eye kernels one eye pass launched, in launch order, probes included: a fixed array (a pass issues at most six: probe, light
+// tiles, primary walk, the frame, its diffuse launch, the relay's cost probe), nothing allocated on the launch path
+enum EyeKernelKind { kEyeGrid = 0, kEyeSched = 1, kEyePrimaryWalk = 2 };  // trace_grid_kernel, trace_grid_sched_kernel, primary_walk_kernel
+static constexpr int kEyeLogCols = 16;  // a row as cgrt_scene_last_eye_launches hands it out: the kind, the lists' 14 columns, POSE
+struct EyeLaunchLog {
+    static constexpr int kCap = 16;
+    struct Entry {
+        int kind;
+        EyeFlags k;
+    } e[kCap];
+    int n = 0;
+    bool overflow = false;
+    void clear() { n = 0, overflow = false; }
+    void add(int kind, const EyeFlags &k) {
+        if (n < kCap) e[n++] = Entry{kind, k};
+        else overflow = true;
+    }
+    // entry i as kind, TREES BEZ DOF GLASS SPH STATS HPS NT SPILL HFONLY DIFF PAIR START LTAB, POSE
+    void row(int i, int32_t out[kEyeLogCols]) const {
+        const EyeFlags &k = e[i].k;
+        const int32_t v[kEyeLogCols] = {e[i].kind, k.trees, k.bez,  k.dof,  k.glass, k.sph,   k.stats, k.hps,
+                                        k.nt,      k.spill, k.hfonly, k.diff, k.pair,  k.start, k.ltab,  k.pose};
+        for (int c = 0; c < kEyeLogCols; c++) out[c] = v[c];
+    }
+};
+
 // ---- the eye pass's choice of kernel ----
 enum class EyeForm { Image, Sched, SpillSph, SpillGen, Capture, Light, LightHF, Diffuse };
 // What the choice reads of a committed scene (DeviceScene's traits and the handle's order_ok), and the choice

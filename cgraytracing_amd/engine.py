@@ -704,6 +704,15 @@ class Scene(_Closing):
         check(self._L.cgrt_inside_probe(self._h, _capi.PROBE_INSIDE_LOOP, rays.ctypes.data, rays.shape[0], out.ctypes.data))
         return out
 
+    def last_eye_launches(self):
+        """The eye kernels this scene's last eye pass launched (cgrt_scene_last_eye_launches; host state, no synchronisation), in
+        launch order, probes included: a list of tuples (kind, TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, SPILL, HFONLY, DIFF,
+        PAIR, START, LTAB, POSE); kind 0 trace_grid_kernel, 1 trace_grid_sched_kernel, 2 primary_walk_kernel (DOF only)."""
+        n = C.c_int64()
+        rows = np.zeros((16, 16), np.int32)
+        check(self._L.cgrt_scene_last_eye_launches(self._h, rows.ctypes.data, rows.shape[0], C.byref(n)))
+        return [tuple(int(v) for v in rows[i]) for i in range(n.value)]
+
     def last_tile_order_reused(self):
         """True when this scene's last trace_grid / trace_grid_host ran no ordering kernel because the handle still held the
         order of the same camera and frame geometry (cgrt_scene_last_tile_order_reused)."""

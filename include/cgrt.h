@@ -1057,6 +1057,13 @@ int cgrt_scene_last_lens_table(const cgrt_scene *s, int64_t *entries, int64_t *c
  * that starts inside it can hit first (itself, and every sphere not provably disjoint from it; all bits: the unchanged loop),
  * rin2[k] = the squared radius below which an origin counts as inside (0: none does). */
 int cgrt_scene_inside_spheres(const cgrt_scene *s, int32_t *index, uint32_t *mask, double *rin2, int32_t cap, int32_t *n);
+/* The eye kernels the LAST eye pass on the handle launched -- cgrt_trace_grid, cgrt_trace_grid_hitpoints, or the eye pass of a PPM
+ * or SPPM session over a grid --, in launch order, probes included (host state: no launch, no synchronisation; at most 16 are
+ * kept, CGRT_ERR_LIMIT beyond).  *n = the launches, and for i < min(*n, cap) rows[16 i ..] = the kind -- 0 trace_grid_kernel,
+ * 1 trace_grid_sched_kernel, 2 primary_walk_kernel --, the instantiation's template flags in the order of the list of compiled
+ * instantiations (cgrt_variants.h): TREES BEZ DOF GLASS SPH STATS HPS NT SPILL HFONLY DIFF PAIR START LTAB, then POSE.  A primary
+ * walk fills DOF only.  Tells a test which instantiations it ran: cgrt_trace_grid_variant names the main launch alone. */
+int cgrt_scene_last_eye_launches(const cgrt_scene *s, int32_t *rows, int64_t cap, int64_t *n);
 
 /* Host evaluation of that table (cgrt_relay.h, the same inline code the kernels run; no GPU): for a list of n_tiles entries,
  * the first n01 of class 0 or 1 and the first n012 of classes 0-2 (cgrt_scene_last_tile_order's plan[2], plan[3], plan[4] and

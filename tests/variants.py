@@ -1,5 +1,5 @@
 """The kernel variants that are compiled, read from cgraytracing_amd/csrc/cgrt_variants.h itself: the X(...) entries of
-CGRT_EYE_VARIANTS and CGRT_RAY_VARIANTS as tuples of ints, and the two families derived from the ray list by the header's rules
+CGRT_EYE_VARIANTS, CGRT_EYE_POSED_VARIANTS and CGRT_RAY_VARIANTS as tuples of ints, and the two families derived from the ray list by the header's rules
 (has_capture, has_occlusion)."""
 import os
 import re
@@ -19,6 +19,11 @@ def _entries(macro, columns):
 def eye_variants():
     """(TREES, BEZ, DOF, GLASS, SPH, STATS, HPS, NT, SPILL, HFONLY, DIFF, PAIR, START, LTAB, SCHED) of every trace_grid_kernel."""
     return _entries("CGRT_EYE_VARIANTS", 15)
+
+
+def posed_eye_variants():
+    """The same columns of every trace_grid_kernel with POSE (CGRT_EYE_POSED_VARIANTS)."""
+    return _entries("CGRT_EYE_POSED_VARIANTS", 15)
 
 
 def ray_variants():
