@@ -66,6 +66,12 @@ class Torch:
                                                                                    self.dev))
         return t
 
+    def triangles(self, what, t):
+        """A mesh's vertices: contiguous float64 [n,9] or [n,3,3].  Returns (n, t)."""
+        if not (self._ok(t, (self.torch.float64,), (None, 9)) or self._ok(t, (self.torch.float64,), (None, 3, 3))):
+            raise ValueError("%s: tris must be a contiguous float64 [n,9] or [n,3,3] tensor on %s" % (what, self.dev))
+        return t.shape[0], t
+
     def results(self, what, spec, names, out, n, cap=0):
         """{name: the caller's out[name], validated, or a fresh tensor} for `names` of the table `spec`."""
         res = {}
@@ -122,6 +128,12 @@ class Numpy:
                 raise ValueError("%s: %s must be a%s %s [n] array" % (what, name, "n" if dtype[1][0] in "aeiou" else "", dtype[1]))
             raise ValueError("%s: %s must %s" % (what, name, "have one entry per %s" % per if cols is None else "be an [n,%d] array" % cols))
         return t
+
+    def triangles(self, what, t):
+        t = np.ascontiguousarray(t, np.float64)
+        if t.size % 9 or (t.ndim > 1 and t.shape[1:] not in ((9,), (3, 3))):
+            raise ValueError("%s: tris must be an [n,9] or [n,3,3] array" % what)
+        return t.size // 9, t
 
     def results(self, what, spec, names, out, n, cap=0):
         make = lambda shape, dtype, fill: np.full(shape, fill, dtype) if fill else np.zeros(shape, dtype)

@@ -104,6 +104,11 @@ class BuildInfo(C.Structure):
 BUILD_HOST, BUILD_DEVICE = 0, 1
 
 
+class RefitInfo(C.Structure):
+    _fields_ = [("refits", C.c_int64), ("nwide", C.c_int32), ("ntris", C.c_int32), ("plan_built", C.c_int32),
+                ("ms_plan", C.c_double), ("geometry_gen", C.c_uint64)]  # 40 bytes
+
+
 class Rays(C.Structure):
     _fields_ = [("n", C.c_int64), ("org3", C.c_void_p), ("dir3", C.c_void_p), ("keys", C.c_void_p),
                 ("first_index", C.c_int64), ("seed", C.c_uint64), ("max_depth", C.c_int32), ("flags", C.c_int32)]
@@ -233,6 +238,11 @@ SIGNATURES = {
     "cgrt_scene_bvh_dump": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "cgrt_scene_bvh_order": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p]),
     "cgrt_scene_wide_dump": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "cgrt_scene_refit_mesh": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "cgrt_scene_refit_mesh_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "cgrt_scene_refit_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RefitInfo)]),
+    "cgrt_scene_refit_plan_host": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
     "cgrt_lens_samples": (C.c_int, [C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
     "cgrt_surface_colors": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "cgrt_trace_grid_variant": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Grid), C.c_char_p, C.c_size_t]),

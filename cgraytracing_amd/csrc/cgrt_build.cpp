@@ -817,6 +817,8 @@ int HostScene::add_mesh_triangles(const double *tri9, int ntri, const double sc[
             // the same bound in pieces (<= 2^kCoverDepth spheres over median-split groups of triangles), for classify_kernel:
             // a long thin mesh fills a small part of its one sphere's silhouette
             cover_spheres(tree.tri9, kCoverDepth, cover);
+            tree.cover_first = first / 4;
+            tree.cover_n = (int)((cover.size() - first) / 4);
         }
     }
     trees.push_back(std::move(tree));

@@ -54,6 +54,13 @@ struct HostTree {
     // filled by the commit for the verification dumps (cgrt_scene_wide_dump on a device-built tree reads the device arrays)
     int32_t dev_nwide = 0;
     bool dev_balanced = false;
+    // a mesh's cover spheres in HostScene::cover, whichever build made them: spheres [cover_first, cover_first + cover_n)
+    // (a refit writes new ones into the same places, cgrt_refit.hpp)
+    size_t cover_first = 0;
+    int cover_n = 0;
+    // cgrt_scene_refit_mesh has moved the vertices: the device's records are the tree now, and what above describes the
+    // reference's tree over the old vertices is reported empty (leaf_ids stays: it maps tris[] to construction order)
+    bool refitted = false;
 };
 // nodes of the reference's tree over n triangles (objects.h:217-267: leaf below 10, halves n/2 and n - n/2): what
 // cgrt_scene_stats reports for a tree that was never built on the host

@@ -22,6 +22,7 @@
 #include <cstring>
 #include <exception>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -29,6 +30,7 @@
 
 #include "../../include/cgrt.h"
 #include "cgrt_build.h"
+#include "cgrt_refit_plan.h"
 #include "cgrt_rng.hpp"
 #include "cgrt_types.h"
 
@@ -167,6 +169,23 @@ public:
 
 #include "cgrt_tile_order.hpp"
 
+// What the first cgrt_scene_refit_mesh of a mesh leaves on the handle (cgrt_refit.hpp): the plan (cgrt_refit_plan.h) and its
+// device copy behind the words every refit clears on its stream
+struct RefitNode {
+    int32_t parent, slot, need, pad;  // RefitPlan::parent, ::slot, ::arrivals
+};
+struct RefitState {
+    RefitPlan plan;
+    DevBuf mem;  // [keys | arrival counters] [nodes] [src, rec]
+    size_t bytes = 0, clear_bytes = 0;
+    unsigned long long *keys = nullptr;
+    int *arrive = nullptr;
+    const RefitNode *nodes = nullptr;
+    const int2 *srcrec = nullptr;
+    int64_t refits = 0;
+    double ms_plan = 0;  // wall-clock of building and uploading the plan (the first refit's read-backs included)
+};
+
 struct cgrt_scene {
     HostScene host;
     bool committed = false;
@@ -198,6 +217,10 @@ struct cgrt_scene {
     // the eye kernels the last eye pass on the handle launched (launch_eye, primary_walk), probes included: host state, cleared
     // by every entry point that runs an eye pass, read by cgrt_scene_last_eye_launches
     mutable EyeLaunchLog eye_log;
+    // cgrt_scene_refit_mesh: per refitted mesh object its plan (built by its first refit; a scene that never refits pays nothing),
+    // and the count of refits of the scene: the photon-mapping sessions remember the one they were created under
+    std::map<int, std::unique_ptr<RefitState>> refit;
+    uint64_t geometry_gen = 0;
 };
 
 template <class T>
@@ -239,7 +262,7 @@ int cgrt_scene_create(cgrt_scene **out) {
 
 void cgrt_scene_destroy(cgrt_scene *s) {
     if (!s) return;
-    if (!s->allocs.empty() || s->scratch.p || s->order.buf.p || s->relay.buf.p || s->lens.buf.p || s->lens.ev || s->tri_ids.p || s->aux_stream || s->order.ev || s->relay.ev) {
+    if (!s->allocs.empty() || s->scratch.p || s->order.buf.p || s->relay.buf.p || s->lens.buf.p || s->lens.ev || s->tri_ids.p || s->aux_stream || s->order.ev || s->relay.ev || !s->refit.empty()) {
         DeviceGuard g(s->device);
         if (g.err == hipSuccess) {
             for (void *p : s->allocs) (void)hipFree(p);
@@ -248,6 +271,7 @@ void cgrt_scene_destroy(cgrt_scene *s) {
             s->relay.release();
             s->lens.release();
             s->tri_ids.release();
+            s->refit.clear();
             if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
             if (s->ev_join) (void)hipEventDestroy(s->ev_join);
             if (s->aux_stream) (void)hipStreamDestroy(s->aux_stream);
@@ -369,6 +393,8 @@ static int device_builds(HostScene &H, SceneLayout &L, const DeviceScene &d) {
             for (int k = 0; k < 3; k++) ob.a[k] = mr.centre[k];
             ob.s0 = mr.r2;
             t.dev_cover_at = H.cover.size();
+            t.cover_first = H.cover.size() / 4;
+            t.cover_n = (int)(mr.cover.size() / 4);
             H.cover.insert(H.cover.end(), mr.cover.begin(), mr.cover.end());
         }
     }
@@ -514,6 +540,7 @@ int cgrt_scene_get_stats(const cgrt_scene *s, cgrt_scene_stats *out) {
     for (auto &t : H.textures) bytes += 3 * (int64_t)t.rows * t.cols;
     out->scene_bytes_fp64 = bytes;
     out->device_bytes = s->device_bytes + (int64_t)s->scratch.cap + (int64_t)s->order.buf.cap + (int64_t)s->tri_ids.cap;  // uploaded scene + the handle's launch scratch (+ the hit-attribute table once asked for)
+    for (const auto &r : s->refit) out->device_bytes += (int64_t)r.second->bytes;  // (+ the refit plans)
     out->committed = s->committed ? 1 : 0;
     return CGRT_OK;
 }
@@ -521,16 +548,17 @@ int cgrt_scene_get_stats(const cgrt_scene *s, cgrt_scene_stats *out) {
 int cgrt_scene_tree_sizes(const cgrt_scene *s, int t, int32_t *nnodes, int32_t *nleaftris, int32_t *ntris) {
     if (!s || t < 0 || t >= (int)s->host.trees.size()) return fail(CGRT_ERR_INVALID, "bad tree index");
     const HostTree &T = s->host.trees[t];
-    if (nnodes) *nnodes = (int32_t)T.nodes.size();  // the reference's tree (fingerprints); the device hierarchy is T.bvh
-    if (nleaftris) *nleaftris = (int32_t)T.leaf_ids.size();
+    // (a refitted tree: the reference's tree over the OLD vertices describes nothing any more -- empty, as for a device-built one)
+    if (nnodes) *nnodes = T.refitted ? 0 : (int32_t)T.nodes.size();  // the reference's tree (fingerprints); the device hierarchy is T.bvh
+    if (nleaftris) *nleaftris = T.refitted ? 0 : (int32_t)T.leaf_ids.size();
     if (ntris) *ntris = T.dev_kind ? (int32_t)T.dev_ntri : (int32_t)(T.tri9.size() / 9);  // device-built: no reference tree exists (0 nodes)
     return CGRT_OK;
 }
 int cgrt_scene_bvh_dump(const cgrt_scene *s, int t, int32_t *nnodes, float *box6, int32_t *skip_leaf2) {
     if (!s || t < 0 || t >= (int)s->host.trees.size()) return fail(CGRT_ERR_INVALID, "bad tree index");
     const HostTree &T = s->host.trees[t];
-    if (nnodes) *nnodes = T.bvh_nodes;
-    for (size_t i = 0; i < T.bvh.size(); i++) {
+    if (nnodes) *nnodes = T.refitted ? 0 : T.bvh_nodes;
+    for (size_t i = 0; i < (T.refitted ? 0 : T.bvh.size()); i++) {
         if (box6) {
             for (int k = 0; k < 3; k++) {
                 box6[6 * i + k] = T.bvh[i].lo[k];
@@ -548,15 +576,17 @@ int cgrt_scene_wide_dump(const cgrt_scene *s, int t, int32_t *nwide, int32_t *st
     if (!s || t < 0 || t >= (int)s->host.trees.size()) return fail(CGRT_ERR_INVALID, "bad tree index");
     const HostTree &T = s->host.trees[t];
     std::vector<WideNodeRec> from_device;
-    if (T.dev_kind == 1 && s->committed && (box24 || ref4)) {  // built on the device (row f3): read the records back
+    const bool on_device = s->committed && (T.dev_kind == 1 || T.refitted);  // built (row f3) or refitted on the device
+    const int32_t n_device = on_device ? s->tree_recs[(size_t)t].nwide : 0;
+    if (on_device && (box24 || ref4)) {  // read the records back
         ON_DEVICE(s->device);
-        from_device.resize((size_t)T.dev_nwide);
-        if (T.dev_nwide > 0)
+        from_device.resize((size_t)n_device);
+        if (n_device > 0)
             HIP_TRY(hipMemcpy(from_device.data(), s->dev.wnodes + s->tree_recs[(size_t)t].wnode_begin,
                               from_device.size() * sizeof(WideNodeRec), hipMemcpyDeviceToHost));
     }
-    const std::vector<WideNodeRec> &wide = T.dev_kind == 1 ? from_device : T.wide;
-    if (nwide) *nwide = T.dev_kind == 1 ? T.dev_nwide : (int32_t)T.wide.size();
+    const std::vector<WideNodeRec> &wide = (T.dev_kind == 1 || on_device) ? from_device : T.wide;
+    if (nwide) *nwide = on_device ? n_device : T.dev_kind == 1 ? T.dev_nwide : (int32_t)T.wide.size();
     if (stack_need) *stack_need = T.wide_stack;
     for (size_t i = 0; i < wide.size(); i++) {
         const WideNodeRec &w = wide[i];
@@ -575,9 +605,9 @@ int cgrt_scene_bvh_order(const cgrt_scene *s, int t, int32_t *tri_level, int32_t
     if (!s || t < 0 || t >= (int)s->host.trees.size()) return fail(CGRT_ERR_INVALID, "bad tree index");
     const HostTree &T = s->host.trees[t];
     if (tri_level) *tri_level = T.tri_level ? 1 : 0;
-    if (order && T.dev_kind == 1 && s->committed) {  // built on the device: k = the triangle's construction index
-        ON_DEVICE(s->device);
-        std::vector<OTriRec> ot((size_t)T.dev_ntri);
+    if (order && (T.dev_kind == 1 || T.refitted) && s->committed) {  // built on the device: k = the triangle's construction index;
+        ON_DEVICE(s->device);                                         // refitted: the records the refit left, k as it was
+        std::vector<OTriRec> ot((size_t)s->tree_recs[(size_t)t].ntris);
         if (!ot.empty())
             HIP_TRY(hipMemcpy(ot.data(), s->dev.otris + s->tree_recs[(size_t)t].otri_begin, ot.size() * sizeof(OTriRec), hipMemcpyDeviceToHost));
         for (size_t j = 0; j < ot.size(); j++) order[j] = ot[j].k;
@@ -591,14 +621,16 @@ int cgrt_scene_tree_dump(const cgrt_scene *s, int t, int32_t *node_lr_size, int3
                          double *tri9) {
     if (!s || t < 0 || t >= (int)s->host.trees.size()) return fail(CGRT_ERR_INVALID, "bad tree index");
     const HostTree &T = s->host.trees[t];
-    if (node_lr_size) std::memcpy(node_lr_size, T.node_lr_size.data(), T.node_lr_size.size() * sizeof(int32_t));
-    if (leaf_ids) std::memcpy(leaf_ids, T.leaf_ids.data(), T.leaf_ids.size() * sizeof(int32_t));
-    if (bbox) std::memcpy(bbox, T.bbox.data(), T.bbox.size() * sizeof(double));
+    if (node_lr_size && !T.refitted) std::memcpy(node_lr_size, T.node_lr_size.data(), T.node_lr_size.size() * sizeof(int32_t));
+    if (leaf_ids && !T.refitted) std::memcpy(leaf_ids, T.leaf_ids.data(), T.leaf_ids.size() * sizeof(int32_t));
+    if (bbox && !T.refitted) std::memcpy(bbox, T.bbox.data(), T.bbox.size() * sizeof(double));
     if (tri9) std::memcpy(tri9, T.tri9.data(), T.tri9.size() * sizeof(double));
     return CGRT_OK;
 }
 
 }  // extern "C"
+
+#include "cgrt_refit.hpp"
 
 // ---- LDS of a launch ----
 // A workgroup may use at most a CU's LDS (MI355X: 160 KiB): the kernel's static __shared__ bytes plus the dynamic bytes of

@@ -105,6 +105,7 @@ struct cgrt_ppm_session {
     int width = 0, rows = 0, spp = 1, max_depth = 0;
     bool striped = false;  // grid session over block-cyclic rows: no rgb8
     bool lookahead = false;  // session: trace the next batch on the producer stream when a call ends
+    uint64_t geometry_gen = 0;  // session: the scene's refit count at creation -- the Hitpoints are those of that geometry
     PpmTable tab;            // the hitpoints in table order and the per-pixel index
     int64_t dev_bytes = 0;  // what this state allocated itself (the table, sort scratch and producer buffers are added by bytes())
     DevBuf pk0, pk1, pv0, pv1, npairs;          // (hitpoint, event) pairs of one batch
@@ -320,6 +321,7 @@ static int session_create(const cgrt_scene *s, const cgrt_photons *ph, int flags
     std::unique_ptr<cgrt_ppm_session> p(new (std::nothrow) cgrt_ppm_session());
     if (!p) return fail(CGRT_ERR_LIMIT, "out of host memory");
     p->lookahead = !(flags & CGRT_PPM_SESSION_NO_LOOKAHEAD);
+    p->geometry_gen = s->geometry_gen;
     p->frame(width, rows, spp, max_depth, striped);
     HIP_TRY(hipEventCreate(&p->img_a));
     HIP_TRY(hipEventCreate(&p->img_b));
@@ -403,6 +405,7 @@ extern "C" void cgrt_ppm_session_destroy(cgrt_ppm_session *p) {
 
 // `count` more photons: the built-in emitter's, or (pr) the caller's
 static int session_add(cgrt_ppm_session *p, long long count, const cgrt_photon_rays *pr) {
+    if (p->geometry_gen != p->s->geometry_gen) return fail(CGRT_ERR_INVALID, kRefitStale);  // (image, hitpoints, get_info go on working)
     ON_DEVICE(p->s->device);
     if (p->img_pending) HIP_TRY(hipStreamWaitEvent(0, p->img_b, 0));  // a gather on a caller's stream reads hp
     // the producer stream does not wait for the null stream: arrays a kernel on the null stream still writes must be complete

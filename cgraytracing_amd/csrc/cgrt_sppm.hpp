@@ -144,6 +144,7 @@ struct cgrt_sppm_session {
     int width = 0, rows = 0, spp = 1, photon_depth = 0;
     long long npix = 0;
     bool have_stripe = false;  // a grid pass has fixed `stripe`
+    uint64_t geometry_gen = 0;  // the scene's refit count at creation: the texels' statistics are those of that geometry
     SppmStripe stripe;
     DevBuf px;                       // [npix][kSppmPixelDoubles], for the session's life
     std::unique_ptr<PpmTable> tab;   // the last pass's Hitpoints (null before the first pass and after a failed one)
@@ -314,6 +315,7 @@ extern "C" int cgrt_sppm_session_create(const cgrt_scene *s, int32_t width, int3
     std::unique_ptr<cgrt_sppm_session> p(new (std::nothrow) cgrt_sppm_session());
     if (!p) return fail(CGRT_ERR_LIMIT, "out of host memory");
     p->s = s;
+    p->geometry_gen = s->geometry_gen;
     p->ph = *ph;
     p->ph.nphotons = 0;
     p->width = width; p->rows = rows; p->spp = spp; p->photon_depth = photon_depth;
@@ -344,6 +346,7 @@ static int sppm_count_ok(const cgrt_sppm_session *p, int64_t nphotons) {
 
 extern "C" int cgrt_sppm_session_pass_grid(cgrt_sppm_session *p, const cgrt_camera *cam, const cgrt_grid *grid, int64_t nphotons) {
     if (!p) return fail(CGRT_ERR_INVALID, "null session");
+    if (p->geometry_gen != p->s->geometry_gen) return fail(CGRT_ERR_INVALID, kRefitStale);  // (image, pixels, get_info go on working)
     int rc = check_grid(p->s, cam, grid);
     if (rc) return rc;
     if (const char *msg = sppm_pass_grid_args(p->width, p->rows, p->spp, grid, p->have_stripe ? &p->stripe : nullptr))
@@ -360,6 +363,7 @@ extern "C" int cgrt_sppm_session_pass_grid(cgrt_sppm_session *p, const cgrt_came
 
 extern "C" int cgrt_sppm_session_pass_rays(cgrt_sppm_session *p, const cgrt_rays *rays, const int64_t *pixel, int64_t nphotons) {
     if (!p) return fail(CGRT_ERR_INVALID, "null session");
+    if (p->geometry_gen != p->s->geometry_gen) return fail(CGRT_ERR_INVALID, kRefitStale);
     int rc = check_capture_rays(p->s, rays);
     if (rc) return rc;
     if ((rc = sppm_count_ok(p, nphotons))) return rc;

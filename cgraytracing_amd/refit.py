@@ -1,0 +1,51 @@
+"""Refit: new vertices for a committed opaque mesh (include/cgrt.h, "refit").
+
+`Scene` here is engine.Scene with the refit calls added, and it is what `cgraytracing_amd.Scene` names: engine.py's public
+surface is pinned to a recorded table (tests/test_py_binding_host.py), so the calls of a new capability live in a module of
+their own and reach the user through the subclass.  Buffers are checked by the adapters of _buffers.py, as everywhere."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _buffers, _capi, engine
+from ._capi import check
+
+
+class Scene(engine.Scene):
+    __doc__ = engine.Scene.__doc__
+
+    def refit_mesh(self, obj, tris, stream=None):
+        """cgrt_scene_refit_mesh on a torch tensor: tris float64 [n,9] or [n,3,3] (pa, pb, pc per triangle in construction
+        order), contiguous on the scene's device, n the mesh's triangle count.  The hierarchy of object `obj` -- an opaque mesh
+        -- keeps its topology and gets boxes, triangle records, bounding and cover spheres for these vertices, by kernels on
+        torch's current stream (or `stream`): every launch that follows on that stream sees the moved mesh.  Asynchronous
+        after the mesh's first refit, which builds the plan.  tris must stay alive until the kernels have run.  Parity class
+        and refusals: include/cgrt.h."""
+        self._refit(self._torch(), "refit_mesh", obj, tris, stream)
+
+    def _refit(self, A, what, obj, tris, stream):
+        n, tris = A.triangles(what, tris)
+        check(getattr(self._L, "cgrt_scene_refit_mesh" + A.suffix)(self._h, int(obj), A.ptr(tris), n, *A.stream(stream)))
+
+    def refit_mesh_host(self, obj, tris):
+        """Synchronous form of refit_mesh on a numpy array (no torch needed); it also refreshes the handle's host mirrors
+        (what tree_dump returns as the triangles)."""
+        self._refit(_buffers.NUMPY, "refit_mesh_host", obj, tris, None)
+
+    def refit_info(self, obj):
+        """cgrt_scene_refit_info: dict(refits, nwide, ntris, plan_built, ms_plan, geometry_gen)."""
+        ri = _capi.RefitInfo()
+        check(self._L.cgrt_scene_refit_info(self._h, int(obj), C.byref(ri)))
+        return {f: getattr(ri, f) for f, _ in ri._fields_}
+
+    def refit_plan(self, t=0):
+        """(parent [nwide], slot [nwide], arrivals [nwide], src [ntris]): see cgrt_scene_refit_plan_host."""
+        nw, nt = C.c_int32(), C.c_int32()
+        check(self._L.cgrt_scene_refit_plan_host(self._h, t, C.byref(nw), C.byref(nt), None, None, None, None))
+        parent, slot, arrivals = (np.zeros(max(nw.value, 1), np.int32) for _ in range(3))
+        src = np.zeros(max(nt.value, 1), np.int32)
+        check(self._L.cgrt_scene_refit_plan_host(self._h, t, C.byref(nw), C.byref(nt), parent.ctypes.data, slot.ctypes.data,
+                                                 arrivals.ctypes.data, src.ctypes.data))
+        return parent[: nw.value], slot[: nw.value], arrivals[: nw.value], src[: nt.value]

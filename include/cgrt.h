@@ -19,7 +19,8 @@
  * a handle owns device scratch that consecutive launches reuse (CGRT_GRID_SPLIT_SAMPLES chunk sums; the schedule of a
  * cost-ordered frame; the tile order of an image-order one; the queue counter of cgrt_trace_rays, cgrt_trace_rays_hitpoints and cgrt_ppm_session_create_rays, which
  * are such launches (cgrt_occlusion_rays and cgrt_bounce_rays use that counter too); cgrt_ray_hit_attributes is one too: its first call that asks for `prim` builds a table the handle keeps;
- * cgrt_wavefront_rays uses the queue counter and keeps its work memory on the handle, and it synchronises its stream, so it cannot be stream-captured).
+ * cgrt_wavefront_rays uses the queue counter and keeps its work memory on the handle, and it synchronises its stream, so it cannot be stream-captured;
+ * cgrt_scene_refit_mesh WRITES the scene's device arrays and keeps a plan and arrival counters on the handle: every launch that reads the scene is ordered against it).
  * All geometry is IEEE double, like the reference (Vec3 = 3 x double, vec3.h:11-30).
  */
 #ifndef CGRT_H
@@ -49,7 +50,8 @@ extern "C" {
                             caller-supplied Hitpoints); the cgrt_sppm_session_ calls, cgrt_sppm_update_host, cgrt_sppm_check_host
                             (stochastic progressive photon mapping); cgrt_posed_camera, CGRT_GRID_POSED, cgrt_look_at
                             (posed camera: a library without them has no cgrt_look_at symbol, and CGRT_GRID_POSED was an
-                            unknown bit that it ignored) */
+                            unknown bit that it ignored); cgrt_scene_refit_mesh, cgrt_scene_refit_mesh_host, cgrt_refit_info,
+                            cgrt_scene_refit_info, cgrt_scene_refit_plan_host (refit of committed opaque meshes) */
 
 enum {
     CGRT_OK = 0,
@@ -358,7 +360,8 @@ int cgrt_scene_add_bezier(cgrt_scene *s, const double *cp3, int ncp, const doubl
                           double refl, double transp);
 
 /* Builds the trees (KDTree::buildKdTree, objects.h:217-267, same leaf order), flattens the scene and uploads
- * it to HIP device `device`.  Must be called once before tracing; the scene is immutable afterwards. */
+ * it to HIP device `device`.  Must be called once before tracing; the scene is immutable afterwards, except for the vertices of
+ * an opaque mesh (cgrt_scene_refit_mesh below). */
 int cgrt_scene_commit(cgrt_scene *s, int device);
 int cgrt_scene_get_stats(const cgrt_scene *s, cgrt_scene_stats *out);
 
@@ -386,6 +389,62 @@ int cgrt_scene_bvh_order(const cgrt_scene *s, int tree, int32_t *tri_level, int3
  * >= 0 a leaf ((first triangle of the hierarchy's order << 4) | count), INT32_MIN an empty slot, otherwise ~(child node).
  * *stack_need = the deepest the walk's stack can get (always below 64).  Two-call protocol: box24 / ref4 may be NULL. */
 int cgrt_scene_wide_dump(const cgrt_scene *s, int tree, int32_t *nwide, int32_t *stack_need, float *box24, int32_t *ref4);
+
+/* ---- refit: new vertices for a committed OPAQUE mesh, on the device -----------------------------
+ * The one thing that may change in a committed scene.  A mesh that moves (a squashed dragon, a cloth, a skinned bunny) keeps its
+ * triangles and their order and gets new vertices: the topology of its 4-wide hierarchy stays, every box is recomputed bottom-up
+ * by the builders' rule (the fp64 extent, grown, rounded outward to fp32), and the triangle records, the mesh's bounding sphere,
+ * its cover spheres and its tree's error bound follow -- all by kernels, into the device arrays.
+ *
+ * tri9: ntri * 9 doubles in the layout of cgrt_scene_add_mesh_triangles (pa, pb, pc per triangle, in construction order, already
+ * transformed); ntri must be the mesh's triangle count.  After the call every kernel that runs LATER ON `stream` sees the mesh
+ * with these vertices.
+ * cgrt_scene_refit_mesh: tri9 is a DEVICE pointer on the scene's device, read by the kernels (it must stay valid until they have
+ * run; it is not inspected on the host).  The call is asynchronous: it launches kernels on `stream` and returns, with no host
+ * read-back and no blocking copy -- except that the FIRST refit of a mesh builds its plan (parents, slots, arrival counts, the
+ * triangle order's construction indices) once, which for a device-built tree reads the tree back, and uploads it with blocking
+ * copies.  It is a launch on the scene handle (Threading above): the caller orders it against launches on other streams, and
+ * against a cgrt_ppm_session's look-ahead batch (destroy the session, or create it with CGRT_PPM_SESSION_NO_LOOKAHEAD);
+ * cgrt_trace_grid's own second stream forks from and joins its `stream`, so for it the same stream is order enough.  Two
+ * refits enqueued back to back are both correct.
+ * cgrt_scene_refit_mesh_host: tri9 is a host pointer; synchronous (null stream), and it refreshes the handle's host mirrors of
+ * what the device now owns (the object's bounding sphere, the tree's error bound, the cover spheres, the triangles
+ * cgrt_scene_tree_dump returns).  The device entry leaves those mirrors as they were.
+ *
+ * What may be refitted: a mesh object of a committed scene whose transparency is < 1e-4 and whose tree has the 4-wide form,
+ * host-built or device-built.  An empty mesh with ntri == 0 is accepted and nothing is done.  Refused with CGRT_ERR_INVALID and
+ * a cgrt_last_error that says which, before any device is touched: a null or uncommitted scene; an `obj` that is no object; a
+ * sphere, a plane, a Bezier object; a bump floor; a transparent mesh (its improvement counter makes the reference's leaf order
+ * observable, quirk Q5, and a refit cannot reproduce that order); a tree without the wide form (CGRT_TREE=ref); an ntri that
+ * is not the mesh's; a null tri9 with ntri > 0.
+ * Vertices: the caller supplies FINITE coordinates with |coordinate| < 1e30 -- the bound the box test's proof assumes
+ * (DESIGN.md section 4.2); a device pointer's values are not checked.
+ * Parity class: that of CGRT_BUILD_DEVICE -- tolerance, not bit-exact.  Every ray with a unique nearest hit gets the hit of a
+ * scene freshly committed with the new vertices, bit for bit (boxes are supersets, the triangle test is the same code); exact
+ * ties (a ray through a shared edge or vertex) keep the tie order the tree had BEFORE the refit: the lower construction index
+ * for a device-built tree, the old leaf order for a host-built one.  Frame time may grow as the mesh moves away from the pose
+ * the topology was built for: this call does not rebuild (profiles/refit_probe.json has the cost of two poses).
+ * After a refit cgrt_scene_tree_dump and cgrt_scene_bvh_dump, which describe the reference's tree, are empty for the tree, as
+ * for a device-built one; cgrt_scene_wide_dump and cgrt_scene_bvh_order read the device's records back.  A cgrt_ppm_session or
+ * cgrt_sppm_session created before a refit holds Hitpoints or pixel statistics of the old geometry: its add_photons,
+ * add_photon_rays, pass_grid and pass_rays return CGRT_ERR_INVALID ("the scene was refitted after this session was created");
+ * its image, hitpoints and get_info calls go on working. */
+int cgrt_scene_refit_mesh(cgrt_scene *s, int obj, const double *tri9, int ntri, void *stream);
+int cgrt_scene_refit_mesh_host(cgrt_scene *s, int obj, const double *tri9, int ntri);
+typedef struct cgrt_refit_info {
+    int64_t refits;        /* refits of this mesh so far                                                               */
+    int32_t nwide, ntris;  /* wide nodes and triangles of its tree                                                     */
+    int32_t plan_built;    /* 1 once the first refit has built the plan                                                */
+    double ms_plan;        /* wall-clock of building and uploading the plan, inside that first refit                   */
+    uint64_t geometry_gen; /* refits of the SCENE so far: what the photon-mapping sessions remember                    */
+} cgrt_refit_info;
+int cgrt_scene_refit_info(const cgrt_scene *s, int obj, cgrt_refit_info *out);
+/* The refit's plan of tree `tree`, for verification; host-built trees also before the commit.  Per wide node i: parent[i] (-1 for
+ * the root, node 0), slot[i] (ref4[4*parent[i] + slot[i]] == ~i) and arrivals[i] (its inner children + 1).  Per position j of the
+ * hierarchy's triangle order: src[j], the triangle's construction index (where tri9 holds it).  Two-call protocol as
+ * cgrt_scene_wide_dump: with the four arrays NULL only *nwide and *ntris are written; a tree without the wide form gives 0, 0. */
+int cgrt_scene_refit_plan_host(const cgrt_scene *s, int tree, int32_t *nwide, int32_t *ntris, int32_t *parent, int32_t *slot,
+                               int32_t *arrivals, int32_t *src);
 
 /* ---- the hot path -------------------------------------------------------------------------------------
  * Renders grid->rows rows: for every pixel and sample it runs the reference's trace(flag=true) recursion

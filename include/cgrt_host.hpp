@@ -253,6 +253,29 @@ class TriangleMesh : public Object {
     int objtype;
 };
 
+// The same object from triangles in memory (cgrt_scene_add_mesh_triangles): 9 doubles per triangle -- pa, pb, pc, already
+// transformed.  What a program that animates a mesh starts from (DeformingScene below).
+class TriangleSoup : public Object {
+  public:
+    TriangleSoup(std::vector<double> tri9_, const Vec3 &sc, const double &refl = 0, const double &transp = 0, int typeofdata = 0)
+        : tri9(std::move(tri9_)), surfaceColor(sc), transparency(transp), reflection(refl), objtype(typeofdata) {
+        if (tri9.size() % 9) throw Error(CGRT_ERR_INVALID, "TriangleSoup: 9 doubles per triangle");
+    }
+    double getTransparency() const override { return transparency; }
+    double getReflection() const override { return reflection; }
+    Vec3 getSurfaceColor(const Vec3 &) const override { return surfaceColor.copy(); }
+    int add_to(SceneBuilder &sb) const override {
+        double s[3];
+        surfaceColor.get(s);
+        return check(cgrt_scene_add_mesh_triangles(sb.scene, tri9.data(), (int)(tri9.size() / 9), s, reflection, transparency, objtype));
+    }
+    std::vector<double> tri9;
+  private:
+    Vec3 surfaceColor;
+    double transparency, reflection;
+    int objtype;
+};
+
 // Bezier(points, pos, sc, refl, transp, typeofdata, ec)   bezier.h:44-45
 class Bezier : public Object {
   public:
@@ -807,6 +830,50 @@ class SppmSession {
     cgrt_sppm_session *session_;
     cgrt_posed_camera cam_;  // the camera with its pose (RenderParams::camera)
     cgrt_grid grid_;
+};
+
+// A scene committed ONCE whose opaque meshes move between frames (cgrt_scene_refit_mesh_host): refit_mesh gives object `obj` --
+// its position in objs -- new vertices, 9 doubles per triangle in the order the mesh was made from; the hierarchy keeps its
+// topology and the next render sees the moved mesh.  What may be refitted, the refusals and the parity class: cgrt.h.
+class DeformingScene {
+  public:
+    explicit DeformingScene(const std::vector<Object *> &objs, int device = 0) {
+        for (const Object *o : objs) o->add_to(sb_);
+        check(cgrt_scene_commit(sb_.scene, device));
+    }
+    void refit_mesh(int obj, const std::vector<double> &tri9) {
+        if (tri9.size() % 9) throw Error(CGRT_ERR_INVALID, "refit_mesh: 9 doubles per triangle");
+        check(cgrt_scene_refit_mesh_host(sb_.scene, obj, tri9.data(), (int)(tri9.size() / 9)));
+    }
+    cgrt_refit_info refit_info(int obj) const {
+        cgrt_refit_info inf;
+        check(cgrt_scene_refit_info(sb_.scene, obj, &inf));
+        return inf;
+    }
+    // render()'s eye pass on the scene as it stands (rp.device is the constructor's)
+    void render(const RenderParams &rp, std::vector<float> &image, RenderStats *stats = nullptr) const {
+        cgrt_grid g{};
+        cgrt_posed_camera pc;
+        const cgrt_camera *cam = rp.camera(pc, g);
+        g.width = rp.width;
+        g.height = rp.height;
+        g.rows = rp.height;
+        g.stripe_nranks = 1;
+        g.spp = rp.num_of_samples;
+        g.spp_total = rp.num_of_samples;
+        g.max_depth = rp.max_depth;
+        g.seed = rp.seed;
+        image.assign((size_t)rp.width * rp.height * 3, 0.f);
+        uint64_t cnt[CGRT_NCOUNTERS] = {0};
+        check(cgrt_trace_grid_host(sb_.scene, cam, &g, image.data(), nullptr, cnt));
+        if (stats) {
+            stats->rays = cnt[CGRT_CNT_RAYS];
+            stats->hitpoints = cnt[CGRT_CNT_HITPOINTS];
+        }
+    }
+
+  private:
+    SceneBuilder sb_;
 };
 
 // stbi_write_png("test.png", width, height, 3, image_data, width * 3), main.cpp:412
