@@ -109,6 +109,16 @@ class RefitInfo(C.Structure):
                 ("ms_plan", C.c_double), ("geometry_gen", C.c_uint64)]  # 40 bytes
 
 
+class RebuildInfo(C.Structure):
+    _fields_ = [("rebuilds", C.c_int64), ("nwide", C.c_int32), ("stack_need", C.c_int32), ("balanced", C.c_int32),
+                ("levels", C.c_int32), ("readbacks", C.c_int32), ("pad_", C.c_int32), ("ms_last", C.c_double),
+                ("scratch_bytes", C.c_int64)]  # 48 bytes
+
+
+class TreeCost(C.Structure):
+    _fields_ = [("node_cost", C.c_double), ("tri_cost", C.c_double), ("root_area", C.c_double)]  # 24 bytes
+
+
 class Rays(C.Structure):
     _fields_ = [("n", C.c_int64), ("org3", C.c_void_p), ("dir3", C.c_void_p), ("keys", C.c_void_p),
                 ("first_index", C.c_int64), ("seed", C.c_uint64), ("max_depth", C.c_int32), ("flags", C.c_int32)]
@@ -243,6 +253,11 @@ SIGNATURES = {
     "cgrt_scene_refit_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RefitInfo)]),
     "cgrt_scene_refit_plan_host": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p]),
+    "cgrt_scene_rebuild_mesh": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "cgrt_scene_rebuild_mesh_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "cgrt_scene_rebuild_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RebuildInfo)]),
+    "cgrt_scene_mesh_cost": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "cgrt_scene_mesh_cost_host": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(TreeCost)]),
     "cgrt_lens_samples": (C.c_int, [C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
     "cgrt_surface_colors": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "cgrt_trace_grid_variant": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Grid), C.c_char_p, C.c_size_t]),

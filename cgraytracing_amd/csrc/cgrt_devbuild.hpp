@@ -12,6 +12,8 @@
 //        <= 4 triangles as leaves, then the 4-wide form level by level with the host build's rule (replace the
 //        larger-surfaced inner child by its children until there are four).  The walk's stack bound (kWideStack) is checked
 //        on the device; a tree that misses it is rebuilt with balanced splits of the sorted order (depth <= log2 n).
+//        build_mesh_core is that builder on a device vertex buffer, a stream and a scratch: the commit runs it with a temporary
+//        scratch on the null stream, cgrt_scene_rebuild_mesh (cgrt_rebuild.hpp) with the handle's scratch on the caller's.
 //
 // Parity class: TOLERANCE, not bit-exact.  Boxes are supersets and the triangle test is the same
 // code, so (len, triangle) of every ray with a UNIQUE nearest hit is bit-identical to the host build's.  What differs:
@@ -126,7 +128,9 @@ struct MeshArgs {
     double *box;  // (2n - 1) x 6: lo(3), hi(3)
     int2 *queue;  // wide-node work list: {binary node, stack entries waiting above it}
     int *tail;    // [0] = wide nodes so far, [1] = stack need, [2] = root (binary node id)
+    int *range;   // wide_level_kernel's level: R_BEGIN, R_END (queue entries), R_LEVELS done so far, R_TICKET
 };
+enum { R_BEGIN = 0, R_END = 1, R_LEVELS = 2, R_TICKET = 3, N_RANGE = 4 };
 
 __device__ inline void tri_box(const double *t, double lo[3], double hi[3]) {
     for (int k = 0; k < 3; k++) {
@@ -316,62 +320,104 @@ __device__ inline bool group_leaf(const MeshArgs &a, int node, int &first, int &
     return cnt <= 4;  // HostTree::build_bvh: max_leaf = 4
 }
 
+// mesh_prep_kernel's starting values, written on the stream (no upload): the keys of an empty box and of radius 0
+__global__ void mesh_init_kernel(MeshArgs a) {
+    if (blockIdx.x != 0 || threadIdx.x >= 7) return;
+    a.gbox[threadIdx.x] = threadIdx.x < 3 ? ~0ull : 0ull;
+}
+
+// The wide form's starting state, once the binary tree's root is known (tail[2]): queue[0] = the root, one wide node so far,
+// level [0, 1), no ticket taken
+__global__ void wide_init_kernel(MeshArgs a) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    a.queue[0] = make_int2(a.tail[2], 0);
+    a.tail[0] = 1;
+    a.tail[1] = 0;
+    a.range[R_BEGIN] = 0;
+    a.range[R_END] = 1;
+    a.range[R_LEVELS] = 0;
+    a.range[R_TICKET] = 0;
+}
+
 // One level of the 4-wide form (BvhBuilder::emit_wide's rule): queue entries [begin, end) become wnodes[begin, end); their
-// inner children are appended to the queue for the next launch.
-__global__ void wide_level_kernel(MeshArgs a, int begin, int end) {
-    const int q = begin + blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= end) return;
-    const int node = a.queue[q].x, acc = a.queue[q].y;
-    int kids[4], nk = 0, f, c;
-    if (group_leaf(a, node, f, c)) {
-        kids[nk++] = node;  // a tree that is one leaf: a root with that one child
-    } else {
-        kids[nk++] = a.left[node];
-        kids[nk++] = a.right[node];
-        while (nk < 4) {
-            int best = -1;
-            double best_area = -1;
-            for (int k = 0; k < nk; k++) {
-                if (group_leaf(a, kids[k], f, c)) continue;
-                const double *b = a.box + 6 * (size_t)kids[k];
-                const double x = b[3] - b[0], y = b[4] - b[1], z = b[5] - b[2];
-                const double area = x * y + y * z + z * x;
-                if (area > best_area) {
-                    best_area = area;
-                    best = k;
-                }
-            }
-            if (best < 0) break;
-            const int cnode = kids[best];
-            kids[best] = a.left[cnode];
-            kids[nk++] = a.right[cnode];
-        }
-    }
-    WideNodeRec w;
-    for (int k = 0; k < 4; k++) {
-        w.pad[k] = 0;
-        if (k >= nk) {
-            w.lox[k] = w.loy[k] = w.loz[k] = w.hix[k] = w.hiy[k] = w.hiz[k] = 0.f;
-            w.ref[k] = kWideNone;
-            continue;
-        }
-        const double *b = a.box + 6 * (size_t)kids[k];
-        w.lox[k] = f_down(b[0] - kBoxPad);
-        w.loy[k] = f_down(b[1] - kBoxPad);
-        w.loz[k] = f_down(b[2] - kBoxPad);
-        w.hix[k] = f_up(b[3] + kBoxPad);
-        w.hiy[k] = f_up(b[4] + kBoxPad);
-        w.hiz[k] = f_up(b[5] + kBoxPad);
-        if (group_leaf(a, kids[k], f, c)) {
-            w.ref[k] = (int32_t)(((uint32_t)f << 4) | (uint32_t)c);
+// inner children are appended to the queue for the next launch.  The level's range is read from device memory
+// (range[R_BEGIN], range[R_END]) and walked grid-stride, so the host enqueues launch after launch without reading anything
+// back: the last workgroup of a launch to finish -- told by the value its agent-scope add to range[R_TICKET] returns -- rotates
+// the range for the NEXT launch (begin = end, end = tail[0]).  Every add to tail[0] of the launch has returned before its
+// workgroup takes a ticket, and all of them are agent-scope atomics on one word, so the last ticket's atomic load of tail[0]
+// sees the level's final count.  No workgroup waits for another (refit_nodes_kernel's rule); the range words are written by
+// one workgroup after every other has read them, and are read again only by the next launch.  A launch on an empty level
+// returns at once, without a ticket (all its workgroups see the same empty range).
+__global__ __launch_bounds__(256) void wide_level_kernel(MeshArgs a) {
+    const int begin = a.range[R_BEGIN], end = a.range[R_END] < a.n ? a.range[R_END] : a.n;  // (queue and wnodes hold n)
+    if (begin >= end) return;
+    int need = 0;
+    for (int q = begin + (int)(blockIdx.x * blockDim.x + threadIdx.x); q < end; q += (int)(gridDim.x * blockDim.x)) {
+        const int node = a.queue[q].x, acc = a.queue[q].y;
+        int kids[4], nk = 0, f, c;
+        if (group_leaf(a, node, f, c)) {
+            kids[nk++] = node;  // a tree that is one leaf: a root with that one child
         } else {
-            const int child = atomicAdd(&a.tail[0], 1);
-            a.queue[child] = make_int2(kids[k], acc + nk - 1);
-            w.ref[k] = ~child;
+            kids[nk++] = a.left[node];
+            kids[nk++] = a.right[node];
+            while (nk < 4) {
+                int best = -1;
+                double best_area = -1;
+                for (int k = 0; k < nk; k++) {
+                    if (group_leaf(a, kids[k], f, c)) continue;
+                    const double *b = a.box + 6 * (size_t)kids[k];
+                    const double x = b[3] - b[0], y = b[4] - b[1], z = b[5] - b[2];
+                    const double area = x * y + y * z + z * x;
+                    if (area > best_area) {
+                        best_area = area;
+                        best = k;
+                    }
+                }
+                if (best < 0) break;
+                const int cnode = kids[best];
+                kids[best] = a.left[cnode];
+                kids[nk++] = a.right[cnode];
+            }
         }
+        WideNodeRec w;
+        for (int k = 0; k < 4; k++) {
+            w.pad[k] = 0;
+            if (k >= nk) {
+                w.lox[k] = w.loy[k] = w.loz[k] = w.hix[k] = w.hiy[k] = w.hiz[k] = 0.f;
+                w.ref[k] = kWideNone;
+                continue;
+            }
+            const double *b = a.box + 6 * (size_t)kids[k];
+            w.lox[k] = f_down(b[0] - kBoxPad);
+            w.loy[k] = f_down(b[1] - kBoxPad);
+            w.loz[k] = f_down(b[2] - kBoxPad);
+            w.hix[k] = f_up(b[3] + kBoxPad);
+            w.hiy[k] = f_up(b[4] + kBoxPad);
+            w.hiz[k] = f_up(b[5] + kBoxPad);
+            if (group_leaf(a, kids[k], f, c)) {
+                w.ref[k] = (int32_t)(((uint32_t)f << 4) | (uint32_t)c);
+            } else {
+                const int child = atomicAdd(&a.tail[0], 1);
+                if (child < a.n) a.queue[child] = make_int2(kids[k], acc + nk - 1);  // (never more nodes than triangles: the host checks)
+                w.ref[k] = ~child;
+            }
+        }
+        need = need > acc + nk - 1 ? need : acc + nk - 1;
+        a.wnodes[q] = w;
     }
-    atomicMax(&a.tail[1], acc + nk - 1);
-    a.wnodes[q] = w;
+    if (need > 0) atomicMax(&a.tail[1], need);
+    // every atomic of this workgroup has been performed before its ticket is taken
+    __threadfence();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const int ticket = __hip_atomic_fetch_add(&a.range[R_TICKET], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (ticket != (int)gridDim.x - 1) return;
+    const int total = __hip_atomic_load(&a.tail[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&a.range[R_BEGIN], end, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&a.range[R_END], total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&a.range[R_LEVELS], a.range[R_LEVELS] + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&a.range[R_TICKET], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // Cover spheres for classify_kernel (cgrt_build.cpp cover_spheres): group g = sorted triangles [g n / G, (g + 1) n / G) --
@@ -470,108 +516,174 @@ static int build_bump_floor(const uint8_t *texels, int R, int C, const double p[
 struct MeshResult {
     int nwide = 0, stack_need = 0;
     bool balanced = false;  // the fallback build was needed
+    int levels = 0, readbacks = 0;  // of the 4-wide form; of its level counters (one per batch of levels)
     double centre[3] = {0, 0, 0}, r2 = -1.0;  // ObjRec.a / s0 (bounding sphere of the vertices, grown like the host's)
     double bmax = 0;  // largest |coordinate| of a vertex (TreeRec::bmax)
     std::vector<double> cover;  // n_groups x (cx, cy, cz, r)
 };
-// tri9_host: n x 9 doubles; tris / otris / wnodes: device destinations (n, n, n records)
-static int build_mesh_hierarchy(const double *tri9_host, int n, TriRec *tris, OTriRec *otris, WideNodeRec *wnodes, MeshResult &out) {
+
+// cover spheres of a mesh of n triangles: a function of n alone
+static inline int cover_groups(int n) {
+    int depth = 0;
+    while (depth < 6 && (n >> (depth + 1)) >= 64) depth++;
+    return 1 << depth;
+}
+
+// Everything a build of n triangles needs besides its input and its three destinations, in ONE allocation: the commit makes a
+// temporary one per mesh (with room for the uploaded vertices), a rebuild keeps one on the handle (with staging records)
+struct MeshScratch {
+    DevBuf mem;
+    size_t bytes = 0, sort_bytes = 0;
+    int n = 0, G = 0;
+    unsigned long long *gbox = nullptr, *keys_in = nullptr, *keys_out = nullptr;
+    unsigned int *idx_in = nullptr, *idx_out = nullptr;
+    int *tree = nullptr, *tail = nullptr;  // tail[4] then range[N_RANGE]: one read-back
+    double *box = nullptr, *cover = nullptr, *tri9 = nullptr;
+    int2 *queue = nullptr;
+    void *sort_tmp = nullptr;
+    TriRec *tris = nullptr;  // staging (rebuild only)
+    OTriRec *otris = nullptr;
+    WideNodeRec *wnodes = nullptr;
+
+    int alloc(int n_, bool with_tri9, bool with_staging) {
+        n = n_;
+        G = cover_groups(n);
+        const size_t N = (size_t)n;
+        HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys_in, keys_out, idx_in, idx_out, N, 0u, 63u, (hipStream_t)0));  // (sizes only)
+        size_t at = 0;
+        auto take = [&at](size_t b) { const size_t o = at; at += (b + 255) & ~(size_t)255; return o; };
+        const size_t o_gbox = take(8 * sizeof(unsigned long long)), o_tail = take((4 + N_RANGE) * sizeof(int));
+        const size_t o_k0 = take(N * 8), o_k1 = take(N * 8), o_i0 = take(N * 4), o_i1 = take(N * 4);
+        const size_t o_tree = take(7 * N * sizeof(int));  // left, right, first, last, flag: n - 1 each; parent: 2n - 1
+        const size_t o_box = take(2 * N * 6 * sizeof(double)), o_queue = take(N * sizeof(int2));
+        const size_t o_cover = take((size_t)G * 4 * sizeof(double)), o_sort = take(sort_bytes);
+        const size_t o_tri9 = take(with_tri9 ? N * 9 * sizeof(double) : 0);
+        const size_t o_tris = take(with_staging ? N * sizeof(TriRec) : 0), o_otris = take(with_staging ? N * sizeof(OTriRec) : 0);
+        const size_t o_wnodes = take(with_staging ? N * sizeof(WideNodeRec) : 0);
+        HIP_TRY(mem.alloc(at));
+        bytes = at;
+        unsigned char *m = mem.as<unsigned char>();
+        gbox = reinterpret_cast<unsigned long long *>(m + o_gbox);
+        tail = reinterpret_cast<int *>(m + o_tail);
+        keys_in = reinterpret_cast<unsigned long long *>(m + o_k0);
+        keys_out = reinterpret_cast<unsigned long long *>(m + o_k1);
+        idx_in = reinterpret_cast<unsigned int *>(m + o_i0);
+        idx_out = reinterpret_cast<unsigned int *>(m + o_i1);
+        tree = reinterpret_cast<int *>(m + o_tree);
+        box = reinterpret_cast<double *>(m + o_box);
+        queue = reinterpret_cast<int2 *>(m + o_queue);
+        cover = reinterpret_cast<double *>(m + o_cover);
+        sort_tmp = m + o_sort;
+        tri9 = with_tri9 ? reinterpret_cast<double *>(m + o_tri9) : nullptr;
+        tris = with_staging ? reinterpret_cast<TriRec *>(m + o_tris) : nullptr;
+        otris = with_staging ? reinterpret_cast<OTriRec *>(m + o_otris) : nullptr;
+        wnodes = with_staging ? reinterpret_cast<WideNodeRec *>(m + o_wnodes) : nullptr;
+        return CGRT_OK;
+    }
+};
+
+static int env_int(const char *name, int lo, int hi, int dflt) {
+    const char *e = std::getenv(name);
+    if (!e || !*e) return dflt;
+    const long v = std::strtol(e, nullptr, 10);
+    return v < lo ? lo : (v > hi ? hi : (int)v);
+}
+
+// The builder: tri9 (DEVICE, n x 9 doubles) -> tris / otris / wnodes (device destinations of n records each) and out, with every
+// launch and copy on stream st, which it synchronises: once per batch of levels for the level counters, once at the end for the
+// bounds.  Nothing is allocated here and no initial value is uploaded.
+static int build_mesh_core(const double *tri9, int n, hipStream_t st, MeshScratch &S, TriRec *tris, OTriRec *otris,
+                           WideNodeRec *wnodes, MeshResult &out) {
     out = MeshResult();
     if (n <= 0) return CGRT_OK;
     const size_t N = (size_t)n;
-    DevBuf tri9, gbox, k0, k1, i0, i1, tree, box, queue, tail, sort_tmp, cover;
-    HIP_TRY(tri9.alloc(N * 9 * sizeof(double)));
-    HIP_TRY(hipMemcpy(tri9.p, tri9_host, N * 9 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(gbox.alloc(7 * sizeof(unsigned long long)));
-    const unsigned long long ginit[7] = {~0ull, ~0ull, ~0ull, 0ull, 0ull, 0ull, 0ull};
-    HIP_TRY(hipMemcpy(gbox.p, ginit, sizeof(ginit), hipMemcpyHostToDevice));
-    HIP_TRY(k0.alloc(N * 8));
-    HIP_TRY(k1.alloc(N * 8));
-    HIP_TRY(i0.alloc(N * 4));
-    HIP_TRY(i1.alloc(N * 4));
-    // left, right, first, last, flag: n - 1 each; parent: 2n - 1
-    HIP_TRY(tree.alloc((5 * N + 2 * N) * sizeof(int)));
-    HIP_TRY(box.alloc((2 * N) * 6 * sizeof(double)));
-    HIP_TRY(queue.alloc(N * sizeof(int2)));
-    HIP_TRY(tail.alloc(4 * sizeof(int)));
     MeshArgs a;
-    a.tri9 = tri9.as<double>();
+    a.tri9 = tri9;
     a.n = n;
     a.tris = tris;
     a.otris = otris;
     a.wnodes = wnodes;
-    a.gbox = gbox.as<unsigned long long>();
-    a.keys_in = k0.as<unsigned long long>();
-    a.keys_out = k1.as<unsigned long long>();
-    a.idx_in = i0.as<unsigned int>();
-    a.idx_out = i1.as<unsigned int>();
-    int *tp = tree.as<int>();
+    a.gbox = S.gbox;
+    a.keys_in = S.keys_in;
+    a.keys_out = S.keys_out;
+    a.idx_in = S.idx_in;
+    a.idx_out = S.idx_out;
+    int *tp = S.tree;
     a.left = tp;
     a.right = tp + N;
     a.first = tp + 2 * N;
     a.last = tp + 3 * N;
     a.flag = tp + 4 * N;
     a.parent = tp + 5 * N;
-    a.box = box.as<double>();
-    a.queue = queue.as<int2>();
-    a.tail = tail.as<int>();
+    a.box = S.box;
+    a.queue = S.queue;
+    a.tail = S.tail;
+    a.range = S.tail + 4;
     const dim3 blk(256), grd((unsigned)((N + 255) / 256));
-    hipLaunchKernelGGL(mesh_prep_kernel, grd, blk, 0, 0, a);
-    hipLaunchKernelGGL(mesh_morton_kernel, grd, blk, 0, 0, a);
-    size_t tmp_bytes = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, a.keys_in, a.keys_out, a.idx_in, a.idx_out, N, 0u, 63u, (hipStream_t)0));
-    HIP_TRY(sort_tmp.alloc(tmp_bytes));
-    HIP_TRY(rocprim::radix_sort_pairs(sort_tmp.p, tmp_bytes, a.keys_in, a.keys_out, a.idx_in, a.idx_out, N, 0u, 63u, (hipStream_t)0));
-    // CGRT_DEVBUILD_BALANCED=1 (test aid, read at every build): skip the radix tree and take the fallback at once
+    hipLaunchKernelGGL(mesh_init_kernel, dim3(1), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(mesh_prep_kernel, grd, blk, 0, st, a);
+    hipLaunchKernelGGL(mesh_morton_kernel, grd, blk, 0, st, a);
+    size_t tmp_bytes = S.sort_bytes;
+    HIP_TRY(rocprim::radix_sort_pairs(S.sort_tmp, tmp_bytes, a.keys_in, a.keys_out, a.idx_in, a.idx_out, N, 0u, 63u, st));
+    // Test aids, read at every build.  CGRT_DEVBUILD_BALANCED=1: skip the radix tree and take the fallback at once;
+    // CGRT_REBUILD_BATCH: levels enqueued per read-back; CGRT_REBUILD_GRID: workgroups of a level's launch
     int first_attempt = 0;
     if (const char *e = std::getenv("CGRT_DEVBUILD_BALANCED")) first_attempt = (*e && *e != '0') ? 1 : 0;
+    const int batch = env_int("CGRT_REBUILD_BATCH", 1, 64, 8);
+    const int grid = env_int("CGRT_REBUILD_GRID", 1, 1024, (int)std::min<size_t>(256, (N + 1023) / 1024));
     for (int attempt = first_attempt; attempt < 2; attempt++) {
-        HIP_TRY(hipMemsetAsync(a.flag, 0, N * sizeof(int), 0));
+        HIP_TRY(hipMemsetAsync(a.flag, 0, N * sizeof(int), st));
         if (n > 1) {
-            if (attempt == 0) hipLaunchKernelGGL(lbvh_nodes_kernel, grd, blk, 0, 0, a);
-            else hipLaunchKernelGGL(balanced_nodes_kernel, grd, blk, 0, 0, a);
+            if (attempt == 0) hipLaunchKernelGGL(lbvh_nodes_kernel, grd, blk, 0, st, a);
+            else hipLaunchKernelGGL(balanced_nodes_kernel, grd, blk, 0, st, a);
         }
-        hipLaunchKernelGGL(lbvh_fit_kernel, grd, blk, 0, 0, a);
-        // the wide form, level by level: queue[0] = the root
-        int root = 0;
-        HIP_TRY(hipMemcpy(&root, a.tail + 2, sizeof(int), hipMemcpyDeviceToHost));
-        const int2 q0 = make_int2(root, 0);
-        const int t0[2] = {1, 0};
-        HIP_TRY(hipMemcpy(a.queue, &q0, sizeof(q0), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(a.tail, t0, sizeof(t0), hipMemcpyHostToDevice));
-        int begin = 0, end = 1;
-        while (begin < end) {
-            hipLaunchKernelGGL(wide_level_kernel, dim3((unsigned)((end - begin + 255) / 256)), blk, 0, 0, a, begin, end);
-            int t[2];
-            HIP_TRY(hipMemcpy(t, a.tail, sizeof(t), hipMemcpyDeviceToHost));
-            begin = end;
-            end = t[0];
-            out.stack_need = t[1];
-            if (end > n) return fail(CGRT_ERR_DEVICE, "device hierarchy build: more wide nodes than triangles");
+        hipLaunchKernelGGL(lbvh_fit_kernel, grd, blk, 0, st, a);
+        // the wide form, level by level, a batch of levels per read-back of {nwide, stack need, root | begin, end, levels, ticket}
+        hipLaunchKernelGGL(wide_init_kernel, dim3(1), dim3(64), 0, st, a);
+        int t[4 + N_RANGE];
+        for (int rounds = 0;; rounds++) {
+            for (int b = 0; b < batch; b++) hipLaunchKernelGGL(wide_level_kernel, dim3((unsigned)grid), blk, 0, st, a);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(t, S.tail, sizeof(t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            out.readbacks++;
+            if (t[0] > n) return fail(CGRT_ERR_DEVICE, "device hierarchy build: more wide nodes than triangles");
+            if (t[4 + R_BEGIN] >= t[4 + R_END]) break;
+            if ((long long)rounds * batch > (long long)n + 1) return fail(CGRT_ERR_DEVICE, "device hierarchy build: more levels than triangles");
         }
-        out.nwide = end;
+        out.nwide = t[0];
+        out.stack_need = t[1];
+        out.levels = t[4 + R_LEVELS];
         out.balanced = attempt == 1;
         if (out.stack_need < kWideStack) break;
         if (attempt == 1) return fail(CGRT_ERR_LIMIT, "device hierarchy build: stack bound missed by the balanced tree");
     }
     // bounding sphere (add_mesh_triangles) and cover spheres (cover_spheres)
+    hipLaunchKernelGGL(cover_kernel, dim3((unsigned)S.G), dim3(256), 0, st, a, S.G, S.cover);
+    HIP_TRY(hipGetLastError());
     unsigned long long g[7];
-    HIP_TRY(hipMemcpy(g, gbox.p, sizeof(g), hipMemcpyDeviceToHost));
+    out.cover.resize((size_t)S.G * 4);
+    HIP_TRY(hipMemcpyAsync(g, S.gbox, sizeof(g), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out.cover.data(), S.cover, out.cover.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     for (int k = 0; k < 3; k++) {
         out.centre[k] = 0.5 * (dunkey(g[k]) + dunkey(g[3 + k]));
         out.bmax = std::max(out.bmax, std::max(std::fabs(dunkey(g[k])), std::fabs(dunkey(g[3 + k]))));
     }
     const double r = std::sqrt(dunkey(g[6])) + 1e-3;
     out.r2 = r * r * (1 + 1e-9);
-    int depth = 0;
-    while (depth < 6 && (n >> (depth + 1)) >= 64) depth++;
-    const int G = 1 << depth;
-    HIP_TRY(cover.alloc((size_t)G * 4 * sizeof(double)));
-    hipLaunchKernelGGL(cover_kernel, dim3((unsigned)G), dim3(256), 0, 0, a, G, cover.as<double>());
-    HIP_TRY(hipGetLastError());
-    out.cover.resize((size_t)G * 4);
-    HIP_TRY(hipMemcpy(out.cover.data(), cover.p, out.cover.size() * sizeof(double), hipMemcpyDeviceToHost));
     return CGRT_OK;
+}
+
+// The commit's form: tri9_host: n x 9 doubles; tris / otris / wnodes: device destinations (n, n, n records).  A temporary
+// scratch, the null stream.
+static int build_mesh_hierarchy(const double *tri9_host, int n, TriRec *tris, OTriRec *otris, WideNodeRec *wnodes, MeshResult &out) {
+    out = MeshResult();
+    if (n <= 0) return CGRT_OK;
+    MeshScratch S;
+    if (const int rc = S.alloc(n, true, false)) return rc;
+    HIP_TRY(hipMemcpy(S.tri9, tri9_host, (size_t)n * 9 * sizeof(double), hipMemcpyHostToDevice));
+    return build_mesh_core(S.tri9, n, (hipStream_t)0, S, tris, otris, wnodes, out);
 }
 
 }  // namespace devbuild

@@ -169,6 +169,8 @@ public:
 
 #include "cgrt_tile_order.hpp"
 
+#include "cgrt_devbuild.hpp"
+
 // What the first cgrt_scene_refit_mesh of a mesh leaves on the handle (cgrt_refit.hpp): the plan (cgrt_refit_plan.h) and its
 // device copy behind the words every refit clears on its stream
 struct RefitNode {
@@ -184,6 +186,15 @@ struct RefitState {
     const int2 *srcrec = nullptr;
     int64_t refits = 0;
     double ms_plan = 0;  // wall-clock of building and uploading the plan (the first refit's read-backs included)
+    bool stale = false;  // a rebuild changed the topology: the plan is dropped (its memory too), the next refit builds it again
+};
+// What the first cgrt_scene_rebuild_mesh of a mesh leaves on the handle (cgrt_rebuild.hpp): the builder's scratch with staging
+// records, and what the last rebuild did
+struct RebuildState {
+    devbuild::MeshScratch scratch;
+    int64_t rebuilds = 0;
+    int32_t balanced = 0, levels = 0, readbacks = 0;
+    double ms_last = 0;
 };
 
 struct cgrt_scene {
@@ -221,6 +232,10 @@ struct cgrt_scene {
     // and the count of refits of the scene: the photon-mapping sessions remember the one they were created under
     std::map<int, std::unique_ptr<RefitState>> refit;
     uint64_t geometry_gen = 0;
+    // cgrt_scene_rebuild_mesh: per rebuilt mesh object the builder's scratch (allocated by its first rebuild)
+    std::map<int, std::unique_ptr<RebuildState>> rebuild;
+    // cgrt_scene_mesh_cost: one partial sum per workgroup of tree_cost_kernel
+    mutable GrowBuf cost_partials;
 };
 
 template <class T>
@@ -236,8 +251,6 @@ static int upload(cgrt_scene *s, const std::vector<T> &v, const T **out, size_t 
     *out = reinterpret_cast<const T *>(p);
     return CGRT_OK;
 }
-
-#include "cgrt_devbuild.hpp"
 
 extern "C" {
 
@@ -262,7 +275,7 @@ int cgrt_scene_create(cgrt_scene **out) {
 
 void cgrt_scene_destroy(cgrt_scene *s) {
     if (!s) return;
-    if (!s->allocs.empty() || s->scratch.p || s->order.buf.p || s->relay.buf.p || s->lens.buf.p || s->lens.ev || s->tri_ids.p || s->aux_stream || s->order.ev || s->relay.ev || !s->refit.empty()) {
+    if (!s->allocs.empty() || s->scratch.p || s->order.buf.p || s->relay.buf.p || s->lens.buf.p || s->lens.ev || s->tri_ids.p || s->aux_stream || s->order.ev || s->relay.ev || !s->refit.empty() || !s->rebuild.empty() || s->cost_partials.p) {
         DeviceGuard g(s->device);
         if (g.err == hipSuccess) {
             for (void *p : s->allocs) (void)hipFree(p);
@@ -272,6 +285,8 @@ void cgrt_scene_destroy(cgrt_scene *s) {
             s->lens.release();
             s->tri_ids.release();
             s->refit.clear();
+            s->rebuild.clear();
+            s->cost_partials.release();
             if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
             if (s->ev_join) (void)hipEventDestroy(s->ev_join);
             if (s->aux_stream) (void)hipStreamDestroy(s->aux_stream);
@@ -541,6 +556,8 @@ int cgrt_scene_get_stats(const cgrt_scene *s, cgrt_scene_stats *out) {
     out->scene_bytes_fp64 = bytes;
     out->device_bytes = s->device_bytes + (int64_t)s->scratch.cap + (int64_t)s->order.buf.cap + (int64_t)s->tri_ids.cap;  // uploaded scene + the handle's launch scratch (+ the hit-attribute table once asked for)
     for (const auto &r : s->refit) out->device_bytes += (int64_t)r.second->bytes;  // (+ the refit plans)
+    for (const auto &r : s->rebuild) out->device_bytes += (int64_t)r.second->scratch.bytes;  // (+ the rebuilds' scratch)
+    out->device_bytes += (int64_t)s->cost_partials.cap;
     out->committed = s->committed ? 1 : 0;
     return CGRT_OK;
 }
@@ -631,6 +648,8 @@ int cgrt_scene_tree_dump(const cgrt_scene *s, int t, int32_t *node_lr_size, int3
 }  // extern "C"
 
 #include "cgrt_refit.hpp"
+#include "cgrt_rebuild.hpp"
+#include "cgrt_tree_cost.hpp"
 
 // ---- LDS of a launch ----
 // A workgroup may use at most a CU's LDS (MI355X: 160 KiB): the kernel's static __shared__ bytes plus the dynamic bytes of

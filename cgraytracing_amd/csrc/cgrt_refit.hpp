@@ -210,24 +210,28 @@ __global__ void refit_finish_kernel(Args a) {
 static const char *const kRefitStale = "the scene was refitted after this session was created";
 
 // Which tree a refit of object `obj` works on, after every check that needs no device.  *tree = -1: an empty mesh, nothing to do.
-static int refit_check(const cgrt_scene *s, int obj, const double *tri9, int ntri, int *tree) {
+// The rebuild (what = "rebuild") and the tree cost (what = "cost", which takes no vertices: cost = true) refuse the same.
+static int refit_check(const cgrt_scene *s, int obj, const double *tri9, int ntri, int *tree, const char *what = "refit", bool cost = false) {
+    const std::string who = what;
     *tree = -1;
-    if (!s) return fail(CGRT_ERR_INVALID, "refit: null scene");
-    if (!s->committed) return fail(CGRT_ERR_INVALID, "refit: scene not committed");
-    if (obj < 0 || obj >= (int)s->host.objs.size()) return fail(CGRT_ERR_INVALID, "refit: no such object");
+    if (!s) return fail(CGRT_ERR_INVALID, who + ": null scene");
+    if (!s->committed) return fail(CGRT_ERR_INVALID, who + ": scene not committed");
+    if (obj < 0 || obj >= (int)s->host.objs.size()) return fail(CGRT_ERR_INVALID, who + ": no such object");
     const ObjRec &o = s->host.objs[(size_t)obj];
-    if (o.kind == KIND_SPHERE) return fail(CGRT_ERR_INVALID, "refit: the object is a sphere, not a mesh");
-    if (o.kind == KIND_BEZIER) return fail(CGRT_ERR_INVALID, "refit: the object is a Bezier surface, not a mesh");
+    if (o.kind == KIND_SPHERE) return fail(CGRT_ERR_INVALID, who + ": the object is a sphere, not a mesh");
+    if (o.kind == KIND_BEZIER) return fail(CGRT_ERR_INVALID, who + ": the object is a Bezier surface, not a mesh");
     if (o.kind == KIND_PLANE)
-        return fail(CGRT_ERR_INVALID, o.tree >= 0 ? "refit: the object is a bump floor, not a mesh" : "refit: the object is a plane, not a mesh");
-    if (o.kind != KIND_MESH || o.tree < 0 || o.tree >= (int)s->tree_recs.size()) return fail(CGRT_ERR_INVALID, "refit: the object is no mesh");
+        return fail(CGRT_ERR_INVALID, o.tree >= 0 ? who + ": the object is a bump floor, not a mesh" : who + ": the object is a plane, not a mesh");
+    if (o.kind != KIND_MESH || o.tree < 0 || o.tree >= (int)s->tree_recs.size()) return fail(CGRT_ERR_INVALID, who + ": the object is no mesh");
+    if (!(o.transp < kEps) && cost) return fail(CGRT_ERR_INVALID, who + ": the mesh is transparent: its tree has no 4-wide hierarchy");
     if (!(o.transp < kEps))
-        return fail(CGRT_ERR_INVALID, "refit: the mesh is transparent (its improvement counter makes the leaf order observable, quirk Q5)");
+        return fail(CGRT_ERR_INVALID, who + ": the mesh is transparent (its improvement counter makes the leaf order observable, quirk Q5)");
     const TreeRec &tr = s->tree_recs[(size_t)o.tree];
-    if (ntri != tr.ntris) return fail(CGRT_ERR_INVALID, "refit: ntri is not the mesh's triangle count (" + std::to_string(tr.ntris) + ")");
+    if (cost) ntri = tr.ntris;
+    if (ntri != tr.ntris) return fail(CGRT_ERR_INVALID, who + ": ntri is not the mesh's triangle count (" + std::to_string(tr.ntris) + ")");
     if (ntri == 0) return CGRT_OK;
-    if (!tr.tri_level || tr.nwide <= 0) return fail(CGRT_ERR_INVALID, "refit: the tree has no 4-wide hierarchy (CGRT_TREE=ref)");
-    if (!tri9) return fail(CGRT_ERR_INVALID, "refit: null tri9");
+    if (!tr.tri_level || tr.nwide <= 0) return fail(CGRT_ERR_INVALID, who + ": the tree has no 4-wide hierarchy (CGRT_TREE=ref)");
+    if (!tri9 && !cost) return fail(CGRT_ERR_INVALID, who + ": null tri9");
     *tree = o.tree;
     return CGRT_OK;
 }
@@ -268,9 +272,13 @@ static int tree_refit_plan(const cgrt_scene *s, int t, RefitPlan &plan) {
 // The first refit of a mesh: its plan, and the plan's device copy in front of the words every refit clears
 static int refit_prepare(cgrt_scene *s, int obj, int t, RefitState **out) {
     auto it = s->refit.find(obj);
+    int64_t refits_so_far = 0;
     if (it != s->refit.end()) {
-        *out = it->second.get();
-        return CGRT_OK;
+        if (!it->second->stale) {
+            *out = it->second.get();
+            return CGRT_OK;
+        }
+        refits_so_far = it->second->refits;  // (a rebuild dropped the plan: built again here, the count goes on)
     }
     const auto t0 = std::chrono::steady_clock::now();
     std::unique_ptr<RefitState> st(new (std::nothrow) RefitState());
@@ -298,6 +306,7 @@ static int refit_prepare(cgrt_scene *s, int obj, int t, RefitState **out) {
     st->nodes = reinterpret_cast<const RefitNode *>(base + nodes_at);
     st->srcrec = reinterpret_cast<const int2 *>(base + srcrec_at);
     st->ms_plan = ms_since(t0);
+    st->refits = refits_so_far;
     *out = st.get();
     s->refit[obj] = std::move(st);
     return CGRT_OK;
@@ -395,7 +404,7 @@ int cgrt_scene_refit_info(const cgrt_scene *s, int obj, cgrt_refit_info *out) {
     const auto it = s->refit.find(obj);
     if (it != s->refit.end()) {
         out->refits = it->second->refits;
-        out->plan_built = 1;
+        out->plan_built = it->second->stale ? 0 : 1;
         out->ms_plan = it->second->ms_plan;
     }
     out->geometry_gen = s->geometry_gen;

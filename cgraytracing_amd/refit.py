@@ -1,4 +1,4 @@
-"""Refit: new vertices for a committed opaque mesh (include/cgrt.h, "refit").
+"""Refit and rebuild: new vertices for a committed opaque mesh (include/cgrt.h, "refit" and "rebuild"; DESIGN.md sections 16, 17).
 
 `Scene` here is engine.Scene with the refit calls added, and it is what `cgraytracing_amd.Scene` names: engine.py's public
 surface is pinned to a recorded table (tests/test_py_binding_host.py), so the calls of a new capability live in a module of
@@ -25,9 +25,9 @@ class Scene(engine.Scene):
         and refusals: include/cgrt.h."""
         self._refit(self._torch(), "refit_mesh", obj, tris, stream)
 
-    def _refit(self, A, what, obj, tris, stream):
+    def _refit(self, A, what, obj, tris, stream, call="refit"):
         n, tris = A.triangles(what, tris)
-        check(getattr(self._L, "cgrt_scene_refit_mesh" + A.suffix)(self._h, int(obj), A.ptr(tris), n, *A.stream(stream)))
+        check(getattr(self._L, "cgrt_scene_%s_mesh" % call + A.suffix)(self._h, int(obj), A.ptr(tris), n, *A.stream(stream)))
 
     def refit_mesh_host(self, obj, tris):
         """Synchronous form of refit_mesh on a numpy array (no torch needed); it also refreshes the handle's host mirrors
@@ -39,6 +39,30 @@ class Scene(engine.Scene):
         ri = _capi.RefitInfo()
         check(self._L.cgrt_scene_refit_info(self._h, int(obj), C.byref(ri)))
         return {f: getattr(ri, f) for f, _ in ri._fields_}
+
+    def rebuild_mesh(self, obj, tris, stream=None):
+        """cgrt_scene_rebuild_mesh on a torch tensor (as refit_mesh's): object `obj` -- an opaque mesh whose tree was built on
+        the device (build="device") -- gets these vertices and the hierarchy a fresh device-build commit of them builds, in
+        place, by kernels on torch's current stream (or `stream`), which the call synchronises.  Refusals: include/cgrt.h."""
+        self._refit(self._torch(), "rebuild_mesh", obj, tris, stream, "rebuild")
+
+    def rebuild_mesh_host(self, obj, tris):
+        """The same on a numpy array (no torch needed); it also refreshes the triangles tree_dump returns."""
+        self._refit(_buffers.NUMPY, "rebuild_mesh_host", obj, tris, None, "rebuild")
+
+    def rebuild_info(self, obj):
+        """cgrt_scene_rebuild_info: dict(rebuilds, nwide, stack_need, balanced, levels, readbacks, ms_last, scratch_bytes)."""
+        ri = _capi.RebuildInfo()
+        check(self._L.cgrt_scene_rebuild_info(self._h, int(obj), C.byref(ri)))
+        return {f: getattr(ri, f) for f, _ in ri._fields_ if f != "pad_"}
+
+    def mesh_cost(self, obj):
+        """cgrt_scene_mesh_cost_host: dict(node_cost, tri_cost, root_area), the surface-area cost of the 4-wide hierarchy the
+        device walks for mesh `obj` now.  Rule of thumb: rebuild when node_cost + tri_cost exceeds some multiple of its value
+        after the last build."""
+        tc = _capi.TreeCost()
+        check(self._L.cgrt_scene_mesh_cost_host(self._h, int(obj), C.byref(tc)))
+        return {f: getattr(tc, f) for f, _ in tc._fields_}
 
     def refit_plan(self, t=0):
         """(parent [nwide], slot [nwide], arrivals [nwide], src [ntris]): see cgrt_scene_refit_plan_host."""

@@ -4,10 +4,13 @@ The scene is committed ONCE.  Every frame makes the new vertices in torch on the
 hierarchy keeps its topology, its boxes, the triangle records and the mesh's bounding and cover spheres are recomputed by
 kernels on the same stream, with no copy through the host -- and renders through trace_grid:
 
-    python examples/deforming_mesh.py OUT [frames] [mesh]
+    python examples/deforming_mesh.py OUT [frames] [mesh] [--rebuild-at RATIO]
 
 writes OUT_00.png, OUT_01.png, ... (mesh: dragon or bunny).  Destroying, adding and committing the scene per frame would give
 the same pictures and cost the build every time (README, "Refit").
+
+--rebuild-at RATIO (off by default): after each refit the hierarchy's surface-area cost (Scene.mesh_cost) is compared with its
+value after the last build; once it exceeds RATIO times that, the mesh is rebuilt in place (Scene.rebuild_mesh) for the pose.
 """
 import os
 import sys
@@ -34,7 +37,7 @@ def twist(tris, turns):
     return q.reshape(-1, 9).contiguous()
 
 
-def main(out="deforming", frames=6, mesh="dragon", W=512, H=384, spp=8):
+def main(out="deforming", frames=6, mesh="dragon", W=512, H=384, spp=8, rebuild_at=None):
     frames = int(frames)
     if mesh == "dragon":
         tris, colour, kind = scenes.dragon_tris(), (0.25, 0.25, 0.5), 1
@@ -45,17 +48,33 @@ def main(out="deforming", frames=6, mesh="dragon", W=512, H=384, spp=8):
     sc = cg.Scene(objs, build="device")
     rest = torch.as_tensor(np.ascontiguousarray(tris), device=torch.device("cuda", sc.device))
     cam = scenes.cam_dof()
+    total = lambda c: c["node_cost"] + c["tri_cost"]
+    built = total(sc.mesh_cost(obj)) if rebuild_at else 0.0
     for f in range(frames):
         pose = twist(rest, 2.5 * np.sin(2 * np.pi * f / max(frames, 1)))
         sc.refit_mesh(obj, pose)  # asynchronous on torch's current stream, as is the frame behind it
+        if rebuild_at:
+            cost = total(sc.mesh_cost(obj))
+            if cost > rebuild_at * built:
+                sc.rebuild_mesh(obj, pose)  # synchronises the stream
+                built = total(sc.mesh_cost(obj))
+                print("frame %d: cost %.1f after the refit, rebuilt: %.1f" % (f, cost, built))
         image, _, _ = sc.trace_grid(W, H, spp, cam, 5, 12345)
         path = "%s_%02d.png" % (out, f)
         cg.write_png(path, cg.tonemap_rgb8(image.double().cpu().numpy()))  # (.cpu() waits for the stream: `pose` may go now)
         print(path)
     inf = sc.refit_info(obj)
     print("%d refits of %d triangles (%d wide nodes); the plan took %.2f ms, once" % (inf["refits"], inf["ntris"], inf["nwide"], inf["ms_plan"]))
+    if rebuild_at:
+        print("%d rebuilds at cost ratio %.2f" % (sc.rebuild_info(obj)["rebuilds"], rebuild_at))
     sc.close()
 
 
 if __name__ == "__main__":
-    main(*sys.argv[1:4])
+    args = sys.argv[1:]
+    ratio = None
+    if "--rebuild-at" in args:
+        at = args.index("--rebuild-at")
+        ratio = float(args[at + 1])
+        del args[at:at + 2]
+    main(*args[:3], rebuild_at=ratio)

@@ -20,7 +20,8 @@
  * cost-ordered frame; the tile order of an image-order one; the queue counter of cgrt_trace_rays, cgrt_trace_rays_hitpoints and cgrt_ppm_session_create_rays, which
  * are such launches (cgrt_occlusion_rays and cgrt_bounce_rays use that counter too); cgrt_ray_hit_attributes is one too: its first call that asks for `prim` builds a table the handle keeps;
  * cgrt_wavefront_rays uses the queue counter and keeps its work memory on the handle, and it synchronises its stream, so it cannot be stream-captured;
- * cgrt_scene_refit_mesh WRITES the scene's device arrays and keeps a plan and arrival counters on the handle: every launch that reads the scene is ordered against it).
+ * cgrt_scene_refit_mesh WRITES the scene's device arrays and keeps a plan and arrival counters on the handle: every launch that reads the scene is ordered against it;
+ * cgrt_scene_rebuild_mesh WRITES them too, keeps its build scratch on the handle, and it synchronises its stream, so it cannot be stream-captured).
  * All geometry is IEEE double, like the reference (Vec3 = 3 x double, vec3.h:11-30).
  */
 #ifndef CGRT_H
@@ -51,7 +52,10 @@ extern "C" {
                             (stochastic progressive photon mapping); cgrt_posed_camera, CGRT_GRID_POSED, cgrt_look_at
                             (posed camera: a library without them has no cgrt_look_at symbol, and CGRT_GRID_POSED was an
                             unknown bit that it ignored); cgrt_scene_refit_mesh, cgrt_scene_refit_mesh_host, cgrt_refit_info,
-                            cgrt_scene_refit_info, cgrt_scene_refit_plan_host (refit of committed opaque meshes) */
+                            cgrt_scene_refit_info, cgrt_scene_refit_plan_host (refit of committed opaque meshes);
+                            cgrt_scene_rebuild_mesh, cgrt_scene_rebuild_mesh_host, cgrt_rebuild_info, cgrt_scene_rebuild_info,
+                            cgrt_tree_cost, cgrt_scene_mesh_cost, cgrt_scene_mesh_cost_host (in-place rebuild of device-built
+                            opaque meshes, and the tree cost that tells when one pays) */
 
 enum {
     CGRT_OK = 0,
@@ -445,6 +449,57 @@ int cgrt_scene_refit_info(const cgrt_scene *s, int obj, cgrt_refit_info *out);
  * cgrt_scene_wide_dump: with the four arrays NULL only *nwide and *ntris are written; a tree without the wide form gives 0, 0. */
 int cgrt_scene_refit_plan_host(const cgrt_scene *s, int tree, int32_t *nwide, int32_t *ntris, int32_t *parent, int32_t *slot,
                                int32_t *arrivals, int32_t *src);
+
+/* ---- rebuild: a new hierarchy for a committed, DEVICE-BUILT opaque mesh, in place -----------------
+ * A refit keeps the topology of the pose the tree was built for, and frames get slower as the mesh moves away from it.
+ * cgrt_scene_rebuild_mesh gives mesh object `obj` the vertices tri9 (n x 9 doubles, the layout and construction order of
+ * cgrt_scene_add_mesh_triangles; the triangle count stays) and the hierarchy a fresh CGRT_BUILD_DEVICE commit of these vertices
+ * builds: Morton sort, radix tree (or the balanced fallback, also on CGRT_DEVBUILD_BALANCED), the 4-wide form -- the same tree up
+ * to the numbering of wide nodes inside a level, which comes from an atomic counter and is not fixed from run to run.  Triangle
+ * records, wide nodes, the object's bounding sphere, the tree's error bound and its cover spheres are recomputed; the handle,
+ * every other object and the hit-attribute table stay.  Parity class: that of CGRT_BUILD_DEVICE itself.
+ * cgrt_scene_rebuild_mesh: tri9 is a DEVICE pointer on the scene's device.  The call enqueues on `stream` (a hipStream_t, NULL =
+ * the null stream) and synchronises it -- the host needs the node count and the stack bound, a few words read back once per
+ * batch of levels --, so it cannot be stream-captured.  Work enqueued earlier on the stream sees the old mesh, everything enqueued
+ * after the call returns sees the new one.  The hierarchy is built in scratch memory and put in place by device-to-device
+ * copies only once the host has seen that it fits the walk's stack: on any error return the committed scene is exactly as
+ * before the call.  The scratch (sort keys, the binary tree, boxes, the level queue, staging records) is allocated by the mesh's
+ * first rebuild, kept on the handle, counted in cgrt_scene_stats.device_bytes and freed with the scene; later rebuilds allocate
+ * nothing.
+ * cgrt_scene_rebuild_mesh_host: tri9 is a host pointer; null stream; it also refreshes the triangles cgrt_scene_tree_dump returns.
+ * Both refresh the handle's host mirrors of the bounding sphere, the error bound and the cover spheres.
+ * Accepted: an opaque mesh of a committed scene whose tree was built on the device.  Refused with CGRT_ERR_INVALID, before any
+ * device is touched: everything cgrt_scene_refit_mesh refuses, and a mesh whose tree was built on the host (its arrays have
+ * room for that one topology only, and its triangle records are in leaf order: commit the scene under CGRT_BUILD_DEVICE).
+ * ntri == 0 is accepted and does nothing.
+ * Afterwards: the mesh's refit plan is dropped and built again by its next refit (cgrt_refit_info.plan_built is 0 until then,
+ * .refits keeps counting); the scene's geometry count grows by one, so photon-mapping sessions created before refuse as after a
+ * refit.  Test aids, read at every build: CGRT_REBUILD_BATCH (levels enqueued per read-back, 1..64, default 8) and
+ * CGRT_REBUILD_GRID (workgroups of a level's launch, default sized from ntri); they serve the commit's device build too. */
+int cgrt_scene_rebuild_mesh(cgrt_scene *s, int obj, const double *tri9_dev, int ntri, void *stream);
+int cgrt_scene_rebuild_mesh_host(cgrt_scene *s, int obj, const double *tri9, int ntri);
+typedef struct cgrt_rebuild_info {
+    int64_t rebuilds;           /* rebuilds of this mesh so far                                                        */
+    int32_t nwide, stack_need;  /* the current tree: wide nodes, deepest the walk's stack can get                      */
+    int32_t balanced;           /* 1: the last rebuild needed the balanced fallback                                    */
+    int32_t levels, readbacks;  /* the last rebuild: levels of the 4-wide form, read-backs of the level counters       */
+    int32_t pad_;
+    double ms_last;             /* wall-clock of the last rebuild, its synchronisation included                        */
+    int64_t scratch_bytes;      /* device memory the mesh's rebuilds keep on the handle                                */
+} cgrt_rebuild_info;            /* 48 bytes */
+int cgrt_scene_rebuild_info(const cgrt_scene *s, int obj, cgrt_rebuild_info *out);
+
+/* The surface-area cost of the 4-wide hierarchy the device currently walks for opaque mesh `obj` (host-built, device-built,
+ * refitted or rebuilt), read from the device's records.  With S(b) = 2(xy + yz + zx) of a slot's fp32 box, the extents taken
+ * as (double)hi - (double)lo: root_area = S of the union of the root node's used slots; node_cost = 1 + the sum over inner
+ * slots of S / root_area; tri_cost = the sum over leaf slots of count * S / root_area.  A caller's rule of thumb: rebuild when
+ * tri_cost + node_cost exceeds some multiple of its value after the last build; the library picks no multiple.
+ * cgrt_scene_mesh_cost: asynchronous on `stream`; cost3_dev = DEVICE room for {node_cost, tri_cost, root_area}.
+ * cgrt_scene_mesh_cost_host: null stream, synchronises.  Refusals as for the refit, except that a transparent mesh is refused
+ * as having no 4-wide hierarchy; an empty mesh gives zeros. */
+typedef struct cgrt_tree_cost { double node_cost, tri_cost, root_area; } cgrt_tree_cost; /* 24 bytes */
+int cgrt_scene_mesh_cost(const cgrt_scene *s, int obj, double *cost3_dev, void *stream);
+int cgrt_scene_mesh_cost_host(const cgrt_scene *s, int obj, cgrt_tree_cost *out);
 
 /* ---- the hot path -------------------------------------------------------------------------------------
  * Renders grid->rows rows: for every pixel and sample it runs the reference's trace(flag=true) recursion

@@ -835,9 +835,12 @@ class SppmSession {
 // A scene committed ONCE whose opaque meshes move between frames (cgrt_scene_refit_mesh_host): refit_mesh gives object `obj` --
 // its position in objs -- new vertices, 9 doubles per triangle in the order the mesh was made from; the hierarchy keeps its
 // topology and the next render sees the moved mesh.  What may be refitted, the refusals and the parity class: cgrt.h.
+// rebuild gives a device-built mesh a new topology too; cost tells when that pays.
 class DeformingScene {
   public:
-    explicit DeformingScene(const std::vector<Object *> &objs, int device = 0) {
+    // build: CGRT_BUILD_HOST / CGRT_BUILD_DEVICE for this scene's structures, or -1 for the default (rebuild() needs the latter)
+    explicit DeformingScene(const std::vector<Object *> &objs, int device = 0, int build = -1) {
+        if (build >= 0) check(cgrt_scene_set_build(sb_.scene, build));
         for (const Object *o : objs) o->add_to(sb_);
         check(cgrt_scene_commit(sb_.scene, device));
     }
@@ -849,6 +852,24 @@ class DeformingScene {
         cgrt_refit_info inf;
         check(cgrt_scene_refit_info(sb_.scene, obj, &inf));
         return inf;
+    }
+    // A new hierarchy for these vertices, in place (cgrt_scene_rebuild_mesh_host): what a refit's kept topology costs in frame
+    // time, a rebuild cures.  The mesh must have been built on the device (the constructor's build = CGRT_BUILD_DEVICE).
+    void rebuild(int obj, const std::vector<double> &tri9) {
+        if (tri9.size() % 9) throw Error(CGRT_ERR_INVALID, "rebuild: 9 doubles per triangle");
+        check(cgrt_scene_rebuild_mesh_host(sb_.scene, obj, tri9.data(), (int)(tri9.size() / 9)));
+    }
+    cgrt_rebuild_info rebuild_info(int obj) const {
+        cgrt_rebuild_info inf;
+        check(cgrt_scene_rebuild_info(sb_.scene, obj, &inf));
+        return inf;
+    }
+    // The surface-area cost of the hierarchy the device walks for mesh `obj` now (cgrt_scene_mesh_cost_host).  Rule of thumb:
+    // rebuild when node_cost + tri_cost exceeds some multiple of its value after the last build.
+    cgrt_tree_cost cost(int obj) const {
+        cgrt_tree_cost c;
+        check(cgrt_scene_mesh_cost_host(sb_.scene, obj, &c));
+        return c;
     }
     // render()'s eye pass on the scene as it stands (rp.device is the constructor's)
     void render(const RenderParams &rp, std::vector<float> &image, RenderStats *stats = nullptr) const {
