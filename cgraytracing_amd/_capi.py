@@ -258,6 +258,8 @@ SIGNATURES = {
     "cgrt_scene_rebuild_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RebuildInfo)]),
     "cgrt_scene_mesh_cost": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cgrt_scene_mesh_cost_host": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(TreeCost)]),
+    "cgrt_scene_mesh_bounds_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_void_p,
+                                              C.c_int32, C.POINTER(C.c_int32)]),
     "cgrt_lens_samples": (C.c_int, [C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
     "cgrt_surface_colors": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "cgrt_trace_grid_variant": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Grid), C.c_char_p, C.c_size_t]),

@@ -776,7 +776,7 @@ static void cover_spheres(const std::vector<double> &tri9, int depth, std::vecto
                 r2 = std::max(r2, dx * dx + dy * dy + dz * dz);
             }
         }
-        out.insert(out.end(), {c[0], c[1], c[2], std::sqrt(r2) + 1e-3});
+        out.insert(out.end(), {c[0], c[1], c[2], cover_radius(r2)});
     }
 }
 
@@ -812,7 +812,7 @@ int HostScene::add_mesh_triangles(const double *tri9, int ntri, const double sc[
             o.s0 = -1.0;  // empty mesh: nothing to hit
         } else {
             for (int k = 0; k < 3; k++) o.a[k] = cover[first + k];
-            o.s0 = cover[first + 3] * cover[first + 3] * (1 + 1e-9);
+            o.s0 = sphere_s0(cover[first + 3]);
             cover.resize(first);
             // the same bound in pieces (<= 2^kCoverDepth spheres over median-split groups of triangles), for classify_kernel:
             // a long thin mesh fills a small part of its one sphere's silhouette
@@ -922,10 +922,6 @@ CommitKnobs commit_knobs() {
     if (prio && std::strcmp(prio, "high") == 0) k.aux_priority = AUX_HIGH;
     return k;
 }
-
-// bound on |coordinate| of every box face (the fp32 box test's error term, cgrt_traverse.hpp Ray32): the vertices' largest
-// magnitude, the growth of the boxes and a little more
-float tree_bmax(double max_abs) { return (float)((max_abs + 2 * kBoxPad) * (1 + 1e-6)) * (1.f + 1e-6f); }
 
 namespace {
 

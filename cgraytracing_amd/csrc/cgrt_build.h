@@ -3,6 +3,7 @@
 // scene on the CPU; the per-ray work is all in cgrt_hip.hip.
 #ifndef CGRT_BUILD_H
 #define CGRT_BUILD_H
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -50,7 +51,6 @@ struct HostTree {
     int dev_tex = -1;           // bump floor: texture index
     double dev_plane_y = 0;     // bump floor: the plane's y (objects.h:489-492)
     int dev_obj = -1;           // mesh: the owning object (its bounding sphere is computed by the device build)
-    size_t dev_cover_at = 0;    // mesh: where its cover spheres go in HostScene::cover (appended at commit)
     // filled by the commit for the verification dumps (cgrt_scene_wide_dump on a device-built tree reads the device arrays)
     int32_t dev_nwide = 0;
     bool dev_balanced = false;
@@ -111,8 +111,19 @@ struct CommitKnobs {
 };
 CommitKnobs commit_knobs();
 
-// TreeRec::bmax from the largest |coordinate| of a tree's vertices: the growth of the boxes and a little more
-float tree_bmax(double max_abs);
+#if defined(__HIPCC__)
+#define CGRT_BOUNDS_HD __host__ __device__ inline
+#else
+#define CGRT_BOUNDS_HD inline
+#endif
+// The bounds formulas, written once for the host builder, the device builder's host tail and the refit's kernels:
+// TreeRec::bmax from the largest |coordinate| of a tree's vertices -- a bound on |coordinate| of every box face (the fp32 box
+// test's error term, cgrt_traverse.hpp Ray32): the growth of the boxes and a little more;
+CGRT_BOUNDS_HD float tree_bmax(double max_abs) { return (float)((max_abs + 2 * kBoxPad) * (1 + 1e-6)) * (1.f + 1e-6f); }
+// the radius of a sphere around vertices whose largest squared distance from its centre is r2 (1e-3: far above the triangle
+// test's rounding), and ObjRec::s0 of a mesh's bounding sphere of that radius
+CGRT_BOUNDS_HD double cover_radius(double r2) { return std::sqrt(r2) + 1e-3; }
+CGRT_BOUNDS_HD double sphere_s0(double r) { return r * r * (1 + 1e-9); }
 
 // Where every record of the device arrays goes.  Host-built records come first, in tree order.  Behind them each array keeps
 // room for what the device builds (HostTree::dev_kind) write at commit, again in tree order; that room has no host copy.

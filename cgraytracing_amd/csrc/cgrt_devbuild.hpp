@@ -28,6 +28,8 @@
 
 namespace devbuild {
 
+using namespace mesh_bounds;
+
 // order-preserving map double -> uint64 (atomicMin / atomicMax on doubles of either sign)
 __host__ __device__ inline unsigned long long dkey(double v) {
     union { double d; unsigned long long u; } c;
@@ -89,14 +91,8 @@ __global__ void bump_cell_kernel(BumpArgs a) {
     const double ya = a.ys[i * nxv + j], yb = a.ys[i * nxv + j + 1], yc = a.ys[(i + 1) * nxv + j], yd = a.ys[(i + 1) * nxv + j + 1];
     const double A[3] = {x1, ya, z1}, B[3] = {x2, yb, z1}, Cc[3] = {x1, yc, z2}, D[3] = {x2, yd, z2};
     HCellRec cell;
-    for (int k = 0; k < 3; k++) {
-        cell.t[0].pa[k] = A[k];
-        cell.t[0].e1[k] = A[k] - B[k];
-        cell.t[0].e2[k] = A[k] - Cc[k];
-        cell.t[1].pa[k] = D[k];
-        cell.t[1].e1[k] = D[k] - B[k];
-        cell.t[1].e2[k] = D[k] - Cc[k];
-    }
+    cell.t[0] = make_tri_rec(A, B, Cc);
+    cell.t[1] = make_tri_rec(D, B, Cc);
     // ties: no reference leaf order here -- the triangle with the lower construction index wins (header comment)
     cell.k[0] = 2 * c;
     cell.k[1] = 2 * c + 1;
@@ -132,25 +128,12 @@ struct MeshArgs {
 };
 enum { R_BEGIN = 0, R_END = 1, R_LEVELS = 2, R_TICKET = 3, N_RANGE = 4 };
 
-__device__ inline void tri_box(const double *t, double lo[3], double hi[3]) {
-    for (int k = 0; k < 3; k++) {
-        lo[k] = fmin(t[k], fmin(t[3 + k], t[6 + k]));
-        hi[k] = fmax(t[k], fmax(t[3 + k], t[6 + k]));
-    }
-}
-
-// TriRec per triangle (objects.h:98-99: e1 = pa - pb, e2 = pa - pc) and the box of all vertices
+// TriRec per triangle and the box of all vertices
 __global__ void mesh_prep_kernel(MeshArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n) return;
     const double *t = a.tri9 + 9 * (size_t)i;
-    TriRec tr;
-    for (int k = 0; k < 3; k++) {
-        tr.pa[k] = t[k];
-        tr.e1[k] = t[k] - t[3 + k];
-        tr.e2[k] = t[k] - t[6 + k];
-    }
-    a.tris[i] = tr;
+    a.tris[i] = make_tri_rec(t, t + 3, t + 6);
     double lo[3], hi[3];
     tri_box(t, lo, hi);
     for (int k = 0; k < 3; k++) {
@@ -193,10 +176,7 @@ __global__ void mesh_morton_kernel(MeshArgs a) {
     a.idx_in[i] = (unsigned int)i;
     const double c[3] = {0.5 * (glo[0] + ghi[0]), 0.5 * (glo[1] + ghi[1]), 0.5 * (glo[2] + ghi[2])};
     double r2 = 0;
-    for (int v = 0; v < 3; v++) {
-        const double dx = t[3 * v] - c[0], dy = t[3 * v + 1] - c[1], dz = t[3 * v + 2] - c[2];
-        r2 = fmax(r2, dx * dx + dy * dy + dz * dz);
-    }
+    for (int v = 0; v < 3; v++) r2 = fmax(r2, dist2(t + 3 * v, c));
     atomicMax(a.gbox + 6, dkey(r2));
 }
 
@@ -422,55 +402,14 @@ __global__ __launch_bounds__(256) void wide_level_kernel(MeshArgs a) {
 
 // Cover spheres for classify_kernel (cgrt_build.cpp cover_spheres): group g = sorted triangles [g n / G, (g + 1) n / G) --
 // contiguous in Morton order, hence compact --, sphere = (centre of the group's vertex box, largest vertex distance + 1e-3).
-// One workgroup per group.
-__global__ __launch_bounds__(256) void cover_kernel(MeshArgs a, int G, double *cover) {
+// One workgroup per group (no group is empty: cover_groups leaves 64 triangles or more to each, or all to the one).
+__global__ __launch_bounds__(kReduceThreads) void cover_kernel(MeshArgs a, int G, double *cover) {
+    __shared__ double part[4 * 6];
     const int g = blockIdx.x, n = a.n;
     const int b = (int)((long long)g * n / G), e = (int)((long long)(g + 1) * n / G);
-    __shared__ double red[256][6];
-    double lo[3] = {kInf, kInf, kInf}, hi[3] = {-kInf, -kInf, -kInf};
-    for (int j = b + threadIdx.x; j < e; j += 256) {
-        double l[3], h[3];
-        tri_box(a.tri9 + 9 * (size_t)a.idx_out[j], l, h);
-        for (int k = 0; k < 3; k++) {
-            lo[k] = fmin(lo[k], l[k]);
-            hi[k] = fmax(hi[k], h[k]);
-        }
-    }
-    for (int k = 0; k < 3; k++) {
-        red[threadIdx.x][k] = lo[k];
-        red[threadIdx.x][3 + k] = hi[k];
-    }
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off)
-            for (int k = 0; k < 3; k++) {
-                red[threadIdx.x][k] = fmin(red[threadIdx.x][k], red[threadIdx.x + off][k]);
-                red[threadIdx.x][3 + k] = fmax(red[threadIdx.x][3 + k], red[threadIdx.x + off][3 + k]);
-            }
-        __syncthreads();
-    }
-    const double c[3] = {0.5 * (red[0][0] + red[0][3]), 0.5 * (red[0][1] + red[0][4]), 0.5 * (red[0][2] + red[0][5])};
-    __syncthreads();
-    double r2 = 0;
-    for (int j = b + threadIdx.x; j < e; j += 256) {
-        const double *t = a.tri9 + 9 * (size_t)a.idx_out[j];
-        for (int v = 0; v < 3; v++) {
-            const double dx = t[3 * v] - c[0], dy = t[3 * v + 1] - c[1], dz = t[3 * v + 2] - c[2];
-            r2 = fmax(r2, dx * dx + dy * dy + dz * dz);
-        }
-    }
-    red[threadIdx.x][0] = r2;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) red[threadIdx.x][0] = fmax(red[threadIdx.x][0], red[threadIdx.x + off][0]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        cover[4 * g] = c[0];
-        cover[4 * g + 1] = c[1];
-        cover[4 * g + 2] = c[2];
-        cover[4 * g + 3] = sqrt(red[0][0]) + 1e-3;
-    }
+    double c[3], r2[2];
+    range_sphere(a.tri9, reinterpret_cast<const int *>(a.idx_out), 1, b, e, nullptr, part, c, r2);
+    if (threadIdx.x == 0) store_cover(cover + 4 * (size_t)g, c, r2[0], true, c);
 }
 
 // ---- host drivers --------------------------------------------------------------------------------------------------
@@ -518,7 +457,7 @@ struct MeshResult {
     bool balanced = false;  // the fallback build was needed
     int levels = 0, readbacks = 0;  // of the 4-wide form; of its level counters (one per batch of levels)
     double centre[3] = {0, 0, 0}, r2 = -1.0;  // ObjRec.a / s0 (bounding sphere of the vertices, grown like the host's)
-    double bmax = 0;  // largest |coordinate| of a vertex (TreeRec::bmax)
+    float bmax = 0;  // TreeRec::bmax (tree_bmax of the largest |coordinate| of a vertex)
     std::vector<double> cover;  // n_groups x (cx, cy, cz, r)
 };
 
@@ -659,19 +598,20 @@ static int build_mesh_core(const double *tri9, int n, hipStream_t st, MeshScratc
         if (attempt == 1) return fail(CGRT_ERR_LIMIT, "device hierarchy build: stack bound missed by the balanced tree");
     }
     // bounding sphere (add_mesh_triangles) and cover spheres (cover_spheres)
-    hipLaunchKernelGGL(cover_kernel, dim3((unsigned)S.G), dim3(256), 0, st, a, S.G, S.cover);
+    hipLaunchKernelGGL(cover_kernel, dim3((unsigned)S.G), dim3(kReduceThreads), 0, st, a, S.G, S.cover);
     HIP_TRY(hipGetLastError());
     unsigned long long g[7];
     out.cover.resize((size_t)S.G * 4);
     HIP_TRY(hipMemcpyAsync(g, S.gbox, sizeof(g), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(out.cover.data(), S.cover, out.cover.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    double max_abs = 0;
     for (int k = 0; k < 3; k++) {
         out.centre[k] = 0.5 * (dunkey(g[k]) + dunkey(g[3 + k]));
-        out.bmax = std::max(out.bmax, std::max(std::fabs(dunkey(g[k])), std::fabs(dunkey(g[3 + k]))));
+        max_abs = std::max(max_abs, std::max(std::fabs(dunkey(g[k])), std::fabs(dunkey(g[3 + k]))));
     }
-    const double r = std::sqrt(dunkey(g[6])) + 1e-3;
-    out.r2 = r * r * (1 + 1e-9);
+    out.bmax = tree_bmax(max_abs);
+    out.r2 = sphere_s0(cover_radius(dunkey(g[6])));
     return CGRT_OK;
 }
 

@@ -169,14 +169,14 @@ public:
 
 #include "cgrt_tile_order.hpp"
 
+#include "cgrt_mesh_bounds.hpp"
 #include "cgrt_devbuild.hpp"
 
-// What the first cgrt_scene_refit_mesh of a mesh leaves on the handle (cgrt_refit.hpp): the plan (cgrt_refit_plan.h) and its
-// device copy behind the words every refit clears on its stream
+// What refits and rebuilds of one mesh object keep on the handle (cgrt_mesh_edit.hpp): a scene that never edits a mesh pays nothing
 struct RefitNode {
     int32_t parent, slot, need, pad;  // RefitPlan::parent, ::slot, ::arrivals
 };
-struct RefitState {
+struct RefitPlanDev {  // the plan (cgrt_refit_plan.h) and its device copy behind the words every refit clears on its stream
     RefitPlan plan;
     DevBuf mem;  // [keys | arrival counters] [nodes] [src, rec]
     size_t bytes = 0, clear_bytes = 0;
@@ -184,16 +184,14 @@ struct RefitState {
     int *arrive = nullptr;
     const RefitNode *nodes = nullptr;
     const int2 *srcrec = nullptr;
-    int64_t refits = 0;
-    double ms_plan = 0;  // wall-clock of building and uploading the plan (the first refit's read-backs included)
-    bool stale = false;  // a rebuild changed the topology: the plan is dropped (its memory too), the next refit builds it again
 };
-// What the first cgrt_scene_rebuild_mesh of a mesh leaves on the handle (cgrt_rebuild.hpp): the builder's scratch with staging
-// records, and what the last rebuild did
-struct RebuildState {
-    devbuild::MeshScratch scratch;
+struct MeshEdit {
+    std::unique_ptr<RefitPlanDev> plan;  // built by the mesh's first refit; a rebuild changes the topology and resets it
+    int64_t refits = 0;
+    double ms_plan = 0;  // wall-clock of building and uploading the plan (the read-backs of that refit included)
+    devbuild::MeshScratch scratch;  // the builder's scratch with staging records, allocated by the mesh's first rebuild
     int64_t rebuilds = 0;
-    int32_t balanced = 0, levels = 0, readbacks = 0;
+    int32_t balanced = 0, levels = 0, readbacks = 0;  // what the last rebuild did
     double ms_last = 0;
 };
 
@@ -228,12 +226,10 @@ struct cgrt_scene {
     // the eye kernels the last eye pass on the handle launched (launch_eye, primary_walk), probes included: host state, cleared
     // by every entry point that runs an eye pass, read by cgrt_scene_last_eye_launches
     mutable EyeLaunchLog eye_log;
-    // cgrt_scene_refit_mesh: per refitted mesh object its plan (built by its first refit; a scene that never refits pays nothing),
-    // and the count of refits of the scene: the photon-mapping sessions remember the one they were created under
-    std::map<int, std::unique_ptr<RefitState>> refit;
+    // cgrt_scene_refit_mesh, cgrt_scene_rebuild_mesh: per edited mesh object its record, and the count of edits of the scene:
+    // the photon-mapping sessions remember the one they were created under
+    std::map<int, MeshEdit> edits;
     uint64_t geometry_gen = 0;
-    // cgrt_scene_rebuild_mesh: per rebuilt mesh object the builder's scratch (allocated by its first rebuild)
-    std::map<int, std::unique_ptr<RebuildState>> rebuild;
     // cgrt_scene_mesh_cost: one partial sum per workgroup of tree_cost_kernel
     mutable GrowBuf cost_partials;
 };
@@ -251,6 +247,8 @@ static int upload(cgrt_scene *s, const std::vector<T> &v, const T **out, size_t 
     *out = reinterpret_cast<const T *>(p);
     return CGRT_OK;
 }
+
+#include "cgrt_mesh_edit.hpp"
 
 extern "C" {
 
@@ -275,7 +273,7 @@ int cgrt_scene_create(cgrt_scene **out) {
 
 void cgrt_scene_destroy(cgrt_scene *s) {
     if (!s) return;
-    if (!s->allocs.empty() || s->scratch.p || s->order.buf.p || s->relay.buf.p || s->lens.buf.p || s->lens.ev || s->tri_ids.p || s->aux_stream || s->order.ev || s->relay.ev || !s->refit.empty() || !s->rebuild.empty() || s->cost_partials.p) {
+    if (!s->allocs.empty() || s->scratch.p || s->order.buf.p || s->relay.buf.p || s->lens.buf.p || s->lens.ev || s->tri_ids.p || s->aux_stream || s->order.ev || s->relay.ev || !s->edits.empty() || s->cost_partials.p) {
         DeviceGuard g(s->device);
         if (g.err == hipSuccess) {
             for (void *p : s->allocs) (void)hipFree(p);
@@ -284,8 +282,7 @@ void cgrt_scene_destroy(cgrt_scene *s) {
             s->relay.release();
             s->lens.release();
             s->tri_ids.release();
-            s->refit.clear();
-            s->rebuild.clear();
+            s->edits.clear();
             s->cost_partials.release();
             if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
             if (s->ev_join) (void)hipEventDestroy(s->ev_join);
@@ -395,22 +392,12 @@ static int device_builds(HostScene &H, SceneLayout &L, const DeviceScene &d) {
             t.hfield.yhi = br.yhi;
         } else if (t.dev_kind == 1) {
             devbuild::MeshResult mr;
-            if ((rc = devbuild::build_mesh_hierarchy(t.tri9.data(), (int)t.dev_ntri, const_cast<TriRec *>(d.tris) + tr.tri_begin,
-                                                     const_cast<OTriRec *>(d.otris) + tr.otri_begin,
-                                                     const_cast<WideNodeRec *>(d.wnodes) + tr.wnode_begin, mr)))
-                return rc;
-            tr.nwide = mr.nwide;
-            tr.bmax = tree_bmax(mr.bmax);
-            t.dev_nwide = mr.nwide;
-            t.wide_stack = mr.stack_need;
-            t.dev_balanced = mr.balanced;
-            ObjRec &ob = H.objs[(size_t)t.dev_obj];
-            for (int k = 0; k < 3; k++) ob.a[k] = mr.centre[k];
-            ob.s0 = mr.r2;
-            t.dev_cover_at = H.cover.size();
-            t.cover_first = H.cover.size() / 4;
+            const MeshSlots at = mesh_slots(d, tr, t.dev_obj, (int)ti, 0);
+            if ((rc = devbuild::build_mesh_hierarchy(t.tri9.data(), (int)t.dev_ntri, at.tris, at.otris, at.wnodes, mr))) return rc;
+            t.cover_first = H.cover.size() / 4;  // the spheres are appended: room for them first
             t.cover_n = (int)(mr.cover.size() / 4);
-            H.cover.insert(H.cover.end(), mr.cover.begin(), mr.cover.end());
+            H.cover.resize(H.cover.size() + mr.cover.size());
+            apply_mesh_result(H, t, tr, t.dev_obj, mr);
         }
     }
     return CGRT_OK;
@@ -555,8 +542,8 @@ int cgrt_scene_get_stats(const cgrt_scene *s, cgrt_scene_stats *out) {
     for (auto &t : H.textures) bytes += 3 * (int64_t)t.rows * t.cols;
     out->scene_bytes_fp64 = bytes;
     out->device_bytes = s->device_bytes + (int64_t)s->scratch.cap + (int64_t)s->order.buf.cap + (int64_t)s->tri_ids.cap;  // uploaded scene + the handle's launch scratch (+ the hit-attribute table once asked for)
-    for (const auto &r : s->refit) out->device_bytes += (int64_t)r.second->bytes;  // (+ the refit plans)
-    for (const auto &r : s->rebuild) out->device_bytes += (int64_t)r.second->scratch.bytes;  // (+ the rebuilds' scratch)
+    for (const auto &e : s->edits)  // (+ the refit plans and the rebuilds' scratch)
+        out->device_bytes += (int64_t)((e.second.plan ? e.second.plan->bytes : 0) + e.second.scratch.bytes);
     out->device_bytes += (int64_t)s->cost_partials.cap;
     out->committed = s->committed ? 1 : 0;
     return CGRT_OK;
@@ -593,15 +580,10 @@ int cgrt_scene_wide_dump(const cgrt_scene *s, int t, int32_t *nwide, int32_t *st
     if (!s || t < 0 || t >= (int)s->host.trees.size()) return fail(CGRT_ERR_INVALID, "bad tree index");
     const HostTree &T = s->host.trees[t];
     std::vector<WideNodeRec> from_device;
-    const bool on_device = s->committed && (T.dev_kind == 1 || T.refitted);  // built (row f3) or refitted on the device
+    const bool on_device = tree_lives_on_device(s, t);
     const int32_t n_device = on_device ? s->tree_recs[(size_t)t].nwide : 0;
-    if (on_device && (box24 || ref4)) {  // read the records back
-        ON_DEVICE(s->device);
-        from_device.resize((size_t)n_device);
-        if (n_device > 0)
-            HIP_TRY(hipMemcpy(from_device.data(), s->dev.wnodes + s->tree_recs[(size_t)t].wnode_begin,
-                              from_device.size() * sizeof(WideNodeRec), hipMemcpyDeviceToHost));
-    }
+    if (on_device && (box24 || ref4))
+        if (const int rc = read_device_tree(s, t, &from_device, nullptr)) return rc;
     const std::vector<WideNodeRec> &wide = (T.dev_kind == 1 || on_device) ? from_device : T.wide;
     if (nwide) *nwide = on_device ? n_device : T.dev_kind == 1 ? T.dev_nwide : (int32_t)T.wide.size();
     if (stack_need) *stack_need = T.wide_stack;
@@ -622,11 +604,9 @@ int cgrt_scene_bvh_order(const cgrt_scene *s, int t, int32_t *tri_level, int32_t
     if (!s || t < 0 || t >= (int)s->host.trees.size()) return fail(CGRT_ERR_INVALID, "bad tree index");
     const HostTree &T = s->host.trees[t];
     if (tri_level) *tri_level = T.tri_level ? 1 : 0;
-    if (order && (T.dev_kind == 1 || T.refitted) && s->committed) {  // built on the device: k = the triangle's construction index;
-        ON_DEVICE(s->device);                                         // refitted: the records the refit left, k as it was
-        std::vector<OTriRec> ot((size_t)s->tree_recs[(size_t)t].ntris);
-        if (!ot.empty())
-            HIP_TRY(hipMemcpy(ot.data(), s->dev.otris + s->tree_recs[(size_t)t].otri_begin, ot.size() * sizeof(OTriRec), hipMemcpyDeviceToHost));
+    if (order && tree_lives_on_device(s, t)) {  // built on the device: k = the triangle's construction index; refitted: the
+        std::vector<OTriRec> ot;                // records the refit left, k as it was
+        if (const int rc = read_device_tree(s, t, nullptr, &ot)) return rc;
         for (size_t j = 0; j < ot.size(); j++) order[j] = ot[j].k;
         return CGRT_OK;
     }

@@ -12,29 +12,24 @@
 
 namespace rebuild {
 
-struct Finish {
-    ObjRec *obj;
-    TreeRec *tree;
-    double centre[3], s0;
-    float bmax;
-    int32_t nwide;
-};
-// the host's own doubles (MeshResult), so the records equal a fresh commit's bit for bit
-__global__ void rebuild_finish_kernel(Finish f) {
+// the builder's own values (MeshResult), so the records equal a fresh commit's bit for bit
+__global__ void rebuild_finish_kernel(MeshSlots at, double cx, double cy, double cz, double s0, float bmax, int32_t nwide) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    for (int k = 0; k < 3; k++) f.obj->a[k] = f.centre[k];
-    f.obj->s0 = f.s0;
-    f.tree->bmax = f.bmax;
-    f.tree->nwide = f.nwide;
+    at.obj->a[0] = cx;
+    at.obj->a[1] = cy;
+    at.obj->a[2] = cz;
+    at.obj->s0 = s0;
+    at.tree->bmax = bmax;
+    at.tree->nwide = nwide;
 }
 
 }  // namespace rebuild
 
-// refit_check's refusals, then the rebuild's own: all before any device is touched
-static int rebuild_check(const cgrt_scene *s, int obj, const double *tri9, int ntri, int *tree) {
-    if (const int rc = refit_check(s, obj, tri9, ntri, tree, "rebuild")) return rc;
-    if (*tree < 0) return CGRT_OK;
-    const HostTree &T = s->host.trees[(size_t)*tree];
+// vertex_target's refusals, then the rebuild's own: all before any device is touched
+static int rebuild_target(const cgrt_scene *s, int obj, const double *tri9, int ntri, MeshTarget &m) {
+    if (const int rc = vertex_target(s, obj, tri9, ntri, "rebuild", m)) return rc;
+    if (m.empty) return CGRT_OK;
+    const HostTree &T = s->host.trees[(size_t)m.tree];
     if (T.dev_kind != 1)
         return fail(CGRT_ERR_INVALID, "rebuild: the mesh's tree was built on the host (its arrays have room for that topology only): commit the scene "
                                       "under CGRT_BUILD_DEVICE");
@@ -45,116 +40,73 @@ static int rebuild_check(const cgrt_scene *s, int obj, const double *tri9, int n
 }
 
 // tri9: DEVICE pointer.  Enqueues on st and synchronises it.
-static int rebuild_launch(cgrt_scene *s, int obj, int t, const double *tri9, hipStream_t st) {
+static int rebuild_launch(cgrt_scene *s, const MeshTarget &m, const double *tri9, hipStream_t st) {
     const auto t0 = std::chrono::steady_clock::now();
-    HostScene &H = s->host;
-    HostTree &T = H.trees[(size_t)t];
-    TreeRec &tr = s->tree_recs[(size_t)t];
+    HostTree &T = s->host.trees[(size_t)m.tree];
+    TreeRec &tr = s->tree_recs[(size_t)m.tree];
     const int n = tr.ntris;
-    RebuildState *rs = nullptr;
-    auto it = s->rebuild.find(obj);
-    if (it != s->rebuild.end()) {
-        rs = it->second.get();
-    } else {  // the mesh's first rebuild: its scratch
-        std::unique_ptr<RebuildState> fresh(new (std::nothrow) RebuildState());
-        if (!fresh) return fail(CGRT_ERR_LIMIT, "out of host memory");
-        if (const int rc = fresh->scratch.alloc(n, false, true)) return rc;
-        rs = fresh.get();
-        s->rebuild[obj] = std::move(fresh);
-    }
-    devbuild::MeshScratch &S = rs->scratch;
+    MeshEdit &ed = s->edits[m.obj];
+    devbuild::MeshScratch &S = ed.scratch;
+    if (!S.bytes)  // the mesh's first rebuild: its scratch
+        if (const int rc = S.alloc(n, false, true)) return rc;
     devbuild::MeshResult mr;
     if (const int rc = devbuild::build_mesh_core(tri9, n, st, S, S.tris, S.otris, S.wnodes, mr)) return rc;  // (the scene is untouched)
     if (mr.nwide < 1 || mr.nwide > n || (int)(mr.cover.size() / 4) != T.cover_n) return fail(CGRT_ERR_DEVICE, "rebuild: the builder's counts are out of range");
     // in place
     const size_t N = (size_t)n;
-    HIP_TRY(hipMemcpyAsync(const_cast<TriRec *>(s->dev.tris) + tr.tri_begin, S.tris, N * sizeof(TriRec), hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(const_cast<OTriRec *>(s->dev.otris) + tr.otri_begin, S.otris, N * sizeof(OTriRec), hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(const_cast<WideNodeRec *>(s->dev.wnodes) + tr.wnode_begin, S.wnodes, (size_t)mr.nwide * sizeof(WideNodeRec),
-                           hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(const_cast<double *>(s->dev.cover) + 4 * T.cover_first, S.cover, mr.cover.size() * sizeof(double), hipMemcpyDeviceToDevice, st));
-    rebuild::Finish f;
-    f.obj = const_cast<ObjRec *>(s->dev.objs) + obj;
-    f.tree = const_cast<TreeRec *>(s->dev.trees) + t;
-    for (int k = 0; k < 3; k++) f.centre[k] = mr.centre[k];
-    f.s0 = mr.r2;
-    f.bmax = tree_bmax(mr.bmax);
-    f.nwide = mr.nwide;
-    hipLaunchKernelGGL(rebuild::rebuild_finish_kernel, dim3(1), dim3(64), 0, st, f);
+    HIP_TRY(hipMemcpyAsync(m.at.tris, S.tris, N * sizeof(TriRec), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m.at.otris, S.otris, N * sizeof(OTriRec), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m.at.wnodes, S.wnodes, (size_t)mr.nwide * sizeof(WideNodeRec), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m.at.cover, S.cover, mr.cover.size() * sizeof(double), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(rebuild::rebuild_finish_kernel, dim3(1), dim3(64), 0, st, m.at, mr.centre[0], mr.centre[1], mr.centre[2], mr.r2, mr.bmax,
+                       (int32_t)mr.nwide);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
-    // the handle's state
-    tr.nwide = mr.nwide;
-    tr.bmax = f.bmax;
-    T.dev_nwide = mr.nwide;
-    T.wide_stack = mr.stack_need;
-    T.dev_balanced = mr.balanced;
-    ObjRec &ob = H.objs[(size_t)obj];
-    for (int k = 0; k < 3; k++) ob.a[k] = mr.centre[k];
-    ob.s0 = mr.r2;
-    std::copy(mr.cover.begin(), mr.cover.end(), H.cover.begin() + (std::ptrdiff_t)(4 * T.cover_first));
-    auto rf = s->refit.find(obj);
-    if (rf != s->refit.end() && !rf->second->stale) {  // the plan describes the old topology
-        RefitState &old = *rf->second;
-        if (void *p = old.mem.release()) (void)hipFree(p);
-        old.bytes = old.clear_bytes = 0;
-        old.keys = nullptr;
-        old.arrive = nullptr;
-        old.nodes = nullptr;
-        old.srcrec = nullptr;
-        old.plan = RefitPlan();
-        old.stale = true;
-    }
+    apply_mesh_result(s->host, T, tr, m.obj, mr);
+    ed.plan.reset();  // it describes the old topology: the next refit builds it again
     s->geometry_gen++;
-    rs->rebuilds++;
-    rs->balanced = mr.balanced ? 1 : 0;
-    rs->levels = mr.levels;
-    rs->readbacks = mr.readbacks;
-    rs->ms_last = ms_since(t0);
+    ed.rebuilds++;
+    ed.balanced = mr.balanced ? 1 : 0;
+    ed.levels = mr.levels;
+    ed.readbacks = mr.readbacks;
+    ed.ms_last = ms_since(t0);
     return CGRT_OK;
 }
 
 extern "C" {
 
 int cgrt_scene_rebuild_mesh(cgrt_scene *s, int obj, const double *tri9_dev, int ntri, void *stream) {
-    int t = -1;
-    if (const int rc = rebuild_check(s, obj, tri9_dev, ntri, &t)) return rc;
-    if (t < 0) return CGRT_OK;
+    MeshTarget m;
+    if (const int rc = rebuild_target(s, obj, tri9_dev, ntri, m)) return rc;
+    if (m.empty) return CGRT_OK;
     ON_DEVICE(s->device);
-    return rebuild_launch(s, obj, t, tri9_dev, reinterpret_cast<hipStream_t>(stream));
+    return rebuild_launch(s, m, tri9_dev, reinterpret_cast<hipStream_t>(stream));
 }
 
 int cgrt_scene_rebuild_mesh_host(cgrt_scene *s, int obj, const double *tri9, int ntri) {
-    int t = -1;
-    if (const int rc = rebuild_check(s, obj, tri9, ntri, &t)) return rc;
-    if (t < 0) return CGRT_OK;
+    MeshTarget m;
+    if (const int rc = rebuild_target(s, obj, tri9, ntri, m)) return rc;
+    if (m.empty) return CGRT_OK;
     ON_DEVICE(s->device);
-    const size_t bytes = (size_t)ntri * 9 * sizeof(double);
-    DevBuf d;
-    HIP_TRY(d.alloc(bytes));
-    HIP_TRY(hipMemcpy(d.p, tri9, bytes, hipMemcpyHostToDevice));
-    if (const int rc = rebuild_launch(s, obj, t, d.as<double>(), 0)) return rc;
-    try {
-        s->host.trees[(size_t)t].tri9.assign(tri9, tri9 + (size_t)ntri * 9);
-    } catch (const std::exception &e) {
-        return fail(CGRT_ERR_LIMIT, std::string("rebuild: ") + e.what());
-    }
-    return CGRT_OK;
+    HostStage hs;
+    const double *d = hs.in(tri9, (size_t)ntri * 9 * sizeof(double));
+    if (hs.error()) return hs.error();
+    if (const int rc = rebuild_launch(s, m, d, 0)) return rc;
+    return keep_vertices(s->host.trees[(size_t)m.tree], tri9, ntri, "rebuild");
 }
 
 int cgrt_scene_rebuild_info(const cgrt_scene *s, int obj, cgrt_rebuild_info *out) {
     if (!s || !out) return fail(CGRT_ERR_INVALID, "null argument");
-    if (obj < 0 || obj >= (int)s->host.objs.size() || s->host.objs[(size_t)obj].kind != KIND_MESH || s->host.objs[(size_t)obj].tree < 0)
-        return fail(CGRT_ERR_INVALID, "rebuild info: the object is no mesh");
-    const int t = s->host.objs[(size_t)obj].tree;
+    const int t = info_tree(s, obj);
+    if (t < 0) return fail(CGRT_ERR_INVALID, "rebuild info: the object is no mesh");
     const HostTree &T = s->host.trees[(size_t)t];
     std::memset(out, 0, sizeof(*out));
     out->nwide = s->committed ? s->tree_recs[(size_t)t].nwide : (int32_t)T.wide.size();
     out->stack_need = T.wide_stack;
     out->balanced = T.dev_balanced ? 1 : 0;
-    const auto it = s->rebuild.find(obj);
-    if (it != s->rebuild.end()) {
-        const RebuildState &r = *it->second;
+    const auto it = s->edits.find(obj);
+    if (it != s->edits.end() && it->second.scratch.bytes) {  // (it has been rebuilt, or tried)
+        const MeshEdit &r = it->second;
         out->rebuilds = r.rebuilds;
         out->balanced = r.balanced;
         out->levels = r.levels;

@@ -13,7 +13,7 @@
 //   refit_bounds_kernel  one workgroup per cover sphere: a contiguous range of the triangle order -> (centre of its vertex box,
 //                        largest vertex distance + 1e-3) into cover[]; the same pass takes the largest squared distance from
 //                        the centre of the MESH's vertex box, complete by now.
-//   refit_finish_kernel  ObjRec::a / s0 (add_mesh_triangles' formulas) and TreeRec::bmax (tree_bmax's) into the device arrays.
+//   refit_finish_kernel  ObjRec::a / s0 and TreeRec::bmax (cgrt_build.h's formulas) into the device arrays.
 //
 // Parity class: that of CGRT_BUILD_DEVICE (cgrt.h).  Boxes are supersets and the triangle test is the same code, so every ray
 // with a unique nearest hit gets the hit of a scene freshly committed with the new vertices, bit for bit; exact ties keep the
@@ -23,12 +23,9 @@
 
 namespace refit {
 
-using devbuild::dkey;
-using devbuild::dunkey;
-using devbuild::f_down;
-using devbuild::f_up;
+using namespace devbuild;  // (dkey, dunkey, f_down, f_up; mesh_bounds)
 
-static constexpr int kThreadsRefit = 256;
+static constexpr int kThreadsRefit = kReduceThreads;
 // keys[]: every value is kept as the key of a MAXIMUM (a lower bound as the maximum of its negation), so one memset clears them
 enum { KEY_NEG_LO = 0, KEY_HI = 3, KEY_MAX_ABS = 6, KEY_R2 = 7, N_KEYS = 8 };
 
@@ -37,41 +34,14 @@ struct Args {
     int n, nwide;
     const int2 *srcrec;        // per position: {construction index, record of tris[]}
     const RefitNode *nodes;    // per wide node
-    TriRec *tris;              // the tree's first record of each array
-    OTriRec *otris;
-    WideNodeRec *wnodes;
+    MeshSlots at;              // where the mesh's records are
     unsigned long long *keys;  // N_KEYS
     int *arrive;               // nwide arrival counters, cleared on the stream by every refit
-    ObjRec *obj;
-    TreeRec *tree;
-    double *cover;  // the mesh's first cover sphere (4 doubles each), or nullptr
-    int n_cover;
+    int n_cover;               // cover spheres of the mesh at at.cover
 };
 
-__device__ inline double neg_inf() { return -__builtin_huge_val(); }
-
-// v[k] = the workgroup's maximum of v[k], in every thread.  All kThreadsRefit threads call it.
-template <int NV>
-__device__ inline void block_max(double (&v)[NV], double (*part)[NV]) {
-    for (int off = 32; off > 0; off >>= 1)
-        for (int k = 0; k < NV; k++) v[k] = fmax(v[k], __shfl_xor(v[k], off));
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < NV; k++) part[threadIdx.x >> 6][k] = v[k];
-    __syncthreads();
-    for (int k = 0; k < NV; k++) v[k] = fmax(fmax(part[0][k], part[1][k]), fmax(part[2][k], part[3][k]));
-    __syncthreads();  // (part is free again)
-}
-
-// max(-lo), max(hi) of a triangle's three vertices into v[0..2], v[3..5]
-__device__ inline void fold_box(const double *t, double *v) {
-    for (int k = 0; k < 3; k++) {
-        v[k] = fmax(v[k], -fmin(t[k], fmin(t[3 + k], t[6 + k])));
-        v[3 + k] = fmax(v[3 + k], fmax(t[k], fmax(t[3 + k], t[6 + k])));
-    }
-}
-
 __global__ __launch_bounds__(kThreadsRefit) void refit_tris_kernel(Args a) {
-    __shared__ double part[4][7];
+    __shared__ double part[4 * 7];
     const int j = blockIdx.x * kThreadsRefit + threadIdx.x;
     double v[7];
     for (int k = 0; k < 7; k++) v[k] = neg_inf();
@@ -80,18 +50,13 @@ __global__ __launch_bounds__(kThreadsRefit) void refit_tris_kernel(Args a) {
         const double *t = a.tri9 + 9 * (size_t)sr.x;
         double p[9];
         for (int k = 0; k < 9; k++) p[k] = t[k];
-        TriRec tr;  // objects.h:98-99, as mesh_prep_kernel
-        for (int k = 0; k < 3; k++) {
-            tr.pa[k] = p[k];
-            tr.e1[k] = p[k] - p[3 + k];
-            tr.e2[k] = p[k] - p[6 + k];
-        }
-        a.otris[j].t = tr;  // (k and leaf stay: ties go on as before)
-        a.tris[sr.y] = tr;
+        const TriRec tr = make_tri_rec(p, p + 3, p + 6);
+        a.at.otris[j].t = tr;  // (k and leaf stay: ties go on as before)
+        a.at.tris[sr.y] = tr;
         fold_box(p, v);
         for (int k = 0; k < 3; k++) v[6] = fmax(v[6], fmax(fabs(v[k]), fabs(v[3 + k])));
     }
-    block_max<7>(v, part);
+    block_reduce<7>(v, part, Max());
     if (threadIdx.x == 0)
         for (int k = 0; k < 7; k++) atomicMax(a.keys + k, dkey(v[k]));
 }
@@ -114,7 +79,7 @@ __global__ __launch_bounds__(kThreadsRefit) void refit_nodes_kernel(Args a) {
     const int i = blockIdx.x * kThreadsRefit + threadIdx.x;
     if (i >= a.nwide) return;
     {   // this node's leaf slots, each fitted to its triangles
-        WideNodeRec *w = a.wnodes + i;
+        WideNodeRec *w = a.at.wnodes + i;
         for (int k = 0; k < 4; k++) {
             const int32_t r = w->ref[k];  // (references are never written by a refit)
             if (r < 0) continue;          // an inner child or an empty slot
@@ -137,7 +102,7 @@ __global__ __launch_bounds__(kThreadsRefit) void refit_nodes_kernel(Args a) {
         if (rn.parent < 0) return;  // the root is complete
         // The union of already grown and rounded boxes, not padded again: rounding is monotone, so this equals "round the fp64
         // union", which is what both builders store.
-        const WideNodeRec *c = a.wnodes + node;
+        const WideNodeRec *c = a.at.wnodes + node;
         float lo[3] = {__builtin_huge_valf(), __builtin_huge_valf(), __builtin_huge_valf()};
         float hi[3] = {-__builtin_huge_valf(), -__builtin_huge_valf(), -__builtin_huge_valf()};
         for (int k = 0; k < 4; k++) {
@@ -149,7 +114,7 @@ __global__ __launch_bounds__(kThreadsRefit) void refit_nodes_kernel(Args a) {
             hi[1] = fmaxf(hi[1], ld_box(&c->hiy[k]));
             hi[2] = fmaxf(hi[2], ld_box(&c->hiz[k]));
         }
-        st_slot(a.wnodes + rn.parent, rn.slot, lo, hi);
+        st_slot(a.at.wnodes + rn.parent, rn.slot, lo, hi);
         node = rn.parent;
     }
 }
@@ -157,110 +122,46 @@ __global__ __launch_bounds__(kThreadsRefit) void refit_nodes_kernel(Args a) {
 // One workgroup per cover sphere g: positions [g n / G, (g + 1) n / G) of the triangle order (cover_kernel's ranges; contiguous
 // in either builder's order, hence compact).  Any spheres that together contain every triangle serve classify_kernel.
 __global__ __launch_bounds__(kThreadsRefit) void refit_bounds_kernel(Args a) {
-    __shared__ double part6[4][6];
-    __shared__ double part2[4][2];
+    __shared__ double part[4 * 6];
     const int G = a.n_cover > 0 ? a.n_cover : 1, g = blockIdx.x, n = a.n;
     const int b = (int)((long long)g * n / G), e = (int)((long long)(g + 1) * n / G);
-    double v[6];
-    for (int k = 0; k < 6; k++) v[k] = neg_inf();
-    for (int j = b + (int)threadIdx.x; j < e; j += kThreadsRefit) fold_box(a.tri9 + 9 * (size_t)a.srcrec[j].x, v);
-    block_max<6>(v, part6);
-    double c[3], mc[3];  // the range's centre, the mesh's (its vertex box is complete: refit_tris_kernel ran before)
-    for (int k = 0; k < 3; k++) {
-        c[k] = 0.5 * (-v[k] + v[3 + k]);
-        mc[k] = 0.5 * (-dunkey(a.keys[KEY_NEG_LO + k]) + dunkey(a.keys[KEY_HI + k]));
-    }
-    double r2[2] = {0.0, 0.0};
-    for (int j = b + (int)threadIdx.x; j < e; j += kThreadsRefit) {
-        const double *t = a.tri9 + 9 * (size_t)a.srcrec[j].x;
-        for (int q = 0; q < 3; q++) {
-            const double dx = t[3 * q] - c[0], dy = t[3 * q + 1] - c[1], dz = t[3 * q + 2] - c[2];
-            r2[0] = fmax(r2[0], dx * dx + dy * dy + dz * dz);
-            const double mx = t[3 * q] - mc[0], my = t[3 * q + 1] - mc[1], mz = t[3 * q + 2] - mc[2];
-            r2[1] = fmax(r2[1], mx * mx + my * my + mz * mz);
-        }
-    }
-    block_max<2>(r2, part2);
+    double mc[3];  // the centre of the mesh's vertex box, complete by now: refit_tris_kernel ran before
+    for (int k = 0; k < 3; k++) mc[k] = 0.5 * (-dunkey(a.keys[KEY_NEG_LO + k]) + dunkey(a.keys[KEY_HI + k]));
+    double c[3], r2[2];
+    range_sphere(a.tri9, reinterpret_cast<const int *>(a.srcrec), 2, b, e, mc, part, c, r2);
     if (threadIdx.x != 0) return;
-    if (a.cover && g < a.n_cover) {
-        double *o = a.cover + 4 * (size_t)g;
-        const bool any = e > b;  // (an empty range: a point at the mesh's centre)
-        o[0] = any ? c[0] : mc[0];
-        o[1] = any ? c[1] : mc[1];
-        o[2] = any ? c[2] : mc[2];
-        o[3] = (any ? sqrt(r2[0]) : 0.0) + 1e-3;
-    }
+    if (g < a.n_cover) store_cover(a.at.cover + 4 * (size_t)g, c, r2[0], e > b, mc);
     atomicMax(a.keys + KEY_R2, dkey(r2[1]));
 }
 
-// HostScene::add_mesh_triangles' bounding sphere and tree_bmax's bound (cgrt_build.cpp), written where the kernels read them
+// the bounding sphere and the coordinate bound by the builders' formulas (cgrt_build.h), written where the kernels read them
 __global__ void refit_finish_kernel(Args a) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    for (int k = 0; k < 3; k++) a.obj->a[k] = 0.5 * (-dunkey(a.keys[KEY_NEG_LO + k]) + dunkey(a.keys[KEY_HI + k]));
-    const double r = sqrt(dunkey(a.keys[KEY_R2])) + 1e-3;
-    a.obj->s0 = r * r * (1 + 1e-9);
-    const double max_abs = dunkey(a.keys[KEY_MAX_ABS]);
-    a.tree->bmax = (float)((max_abs + 2 * kBoxPad) * (1 + 1e-6)) * (1.f + 1e-6f);
+    for (int k = 0; k < 3; k++) a.at.obj->a[k] = 0.5 * (-dunkey(a.keys[KEY_NEG_LO + k]) + dunkey(a.keys[KEY_HI + k]));
+    a.at.obj->s0 = sphere_s0(cover_radius(dunkey(a.keys[KEY_R2])));
+    a.at.tree->bmax = tree_bmax(dunkey(a.keys[KEY_MAX_ABS]));
 }
 
 }  // namespace refit
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
-static const char *const kRefitStale = "the scene was refitted after this session was created";
-
-// Which tree a refit of object `obj` works on, after every check that needs no device.  *tree = -1: an empty mesh, nothing to do.
-// The rebuild (what = "rebuild") and the tree cost (what = "cost", which takes no vertices: cost = true) refuse the same.
-static int refit_check(const cgrt_scene *s, int obj, const double *tri9, int ntri, int *tree, const char *what = "refit", bool cost = false) {
-    const std::string who = what;
-    *tree = -1;
-    if (!s) return fail(CGRT_ERR_INVALID, who + ": null scene");
-    if (!s->committed) return fail(CGRT_ERR_INVALID, who + ": scene not committed");
-    if (obj < 0 || obj >= (int)s->host.objs.size()) return fail(CGRT_ERR_INVALID, who + ": no such object");
-    const ObjRec &o = s->host.objs[(size_t)obj];
-    if (o.kind == KIND_SPHERE) return fail(CGRT_ERR_INVALID, who + ": the object is a sphere, not a mesh");
-    if (o.kind == KIND_BEZIER) return fail(CGRT_ERR_INVALID, who + ": the object is a Bezier surface, not a mesh");
-    if (o.kind == KIND_PLANE)
-        return fail(CGRT_ERR_INVALID, o.tree >= 0 ? who + ": the object is a bump floor, not a mesh" : who + ": the object is a plane, not a mesh");
-    if (o.kind != KIND_MESH || o.tree < 0 || o.tree >= (int)s->tree_recs.size()) return fail(CGRT_ERR_INVALID, who + ": the object is no mesh");
-    if (!(o.transp < kEps) && cost) return fail(CGRT_ERR_INVALID, who + ": the mesh is transparent: its tree has no 4-wide hierarchy");
-    if (!(o.transp < kEps))
-        return fail(CGRT_ERR_INVALID, who + ": the mesh is transparent (its improvement counter makes the leaf order observable, quirk Q5)");
-    const TreeRec &tr = s->tree_recs[(size_t)o.tree];
-    if (cost) ntri = tr.ntris;
-    if (ntri != tr.ntris) return fail(CGRT_ERR_INVALID, who + ": ntri is not the mesh's triangle count (" + std::to_string(tr.ntris) + ")");
-    if (ntri == 0) return CGRT_OK;
-    if (!tr.tri_level || tr.nwide <= 0) return fail(CGRT_ERR_INVALID, who + ": the tree has no 4-wide hierarchy (CGRT_TREE=ref)");
-    if (!tri9 && !cost) return fail(CGRT_ERR_INVALID, who + ": null tri9");
-    *tree = o.tree;
-    return CGRT_OK;
-}
-
-// The plan of tree t: from the host's records (a host-built tree, committed or not) or from the device's (a device-built one)
+// The plan of tree t: from the host's records (a host-built tree, committed or not) or from the device's
 static int tree_refit_plan(const cgrt_scene *s, int t, RefitPlan &plan) {
     const HostTree &T = s->host.trees[(size_t)t];
     std::vector<WideNodeRec> wide_dev;
+    std::vector<OTriRec> ot_dev;
+    if (T.dev_kind == 1 && !s->committed) return fail(CGRT_ERR_INVALID, "refit plan: a device-built tree exists only after the commit");
+    const bool dev = tree_lives_on_device(s, t);
+    if (dev)
+        if (const int rc = read_device_tree(s, t, &wide_dev, &ot_dev)) return rc;
+    const std::vector<WideNodeRec> &wide = dev ? wide_dev : T.wide;
     std::vector<int32_t> k;
-    const WideNodeRec *wide = T.wide.data();
-    int32_t nwide = (int32_t)T.wide.size(), ntri = (int32_t)T.otris.size();
-    if (T.dev_kind == 1) {
-        if (!s->committed) return fail(CGRT_ERR_INVALID, "refit plan: a device-built tree exists only after the commit");
-        ON_DEVICE(s->device);
-        const TreeRec &tr = s->tree_recs[(size_t)t];
-        nwide = tr.nwide;
-        ntri = tr.ntris;
-        wide_dev.resize((size_t)std::max(nwide, 0));
-        std::vector<OTriRec> ot((size_t)std::max(ntri, 0));
-        if (!wide_dev.empty()) HIP_TRY(hipMemcpy(wide_dev.data(), s->dev.wnodes + tr.wnode_begin, wide_dev.size() * sizeof(WideNodeRec), hipMemcpyDeviceToHost));
-        if (!ot.empty()) HIP_TRY(hipMemcpy(ot.data(), s->dev.otris + tr.otri_begin, ot.size() * sizeof(OTriRec), hipMemcpyDeviceToHost));
-        wide = wide_dev.data();
-        for (const OTriRec &o : ot) k.push_back(o.k);
-    } else {
-        for (const OTriRec &o : T.otris) k.push_back(o.k);
-        if ((size_t)ntri != T.leaf_ids.size()) return fail(CGRT_ERR_INVALID, "refit plan: the tree has no triangle-level hierarchy");
-    }
+    for (const OTriRec &o : dev ? ot_dev : T.otris) k.push_back(o.k);
+    if (T.dev_kind != 1 && k.size() != T.leaf_ids.size()) return fail(CGRT_ERR_INVALID, "refit plan: the tree has no triangle-level hierarchy");
     try {
-        if (const char *bad = refit_plan(wide, nwide, k.data(), ntri, T.dev_kind == 1 ? nullptr : T.leaf_ids.data(), plan)) return fail(CGRT_ERR_INVALID, bad);
+        if (const char *bad = refit_plan(wide.data(), (int32_t)wide.size(), k.data(), (int32_t)k.size(), T.dev_kind == 1 ? nullptr : T.leaf_ids.data(), plan))
+            return fail(CGRT_ERR_INVALID, bad);
     } catch (const std::exception &e) {
         return fail(CGRT_ERR_LIMIT, std::string("refit plan: ") + e.what());
     }
@@ -269,19 +170,12 @@ static int tree_refit_plan(const cgrt_scene *s, int t, RefitPlan &plan) {
     return CGRT_OK;
 }
 
-// The first refit of a mesh: its plan, and the plan's device copy in front of the words every refit clears
-static int refit_prepare(cgrt_scene *s, int obj, int t, RefitState **out) {
-    auto it = s->refit.find(obj);
-    int64_t refits_so_far = 0;
-    if (it != s->refit.end()) {
-        if (!it->second->stale) {
-            *out = it->second.get();
-            return CGRT_OK;
-        }
-        refits_so_far = it->second->refits;  // (a rebuild dropped the plan: built again here, the count goes on)
-    }
+// The first refit of a mesh, or the first after a rebuild: its plan, and the plan's device copy in front of the words every
+// refit clears
+static int refit_prepare(cgrt_scene *s, MeshEdit &ed, int t) {
+    if (ed.plan) return CGRT_OK;
     const auto t0 = std::chrono::steady_clock::now();
-    std::unique_ptr<RefitState> st(new (std::nothrow) RefitState());
+    std::unique_ptr<RefitPlanDev> st(new (std::nothrow) RefitPlanDev());
     if (!st) return fail(CGRT_ERR_LIMIT, "out of host memory");
     if (const int rc = tree_refit_plan(s, t, st->plan)) return rc;
     const RefitPlan &p = st->plan;
@@ -305,93 +199,88 @@ static int refit_prepare(cgrt_scene *s, int obj, int t, RefitState **out) {
     st->arrive = reinterpret_cast<int *>(base + refit::N_KEYS * sizeof(unsigned long long));
     st->nodes = reinterpret_cast<const RefitNode *>(base + nodes_at);
     st->srcrec = reinterpret_cast<const int2 *>(base + srcrec_at);
-    st->ms_plan = ms_since(t0);
-    st->refits = refits_so_far;
-    *out = st.get();
-    s->refit[obj] = std::move(st);
+    ed.ms_plan = ms_since(t0);
+    ed.plan = std::move(st);
     return CGRT_OK;
 }
 
 // tri9: DEVICE pointer.  Everything behind the first call's plan is enqueued on st.
-static int refit_launch(cgrt_scene *s, int obj, int t, const double *tri9, hipStream_t st) {
-    RefitState *rs = nullptr;
-    if (const int rc = refit_prepare(s, obj, t, &rs)) return rc;
-    const TreeRec &tr = s->tree_recs[(size_t)t];
+static int refit_launch(cgrt_scene *s, const MeshTarget &m, const double *tri9, hipStream_t st) {
+    MeshEdit &ed = s->edits[m.obj];
+    if (const int rc = refit_prepare(s, ed, m.tree)) return rc;
+    const RefitPlanDev &rs = *ed.plan;
+    const TreeRec &tr = s->tree_recs[(size_t)m.tree];
     refit::Args a;
     a.tri9 = tri9;
     a.n = tr.ntris;
     a.nwide = tr.nwide;
-    a.srcrec = rs->srcrec;
-    a.nodes = rs->nodes;
-    a.tris = const_cast<TriRec *>(s->dev.tris) + tr.tri_begin;
-    a.otris = const_cast<OTriRec *>(s->dev.otris) + tr.otri_begin;
-    a.wnodes = const_cast<WideNodeRec *>(s->dev.wnodes) + tr.wnode_begin;
-    a.keys = rs->keys;
-    a.arrive = rs->arrive;
-    a.obj = const_cast<ObjRec *>(s->dev.objs) + obj;
-    a.tree = const_cast<TreeRec *>(s->dev.trees) + t;
-    a.n_cover = rs->plan.n_cover;
-    a.cover = a.n_cover > 0 ? const_cast<double *>(s->dev.cover) + 4 * (size_t)rs->plan.cover_first : nullptr;
+    a.srcrec = rs.srcrec;
+    a.nodes = rs.nodes;
+    a.at = m.at;
+    a.keys = rs.keys;
+    a.arrive = rs.arrive;
+    a.n_cover = rs.plan.n_cover;
     const int T = refit::kThreadsRefit;
-    HIP_TRY(hipMemsetAsync(rs->mem.p, 0, rs->clear_bytes, st));
+    HIP_TRY(hipMemsetAsync(rs.mem.p, 0, rs.clear_bytes, st));
     hipLaunchKernelGGL(refit::refit_tris_kernel, dim3((unsigned)((a.n + T - 1) / T)), dim3(T), 0, st, a);
     hipLaunchKernelGGL(refit::refit_nodes_kernel, dim3((unsigned)((a.nwide + T - 1) / T)), dim3(T), 0, st, a);
     hipLaunchKernelGGL(refit::refit_bounds_kernel, dim3((unsigned)std::max(a.n_cover, 1)), dim3(T), 0, st, a);
     hipLaunchKernelGGL(refit::refit_finish_kernel, dim3(1), dim3(64), 0, st, a);
     HIP_TRY(hipGetLastError());
-    rs->refits++;
+    ed.refits++;
     s->geometry_gen++;
-    s->host.trees[(size_t)t].refitted = true;  // the reference's tree over the old vertices describes nothing any more
+    s->host.trees[(size_t)m.tree].refitted = true;  // the reference's tree over the old vertices describes nothing any more
+    return CGRT_OK;
+}
+
+// The bounds the device holds for the mesh now, as a build's result: what the topology fixes comes from the handle
+static int read_mesh_bounds(const cgrt_scene *s, const MeshTarget &m, devbuild::MeshResult &mr) {
+    const HostTree &T = s->host.trees[(size_t)m.tree];
+    ObjRec o;
+    TreeRec tr;
+    HIP_TRY(hipMemcpy(&o, m.at.obj, sizeof(o), hipMemcpyDeviceToHost));  // synchronises
+    HIP_TRY(hipMemcpy(&tr, m.at.tree, sizeof(tr), hipMemcpyDeviceToHost));
+    mr.nwide = tr.nwide;
+    mr.stack_need = T.wide_stack;
+    mr.balanced = T.dev_balanced;
+    for (int k = 0; k < 3; k++) mr.centre[k] = o.a[k];
+    mr.r2 = o.s0;
+    mr.bmax = tr.bmax;
+    mr.cover.resize((size_t)T.cover_n * 4);
+    if (T.cover_n > 0) HIP_TRY(hipMemcpy(mr.cover.data(), m.at.cover, mr.cover.size() * sizeof(double), hipMemcpyDeviceToHost));
     return CGRT_OK;
 }
 
 extern "C" {
 
 int cgrt_scene_refit_mesh(cgrt_scene *s, int obj, const double *tri9, int ntri, void *stream) {
-    int t = -1;
-    if (const int rc = refit_check(s, obj, tri9, ntri, &t)) return rc;
-    if (t < 0) return CGRT_OK;
+    MeshTarget m;
+    if (const int rc = vertex_target(s, obj, tri9, ntri, "refit", m)) return rc;
+    if (m.empty) return CGRT_OK;
     ON_DEVICE(s->device);
-    return refit_launch(s, obj, t, tri9, reinterpret_cast<hipStream_t>(stream));
+    return refit_launch(s, m, tri9, reinterpret_cast<hipStream_t>(stream));
 }
 
 int cgrt_scene_refit_mesh_host(cgrt_scene *s, int obj, const double *tri9, int ntri) {
-    int t = -1;
-    if (const int rc = refit_check(s, obj, tri9, ntri, &t)) return rc;
-    if (t < 0) return CGRT_OK;
+    MeshTarget m;
+    if (const int rc = vertex_target(s, obj, tri9, ntri, "refit", m)) return rc;
+    if (m.empty) return CGRT_OK;
     ON_DEVICE(s->device);
-    const size_t bytes = (size_t)ntri * 9 * sizeof(double);
-    DevBuf d;
-    HIP_TRY(d.alloc(bytes));
-    HIP_TRY(hipMemcpy(d.p, tri9, bytes, hipMemcpyHostToDevice));
-    if (const int rc = refit_launch(s, obj, t, d.as<double>(), 0)) return rc;
-    HIP_TRY(hipStreamSynchronize(0));
-    // the host mirrors of what the device now owns
-    HostScene &H = s->host;
-    ObjRec o;
-    HIP_TRY(hipMemcpy(&o, s->dev.objs + obj, sizeof(o), hipMemcpyDeviceToHost));
-    for (int k = 0; k < 3; k++) H.objs[(size_t)obj].a[k] = o.a[k];
-    H.objs[(size_t)obj].s0 = o.s0;
-    TreeRec tr;
-    HIP_TRY(hipMemcpy(&tr, s->dev.trees + t, sizeof(tr), hipMemcpyDeviceToHost));
-    s->tree_recs[(size_t)t].bmax = tr.bmax;
-    const RefitPlan &p = s->refit[obj]->plan;
-    if (p.n_cover > 0)
-        HIP_TRY(hipMemcpy(H.cover.data() + 4 * (size_t)p.cover_first, s->dev.cover + 4 * (size_t)p.cover_first,
-                          (size_t)p.n_cover * 4 * sizeof(double), hipMemcpyDeviceToHost));
-    try {
-        H.trees[(size_t)t].tri9.assign(tri9, tri9 + (size_t)ntri * 9);
-    } catch (const std::exception &e) {
-        return fail(CGRT_ERR_LIMIT, std::string("refit: ") + e.what());
-    }
-    return CGRT_OK;
+    HostStage hs;
+    const double *d = hs.in(tri9, (size_t)ntri * 9 * sizeof(double));
+    if (hs.error()) return hs.error();
+    if (const int rc = hs.finish(refit_launch(s, m, d, 0))) return rc;
+    devbuild::MeshResult mr;  // the host mirrors of what the device now owns
+    if (const int rc = read_mesh_bounds(s, m, mr)) return rc;
+    HostTree &T = s->host.trees[(size_t)m.tree];
+    apply_mesh_result(s->host, T, s->tree_recs[(size_t)m.tree], obj, mr);
+    return keep_vertices(T, tri9, ntri, "refit");
 }
 
 int cgrt_scene_refit_info(const cgrt_scene *s, int obj, cgrt_refit_info *out) {
     if (!s || !out) return fail(CGRT_ERR_INVALID, "null argument");
-    if (obj < 0 || obj >= (int)s->host.objs.size() || s->host.objs[(size_t)obj].kind != KIND_MESH || s->host.objs[(size_t)obj].tree < 0)
-        return fail(CGRT_ERR_INVALID, "refit info: the object is no mesh");
-    const int t = s->host.objs[(size_t)obj].tree;
+    const int t = info_tree(s, obj);
+    if (t < 0) return fail(CGRT_ERR_INVALID, "refit info: the object is no mesh");
     const HostTree &T = s->host.trees[(size_t)t];
     std::memset(out, 0, sizeof(*out));
     if (s->committed) {
@@ -401,13 +290,30 @@ int cgrt_scene_refit_info(const cgrt_scene *s, int obj, cgrt_refit_info *out) {
         out->nwide = (int32_t)T.wide.size();
         out->ntris = T.dev_kind ? (int32_t)T.dev_ntri : (int32_t)(T.tri9.size() / 9);
     }
-    const auto it = s->refit.find(obj);
-    if (it != s->refit.end()) {
-        out->refits = it->second->refits;
-        out->plan_built = it->second->stale ? 0 : 1;
-        out->ms_plan = it->second->ms_plan;
+    const auto it = s->edits.find(obj);
+    if (it != s->edits.end()) {
+        out->refits = it->second.refits;
+        out->plan_built = it->second.plan ? 1 : 0;
+        out->ms_plan = it->second.ms_plan;
     }
     out->geometry_gen = s->geometry_gen;
+    return CGRT_OK;
+}
+
+int cgrt_scene_mesh_bounds_host(const cgrt_scene *s, int obj, double centre3[3], double *s0, float *bmax, double *cover4, int32_t cap,
+                                int32_t *n_cover) {
+    MeshTarget m;
+    if (const int rc = walk_target(s, obj, "bounds", m)) return rc;
+    const int n = s->host.trees[(size_t)m.tree].cover_n;
+    if (n_cover) *n_cover = n;
+    if (cover4 && cap < n) return fail(CGRT_ERR_INVALID, "bounds: room for fewer cover spheres than the mesh has (" + std::to_string(n) + ")");
+    ON_DEVICE(s->device);
+    devbuild::MeshResult mr;
+    if (const int rc = read_mesh_bounds(s, m, mr)) return rc;
+    if (centre3) std::copy(mr.centre, mr.centre + 3, centre3);
+    if (s0) *s0 = mr.r2;
+    if (bmax) *bmax = mr.bmax;
+    if (cover4) std::copy(mr.cover.begin(), mr.cover.end(), cover4);
     return CGRT_OK;
 }
 
@@ -415,15 +321,11 @@ int cgrt_scene_refit_plan_host(const cgrt_scene *s, int tree, int32_t *nwide, in
                                int32_t *arrivals, int32_t *src) {
     if (!s || tree < 0 || tree >= (int)s->host.trees.size()) return fail(CGRT_ERR_INVALID, "bad tree index");
     const HostTree &T = s->host.trees[(size_t)tree];
-    const bool wide = T.dev_kind == 1 ? (s->committed && s->tree_recs[(size_t)tree].nwide > 0) : (T.tri_level && !T.wide.empty());
-    if (!wide) {  // no 4-wide hierarchy: nothing to plan (as cgrt_scene_wide_dump reports no node)
-        if (nwide) *nwide = 0;
-        if (ntris) *ntris = 0;
-        return CGRT_OK;
-    }
-    if (!parent && !slot && !arrivals && !src) {  // the sizing call
-        if (nwide) *nwide = T.dev_kind == 1 ? s->tree_recs[(size_t)tree].nwide : (int32_t)T.wide.size();
-        if (ntris) *ntris = T.dev_kind == 1 ? s->tree_recs[(size_t)tree].ntris : (int32_t)T.otris.size();
+    const bool dev = T.dev_kind == 1, sizing = !parent && !slot && !arrivals && !src;
+    const bool wide = dev ? (s->committed && s->tree_recs[(size_t)tree].nwide > 0) : (T.tri_level && !T.wide.empty());
+    if (!wide || sizing) {  // no 4-wide hierarchy: nothing to plan (as cgrt_scene_wide_dump reports no node); or the sizing call
+        if (nwide) *nwide = !wide ? 0 : dev ? s->tree_recs[(size_t)tree].nwide : (int32_t)T.wide.size();
+        if (ntris) *ntris = !wide ? 0 : dev ? s->tree_recs[(size_t)tree].ntris : (int32_t)T.otris.size();
         return CGRT_OK;
     }
     RefitPlan plan;

@@ -8,14 +8,15 @@
 //   tri_cost   the sum over leaf slots of count * S / root_area
 //
 // Two launches, so that no sum is handed from workgroup to workgroup inside one: tree_cost_kernel, a thread per wide node, sums
-// in fp64 (wave shuffles, then LDS, as refit::block_max) and writes one partial pair per workgroup; tree_cost_sum_kernel, one
+// in fp64 (mesh_bounds::block_reduce) and writes one partial pair per workgroup; tree_cost_sum_kernel, one
 // workgroup, adds the partials in workgroup order and divides by root_area.  The result does not depend on the launch.
 #ifndef CGRT_TREE_COST_HPP
 #define CGRT_TREE_COST_HPP
 
 namespace tree_cost {
 
-static constexpr int kThreadsCost = 256;
+using namespace mesh_bounds;
+static constexpr int kThreadsCost = kReduceThreads;
 
 __device__ inline double slot_area(float lox, float loy, float loz, float hix, float hiy, float hiz) {
     const double x = (double)hix - (double)lox, y = (double)hiy - (double)loy, z = (double)hiz - (double)loz;
@@ -24,7 +25,7 @@ __device__ inline double slot_area(float lox, float loy, float loz, float hix, f
 
 // partial[2 b] = the sum of S over workgroup b's inner slots, partial[2 b + 1] = of count * S over its leaf slots
 __global__ __launch_bounds__(kThreadsCost) void tree_cost_kernel(const WideNodeRec *wnodes, int nwide, double *partial) {
-    __shared__ double part[kThreadsCost / 64][2];
+    __shared__ double part[4 * 2];
     const int i = blockIdx.x * kThreadsCost + threadIdx.x;
     double v[2] = {0.0, 0.0};
     if (i < nwide) {
@@ -37,13 +38,9 @@ __global__ __launch_bounds__(kThreadsCost) void tree_cost_kernel(const WideNodeR
             else v[1] += (double)(r & 15) * S;
         }
     }
-    for (int off = 32; off > 0; off >>= 1)
-        for (int k = 0; k < 2; k++) v[k] += __shfl_xor(v[k], off);
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < 2; k++) part[threadIdx.x >> 6][k] = v[k];
-    __syncthreads();
+    block_reduce<2>(v, part, Sum());  // (its fixed order: the same doubles in every launch)
     if (threadIdx.x == 0)
-        for (int k = 0; k < 2; k++) partial[2 * (size_t)blockIdx.x + k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
+        for (int k = 0; k < 2; k++) partial[2 * (size_t)blockIdx.x + k] = v[k];
 }
 
 // cost3 = {node_cost, tri_cost, root_area}
@@ -90,30 +87,30 @@ static int mesh_cost_launch(const cgrt_scene *s, int t, double *cost3, hipStream
 extern "C" {
 
 int cgrt_scene_mesh_cost(const cgrt_scene *s, int obj, double *cost3_dev, void *stream) {
-    int t = -1;
-    if (const int rc = refit_check(s, obj, nullptr, 0, &t, "cost", true)) return rc;
+    MeshTarget m;
+    if (const int rc = walk_target(s, obj, "cost", m)) return rc;
     if (!cost3_dev) return fail(CGRT_ERR_INVALID, "cost: null cost3");
     ON_DEVICE(s->device);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (t < 0) {  // an empty mesh: zeros
+    if (m.empty) {  // zeros
         HIP_TRY(hipMemsetAsync(cost3_dev, 0, 3 * sizeof(double), st));
         return CGRT_OK;
     }
-    return mesh_cost_launch(s, t, cost3_dev, st);
+    return mesh_cost_launch(s, m.tree, cost3_dev, st);
 }
 
 int cgrt_scene_mesh_cost_host(const cgrt_scene *s, int obj, cgrt_tree_cost *out) {
-    int t = -1;
-    if (const int rc = refit_check(s, obj, nullptr, 0, &t, "cost", true)) return rc;
+    MeshTarget m;
+    if (const int rc = walk_target(s, obj, "cost", m)) return rc;
     if (!out) return fail(CGRT_ERR_INVALID, "cost: null out");
     out->node_cost = out->tri_cost = out->root_area = 0.0;
-    if (t < 0) return CGRT_OK;
+    if (m.empty) return CGRT_OK;
     ON_DEVICE(s->device);
-    DevBuf d;
-    HIP_TRY(d.alloc(3 * sizeof(double)));
-    if (const int rc = mesh_cost_launch(s, t, d.as<double>(), 0)) return rc;
+    HostStage hs;
     double c[3];
-    HIP_TRY(hipMemcpy(c, d.p, sizeof(c), hipMemcpyDeviceToHost));  // synchronises
+    double *d = hs.out(c, sizeof(c));
+    if (hs.error()) return hs.error();
+    if (const int rc = hs.finish(mesh_cost_launch(s, m.tree, d, 0))) return rc;
     out->node_cost = c[0];
     out->tri_cost = c[1];
     out->root_area = c[2];

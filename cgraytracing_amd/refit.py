@@ -64,6 +64,16 @@ class Scene(engine.Scene):
         check(self._L.cgrt_scene_mesh_cost_host(self._h, int(obj), C.byref(tc)))
         return {f: getattr(tc, f) for f, _ in tc._fields_}
 
+    def mesh_bounds(self, obj):
+        """cgrt_scene_mesh_bounds_host: dict(centre float64 [3], s0 float, bmax np.float32, cover float64 [n,4]) -- the bounding
+        sphere, the tree's coordinate bound and the cover spheres of mesh `obj` as the device holds them now."""
+        n, s0, bmax, centre = C.c_int32(), C.c_double(), C.c_float(), np.zeros(3)
+        check(self._L.cgrt_scene_mesh_bounds_host(self._h, int(obj), None, None, None, None, 0, C.byref(n)))
+        cover = np.zeros((n.value, 4))
+        check(self._L.cgrt_scene_mesh_bounds_host(self._h, int(obj), centre.ctypes.data, C.byref(s0), C.byref(bmax),
+                                                  cover.ctypes.data if n.value else None, n.value, C.byref(n)))
+        return dict(centre=centre, s0=s0.value, bmax=np.float32(bmax.value), cover=cover)
+
     def refit_plan(self, t=0):
         """(parent [nwide], slot [nwide], arrivals [nwide], src [ntris]): see cgrt_scene_refit_plan_host."""
         nw, nt = C.c_int32(), C.c_int32()

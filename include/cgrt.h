@@ -55,7 +55,8 @@ extern "C" {
                             cgrt_scene_refit_info, cgrt_scene_refit_plan_host (refit of committed opaque meshes);
                             cgrt_scene_rebuild_mesh, cgrt_scene_rebuild_mesh_host, cgrt_rebuild_info, cgrt_scene_rebuild_info,
                             cgrt_tree_cost, cgrt_scene_mesh_cost, cgrt_scene_mesh_cost_host (in-place rebuild of device-built
-                            opaque meshes, and the tree cost that tells when one pays) */
+                            opaque meshes, and the tree cost that tells when one pays); cgrt_scene_mesh_bounds_host (a
+                            mesh's bounding and cover spheres as the device holds them, for verification) */
 
 enum {
     CGRT_OK = 0,
@@ -500,6 +501,14 @@ int cgrt_scene_rebuild_info(const cgrt_scene *s, int obj, cgrt_rebuild_info *out
 typedef struct cgrt_tree_cost { double node_cost, tri_cost, root_area; } cgrt_tree_cost; /* 24 bytes */
 int cgrt_scene_mesh_cost(const cgrt_scene *s, int obj, double *cost3_dev, void *stream);
 int cgrt_scene_mesh_cost_host(const cgrt_scene *s, int obj, cgrt_tree_cost *out);
+
+/* The bounds the device currently holds for opaque mesh `obj`, for verification: whichever of commit, refit and rebuild wrote them
+ * last.  centre3 / s0: the bounding sphere (centre, squared radius); bmax: the tree's bound of |coordinate|; cover4: the mesh's
+ * cover spheres, 4 doubles each (centre, radius), *n_cover of them.  cover4 == NULL is the sizing call; with cover4, cap is its
+ * room in spheres.  Any other output may be NULL.  Null stream, synchronises (as cgrt_scene_wide_dump after a refit).  Refusals as
+ * for cgrt_scene_mesh_cost, under the name "bounds"; an empty mesh has no cover sphere and s0 = -1. */
+int cgrt_scene_mesh_bounds_host(const cgrt_scene *s, int obj, double centre3[3], double *s0, float *bmax, double *cover4, int32_t cap,
+                                int32_t *n_cover);
 
 /* ---- the hot path -------------------------------------------------------------------------------------
  * Renders grid->rows rows: for every pixel and sample it runs the reference's trace(flag=true) recursion
