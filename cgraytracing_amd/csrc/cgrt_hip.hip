@@ -1487,6 +1487,7 @@ int cgrt_inside_probe(const cgrt_scene *s, int op, const double *rays, int64_t n
 #include "cgrt_ppm_table.hpp"
 #include "cgrt_photon_trace.hpp"
 #include "cgrt_ppm_apply.hpp"
+#include "cgrt_photon_session.hpp"
 #include "cgrt_ppm_session.hpp"
 #include "cgrt_sppm.hpp"
 #include "cgrt_output.hpp"

@@ -1,5 +1,7 @@
 // Photon pass: cgrt_ppm_session -- the state of a photon-mapping run -- its stages (eye, table,
-// photons in batches as PpmSchedule of cgrt_ppm_plan.h decides, gather) and the cgrt_ppm_* entry points.
+// photons in batches as PpmSchedule of cgrt_ppm_plan.h decides, gather) and the cgrt_ppm_* entry points.  What it shares with
+// cgrt_sppm_session (cgrt_sppm.hpp) -- the eye capture, the pair buffers, the producer's setup, the byte accounting, the image
+// to the host or the device, the Hitpoint read-back, destroy, the stage timer -- is PhotonSession of cgrt_photon_session.hpp.
 //
 // Reference: render() main.cpp:223-258 + trace(flag=false) main.cpp:101-128,158-165 + Hashtable hash.h:20-70.
 // The reference runs eight OpenMP threads that race on the hitpoints and seed rand() from the clock, so its
@@ -21,32 +23,8 @@
 //                              (main.cpp:116-122), re-checking the distance against the current radius.
 // Hitpoints are kept sorted by (bucket, emission order) = the reference's table order, which is also the order of
 // its final gather (main.cpp:252-258); the image is summed per pixel in that order.
-#include <climits>
-#include <memory>
-
-namespace {
-struct Timer {  // device time between two points of the null stream
-    hipEvent_t a = nullptr, b = nullptr;
-    Timer() { (void)hipEventCreate(&a); (void)hipEventCreate(&b); }
-    ~Timer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    void start() { (void)hipEventRecord(a, 0); }
-    double stop() {
-        (void)hipEventRecord(b, 0);
-        (void)hipEventSynchronize(b);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, a, b);
-        return (double)ms;
-    }
-};
-}  // namespace
 
 // ---- the batch loop of every photon stage (cgrt_ppm_session::photons; a pass of cgrt_sppm_session) ---------------------------
-// The pair buffers of one batch: the search writes (k0, v0), the sort (k1, v1); npairs = {pairs, events} of the batch
-struct PairBufs {
-    unsigned long long *k0, *k1;
-    unsigned int *v0, *v1;
-    unsigned long long *npairs;
-};
 // The photons of the call `sched` has begun, against table `tab`, applied on the null stream batch by batch as `sched` decides.
 // produce(batch) enqueues a batch on the producer.  apply(np, buf) launches what consumes an applied batch: its np pairs sorted
 // by (hitpoint, slot) in (pb.k1, pb.v1) and the events of buffer buf.  n_events, n_pairs: added to for every applied batch.
@@ -97,78 +75,42 @@ static int photon_batches(PpmSchedule &sched, PhotonProducer &pp, PpmTable &tab,
 // photon count.  Photon i always draws from the keyed stream
 // (seed, i) and a hitpoint replays its events in photon order, so the state after photons [0, a) then [a, b) is the state
 // after [0, b): how the photons are split into calls and batches never shows in the result.
-struct cgrt_ppm_session {
-    const cgrt_scene *s = nullptr;
-    cgrt_photons ph{};
-    // the image the session gathers into, the gather's normaliser and the photons' depth limit: a grid session's grid.width,
-    // .rows, .spp, .max_depth; a ray session's cgrt_ray_pixels and rays->max_depth; a hitpoint session's cgrt_hitpoints fields
-    int width = 0, rows = 0, spp = 1, max_depth = 0;
+struct cgrt_ppm_session : PhotonSession {
+    static constexpr const char *kWho = "photon session";
+    // width, rows, spp and the photons' depth limit: a grid session's grid.width, .rows, .spp, .max_depth; a ray session's
+    // cgrt_ray_pixels and rays->max_depth; a hitpoint session's cgrt_hitpoints fields
+    int max_depth = 0;
     bool striped = false;  // grid session over block-cyclic rows: no rgb8
     bool lookahead = false;  // session: trace the next batch on the producer stream when a call ends
-    uint64_t geometry_gen = 0;  // session: the scene's refit count at creation -- the Hitpoints are those of that geometry
     PpmTable tab;            // the hitpoints in table order and the per-pixel index
-    int64_t dev_bytes = 0;  // what this state allocated itself (the table, sort scratch and producer buffers are added by bytes())
-    DevBuf pk0, pk1, pv0, pv1, npairs;          // (hitpoint, event) pairs of one batch
-    DevBuf img, rgb8;                           // session: device image of cgrt_ppm_session_image (host outputs)
-    GrowBuf main_tmp;
-    PhotonProducer pp;  // declared last of the buffers: its destructor waits for its stream before they are freed
     PpmSchedule sched;  // the setup, which photons are applied (sched.done), the batch size, the batch traced ahead
-    uint64_t n_events = 0, n_pairs = 0;
-    double ms_eye = 0, ms_table = 0, ms_photons = 0, ms_last_add = 0;
-    mutable double ms_last_image = 0;
-    mutable hipEvent_t img_a = nullptr, img_b = nullptr;  // session: brackets the last gather (on the stream it ran on)
-    mutable bool img_pending = false;                     // img_b recorded, ms_last_image not yet read from it
+    double ms_last_add = 0;
 
-    ~cgrt_ppm_session() {
-        if (img_b) (void)hipEventSynchronize(img_b);
-        if (img_a) (void)hipEventDestroy(img_a);
-        if (img_b) (void)hipEventDestroy(img_b);
-    }
-    hipError_t take(DevBuf &b, size_t bytes) {
-        dev_bytes += (int64_t)bytes;
-        return b.alloc(bytes);
-    }
-    int64_t bytes() const { return dev_bytes + tab.dev_bytes + sched.setup.producer_bytes + (int64_t)main_tmp.cap + (int64_t)pp.tmp.cap; }
-    void frame(int width_, int rows_, int spp_, int max_depth_, bool striped_) {
-        width = width_; rows = rows_; spp = spp_; max_depth = max_depth_;
+    ~cgrt_ppm_session() { settle(); }
+    long long done() const { return sched.done; }
+    bool is_striped() const { return striped; }
+    const PpmTable *hitpoint_table() const { return &tab; }
+    int64_t bytes() const { return PhotonSession::bytes(&tab); }
+    void frame(const cgrt_scene *s_, const cgrt_photons *ph_, int width_, int rows_, int spp_, int max_depth_, bool striped_) {
+        open(s_, *ph_, width_, rows_, spp_);
+        max_depth = max_depth_;
         striped = striped_;
+        tab.npix = texels();
     }
-    template <class Capture> int eye(const cgrt_scene *s_, const cgrt_photons *ph_, Capture capture, DevBuf &rec);
+    // eye pass (capture: see PhotonSession::capture_eye); frame() has been called
+    template <class Capture> int eye(Capture capture, DevBuf &rec) { return capture_eye(capture, "photon pass", rec, tab.n); }
     int table(DevBuf &rec, const int64_t *ray_pixel, bool rays);
-    int table(const cgrt_scene *s_, const cgrt_photons *ph_, const cgrt_hitpoints &in);
+    int table(const cgrt_hitpoints &in);
     int photon_setup(bool session);
     int photons(long long last, bool keep_ahead, const cgrt_photon_rays *pr = nullptr);
     int gather(double *d_img, unsigned char *d_rgb8, hipStream_t st) const;
 };
 
-// ---- eye pass: hitpoint records, device resident (count first, then capture).  capture(cap, &d_rec, &count) is
-// hitpoints_device over a grid or ray_hitpoints_device over a ray buffer; frame() has been called ----
-template <class Capture>
-int cgrt_ppm_session::eye(const cgrt_scene *s_, const cgrt_photons *ph_, Capture capture, DevBuf &rec) {
-    s = s_; ph = *ph_;
-    Timer tm;
-    tm.start();
-    uint64_t nhp = 0;
-    int rc = capture(0, nullptr, &nhp);
-    if (rc) return rc;
-    tab.npix = (long long)rows * width;
-    tab.n = (size_t)nhp;
-    if (tab.n >= (1ull << 31)) return fail(CGRT_ERR_LIMIT, "photon pass: more than 2^31 hitpoints");
-    if (tab.n) {
-        double *d_rec = nullptr;
-        rc = capture(nhp, &d_rec, &nhp);
-        rec.p = d_rec;
-        if (rc) return rc;
-    }
-    ms_eye = tm.stop();
-    return CGRT_OK;
-}
 static auto grid_capture(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid) {
     return [=](uint64_t cap, double **d_rec, uint64_t *count) { return hitpoints_device(s, cam, grid, cap, d_rec, count); };
 }
 
 int cgrt_ppm_session::table(DevBuf &rec, const int64_t *ray_pixel, bool rays) {
-    Timer tm;
     tm.start();
     if (const int rc = tab.build(rec, ph, spp, ray_pixel, rays, main_tmp)) return rc;
     ms_table = tm.stop();
@@ -176,10 +118,7 @@ int cgrt_ppm_session::table(DevBuf &rec, const int64_t *ray_pixel, bool rays) {
 }
 
 // The table of a session whose Hitpoints are the caller's records: there is no eye stage (ms_eye stays 0); frame() has been called
-int cgrt_ppm_session::table(const cgrt_scene *s_, const cgrt_photons *ph_, const cgrt_hitpoints &in) {
-    s = s_; ph = *ph_;
-    tab.npix = (long long)rows * width;
-    Timer tm;
+int cgrt_ppm_session::table(const cgrt_hitpoints &in) {
     tm.start();
     if (const int rc = tab.build(in, ph, main_tmp)) return rc;
     ms_table = tm.stop();
@@ -189,13 +128,8 @@ int cgrt_ppm_session::table(const cgrt_scene *s_, const cgrt_photons *ph_, const
 // Batch size, pair buffers and the producer (ppm_setup decides)
 int cgrt_ppm_session::photon_setup(bool session) {
     sched.start(ppm_setup(ph, tab.n, session, photon_overlap_allowed()));
-    const PpmSetup &setup = sched.setup;
-    if (setup.nbuf)
-        if (const int rc = pp.init(setup.nbuf, (size_t)setup.batch * kSegStride, setup.overlap)) return rc;
-    HIP_TRY(take(pk0, (size_t)setup.pair_cap * 8)); HIP_TRY(take(pk1, (size_t)setup.pair_cap * 8));
-    HIP_TRY(take(pv0, (size_t)setup.pair_cap * 4)); HIP_TRY(take(pv1, (size_t)setup.pair_cap * 4));
-    HIP_TRY(take(npairs, 16));
-    return CGRT_OK;
+    if (const int rc = producer(sched.setup, "photon pass")) return rc;
+    return pair_buffers(sched.setup.pair_cap);
 }
 
 // Photons [done, last), applied on the null stream, batch by batch as `sched` decides.  keep_ahead: when the range is done,
@@ -223,8 +157,6 @@ int cgrt_ppm_session::photons(long long last, bool keep_ahead, const cgrt_photon
     };
     const int T = 256;
     const unsigned nb = (unsigned)((tab.n + T - 1) / T);
-    const PairBufs pb{pk0.as<unsigned long long>(), pk1.as<unsigned long long>(), pv0.as<unsigned int>(), pv1.as<unsigned int>(),
-                      npairs.as<unsigned long long>()};
     int rc = photon_batches(
         sched, pp, tab, pb, main_tmp, n_events, n_pairs, [&](const PpmBatch &b) { return produce(b, pr); },
         [&](unsigned int np, int cur) -> int {  // 4. the ordered replay
@@ -271,42 +203,33 @@ extern "C" int cgrt_ppm_render(const cgrt_scene *s, const cgrt_camera *cam, cons
         return fail(CGRT_ERR_UNSUPPORTED, "photon pass: rgb8 needs contiguous rows; tone-map the assembled frame (cgrt_tonemap_rgb8)");
     ON_DEVICE(s->device);
     cgrt_ppm_session run;
-    run.frame(grid->width, grid->rows, grid->spp, grid->max_depth, grid->stripe_nranks > 1);
+    run.frame(s, ph, grid->width, grid->rows, grid->spp, grid->max_depth, grid->stripe_nranks > 1);
+    if ((rc = run.events_ok("photon pass"))) return rc;
     {
         DevBuf rec;
-        rc = run.eye(s, ph, grid_capture(s, cam, grid), rec);
+        rc = run.eye(grid_capture(s, cam, grid), rec);
         out->ms_eye = run.ms_eye;
         if (rc == CGRT_OK) rc = run.table(rec, nullptr, false);
         out->ms_table = run.ms_table;
         if (rc) return rc;
     }
     // ---- photons, in batches ----
-    Timer tm;
-    tm.start();
+    run.tm.start();
     rc = run.photon_setup(false);
     if (rc == CGRT_OK) rc = run.photons(ph->nphotons, false);
     out->n_events = run.n_events;
     out->n_pairs = run.n_pairs;
     out->n_batch_halvings = run.sched.n_halvings;
     if (rc) return rc;
-    out->ms_photons = tm.stop();
-    // ---- final gather + tone map ----
-    tm.start();
-    const long long npix = run.tab.npix;
-    DevBuf img, rgb8;
-    HIP_TRY(img.alloc((size_t)npix * 3 * sizeof(double)));
-    if (out->rgb8) HIP_TRY(rgb8.alloc((size_t)npix * 3));
-    rc = run.gather(img.as<double>(), out->rgb8 ? rgb8.as<unsigned char>() : nullptr, 0);
-    if (rc) return rc;
-    out->ms_gather = tm.stop();
-    if (out->image) HIP_TRY(hipMemcpy(out->image, img.p, (size_t)npix * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out->rgb8) HIP_TRY(hipMemcpy(out->rgb8, rgb8.p, (size_t)npix * 3, hipMemcpyDeviceToHost));
-    out->hp_count = run.tab.n;
-    if (out->hp16 && out->hp_cap) {
-        const size_t m = run.tab.n < out->hp_cap ? run.tab.n : (size_t)out->hp_cap;
-        HIP_TRY(hipMemcpy(out->hp16, run.tab.hp.p, m * 16 * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return CGRT_OK;
+    out->ms_photons = run.tm.stop();
+    // ---- final gather + tone map, then the Hitpoints ----
+    const auto gather = [&run](double *d_img, unsigned char *d_rgb8, hipStream_t st) { return run.gather(d_img, d_rgb8, st); };
+    run.tm.start();  // ms_gather: from before the scratch is allocated to behind the gather
+    if ((rc = run.image_host(gather, out->image, out->rgb8))) return rc;
+    float ms_gather = 0;
+    HIP_TRY(hipEventElapsedTime(&ms_gather, run.tm.a, run.img_tm.b));
+    out->ms_gather = ms_gather;
+    return hitpoints_to_host(&run.tab, out->hp16, out->hp16 ? out->hp_cap : 0, &out->hp_count);
 }
 
 // ---- resumable photon mapping: the state above, kept between calls -------------------------------------------------
@@ -321,25 +244,22 @@ static int session_create(const cgrt_scene *s, const cgrt_photons *ph, int flags
     std::unique_ptr<cgrt_ppm_session> p(new (std::nothrow) cgrt_ppm_session());
     if (!p) return fail(CGRT_ERR_LIMIT, "out of host memory");
     p->lookahead = !(flags & CGRT_PPM_SESSION_NO_LOOKAHEAD);
-    p->geometry_gen = s->geometry_gen;
-    p->frame(width, rows, spp, max_depth, striped);
-    HIP_TRY(hipEventCreate(&p->img_a));
-    HIP_TRY(hipEventCreate(&p->img_b));
-    int rc = CGRT_OK;
+    p->frame(s, ph, width, rows, spp, max_depth, striped);
+    int rc = p->events_ok(cgrt_ppm_session::kWho);
+    if (rc) return rc;
     if (hps) {
-        if ((rc = p->table(s, ph, *hps))) return rc;
+        if ((rc = p->table(*hps))) return rc;
         HIP_TRY(hipDeviceSynchronize());  // the records are read before the call returns
     } else {
         DevBuf rec;
-        if ((rc = p->eye(s, ph, capture, rec))) return rc;
+        if ((rc = p->eye(capture, rec))) return rc;
         if ((rc = p->table(rec, ray_pixel, rays))) return rc;
         if (rays) HIP_TRY(hipDeviceSynchronize());  // ray_pixel and the records are read before the call returns
     }
-    Timer tm;
-    tm.start();
+    p->tm.start();
     rc = p->photon_setup(true);
     if (rc == CGRT_OK) rc = p->photons(p->ph.nphotons, p->lookahead);
-    p->ms_last_add = tm.stop();
+    p->ms_last_add = p->tm.stop();
     p->ms_photons = p->ms_last_add;
     if (rc) return rc;
     *out = p.release();
@@ -396,23 +316,18 @@ extern "C" int cgrt_ppm_session_create_hitpoints(const cgrt_scene *s, const cgrt
     return session_create(s, ph, flags, hps->width, hps->rows, hps->spp, hps->max_depth, false, no_eye, nullptr, false, out, hps);
 }
 
-extern "C" void cgrt_ppm_session_destroy(cgrt_ppm_session *p) {
-    if (!p) return;
-    DeviceGuard g(p->s->device);
-    if (g.err == hipSuccess) (void)hipStreamSynchronize(0);
-    delete p;  // waits for the last gather and the producer stream (lookahead) before freeing
-}
+extern "C" void cgrt_ppm_session_destroy(cgrt_ppm_session *p) { session_destroy(p); }
 
 // `count` more photons: the built-in emitter's, or (pr) the caller's
 static int session_add(cgrt_ppm_session *p, long long count, const cgrt_photon_rays *pr) {
-    if (p->geometry_gen != p->s->geometry_gen) return fail(CGRT_ERR_INVALID, kRefitStale);  // (image, hitpoints, get_info go on working)
+    int rc = p->fresh();
+    if (rc) return rc;
     ON_DEVICE(p->s->device);
-    if (p->img_pending) HIP_TRY(hipStreamWaitEvent(0, p->img_b, 0));  // a gather on a caller's stream reads hp
+    if ((rc = p->wait_image())) return rc;  // a gather on a caller's stream reads hp
     // the producer stream does not wait for the null stream: arrays a kernel on the null stream still writes must be complete
     if (pr && p->pp.st) HIP_TRY(hipStreamSynchronize(0));
-    Timer tm;
-    tm.start();
-    const int rc = p->photons(p->sched.done + count, pr ? false : p->lookahead, pr);
+    p->tm.start();
+    rc = p->photons(p->sched.done + count, pr ? false : p->lookahead, pr);
     if (pr) {  // also when a batch failed: nothing traced ahead from pr's arrays outlives the call
         p->sched.drop_ahead();
         if (p->pp.st) {
@@ -420,7 +335,7 @@ static int session_add(cgrt_ppm_session *p, long long count, const cgrt_photon_r
             if (e != hipSuccess && rc == CGRT_OK) return fail(CGRT_ERR_DEVICE, std::string("producer stream: ") + hipGetErrorString(e));
         }
     }
-    p->ms_last_add = tm.stop();  // also when a batch failed: what was applied before it has finished
+    p->ms_last_add = p->tm.stop();  // also when a batch failed: what was applied before it has finished
     p->ms_photons += p->ms_last_add;
     return rc;
 }
@@ -437,66 +352,24 @@ extern "C" int cgrt_ppm_session_add_photon_rays(cgrt_ppm_session *p, const cgrt_
     return session_add(p, pr->n, pr);
 }
 
-static int session_image_args(const cgrt_ppm_session *p, const uint8_t *rgb8) {
-    if (!p) return fail(CGRT_ERR_INVALID, "null session");
-    if (p->sched.done == 0) return fail(CGRT_ERR_INVALID, "photon session: no photon yet (the image would be flux / (PI r2 0))");
-    if (rgb8 && p->striped)
-        return fail(CGRT_ERR_UNSUPPORTED, "photon session: rgb8 needs contiguous rows; tone-map the assembled frame (cgrt_tonemap_rgb8)");
-    return CGRT_OK;
-}
-
-extern "C" int cgrt_ppm_session_image(const cgrt_ppm_session *cp, double *image, uint8_t *rgb8) {
-    int rc = session_image_args(cp, rgb8);
-    if (rc) return rc;
-    cgrt_ppm_session *p = const_cast<cgrt_ppm_session *>(cp);  // the image buffers are scratch, not state
-    ON_DEVICE(p->s->device);
-    const size_t npix = (size_t)p->tab.npix;
-    if (image && !p->img.p) HIP_TRY(p->take(p->img, npix * 3 * sizeof(double)));
-    if (rgb8 && !p->rgb8.p) HIP_TRY(p->take(p->rgb8, npix * 3));
-    HIP_TRY(hipEventRecord(p->img_a, 0));
-    rc = p->gather(image ? p->img.as<double>() : nullptr, rgb8 ? p->rgb8.as<unsigned char>() : nullptr, 0);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(p->img_b, 0));
-    HIP_TRY(hipEventSynchronize(p->img_b));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, p->img_a, p->img_b));
-    p->ms_last_image = ms;
-    p->img_pending = false;
-    if (image) HIP_TRY(hipMemcpy(image, p->img.p, npix * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (rgb8) HIP_TRY(hipMemcpy(rgb8, p->rgb8.p, npix * 3, hipMemcpyDeviceToHost));
-    return CGRT_OK;
+extern "C" int cgrt_ppm_session_image(const cgrt_ppm_session *p, double *image, uint8_t *rgb8) {
+    return session_image(p, image, rgb8, nullptr);
 }
 
 extern "C" int cgrt_ppm_session_image_device(const cgrt_ppm_session *p, double *image, uint8_t *rgb8, void *stream) {
-    int rc = session_image_args(p, rgb8);
-    if (rc) return rc;
-    ON_DEVICE(p->s->device);
     const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    HIP_TRY(hipEventRecord(p->img_a, st));
-    if ((rc = p->gather(image, rgb8, st))) return rc;
-    HIP_TRY(hipEventRecord(p->img_b, st));
-    p->img_pending = true;  // the next add_photons waits for it; get_info reads its time
-    return CGRT_OK;
+    return session_image(p, image, rgb8, &st);
 }
 
 extern "C" int cgrt_ppm_session_hitpoints(const cgrt_ppm_session *p, double *hp16, uint64_t cap, uint64_t *count) {
-    if (!p || !count || (cap > 0 && !hp16)) return fail(CGRT_ERR_INVALID, "bad argument");
-    ON_DEVICE(p->s->device);
-    *count = p->tab.n;
-    const size_t m = p->tab.n < cap ? p->tab.n : (size_t)cap;
-    if (m) HIP_TRY(hipMemcpy(hp16, p->tab.hp.p, m * 16 * sizeof(double), hipMemcpyDeviceToHost));
-    return CGRT_OK;
+    return session_hitpoints(p, hp16, cap, count);
 }
 
 extern "C" int cgrt_ppm_session_get_info(const cgrt_ppm_session *p, cgrt_ppm_session_info *out) {
     if (!p || !out) return fail(CGRT_ERR_INVALID, "null argument");
-    if (p->img_pending) {
+    if (p->img_pending) {  // the time of an image on a caller's stream is read when it is asked for
         ON_DEVICE(p->s->device);
-        HIP_TRY(hipEventSynchronize(p->img_b));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, p->img_a, p->img_b));
-        p->ms_last_image = ms;
-        p->img_pending = false;
+        if (const int rc = p->image_time()) return rc;
     }
     out->photons_done = p->sched.done;
     out->hp_count = p->tab.n;

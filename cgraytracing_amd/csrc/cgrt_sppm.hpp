@@ -3,7 +3,9 @@
 //
 // A pass is the photon pass of cgrt_ppm_session.hpp with another ending.  Its stages up to the sorted pairs are that file's, the
 // same code: the Hitpoint capture of a grid or of rays, PpmTable::build, PhotonProducer, photon_pairs_kernel, sort_pairs, the
-// batches PpmSchedule decides.  Every Hitpoint searches with its texel's radius, which does not change while the pass runs, so
+// batches PpmSchedule decides.  The session's host core (eye capture, pair buffers, producer setup, byte accounting, the image
+// paths, the Hitpoint read-back, destroy) is PhotonSession of cgrt_photon_session.hpp, shared with cgrt_ppm_session.
+// Every Hitpoint searches with its texel's radius, which does not change while the pass runs, so
 // the pairs that pass the search's two tests ARE the accepted set: there is no replay against a shrinking radius.  Per
 // Hitpoint the accepted photons' flux is summed in slot order (sppm_hitpoint_sum_kernel, once per applied batch), per texel the
 // Hitpoints' sums in the per-pixel index order, and the texel takes sppm_update (cgrt_sppm_plan.h) once
@@ -138,74 +140,42 @@ __global__ void sppm_image_kernel(const double *__restrict__ px, double norm, lo
 
 }  // namespace
 
-struct cgrt_sppm_session {
-    const cgrt_scene *s = nullptr;
-    cgrt_photons ph{};  // nphotons is not used
-    int width = 0, rows = 0, spp = 1, photon_depth = 0;
-    long long npix = 0;
+struct cgrt_sppm_session : PhotonSession {  // (ph.nphotons is not used)
+    static constexpr const char *kWho = "sppm session";
+    int photon_depth = 0;
     bool have_stripe = false;  // a grid pass has fixed `stripe`
-    uint64_t geometry_gen = 0;  // the scene's refit count at creation: the texels' statistics are those of that geometry
     SppmStripe stripe;
-    DevBuf px;                       // [npix][kSppmPixelDoubles], for the session's life
+    DevBuf px;                       // [texels()][kSppmPixelDoubles], for the session's life
     std::unique_ptr<PpmTable> tab;   // the last pass's Hitpoints (null before the first pass and after a failed one)
-    GrowBuf pk0, pk1, pv0, pv1;      // (hitpoint, event) pairs of one batch; they grow with the largest pass's pair_cap
-    DevBuf npairs, img, rgb8;
-    int64_t dev_bytes = 0;  // px, npairs, img, rgb8
-    int64_t producer_bytes = 0;
-    GrowBuf main_tmp;
-    PhotonProducer pp;  // declared last of the buffers: its destructor waits for its stream before they are freed
-    bool pp_ready = false, pp_broken = false;
     long long photons_done = 0, passes = 0;
-    uint64_t n_events = 0, n_pairs = 0, n_halvings = 0;
-    double ms_eye = 0, ms_table = 0, ms_photons = 0, ms_update = 0;
-    hipEvent_t img_b = nullptr;  // behind the last image on a caller's stream: the next pass waits for it
-    bool img_pending = false;
+    uint64_t n_halvings = 0;
+    double ms_update = 0;
 
-    ~cgrt_sppm_session() {
-        if (img_b) {
-            (void)hipEventSynchronize(img_b);
-            (void)hipEventDestroy(img_b);
-        }
-    }
-    hipError_t take(DevBuf &b, size_t bytes) {
-        dev_bytes += (int64_t)bytes;
-        return b.alloc(bytes);
-    }
-    int64_t bytes() const {
-        return dev_bytes + (tab ? tab->dev_bytes : 0) + producer_bytes + (int64_t)(pk0.cap + pk1.cap + pv0.cap + pv1.cap) +
-               (int64_t)main_tmp.cap + (int64_t)pp.tmp.cap;
-    }
-    bool striped() const { return have_stripe && stripe.nranks > 1; }
+    ~cgrt_sppm_session() { settle(); }
+    long long done() const { return photons_done; }
+    bool is_striped() const { return have_stripe && stripe.nranks > 1; }
+    const PpmTable *hitpoint_table() const { return tab.get(); }
+    int64_t bytes() const { return PhotonSession::bytes(tab.get()); }
     template <class Capture> int pass(Capture capture, const int64_t *ray_pixel, bool rays, long long count);
     int photons(PpmTable &t, long long count, uint64_t &events, uint64_t &pairs);
-    int image(double *d_img, unsigned char *d_rgb8, hipStream_t st) const;
+    int gather(double *d_img, unsigned char *d_rgb8, hipStream_t st) const;
 };
 
 // Photons [photons_done, photons_done + count) against table t, applied on the null stream batch by batch as a fresh PpmSchedule
 // decides: cgrt_ppm_session::photons with the sum in the replay's place, its own photons only and nothing traced ahead when it
 // ends.  Nothing of the session's state changes here: the caller commits the pass.
 int cgrt_sppm_session::photons(PpmTable &t, long long count, uint64_t &events, uint64_t &pairs) {
-    if (pp_broken) return fail(CGRT_ERR_DEVICE, "sppm session: the photon producer could not be set up");
     const PpmSetup setup = ppm_setup(ph, t.n, true, photon_overlap_allowed());
-    if (!pp_ready) {  // the event buffers' size is ph.batch's: set up once
-        if (const int rc = pp.init(setup.nbuf, (size_t)setup.batch * kSegStride, setup.overlap)) {
-            pp_broken = true;
-            return rc;
-        }
-        pp_ready = true;
-        producer_bytes = setup.producer_bytes;
-    }
-    HIP_TRY(pk0.need((size_t)setup.pair_cap * 8)); HIP_TRY(pk1.need((size_t)setup.pair_cap * 8));
-    HIP_TRY(pv0.need((size_t)setup.pair_cap * 4)); HIP_TRY(pv1.need((size_t)setup.pair_cap * 4));
+    int rc = producer(setup, kWho);
+    if (rc == CGRT_OK) rc = pair_buffers(setup.pair_cap);  // they grow with the largest pass's pair_cap
+    if (rc) return rc;
     PpmSchedule sched;  // a fresh one per pass: nothing is traced ahead from one pass to the next
     sched.start(setup);
     sched.done = photons_done;
     (void)sched.begin(photons_done + count, false, false);
-    const PairBufs pb{static_cast<unsigned long long *>(pk0.p), static_cast<unsigned long long *>(pk1.p), static_cast<unsigned int *>(pv0.p),
-                      static_cast<unsigned int *>(pv1.p), npairs.as<unsigned long long>()};
     const int T = 256;
     const unsigned nb = (unsigned)((t.n + T - 1) / T);
-    const int rc = photon_batches(
+    rc = photon_batches(
         sched, pp, t, pb, main_tmp, events, pairs,
         [&](const PpmBatch &b) { return pp.produce(s, photon_args(ph, b.first, b.count, photon_depth), t.ha, b.buf); },
         [&](unsigned int np, int cur) -> int {  // 3. the sums, in the replay's place
@@ -223,30 +193,17 @@ int cgrt_sppm_session::photons(PpmTable &t, long long count, uint64_t &events, u
 // ray_pixel, rays: see PpmTable::build
 template <class Capture>
 int cgrt_sppm_session::pass(Capture capture, const int64_t *ray_pixel, bool rays, long long count) {
-    if (img_pending) {  // an image on a caller's stream reads the texels
-        HIP_TRY(hipStreamWaitEvent(0, img_b, 0));
-        img_pending = false;
-    }
+    int rc = wait_image();  // an image on a caller's stream reads the texels
+    if (rc) return rc;
+    img_pending = false;  // the null stream is behind it now, and nothing here reads its time
     tab.reset();  // the last pass's Hitpoints go before the new ones come: a session never holds two tables
     std::unique_ptr<PpmTable> t(new (std::nothrow) PpmTable());
     if (!t) return fail(CGRT_ERR_LIMIT, "out of host memory");
-    Timer tm;
-    int rc = CGRT_OK;
+    const long long npix = texels();
     {
         DevBuf rec;
-        tm.start();
-        uint64_t nhp = 0;
-        if ((rc = capture(0, nullptr, &nhp))) return rc;
-        if (nhp >= (1ull << 31)) return fail(CGRT_ERR_LIMIT, "sppm pass: more than 2^31 hitpoints");
         t->npix = npix;
-        t->n = (size_t)nhp;
-        if (t->n) {
-            double *d_rec = nullptr;
-            rc = capture(nhp, &d_rec, &nhp);
-            rec.p = d_rec;
-            if (rc) return rc;
-        }
-        ms_eye = tm.stop();
+        if ((rc = capture_eye(capture, "sppm pass", rec, t->n))) return rc;
         tm.start();
         if ((rc = t->build(rec, ph, spp, ray_pixel, rays, main_tmp))) return rc;
         const int T = 256;
@@ -277,8 +234,9 @@ int cgrt_sppm_session::pass(Capture capture, const int64_t *ray_pixel, bool rays
     return CGRT_OK;
 }
 
-int cgrt_sppm_session::image(double *d_img, unsigned char *d_rgb8, hipStream_t st) const {
+int cgrt_sppm_session::gather(double *d_img, unsigned char *d_rgb8, hipStream_t st) const {
     const int T = 256;
+    const long long npix = texels();
     hipLaunchKernelGGL(sppm_image_kernel, dim3((unsigned)((npix + T - 1) / T)), dim3(T), 0, st, static_cast<const double *>(px.p),
                        (double)photons_done * spp, npix, width, rows, d_img, d_rgb8);
     HIP_TRY(hipGetLastError());
@@ -314,30 +272,23 @@ extern "C" int cgrt_sppm_session_create(const cgrt_scene *s, int32_t width, int3
     ON_DEVICE(s->device);
     std::unique_ptr<cgrt_sppm_session> p(new (std::nothrow) cgrt_sppm_session());
     if (!p) return fail(CGRT_ERR_LIMIT, "out of host memory");
-    p->s = s;
-    p->geometry_gen = s->geometry_gen;
-    p->ph = *ph;
+    p->open(s, *ph, width, rows, spp);
     p->ph.nphotons = 0;
-    p->width = width; p->rows = rows; p->spp = spp; p->photon_depth = photon_depth;
-    p->npix = (long long)width * rows;
-    HIP_TRY(hipEventCreateWithFlags(&p->img_b, hipEventDisableTiming));
-    HIP_TRY(p->take(p->px, (size_t)p->npix * kSppmPixelDoubles * sizeof(double)));
+    p->photon_depth = photon_depth;
+    if (const int rc = p->events_ok(cgrt_sppm_session::kWho)) return rc;
+    const long long npix = p->texels();
+    HIP_TRY(p->take(p->px, (size_t)npix * kSppmPixelDoubles * sizeof(double)));
     HIP_TRY(p->take(p->npairs, 16));
     const double r0 = ppm_grid(p->ph).r0;
     const int T = 256;
-    hipLaunchKernelGGL(sppm_init_kernel, dim3((unsigned)((p->npix + T - 1) / T)), dim3(T), 0, 0, r0 * r0, p->npix, p->px.as<double>());
+    hipLaunchKernelGGL(sppm_init_kernel, dim3((unsigned)((npix + T - 1) / T)), dim3(T), 0, 0, r0 * r0, npix, p->px.as<double>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(0));
     *out = p.release();
     return CGRT_OK;
 }
 
-extern "C" void cgrt_sppm_session_destroy(cgrt_sppm_session *p) {
-    if (!p) return;
-    DeviceGuard g(p->s->device);
-    if (g.err == hipSuccess) (void)hipStreamSynchronize(0);
-    delete p;  // waits for the last image and the producer stream before freeing
-}
+extern "C" void cgrt_sppm_session_destroy(cgrt_sppm_session *p) { session_destroy(p); }
 
 static int sppm_count_ok(const cgrt_sppm_session *p, int64_t nphotons) {
     if (nphotons < 0 || nphotons > LLONG_MAX - p->photons_done) return fail(CGRT_ERR_INVALID, "sppm pass: bad photon count");
@@ -346,8 +297,8 @@ static int sppm_count_ok(const cgrt_sppm_session *p, int64_t nphotons) {
 
 extern "C" int cgrt_sppm_session_pass_grid(cgrt_sppm_session *p, const cgrt_camera *cam, const cgrt_grid *grid, int64_t nphotons) {
     if (!p) return fail(CGRT_ERR_INVALID, "null session");
-    if (p->geometry_gen != p->s->geometry_gen) return fail(CGRT_ERR_INVALID, kRefitStale);  // (image, pixels, get_info go on working)
-    int rc = check_grid(p->s, cam, grid);
+    int rc = p->fresh();
+    if (rc == CGRT_OK) rc = check_grid(p->s, cam, grid);
     if (rc) return rc;
     if (const char *msg = sppm_pass_grid_args(p->width, p->rows, p->spp, grid, p->have_stripe ? &p->stripe : nullptr))
         return fail(CGRT_ERR_INVALID, msg);
@@ -363,8 +314,8 @@ extern "C" int cgrt_sppm_session_pass_grid(cgrt_sppm_session *p, const cgrt_came
 
 extern "C" int cgrt_sppm_session_pass_rays(cgrt_sppm_session *p, const cgrt_rays *rays, const int64_t *pixel, int64_t nphotons) {
     if (!p) return fail(CGRT_ERR_INVALID, "null session");
-    if (p->geometry_gen != p->s->geometry_gen) return fail(CGRT_ERR_INVALID, kRefitStale);
-    int rc = check_capture_rays(p->s, rays);
+    int rc = p->fresh();
+    if (rc == CGRT_OK) rc = check_capture_rays(p->s, rays);
     if (rc) return rc;
     if ((rc = sppm_count_ok(p, nphotons))) return rc;
     ON_DEVICE(p->s->device);
@@ -373,56 +324,24 @@ extern "C" int cgrt_sppm_session_pass_rays(cgrt_sppm_session *p, const cgrt_rays
     return p->pass(capture, pixel, true, nphotons);
 }
 
-static int sppm_image_args(const cgrt_sppm_session *p, const uint8_t *rgb8) {
-    if (!p) return fail(CGRT_ERR_INVALID, "null session");
-    if (p->photons_done == 0) return fail(CGRT_ERR_INVALID, "sppm session: no photon yet (the image would be tau / (PI R2 0))");
-    if (rgb8 && p->striped())
-        return fail(CGRT_ERR_UNSUPPORTED, "sppm session: rgb8 needs contiguous rows; tone-map the assembled frame (cgrt_tonemap_rgb8)");
-    return CGRT_OK;
+extern "C" int cgrt_sppm_session_image(const cgrt_sppm_session *p, double *image, uint8_t *rgb8) {
+    return session_image(p, image, rgb8, nullptr);
 }
 
-extern "C" int cgrt_sppm_session_image(const cgrt_sppm_session *cp, double *image, uint8_t *rgb8) {
-    int rc = sppm_image_args(cp, rgb8);
-    if (rc) return rc;
-    cgrt_sppm_session *p = const_cast<cgrt_sppm_session *>(cp);  // the image buffers are scratch, not state
-    ON_DEVICE(p->s->device);
-    const size_t npix = (size_t)p->npix;
-    if (image && !p->img.p) HIP_TRY(p->take(p->img, npix * 3 * sizeof(double)));
-    if (rgb8 && !p->rgb8.p) HIP_TRY(p->take(p->rgb8, npix * 3));
-    if ((rc = p->image(image ? p->img.as<double>() : nullptr, rgb8 ? p->rgb8.as<unsigned char>() : nullptr, 0))) return rc;
-    HIP_TRY(hipStreamSynchronize(0));
-    if (image) HIP_TRY(hipMemcpy(image, p->img.p, npix * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (rgb8) HIP_TRY(hipMemcpy(rgb8, p->rgb8.p, npix * 3, hipMemcpyDeviceToHost));
-    return CGRT_OK;
-}
-
-extern "C" int cgrt_sppm_session_image_device(const cgrt_sppm_session *cp, double *image, uint8_t *rgb8, void *stream) {
-    int rc = sppm_image_args(cp, rgb8);
-    if (rc) return rc;
-    cgrt_sppm_session *p = const_cast<cgrt_sppm_session *>(cp);
-    ON_DEVICE(p->s->device);
+extern "C" int cgrt_sppm_session_image_device(const cgrt_sppm_session *p, double *image, uint8_t *rgb8, void *stream) {
     const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if ((rc = p->image(image, rgb8, st))) return rc;
-    HIP_TRY(hipEventRecord(p->img_b, st));
-    p->img_pending = true;  // the next pass waits for it
-    return CGRT_OK;
+    return session_image(p, image, rgb8, &st);
 }
 
 extern "C" int cgrt_sppm_session_pixels(const cgrt_sppm_session *p, double *px8) {
     if (!p || !px8) return fail(CGRT_ERR_INVALID, "null argument");
     ON_DEVICE(p->s->device);
-    HIP_TRY(hipMemcpy(px8, p->px.p, (size_t)p->npix * kSppmPixelDoubles * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(px8, p->px.p, (size_t)p->texels() * kSppmPixelDoubles * sizeof(double), hipMemcpyDeviceToHost));
     return CGRT_OK;
 }
 
 extern "C" int cgrt_sppm_session_last_hitpoints(const cgrt_sppm_session *p, double *hp16, uint64_t cap, uint64_t *count) {
-    if (!p || !count || (cap > 0 && !hp16)) return fail(CGRT_ERR_INVALID, "bad argument");
-    ON_DEVICE(p->s->device);
-    const size_t n = p->tab ? p->tab->n : 0;
-    *count = n;
-    const size_t m = n < cap ? n : (size_t)cap;
-    if (m) HIP_TRY(hipMemcpy(hp16, p->tab->hp.p, m * 16 * sizeof(double), hipMemcpyDeviceToHost));
-    return CGRT_OK;
+    return session_hitpoints(p, hp16, cap, count);
 }
 
 extern "C" int cgrt_sppm_session_get_info(const cgrt_sppm_session *p, cgrt_sppm_session_info *out) {

@@ -159,6 +159,40 @@ def test_device_image_on_a_side_stream(gpu_ready):
         assert ses.info()["ms_last_image"] >= 0
 
 
+def test_device_image_then_photons_at_once(gpu_ready):
+    """A gather on a caller's stream is still reading the Hitpoints when add_photons comes: the photons wait for it.  The image
+    is the host image of that photon count bit for bit, the photons after it leave what a session without an image has, and
+    the device image's time is there without a host image in between.  32 x 24, spp 2, four batches a call."""
+    import torch
+    import cgraytracing_amd as cg
+    w, h, spp2, n = 32, 24, 2, 3000
+    with cg.Scene(scenes.scene_c2()) as sc:
+        dev = torch.device("cuda", sc.device)
+        side = torch.cuda.Stream(dev)
+        kw = dict(camera=scenes.cam_dof(), max_depth=5, seed=12345, nphotons=n, batch=800)
+        with sc.ppm_session(w, h, spp2, **kw) as plain, sc.ppm_session(w, h, spp2, **kw) as ses:
+            want, want_rgb = ses.image(), ses.rgb8()
+            rgb = torch.full((h, w, 3), 7, dtype=torch.uint8, device=dev)
+            img = ses.image_tensor(rgb8_out=rgb, stream=side.cuda_stream)
+            ses.add_photons(n)
+            assert ses.info()["ms_last_image"] >= 0
+            side.synchronize()
+            plain.add_photons(n)
+            assert want.max() > 0 and np.array_equal(img.cpu().numpy(), want) and np.array_equal(rgb.cpu().numpy(), want_rgb)
+            assert ses.photons_done == 2 * n and not np.array_equal(ses.image(), want)
+            assert np.array_equal(ses.hitpoints(), plain.hitpoints()) and np.array_equal(ses.image(), plain.image())
+            # the same with a host image between the device image and the photons
+            want = ses.image()
+            img = ses.image_tensor(stream=side.cuda_stream)
+            host = ses.image()
+            ses.add_photons(n)
+            side.synchronize()
+            plain.add_photons(n)
+            assert np.array_equal(host, want) and np.array_equal(img.cpu().numpy(), want)
+            assert ses.photons_done == 3 * n and not np.array_equal(ses.image(), want)
+            assert np.array_equal(ses.hitpoints(), plain.hitpoints()) and np.array_equal(ses.image(), plain.image())
+
+
 def test_session_edge_cases(gpu_ready):
     import cgraytracing_amd as cg
     from cgraytracing_amd._capi import CgrtError

@@ -114,6 +114,28 @@ def test_torch_preallocated_and_host_forms_agree(scene, n):
     assert fresh["hp_count"] == (n if n else 0) and fresh["levels"] == (1 if n else 0)  # C1 is diffuse: one Hitpoint a ray
 
 
+def test_hitpoint_getters_with_less_room_than_records(gpu_ready):
+    """cgrt_ppm_session_hitpoints / cgrt_sppm_session_last_hitpoints given room for fewer records than the table holds: the first
+    `cap` rows of the full dump, nothing written behind them, and the full count.  32 x 24, spp 2, four batches a call."""
+    import ctypes as C
+    import cgraytracing_amd as cg
+    from cgraytracing_amd._capi import check
+    with cg.Scene(scenes.scene_c2()) as sc:
+        ppm = sc.ppm_session(32, 24, 2, scenes.cam_dof(), nphotons=3000, batch=800)
+        sppm = sc.sppm_session(32, 24, 2, scenes.cam_dof(), initial_radius=2.0, batch=800).add_passes(1, 3000)
+        for ses in (ppm, sppm):
+            full = ses._hitpoint_dump()
+            n = len(full)
+            assert n == ses.info()["hp_count"] > 2 * 32 * 24 and full[:, 11:14].any()
+            for cap in (0, 1, n // 2 + 1, n - 1, n + 5):
+                part = np.full((cap + 2, 16), 7.0)
+                count = C.c_uint64(0)
+                check(ses._fn(ses._HITPOINTS)(ses._h, part.ctypes.data if cap else None, cap, C.byref(count)))
+                m = min(cap, n)
+                assert count.value == n, cap
+                assert np.array_equal(part[:m].view(np.uint64), full[:m].view(np.uint64)) and (part[m:] == 7.0).all(), cap
+
+
 def test_sessions_share_their_image_getters_and_their_end(gpu_ready):
     import torch
     import cgraytracing_amd as cg

@@ -330,6 +330,42 @@ def test_bounded_memory_and_monotonic_state(gpu_ready):
         assert (px[7][:, 1] < px[1][:, 1]).sum() >= W * H // 2
 
 
+def test_device_image_then_pass_at_once(gpu_ready):
+    """An image on a caller's stream is still reading the texels when the next pass comes: the pass waits for it.  The image is
+    the host image of that pass count bit for bit, and the pass after it leaves the texels and Hitpoints of a session that took
+    no image.  32 x 24, four batches a pass."""
+    import cgraytracing_amd as cg
+    import torch
+    w, h, n = 32, 24, 3000
+    kw = dict(initial_radius=R0, batch=800)
+    with cg.Scene(scenes.scene_c2()) as sc:
+        dev = torch.device("cuda", sc.device)
+        side = torch.cuda.Stream(dev)
+        with sc.sppm_session(w, h, SPP, scenes.cam_dof(), **kw) as plain, sc.sppm_session(w, h, SPP, scenes.cam_dof(), **kw) as ses:
+            ses.add_passes(1, n)
+            want, want_rgb = ses.image(), ses.rgb8()
+            rgb = torch.full((h, w, 3), 7, dtype=torch.uint8, device=dev)
+            img = ses.image_tensor(rgb8_out=rgb, stream=side.cuda_stream)
+            ses.add_passes(1, n)
+            side.synchronize()
+            plain.add_passes(2, n)
+            assert want.max() > 0 and _same(img.cpu().numpy(), want) and np.array_equal(rgb.cpu().numpy(), want_rgb)
+            assert ses.passes == 2 and not _same(ses.image(), want)
+            assert _same(ses.pixels(), plain.pixels()) and _same(ses.last_hitpoints(), plain.last_hitpoints())
+            # the same with a host image between the two, while the caller's stream is still busy with work of its own in
+            # front of the device image: the pass comes behind both images
+            want = ses.image()
+            with torch.cuda.stream(side):
+                torch.cuda._sleep(20000000)
+            img = ses.image_tensor(stream=side.cuda_stream)
+            host = ses.image()
+            ses.add_passes(1, n)
+            side.synchronize()
+            plain.add_passes(1, n)
+            assert _same(host, want) and _same(img.cpu().numpy(), want) and not _same(ses.image(), want)
+            assert ses.passes == 3 and _same(ses.pixels(), plain.pixels()) and _same(ses.last_hitpoints(), plain.last_hitpoints())
+
+
 def test_example_sppm_dof(gpu_ready, tmp_path):
     import os
     import sys
