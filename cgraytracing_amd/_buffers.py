@@ -8,7 +8,8 @@ speak of.  The torch name is spelled as the error message spells it ("int64" or 
 callers may match on); a tuple of names accepts any of them and reports the first.
 
 A result table is {name: (rows, cols, dtype pair, numpy fill)}: rows "n", "2n" or "cap" -- or a (torch, numpy) pair of those
-where the two forms differ ("max(n,1)") --, cols None for a vector."""
+where the two forms differ ("max(n,1)") --, cols None for a vector.  rows "frame": one entry, or one row of `cols`, per pixel of
+a frame whose (rows, width) is given as `frame` (the grid AOVs, aov.py)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -21,10 +22,10 @@ F64, I32, I64, U8 = ("float64", "float64"), ("int32", "int32"), ("int64", "int64
 U32, U64 = ("int32", "uint32"), ("int64", "uint64")  # bit patterns of unsigned values in signed tensors
 
 
-def _shape(row, form, n, cap):
+def _shape(row, form, n, cap, frame=None):
     rows, cols = row[0] if isinstance(row[0], str) else row[0][form], row[1]
-    m = {"n": n, "2n": 2 * n, "cap": cap, "max(n,1)": max(n, 1)}[rows]
-    return (m,) if cols is None else (m, cols)
+    lead = tuple(frame) if rows == "frame" else ({"n": n, "2n": 2 * n, "cap": cap, "max(n,1)": max(n, 1)}[rows],)
+    return lead if cols is None else lead + (cols,)
 
 
 def _differ(what, names):
@@ -72,11 +73,11 @@ class Torch:
             raise ValueError("%s: tris must be a contiguous float64 [n,9] or [n,3,3] tensor on %s" % (what, self.dev))
         return t.shape[0], t
 
-    def results(self, what, spec, names, out, n, cap=0):
+    def results(self, what, spec, names, out, n, cap=0, frame=None):
         """{name: the caller's out[name], validated, or a fresh tensor} for `names` of the table `spec`."""
         res = {}
         for name in names:
-            shape, dtype = _shape(spec[name], 0, n, cap), getattr(self.torch, spec[name][2][0])
+            shape, dtype = _shape(spec[name], 0, n, cap, frame), getattr(self.torch, spec[name][2][0])
             t = out.get(name) if out else None
             if t is None:
                 t = self.torch.empty(shape, dtype=dtype, device=self.dev)
@@ -135,9 +136,9 @@ class Numpy:
             raise ValueError("%s: tris must be an [n,9] or [n,3,3] array" % what)
         return t.size // 9, t
 
-    def results(self, what, spec, names, out, n, cap=0):
+    def results(self, what, spec, names, out, n, cap=0, frame=None):
         make = lambda shape, dtype, fill: np.full(shape, fill, dtype) if fill else np.zeros(shape, dtype)
-        return {k: make(_shape(spec[k], 1, n, cap), spec[k][2][1], spec[k][3]) for k in names}
+        return {k: make(_shape(spec[k], 1, n, cap, frame), spec[k][2][1], spec[k][3]) for k in names}
 
     def counters(self, what, counters=None):
         return np.zeros((CGRT_NCOUNTERS,), np.uint64)

@@ -133,6 +133,11 @@ class HitAttributes(C.Structure):
     _fields_ = [("prim", C.c_void_p), ("uv2", C.c_void_p), ("color3", C.c_void_p), ("material2", C.c_void_p)]
 
 
+class GridAov(C.Structure):
+    _fields_ = [("albedo3", C.c_void_p), ("normal3", C.c_void_p), ("depth", C.c_void_p), ("hits", C.c_void_p),
+                ("obj_id", C.c_void_p)]  # 40 bytes
+
+
 class Occlusion(C.Structure):
     _fields_ = [("tmax", C.c_void_p), ("occluded", C.c_void_p)]
 
@@ -304,6 +309,9 @@ SIGNATURES = {
     "cgrt_scene_last_wavefront_rays": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cgrt_camera_rays": (C.c_int, [C.POINTER(Camera), C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cgrt_camera_rays_host": (C.c_int, [C.POINTER(Camera), C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cgrt_trace_grid_aov": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Grid), C.POINTER(GridAov), C.c_void_p, C.c_void_p]),
+    "cgrt_trace_grid_aov_host": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Grid), C.POINTER(GridAov), C.c_void_p]),
+    "cgrt_trace_grid_aov_variant": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(Grid), C.c_char_p, C.c_size_t]),
     "cgrt_intersect_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "cgrt_math_probe": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -1294,6 +1294,8 @@ static int hitpoints_device(const cgrt_scene *s, const cgrt_camera *cam, const c
 // caller-supplied rays: the ray-list kernels' table, launch path, checks and entry points
 #include "cgrt_rays_plan.h"
 #include "cgrt_ray_queries.hpp"
+// grid AOVs: the first-hit feature buffers of a frame (kernel, plan, entry points)
+#include "cgrt_aov.hpp"
 
 extern "C" {
 

@@ -789,6 +789,52 @@ int cgrt_camera_rays(const cgrt_camera *cam, const cgrt_grid *grid, double *org3
 /* The same bits evaluated on the HOST into host buffers; needs no GPU (like cgrt_lens_samples). */
 int cgrt_camera_rays_host(const cgrt_camera *cam, const cgrt_grid *grid, double *org3, double *dir3, uint64_t *keys);
 
+/* ---- grid AOVs: a frame's feature buffers -- albedo, shading normal, depth, coverage and object id of the first hit ------
+ * What a denoiser, a compositor, a picker or a debug view asks of a frame, by one launch over the grid: the pixel is the lane,
+ * no ray is written to memory.  It is the composition cgrt_camera_rays -> cgrt_trace_rays (nearest-hit query) ->
+ * cgrt_ray_hit_attributes folded per pixel, bit for bit:
+ *   rays    for the pixel at local row j, column w and k in [0, spp): the ray, key included, that cgrt_camera_rays writes at
+ *           index (k * rows + j) * width + w -- pinhole or thin lens, the built-in or a posed camera (CGRT_GRID_POSED),
+ *           contiguous or striped rows;
+ *   hit     (id_k, t_k, n_k) = the nearest-hit query's hit_obj, hit_t and hit_normal3 for that ray and key; on an opaque mesh
+ *           n_k as the pruned scene walk gives it (CGRT_RAYS_NO_SIGN_PASS), since the flip below does not depend on its sign.
+ *           A hit contributes c_k = cgrt_ray_hit_attributes' color3 at P = org + dir * t_k, m_k = n_k turned against the ray
+ *           (main.cpp:73-76: dot(n, dir) > 0 ? -n : n) and t_k itself; a miss contributes nothing;
+ *   sums    in fp64 from +0.0, in the order k = 0, 1, ...;
+ *   albedo3, normal3, depth   (float)(sum * (1 / spp_total)); with CGRT_GRID_ACCUMULATE added to the destination in fp32,
+ *           exactly as cgrt_trace_grid stores rgb.  normal3 is a mean of unit vectors, not a unit vector;
+ *   hits    the samples that hit; added to under CGRT_GRID_ACCUMULATE, else overwritten.  The mean depth over the hits is
+ *           depth * spp_total / hits;
+ *   obj_id  id_0, the object sample `sample_offset` hits, or -1; every call overwrites it;
+ *   rows of a striped grid beyond `height` get zeros and -1; under CGRT_GRID_ACCUMULATE they are left untouched.
+ * max_depth is not looked at (0 is as good as 5).  Of the flags only CGRT_GRID_ACCUMULATE and CGRT_GRID_POSED are honoured:
+ * every other one is "same image either way" by its own contract and is ignored, CGRT_GRID_STATS too.
+ * counters: CGRT_CNT_RAYS is added to by the rays traced (spp per pixel of the image) and CGRT_CNT_WAVE_ITERS by the waves'
+ * iterations; CGRT_CNT_HITPOINTS and the rest are untouched.
+ * Errors: the argument checks are cgrt_trace_grid's (max_depth apart); a null scene, cam, grid or out and an uncommitted scene
+ * give CGRT_ERR_INVALID; everything is refused before a device is touched.  With every pointer of `out` NULL the call is
+ * CGRT_OK and launches nothing.
+ * A launch on the scene handle (Threading above).  It leaves the handle's cached tile order, cost probe and lens table and
+ * every cgrt_scene_last_* record as they were. */
+typedef struct cgrt_grid_aov {   /* every pointer may be NULL: only the arrays asked for are written */
+    float    *albedo3;  /* [rows][width][3] */
+    float    *normal3;  /* [rows][width][3] */
+    float    *depth;    /* [rows][width]    */
+    uint32_t *hits;     /* [rows][width]    */
+    int32_t  *obj_id;   /* [rows][width]    */
+} cgrt_grid_aov;        /* 40 bytes */
+/* DEVICE pointers on the scene's device; asynchronous on `stream`. */
+int cgrt_trace_grid_aov(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, const cgrt_grid_aov *out,
+                        uint64_t *counters, void *stream);
+/* HOST pointers: allocates device buffers, runs, synchronises and copies back, like cgrt_trace_grid_host (counters are
+ * overwritten, not added to).  The device buffers are the call's own, so CGRT_GRID_ACCUMULATE has nothing to add to and is
+ * ignored: the arrays are overwritten. */
+int cgrt_trace_grid_aov_host(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, const cgrt_grid_aov *out,
+                             uint64_t *counters);
+/* The kernel instantiation cgrt_trace_grid_aov launches for (scene, cam, grid), e.g.
+ * "aov_grid_kernel<TREES=0,BEZ=0,SPH=1,SPILL=0,NT=256>": the row the nearest-hit query of the same scene runs. */
+int cgrt_trace_grid_aov_variant(const cgrt_scene *s, const cgrt_camera *cam, const cgrt_grid *grid, char *name, size_t cap);
+
 /* Row e of SURVEY.md section 8: the un-permute that follows the framebuffer gather.  shares = n_present buffers
  * [rows_local][width][channels] float, share-major (share r's local row j is global row ((j / stripe_rows) * nshares + r) *
  * stripe_rows + j % stripe_rows, as in cgrt_grid); frame = [height][width][channels].  Rows of shares >= n_present are

@@ -391,6 +391,44 @@ inline void render(const std::vector<Object *> &objs, const RenderParams &rp, st
     }
 }
 
+// The frame's feature buffers (cgrt_trace_grid_aov_host): per pixel of render()'s frame, row 0 = bottom, the first hit's albedo
+// and normal (turned against the ray) averaged over the samples, the summed hit distance / num_of_samples, the samples that hit
+// and the object -- its position in objs -- the first sample hits, or -1.  What a denoiser, a compositor or a picker asks for.
+struct GridAov {
+    std::vector<float> albedo, normal;  // 3 per pixel
+    std::vector<float> depth;           // mean depth over the hits: depth * num_of_samples / hits
+    std::vector<uint32_t> hits;
+    std::vector<int32_t> obj_id;
+};
+inline void render_aov(cgrt_scene *scene, const RenderParams &rp, GridAov &aov, RenderStats *stats) {
+    cgrt_grid g{};
+    cgrt_posed_camera pc;
+    const cgrt_camera *cam = rp.camera(pc, g);
+    g.width = rp.width;
+    g.height = rp.height;
+    g.rows = rp.height;
+    g.stripe_nranks = 1;
+    g.spp = rp.num_of_samples;
+    g.spp_total = rp.num_of_samples;
+    g.seed = rp.seed;
+    const size_t npx = (size_t)rp.width * rp.height;
+    aov.albedo.assign(npx * 3, 0.f);
+    aov.normal.assign(npx * 3, 0.f);
+    aov.depth.assign(npx, 0.f);
+    aov.hits.assign(npx, 0u);
+    aov.obj_id.assign(npx, -1);
+    const cgrt_grid_aov out = {aov.albedo.data(), aov.normal.data(), aov.depth.data(), aov.hits.data(), aov.obj_id.data()};
+    uint64_t cnt[CGRT_NCOUNTERS] = {0};
+    check(cgrt_trace_grid_aov_host(scene, cam, &g, &out, cnt));
+    if (stats) stats->rays = cnt[CGRT_CNT_RAYS];
+}
+inline void render_aov(const std::vector<Object *> &objs, const RenderParams &rp, GridAov &aov, RenderStats *stats = nullptr) {
+    SceneBuilder sb;
+    for (const Object *o : objs) o->add_to(sb);
+    check(cgrt_scene_commit(sb.scene, rp.device));
+    render_aov(sb.scene, rp, aov, stats);
+}
+
 // trace() for rays of the caller's own (cgrt_trace_rays_host): acc[i] = the sum of hp.f over ray i's Hitpoints (three doubles, not
 // divided by anything), nhit[i] their number; dir is used as given (unit length is the caller's contract).  A look-at camera,
 // a fisheye or a light probe is a ray list away.
@@ -892,6 +930,8 @@ class DeformingScene {
             stats->hitpoints = cnt[CGRT_CNT_HITPOINTS];
         }
     }
+    // render_aov()'s feature buffers of the scene as it stands
+    void render_aov(const RenderParams &rp, GridAov &aov, RenderStats *stats = nullptr) const { cgrt_host::render_aov(sb_.scene, rp, aov, stats); }
 
   private:
     SceneBuilder sb_;

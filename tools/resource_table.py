@@ -86,6 +86,10 @@ def demangle_variant(name):
     if m:
         t = [int(x) for x in m.groups()]
         return "wavefront_step_kernel<TREES=%d,BEZ=%d,SPH=%d,STATS=%d,SPILL=%d,NT=%d>" % tuple(t)
+    m = re.match(r"_Z15aov_grid_kernelIL?b(\d)EL?b(\d)EL?b(\d)EL?b(\d)ELi(\d+)EE", name)
+    if m:
+        t = [int(x) for x in m.groups()]
+        return "aov_grid_kernel<TREES=%d,BEZ=%d,SPH=%d,SPILL=%d,NT=%d>" % tuple(t)
     m = re.search(r"19photon_trace_kernelILb(\d)ELb(\d)ELb(\d)EE", name)
     if m:
         return "photon_trace_kernel<BEZ=%s,SPILL=%s,RAYS=%s>" % m.groups()
