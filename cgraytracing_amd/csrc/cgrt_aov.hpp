@@ -50,15 +50,9 @@ __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) voi
     unsigned long long *wc = wg_counters_begin(wg_cnt, counters);
 
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    const WgLds lay = wg_lds(wg_ask_trace(NT, TREES, BEZ, false, SPILL, false), sc);  // aov_ask's, cgrt_aov_plan.h
-    const WgLdsPtrs lds = wg_lds_carve(lay, lds_raw);
+    const WgLdsPtrs lds = ray_wg_begin<NT, TREES, BEZ, false, SPILL>(sc, lds_raw);  // aov_ask's layout, cgrt_aov_plan.h
     ObjRec *const lobjs = lds.lobjs;
     const LdsAux aux = lds.aux;
-    if (lay.has.nodes)
-        wg_stage16<NT>(const_cast<NodeRec *>(aux.lnodes), sc.nodes + sc.trees[sc.cached_tree].node_begin,
-                       sc.cached_nodes * (int)(sizeof(NodeRec) / 16));
-    wg_stage16<NT>(lobjs, sc.objs, sc.n_lds * (int)(sizeof(ObjRec) / 16));
-    __syncthreads();
 
     // the lane's pixel: wave tile (wx, wy), lane & 15 across and lane >> 4 down, as set_pixel of trace_grid_body
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -132,15 +126,7 @@ __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) voi
         }
     }
 
-    if (wc) {
-        // wave reduction, then one LDS atomic per wave and counter; the workgroup adds its sums once (wg_counters_end)
-        unsigned long long rr = my_rays;
-        for (int off = 32; off > 0; off >>= 1) rr += __shfl_xor(rr, off);
-        if (lane == 0 && (rr | (unsigned long long)wave_iters) != 0ull) {
-            atomicAdd(&wc[CGRT_CNT_RAYS], rr);
-            atomicAdd(&wc[CGRT_CNT_WAVE_ITERS], (unsigned long long)wave_iters);
-        }
-    }
+    ray_counters_flush</*STATS*/ false, /*HITS*/ false>(wc, lane, my_rays, 0u, my_nodes, my_tris, wave_iters);
     wg_counters_end(wg_cnt, counters);
 }
 

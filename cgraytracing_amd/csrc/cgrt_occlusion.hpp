@@ -9,11 +9,7 @@
 
 // Kernel arguments of occlusion_rays_kernel (cgrt_rays / cgrt_occlusion of cgrt.h)
 struct OccParams {
-    long long n;
-    const double *org, *dir;
-    const unsigned long long *keys;  // nullptr: sample_key(pixel_key(seed, first_index + i), 0)
-    long long first_index;
-    uint64_t seed;
+    RayInput in;
     const double *tmax;  // nullptr: kInf for every ray
     uint8_t *occluded;
     unsigned int *queue;  // head of the block queue (block = 64 consecutive rays), zeroed before the launch
@@ -399,25 +395,20 @@ __device__ __forceinline__ bool occluded_scene(const ObjRec *__restrict__ objs, 
 template <bool TREES, bool BEZ, bool SPH, bool STATS, bool SPILL, int NT>
 __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) void occlusion_rays_kernel(DeviceScene sc, OccParams rp,
                                                                                                     unsigned long long *__restrict__ counters) {
-    static_assert(NT == 256 || NT == 64, "workgroup = 4 waves or 1 wave");
     __shared__ unsigned long long wg_cnt[CGRT_NCOUNTERS];
     unsigned long long *wc = wg_counters_begin(wg_cnt, counters);
 
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    const WgLds lay = wg_lds(wg_ask_trace(NT, TREES, BEZ, false, SPILL, false), sc);
-    const WgLdsPtrs lds = wg_lds_carve(lay, lds_raw);
+    const WgLdsPtrs lds = ray_wg_begin<NT, TREES, BEZ, false, SPILL>(sc, lds_raw);
     ObjRec *const lobjs = lds.lobjs;
     const LdsAux aux = lds.aux;
-    if (lay.has.nodes)
-        wg_stage16<NT>(const_cast<NodeRec *>(aux.lnodes), sc.nodes + sc.trees[sc.cached_tree].node_begin,
-                       sc.cached_nodes * (int)(sizeof(NodeRec) / 16));
-    wg_stage16<NT>(lobjs, sc.objs, sc.n_lds * (int)(sizeof(ObjRec) / 16));
-    __syncthreads();
 
     const int lane = threadIdx.x & 63;
-    const unsigned n_blocks = (unsigned)((rp.n + 63) >> 6);
+    const unsigned n_blocks = (unsigned)((rp.in.n + 63) >> 6);
     const bool skip = rp.skip_transparent != 0;
     uint32_t my_rays = 0, my_nodes = 0, my_tris = 0, wave_iters = 0;
+    // Lane k takes ray k of a block, so of RayBlocks (cgrt_ray_wave.hpp) only the fetch-ahead is left, and a wave that finds the
+    // queue empty asks for nothing more: written out
     unsigned block_ahead = 0;
     if (lane == 0) block_ahead = atomicAdd(rp.queue, 1u);
     while (true) {
@@ -425,20 +416,20 @@ __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) voi
         if (blk >= n_blocks) break;
         if (lane == 0) block_ahead = atomicAdd(rp.queue, 1u);
         const long long u = ((long long)blk << 6) + lane;
-        const bool in = u < rp.n;
+        const bool in = u < rp.in.n;
         V3 o = mk(0, 0, 0), d = mk(0, 0, 0);
         double tmax = kInf;
         uint64_t key = 0;
         if (in) {
-            o = ld3(rp.org + 3 * u);
-            d = ld3(rp.dir + 3 * u);
+            o = ld3(rp.in.org + 3 * u);
+            d = ld3(rp.in.dir + 3 * u);
             if (rp.tmax) tmax = rp.tmax[u];
         }
-        const bool ray = in && !(d.x == 0.0 && d.y == 0.0 && d.z == 0.0);  // dir == 0: not a ray, nothing counted
+        const bool ray = in && !ray_is_none(d);  // nothing counted
         // A NaN tmax admits nothing and is answered without a walk.  tmax <= 0 is walked: Sphere::intersect and the Bezier cap
         // can return a length below zero (a ray that starts on a sphere's surface within rounding), which the query keeps
         const bool on = ray && tmax == tmax;
-        if (BEZ && on) key = rp.keys ? (uint64_t)rp.keys[u] : sample_key(pixel_key(rp.seed, (uint64_t)(rp.first_index + u)), 0);
+        if (BEZ && on) key = ray_default_key(rp.in, u);
         tmax = fmin(tmax, kInf);
         if (ray) my_rays++;
         bool occ = false;
@@ -450,24 +441,7 @@ __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) voi
         if (in) rp.occluded[u] = occ ? (uint8_t)1 : (uint8_t)0;
     }
 
-    if (wc) {
-        unsigned long long rr = my_rays, nn = my_nodes, tt = my_tris;
-        for (int off = 32; off > 0; off >>= 1) {
-            rr += __shfl_xor(rr, off);
-            if (STATS) {
-                nn += __shfl_xor(nn, off);
-                tt += __shfl_xor(tt, off);
-            }
-        }
-        if (lane == 0 && (rr | (unsigned long long)wave_iters) != 0ull) {
-            atomicAdd(&wc[CGRT_CNT_RAYS], rr);
-            atomicAdd(&wc[CGRT_CNT_WAVE_ITERS], (unsigned long long)wave_iters);
-            if (STATS) {
-                atomicAdd(&wc[CGRT_CNT_NODE_TESTS], nn);
-                atomicAdd(&wc[CGRT_CNT_TRI_TESTS], tt);
-            }
-        }
-    }
+    ray_counters_flush<STATS, false>(wc, lane, my_rays, 0u, my_nodes, my_tris, wave_iters);
     wg_counters_end(wg_cnt, counters);
 }
 

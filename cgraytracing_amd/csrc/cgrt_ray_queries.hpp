@@ -66,23 +66,18 @@ static int ray_queue(const cgrt_scene *s, size_t tail, hipStream_t st, unsigned 
     *queue = reinterpret_cast<unsigned int *>(s->scratch.p);
     return CGRT_OK;
 }
-// what RayParams, OccParams, BounceParams and WavefrontParams all read of a ray list
-template <class P>
-static void fill_ray_inputs(P &p, const cgrt_rays *r, unsigned int *queue) {
-    p.n = r->n;
-    p.org = r->org3;
-    p.dir = r->dir3;
-    p.keys = reinterpret_cast<const unsigned long long *>(r->keys);
-    p.first_index = r->first_index;
-    p.seed = r->seed;
-    p.queue = queue;
+static void fill_ray_inputs(RayInput &in, const cgrt_rays *r) {
+    in.n = r->n;
+    in.org = r->org3;
+    in.dir = r->dir3;
+    in.keys = reinterpret_cast<const unsigned long long *>(r->keys);
+    in.first_index = r->first_index;
+    in.seed = r->seed;
 }
 template <class... P>
 static int launch_rays(const cgrt_scene *s, const RaysLaunch &L, void (*fn)(DeviceScene, P...), hipStream_t st, typename same_type<P>::type... args) {
     return launch_checked(fn, L.plan.what(), s->device, dim3((unsigned)L.plan.wgs), dim3((unsigned)L.plan.k.nt), L.plan.lds, st, L.dev, args...);
 }
-
-static constexpr long long kMaxRays = 1ll << 36;  // blocks of 64 rays are numbered in 32 bits with room for the waves' last draws
 
 // A ray list and the scene it meets.  own_ok: the entry point's other pointers; own_null: what to say of an output it cannot
 // do without.  traced: the rays are traced, so max_depth counts (where `depth`) and the scene must be committed, both looked at
@@ -164,7 +159,8 @@ static int ray_hitpoints_device(const cgrt_scene *s, const cgrt_rays *rays, cons
     unsigned int *queue = nullptr;
     if ((rc = ray_queue(s, 0, 0, &queue))) return rc;
     RayParams rp{};
-    fill_ray_inputs(rp, rays, queue);
+    fill_ray_inputs(rp.in, rays);
+    rp.queue = queue;
     rp.max_depth = rays->max_depth;
     const RaySink sink{b_rec.as<double>(), b_cnt.as<unsigned long long>(), (unsigned long long)cap,
                        reinterpret_cast<const long long *>(pixel)};
@@ -261,20 +257,20 @@ static int wavefront_levels(const cgrt_scene *s, const cgrt_rays *rays, const cg
         int rc = rays_launch(s, &lr, RaysKind::Wavefront, L);
         if (rc) return rc;
         WavefrontParams wp{};
-        wp.n = n_in;
+        wp.in.n = n_in;
         wp.queue = queue;
-        wp.seed = rays->seed;
+        wp.in.seed = rays->seed;
         if (level == 1) {  // the caller's arrays
-            wp.org = rays->org3 + 3 * b;
-            wp.dir = rays->dir3 + 3 * b;
-            wp.keys = rays->keys ? reinterpret_cast<const unsigned long long *>(rays->keys) + b : nullptr;
-            wp.first_index = rays->first_index + b;
+            wp.in.org = rays->org3 + 3 * b;
+            wp.in.dir = rays->dir3 + 3 * b;
+            wp.in.keys = rays->keys ? reinterpret_cast<const unsigned long long *>(rays->keys) + b : nullptr;
+            wp.in.first_index = rays->first_index + b;
         } else {
             const WavefrontQueue &in = mem.q[level & 1];
-            wp.org = in.org;
-            wp.dir = in.dir;
+            wp.in.org = in.org;
+            wp.in.dir = in.dir;
             wp.adj = in.adj;
-            wp.keys = in.key;
+            wp.in.keys = in.key;
             wp.path = in.path;
             wp.root = in.root;
         }
@@ -413,7 +409,8 @@ int cgrt_trace_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_ray_r
     unsigned int *queue = nullptr;
     if ((rc = ray_queue(s, own_obj, st, &queue))) return rc;
     RayParams rp{};
-    fill_ray_inputs(rp, rays, queue);
+    fill_ray_inputs(rp.in, rays);
+    rp.queue = queue;
     rp.max_depth = rays->max_depth;
     rp.acc = out->acc3;
     rp.nhit = out->nhit;
@@ -471,7 +468,8 @@ int cgrt_occlusion_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_o
     unsigned int *queue = nullptr;
     if ((rc = ray_queue(s, 0, st, &queue))) return rc;
     OccParams rp{};
-    fill_ray_inputs(rp, rays, queue);
+    fill_ray_inputs(rp.in, rays);
+    rp.queue = queue;
     rp.tmax = occ->tmax;
     rp.occluded = occ->occluded;
     rp.skip_transparent = (rays->flags & CGRT_RAYS_SKIP_TRANSPARENT) != 0;
@@ -518,7 +516,8 @@ int cgrt_bounce_rays(const cgrt_scene *s, const cgrt_rays *rays, const cgrt_boun
     unsigned int *queue = nullptr;
     if ((rc = ray_queue(s, 0, st, &queue))) return rc;
     BounceParams bp{};
-    fill_ray_inputs(bp, rays, queue);
+    fill_ray_inputs(bp.in, rays);
+    bp.queue = queue;
     bp.adj = b->adj3;
     bp.path = b->path;
     bp.step = b->step;

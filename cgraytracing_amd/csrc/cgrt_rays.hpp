@@ -3,14 +3,11 @@
 #ifndef CGRT_RAYS_HPP
 #define CGRT_RAYS_HPP
 #include "cgrt_eye.hpp"
+#include "cgrt_ray_wave.hpp"
 
 // Kernel arguments of trace_rays_kernel (cgrt_rays / cgrt_ray_results of cgrt.h; every output pointer may be nullptr)
 struct RayParams {
-    long long n;
-    const double *org, *dir;
-    const unsigned long long *keys;  // nullptr: sample_key(pixel_key(seed, first_index + i), 0)
-    long long first_index;
-    uint64_t seed;
+    RayInput in;
     int32_t max_depth, pad_;
     double *acc;
     uint32_t *nhit;
@@ -125,27 +122,21 @@ __device__ __forceinline__ RayStep shade_step(const DeviceScene &sc, const ObjRe
 // Dynamic LDS: wg_ask_trace's layout (cgrt_wg_lds.h), as the eye pass.
 template <bool TREES, bool BEZ, bool GLASS, bool SPH, bool STATS, bool SPILL, bool FIRST, int NT, bool CAPTURE>
 __device__ __forceinline__ void trace_rays_body(const DeviceScene &sc, const RayParams &rp, unsigned long long *wc, const RaySink &sink) {
-    static_assert(NT == 256 || NT == 64, "workgroup = 4 waves or 1 wave");
     static_assert(!(FIRST && GLASS), "a nearest-hit query has no pending rays");
     static_assert(!(CAPTURE && (FIRST || STATS)), "Hitpoints come from the full trace; the capture counts nothing");
     constexpr size_t level_bytes = pending_level_bytes(NT);
 
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    const WgLds lay = wg_lds(wg_ask_trace(NT, TREES, BEZ, GLASS, SPILL, false), sc);
-    const WgLdsPtrs lds = wg_lds_carve(lay, lds_raw);
+    const WgLdsPtrs lds = ray_wg_begin<NT, TREES, BEZ, GLASS, SPILL>(sc, lds_raw);
     ObjRec *const lobjs = lds.lobjs;
     const LdsAux aux = lds.aux;
-    if (lay.has.nodes)
-        wg_stage16<NT>(const_cast<NodeRec *>(aux.lnodes), sc.nodes + sc.trees[sc.cached_tree].node_begin,
-                       sc.cached_nodes * (int)(sizeof(NodeRec) / 16));
-    wg_stage16<NT>(lobjs, sc.objs, sc.n_lds * (int)(sizeof(ObjRec) / 16));
-    __syncthreads();
 
     const int lane = threadIdx.x & 63;
     const unsigned long long lanes_below = (1ull << lane) - 1ull;
-    const unsigned n_blocks = (unsigned)((rp.n + 63) >> 6);
+    const unsigned n_blocks = (unsigned)((rp.in.n + 63) >> 6);
 
-    // the wave's block: rays [ray_next, ray_end) are still to be handed out (wave-uniform)
+    // RayBlocks (cgrt_ray_wave.hpp) written out: through the struct a nearest-hit variant's occupancy moved.
+    // The wave's block: rays [ray_next, ray_end) are still to be handed out (wave-uniform)
     long long ray_next = 0, ray_end = 0;
     bool queue_empty = false;
     unsigned block_ahead = 0;
@@ -178,12 +169,7 @@ __device__ __forceinline__ void trace_rays_body(const DeviceScene &sc, const Ray
         const unsigned long long m = __ballot(want);
         if (m != 0ull) {
             if (!FIRST && want && open) {  // the finished ray's sums
-                if (rp.acc) {
-                    double *q = rp.acc + 3 * my_ray;
-                    q[0] = acc_r;
-                    q[1] = acc_g;
-                    q[2] = acc_b;
-                }
+                if (rp.acc) st3(rp.acc + 3 * my_ray, mk(acc_r, acc_g, acc_b));
                 if (rp.nhit) rp.nhit[my_ray] = ray_hits;
                 open = false;
             }
@@ -195,36 +181,26 @@ __device__ __forceinline__ void trace_rays_body(const DeviceScene &sc, const Ray
                     queue_empty = true;
                 } else {
                     ray_next = (long long)blk << 6;
-                    ray_end = ray_next + 64 < rp.n ? ray_next + 64 : rp.n;
+                    ray_end = ray_next + 64 < rp.in.n ? ray_next + 64 : rp.in.n;
                 }
             }
             const long long u = ray_next + (long long)__popcll(m & lanes_below);
             ray_next += (long long)__popcll(m);  // lanes that drew beyond ray_end draw again from the next block
             if (want && u < ray_end) {
-                r.o = ld3(rp.org + 3 * u);
-                r.d = ld3(rp.dir + 3 * u);
-                bool skip = r.d.x == 0.0 && r.d.y == 0.0 && r.d.z == 0.0;
+                r.o = ld3(rp.in.org + 3 * u);
+                r.d = ld3(rp.in.dir + 3 * u);
+                bool skip = ray_is_none(r.d);
                 if (CAPTURE && sink.pixel) skip = skip || sink.pixel[u] < 0;
                 if (skip) {
                     // not a ray (cgrt_camera_rays' padding rows; a ray without a texel): the results of a miss, nothing counted
-                    if (!FIRST && rp.acc) {
-                        double *q = rp.acc + 3 * u;
-                        q[0] = 0.0;
-                        q[1] = 0.0;
-                        q[2] = 0.0;
-                    }
+                    if (!FIRST && rp.acc) st3(rp.acc + 3 * u, mk(0, 0, 0));
                     if (!FIRST && rp.nhit) rp.nhit[u] = 0u;
                     if (rp.hit_obj) rp.hit_obj[u] = -1;
                     if (rp.hit_t) rp.hit_t[u] = 0.0;
-                    if (rp.hit_normal) {
-                        double *q = rp.hit_normal + 3 * u;
-                        q[0] = 0.0;
-                        q[1] = 0.0;
-                        q[2] = 0.0;
-                    }
+                    if (rp.hit_normal) st3(rp.hit_normal + 3 * u, mk(0, 0, 0));
                 } else {
                     my_ray = u;
-                    key = rp.keys ? (uint64_t)rp.keys[u] : sample_key(pixel_key(rp.seed, (uint64_t)(rp.first_index + u)), 0);
+                    key = ray_default_key(rp.in, u);
                     r.adj = mk(1, 1, 1);
                     r.depth_left = rp.max_depth;
                     r.path = 1;
@@ -238,7 +214,7 @@ __device__ __forceinline__ void trace_rays_body(const DeviceScene &sc, const Ray
         }
         if (__ballot(have) == 0ull) {
             if (queue_empty && ray_next >= ray_end) break;  // nothing left anywhere
-            continue;                                       // drew nothing traceable (block boundary, padding rays)
+            continue;  // drew nothing traceable (block boundary, padding rays)
         }
         wave_iters++;
         // All 64 lanes enter the scene walk together (lanes without a ray carry on == false)
@@ -253,7 +229,7 @@ __device__ __forceinline__ void trace_rays_body(const DeviceScene &sc, const Ray
                 const bool is_hit = hit.id >= 0;
                 if (rp.hit_obj) rp.hit_obj[my_ray] = is_hit ? hit.id : -1;
                 if (rp.hit_t) rp.hit_t[my_ray] = is_hit ? hit.t : 0.0;
-                if (rp.hit_normal) {
+                if (rp.hit_normal) {  // (not st3 of a selected V3: DESIGN.md section 4.21)
                     double *q = rp.hit_normal + 3 * my_ray;
                     q[0] = is_hit ? hit.n.x : 0.0;
                     q[1] = is_hit ? hit.n.y : 0.0;
@@ -346,27 +322,7 @@ __device__ __forceinline__ void trace_rays_body(const DeviceScene &sc, const Ray
         }
     }  // ray loop
 
-    if (wc) {
-        // wave reduction, then one LDS atomic per wave and counter; the workgroup adds its sums once (wg_counters_end)
-        unsigned long long rr = my_rays, hh = my_hits, nn = my_nodes, tt = my_tris;
-        for (int off = 32; off > 0; off >>= 1) {
-            rr += __shfl_xor(rr, off);
-            hh += __shfl_xor(hh, off);
-            if (STATS) {
-                nn += __shfl_xor(nn, off);
-                tt += __shfl_xor(tt, off);
-            }
-        }
-        if (lane == 0 && (rr | (unsigned long long)wave_iters) != 0ull) {
-            atomicAdd(&wc[CGRT_CNT_RAYS], rr);
-            atomicAdd(&wc[CGRT_CNT_HITPOINTS], hh);
-            atomicAdd(&wc[CGRT_CNT_WAVE_ITERS], (unsigned long long)wave_iters);
-            if (STATS) {
-                atomicAdd(&wc[CGRT_CNT_NODE_TESTS], nn);
-                atomicAdd(&wc[CGRT_CNT_TRI_TESTS], tt);
-            }
-        }
-    }
+    ray_counters_flush<STATS, true>(wc, lane, my_rays, my_hits, my_nodes, my_tris, wave_iters);
 }
 
 template <bool TREES, bool BEZ, bool GLASS, bool SPH, bool STATS, bool SPILL, bool FIRST, int NT>
@@ -391,14 +347,14 @@ __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) voi
 // pruning (tree_count_wide) and turns the normal where the reference's count is even.  One thread per ray.
 __global__ __launch_bounds__(256) void ray_normal_sign_kernel(DeviceScene sc, RayParams rp) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rp.n) return;
+    if (i >= rp.in.n) return;
     const int id = rp.hit_obj[i];
     if (id < 0) return;
     const ObjRec &ob = sc.objs[id];
     if (ob.kind != KIND_MESH || !(ob.transp < kEps) || ob.aux == 2) return;  // (objtype 2 fixes the sign itself, objects.h:434-436)
     const TreeRec T = sc.trees[ob.tree];
     if (!T.tri_level || T.nwide == 0) return;
-    const V3 o = ld3(rp.org + 3 * i), d = ld3(rp.dir + 3 * i);
+    const V3 o = ld3(rp.in.org + 3 * i), d = ld3(rp.in.dir + 3 * i);
     const V3 inv = mk(1.0 / d.x, 1.0 / d.y, 1.0 / d.z);
     const Ray32 r32 = make_ray32(o, inv, T.bmax);
     const int c = tree_count_wide(sc.wnodes + T.wnode_begin, sc.otris + T.otri_begin, sc.tris + T.tri_begin, o, d, r32);

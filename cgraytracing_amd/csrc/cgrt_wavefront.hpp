@@ -26,12 +26,8 @@ struct WavefrontParked {
 };
 // Kernel arguments of wavefront_step_kernel
 struct WavefrontParams {
-    long long n;  // rays of this level
-    const double *org, *dir;
-    const unsigned long long *keys;  // nullptr: sample_key(pixel_key(seed, first_index + i), 0)
-    long long first_index;
-    uint64_t seed;
-    const double *adj;     // nullptr: (1,1,1)
+    RayInput in;           // this level's rays
+    const double *adj;    // nullptr: (1,1,1)
     const uint32_t *path;  // nullptr: 1
     const uint32_t *root;  // nullptr: the ray's index
     unsigned int *queue;   // head of the block queue (block = 64 consecutive rays), zeroed before the launch
@@ -71,30 +67,18 @@ __device__ __forceinline__ void wavefront_store_ray(const WavefrontQueue &q, uns
 template <bool TREES, bool BEZ, bool SPH, bool STATS, bool SPILL, int NT>
 __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) void wavefront_step_kernel(DeviceScene sc, WavefrontParams wp,
                                                                                                     unsigned long long *__restrict__ counters) {
-    static_assert(NT == 256 || NT == 64, "workgroup = 4 waves or 1 wave");
     __shared__ unsigned long long wg_cnt[CGRT_NCOUNTERS];
     unsigned long long *wc = wg_counters_begin(wg_cnt, counters);
 
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    const WgLds lay = wg_lds(wg_ask_trace(NT, TREES, BEZ, false, SPILL, false), sc);
-    const WgLdsPtrs lds = wg_lds_carve(lay, lds_raw);
+    const WgLdsPtrs lds = ray_wg_begin<NT, TREES, BEZ, false, SPILL>(sc, lds_raw);
     ObjRec *const lobjs = lds.lobjs;
     const LdsAux aux = lds.aux;
-    if (lay.has.nodes)
-        wg_stage16<NT>(const_cast<NodeRec *>(aux.lnodes), sc.nodes + sc.trees[sc.cached_tree].node_begin,
-                       sc.cached_nodes * (int)(sizeof(NodeRec) / 16));
-    wg_stage16<NT>(lobjs, sc.objs, sc.n_lds * (int)(sizeof(ObjRec) / 16));
-    __syncthreads();
 
     const int lane = threadIdx.x & 63;
     const unsigned long long lanes_below = (1ull << lane) - 1ull;
-    const unsigned n_blocks = (unsigned)((wp.n + 63) >> 6);
-
-    // the wave's block: rays [ray_next, ray_end) are still to be handed out (wave-uniform)
-    long long ray_next = 0, ray_end = 0;
-    bool queue_empty = false;
-    unsigned block_ahead = 0;
-    if (lane == 0) block_ahead = atomicAdd(wp.queue, 1u);
+    RayBlocks blocks;
+    blocks.begin(wp.queue, wp.in.n, lane);
 
     // the lane's ray
     uint32_t my_root = 0;
@@ -112,27 +96,15 @@ __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) voi
         const bool want = !have;
         const unsigned long long m = __ballot(want);
         if (m != 0ull) {
-            if (ray_next >= ray_end && !queue_empty) {
-                // the block fetched ahead, and the request for the one after it
-                const unsigned blk = (unsigned)__builtin_amdgcn_readfirstlane((int)block_ahead);
-                if (lane == 0) block_ahead = atomicAdd(wp.queue, 1u);
-                if (blk >= n_blocks) {
-                    queue_empty = true;
-                } else {
-                    ray_next = (long long)blk << 6;
-                    ray_end = ray_next + 64 < wp.n ? ray_next + 64 : wp.n;
-                }
-            }
-            const long long u = ray_next + (long long)__popcll(m & lanes_below);
-            ray_next += (long long)__popcll(m);  // lanes that drew beyond ray_end draw again from the next block
-            if (want && u < ray_end) {
-                r.o = ld3(wp.org + 3 * u);
-                r.d = ld3(wp.dir + 3 * u);
+            const long long u = blocks.draw(m, lane, lanes_below);
+            if (want && u < blocks.ray_end) {
+                r.o = ld3(wp.in.org + 3 * u);
+                r.d = ld3(wp.in.dir + 3 * u);
                 r.path = wp.path ? wp.path[u] : 1u;
-                const bool skip = (r.d.x == 0.0 && r.d.y == 0.0 && r.d.z == 0.0) || r.path == 0u || r.path >= 0x80000000u;
+                const bool skip = ray_is_none(r.d) || r.path == 0u || r.path >= 0x80000000u;
                 if (!skip) {  // (a ray that is none leaves nothing behind: the outputs are zeroed ahead of the sum)
                     my_root = wp.root ? wp.root[u] : (uint32_t)u;
-                    key = wp.keys ? (uint64_t)wp.keys[u] : sample_key(pixel_key(wp.seed, (uint64_t)(wp.first_index + u)), 0);
+                    key = ray_default_key(wp.in, u);
                     r.adj = wp.adj ? ld3(wp.adj + 3 * u) : mk(1, 1, 1);
                     r.depth_left = 2;  // the step never ends a ray for depth: the level count does
                     have = true;
@@ -140,7 +112,7 @@ __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) voi
             }
         }
         if (__ballot(have) == 0ull) {
-            if (queue_empty && ray_next >= ray_end) break;  // nothing left anywhere
+            if (blocks.drained()) break;
             continue;                                       // drew nothing traceable (block boundary, rays that are none)
         }
         wave_iters++;
@@ -198,27 +170,7 @@ __global__ __launch_bounds__(NT, BEZ ? kBezWaves : (TREES ? kTreeWaves : 4)) voi
         }
     }  // ray loop
 
-    if (wc) {
-        // wave reduction, then one LDS atomic per wave and counter; the workgroup adds its sums once (wg_counters_end)
-        unsigned long long rr = my_rays, hh = my_hits, nn = my_nodes, tt = my_tris;
-        for (int off = 32; off > 0; off >>= 1) {
-            rr += __shfl_xor(rr, off);
-            hh += __shfl_xor(hh, off);
-            if (STATS) {
-                nn += __shfl_xor(nn, off);
-                tt += __shfl_xor(tt, off);
-            }
-        }
-        if (lane == 0 && (rr | (unsigned long long)wave_iters) != 0ull) {
-            atomicAdd(&wc[CGRT_CNT_RAYS], rr);
-            atomicAdd(&wc[CGRT_CNT_HITPOINTS], hh);
-            atomicAdd(&wc[CGRT_CNT_WAVE_ITERS], (unsigned long long)wave_iters);
-            if (STATS) {
-                atomicAdd(&wc[CGRT_CNT_NODE_TESTS], nn);
-                atomicAdd(&wc[CGRT_CNT_TRI_TESTS], tt);
-            }
-        }
-    }
+    ray_counters_flush<STATS, true>(wc, lane, my_rays, my_hits, my_nodes, my_tris, wave_iters);
     wg_counters_end(wg_cnt, counters);
 }
 
